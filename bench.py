@@ -11,16 +11,26 @@ every step ends with an RCCL all-gather of the 6 doubles of v_c.
 The steps of a throughput run do not depend on each other: `value` is measured with `--in-flight` (default 4) of them
 enqueued at a time, each through its own handle on its own high-priority stream (vit-vs_amd/pipeline.py: one copy of the
 weights, graph replay per slot, the in-flight tile plan); W warm-up steps, then exactly K timed steps between barriers and
-device synchronisations, as for one stream.  The line's `sequential` object is the same W + K steps with ONE update in flight
-(one handle, one stream, plain launches) — what `value` was in rounds 1-2 — measured first, on every rank.
+device synchronisations, as for one stream.  With `--full`, the line's `sequential` object is the same W + K steps with ONE
+update in flight (one handle, one stream, plain launches) — what `value` was in rounds 1-2 — measured first, on every rank.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp16|f16x2|fp32] [--pairs B] [--config KEY] [--in-flight D]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, config,
+protocol, path, status, v_c).  Everything else the benchmark measures or checks — the `sequential` leg, latencies, the
+instrumented kernel pass and `roofline`, `parity`, `secondary`, `goal_cached`, `host_buffers`, `controller_loop`,
+`same_kernels_fp16` and `cpu_baseline` — runs only with `--full` (the `--no-*` options below select among those legs).
+`--dump-outputs DIR` writes what the timed path returned in its last step, taken right after the timed region: DIR/v_c.npy
+(float64 [B, 6]), DIR/status.npy (the status codes as float64 [B]) and, with the per-update all-gather at N > 1,
+DIR/v_c_gathered.npy (float64 [N * B, 6]); rank 0 writes them.  Weights, frames and visiting orders are seeded, so the same
+arguments give the same inputs in every run.
 
 `--gpus N` with N > 1 and no launcher in the environment (WORLD_SIZE unset) starts the N ranks itself — one process
 per GPU, before this process touches a GPU — and relays rank 0's line; it fails if fewer than N devices are visible.
 Under `torch.distributed.run` (WORLD_SIZE set) each process is one rank, as the driver launches it.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the kernel symbol with the largest share of the step, timed with
+Prints ONE JSON line (rank 0).  With `--full`: `roofline` is for the kernel symbol with the largest share of the step, timed with
 HIP event pairs on the launch stream in a second, instrumented pass over the same steps, one update at a time on one of the
 pipeline's handles (the kernels and the tile plan of `value`'s pass; `value` itself comes from the un-instrumented pass).  `parity` compares the benchmarked update with the CPU oracle under the same visiting order;
 `secondary` is the fp32 parity mode measured in the same process; `cpu_baseline` is the CPU oracle (PyTorch-CPU fp32
@@ -79,6 +89,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true", help="skip the fp32 parity-mode leg")
     ap.add_argument("--no-plain-chain", action="store_true",
                     help="skip the plain-launch chain of the dominant GEMM (profiler runs: keeps the kernel trace to the steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the one-stream `sequential` leg, latencies, the instrumented "
+                         "kernel pass and roofline, parity, the secondary precisions and seams, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's v_c and status (and the gathered v_c at N > 1) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -669,7 +684,9 @@ def run_rank(args):
     sd = weights.synthetic_state_dict(cfg, 0)
     B = args.pairs
     dense = args.selection == "dense"
-    eng = Engine(cfg, params, precision=args.precision, max_pairs=B, max_rows=cfg.tokens if dense else None).load_state_dict(sd)
+    # the one-stream handle: `value`'s own when one update is in flight, otherwise only the legs of --full use it
+    eng = (Engine(cfg, params, precision=args.precision, max_pairs=B, max_rows=cfg.tokens if dense else None).load_state_dict(sd)
+           if args.full or args.in_flight == 1 else None)
     # Updates of a throughput run do not depend on each other: `value` is measured with `in_flight` of them enqueued on as
     # many streams through as many handles (vit-vs_amd/pipeline.py); the one-stream figure of the earlier rounds is reported
     # beside it as `sequential`.
@@ -786,19 +803,20 @@ def run_rank(args):
     slots_calibration = None
     with torch.cuda.stream(stream):
         if pipe is not None:
-            # first the same updates one at a time on one stream — rounds 1-2's `value`, same W and K, with its per-update
+            # --full: first the same updates one at a time on one stream — rounds 1-2's `value`, same W and K, with its per-update
             # all-gather at N > 1 — then the pipelined leg that `value` reports (every rank runs both, in this order)
-            el_seq = timed_updates(eng, step, fence, args.warmup, args.steps, dev)
-            seq_rank_ms = None
-            if multi:
-                seq_rank_ms = rank_spread(el_seq)
-                el_seq = seq_rank_ms["max"] * args.steps * 1e-3
-            sequential = dict(metric="servo_updates_per_sec", value=round(world * B * args.steps / el_seq, 2), unit="updates/s",
-                              steps=args.steps, warmup=args.warmup, ms_per_step=round(el_seq / args.steps * 1e3, 4),
-                              note="one update in flight per GPU: one handle, one stream, plain launches, the one-stream tile "
-                                   "plan (what `value` was in rounds 1-2); measured before the pipelined leg")
-            if seq_rank_ms:
-                sequential["per_rank_ms_per_step"] = dict(seq_rank_ms, max=round(seq_rank_ms["max"], 4))
+            if args.full:
+                el_seq = timed_updates(eng, step, fence, args.warmup, args.steps, dev)
+                seq_rank_ms = None
+                if multi:
+                    seq_rank_ms = rank_spread(el_seq)
+                    el_seq = seq_rank_ms["max"] * args.steps * 1e-3
+                sequential = dict(metric="servo_updates_per_sec", value=round(world * B * args.steps / el_seq, 2), unit="updates/s",
+                                  steps=args.steps, warmup=args.warmup, ms_per_step=round(el_seq / args.steps * 1e3, 4),
+                                  note="one update in flight per GPU: one handle, one stream, plain launches, the one-stream tile "
+                                       "plan (what `value` was in rounds 1-2); measured before the pipelined leg")
+                if seq_rank_ms:
+                    sequential["per_rank_ms_per_step"] = dict(seq_rank_ms, max=round(seq_rank_ms["max"], 4))
             for i in range(2 * in_flight):          # set-up, not warm-up: every slot captures its graph (first call) and
                 pipe_step(i)                        # uploads the instantiated graph (first replay) before anything is timed
             pipe_fence()
@@ -843,362 +861,372 @@ def run_rank(args):
             seen = torch.ones(1, dtype=torch.int32, device=dev)
             dist.all_reduce(seen, op=dist.ReduceOp.SUM)
             ranks_seen = int(seen.item())
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path holds after its last step (before any leg of --full reuses the buffers)
+            dumped = dict(v_c=v_host.astype(np.float64), status=status_host.astype(np.float64))
+            if do_gather and not async_gather:
+                dumped["v_c_gathered"] = v_all.cpu().numpy().astype(np.float64)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
 
-        # what one update takes on its queue while the others share the chip (device time between two events on the slot's stream)
-        lat_in_flight = None
-        if pipe is not None and not multi:
-            evs = []
-            for i in range(10 * in_flight):
-                st_k = pipe.streams[pipe.submitted % in_flight]
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st_k)
-                pipe_step(i)
-                e1.record(st_k)
-                evs.append((e0, e1))
-            pipe_fence()
-            lat_in_flight = float(np.median([a.elapsed_time(b) for a, b in evs[2 * in_flight:]]))
+        if args.full:
+            # what one update takes on its queue while the others share the chip (device time between two events on the slot's stream)
+            lat_in_flight = None
+            if pipe is not None and not multi:
+                evs = []
+                for i in range(10 * in_flight):
+                    st_k = pipe.streams[pipe.submitted % in_flight]
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(st_k)
+                    pipe_step(i)
+                    e1.record(st_k)
+                    evs.append((e0, e1))
+                pipe_fence()
+                lat_in_flight = float(np.median([a.elapsed_time(b) for a, b in evs[2 * in_flight:]]))
 
-        # single-update latency with a host synchronisation per update (a control loop's view)
-        lat = []
-        for i in range(10):
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            step(args.warmup + i % max(args.steps, 1))
-            torch.cuda.synchronize(dev)
-            lat.append(time.perf_counter() - t1)
-
-        # instrumented pass: HIP event pairs around every launch, on the launch stream, one update at a time (kernels of
-        # several queues share the chip: a kernel's own duration is only defined while it runs alone).  With several updates
-        # in flight it runs on one of the pipeline's handles, i.e. the kernels and the tile plan `value` was measured with.
-        eng_prof = pipe.engines[0] if pipe is not None else eng
-        prof_step = make_step(eng_prof)
-        eng.lib.vitvs_op_plan_in_flight(in_flight)      # the operator hooks below (tile symbol, plain chain) plan alike
-        eng_prof.timing_enable(True)
-        n_prof = min(args.steps, 50)
-        for i in range(n_prof):
-            prof_step(args.warmup + i)
-        if gather is not None:
-            gather.finish()
-        prof = eng_prof.timing_collect()
-        eng_prof.timing_enable(False)
-        plain = None
-        if rank == 0 and world == 1 and not args.no_plain_chain:   # single-process extra; ranks stay in lock step at N > 1
-            m_rows, bk_ = 2 * B * cfg.seq, 128 // ELEM_BYTES[args.precision]
-            plain = {name: plain_chain_us(args.precision, m_rows, cfg.dim, kk, split_k(m_rows, cfg.dim, kk, bk_, in_flight, args.precision != "fp32"), dev)
-                     for name, kk in (("proj", cfg.dim), ("fc2", cfg.hidden))}
-
-        overlapped = None
-        if rank == 0 and world == 1 and not args.no_plain_chain and in_flight > 1:
-            m_rows, bk_ = 2 * B * cfg.seq, 128 // ELEM_BYTES[args.precision]
-            try:                                     # an auxiliary figure: it must never cost the line
-                overlapped = overlapped_chain_us(args.precision, m_rows, cfg.dim, cfg.hidden, split_k(m_rows, cfg.dim, cfg.dim, bk_, in_flight, args.precision != "fp32"),
-                                                 split_k(m_rows, cfg.dim, cfg.hidden, bk_, in_flight, args.precision != "fp32"), dev, queues=in_flight)
-            except Exception as exc:                 # noqa: BLE001
-                print(f"bench.py: roofline.overlapped not measured ({type(exc).__name__}: {exc})", file=sys.stderr)
+            # single-update latency with a host synchronisation per update (a control loop's view)
+            lat = []
+            for i in range(10):
                 torch.cuda.synchronize(dev)
-        eng.lib.vitvs_op_plan_in_flight(1)              # the thread's hint back to its default: handles created below plan for themselves
+                t1 = time.perf_counter()
+                step(args.warmup + i % max(args.steps, 1))
+                torch.cuda.synchronize(dev)
+                lat.append(time.perf_counter() - t1)
 
-        parity = None
-        secondary = None
-        if world == 1 and rank == 0 and not args.no_cpu_baseline and not dense:
-            # (the handle and tile plan `value` was measured with: a pipeline slot when several updates are in flight)
-            parity = parity_block(eng_prof, cfg, sd, params, des_np[0], cur_np[0], depth_np, I_cur, I_des, Z, K, orders[0, 0], _lib)
-        if world == 1 and rank == 0 and not args.no_secondary and args.precision in ("bf16", "fp16") and not dense:
-            # The parity mode at servo rate: split-f16 (VITVS_F16X2: every operand an fp16 hi / lo pair, three f16 MFMAs per
-            # k-step) — the precision every fp32-mode parity test also runs under, unchanged bars (tests/test_gpu_path.py EXACT) —
-            # same process, same inputs and orders, one update in flight and `in_flight` in flight like `value`; the fp32
-            # matrix pipe's own rate (the mode of the earlier rounds' `secondary`) beside it.
-            eng_x2 = Engine(cfg, params, precision="f16x2", max_pairs=B).load_state_dict(sd)
-            s_steps, s_warm = max(10, args.steps // 2), max(3, args.warmup // 2)
-            el_x2 = timed_updates(eng_x2, make_step(eng_x2), fence, s_warm, s_steps, dev)
-            secondary = dict(dtype="f16x2", metric="servo_updates_per_sec", value_one_in_flight=round(B * s_steps / el_x2, 2),
-                             unit="updates/s", steps=s_steps, warmup=s_warm, ms_per_step_one_in_flight=round(el_x2 / s_steps * 1e3, 4),
-                             note="split-f16 parity mode: fp32-class results (bit-exact arg-max tables on the strict fixtures, tokens "
-                                  "<= 2e-5, v_c <= 1e-9: the fp32 tests of tests/test_gpu_path.py run under it unchanged) on the f16 "
-                                  "matrix cores; operand bytes as fp32, three MFMAs per k-step")
-            if not args.no_cpu_baseline:
-                secondary["parity"] = parity_block(eng_x2, cfg, sd, params, des_np[0], cur_np[0], depth_np, I_cur, I_des, Z, K,
-                                                   orders[0, 0], _lib)
-            eng_x2.close()
-            if pipe is not None:
-                # (on the main pipeline's streams, idle now: three more high-priority streams would share the class's four hardware
-                # queues with them, and two slots that land on one queue take turns — measured 1614 instead of 2367 updates/s)
-                pipe_x2 = UpdatePipeline(cfg, params, sd, precision="f16x2", depth=in_flight, max_pairs=B, device=dev, streams=pipe.streams)
+            # instrumented pass: HIP event pairs around every launch, on the launch stream, one update at a time (kernels of
+            # several queues share the chip: a kernel's own duration is only defined while it runs alone).  With several updates
+            # in flight it runs on one of the pipeline's handles, i.e. the kernels and the tile plan `value` was measured with.
+            eng_prof = pipe.engines[0] if pipe is not None else eng
+            prof_step = make_step(eng_prof)
+            eng.lib.vitvs_op_plan_in_flight(in_flight)      # the operator hooks below (tile symbol, plain chain) plan alike
+            eng_prof.timing_enable(True)
+            n_prof = min(args.steps, 50)
+            for i in range(n_prof):
+                prof_step(args.warmup + i)
+            if gather is not None:
+                gather.finish()
+            prof = eng_prof.timing_collect()
+            eng_prof.timing_enable(False)
+            plain = None
+            if rank == 0 and world == 1 and not args.no_plain_chain:   # single-process extra; ranks stay in lock step at N > 1
+                m_rows, bk_ = 2 * B * cfg.seq, 128 // ELEM_BYTES[args.precision]
+                plain = {name: plain_chain_us(args.precision, m_rows, cfg.dim, kk, split_k(m_rows, cfg.dim, kk, bk_, in_flight, args.precision != "fp32"), dev)
+                         for name, kk in (("proj", cfg.dim), ("fc2", cfg.hidden))}
 
-                def x2_step(i):
-                    pipe_x2.submit(I_cur, I_des, Z, K, _lib.SELECT_ORDER, orders[i % total], None, False, inputs_ready=True)
+            overlapped = None
+            if rank == 0 and world == 1 and not args.no_plain_chain and in_flight > 1:
+                m_rows, bk_ = 2 * B * cfg.seq, 128 // ELEM_BYTES[args.precision]
+                try:                                     # an auxiliary figure: it must never cost the line
+                    overlapped = overlapped_chain_us(args.precision, m_rows, cfg.dim, cfg.hidden, split_k(m_rows, cfg.dim, cfg.dim, bk_, in_flight, args.precision != "fp32"),
+                                                     split_k(m_rows, cfg.dim, cfg.hidden, bk_, in_flight, args.precision != "fp32"), dev, queues=in_flight)
+                except Exception as exc:                 # noqa: BLE001
+                    print(f"bench.py: roofline.overlapped not measured ({type(exc).__name__}: {exc})", file=sys.stderr)
+                    torch.cuda.synchronize(dev)
+            eng.lib.vitvs_op_plan_in_flight(1)              # the thread's hint back to its default: handles created below plan for themselves
 
-                def x2_fence():
-                    pipe_x2.synchronize()
+            parity = None
+            secondary = None
+            if world == 1 and rank == 0 and not args.no_cpu_baseline and not dense:
+                # (the handle and tile plan `value` was measured with: a pipeline slot when several updates are in flight)
+                parity = parity_block(eng_prof, cfg, sd, params, des_np[0], cur_np[0], depth_np, I_cur, I_des, Z, K, orders[0, 0], _lib)
+            if world == 1 and rank == 0 and not args.no_secondary and args.precision in ("bf16", "fp16") and not dense:
+                # The parity mode at servo rate: split-f16 (VITVS_F16X2: every operand an fp16 hi / lo pair, three f16 MFMAs per
+                # k-step) — the precision every fp32-mode parity test also runs under, unchanged bars (tests/test_gpu_path.py EXACT) —
+                # same process, same inputs and orders, one update in flight and `in_flight` in flight like `value`; the fp32
+                # matrix pipe's own rate (the mode of the earlier rounds' `secondary`) beside it.
+                eng_x2 = Engine(cfg, params, precision="f16x2", max_pairs=B).load_state_dict(sd)
+                s_steps, s_warm = max(10, args.steps // 2), max(3, args.warmup // 2)
+                el_x2 = timed_updates(eng_x2, make_step(eng_x2), fence, s_warm, s_steps, dev)
+                secondary = dict(dtype="f16x2", metric="servo_updates_per_sec", value_one_in_flight=round(B * s_steps / el_x2, 2),
+                                 unit="updates/s", steps=s_steps, warmup=s_warm, ms_per_step_one_in_flight=round(el_x2 / s_steps * 1e3, 4),
+                                 note="split-f16 parity mode: fp32-class results (bit-exact arg-max tables on the strict fixtures, tokens "
+                                      "<= 2e-5, v_c <= 1e-9: the fp32 tests of tests/test_gpu_path.py run under it unchanged) on the f16 "
+                                      "matrix cores; operand bytes as fp32, three MFMAs per k-step")
+                if not args.no_cpu_baseline:
+                    secondary["parity"] = parity_block(eng_x2, cfg, sd, params, des_np[0], cur_np[0], depth_np, I_cur, I_des, Z, K,
+                                                       orders[0, 0], _lib)
+                eng_x2.close()
+                if pipe is not None:
+                    # (on the main pipeline's streams, idle now: three more high-priority streams would share the class's four hardware
+                    # queues with them, and two slots that land on one queue take turns — measured 1614 instead of 2367 updates/s)
+                    pipe_x2 = UpdatePipeline(cfg, params, sd, precision="f16x2", depth=in_flight, max_pairs=B, device=dev, streams=pipe.streams)
+
+                    def x2_step(i):
+                        pipe_x2.submit(I_cur, I_des, Z, K, _lib.SELECT_ORDER, orders[i % total], None, False, inputs_ready=True)
+
+                    def x2_fence():
+                        pipe_x2.synchronize()
+                        torch.cuda.synchronize(dev)
+                    for i in range(2 * in_flight):
+                        x2_step(i)
+                    x2_fence()
+                    el_p = timed_updates(None, x2_step, x2_fence, s_warm, s_steps, dev)
+                    secondary.update(value=round(B * s_steps / el_p, 2), ms_per_step=round(el_p / s_steps * 1e3, 4),
+                                     updates_in_flight=in_flight)
+                    pipe_x2.close()
+                else:
+                    secondary.update(value=secondary["value_one_in_flight"], ms_per_step=secondary["ms_per_step_one_in_flight"],
+                                     updates_in_flight=1)
+                eng32 = Engine(cfg, params, precision="fp32", max_pairs=B).load_state_dict(sd)
+                f_steps32, f_warm32 = max(10, args.steps // 8), 3
+                el32 = timed_updates(eng32, make_step(eng32), fence, f_warm32, f_steps32, dev)
+                secondary["fp32_matrix_pipe"] = dict(value_one_in_flight=round(B * f_steps32 / el32, 2), steps=f_steps32,
+                                                     ms_per_step=round(el32 / f_steps32 * 1e3, 4),
+                                                     note="the same updates on v_mfma_f32_16x16x4_f32 (157 TFLOP/s dense peak -> a ceiling "
+                                                          "of ~2.2 k updates/s): what the split-f16 mode replaces as the parity mode")
+                eng32.close()
+
+            # NOT the headline: the same updates with the goal frame's tokens computed once (vitvs_set_goal_dev) — what a servo
+            # loop with a fixed goal image can use; the reference (and `value`) recompute them on every update
+            goal_cached = None
+            if world == 1 and rank == 0 and not args.no_secondary and not dense:
+                eng.set_goal(I_des)
+                c_steps, c_warm = max(10, args.steps // 2), max(3, args.warmup // 2)
+                elc = timed_updates(eng, make_step(eng, "cached"), fence, c_warm, c_steps, dev)
+                goal_cached = dict(metric="servo_updates_per_sec", value=round(B * c_steps / elc, 2), unit="updates/s", steps=c_steps,
+                                   warmup=c_warm, ms_per_step=round(elc / c_steps * 1e3, 4), dtype=args.precision,
+                                   note="one update in flight, goal tokens cached (vitvs_set_goal_dev): only the current frame is forwarded; the "
+                                        "reference recomputes I_des every update, and so does `value`")
+
+            # The boundary's host-buffer form (vitvs_compute_velocity: frames, depth, intrinsics and the visiting order in HOST memory,
+            # v_c back in host memory, one synchronous call per update): the PCIe-inclusive rate of one control loop.  Never `value`.
+            host_buffers = None
+            if world == 1 and rank == 0 and not args.no_secondary and not dense:
+                import ctypes as C
+                hp = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
+                k_host = np.ascontiguousarray(np.array([params.intrinsics()] * B, np.float64))
+                z_host = np.ascontiguousarray(np.stack([depth_np] * B))
+                orders_host = orders[:8].cpu().numpy().copy()
+                v_out, st_out = np.zeros((B, 6), np.float64), np.zeros(B, np.int32)
+                eng.set_option("in_flight", 1)
+
+                # (argument pointers built once: a C caller passes addresses, and eight numpy -> ctypes conversions per call are ~10 us of
+                #  interpreter time inside a 0.5 ms call)
+                p_cur, p_des, p_z, p_k, p_v, p_st = hp(cur_np), hp(des_np), hp(z_host), hp(k_host), hp(v_out), hp(st_out)
+                p_orders = [hp(orders_host[j]) for j in range(8)]
+                call_host = eng.lib.vitvs_compute_velocity
+
+                def host_step(i):
+                    rc = call_host(eng.handle, B, p_cur, p_des, 0, p_z, p_k, _lib.SELECT_ORDER, p_orders[i % 8], None, 0, p_v, p_st)
+                    if rc != 0:
+                        raise RuntimeError(f"vitvs_compute_velocity failed ({rc})")
+                h_steps = max(10, args.steps // 2)
+                for i in range(3):
+                    host_step(i)
+                t_h = time.perf_counter()
+                for i in range(h_steps):
+                    host_step(3 + i)
+                el_h = time.perf_counter() - t_h
+                host_buffers = dict(metric="servo_updates_per_sec", value=round(B * h_steps / el_h, 2), unit="updates/s", steps=h_steps,
+                                    ms_per_step=round(el_h / h_steps * 1e3, 4), dtype=args.precision,
+                                    bytes_over_pcie_per_update=int(B * (2 * cfg.img_size ** 2 * 3 + depth_np.nbytes + 32 + cfg.tokens * 4 + 52)),
+                                    note="host-pointer entry point (vitvs_compute_velocity), pageable numpy buffers in, v_c out, one synchronous "
+                                         "call per update on one handle: memcpy into the handle's pinned block, one copy launch for the frames, "
+                                         "the depth image copied behind the forward's launches and read in place by the law (the PCIe-inclusive "
+                                         "form of `sequential`); `value` is device-resident by contract")
+
+            # The drop-in's own rate: the reference's Controller.ibvs() (vitvs_v2.py:588-632) through vit-vs_amd/servo.py — camera
+            # frames (u_max x v_max uint8, the fused Pillow resize) and the uint16 depth image as HOST numpy arrays, handed over by the
+            # callbacks before every step like the reference's ROS callbacks do; one handle, one update at a time, EMA and feature
+            # arrays included.  selection "order": the device-side draw (one C call per update); "reference": the reference's own
+            # sort + randperm draw on the host between the correspondence and the law (two device round trips).
+            controller_loop = None
+            if world == 1 and rank == 0 and not args.no_secondary and not dense and B == 1:
+                from PIL import Image
+                from vitvs_amd import servo as vservo
+                cam = lambda a: np.asarray(Image.fromarray(a).resize((params.u_max, params.v_max)), dtype=np.uint8)   # noqa: E731
+                goal_cam, cur_cam = cam(des_np[0]), cam(cur_np[0])
+                eng_c = Engine(cfg, params, precision=args.precision, max_pairs=1).load_state_dict(sd)
+                controller_loop = dict(frames=f"{params.u_max}x{params.v_max} uint8 host arrays + uint16 depth, fused Pillow-exact resize",
+                                       dtype=args.precision, note="Controller.ibvs() per update incl. the callbacks' hand-over, the draw, "
+                                       "EMA and the feature arrays the reference's detect_features returns; one update in flight")
+                eng_cx = Engine(cfg, params, precision="f16x2", max_pairs=1).load_state_dict(sd) if args.precision != "f16x2" else None
+                for sel_name, eng_l in (("order", eng_c), ("reference", eng_c), ("order_f16x2", eng_cx), ("reference_f16x2", eng_cx)):
+                    if eng_l is None:
+                        continue
+                    ctl = vservo.Controller(eng_l, goal_image=goal_cam, selection=sel_name.split("_")[0])
+                    ctl.generator = torch.Generator().manual_seed(121)
+                    n_loop, lat_c = 230, []
+                    for i in range(n_loop):
+                        ctl.image_callback_rgb(cur_cam)
+                        ctl.image_callback_depth(depth_np)
+                        t_c = time.perf_counter()
+                        ctl.ibvs()
+                        lat_c.append(time.perf_counter() - t_c)
+                    lat_c = np.array(lat_c[30:]) * 1e3
+                    controller_loop[sel_name] = dict(updates=len(lat_c), updates_per_s=round(1e3 / float(lat_c.mean()), 1),
+                                                     median_ms=round(float(np.median(lat_c)), 4), p90_ms=round(float(np.percentile(lat_c, 90)), 4),
+                                                     v_c_is_set=ctl.v_c is not None, status=ctl.last_status)
+                eng_c.close()
+                if eng_cx is not None:
+                    eng_cx.close()
+
+            # fp16: the same kernels on v_mfma_f32_16x16x32_f16 — the throughput dtype for trained checkpoints (DESIGN.md section 3:
+            # 96-99.5 % arg-max agreement on trained-like weights where bf16 keeps 77-91 %); same protocol as `value`, fewer steps
+            same_kernels_fp16 = None
+            if world == 1 and rank == 0 and not args.no_secondary and not dense and args.precision == "bf16" and pipe is not None:
+                pipe16 = UpdatePipeline(cfg, params, sd, precision="fp16", depth=in_flight, max_pairs=B, device=dev, streams=pipe.streams)
+
+                def step16(i):
+                    pipe16.submit(I_cur, I_des, Z, K, _lib.SELECT_ORDER, orders[i % total], None, False, inputs_ready=True)
+
+                def fence16():
+                    pipe16.synchronize()
                     torch.cuda.synchronize(dev)
                 for i in range(2 * in_flight):
-                    x2_step(i)
-                x2_fence()
-                el_p = timed_updates(None, x2_step, x2_fence, s_warm, s_steps, dev)
-                secondary.update(value=round(B * s_steps / el_p, 2), ms_per_step=round(el_p / s_steps * 1e3, 4),
-                                 updates_in_flight=in_flight)
-                pipe_x2.close()
-            else:
-                secondary.update(value=secondary["value_one_in_flight"], ms_per_step=secondary["ms_per_step_one_in_flight"],
-                                 updates_in_flight=1)
-            eng32 = Engine(cfg, params, precision="fp32", max_pairs=B).load_state_dict(sd)
-            f_steps32, f_warm32 = max(10, args.steps // 8), 3
-            el32 = timed_updates(eng32, make_step(eng32), fence, f_warm32, f_steps32, dev)
-            secondary["fp32_matrix_pipe"] = dict(value_one_in_flight=round(B * f_steps32 / el32, 2), steps=f_steps32,
-                                                 ms_per_step=round(el32 / f_steps32 * 1e3, 4),
-                                                 note="the same updates on v_mfma_f32_16x16x4_f32 (157 TFLOP/s dense peak -> a ceiling "
-                                                      "of ~2.2 k updates/s): what the split-f16 mode replaces as the parity mode")
-            eng32.close()
-
-        # NOT the headline: the same updates with the goal frame's tokens computed once (vitvs_set_goal_dev) — what a servo
-        # loop with a fixed goal image can use; the reference (and `value`) recompute them on every update
-        goal_cached = None
-        if world == 1 and rank == 0 and not args.no_secondary and not dense:
-            eng.set_goal(I_des)
-            c_steps, c_warm = max(10, args.steps // 2), max(3, args.warmup // 2)
-            elc = timed_updates(eng, make_step(eng, "cached"), fence, c_warm, c_steps, dev)
-            goal_cached = dict(metric="servo_updates_per_sec", value=round(B * c_steps / elc, 2), unit="updates/s", steps=c_steps,
-                               warmup=c_warm, ms_per_step=round(elc / c_steps * 1e3, 4), dtype=args.precision,
-                               note="one update in flight, goal tokens cached (vitvs_set_goal_dev): only the current frame is forwarded; the "
-                                    "reference recomputes I_des every update, and so does `value`")
-
-        # The boundary's host-buffer form (vitvs_compute_velocity: frames, depth, intrinsics and the visiting order in HOST memory,
-        # v_c back in host memory, one synchronous call per update): the PCIe-inclusive rate of one control loop.  Never `value`.
-        host_buffers = None
-        if world == 1 and rank == 0 and not args.no_secondary and not dense:
-            import ctypes as C
-            hp = lambda a: a.ctypes.data_as(C.c_void_p)                       # noqa: E731
-            k_host = np.ascontiguousarray(np.array([params.intrinsics()] * B, np.float64))
-            z_host = np.ascontiguousarray(np.stack([depth_np] * B))
-            orders_host = orders[:8].cpu().numpy().copy()
-            v_out, st_out = np.zeros((B, 6), np.float64), np.zeros(B, np.int32)
-            eng.set_option("in_flight", 1)
-
-            # (argument pointers built once: a C caller passes addresses, and eight numpy -> ctypes conversions per call are ~10 us of
-            #  interpreter time inside a 0.5 ms call)
-            p_cur, p_des, p_z, p_k, p_v, p_st = hp(cur_np), hp(des_np), hp(z_host), hp(k_host), hp(v_out), hp(st_out)
-            p_orders = [hp(orders_host[j]) for j in range(8)]
-            call_host = eng.lib.vitvs_compute_velocity
-
-            def host_step(i):
-                rc = call_host(eng.handle, B, p_cur, p_des, 0, p_z, p_k, _lib.SELECT_ORDER, p_orders[i % 8], None, 0, p_v, p_st)
-                if rc != 0:
-                    raise RuntimeError(f"vitvs_compute_velocity failed ({rc})")
-            h_steps = max(10, args.steps // 2)
-            for i in range(3):
-                host_step(i)
-            t_h = time.perf_counter()
-            for i in range(h_steps):
-                host_step(3 + i)
-            el_h = time.perf_counter() - t_h
-            host_buffers = dict(metric="servo_updates_per_sec", value=round(B * h_steps / el_h, 2), unit="updates/s", steps=h_steps,
-                                ms_per_step=round(el_h / h_steps * 1e3, 4), dtype=args.precision,
-                                bytes_over_pcie_per_update=int(B * (2 * cfg.img_size ** 2 * 3 + depth_np.nbytes + 32 + cfg.tokens * 4 + 52)),
-                                note="host-pointer entry point (vitvs_compute_velocity), pageable numpy buffers in, v_c out, one synchronous "
-                                     "call per update on one handle: memcpy into the handle's pinned block, one copy launch for the frames, "
-                                     "the depth image copied behind the forward's launches and read in place by the law (the PCIe-inclusive "
-                                     "form of `sequential`); `value` is device-resident by contract")
-
-        # The drop-in's own rate: the reference's Controller.ibvs() (vitvs_v2.py:588-632) through vit-vs_amd/servo.py — camera
-        # frames (u_max x v_max uint8, the fused Pillow resize) and the uint16 depth image as HOST numpy arrays, handed over by the
-        # callbacks before every step like the reference's ROS callbacks do; one handle, one update at a time, EMA and feature
-        # arrays included.  selection "order": the device-side draw (one C call per update); "reference": the reference's own
-        # sort + randperm draw on the host between the correspondence and the law (two device round trips).
-        controller_loop = None
-        if world == 1 and rank == 0 and not args.no_secondary and not dense and B == 1:
-            from PIL import Image
-            from vitvs_amd import servo as vservo
-            cam = lambda a: np.asarray(Image.fromarray(a).resize((params.u_max, params.v_max)), dtype=np.uint8)   # noqa: E731
-            goal_cam, cur_cam = cam(des_np[0]), cam(cur_np[0])
-            eng_c = Engine(cfg, params, precision=args.precision, max_pairs=1).load_state_dict(sd)
-            controller_loop = dict(frames=f"{params.u_max}x{params.v_max} uint8 host arrays + uint16 depth, fused Pillow-exact resize",
-                                   dtype=args.precision, note="Controller.ibvs() per update incl. the callbacks' hand-over, the draw, "
-                                   "EMA and the feature arrays the reference's detect_features returns; one update in flight")
-            eng_cx = Engine(cfg, params, precision="f16x2", max_pairs=1).load_state_dict(sd) if args.precision != "f16x2" else None
-            for sel_name, eng_l in (("order", eng_c), ("reference", eng_c), ("order_f16x2", eng_cx), ("reference_f16x2", eng_cx)):
-                if eng_l is None:
-                    continue
-                ctl = vservo.Controller(eng_l, goal_image=goal_cam, selection=sel_name.split("_")[0])
-                ctl.generator = torch.Generator().manual_seed(121)
-                n_loop, lat_c = 230, []
-                for i in range(n_loop):
-                    ctl.image_callback_rgb(cur_cam)
-                    ctl.image_callback_depth(depth_np)
-                    t_c = time.perf_counter()
-                    ctl.ibvs()
-                    lat_c.append(time.perf_counter() - t_c)
-                lat_c = np.array(lat_c[30:]) * 1e3
-                controller_loop[sel_name] = dict(updates=len(lat_c), updates_per_s=round(1e3 / float(lat_c.mean()), 1),
-                                                 median_ms=round(float(np.median(lat_c)), 4), p90_ms=round(float(np.percentile(lat_c, 90)), 4),
-                                                 v_c_is_set=ctl.v_c is not None, status=ctl.last_status)
-            eng_c.close()
-            if eng_cx is not None:
-                eng_cx.close()
-
-        # fp16: the same kernels on v_mfma_f32_16x16x32_f16 — the throughput dtype for trained checkpoints (DESIGN.md section 3:
-        # 96-99.5 % arg-max agreement on trained-like weights where bf16 keeps 77-91 %); same protocol as `value`, fewer steps
-        same_kernels_fp16 = None
-        if world == 1 and rank == 0 and not args.no_secondary and not dense and args.precision == "bf16" and pipe is not None:
-            pipe16 = UpdatePipeline(cfg, params, sd, precision="fp16", depth=in_flight, max_pairs=B, device=dev, streams=pipe.streams)
-
-            def step16(i):
-                pipe16.submit(I_cur, I_des, Z, K, _lib.SELECT_ORDER, orders[i % total], None, False, inputs_ready=True)
-
-            def fence16():
-                pipe16.synchronize()
-                torch.cuda.synchronize(dev)
-            for i in range(2 * in_flight):
-                step16(i)
-            fence16()
-            f_steps, f_warm = max(20, args.steps // 2), max(5, args.warmup // 2)
-            el16 = timed_updates(None, step16, fence16, f_warm, f_steps, dev)
-            same_kernels_fp16 = dict(metric="servo_updates_per_sec", value=round(B * f_steps / el16, 2), unit="updates/s", dtype="fp16",
-                                     steps=f_steps, warmup=f_warm, ms_per_step=round(el16 / f_steps * 1e3, 4),
-                                     note=f"{in_flight} updates in flight, fp16 operands: the recommended throughput dtype for trained "
-                                          "checkpoints (tests/test_gpu_path.py::test_trained_like_statistics_end_to_end)")
-            pipe16.close()
+                    step16(i)
+                fence16()
+                f_steps, f_warm = max(20, args.steps // 2), max(5, args.warmup // 2)
+                el16 = timed_updates(None, step16, fence16, f_warm, f_steps, dev)
+                same_kernels_fp16 = dict(metric="servo_updates_per_sec", value=round(B * f_steps / el16, 2), unit="updates/s", dtype="fp16",
+                                         steps=f_steps, warmup=f_warm, ms_per_step=round(el16 / f_steps * 1e3, 4),
+                                         note=f"{in_flight} updates in flight, fp16 operands: the recommended throughput dtype for trained "
+                                              "checkpoints (tests/test_gpu_path.py::test_trained_like_statistics_end_to_end)")
+                pipe16.close()
 
     updates = world * B * args.steps
     value = updates / elapsed
     es = ELEM_BYTES[args.precision]
-    big_rule = args.precision != "fp32"
-    work = kernel_work(cfg, 2 * B, B, es, binned, in_flight, big_rule)
-    kernels = {}
-    for name, (ms, cnt) in prof.items():
-        if cnt == 0:
-            continue
-        avg = max(ms / cnt * 1e-3, 1e-7)
-        fl, by = work[name]
-        kernels[name] = dict(launches_per_step=cnt / n_prof, avg_us=round(avg * 1e6, 3),
-                             step_share_us=round(avg * cnt / n_prof * 1e6, 2),
-                             tflops=round(fl / avg / 1e12, 3), gbps=round(by / avg / 1e9, 1))
-    # roofline object: the kernel SYMBOL with the largest share of the step (proj and fc2 are the same
-    # split-K kernel, as rocprofv3 --stats reports them), priced with its algorithmic work per launch
-    prec_tag = {"bf16": "bf16", "fp16": "f16", "fp32": "f32", "f16x2": "hx2"}[args.precision]
-    groups = {"linear_partial(proj+fc2)": ["proj", "fc2"]}
-    for k in kernels:
-        if k not in ("proj", "fc2"):
-            groups[k] = [k]
+    if args.full:
+        big_rule = args.precision != "fp32"
+        work = kernel_work(cfg, 2 * B, B, es, binned, in_flight, big_rule)
+        kernels = {}
+        for name, (ms, cnt) in prof.items():
+            if cnt == 0:
+                continue
+            avg = max(ms / cnt * 1e-3, 1e-7)
+            fl, by = work[name]
+            kernels[name] = dict(launches_per_step=cnt / n_prof, avg_us=round(avg * 1e6, 3),
+                                 step_share_us=round(avg * cnt / n_prof * 1e6, 2),
+                                 tflops=round(fl / avg / 1e12, 3), gbps=round(by / avg / 1e9, 1))
+        # roofline object: the kernel SYMBOL with the largest share of the step (proj and fc2 are the same
+        # split-K kernel, as rocprofv3 --stats reports them), priced with its algorithmic work per launch
+        prec_tag = {"bf16": "bf16", "fp16": "f16", "fp32": "f32", "f16x2": "hx2"}[args.precision]
+        groups = {"linear_partial(proj+fc2)": ["proj", "fc2"]}
+        for k in kernels:
+            if k not in ("proj", "fc2"):
+                groups[k] = [k]
 
-    def g_share(g):
-        return sum(kernels[c]["step_share_us"] for c in groups[g] if c in kernels)
-    dom = max(groups, key=g_share)
-    members = [c for c in groups[dom] if c in kernels]
-    launches = sum(kernels[c]["launches_per_step"] for c in members)
-    avg_s = g_share(dom) / launches * 1e-6
-    fl = sum(work[c][0] * kernels[c]["launches_per_step"] for c in members) / launches
-    by = sum(work[c][1] * kernels[c]["launches_per_step"] for c in members) / launches
+        def g_share(g):
+            return sum(kernels[c]["step_share_us"] for c in groups[g] if c in kernels)
+        dom = max(groups, key=g_share)
+        members = [c for c in groups[dom] if c in kernels]
+        launches = sum(kernels[c]["launches_per_step"] for c in members)
+        avg_s = g_share(dom) / launches * 1e-6
+        fl = sum(work[c][0] * kernels[c]["launches_per_step"] for c in members) / launches
+        by = sum(work[c][1] * kernels[c]["launches_per_step"] for c in members) / launches
 
-    def linear_symbol(m, n, kk, s_, partial):   # the kernel symbol of the tile the LIBRARY reports for this layer (no mirror)
-        import ctypes
-        tile = (ctypes.c_int32 * 3)()
-        prec_id = {"f32": _lib.F32, "bf16": _lib.BF16, "f16": _lib.F16, "hx2": _lib.F16X2}[prec_tag]
-        prev_hint = eng.lib.vitvs_op_plan_in_flight(in_flight)       # the plan `value` ran under; restored at once
-        rc_ = eng.lib.vitvs_op_linear_tile(prec_id, m, n, kk, s_ if partial else 0, tile)
-        eng.lib.vitvs_op_plan_in_flight(prev_hint)
-        if rc_ != 0:
-            return None
-        if tile[2] == 0:
-            return f"linear_big_kernel<{prec_tag},{tile[0]}x{tile[1]}>:" + ("BigPartial" if partial else "BigStore")
-        return f"linear_kernel<{prec_tag},{tile[0]},{tile[1]},{tile[2]}>:" + ("EpiPartial" if partial else "EpiStore")
-    def attention_symbol(tag, cfg_, b_):     # mirror of launch_attention's dispatch (attention.hip)
-        short = cfg_.seq <= 256 and -(-cfg_.seq // 16) * cfg_.heads * 2 * b_ <= 640
-        if tag == "f32":
-            return "attention_f32_kernel"
-        if tag == "hx2":
-            return "attention_x2_short_kernel" if short else ("attention_x2_long_kernel" if cfg_.seq >= 2048 else "attention_x2_kernel")
-        if short:
-            return f"attention_16_short_kernel<{tag}>"
-        if cfg_.seq >= 512 or (cfg_.seq >= 128 and -(-cfg_.seq // 64) * cfg_.heads * 2 * b_ > 256):
-            return f"attention_16_long_kernel<{tag}>"
-        return f"attention_16_kernel<{tag}>"
-    m_all = 2 * B * cfg.seq
-    bk_es = 128 // es
-    symbol = {"linear_partial(proj+fc2)": linear_symbol(m_all, cfg.dim, cfg.hidden, split_k(m_all, cfg.dim, cfg.hidden, bk_es, in_flight, big_rule), True),
-              "residual_ln": f"residual_ln_kernel<{prec_tag}>",
-              "fc1": linear_symbol(m_all, cfg.hidden, cfg.dim, 1, False),
-              "qkv": linear_symbol(m_all, 3 * cfg.dim, cfg.dim, 1, False),
-              "attention": attention_symbol(prec_tag, cfg, B)}.get(dom, dom)
-    # HBM traffic (PMC) comes from separate rocprofv3 --pmc passes of this same command, never from this run: the line
-    # says which committed file and which commit of the kernels it was measured on, and mixes it into no live ratio.
-    traffic, traffic_source = None, None
-    TRAFFIC_PROFILE = _profile(TRAFFIC_PROFILES.get(args.precision, "none"))
-    STATS_PROFILE = _profile(STATS_PROFILES.get(args.precision, "none"))
-    pmc_path = os.path.join(ROOT, TRAFFIC_PROFILE)
-    if os.path.isfile(pmc_path) and args.precision in TRAFFIC_PROFILES and args.config == "vitb16_224" and B == 1:
-        with open(pmc_path) as fh:
-            blob = json.load(fh)
-        entry = blob.get("kernels", blob).get(symbol)
-        if entry:
-            traffic = entry.get("hbm_bytes_per_launch")
-            traffic_source = dict(file=TRAFFIC_PROFILE, symbol=symbol, measured_at_commit=blob.get("git_commit"),
-                                  command=blob.get("command"), mfma_busy_cycles_per_launch=entry.get("mfma_busy_cycles_per_launch"),
-                                  note="separate --pmc FETCH_SIZE / WRITE_SIZE (and SQ_VALU_MFMA_BUSY_CYCLES) passes; "
-                                       "FETCH_SIZE doubled per the gfx950 correction")
-    # the committed rocprofv3 --stats summary of the same command: average duration of the same symbol, so that the line and
-    # profiles/ can be reconciled mechanically (it is a record of ANOTHER run, on another box of the pool: +-4 %)
-    from_profile = None
-    stats_path = os.path.join(ROOT, STATS_PROFILE)
-    if os.path.isfile(stats_path) and args.precision in STATS_PROFILES and args.config == "vitb16_224" and B == 1 and symbol:
-        import csv
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        from symbols import short as short_symbol          # rocprofv3's (mangled) kernel names -> the names used here
-        with open(stats_path, newline="") as fh:
-            for row in csv.DictReader(fh):
-                name = row.get("Name", "")
-                if short_symbol(name) == symbol:
-                    calls, avg_ns = int(row["Calls"]), float(row["AverageNs"])
-                    from_profile = dict(file=STATS_PROFILE, name=name[:120], calls=calls, avg_ns=round(avg_ns, 1),
-                                        total_ms=round(calls * avg_ns * 1e-6, 3))
-                    break
-    mfma_bound = dom in ("qkv", "fc1", "attention", "patch_embed", "gram_argmax", "linear_partial(proj+fc2)")
-    if mfma_bound:
-        peak = PEAK_MFMA["fp32" if dom == "gram_argmax" else args.precision]
-        roof = dict(kernel=symbol, classes=members, bound="mfma", achieved=round(fl / avg_s / 1e12, 3), peak=peak / 1e12,
-                    unit="TFLOP/s", frac=round(fl / avg_s / peak, 5), traffic=traffic, traffic_source=traffic_source,
-                    algorithmic_flops_per_launch=fl, algorithmic_bytes_per_launch=by,
-                    avg_launch_us=round(avg_s * 1e6, 3))
-        if args.precision == "f16x2" and dom != "gram_argmax":
-            roof["executed_flops_per_launch"] = 3 * fl
-            roof["frac_of_split_ceiling"] = round(3 * fl / avg_s / peak, 5)
-            roof["note"] = ("split-f16: hi.hi + hi.lo + lo.hi = three f16 MFMAs per algorithmic MAC, so peak / 3 is the scheme's "
-                            "ceiling; `achieved` / `frac` price the ALGORITHMIC FLOPs against the full f16 peak")
-        if from_profile:
-            from_profile["achieved"] = round(fl / (from_profile["avg_ns"] * 1e-9) / 1e12, 3)
-            from_profile["frac"] = round(fl / (from_profile["avg_ns"] * 1e-9) / peak, 5)
-            roof["recomputed_from_profile"] = from_profile
-        if plain and dom == "linear_partial(proj+fc2)":
-            # the same kernel in a chain of plain launches (what the un-instrumented step pays per launch)
-            p_us = sum(plain[c] * kernels[c]["launches_per_step"] for c in members) / launches
-            roof.update(plain_launch_us=round(p_us, 3), achieved_plain=round(fl / (p_us * 1e-6) / 1e12, 3),
-                        frac_plain=round(fl / (p_us * 1e-6) / peak, 5))
-        if overlapped and dom == "linear_partial(proj+fc2)":
-            # ... and with `in_flight` queues busy, the regime `value` is measured in: proj and fc2 alternate 1 : 1 there, as in
-            # the forward (the patch-embedding launch, 1 of the symbol's 25 per update, is left out), so the FLOPs per launch
-            # are their mean
-            fl_o = (work["proj"][0] + work["fc2"][0]) / 2
-            o_us = overlapped["per_launch_us"]
-            overlapped.update(achieved=round(fl_o / (o_us * 1e-6) / 1e12, 3), unit="TFLOP/s", frac=round(fl_o / (o_us * 1e-6) / peak, 5),
-                              achieved_one_queue=round(fl_o / (overlapped["per_launch_us_one_queue"] * 1e-6) / 1e12, 3),
-                              algorithmic_flops_per_launch=fl_o,
-                              note="the dominant symbol as a captured chain of proj / fc2 launches in forward order on each of the "
-                                   "queues (random operands, 12 shared weight sets): wall time / launches over all queues")
-            roof["overlapped"] = overlapped
-    else:
-        roof = dict(kernel=symbol, classes=members, bound="hbm", achieved=round(by / avg_s / 1e9, 2), peak=PEAK_HBM / 1e9,
-                    unit="GB/s", frac=round(by / avg_s / PEAK_HBM, 5), traffic=traffic, traffic_source=traffic_source,
-                    algorithmic_bytes_per_launch=by, avg_launch_us=round(avg_s * 1e6, 3))
-        if from_profile:
-            from_profile["achieved"] = round(by / (from_profile["avg_ns"] * 1e-9) / 1e9, 2)
-            from_profile["frac"] = round(by / (from_profile["avg_ns"] * 1e-9) / PEAK_HBM, 5)
-            roof["recomputed_from_profile"] = from_profile
+        def linear_symbol(m, n, kk, s_, partial):   # the kernel symbol of the tile the LIBRARY reports for this layer (no mirror)
+            import ctypes
+            tile = (ctypes.c_int32 * 3)()
+            prec_id = {"f32": _lib.F32, "bf16": _lib.BF16, "f16": _lib.F16, "hx2": _lib.F16X2}[prec_tag]
+            prev_hint = eng.lib.vitvs_op_plan_in_flight(in_flight)       # the plan `value` ran under; restored at once
+            rc_ = eng.lib.vitvs_op_linear_tile(prec_id, m, n, kk, s_ if partial else 0, tile)
+            eng.lib.vitvs_op_plan_in_flight(prev_hint)
+            if rc_ != 0:
+                return None
+            if tile[2] == 0:
+                return f"linear_big_kernel<{prec_tag},{tile[0]}x{tile[1]}>:" + ("BigPartial" if partial else "BigStore")
+            return f"linear_kernel<{prec_tag},{tile[0]},{tile[1]},{tile[2]}>:" + ("EpiPartial" if partial else "EpiStore")
+        def attention_symbol(tag, cfg_, b_):     # mirror of launch_attention's dispatch (attention.hip)
+            short = cfg_.seq <= 256 and -(-cfg_.seq // 16) * cfg_.heads * 2 * b_ <= 640
+            if tag == "f32":
+                return "attention_f32_kernel"
+            if tag == "hx2":
+                return "attention_x2_short_kernel" if short else ("attention_x2_long_kernel" if cfg_.seq >= 2048 else "attention_x2_kernel")
+            if short:
+                return f"attention_16_short_kernel<{tag}>"
+            if cfg_.seq >= 512 or (cfg_.seq >= 128 and -(-cfg_.seq // 64) * cfg_.heads * 2 * b_ > 256):
+                return f"attention_16_long_kernel<{tag}>"
+            return f"attention_16_kernel<{tag}>"
+        m_all = 2 * B * cfg.seq
+        bk_es = 128 // es
+        symbol = {"linear_partial(proj+fc2)": linear_symbol(m_all, cfg.dim, cfg.hidden, split_k(m_all, cfg.dim, cfg.hidden, bk_es, in_flight, big_rule), True),
+                  "residual_ln": f"residual_ln_kernel<{prec_tag}>",
+                  "fc1": linear_symbol(m_all, cfg.hidden, cfg.dim, 1, False),
+                  "qkv": linear_symbol(m_all, 3 * cfg.dim, cfg.dim, 1, False),
+                  "attention": attention_symbol(prec_tag, cfg, B)}.get(dom, dom)
+        # HBM traffic (PMC) comes from separate rocprofv3 --pmc passes of this same command, never from this run: the line
+        # says which committed file and which commit of the kernels it was measured on, and mixes it into no live ratio.
+        traffic, traffic_source = None, None
+        TRAFFIC_PROFILE = _profile(TRAFFIC_PROFILES.get(args.precision, "none"))
+        STATS_PROFILE = _profile(STATS_PROFILES.get(args.precision, "none"))
+        pmc_path = os.path.join(ROOT, TRAFFIC_PROFILE)
+        if os.path.isfile(pmc_path) and args.precision in TRAFFIC_PROFILES and args.config == "vitb16_224" and B == 1:
+            with open(pmc_path) as fh:
+                blob = json.load(fh)
+            entry = blob.get("kernels", blob).get(symbol)
+            if entry:
+                traffic = entry.get("hbm_bytes_per_launch")
+                traffic_source = dict(file=TRAFFIC_PROFILE, symbol=symbol, measured_at_commit=blob.get("git_commit"),
+                                      command=blob.get("command"), mfma_busy_cycles_per_launch=entry.get("mfma_busy_cycles_per_launch"),
+                                      note="separate --pmc FETCH_SIZE / WRITE_SIZE (and SQ_VALU_MFMA_BUSY_CYCLES) passes; "
+                                           "FETCH_SIZE doubled per the gfx950 correction")
+        # the committed rocprofv3 --stats summary of the same command: average duration of the same symbol, so that the line and
+        # profiles/ can be reconciled mechanically (it is a record of ANOTHER run, on another machine of the same type: +-4 %)
+        from_profile = None
+        stats_path = os.path.join(ROOT, STATS_PROFILE)
+        if os.path.isfile(stats_path) and args.precision in STATS_PROFILES and args.config == "vitb16_224" and B == 1 and symbol:
+            import csv
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            from symbols import short as short_symbol          # rocprofv3's (mangled) kernel names -> the names used here
+            with open(stats_path, newline="") as fh:
+                for row in csv.DictReader(fh):
+                    name = row.get("Name", "")
+                    if short_symbol(name) == symbol:
+                        calls, avg_ns = int(row["Calls"]), float(row["AverageNs"])
+                        from_profile = dict(file=STATS_PROFILE, name=name[:120], calls=calls, avg_ns=round(avg_ns, 1),
+                                            total_ms=round(calls * avg_ns * 1e-6, 3))
+                        break
+        mfma_bound = dom in ("qkv", "fc1", "attention", "patch_embed", "gram_argmax", "linear_partial(proj+fc2)")
+        if mfma_bound:
+            peak = PEAK_MFMA["fp32" if dom == "gram_argmax" else args.precision]
+            roof = dict(kernel=symbol, classes=members, bound="mfma", achieved=round(fl / avg_s / 1e12, 3), peak=peak / 1e12,
+                        unit="TFLOP/s", frac=round(fl / avg_s / peak, 5), traffic=traffic, traffic_source=traffic_source,
+                        algorithmic_flops_per_launch=fl, algorithmic_bytes_per_launch=by,
+                        avg_launch_us=round(avg_s * 1e6, 3))
+            if args.precision == "f16x2" and dom != "gram_argmax":
+                roof["executed_flops_per_launch"] = 3 * fl
+                roof["frac_of_split_ceiling"] = round(3 * fl / avg_s / peak, 5)
+                roof["note"] = ("split-f16: hi.hi + hi.lo + lo.hi = three f16 MFMAs per algorithmic MAC, so peak / 3 is the scheme's "
+                                "ceiling; `achieved` / `frac` price the ALGORITHMIC FLOPs against the full f16 peak")
+            if from_profile:
+                from_profile["achieved"] = round(fl / (from_profile["avg_ns"] * 1e-9) / 1e12, 3)
+                from_profile["frac"] = round(fl / (from_profile["avg_ns"] * 1e-9) / peak, 5)
+                roof["recomputed_from_profile"] = from_profile
+            if plain and dom == "linear_partial(proj+fc2)":
+                # the same kernel in a chain of plain launches (what the un-instrumented step pays per launch)
+                p_us = sum(plain[c] * kernels[c]["launches_per_step"] for c in members) / launches
+                roof.update(plain_launch_us=round(p_us, 3), achieved_plain=round(fl / (p_us * 1e-6) / 1e12, 3),
+                            frac_plain=round(fl / (p_us * 1e-6) / peak, 5))
+            if overlapped and dom == "linear_partial(proj+fc2)":
+                # ... and with `in_flight` queues busy, the regime `value` is measured in: proj and fc2 alternate 1 : 1 there, as in
+                # the forward (the patch-embedding launch, 1 of the symbol's 25 per update, is left out), so the FLOPs per launch
+                # are their mean
+                fl_o = (work["proj"][0] + work["fc2"][0]) / 2
+                o_us = overlapped["per_launch_us"]
+                overlapped.update(achieved=round(fl_o / (o_us * 1e-6) / 1e12, 3), unit="TFLOP/s", frac=round(fl_o / (o_us * 1e-6) / peak, 5),
+                                  achieved_one_queue=round(fl_o / (overlapped["per_launch_us_one_queue"] * 1e-6) / 1e12, 3),
+                                  algorithmic_flops_per_launch=fl_o,
+                                  note="the dominant symbol as a captured chain of proj / fc2 launches in forward order on each of the "
+                                       "queues (random operands, 12 shared weight sets): wall time / launches over all queues")
+                roof["overlapped"] = overlapped
+        else:
+            roof = dict(kernel=symbol, classes=members, bound="hbm", achieved=round(by / avg_s / 1e9, 2), peak=PEAK_HBM / 1e9,
+                        unit="GB/s", frac=round(by / avg_s / PEAK_HBM, 5), traffic=traffic, traffic_source=traffic_source,
+                        algorithmic_bytes_per_launch=by, avg_launch_us=round(avg_s * 1e6, 3))
+            if from_profile:
+                from_profile["achieved"] = round(by / (from_profile["avg_ns"] * 1e-9) / 1e9, 2)
+                from_profile["frac"] = round(by / (from_profile["avg_ns"] * 1e-9) / PEAK_HBM, 5)
+                roof["recomputed_from_profile"] = from_profile
 
-    if host_buffers:
-        # a host-pointer call ends with the caller holding v_c, i.e. with a wait: its device-resident counterpart is the
-        # synchronised single update (latency_ms_with_host_sync), not the back-to-back stream of `sequential`
-        sync_ms = float(np.median(lat)) * 1e3
-        host_buffers["vs_sequential"] = round(host_buffers["value"] / (sequential["value"] if sequential else value), 4)
-        host_buffers["vs_device_resident_update_with_host_sync"] = round(sync_ms / host_buffers["ms_per_step"], 4)
+        if host_buffers:
+            # a host-pointer call ends with the caller holding v_c, i.e. with a wait: its device-resident counterpart is the
+            # synchronised single update (latency_ms_with_host_sync), not the back-to-back stream of `sequential`
+            sync_ms = float(np.median(lat)) * 1e3
+            host_buffers["vs_sequential"] = round(host_buffers["value"] / (sequential["value"] if sequential else value), 4)
+            host_buffers["vs_device_resident_update_with_host_sync"] = round(sync_ms / host_buffers["ms_per_step"], 4)
     out = dict(
         metric="servo_updates_per_sec", value=round(value, 2), unit="updates/s", n_gpus=world, steps=args.steps,
         warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4), higher_is_better=True, scaling="weak",
@@ -1216,27 +1244,32 @@ def run_rank(args):
                   f"weights, hipGraph replay, the in_flight tile plan); the timed region is K updates between two barrier + "
                   f"synchronize pairs, filling and draining the {pipe.active} slots included" if in_flight > 1 else
                   "one update in flight per GPU: one handle, one stream, plain launches"),
-        value_one_in_flight=(sequential["value"] if sequential else round(value, 2)),
-        roofline=roof,
-        cpu_baseline=None,
-        parity=parity,
-        sequential=sequential,
-        secondary=secondary,
-        goal_cached=goal_cached,
-        host_buffers=host_buffers,
-        controller_loop=controller_loop,
-        same_kernels_fp16=same_kernels_fp16,
-        path=dict(gflop_per_update=round(cfg.flops_per_pair(binned) / 1e9, 3),
-                  tflops=round(cfg.flops_per_pair(binned) * value / world / 1e12, 3),
-                  frac_of_mfma_peak=round(cfg.flops_per_pair(binned) * value / world / PEAK_MFMA[args.precision], 5),
-                  weight_bytes=cfg.weight_elems() * es,
-                  weight_stream_frac_of_hbm_peak=round(cfg.weight_elems() * es * value / world / B / PEAK_HBM, 5)),
-        latency_ms_with_host_sync=round(float(np.median(lat)) * 1e3, 4),
-        latency_ms_per_update_in_flight=None if lat_in_flight is None else round(lat_in_flight, 4),
-        kernels=kernels,
-        status=[int(s) for s in status_host],
-        v_c=[float(x) for x in v_host[0]],
     )
+    if args.full:
+        out.update(
+            value_one_in_flight=(sequential["value"] if sequential else round(value, 2)),
+            roofline=roof,
+            cpu_baseline=None,
+            parity=parity,
+            sequential=sequential,
+            secondary=secondary,
+            goal_cached=goal_cached,
+            host_buffers=host_buffers,
+            controller_loop=controller_loop,
+            same_kernels_fp16=same_kernels_fp16,
+        )
+    out["path"] = dict(gflop_per_update=round(cfg.flops_per_pair(binned) / 1e9, 3),
+                       tflops=round(cfg.flops_per_pair(binned) * value / world / 1e12, 3),
+                       frac_of_mfma_peak=round(cfg.flops_per_pair(binned) * value / world / PEAK_MFMA[args.precision], 5),
+                       weight_bytes=cfg.weight_elems() * es,
+                       weight_stream_frac_of_hbm_peak=round(cfg.weight_elems() * es * value / world / B / PEAK_HBM, 5))
+    if args.full:
+        out.update(
+            latency_ms_with_host_sync=round(float(np.median(lat)) * 1e3, 4),
+            latency_ms_per_update_in_flight=None if lat_in_flight is None else round(lat_in_flight, 4),
+            kernels=kernels,
+        )
+    out.update(status=[int(s) for s in status_host], v_c=[float(x) for x in v_host[0]])
     if rank_ms is not None:
         out["per_rank_ms_per_step"] = dict(rank_ms, max=round(rank_ms["max"], 4))
         out["v_c_gather"] = ("none (--no-gather: every rank keeps its own twists)" if not do_gather else
@@ -1252,7 +1285,7 @@ def run_rank(args):
         out["dist_backend"] = os.environ.get("VITVS_DIST_BACKEND", "nccl")
         if ranks_seen != world:
             raise SystemExit(f"the communicator spans {ranks_seen} ranks, expected {world}")
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, sd, des_np[0], cur_np[0], depth_np, params)
     if rank == 0:
         print(json.dumps(out))

@@ -26,6 +26,13 @@ def test_rank_environments(bench):
     assert all(e["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" for e in envs)
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(bench):
+    args = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 5 and args.warmup == 2
+    args = bench.parse_args(["--full", "--dump-outputs", "out_dir"])
+    assert args.full is True and args.dump_outputs == "out_dir"
+
+
 def test_more_gpus_than_devices_fails_loudly(bench, monkeypatch, capsys):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.delenv("VITVS_BENCH_SHARE_GPU", raising=False)

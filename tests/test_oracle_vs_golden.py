@@ -161,21 +161,48 @@ def test_rig8_fixture_pairs_meet_the_acceptance_rule_and_match_the_oracle():
         np.testing.assert_allclose(out["v_c"], case["v_c"], rtol=1e-10)
 
 
-def test_rotation_fixture_matches_the_oracle_draws_and_scores():
-    """find_and_set_best_pose (vitvs_v2.py:1151-1189): four views, num_pairs = 48, consecutive draws, mean similarity."""
+def test_rotation_fixture_matches_the_oracle_draws_and_scores(monkeypatch):
+    """find_and_set_best_pose (vitvs_v2.py:1151-1189): four views, num_pairs = 48, consecutive draws, mean similarity.
+
+    The draws see the tokens only through the nearest-neighbour tables (sim_1, nn_1, sim_2, nn_2) of each goal / view pair.
+    rotation_vits16_224_tables.npz holds the fixture's own tables (servo_ref.nearest_neighbours of servo_ref.cosine_matrix of
+    the tokens the fixture was made from): on them the oracle's filter, draws, similarities and scores must be bit-exact.
+    The float32 forward computed here rounds differently in the last bits on CPUs whose vector kernels differ (AVX2 against
+    AVX-512), so its own tables must give the same arg-max indices and the same draws, similarities and scores to float32
+    round-off."""
     blob = load_golden("rotation_vits16_224.npz")
+    tables = load_golden("rotation_vits16_224_tables.npz")
+    fixture = [tuple(torch.from_numpy(tables[f"view{i}/{k}"]) for k in ("sim_1", "nn_1", "sim_2", "nn_2")) for i in range(4)]
     cfg = config.baseline_config("vits16_224")
     sd = weights.synthetic_state_dict(cfg, int(blob["weight_seed"]))
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
     views = [np.rot90(cur, int(k)).copy() for k in blob["rot90_k"]]
     toks = vit_ref.block_tokens(sd, np.stack([des] + views), patch=cfg.patch, stride=cfg.stride, heads=cfg.heads,
                                 layer=cfg.layer, mean=cfg.mean, std=cfg.std)[:, 1:]
-    torch.manual_seed(121)
-    scores = []
-    for i in range(4):
-        corr = sr.find_correspondences(toks[0], toks[1 + i], num_pairs=int(blob["num_pairs"]))
-        assert np.array_equal(corr["points1"].numpy(), blob[f"view{i}/points1"])
-        assert np.array_equal(corr["points2"].numpy(), blob[f"view{i}/points2"])
-        scores.append(corr["sim"].mean().item())
-        assert scores[-1] == float(blob[f"view{i}/score"])
-    assert int(np.argmax(scores)) == int(blob["best"]) == 1          # the un-rotated view
+    for i in range(4):                                               # the forward computed here against the fixture's tables
+        local = sr.nearest_neighbours(sr.cosine_matrix(toks[0], toks[1 + i]))
+        assert torch.equal(local[1], fixture[i][1]) and torch.equal(local[3], fixture[i][3])
+        np.testing.assert_allclose(local[0].numpy(), fixture[i][0].numpy(), rtol=1e-6, atol=0)
+        np.testing.assert_allclose(local[2].numpy(), fixture[i][2].numpy(), rtol=1e-6, atol=0)
+
+    def draw_all():
+        torch.manual_seed(121)
+        scores = []
+        for i in range(4):
+            view[0] = i
+            corr = sr.find_correspondences(toks[0], toks[1 + i], num_pairs=int(blob["num_pairs"]))
+            assert np.array_equal(corr["points1"].numpy(), blob[f"view{i}/points1"])
+            assert np.array_equal(corr["points2"].numpy(), blob[f"view{i}/points2"])
+            scores.append(corr["sim"].mean().item())
+            yield i, corr["sim"].reshape(-1).numpy(), scores[-1]
+        assert int(np.argmax(scores)) == int(blob["best"]) == 1      # the un-rotated view
+
+    view = [0]
+    with monkeypatch.context() as m:                                 # the oracle's draws on the fixture's own tables
+        m.setattr(sr, "nearest_neighbours", lambda sim: fixture[view[0]])
+        for i, sim, score in draw_all():
+            assert np.array_equal(sim, blob[f"view{i}/sim_selected"])      # bit-exact fp32
+            assert score == float(blob[f"view{i}/score"])
+    for i, sim, score in draw_all():                                 # ... and end to end on the tables computed here
+        np.testing.assert_allclose(sim, blob[f"view{i}/sim_selected"], rtol=1e-6, atol=0)
+        assert score == pytest.approx(float(blob[f"view{i}/score"]), rel=1e-6, abs=0)
