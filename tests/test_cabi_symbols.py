@@ -125,3 +125,20 @@ def test_linear_tile_plan_of_the_library():
     assert plan(_lib.F32, 6274, 3072, 768) == (128, 128, 1)  # fp32 never takes the 256-row kernels
     t = (ctypes.c_int32 * 3)()
     assert lib.vitvs_op_linear_tile(b, 394, 768, 3072, 5, t) != 0   # 3072 is not a multiple of 5 k-tiles
+    # The whole table: every linear shape of the BASELINE configs at 1 .. 16 images (patch-embed, qkv, proj, fc1, fc2) and the
+    # shapes above, in the four precisions, under the hints 1 .. 4 of updates in flight, as vitvs_op_linear and as the partial-sum
+    # form at the library's slice count.  Columns: hint, precision, M, N, K, slices (0: vitvs_op_linear), return code, tile[0..2];
+    # recorded through this ABI.
+    import numpy as np
+    table = np.load(os.path.join(ROOT, "tests", "golden", "linear_plans.npz"))["plans"]
+    assert len(table) > 15000
+    prev = lib.vitvs_op_plan_in_flight(1)
+    try:
+        for hint, prec, m, n, k, slices, rc, *tile in table.tolist():
+            lib.vitvs_op_plan_in_flight(hint)
+            if slices:
+                assert lib.vitvs_op_splitk_slices(prec, m, n, k) == slices, (hint, prec, m, n, k)
+            got = lib.vitvs_op_linear_tile(prec, m, n, k, slices, t)
+            assert (got, list(t)) == (rc, tile), (hint, prec, m, n, k, slices)
+    finally:
+        lib.vitvs_op_plan_in_flight(prev)

@@ -399,7 +399,7 @@ def test_long_attention_deferred_rescale_with_slowly_growing_scores(lib, slope):
 
 # ------------------------------------------------------------------------------------------------------------------
 # The many-row selections of the "in_flight" hint (vitvs_set_option; kernels.h g_updates_in_flight): 256 x 256 tiles wherever they
-# divide from 1536 rows on (gemm_big.hip big_tile_width), at most two K slices and exactly two from 2048 rows on for the narrow
+# divide from 1536 rows on (gemm.hip big_tile), at most two K slices and exactly two from 2048 rows on for the narrow
 # layers (gemm.hip splitk_slices), whole query blocks in the long-sequence attention (attention.hip attention_plan).  Row counts:
 # 4 / 8 ViT-B/16 pairs (1576 / 3152), ViT-B/8 448² (6274), ViT-L/14 518² (2740).
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])

@@ -1,7 +1,7 @@
 """Short, stable names for this library's kernels as rocprofv3 reports them (mangled or demangled)."""
 import re
 
-_EPI = r"(EpiStore|EpiPartial|EpiPatch|EpiResidual|BigStore|BigPartial)"
+_EPI = r"(EpiStore|EpiPartial|EpiResidual|BigStore|BigPartial)"
 
 
 def _prec(name):

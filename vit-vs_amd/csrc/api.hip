@@ -369,6 +369,7 @@ struct ChainCtx {
     const ResizeArgs* rs = nullptr;   // camera-resolution frames (vitvs_set_frame_size): resize inside the patch-row build
     bool want_desc = false;   // the last residual_ln also writes the plain descriptors (launch_residual_ln)
     DescOut desc;
+    struct { LinearPlan embed, qkv, proj, fc1, fc2; } plan;   // of the chain's five linear shapes (forward_chain)
 };
 
 // The forward, operator by operator, on one stream.  (The two FRAMES of one update as two chains — on two streams, or in
@@ -376,44 +377,41 @@ struct ChainCtx {
 // nearly what full-size ones do, gfx9 ignores the any-order flag, and the kernel-trace timelines that showed the queues
 // taking turns were the profiler's own serialisation (profiles/r03_notes.md section 5).  What does overlap is whole,
 // independent UPDATES on separate handles and queues: include/vitvs.h "several updates in flight", vit-vs_amd/pipeline.py.)
-int forward_lockstep(vitvs_handle* h, ChainCtx* cx, int n, hipStream_t st) {
+int forward_launches(vitvs_handle* h, const ChainCtx& cx, hipStream_t st) {
     const vitvs_config& c = h->cfg;
     const int D = c.dim;
     int rc = 0;
-    for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_PATCHIFY, st);
-        rc = launch_patchify(h->prec, cx[k].pa, cx[k].rs, cx[k].Ape, cx[k].x, st); }
+    { Span sp(h, KC_PATCHIFY, st);
+        rc = launch_patchify(h->prec, cx.pa, cx.rs, cx.Ape, cx.x, st); }
     // Patch embedding as a split-K GEMM (more workgroups than its 84 output tiles), finished together with
     // cls / pos_embed and block 0's norm1 by one residual_ln-style launch.
     // Block i: qkv -> attention -> proj (split-K partials) -> [residual + norm2] -> fc1+GELU ->
     // fc2 (split-K partials) -> [residual + norm1 of block i+1].
-    for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_PATCH_EMBED, st);
-        rc = launch_linear_partial(h->prec, cx[k].Ape, h->pe_w, cx[k].part, cx[k].cnt * h->T, D, h->Kp,
-                                   splitk_slices(h->prec, cx[k].cnt * h->T, D, h->Kp), st, h->pe_e); }
-    for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_LAYERNORM, st);
-        rc = launch_embed_ln(h->prec, cx[k].x, cx[k].part, splitk_slices(h->prec, cx[k].cnt * h->T, D, h->Kp), h->pe_b, h->pos,
-                             h->cls, h->blk[0].n1w, h->blk[0].n1b, cx[k].xn, cx[k].cnt, h->T, D, c.ln_eps, st); }
+    if (!rc) { Span sp(h, KC_PATCH_EMBED, st);
+        rc = launch_linear(cx.plan.embed, cx.Ape, h->pe_w, nullptr, cx.part, 0, st, h->pe_e); }
+    if (!rc) { Span sp(h, KC_LAYERNORM, st);
+        rc = launch_embed_ln(h->prec, cx.x, cx.part, cx.plan.embed.splits, h->pe_b, h->pos, h->cls, h->blk[0].n1w, h->blk[0].n1b,
+                             cx.xn, cx.cnt, h->T, D, c.ln_eps, st); }
     for (int i = 0; i < c.blocks && !rc; ++i) {
         const Block& b = h->blk[i];
         const Block* nx = (i + 1 < c.blocks) ? &h->blk[i + 1] : nullptr;
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_QKV, st);
-            rc = launch_linear(h->prec, cx[k].xn, b.qkvw, b.qkvb, cx[k].qkv, cx[k].M, 3 * D, D, 0, st, b.qkve); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_ATTENTION, st);
-            rc = launch_attention(h->prec, cx[k].qkv, cx[k].attn, cx[k].cnt, h->N, c.heads, st, &h->attn_ws, plain16(h->prec)); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_PROJ, st);
-            rc = launch_linear_partial(h->prec, cx[k].attn, b.projw, cx[k].part, cx[k].M, D, D,
-                                       splitk_slices(h->prec, cx[k].M, D, D), st, b.proje); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_RESIDUAL_LN, st);
-            rc = launch_residual_ln(h->prec, cx[k].x, cx[k].part, splitk_slices(h->prec, cx[k].M, D, D), b.projb, b.ls1,
-                                    b.n2w, b.n2b, cx[k].xn, cx[k].M, D, c.ln_eps, st); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_FC1, st);
-            rc = launch_linear(h->prec, cx[k].xn, b.fc1w, b.fc1b, cx[k].hid, cx[k].M, h->hidden, D, 1, st, b.fc1e); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_FC2, st);
-            rc = launch_linear_partial(h->prec, cx[k].hid, b.fc2w, cx[k].part, cx[k].M, D, h->hidden,
-                                       splitk_slices(h->prec, cx[k].M, D, h->hidden), st, b.fc2e); }
-        for (int k = 0; k < n && !rc; ++k) { Span sp(h, KC_RESIDUAL_LN, st);
-            rc = launch_residual_ln(h->prec, cx[k].x, cx[k].part, splitk_slices(h->prec, cx[k].M, D, h->hidden), b.fc2b,
-                                    b.ls2, nx ? nx->n1w : nullptr, nx ? nx->n1b : nullptr, cx[k].xn, cx[k].M, D, c.ln_eps, st,
-                                    (!nx && cx[k].want_desc) ? &cx[k].desc : nullptr); }
+        { Span sp(h, KC_QKV, st);
+            rc = launch_linear(cx.plan.qkv, cx.xn, b.qkvw, b.qkvb, cx.qkv, 0, st, b.qkve); }
+        if (!rc) { Span sp(h, KC_ATTENTION, st);
+            rc = launch_attention(h->prec, cx.qkv, cx.attn, cx.cnt, h->N, c.heads, st, &h->attn_ws, plain16(h->prec)); }
+        if (!rc) { Span sp(h, KC_PROJ, st);
+            rc = launch_linear(cx.plan.proj, cx.attn, b.projw, nullptr, cx.part, 0, st, b.proje); }
+        if (!rc) { Span sp(h, KC_RESIDUAL_LN, st);
+            rc = launch_residual_ln(h->prec, cx.x, cx.part, cx.plan.proj.splits, b.projb, b.ls1, b.n2w, b.n2b, cx.xn, cx.M, D,
+                                    c.ln_eps, st); }
+        if (!rc) { Span sp(h, KC_FC1, st);
+            rc = launch_linear(cx.plan.fc1, cx.xn, b.fc1w, b.fc1b, cx.hid, 1, st, b.fc1e); }
+        if (!rc) { Span sp(h, KC_FC2, st);
+            rc = launch_linear(cx.plan.fc2, cx.hid, b.fc2w, nullptr, cx.part, 0, st, b.fc2e); }
+        if (!rc) { Span sp(h, KC_RESIDUAL_LN, st);
+            rc = launch_residual_ln(h->prec, cx.x, cx.part, cx.plan.fc2.splits, b.fc2b, b.ls2, nx ? nx->n1w : nullptr,
+                                    nx ? nx->n1b : nullptr, cx.xn, cx.M, D, c.ln_eps, st,
+                                    (!nx && cx.want_desc) ? &cx.desc : nullptr); }
     }
     if (rc) return set_err(h, rc, "forward launch failed");
     return 0;
@@ -451,6 +449,13 @@ int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
                   hipStream_t st) {
     if (i0 == 0) h->goal_frames = 0;            // rows of a cached goal are about to be overwritten (vitvs_set_goal_dev re-arms)
     ChainCtx cx = fill_ctx(h, i0, cnt, n_des, des, cur, part);
+    const Precision p = h->prec;
+    const int D = h->cfg.dim;
+    cx.plan.embed = plan_linear(p, cnt * h->T, D, h->Kp, EPI_PARTIAL);
+    cx.plan.qkv = plan_linear(p, cx.M, 3 * D, D, EPI_STORE);
+    cx.plan.proj = plan_linear(p, cx.M, D, D, EPI_PARTIAL);
+    cx.plan.fc1 = plan_linear(p, cx.M, h->hidden, D, EPI_STORE);
+    cx.plan.fc2 = plan_linear(p, cx.M, D, h->hidden, EPI_PARTIAL);
     if (h->desc_keys >= 0 && desc_in_forward(h)) {
         cx.want_desc = true;
         if (h->cfg.binned) cx.desc.sq = h->sq + (size_t)i0 * h->T;
@@ -459,7 +464,7 @@ int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
         cx.desc.T = h->T;
         cx.desc.zero_count = (i0 == 0 || h->goal_frames > 0) ? h->desc_keys : 0;   // the call's only chain clears the arg-max keys
     }
-    return forward_lockstep(h, &cx, 1, st);
+    return forward_launches(h, cx, st);
 }
 
 int forward(vitvs_handle* h, int n_des, const uint8_t* des, int n_cur, const uint8_t* cur, hipStream_t st) {
@@ -544,6 +549,20 @@ int wait_stream(hipStream_t st) {
     }
     VITVS_HIP_CHECK(hipStreamSynchronize(st));
     return 0;
+}
+
+// The plan of vitvs_op_linear_variant's tile codes; slices > 0: the partial-sum form with that many K slices.
+LinearPlan variant_plan(Precision p, int variant, int M, int N, int K, int slices) {
+    const LinearEpi epi = slices > 0 ? EPI_PARTIAL : EPI_STORE;
+    switch (variant) {
+    case 0: return plan_linear(p, M, N, K, epi, slices);
+    case 1: return plan_linear(p, M, N, K, epi, slices, false);
+    case 2: return plan_linear(p, M, N, K, epi, slices, false, 128, 128);
+    case 128: case 192: case 256: return plan_linear(p, M, N, K, epi, slices, true, 256, variant);
+    case 1192: return plan_linear(p, M, N, K, epi, slices, true, 192, 128);
+    case 1256: return plan_linear(p, M, N, K, epi, slices, true, 192, 256);
+    default: return LinearPlan{};
+    }
 }
 
 }  // namespace
@@ -1396,7 +1415,7 @@ int vitvs_timing_collect(vitvs_handle* h, int32_t n_classes, double* total_ms, i
 int vitvs_op_linear(int32_t precision, const void* A, const void* W, const float* bias, void* out, int32_t M,
                     int32_t N, int32_t K, int32_t gelu, void* stream) {
     DeviceScope dev(nullptr);
-    return launch_linear(to_prec(precision), A, W, bias, out, M, N, K, gelu, as_stream(stream), g_op_wexp);
+    return launch_linear(plan_linear(to_prec(precision), M, N, K, EPI_STORE), A, W, bias, out, gelu, as_stream(stream), g_op_wexp);
 }
 int vitvs_op_weight_exponent(int32_t e) {
     const int prev = g_op_wexp;
@@ -1406,25 +1425,14 @@ int vitvs_op_weight_exponent(int32_t e) {
 int vitvs_op_linear_variant(int32_t precision, int32_t variant, const void* A, const void* W, const float* bias, void* out,
                             int32_t M, int32_t N, int32_t K, int32_t gelu, int32_t slices, void* stream) {
     DeviceScope dev(nullptr);
-    const Precision p = to_prec(precision);
-    hipStream_t st = as_stream(stream);
-    if (variant == 0)
-        return slices > 0 ? launch_linear_partial(p, A, W, (float*)out, M, N, K, slices, st, g_op_wexp)
-                          : launch_linear(p, A, W, bias, out, M, N, K, gelu, st, g_op_wexp);
-    if (variant == 1)
-        return slices > 0 ? launch_linear_partial_classic(p, A, W, (float*)out, M, N, K, slices, st, g_op_wexp)
-                          : launch_linear_classic(p, A, W, bias, out, M, N, K, gelu, st, g_op_wexp);
-    if (variant == 2) return p == PREC_X2 ? -2 : launch_linear_128(p, A, W, bias, out, M, N, K, gelu, slices > 0 ? slices : 1, slices > 0, st);
-    const int kk = (p == PREC_X2 ? 2 : 1) * K;     // elements per row of the big kernels' operands
-    if (variant == 1256) return (N % 256 || kk % 64) ? -2 : launch_linear_big(p, 1256, A, W, bias, out, M, N, K, slices > 0 ? slices : 1, gelu, slices > 0, st, g_op_wexp);
-    if (variant == 1192) return (N % 128 || kk % 64) ? -2 : launch_linear_big(p, 1192, A, W, bias, out, M, N, K, slices > 0 ? slices : 1, gelu, slices > 0, st, g_op_wexp);
-    if ((variant != 256 && variant != 192 && variant != 128) || N % variant != 0 || kk % 64 != 0) return -2;
-    return launch_linear_big(p, variant, A, W, bias, out, M, N, K, slices > 0 ? slices : 1, gelu, slices > 0, st, g_op_wexp);
+    return launch_linear(variant_plan(to_prec(precision), variant, M, N, K, slices), A, W, bias, out, gelu, as_stream(stream),
+                         g_op_wexp);
 }
 int vitvs_op_linear_residual(int32_t precision, const void* A, const void* W, const float* bias, const float* ls,
                              float* x, int32_t M, int32_t N, int32_t K, void* stream) {
     DeviceScope dev(nullptr);
-    return launch_linear_residual(to_prec(precision), A, W, bias, ls, x, M, N, K, as_stream(stream), g_op_wexp);
+    return launch_linear(plan_linear(to_prec(precision), M, N, K, EPI_RESIDUAL), A, W, bias, x, 0, as_stream(stream), g_op_wexp,
+                         ls);
 }
 int vitvs_op_layernorm(int32_t precision, const float* x, const float* gamma, const float* beta, void* out, int32_t M,
                        int32_t D, float eps, void* stream) {
@@ -1444,10 +1452,9 @@ int vitvs_op_attention_q(int32_t precision, const void* qkv, void* out, int32_t 
 }
 int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* tile) {
     if (!tile) return -1;
-    int t[3] = {0, 0, 0};
-    const int rc = linear_tile_plan(to_prec(precision), M, N, K, slices > 0 ? slices : 1, slices > 0, t);
-    tile[0] = t[0]; tile[1] = t[1]; tile[2] = t[2];
-    return rc;
+    const LinearPlan pl = plan_linear(to_prec(precision), M, N, K, slices > 0 ? EPI_PARTIAL : EPI_STORE, slices);
+    tile[0] = pl.rows; tile[1] = pl.cols; tile[2] = pl.rows && !pl.big ? pl.kgroups : 0;
+    return pl.rows ? 0 : -2;
 }
 int vitvs_op_touch(const void* p, int64_t bytes, int32_t share_xcds, void* stream) {
     DeviceScope dev(nullptr);
@@ -1459,12 +1466,14 @@ int vitvs_op_plan_in_flight(int32_t n) {
     return prev;
 }
 int vitvs_op_splitk_slices(int32_t precision, int32_t M, int32_t N, int32_t K) {
-    return splitk_slices(to_prec(precision), M, N, K);
+    return plan_linear(to_prec(precision), M, N, K, EPI_PARTIAL).splits;
 }
 int vitvs_op_linear_partial(int32_t precision, const void* A, const void* W, float* part, int32_t M, int32_t N,
                             int32_t K, int32_t slices, void* stream) {
     DeviceScope dev(nullptr);
-    return launch_linear_partial(to_prec(precision), A, W, part, M, N, K, slices, as_stream(stream), g_op_wexp);
+    if (slices < 1) return -2;
+    return launch_linear(plan_linear(to_prec(precision), M, N, K, EPI_PARTIAL, slices), A, W, nullptr, part, 0, as_stream(stream),
+                         g_op_wexp);
 }
 int vitvs_op_residual_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias,
                          const float* ls, const float* gamma, const float* beta, void* out, int32_t M, int32_t D,

@@ -99,26 +99,6 @@ struct EpiResidual {
     }
 };
 
-struct EpiPatch {
-    static constexpr bool STAGED = false;
-    float* x;
-    const float* bias;
-    const float* pos;
-    int T, D;
-    __device__ __forceinline__ void set_slice(int) {}
-    __device__ __forceinline__ static EpiPatch make(void* out, const float* c0, const float* c1, int, int N, int i0) {
-        return EpiPatch{(float*)out, c0, c1, i0, N};
-    }
-    __device__ __forceinline__ float4 column_terms(int n) const { return *reinterpret_cast<const float4*>(bias + n); }
-    template <bool WT>
-    __device__ __forceinline__ void store(int m, int n, f32x4 v, float4 b) const {
-        const int img = m / T, t = m - img * T;
-        const float4 pe = *reinterpret_cast<const float4*>(pos + (size_t)(1 + t) * D + n);
-        float4 r = make_float4(v[0] + b.x + pe.x, v[1] + b.y + pe.y, v[2] + b.z + pe.z, v[3] + b.w + pe.w);
-        *reinterpret_cast<float4*>(x + ((size_t)img * (T + 1) + 1 + t) * D + n) = r;
-    }
-};
-
 // Raw fp32 partial sums of one K slice (split-K): part[z][m][n]; bias / LayerScale / residual /
 // LayerNorm are applied by residual_ln_kernel (elementwise.hip), which sums the slices in a fixed
 // order, so the result does not depend on scheduling (no atomics).
@@ -272,7 +252,112 @@ static bool shapes_ok(Precision p, int M, int N, int K) {
            (long long)N * K * es < (1ll << 32);
 }
 
-// Tile plan.  In the one-frame-pair regime a launch cannot fill the chip, and a second wave of
+// ---------------------------------------------------------------------------------------------------- the plan
+// The rules below are plan_linear's; `hint` is the calling thread's updates in flight (g_updates_in_flight), read once there.
+
+// K slices of a partial-sum layer.
+static int splitk_slices(Precision p, int M, int N, int K, int hint) {
+    const int bk = k_tile(p);
+    // Many rows, narrow layer (8 frame pairs or a 518² input through proj / fc2): the 256x128 tiles of gemm_big.hip fill
+    // well under half of the chip (78 tiles at 3152 x 768), so K is cut into the most slices that still fit one workgroup
+    // per CU and leave >= 8 k-tiles per slice (3152 x 768 x 3072: 35 us on the tiles below -> 3 slices of 234 tiles).
+    if (p != PREC_F32 && M >= 1024 && N % 128 == 0) {
+        const long t128 = (long)((M + 255) / 256) * (N / 128);
+        if (t128 >= 96) return 1;
+        int pick = 1;
+        for (int c : {2, 3, 4}) {
+            if (K % (c * 64) != 0 || K / c < 8 * 64) continue;
+            if (t128 * c <= 256) pick = c;
+        }
+        // Beside other queues' launches (vitvs_set_option "in_flight"), from ~2000 rows on, a third slice costs more in partial sums
+        // (residual_ln is at the HBM rate there and does not overlap with anything) than it gains in fill: three in flight, same
+        // box, 8 / 6 pairs 9108 -> 9578 / 8640 -> 9105 updates/s with two; 4 pairs (1576 rows, 4 slices) 7610 -> 7248: not there.
+        if (hint >= 2 && pick > 2 && M >= 2048) pick = 2;
+        if (pick > 1) return pick;
+    }
+    // The most K slices that still put at most one workgroup on every CU (each slice >= 4 k-tiles);
+    // none if the tiles alone already cover the chip.
+    const long tiles = (long)((M + 63) / 64) * (N / 64);
+    int best = 1;
+    for (int c : {2, 3, 4, 6, 8}) {
+        if ((K % (c * bk)) != 0 || K / c < 4 * bk) continue;
+        if (tiles * c <= 256) best = c;
+    }
+    // Beside other queues' launches (vitvs_set_option "in_flight") the chip is filled by THEIR workgroups: a third K slice
+    // only adds partial sums for residual_ln to read (ViT-B/16 224², 4 in flight, same box: 3946 -> 4075 updates/s with 2; ONE slice:
+    // 4301-4348 -> 4045-4091, round 5 — 84 workgroups with 48 k-tiles each are too long a chain; THREE slices again with four clean
+    // queues: 4818-4841 -> 4420-4464).
+    if (hint >= 2 && best > 2) best = 2;
+    return best;
+}
+
+struct TileShape {
+    int rows = 0, cols = 0;
+};
+
+// Which tile of gemm_big.hip for a many-row problem, or none (rows = 0: the tiles of gemm.hip).  Measured on MI355X
+// (tools/big_ops [mid], random bf16 data, profiles/r02_big_ops*.txt): in its k-loop the 256x256 tile sustains ~1.5 PFLOP/s
+// chip-wide, so what decides is how many tiles the busiest CU walks (workgroups are persistent, one per CU) and the fixed cost
+// per tile (operand latency at the start, the output burst at the end: ~8 us at 6274 x 2304) — the rule below is that model
+// with the relative tile costs measured.
+static TileShape big_tile(Precision p, int M, int N, int K, int splits, bool partial, int hint) {
+    if (p == PREC_F32 || splits < 1) return {};
+    // f16x2 runs the same kernels on rows of 2 K fp16 (a k-tile = 32 logical k, three MFMAs per k-step): the tile rule below is
+    // about rows, columns and rounds of workgroups, which do not change; only the k-tile count does
+    const int kt = (p == PREC_X2 ? 2 : 1) * K;
+    if (kt % (splits * 64) || kt / splits < 128 || kt / splits / 64 > 255) return {};
+    // The 64-row tiles of gemm.hip keep the layers they cover in ONE round of <= 256 workgroups (788 x 2304: 7.9 us there,
+    // 11.9 us on 256 x 128 tiles); where they need a second round the 256-row tiles win from 64 tiles up (985 x 2304: 18.4 vs
+    // 11.9 us).  Between the tile families of gemm_big.hip the busiest CU's share decides (below).
+    const long mt = (M + 63) / 64;
+    for (int c : {128, 96, 64}) {
+        if (partial && c != 64) continue;                         // the partial-sum kernels of gemm.hip are 64 wide
+        if (N % c == 0 && mt * (N / c) * splits <= 256) return {};
+    }
+    // A little over one workgroup per CU, the 64 x 128 tiles of gemm.hip on their 2-stage ring (48 KB: three resident per CU, so
+    // still one round) are ahead of every tile of gemm_big.hip: 788 x 3072 x 768 (312 workgroups) 11.4-12.5 us against 13.3 on
+    // 192 x 128 tiles, 985 x 2304 (288) 11.3 / 11.8; end to end +1.6 % at 2 frame pairs.  From ~340 workgroups on the forward
+    // does not gain (3 pairs, qkv 1182 x 2304: -0.4 % end to end although 11.7 / 11.8 us alone), so the rule stops at 320.
+    if (!partial && splits == 1 && N % 128 == 0 && mt * (N / 128) <= 320) return {};
+    const long ny = (M + 255) / 256;
+    if (N % 128 != 0 || N / 128 > 255) return {};
+    const long t128 = ny * (N / 128) * splits;
+    if (t128 < (partial ? 96 : 64)) return {};
+    // relative cost of one tile (k-loop share + the same fixed cost): 256 x 256 = 1, 256 x 192 = 0.85, 256 x 128 = 0.62
+    // (3152 x 3072: 156 tiles of 256 x 256 25.1 us, 208 of 256 x 192 21.4 us, 312 of 256 x 128 29.6 us;
+    //  6274 x 3072: 300 -> 51.6, 400 -> 41.9, 600 -> 44.6 us; 2740 x 3072 x 1024: 132 -> 23.9, 176 -> 20.6, 264 -> 30.3 us)
+    auto rounds = [](long tiles) { return (double)((tiles + 255) / 256); };
+    TileShape best{256, 128};
+    double cost = 0.62 * rounds(t128);
+    if (N % 192 == 0 && 0.85 * rounds(ny * (N / 192) * splits) < cost) { best = {256, 192}; cost = 0.85 * rounds(ny * (N / 192) * splits); }
+    if (N % 256 == 0 && rounds(ny * (N / 256) * splits) < cost) { best = {256, 256}; cost = rounds(ny * (N / 256) * splits); }
+    // 192-row x 128-column tiles: more, smaller tiles for the narrow layers — 6274 x 768 x 3072: 198 tiles 34.8 us against 150
+    // of 256 x 128 37.4 us; 2740 x 1024 x 4096 in 2 K slices: 240 tiles 25.7 us against 176 -> 27.8 us; a tile costs 0.58 (its
+    // waves' 96 x 32 sub-tiles read more LDS per FLOP than 64 x 64 ones, so it only pays while it stays in one round where
+    // 256 x 128 leaves CUs idle: 3152 x 768 x 3072 in 3 slices, 306 tiles, 27.5 us against 234 -> 19.3 us)
+    const long t192 = (long)((M + 191) / 192) * (N / 128) * splits;
+    // (also ahead on wide layers while in one round: 788 .. 1576 x 3072: 13.2 .. 14.1 us against 14.8 .. 15.7; two rounds from
+    //  1970 rows on: 24.8 against 16.2 us)
+    if (0.58 * rounds(t192) < cost) { best = {192, 128}; cost = 0.58 * rounds(t192); }
+    // 192 x 256, priced 0.9: 2740 x 4096 x 1024 (N is not a multiple of 192): 240 tiles 27.6 us against 176 of 256 x 256
+    // -> 29.8 us; level with 256 x 192 where that applies (3152 x 3072: 21.7 / 21.6 us)
+    if (N % 256 == 0 && 0.9 * rounds((long)((M + 191) / 192) * (N / 256) * splits) < cost) best = {192, 256};
+    // Everything above balances ONE launch over the chip.  Beside other queues' launches (vitvs_set_option "in_flight") the
+    // other queues' workgroups fill what a launch leaves idle, and the tile with the fewest operand bytes per FLOP wins: three
+    // updates in flight, same box, 256 x 256 for every layer it divides: 8 / 6 / 4 pairs 8607 -> 9249 / 7980 -> 8730 / 7385 -> 7760
+    // updates/s, ViT-B/8 448² 438 -> 460, ViT-L/14 518² 731 -> 793 (3 pairs, 1182 rows = 4.6 row tiles: 6787 -> 6664, hence the bound).
+    if (hint >= 2 && N % 256 == 0 && M >= 1536) best = {256, 256};
+    return best;
+}
+
+// Many-row problems (many frame pairs, 448² / 518² inputs): 128x128 tiles halve the LDS and L2 bytes per MFMA.
+static bool big_problem(int M, int N, int splits) {
+    // >= 256 tiles: with 2 workgroups per CU that is one round on every CU or more (measured: 294 tiles -12 %, 176 tiles
+    // +37 % against 64x64 tiles)
+    return splits == 1 && (N % 128) == 0 && (long)((M + 127) / 128) * (N / 128) >= 256;
+}
+
+// 64-row tiles.  In the one-frame-pair regime a launch cannot fill the chip, and a second wave of
 // workgroups costs more than bigger tiles save (measured: 336 workgroups of 64x64 ran 2.4 us longer than
 // 252), so: the column-tile width with the MOST workgroups that still fit the 256 CUs; if even the
 // widest tile needs more than 256 workgroups the problem is large and the widest tile wins.  Two
@@ -280,7 +365,7 @@ static bool shapes_ok(Precision p, int M, int N, int K) {
 struct TilePlan {
     int bn, kg;
 };
-static TilePlan plan_tiles(int M, int N, int nk_per_slice, int splits, bool fixed64) {
+static TilePlan plan_tiles(int M, int N, int nk_per_slice, int splits, bool fixed64, int hint) {
     const long mt = (M + 63) / 64;
     int bn = 64;
     if (!fixed64) {
@@ -302,53 +387,8 @@ static TilePlan plan_tiles(int M, int N, int nk_per_slice, int splits, bool fixe
     // keeps a second launch's workgroups off the CU until the first has left; 4-wave workgroups (64-80 KB) let two launches
     // share it: ViT-B/16 224², 3 updates in flight 3113 -> 3392 updates/s, but 2220 -> 2078 on one stream (same box,
     // profiles/r03_notes.md section 5), hence by the caller's hint and not by default.
-    int kg = (g_updates_in_flight < 2 && wgs <= 256 && nk_per_slice >= 4 && nk_per_slice % 2 == 0) ? 2 : 1;
+    int kg = (hint < 2 && wgs <= 256 && nk_per_slice >= 4 && nk_per_slice % 2 == 0) ? 2 : 1;
     return TilePlan{bn, kg};
-}
-
-struct EpiArgs {   // host image of the flat epilogue arguments
-    void* out;
-    const float* c0;
-    const float* c1;
-    int i0;
-    int wexp = 0;   // f16x2: the weights carry 2^wexp (linear_kernel)
-};
-
-// The XCD map (linear_kernel) is for the partial-sum launches only (their i0 field is unused, bit 16 of the packed argument is free)
-template <class Epi> constexpr bool xcd_mapped() { return false; }
-template <> constexpr bool xcd_mapped<EpiPartial>() { return true; }
-static bool want_xcd_map() {
-    // Beside other queues' launches the narrow layers are bound by what their private L2s fetch, not by latency (fc2 at three
-    // queues 4.48 -> 3.67 us per launch, 3932 -> 4072 updates/s); alone, XCD balance comes first (round 1: the map lost).
-    // (A column-class map for the one-slice launches — qkv's 36 column tiles over 8 XCDs — lost: 3.13 -> 3.37 us.)
-    return g_updates_in_flight >= 2;
-}
-
-static bool want_staged_epilogue(int kg) {
-    // 4-wave workgroups: measured faster alone and side by side (qkv 6.00 -> 5.11 us alone, 3.07 -> 2.81 at three queues; fc1
-    // 8.62 -> 7.16, 3.99 -> 3.39; 2 pairs +3 % on one stream and +10 % with three updates in flight; never slower)
-    // 8-wave workgroups (two k-groups, the one-stream plan): +1.4 % updates/s on one stream (2202 -> 2233, three interleaved rounds)
-    return true;
-}
-
-template <typename T, int BN, int KG, class Epi, int BM = 64, int NS = 0>
-static int launch_one(const T* A, const T* W, int M, int N, int K, const EpiArgs& e, hipStream_t stream, int splits) {
-    using Tile = GemmTile<BM, BN, KG, NS>;
-    static std::atomic<unsigned long long> raised{0};   // > 64 KiB of dynamic LDS needs the opt-in attribute, per device
-    if (raise_lds_limit(reinterpret_cast<const void*>(&linear_kernel<T, BM, BN, KG, Epi, NS>), Tile::LDS_BYTES, raised)) return -1;
-    dim3 grid(N / BN, (M + BM - 1) / BM, splits);
-    constexpr int KU = 128 / (int)sizeof(T);   // elements per k-tile (f16x2: K counts fp16, two per logical k)
-    const int kslice = K / splits;
-    if (kslice % KU != 0 || kslice / KU > 255 || splits > 15 || e.i0 < 0 || e.i0 > 0xffff || e.wexp < 0 || e.wexp > 31) return -2;
-    unsigned xcd_map = 0;
-    if (xcd_mapped<Epi>() && splits == 2 && (N / BN) % 4 == 0 && want_xcd_map()) {
-        grid = dim3(grid.x * grid.y * 2, 1, 1);
-        xcd_map = 1u << 16;
-    }
-    if (BM == 64 && want_staged_epilogue(KG)) xcd_map |= 1u << 18;
-    launch(linear_kernel<T, BM, BN, KG, Epi, NS>, grid, dim3(Tile::THREADS), Tile::LDS_BYTES, stream, A, W, e.out, e.c0, e.c1,
-           M, N, K, (int)(((unsigned)(kslice / KU) << 24) | ((unsigned)e.wexp << 19) | xcd_map | (unsigned)e.i0));
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // Ring depth of a one-k-group 64-row launch.  Up to one workgroup per CU the deep ring (4 stages) hides the operand latency
@@ -367,168 +407,118 @@ static int ring_stages(int bn, long wgs) {
     return wgs <= 512 ? 3 : 2;
 }
 
-// Many-row problems (many frame pairs, 448² / 518² inputs): 128x128 tiles halve the LDS and L2 bytes per MFMA.
-static bool big_problem(int M, int N, int splits) {
-    // >= 256 tiles: with 2 workgroups per CU that is one round on every CU or more (measured: 294 tiles -12 %, 176 tiles
-    // +37 % against 64x64 tiles)
-    return splits == 1 && (N % 128) == 0 && (long)((M + 127) / 128) * (N / 128) >= 256;
+LinearPlan plan_linear(Precision p, int M, int N, int K, LinearEpi epi, int splits, bool big_family, int rows, int cols) {
+    const int hint = g_updates_in_flight;
+    LinearPlan pl;
+    pl.prec = p; pl.epi = epi; pl.M = M; pl.N = N; pl.K = K;
+    const bool partial = epi == EPI_PARTIAL;
+    pl.splits = !partial ? 1 : splits > 0 ? splits : splitk_slices(p, M, N, K, hint);
+    const int s = pl.splits;
+    if (!shapes_ok(p, M, N, K) || (K % (s * k_tile(p))) != 0) return pl;
+    // (the residual epilogue never takes the tiles of gemm_big.hip: it has no kernel there)
+    const TileShape big = rows || !big_family || epi == EPI_RESIDUAL ? TileShape{} : big_tile(p, M, N, K, s, partial, hint);
+    if (rows) {   // a forced tile
+        const bool known = rows == 128 ? cols == 128 && plain16(p)
+                                       : p != PREC_F32 && (rows == 256 ? cols == 256 || cols == 192 || cols == 128
+                                                                       : rows == 192 && (cols == 256 || cols == 128));
+        if (!known || N % cols) return pl;
+        pl.big = rows != 128;
+        pl.rows = rows; pl.cols = cols;
+    } else if (big.rows) {
+        pl.big = true;
+        pl.rows = big.rows; pl.cols = big.cols;
+    } else if (big_problem(M, N, s)) {
+        pl.rows = pl.cols = 128;
+    } else {   // the partial sums and the residual epilogue are 64 wide (fewer instantiations)
+        const TilePlan tp = plan_tiles(M, N, K / s / k_tile(p), s, epi != EPI_STORE, hint);
+        pl.rows = 64; pl.cols = tp.bn; pl.kgroups = tp.kg;
+        if (tp.kg == 1) pl.stages = ring_stages(tp.bn, (long)((M + 63) / 64) * (N / tp.bn) * s);
+    }
+    // The XCD map (linear_kernel) is for the two-slice partial-sum launches only (their i0 field is unused, bit 16 of the packed
+    // argument is free).  Beside other queues' launches the narrow layers are bound by what their private L2s fetch, not by
+    // latency (fc2 at three queues 4.48 -> 3.67 us per launch, 3932 -> 4072 updates/s); alone, XCD balance comes first (round 1:
+    // the map lost).  (A column-class map for the one-slice launches — qkv's 36 column tiles over 8 XCDs — lost: 3.13 -> 3.37 us.)
+    pl.xcd_map = !pl.big && partial && s == 2 && (N / pl.cols) % 4 == 0 && hint >= 2;
+    return pl;
 }
 
+// ---------------------------------------------------------------------------------------------------- the launch
+struct EpiArgs {   // host image of the flat epilogue arguments
+    void* out;
+    const float* c0;
+    const float* c1;
+    int i0;
+    int wexp = 0;   // f16x2: the weights carry 2^wexp (linear_kernel)
+};
+
+template <typename T, int BN, int KG, class Epi, int BM = 64, int NS = 0>
+static int launch_one(const LinearPlan& pl, const T* A, const T* W, int K, const EpiArgs& e, hipStream_t stream) {
+    using Tile = GemmTile<BM, BN, KG, NS>;
+    static std::atomic<unsigned long long> raised{0};   // > 64 KiB of dynamic LDS needs the opt-in attribute, per device
+    if (raise_lds_limit(reinterpret_cast<const void*>(&linear_kernel<T, BM, BN, KG, Epi, NS>), Tile::LDS_BYTES, raised)) return -1;
+    const int M = pl.M, N = pl.N, splits = pl.splits;
+    dim3 grid(N / BN, (M + BM - 1) / BM, splits);
+    constexpr int KU = 128 / (int)sizeof(T);   // elements per k-tile (f16x2: K counts fp16, two per logical k)
+    const int kslice = K / splits;
+    if (kslice % KU != 0 || kslice / KU > 255 || splits > 15 || e.i0 < 0 || e.i0 > 0xffff || e.wexp < 0 || e.wexp > 31) return -2;
+    // Staged epilogue, always on for 64-row tiles.  4-wave workgroups: measured faster alone and side by side (qkv 6.00 -> 5.11
+    // us alone, 3.07 -> 2.81 at three queues; fc1 8.62 -> 7.16, 3.99 -> 3.39; 2 pairs +3 % on one stream and +10 % with three
+    // updates in flight; never slower).  8-wave workgroups (two k-groups, the one-stream plan): +1.4 % updates/s on one stream
+    // (2202 -> 2233, three interleaved rounds).
+    unsigned flags = BM == 64 ? 1u << 18 : 0u;
+    if (pl.xcd_map) {
+        grid = dim3(grid.x * grid.y * 2, 1, 1);
+        flags |= 1u << 16;
+    }
+    launch(linear_kernel<T, BM, BN, KG, Epi, NS>, grid, dim3(Tile::THREADS), Tile::LDS_BYTES, stream, A, W, e.out, e.c0, e.c1,
+           M, N, K, (int)(((unsigned)(kslice / KU) << 24) | ((unsigned)e.wexp << 19) | flags | (unsigned)e.i0));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <typename T, int BN, class Epi>
+static int launch_ring(const LinearPlan& pl, const T* A, const T* W, int K, const EpiArgs& e, hipStream_t stream) {
+    if (pl.kgroups == 2) return launch_one<T, BN, 2, Epi>(pl, A, W, K, e, stream);
+    if constexpr (BN != 96) {   // (96 columns are picked only where they cover the layer in one round: the default ring)
+        if (pl.stages == 3) return launch_one<T, BN, 1, Epi, 64, 3>(pl, A, W, K, e, stream);
+        if (pl.stages == 2) return launch_one<T, BN, 1, Epi, 64, 2>(pl, A, W, K, e, stream);
+    }
+    return launch_one<T, BN, 1, Epi>(pl, A, W, K, e, stream);
+}
+
+// 128 x 128 for every epilogue; 64 rows by 64 columns for every epilogue, by 96 / 128 for the store only
 template <typename T, class Epi>
-static int launch_64wide(const T* A, const T* W, int M, int N, int K, const EpiArgs& epi, hipStream_t stream, int splits, int kg,
-                         int ns) {
-    if (kg == 2) return launch_one<T, 64, 2, Epi>(A, W, M, N, K, epi, stream, splits);
-    if (ns == 3) return launch_one<T, 64, 1, Epi, 64, 3>(A, W, M, N, K, epi, stream, splits);
-    if (ns == 2) return launch_one<T, 64, 1, Epi, 64, 2>(A, W, M, N, K, epi, stream, splits);
-    return launch_one<T, 64, 1, Epi>(A, W, M, N, K, epi, stream, splits);
-}
-
-template <typename T, class Epi>
-static int launch_tiles(const T* A, const T* W, int M, int N, int K, const EpiArgs& epi, hipStream_t stream,
-                        int splits = 1, bool fixed64 = false) {
-    const int bk = 128 / (int)sizeof(T);
-    if (big_problem(M, N, splits)) return launch_one<T, 128, 1, Epi, 128>(A, W, M, N, K, epi, stream, splits);
-    const TilePlan pl = plan_tiles(M, N, K / splits / bk, splits, fixed64);
-    int ns = pl.kg == 1 ? ring_stages(pl.bn, (long)((M + 63) / 64) * (N / pl.bn) * splits) : 0;
-    if (pl.bn == 128) {
-        if (pl.kg == 2) return launch_one<T, 128, 2, Epi>(A, W, M, N, K, epi, stream, splits);
-        if (ns == 2) return launch_one<T, 128, 1, Epi, 64, 2>(A, W, M, N, K, epi, stream, splits);
-        if (ns == 3) return launch_one<T, 128, 1, Epi, 64, 3>(A, W, M, N, K, epi, stream, splits);
-        return launch_one<T, 128, 1, Epi>(A, W, M, N, K, epi, stream, splits);
+static int launch_tile(const LinearPlan& pl, const T* A, const T* W, int K, const EpiArgs& e, hipStream_t stream) {
+    if (pl.rows == 128 && pl.cols == 128) return launch_one<T, 128, 1, Epi, 128>(pl, A, W, K, e, stream);
+    if (pl.rows != 64) return -2;
+    if (pl.cols == 64) return launch_ring<T, 64, Epi>(pl, A, W, K, e, stream);
+    if constexpr (std::is_same<Epi, EpiStore<T>>::value) {
+        if (pl.cols == 96) return launch_ring<T, 96, Epi>(pl, A, W, K, e, stream);
+        if (pl.cols == 128) return launch_ring<T, 128, Epi>(pl, A, W, K, e, stream);
     }
-    if (pl.bn == 96) {
-        if (pl.kg == 2) return launch_one<T, 96, 2, Epi>(A, W, M, N, K, epi, stream, splits);
-        return launch_one<T, 96, 1, Epi>(A, W, M, N, K, epi, stream, splits);
+    return -2;
+}
+
+template <typename T>
+static int launch_typed(const LinearPlan& pl, const T* A, const T* W, const float* bias, const float* ls, void* out, int K,
+                        int gelu, hipStream_t stream, int wexp) {
+    if (pl.big) {
+        if constexpr (std::is_same<T, float>::value) return -2;
+        else return launch_linear_big<T>(pl, A, W, bias, out, K, gelu, stream, wexp);
     }
-    return launch_64wide<T, Epi>(A, W, M, N, K, epi, stream, splits, pl.kg, ns);
+    if (pl.epi == EPI_PARTIAL) return launch_tile<T, EpiPartial>(pl, A, W, K, EpiArgs{out, nullptr, nullptr, 0, wexp}, stream);
+    if (pl.epi == EPI_RESIDUAL) return launch_tile<T, EpiResidual>(pl, A, W, K, EpiArgs{out, bias, ls, 0, wexp}, stream);
+    return launch_tile<T, EpiStore<T>>(pl, A, W, K, EpiArgs{out, bias, nullptr, gelu, wexp}, stream);
 }
 
-// narrow layers / patch embed: 64-wide tiles only (keeps the number of instantiations down)
-template <typename T, class Epi>
-static int launch_tiles64(const T* A, const T* W, int M, int N, int K, const EpiArgs& epi, hipStream_t stream,
-                          int splits = 1) {
-    const int bk = 128 / (int)sizeof(T);
-    if (big_problem(M, N, splits)) return launch_one<T, 128, 1, Epi, 128>(A, W, M, N, K, epi, stream, splits);
-    const TilePlan pl = plan_tiles(M, N, K / splits / bk, splits, true);
-    const int ns = pl.kg == 1 ? ring_stages(64, (long)((M + 63) / 64) * (N / 64) * splits) : 0;
-    return launch_64wide<T, Epi>(A, W, M, N, K, epi, stream, splits, pl.kg, ns);
-}
-
-int launch_linear(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                  int gelu, hipStream_t stream, int wexp) {
-    if (!shapes_ok(p, M, N, K)) return -2;
-    if (const int bn = big_tile_width(p, M, N, K, 1, false)) return launch_linear_big(p, bn, A, W, bias, out, M, N, K, 1, gelu, false, stream, wexp);
-    return launch_linear_classic(p, A, W, bias, out, M, N, K, gelu, stream, wexp);
-}
-
-int launch_linear_classic(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                          int gelu, hipStream_t stream, int wexp) {
-    if (!shapes_ok(p, M, N, K)) return -2;
-    const EpiArgs e{out, bias, nullptr, gelu, p == PREC_X2 ? wexp : 0};
-    if (p == PREC_X2) return launch_tiles<hx2, EpiStore<hx2>>((const hx2*)A, (const hx2*)W, M, N, 2 * K, e, stream);
-    if (p == PREC_F32) return launch_tiles<float, EpiStore<float>>((const float*)A, (const float*)W, M, N, K, e, stream);
-    if (p == PREC_F16) return launch_tiles<f16, EpiStore<f16>>((const f16*)A, (const f16*)W, M, N, K, e, stream);
-    return launch_tiles<bf16, EpiStore<bf16>>((const bf16*)A, (const bf16*)W, M, N, K, e, stream);
-}
-
-// experiments (vitvs_op_linear_variant 2): the 128 x 128 tiles of this file whatever the shape
-int launch_linear_128(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int gelu,
-                      int splits, bool partial, hipStream_t stream) {
-    if (!shapes_ok(p, M, N, K) || N % 128 != 0 || !plain16(p)) return -2;
-    if (partial) {
-        const EpiArgs e{out, nullptr, nullptr, 0};
-        if (p == PREC_F16) return launch_one<f16, 128, 1, EpiPartial, 128>((const f16*)A, (const f16*)W, M, N, K, e, stream, splits);
-        return launch_one<bf16, 128, 1, EpiPartial, 128>((const bf16*)A, (const bf16*)W, M, N, K, e, stream, splits);
+int launch_linear(const LinearPlan& pl, const void* A, const void* W, const float* bias, void* out, int gelu,
+                  hipStream_t stream, int wexp, const float* ls) {
+    if (!pl.rows) return -2;
+    switch (pl.prec) {
+    case PREC_X2: return launch_typed(pl, (const hx2*)A, (const hx2*)W, bias, ls, out, 2 * pl.K, gelu, stream, wexp);
+    case PREC_F32: return launch_typed(pl, (const float*)A, (const float*)W, bias, ls, out, pl.K, gelu, stream, 0);
+    case PREC_F16: return launch_typed(pl, (const f16*)A, (const f16*)W, bias, ls, out, pl.K, gelu, stream, 0);
+    default: return launch_typed(pl, (const bf16*)A, (const bf16*)W, bias, ls, out, pl.K, gelu, stream, 0);
     }
-    const EpiArgs e{out, bias, nullptr, gelu};
-    if (p == PREC_F16) return launch_one<f16, 128, 1, EpiStore<f16>, 128>((const f16*)A, (const f16*)W, M, N, K, e, stream, 1);
-    return launch_one<bf16, 128, 1, EpiStore<bf16>, 128>((const bf16*)A, (const bf16*)W, M, N, K, e, stream, 1);
-}
-
-int launch_linear_residual(Precision p, const void* A, const void* W, const float* bias, const float* ls, float* x,
-                           int M, int N, int K, hipStream_t stream, int wexp) {
-    if (!shapes_ok(p, M, N, K)) return -2;
-    const EpiArgs e{x, bias, ls, 0, p == PREC_X2 ? wexp : 0};
-    if (p == PREC_X2) return launch_tiles64<hx2, EpiResidual>((const hx2*)A, (const hx2*)W, M, N, 2 * K, e, stream);
-    if (p == PREC_F32) return launch_tiles64<float, EpiResidual>((const float*)A, (const float*)W, M, N, K, e, stream);
-    if (p == PREC_F16) return launch_tiles64<f16, EpiResidual>((const f16*)A, (const f16*)W, M, N, K, e, stream);
-    return launch_tiles64<bf16, EpiResidual>((const bf16*)A, (const bf16*)W, M, N, K, e, stream);
-}
-
-int splitk_slices(Precision p, int M, int N, int K) {
-    const int bk = k_tile(p);
-    // Many rows, narrow layer (8 frame pairs or a 518² input through proj / fc2): the 256x128 tiles of gemm_big.hip fill
-    // well under half of the chip (78 tiles at 3152 x 768), so K is cut into the most slices that still fit one workgroup
-    // per CU and leave >= 8 k-tiles per slice (3152 x 768 x 3072: 35 us on the tiles below -> 3 slices of 234 tiles).
-    if (p != PREC_F32 && M >= 1024 && N % 128 == 0) {
-        const long t128 = (long)((M + 255) / 256) * (N / 128);
-        if (t128 >= 96) return 1;
-        int pick = 1;
-        for (int c : {2, 3, 4}) {
-            if (K % (c * 64) != 0 || K / c < 8 * 64) continue;
-            if (t128 * c <= 256) pick = c;
-        }
-        // Beside other queues' launches (vitvs_set_option "in_flight"), from ~2000 rows on, a third slice costs more in partial sums
-        // (residual_ln is at the HBM rate there and does not overlap with anything) than it gains in fill: three in flight, same
-        // box, 8 / 6 pairs 9108 -> 9578 / 8640 -> 9105 updates/s with two; 4 pairs (1576 rows, 4 slices) 7610 -> 7248: not there.
-        if (g_updates_in_flight >= 2 && pick > 2 && M >= 2048) pick = 2;
-        if (pick > 1) return pick;
-    }
-    // The most K slices that still put at most one workgroup on every CU (each slice >= 4 k-tiles);
-    // none if the tiles alone already cover the chip.
-    const long tiles = (long)((M + 63) / 64) * (N / 64);
-    int best = 1;
-    for (int c : {2, 3, 4, 6, 8}) {
-        if ((K % (c * bk)) != 0 || K / c < 4 * bk) continue;
-        if (tiles * c <= 256) best = c;
-    }
-    // Beside other queues' launches (vitvs_set_option "in_flight") the chip is filled by THEIR workgroups: a third K slice
-    // only adds partial sums for residual_ln to read (ViT-B/16 224², 4 in flight, same box: 3946 -> 4075 updates/s with 2; ONE slice:
-    // 4301-4348 -> 4045-4091, round 5 — 84 workgroups with 48 k-tiles each are too long a chain; THREE slices again with four clean
-    // queues: 4818-4841 -> 4420-4464).
-    if (g_updates_in_flight >= 2 && best > 2) best = 2;
-    return best;
-}
-
-int launch_linear_partial(Precision p, const void* A, const void* W, float* part, int M, int N, int K, int splits,
-                          hipStream_t stream, int wexp) {
-    if (!shapes_ok(p, M, N, K) || splits < 1 || (K % (splits * k_tile(p))) != 0) return -2;
-    if (const int bn = big_tile_width(p, M, N, K, splits, true))
-        return launch_linear_big(p, bn, A, W, nullptr, part, M, N, K, splits, 0, true, stream, wexp);
-    return launch_linear_partial_classic(p, A, W, part, M, N, K, splits, stream, wexp);
-}
-
-int launch_linear_partial_classic(Precision p, const void* A, const void* W, float* part, int M, int N, int K, int splits,
-                                  hipStream_t stream, int wexp) {
-    if (!shapes_ok(p, M, N, K) || splits < 1 || (K % (splits * k_tile(p))) != 0) return -2;
-    const EpiArgs e{part, nullptr, nullptr, 0, p == PREC_X2 ? wexp : 0};
-    if (p == PREC_X2) return launch_tiles64<hx2, EpiPartial>((const hx2*)A, (const hx2*)W, M, N, 2 * K, e, stream, splits);
-    if (p == PREC_F32) return launch_tiles64<float, EpiPartial>((const float*)A, (const float*)W, M, N, K, e, stream, splits);
-    if (p == PREC_F16) return launch_tiles64<f16, EpiPartial>((const f16*)A, (const f16*)W, M, N, K, e, stream, splits);
-    return launch_tiles64<bf16, EpiPartial>((const bf16*)A, (const bf16*)W, M, N, K, e, stream, splits);
-}
-
-int linear_tile_plan(Precision p, int M, int N, int K, int splits, bool partial, int out[3]) {
-    if (!shapes_ok(p, M, N, K) || splits < 1 || (K % (splits * k_tile(p))) != 0 || (!partial && splits != 1)) return -2;
-    if (const int bn = big_tile_width(p, M, N, K, splits, partial)) {
-        out[0] = bn > 1000 ? 192 : 256; out[1] = bn > 1000 ? bn - 1000 - 64 * (bn == 1192) : bn; out[2] = 0;   // 1192 -> 128, 1256 -> 256
-        return 0;
-    }
-    if (big_problem(M, N, splits)) { out[0] = 128; out[1] = 128; out[2] = 1; return 0; }
-    const TilePlan pl = plan_tiles(M, N, K / splits / k_tile(p), splits, partial);
-    out[0] = 64; out[1] = pl.bn; out[2] = pl.kg;
-    return 0;
-}
-
-int launch_patch_embed(Precision p, const void* Ape, const void* Wpe, const float* bias, const float* pos, float* x,
-                       int n_img, int T, int D, int Kp, hipStream_t stream, int wexp) {
-    const int M = n_img * T;
-    if (!shapes_ok(p, M, D, Kp)) return -2;
-    const EpiArgs e{x, bias, pos, T, p == PREC_X2 ? wexp : 0};
-    if (p == PREC_X2) return launch_tiles64<hx2, EpiPatch>((const hx2*)Ape, (const hx2*)Wpe, M, D, 2 * Kp, e, stream);
-    if (p == PREC_F32) return launch_tiles64<float, EpiPatch>((const float*)Ape, (const float*)Wpe, M, D, Kp, e, stream);
-    if (p == PREC_F16) return launch_tiles64<f16, EpiPatch>((const f16*)Ape, (const f16*)Wpe, M, D, Kp, e, stream);
-    return launch_tiles64<bf16, EpiPatch>((const bf16*)Ape, (const bf16*)Wpe, M, D, Kp, e, stream);
 }
 
 }  // namespace vitvs

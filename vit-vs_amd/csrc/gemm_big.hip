@@ -474,8 +474,8 @@ __global__ __launch_bounds__(512, 2) void linear_big_kernel(const T* __restrict_
 typedef BigTile<2, 4, 8, 4> Tile256x256;
 typedef BigTile<4, 2, 4, 4> Tile256x128;
 typedef BigTile<4, 2, 4, 6> Tile256x192;
-typedef BigTile<2, 4, 6, 2> Tile192x128;      // selected as width code 1192 (192 rows x 128 columns)
-typedef BigTile<2, 4, 6, 4> Tile192x256;      // width code 1256 (192 rows x 256 columns)
+typedef BigTile<2, 4, 6, 2> Tile192x128;
+typedef BigTile<2, 4, 6, 4> Tile192x256;
 
 template <typename T, class Tile, class Epi>
 static int launch_big_one(const T* A, const T* W, typename Epi::Out* out, const float* bias, int M, int N, int K, int splits,
@@ -508,89 +508,28 @@ static int launch_big_one(const T* A, const T* W, typename Epi::Out* out, const 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Which tile family for a many-row problem.  Measured on MI355X (tools/big_ops [mid], random bf16 data, profiles/r02_big_ops*.txt):
-// in its k-loop the 256x256 tile sustains ~1.5 PFLOP/s chip-wide, so what decides is how many tiles the busiest CU walks
-// (workgroups are persistent, one per CU) and the fixed cost per tile (operand latency at the start, the output burst at the
-// end: ~8 us at 6274 x 2304) — the rule below is that model with the relative tile costs measured.
-// Returns 0 (use gemm.hip), the column width 256, 192 or 128 of a 256-row tile, or 1192 / 1256 for the 192 x 128 / 192 x 256 tile.
-int big_tile_width(Precision p, int M, int N, int K, int splits, bool partial) {
-    if (p == PREC_F32 || splits < 1) return 0;
-    // f16x2 runs the same kernels on rows of 2 K fp16 (a k-tile = 32 logical k, three MFMAs per k-step): the tile rule below is
-    // about rows, columns and rounds of workgroups, which do not change; only the k-tile count does
-    const int kt = (p == PREC_X2 ? 2 : 1) * K;
-    if (kt % (splits * 64) || kt / splits < 128 || kt / splits / 64 > 255) return 0;
-    // The 64-row tiles of gemm.hip keep the layers they cover in ONE round of <= 256 workgroups (788 x 2304: 7.9 us there,
-    // 11.9 us on 256 x 128 tiles); where they need a second round the 256-row tiles win from 64 tiles up (985 x 2304: 18.4 vs
-    // 11.9 us).  Between the tile families of this file the busiest CU's share decides (below).
-    const long mt = (M + 63) / 64;
-    for (int c : {128, 96, 64}) {
-        if (partial && c != 64) continue;                         // the partial-sum kernels of gemm.hip are 64 wide
-        if (N % c == 0 && mt * (N / c) * splits <= 256) return 0;
-    }
-    // A little over one workgroup per CU, the 64 x 128 tiles of gemm.hip on their 2-stage ring (48 KB: three resident per CU, so
-    // still one round) are ahead of every tile of this file: 788 x 3072 x 768 (312 workgroups) 11.4-12.5 us against 13.3 on
-    // 192 x 128 tiles, 985 x 2304 (288) 11.3 / 11.8; end to end +1.6 % at 2 frame pairs.  From ~340 workgroups on the forward
-    // does not gain (3 pairs, qkv 1182 x 2304: -0.4 % end to end although 11.7 / 11.8 us alone), so the rule stops at 320.
-    if (!partial && splits == 1 && N % 128 == 0 && mt * (N / 128) <= 320) return 0;
-    const long ny = (M + 255) / 256;
-    if (N % 128 != 0 || N / 128 > 255) return 0;
-    const long t128 = ny * (N / 128) * splits;
-    if (t128 < (partial ? 96 : 64)) return 0;
-    // relative cost of one tile (k-loop share + the same fixed cost): 256 x 256 = 1, 256 x 192 = 0.85, 256 x 128 = 0.62
-    // (3152 x 3072: 156 tiles of 256 x 256 25.1 us, 208 of 256 x 192 21.4 us, 312 of 256 x 128 29.6 us;
-    //  6274 x 3072: 300 -> 51.6, 400 -> 41.9, 600 -> 44.6 us; 2740 x 3072 x 1024: 132 -> 23.9, 176 -> 20.6, 264 -> 30.3 us)
-    auto rounds = [](long tiles) { return (double)((tiles + 255) / 256); };
-    int best = 128;
-    double cost = 0.62 * rounds(t128);
-    if (N % 192 == 0 && 0.85 * rounds(ny * (N / 192) * splits) < cost) { best = 192; cost = 0.85 * rounds(ny * (N / 192) * splits); }
-    if (N % 256 == 0 && rounds(ny * (N / 256) * splits) < cost) { best = 256; cost = rounds(ny * (N / 256) * splits); }
-    // 192-row x 128-column tiles (code 1192): more, smaller tiles for the narrow layers — 6274 x 768 x 3072: 198 tiles 34.8 us
-    // against 150 of 256 x 128 37.4 us; 2740 x 1024 x 4096 in 2 K slices: 240 tiles 25.7 us against 176 -> 27.8 us; a tile costs
-    // 0.58 (its waves' 96 x 32 sub-tiles read more LDS per FLOP than 64 x 64 ones, so it only pays while it stays in one round
-    // where 256 x 128 leaves CUs idle: 3152 x 768 x 3072 in 3 slices, 306 tiles, 27.5 us against 234 -> 19.3 us)
-    const long t1192 = (long)((M + 191) / 192) * (N / 128) * splits;
-    // (also ahead on wide layers while in one round: 788 .. 1576 x 3072: 13.2 .. 14.1 us against 14.8 .. 15.7; two rounds from
-    //  1970 rows on: 24.8 against 16.2 us)
-    if (0.58 * rounds(t1192) < cost) { best = 1192; cost = 0.58 * rounds(t1192); }
-    // 192 x 256 (code 1256), priced 0.9: 2740 x 4096 x 1024 (N is not a multiple of 192): 240 tiles 27.6 us against 176 of
-    // 256 x 256 -> 29.8 us; level with 256 x 192 where that applies (3152 x 3072: 21.7 / 21.6 us)
-    if (N % 256 == 0 && 0.9 * rounds((long)((M + 191) / 192) * (N / 256) * splits) < cost) best = 1256;
-    // Everything above balances ONE launch over the chip.  Beside other queues' launches (vitvs_set_option "in_flight") the
-    // other queues' workgroups fill what a launch leaves idle, and the tile with the fewest operand bytes per FLOP wins: three
-    // updates in flight, same box, 256 x 256 for every layer it divides: 8 / 6 / 4 pairs 8607 -> 9249 / 7980 -> 8730 / 7385 -> 7760
-    // updates/s, ViT-B/8 448² 438 -> 460, ViT-L/14 518² 731 -> 793 (3 pairs, 1182 rows = 4.6 row tiles: 6787 -> 6664, hence the bound).
-    if (g_updates_in_flight >= 2 && N % 256 == 0 && M >= 1536) best = 256;
-    return best;
-}
-
-template <typename T>
-static int launch_big_t(int bn, const T* A, const T* W, const float* bias, void* out, int M, int N, int K, int splits, int gelu,
-                        bool partial, hipStream_t stream, int wexp = 0) {
-    if (bn == 1256) {
-        if (partial) return launch_big_one<T, Tile192x256, BigPartial>(A, W, (float*)out, nullptr, M, N, K, splits, 0, stream, wexp);
-        return launch_big_one<T, Tile192x256, BigStore<T>>(A, W, (T*)out, bias, M, N, K, 1, gelu, stream, wexp);
-    }
-    if (bn == 1192) {
-        if (partial) return launch_big_one<T, Tile192x128, BigPartial>(A, W, (float*)out, nullptr, M, N, K, splits, 0, stream, wexp);
-        return launch_big_one<T, Tile192x128, BigStore<T>>(A, W, (T*)out, bias, M, N, K, 1, gelu, stream, wexp);
-    }
-    if (partial) {
-        if (bn == 256) return launch_big_one<T, Tile256x256, BigPartial>(A, W, (float*)out, nullptr, M, N, K, splits, 0, stream, wexp);
-        if (bn == 192) return launch_big_one<T, Tile256x192, BigPartial>(A, W, (float*)out, nullptr, M, N, K, splits, 0, stream, wexp);
-        return launch_big_one<T, Tile256x128, BigPartial>(A, W, (float*)out, nullptr, M, N, K, splits, 0, stream, wexp);
-    }
-    if (bn == 256) return launch_big_one<T, Tile256x256, BigStore<T>>(A, W, (T*)out, bias, M, N, K, 1, gelu, stream, wexp);
-    if (bn == 192) return launch_big_one<T, Tile256x192, BigStore<T>>(A, W, (T*)out, bias, M, N, K, 1, gelu, stream, wexp);
-    return launch_big_one<T, Tile256x128, BigStore<T>>(A, W, (T*)out, bias, M, N, K, 1, gelu, stream, wexp);
-}
-
-int launch_linear_big(Precision p, int bn, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                      int splits, int gelu, bool partial, hipStream_t stream, int wexp) {
-    if ((long long)M * K * (long long)elem_size(p) >= (1ll << 32) || (long long)N * K * (long long)elem_size(p) >= (1ll << 32)) return -2;   // 32-bit operand offsets
-    if (p == PREC_X2) return launch_big_t<hx2>(bn, (const hx2*)A, (const hx2*)W, bias, out, M, N, 2 * K, splits, gelu, partial, stream, wexp);
-    if (p == PREC_BF16) return launch_big_t<bf16>(bn, (const bf16*)A, (const bf16*)W, bias, out, M, N, K, splits, gelu, partial, stream);
-    if (p == PREC_F16) return launch_big_t<f16>(bn, (const f16*)A, (const f16*)W, bias, out, M, N, K, splits, gelu, partial, stream);
+template <typename T, class Epi>
+static int launch_big_tile(const LinearPlan& pl, const T* A, const T* W, typename Epi::Out* out, const float* bias, int K,
+                           int gelu, hipStream_t stream, int wexp) {
+    const int M = pl.M, N = pl.N, s = pl.splits;
+    if (pl.rows == 256 && pl.cols == 256) return launch_big_one<T, Tile256x256, Epi>(A, W, out, bias, M, N, K, s, gelu, stream, wexp);
+    if (pl.rows == 256 && pl.cols == 192) return launch_big_one<T, Tile256x192, Epi>(A, W, out, bias, M, N, K, s, gelu, stream, wexp);
+    if (pl.rows == 256 && pl.cols == 128) return launch_big_one<T, Tile256x128, Epi>(A, W, out, bias, M, N, K, s, gelu, stream, wexp);
+    if (pl.rows == 192 && pl.cols == 256) return launch_big_one<T, Tile192x256, Epi>(A, W, out, bias, M, N, K, s, gelu, stream, wexp);
+    if (pl.rows == 192 && pl.cols == 128) return launch_big_one<T, Tile192x128, Epi>(A, W, out, bias, M, N, K, s, gelu, stream, wexp);
     return -2;
 }
+
+// out[m][n] = act(sum + bias[n]) in the operand type (EPI_STORE) or fp32 part[z][m][n], z < splits (EPI_PARTIAL)
+template <typename T>
+int launch_linear_big(const LinearPlan& pl, const T* A, const T* W, const float* bias, void* out, int K, int gelu,
+                      hipStream_t stream, int wexp) {
+    if (pl.epi == EPI_PARTIAL) return launch_big_tile<T, BigPartial>(pl, A, W, (float*)out, nullptr, K, 0, stream, wexp);
+    if (pl.epi == EPI_STORE) return launch_big_tile<T, BigStore<T>>(pl, A, W, (T*)out, bias, K, gelu, stream, wexp);
+    return -2;
+}
+template int launch_linear_big<hx2>(const LinearPlan&, const hx2*, const hx2*, const float*, void*, int, int, hipStream_t, int);
+template int launch_linear_big<bf16>(const LinearPlan&, const bf16*, const bf16*, const float*, void*, int, int, hipStream_t, int);
+template int launch_linear_big<f16>(const LinearPlan&, const f16*, const f16*, const float*, void*, int, int, hipStream_t, int);
 
 }  // namespace vitvs

@@ -37,7 +37,7 @@ inline void launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stre
 }
 
 // Updates the calling handle expects to run beside its own (vitvs_set_option "in_flight"; set by api.hip around a handle's
-// launches, 1 otherwise).  From 2 on the one-round GEMM launches of gemm.hip use 4-wave workgroups (plan_tiles).
+// launches, 1 otherwise).  From 2 on the one-round GEMM launches of gemm.hip use 4-wave workgroups (plan_linear).
 extern thread_local int g_updates_in_flight;
 
 // The HIP device the calling thread's current entry point runs on (set by the C-ABI layer's DeviceScope; api.hip).
@@ -64,40 +64,38 @@ enum Precision : int { PREC_F32 = 0, PREC_BF16 = 1, PREC_F16 = 2, PREC_X2 = 3 };
 inline size_t elem_size(Precision p) { return (p == PREC_F32 || p == PREC_X2) ? 4 : 2; }   // bytes per LOGICAL element
 inline bool plain16(Precision p) { return p == PREC_BF16 || p == PREC_F16; }
 
-// ---- gemm.hip ------------------------------------------------------------------------------
-// out[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]); A, W, out in precision p; gelu: erf GELU.
+// ---- gemm.hip / gemm_big.hip: linear layers ----------------------------------------------------------
+//   EPI_STORE    out[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]); A, W, out in precision p; gelu: erf GELU.
+//   EPI_PARTIAL  split-K form for the narrow (N = D) layers: part[z][m][n] = sum over K slice z of A[m][k] W[n][k], fp32,
+//                z < splits; finished by launch_residual_ln / launch_embed_ln with the same slice count.
+//   EPI_RESIDUAL x[m][n] += ls[n] * (sum_k A[m][k] W[n][k] + bias[n]); x fp32 residual stream, ls may be null.
 // wexp (PREC_X2 only, 0 .. 31): W holds the weights times 2^wexp (so that their lo halves are normal fp16 numbers); the
 // kernel multiplies the sums by 2^-wexp before the epilogue.
-int launch_linear(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                  int gelu, hipStream_t stream, int wexp = 0);
-// the same two operators restricted to the tiles of gemm.hip (no hand-over to gemm_big.hip)
-int launch_linear_128(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int gelu,
-                      int splits, bool partial, hipStream_t stream);
-int launch_linear_classic(Precision p, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                          int gelu, hipStream_t stream, int wexp = 0);
-int launch_linear_partial_classic(Precision p, const void* A, const void* W, float* part, int M, int N, int K, int splits,
-                                  hipStream_t stream, int wexp = 0);
-// x[m][n] += ls[n] * (sum_k A[m][k] W[n][k] + bias[n]); x fp32 residual stream, ls may be null.
-int launch_linear_residual(Precision p, const void* A, const void* W, const float* bias, const float* ls, float* x,
-                           int M, int N, int K, hipStream_t stream, int wexp = 0);
-// Split-K form for the narrow (N = D) layers: part[z][m][n] = sum over K slice z of A[m][k] W[n][k], fp32,
-// z < splits (splitk_slices picks the count); finished by launch_residual_ln.
-int splitk_slices(Precision p, int M, int N, int K);
-int launch_linear_partial(Precision p, const void* A, const void* W, float* part, int M, int N, int K, int splits,
-                          hipStream_t stream, int wexp = 0);
-// x[img*(T+1) + 1 + t][n] = sum_k Ape[img*T + t][k] Wpe[n][k] + bias[n] + pos[1 + t][n]
-int launch_patch_embed(Precision p, const void* Ape, const void* Wpe, const float* bias, const float* pos, float* x,
-                       int n_img, int T, int D, int Kp, hipStream_t stream, int wexp = 0);
+enum LinearEpi : int { EPI_STORE = 0, EPI_PARTIAL = 1, EPI_RESIDUAL = 2 };
 
-// ---- gemm_big.hip: 256-row tiles for many-row problems (16-bit operands) --------------------------------
-// big_tile_width: 0 = not applicable (use the tiles of gemm.hip), else the tile code to pass on: the column width 256, 192 or 128 of a
-// 256-row tile, or 1192 = 192 rows x 128 columns.
-int big_tile_width(Precision p, int M, int N, int K, int splits, bool partial);
-// (BM, BN, KG) of the kernel launch_linear (partial = false, splits = 1) / launch_linear_partial picks; KG = 0: 256-row tiles
-int linear_tile_plan(Precision p, int M, int N, int K, int splits, bool partial, int out[3]);
-// partial = false: out[m][n] = act(sum + bias[n]) in precision p; partial = true: out = fp32 part[z][m][n], z < splits.
-int launch_linear_big(Precision p, int bn, const void* A, const void* W, const float* bias, void* out, int M, int N, int K,
-                      int splits, int gelu, bool partial, hipStream_t stream, int wexp = 0);
+// One linear layer's launch, decided by plan_linear and carried out by launch_linear.
+struct LinearPlan {
+    Precision prec = PREC_F32;
+    LinearEpi epi = EPI_STORE;
+    int M = 0, N = 0, K = 0;
+    bool big = false;       // the linear_big_kernel tiles of gemm_big.hip, else the linear_kernel tiles of gemm.hip
+    int rows = 0, cols = 0; // the tile; rows = 0: the shape cannot be launched
+    int kgroups = 1;        // linear_kernel: 1 or 2 k-groups of 4 waves
+    int stages = 0;         // linear_kernel, 64 rows, one k-group: ring stages (0: the tile's default)
+    int splits = 1;         // K slices (EPI_PARTIAL; set even when rows = 0)
+    bool xcd_map = false;   // linear_kernel: the XCD map of the two-slice partial-sum launches
+};
+// The plan under the calling thread's hint of updates in flight (g_updates_in_flight).  splits = 0: the library's slice count
+// (EPI_PARTIAL; the other epilogues have one slice).  big_family = false: the tiles of gemm.hip only.  rows, cols != 0: that tile
+// (128 x 128 of gemm.hip; 256 x 256 / 192 / 128 or 192 x 128 / 256 of gemm_big.hip) whatever the rule would pick.
+LinearPlan plan_linear(Precision p, int M, int N, int K, LinearEpi epi, int splits = 0, bool big_family = true, int rows = 0,
+                       int cols = 0);
+int launch_linear(const LinearPlan& plan, const void* A, const void* W, const float* bias, void* out, int gelu,
+                  hipStream_t stream, int wexp = 0, const float* ls = nullptr);
+// gemm_big.hip's part of launch_linear, for T = hx2 (K counts fp16 per row), bf16, f16
+template <typename T>
+int launch_linear_big(const LinearPlan& plan, const T* A, const T* W, const float* bias, void* out, int K, int gelu,
+                      hipStream_t stream, int wexp);
 
 // ---- elementwise.hip -----------------------------------------------------------------------
 struct PatchifyArgs {
@@ -140,7 +138,7 @@ struct DescOut {
 int launch_residual_ln(Precision p, float* x, const float* part, int splits, const float* bias, const float* ls,
                        const float* gamma, const float* beta, void* out, int M, int D, float eps, hipStream_t stream,
                        const DescOut* desc = nullptr);
-// Finishes a split-K patch embedding (partial rows [n_img][T], launch_linear_partial) and applies block 0's norm1:
+// Finishes a split-K patch embedding (partial rows [n_img][T], launch_linear EPI_PARTIAL) and applies block 0's norm1:
 //   x[img][0][:] = cls + pos[0];  x[img][1+t][:] = pos[1+t] + sum_z part[z][img*T+t][:] + bias;  out = LayerNorm(x).
 int launch_embed_ln(Precision p, float* x, const float* part, int splits, const float* bias, const float* pos,
                     const float* cls, const float* gamma, const float* beta, void* out, int n_img, int T, int D, float eps,
