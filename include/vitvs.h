@@ -94,6 +94,15 @@ typedef struct vitvs_config {
 /* --- lifetime --------------------------------------------------------------------------------
  * Replaces ViTExtractor(model_type, stride, model=...) + model.to(device) (dinov2_extractor.py:25-55). */
 VITVS_API int vitvs_create(const vitvs_config* cfg, vitvs_handle** out);
+/* The same for a network with register tokens (DINOv2 "_reg" models, Darcet et al. 2023: dinov2_vit{s,b,l}14_reg have 4).
+ * Every image's token rows are then [cls + pos[0], reg_0 .. reg_{R-1}, patch_t + pos[1 + t]] — the registers are inserted
+ * after the position embedding and carry none — so N = 1 + R + T rows go through every block.  The registers never enter a
+ * descriptor, the correspondence or the control law; pos_embed stays [1 + T][D].  register_tokens is 0 ..
+ * VITVS_MAX_REGISTER_TOKENS (checked before the device is touched); vitvs_create(cfg, out) is vitvs_create_ex(cfg, 0, out). */
+#define VITVS_MAX_REGISTER_TOKENS 16
+VITVS_API int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_handle** out);
+/* R of the handle (0 for vitvs_create), -1 for NULL. */
+VITVS_API int vitvs_register_tokens(const vitvs_handle* h);
 VITVS_API void vitvs_destroy(vitvs_handle* h);
 VITVS_API const char* vitvs_last_error(const vitvs_handle* h); /* h may be NULL: last creation error */
 VITVS_API int vitvs_abi_version(void);
@@ -102,7 +111,9 @@ VITVS_API int vitvs_abi_version(void);
  * Replaces model.load_state_dict (dinov2_extractor.py:79-82).  `name` is the DINO/timm/DINOv2
  * state-dict key (patch_embed.proj.weight, cls_token, pos_embed — already resampled to the token
  * grid, shape [1+T][D] —, blocks.{i}.norm1.weight, ... , blocks.{i}.ls2.gamma); `data` is fp32 on
- * the host.  vitvs_weights_ready returns 0 when every tensor the forward reads has been set. */
+ * the host.  vitvs_weights_ready returns 0 when every tensor the forward reads has been set.  A handle with R > 0 register
+ * tokens (vitvs_create_ex) also needs "register_tokens", R * D elements; a wrong count, or the name on a handle with R == 0,
+ * is error -5. */
 VITVS_API int vitvs_set_tensor(vitvs_handle* h, const char* name, const float* data, int64_t numel);
 VITVS_API int vitvs_weights_ready(const vitvs_handle* h);
 
@@ -189,21 +200,23 @@ VITVS_API int vitvs_extract_facet_dev(vitvs_handle* h, int32_t n_frames, const u
                             void* stream);
 /* The extractor's whole descriptor surface, extract_descriptors(batch, layer, facet, bin, include_cls)
  * (dinov2_extractor.py:313-337): facet 0 query, 1 key, 2 value, 3 token; bin != 0: the 3x3 log-bin of that facet (:265-311),
- * desc fp32 [n][T][9 D]; include_cls != 0: the cls row is kept, desc [n][1 + T][D]; neither: [n][T][D].  bin together with
+ * desc fp32 [n][T][9 D]; include_cls != 0: the cls row is kept, desc [n][1 + T][D] (register tokens are always dropped);
+ * neither: [n][T][D].  bin together with
  * include_cls is refused like the reference's assertion (error -5).  Independent of cfg.binned (which selects what the
  * velocity path correlates).  Raw, un-normalised values, like vitvs_extract_descriptors_dev. */
 VITVS_API int vitvs_extract_descriptors_ex_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, int32_t facet, int32_t bin,
                                      int32_t include_cls, float* desc, void* stream);
 /* ViTExtractor.extract_saliency_maps(batch) (dinov2_extractor.py:339-353; the 'attn' facet, :230-231): the class token's
- * attention over the patch tokens in blocks[layer] — softmax over all 1 + T keys, patch columns kept — averaged over the
+ * attention over the patch tokens in blocks[layer] — softmax over all 1 + R + T keys (cls, registers, patches), patch columns
+ * kept — averaged over the
  * heads head_idxs (host array; the reference uses [0, 2, 4, 5] and supports dino_vits8 only) and min-max normalised per
  * image (the reference's broadcast of the [B] extremes is only well-formed for a batch of one; every image gets its own):
  * saliency fp32 [n][T] in [0, 1].  The handle must have been created with layer = the block wanted (the reference hooks
  * block 11). */
 VITVS_API int vitvs_extract_saliency_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, int32_t n_heads,
                                const int32_t* head_idxs, float* saliency, void* stream);
-/* Residual stream after block `cfg.blocks - 1`, fp32 [n][1+T][D] (what the forward hook captures,
- * dinov2_extractor.py:198-199), for parity tests. */
+/* Residual stream after block `cfg.blocks - 1`, fp32 [n][1+R+T][D] (what the forward hook captures,
+ * dinov2_extractor.py:198-199; every row: cls, the R register tokens, the patches), for parity tests. */
 VITVS_API int vitvs_forward_tokens_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, float* tokens, void* stream);
 
 /* find_correspondences_batch's similarity + argmax stage (vitvs_v2.py:78-81) on caller descriptors:

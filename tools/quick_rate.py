@@ -2,6 +2,7 @@
 per-class kernel times of one instrumented update — the short form used while iterating on kernels (bench.py is the record).
 
   python tools/quick_rate.py [--precision f16x2] [--config vitb16_224] [--steps 200] [--depth 3]
+  python tools/quick_rate.py --model dinov2_vits14_reg --size 308 --binned     (any model of config.vit_config at any size)
 """
 import argparse
 import ctypes as C
@@ -23,17 +24,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16x2")
     ap.add_argument("--config", default="vitb16_224")
+    ap.add_argument("--model", default=None, help="a model name of config.vit_config instead of --config (with --size)")
+    ap.add_argument("--size", type=int, default=None, help="input side S for --model (default: 224, 308 for dinov2 models)")
+    ap.add_argument("--binned", action="store_true", help="3x3 log-binned descriptors (use_feature_binning)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--depth", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=1)
     ap.add_argument("--no-hint", action="store_true", help="pipeline slots keep the one-stream tile plan (no in_flight hint)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    cfg = config.baseline_config(args.config)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
+    if args.model:
+        cfg = config.vit_config(args.model, args.size or (308 if args.model.startswith("dinov2") else 224))
+        args.config = f"{args.model}_{cfg.img_size}"
+        seed = synth.ACCEPTED_FRAME_SEEDS["vits14_308"]
+    else:
+        cfg = config.baseline_config(args.config)
+        seed = synth.RIG8_FRAME_SEEDS[0] if args.config == "vitb16_224" else synth.ACCEPTED_FRAME_SEEDS[args.config]
+    if args.binned:
+        args.config += " binned"
+    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=args.binned)
     sd = weights.synthetic_state_dict(cfg, 0)
     B = args.pairs
-    des, cur = synth.frame_pair(cfg.img_size, synth.RIG8_FRAME_SEEDS[0] if args.config == "vitb16_224" else synth.ACCEPTED_FRAME_SEEDS[args.config])
+    des, cur = synth.frame_pair(cfg.img_size, seed)
     I_des = torch.from_numpy(np.stack([des] * B)).to(dev)
     I_cur = torch.from_numpy(np.stack([cur] * B)).to(dev)
     Z = torch.from_numpy(np.stack([synth.depth_pattern()] * B)).to(dev)

@@ -41,6 +41,8 @@ _I = C.c_int32
 PROTOTYPES = {
     "vitvs_abi_version": (_I, []),
     "vitvs_create": (_I, [C.POINTER(VitvsConfig), C.POINTER(_P)]),
+    "vitvs_create_ex": (_I, [C.POINTER(VitvsConfig), _I, C.POINTER(_P)]),
+    "vitvs_register_tokens": (_I, [_P]),
     "vitvs_destroy": (None, [_P]),
     "vitvs_last_error": (C.c_char_p, [_P]),
     "vitvs_set_tensor": (_I, [_P, C.c_char_p, _P, C.c_int64]),

@@ -36,6 +36,7 @@ class ViTConfig:
     layer: int = 11
     mlp_ratio: int = 4
     ln_eps: float = 1e-6
+    registers: int = 0     # R: register tokens (DINOv2 "_reg" checkpoints), rows 1 .. R of the sequence, no position embedding
 
     @property
     def grid(self) -> int:
@@ -47,8 +48,12 @@ class ViTConfig:
         return self.grid * self.grid
 
     @property
-    def seq(self) -> int:  # N = T + cls
-        return self.tokens + 1
+    def prefix(self) -> int:  # P: rows in front of the patch tokens (cls + registers)
+        return 1 + self.registers
+
+    @property
+    def seq(self) -> int:  # N = T + cls + registers
+        return self.tokens + self.prefix
 
     @property
     def head_dim(self) -> int:
@@ -92,7 +97,7 @@ class ViTConfig:
 
 
 _FAMILY = {
-    # name: (patch, dim, depth, heads, layerscale, native image side)
+    # name: (patch, dim, depth, heads, layerscale, native image side[, register tokens])
     "dino_vits16": (16, 384, 12, 6, False, 224),
     "dino_vits8": (8, 384, 12, 6, False, 224),
     "dino_vitb16": (16, 768, 12, 12, False, 224),
@@ -104,13 +109,18 @@ _FAMILY = {
     "dinov2_vits14": (14, 384, 12, 6, True, 518),
     "dinov2_vitb14": (14, 768, 12, 12, True, 518),
     "dinov2_vitl14": (14, 1024, 24, 16, True, 518),
+    # DINOv2 with registers (Darcet et al., "Vision Transformers Need Registers"): the same networks plus 4 learned tokens
+    # between the class token and the patches, published beside the plain checkpoints under these names
+    "dinov2_vits14_reg": (14, 384, 12, 6, True, 518, 4),
+    "dinov2_vitb14_reg": (14, 768, 12, 12, True, 518, 4),
+    "dinov2_vitl14_reg": (14, 1024, 24, 16, True, 518, 4),
 }
 
 
 def vit_config(model_type: str, img_size: int, stride: int | None = None, layer: int = 11) -> ViTConfig:
     if model_type not in _FAMILY:
         raise ValueError(f"unknown model_type {model_type!r}; known: {sorted(_FAMILY)}")
-    patch, dim, depth, heads, ls, native = _FAMILY[model_type]
+    patch, dim, depth, heads, ls, native, *reg = _FAMILY[model_type]
     stride = patch if stride is None else int(stride)
     if (patch // stride) * stride != patch:
         # reference: dinov2_extractor.py:137-138
@@ -126,7 +136,8 @@ def vit_config(model_type: str, img_size: int, stride: int | None = None, layer:
         raise ValueError(f"img_size {img_size} leaves a remainder for patch {patch} / stride {stride}: "
                          f"resize or crop to {used} (the extent the reference's floor would use)")
     return ViTConfig(model_type=model_type, img_size=int(img_size), patch=patch, stride=stride, dim=dim,
-                     depth=depth, heads=heads, layerscale=ls, native_grid=native // patch, layer=layer)
+                     depth=depth, heads=heads, layerscale=ls, native_grid=native // patch, layer=layer,
+                     registers=reg[0] if reg else 0)
 
 
 # The five BASELINE.json configs + the reference's shipped default, by short key.

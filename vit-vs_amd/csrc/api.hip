@@ -84,6 +84,7 @@ struct vitvs_handle {
     Precision prec;
     int device = 0;
     int grid = 0, T = 0, N = 0, Kp = 0, Dp = 0, hidden = 0, n_img_max = 0;
+    int R = 0;                // register tokens (vitvs_create_ex): token rows are [cls, R registers, T patches], N = 1 + R + T
     std::string err;
     std::vector<void*> allocs;                      // workspaces, outputs, staging: this handle's own
     std::shared_ptr<WeightStore> wstore;            // the weights: shared with the handles that borrow them
@@ -98,7 +99,7 @@ struct vitvs_handle {
     std::vector<Block> blk;
     void* pe_w = nullptr;
     int pe_e = 0;
-    float *pe_b = nullptr, *cls = nullptr, *pos = nullptr;
+    float *pe_b = nullptr, *cls = nullptr, *pos = nullptr, *reg = nullptr;   // reg: register tokens [R][D] (R > 0 only)
     // activations
     void *Ape = nullptr, *xn = nullptr, *qkv = nullptr, *attn = nullptr, *hid = nullptr;
     float *x = nullptr, *dn = nullptr, *sq = nullptr, *part = nullptr;  // part: split-K partial sums [8][M][D]
@@ -390,8 +391,8 @@ int forward_launches(vitvs_handle* h, const ChainCtx& cx, hipStream_t st) {
     if (!rc) { Span sp(h, KC_PATCH_EMBED, st);
         rc = launch_linear(cx.plan.embed, cx.Ape, h->pe_w, nullptr, cx.part, 0, st, h->pe_e); }
     if (!rc) { Span sp(h, KC_LAYERNORM, st);
-        rc = launch_embed_ln(h->prec, cx.x, cx.part, cx.plan.embed.splits, h->pe_b, h->pos, h->cls, h->blk[0].n1w, h->blk[0].n1b,
-                             cx.xn, cx.cnt, h->T, D, c.ln_eps, st); }
+        rc = launch_embed_ln(h->prec, cx.x, cx.part, cx.plan.embed.splits, h->pe_b, h->pos, h->cls, h->reg, h->blk[0].n1w,
+                             h->blk[0].n1b, cx.xn, cx.cnt, h->T, 1 + h->R, D, c.ln_eps, st); }
     for (int i = 0; i < c.blocks && !rc; ++i) {
         const Block& b = h->blk[i];
         const Block* nx = (i + 1 < c.blocks) ? &h->blk[i + 1] : nullptr;
@@ -439,7 +440,7 @@ ChainCtx fill_ctx(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
     pa.cur = cur ? cur + (size_t)std::max(i0 - n_des, 0) * img_bytes : nullptr;
     pa.S = c.img_size; pa.patch = c.patch; pa.stride = c.stride; pa.grid = h->grid; pa.Kp = h->Kp; pa.D = D;
     for (int i = 0; i < 3; ++i) { pa.mean[i] = c.mean[i]; pa.std[i] = c.std[i]; }
-    pa.cls = h->cls; pa.pos = h->pos;
+    pa.cls = h->cls; pa.pos = h->pos; pa.prefix = 1 + h->R;
     return cx;
 }
 
@@ -462,6 +463,7 @@ int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
         else cx.desc.dn = h->dn + (size_t)i0 * h->T * h->Dp;
         cx.desc.zero_a = h->row_best; cx.desc.zero_b = h->col_best;
         cx.desc.T = h->T;
+        cx.desc.P = 1 + h->R;
         cx.desc.zero_count = (i0 == 0 || h->goal_frames > 0) ? h->desc_keys : 0;   // the call's only chain clears the arg-max keys
     }
     return forward_launches(h, cx, st);
@@ -579,10 +581,17 @@ const char* vitvs_last_error(const vitvs_handle* h) {
 int vitvs_tokens(const vitvs_handle* h) { return h ? h->T : -1; }
 int vitvs_desc_dim(const vitvs_handle* h) { return h ? h->Dp : -1; }
 
-int vitvs_create(const vitvs_config* cfg, vitvs_handle** out) {
+int vitvs_register_tokens(const vitvs_handle* h) { return h ? h->R : -1; }
+
+int vitvs_create(const vitvs_config* cfg, vitvs_handle** out) { return vitvs_create_ex(cfg, 0, out); }
+
+int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_handle** out) {
     if (!cfg || !out) return set_err(nullptr, -1, "null argument");
     std::string why;
     if (check_cfg(cfg, why)) return set_err(nullptr, -1, "bad config: " + why);
+    if (register_tokens < 0 || register_tokens > VITVS_MAX_REGISTER_TOKENS)
+        return set_err(nullptr, -1, "bad config: register_tokens must be 0 .. " + std::to_string(VITVS_MAX_REGISTER_TOKENS) +
+                                        ", got " + std::to_string(register_tokens));
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) return set_err(nullptr, -2, "no HIP device available");
@@ -595,7 +604,8 @@ int vitvs_create(const vitvs_config* cfg, vitvs_handle** out) {
     h->wstore->device = h->device;
     h->grid = 1 + (cfg->img_size - cfg->patch) / cfg->stride;
     h->T = h->grid * h->grid;
-    h->N = h->T + 1;
+    h->R = register_tokens;
+    h->N = h->T + 1 + h->R;
     const int pk = 3 * cfg->patch * cfg->patch;
     h->Kp = (pk + 63) / 64 * 64;
     h->Dp = cfg->binned ? 9 * cfg->dim : cfg->dim;
@@ -705,8 +715,8 @@ int vitvs_share_weights(vitvs_handle* h, const vitvs_handle* src) {
     const vitvs_config &a = h->cfg, &b = src->cfg;
     if (h->device != src->device) return set_err(h, -5, "handles of different devices cannot share weights");
     if (a.img_size != b.img_size || a.patch != b.patch || a.stride != b.stride || a.dim != b.dim || a.heads != b.heads ||
-        a.blocks != b.blocks || a.layerscale != b.layerscale || a.precision != b.precision)
-        return set_err(h, -5, "weights are shared between handles of one network, input geometry and precision");
+        a.blocks != b.blocks || a.layerscale != b.layerscale || a.precision != b.precision || h->R != src->R)
+        return set_err(h, -5, "weights are shared between handles of one network (register tokens included), input geometry and precision");
     if (!h->have.empty() && !h->borrowed) return set_err(h, -5, "this handle already holds weights of its own");
     if (src->borrowed) return set_err(h, -5, "share from the handle that owns the weights");
     if (vitvs_weights_ready(src) != 0) return set_err(h, -4, "the source handle's weights are not fully loaded");
@@ -717,6 +727,7 @@ int vitvs_share_weights(vitvs_handle* h, const vitvs_handle* src) {
     }
     h->blk = src->blk;
     h->pe_w = src->pe_w; h->pe_e = src->pe_e; h->pe_b = src->pe_b; h->cls = src->cls; h->pos = src->pos;
+    h->reg = src->reg;
     h->have = src->have;
     h->wstore = src->wstore;                    // shared ownership: the weights outlive whichever of the two is destroyed first
     h->ready = true;
@@ -746,9 +757,15 @@ int vitvs_set_tensor(vitvs_handle* h, const char* name, const float* data, int64
     } else if (nm == "cls_token") {
         if ((rc = want(D))) return rc;
         rc = upload_f32(h, &h->cls, data, D);
-    } else if (nm == "pos_embed") {
-        if ((rc = want((size_t)h->N * D))) return rc;
-        rc = upload_f32(h, &h->pos, data, (size_t)h->N * D);
+    } else if (nm == "pos_embed") {   // cls + patches only: the register tokens carry no position embedding
+        if ((rc = want((size_t)(1 + h->T) * D))) return rc;
+        rc = upload_f32(h, &h->pos, data, (size_t)(1 + h->T) * D);
+    } else if (nm == "register_tokens") {
+        if (h->R == 0) return set_err(h, -5, "register_tokens given to a handle created without register tokens (vitvs_create_ex)");
+        if ((size_t)numel != (size_t)h->R * D)
+            return set_err(h, -5, "register_tokens: the handle has " + std::to_string(h->R) + " register tokens, expected " +
+                                      std::to_string((size_t)h->R * D) + " elements, got " + std::to_string(numel));
+        rc = upload_f32(h, &h->reg, data, (size_t)h->R * D);
     } else if (nm.rfind("blocks.", 0) == 0) {
         const size_t dot = nm.find('.', 7);
         if (dot == std::string::npos) return set_err(h, -6, "unknown tensor " + nm);
@@ -802,6 +819,7 @@ int vitvs_weights_ready(const vitvs_handle* hc) {
     if (!h) return -1;
     if (h->ready) return 0;
     std::vector<std::string> need = {"patch_embed.proj.weight", "patch_embed.proj.bias", "cls_token", "pos_embed"};
+    if (h->R > 0) need.push_back("register_tokens");
     static const char* leaves[] = {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
                                    "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
                                    "mlp.fc2.weight", "mlp.fc2.bias"};
@@ -930,7 +948,8 @@ int vitvs_extract_descriptors_dev(vitvs_handle* h, int32_t n_frames, const uint8
     hipStream_t st = as_stream(stream);
     int rc = forward(h, n_frames, frames, 0, nullptr, st);
     if (rc) return rc;
-    rc = launch_descriptors(h->x, h->dn, desc, h->sq, n_frames, h->T, h->grid, h->cfg.dim, h->cfg.binned, nullptr, nullptr, 0, st);
+    rc = launch_descriptors(h->x, h->dn, desc, h->sq, n_frames, h->T, 1 + h->R, h->grid, h->cfg.dim, h->cfg.binned, nullptr, nullptr,
+                            0, st);
     if (rc) return set_err(h, rc, "descriptor launch failed");
     return 0;
 }
@@ -952,22 +971,30 @@ int vitvs_extract_descriptors_ex_dev(vitvs_handle* h, int32_t n_frames, const ui
     int rc = forward(h, n_frames, frames, 0, nullptr, st);   // the last block's qkv launch leaves its output in h->qkv
     if (rc) return rc;
     const int T = h->T, D = h->cfg.dim;
-    const float* src = h->x;                                  // token facet: the residual stream itself, [n][1 + T][D]
+    const float* src = h->x;                                  // token facet: the residual stream itself, [n][P + T][D]
+    int P = 1 + h->R;                                         // rows in front of each image's patch rows in src
     if (facet < 3) {
-        // q / k / v of blocks[layer] in the reference's layout (index d * H + h), fp32, WITH the cls row, over the residual
-        // stream's own buffer (the forward is done with it; any cached goal was dropped by the forward above)
-        rc = launch_facet(h->prec, h->qkv, h->x, n_frames, T, h->cfg.heads, facet,
+        // q / k / v of blocks[layer] in the reference's layout (index d * H + h), fp32, WITH the cls row (registers dropped),
+        // over the residual stream's own buffer (the forward is done with it; any cached goal was dropped by the forward above)
+        rc = launch_facet(h->prec, h->qkv, h->x, n_frames, T, P, h->cfg.heads, facet,
                           (facet == 0 && plain16(h->prec)) ? 1.0f / kAttnQScale : 1.0f, 1, st);   // the q rows carry the attention scale
         if (rc) return set_err(h, rc, "facet launch failed");
+        P = 1;                                                // src is now [n][1 + T][D]
     }
+    const size_t row_bytes = (size_t)D * sizeof(float);
     if (bin) {
-        rc = launch_descriptors(src, nullptr, desc, h->sq, n_frames, T, h->grid, D, 1, nullptr, nullptr, 0, st);
+        rc = launch_descriptors(src, nullptr, desc, h->sq, n_frames, T, P, h->grid, D, 1, nullptr, nullptr, 0, st);
         if (rc) return set_err(h, rc, "descriptor launch failed");
-    } else if (include_cls) {
-        VITVS_HIP_CHECK(hipMemcpyAsync(desc, src, (size_t)n_frames * (T + 1) * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else if (include_cls && P == 1) {
+        VITVS_HIP_CHECK(hipMemcpyAsync(desc, src, (size_t)n_frames * (T + 1) * row_bytes, hipMemcpyDeviceToDevice, st));
+    } else if (include_cls) {                                 // [cls, patches]: the register rows are dropped
+        VITVS_HIP_CHECK(hipMemcpy2DAsync(desc, (T + 1) * row_bytes, src, (T + P) * row_bytes, row_bytes, n_frames,
+                                         hipMemcpyDeviceToDevice, st));
+        VITVS_HIP_CHECK(hipMemcpy2DAsync(desc + D, (T + 1) * row_bytes, src + (size_t)P * D, (T + P) * row_bytes, T * row_bytes,
+                                         n_frames, hipMemcpyDeviceToDevice, st));
     } else {
-        VITVS_HIP_CHECK(hipMemcpy2DAsync(desc, (size_t)T * D * sizeof(float), src + D, (size_t)(T + 1) * D * sizeof(float),
-                                         (size_t)T * D * sizeof(float), n_frames, hipMemcpyDeviceToDevice, st));
+        VITVS_HIP_CHECK(hipMemcpy2DAsync(desc, T * row_bytes, src + (size_t)P * D, (T + P) * row_bytes, T * row_bytes, n_frames,
+                                         hipMemcpyDeviceToDevice, st));
     }
     return 0;
 }
@@ -983,7 +1010,8 @@ int vitvs_extract_saliency_dev(vitvs_handle* h, int32_t n_frames, const uint8_t*
     int rc = forward(h, n_frames, frames, 0, nullptr, st);   // the last block's qkv launch leaves its output in h->qkv
     if (rc) return rc;
     if (h->prec == PREC_X2) return set_err(h, -5, "saliency maps are not available in the f16x2 precision (use fp32)");
-    rc = launch_saliency(h->prec, h->qkv, saliency, n_frames, h->T, h->cfg.heads, head_idxs, n_heads, plain16(h->prec), st);
+    rc = launch_saliency(h->prec, h->qkv, saliency, n_frames, h->T, 1 + h->R, h->cfg.heads, head_idxs, n_heads, plain16(h->prec),
+                         st);
     if (rc) return set_err(h, rc, rc == -3 ? "too many tokens for the saliency kernel's LDS rows" : "saliency launch failed");
     return 0;
 }
@@ -1065,7 +1093,7 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
         // binned descriptors as a stencil over the raw token Gram: nothing 9 D wide is built or read (correspond.hip header)
         // (the tokens' squared norms came out of the forward's last launch, which also cleared the arg-max keys)
         { Span sp(h, KC_GRAM, st);
-          rc = launch_gram_raw_tokens(h->x, h->T, h->cfg.dim, u.n_pairs, u.des_shared ? 1 : 0, h->gram_ws, st); }
+          rc = launch_gram_raw_tokens(h->x, h->T, 1 + h->R, h->cfg.dim, u.n_pairs, u.des_shared ? 1 : 0, h->gram_ws, st); }
         if (rc) return set_err(h, rc, "gram launch failed");
         { Span sp(h, KC_GRAM_STENCIL, st);
           rc = launch_gram_stencil_argmax(h->gram_ws, h->sq, h->T, h->grid, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st); }
@@ -1075,7 +1103,7 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
     }
     if (!desc_in_forward(h)) {
         Span sp(h, KC_DESCRIPTORS, st);
-        rc = launch_descriptors(h->x, h->dn, nullptr, h->sq, n_img, h->T, h->grid, h->cfg.dim, h->cfg.binned,
+        rc = launch_descriptors(h->x, h->dn, nullptr, h->sq, n_img, h->T, 1 + h->R, h->grid, h->cfg.dim, h->cfg.binned,
                                 h->row_best, h->col_best, u.n_pairs * h->T, st);
         if (rc) return set_err(h, rc, "descriptor launch failed");
     }

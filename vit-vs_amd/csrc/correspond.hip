@@ -136,8 +136,8 @@ __global__ __launch_bounds__(256 * KG) void gram_argmax_kernel(const E* __restri
 }
 
 // S[b][i][j] = <row i of image a(b), row j of image c(b)> over Dp elements; rows of image k start at src + k * img_stride and are
-// ld apart (normalised descriptors: img_stride = T * Dp, ld = Dp; raw tokens of the residual stream: src = x + D, img_stride =
-// (T + 1) * D, ld = D — the cls row is skipped by the base and the stride).  Tiles in the band order of gram_tile.
+// ld apart (normalised descriptors: img_stride = T * Dp, ld = Dp; raw tokens of the residual stream: src = x + P D, img_stride =
+// (T + P) * D, ld = D — the cls and register rows are skipped by the base and the stride).  Tiles in the band order of gram_tile.
 template <int BM, int BN, int KG>
 __global__ __launch_bounds__(256 * KG) void gram_dense_kernel(const float* __restrict__ src, long img_stride, int ld, int T, int Dp,
                                                               int n_pairs, int des_shared, float* __restrict__ S, int hb) {
@@ -378,8 +378,9 @@ int launch_gram_dense(const float* dn, int T, int Dp, int n_pairs, int des_share
     return launch_gram_dense_strided(dn, (long)T * Dp, Dp, T, Dp, n_pairs, des_shared, S, stream);
 }
 
-int launch_gram_raw_tokens(const float* x, int T, int D, int n_pairs, int des_shared, float* G, hipStream_t stream) {
-    return launch_gram_dense_strided(x + D, (long)(T + 1) * D, D, T, D, n_pairs, des_shared, G, stream);
+int launch_gram_raw_tokens(const float* x, int T, int P, int D, int n_pairs, int des_shared, float* G, hipStream_t stream) {
+    if (P < 1) return -2;
+    return launch_gram_dense_strided(x + (size_t)P * D, (long)(T + P) * D, D, T, D, n_pairs, des_shared, G, stream);
 }
 
 int launch_gram_stencil_argmax(const float* G, const float* sq, int T, int grid, int n_pairs, int des_shared,

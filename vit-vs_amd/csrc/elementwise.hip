@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(PatchifyArgs a, T* __rest
     const int row = blockIdx.x;
     if (row >= n_img * Tn) {  // cls rows: x[img][0][:] = cls + pos[0]
         const int img = row - n_img * Tn;
-        const size_t xrow = (size_t)img * (Tn + 1);
+        const size_t xrow = (size_t)img * (Tn + a.prefix);
         float* dst = x + xrow * a.D;
         for (int d = threadIdx.x; d < a.D; d += blockDim.x) dst[d] = a.cls[d] + a.pos[d];
         return;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void patchify_resize_kernel(PatchifyArgs a, Re
     const int row = blockIdx.x, tid = threadIdx.x;
     if (row >= n_img * Tn) {  // cls rows: x[img][0][:] = cls + pos[0]
         const int img = row - n_img * Tn;
-        float* dst = x + (size_t)img * (Tn + 1) * a.D;
+        float* dst = x + (size_t)img * (Tn + a.prefix) * a.D;
         for (int d = tid; d < a.D; d += blockDim.x) dst[d] = a.cls[d] + a.pos[d];
         return;
     }
@@ -247,11 +247,14 @@ struct RlnExtra {   // by-value tail argument of the DESC / EMBED variants
     DescOut desc;
     const float* pos = nullptr;   // EMBED: position embedding [1 + T][D]
     const float* cls = nullptr;   // EMBED: class token [D]
+    const float* reg = nullptr;   // EMBED: register tokens [P - 1][D] (desc.P > 1 only)
 };
 
 // MODE = RLN_EMBED finishes the patch embedding instead of a block: x (write-only) = pos_embed + split-K sum +
-// bias for the patch tokens (partial rows are [img][T], x rows [img][1 + T]), cls + pos[0] for the class
-// token, followed by block 0's norm1 — so neither the embedding epilogue nor a LayerNorm launch is needed.
+// bias for the patch tokens (partial rows are [img][T], x rows [img][P + T]), cls + pos[0] for the class
+// token, the register tokens as they are for rows 1 .. P - 1 (inserted after the position embedding: DINOv2's
+// prepare_tokens_with_masks), followed by block 0's norm1 — so neither the embedding epilogue nor a LayerNorm
+// launch is needed.
 template <typename T, int NV4, int LANES, int MODE = RLN_PLAIN>
 __global__ __launch_bounds__(64) void residual_ln_kernel(float* __restrict__ x, const float* __restrict__ part,
                                                          const float* __restrict__ bias, const float* __restrict__ gamma,
@@ -269,10 +272,11 @@ __global__ __launch_bounds__(64) void residual_ln_kernel(float* __restrict__ x, 
     float4* xr = reinterpret_cast<float4*>(x + (size_t)row * D);
     float4 v[NV4], pv[SMAX][NV4], bb[NV4], ll[NV4], gg[NV4], be[NV4];
     if constexpr (MODE == RLN_EMBED) {
-        const int Tn = ex.desc.T, img = row / (Tn + 1), t = row - img * (Tn + 1) - 1;
-        const int Mp = (M / (Tn + 1)) * Tn;                       // rows of one partial slice
+        const int Tn = ex.desc.T, P = ex.desc.P, img = row / (Tn + P), j = row - img * (Tn + P), t = j - P;
+        const int Mp = (M / (Tn + P)) * Tn;                       // rows of one partial slice
         const int prow = img * Tn + max(t, 0);
-        const float4* posr = reinterpret_cast<const float4*>(ex.pos + (size_t)(1 + t) * D);
+        const bool reg = t < 0 && j > 0;                          // register token j - 1: no pos, no bias
+        const float4* posr = reinterpret_cast<const float4*>(reg ? ex.reg + (size_t)(j - 1) * D : ex.pos + (size_t)max(t + 1, 0) * D);
 #pragma unroll
         for (int z = 0; z < SMAX; ++z)
             if (z < splits) {
@@ -284,11 +288,11 @@ __global__ __launch_bounds__(64) void residual_ln_kernel(float* __restrict__ x, 
         for (int i = 0; i < NV4; ++i) {
             const int c = i * LANES + l;
             v[i] = posr[c];
-            bb[i] = reinterpret_cast<const float4*>(t >= 0 ? bias : ex.cls)[c];
+            bb[i] = reg ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(t >= 0 ? bias : ex.cls)[c];
             gg[i] = reinterpret_cast<const float4*>(gamma)[c];
             be[i] = reinterpret_cast<const float4*>(beta)[c];
         }
-        if (t < 0) {   // class token: cls + pos[0], no patch-embedding terms
+        if (t < 0) {   // class token (cls + pos[0]) or register: no patch-embedding terms
 #pragma unroll
             for (int z = 0; z < SMAX; ++z)
 #pragma unroll
@@ -343,7 +347,7 @@ __global__ __launch_bounds__(64) void residual_ln_kernel(float* __restrict__ x, 
         const DescOut& desc = ex.desc;
         const int gid = blockIdx.x * 64 + lane;
         if (gid < desc.zero_count) { desc.zero_a[gid] = 0ull; desc.zero_b[gid] = 0ull; }
-        const int img = row / (desc.T + 1), t = row - img * (desc.T + 1) - 1;
+        const int img = row / (desc.T + desc.P), t = row - img * (desc.T + desc.P) - desc.P;
         float s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < NV4; ++i)
@@ -426,26 +430,29 @@ int launch_residual_ln(Precision p, float* x, const float* part, int splits, con
     if (M <= 0 || splits < 1 || splits > SMAX) return -2;
     RlnExtra ex;
     if (!desc) return launch_rln_p<RLN_PLAIN>(p, x, part, splits, bias, ls, gamma, beta, out, M, D, eps, stream, ex);
-    if (gamma || (!desc->dn && !desc->sq) || desc->T <= 0 || M % (desc->T + 1) != 0 || desc->zero_count > M * 64) return -2;
+    if (gamma || (!desc->dn && !desc->sq) || desc->T <= 0 || desc->P < 1 || M % (desc->T + desc->P) != 0 || desc->zero_count > M * 64) return -2;
     ex.desc = *desc;
     return launch_rln_p<RLN_DESC>(p, x, part, splits, bias, ls, gamma, beta, out, M, D, eps, stream, ex);
 }
 
 int launch_embed_ln(Precision p, float* x, const float* part, int splits, const float* bias, const float* pos,
-                    const float* cls, const float* gamma, const float* beta, void* out, int n_img, int T, int D, float eps,
-                    hipStream_t stream) {
-    if (n_img <= 0 || T <= 0 || splits < 1 || splits > SMAX || !gamma || !beta || !pos || !cls) return -2;
+                    const float* cls, const float* reg, const float* gamma, const float* beta, void* out, int n_img, int T,
+                    int P, int D, float eps, hipStream_t stream) {
+    if (n_img <= 0 || T <= 0 || P < 1 || splits < 1 || splits > SMAX || !gamma || !beta || !pos || !cls || (P > 1 && !reg))
+        return -2;
     RlnExtra ex;
     ex.desc.T = T;
+    ex.desc.P = P;
     ex.pos = pos;
     ex.cls = cls;
-    return launch_rln_p<RLN_EMBED>(p, x, part, splits, bias, nullptr, gamma, beta, out, n_img * (T + 1), D, eps, stream, ex);
+    ex.reg = reg;
+    return launch_rln_p<RLN_EMBED>(p, x, part, splits, bias, nullptr, gamma, beta, out, n_img * (T + P), D, eps, stream, ex);
 }
 
 // ------------------------------------------------------------------------------------ descriptors
 // plain: one wave per patch token: dn = x / max(||x||, 1e-8)
 __global__ __launch_bounds__(256) void desc_plain_kernel(const float* __restrict__ x, float* __restrict__ dn,
-                                                         float* __restrict__ raw, int n_img, int T, int D,
+                                                         float* __restrict__ raw, int n_img, int T, int P, int D,
                                                          unsigned long long* zero_a, unsigned long long* zero_b,
                                                          int zero_count) {
     const int lane = threadIdx.x & 63;
@@ -456,7 +463,7 @@ __global__ __launch_bounds__(256) void desc_plain_kernel(const float* __restrict
     }
     if (tok >= n_img * T) return;
     const int img = tok / T, t = tok - img * T;
-    const float4* src = reinterpret_cast<const float4*>(x + ((size_t)img * (T + 1) + 1 + t) * D);
+    const float4* src = reinterpret_cast<const float4*>(x + ((size_t)img * (T + P) + P + t) * D);
     // the row is read once, 16 bytes per lane (D <= 1024 -> at most 4 float4 per lane), and kept in registers
     const int n4 = D >> 2;
     float4 v[4];
@@ -482,7 +489,7 @@ __global__ __launch_bounds__(256) void desc_plain_kernel(const float* __restrict
 }
 
 __global__ __launch_bounds__(256) void token_sqnorm_kernel(const float* __restrict__ x, float* __restrict__ sq,
-                                                           int n_img, int T, int D, unsigned long long* zero_a,
+                                                           int n_img, int T, int P, int D, unsigned long long* zero_a,
                                                            unsigned long long* zero_b, int zero_count) {
     const int lane = threadIdx.x & 63;
     const int tok = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -492,7 +499,7 @@ __global__ __launch_bounds__(256) void token_sqnorm_kernel(const float* __restri
     }
     if (tok >= n_img * T) return;
     const int img = tok / T, t = tok - img * T;
-    const float* src = x + ((size_t)img * (T + 1) + 1 + t) * D;
+    const float* src = x + ((size_t)img * (T + P) + P + t) * D;
     float s = 0.f;
     for (int d = lane; d < D; d += 64) {
         const float v = src[d];
@@ -506,7 +513,7 @@ __global__ __launch_bounds__(256) void token_sqnorm_kernel(const float* __restri
 // concatenated and the 9D vector normalised.
 __global__ __launch_bounds__(256) void desc_binned_kernel(const float* __restrict__ x, const float* __restrict__ sq,
                                                           float* __restrict__ dn, float* __restrict__ raw, int n_img,
-                                                          int T, int grid, int D) {
+                                                          int T, int P, int grid, int D) {
     const int tok = blockIdx.x;
     const int img = tok / T, t = tok - img * T;
     const int ty = t / grid, tx = t - ty * grid;
@@ -523,7 +530,7 @@ __global__ __launch_bounds__(256) void desc_binned_kernel(const float* __restric
     float* dst = dn + (size_t)tok * 9 * D;
     for (int e = threadIdx.x; e < 9 * D; e += blockDim.x) {
         const int o = e / D, d = e - o * D;
-        const float v = x[((size_t)img * (T + 1) + 1 + nb[o]) * D + d];
+        const float v = x[((size_t)img * (T + P) + P + nb[o]) * D + d];
         if (dn) dst[e] = __fdiv_rn(v, nrm);
         if (raw) raw[(size_t)tok * 9 * D + e] = v;
     }
@@ -579,15 +586,15 @@ int launch_normalize_rows(const float* src, float* dst, int rows, int Dp, hipStr
 }
 
 // Facet descriptors (query / key / value of blocks[layer], dinov2_extractor.py:193-217, 326-334): from the qkv
-// GEMM's output [n_img*(1+T)][3][H][64] to fp32 [n_img][T][D] with descriptor index d * H + h, cls token dropped.
+// GEMM's output [n_img*(P+T)][3][H][64] to fp32 [n_img][T][D] with descriptor index d * H + h, cls and register tokens dropped.
 template <typename T>
-__global__ __launch_bounds__(256) void facet_kernel(const T* __restrict__ qkv, float* __restrict__ out, int Tn, int H,
+__global__ __launch_bounds__(256) void facet_kernel(const T* __restrict__ qkv, float* __restrict__ out, int Tn, int P, int H,
                                                     int which, float unscale, int keep_cls) {
-    // keep_cls = 0: out [n_img][T][D] (cls dropped); 1: out [n_img][1 + T][D]
+    // keep_cls = 0: out [n_img][T][D] (cls dropped); 1: out [n_img][1 + T][D] (registers dropped)
     const int rows = Tn + keep_cls;
     const int tok = blockIdx.x, img = tok / rows, t = tok - img * rows;
     const int D = H * 64;
-    const size_t qrow = (size_t)img * (Tn + 1) + (1 - keep_cls) + t;
+    const size_t qrow = (size_t)img * (Tn + P) + ((keep_cls && t == 0) ? 0 : P - keep_cls + t);
     float* dst = out + (size_t)tok * D;
     for (int j = threadIdx.x; j < D; j += 256) {
         const int h = j % H, d = j / H;
@@ -596,32 +603,33 @@ __global__ __launch_bounds__(256) void facet_kernel(const T* __restrict__ qkv, f
     }
 }
 
-int launch_facet(Precision p, const void* qkv, float* out, int n_img, int T, int H, int which, float q_unscale, int keep_cls,
+int launch_facet(Precision p, const void* qkv, float* out, int n_img, int T, int P, int H, int which, float q_unscale, int keep_cls,
                  hipStream_t stream) {
-    if (n_img <= 0 || T <= 0 || H <= 0 || which < 0 || which > 2) return -2;
+    if (n_img <= 0 || T <= 0 || P < 1 || H <= 0 || which < 0 || which > 2) return -2;
     const dim3 grid(n_img * (T + (keep_cls ? 1 : 0)));
     const int kc = keep_cls ? 1 : 0;
-    if (p == PREC_X2) launch(facet_kernel<hx2>, grid, dim3(256), 0, stream, (const hx2*)qkv, out, T, H, which, q_unscale, kc);
-    else if (p == PREC_F32) launch(facet_kernel<float>, grid, dim3(256), 0, stream, (const float*)qkv, out, T, H, which, q_unscale, kc);
-    else if (p == PREC_F16) launch(facet_kernel<f16>, grid, dim3(256), 0, stream, (const f16*)qkv, out, T, H, which, q_unscale, kc);
-    else launch(facet_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)qkv, out, T, H, which, q_unscale, kc);
+    if (p == PREC_X2) launch(facet_kernel<hx2>, grid, dim3(256), 0, stream, (const hx2*)qkv, out, T, P, H, which, q_unscale, kc);
+    else if (p == PREC_F32) launch(facet_kernel<float>, grid, dim3(256), 0, stream, (const float*)qkv, out, T, P, H, which, q_unscale, kc);
+    else if (p == PREC_F16) launch(facet_kernel<f16>, grid, dim3(256), 0, stream, (const f16*)qkv, out, T, P, H, which, q_unscale, kc);
+    else launch(facet_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)qkv, out, T, P, H, which, q_unscale, kc);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // Saliency maps (ViTExtractor.extract_saliency_maps, dinov2_extractor.py:339-353: the 'attn' facet of the last block, hooked
-// behind attn_drop): the class token's attention row softmax(q_cls . K^T * hd^-0.5) over ALL 1 + T keys, patch columns only,
+// behind attn_drop): the class token's attention row softmax(q_cls . K^T * hd^-0.5) over ALL P + T keys (cls, registers,
+// patches), patch columns only,
 // averaged over the chosen heads, then min-max normalised per image.  One workgroup per image; the row of each head is formed
-// in LDS (scores, max, exp, sum) — T + 1 dot products of 64 per head, nothing worth the matrix pipe.
+// in LDS (scores, max, exp, sum) — P + T dot products of 64 per head, nothing worth the matrix pipe.
 struct SaliencyHeads { int n; int idx[16]; };
 template <typename T>
-__global__ __launch_bounds__(256) void saliency_kernel(const T* __restrict__ qkv, float* __restrict__ out, int Tn, int H,
+__global__ __launch_bounds__(256) void saliency_kernel(const T* __restrict__ qkv, float* __restrict__ out, int Tn, int P, int H,
                                                        SaliencyHeads heads, float scale, int base2) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* row = reinterpret_cast<float*>(smem);          // [1 + T] scores, then probabilities of one head
-    float* acc = row + (Tn + 1);                          // [T] sum over the heads
+    float* row = reinterpret_cast<float*>(smem);          // [P + T] scores, then probabilities of one head
+    float* acc = row + (Tn + P);                          // [T] sum over the heads
     __shared__ float red[8];
     __shared__ float qs[64];
-    const int img = blockIdx.x, tid = threadIdx.x, N = Tn + 1, D = H * 64;
+    const int img = blockIdx.x, tid = threadIdx.x, N = Tn + P, D = H * 64;
     const T* base = qkv + (size_t)img * N * 3 * D;
     for (int j = tid; j < Tn; j += 256) acc[j] = 0.f;
     auto block_reduce = [&](float v, bool is_max) {
@@ -654,7 +662,7 @@ __global__ __launch_bounds__(256) void saliency_kernel(const T* __restrict__ qkv
             sum += e;
         }
         sum = block_reduce(sum, false);
-        for (int j = tid; j < Tn; j += 256) acc[j] += __fdiv_rn(row[j + 1], sum);
+        for (int j = tid; j < Tn; j += 256) acc[j] += __fdiv_rn(row[j + P], sum);
     }
     __syncthreads();
     float lo = INFINITY, hi = -INFINITY;
@@ -669,9 +677,9 @@ __global__ __launch_bounds__(256) void saliency_kernel(const T* __restrict__ qkv
     for (int j = tid; j < Tn; j += 256) out[(size_t)img * Tn + j] = __fdiv_rn(acc[j] - lo, hi - lo);
 }
 
-int launch_saliency(Precision p, const void* qkv, float* out, int n_img, int T, int H, const int* head_idx, int n_heads,
+int launch_saliency(Precision p, const void* qkv, float* out, int n_img, int T, int P, int H, const int* head_idx, int n_heads,
                     bool q_prescaled, hipStream_t stream) {
-    if (n_img <= 0 || T <= 0 || H <= 0 || n_heads <= 0 || n_heads > 16) return -2;
+    if (n_img <= 0 || T <= 0 || P < 1 || H <= 0 || n_heads <= 0 || n_heads > 16) return -2;
     if (p == PREC_X2) return -2;   // the saliency surface is frozen (outside SURVEY section 8): fp32 / bf16 / fp16 handles only
     SaliencyHeads hs;
     hs.n = n_heads;
@@ -679,29 +687,29 @@ int launch_saliency(Precision p, const void* qkv, float* out, int n_img, int T, 
         if (head_idx[i] < 0 || head_idx[i] >= H) return -2;
         hs.idx[i] = head_idx[i];
     }
-    const size_t lds = (size_t)(2 * T + 1) * sizeof(float);
+    const size_t lds = (size_t)(2 * T + P) * sizeof(float);
     if (lds > 64 * 1024) return -3;
     // 16-bit modes: the q rows of the qkv weights carry hd^-0.5 * log2(e) (kAttnQScale), so the scores are in log2 units
     const float scale = q_prescaled ? 1.0f : 0.125f;
     const int base2 = q_prescaled ? 1 : 0;
-    if (p == PREC_F32) launch(saliency_kernel<float>, dim3(n_img), dim3(256), lds, stream, (const float*)qkv, out, T, H, hs, scale, base2);
-    else if (p == PREC_F16) launch(saliency_kernel<f16>, dim3(n_img), dim3(256), lds, stream, (const f16*)qkv, out, T, H, hs, scale, base2);
-    else launch(saliency_kernel<bf16>, dim3(n_img), dim3(256), lds, stream, (const bf16*)qkv, out, T, H, hs, scale, base2);
+    if (p == PREC_F32) launch(saliency_kernel<float>, dim3(n_img), dim3(256), lds, stream, (const float*)qkv, out, T, P, H, hs, scale, base2);
+    else if (p == PREC_F16) launch(saliency_kernel<f16>, dim3(n_img), dim3(256), lds, stream, (const f16*)qkv, out, T, P, H, hs, scale, base2);
+    else launch(saliency_kernel<bf16>, dim3(n_img), dim3(256), lds, stream, (const bf16*)qkv, out, T, P, H, hs, scale, base2);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_descriptors(const float* x, float* dn, float* raw, float* sqnorm_ws, int n_img, int T, int grid, int D,
+int launch_descriptors(const float* x, float* dn, float* raw, float* sqnorm_ws, int n_img, int T, int P, int grid, int D,
                        int binned, unsigned long long* zero_a, unsigned long long* zero_b, int zero_count,
                        hipStream_t stream) {
     const int toks = n_img * T;
-    if (toks <= 0 || grid * grid != T || zero_count > toks * 64) return -2;
+    if (toks <= 0 || P < 1 || grid * grid != T || zero_count > toks * 64) return -2;
     if (!binned) {
-        launch(desc_plain_kernel, dim3((toks + 3) / 4), dim3(256), 0, stream, x, dn, raw, n_img, T, D,
+        launch(desc_plain_kernel, dim3((toks + 3) / 4), dim3(256), 0, stream, x, dn, raw, n_img, T, P, D,
                            zero_a, zero_b, zero_count);
     } else {
-        launch(token_sqnorm_kernel, dim3((toks + 3) / 4), dim3(256), 0, stream, x, sqnorm_ws, n_img, T, D,
+        launch(token_sqnorm_kernel, dim3((toks + 3) / 4), dim3(256), 0, stream, x, sqnorm_ws, n_img, T, P, D,
                            zero_a, zero_b, zero_count);
-        launch(desc_binned_kernel, dim3(toks), dim3(256), 0, stream, x, sqnorm_ws, dn, raw, n_img, T, grid,
+        launch(desc_binned_kernel, dim3(toks), dim3(256), 0, stream, x, sqnorm_ws, dn, raw, n_img, T, P, grid,
                            D);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;

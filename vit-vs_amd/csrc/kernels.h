@@ -106,6 +106,7 @@ struct PatchifyArgs {
     float mean[3], std[3];
     const float* cls;     // [D]
     const float* pos;     // [1+T][D]
+    int prefix = 1;       // rows in front of the patch tokens in x: cls + registers (P = 1 + R)
 };
 // Camera-resolution frames ([in_h][in_w][3] instead of [S][S][3]): Pillow's 8-bit bicubic resample tables of
 // resize_coefficients() (resize.hip) for both axes, on the device.  rows = the most camera rows one patch's pixels draw on.
@@ -116,7 +117,7 @@ struct ResizeArgs {
 constexpr int kResizePrecisionBits = 32 - 8 - 2;   // Pillow Resample.c: PRECISION_BITS
 __device__ __forceinline__ int resize_clip8(int v) { return min(max(v >> kResizePrecisionBits, 0), 255); }
 // Ape[(img*T + t)][k] = ((u8/255) - mean_c)/std_c for k = c*p*p + py*p + px (zero for k >= 3p²);
-// x[img*(T+1)][:] = cls + pos[0].  rs != nullptr: des / cur are camera frames and u8 is the pixel PIL's
+// x[img*(T+P)][:] = cls + pos[0].  rs != nullptr: des / cur are camera frames and u8 is the pixel PIL's
 // Image.resize((S, S)) would produce (vitvs_v2.py:474-475), computed while the row is built.
 int launch_patchify(Precision p, const PatchifyArgs& a, const ResizeArgs* rs, void* Ape, float* x, hipStream_t stream);
 // out[m][:] = LayerNorm(x[m][:]) * gamma + beta, out in precision p.
@@ -125,31 +126,33 @@ int launch_layernorm(Precision p, const float* x, const float* gamma, const floa
 // x[m][:] += ls * (sum_z part[z][m][:] + bias)  (fixed slice order), then, if gamma != null,
 // out[m][:] = LayerNorm(x[m][:]) * gamma + beta in precision p.  One pass over the row.
 // desc (optional, only with gamma == null, i.e. after the last block): the same launch also writes the plain
-// L2-normalised descriptors dn[img][t][:] = x[img][1+t][:] / max(norm, 1e-8) (rows are [img][1+T] tokens, cls
-// first) and clears zero_count 64-bit words of zero_a / zero_b (the Gram kernel's atomicMax targets).
+// L2-normalised descriptors dn[img][t][:] = x[img][P+t][:] / max(norm, 1e-8) (rows are [img][P+T] tokens: cls,
+// the R = P - 1 register tokens, then the patches) and clears zero_count 64-bit words of zero_a / zero_b (the Gram kernel's atomicMax targets).
 struct DescOut {
     float* dn = nullptr;          // may be null when sq is given
-    float* sq = nullptr;          // optional: sq[img * T + t] = |x[img][1 + t][:]|^2 (the stencil form of the binned Gram, correspond.hip)
+    float* sq = nullptr;          // optional: sq[img * T + t] = |x[img][P + t][:]|^2 (the stencil form of the binned Gram, correspond.hip)
     unsigned long long* zero_a = nullptr;
     unsigned long long* zero_b = nullptr;
     int T = 0;
+    int P = 1;                    // prefix rows of each image: cls + register tokens
     int zero_count = 0;
 };
 int launch_residual_ln(Precision p, float* x, const float* part, int splits, const float* bias, const float* ls,
                        const float* gamma, const float* beta, void* out, int M, int D, float eps, hipStream_t stream,
                        const DescOut* desc = nullptr);
 // Finishes a split-K patch embedding (partial rows [n_img][T], launch_linear EPI_PARTIAL) and applies block 0's norm1:
-//   x[img][0][:] = cls + pos[0];  x[img][1+t][:] = pos[1+t] + sum_z part[z][img*T+t][:] + bias;  out = LayerNorm(x).
+//   x[img][0][:] = cls + pos[0];  x[img][r][:] = reg[r-1] (1 <= r < P, no position embedding);
+//   x[img][P+t][:] = pos[1+t] + sum_z part[z][img*T+t][:] + bias;  out = LayerNorm(x).  P = 1: no registers (reg unused).
 int launch_embed_ln(Precision p, float* x, const float* part, int splits, const float* bias, const float* pos,
-                    const float* cls, const float* gamma, const float* beta, void* out, int n_img, int T, int D, float eps,
-                    hipStream_t stream);
-// Descriptors for the correspondence stage, fp32, L2-normalised with max(|x|,1e-8):
-//   plain : dn[img][t][D]   = x[img][1+t][:] / max(norm, eps)
+                    const float* cls, const float* reg, const float* gamma, const float* beta, void* out, int n_img, int T,
+                    int P, int D, float eps, hipStream_t stream);
+// Descriptors for the correspondence stage, fp32, L2-normalised with max(|x|,1e-8), from x rows [img][P+T]:
+//   plain : dn[img][t][D]   = x[img][P+t][:] / max(norm, eps)
 //   binned: dn[img][t][9D]  = 3x3 replicate-clamped neighbourhood concat, then normalised.
 // raw (optional, may be null): the un-normalised descriptor in the same layout.
 // zero_a / zero_b (may be null with zero_count 0): zero_count 64-bit words of each are cleared by the
 // same launch (the Gram kernel's atomicMax targets), saving two memset nodes per update.
-int launch_descriptors(const float* x, float* dn, float* raw, float* sqnorm_ws, int n_img, int T, int grid, int D,
+int launch_descriptors(const float* x, float* dn, float* raw, float* sqnorm_ws, int n_img, int T, int P, int grid, int D,
                        int binned, unsigned long long* zero_a, unsigned long long* zero_b, int zero_count,
                        hipStream_t stream);
 
@@ -199,9 +202,9 @@ int launch_gram_argmax_split(const void* dh, int T, int Dp, int n_pairs, int des
                              unsigned long long* col_best, hipStream_t stream);
 int launch_gram_dense(const float* dn, int T, int Dp, int n_pairs, int des_shared, float* S, hipStream_t stream);
 // Binned descriptors without building them (correspond.hip header): G[b][i][j] = raw dot products of the patch tokens in the
-// residual stream x ([frames][1 + T][D] fp32, desired frames first), then the 3 x 3 "diagonal" stencil over G, normalised by the
+// residual stream x ([frames][P + T][D] fp32, desired frames first), then the 3 x 3 "diagonal" stencil over G, normalised by the
 // binned descriptors' norms (sq = |t|^2 per token: DescOut::sq of the forward's last launch), with the fused arg-max into row_best / col_best.
-int launch_gram_raw_tokens(const float* x, int T, int D, int n_pairs, int des_shared, float* G, hipStream_t stream);
+int launch_gram_raw_tokens(const float* x, int T, int P, int D, int n_pairs, int des_shared, float* G, hipStream_t stream);
 int launch_gram_stencil_argmax(const float* G, const float* sq, int T, int grid, int n_pairs, int des_shared,
                                unsigned long long* row_best, unsigned long long* col_best, hipStream_t stream);
 
@@ -247,14 +250,15 @@ struct ServoArgs {
 };
 int launch_servo(const ServoArgs& a, hipStream_t stream);
 
-// out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(1+T)][3][H][64], cls dropped
+// out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
-// keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first)
-int launch_facet(Precision p, const void* qkv, float* out, int n_img, int T, int H, int which, float q_unscale, int keep_cls,
+// keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)
+int launch_facet(Precision p, const void* qkv, float* out, int n_img, int T, int P, int H, int which, float q_unscale, int keep_cls,
                  hipStream_t stream);
 // Saliency maps of the extractor (dinov2_extractor.py:339-353): out fp32 [n_img][T], class-token attention of the chosen heads
-// of the block whose qkv is given, averaged and min-max normalised per image.
-int launch_saliency(Precision p, const void* qkv, float* out, int n_img, int T, int H, const int* head_idx, int n_heads,
+// of the block whose qkv is given ([n_img][P+T] rows: softmax over all P + T keys, patch columns kept), averaged and min-max
+// normalised per image.
+int launch_saliency(Precision p, const void* qkv, float* out, int n_img, int T, int P, int H, const int* head_idx, int n_heads,
                     bool q_prescaled, hipStream_t stream);
 // Pillow-exact bicubic resize of n RGB uint8 frames [in_h][in_w][3] -> [out][out][3] (resize.hip).  The tables come from
 // resize_coefficients (host, double precision, Pillow's expressions): bounds [out][2] = (first tap, taps), coefficients

@@ -66,14 +66,17 @@ class Engine:
         self._c = c
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self.lib.vitvs_create(C.byref(c), C.byref(self.handle))
+            if cfg.registers:
+                rc = self.lib.vitvs_create_ex(C.byref(c), cfg.registers, C.byref(self.handle))
+            else:
+                rc = self.lib.vitvs_create(C.byref(c), C.byref(self.handle))
         if rc != 0:
             raise VitvsError(f"vitvs_create failed ({rc}): {_lib.last_error(None)}")
         self.frame_size = (cfg.img_size, cfg.img_size)   # geometry of the frames the calls take (set_frame_size)
         self._last_host_pairs = 1                         # pairs of the last host-pointer velocity call (reselect_host)
         self.tokens = self.lib.vitvs_tokens(self.handle)
         self.desc_dim = self.lib.vitvs_desc_dim(self.handle)
-        assert self.tokens == cfg.tokens
+        assert self.tokens == cfg.tokens and self.lib.vitvs_register_tokens(self.handle) == cfg.registers
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -103,7 +106,7 @@ class Engine:
             elif name.startswith("blocks."):
                 if int(name.split(".")[1]) >= self.cfg.blocks_run:
                     continue
-            elif name not in ("patch_embed.proj.weight", "patch_embed.proj.bias", "cls_token"):
+            elif name not in ("patch_embed.proj.weight", "patch_embed.proj.bias", "cls_token", "register_tokens"):
                 continue
             a = np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy())
             rc = self.lib.vitvs_set_tensor(self.handle, name.encode(), a.ctypes.data_as(C.c_void_p), a.size)
@@ -144,8 +147,8 @@ class Engine:
 
     # ------------------------------------------------------------------ seams
     def forward_tokens(self, frames) -> torch.Tensor:
-        """Residual stream after block ``layer``: float32 [n, 1+T, D] (the hooked tensor,
-        reference: dinov2_extractor.py:198-199)."""
+        """Residual stream after block ``layer``: float32 [n, 1+R+T, D] (the hooked tensor,
+        reference: dinov2_extractor.py:198-199; rows cls, the R register tokens, the patches)."""
         f = self._frames(frames)
         n = f.shape[0]
         out = torch.empty((n, self.cfg.seq, self.cfg.dim), dtype=torch.float32, device=self.device)

@@ -25,7 +25,7 @@ def expected_tensors(cfg: ViTConfig) -> Dict[str, tuple]:
         "patch_embed.proj.weight": (d, 3, p, p),
         "patch_embed.proj.bias": (d,),
         "cls_token": (1, 1, d),
-        "pos_embed": (1, 1 + g * g, d),
+        "pos_embed": (1, 1 + g * g, d),   # cls + patches: register tokens carry no position embedding
     }
     for i in range(cfg.blocks_run):
         b = f"blocks.{i}."
@@ -44,6 +44,8 @@ def expected_tensors(cfg: ViTConfig) -> Dict[str, tuple]:
         if cfg.layerscale:
             out[b + "ls1.gamma"] = (d,)
             out[b + "ls2.gamma"] = (d,)
+    if cfg.registers:
+        out["register_tokens"] = (1, cfg.registers, d)   # last: the draws of every other tensor match the plain model's
     return out
 
 
@@ -54,7 +56,7 @@ def synthetic_state_dict(cfg: ViTConfig, seed: int = 0, affine_jitter: bool = Tr
     sd: Dict[str, torch.Tensor] = {}
     for name, shape in expected_tensors(cfg).items():
         leaf = name.rsplit(".", 1)[-1]
-        if name in ("cls_token", "pos_embed"):
+        if name in ("cls_token", "pos_embed", "register_tokens"):
             t = torch.randn(shape, generator=gen) * 0.02
         elif leaf == "gamma":
             t = 1.0 + (torch.rand(shape, generator=gen) - 0.5) * (0.5 if affine_jitter else 0.0)
@@ -122,6 +124,10 @@ def resample_pos_embed(pos_embed: torch.Tensor, grid: int) -> torch.Tensor:
 
 
 def check_state_dict(cfg: ViTConfig, sd: Dict[str, torch.Tensor]) -> None:
+    if "register_tokens" in sd and not cfg.registers:
+        # a "_reg" checkpoint under its plain model's name: the network would run without the registers it was trained with
+        raise ValueError(f"state dict holds register_tokens {tuple(sd['register_tokens'].shape)} but {cfg.model_type!r} has "
+                         f"none: load it as {cfg.model_type + '_reg'!r}")
     want = expected_tensors(cfg)
     missing = [k for k in want if k not in sd]
     if missing:
