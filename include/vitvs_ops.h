@@ -67,6 +67,12 @@ VITVS_API int vitvs_op_plan_in_flight(int32_t n);
 /* the tile the library launches for a linear layer: tile[0..2] = rows, columns, k-groups (k-groups 0: the 256-row kernels of
  * gemm_big.hip); slices = 0: vitvs_op_linear, > 0: vitvs_op_linear_partial with that many K slices.  No device work. */
 VITVS_API int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* tile);
+/* the attention launch the library makes for vitvs_op_attention / _q (and the handle's forward) at this shape, under the
+ * calling thread's plan hint: out[0..5] = kernel, workgroups, threads per workgroup, dynamic LDS bytes, key tiles per
+ * workgroup (long kernel; 0 otherwise), divided (1: the 16-bit long kernel cuts the keys of a query block into ranges merged
+ * through the workspace).  Kernels: 1 fp32; 2 short (16 queries per workgroup); 3 64 queries per workgroup; 4 the same with
+ * two key groups; 5 long (128 queries per workgroup).  Returns 0, or -2 (out[0] = 0) when a size is not positive.  No device work. */
+VITVS_API int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t H, int32_t* out);
 VITVS_API int vitvs_op_linear_partial(int32_t precision, const void* A, const void* W, float* part, int32_t M, int32_t N,
                             int32_t K, int32_t slices, void* stream);
 VITVS_API int vitvs_op_residual_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias,

@@ -142,3 +142,45 @@ def test_linear_tile_plan_of_the_library():
             assert (got, list(t)) == (rc, tile), (hint, prec, m, n, k, slices)
     finally:
         lib.vitvs_op_plan_in_flight(prev)
+
+
+def test_attention_plan_of_the_library():
+    """The attention launch per shape is host arithmetic too (vitvs_op_attention_plan, no device call): kernel, workgroups,
+    threads, dynamic LDS bytes, key tiles per workgroup, divided.  Every attention kernel is exact for every shape it accepts,
+    so the numeric tests pass whichever one is picked; this pins the pick."""
+    import numpy as np
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 6)()
+
+    def plan(prec, n_img, n, h):
+        assert lib.vitvs_op_attention_plan(prec, n_img, n, h, out) == 0
+        return list(out)
+    prev = lib.vitvs_op_plan_in_flight(1)
+    try:
+        # one ViT-B/16 224 pair: the 16-query kernel, 312 workgroups
+        assert plan(_lib.BF16, 2, 197, 12) == [2, 312, 256, 4 * 8192 + 4 * 5 * 64 * 16, 0, 0]
+        # one ViT-B/8 448 pair alone: the long kernel, key ranges of 25 tiles (half an item) merged through the workspace
+        assert plan(_lib.BF16, 2, 3137, 12) == [5, 1200, 256, 3 * 2 * 64 * 128 + 16, 25, 1]
+        # the same pair in f16x2: its own long kernel (from 2048 tokens), whole items
+        assert plan(_lib.F16X2, 2, 3137, 12) == [5, 600, 256, 3 * 2 * 32 * 256, 50, 0]
+        lib.vitvs_op_plan_in_flight(3)
+        # beside other updates: whole items, no workspace
+        assert plan(_lib.BF16, 2, 3137, 12) == [5, 600, 256, 3 * 2 * 64 * 128 + 16, 50, 0]
+    finally:
+        lib.vitvs_op_plan_in_flight(prev)
+    assert lib.vitvs_op_attention_plan(_lib.BF16, 0, 197, 12, out) == -2 and out[0] == 0
+    # The whole table: hints {1, 3} x the four precisions x H in {2, 4, 6, 12, 16} x n_img in {1 .. 16, 24, 32, 49, 96} x N on
+    # both sides of every threshold and at every config's sequence length (with and without register tokens).  Columns: hint,
+    # precision, n_img, N, H, return code, out[0..5]; recorded through this ABI and checked against the kernels the parent
+    # library launched for every row.
+    table = np.load(os.path.join(ROOT, "tests", "golden", "attention_plans.npz"))["plans"]
+    assert len(table) == 2 * 4 * 5 * 20 * 23
+    assert (table[table[:, 1] == _lib.F32, 6] == 1).all()   # fp32 is always the fp32 kernel
+    prev = lib.vitvs_op_plan_in_flight(1)
+    try:
+        for hint, prec, n_img, n, h, rc, *want in table.tolist():
+            lib.vitvs_op_plan_in_flight(hint)
+            got = lib.vitvs_op_attention_plan(prec, n_img, n, h, out)
+            assert (got, list(out)) == (rc, want), (hint, prec, n_img, n, h)
+    finally:
+        lib.vitvs_op_plan_in_flight(prev)

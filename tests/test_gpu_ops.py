@@ -400,7 +400,7 @@ def test_long_attention_deferred_rescale_with_slowly_growing_scores(lib, slope):
 # ------------------------------------------------------------------------------------------------------------------
 # The many-row selections of the "in_flight" hint (vitvs_set_option; kernels.h g_updates_in_flight): 256 x 256 tiles wherever they
 # divide from 1536 rows on (gemm.hip big_tile), at most two K slices and exactly two from 2048 rows on for the narrow
-# layers (gemm.hip splitk_slices), whole query blocks in the long-sequence attention (attention.hip attention_plan).  Row counts:
+# layers (gemm.hip splitk_slices), whole query blocks in the long-sequence attention (attention.hip plan_attention).  Row counts:
 # 4 / 8 ViT-B/16 pairs (1576 / 3152), ViT-B/8 448² (6274), ViT-L/14 518² (2740).
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])
 @pytest.mark.parametrize("M,N,K,gelu", [(1576, 2304, 768, 0), (1576, 3072, 768, 1), (3152, 2304, 768, 0), (3152, 3072, 768, 1),
@@ -471,9 +471,12 @@ def test_split_k_pair_many_rows_under_the_in_flight_plan(lib, in_flight_plan, na
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])
 @pytest.mark.parametrize("n_img,N,H", [(2, 3137, 12), (2, 1370, 16), (1, 3026, 6), (16, 197, 12)])
 def test_attention_under_the_in_flight_plan(lib, in_flight_plan, name, prec, dtype, tol, n_img, N, H):
-    """Long sequences under the hint: whole query blocks per workgroup (no key ranges, no hand-off), with the forward's
-    pre-scaled q; against the fp64 softmax and bit for bit against the divided plan's merge order?  No: the divided plan sums
-    the same tiles in ranges, so the two agree to rounding only — asserted at the operator tolerance."""
+    """Long sequences under the hint: the long kernel with whole query blocks per workgroup (no key ranges, no hand-off), with
+    the forward's pre-scaled q; against the fp64 softmax, and against the alone plan (which may cut the keys into ranges: the
+    two agree to rounding only) at the operator tolerance."""
+    plan = (C.c_int32 * 6)()
+    assert lib.vitvs_op_attention_plan(prec, n_img, N, H, plan) == 0
+    assert plan[0] == 5 and plan[5] == 0, f"the hint should select the long kernel with whole query blocks, got {list(plan)}"
     g = torch.Generator().manual_seed(N * 3 + H)
     D = H * 64
     qkv = _mk((n_img * N, 3 * D), g).to(dtype)

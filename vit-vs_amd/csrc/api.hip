@@ -370,7 +370,7 @@ struct ChainCtx {
     const ResizeArgs* rs = nullptr;   // camera-resolution frames (vitvs_set_frame_size): resize inside the patch-row build
     bool want_desc = false;   // the last residual_ln also writes the plain descriptors (launch_residual_ln)
     DescOut desc;
-    struct { LinearPlan embed, qkv, proj, fc1, fc2; } plan;   // of the chain's five linear shapes (forward_chain)
+    struct { LinearPlan embed, qkv, proj, fc1, fc2; AttnPlan attn; } plan;   // of the chain's six launch shapes (forward_chain)
 };
 
 // The forward, operator by operator, on one stream.  (The two FRAMES of one update as two chains — on two streams, or in
@@ -399,7 +399,7 @@ int forward_launches(vitvs_handle* h, const ChainCtx& cx, hipStream_t st) {
         { Span sp(h, KC_QKV, st);
             rc = launch_linear(cx.plan.qkv, cx.xn, b.qkvw, b.qkvb, cx.qkv, 0, st, b.qkve); }
         if (!rc) { Span sp(h, KC_ATTENTION, st);
-            rc = launch_attention(h->prec, cx.qkv, cx.attn, cx.cnt, h->N, c.heads, st, &h->attn_ws, plain16(h->prec)); }
+            rc = launch_attention(cx.plan.attn, cx.qkv, cx.attn, st, &h->attn_ws, plain16(h->prec)); }
         if (!rc) { Span sp(h, KC_PROJ, st);
             rc = launch_linear(cx.plan.proj, cx.attn, b.projw, nullptr, cx.part, 0, st, b.proje); }
         if (!rc) { Span sp(h, KC_RESIDUAL_LN, st);
@@ -457,6 +457,7 @@ int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
     cx.plan.proj = plan_linear(p, cx.M, D, D, EPI_PARTIAL);
     cx.plan.fc1 = plan_linear(p, cx.M, h->hidden, D, EPI_STORE);
     cx.plan.fc2 = plan_linear(p, cx.M, D, h->hidden, EPI_PARTIAL);
+    cx.plan.attn = plan_attention(p, cnt, h->N, h->cfg.heads);
     if (h->desc_keys >= 0 && desc_in_forward(h)) {
         cx.want_desc = true;
         if (h->cfg.binned) cx.desc.sq = h->sq + (size_t)i0 * h->T;
@@ -650,14 +651,12 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     {   // the key-split plan depends on the image count of a call: size for the largest need over 1 .. n_img_max, under the
         // plan of a handle that runs ALONE (in_flight 1: the divided plan, the only one that needs a workspace) — whatever hint
         // the calling thread carries (vitvs_op_plan_in_flight) and whatever `in_flight` the handle is given later
-        const int thread_hint = g_updates_in_flight;
-        g_updates_in_flight = 1;
         size_t f = 0, t = 0;
         for (int n = 1; n <= h->n_img_max; ++n) {
-            f = std::max(f, attention_workspace_floats(n, h->N, cfg->heads));
-            t = std::max(t, attention_ticket_count(n, h->N, cfg->heads));
+            const AttnPlan pl = plan_attention(h->prec, n, h->N, cfg->heads, /*in_flight=*/1);
+            f = std::max(f, pl.ws_floats);
+            t = std::max(t, pl.tickets);
         }
-        g_updates_in_flight = thread_hint;
         if (!rc && f) rc = dev_alloc(h, &h->attn_ws.state, f);
         if (!rc && t) rc = dev_alloc(h, &h->attn_ws.tickets, t);   // dev_alloc zeroes: the tickets start at 0
     }
@@ -1470,19 +1469,26 @@ int vitvs_op_layernorm(int32_t precision, const float* x, const float* gamma, co
 int vitvs_op_attention(int32_t precision, const void* qkv, void* out, int32_t n_img, int32_t N, int32_t H,
                        void* stream) {
     DeviceScope dev(nullptr);
-    return launch_attention(to_prec(precision), qkv, out, n_img, N, H, as_stream(stream));
+    return launch_attention(plan_attention(to_prec(precision), n_img, N, H), qkv, out, as_stream(stream));
 }
 int vitvs_op_attention_q(int32_t precision, const void* qkv, void* out, int32_t n_img, int32_t N, int32_t H,
                          int32_t q_prescaled, void* stream) {
     DeviceScope dev(nullptr);
     const Precision p = to_prec(precision);
-    return launch_attention(p, qkv, out, n_img, N, H, as_stream(stream), nullptr, q_prescaled != 0 && plain16(p));
+    return launch_attention(plan_attention(p, n_img, N, H), qkv, out, as_stream(stream), nullptr, q_prescaled != 0 && plain16(p));
 }
 int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* tile) {
     if (!tile) return -1;
     const LinearPlan pl = plan_linear(to_prec(precision), M, N, K, slices > 0 ? EPI_PARTIAL : EPI_STORE, slices);
     tile[0] = pl.rows; tile[1] = pl.cols; tile[2] = pl.rows && !pl.big ? pl.kgroups : 0;
     return pl.rows ? 0 : -2;
+}
+int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t H, int32_t* out) {
+    if (!out) return -1;
+    const AttnPlan pl = plan_attention(to_prec(precision), n_img, N, H);
+    out[0] = pl.kernel; out[1] = (int32_t)(pl.grid.x * pl.grid.y * pl.grid.z); out[2] = pl.threads; out[3] = pl.lds;
+    out[4] = pl.per; out[5] = pl.divided;
+    return pl.kernel == ATTN_NONE ? -2 : 0;
 }
 int vitvs_op_touch(const void* p, int64_t bytes, int32_t share_xcds, void* stream) {
     DeviceScope dev(nullptr);

@@ -271,7 +271,7 @@ __device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) { return __
 
 // Work division over key tiles.  The unit of work is one 64-key tile of one 128-query block; a launch has W = items x nt of them
 // (items = images x heads x query blocks, nt = key tiles per sequence), in item-major order.  Workgroup g walks the contiguous
-// range [g per, (g + 1) per) of that list; `per` comes from attention_plan() below (whole items, halves or quarters of an item:
+// range [g per, (g + 1) per) of that list; `per` comes from plan_attention() below (whole items, halves or quarters of an item:
 // the fewest ranges per item that minimise rounds x (tiles + hand-off)).  A range may cross item boundaries: it is cut into
 // segments, one per item it touches.  A segment that covers its item's whole key range finishes like a plain flash kernel.
 // Any other segment leaves its un-normalised state (O, running maximum, running sum) in `ws`, draws a ticket for its item, and
@@ -300,7 +300,7 @@ __device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) { return __
 // starts inside an item (its first), slot 1 = the one that starts an item and ends inside it (its last).
 constexpr int kAttnStateFloats = 9 * 64 * 4;                // per wave: 8 x 16 bytes of accumulators + (maximum, sum), lane-major
 
-// ONES (measured variant; launch_attention_16 has the outcome): the row sums l = sum_k P come out of the matrix
+// ONES (measured variant; plan_attention has the outcome): the row sums l = sum_k P come out of the matrix
 // pipe — a third 32-row block of V^T whose rows are all ones, i.e. one more MFMA per 16-key step with a constant A operand —
 // instead of 32 vector adds per tile; the fast path's headroom test then takes the maximum of the shifted scores (16 v_max3)
 // BEFORE the exponentials rather than the sum of the probabilities after them.
@@ -1548,7 +1548,8 @@ __global__ __launch_bounds__(256) void attention_x2_short_kernel(const hx2* __re
     if (q < N) store_x2<true>(out + ((size_t)img * N + q) * D * 2, h * 64 + 16 * wave + 4 * g, f32x4{o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv});
 }
 
-// Work division of the long-sequence kernel: `per` key tiles per workgroup (see the kernel's header).  Measured on MI355X
+// Every choice of an attention launch, made once: the kernel for precision p and the shape, its grid, block and LDS, and the
+// work division of the 16-bit long kernel, `per` key tiles per workgroup (see the kernel's header).  Measured on MI355X
 // (profiles/r03_notes.md, attention): the three workgroups a CU holds do NOT share it evenly — issue arbitration is by age, the
 // first-dispatched workgroup runs almost unimpeded — and three resident workgroups finish tiles only 1.3x faster than one, so an
 // even cut of the list over 768 co-resident workgroups (every CU the same work, all ending together) gains nothing over whole
@@ -1556,35 +1557,59 @@ __global__ __launch_bounds__(256) void attention_x2_short_kernel(const hx2* __re
 // CUs as units finish and the hand-offs of one unit hide behind the tiles of its neighbours.  The plan is therefore the
 // fewest ranges per item, of {1, 2, 4}, that minimises (rounds of 256 units) x (tiles per unit + 1.5 tiles of hand-off); a
 // range keeps at least 4 key tiles.
-struct AttnPlan { int per, groups; bool divided; };
-static AttnPlan attention_plan(int n_img, int N, int H) {
+AttnPlan plan_attention(Precision p, int n_img, int N, int H, int in_flight) {
+    AttnPlan pl{p, ATTN_NONE, n_img, N, H, dim3(0, 0, 0)};
+    if (n_img <= 0 || N <= 0 || H <= 0) return pl;
+    const bool x2 = p == PREC_X2;
     const int nt = (N + 63) / 64;
-    const long items = (long)((N + 127) / 128) * H * n_img;
-    const long W = items * nt;
-    AttnPlan best{nt, (int)items, false};
-    if (N < 512) return best;                                   // short sequences in batches: whole items (tools/big_ops attnmid)
-    // Beside other queues' launches (vitvs_set_option "in_flight") the chip is filled by THEIR workgroups: whole items, no hand-off
-    // (three updates in flight, same box: ViT-B/8 448² 419 -> 436 updates/s, ViT-L/14 518² 703 -> 732; the 64-query kernel of the
-    // mid sizes keeps its two key groups: ViT-S/14 308² 4480 -> 4333 without them)
-    if (g_updates_in_flight >= 2) return best;
-    double best_cost = 1e30;
-    for (int sp : {1, 2, 4}) {
-        if (sp > 1 && nt / sp < 4) break;
-        const int per = (nt + sp - 1) / sp;
-        const long units = (W + per - 1) / per;
-        const double cost = (double)((units + 255) / 256) * ((double)per + (sp > 1 ? 1.5 : 0.0));
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = AttnPlan{per, (int)units, sp > 1}; }   // ties: the fewer ranges
+    const long items16 = (long)((N + 15) / 16) * H * n_img, items = (long)((N + 127) / 128) * H * n_img;   // 16 / 128 queries each
+    const bool fits = (long)n_img * N * 3 * H * 64 * elem_size(p) < (1l << 32);   // short and long kernels: qkv below 4 GiB
+    pl.grid = dim3(nt, H, n_img);
+    pl.threads = 256;
+    if (p == PREC_F32) { pl.kernel = ATTN_F32; return pl; }
+    // (16-bit: the 16-query kernel beyond 640 workgroups: 16 images x 197 tokens 16.2 us against 12.6 us on the 64-query kernel)
+    if (N <= 256 && items16 <= 640 && fits) {
+        pl.kernel = ATTN_SHORT; pl.grid = dim3(8 * ((items16 + 7) / 8)); pl.lds = x2 ? 4 * 16384 : 4 * 8192 + 4 * 5 * 64 * 16;
+        return pl;
     }
-    return best;
-}
-int attention_splits(int n_img, int N, int H) { return attention_plan(n_img, N, H).divided ? 2 : 1; }   // (reported by tools only)
-
-size_t attention_workspace_floats(int n_img, int N, int H) {
-    const AttnPlan pl = attention_plan(n_img, N, H);
-    return pl.divided ? (size_t)2 * (8 * ((pl.groups + 7) / 8)) * 4 * kAttnStateFloats : 0;
-}
-size_t attention_ticket_count(int n_img, int N, int H) {
-    return attention_plan(n_img, N, H).divided ? (size_t)((N + 127) / 128) * H * n_img : 0;
+    // f16x2 (measured on one box, generic | this kernel, back to back on random operands: 2 x 3137 x 12 275 | 252 us,
+    //  2 x 1370 x 16 70 | 74 us, 2 x 485 x 6 11.5 | 18 us: it pays from a few thousand tokens on, where the generic kernel's
+    //  64-query workgroups stage K / V through registers twice as often)
+    // 16-bit: 128 queries per workgroup: from 512 tokens on, and for shorter sequences once the 64-query kernel no longer fits
+    // its 512-thread one-workgroup-per-CU form (each of its workgroups re-reads its head's K / V): 16 x 197 x 12 heads
+    // 12.7 -> 10.7 us, 6 x 485 x 6 heads 12.9 -> 10.9 us; equal at 6..12 x 197; below that bound the 64-query kernel wins
+    // (5 x 197, the rotation search: 5.3 vs 7.2 us; 5 x 485 x 6: 8.0 vs 10.7 us)  [tools/big_ops attnmid]
+    if (fits && (x2 ? N >= 2048 : (N >= 512 || (N >= 128 && (long)nt * H * n_img > 256)))) {
+        pl.kernel = ATTN_LONG; pl.per = nt;                         // whole items
+        pl.lds = x2 ? 3 * 2 * 32 * 256 : 3 * 2 * 64 * 128 + 16;
+        VITVS_IF_PROBE(if (!x2) pl.lds = g_attn_lds_bytes + 16;)
+        long groups = items;
+        // Short sequences in batches: whole items (tools/big_ops attnmid).  Beside other queues' launches (vitvs_set_option
+        // "in_flight") the chip is filled by THEIR workgroups: whole items, no hand-off (three updates in flight, same box:
+        // ViT-B/8 448² 419 -> 436 updates/s, ViT-L/14 518² 703 -> 732; the 64-query kernel of the mid sizes keeps its two key
+        // groups: ViT-S/14 308² 4480 -> 4333 without them)
+        if (!x2 && N >= 512 && in_flight < 2) {
+            double best_cost = 1e30;
+            for (int sp : {1, 2, 4}) {                            // ties: the fewer ranges
+                if (sp > 1 && nt / sp < 4) break;
+                const int per = (nt + sp - 1) / sp;
+                const long units = (items * nt + per - 1) / per;
+                const double cost = (double)((units + 255) / 256) * ((double)per + (sp > 1 ? 1.5 : 0.0));
+                if (cost < best_cost - 1e-9) { best_cost = cost; pl.per = per; groups = units; pl.divided = sp > 1; }
+            }
+        }
+        pl.g_per_xcd = (int)((groups + 7) / 8); pl.grid = dim3(8 * pl.g_per_xcd);
+        if (pl.divided) { pl.ws_floats = (size_t)2 * (8 * pl.g_per_xcd) * 4 * kAttnStateFloats; pl.tickets = (size_t)items; }
+        // Row sums on the matrix pipe (the ONES variant above): VITVS_ATTN_ONES=1 selects it for A/B runs; the measured outcome
+        // is in profiles/r05_notes.md — the default is what measured faster.
+        static const bool ones_variant = [] { const char* e = getenv("VITVS_ATTN_ONES"); return e && e[0] == '1'; }();
+        pl.ones = !x2 && ones_variant;
+        return pl;
+    }
+    const bool ks2 = (long)nt * H * n_img <= 256 && nt >= 2;       // 64 queries, two key groups of 4 waves
+    pl.kernel = ks2 ? ATTN_Q64_KS2 : ATTN_Q64; pl.threads = ks2 ? 512 : 256;
+    pl.lds = (ks2 ? 2 : 1) * 2 * 64 * (x2 ? 256 : 128);
+    return pl;
 }
 
 // The pointer-only operator hook (vitvs_op_attention) has no handle to own the key-split workspace: one per (device, stream),
@@ -1624,80 +1649,53 @@ static const AttnWorkspace* shared_attention_workspace(hipStream_t stream, size_
 }
 
 template <typename HT>
-static int launch_attention_16(const HT* qkv, HT* out, int n_img, int N, int H, hipStream_t stream, const AttnWorkspace* ws,
+static int launch_attention_16(const AttnPlan& pl, const HT* qkv, HT* out, hipStream_t stream, const AttnWorkspace* ws,
                                bool q_prescaled) {
-    const int D = H * 64;
+    const int N = pl.N, D = pl.H * 64;
     const float sc = q_prescaled ? 1.0f : kScaleLog2e;         // what is left to apply to q . k (log2 units)
-    const int nt = (N + 63) / 64;
-    dim3 grid(nt, H, n_img);
-    // (the 16-query kernel beyond 640 workgroups: 16 images x 197 tokens 16.2 us against 12.6 us on the 64-query kernel)
-    if (N <= 256 && (long)((N + 15) / 16) * H * n_img <= 640 && (long)n_img * N * 6 * D < (1l << 32)) {
-        const int items = ((N + 15) / 16) * H * n_img;
-        launch(attention_16_short_kernel<HT>, dim3(8 * ((items + 7) / 8)), dim3(256), 4 * 8192 + 4 * 5 * 64 * 16, stream, qkv,
-               out, N, D, n_img, sc);
-    } else if ((N >= 512 || (N >= 128 && (long)nt * H * n_img > 256)) && (long)n_img * N * 6 * D < (1l << 32)) {
-        // 128 queries per workgroup: from 512 tokens on, and for shorter sequences once the 64-query kernel no longer fits its
-        // 512-thread one-workgroup-per-CU form (each of its workgroups re-reads its head's K / V): 16 x 197 x 12 heads
-        // 12.7 -> 10.7 us, 6 x 485 x 6 heads 12.9 -> 10.9 us; equal at 6..12 x 197; below that bound the 64-query kernel wins
-        // (5 x 197, the rotation search: 5.3 vs 7.2 us; 5 x 485 x 6: 8.0 vs 10.7 us)  [tools/big_ops attnmid]
-        const AttnPlan pl = attention_plan(n_img, N, H);
+    const dim3 block(pl.threads);
+    if (pl.kernel == ATTN_SHORT) {
+        launch(attention_16_short_kernel<HT>, pl.grid, block, pl.lds, stream, qkv, out, N, D, pl.n_img, sc);
+    } else if (pl.kernel == ATTN_LONG) {
         if (pl.divided) {
-            if (!ws) ws = shared_attention_workspace(stream, attention_workspace_floats(n_img, N, H), attention_ticket_count(n_img, N, H));
+            if (!ws) ws = shared_attention_workspace(stream, pl.ws_floats, pl.tickets);
             if (!ws || !ws->state || !ws->tickets) return -3;
         }
-        int lds = 3 * 2 * 64 * 128 + 16;
         VITVS_IF_PROBE(
-            lds = g_attn_lds_bytes + 16;
-            if (lds > 64 * 1024) {
+            if (pl.lds > 64 * 1024) {
                 static std::atomic<unsigned long long> raised{0};
                 if (raise_lds_limit((const void*)attention_16_long_kernel<HT, false>, 160 * 1024, raised)) return -3;
             }
         )
-        const int g_per_xcd = (pl.groups + 7) / 8;
-        // Row sums on the matrix pipe (the ONES variant above): VITVS_ATTN_ONES=1 selects it for A/B runs; the measured outcome is
-        // in profiles/r05_notes.md — the default is what measured faster.
-        static const bool ones_variant = [] { const char* e = getenv("VITVS_ATTN_ONES"); return e && e[0] == '1'; }();
-        if (ones_variant)
-            launch((attention_16_long_kernel<HT, true>), dim3(8 * g_per_xcd), dim3(256), lds, stream, qkv, out, N, D, n_img, pl.per, g_per_xcd, sc,
-                   pl.divided ? ws->state : nullptr, pl.divided ? ws->tickets : nullptr);
-        else
-            launch((attention_16_long_kernel<HT, false>), dim3(8 * g_per_xcd), dim3(256), lds, stream, qkv, out, N, D, n_img, pl.per, g_per_xcd, sc,
-                   pl.divided ? ws->state : nullptr, pl.divided ? ws->tickets : nullptr);
-    } else if ((long)nt * H * n_img <= 256 && nt >= 2) {
-        launch((attention_16_kernel<HT, 2>), grid, dim3(512), 2 * 2 * 64 * 128, stream, qkv, out, N, D, sc);
+        launch(pl.ones ? attention_16_long_kernel<HT, true> : attention_16_long_kernel<HT, false>, pl.grid, block, pl.lds, stream,
+               qkv, out, N, D, pl.n_img, pl.per, pl.g_per_xcd, sc, pl.divided ? ws->state : nullptr, pl.divided ? ws->tickets : nullptr);
     } else {
-        launch((attention_16_kernel<HT, 1>), grid, dim3(256), 2 * 64 * 128, stream, qkv, out, N, D, sc);
+        launch(pl.kernel == ATTN_Q64_KS2 ? attention_16_kernel<HT, 2> : attention_16_kernel<HT, 1>, pl.grid, block, pl.lds, stream,
+               qkv, out, N, D, sc);
     }
     return 0;
 }
 
-int launch_attention(Precision p, const void* qkv, void* out, int n_img, int N, int H, hipStream_t stream,
-                     const AttnWorkspace* ws, bool q_prescaled) {
-    if (n_img <= 0 || N <= 0 || H <= 0) return -2;
-    const int D = H * 64;
-    const int nt = (N + 63) / 64;
-    dim3 grid(nt, H, n_img);
+int launch_attention(const AttnPlan& pl, const void* qkv, void* out, hipStream_t stream, const AttnWorkspace* ws,
+                     bool q_prescaled) {
+    if (pl.kernel == ATTN_NONE) return -2;
+    const int N = pl.N, D = pl.H * 64;
+    const dim3 block(pl.threads);
     int rc = 0;
-    if (p == PREC_X2) {
-        const int items16 = ((N + 15) / 16) * H * n_img;
-        if (N <= 256 && items16 <= 640 && (long)n_img * N * 12 * D < (1l << 32))
-            launch(attention_x2_short_kernel, dim3(8 * ((items16 + 7) / 8)), dim3(256), 4 * 16384, stream, (const hx2*)qkv, (hx2*)out, N, D, n_img);
-        else if (N >= 2048 && (long)n_img * N * 12 * D < (1l << 32)) {
-            // (measured on one box, generic | this kernel, back to back on random operands: 2 x 3137 x 12 275 | 252 us, 2 x 1370 x 16 70 | 74 us,
-            //  2 x 485 x 6 11.5 | 18 us: it pays from a few thousand tokens on, where the generic kernel's 64-query workgroups stage
-            //  K / V through registers twice as often)
-            const int items = ((N + 127) / 128) * H * n_img, g_per_xcd = (items + 7) / 8;
-            launch(attention_x2_long_kernel, dim3(8 * g_per_xcd), dim3(256), 3 * 2 * 32 * 256, stream, (const hx2*)qkv, (hx2*)out, N, D, n_img, g_per_xcd);
-        } else if ((long)nt * H * n_img <= 256 && nt >= 2)
-            launch((attention_x2_kernel<2>), grid, dim3(512), 2 * 2 * 64 * 256, stream, (const hx2*)qkv, (hx2*)out, N, D);
+    if (pl.prec == PREC_X2) {
+        const hx2* x = (const hx2*)qkv; hx2* o = (hx2*)out;
+        if (pl.kernel == ATTN_SHORT)
+            launch(attention_x2_short_kernel, pl.grid, block, pl.lds, stream, x, o, N, D, pl.n_img);
+        else if (pl.kernel == ATTN_LONG)
+            launch(attention_x2_long_kernel, pl.grid, block, pl.lds, stream, x, o, N, D, pl.n_img, pl.g_per_xcd);
         else
-            launch((attention_x2_kernel<1>), grid, dim3(256), 2 * 64 * 256, stream, (const hx2*)qkv, (hx2*)out, N, D);
-    } else if (p == PREC_F32) {
-        launch(attention_f32_kernel, grid, dim3(256), 0, stream, (const float*)qkv, (float*)out, N, D);
-    } else if (p == PREC_F16) {
-        rc = launch_attention_16<f16>((const f16*)qkv, (f16*)out, n_img, N, H, stream, ws, q_prescaled);
+            launch(pl.kernel == ATTN_Q64_KS2 ? attention_x2_kernel<2> : attention_x2_kernel<1>, pl.grid, block, pl.lds, stream, x, o, N, D);
+    } else if (pl.prec == PREC_F32) {
+        launch(attention_f32_kernel, pl.grid, block, pl.lds, stream, (const float*)qkv, (float*)out, N, D);
+    } else if (pl.prec == PREC_F16) {
+        rc = launch_attention_16<f16>(pl, (const f16*)qkv, (f16*)out, stream, ws, q_prescaled);
     } else {
-        rc = launch_attention_16<bf16>((const bf16*)qkv, (bf16*)out, n_img, N, H, stream, ws, q_prescaled);
+        rc = launch_attention_16<bf16>(pl, (const bf16*)qkv, (bf16*)out, stream, ws, q_prescaled);
     }
     if (rc) return rc;
     return hipGetLastError() == hipSuccess ? 0 : -1;

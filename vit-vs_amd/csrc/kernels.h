@@ -37,7 +37,8 @@ inline void launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stre
 }
 
 // Updates the calling handle expects to run beside its own (vitvs_set_option "in_flight"; set by api.hip around a handle's
-// launches, 1 otherwise).  From 2 on the one-round GEMM launches of gemm.hip use 4-wave workgroups (plan_linear).
+// launches, 1 otherwise).  From 2 on the one-round GEMM launches of gemm.hip use 4-wave workgroups (plan_linear), and the
+// long-sequence attention keeps whole query blocks (plan_attention).
 extern thread_local int g_updates_in_flight;
 
 // The HIP device the calling thread's current entry point runs on (set by the C-ABI layer's DeviceScope; api.hip).
@@ -171,22 +172,39 @@ int launch_normalize_rows(const float* src, float* dst, int rows, int Dp, hipStr
 
 // ---- attention.hip -------------------------------------------------------------------------
 // out[img*N + q][h*64 + d] = softmax_k(q.k * 64^-0.5) v ; qkv [n_img*N][3*D] in precision p.
-// Long sequences (>= 512 tokens) may cut the keys of a query block into ranges merged inside the launch; that needs a
-// workspace: `state` (attention_workspace_floats floats) and `tickets` (attention_ticket_count ints, ZERO before the first
-// launch; every launch leaves them zero).  ws = nullptr: a per-device workspace shared by all callers without one (the
-// operator hook), grown on demand.
+// One attention launch, decided by plan_attention and carried out by launch_attention.  The kernels (the codes are ABI:
+// vitvs_op_attention_plan): ATTN_F32 the fp32 kernel; ATTN_SHORT 16 queries per workgroup (<= 256 tokens, few workgroups);
+// ATTN_Q64 / ATTN_Q64_KS2 64 queries per workgroup, one or two key groups; ATTN_LONG 128 queries per workgroup.  ATTN_NONE:
+// a non-positive size.
+enum AttnKernel : int { ATTN_NONE = 0, ATTN_F32, ATTN_SHORT, ATTN_Q64, ATTN_Q64_KS2, ATTN_LONG };
+struct AttnPlan {
+    Precision prec = PREC_F32;
+    AttnKernel kernel = ATTN_NONE;
+    int n_img = 0, N = 0, H = 0;
+    dim3 grid;
+    int threads = 0, lds = 0;     // block size, dynamic LDS bytes
+    int per = 0, g_per_xcd = 0;   // ATTN_LONG: key tiles per range, workgroups per XCD
+    bool divided = false;         // 16-bit ATTN_LONG cut into key ranges: needs the workspace below
+    size_t ws_floats = 0, tickets = 0;
+    bool ones = false;            // 16-bit ATTN_LONG: the ONES variant (VITVS_ATTN_ONES, attention.hip)
+};
+// The plan under the hint `in_flight` of updates in flight (by default the calling thread's, g_updates_in_flight): from 2 on
+// the long kernel keeps whole query blocks.
+AttnPlan plan_attention(Precision p, int n_img, int N, int H, int in_flight = g_updates_in_flight);
+// A divided plan merges the key ranges of a query block inside the launch through a workspace: `state` (plan.ws_floats
+// floats) and `tickets` (plan.tickets ints, ZERO before the first launch; every launch leaves them zero).  ws = nullptr: a
+// per-(device, stream) workspace shared by all callers without one (the operator hook), grown on demand.
+// Returns -2 for ATTN_NONE, -3 when a divided plan gets no workspace.
 struct AttnWorkspace {
     float* state = nullptr;
     int* tickets = nullptr;
 };
-size_t attention_workspace_floats(int n_img, int N, int H);
-size_t attention_ticket_count(int n_img, int N, int H);
 // q_prescaled (16-bit precisions only): the q third of qkv already carries hd^-0.5 * log2(e) (kAttnQScale) — the handle folds it
 // into the q rows of attn.qkv.weight / bias at upload, in fp32 before the one rounding to 16 bits, so the scale costs the
 // forward neither an instruction nor a rounding; raw q (the operator hook) is scaled inside the kernels.
 constexpr float kAttnQScale = 0.125f * 1.44269504088896340736f;
-int launch_attention(Precision p, const void* qkv, void* out, int n_img, int N, int H, hipStream_t stream,
-                     const AttnWorkspace* ws = nullptr, bool q_prescaled = false);
+int launch_attention(const AttnPlan& plan, const void* qkv, void* out, hipStream_t stream, const AttnWorkspace* ws = nullptr,
+                     bool q_prescaled = false);
 
 // ---- correspond.hip ------------------------------------------------------------------------
 // For pair b: S = dn[a_img(b)] . dn[b_img(b)]^T (T x T, fp32); row_best[b][i] / col_best[b][j] receive
