@@ -67,6 +67,11 @@ VITVS_API int vitvs_op_plan_in_flight(int32_t n);
 /* the tile the library launches for a linear layer: tile[0..2] = rows, columns, k-groups (k-groups 0: the 256-row kernels of
  * gemm_big.hip); slices = 0: vitvs_op_linear, > 0: vitvs_op_linear_partial with that many K slices.  No device work. */
 VITVS_API int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* tile);
+/* the linear launch the library makes at this shape under the calling thread's plan hint, no device work:
+ * epilogue 0 store (vitvs_op_linear), 1 partial sums (vitvs_op_linear_partial; slices 0 = the library's count);
+ * out[0..6] = big family (gemm_big.hip), rows, columns, k-groups, ring stages, K slices, XCD map.  0, or -2 when unlaunchable.
+ * (k-groups 0: the kernels of gemm_big.hip; ring stages 0: the tile's default ring.) */
+VITVS_API int vitvs_op_linear_plan(int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* out);
 /* the attention launch the library makes for vitvs_op_attention / _q (and the handle's forward) at this shape, under the
  * calling thread's plan hint: out[0..5] = kernel, workgroups, threads per workgroup, dynamic LDS bytes, key tiles per
  * workgroup (long kernel; 0 otherwise), divided (1: the 16-bit long kernel cuts the keys of a query block into ranges merged

@@ -82,6 +82,7 @@ PROTOTYPES = {
     "vitvs_op_touch": (_I, [_P, C.c_int64, _I, _P]),
     "vitvs_op_linear_tile": (_I, [_I, _I, _I, _I, _I, _P]),
     "vitvs_op_attention_plan": (_I, [_I, _I, _I, _I, _P]),
+    "vitvs_op_linear_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "vitvs_op_linear_partial": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vitvs_op_residual_ln": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, C.c_float, _P]),
 }

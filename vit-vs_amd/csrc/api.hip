@@ -1483,6 +1483,13 @@ int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int32_t K, int
     tile[0] = pl.rows; tile[1] = pl.cols; tile[2] = pl.rows && !pl.big ? pl.kgroups : 0;
     return pl.rows ? 0 : -2;
 }
+int vitvs_op_linear_plan(int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* out) {
+    if (!out || (epilogue != EPI_STORE && epilogue != EPI_PARTIAL) || slices < 0) return -1;
+    const LinearPlan pl = plan_linear(to_prec(precision), M, N, K, (LinearEpi)epilogue, slices);
+    out[0] = pl.big; out[1] = pl.rows; out[2] = pl.cols; out[3] = pl.rows && !pl.big ? pl.kgroups : 0; out[4] = pl.stages;
+    out[5] = pl.splits; out[6] = pl.xcd_map;
+    return pl.rows ? 0 : -2;
+}
 int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t H, int32_t* out) {
     if (!out) return -1;
     const AttnPlan pl = plan_attention(to_prec(precision), n_img, N, H);
