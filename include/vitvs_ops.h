@@ -78,6 +78,26 @@ VITVS_API int vitvs_op_linear_plan(int32_t precision, int32_t epilogue, int32_t 
  * through the workspace).  Kernels: 1 fp32; 2 short (16 queries per workgroup); 3 64 queries per workgroup; 4 the same with
  * two key groups; 5 long (128 queries per workgroup).  Returns 0, or -2 (out[0] = 0) when a size is not positive.  No device work. */
 VITVS_API int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t H, int32_t* out);
+/* the Gram stage a handle (precision, binned descriptors, T tokens, model width D, max_pairs) runs for a call of n_pairs pairs, no
+ * device work: out[0..6] = form, tile rows, columns, k-groups, band rows, workgroups per XCD, split operands.  Forms: 1 fused
+ * arg-max over fp32 descriptors; 2 the same from the fp16 hi / lo split (16-bit modes from 1024 tokens); 3 raw token Gram + 3 x 3
+ * stencil arg-max (binned; the tile is the raw Gram's); 4 binned descriptors taken 9 D wide (the raw Gram workspace would pass
+ * 8 GiB).  Returns 0, or -2 when unlaunchable. */
+VITVS_API int vitvs_op_gram_plan(int32_t precision, int32_t binned, int32_t T, int32_t D, int32_t n_pairs, int32_t max_pairs,
+                       int32_t* out);
+/* The fused Gram arg-max of the velocity path on caller-normalised descriptors dn [n_des + n_pairs][T][Dp] fp32 (desired frames
+ * first; n_des = 1 with des_shared): the plan of vitvs_op_gram_plan(precision, 0, T, Dp, n_pairs, n_pairs), the split into dh
+ * (3 (n_des + n_pairs) T Dp fp16, only when the plan splits) and the keys row_best / col_best [n_pairs][T] (cleared here), decoded
+ * into nn_1 / nn_2 / sim_1 [n_pairs][T]. */
+VITVS_API int vitvs_op_gram_argmax(int32_t precision, const float* dn, int32_t T, int32_t Dp, int32_t n_pairs, int32_t des_shared,
+                         void* dh, uint64_t* row_best, uint64_t* col_best, int32_t* nn_1, int32_t* nn_2, float* sim_1,
+                         void* stream);
+/* The binned form: x = residual-stream rows [n_des + n_pairs][P + T][D] fp32 (P prefix rows skipped), grid * grid = T.  Token
+ * squared norms into sq [n_des + n_pairs][T], raw token Gram into G [n_pairs][T][T], stencil arg-max into the keys, decoded as
+ * above. */
+VITVS_API int vitvs_op_gram_stencil(const float* x, int32_t T, int32_t P, int32_t D, int32_t grid, int32_t n_pairs,
+                          int32_t des_shared, float* G, float* sq, uint64_t* row_best, uint64_t* col_best, int32_t* nn_1,
+                          int32_t* nn_2, float* sim_1, void* stream);
 VITVS_API int vitvs_op_linear_partial(int32_t precision, const void* A, const void* W, float* part, int32_t M, int32_t N,
                             int32_t K, int32_t slices, void* stream);
 VITVS_API int vitvs_op_residual_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias,

@@ -1550,7 +1550,8 @@ def test_identical_frames_take_the_same_image_shortcut_and_give_zero_velocity(ex
 @pytest.mark.parametrize("exact", EXACT)
 def test_dense_correspondence_and_interaction_matrix_at_3136_tokens(exact):
     """BASELINE configs[2]: DINO ViT-B/8 448² — every mutual nearest neighbour of the 3136 tokens enters L_e (thousands of
-    rows: the interaction matrix lives in the global workspace and the pseudo-inverse runs as one-sided Jacobi SVD).
+    rows: the interaction matrix lives in the global workspace; it has full column rank, so the pseudo-inverse is the LDL^T
+    solution of the normal equations, info[4] = -1, not the one-sided Jacobi SVD of the rank-deficient case).
     The law is checked against the oracle GIVEN the device's own nearest-neighbour tables (their parity with the oracle's
     similarity matrix is test_compute_velocity_fp32_many_tokens)."""
     key = "vitb8_448"
@@ -1568,6 +1569,7 @@ def test_dense_correspondence_and_interaction_matrix_at_3136_tokens(exact):
     mutual = np.nonzero(nn2[nn1] == np.arange(cfg.tokens))[0]
     assert int(st[0]) == 0 and len(mutual) > 128                       # more rows than the on-chip L_e holds
     assert int(det["info"][0, 1]) == len(mutual) and det["selected"][0, :len(mutual)].tolist() == mutual.tolist()
+    assert int(det["info"][0, 4]) == -1 and int(det["info"][0, 5]) == 2 * len(mutual)     # LDL^T over all the rows
     p1 = torch.from_numpy(np.stack([mutual // g, mutual % g], 1))
     p2 = torch.from_numpy(np.stack([nn1[mutual] // g, nn1[mutual] % g], 1))
     s_star, s = sr.calculate_uv(sr.patch_centres(p1, cfg.img_size, g), sr.patch_centres(p2, cfg.img_size, g), len(mutual),

@@ -1,0 +1,301 @@
+"""Every code path of the control law (servo.hip) against the oracle's numpy law (GPU).
+
+servo_kernel picks among several paths: the depth prefetch (T <= 256) or direct depth reads; the one-position ballot scan
+(T <= 256) or the shuffle scan over ceil(T / 256) positions per thread, with tail threads holding none (T = 289: threads from
+145 on); L in LDS (R = 2 * rows <= 128) or in the global workspace with column stride 2 * max_rows; the LDL^T normal equations or,
+when a pivot falls below 1e-8 of its diagonal, one-sided Jacobi SVD, whose lanes loop over several rows once R > 64.  Every case
+asserts which solver ran through info[4] (-1: LDL^T, otherwise the Jacobi sweeps, <= 40) and R through info[5], and checks the
+law against oracle/servo_ref (numpy pinv): s_uv exact, Z exact, L within 1e-13, v_c within 1e-9 (relative L2).  The tables go
+in through vitvs_servo_from_nn_dev (tiny handles, T up to 1024) or come from velocity calls of the 2-block tiny model.
+Also here: the reselect state of the host-pointer entry point ends with every call that rewrites the arg-max keys."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+import vitvs_amd  # noqa: F401
+from vitvs_amd import _lib, config, synth, weights
+from vitvs_amd.engine import Engine, VitvsError
+from oracle import servo_ref as sr
+
+pytestmark = pytest.mark.gpu
+
+LDLT = -1
+MAX_SWEEPS = 40
+VC_BAR, L_BAR = 1e-9, 1e-13
+
+
+def _tiny_cfg(img):
+    base = config.vit_config("dino_vits16", img)
+    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
+
+
+def _rel_l2(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def _tables(rng, t, n_boost):
+    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
+    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
+    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
+    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
+    nn1, nn2 = nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64)
+    mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
+    assert 0 < len(mutual) < t
+    return nn1, nn2, sim1.numpy(), mutual
+
+
+def _depth(rng):
+    depth = synth.depth_pattern().copy()
+    depth.reshape(-1)[rng.integers(0, depth.size, size=depth.size // 7)] = 0     # holes: the 100 m sentinel
+    return depth
+
+
+def _intrinsics(rng, params):
+    return (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
+            params.v_max / 2 + float(rng.uniform(-20, 20)))
+
+
+def _oracle(g, img, params, nn1, ids, rows, depth, K):
+    ids = np.asarray(ids, np.int64)
+    p1 = torch.from_numpy(np.stack([ids // g, ids % g], 1))
+    p2 = torch.from_numpy(np.stack([nn1[ids] // g, nn1[ids] % g], 1))
+    s_star, s_ = sr.calculate_uv(sr.patch_centres(p1, img, g), sr.patch_centres(p2, img, g), rows, params.u_max, params.v_max, img)
+    return np.asarray(s_star), np.asarray(s_), sr.velocity(s_star, s_, depth, K[0], K[1], K[2], K[3], params.lambda_)
+
+
+def _ldlt_passes(L):
+    """servo.hip's pivot test on the normal equations of L (rows x 6), restated in fp64."""
+    G = L.T @ L
+    Lf, dpiv = np.zeros((6, 6)), np.zeros(6)
+    good = True
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return _ldlt_pivots(G, Lf, dpiv, good)
+
+
+def _ldlt_pivots(G, Lf, dpiv, good):
+    for j in range(6):
+        d = G[j, j] - sum(Lf[j, k] ** 2 * dpiv[k] for k in range(j))
+        good = good and d > 1e-8 * G[j, j] and G[j, j] > 0
+        dpiv[j] = d
+        for i in range(j + 1, 6):
+            Lf[i, j] = (G[i, j] - sum(Lf[i, k] * Lf[j, k] * dpiv[k] for k in range(j))) / d
+    return bool(good)
+
+
+def _check_law(det, b, v, st, ref, s_star, s_, rows, solver, what):
+    """One pair's law against the oracle's, and the solver that ran."""
+    assert int(st) == _lib.STATUS_OK, (what, int(st))
+    info = det["info"][b]
+    assert int(info[5]) == 2 * rows, (what, info)
+    assert (_ldlt_passes(ref["L"]) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
+    if solver == "ldlt":
+        assert int(info[4]) == LDLT, (what, "expected LDL^T", info)
+    else:
+        assert 0 <= int(info[4]) <= MAX_SWEEPS, (what, "expected Jacobi", info)
+    suv = det["s_uv"][b, :rows]
+    assert np.array_equal(suv[:, 0:2], s_star) and np.array_equal(suv[:, 2:4], s_), what
+    assert np.array_equal(det["feat"][b, :rows, 0:1], ref["Z"]), what
+    np.testing.assert_allclose(det["L"][b, :6, :2 * rows].T, ref["L"], rtol=0, atol=L_BAR, err_msg=what)
+    np.testing.assert_allclose(det["L"][b, 6, :2 * rows], ref["e"][:, 0], rtol=0, atol=L_BAR, err_msg=what)
+    err = _rel_l2(v, ref["v_c"])
+    assert err <= VC_BAR, (what, err)
+    return int(info[4])
+
+
+_ENGINES = {}
+
+
+def _servo_engine(g, max_rows):
+    """A tiny handle (no weights: the law alone) for a g x g grid."""
+    key = (g, max_rows)
+    if key not in _ENGINES:
+        img = 16 * g
+        params = config.ServoParams(dino_input_size=img)
+        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
+    return _ENGINES[key]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_engines():
+    yield
+    for eng, _ in _ENGINES.values():
+        eng.close()
+    _ENGINES.clear()
+
+
+# ----------------------------------------------------------------------------- random tables, every selection mode
+@pytest.mark.parametrize("mode", ["order", "explicit", "dense"])
+@pytest.mark.parametrize("g", [14, 17, 22, 32])
+def test_law_on_random_tables(g, mode):
+    """T = 196 (prefetched depth, ballot scan), 289 (direct depth reads, shuffle scan, threads from 145 on without a position),
+    484 and 1024 (4 positions per thread).  ORDER and EXPLICIT keep 24 pairs (L in LDS), DENSE all mutual tokens (L global)."""
+    t, k = g * g, 24
+    rng = np.random.default_rng(7000 + 10 * g + ["order", "explicit", "dense"].index(mode))
+    eng, params = _servo_engine(g, t)
+    img = 16 * g
+    nn1, nn2, sim1, mutual = _tables(rng, t, int(rng.integers(t // 4, t // 2)))
+    depth, K = _depth(rng), _intrinsics(rng, params)
+    if mode == "order":
+        order = rng.permutation(t).astype(np.int32)
+        mset = set(mutual.tolist())
+        ids, rows = np.array([x for x in order if x in mset][:k]), k
+        v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
+    elif mode == "explicit":
+        ids, rows = rng.choice(t, size=k, replace=False).astype(np.int32), k      # any tokens, mutual or not
+        v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=k)
+    else:
+        ids, rows = mutual, len(mutual)
+        v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_DENSE, num_pairs=k)
+    det = eng.last_details(1)
+    assert int(det["info"][0, 0]) == len(mutual) and int(det["info"][0, 3]) == rows
+    assert det["selected"][0, :rows].tolist() == [int(x) for x in ids]
+    s_star, s_, ref = _oracle(g, img, params, nn1, ids, rows, depth, K)
+    _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, rows, "ldlt", (g, mode))
+    if mode == "dense":
+        assert 2 * rows > 128                                 # L in the global workspace
+
+
+# ----------------------------------------------------------------------------- both solvers across the LDS / global edge
+@pytest.mark.parametrize("solver", ["ldlt", "jacobi"])
+@pytest.mark.parametrize("num_pairs", [4, 24, 40, 64, 65])
+def test_both_solvers_across_the_lds_edge(num_pairs, solver):
+    """R = 8 .. 130: LDS up to 128 rows, the global workspace beyond with column stride 2 * max_rows = 160 != R.  Well conditioned
+    (distinct mutual tokens: LDL^T) and rank-deficient (Jacobi, each lane over several rows from R = 65 on): one token repeated
+    below 32 pairs; from 32 pairs on two tokens in two blocks, the second holding the last 4 pairs, so that rows past 64 are not
+    a repeat of the first 64."""
+    g, max_rows = 17, 80
+    t = g * g
+    rng = np.random.default_rng(100 * num_pairs + (solver == "jacobi"))
+    eng, params = _servo_engine(g, max_rows)
+    nn1, nn2, sim1, mutual = _tables(rng, t, 200)
+    depth, K = _depth(rng), _intrinsics(rng, params)
+    if solver == "ldlt":
+        ids = rng.choice(mutual, size=num_pairs, replace=False)
+    else:
+        moved = np.nonzero(nn1 != np.arange(t))[0]            # displaced matches: e != 0
+        if num_pairs < 32:
+            ids = np.full(num_pairs, rng.choice(moved))
+        else:
+            a, b = rng.choice(moved, size=2, replace=False)
+            ids = np.where(np.arange(num_pairs) < num_pairs - 4, a, b)
+    ids = ids.astype(np.int32)
+    v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=num_pairs)
+    det = eng.last_details(1)
+    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, num_pairs, depth, K)
+    _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, num_pairs, solver, (num_pairs, solver))
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_rank_four_selections_within_the_sweep_cap(seed):
+    """Two distinct tokens (rank 4): the Jacobi sweeps converge slowly and may stop at the cap of 40; v_c still matches."""
+    g, k = 14, 24
+    t = g * g
+    rng = np.random.default_rng(500 + seed)
+    eng, params = _servo_engine(g, 48)
+    nn1, nn2, sim1, _ = _tables(rng, t, 80)
+    depth, K = _depth(rng), _intrinsics(rng, params)
+    moved = np.nonzero(nn1 != np.arange(t))[0]
+    ids = np.resize(rng.choice(moved, size=2, replace=False), k).astype(np.int32)
+    v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=k)
+    det = eng.last_details(1)
+    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, k, depth, K)
+    assert np.linalg.matrix_rank(ref["L"]) == 4
+    sweeps = _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, k, "jacobi", seed)
+    print(f"rank-4 selection {seed}: {sweeps} sweeps")
+
+
+# ----------------------------------------------------------------------------- statuses and the same-image shortcut
+@pytest.mark.parametrize("g", [17, 32])
+def test_statuses_at_many_tokens(g):
+    t, k = g * g, 24
+    rng = np.random.default_rng(300 + g)
+    eng, params = _servo_engine(g, t)
+    nn1, nn2, sim1, mutual = _tables(rng, t, t // 3)
+    depth, K = _depth(rng), params.intrinsics()
+    few = rng.choice(mutual, size=3, replace=False).astype(np.int32)
+    v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[few], num_pairs=k)
+    det = eng.last_details(1)
+    assert int(st) == _lib.STATUS_TOO_FEW and np.all(v.cpu().numpy() == 0) and not det["s_uv"][0, :k].any()
+    v, st = eng.servo_from_nn(nn1, nn2, sim1, None, K, mode=_lib.SELECT_DENSE, num_pairs=k)
+    assert int(st) == _lib.STATUS_NO_DEPTH and np.all(v.cpu().numpy() == 0)
+    ident = np.arange(t)
+    for a, b in ((ident, ident), ((ident + 1) % t, (ident + 2) % t)):      # every token mutual; none
+        v, st = eng.servo_from_nn(a, b, np.full(t, 0.5, np.float32), depth, K, mode=_lib.SELECT_ORDER,
+                                  selection=rng.permutation(t).astype(np.int32), num_pairs=k)
+        det = eng.last_details(1)
+        assert int(st) == _lib.STATUS_NO_CORRESPONDENCE and np.all(v.cpu().numpy() == 0), int(st)
+        assert int(det["info"][0, 0]) in (0, t)
+    # identical frames (mean sim_1 > 0.99): every token is its own match, e = 0, v_c = 0 exactly
+    order = rng.permutation(t).astype(np.int32)
+    v, st = eng.servo_from_nn(nn1, nn2, np.ones(t, np.float32), depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
+    det = eng.last_details(1)
+    assert int(det["info"][0, 2]) == 1 and det["selected"][0, :k].tolist() == order[:k].tolist()
+    s_star, s_, ref = _oracle(g, 16 * g, params, ident, order[:k], k, depth, K)
+    assert np.all(v.cpu().numpy() == 0) and np.array_equal(s_star, s_)
+    _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, k, "ldlt" if _ldlt_passes(ref["L"]) else "jacobi", ("same", g))
+
+
+# ----------------------------------------------------------------------------- several pairs in one velocity call
+def _tiny_model(max_pairs, max_rows):
+    cfg = _tiny_cfg(224)
+    params = config.ServoParams(dino_input_size=224, use_feature_binning=False)
+    eng = Engine(cfg, params, precision="fp32", max_pairs=max_pairs, max_rows=max_rows)
+    return eng.load_state_dict(weights.synthetic_state_dict(cfg, 3)), cfg, params
+
+
+def test_three_pairs_each_with_its_own_intrinsics_depth_and_selection():
+    """One velocity call, three pairs: each its own frames, K, depth image and EXPLICIT ids; pair 1 rank-deficient (Jacobi)
+    beside two LDL^T pairs.  Each pair must be the oracle's law on its own device tables."""
+    eng, cfg, params = _tiny_model(3, 196)                   # (max_rows >= T: the DENSE call that draws the tables)
+    g, t, k = cfg.grid, cfg.tokens, 24
+    rng = np.random.default_rng(33)
+    pairs = [synth.frame_pair(cfg.img_size, s) for s in (20250705, 20250715, 20250738)]
+    des = np.stack([p[0] for p in pairs])
+    cur = np.stack([p[1] for p in pairs])
+    depth = np.stack([_depth(rng), np.roll(synth.depth_pattern(), 37, axis=1), (synth.depth_pattern() // 2 + 300).astype(np.uint16)])
+    K = np.array([_intrinsics(rng, params) for _ in range(3)])
+    eng.compute_velocity(cur, des, depth, K, mode=_lib.SELECT_DENSE, num_pairs=k)    # the tables, to draw from
+    tabs = eng.last_details(3)
+    ids = []
+    for b in range(3):
+        moved = np.nonzero(tabs["nn_1"][b] != np.arange(t))[0]
+        if b == 1:
+            ids.append(np.resize(rng.choice(moved, size=1), k).astype(np.int32))
+        else:
+            ids.append(rng.choice(t, size=k, replace=False).astype(np.int32))
+    v, st = eng.compute_velocity(cur, des, depth, K, mode=_lib.SELECT_EXPLICIT, selection=ids, num_pairs=k)
+    det = eng.last_details(3)
+    v, st = v.cpu().numpy(), st.cpu().numpy()
+    for b in range(3):
+        assert np.array_equal(det["nn_1"][b], tabs["nn_1"][b]) and int(det["info"][b, 2]) == 0
+        s_star, s_, ref = _oracle(g, cfg.img_size, params, det["nn_1"][b].astype(np.int64), ids[b], k, depth[b], K[b])
+        _check_law(det, b, v[b], st[b], ref, s_star, s_, k, "jacobi" if b == 1 else "ldlt", ("pair", b))
+    eng.close()
+
+
+# ----------------------------------------------------------------------------- reselect state
+@pytest.mark.parametrize("between", ["set_goal", "extract_descriptors", "correspond"])
+def test_reselect_ends_with_calls_that_rewrite_the_keys(between):
+    """vitvs_reselect re-runs the law on the arg-max keys a host-pointer velocity call left.  set_goal and extract_descriptors
+    (their forward clears or overwrites the keys) and correspond (overwrites them) end that state: reselect then fails with -5
+    rather than returning a v_c of foreign keys."""
+    eng, cfg, params = _tiny_model(1, 196)
+    des, cur = synth.frame_pair(cfg.img_size, 20250705)
+    depth = synth.depth_pattern()
+    v0, st0 = eng.compute_velocity_host(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
+    v1, st1 = eng.reselect_host(_lib.SELECT_DENSE)
+    assert np.array_equal(v0, v1) and np.array_equal(st0, st1)
+    if between == "set_goal":
+        eng.set_goal(des)
+    elif between == "extract_descriptors":
+        eng.extract_descriptors(np.stack([des, cur]))
+    else:
+        d = torch.randn(cfg.tokens, cfg.dim, generator=torch.Generator().manual_seed(1))
+        eng.correspond(d, d.flip(0))
+    torch.cuda.synchronize()
+    with pytest.raises(VitvsError, match=r"\(-5\)"):
+        eng.reselect_host(_lib.SELECT_DENSE)
+    eng.close()

@@ -449,6 +449,8 @@ ChainCtx fill_ctx(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
 int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* des, const uint8_t* cur, float* part,
                   hipStream_t st) {
     if (i0 == 0) h->goal_frames = 0;            // rows of a cached goal are about to be overwritten (vitvs_set_goal_dev re-arms)
+    h->details_pinned = false;                  // the arg-max keys vitvs_reselect builds on are cleared or rewritten from here on
+    h->host_tables = vitvs_handle::HostTables{};
     ChainCtx cx = fill_ctx(h, i0, cnt, n_des, des, cur, part);
     const Precision p = h->prec;
     const int D = h->cfg.dim;
@@ -505,6 +507,7 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     a.sel_stride = (mode == VITVS_SELECT_EXPLICIT) ? num_pairs : T;
     a.v_c = v_c; a.status = status; a.nn1 = h->nn1; a.nn2 = h->nn2; a.sim1 = h->sim1; a.info = h->info;
     a.sel_out = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.L_ws = h->Lws; a.max_rows = c.max_rows;
+    a.L_work = h->Lws + (size_t)c.max_pairs * 7 * 2 * c.max_rows;
     h->last_pairs = n_pairs; h->last_T = T;
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(a, st); }
@@ -662,14 +665,11 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     }
     h->dn_elems = (size_t)h->n_img_max * h->T * h->Dp;
     if (!rc) rc = dev_alloc(h, &h->dn, h->dn_elems);
-    // binned descriptors: the velocity path takes the 9 D-wide Gram as a 3 x 3 stencil over the raw token Gram (correspond.hip),
-    // which needs T x T floats per pair (3136 tokens: 39 MB); beyond 8 GiB in all it keeps the concatenated form
-    if (!rc && cfg->binned && (size_t)cfg->max_pairs * h->T * h->T * 4 <= (8ull << 30))
-        rc = dev_alloc(h, &h->gram_ws, (size_t)cfg->max_pairs * h->T * h->T);
-    // 16-bit modes, >= 1024 tokens: the Gram runs on the f16 matrix cores from a hi / lo split of the descriptors (correspond.hip)
-    if (!rc && !h->gram_ws && plain16(h->prec) && h->T >= 1024 && h->Dp % 64 == 0 &&
-        gram_split_elems(h->n_img_max, h->T, h->Dp) * 2 < (1ull << 32))
-        rc = dev_alloc(h, &h->dh, gram_split_elems(h->n_img_max, h->T, h->Dp));
+    // the workspaces of the Gram stage (correspond.hip plan_gram): the raw token Gram [max_pairs][T][T] of the stencil form, the
+    // fp16 hi / lo split of every frame's descriptors
+    const GramPlan gp = plan_gram(h->prec, cfg->binned != 0, h->T, cfg->dim, cfg->max_pairs, cfg->max_pairs);
+    if (!rc && gp.form == GRAM_STENCIL) rc = dev_alloc(h, &h->gram_ws, (size_t)cfg->max_pairs * h->T * h->T);
+    if (!rc && gp.split) rc = dev_alloc(h, &h->dh, gram_split_elems(h->n_img_max, h->T, h->Dp));
     if (!rc) rc = dev_alloc(h, &h->sq, (size_t)h->n_img_max * h->T);
 
     h->best_elems = (size_t)cfg->max_pairs * h->T;
@@ -680,7 +680,7 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     if (!rc) rc = dev_alloc(h, &h->det_block, h->det_bytes);
     if (!rc) detail_pointers(h, h->det_block);
     if (!rc) rc = dev_alloc(h, &h->sel_out, P * R);
-    if (!rc) rc = dev_alloc(h, &h->Lws, P * 7 * 2 * R);
+    if (!rc) rc = dev_alloc(h, &h->Lws, 2 * P * 7 * 2 * R);   // L and e per pair, then the Jacobi SVD's working copies
     const size_t img_bytes = (size_t)cfg->img_size * cfg->img_size * 3;
     h->staged_frame_bytes = img_bytes;
     if (!rc) rc = dev_alloc(h, &h->st_cur, P * img_bytes);
@@ -1024,6 +1024,8 @@ int vitvs_correspond_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* de
     DeviceScope dev(h);
     hipStream_t st = as_stream(stream);
     h->goal_frames = 0;                         // the descriptor workspace is overwritten
+    h->details_pinned = false;                  // and the arg-max keys: nothing left for vitvs_reselect
+    h->host_tables = vitvs_handle::HostTables{};
     int rc = launch_normalize_rows(desc1, h->dn, T, Dp, st);
     if (!rc) rc = launch_normalize_rows(desc2, h->dn + (size_t)T * Dp, T, Dp, st);
     if (rc) return set_err(h, rc, "normalise launch failed");
@@ -1088,7 +1090,8 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
                      : forward_chain(h, n_des, u.n_pairs, n_des, nullptr, u.I_cur, h->part, st);
     h->desc_keys = -1;
     if (rc) return rc;
-    if (h->cfg.binned && h->gram_ws) {
+    const GramPlan gp = plan_gram(h->prec, h->cfg.binned != 0, h->T, h->cfg.dim, u.n_pairs, h->cfg.max_pairs);
+    if (gp.form == GRAM_STENCIL) {
         // binned descriptors as a stencil over the raw token Gram: nothing 9 D wide is built or read (correspond.hip header)
         // (the tokens' squared norms came out of the forward's last launch, which also cleared the arg-max keys)
         { Span sp(h, KC_GRAM, st);
@@ -1106,12 +1109,12 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
                                 h->row_best, h->col_best, u.n_pairs * h->T, st);
         if (rc) return set_err(h, rc, "descriptor launch failed");
     }
-    if (h->dh) {
+    if (gp.split) {
         rc = launch_split_desc(h->dn, h->dh, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, st);
         if (rc) return set_err(h, rc, "descriptor split launch failed");
     }
     { Span sp(h, KC_GRAM, st);
-      rc = h->dh ? launch_gram_argmax_split(h->dh, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st)
+      rc = gp.split ? launch_gram_argmax_split(h->dh, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st)
                  : launch_gram_argmax(h->dn, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st); }
     if (rc) return set_err(h, rc, "gram launch failed");
     late_inputs(u);
@@ -1496,6 +1499,55 @@ int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t
     out[0] = pl.kernel; out[1] = (int32_t)(pl.grid.x * pl.grid.y * pl.grid.z); out[2] = pl.threads; out[3] = pl.lds;
     out[4] = pl.per; out[5] = pl.divided;
     return pl.kernel == ATTN_NONE ? -2 : 0;
+}
+int vitvs_op_gram_plan(int32_t precision, int32_t binned, int32_t T, int32_t D, int32_t n_pairs, int32_t max_pairs, int32_t* out) {
+    if (!out) return -1;
+    const GramPlan pl = plan_gram(to_prec(precision), binned != 0, T, D, n_pairs, max_pairs);
+    out[0] = pl.form; out[1] = pl.rows; out[2] = pl.cols; out[3] = pl.kgroups; out[4] = pl.hb; out[5] = pl.per_xcd;
+    out[6] = pl.split;
+    return pl.rows ? 0 : -2;
+}
+// the arg-max keys of n_pairs pairs -> nn_1 / nn_2 / sim_1 [n_pairs][T], as the law's kernel decodes them
+static int decode_pairs(const unsigned long long* row_best, const unsigned long long* col_best, int T, int n_pairs, int32_t* nn_1,
+                        int32_t* nn_2, float* sim_1, hipStream_t st) {
+    int rc = 0;
+    for (int b = 0; !rc && b < n_pairs; ++b) {
+        const size_t o = (size_t)b * T;
+        rc = launch_decode_best(row_best + o, col_best + o, T, nn_1 + o, nn_2 + o, sim_1 + o, st);
+    }
+    return rc;
+}
+int vitvs_op_gram_argmax(int32_t precision, const float* dn, int32_t T, int32_t Dp, int32_t n_pairs, int32_t des_shared, void* dh,
+                         uint64_t* row_best, uint64_t* col_best, int32_t* nn_1, int32_t* nn_2, float* sim_1, void* stream) {
+    if (!dn || !row_best || !col_best || !nn_1 || !nn_2 || !sim_1) return -1;
+    const GramPlan pl = plan_gram(to_prec(precision), false, T, Dp, n_pairs, n_pairs);
+    if (!pl.rows) return -2;
+    if (pl.split && !dh) return -1;
+    DeviceScope dev(nullptr);
+    hipStream_t st = as_stream(stream);
+    unsigned long long *rb = reinterpret_cast<unsigned long long*>(row_best), *cb = reinterpret_cast<unsigned long long*>(col_best);
+    VITVS_HIP_CHECK(hipMemsetAsync(rb, 0, (size_t)n_pairs * T * 8, st));
+    VITVS_HIP_CHECK(hipMemsetAsync(cb, 0, (size_t)n_pairs * T * 8, st));
+    int rc = pl.split ? launch_split_desc(dn, dh, T, Dp, n_pairs, des_shared, st) : 0;
+    if (!rc) rc = pl.split ? launch_gram_argmax_split(dh, T, Dp, n_pairs, des_shared, rb, cb, st)
+                           : launch_gram_argmax(dn, T, Dp, n_pairs, des_shared, rb, cb, st);
+    return rc ? rc : decode_pairs(rb, cb, T, n_pairs, nn_1, nn_2, sim_1, st);
+}
+int vitvs_op_gram_stencil(const float* x, int32_t T, int32_t P, int32_t D, int32_t grid, int32_t n_pairs, int32_t des_shared,
+                          float* G, float* sq, uint64_t* row_best, uint64_t* col_best, int32_t* nn_1, int32_t* nn_2, float* sim_1,
+                          void* stream) {
+    if (!x || !G || !sq || !row_best || !col_best || !nn_1 || !nn_2 || !sim_1) return -1;
+    const GramPlan pl = plan_gram(PREC_F32, true, T, D, n_pairs, n_pairs);
+    if (pl.form != GRAM_STENCIL || !pl.rows || grid * grid != T || P < 1) return -2;
+    DeviceScope dev(nullptr);
+    hipStream_t st = as_stream(stream);
+    unsigned long long *rb = reinterpret_cast<unsigned long long*>(row_best), *cb = reinterpret_cast<unsigned long long*>(col_best);
+    const int n_frames = (des_shared ? 1 : n_pairs) + n_pairs;
+    // the tokens' squared norms; the same launch clears the keys (what the forward's last launch does on the velocity path)
+    int rc = launch_descriptors(x, nullptr, nullptr, sq, n_frames, T, P, grid, D, 1, rb, cb, n_pairs * T, st);
+    if (!rc) rc = launch_gram_raw_tokens(x, T, P, D, n_pairs, des_shared, G, st);
+    if (!rc) rc = launch_gram_stencil_argmax(G, sq, T, grid, n_pairs, des_shared, rb, cb, st);
+    return rc ? rc : decode_pairs(rb, cb, T, n_pairs, nn_1, nn_2, sim_1, st);
 }
 int vitvs_op_touch(const void* p, int64_t bytes, int32_t share_xcds, void* stream) {
     DeviceScope dev(nullptr);

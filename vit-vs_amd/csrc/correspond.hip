@@ -302,6 +302,44 @@ __global__ __launch_bounds__(256) void split_desc_kernel(const float* __restrict
 
 size_t gram_split_elems(int n_frames, int T, int Dp) { return (size_t)n_frames * T * 3 * Dp; }
 
+GramPlan plan_gram_tiles(bool split, int T, int Dp, int n_pairs) {
+    GramPlan pl;
+    pl.split = split;
+    if (T <= 0 || n_pairs <= 0 || Dp % (split ? 64 : 32) != 0) return pl;
+    if (split) {
+        const long t128 = (long)((T + 127) / 128) * ((T + 127) / 128) * n_pairs;
+        // enough 128 x 128 tiles for every CU (3136 tokens: 625); 1369 tokens: 121 tiles of 128 x 128, 484 of 64 x 64
+        pl.rows = pl.cols = t128 >= 256 ? 128 : 64;
+        pl.kgroups = 1;
+    } else if (T <= 512 && (Dp / 32) % 2 == 0) {
+        pl.rows = pl.cols = 32;             // few tokens: 32x32 tiles (49 workgroups at T = 196 instead of 16) with two k-groups
+        pl.kgroups = 2;
+    } else {
+        pl.rows = pl.cols = 64;
+        pl.kgroups = 1;
+    }
+    pl.hb = gram_band_rows(T, pl.rows, pl.cols, &pl.per_xcd);
+    return pl;
+}
+
+GramPlan plan_gram(Precision p, bool binned, int T, int D, int n_pairs, int max_pairs) {
+    if (T <= 0 || D <= 0 || n_pairs <= 0 || max_pairs < n_pairs) return GramPlan{};
+    // binned descriptors: the 9 D-wide Gram as a 3 x 3 stencil over the raw token Gram (header), which needs T x T floats per
+    // pair (3136 tokens: 39 MB); beyond 8 GiB in all the handle keeps the concatenated form
+    if (binned && (size_t)max_pairs * T * T * 4 <= (8ull << 30)) {
+        GramPlan pl = plan_gram_tiles(false, T, D, n_pairs);
+        pl.form = GRAM_STENCIL;
+        return pl;
+    }
+    // 16-bit modes, >= 1024 tokens: the Gram runs on the f16 matrix cores from a hi / lo split of the descriptors of all the
+    // handle's frames (32-bit operand offsets)
+    const int Dp = binned ? 9 * D : D;
+    const bool split = plain16(p) && T >= 1024 && Dp % 64 == 0 && gram_split_elems(2 * max_pairs, T, Dp) * 2 < (1ull << 32);
+    GramPlan pl = plan_gram_tiles(split, T, Dp, n_pairs);
+    pl.form = binned ? GRAM_WIDE : split ? GRAM_SPLIT : GRAM_F32;
+    return pl;
+}
+
 int launch_split_desc(const float* dn, void* dh, int T, int Dp, int n_pairs, int des_shared, hipStream_t stream) {
     if (T <= 0 || n_pairs <= 0 || (Dp % 64) != 0 || !dh) return -2;
     const int n_des = des_shared ? 1 : n_pairs, n_frames = n_des + n_pairs;
@@ -313,63 +351,54 @@ int launch_split_desc(const float* dn, void* dh, int T, int Dp, int n_pairs, int
 
 int launch_gram_argmax_split(const void* dh, int T, int Dp, int n_pairs, int des_shared, unsigned long long* row_best,
                              unsigned long long* col_best, hipStream_t stream) {
-    if (T <= 0 || n_pairs <= 0 || (Dp % 64) != 0 || !dh) return -2;
-    const long t128 = (long)((T + 127) / 128) * ((T + 127) / 128) * n_pairs;
-    if (t128 >= 256) {                                             // enough 128 x 128 tiles for every CU (3136 tokens: 625)
+    const GramPlan pl = plan_gram_tiles(true, T, Dp, n_pairs);
+    if (!pl.rows || !dh) return -2;
+    if (pl.rows == 128) {
         using Tile = GemmTile<128, 128, 1>;
         static std::atomic<unsigned long long> raised{0};
         if (raise_lds_limit(reinterpret_cast<const void*>(&gram_argmax_kernel<f16, 128, 128, 1>), Tile::LDS_BYTES, raised)) return -1;
-        int per = 0;
-        const int hb = gram_band_rows(T, 128, 128, &per);
-        launch((gram_argmax_kernel<f16, 128, 128, 1>), dim3(8 * per, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh, T,
-               3 * Dp, n_pairs, des_shared, row_best, col_best, hb);
-    } else {                                                       // 1369 tokens: 121 tiles of 128 x 128, 484 of 64 x 64
+        launch((gram_argmax_kernel<f16, 128, 128, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh,
+               T, 3 * Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
+    } else {
         using Tile = GemmTile<64, 64, 1>;
         static std::atomic<unsigned long long> raised{0};
         if (raise_lds_limit(reinterpret_cast<const void*>(&gram_argmax_kernel<f16, 64, 64, 1>), Tile::LDS_BYTES, raised)) return -1;
-        int per = 0;
-        const int hb = gram_band_rows(T, 64, 64, &per);
-        launch((gram_argmax_kernel<f16, 64, 64, 1>), dim3(8 * per, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh, T,
-               3 * Dp, n_pairs, des_shared, row_best, col_best, hb);
+        launch((gram_argmax_kernel<f16, 64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh,
+               T, 3 * Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_gram_argmax(const float* dn, int T, int Dp, int n_pairs, int des_shared, unsigned long long* row_best,
                        unsigned long long* col_best, hipStream_t stream) {
-    if (T <= 0 || n_pairs <= 0 || (Dp % 32) != 0) return -2;
-    int per = 0;
-    if (T <= 512 && (Dp / 32) % 2 == 0) {
-        // few tokens: 32x32 tiles (49 workgroups at T = 196 instead of 16) with two k-groups
+    const GramPlan pl = plan_gram_tiles(false, T, Dp, n_pairs);
+    if (!pl.rows) return -2;
+    if (pl.rows == 32) {
         using Tile = GemmTile<32, 32, 2>;
-        const int hb = gram_band_rows(T, 32, 32, &per);
-        launch((gram_argmax_kernel<float, 32, 32, 2>), dim3(8 * per, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, dn, T, Dp,
-               n_pairs, des_shared, row_best, col_best, hb);
+        launch((gram_argmax_kernel<float, 32, 32, 2>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, dn,
+               T, Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     constexpr int lds = GemmTile<64, 64, 1>::LDS_BYTES;
-    const int hb = gram_band_rows(T, 64, 64, &per);
-    launch((gram_argmax_kernel<float, 64, 64, 1>), dim3(8 * per, 1, n_pairs), dim3(256), lds, stream, dn, T, Dp, n_pairs, des_shared,
-           row_best, col_best, hb);
+    launch((gram_argmax_kernel<float, 64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), lds, stream, dn, T, Dp, n_pairs,
+           des_shared, row_best, col_best, pl.hb);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 static int launch_gram_dense_strided(const float* src, long img_stride, int ld, int T, int Dp, int n_pairs, int des_shared, float* S,
                                      hipStream_t stream) {
-    if (T <= 0 || n_pairs <= 0 || (Dp % 32) != 0) return -2;
+    const GramPlan pl = plan_gram_tiles(false, T, Dp, n_pairs);
+    if (!pl.rows) return -2;
     // 32-bit byte offsets in the main loop: every row the launch touches lies within 4 GiB of its image's first row
     if ((long long)T * ld * 4 >= (1ll << 32)) return -2;
-    int per = 0;
-    if (T <= 512 && (Dp / 32) % 2 == 0) {                       // few tokens: 32 x 32 tiles with two k-groups, like the fused arg-max form
+    if (pl.rows == 32) {
         using Tile = GemmTile<32, 32, 2>;
-        const int hb = gram_band_rows(T, 32, 32, &per);
-        launch((gram_dense_kernel<32, 32, 2>), dim3(8 * per, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, src, img_stride, ld,
-               T, Dp, n_pairs, des_shared, S, hb);
+        launch((gram_dense_kernel<32, 32, 2>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, src,
+               img_stride, ld, T, Dp, n_pairs, des_shared, S, pl.hb);
     } else {
         constexpr int lds = GemmTile<64, 64, 1>::LDS_BYTES;
-        const int hb = gram_band_rows(T, 64, 64, &per);
-        launch((gram_dense_kernel<64, 64, 1>), dim3(8 * per, 1, n_pairs), dim3(256), lds, stream, src, img_stride, ld, T, Dp, n_pairs,
-               des_shared, S, hb);
+        launch((gram_dense_kernel<64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), lds, stream, src, img_stride, ld, T, Dp,
+               n_pairs, des_shared, S, pl.hb);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -207,6 +207,24 @@ int launch_attention(const AttnPlan& plan, const void* qkv, void* out, hipStream
                      bool q_prescaled = false);
 
 // ---- correspond.hip ------------------------------------------------------------------------
+// The Gram stage of a velocity update, decided once by plan_gram (the codes are ABI: vitvs_op_gram_plan):
+//   GRAM_F32      fused Gram + row / column arg-max over the fp32 descriptors (gram_argmax_kernel<float>)
+//   GRAM_SPLIT    the same on the f16 matrix cores from a hi / lo split of the descriptors (16-bit modes from 1024 tokens)
+//   GRAM_STENCIL  binned descriptors: raw token Gram into the handle's T x T workspace, then the 3 x 3 stencil arg-max
+//   GRAM_WIDE     binned descriptors whose raw Gram workspace would pass 8 GiB: the 9 D-wide descriptors through the fused
+//                 arg-max, split as GRAM_SPLIT is
+enum GramForm : int { GRAM_NONE = 0, GRAM_F32, GRAM_SPLIT, GRAM_STENCIL, GRAM_WIDE };
+struct GramPlan {
+    GramForm form = GRAM_NONE;
+    bool split = false;                   // the Gram's operands are the fp16 hi / lo split (launch_split_desc into `dh` first)
+    int rows = 0, cols = 0, kgroups = 0;  // tile of the Gram kernel (GRAM_STENCIL: of the raw Gram); rows = 0: unlaunchable
+    int hb = 0, per_xcd = 0;              // band rows and workgroups per XCD of the tile order (gram_tile)
+};
+// The tile of one Gram launch over T tokens, rows Dp wide, n_pairs pairs: fp32 operands or the split.
+GramPlan plan_gram_tiles(bool split, int T, int Dp, int n_pairs);
+// The Gram stage of a handle (precision, binned descriptors, tokens, model width D, max_pairs) for a call of n_pairs pairs.
+// vitvs_create_ex allocates the workspaces of the plan at n_pairs = max_pairs.
+GramPlan plan_gram(Precision p, bool binned, int T, int D, int n_pairs, int max_pairs);
 // For pair b: S = dn[a_img(b)] . dn[b_img(b)]^T (T x T, fp32); row_best[b][i] / col_best[b][j] receive
 // the packed (max similarity, first index) keys (common.h pack_best).  Buffers must be zeroed first.
 int launch_gram_argmax(const float* dn, int T, int Dp, int n_pairs, int des_shared,
@@ -265,6 +283,7 @@ struct ServoArgs {
     double* feat;             // [n_pairs][max_rows][4]: Z, x, y, sim
     double* L_ws;             // [n_pairs][7][rows_cap] workspace (L columns + e), also an output for tests
     int max_rows;             // capacity in feature pairs (>= num_pairs; >= T for DENSE)
+    double* L_work;           // [n_pairs][7][rows_cap]: the Jacobi SVD's working copy of an L too large for LDS (L_ws keeps L)
 };
 int launch_servo(const ServoArgs& a, hipStream_t stream);
 

@@ -334,6 +334,14 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         }
     }
     if (status == ST_OK && R > 0 && !solved) {
+        if (!use_lds) {
+            // the rotations below overwrite their operand: an L kept in the global workspace (an output) is rotated in a copy.
+            // Each lane copies the rows it alone reads and writes below (r = lane mod 64), so its own program order suffices.
+            double* Lw = a.L_work + (size_t)b * 7 * gcap;
+            for (int c = 0; c < 7; ++c)
+                for (int r = lane; r < R; r += 64) Lw[(size_t)c * rcap + r] = Lc[(size_t)c * rcap + r];
+            Lc = Lw;
+        }
         double V[6][6];
 #pragma unroll
         for (int i = 0; i < 6; ++i)
