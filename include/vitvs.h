@@ -234,7 +234,9 @@ VITVS_API int vitvs_servo_from_nn_dev(vitvs_handle* h, int32_t T, const int32_t*
 /* --- introspection of the last compute_velocity / servo call (device -> host copies, synchronising).
  * What detect_features() returns besides v_c (vitvs_v2.py:523) and what the parity tests check.
  *   nn_1, nn_2 int32 [n_pairs][T]; sim_1 fp32 [n_pairs][T]
- *   info int32 [n_pairs][8]: n_mutual, n_feature_rows, same_image, n_matched, svd_sweeps, L_rows, 0, 0
+ *   info int32 [n_pairs][8]: n_mutual, n_feature_rows, same_image, n_matched, svd_sweeps, L_rows, reweightings, zero_weights
+ *        (svd_sweeps: -1 = LDL^T, else the Jacobi sweeps, of the FINAL solve; reweightings / zero_weights: option "robust_law"
+ *        below, both 0 with the option off or when a status skipped the law)
  *   selected int32 [n_pairs][max_rows] token ids of the desired frame (-1 = zero-padded row)
  *   s_uv int32 [n_pairs][max_rows][4] = u*, v*, u, v ; feat double [n_pairs][max_rows][4] = Z, x, y, sim
  *        (feat[..][3] over the first n_matched rows is the reference's sim_selected_12, vitvs_v2.py:523, 1167-1174)
@@ -246,6 +248,11 @@ VITVS_API int vitvs_servo_from_nn_dev(vitvs_handle* h, int32_t T, const int32_t*
  * `selected` and `L` is served from host memory (the handle's pinned block) without a device call. */
 VITVS_API int vitvs_last_details(vitvs_handle* h, int32_t n_pairs, int32_t* nn_1, int32_t* nn_2, float* sim_1, int32_t* info,
                        int32_t* selected, int32_t* s_uv, double* feat, double* L);
+/* The weight every feature pair had in the FINAL solve of the last law evaluation (option "robust_law", below):
+ *   w double [n_pairs][max_rows]; with the option off 1 for every live pair; 0 for zero-padded pairs (rows from n_matched on
+ *   of a short selection) and from n_feature_rows on.  `L` and `e` of vitvs_last_details stay the unweighted ones.
+ * Synchronising, always read from the device.  Replaces nothing: the reference's law has no weights (vitvs_v2.py:613-622). */
+VITVS_API int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w);
 
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
@@ -265,6 +272,15 @@ VITVS_API int vitvs_last_details(vitvs_handle* h, int32_t n_pairs, int32_t* nn_1
  *                          256 x 256 tiles wherever they divide (fewest operand bytes per FLOP instead of launch balance)
  *                          and at most two K slices.
  *   "reuse_goal_frames" 0 / 1  host-pointer calls: see vitvs_compute_velocity above.
+ *   "robust_law"   0 .. 16 an extension beyond the reference (its law is plain least squares, vitvs_v2.py:613-622, with no
+ *                          defence against a wrong match).  0 (default): that law, bit for bit.  N >= 1: iteratively
+ *                          re-weighted least squares with N re-weightings (N + 1 solves) inside the law's kernel, in fp64:
+ *                          per feature pair the residual rho = |e_k - L_k x|, the scale sigma = max(1.4826 median(rho),
+ *                          sigma_min) over the live pairs, sigma_min = half a patch pitch in normalised image coordinates
+ *                          (0.5 max(stride u_max / S / fx, stride v_max / S / fy)), Tukey's biweight with c = 4.6851:
+ *                          w = (1 - t^2)^2 for t = rho / (c sigma) < 1, else 0; v_c = -lambda x of the last weighted solve.
+ *                          Zero-padded pairs have weight 0.  Applies to every entry point that evaluates the law; changing
+ *                          it drops the handle's captured graphs.  vitvs_last_weights returns the final weights.
  * Returns 0, or -5 for an unknown name / a value out of range. */
 VITVS_API int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value);
 /* The handles of such an arrangement run ONE network: `h` (created with the same network, input geometry and precision, no

@@ -113,6 +113,9 @@ struct vitvs_handle {
     int32_t *nn1 = nullptr, *nn2 = nullptr, *info = nullptr, *sel_out = nullptr, *s_uv = nullptr;
     float* sim1 = nullptr;
     double *feat = nullptr, *Lws = nullptr;
+    double* Wws = nullptr;    // [max_pairs][max_rows] the robust law's final weights (vitvs_last_weights)
+    int robust_iters = 0;     // option "robust_law": Tukey re-weightings of the control law, 0 = the reference's plain law
+    bool last_robust = false; // the last law evaluation wrote Wws
     int last_pairs = 0, last_T = 0;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
     // graph replays' own copy of the selection
@@ -508,7 +511,10 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     a.v_c = v_c; a.status = status; a.nn1 = h->nn1; a.nn2 = h->nn2; a.sim1 = h->sim1; a.info = h->info;
     a.sel_out = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.L_ws = h->Lws; a.max_rows = c.max_rows;
     a.L_work = h->Lws + (size_t)c.max_pairs * 7 * 2 * c.max_rows;
-    h->last_pairs = n_pairs; h->last_T = T;
+    a.robust_iters = h->robust_iters; a.W_ws = h->Wws;
+    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
+    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    h->last_pairs = n_pairs; h->last_T = T; h->last_robust = h->robust_iters > 0;
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(a, st); }
     if (rc) return set_err(h, rc, "servo launch failed (LDS budget or bad arguments)");
@@ -681,6 +687,7 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     if (!rc) detail_pointers(h, h->det_block);
     if (!rc) rc = dev_alloc(h, &h->sel_out, P * R);
     if (!rc) rc = dev_alloc(h, &h->Lws, 2 * P * 7 * 2 * R);   // L and e per pair, then the Jacobi SVD's working copies
+    if (!rc) rc = dev_alloc(h, &h->Wws, P * R);
     const size_t img_bytes = (size_t)cfg->img_size * cfg->img_size * 3;
     h->staged_frame_bytes = img_bytes;
     if (!rc) rc = dev_alloc(h, &h->st_cur, P * img_bytes);
@@ -1173,7 +1180,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
         ge = &h->graphs.back();
     }
     ge->last_use = ++h->graph_clock;
-    h->last_pairs = u.n_pairs; h->last_T = h->T;
+    h->last_pairs = u.n_pairs; h->last_T = h->T; h->last_robust = h->robust_iters > 0;
     VITVS_HIP_CHECK(hipGraphLaunch(ge->exec, st));
     return 0;
 }
@@ -1408,7 +1415,39 @@ int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value) {
         }
         return 0;
     }
+    if (nm == "robust_law") {
+        if (value < 0 || value > 16) return set_err(h, -5, "robust_law takes 0 (the plain law) or 1 .. 16 re-weightings");
+        if ((int)value != h->robust_iters) {    // captured updates hold the previous law's kernel and arguments
+            DeviceScope dev(h);
+            VITVS_HIP_CHECK(hipDeviceSynchronize());
+            drop_graphs(h);
+            h->robust_iters = (int)value;
+        }
+        return 0;
+    }
     return set_err(h, -5, "unknown option " + nm);
+}
+
+int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w) {
+    if (!h || !w) return set_err(h, -1, "null argument");
+    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    DeviceScope dev(h);
+    const size_t R = h->cfg.max_rows, P = n_pairs;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<int32_t> inf(P * 8);
+    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
+    if (h->last_robust) VITVS_HIP_CHECK(hipMemcpy(w, h->Wws, P * R * 8, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < P; ++b) {
+        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
+        if (!h->last_robust) {
+            // the plain law: weight 1 on every live pair; fewer than 4 matches of a short selection leave none (TOO_FEW)
+            size_t live = std::min<size_t>(n, (size_t)std::max(inf[b * 8 + 3], 0));
+            if (live < n && live < 4) live = 0;
+            for (size_t k = 0; k < n; ++k) w[b * R + k] = k < live ? 1.0 : 0.0;
+        }
+        for (size_t k = n; k < R; ++k) w[b * R + k] = 0.0;
+    }
+    return 0;
 }
 
 int vitvs_timing_enable(vitvs_handle* h, int32_t on) {

@@ -277,13 +277,17 @@ struct ServoArgs {
     int32_t* nn1;             // [n_pairs][T]
     int32_t* nn2;             // [n_pairs][T]
     float* sim1;              // [n_pairs][T]
-    int32_t* info;            // [n_pairs][8]: n_mutual, n_rows_pairs, same_image, n_matched, sweeps, ...
+    int32_t* info;            // [n_pairs][8]: n_mutual, n_rows_pairs, same_image, n_matched, sweeps, L rows, re-weightings, zero weights
     int32_t* sel_out;         // [n_pairs][max_rows] selected token ids (image 1)
     int32_t* s_uv;            // [n_pairs][max_rows][4]: u*, v*, u, v
     double* feat;             // [n_pairs][max_rows][4]: Z, x, y, sim
     double* L_ws;             // [n_pairs][7][rows_cap] workspace (L columns + e), also an output for tests
     int max_rows;             // capacity in feature pairs (>= num_pairs; >= T for DENSE)
     double* L_work;           // [n_pairs][7][rows_cap]: the Jacobi SVD's working copy of an L too large for LDS (L_ws keeps L)
+    // Tukey IRLS (option "robust_law"); with robust_iters == 0 the plain law's instantiation runs and none of these is read
+    int robust_iters;         // re-weightings N, 0 .. 16
+    double pitch_u, pitch_v;  // patch pitch in camera pixels (stride * u_max / S, stride * v_max / S): sigma_min = half of it, normalised
+    double* W_ws;             // [n_pairs][max_rows] final weight of every feature pair (output); the working weights when L is global
 };
 int launch_servo(const ServoArgs& a, hipStream_t stream);
 

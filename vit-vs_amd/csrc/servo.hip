@@ -1,6 +1,8 @@
 // From nearest-neighbour tables to the camera twist: mutual-NN filter, feature selection,
 // pixel features, depth lookup, interaction matrix L_e and v_c = -lambda * pinv(L_e) e.
 // One workgroup per frame pair; the SVD-based pseudo-inverse runs in fp64 on one wavefront.
+// servo_kernel<false> is that law; servo_kernel<true> (option "robust_law", no counterpart in the reference) re-weights the
+// feature pairs by Tukey's biweight of their residuals and solves again, N times, in the same launch.
 //
 // Reference arithmetic being replaced (vitvs_v2.py):
 //   same-image shortcut  mean(sim_1) > 0.99                   :84-101
@@ -51,8 +53,169 @@ __device__ __forceinline__ void token_pixel(const ServoArgs& a, int tok, long& u
     v = (long)rint((double)r * a.scale_y);
 }
 
+// G = L^T W L (21, upper triangle) and g = L^T W e (6): 27 quantities x 8 row slices on 216 threads into Gs[40 ..) (fixed
+// slice order -> deterministic), W = wk[pair] on both rows of a pair.
+__device__ __forceinline__ void normal_equation_slices(const double* Lc, int rcap, int R, const double* wk, double* Gs, int tid) {
+    const int qid = tid & 31, slice = tid >> 5;
+    if (qid < 27) {
+        int ca, cb;
+        if (qid < 21) {
+            int q = qid;
+            ca = 0;
+            while (q >= 6 - ca) { q -= 6 - ca; ++ca; }
+            cb = ca + q;
+        } else {
+            ca = qid - 21;
+            cb = 6;
+        }
+        // 4 independent chains keep 8 loads in flight (dense selections read L from the global workspace);
+        // fixed combination order -> still deterministic
+        double acc4[4] = {0.0, 0.0, 0.0, 0.0};
+        int r = slice;
+        for (; r + 24 < R; r += 32) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                acc4[u] += wk[(r + 8 * u) >> 1] * (Lc[ca * rcap + r + 8 * u] * Lc[cb * rcap + r + 8 * u]);
+            }
+        }
+        for (; r < R; r += 8) {
+            acc4[0] += wk[r >> 1] * (Lc[ca * rcap + r] * Lc[cb * rcap + r]);
+        }
+        Gs[40 + slice * 27 + qid] = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
+    }
+}
+
+// One wavefront: 27 lanes add the 8 slices, every lane then factors the same 6x6 system in registers (fully unrolled: no
+// private-memory arrays, no cross-lane traffic).  True, and xsol = G^-1 g, when every pivot passes the 1e-8 test.
+__device__ __forceinline__ bool solve_ldlt(double* Gs, int lane, double xsol[6]) {
+    if (lane < 27) {
+        double acc = 0.0;
+#pragma unroll
+        for (int sl = 0; sl < 8; ++sl) acc += Gs[40 + sl * 27 + lane];
+        Gs[lane] = acc;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same wave: LDS writes above are visible below
+    double Gm[6][6], rhs[6];
+    {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) { Gm[j][i] = Gs[q]; ++q; }   // lower triangle
+#pragma unroll
+        for (int i = 0; i < 6; ++i) rhs[i] = Gs[21 + i];
+    }
+    // G = L D L^T (unit lower-triangular L, no square roots, one reciprocal per pivot)
+    bool good = true;
+    double Lf[6][6], dinv[6], dpiv[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = Gm[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= Lf[j][k] * Lf[j][k] * dpiv[k];
+        good = good && (d > 1e-8 * Gm[j][j]) && (Gm[j][j] > 0.0);
+        dpiv[j] = d;
+        dinv[j] = 1.0 / d;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double t = Gm[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t -= Lf[i][k] * Lf[j][k] * dpiv[k];
+            Lf[i][j] = t * dinv[j];
+        }
+    }
+    if (good) {
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {          // L y = rhs
+            double t = rhs[i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) t -= Lf[i][k] * y[k];
+            y[i] = t;
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {         // L^T x = D^-1 y
+            double t = y[i] * dinv[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) t -= Lf[k][i] * xsol[k];
+            xsol[i] = t;
+        }
+    }
+    return good;
+}
+
+// One wavefront: xsol = pinv(A) rhs by one-sided Jacobi SVD with numpy.linalg.pinv's rcond = 1e-15 cut-off; A = the 6 columns
+// of Lc, rhs its 7th.  The rotations overwrite Lc.  Returns the sweeps that ran (<= 40).
+__device__ __forceinline__ int solve_jacobi(double* Lc, int rcap, int R, int lane, double xsol[6]) {
+    double V[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+    const double tol = 4e-15;
+    int sweeps;
+    for (sweeps = 0; sweeps < 40; ++sweeps) {
+        int rotated = 0;
+#pragma unroll
+        for (int p = 0; p < 5; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 6; ++q) {
+                double al = 0.0, be = 0.0, ga = 0.0;
+                for (int r = lane; r < R; r += 64) {
+                    const double ap = Lc[p * rcap + r], aq = Lc[q * rcap + r];
+                    al += ap * ap; be += aq * aq; ga += ap * aq;
+                }
+                al = wave_sum(al); be = wave_sum(be); ga = wave_sum(ga);
+                if (fabs(ga) > tol * sqrt(al * be) && al > 0.0 && be > 0.0) {
+                    ++rotated;
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                    for (int r = lane; r < R; r += 64) {
+                        const double ap = Lc[p * rcap + r], aq = Lc[q * rcap + r];
+                        Lc[p * rcap + r] = c * ap - s * aq;
+                        Lc[q * rcap + r] = s * ap + c * aq;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) {
+                        const double vp = V[i][p], vq = V[i][q];
+                        V[i][p] = c * vp - s * vq;
+                        V[i][q] = s * vp + c * vq;
+                    }
+                }
+            }
+        if (rotated == 0) break;
+    }
+    double sig2[6], w[6], smax2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double s2 = 0.0, dot = 0.0;
+        for (int r = lane; r < R; r += 64) {
+            const double aj = Lc[j * rcap + r];
+            s2 += aj * aj;
+            dot += aj * Lc[6 * rcap + r];
+        }
+        sig2[j] = wave_sum(s2);
+        w[j] = wave_sum(dot);
+        smax2 = fmax(smax2, sig2[j]);
+    }
+    const double cutoff = 1e-15 * sqrt(smax2);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) xsol[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        if (sqrt(sig2[j]) > cutoff) {
+            const double coef = w[j] / sig2[j];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xsol[i] += V[i][j] * coef;
+        }
+    }
+    return sweeps;
+}
+
 // The leading flat arguments repeat the fields of `a` the first memory requests depend on: they are
 // preloaded into SGPRs by the command processor (kernarg preload), the struct is fetched by the wave.
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __restrict__ row_best,
                                                     const unsigned long long* __restrict__ col_best,
                                                     const double* __restrict__ Kin, const int32_t* __restrict__ selection,
@@ -240,6 +403,141 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     if (!depth) status = ST_NO_DEPTH;
     else if (none) status = ST_NO_CORRESPONDENCE;
     else if (too_few) status = ST_TOO_FEW;
+    if constexpr (ROBUST) {
+        const bool try_fast = status == ST_OK && R > 0;
+        double vout[6] = {0, 0, 0, 0, 0, 0};
+        int sweeps = 0, reweighted = 0, n_zero = 0;
+        // Tukey IRLS (option "robust_law" = N): N re-weightings, N + 1 weighted solves.  The weights sit in LDS beside L, or
+        // in the global workspace when L does; the residuals always in LDS.  L and e themselves are never scaled: the normal
+        // equations take the weight as a factor, the Jacobi fallback rotates a copy of the rows scaled by sqrt(w).
+        double* Lwk = Gs + 40 + 8 * 27;            // [7][kLdsRows] the Jacobi fallback's copy of an L kept in LDS
+        double* Wl = Lwk + 7 * kLdsRows;           // [kLdsRows / 2]
+        double* rho = Wl + kLdsRows / 2;           // [max_rows]
+        double* Wg = a.W_ws + (size_t)b * a.max_rows;
+        double* wk = use_lds ? Wl : Wg;
+        for (int k = tid; k < n_rows; k += 256) {
+            const double w0 = (try_fast && k < n_matched) ? 1.0 : 0.0;     // zero-padded pairs take no part
+            wk[k] = w0;
+            if (use_lds) Wg[k] = w0;
+        }
+        if (use_lds) lds_barrier();
+        else __syncthreads();
+        if (try_fast) {
+            const int N = a.robust_iters, n = n_matched;
+            const double sigma_min = 0.5 * fmax(a.pitch_u / fx, a.pitch_v / fy);
+            for (int it = 0;; ++it) {
+                normal_equation_slices(Lc, rcap, R, wk, Gs, tid);
+                lds_barrier();
+                if (wave == 0) {
+                    double xsol[6];
+                    const bool solved = solve_ldlt(Gs, lane, xsol);
+                    sweeps = -1;
+                    if (!solved) {
+                        // each lane scales and copies the rows it alone rotates (r = lane mod 64)
+                        double* Lw = use_lds ? Lwk : a.L_work + (size_t)b * 7 * gcap;
+                        for (int r = lane; r < R; r += 64) {
+                            const double sw = sqrt(wk[r >> 1]);
+                            for (int c = 0; c < 7; ++c) Lw[(size_t)c * rcap + r] = sw * Lc[(size_t)c * rcap + r];
+                        }
+                        sweeps = solve_jacobi(Lw, rcap, R, lane, xsol);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) {
+                        vout[i] = -a.lambda * xsol[i];
+                        if (lane == 0) Gs[28 + i] = xsol[i];
+                    }
+                    if (lane == 0) { Gs[34] = 0.0; Gs[35] = 0.0; }
+                }
+                if (it == N) break;
+                lds_barrier();
+                // residual of every live pair
+                double x[6];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) x[i] = Gs[28 + i];
+                for (int k = tid; k < n; k += 256) {
+                    double r0 = Lc[6 * rcap + 2 * k], r1 = Lc[6 * rcap + 2 * k + 1];
+                    double p0 = 0.0, p1 = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) {
+                        p0 += Lc[c * rcap + 2 * k] * x[c];
+                        p1 += Lc[c * rcap + 2 * k + 1] * x[c];
+                    }
+                    r0 -= p0; r1 -= p1;
+                    rho[k] = sqrt(r0 * r0 + r1 * r1);
+                }
+                lds_barrier();
+                // median by rank counting: ties are ordered by index, so every value has its own rank; the two middle ranks
+                // (the same one for an odd count) each have exactly one writer
+                const int m_lo = (n - 1) >> 1, m_hi = n >> 1;
+                // (the residuals are >= +0, so their bit patterns order like their values: integer compares, no branches)
+                if (n <= 256) {
+                    if (tid < n) {
+                        const long long ki = __double_as_longlong(rho[tid]);
+                        int rank = 0;
+#pragma unroll 4
+                        for (int j = 0; j < n; ++j) {
+                            const long long kj = __double_as_longlong(rho[j]);
+                            rank += (int)(kj < ki) | ((int)(kj == ki) & (int)(j < tid));
+                        }
+                        if (rank == m_lo) Gs[34] = __longlong_as_double(ki);
+                        if (rank == m_hi) Gs[35] = __longlong_as_double(ki);
+                    }
+                } else {
+                    // dense selections rank thousands of values: 4 per thread and pass over the others
+                    for (int i0 = tid; i0 < n; i0 += 4 * 256) {
+                        long long ki[4];
+                        int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
+#pragma unroll 4
+                        for (int j = 0; j < n; ++j) {
+                            const long long kj = __double_as_longlong(rho[j]);
+#pragma unroll
+                            for (int u = 0; u < 4; ++u)
+                                rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            if (i0 + 256 * u < n && rank[u] == m_lo) Gs[34] = __longlong_as_double(ki[u]);
+                            if (i0 + 256 * u < n && rank[u] == m_hi) Gs[35] = __longlong_as_double(ki[u]);
+                        }
+                    }
+                }
+                lds_barrier();
+                const double sigma = fmax(1.4826 * ((Gs[34] + Gs[35]) * 0.5), sigma_min);
+                const double cs = 4.6851 * sigma;
+                int zeros = 0;
+                for (int k = tid; k < n; k += 256) {
+                    const double t = rho[k] / cs;
+                    const double u = 1.0 - t * t;
+                    const double w1 = t < 1.0 ? u * u : 0.0;
+                    wk[k] = w1;
+                    if (use_lds) Wg[k] = w1;
+                    zeros += w1 == 0.0 ? 1 : 0;
+                }
+                zeros = wave_sum(zeros);
+                if (lane == 0) iscr[8 + wave] = zeros;
+                if (use_lds) lds_barrier();
+                else __syncthreads();
+                n_zero = iscr[8] + iscr[9] + iscr[10] + iscr[11] + (n_rows - n);
+                reweighted = it + 1;
+            }
+        } else {
+            n_zero = n_rows;
+        }
+        if (wave != 0) return;
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) a.v_c[(size_t)b * 6 + i] = vout[i];
+            a.status[b] = status;
+            int32_t* info = a.info + (size_t)b * 8;
+            info[0] = n_mutual; info[1] = n_rows; info[2] = same_image ? 1 : 0; info[3] = n_matched;
+            info[4] = sweeps; info[5] = R; info[6] = reweighted; info[7] = n_zero;
+        }
+        return;
+    }
+    // The plain law (servo_kernel<false>, what every default update runs), inline and as it was before the robust law existed:
+    // routed through the device functions above, this instantiation measured 0.5 us slower (profiles/robust_law.txt).
     const bool try_fast = status == ST_OK && R > 0;   // L in LDS or (dense selections) in the global workspace
     if (try_fast) {
         // 27 quantities x 8 row slices on 216 threads (fixed slice order -> deterministic)
@@ -415,15 +713,31 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     }
 }
 
+template <bool ROBUST>
+static size_t servo_lds_bytes(const ServoArgs& a) {
+    size_t lds = servo_f64_offset(a.T, a.max_rows) + (size_t)7 * kLdsRows * 8 + (40 + 8 * 27) * 8;
+    if (ROBUST) lds += ((size_t)7 * kLdsRows + kLdsRows / 2 + a.max_rows) * 8;
+    return lds;
+}
+
 int launch_servo(const ServoArgs& a, hipStream_t stream) {
     if (a.n_pairs <= 0 || a.T <= 0 || a.grid * a.grid != a.T || a.max_rows < a.num_pairs || a.num_pairs <= 0) return -2;
     if (a.mode == SEL_DENSE && a.max_rows < a.T) return -2;
-    const size_t lds = servo_f64_offset(a.T, a.max_rows) + (size_t)7 * kLdsRows * 8 + (40 + 8 * 27) * 8;
+    if (a.robust_iters < 0 || a.robust_iters > 16 || (a.robust_iters > 0 && !a.W_ws)) return -2;
+    const bool robust = a.robust_iters > 0;
+    const size_t lds = robust ? servo_lds_bytes<true>(a) : servo_lds_bytes<false>(a);
     if (lds > 160 * 1024) return -3;
-    static std::atomic<unsigned long long> raised{0};   // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in
-    if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel), 160 * 1024, raised)) return -3;
-    launch(servo_kernel, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T,
-           a.mode, a.sel_stride, a);
+    // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in, per instantiation
+    static std::atomic<unsigned long long> raised{0}, raised_robust{0};
+    if (robust) {
+        if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<true>), 160 * 1024, raised_robust)) return -3;
+        launch(servo_kernel<true>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T,
+               a.mode, a.sel_stride, a);
+    } else {
+        if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<false>), 160 * 1024, raised)) return -3;
+        launch(servo_kernel<false>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T,
+               a.mode, a.sel_stride, a);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

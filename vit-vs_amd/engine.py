@@ -77,6 +77,8 @@ class Engine:
         self.tokens = self.lib.vitvs_tokens(self.handle)
         self.desc_dim = self.lib.vitvs_desc_dim(self.handle)
         assert self.tokens == cfg.tokens and self.lib.vitvs_register_tokens(self.handle) == cfg.registers
+        if self.params.robust_iterations:
+            self.set_option("robust_law", self.params.robust_iterations)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -433,7 +435,8 @@ class Engine:
 
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
-        """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's)."""
+        """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),
+        ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings)."""
         self._check(self.lib.vitvs_set_option(self.handle, name.encode(), int(value)), f"vitvs_set_option({name})")
         return self
 
@@ -464,4 +467,12 @@ class Engine:
         rc = self.lib.vitvs_last_details(self.handle, n_pairs, p(nn1), p(nn2), p(sim1), p(info), p(sel), p(suv),
                                          p(feat), p(L))
         self._check(rc, "vitvs_last_details")
-        return dict(nn_1=nn1, nn_2=nn2, sim_1=sim1, info=info, selected=sel, s_uv=suv, feat=feat, L=L)
+        return dict(nn_1=nn1, nn_2=nn2, sim_1=sim1, info=info, selected=sel, s_uv=suv, feat=feat, L=L,
+                    weights=self.last_weights(n_pairs))
+
+    def last_weights(self, n_pairs: int = 1) -> np.ndarray:
+        """``vitvs_last_weights``: float64 [n, max_rows], the weight of every feature pair in the last law evaluation's final
+        solve (all 1 on live pairs with ``robust_law`` off; 0 on zero-padded and unused rows).  Synchronises."""
+        w = np.empty((n_pairs, self.max_rows), np.float64)
+        self._check(self.lib.vitvs_last_weights(self.handle, n_pairs, w.ctypes.data_as(C.c_void_p)), "vitvs_last_weights")
+        return w

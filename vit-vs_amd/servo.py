@@ -220,6 +220,9 @@ class Controller:
                  selection: str = "reference"):
         self.engine = engine
         self.params = params or engine.params
+        if params is not None and params.robust_iterations != engine.params.robust_iterations:
+            engine.set_option("robust_law", params.robust_iterations)      # the law of the params this controller was given
+            engine.params = engine.params.replace(robust_iterations=params.robust_iterations)
         self.num_pairs = self.params.num_pairs
         self.dino_input_size = engine.cfg.img_size
         self.goal_image = goal_image                      # PIL image or uint8 array, any size
@@ -438,6 +441,11 @@ class MultiController:
         n = len(goal_images)
         if self.pipe is None and self.engine.max_pairs < n:
             raise ValueError(f"engine.max_pairs ({self.engine.max_pairs}) is smaller than the number of cameras ({n})")
+        if params is not None:
+            for e in self.engines:                        # every pipeline slot evaluates the law of the params given
+                if e.params.robust_iterations != params.robust_iterations:
+                    e.set_option("robust_law", params.robust_iterations)
+                    e.params = e.params.replace(robust_iterations=params.robust_iterations)
         self.cameras = [Controller(self.engine, g, params, selection="order") for g in goal_images]
         self.params = self.cameras[0].params
         self._buffers = {}                                # pipeline mode: per-camera device inputs at stable addresses
