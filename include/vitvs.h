@@ -231,6 +231,19 @@ VITVS_API int vitvs_servo_from_nn_dev(vitvs_handle* h, int32_t T, const int32_t*
                             const uint16_t* Z_mm, const double* K, int32_t select_mode, const int32_t* selection,
                             int32_t n_selected, int32_t num_pairs, double* v_c, int32_t* status, void* stream);
 
+/* vitvs_servo_from_nn_dev with sub-patch offsets of the matches (option "subpatch", below): `offsets` fp32 [T][2] = (dr, dc) in
+ * patch pitches for every token of the desired frame, moves the match of each selected token off its patch centre before the
+ * pixel features are formed, whatever the handle's option says; NULL: exactly vitvs_servo_from_nn_dev.  Replaces nothing: the
+ * reference's features are patch centres (vitvs_v2.py:511-513). */
+VITVS_API int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1,
+                            const uint16_t* Z_mm, const double* K, int32_t select_mode, const int32_t* selection,
+                            int32_t n_selected, int32_t num_pairs, const float* offsets, double* v_c, int32_t* status, void* stream);
+/* The sub-patch offsets themselves on caller descriptors (normalised inside, like vitvs_correspond_dev): desc1 (desired), desc2
+ * (current) fp32 [T][Dp], Dp a multiple of 32, T a square; nn_1 int32 [T] -> offsets fp32 [T][2] = (dr, dc) of every token (0 for
+ * a match outside 0 .. T - 1).  The arithmetic the law's kernel runs under the option, without a forward.  Replaces nothing. */
+VITVS_API int vitvs_refine_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* desc1, const float* desc2, const int32_t* nn_1,
+                            float* offsets, void* stream);
+
 /* --- introspection of the last compute_velocity / servo call (device -> host copies, synchronising).
  * What detect_features() returns besides v_c (vitvs_v2.py:523) and what the parity tests check.
  *   nn_1, nn_2 int32 [n_pairs][T]; sim_1 fp32 [n_pairs][T]
@@ -253,6 +266,11 @@ VITVS_API int vitvs_last_details(vitvs_handle* h, int32_t n_pairs, int32_t* nn_1
  *   of a short selection) and from n_feature_rows on.  `L` and `e` of vitvs_last_details stay the unweighted ones.
  * Synchronising, always read from the device.  Replaces nothing: the reference's law has no weights (vitvs_v2.py:613-622). */
 VITVS_API int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w);
+/* The sub-patch offsets (dr, dc), in patch pitches, every feature row's match had in the last law evaluation (option "subpatch",
+ * below): offsets float [n_pairs][max_rows][2]; 0 for zero-padded rows, from n_feature_rows on, under the same-image shortcut
+ * and with the option off.  With the option on, s_uv[..][2:4], feat (Z, x, y) and L of vitvs_last_details are those of the
+ * moved matches.  Synchronising, always read from the device.  Replaces nothing (vitvs_v2.py:511-513: patch centres). */
+VITVS_API int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets);
 
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
@@ -281,6 +299,17 @@ VITVS_API int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w);
  *                          w = (1 - t^2)^2 for t = rho / (c sigma) < 1, else 0; v_c = -lambda x of the last weighted solve.
  *                          Zero-padded pairs have weight 0.  Applies to every entry point that evaluates the law; changing
  *                          it drops the handle's captured graphs.  vitvs_last_weights returns the final weights.
+ *   "subpatch"     0 / 1   an extension beyond the reference (its features are patch centres, vitvs_v2.py:511-513, so a match
+ *                          moves in steps of one patch pitch).  0 (default): that, bit for bit.  1: inside the law's kernel
+ *                          every selected match j = nn_1[i] is moved by (dr, dc) patch pitches, per axis the vertex of the
+ *                          parabola through the similarities of goal token i to j and its two neighbours (a, m, p):
+ *                          den = a - 2 m + p, delta = clamp(0.5 (a - p) / den, -1/2, 1/2) when den < 0, else 0, and 0 on the
+ *                          border row / column; the similarities are the ones the arg-max used, recomputed in fp32 from the
+ *                          handle's normalised descriptors (binned descriptors: from the raw Gram).  The current-frame pixel is
+ *                          rint((centre + delta S / grid) scale), the depth is read there; the goal side stays the patch
+ *                          centre.  Applies to every entry point that evaluates the law from the handle's own forward
+ *                          (vitvs_compute_velocity[_dev], vitvs_reselect), composes with "robust_law", and drops the handle's
+ *                          captured graphs when changed.  vitvs_last_offsets returns the offsets.
  * Returns 0, or -5 for an unknown name / a value out of range. */
 VITVS_API int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value);
 /* The handles of such an arrangement run ONE network: `h` (created with the same network, input geometry and precision, no

@@ -170,6 +170,8 @@ class ServoParams:
     max_velocity: float = 1.0
     robust_iterations: int = 0     # Tukey re-weightings of the control law (option "robust_law", 1 .. 16); 0 = the reference's
                                    # plain least squares.  Not in the reference's config.yaml: an extension, off by default
+    subpatch: bool = False         # sub-patch refinement of the matches (option "subpatch"); False = the reference's patch centres.
+                                   # Not in the reference's config.yaml either: an extension, off by default
 
     @property
     def c_x(self) -> float:
@@ -226,7 +228,8 @@ def load_reference_config(source) -> ReferenceConfig:
     Same required keys as ``Controller.load_parameters`` (a missing one raises ``KeyError`` naming it) and the same
     defaults for the optional ones: ``max_velocity`` 1.0, ``ema_alpha`` 0.1 (NOT the 0.8 the shipped file sets),
     ``max_velocity_vector_history`` 200, ``background_thresh`` 0.5 (vitvs_v2.py:287, 296, 316, 319).  ``robust_iterations`` (this
-    project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0."""
+    project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
+    sub-patch refinement of the matches) likewise, else False."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -242,9 +245,10 @@ def load_reference_config(source) -> ReferenceConfig:
                         lambda_=float(cfg["lambda_"]), num_pairs=int(cfg["num_pairs"]),
                         dino_input_size=int(cfg["dino_input_size"]), use_feature_binning=bool(cfg["use_feature_binning"]),
                         ema_alpha=float(cfg.get("ema_alpha", 0.1)), max_velocity=float(cfg.get("max_velocity", 1.0)),
-                        robust_iterations=int(cfg.get("robust_iterations", 0)))
+                        robust_iterations=int(cfg.get("robust_iterations", 0)), subpatch=bool(cfg.get("subpatch", False)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
-            "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations"}
+            "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
+            "subpatch"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

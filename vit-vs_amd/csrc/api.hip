@@ -116,6 +116,9 @@ struct vitvs_handle {
     double* Wws = nullptr;    // [max_pairs][max_rows] the robust law's final weights (vitvs_last_weights)
     int robust_iters = 0;     // option "robust_law": Tukey re-weightings of the control law, 0 = the reference's plain law
     bool last_robust = false; // the last law evaluation wrote Wws
+    float* off_ws = nullptr;  // [max_pairs][max_rows][2] the sub-patch offsets of the last law evaluation (vitvs_last_offsets)
+    int subpatch = 0;         // option "subpatch": matches are refined off their patch centres, 0 = the reference's patch centres
+    bool last_refine = false; // the last law evaluation wrote off_ws
     int last_pairs = 0, last_T = 0;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
     // graph replays' own copy of the selection
@@ -155,7 +158,7 @@ struct vitvs_handle {
     } hs;
     hipStream_t host_stream = nullptr;
     bool details_pinned = false;        // hs.det holds the last call's detail block (vitvs_last_details serves it from there)
-    struct HostTables { int n_pairs = 0, T = 0; bool have_depth = false; } host_tables;   // what vitvs_reselect may build on
+    struct HostTables { int n_pairs = 0, T = 0; bool have_depth = false; int des_shared = 0; } host_tables;   // what vitvs_reselect may build on
     unsigned char* det_block = nullptr; // device copy of the detail block (detail_pointers), one allocation
     size_t det_bytes = 0;
     std::vector<int32_t> depth_sites;   // linear pixel index of every token's patch centre that lies inside the depth image (the only
@@ -486,8 +489,16 @@ int forward(vitvs_handle* h, int n_des, const uint8_t* des, int n_cur, const uin
 // (24 in the servo loop, 48 in the rotation search, vitvs_v2.py:1151-1189), so it is a per-call argument.
 int call_num_pairs(const vitvs_handle* h, int32_t num_pairs) { return num_pairs > 0 ? num_pairs : h->cfg.num_pairs; }
 
+// The sub-patch refinement of one law evaluation: OFF, from a caller's offset table, or from the handle's own forward
+struct RefineSpec {
+    const float* table = nullptr;   // [T][2] (vitvs_servo_from_nn_ex_dev)
+    bool from_forward = false;      // option "subpatch": the descriptors / raw Gram the forward left in the handle
+    int des_shared = 0;
+};
+
 int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const double* K, int mode, int num_pairs,
-              const int32_t* selection, const int32_t* n_selected, double* v_c, int32_t* status, hipStream_t st) {
+              const int32_t* selection, const int32_t* n_selected, double* v_c, int32_t* status, hipStream_t st,
+              const RefineSpec& rf = RefineSpec{}) {
     const vitvs_config& c = h->cfg;
     if (num_pairs <= 0 || num_pairs > c.max_rows) return set_err(h, -5, "num_pairs must be in 1 .. max_rows");
     const int g = (int)floor(sqrt((double)T));  // reference: int(np.sqrt(T)), vitvs_v2.py:75
@@ -514,7 +525,16 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     a.robust_iters = h->robust_iters; a.W_ws = h->Wws;
     a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
     a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
-    h->last_pairs = n_pairs; h->last_T = T; h->last_robust = h->robust_iters > 0;
+    a.refine = (rf.table || rf.from_forward) ? 1 : 0;
+    if (a.refine) {
+        a.pitch_in = scale; a.off_out = h->off_ws; a.off_in = rf.table;
+        if (rf.from_forward) {
+            a.des_shared = rf.des_shared;
+            if (h->gram_ws) { a.G = h->gram_ws; a.sq = h->sq; }
+            else { a.dn = h->dn; a.Dp = h->Dp; }
+        }
+    }
+    h->last_pairs = n_pairs; h->last_T = T; h->last_robust = h->robust_iters > 0; h->last_refine = a.refine != 0;
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(a, st); }
     if (rc) return set_err(h, rc, "servo launch failed (LDS budget or bad arguments)");
@@ -688,6 +708,7 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     if (!rc) rc = dev_alloc(h, &h->sel_out, P * R);
     if (!rc) rc = dev_alloc(h, &h->Lws, 2 * P * 7 * 2 * R);   // L and e per pair, then the Jacobi SVD's working copies
     if (!rc) rc = dev_alloc(h, &h->Wws, P * R);
+    if (!rc) rc = dev_alloc(h, &h->off_ws, P * R * 2);
     const size_t img_bytes = (size_t)cfg->img_size * cfg->img_size * 3;
     h->staged_frame_bytes = img_bytes;
     if (!rc) rc = dev_alloc(h, &h->st_cur, P * img_bytes);
@@ -1045,9 +1066,36 @@ int vitvs_correspond_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* de
     return 0;
 }
 
+int vitvs_refine_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* desc1, const float* desc2, const int32_t* nn_1,
+                     float* offsets, void* stream) {
+    if (!h || !desc1 || !desc2 || !nn_1 || !offsets) return set_err(h, -1, "null argument");
+    if (T <= 0 || Dp <= 0 || Dp % 32 != 0) return set_err(h, -5, "Dp must be a positive multiple of 32");
+    const int g = (int)floor(sqrt((double)T));
+    if (g * g != T) return set_err(h, -5, "token count is not a square grid");
+    if ((size_t)2 * T * Dp > h->dn_elems) return set_err(h, -3, "descriptors exceed the handle's workspace");
+    DeviceScope dev(h);
+    hipStream_t st = as_stream(stream);
+    h->goal_frames = 0;                         // the descriptor workspace is overwritten
+    h->host_tables = vitvs_handle::HostTables{};   // and with it what vitvs_reselect would refine from
+    int rc = launch_normalize_rows(desc1, h->dn, T, Dp, st);
+    if (!rc) rc = launch_normalize_rows(desc2, h->dn + (size_t)T * Dp, T, Dp, st);
+    if (rc) return set_err(h, rc, "normalise launch failed");
+    rc = launch_refine(h->dn, h->dn + (size_t)T * Dp, nn_1, T, g, Dp, offsets, st);
+    if (rc) return set_err(h, rc, "refine launch failed");
+    return 0;
+}
+
 int vitvs_servo_from_nn_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1,
                             const uint16_t* Z_mm, const double* K, int32_t select_mode, const int32_t* selection,
                             int32_t n_selected, int32_t num_pairs, double* v_c, int32_t* status, void* stream) {
+    return vitvs_servo_from_nn_ex_dev(h, T, nn_1, nn_2, sim_1, Z_mm, K, select_mode, selection, n_selected, num_pairs, nullptr, v_c,
+                                      status, stream);
+}
+
+int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1,
+                               const uint16_t* Z_mm, const double* K, int32_t select_mode, const int32_t* selection,
+                               int32_t n_selected, int32_t num_pairs, const float* offsets, double* v_c, int32_t* status,
+                               void* stream) {
     if (!h || !nn_1 || !nn_2 || !sim_1 || !K || !v_c || !status) return set_err(h, -1, "null argument");
     if ((size_t)T > h->best_elems) return set_err(h, -3, "T exceeds the handle's workspace");
     DeviceScope dev(h);
@@ -1056,7 +1104,9 @@ int vitvs_servo_from_nn_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, con
     int rc = launch_encode_best(nn_1, nn_2, sim_1, T, h->row_best, h->col_best, st);
     if (rc) return set_err(h, rc, "encode launch failed");
     VITVS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->st_nsel), n_selected, 1, st));
-    return run_servo(h, 1, T, Z_mm, K, select_mode, call_num_pairs(h, num_pairs), selection, h->st_nsel, v_c, status, st);
+    RefineSpec rf;
+    rf.table = offsets;
+    return run_servo(h, 1, T, Z_mm, K, select_mode, call_num_pairs(h, num_pairs), selection, h->st_nsel, v_c, status, st, rf);
 }
 
 // One update = forward of the call's image list (desired frames first, then current frames) + the tail
@@ -1076,6 +1126,7 @@ struct UpdateArgs {
     // depth_sites), so T 2-byte gathers stand for the 614 KB image.
     const uint16_t* late_src = nullptr;
     uint16_t* late_dst = nullptr;
+    // (option "subpatch": a refined match can lie on any pixel, so the whole image is copied: late_sites == nullptr)
     const int32_t* late_sites = nullptr;
     int late_count = 0, late_pairs = 0;
     size_t late_stride = 0;                     // pixels per depth image
@@ -1085,12 +1136,16 @@ static inline void late_inputs(const UpdateArgs& u) {
     for (int b = 0; b < u.late_pairs; ++b) {
         const uint16_t* src = u.late_src + (size_t)b * u.late_stride;
         uint16_t* dst = u.late_dst + (size_t)b * u.late_stride;
+        if (!u.late_sites) { memcpy(dst, src, u.late_stride * sizeof(uint16_t)); continue; }
         for (int i = 0; i < u.late_count; ++i) dst[u.late_sites[i]] = src[u.late_sites[i]];
     }
 }
 
 static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) {
     const int n_des = u.des_shared ? 1 : u.n_pairs, n_img = n_des + u.n_pairs;
+    RefineSpec rf;
+    rf.from_forward = h->subpatch != 0;
+    rf.des_shared = u.des_shared ? 1 : 0;
     h->desc_keys = u.n_pairs * h->T;
     // cached goal: only the current frames (images n_des .. n_img - 1 of the call's list) go through the network
     int rc = u.I_des ? forward_chain(h, 0, n_img, n_des, u.I_des, u.I_cur, h->part, st)
@@ -1108,7 +1163,7 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
           rc = launch_gram_stencil_argmax(h->gram_ws, h->sq, h->T, h->grid, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st); }
         if (rc) return set_err(h, rc, "gram stencil launch failed");
         late_inputs(u);
-        return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st);
+        return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st, rf);
     }
     if (!desc_in_forward(h)) {
         Span sp(h, KC_DESCRIPTORS, st);
@@ -1126,7 +1181,7 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
     if (rc) return set_err(h, rc, "gram launch failed");
     late_inputs(u);
     return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c,
-                     u.status, st);
+                     u.status, st, rf);
 }
 
 // VITVS_GRAPH=1: the update is captured once per argument tuple and replayed.  The selection array is the one argument
@@ -1180,7 +1235,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
         ge = &h->graphs.back();
     }
     ge->last_use = ++h->graph_clock;
-    h->last_pairs = u.n_pairs; h->last_T = h->T; h->last_robust = h->robust_iters > 0;
+    h->last_pairs = u.n_pairs; h->last_T = h->T; h->last_robust = h->robust_iters > 0; h->last_refine = h->subpatch != 0;
     VITVS_HIP_CHECK(hipGraphLaunch(ge->exec, st));
     return 0;
 }
@@ -1287,7 +1342,8 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     UpdateArgs u{n_pairs, des_shared, select_mode, np, h->st_cur, I_des ? h->st_des : nullptr, Z_mm ? hs.depth : nullptr, hs.K,
                  hs.sel, hs.nsel, hs.vc, hs.status};
     if (Z_mm) {
-        u.late_src = Z_mm; u.late_dst = hs.depth; u.late_sites = h->depth_sites.data(); u.late_count = (int)h->depth_sites.size();
+        u.late_src = Z_mm; u.late_dst = hs.depth; u.late_count = (int)h->depth_sites.size();
+        u.late_sites = h->subpatch ? nullptr : h->depth_sites.data();
         u.late_pairs = n_pairs; u.late_stride = (size_t)c.u_max * c.v_max;
     }
     rc = velocity_update(h, u, st);
@@ -1300,7 +1356,7 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     memcpy(v_c, hs.vc, (size_t)n_pairs * 6 * sizeof(double));
     memcpy(status, hs.status, (size_t)n_pairs * 4);
     h->details_pinned = true;
-    h->host_tables = vitvs_handle::HostTables{n_pairs, h->T, Z_mm != nullptr};
+    h->host_tables = vitvs_handle::HostTables{n_pairs, h->T, Z_mm != nullptr, des_shared ? 1 : 0};
     return 0;
 }
 
@@ -1327,8 +1383,11 @@ int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t* selectio
     } else if (select_mode == VITVS_SELECT_ORDER) {
         memcpy(hs.sel, selection, (size_t)n_pairs * T * 4);
     }
+    RefineSpec rf;
+    rf.from_forward = h->subpatch != 0;
+    rf.des_shared = h->host_tables.des_shared;
     int rc = run_servo(h, n_pairs, T, h->host_tables.have_depth ? hs.depth : nullptr, hs.K, select_mode, np, hs.sel, hs.nsel, hs.vc,
-                       hs.status, h->host_stream);
+                       hs.status, h->host_stream, rf);
     if (rc) return rc;
     rc = launch_copy16(h->det_block, hs.det, h->det_bytes, h->host_stream);
     if (rc) return set_err(h, rc, "detail copy launch failed");
@@ -1425,6 +1484,18 @@ int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value) {
         }
         return 0;
     }
+    if (nm == "subpatch") {
+        if (value != 0 && value != 1) return set_err(h, -5, "subpatch takes 0 (patch centres) or 1 (refined matches)");
+        if ((int)value != h->subpatch) {        // captured updates hold the previous law's kernel and arguments; the pinned depth
+            DeviceScope dev(h);                 // image of the last host-pointer call holds only what the previous setting reads
+            VITVS_HIP_CHECK(hipDeviceSynchronize());
+            drop_graphs(h);
+            h->subpatch = (int)value;
+            h->details_pinned = false;
+            h->host_tables = vitvs_handle::HostTables{};
+        }
+        return 0;
+    }
     return set_err(h, -5, "unknown option " + nm);
 }
 
@@ -1446,6 +1517,26 @@ int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w) {
             for (size_t k = 0; k < n; ++k) w[b * R + k] = k < live ? 1.0 : 0.0;
         }
         for (size_t k = n; k < R; ++k) w[b * R + k] = 0.0;
+    }
+    return 0;
+}
+
+int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets) {
+    if (!h || !offsets) return set_err(h, -1, "null argument");
+    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    DeviceScope dev(h);
+    const size_t R = h->cfg.max_rows, P = n_pairs;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    if (!h->last_refine) {
+        memset(offsets, 0, P * R * 2 * sizeof(float));
+        return 0;
+    }
+    std::vector<int32_t> inf(P * 8);
+    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(offsets, h->off_ws, P * R * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < P; ++b) {
+        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
+        for (size_t k = n; k < R; ++k) offsets[(b * R + k) * 2] = offsets[(b * R + k) * 2 + 1] = 0.f;
     }
     return 0;
 }

@@ -26,6 +26,7 @@
 
 #include "gemm_core.h"
 #include "kernels.h"
+#include "refine.h"
 
 namespace vitvs {
 
@@ -258,6 +259,34 @@ __global__ void encode_best_kernel(const int32_t* __restrict__ nn1, const int32_
     if (i >= T) return;
     rb[i] = pack_best(sim1[i], (unsigned)nn1[i]);
     cb[i] = pack_best(0.f, (unsigned)nn2[i]);
+}
+
+// Sub-patch offsets of every token of one pair (vitvs_refine_dev): the arithmetic of the law's REFINE instantiations (refine.h)
+// without a forward or a law around it.  One wave per goal token, four tokens per workgroup.
+__global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ d1, const float* __restrict__ d2,
+                                                     const int32_t* __restrict__ nn1, int T, int grid, int Dp,
+                                                     float* __restrict__ offsets) {
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (i >= T) return;                                            // (a whole wave; the kernel has no barrier)
+    const int j = __builtin_amdgcn_readfirstlane(nn1[i]);
+    float dr = 0.f, dc = 0.f;
+    if (j >= 0 && j < T) {
+        const RefineSites t = refine_sites(j, grid);
+        float s[5];
+        refine_wave_sims(d1 + (size_t)i * Dp, d2, t, Dp, lane, s);
+        refine_from_sims(t, s, dr, dc);
+    }
+    if (lane == 0) {
+        offsets[2 * i] = dr;
+        offsets[2 * i + 1] = dc;
+    }
+}
+
+int launch_refine(const float* d1, const float* d2, const int32_t* nn1, int T, int grid, int Dp, float* offsets, hipStream_t stream) {
+    if (T <= 0 || grid * grid != T || Dp <= 0 || Dp % 4 != 0) return -2;
+    launch(refine_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, d1, d2, nn1, T, grid, Dp, offsets);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_decode_best(const unsigned long long* row_best, const unsigned long long* col_best, int T, int32_t* nn1,

@@ -243,6 +243,9 @@ int launch_gram_dense(const float* dn, int T, int Dp, int n_pairs, int des_share
 int launch_gram_raw_tokens(const float* x, int T, int P, int D, int n_pairs, int des_shared, float* G, hipStream_t stream);
 int launch_gram_stencil_argmax(const float* G, const float* sq, int T, int grid, int n_pairs, int des_shared,
                                unsigned long long* row_best, unsigned long long* col_best, hipStream_t stream);
+// Sub-patch offsets (refine.h) of every token of one pair: d1, d2 fp32 normalised rows [T][Dp] (Dp a multiple of 4), nn1 [T]
+// -> offsets [T][2] = (dr, dc); matches outside 0 .. T - 1 get (0, 0).  One wave per token.
+int launch_refine(const float* d1, const float* d2, const int32_t* nn1, int T, int grid, int Dp, float* offsets, hipStream_t stream);
 
 // packed keys <-> (nn_1, sim_1, nn_2) tables for the standalone correspondence / servo entry points
 int launch_decode_best(const unsigned long long* row_best, const unsigned long long* col_best, int T, int32_t* nn1,
@@ -288,6 +291,15 @@ struct ServoArgs {
     int robust_iters;         // re-weightings N, 0 .. 16
     double pitch_u, pitch_v;  // patch pitch in camera pixels (stride * u_max / S, stride * v_max / S): sigma_min = half of it, normalised
     double* W_ws;             // [n_pairs][max_rows] final weight of every feature pair (output); the working weights when L is global
+    // Sub-patch refinement (option "subpatch", refine.h); with refine == 0 none of these is read
+    int refine;               // 1: the REFINE instantiation moves every selected match by its (dr, dc)
+    int des_shared, Dp;       // frames of dn / sq: goal frame of pair b = (des_shared ? 0 : b), current frame = n_des + b
+    double pitch_in;          // patch pitch in extractor-input pixels, S / grid
+    const float* off_in;      // [n_pairs][T][2] given offsets per goal token, or null: computed from one of the sources below
+    const float* dn;          // fp32 normalised descriptors [frames][T][Dp] (GRAM_F32, GRAM_SPLIT, GRAM_WIDE), or
+    const float* G;           // raw token Gram [n_pairs][T][T] with
+    const float* sq;          // the tokens' squared norms [frames][T] (GRAM_STENCIL)
+    float* off_out;           // [n_pairs][max_rows][2] (dr, dc) of every feature row (output)
 };
 int launch_servo(const ServoArgs& a, hipStream_t stream);
 

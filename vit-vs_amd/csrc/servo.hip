@@ -1,8 +1,10 @@
 // From nearest-neighbour tables to the camera twist: mutual-NN filter, feature selection,
 // pixel features, depth lookup, interaction matrix L_e and v_c = -lambda * pinv(L_e) e.
 // One workgroup per frame pair; the SVD-based pseudo-inverse runs in fp64 on one wavefront.
-// servo_kernel<false> is that law; servo_kernel<true> (option "robust_law", no counterpart in the reference) re-weights the
+// servo_kernel<false, .> is that law; servo_kernel<true, .> (option "robust_law", no counterpart in the reference) re-weights the
 // feature pairs by Tukey's biweight of their residuals and solves again, N times, in the same launch.
+// servo_kernel<., true> (option "subpatch", no counterpart in the reference either) moves every selected match off its patch
+// centre by the sub-patch offsets of refine.h before the pixel features are formed.
 //
 // Reference arithmetic being replaced (vitvs_v2.py):
 //   same-image shortcut  mean(sim_1) > 0.99                   :84-101
@@ -22,6 +24,7 @@
 // So: candidates = { i : nn_2[nn_1[i]] == i } when their count is < T, nothing when it equals T.
 #include "common.h"
 #include "kernels.h"
+#include "refine.h"
 
 #pragma clang fp contract(off)
 
@@ -51,6 +54,14 @@ __device__ __forceinline__ void token_pixel(const ServoArgs& a, int tok, long& u
     const float c = __fadd_rn(__fmul_rn((float)(tok % g), a.scale_f), a.half_f);
     u = (long)rint((double)c * a.scale_x);
     v = (long)rint((double)r * a.scale_y);
+}
+// The same with the match moved by (dr, dc) patch pitches off its centre (REFINE); zero offsets give token_pixel's result.
+__device__ __forceinline__ void refined_pixel(const ServoArgs& a, int tok, float dr, float dc, long& u, long& v) {
+    const int g = a.grid;
+    const float r = __fadd_rn(__fmul_rn((float)(tok / g), a.scale_f), a.half_f);
+    const float c = __fadd_rn(__fmul_rn((float)(tok % g), a.scale_f), a.half_f);
+    u = (long)rint(((double)c + (double)dc * a.pitch_in) * a.scale_x);
+    v = (long)rint(((double)r + (double)dr * a.pitch_in) * a.scale_y);
 }
 
 // G = L^T W L (21, upper triangle) and g = L^T W e (6): 27 quantities x 8 row slices on 216 threads into Gs[40 ..) (fixed
@@ -215,7 +226,7 @@ __device__ __forceinline__ int solve_jacobi(double* Lc, int rcap, int R, int lan
 
 // The leading flat arguments repeat the fields of `a` the first memory requests depend on: they are
 // preloaded into SGPRs by the command processor (kernarg preload), the struct is fetched by the wave.
-template <bool ROBUST>
+template <bool ROBUST, bool REFINE>
 __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __restrict__ row_best,
                                                     const unsigned long long* __restrict__ col_best,
                                                     const double* __restrict__ Kin, const int32_t* __restrict__ selection,
@@ -253,7 +264,8 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
 
     // 1. decode the packed (similarity, index) keys.  With one token per thread the depth of the
     // token's match is requested here as well (its address depends on nn_1 only), two phases early.
-    const bool prefetch_depth = depth_all != nullptr && T <= 256;
+    // (REFINE: the pixel of a match is known only after its offsets, phase 3b; the depth is read there)
+    const bool prefetch_depth = !REFINE && depth_all != nullptr && T <= 256;
     int dpre = 0;
     float ssum = 0.f;
     unsigned long long kr0 = 0, kc0 = 0;
@@ -356,6 +368,60 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     int32_t* uv_out = a.s_uv + (size_t)b * a.max_rows * 4;
     double* feat_out = a.feat + (size_t)b * a.max_rows * 4;
     int32_t* sel_out = a.sel_out + (size_t)b * a.max_rows;
+    // 3b. (REFINE) sub-patch offsets (dr, dc) of the selected rows, kept in LDS behind everything else and written out for
+    // vitvs_last_offsets; zero for padded rows and under the same-image shortcut
+    float* offL = reinterpret_cast<float*>(Gs + 40 + 8 * 27 + (ROBUST ? 7 * kLdsRows + kLdsRows / 2 + a.max_rows : 0));   // [max_rows][2]
+    if constexpr (REFINE) {
+        const bool any = !none && !too_few && !same_image;
+        float* off_out = a.off_out + (size_t)b * a.max_rows * 2;
+        const int n_des = a.des_shared ? 1 : a.n_pairs;
+        if (a.off_in || a.G) {
+            // a given table, or the stencil form (nine reads of the raw Gram per similarity): one thread per row
+            const float* tab = a.off_in ? a.off_in + (size_t)b * T * 2 : nullptr;
+            for (int k = tid; k < n_rows; k += 256) {
+                float dr = 0.f, dc = 0.f;
+                if (any && k < n_matched) {
+                    const int tok = sel[k], j = nn1[tok];
+                    if (tab) {
+                        dr = tab[2 * tok];
+                        dc = tab[2 * tok + 1];
+                    } else if (j >= 0 && j < T) {
+                        const RefineStencil sim{a.G + (size_t)b * T * T, a.sq + (size_t)(a.des_shared ? 0 : b) * T,
+                                                a.sq + (size_t)(n_des + b) * T, T, a.grid, tok};
+                        const RefineSites t = refine_sites(j, a.grid);
+                        float s[5];
+#pragma unroll
+                        for (int q = 0; q < 5; ++q) s[q] = sim(t.nb[q]);
+                        refine_from_sims(t, s, dr, dc);
+                    }
+                }
+                offL[2 * k] = dr; offL[2 * k + 1] = dc;
+                off_out[2 * k] = dr; off_out[2 * k + 1] = dc;
+            }
+        } else {
+            // the descriptor forms: one wave per row, five fixed-order dot products over the fp32 normalised descriptors
+            const float* d1 = a.dn + (size_t)(a.des_shared ? 0 : b) * T * a.Dp;
+            const float* d2 = a.dn + (size_t)(n_des + b) * T * a.Dp;
+            for (int k = wave; k < n_rows; k += 4) {
+                float dr = 0.f, dc = 0.f;
+                if (any && k < n_matched) {
+                    const int tok = __builtin_amdgcn_readfirstlane(sel[k]);
+                    const int j = __builtin_amdgcn_readfirstlane(nn1[tok]);
+                    if (j >= 0 && j < T) {
+                        const RefineSites t = refine_sites(j, a.grid);
+                        float s[5];
+                        refine_wave_sims(d1 + (size_t)tok * a.Dp, d2, t, a.Dp, lane, s);
+                        refine_from_sims(t, s, dr, dc);
+                    }
+                }
+                if (lane == 0) {
+                    offL[2 * k] = dr; offL[2 * k + 1] = dc;
+                    off_out[2 * k] = dr; off_out[2 * k + 1] = dc;
+                }
+            }
+        }
+        lds_barrier();
+    }
     for (int k = tid; k < n_rows; k += 256) {
         long us = 0, vs = 0, u = 0, v = 0;
         int tok = -1;
@@ -364,7 +430,8 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         if (live) {
             tok = sel[k];
             token_pixel(a, tok, us, vs);
-            token_pixel(a, same_image ? tok : nn1[tok], u, v);
+            if constexpr (REFINE) refined_pixel(a, same_image ? tok : nn1[tok], offL[2 * k], offL[2 * k + 1], u, v);
+            else token_pixel(a, same_image ? tok : nn1[tok], u, v);
             simk = same_image ? 1.0 : (double)simL[tok];
         }
         const double x = ((double)u - cx) / fx, y = ((double)v - cy) / fy;
@@ -536,7 +603,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         }
         return;
     }
-    // The plain law (servo_kernel<false>, what every default update runs), inline and as it was before the robust law existed:
+    // The plain law (servo_kernel<false, .>; <false, false> is what every default update runs), inline and as it was before the robust law existed:
     // routed through the device functions above, this instantiation measured 0.5 us slower (profiles/robust_law.txt).
     const bool try_fast = status == ST_OK && R > 0;   // L in LDS or (dense selections) in the global workspace
     if (try_fast) {
@@ -713,32 +780,35 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     }
 }
 
-template <bool ROBUST>
-static size_t servo_lds_bytes(const ServoArgs& a) {
+static size_t servo_lds_bytes(const ServoArgs& a, bool robust, bool refine) {
     size_t lds = servo_f64_offset(a.T, a.max_rows) + (size_t)7 * kLdsRows * 8 + (40 + 8 * 27) * 8;
-    if (ROBUST) lds += ((size_t)7 * kLdsRows + kLdsRows / 2 + a.max_rows) * 8;
+    if (robust) lds += ((size_t)7 * kLdsRows + kLdsRows / 2 + a.max_rows) * 8;
+    if (refine) lds += (size_t)a.max_rows * 2 * 4;
     return lds;
+}
+
+template <bool ROBUST, bool REFINE>
+static int launch_servo_as(const ServoArgs& a, size_t lds, hipStream_t stream) {
+    // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in, per instantiation
+    static std::atomic<unsigned long long> raised{0};
+    if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<ROBUST, REFINE>), 160 * 1024, raised)) return -3;
+    launch(servo_kernel<ROBUST, REFINE>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth,
+           a.T, a.mode, a.sel_stride, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_servo(const ServoArgs& a, hipStream_t stream) {
     if (a.n_pairs <= 0 || a.T <= 0 || a.grid * a.grid != a.T || a.max_rows < a.num_pairs || a.num_pairs <= 0) return -2;
     if (a.mode == SEL_DENSE && a.max_rows < a.T) return -2;
     if (a.robust_iters < 0 || a.robust_iters > 16 || (a.robust_iters > 0 && !a.W_ws)) return -2;
-    const bool robust = a.robust_iters > 0;
-    const size_t lds = robust ? servo_lds_bytes<true>(a) : servo_lds_bytes<false>(a);
+    // the refinement needs a place for its offsets and one source of them: a table, the raw Gram with the squared norms, or
+    // the normalised descriptors (16-byte rows)
+    if (a.refine && (!a.off_out || !(a.off_in || (a.G && a.sq) || (a.dn && a.Dp > 0 && a.Dp % 4 == 0)))) return -2;
+    const bool robust = a.robust_iters > 0, refine = a.refine != 0;
+    const size_t lds = servo_lds_bytes(a, robust, refine);
     if (lds > 160 * 1024) return -3;
-    // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in, per instantiation
-    static std::atomic<unsigned long long> raised{0}, raised_robust{0};
-    if (robust) {
-        if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<true>), 160 * 1024, raised_robust)) return -3;
-        launch(servo_kernel<true>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T,
-               a.mode, a.sel_stride, a);
-    } else {
-        if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<false>), 160 * 1024, raised)) return -3;
-        launch(servo_kernel<false>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T,
-               a.mode, a.sel_stride, a);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (robust) return refine ? launch_servo_as<true, true>(a, lds, stream) : launch_servo_as<true, false>(a, lds, stream);
+    return refine ? launch_servo_as<false, true>(a, lds, stream) : launch_servo_as<false, false>(a, lds, stream);
 }
 
 }  // namespace vitvs

@@ -79,6 +79,8 @@ class Engine:
         assert self.tokens == cfg.tokens and self.lib.vitvs_register_tokens(self.handle) == cfg.registers
         if self.params.robust_iterations:
             self.set_option("robust_law", self.params.robust_iterations)
+        if self.params.subpatch:
+            self.set_option("subpatch", 1)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -234,6 +236,22 @@ class Engine:
         self._check(rc, "vitvs_correspond_dev")
         return (nn1, nn2, sim1, smat) if want_matrix else (nn1, nn2, sim1)
 
+    def refine(self, desc1: torch.Tensor, desc2: torch.Tensor, nn_1) -> torch.Tensor:
+        """``vitvs_refine_dev``: the sub-patch offsets (option ``subpatch``) of every token's match on [T, D] descriptors and a
+        given ``nn_1`` [T]: float32 [T, 2] = (dr, dc) in patch pitches, on the device."""
+        d1 = desc1.to(self.device, torch.float32).contiguous()
+        d2 = desc2.to(self.device, torch.float32).contiguous()
+        t, d = d1.shape
+        pad = (-d) % 32
+        if pad:  # zero columns leave cosine similarities unchanged
+            d1 = torch.nn.functional.pad(d1, (0, pad))
+            d2 = torch.nn.functional.pad(d2, (0, pad))
+        nn1 = torch.as_tensor(nn_1).to(self.device, torch.int32).contiguous()
+        off = torch.empty((t, 2), dtype=torch.float32, device=self.device)
+        rc = self.lib.vitvs_refine_dev(self.handle, t, d + pad, _ptr(d1), _ptr(d2), _ptr(nn1), _ptr(off), _stream_ptr(self.device))
+        self._check(rc, "vitvs_refine_dev")
+        return off
+
     def _num_pairs(self, num_pairs) -> int:
         k = int(self.params.num_pairs if num_pairs is None else num_pairs)
         if not 1 <= k <= self.max_rows:
@@ -260,8 +278,9 @@ class Engine:
         order = torch.as_tensor(selection, dtype=torch.int32).reshape(n_pairs, tokens)
         return order.to(self.device).contiguous(), None
 
-    def servo_from_nn(self, nn_1, nn_2, sim_1, depth, K, mode=_lib.SELECT_DENSE, selection=None, num_pairs=None):
-        """Control law on given nearest-neighbour tables (one pair); ``num_pairs`` as in ``compute_velocity``."""
+    def servo_from_nn(self, nn_1, nn_2, sim_1, depth, K, mode=_lib.SELECT_DENSE, selection=None, num_pairs=None, offsets=None):
+        """Control law on given nearest-neighbour tables (one pair); ``num_pairs`` as in ``compute_velocity``.  ``offsets``
+        float32 [T, 2]: the sub-patch offsets (dr, dc) of every token's match (``vitvs_servo_from_nn_ex_dev``); None: patch centres."""
         nn1 = torch.as_tensor(nn_1).to(self.device, torch.int32).contiguous()
         nn2 = torch.as_tensor(nn_2).to(self.device, torch.int32).contiguous()
         s1 = torch.as_tensor(sim_1).to(self.device, torch.float32).contiguous()
@@ -275,8 +294,15 @@ class Engine:
         v = torch.zeros((1, 6), dtype=torch.float64, device=self.device)
         st = torch.zeros(1, dtype=torch.int32, device=self.device)
         n_sel = int(cnt[0].item()) if cnt is not None else 0
-        rc = self.lib.vitvs_servo_from_nn_dev(self.handle, t, _ptr(nn1), _ptr(nn2), _ptr(s1), _ptr(z), _ptr(kk), mode,
-                                              _ptr(sel), n_sel, k, _ptr(v), _ptr(st), _stream_ptr(self.device))
+        if offsets is None:
+            rc = self.lib.vitvs_servo_from_nn_dev(self.handle, t, _ptr(nn1), _ptr(nn2), _ptr(s1), _ptr(z), _ptr(kk), mode,
+                                                  _ptr(sel), n_sel, k, _ptr(v), _ptr(st), _stream_ptr(self.device))
+        else:
+            off = torch.as_tensor(offsets).to(self.device, torch.float32).contiguous()
+            if tuple(off.shape) != (t, 2):
+                raise VitvsError("offsets must be [T, 2]")
+            rc = self.lib.vitvs_servo_from_nn_ex_dev(self.handle, t, _ptr(nn1), _ptr(nn2), _ptr(s1), _ptr(z), _ptr(kk), mode,
+                                                     _ptr(sel), n_sel, k, _ptr(off), _ptr(v), _ptr(st), _stream_ptr(self.device))
         self._check(rc, "vitvs_servo_from_nn_dev")
         self._last_tokens = t
         return v[0], st[0]
@@ -436,7 +462,8 @@ class Engine:
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),
-        ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings)."""
+        ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings), ``subpatch`` (0: patch centres; 1: matches
+        refined by their sub-patch offsets)."""
         self._check(self.lib.vitvs_set_option(self.handle, name.encode(), int(value)), f"vitvs_set_option({name})")
         return self
 
@@ -468,7 +495,14 @@ class Engine:
                                          p(feat), p(L))
         self._check(rc, "vitvs_last_details")
         return dict(nn_1=nn1, nn_2=nn2, sim_1=sim1, info=info, selected=sel, s_uv=suv, feat=feat, L=L,
-                    weights=self.last_weights(n_pairs))
+                    weights=self.last_weights(n_pairs), offsets=self.last_offsets(n_pairs))
+
+    def last_offsets(self, n_pairs: int = 1) -> np.ndarray:
+        """``vitvs_last_offsets``: float32 [n, max_rows, 2], the sub-patch offsets (dr, dc) of every feature row's match in the
+        last law evaluation (all 0 with ``subpatch`` off, on zero-padded and unused rows).  Synchronises."""
+        off = np.empty((n_pairs, self.max_rows, 2), np.float32)
+        self._check(self.lib.vitvs_last_offsets(self.handle, n_pairs, off.ctypes.data_as(C.c_void_p)), "vitvs_last_offsets")
+        return off
 
     def last_weights(self, n_pairs: int = 1) -> np.ndarray:
         """``vitvs_last_weights``: float64 [n, max_rows], the weight of every feature pair in the last law evaluation's final

@@ -223,6 +223,9 @@ class Controller:
         if params is not None and params.robust_iterations != engine.params.robust_iterations:
             engine.set_option("robust_law", params.robust_iterations)      # the law of the params this controller was given
             engine.params = engine.params.replace(robust_iterations=params.robust_iterations)
+        if params is not None and params.subpatch != engine.params.subpatch:
+            engine.set_option("subpatch", int(params.subpatch))
+            engine.params = engine.params.replace(subpatch=params.subpatch)
         self.num_pairs = self.params.num_pairs
         self.dino_input_size = engine.cfg.img_size
         self.goal_image = goal_image                      # PIL image or uint8 array, any size
@@ -446,6 +449,9 @@ class MultiController:
                 if e.params.robust_iterations != params.robust_iterations:
                     e.set_option("robust_law", params.robust_iterations)
                     e.params = e.params.replace(robust_iterations=params.robust_iterations)
+                if e.params.subpatch != params.subpatch:
+                    e.set_option("subpatch", int(params.subpatch))
+                    e.params = e.params.replace(subpatch=params.subpatch)
         self.cameras = [Controller(self.engine, g, params, selection="order") for g in goal_images]
         self.params = self.cameras[0].params
         self._buffers = {}                                # pipeline mode: per-camera device inputs at stable addresses
