@@ -184,3 +184,28 @@ def test_attention_plan_of_the_library():
             assert (got, list(out)) == (rc, want), (hint, prec, n_img, n, h)
     finally:
         lib.vitvs_op_plan_in_flight(prev)
+
+
+def test_gram_plan_of_the_library():
+    """The correspondence stage per handle and call is host arithmetic as well (vitvs_op_gram_plan, no device call): form,
+    tile rows, columns, k-groups, band rows, workgroups per XCD, split.  The table: every geometry of tools/plan_cover.py x the
+    four precisions x binned off / on x max_pairs 1 .. 16 x n_pairs 1 .. max_pairs, then both sides of every switch point of
+    tests/test_gram_cover_host.py (each also at n_pairs = max_pairs) and its refusals, in the four precisions.  Columns: precision, binned, T, D, n_pairs,
+    max_pairs, return code, out[0..6]; recorded through this ABI before the stage was launched from its plan."""
+    import numpy as np
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 7)()
+    table = np.load(os.path.join(ROOT, "tests", "golden", "gram_plans.npz"))["plans"]
+    assert len(table) == 84 * 4 * 2 * 136 + 4 * 21
+    assert set(np.unique(table[:, 7]).tolist()) == {0, 1, 2, 3, 4} and (table[:, 6] == -2).sum() >= 16
+    at_capacity = {}
+    for prec, binned, T, D, n, max_pairs, rc, *want in table.tolist():
+        got = lib.vitvs_op_gram_plan(prec, binned, T, D, n, max_pairs, out)
+        assert (got, list(out)) == (rc, want), (prec, binned, T, D, n, max_pairs)
+        if n == max_pairs:
+            at_capacity[(prec, binned, T, D, max_pairs)] = (want[0], want[6])
+    # What the handle's workspaces rest on (it plans them at n_pairs = max_pairs): the form and the split of a call's plan do
+    # not depend on its pairs, only the tile does.
+    for prec, binned, T, D, n, max_pairs, rc, *want in table.tolist():
+        if rc == 0:
+            assert (want[0], want[6]) == at_capacity[(prec, binned, T, D, max_pairs)], (prec, binned, T, D, n, max_pairs)

@@ -4,7 +4,8 @@ The velocity path's correspondence is decided by plan_gram (correspond.hip): the
 tiles with two k-groups up to 512 tokens, 64 x 64 beyond), the same from the fp16 hi / lo split in the 16-bit modes from 1024
 tokens (64 x 64 below 256 tiles of 128 x 128 over all pairs, 128 x 128 from there), and for binned descriptors the raw token
 Gram with the 3 x 3 stencil arg-max.  Each case below names the plan it expects and asserts it through vitvs_op_gram_plan, then
-runs the stage through vitvs_op_gram_argmax / vitvs_op_gram_stencil: the launches the velocity path makes.  The reference is an
+runs the stage through vitvs_op_gram_argmax / vitvs_op_gram_stencil, which launch the steps of that plan through launch_gram_step
+(correspond.hip) as the velocity path does: the same launches by construction.  The reference is an
 fp64 Gram of the same normalised descriptors (for the stencil: of the concatenated 9 D-wide descriptors).  Bars:
   * every device arg-max is a row (nn_1) or column (nn_2) maximum to within 1e-6;
   * sim_1 is within 2e-6 of the row maximum;

@@ -103,6 +103,10 @@ struct vitvs_handle {
     // activations
     void *Ape = nullptr, *xn = nullptr, *qkv = nullptr, *attn = nullptr, *hid = nullptr;
     float *x = nullptr, *dn = nullptr, *sq = nullptr, *part = nullptr;  // part: split-K partial sums [8][M][D]
+    // The correspondence stage at max_pairs pairs (plan_gram): dh and gram_ws are its workspaces, and the forward and the law read
+    // `emit` and `refine_from_gram` from it — form and split, and all that follows from them, do not depend on the pairs of a
+    // call; only the tile does, which is why enqueue_update plans the call's own launches.
+    GramPlan gram;
     unsigned short* dh = nullptr;   // fp16 hi / lo split of dn for the many-token Gram of the 16-bit modes (null: fp32 Gram)
     float* gram_ws = nullptr;       // binned descriptors: raw token Gram [max_pairs][T][T] for the stencil form (correspond.hip; null: the 9 D-wide Gram)
     AttnWorkspace attn_ws;    // key-split states / tickets of the long-sequence attention, sized for every image count <= n_img_max
@@ -329,13 +333,16 @@ const char* const kClassNames[KC_COUNT] = {"patchify", "patch_embed", "layernorm
                                            "fc1", "fc2", "descriptors", "gram_argmax", "servo",
                                            "residual_ln", "gram_stencil"};
 
+// the class each step of the correspondence stage is timed in, by GramStep; the split of the descriptors is not timed (-1)
+const int kGramStepClass[] = {KC_DESCRIPTORS, -1, KC_GRAM, KC_GRAM, KC_GRAM_STENCIL};
+
 // When timing is enabled, arms the launch helper (kernels.h) so that the next kernel launched inside the span
 // is dispatched with an event pair stamped with its own begin / end times.
 struct Span {
     vitvs_handle* h;
     bool armed = false;
     Span(vitvs_handle* h_, int cls, hipStream_t) : h(h_) {
-        if (!h->timing) return;
+        if (!h->timing || cls < 0) return;
         if (h->ev_used + 2 > h->ev_pool.size()) {
             hipEvent_t a = nullptr, b = nullptr;
             if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
@@ -363,10 +370,6 @@ static size_t frame_bytes(const vitvs_handle* h) {
 }
 
 // One launch chain's view of the workspaces (a contiguous range of images).
-// Plain descriptors of the default forward are produced by the forward's own last launch.
-// (binned descriptors in their stencil form need only the tokens' squared norms: the same launch writes those instead)
-static bool desc_in_forward(const vitvs_handle* h) { return h->cfg.binned ? h->gram_ws != nullptr : h->Dp == h->cfg.dim; }
-
 struct ChainCtx {
     int cnt = 0, M = 0;
     float* x = nullptr;
@@ -374,7 +377,7 @@ struct ChainCtx {
     float* part = nullptr;
     PatchifyArgs pa;
     const ResizeArgs* rs = nullptr;   // camera-resolution frames (vitvs_set_frame_size): resize inside the patch-row build
-    bool want_desc = false;   // the last residual_ln also writes the plain descriptors (launch_residual_ln)
+    bool want_desc = false;   // the last residual_ln also writes what the Gram plan asks of it (GramEmit; launch_residual_ln)
     DescOut desc;
     struct { LinearPlan embed, qkv, proj, fc1, fc2; AttnPlan attn; } plan;   // of the chain's six launch shapes (forward_chain)
 };
@@ -466,9 +469,9 @@ int forward_chain(vitvs_handle* h, int i0, int cnt, int n_des, const uint8_t* de
     cx.plan.fc1 = plan_linear(p, cx.M, h->hidden, D, EPI_STORE);
     cx.plan.fc2 = plan_linear(p, cx.M, D, h->hidden, EPI_PARTIAL);
     cx.plan.attn = plan_attention(p, cnt, h->N, h->cfg.heads);
-    if (h->desc_keys >= 0 && desc_in_forward(h)) {
+    if (h->desc_keys >= 0 && h->gram.emit != EMIT_NONE) {
         cx.want_desc = true;
-        if (h->cfg.binned) cx.desc.sq = h->sq + (size_t)i0 * h->T;
+        if (h->gram.emit == EMIT_SQ) cx.desc.sq = h->sq + (size_t)i0 * h->T;
         else cx.desc.dn = h->dn + (size_t)i0 * h->T * h->Dp;
         cx.desc.zero_a = h->row_best; cx.desc.zero_b = h->col_best;
         cx.desc.T = h->T;
@@ -530,7 +533,7 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
         a.pitch_in = scale; a.off_out = h->off_ws; a.off_in = rf.table;
         if (rf.from_forward) {
             a.des_shared = rf.des_shared;
-            if (h->gram_ws) { a.G = h->gram_ws; a.sq = h->sq; }
+            if (h->gram.refine_from_gram) { a.G = h->gram_ws; a.sq = h->sq; }
             else { a.dn = h->dn; a.Dp = h->Dp; }
         }
     }
@@ -693,9 +696,9 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     if (!rc) rc = dev_alloc(h, &h->dn, h->dn_elems);
     // the workspaces of the Gram stage (correspond.hip plan_gram): the raw token Gram [max_pairs][T][T] of the stencil form, the
     // fp16 hi / lo split of every frame's descriptors
-    const GramPlan gp = plan_gram(h->prec, cfg->binned != 0, h->T, cfg->dim, cfg->max_pairs, cfg->max_pairs);
-    if (!rc && gp.form == GRAM_STENCIL) rc = dev_alloc(h, &h->gram_ws, (size_t)cfg->max_pairs * h->T * h->T);
-    if (!rc && gp.split) rc = dev_alloc(h, &h->dh, gram_split_elems(h->n_img_max, h->T, h->Dp));
+    h->gram = plan_gram(h->prec, cfg->binned != 0, h->T, cfg->dim, cfg->max_pairs, cfg->max_pairs);
+    if (!rc && h->gram.gram_floats) rc = dev_alloc(h, &h->gram_ws, h->gram.gram_floats);
+    if (!rc && h->gram.split_elems) rc = dev_alloc(h, &h->dh, h->gram.split_elems);
     if (!rc) rc = dev_alloc(h, &h->sq, (size_t)h->n_img_max * h->T);
 
     h->best_elems = (size_t)cfg->max_pairs * h->T;
@@ -1059,9 +1062,12 @@ int vitvs_correspond_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* de
     if (rc) return set_err(h, rc, "normalise launch failed");
     VITVS_HIP_CHECK(hipMemsetAsync(h->row_best, 0, (size_t)T * 8, st));
     VITVS_HIP_CHECK(hipMemsetAsync(h->col_best, 0, (size_t)T * 8, st));
-    rc = launch_gram_argmax(h->dn, T, Dp, 1, 0, h->row_best, h->col_best, st);
+    const GramPlan gp = plan_gram(PREC_F32, false, T, Dp, 1, 1);   // caller's descriptors: the exact fp32 Gram in every precision
+    GramOperands go;
+    go.dn = h->dn; go.row_best = h->row_best; go.col_best = h->col_best;
+    rc = launch_gram(gp, go, st);
     if (!rc) rc = launch_decode_best(h->row_best, h->col_best, T, nn_1, nn_2, sim_1, st);
-    if (!rc && S_out) rc = launch_gram_dense(h->dn, T, Dp, 1, 0, S_out, st);
+    if (!rc && S_out) rc = launch_gram_dense(gp, h->dn, (long)T * Dp, Dp, 0, S_out, st);
     if (rc) return set_err(h, rc, "correspondence launch failed");
     return 0;
 }
@@ -1152,36 +1158,18 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
                      : forward_chain(h, n_des, u.n_pairs, n_des, nullptr, u.I_cur, h->part, st);
     h->desc_keys = -1;
     if (rc) return rc;
+    // the forward's last launch wrote what the plan asked of it (GramEmit) and cleared the arg-max keys
     const GramPlan gp = plan_gram(h->prec, h->cfg.binned != 0, h->T, h->cfg.dim, u.n_pairs, h->cfg.max_pairs);
-    if (gp.form == GRAM_STENCIL) {
-        // binned descriptors as a stencil over the raw token Gram: nothing 9 D wide is built or read (correspond.hip header)
-        // (the tokens' squared norms came out of the forward's last launch, which also cleared the arg-max keys)
-        { Span sp(h, KC_GRAM, st);
-          rc = launch_gram_raw_tokens(h->x, h->T, 1 + h->R, h->cfg.dim, u.n_pairs, u.des_shared ? 1 : 0, h->gram_ws, st); }
-        if (rc) return set_err(h, rc, "gram launch failed");
-        { Span sp(h, KC_GRAM_STENCIL, st);
-          rc = launch_gram_stencil_argmax(h->gram_ws, h->sq, h->T, h->grid, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st); }
-        if (rc) return set_err(h, rc, "gram stencil launch failed");
-        late_inputs(u);
-        return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st, rf);
+    GramOperands go;
+    go.x = h->x; go.P = 1 + h->R; go.dn = h->dn; go.dh = h->dh; go.G = h->gram_ws; go.sq = h->sq; go.grid = h->grid;
+    go.des_shared = rf.des_shared; go.row_best = h->row_best; go.col_best = h->col_best;
+    for (int i = 0; i < gp.n_steps && !rc; ++i) {
+        Span sp(h, kGramStepClass[gp.steps[i]], st);
+        rc = launch_gram_step(gp, i, go, st);
     }
-    if (!desc_in_forward(h)) {
-        Span sp(h, KC_DESCRIPTORS, st);
-        rc = launch_descriptors(h->x, h->dn, nullptr, h->sq, n_img, h->T, 1 + h->R, h->grid, h->cfg.dim, h->cfg.binned,
-                                h->row_best, h->col_best, u.n_pairs * h->T, st);
-        if (rc) return set_err(h, rc, "descriptor launch failed");
-    }
-    if (gp.split) {
-        rc = launch_split_desc(h->dn, h->dh, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, st);
-        if (rc) return set_err(h, rc, "descriptor split launch failed");
-    }
-    { Span sp(h, KC_GRAM, st);
-      rc = gp.split ? launch_gram_argmax_split(h->dh, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st)
-                 : launch_gram_argmax(h->dn, h->T, h->Dp, u.n_pairs, u.des_shared ? 1 : 0, h->row_best, h->col_best, st); }
-    if (rc) return set_err(h, rc, "gram launch failed");
+    if (rc) return set_err(h, rc, "correspondence launch failed");
     late_inputs(u);
-    return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c,
-                     u.status, st, rf);
+    return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st, rf);
 }
 
 // VITVS_GRAPH=1: the update is captured once per argument tuple and replayed.  The selection array is the one argument
@@ -1658,9 +1646,9 @@ int vitvs_op_gram_argmax(int32_t precision, const float* dn, int32_t T, int32_t 
     unsigned long long *rb = reinterpret_cast<unsigned long long*>(row_best), *cb = reinterpret_cast<unsigned long long*>(col_best);
     VITVS_HIP_CHECK(hipMemsetAsync(rb, 0, (size_t)n_pairs * T * 8, st));
     VITVS_HIP_CHECK(hipMemsetAsync(cb, 0, (size_t)n_pairs * T * 8, st));
-    int rc = pl.split ? launch_split_desc(dn, dh, T, Dp, n_pairs, des_shared, st) : 0;
-    if (!rc) rc = pl.split ? launch_gram_argmax_split(dh, T, Dp, n_pairs, des_shared, rb, cb, st)
-                           : launch_gram_argmax(dn, T, Dp, n_pairs, des_shared, rb, cb, st);
+    GramOperands go;                            // (dn is written only by the descriptor step of a binned plan)
+    go.dn = const_cast<float*>(dn); go.dh = dh; go.des_shared = des_shared; go.row_best = rb; go.col_best = cb;
+    const int rc = launch_gram(pl, go, st);
     return rc ? rc : decode_pairs(rb, cb, T, n_pairs, nn_1, nn_2, sim_1, st);
 }
 int vitvs_op_gram_stencil(const float* x, int32_t T, int32_t P, int32_t D, int32_t grid, int32_t n_pairs, int32_t des_shared,
@@ -1675,8 +1663,9 @@ int vitvs_op_gram_stencil(const float* x, int32_t T, int32_t P, int32_t D, int32
     const int n_frames = (des_shared ? 1 : n_pairs) + n_pairs;
     // the tokens' squared norms; the same launch clears the keys (what the forward's last launch does on the velocity path)
     int rc = launch_descriptors(x, nullptr, nullptr, sq, n_frames, T, P, grid, D, 1, rb, cb, n_pairs * T, st);
-    if (!rc) rc = launch_gram_raw_tokens(x, T, P, D, n_pairs, des_shared, G, st);
-    if (!rc) rc = launch_gram_stencil_argmax(G, sq, T, grid, n_pairs, des_shared, rb, cb, st);
+    GramOperands go;
+    go.x = x; go.P = P; go.G = G; go.sq = sq; go.grid = grid; go.des_shared = des_shared; go.row_best = rb; go.col_best = cb;
+    if (!rc) rc = launch_gram(pl, go, st);
     return rc ? rc : decode_pairs(rb, cb, T, n_pairs, nn_1, nn_2, sim_1, st);
 }
 int vitvs_op_touch(const void* p, int64_t bytes, int32_t share_xcds, void* stream) {

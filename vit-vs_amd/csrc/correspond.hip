@@ -22,6 +22,10 @@
 // T x T workspace, then gram_stencil_argmax_kernel (nine L2-resident reads per similarity).  DINOv2 ViT-S/14 308² (484 tokens,
 // 9 x 384 = 3456): 30 us + 5 us of descriptor building -> see profiles/r04_notes.md.  extract_descriptors(bin=True) still
 // returns the concatenated descriptors (elementwise.hip desc_binned_kernel); vitvs_correspond_dev takes whatever rows it is given.
+//
+// One path from decision to launch: plan_gram picks the form, the tile and the steps of the stage (GramPlan, kernels.h), and
+// launch_gram_step launches step i of a plan exactly as planned — for the velocity path, vitvs_correspond_dev and the operator
+// hooks alike.  Nothing below plans again, and one table (with_tile) maps (operand type, tile) to the kernel instantiation.
 #include <algorithm>
 
 #include "gemm_core.h"
@@ -329,12 +333,20 @@ __global__ __launch_bounds__(256) void split_desc_kernel(const float* __restrict
     *reinterpret_cast<f16x8*>(dst + 2 * Dp) = desired ? lo : hi;
 }
 
-size_t gram_split_elems(int n_frames, int T, int Dp) { return (size_t)n_frames * T * 3 * Dp; }
-
-GramPlan plan_gram_tiles(bool split, int T, int Dp, int n_pairs) {
+// One Gram launch over T tokens, rows Dp wide, n_pairs pairs, on fp32 operands or the split, and the steps of `form` around it.
+static GramPlan plan_gram_tiles(bool split, int T, int Dp, int n_pairs, GramForm form) {
     GramPlan pl;
+    pl.form = form;
     pl.split = split;
+    const bool stencil = form == GRAM_STENCIL, wide = form == GRAM_WIDE;
+    pl.emit = stencil ? EMIT_SQ : wide ? EMIT_NONE : EMIT_DN;
+    pl.refine_from_gram = stencil;
+    if (wide) pl.steps[pl.n_steps++] = GSTEP_DESCRIPTORS;
+    if (split) pl.steps[pl.n_steps++] = GSTEP_SPLIT;
+    pl.steps[pl.n_steps++] = stencil ? GSTEP_RAW_GRAM : GSTEP_ARGMAX;
+    if (stencil) pl.steps[pl.n_steps++] = GSTEP_STENCIL;
     if (T <= 0 || n_pairs <= 0 || Dp % (split ? 64 : 32) != 0) return pl;
+    pl.T = T; pl.Dp = Dp; pl.n_pairs = n_pairs;
     if (split) {
         const long t128 = (long)((T + 127) / 128) * ((T + 127) / 128) * n_pairs;
         // enough 128 x 128 tiles for every CU (3136 tokens: 625); 1369 tokens: 121 tiles of 128 x 128, 484 of 64 x 64
@@ -355,98 +367,88 @@ GramPlan plan_gram(Precision p, bool binned, int T, int D, int n_pairs, int max_
     if (T <= 0 || D <= 0 || n_pairs <= 0 || max_pairs < n_pairs) return GramPlan{};
     // binned descriptors: the 9 D-wide Gram as a 3 x 3 stencil over the raw token Gram (header), which needs T x T floats per
     // pair (3136 tokens: 39 MB); beyond 8 GiB in all the handle keeps the concatenated form
-    if (binned && (size_t)max_pairs * T * T * 4 <= (8ull << 30)) {
-        GramPlan pl = plan_gram_tiles(false, T, D, n_pairs);
-        pl.form = GRAM_STENCIL;
+    const size_t gram_floats = (size_t)max_pairs * T * T;
+    if (binned && gram_floats * 4 <= (8ull << 30)) {
+        GramPlan pl = plan_gram_tiles(false, T, D, n_pairs, GRAM_STENCIL);
+        pl.gram_floats = gram_floats;
         return pl;
     }
     // 16-bit modes, >= 1024 tokens: the Gram runs on the f16 matrix cores from a hi / lo split of the descriptors of all the
     // handle's frames (32-bit operand offsets)
     const int Dp = binned ? 9 * D : D;
-    const bool split = plain16(p) && T >= 1024 && Dp % 64 == 0 && gram_split_elems(2 * max_pairs, T, Dp) * 2 < (1ull << 32);
-    GramPlan pl = plan_gram_tiles(split, T, Dp, n_pairs);
-    pl.form = binned ? GRAM_WIDE : split ? GRAM_SPLIT : GRAM_F32;
+    const size_t split_elems = (size_t)2 * max_pairs * T * 3 * Dp;
+    const bool split = plain16(p) && T >= 1024 && Dp % 64 == 0 && split_elems * 2 < (1ull << 32);
+    GramPlan pl = plan_gram_tiles(split, T, Dp, n_pairs, binned ? GRAM_WIDE : split ? GRAM_SPLIT : GRAM_F32);
+    if (split) pl.split_elems = split_elems;
     return pl;
 }
 
-int launch_split_desc(const float* dn, void* dh, int T, int Dp, int n_pairs, int des_shared, hipStream_t stream) {
-    if (T <= 0 || n_pairs <= 0 || (Dp % 64) != 0 || !dh) return -2;
-    const int n_des = des_shared ? 1 : n_pairs, n_frames = n_des + n_pairs;
-    if ((long)n_frames * T * 3 * Dp * 2 >= (1l << 32)) return -2;  // 32-bit operand offsets in the main loop
-    const long chunks = (long)n_frames * T * (Dp >> 3), des_chunks = (long)n_des * T * (Dp >> 3);
-    launch(split_desc_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, dn, (f16*)dh, Dp, chunks, des_chunks);
+// The one table of Gram tiles: (operand type, tile of the plan) -> the template arguments of its kernel
+template <typename E, int BM, int BN, int KG>
+struct TileTag { using elem = E; static constexpr int bm = BM, bn = BN, kg = KG; };
+template <typename F>
+static int with_tile(const GramPlan& pl, F f) {
+    if (pl.split) return pl.rows == 128 ? f(TileTag<f16, 128, 128, 1>{}) : f(TileTag<f16, 64, 64, 1>{});
+    return pl.rows == 32 ? f(TileTag<float, 32, 32, 2>{}) : f(TileTag<float, 64, 64, 1>{});
+}
+// and the launch of that kernel over the plan's tiles; the f16 instantiations opt in to their dynamic LDS
+template <typename Tag, typename K, typename... Args>
+static int launch_tiles(K kernel, const GramPlan& pl, hipStream_t stream, Args... args) {
+    using Tile = GemmTile<Tag::bm, Tag::bn, Tag::kg>;
+    if constexpr (sizeof(typename Tag::elem) == 2) {
+        static std::atomic<unsigned long long> raised{0};
+        if (raise_lds_limit(reinterpret_cast<const void*>(kernel), Tile::LDS_BYTES, raised)) return -1;
+    }
+    launch(kernel, dim3(8 * pl.per_xcd, 1, pl.n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, args..., pl.hb);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_gram_argmax_split(const void* dh, int T, int Dp, int n_pairs, int des_shared, unsigned long long* row_best,
-                             unsigned long long* col_best, hipStream_t stream) {
-    const GramPlan pl = plan_gram_tiles(true, T, Dp, n_pairs);
-    if (!pl.rows || !dh) return -2;
-    if (pl.rows == 128) {
-        using Tile = GemmTile<128, 128, 1>;
-        static std::atomic<unsigned long long> raised{0};
-        if (raise_lds_limit(reinterpret_cast<const void*>(&gram_argmax_kernel<f16, 128, 128, 1>), Tile::LDS_BYTES, raised)) return -1;
-        launch((gram_argmax_kernel<f16, 128, 128, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh,
-               T, 3 * Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
-    } else {
-        using Tile = GemmTile<64, 64, 1>;
-        static std::atomic<unsigned long long> raised{0};
-        if (raise_lds_limit(reinterpret_cast<const void*>(&gram_argmax_kernel<f16, 64, 64, 1>), Tile::LDS_BYTES, raised)) return -1;
-        launch((gram_argmax_kernel<f16, 64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), Tile::LDS_BYTES, stream, (const f16*)dh,
-               T, 3 * Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
+int launch_gram_step(const GramPlan& pl, int i, const GramOperands& o, hipStream_t stream) {
+    if (!pl.rows || i < 0 || i >= pl.n_steps) return -2;
+    const int T = pl.T, Dp = pl.Dp, n_des = o.des_shared ? 1 : pl.n_pairs;
+    switch (pl.steps[i]) {
+    case GSTEP_DESCRIPTORS:
+        return launch_descriptors(o.x, o.dn, nullptr, o.sq, n_des + pl.n_pairs, T, o.P, o.grid, Dp / 9, 1, o.row_best, o.col_best,
+                                  pl.n_pairs * T, stream);
+    case GSTEP_SPLIT: {     // (plan_gram keeps dh under the 4 GiB of the main loop's 32-bit operand offsets)
+        if (!o.dn || !o.dh) return -2;
+        const long chunks = (long)(n_des + pl.n_pairs) * T * (Dp >> 3), des_chunks = (long)n_des * T * (Dp >> 3);
+        launch(split_desc_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, o.dn, (f16*)o.dh, Dp, chunks, des_chunks);
+        break;
+    }
+    case GSTEP_ARGMAX: {
+        const void* rows = pl.split ? o.dh : o.dn;
+        if (!rows) return -2;
+        return with_tile(pl, [&](auto tag) {
+            using Tag = decltype(tag);
+            using E = typename Tag::elem;
+            return launch_tiles<Tag>(gram_argmax_kernel<E, Tag::bm, Tag::bn, Tag::kg>, pl, stream, static_cast<const E*>(rows), T,
+                                     pl.split ? 3 * Dp : Dp, pl.n_pairs, o.des_shared, o.row_best, o.col_best);
+        });
+    }
+    case GSTEP_RAW_GRAM:    // the cls and register rows of x are skipped by the base and the image stride
+        if (o.P < 1) return -2;
+        return launch_gram_dense(pl, o.x + (size_t)o.P * Dp, (long)(T + o.P) * Dp, Dp, o.des_shared, o.G, stream);
+    case GSTEP_STENCIL:
+        if (o.grid * o.grid != T) return -2;
+        launch(gram_stencil_argmax_kernel, dim3((T + 31) / 32, (T + 31) / 32, pl.n_pairs), dim3(256), 0, stream, o.G, o.sq, T, o.grid,
+               pl.n_pairs, o.des_shared, o.row_best, o.col_best);
+        break;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_gram_argmax(const float* dn, int T, int Dp, int n_pairs, int des_shared, unsigned long long* row_best,
-                       unsigned long long* col_best, hipStream_t stream) {
-    const GramPlan pl = plan_gram_tiles(false, T, Dp, n_pairs);
-    if (!pl.rows) return -2;
-    if (pl.rows == 32) {
-        using Tile = GemmTile<32, 32, 2>;
-        launch((gram_argmax_kernel<float, 32, 32, 2>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, dn,
-               T, Dp, n_pairs, des_shared, row_best, col_best, pl.hb);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    constexpr int lds = GemmTile<64, 64, 1>::LDS_BYTES;
-    launch((gram_argmax_kernel<float, 64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), lds, stream, dn, T, Dp, n_pairs,
-           des_shared, row_best, col_best, pl.hb);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-static int launch_gram_dense_strided(const float* src, long img_stride, int ld, int T, int Dp, int n_pairs, int des_shared, float* S,
-                                     hipStream_t stream) {
-    const GramPlan pl = plan_gram_tiles(false, T, Dp, n_pairs);
-    if (!pl.rows) return -2;
+int launch_gram_dense(const GramPlan& pl, const float* src, long img_stride, int ld, int des_shared, float* S, hipStream_t stream) {
     // 32-bit byte offsets in the main loop: every row the launch touches lies within 4 GiB of its image's first row
-    if ((long long)T * ld * 4 >= (1ll << 32)) return -2;
-    if (pl.rows == 32) {
-        using Tile = GemmTile<32, 32, 2>;
-        launch((gram_dense_kernel<32, 32, 2>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(Tile::THREADS), Tile::LDS_BYTES, stream, src,
-               img_stride, ld, T, Dp, n_pairs, des_shared, S, pl.hb);
-    } else {
-        constexpr int lds = GemmTile<64, 64, 1>::LDS_BYTES;
-        launch((gram_dense_kernel<64, 64, 1>), dim3(8 * pl.per_xcd, 1, n_pairs), dim3(256), lds, stream, src, img_stride, ld, T, Dp,
-               n_pairs, des_shared, S, pl.hb);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_gram_dense(const float* dn, int T, int Dp, int n_pairs, int des_shared, float* S, hipStream_t stream) {
-    return launch_gram_dense_strided(dn, (long)T * Dp, Dp, T, Dp, n_pairs, des_shared, S, stream);
-}
-
-int launch_gram_raw_tokens(const float* x, int T, int P, int D, int n_pairs, int des_shared, float* G, hipStream_t stream) {
-    if (P < 1) return -2;
-    return launch_gram_dense_strided(x + (size_t)P * D, (long)(T + P) * D, D, T, D, n_pairs, des_shared, G, stream);
-}
-
-int launch_gram_stencil_argmax(const float* G, const float* sq, int T, int grid, int n_pairs, int des_shared,
-                               unsigned long long* row_best, unsigned long long* col_best, hipStream_t stream) {
-    if (T <= 0 || n_pairs <= 0 || grid * grid != T) return -2;
-    launch(gram_stencil_argmax_kernel, dim3((T + 31) / 32, (T + 31) / 32, n_pairs), dim3(256), 0, stream, G, sq, T, grid, n_pairs,
-           des_shared, row_best, col_best);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (!pl.rows || (long long)pl.T * ld * 4 >= (1ll << 32)) return -2;
+    return with_tile(pl, [&](auto tag) {
+        using Tag = decltype(tag);
+        if constexpr (sizeof(typename Tag::elem) == 4)
+            return launch_tiles<Tag>(gram_dense_kernel<Tag::bm, Tag::bn, Tag::kg>, pl, stream, src, img_stride, ld, pl.T, pl.Dp,
+                                     pl.n_pairs, des_shared, S);
+        else
+            return -2;          // no dense form of the split
+    });
 }
 
 }  // namespace vitvs

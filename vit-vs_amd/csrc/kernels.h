@@ -207,42 +207,65 @@ int launch_attention(const AttnPlan& plan, const void* qkv, void* out, hipStream
                      bool q_prescaled = false);
 
 // ---- correspond.hip ------------------------------------------------------------------------
-// The Gram stage of a velocity update, decided once by plan_gram (the codes are ABI: vitvs_op_gram_plan):
+// The correspondence stage of a velocity update — from the forward's last launch to the packed arg-max keys the law reads —
+// decided once by plan_gram and launched from that plan by launch_gram_step, by the product and by the operator hooks alike.
+// The forms (the codes are ABI: vitvs_op_gram_plan):
 //   GRAM_F32      fused Gram + row / column arg-max over the fp32 descriptors (gram_argmax_kernel<float>)
 //   GRAM_SPLIT    the same on the f16 matrix cores from a hi / lo split of the descriptors (16-bit modes from 1024 tokens)
 //   GRAM_STENCIL  binned descriptors: raw token Gram into the handle's T x T workspace, then the 3 x 3 stencil arg-max
 //   GRAM_WIDE     binned descriptors whose raw Gram workspace would pass 8 GiB: the 9 D-wide descriptors through the fused
 //                 arg-max, split as GRAM_SPLIT is
 enum GramForm : int { GRAM_NONE = 0, GRAM_F32, GRAM_SPLIT, GRAM_STENCIL, GRAM_WIDE };
+// The launches of a form, in order (GramPlan::steps):
+//   GSTEP_DESCRIPTORS  x -> the 9 D-wide normalised descriptors dn; clears the keys (GRAM_WIDE; launch_descriptors)
+//   GSTEP_SPLIT        dn -> the fp16 hi / lo rows dh (a split plan)
+//   GSTEP_ARGMAX       dn or dh -> keys: for pair b, S = dn[a_img(b)] . dn[b_img(b)]^T (T x T) and its row / column arg-max
+//   GSTEP_RAW_GRAM     x -> G[b][i][j] = raw dot products of the patch tokens (GRAM_STENCIL: binned descriptors without building them)
+//   GSTEP_STENCIL      G, sq -> keys: the 3 x 3 "diagonal" stencil over G, normalised by the binned descriptors' norms, and its arg-max
+enum GramStep : int { GSTEP_DESCRIPTORS = 0, GSTEP_SPLIT, GSTEP_ARGMAX, GSTEP_RAW_GRAM, GSTEP_STENCIL };
+// What the forward's last launch writes for the stage (DescOut) while it clears the keys: the normalised descriptors, the tokens'
+// squared norms, or nothing at all (GSTEP_DESCRIPTORS follows and clears the keys itself).
+enum GramEmit : int { EMIT_NONE = 0, EMIT_DN, EMIT_SQ };
 struct GramPlan {
     GramForm form = GRAM_NONE;
-    bool split = false;                   // the Gram's operands are the fp16 hi / lo split (launch_split_desc into `dh` first)
+    bool split = false;                   // the Gram's operands are the fp16 hi / lo split (GSTEP_SPLIT into `dh` first)
     int rows = 0, cols = 0, kgroups = 0;  // tile of the Gram kernel (GRAM_STENCIL: of the raw Gram); rows = 0: unlaunchable
     int hb = 0, per_xcd = 0;              // band rows and workgroups per XCD of the tile order (gram_tile)
+    int T = 0, Dp = 0, n_pairs = 0;       // tokens, width of the Gram's rows (GRAM_STENCIL: the model width D), pairs of the call
+    GramStep steps[3] = {};               // the launches of the form, in order
+    int n_steps = 0;
+    GramEmit emit = EMIT_NONE;
+    bool refine_from_gram = false;        // the sub-patch refinement reads G and sq (ServoArgs), else dn
+    // workspaces at the handle's max_pairs (plan_gram only): G in floats; dh in fp16 elements, under 4 GiB (32-bit operand offsets)
+    size_t gram_floats = 0, split_elems = 0;
 };
-// The tile of one Gram launch over T tokens, rows Dp wide, n_pairs pairs: fp32 operands or the split.
-GramPlan plan_gram_tiles(bool split, int T, int Dp, int n_pairs);
-// The Gram stage of a handle (precision, binned descriptors, tokens, model width D, max_pairs) for a call of n_pairs pairs.
-// vitvs_create_ex allocates the workspaces of the plan at n_pairs = max_pairs.
+// The stage of a handle (precision, binned descriptors, tokens, model width D, max_pairs) for a call of n_pairs pairs.
 GramPlan plan_gram(Precision p, bool binned, int T, int D, int n_pairs, int max_pairs);
-// For pair b: S = dn[a_img(b)] . dn[b_img(b)]^T (T x T, fp32); row_best[b][i] / col_best[b][j] receive
-// the packed (max similarity, first index) keys (common.h pack_best).  Buffers must be zeroed first.
-int launch_gram_argmax(const float* dn, int T, int Dp, int n_pairs, int des_shared,
-                       unsigned long long* row_best, unsigned long long* col_best, hipStream_t stream);
-// Optional dense similarity matrix (tests / debugging): S[b][i][j].
-// 16-bit modes from 1024 tokens on: hi / lo fp16 split of the descriptors into `dh` (gram_split_elems fp16 elements), then the
-// Gram on the f16 matrix cores (correspond.hip)
-size_t gram_split_elems(int n_frames, int T, int Dp);
-int launch_split_desc(const float* dn, void* dh, int T, int Dp, int n_pairs, int des_shared, hipStream_t stream);
-int launch_gram_argmax_split(const void* dh, int T, int Dp, int n_pairs, int des_shared, unsigned long long* row_best,
-                             unsigned long long* col_best, hipStream_t stream);
-int launch_gram_dense(const float* dn, int T, int Dp, int n_pairs, int des_shared, float* S, hipStream_t stream);
-// Binned descriptors without building them (correspond.hip header): G[b][i][j] = raw dot products of the patch tokens in the
-// residual stream x ([frames][P + T][D] fp32, desired frames first), then the 3 x 3 "diagonal" stencil over G, normalised by the
-// binned descriptors' norms (sq = |t|^2 per token: DescOut::sq of the forward's last launch), with the fused arg-max into row_best / col_best.
-int launch_gram_raw_tokens(const float* x, int T, int P, int D, int n_pairs, int des_shared, float* G, hipStream_t stream);
-int launch_gram_stencil_argmax(const float* G, const float* sq, int T, int grid, int n_pairs, int des_shared,
-                               unsigned long long* row_best, unsigned long long* col_best, hipStream_t stream);
+// What the steps read and write.  Frames are in the call's order, desired first (one desired frame when des_shared).
+//   x        residual stream [frames][P + T][D] fp32, P = prefix rows of each image: cls + register tokens
+//   dn, dh   normalised descriptors [frames][T][Dp] fp32 and their split [frames][T][3 Dp] fp16
+//   G, sq    raw token Gram [n_pairs][T][T]; |t|^2 per token [frames][T]: DescOut::sq of the forward's last launch
+//   grid     tokens per side
+//   row_best, col_best   packed (max similarity, first index) keys [n_pairs][T] (common.h pack_best); zero before the arg-max
+struct GramOperands {
+    const float* x = nullptr;
+    int P = 1, grid = 0, des_shared = 0;
+    float *dn = nullptr, *G = nullptr, *sq = nullptr;
+    void* dh = nullptr;
+    unsigned long long *row_best = nullptr, *col_best = nullptr;
+};
+// Launches step i of the plan as planned.  -2: not a launchable plan or step, or operands the step cannot take (no dh, grid *
+// grid != T, P < 1, rows beyond the 32-bit offsets of the main loop).
+int launch_gram_step(const GramPlan& plan, int i, const GramOperands& o, hipStream_t stream);
+// The whole stage.  (The product loops over the steps itself, to time each in its class: api.hip enqueue_update.)
+inline int launch_gram(const GramPlan& plan, const GramOperands& o, hipStream_t stream) {
+    int rc = plan.rows ? 0 : -2;
+    for (int i = 0; i < plan.n_steps && !rc; ++i) rc = launch_gram_step(plan, i, o, stream);
+    return rc;
+}
+// The Gram itself, in the tile of an unsplit plan: S[b][i][j] over fp32 rows `ld` apart of images `img_stride` apart (descriptors:
+// T * Dp, Dp).  GSTEP_RAW_GRAM, and vitvs_correspond_dev's optional dense similarity matrix.
+int launch_gram_dense(const GramPlan& plan, const float* src, long img_stride, int ld, int des_shared, float* S, hipStream_t stream);
 // Sub-patch offsets (refine.h) of every token of one pair: d1, d2 fp32 normalised rows [T][Dp] (Dp a multiple of 4), nn1 [T]
 // -> offsets [T][2] = (dr, dc); matches outside 0 .. T - 1 get (0, 0).  One wave per token.
 int launch_refine(const float* d1, const float* d2, const int32_t* nn1, int T, int grid, int Dp, float* offsets, hipStream_t stream);
