@@ -272,6 +272,23 @@ VITVS_API int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w);
  * moved matches.  Synchronising, always read from the device.  Replaces nothing (vitvs_v2.py:511-513: patch centres). */
 VITVS_API int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets);
 
+/* --- the goal depth (option "interaction", below) ------------------------------------------------
+ * Z_des_mm uint16 [n_goal][v_max][u_max], the depth image(s) taken at the goal pose, in the sensor's millimetres (device memory
+ * for _dev, host memory for the other form, which may synchronise).  One launch reduces them to what the law reads: per goal
+ * image the depth at every token's patch centre (the pixel of the goal feature s*, vitvs_v2.py:511-513, 544-549) and at pixel
+ * (0, 0), the goal pixel of a zero-padded row; 0 or outside the image means 100 m, as for the current depth (:566-586).  The
+ * table lives in the handle, allocated by the first call; later calls with the same n_goal rewrite it in place, in stream
+ * order, and captured graphs stay valid; a call that changes n_goal (the first, a clear with n_goal = 0, another count) drains
+ * the device and drops the handle's graphs.  A velocity call of n_pairs pairs reads image b for pair b when n_goal == n_pairs,
+ * image 0 for every pair when n_goal == 1, and is error -5 otherwise.  Independent of vitvs_set_goal's token cache; no other
+ * call drops it.  Replaces nothing: the reference evaluates L at the current features only (vitvs_v2.py:650-659).
+ * Returns 0, -1 (null), -3 (n_goal outside 0 .. max_pairs). */
+VITVS_API int vitvs_set_goal_depth_dev(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_mm, void* stream);
+VITVS_API int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_mm);
+/* Z* of every feature row of the last law evaluation, in metres: z double [n_pairs][max_rows]; 0 from n_feature_rows on, and
+ * everywhere with option "interaction" at 0.  Synchronising, always read from the device. */
+VITVS_API int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several
@@ -310,6 +327,19 @@ VITVS_API int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offset
  *                          centre.  Applies to every entry point that evaluates the law from the handle's own forward
  *                          (vitvs_compute_velocity[_dev], vitvs_reselect), composes with "robust_law", and drops the handle's
  *                          captured graphs when changed.  vitvs_last_offsets returns the offsets.
+ *   "interaction"  0 / 1 / 2  which interaction matrix the law inverts; 1 and 2 are extensions beyond the reference (ViSP's DESIRED
+ *                          and MEAN).  With rows(x, y, Z) the two rows of vitvs_v2.py:650-659, (x, y) / (xs, ys) the normalised
+ *                          current / goal point of a feature pair, Z the current depth at (u, v) and Z* the goal depth at
+ *                          (u*, v*) (vitvs_set_goal_depth_dev): 0 (default) rows(x, y, Z), the reference, bit for bit;
+ *                          1 rows(xs, ys, Z*): the current depth is never read, Z_mm may be NULL (no VITVS_NO_DEPTH) and
+ *                          feat[..][0] of vitvs_last_details reports Z*; 2 the element-wise mean 0.5 (rows(x, y, Z) +
+ *                          rows(xs, ys, Z*)) in fp64, Z_mm required as for 0.  e = s - s*, the selection, the statuses and the
+ *                          solve are unchanged; zero-padded rows use the same formulas at pixel (0, 0).  1 and 2 without a goal
+ *                          depth that pairs with the call are error -5 before anything is enqueued.  Applies to every entry
+ *                          point that evaluates the law (vitvs_compute_velocity[_dev], vitvs_servo_from_nn[_ex]_dev,
+ *                          vitvs_reselect), composes with "robust_law" and "subpatch" (the goal side of a refined match stays
+ *                          the patch centre), and drops the handle's captured graphs when changed.  vitvs_last_goal_depth
+ *                          returns Z*; L of vitvs_last_details is the matrix the mode built.
  * Returns 0, or -5 for an unknown name / a value out of range. */
 VITVS_API int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value);
 /* The handles of such an arrangement run ONE network: `h` (created with the same network, input geometry and precision, no

@@ -59,6 +59,9 @@ PROTOTYPES = {
     "vitvs_servo_from_nn_ex_dev": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "vitvs_refine_dev": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "vitvs_last_offsets": (_I, [_P, _I, _P]),
+    "vitvs_set_goal_depth_dev": (_I, [_P, _I, _P, _P]),
+    "vitvs_set_goal_depth": (_I, [_P, _I, _P]),
+    "vitvs_last_goal_depth": (_I, [_P, _I, _P]),
     "vitvs_last_details": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_weights": (_I, [_P, _I, _P]),
     "vitvs_set_option": (_I, [_P, C.c_char_p, C.c_int64]),

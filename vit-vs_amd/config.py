@@ -155,6 +155,9 @@ def baseline_config(key: str) -> ViTConfig:
     return vit_config(name, size)
 
 
+INTERACTIONS = ("current", "desired", "mean")    # values 0 / 1 / 2 of option "interaction" (include/vitvs.h)
+
+
 @dataclass
 class ServoParams:
     """Camera + control-law parameters (reference: config.yaml:1-17,38; vitvs_v2.py:278-283)."""
@@ -172,6 +175,12 @@ class ServoParams:
                                    # plain least squares.  Not in the reference's config.yaml: an extension, off by default
     subpatch: bool = False         # sub-patch refinement of the matches (option "subpatch"); False = the reference's patch centres.
                                    # Not in the reference's config.yaml either: an extension, off by default
+    interaction: str = "current"   # the interaction matrix the law inverts (option "interaction"): "current" L(s, Z), the reference's;
+                                   # "desired" L(s*, Z*); "mean" of the two.  The last two need a goal depth (Engine.set_goal_depth)
+
+    def __post_init__(self):
+        if self.interaction not in INTERACTIONS:
+            raise ValueError(f"interaction is one of {INTERACTIONS}, got {self.interaction!r}")
 
     @property
     def c_x(self) -> float:
@@ -229,7 +238,8 @@ def load_reference_config(source) -> ReferenceConfig:
     defaults for the optional ones: ``max_velocity`` 1.0, ``ema_alpha`` 0.1 (NOT the 0.8 the shipped file sets),
     ``max_velocity_vector_history`` 200, ``background_thresh`` 0.5 (vitvs_v2.py:287, 296, 316, 319).  ``robust_iterations`` (this
     project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
-    sub-patch refinement of the matches) likewise, else False."""
+    sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
+    else "current"."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -245,10 +255,11 @@ def load_reference_config(source) -> ReferenceConfig:
                         lambda_=float(cfg["lambda_"]), num_pairs=int(cfg["num_pairs"]),
                         dino_input_size=int(cfg["dino_input_size"]), use_feature_binning=bool(cfg["use_feature_binning"]),
                         ema_alpha=float(cfg.get("ema_alpha", 0.1)), max_velocity=float(cfg.get("max_velocity", 1.0)),
-                        robust_iterations=int(cfg.get("robust_iterations", 0)), subpatch=bool(cfg.get("subpatch", False)))
+                        robust_iterations=int(cfg.get("robust_iterations", 0)), subpatch=bool(cfg.get("subpatch", False)),
+                        interaction=str(cfg.get("interaction", "current")))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
-            "subpatch"}
+            "subpatch", "interaction"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -123,6 +123,11 @@ struct vitvs_handle {
     float* off_ws = nullptr;  // [max_pairs][max_rows][2] the sub-patch offsets of the last law evaluation (vitvs_last_offsets)
     int subpatch = 0;         // option "subpatch": matches are refined off their patch centres, 0 = the reference's patch centres
     bool last_refine = false; // the last law evaluation wrote off_ws
+    int interaction = 0;      // option "interaction": 0 L(s, Z) (the reference), 1 L(s*, Z*), 2 their mean
+    uint16_t* zgoal = nullptr;  // [max_pairs][T + 1] mm, goal depth at every token's patch centre and at pixel (0, 0) (vitvs_set_goal_depth_dev)
+    int n_goal_depth = 0;     // goal depth images held in zgoal, 0: none
+    double* zgoal_ws = nullptr; // [max_pairs][max_rows] Z* of the last law evaluation's feature rows (vitvs_last_goal_depth)
+    bool last_goalz = false;  // the last law evaluation wrote zgoal_ws
     int last_pairs = 0, last_T = 0;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
     // graph replays' own copy of the selection
@@ -499,6 +504,28 @@ struct RefineSpec {
     int des_shared = 0;
 };
 
+// The geometry of a law call over T = g * g tokens: what token_pixel (servo.hip) reads
+void servo_geometry(const vitvs_handle* h, int T, int g, ServoArgs& a) {
+    const vitvs_config& c = h->cfg;
+    a.T = T; a.grid = g;
+    a.input_size = c.img_size; a.u_max = c.u_max; a.v_max = c.v_max; a.depth_h = c.v_max; a.depth_w = c.u_max;
+    const double scale = (double)c.img_size / (double)g;                 // vitvs_v2.py:511
+    a.scale_f = (float)scale; a.half_f = (float)(scale / 2.0);
+    a.scale_x = (double)c.u_max / (double)c.img_size;                    // vitvs_v2.py:544
+    a.scale_y = (double)c.v_max / (double)c.img_size;                    // vitvs_v2.py:545
+}
+
+// Option "interaction" != 0: the law of a call of n_pairs pairs over T tokens needs a goal depth that pairs with it.  Host-side
+// state, checked by every entry point before it enqueues anything (and never inside a body that a hipGraph captures).
+int check_interaction(vitvs_handle* h, int n_pairs, int T) {
+    if (!h->interaction) return 0;
+    if (!h->n_goal_depth) return set_err(h, -5, "option interaction needs a goal depth (vitvs_set_goal_depth_dev)");
+    if (T != h->T) return set_err(h, -5, "the goal depth table is laid out for the handle's own token grid");
+    if (h->n_goal_depth != n_pairs && h->n_goal_depth != 1)
+        return set_err(h, -5, "the goal depth holds " + std::to_string(h->n_goal_depth) + " images: one per pair, or one for all");
+    return 0;
+}
+
 int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const double* K, int mode, int num_pairs,
               const int32_t* selection, const int32_t* n_selected, double* v_c, int32_t* status, hipStream_t st,
               const RefineSpec& rf = RefineSpec{}) {
@@ -512,12 +539,9 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     if (mode == VITVS_SELECT_DENSE && c.max_rows < T) return set_err(h, -5, "DENSE selection needs max_rows >= T");
     ServoArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_pairs = n_pairs; a.T = T; a.grid = g; a.num_pairs = num_pairs; a.mode = mode;
-    a.input_size = c.img_size; a.u_max = c.u_max; a.v_max = c.v_max; a.depth_h = c.v_max; a.depth_w = c.u_max;
-    const double scale = (double)c.img_size / (double)g;                 // vitvs_v2.py:511
-    a.scale_f = (float)scale; a.half_f = (float)(scale / 2.0);
-    a.scale_x = (double)c.u_max / (double)c.img_size;                    // vitvs_v2.py:544
-    a.scale_y = (double)c.v_max / (double)c.img_size;                    // vitvs_v2.py:545
+    a.n_pairs = n_pairs; a.num_pairs = num_pairs; a.mode = mode;
+    servo_geometry(h, T, g, a);
+    const double scale = (double)c.img_size / (double)g;
     a.K = K; a.lambda = c.lambda;
     a.row_best = h->row_best; a.col_best = h->col_best; a.depth = Z;
     a.selection = selection; a.n_selected = n_selected;
@@ -537,7 +561,13 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
             else { a.dn = h->dn; a.Dp = h->Dp; }
         }
     }
+    if (h->interaction) {
+        if (int rc = check_interaction(h, n_pairs, T)) return rc;
+        a.interaction = h->interaction; a.zgoal = h->zgoal; a.zgoal_out = h->zgoal_ws;
+        a.zgoal_stride = h->n_goal_depth == 1 ? 0 : T + 1;
+    }
     h->last_pairs = n_pairs; h->last_T = T; h->last_robust = h->robust_iters > 0; h->last_refine = a.refine != 0;
+    h->last_goalz = h->interaction != 0;
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(a, st); }
     if (rc) return set_err(h, rc, "servo launch failed (LDS budget or bad arguments)");
@@ -1104,6 +1134,7 @@ int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, 
                                void* stream) {
     if (!h || !nn_1 || !nn_2 || !sim_1 || !K || !v_c || !status) return set_err(h, -1, "null argument");
     if ((size_t)T > h->best_elems) return set_err(h, -3, "T exceeds the handle's workspace");
+    if (int rc = check_interaction(h, 1, T)) return rc;
     DeviceScope dev(h);
     hipStream_t st = as_stream(stream);
     h->details_pinned = false;
@@ -1224,6 +1255,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
     }
     ge->last_use = ++h->graph_clock;
     h->last_pairs = u.n_pairs; h->last_T = h->T; h->last_robust = h->robust_iters > 0; h->last_refine = h->subpatch != 0;
+    h->last_goalz = h->interaction != 0;
     VITVS_HIP_CHECK(hipGraphLaunch(ge->exec, st));
     return 0;
 }
@@ -1266,6 +1298,7 @@ static int velocity_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
     if (u.select_mode != VITVS_SELECT_DENSE && !u.selection) return set_err(h, -5, "selection array required for this mode");
     if (u.select_mode == VITVS_SELECT_EXPLICIT && !u.n_selected) return set_err(h, -5, "n_selected required for EXPLICIT");
     if (vitvs_weights_ready(h) != 0) return set_err(h, -4, "weights not fully loaded: " + h->err);
+    if (int rc = check_interaction(h, u.n_pairs, h->T)) return rc;
     // The goal cache is host-side state of the handle: it is checked and invalidated here, on every call, and never
     // inside the body that a hipGraph captures (a replay runs none of the body's host code).
     if (!u.I_des && h->goal_frames != (u.des_shared ? 1 : u.n_pairs))
@@ -1303,6 +1336,7 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     if (np > c.max_rows) return set_err(h, -5, "num_pairs exceeds max_rows");
     if (select_mode == VITVS_SELECT_EXPLICIT && (!selection || !n_selected)) return set_err(h, -5, "EXPLICIT selection needs ids and counts");
     if (select_mode == VITVS_SELECT_ORDER && !selection) return set_err(h, -5, "ORDER selection needs a visiting order");
+    if (int rc = check_interaction(h, n_pairs, h->T)) return rc;   // (before the frames are staged)
     DeviceScope dev(h);
     if (int rc = ensure_host_stage(h)) return rc;
     vitvs_handle::HostStage& hs = h->hs;
@@ -1329,7 +1363,7 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     }
     UpdateArgs u{n_pairs, des_shared, select_mode, np, h->st_cur, I_des ? h->st_des : nullptr, Z_mm ? hs.depth : nullptr, hs.K,
                  hs.sel, hs.nsel, hs.vc, hs.status};
-    if (Z_mm) {
+    if (Z_mm && h->interaction != IL_DESIRED) {   // L(s*, Z*) never reads the current depth: nothing to stage
         u.late_src = Z_mm; u.late_dst = hs.depth; u.late_count = (int)h->depth_sites.size();
         u.late_sites = h->subpatch ? nullptr : h->depth_sites.data();
         u.late_pairs = n_pairs; u.late_stride = (size_t)c.u_max * c.v_max;
@@ -1363,6 +1397,7 @@ int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t* selectio
     if (np > h->cfg.max_rows) return set_err(h, -5, "num_pairs exceeds max_rows");
     if (select_mode == VITVS_SELECT_EXPLICIT && (!selection || !n_selected)) return set_err(h, -5, "EXPLICIT selection needs ids and counts");
     if (select_mode == VITVS_SELECT_ORDER && !selection) return set_err(h, -5, "ORDER selection needs a visiting order");
+    if (int rc = check_interaction(h, n_pairs, T)) return rc;
     DeviceScope dev(h);
     vitvs_handle::HostStage& hs = h->hs;
     if (select_mode == VITVS_SELECT_EXPLICIT) {
@@ -1484,7 +1519,85 @@ int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value) {
         }
         return 0;
     }
+    if (nm == "interaction") {
+        if (value < IL_CURRENT || value > IL_MEAN)
+            return set_err(h, -5, "interaction takes 0 (current, L(s, Z)), 1 (desired, L(s*, Z*)) or 2 (their mean)");
+        if ((int)value != h->interaction) {     // captured updates hold the previous law's kernel and arguments; the pinned depth
+            DeviceScope dev(h);                 // image of the last host-pointer call holds only what the previous setting reads
+            VITVS_HIP_CHECK(hipDeviceSynchronize());
+            drop_graphs(h);
+            h->interaction = (int)value;
+            h->details_pinned = false;
+            h->host_tables = vitvs_handle::HostTables{};
+        }
+        return 0;
+    }
     return set_err(h, -5, "unknown option " + nm);
+}
+
+int vitvs_set_goal_depth_dev(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_mm, void* stream) {
+    if (!h || (n_goal > 0 && !Z_des_mm)) return set_err(h, -1, "null argument");
+    if (n_goal < 0 || n_goal > h->cfg.max_pairs) return set_err(h, -3, "n_goal exceeds max_pairs");
+    if (h->grid * h->grid != h->T) return set_err(h, -5, "token count is not a square grid");
+    DeviceScope dev(h);
+    if (n_goal != h->n_goal_depth) {            // the first set, a clear, another pairing: captured updates hold the table's
+        VITVS_HIP_CHECK(hipDeviceSynchronize());  // address and its stride between pairs.  Set-up, not the call path.
+        drop_graphs(h);
+        if (n_goal && !h->zgoal) {
+            int rc = dev_alloc(h, &h->zgoal, (size_t)h->cfg.max_pairs * (h->T + 1));
+            if (!rc) rc = dev_alloc(h, &h->zgoal_ws, (size_t)h->cfg.max_pairs * h->cfg.max_rows);
+            if (rc) return set_err(h, rc, "goal depth allocation failed");
+        }
+        h->n_goal_depth = n_goal;
+    }
+    if (!n_goal) return 0;
+    ServoArgs geom;
+    memset(&geom, 0, sizeof(geom));
+    servo_geometry(h, h->T, h->grid, geom);
+    // same count as before: the table is rewritten in place, in stream order — captured updates read the new goal
+    const int rc = launch_goal_depth(geom, Z_des_mm, n_goal, h->zgoal, as_stream(stream));
+    if (rc) return set_err(h, rc, "goal depth launch failed");
+    return 0;
+}
+
+int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_mm) {
+    if (!h || (n_goal > 0 && !Z_des_mm)) return set_err(h, -1, "null argument");
+    if (n_goal < 0 || n_goal > h->cfg.max_pairs) return set_err(h, -3, "n_goal exceeds max_pairs");
+    if (n_goal == 0) return vitvs_set_goal_depth_dev(h, 0, nullptr, nullptr);
+    DeviceScope dev(h);
+    // set-up: a device copy of the images for the one launch that reads them, released again behind it
+    const size_t bytes = (size_t)n_goal * h->cfg.u_max * h->cfg.v_max * sizeof(uint16_t);
+    void* tmp = nullptr;
+    VITVS_HIP_CHECK(hipMalloc(&tmp, bytes));
+    hipError_t e = hipMemcpy(tmp, Z_des_mm, bytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? vitvs_set_goal_depth_dev(h, n_goal, static_cast<const uint16_t*>(tmp), nullptr)
+                             : fail_hip(e, "hipMemcpy", __FILE__, __LINE__);
+    if (!rc) {
+        e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail_hip(e, "hipDeviceSynchronize", __FILE__, __LINE__);
+    }
+    (void)hipFree(tmp);
+    return rc;
+}
+
+int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
+    if (!h || !z) return set_err(h, -1, "null argument");
+    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    DeviceScope dev(h);
+    const size_t R = h->cfg.max_rows, P = n_pairs;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    if (!h->last_goalz) {
+        memset(z, 0, P * R * sizeof(double));
+        return 0;
+    }
+    std::vector<int32_t> inf(P * 8);
+    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(z, h->zgoal_ws, P * R * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < P; ++b) {
+        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
+        for (size_t k = n; k < R; ++k) z[b * R + k] = 0.0;
+    }
+    return 0;
 }
 
 int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w) {

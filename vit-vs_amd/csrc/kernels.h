@@ -279,6 +279,8 @@ int launch_encode_best(const int32_t* nn1, const int32_t* nn2, const float* sim1
 // ---- servo.hip -----------------------------------------------------------------------------
 enum SelectMode : int { SEL_EXPLICIT = 0, SEL_PRIORITY = 1, SEL_DENSE = 2 };
 enum Status : int { ST_OK = 0, ST_NO_CORRESPONDENCE = 1, ST_TOO_FEW = 2, ST_NO_DEPTH = 3 };
+// Which interaction matrix the law inverts (option "interaction"): L(s, Z), L(s*, Z*) or their mean
+enum Interaction : int { IL_CURRENT = 0, IL_DESIRED = 1, IL_MEAN = 2 };
 
 struct ServoArgs {
     int n_pairs, T, grid;
@@ -323,8 +325,17 @@ struct ServoArgs {
     const float* G;           // raw token Gram [n_pairs][T][T] with
     const float* sq;          // the tokens' squared norms [frames][T] (GRAM_STENCIL)
     float* off_out;           // [n_pairs][max_rows][2] (dr, dc) of every feature row (output)
+    // Goal-side interaction matrices (option "interaction"); with interaction == IL_CURRENT none of these is read.
+    // IL_DESIRED never reads `depth` (null is not ST_NO_DEPTH) and reports Z* in feat[..][0]; IL_MEAN keeps Z there.
+    int interaction;          // Interaction
+    int zgoal_stride;         // entries between the goal images of consecutive pairs: T + 1, or 0 when one image serves all
+    const uint16_t* zgoal;    // [n_goal][T + 1] mm: goal depth at every token's patch centre, entry T at pixel (0, 0)
+    double* zgoal_out;        // [n_pairs][max_rows] Z* of every feature row in metres (output)
 };
 int launch_servo(const ServoArgs& a, hipStream_t stream);
+// table [n_goal][T + 1] <- goal depth images Z [n_goal][depth_h][depth_w] (mm) at the sites the law reads; `geom` carries
+// the geometry fields of a law call (T, grid, scale_*, half_f, depth_h, depth_w)
+int launch_goal_depth(const ServoArgs& geom, const uint16_t* Z, int n_goal, uint16_t* table, hipStream_t stream);
 
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)

@@ -5,6 +5,8 @@
 // feature pairs by Tukey's biweight of their residuals and solves again, N times, in the same launch.
 // servo_kernel<., true> (option "subpatch", no counterpart in the reference either) moves every selected match off its patch
 // centre by the sub-patch offsets of refine.h before the pixel features are formed.
+// servo_kernel<., ., true> (option "interaction", ViSP's DESIRED / MEAN choices of the interaction matrix) builds L at the goal
+// features with the goal depth, L(s*, Z*), or the mean of that and the reference's L(s, Z).
 //
 // Reference arithmetic being replaced (vitvs_v2.py):
 //   same-image shortcut  mean(sim_1) > 0.99                   :84-101
@@ -226,7 +228,7 @@ __device__ __forceinline__ int solve_jacobi(double* Lc, int rcap, int R, int lan
 
 // The leading flat arguments repeat the fields of `a` the first memory requests depend on: they are
 // preloaded into SGPRs by the command processor (kernarg preload), the struct is fetched by the wave.
-template <bool ROBUST, bool REFINE>
+template <bool ROBUST, bool REFINE, bool GOALZ>
 __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __restrict__ row_best,
                                                     const unsigned long long* __restrict__ col_best,
                                                     const double* __restrict__ Kin, const int32_t* __restrict__ selection,
@@ -265,13 +267,15 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     // 1. decode the packed (similarity, index) keys.  With one token per thread the depth of the
     // token's match is requested here as well (its address depends on nn_1 only), two phases early.
     // (REFINE: the pixel of a match is known only after its offsets, phase 3b; the depth is read there)
-    const bool prefetch_depth = !REFINE && depth_all != nullptr && T <= 256;
+    // (GOALZ: L(s*, Z*) alone never reads the current depth; first use of `a` moves up here in those instantiations)
+    const bool cur_depth = !GOALZ || a.interaction != IL_DESIRED;
+    const bool prefetch_depth = !REFINE && depth_all != nullptr && T <= 256 && cur_depth;
     int dpre = 0;
     float ssum = 0.f;
     unsigned long long kr0 = 0, kc0 = 0;
     if (tid < T) { kr0 = rb[tid]; kc0 = cb[tid]; }
     // first use of a field of `a` (fetched by the wave itself): after the requests above are in flight
-    const uint16_t* depth = depth_all ? depth_all + (size_t)b * a.depth_h * a.depth_w : nullptr;
+    const uint16_t* depth = (depth_all && cur_depth) ? depth_all + (size_t)b * a.depth_h * a.depth_w : nullptr;
     for (int i = tid; i < T; i += 256) {
         const unsigned long long kr = (i == tid) ? kr0 : rb[i], kc = (i == tid) ? kc0 : cb[i];
         const int n1 = (int)best_index(kr), n2 = (int)best_index(kc);
@@ -439,10 +443,27 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         unsigned d = 0;
         if (live && prefetch_depth && !same_image) d = (unsigned)zraw[tok];
         else if (depth && u >= 0 && u < a.depth_w && v >= 0 && v < a.depth_h) d = depth[(size_t)v * a.depth_w + u];
-        const double z = d != 0 ? (double)d / 1000.0 : 100.0;
+        double z = d != 0 ? (double)d / 1000.0 : 100.0;
         const int r0 = 2 * k, r1i = 2 * k + 1;
-        const double l0[7] = {-1.0 / z, 0.0, x / z, x * y, -(1.0 + x * x), y, x - xs};
-        const double l1[7] = {0.0, -1.0 / z, y / z, 1.0 + y * y, -(x * y), -x, y - ys};
+        double l0[7] = {-1.0 / z, 0.0, x / z, x * y, -(1.0 + x * x), y, x - xs};
+        double l1[7] = {0.0, -1.0 / z, y / z, 1.0 + y * y, -(x * y), -x, y - ys};
+        if constexpr (GOALZ) {
+            // Z* from the handle's table: the goal depth at the patch centre of goal token `tok`; a zero-padded row's goal
+            // pixel is (0, 0), entry T.  The same rows at (xs, ys, Z*) replace the ones above (DESIRED) or are averaged with
+            // them element by element (MEAN); e = s - s* stays.
+            const unsigned ds = a.zgoal[(size_t)b * a.zgoal_stride + (live ? tok : T)];
+            const double zs = ds != 0 ? (double)ds / 1000.0 : 100.0;
+            const double m0[6] = {-1.0 / zs, 0.0, xs / zs, xs * ys, -(1.0 + xs * xs), ys};
+            const double m1[6] = {0.0, -1.0 / zs, ys / zs, 1.0 + ys * ys, -(xs * ys), -xs};
+            const bool mean = a.interaction == IL_MEAN;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                l0[c] = mean ? 0.5 * (l0[c] + m0[c]) : m0[c];
+                l1[c] = mean ? 0.5 * (l1[c] + m1[c]) : m1[c];
+            }
+            if (!mean) z = zs;
+            a.zgoal_out[(size_t)b * a.max_rows + k] = zs;
+        }
 #pragma unroll
         for (int c = 0; c < 7; ++c) {
             Lc[c * rcap + r0] = l0[c];
@@ -467,7 +488,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     // e.g. all-identical zero-padded rows) the general path below runs instead: one-sided Jacobi SVD
     // with numpy.linalg.pinv's rcond = 1e-15 cut-off.
     int status = ST_OK;
-    if (!depth) status = ST_NO_DEPTH;
+    if (!depth && cur_depth) status = ST_NO_DEPTH;
     else if (none) status = ST_NO_CORRESPONDENCE;
     else if (too_few) status = ST_TOO_FEW;
     if constexpr (ROBUST) {
@@ -787,12 +808,12 @@ static size_t servo_lds_bytes(const ServoArgs& a, bool robust, bool refine) {
     return lds;
 }
 
-template <bool ROBUST, bool REFINE>
+template <bool ROBUST, bool REFINE, bool GOALZ>
 static int launch_servo_as(const ServoArgs& a, size_t lds, hipStream_t stream) {
     // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in, per instantiation
     static std::atomic<unsigned long long> raised{0};
-    if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<ROBUST, REFINE>), 160 * 1024, raised)) return -3;
-    launch(servo_kernel<ROBUST, REFINE>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth,
+    if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<ROBUST, REFINE, GOALZ>), 160 * 1024, raised)) return -3;
+    launch(servo_kernel<ROBUST, REFINE, GOALZ>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth,
            a.T, a.mode, a.sel_stride, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -804,11 +825,37 @@ int launch_servo(const ServoArgs& a, hipStream_t stream) {
     // the refinement needs a place for its offsets and one source of them: a table, the raw Gram with the squared norms, or
     // the normalised descriptors (16-byte rows)
     if (a.refine && (!a.off_out || !(a.off_in || (a.G && a.sq) || (a.dn && a.Dp > 0 && a.Dp % 4 == 0)))) return -2;
+    // the goal-side interaction matrices need the goal-depth table (T + 1 entries per goal image) and a place for Z*
+    if (a.interaction < IL_CURRENT || a.interaction > IL_MEAN) return -2;
+    if (a.interaction != IL_CURRENT && (!a.zgoal || !a.zgoal_out || (a.zgoal_stride != 0 && a.zgoal_stride != a.T + 1))) return -2;
     const bool robust = a.robust_iters > 0, refine = a.refine != 0;
     const size_t lds = servo_lds_bytes(a, robust, refine);
     if (lds > 160 * 1024) return -3;
-    if (robust) return refine ? launch_servo_as<true, true>(a, lds, stream) : launch_servo_as<true, false>(a, lds, stream);
-    return refine ? launch_servo_as<false, true>(a, lds, stream) : launch_servo_as<false, false>(a, lds, stream);
+    if (a.interaction != IL_CURRENT) {
+        if (robust) return refine ? launch_servo_as<true, true, true>(a, lds, stream) : launch_servo_as<true, false, true>(a, lds, stream);
+        return refine ? launch_servo_as<false, true, true>(a, lds, stream) : launch_servo_as<false, false, true>(a, lds, stream);
+    }
+    if (robust) return refine ? launch_servo_as<true, true, false>(a, lds, stream) : launch_servo_as<true, false, false>(a, lds, stream);
+    return refine ? launch_servo_as<false, true, false>(a, lds, stream) : launch_servo_as<false, false, false>(a, lds, stream);
+}
+
+// Goal depth of every token (vitvs_set_goal_depth_dev): table[g][t] = Z[g] at token t's patch centre (token_pixel; 0 outside the
+// image, which the law reads as 100 m like a hole), table[g][T] = Z[g] at pixel (0, 0), the goal pixel of a zero-padded row.
+__global__ __launch_bounds__(256) void goal_depth_kernel(const uint16_t* __restrict__ Z, uint16_t* __restrict__ table, ServoArgs a) {
+    const int t = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    if (t > a.T) return;
+    const uint16_t* img = Z + (size_t)g * a.depth_h * a.depth_w;
+    long u = 0, v = 0;
+    if (t < a.T) token_pixel(a, t, u, v);
+    uint16_t d = 0;
+    if (u >= 0 && u < a.depth_w && v >= 0 && v < a.depth_h) d = img[(size_t)v * a.depth_w + u];
+    table[(size_t)g * (a.T + 1) + t] = d;
+}
+
+int launch_goal_depth(const ServoArgs& geom, const uint16_t* Z, int n_goal, uint16_t* table, hipStream_t stream) {
+    if (n_goal <= 0 || geom.T <= 0 || geom.grid * geom.grid != geom.T || geom.depth_h <= 0 || geom.depth_w <= 0 || !Z || !table) return -2;
+    launch(goal_depth_kernel, dim3((geom.T + 1 + 255) / 256, n_goal), dim3(256), 0, stream, Z, table, geom);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace vitvs

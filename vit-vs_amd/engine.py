@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ServoParams, ViTConfig
+from .config import INTERACTIONS, ServoParams, ViTConfig
 from .weights import check_state_dict, resample_pos_embed
 
 
@@ -81,6 +81,8 @@ class Engine:
             self.set_option("robust_law", self.params.robust_iterations)
         if self.params.subpatch:
             self.set_option("subpatch", 1)
+        if self.params.interaction != "current":
+            self.set_option("interaction", INTERACTIONS.index(self.params.interaction))
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -318,6 +320,28 @@ class Engine:
         self._check(self.lib.vitvs_set_goal_dev(self.handle, int(des.shape[0]), _ptr(des), _stream_ptr(self.device)), "vitvs_set_goal_dev")
         return self
 
+    def set_goal_depth(self, Z) -> "Engine":
+        """The depth image(s) taken at the goal pose, uint16 millimetres [v_max, u_max] or [n, v_max, u_max] (``vitvs_set_goal_depth_dev``
+        on the current stream for a device tensor, else ``vitvs_set_goal_depth``): what ``interaction`` "desired" and "mean" read
+        Z* from.  One image per pair of the later calls, or one image for all of them.  ``None`` clears it."""
+        if Z is None:
+            self._check(self.lib.vitvs_set_goal_depth(self.handle, 0, None), "vitvs_set_goal_depth")
+            return self
+        dev = torch.is_tensor(Z) and Z.is_cuda
+        z = Z if dev else np.ascontiguousarray(Z)
+        if z.dtype != (torch.uint16 if dev else np.uint16) or tuple(z.shape[-2:]) != (self.params.v_max, self.params.u_max) \
+                or z.ndim not in (2, 3):
+            raise VitvsError("the goal depth is the sensor's uint16 millimetre image(s) [v_max, u_max]")
+        n = 1 if z.ndim == 2 else int(z.shape[0])
+        if dev:
+            z = z.to(self.device).contiguous()
+            rc = self.lib.vitvs_set_goal_depth_dev(self.handle, n, _ptr(z), _stream_ptr(self.device))
+            z.record_stream(torch.cuda.current_stream(self.device))
+        else:
+            rc = self.lib.vitvs_set_goal_depth(self.handle, n, z.ctypes.data_as(C.c_void_p))
+        self._check(rc, "vitvs_set_goal_depth")
+        return self
+
     def compute_velocity_dev(self, I_cur: torch.Tensor, I_des: Optional[torch.Tensor], Z: Optional[torch.Tensor],
                              K: torch.Tensor, mode: int = _lib.SELECT_DENSE, selection: Optional[torch.Tensor] = None,
                              n_selected: Optional[torch.Tensor] = None, des_shared: bool = False,
@@ -463,7 +487,7 @@ class Engine:
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),
         ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings), ``subpatch`` (0: patch centres; 1: matches
-        refined by their sub-patch offsets)."""
+        refined by their sub-patch offsets), ``interaction`` (0: L(s, Z); 1: L(s*, Z*); 2: their mean)."""
         self._check(self.lib.vitvs_set_option(self.handle, name.encode(), int(value)), f"vitvs_set_option({name})")
         return self
 
@@ -495,7 +519,14 @@ class Engine:
                                          p(feat), p(L))
         self._check(rc, "vitvs_last_details")
         return dict(nn_1=nn1, nn_2=nn2, sim_1=sim1, info=info, selected=sel, s_uv=suv, feat=feat, L=L,
-                    weights=self.last_weights(n_pairs), offsets=self.last_offsets(n_pairs))
+                    weights=self.last_weights(n_pairs), offsets=self.last_offsets(n_pairs), Z_goal=self.last_goal_depth(n_pairs))
+
+    def last_goal_depth(self, n_pairs: int = 1) -> np.ndarray:
+        """``vitvs_last_goal_depth``: float64 [n, max_rows], Z* in metres of every feature row in the last law evaluation (all 0
+        with ``interaction`` "current", and on unused rows).  Synchronises."""
+        z = np.empty((n_pairs, self.max_rows), np.float64)
+        self._check(self.lib.vitvs_last_goal_depth(self.handle, n_pairs, z.ctypes.data_as(C.c_void_p)), "vitvs_last_goal_depth")
+        return z
 
     def last_offsets(self, n_pairs: int = 1) -> np.ndarray:
         """``vitvs_last_offsets``: float32 [n, max_rows, 2], the sub-patch offsets (dr, dc) of every feature row's match in the

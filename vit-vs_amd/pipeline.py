@@ -145,6 +145,14 @@ class UpdatePipeline:
             with torch.cuda.stream(self.streams[k]):
                 e.set_goal(I_des)
 
+    def set_goal_depth(self, Z):
+        """The goal depth image(s) into every handle (``Engine.set_goal_depth``), each on its slot's stream: updates submitted
+        afterwards read it.  ``None`` clears it."""
+        for k, e in enumerate(self.engines):
+            self.streams[k].wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(self.streams[k]):
+                e.set_goal_depth(Z)
+
     # ------------------------------------------------------------------ collect
     def slot(self, ticket: int) -> Tuple[torch.Tensor, torch.Tensor, torch.cuda.Stream]:
         """Output buffers (v_c [n, 6] float64, status [n] int32) and stream of ``ticket`` without waiting."""

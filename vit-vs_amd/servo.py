@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ServoParams
+from .config import INTERACTIONS, ServoParams
 from .engine import Engine, VitvsError
 
 STATUS_NAMES = {0: "ok", 1: "no_correspondence", 2: "too_few_features", 3: "no_depth"}
@@ -217,9 +217,15 @@ class Controller:
     in the control loop, read ``v_c``.  Attribute names follow the reference so its ``run()`` logic ports 1:1."""
 
     def __init__(self, engine: Engine, goal_image, params: Optional[ServoParams] = None,
-                 selection: str = "reference"):
+                 selection: str = "reference", goal_depth=None):
         self.engine = engine
         self.params = params or engine.params
+        if params is not None and params.interaction != engine.params.interaction:
+            engine.set_option("interaction", INTERACTIONS.index(params.interaction))
+            engine.params = engine.params.replace(interaction=params.interaction)
+        self.goal_depth = None                            # uint16 millimetres at the goal pose (interaction "desired" / "mean")
+        if goal_depth is not None:
+            self.set_goal_depth(goal_depth)
         if params is not None and params.robust_iterations != engine.params.robust_iterations:
             engine.set_option("robust_law", params.robust_iterations)      # the law of the params this controller was given
             engine.params = engine.params.replace(robust_iterations=params.robust_iterations)
@@ -243,6 +249,12 @@ class Controller:
         self._goal_key, self._goal_np = None, None        # a private, never-written copy of the goal frame: its address tells the
                                                           # library that the staged goal is still the goal (option "reuse_goal_frames")
         self._rejected_geometries = set()                 # camera geometries the fused resize refused (set_frame_size), per engine
+
+    def set_goal_depth(self, depth_u16):
+        """The depth image taken at the goal pose (uint16 millimetres, v_max x u_max): Z* of the "desired" and "mean" interaction
+        matrices.  With "desired" the run then needs no depth image at all.  ``None`` clears it."""
+        self.goal_depth = None if depth_u16 is None else np.asarray(depth_u16)
+        self.engine.set_goal_depth(self.goal_depth)
 
     # -- inputs (the reference's ROS callbacks)
     def image_callback_rgb(self, rgb_u8):
@@ -359,8 +371,8 @@ class Controller:
     def _law_step(self, have_features: bool):
         if not have_features:
             return
-        if self.latest_image_depth is None:               # reference: "Failed to get depth - skipping"
-            return
+        if self.latest_image_depth is None and self.params.interaction != "desired":
+            return                                        # reference: "Failed to get depth - skipping"; L(s*, Z*) reads none
         # fewer than 4 matches: the reference's calculate_uv hands back all-zero feature arrays of num_pairs rows
         # (vitvs_v2.py:539-541), len() >= 4 passes the check at :604, e = 0 and the raw twist is exactly 0 — which is
         # what the kernel reports with status TOO_FEW; the EMA is updated with it, as in the reference
@@ -433,7 +445,7 @@ class MultiController:
     """
 
     def __init__(self, backend, goal_images: Sequence, params: Optional[ServoParams] = None, selection: str = "order",
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, goal_depth=None):
         from .pipeline import UpdatePipeline
         self.pipe = backend if isinstance(backend, UpdatePipeline) else None
         self.engines = list(backend.engines) if self.pipe is not None else [backend]
@@ -452,8 +464,18 @@ class MultiController:
                 if e.params.subpatch != params.subpatch:
                     e.set_option("subpatch", int(params.subpatch))
                     e.params = e.params.replace(subpatch=params.subpatch)
+                if e.params.interaction != params.interaction:
+                    e.set_option("interaction", INTERACTIONS.index(params.interaction))
+                    e.params = e.params.replace(interaction=params.interaction)
         self.cameras = [Controller(self.engine, g, params, selection="order") for g in goal_images]
         self.params = self.cameras[0].params
+        # the goal depth of interaction "desired" / "mean": one image (uint16 [v_max, u_max]) that serves every camera, in every
+        # engine or slot (one image pairs with a call of any number of pairs)
+        if goal_depth is not None:
+            if self.pipe is not None:
+                self.pipe.set_goal_depth(np.asarray(goal_depth))
+            else:
+                self.engine.set_goal_depth(np.asarray(goal_depth))
         self._buffers = {}                                # pipeline mode: per-camera device inputs at stable addresses
 
     def __len__(self):
