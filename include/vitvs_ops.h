@@ -85,6 +85,13 @@ VITVS_API int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t 
  * 8 GiB).  Returns 0, or -2 when unlaunchable. */
 VITVS_API int vitvs_op_gram_plan(int32_t precision, int32_t binned, int32_t T, int32_t D, int32_t n_pairs, int32_t max_pairs,
                        int32_t* out);
+/* the control law's launch for T tokens, max_rows feature pairs, robust_law = robust_iters, the refinement's source (0 off, 1 a
+ * given table, 2 the raw Gram, 3 the normalised descriptors) and option interaction, no device work: out[0..6] = the ROBUST, REFINE
+ * and GOALZ instantiation bits, dynamic LDS bytes, the source, whether the current depth image is read, and whether at any pixel
+ * (else at patch centres only).  Returns 0, -2 for an argument out of range (out is the plain law's of no tokens), or -3 past
+ * 160 KiB of LDS (out filled). */
+VITVS_API int vitvs_op_servo_plan(int32_t T, int32_t max_rows, int32_t robust_iters, int32_t refine_source, int32_t interaction,
+                        int32_t* out);
 /* The fused Gram arg-max of the velocity path on caller-normalised descriptors dn [n_des + n_pairs][T][Dp] fp32 (desired frames
  * first; n_des = 1 with des_shared): the plan of vitvs_op_gram_plan(precision, 0, T, Dp, n_pairs, n_pairs), the split into dh
  * (3 (n_des + n_pairs) T Dp fp16, only when the plan splits) and the keys row_best / col_best [n_pairs][T] (cleared here), decoded

@@ -209,3 +209,51 @@ def test_gram_plan_of_the_library():
     for prec, binned, T, D, n, max_pairs, rc, *want in table.tolist():
         if rc == 0:
             assert (want[0], want[6]) == at_capacity[(prec, binned, T, D, max_pairs)], (prec, binned, T, D, n, max_pairs)
+
+
+def test_servo_plan_of_the_library():
+    """The control law's launch is host arithmetic too (vitvs_op_servo_plan, no device call): the instantiation bits, the dynamic
+    LDS bytes, the refinement's source and what the launch reads of the current depth image.  The kernel lays its LDS out by the
+    same sizes, so a plan that came out too small would write past its allocation: the bytes are pinned here, against a
+    restatement of the formula the launch used before it was planned and against literal anchors, before anything runs."""
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 7)()
+    ROWS = 128                                               # L rows kept in LDS (servo.hip kLdsRows)
+
+    def lds_bytes(T, max_rows, robust, refine):
+        words = 4 * T + (T if T <= 256 else 0) + max_rows + 16 + 4      # zraw [T]: the depth prefetch, T <= 256 only
+        lds = ((words * 4 + 15) & ~15) + 7 * ROWS * 8 + (40 + 8 * 27) * 8
+        if robust:
+            lds += (7 * ROWS + ROWS // 2 + max_rows) * 8
+        if refine:
+            lds += max_rows * 2 * 4
+        return lds
+
+    def plan(T, max_rows, robust=0, source=0, interaction=0):
+        rc = lib.vitvs_op_servo_plan(T, max_rows, robust, source, interaction, out)
+        return rc, list(out)
+    for T in (16, 196, 256, 289, 484, 1024, 3136, 4096, 5184, 6400):
+        for max_rows in (24, 48, 130, T):
+            for robust in (0, 1, 16):
+                for source in (0, 1, 2, 3):
+                    for interaction in (0, 1, 2):
+                        want = lds_bytes(T, max_rows, robust > 0, source != 0)
+                        rc, got = plan(T, max_rows, robust, source, interaction)
+                        what = (T, max_rows, robust, source, interaction)
+                        assert rc == (-3 if want > 160 * 1024 else 0), what
+                        assert got == [int(robust > 0), int(source != 0), int(interaction != 0), want, source,
+                                       int(interaction != 1), int(source != 0)], (what, got)
+    # T, max_rows -> plain, refine, robust, robust + refine; T = 256 and 289 on either side of the depth-prefetch words; at
+    # T = 3136 the plain and refine plans stay under 64 KiB (the per-instantiation opt-in) and both robust plans pass it
+    anchors = {(196, 48): (13408, 13792, 21472, 21856), (256, 48): (14608, None, None, None), (289, 48): (14112, None, None, None),
+               (3136, 48): (59664, 60048, 67728, 68112), (4096, 4096): (91216, 123984, 131664, 164432),
+               (5184, 5184): (None, 154448, 162128, None)}
+    for (T, max_rows), sizes in anchors.items():
+        for (robust, source), want in zip(((0, 0), (0, 3), (2, 0), (2, 3)), sizes):
+            if want is not None:
+                rc, got = plan(T, max_rows, robust, source)
+                assert (rc, got[3]) == (-3 if want > 160 * 1024 else 0, want), (T, max_rows, robust, source, got)
+    assert 60048 < 64 * 1024 < 67728 and plan(5184, 5184, 2, 3)[0] == -3
+    for bad in (dict(robust=17), dict(robust=-1), dict(interaction=3), dict(interaction=-1), dict(source=4), dict(source=-1)):
+        assert plan(196, 48, **bad)[0] == -2, bad
+    assert plan(0, 48)[0] == -2 and plan(196, 0)[0] == -2

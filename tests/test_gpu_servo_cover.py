@@ -7,7 +7,8 @@ when a pivot falls below 1e-8 of its diagonal, one-sided Jacobi SVD, whose lanes
 asserts which solver ran through info[4] (-1: LDL^T, otherwise the Jacobi sweeps, <= 40) and R through info[5], and checks the
 law against oracle/servo_ref (numpy pinv): s_uv exact, Z exact, L within 1e-13, v_c within 1e-9 (relative L2).  The tables go
 in through vitvs_servo_from_nn_dev (tiny handles, T up to 1024) or come from velocity calls of the 2-block tiny model.
-Also here: the reselect state of the host-pointer entry point ends with every call that rewrites the arg-max keys."""
+Also here: the three law options (robust_law, subpatch, interaction) together through the forward and every entry point, and the
+reselect state of the host-pointer entry point, which ends with every call that rewrites the arg-max keys."""
 import dataclasses
 
 import numpy as np
@@ -18,6 +19,7 @@ import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
 from oracle import servo_ref as sr
+import robust_ref as rr
 
 pytestmark = pytest.mark.gpu
 
@@ -273,6 +275,85 @@ def test_three_pairs_each_with_its_own_intrinsics_depth_and_selection():
         assert np.array_equal(det["nn_1"][b], tabs["nn_1"][b]) and int(det["info"][b, 2]) == 0
         s_star, s_, ref = _oracle(g, cfg.img_size, params, det["nn_1"][b].astype(np.int64), ids[b], k, depth[b], K[b])
         _check_law(det, b, v[b], st[b], ref, s_star, s_, k, "jacobi" if b == 1 else "ldlt", ("pair", b))
+    eng.close()
+
+
+# ----------------------------------------------------------------------------- the three law options at once
+@pytest.mark.parametrize("binned", [False, True])
+def test_all_three_law_options_through_every_entry_point(binned):
+    """robust_law, subpatch and interaction together on a ViT-S/16 forward (T = 196, fp32): the refinement reads the normalised
+    descriptors (plain) or the raw Gram (binned).  The device call, the host call, the reselect seam and a captured update on a
+    side stream give the same v_c and the same per-row outputs bit for bit; switching the options off one by one changes the
+    replay and returns each getter to its "off" value."""
+    cfg = config.baseline_config("vits16_224")
+    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=binned, robust_iterations=2, subpatch=True,
+                                interaction="mean")
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
+    des, cur = synth.frame_pair(cfg.img_size, 20250705)
+    depth, K, k = synth.depth_pattern(), params.intrinsics(), 24
+    zg = (np.ascontiguousarray(depth[::-1, ::-1]).astype(np.int64) + 137).clip(1, 65535).astype(np.uint16)
+    eng.set_goal_depth(zg)
+    order = np.random.default_rng(11).permutation(cfg.tokens).astype(np.int32)
+
+    def rows():
+        return dict(weights=eng.last_weights(1), offsets=eng.last_offsets(1), Z_goal=eng.last_goal_depth(1), **eng.last_features(1))
+
+    def same_rows(what):
+        got = rows()
+        for key, want in eager.items():
+            assert np.array_equal(got[key], want), (what, key)
+    v, st = eng.compute_velocity(cur, des, depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
+    assert int(st[0]) == _lib.STATUS_OK
+    v, det, eager = v.cpu().numpy()[0], eng.last_details(1), rows()
+    assert det["offsets"][0, :k].any() and det["Z_goal"][0, :k].all() and int(det["info"][0, 6]) == 2
+    rob = rr.robust_velocity(det["L"][0, :6, :2 * k].T, det["L"][0, 6, :2 * k], params.lambda_, 2,
+                             rr.sigma_min(cfg.stride, params.u_max, params.v_max, cfg.img_size, K[0], K[1]))
+    if rob["margin"] >= 1e-6:
+        assert rr.rel_l2(v, rob["v_c"]) <= VC_BAR
+    vh, sth = eng.compute_velocity_host(cur, des, depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
+    assert int(sth[0]) == _lib.STATUS_OK and np.array_equal(vh[0], v)
+    same_rows("host")
+    vr, str_ = eng.reselect_host(_lib.SELECT_ORDER, order, num_pairs=k)
+    assert int(str_[0]) == _lib.STATUS_OK and np.array_equal(vr[0], v)
+    same_rows("reselect")
+    # a captured update (a side stream: the default stream is never captured)
+    eng.set_option("graph_replay", 1)
+    cur_d, des_d = eng._frames(cur), eng._frames(des)
+    z_d = torch.as_tensor(depth).reshape(1, params.v_max, params.u_max).to(eng.device).contiguous()
+    k_d = torch.as_tensor(K, dtype=torch.float64).reshape(1, 4).to(eng.device)
+    sel_d, cnt_d = eng._selection_args(_lib.SELECT_ORDER, order, 1, cfg.tokens, k)
+    out_v = torch.zeros((1, 6), dtype=torch.float64, device=eng.device)
+    out_s = torch.zeros(1, dtype=torch.int32, device=eng.device)
+    side = torch.cuda.Stream(eng.device)
+    torch.cuda.synchronize()
+
+    def replayed():
+        with torch.cuda.stream(side):
+            eng.compute_velocity_dev(cur_d, des_d, z_d, k_d, _lib.SELECT_ORDER, sel_d, cnt_d, out_v=out_v, out_status=out_s, num_pairs=k)
+        torch.cuda.synchronize()
+        return out_v.cpu().numpy()[0].copy()
+    for what in ("captured", "replayed"):
+        assert np.array_equal(replayed(), v), what
+        same_rows(what)
+    eng.set_option("graph_replay", 0)
+    ve, _ = eng.compute_velocity(cur, des, depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
+    assert np.array_equal(ve.cpu().numpy()[0], v)
+    same_rows("eager again")
+    # off, one by one
+    eng.set_option("graph_replay", 1)
+    prev = replayed()
+    eng.set_option("robust_law", 0)
+    now = replayed()
+    assert not np.array_equal(now, prev) and np.all(eng.last_weights(1)[0, :k] == 1.0) and not eng.last_weights(1)[0, k:].any()
+    assert eng.last_offsets(1).any() and eng.last_goal_depth(1).any()
+    prev = now
+    eng.set_option("subpatch", 0)
+    now = replayed()
+    assert not np.array_equal(now, prev) and not eng.last_offsets(1).any() and eng.last_goal_depth(1).any()
+    prev = now
+    eng.set_option("interaction", 0)
+    now = replayed()
+    assert not np.array_equal(now, prev) and not eng.last_goal_depth(1).any() and int(out_s[0]) == _lib.STATUS_OK
     eng.close()
 
 

@@ -91,6 +91,7 @@ PROTOTYPES = {
     "vitvs_op_attention_plan": (_I, [_I, _I, _I, _I, _P]),
     "vitvs_op_linear_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "vitvs_op_gram_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "vitvs_op_servo_plan": (_I, [_I, _I, _I, _I, _I, _P]),
     "vitvs_op_gram_argmax": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_gram_stencil": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_linear_partial": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),

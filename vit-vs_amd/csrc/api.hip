@@ -119,16 +119,15 @@ struct vitvs_handle {
     double *feat = nullptr, *Lws = nullptr;
     double* Wws = nullptr;    // [max_pairs][max_rows] the robust law's final weights (vitvs_last_weights)
     int robust_iters = 0;     // option "robust_law": Tukey re-weightings of the control law, 0 = the reference's plain law
-    bool last_robust = false; // the last law evaluation wrote Wws
     float* off_ws = nullptr;  // [max_pairs][max_rows][2] the sub-patch offsets of the last law evaluation (vitvs_last_offsets)
     int subpatch = 0;         // option "subpatch": matches are refined off their patch centres, 0 = the reference's patch centres
-    bool last_refine = false; // the last law evaluation wrote off_ws
     int interaction = 0;      // option "interaction": 0 L(s, Z) (the reference), 1 L(s*, Z*), 2 their mean
     uint16_t* zgoal = nullptr;  // [max_pairs][T + 1] mm, goal depth at every token's patch centre and at pixel (0, 0) (vitvs_set_goal_depth_dev)
     int n_goal_depth = 0;     // goal depth images held in zgoal, 0: none
     double* zgoal_ws = nullptr; // [max_pairs][max_rows] Z* of the last law evaluation's feature rows (vitvs_last_goal_depth)
-    bool last_goalz = false;  // the last law evaluation wrote zgoal_ws
+    // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
+    ServoPlan last_law;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
     // graph replays' own copy of the selection
     uint8_t *st_cur = nullptr, *st_des = nullptr;
@@ -503,6 +502,18 @@ struct RefineSpec {
     bool from_forward = false;      // option "subpatch": the descriptors / raw Gram the forward left in the handle
     int des_shared = 0;
 };
+// The law of one call over T tokens, planned once from the handle's options and the call's refinement (plan_servo): what
+// run_servo launches, what a replay "last ran", and what a host-pointer call stages of the depth image
+int plan_law(vitvs_handle* h, int T, const RefineSpec& rf, ServoPlan& plan) {
+    const RefineSource src = rf.table ? RS_TABLE : !rf.from_forward ? RS_OFF : h->gram.refine_from_gram ? RS_GRAM : RS_DESC;
+    const int rc = plan_servo(T, h->cfg.max_rows, h->robust_iters, src, h->interaction, &plan);
+    return rc ? set_err(h, rc, "servo launch failed (LDS budget or bad arguments)") : 0;
+}
+
+// The one place that records which law the handle's per-row workspaces and detail block are about to hold
+void note_law(vitvs_handle* h, int n_pairs, int T, const ServoPlan& plan) {
+    h->last_pairs = n_pairs; h->last_T = T; h->last_law = plan;
+}
 
 // The geometry of a law call over T = g * g tokens: what token_pixel (servo.hip) reads
 void servo_geometry(const vitvs_handle* h, int T, int g, ServoArgs& a) {
@@ -526,22 +537,29 @@ int check_interaction(vitvs_handle* h, int n_pairs, int T) {
     return 0;
 }
 
+// What every entry point asks of a call's selection over T tokens, before it stages or enqueues anything
+int check_selection(vitvs_handle* h, int T, int mode, const int32_t* selection, const int32_t* n_selected, int num_pairs) {
+    if (num_pairs <= 0 || num_pairs > h->cfg.max_rows) return set_err(h, -5, "num_pairs must be in 1 .. max_rows");
+    if (mode < 0 || mode > 2) return set_err(h, -5, "unknown selection mode");
+    if (mode != VITVS_SELECT_DENSE && !selection) return set_err(h, -5, "selection array required for this mode");
+    if (mode == VITVS_SELECT_EXPLICIT && !n_selected) return set_err(h, -5, "n_selected required for EXPLICIT");
+    if (mode == VITVS_SELECT_DENSE && h->cfg.max_rows < T) return set_err(h, -5, "DENSE selection needs max_rows >= T");
+    return 0;
+}
+
+// The law on the arg-max keys in the handle, for a selection the entry point has checked (check_selection)
 int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const double* K, int mode, int num_pairs,
               const int32_t* selection, const int32_t* n_selected, double* v_c, int32_t* status, hipStream_t st,
               const RefineSpec& rf = RefineSpec{}) {
     const vitvs_config& c = h->cfg;
-    if (num_pairs <= 0 || num_pairs > c.max_rows) return set_err(h, -5, "num_pairs must be in 1 .. max_rows");
     const int g = (int)floor(sqrt((double)T));  // reference: int(np.sqrt(T)), vitvs_v2.py:75
     if (g * g != T) return set_err(h, -5, "token count is not a square grid");
-    if (mode < 0 || mode > 2) return set_err(h, -5, "unknown selection mode");
-    if (mode != VITVS_SELECT_DENSE && !selection) return set_err(h, -5, "selection array required for this mode");
-    if (mode == VITVS_SELECT_EXPLICIT && !n_selected) return set_err(h, -5, "n_selected required for EXPLICIT");
-    if (mode == VITVS_SELECT_DENSE && c.max_rows < T) return set_err(h, -5, "DENSE selection needs max_rows >= T");
+    ServoPlan plan;
+    if (int rc = plan_law(h, T, rf, plan)) return rc;
     ServoArgs a;
     memset(&a, 0, sizeof(a));
     a.n_pairs = n_pairs; a.num_pairs = num_pairs; a.mode = mode;
     servo_geometry(h, T, g, a);
-    const double scale = (double)c.img_size / (double)g;
     a.K = K; a.lambda = c.lambda;
     a.row_best = h->row_best; a.col_best = h->col_best; a.depth = Z;
     a.selection = selection; a.n_selected = n_selected;
@@ -549,27 +567,23 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     a.v_c = v_c; a.status = status; a.nn1 = h->nn1; a.nn2 = h->nn2; a.sim1 = h->sim1; a.info = h->info;
     a.sel_out = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.L_ws = h->Lws; a.max_rows = c.max_rows;
     a.L_work = h->Lws + (size_t)c.max_pairs * 7 * 2 * c.max_rows;
-    a.robust_iters = h->robust_iters; a.W_ws = h->Wws;
+    a.robust_iters = plan.robust_iters; a.W_ws = h->Wws;
     a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
     a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
-    a.refine = (rf.table || rf.from_forward) ? 1 : 0;
-    if (a.refine) {
-        a.pitch_in = scale; a.off_out = h->off_ws; a.off_in = rf.table;
-        if (rf.from_forward) {
-            a.des_shared = rf.des_shared;
-            if (h->gram.refine_from_gram) { a.G = h->gram_ws; a.sq = h->sq; }
-            else { a.dn = h->dn; a.Dp = h->Dp; }
-        }
+    a.refine = plan.refine;
+    if (plan.refine) {
+        a.pitch_in = (double)c.img_size / (double)g; a.off_out = h->off_ws; a.des_shared = rf.des_shared;
+        if (plan.source == RS_TABLE) a.off_in = rf.table;
+        else if (plan.source == RS_GRAM) { a.G = h->gram_ws; a.sq = h->sq; }
+        else { a.dn = h->dn; a.Dp = h->Dp; }
     }
-    if (h->interaction) {
-        if (int rc = check_interaction(h, n_pairs, T)) return rc;
-        a.interaction = h->interaction; a.zgoal = h->zgoal; a.zgoal_out = h->zgoal_ws;
+    if (plan.goalz) {                           // (the entry points have checked the goal depth: check_interaction)
+        a.interaction = plan.interaction; a.zgoal = h->zgoal; a.zgoal_out = h->zgoal_ws;
         a.zgoal_stride = h->n_goal_depth == 1 ? 0 : T + 1;
     }
-    h->last_pairs = n_pairs; h->last_T = T; h->last_robust = h->robust_iters > 0; h->last_refine = a.refine != 0;
-    h->last_goalz = h->interaction != 0;
+    note_law(h, n_pairs, T, plan);
     int rc = 0;
-    { Span sp(h, KC_SERVO, st); rc = launch_servo(a, st); }
+    { Span sp(h, KC_SERVO, st); rc = launch_servo(plan, a, st); }
     if (rc) return set_err(h, rc, "servo launch failed (LDS budget or bad arguments)");
     return 0;
 }
@@ -613,6 +627,61 @@ int wait_stream(hipStream_t st) {
         if (e != hipErrorNotReady) return fail_hip(e, "hipStreamQuery", __FILE__, __LINE__);
     }
     VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Head and tail of a host-pointer law evaluation (vitvs_compute_velocity, vitvs_reselect).  The call's selection goes into the
+// pinned block, where the law's kernel reads it in place
+void stage_selection(vitvs_handle* h, int n_pairs, int T, int mode, const int32_t* selection, const int32_t* n_selected, int num_pairs) {
+    if (mode == VITVS_SELECT_EXPLICIT) {
+        memcpy(h->hs.sel, selection, (size_t)n_pairs * num_pairs * 4);
+        memcpy(h->hs.nsel, n_selected, (size_t)n_pairs * 4);
+    } else if (mode == VITVS_SELECT_ORDER) {
+        memcpy(h->hs.sel, selection, (size_t)n_pairs * T * 4);
+    }
+}
+// ... and behind the law: the detail block of this call -> the pinned block, one copy launch of 16-byte stores (measured: the
+// law's kernel writing its ~20 small detail stores straight into host memory cost 60 us per update; one coalesced copy costs 3),
+// one polled wait, v_c and status out
+int finish_host_call(vitvs_handle* h, int n_pairs, double* v_c, int32_t* status) {
+    const int rc = launch_copy16(h->det_block, h->hs.det, h->det_bytes, h->host_stream);
+    if (rc) return set_err(h, rc, "detail copy launch failed");
+    if (int w = wait_stream(h->host_stream)) return w;
+    memcpy(v_c, h->hs.vc, (size_t)n_pairs * 6 * sizeof(double));
+    memcpy(status, h->hs.status, (size_t)n_pairs * 4);
+    return 0;
+}
+
+// What the vitvs_last_* getters start with: n_pairs against the last call, the device drained, every pair's info.  pinned: info
+// comes from the pinned block of the last host-pointer call, without a HIP call (vitvs_last_details)
+int last_info(vitvs_handle* h, int n_pairs, bool pinned, std::vector<int32_t>& inf) {
+    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    inf.resize((size_t)n_pairs * 8);
+    if (pinned) {
+        memcpy(inf.data(), h->hs.det, inf.size() * 4);
+        return 0;
+    }
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, inf.size() * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The kernel writes the first n_feature_rows (info[1]) rows of a pair; the workspace rows behind them may still hold an earlier,
+// larger call's values.  The copies handed out are defined everywhere: selected = -1, everything else 0.
+size_t feature_rows(const vitvs_handle* h, const std::vector<int32_t>& inf, size_t b) {
+    return std::min<size_t>(h->cfg.max_rows, (size_t)std::max(inf[b * 8 + 1], 0));
+}
+// A per-row workspace [max_pairs][max_rows][width] of the last law: copied out when that law wrote it, zeros when it did not
+template <typename V>
+int last_row_output(vitvs_handle* h, int n_pairs, bool written, const V* ws, size_t width, V* out) {
+    DeviceScope dev(h);
+    std::vector<int32_t> inf;
+    if (int rc = last_info(h, n_pairs, false, inf)) return rc;
+    const size_t R = h->cfg.max_rows, P = n_pairs;
+    if (written) VITVS_HIP_CHECK(hipMemcpy(out, ws, P * R * width * sizeof(V), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < P; ++b) {
+        const size_t n = written ? feature_rows(h, inf, b) : 0;
+        memset(out + (b * R + n) * width, 0, (R - n) * width * sizeof(V));
+    }
     return 0;
 }
 
@@ -1134,6 +1203,8 @@ int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, 
                                void* stream) {
     if (!h || !nn_1 || !nn_2 || !sim_1 || !K || !v_c || !status) return set_err(h, -1, "null argument");
     if ((size_t)T > h->best_elems) return set_err(h, -3, "T exceeds the handle's workspace");
+    const int np = call_num_pairs(h, num_pairs);
+    if (int rc = check_selection(h, T, select_mode, selection, h->st_nsel, np)) return rc;
     if (int rc = check_interaction(h, 1, T)) return rc;
     DeviceScope dev(h);
     hipStream_t st = as_stream(stream);
@@ -1141,9 +1212,7 @@ int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, 
     int rc = launch_encode_best(nn_1, nn_2, sim_1, T, h->row_best, h->col_best, st);
     if (rc) return set_err(h, rc, "encode launch failed");
     VITVS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->st_nsel), n_selected, 1, st));
-    RefineSpec rf;
-    rf.table = offsets;
-    return run_servo(h, 1, T, Z_mm, K, select_mode, call_num_pairs(h, num_pairs), selection, h->st_nsel, v_c, status, st, rf);
+    return run_servo(h, 1, T, Z_mm, K, select_mode, np, selection, h->st_nsel, v_c, status, st, RefineSpec{offsets});
 }
 
 // One update = forward of the call's image list (desired frames first, then current frames) + the tail
@@ -1156,33 +1225,29 @@ struct UpdateArgs {
     const int32_t *selection, *n_selected;
     double* v_c;
     int32_t* status;
-    // host-pointer entry point: the caller's depth image is copied into the pinned staging block on the HOST, after the
+    // host-pointer entry point: the caller's depth image (late_src) is copied into the pinned staging block on the HOST, after the
     // forward's launches have been enqueued and before the law's launch (the only kernel that reads it): off the critical path
     // Only the pixels the law can ask for are copied: it looks the depth up at the patch CENTRE of a current-frame token
-    // (vitvs_v2.py:511-553, 566-586), i.e. at one of T fixed sites of the image (late_sites: linear pixel indices, the handle's
-    // depth_sites), so T 2-byte gathers stand for the 614 KB image.
+    // (vitvs_v2.py:511-553, 566-586), i.e. at one of T fixed sites of the image (linear pixel indices, the handle's depth_sites),
+    // so T 2-byte gathers stand for the 614 KB image.  A law whose plan reads the depth anywhere (a refined match can lie on any
+    // pixel) has the whole image copied; one that does not read it (L(s*, Z*)) none of it.
     const uint16_t* late_src = nullptr;
-    uint16_t* late_dst = nullptr;
-    // (option "subpatch": a refined match can lie on any pixel, so the whole image is copied: late_sites == nullptr)
-    const int32_t* late_sites = nullptr;
-    int late_count = 0, late_pairs = 0;
-    size_t late_stride = 0;                     // pixels per depth image
+    ServoPlan law;                              // the law of this update (velocity_update)
 };
-static inline void late_inputs(const UpdateArgs& u) {
-    if (!u.late_src) return;
-    for (int b = 0; b < u.late_pairs; ++b) {
-        const uint16_t* src = u.late_src + (size_t)b * u.late_stride;
-        uint16_t* dst = u.late_dst + (size_t)b * u.late_stride;
-        if (!u.late_sites) { memcpy(dst, src, u.late_stride * sizeof(uint16_t)); continue; }
-        for (int i = 0; i < u.late_count; ++i) dst[u.late_sites[i]] = src[u.late_sites[i]];
+static inline void late_inputs(vitvs_handle* h, const UpdateArgs& u) {
+    if (!u.late_src || !u.law.reads_depth) return;
+    const size_t stride = (size_t)h->cfg.u_max * h->cfg.v_max;   // pixels per depth image
+    for (int b = 0; b < u.n_pairs; ++b) {
+        const uint16_t* src = u.late_src + (size_t)b * stride;
+        uint16_t* dst = h->hs.depth + (size_t)b * stride;
+        if (u.law.depth_anywhere) { memcpy(dst, src, stride * sizeof(uint16_t)); continue; }
+        for (const int32_t site : h->depth_sites) dst[site] = src[site];
     }
 }
 
 static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) {
     const int n_des = u.des_shared ? 1 : u.n_pairs, n_img = n_des + u.n_pairs;
-    RefineSpec rf;
-    rf.from_forward = h->subpatch != 0;
-    rf.des_shared = u.des_shared ? 1 : 0;
+    const RefineSpec rf{nullptr, h->subpatch != 0, u.des_shared ? 1 : 0};
     h->desc_keys = u.n_pairs * h->T;
     // cached goal: only the current frames (images n_des .. n_img - 1 of the call's list) go through the network
     int rc = u.I_des ? forward_chain(h, 0, n_img, n_des, u.I_des, u.I_cur, h->part, st)
@@ -1199,7 +1264,7 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
         rc = launch_gram_step(gp, i, go, st);
     }
     if (rc) return set_err(h, rc, "correspondence launch failed");
-    late_inputs(u);
+    late_inputs(h, u);
     return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st, rf);
 }
 
@@ -1213,7 +1278,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
         VITVS_HIP_CHECK(hipMemcpyAsync(h->st_sel, u.selection, sel_elems * 4, hipMemcpyDefault, st));
     if (u.select_mode == VITVS_SELECT_EXPLICIT && u.n_selected && u.n_selected != h->st_nsel)
         VITVS_HIP_CHECK(hipMemcpyAsync(h->st_nsel, u.n_selected, (size_t)u.n_pairs * 4, hipMemcpyDefault, st));
-    late_inputs(u);                             // a replay has no seam to do this later: before the launch
+    late_inputs(h, u);                          // a replay has no seam to do this later: before the launch
     if (u.selection) u.selection = h->st_sel;
     if (u.n_selected) u.n_selected = h->st_nsel;
     const std::vector<uintptr_t> key = {(uintptr_t)u.n_pairs, (uintptr_t)u.I_cur, (uintptr_t)u.I_des, (uintptr_t)u.des_shared,
@@ -1254,8 +1319,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
         ge = &h->graphs.back();
     }
     ge->last_use = ++h->graph_clock;
-    h->last_pairs = u.n_pairs; h->last_T = h->T; h->last_robust = h->robust_iters > 0; h->last_refine = h->subpatch != 0;
-    h->last_goalz = h->interaction != 0;
+    note_law(h, u.n_pairs, h->T, u.law);        // (a replay runs none of run_servo's host code)
     VITVS_HIP_CHECK(hipGraphLaunch(ge->exec, st));
     return 0;
 }
@@ -1294,11 +1358,10 @@ static int velocity_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
     if (!u.I_cur || !u.K || !u.v_c || !u.status) return set_err(h, -1, "null argument");   // I_des NULL: the cached goal
     if (u.n_pairs <= 0 || u.n_pairs > h->cfg.max_pairs) return set_err(h, -3, "n_pairs exceeds max_pairs");
     u.num_pairs = call_num_pairs(h, u.num_pairs);
-    if (u.num_pairs > h->cfg.max_rows) return set_err(h, -5, "num_pairs exceeds max_rows");
-    if (u.select_mode != VITVS_SELECT_DENSE && !u.selection) return set_err(h, -5, "selection array required for this mode");
-    if (u.select_mode == VITVS_SELECT_EXPLICIT && !u.n_selected) return set_err(h, -5, "n_selected required for EXPLICIT");
+    if (int rc = check_selection(h, h->T, u.select_mode, u.selection, u.n_selected, u.num_pairs)) return rc;
     if (vitvs_weights_ready(h) != 0) return set_err(h, -4, "weights not fully loaded: " + h->err);
     if (int rc = check_interaction(h, u.n_pairs, h->T)) return rc;
+    if (int rc = plan_law(h, h->T, RefineSpec{nullptr, h->subpatch != 0, u.des_shared ? 1 : 0}, u.law)) return rc;
     // The goal cache is host-side state of the handle: it is checked and invalidated here, on every call, and never
     // inside the body that a hipGraph captures (a replay runs none of the body's host code).
     if (!u.I_des && h->goal_frames != (u.des_shared ? 1 : u.n_pairs))
@@ -1331,12 +1394,9 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
                            int32_t* status) {
     if (!h || !I_cur || !K || !v_c || !status) return set_err(h, -1, "null argument");   // I_des NULL: the cached goal
     if (n_pairs <= 0 || n_pairs > h->cfg.max_pairs) return set_err(h, -3, "n_pairs exceeds max_pairs");
-    const vitvs_config& c = h->cfg;
     const int np = call_num_pairs(h, num_pairs);
-    if (np > c.max_rows) return set_err(h, -5, "num_pairs exceeds max_rows");
-    if (select_mode == VITVS_SELECT_EXPLICIT && (!selection || !n_selected)) return set_err(h, -5, "EXPLICIT selection needs ids and counts");
-    if (select_mode == VITVS_SELECT_ORDER && !selection) return set_err(h, -5, "ORDER selection needs a visiting order");
-    if (int rc = check_interaction(h, n_pairs, h->T)) return rc;   // (before the frames are staged)
+    if (int rc = check_selection(h, h->T, select_mode, selection, n_selected, np)) return rc;   // (before the frames are staged)
+    if (int rc = check_interaction(h, n_pairs, h->T)) return rc;
     DeviceScope dev(h);
     if (int rc = ensure_host_stage(h)) return rc;
     vitvs_handle::HostStage& hs = h->hs;
@@ -1355,28 +1415,12 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     }
     if (rc) return set_err(h, rc, "frame staging launch failed");
     memcpy(hs.K, K, (size_t)n_pairs * 4 * sizeof(double));
-    if (select_mode == VITVS_SELECT_EXPLICIT) {
-        memcpy(hs.sel, selection, (size_t)n_pairs * np * 4);
-        memcpy(hs.nsel, n_selected, (size_t)n_pairs * 4);
-    } else if (select_mode == VITVS_SELECT_ORDER) {
-        memcpy(hs.sel, selection, (size_t)n_pairs * h->T * 4);
-    }
+    stage_selection(h, n_pairs, h->T, select_mode, selection, n_selected, np);
     UpdateArgs u{n_pairs, des_shared, select_mode, np, h->st_cur, I_des ? h->st_des : nullptr, Z_mm ? hs.depth : nullptr, hs.K,
-                 hs.sel, hs.nsel, hs.vc, hs.status};
-    if (Z_mm && h->interaction != IL_DESIRED) {   // L(s*, Z*) never reads the current depth: nothing to stage
-        u.late_src = Z_mm; u.late_dst = hs.depth; u.late_count = (int)h->depth_sites.size();
-        u.late_sites = h->subpatch ? nullptr : h->depth_sites.data();
-        u.late_pairs = n_pairs; u.late_stride = (size_t)c.u_max * c.v_max;
-    }
+                 hs.sel, hs.nsel, hs.vc, hs.status, Z_mm};
     rc = velocity_update(h, u, st);
+    if (!rc) rc = finish_host_call(h, n_pairs, v_c, status);
     if (rc) return rc;
-    // the detail block of this call -> the pinned block, one copy launch of 16-byte stores (measured: the law's kernel writing
-    // its ~20 small detail stores straight into host memory cost 60 us per update; one coalesced copy costs 3)
-    rc = launch_copy16(h->det_block, hs.det, h->det_bytes, st);
-    if (rc) return set_err(h, rc, "detail copy launch failed");
-    if (int w = wait_stream(st)) return w;
-    memcpy(v_c, hs.vc, (size_t)n_pairs * 6 * sizeof(double));
-    memcpy(status, hs.status, (size_t)n_pairs * 4);
     h->details_pinned = true;
     h->host_tables = vitvs_handle::HostTables{n_pairs, h->T, Z_mm != nullptr, des_shared ? 1 : 0};
     return 0;
@@ -1394,74 +1438,44 @@ int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t* selectio
         return set_err(h, -5, "vitvs_reselect follows a host-pointer velocity call on the same handle (vitvs_compute_velocity)");
     const int n_pairs = h->host_tables.n_pairs, T = h->host_tables.T;
     const int np = call_num_pairs(h, num_pairs);
-    if (np > h->cfg.max_rows) return set_err(h, -5, "num_pairs exceeds max_rows");
-    if (select_mode == VITVS_SELECT_EXPLICIT && (!selection || !n_selected)) return set_err(h, -5, "EXPLICIT selection needs ids and counts");
-    if (select_mode == VITVS_SELECT_ORDER && !selection) return set_err(h, -5, "ORDER selection needs a visiting order");
+    if (int rc = check_selection(h, T, select_mode, selection, n_selected, np)) return rc;
     if (int rc = check_interaction(h, n_pairs, T)) return rc;
     DeviceScope dev(h);
     vitvs_handle::HostStage& hs = h->hs;
-    if (select_mode == VITVS_SELECT_EXPLICIT) {
-        memcpy(hs.sel, selection, (size_t)n_pairs * np * 4);
-        memcpy(hs.nsel, n_selected, (size_t)n_pairs * 4);
-    } else if (select_mode == VITVS_SELECT_ORDER) {
-        memcpy(hs.sel, selection, (size_t)n_pairs * T * 4);
-    }
-    RefineSpec rf;
-    rf.from_forward = h->subpatch != 0;
-    rf.des_shared = h->host_tables.des_shared;
-    int rc = run_servo(h, n_pairs, T, h->host_tables.have_depth ? hs.depth : nullptr, hs.K, select_mode, np, hs.sel, hs.nsel, hs.vc,
-                       hs.status, h->host_stream, rf);
-    if (rc) return rc;
-    rc = launch_copy16(h->det_block, hs.det, h->det_bytes, h->host_stream);
-    if (rc) return set_err(h, rc, "detail copy launch failed");
-    if (int w = wait_stream(h->host_stream)) return w;
-    memcpy(v_c, hs.vc, (size_t)n_pairs * 6 * sizeof(double));
-    memcpy(status, hs.status, (size_t)n_pairs * 4);
-    return 0;
+    stage_selection(h, n_pairs, T, select_mode, selection, n_selected, np);
+    const int rc = run_servo(h, n_pairs, T, h->host_tables.have_depth ? hs.depth : nullptr, hs.K, select_mode, np, hs.sel, hs.nsel,
+                             hs.vc, hs.status, h->host_stream, RefineSpec{nullptr, h->subpatch != 0, h->host_tables.des_shared});
+    return rc ? rc : finish_host_call(h, n_pairs, v_c, status);
 }
 
 int vitvs_last_details(vitvs_handle* h, int32_t n_pairs, int32_t* nn_1, int32_t* nn_2, float* sim_1, int32_t* info,
                        int32_t* selected, int32_t* s_uv, double* feat, double* L) {
     if (!h) return set_err(h, -1, "null argument");
-    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
     DeviceScope dev(h);
-    const size_t T = h->last_T, R = h->cfg.max_rows, P = n_pairs, PM = h->cfg.max_pairs;
+    const size_t T = h->last_T, R = h->cfg.max_rows, P = n_pairs;
     // after a host-pointer call the feature rows are already in host memory (the handle's pinned block): a caller that asks
     // for those alone (the reference's detect_features return value: s_uv*, s_uv, the selected similarities) costs no HIP call
     const bool pinned = h->details_pinned;
-    const unsigned char* pd = h->hs.det;
-    if (!pinned || selected || L) VITVS_HIP_CHECK(hipDeviceSynchronize());
-    const size_t o_nn = PM * 32 + PM * R * 48;              // nn_1 | nn_2 | sim_1 behind info | s_uv | feat (detail_pointers)
-    if (nn_1) {
-        if (pinned) memcpy(nn_1, pd + o_nn, P * T * 4);
-        else VITVS_HIP_CHECK(hipMemcpy(nn_1, h->nn1, P * T * 4, hipMemcpyDeviceToHost));
-    }
-    if (nn_2) {
-        if (pinned) memcpy(nn_2, pd + o_nn + h->best_elems * 4, P * T * 4);
-        else VITVS_HIP_CHECK(hipMemcpy(nn_2, h->nn2, P * T * 4, hipMemcpyDeviceToHost));
-    }
-    if (sim_1) {
-        if (pinned) memcpy(sim_1, pd + o_nn + 2 * h->best_elems * 4, P * T * 4);
-        else VITVS_HIP_CHECK(hipMemcpy(sim_1, h->sim1, P * T * 4, hipMemcpyDeviceToHost));
-    }
-    std::vector<int32_t> inf(P * 8);
-    if (pinned) memcpy(inf.data(), pd, P * 8 * 4);
-    else VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> inf;
+    if (int rc = last_info(h, n_pairs, pinned, inf)) return rc;
+    if (pinned && (selected || L)) VITVS_HIP_CHECK(hipDeviceSynchronize());
+    // a part of the detail block: from its image in the pinned block (same layout, detail_pointers) or from the device
+    auto part = [&](void* dst, const void* src, size_t bytes) -> int {
+        if (dst && pinned) memcpy(dst, h->hs.det + (static_cast<const unsigned char*>(src) - h->det_block), bytes);
+        else if (dst) VITVS_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    int rc = part(nn_1, h->nn1, P * T * 4);
+    if (!rc) rc = part(nn_2, h->nn2, P * T * 4);
+    if (!rc) rc = part(sim_1, h->sim1, P * T * 4);
+    if (!rc) rc = part(s_uv, h->s_uv, P * R * 16);
+    if (!rc) rc = part(feat, h->feat, P * R * 32);
+    if (rc) return rc;
     if (info) memcpy(info, inf.data(), P * 8 * 4);
     if (selected) VITVS_HIP_CHECK(hipMemcpy(selected, h->sel_out, P * R * 4, hipMemcpyDeviceToHost));
-    if (s_uv) {
-        if (pinned) memcpy(s_uv, pd + PM * 32, P * R * 16);
-        else VITVS_HIP_CHECK(hipMemcpy(s_uv, h->s_uv, P * R * 4 * 4, hipMemcpyDeviceToHost));
-    }
-    if (feat) {
-        if (pinned) memcpy(feat, pd + PM * 32 + PM * R * 16, P * R * 32);
-        else VITVS_HIP_CHECK(hipMemcpy(feat, h->feat, P * R * 4 * 8, hipMemcpyDeviceToHost));
-    }
     if (L) VITVS_HIP_CHECK(hipMemcpy(L, h->Lws, P * 7 * 2 * R * 8, hipMemcpyDeviceToHost));
-    // The kernel writes the first n_feature_rows (info[1]) rows of a pair; the workspace rows behind them may still hold
-    // an earlier, larger call's values.  The copies handed out are defined everywhere: selected = -1, everything else 0.
     for (size_t b = 0; b < P; ++b) {
-        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
+        const size_t n = feature_rows(h, inf, b);
         for (size_t k = n; k < R; ++k) {
             if (selected) selected[b * R + k] = -1;
             if (s_uv) memset(s_uv + (b * R + k) * 4, 0, 16);
@@ -1469,6 +1483,22 @@ int vitvs_last_details(vitvs_handle* h, int32_t n_pairs, int32_t* nn_1, int32_t*
         }
         if (L)
             for (size_t c = 0; c < 7; ++c) memset(L + (b * 7 + c) * 2 * R + 2 * n, 0, (2 * R - 2 * n) * 8);
+    }
+    return 0;
+}
+
+// An option that captured updates depend on: those of the control law (they hold the previous law's kernel and arguments) and
+// the tile plan hint.  staged_depth: the pinned depth image of the last host-pointer call holds only what the previous setting
+// reads, so vitvs_reselect may not build on it
+static int set_captured_option(vitvs_handle* h, int& option, int value, bool staged_depth) {
+    if (value == option) return 0;
+    DeviceScope dev(h);
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    drop_graphs(h);
+    option = value;
+    if (staged_depth) {
+        h->details_pinned = false;
+        h->host_tables = vitvs_handle::HostTables{};
     }
     return 0;
 }
@@ -1489,48 +1519,16 @@ int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value) {
     }
     if (nm == "in_flight") {
         if (value < 1 || value > 64) return set_err(h, -5, "in_flight takes 1 .. 64");
-        if ((int)value != h->in_flight) {       // captured updates hold the previous plan's launches
-            DeviceScope dev(h);
-            VITVS_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(h);
-            h->in_flight = (int)value;
-        }
-        return 0;
+        return set_captured_option(h, h->in_flight, (int)value, false);   // captured updates hold the previous plan's launches
     }
-    if (nm == "robust_law") {
-        if (value < 0 || value > 16) return set_err(h, -5, "robust_law takes 0 (the plain law) or 1 .. 16 re-weightings");
-        if ((int)value != h->robust_iters) {    // captured updates hold the previous law's kernel and arguments
-            DeviceScope dev(h);
-            VITVS_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(h);
-            h->robust_iters = (int)value;
-        }
-        return 0;
-    }
-    if (nm == "subpatch") {
-        if (value != 0 && value != 1) return set_err(h, -5, "subpatch takes 0 (patch centres) or 1 (refined matches)");
-        if ((int)value != h->subpatch) {        // captured updates hold the previous law's kernel and arguments; the pinned depth
-            DeviceScope dev(h);                 // image of the last host-pointer call holds only what the previous setting reads
-            VITVS_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(h);
-            h->subpatch = (int)value;
-            h->details_pinned = false;
-            h->host_tables = vitvs_handle::HostTables{};
-        }
-        return 0;
-    }
-    if (nm == "interaction") {
-        if (value < IL_CURRENT || value > IL_MEAN)
-            return set_err(h, -5, "interaction takes 0 (current, L(s, Z)), 1 (desired, L(s*, Z*)) or 2 (their mean)");
-        if ((int)value != h->interaction) {     // captured updates hold the previous law's kernel and arguments; the pinned depth
-            DeviceScope dev(h);                 // image of the last host-pointer call holds only what the previous setting reads
-            VITVS_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(h);
-            h->interaction = (int)value;
-            h->details_pinned = false;
-            h->host_tables = vitvs_handle::HostTables{};
-        }
-        return 0;
+    const struct { const char* name; int* option; int lo, hi; bool staged_depth; const char* takes; } law[] = {
+        {"robust_law", &h->robust_iters, 0, 16, false, "robust_law takes 0 (the plain law) or 1 .. 16 re-weightings"},
+        {"subpatch", &h->subpatch, 0, 1, true, "subpatch takes 0 (patch centres) or 1 (refined matches)"},
+        {"interaction", &h->interaction, IL_CURRENT, IL_MEAN, true, "interaction takes 0 (current, L(s, Z)), 1 (desired, L(s*, Z*)) or 2 (their mean)"}};
+    for (const auto& o : law) {
+        if (nm != o.name) continue;
+        if (value < o.lo || value > o.hi) return set_err(h, -5, o.takes);
+        return set_captured_option(h, *o.option, (int)value, o.staged_depth);
     }
     return set_err(h, -5, "unknown option " + nm);
 }
@@ -1582,64 +1580,29 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
 
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
-    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
-    DeviceScope dev(h);
-    const size_t R = h->cfg.max_rows, P = n_pairs;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());
-    if (!h->last_goalz) {
-        memset(z, 0, P * R * sizeof(double));
-        return 0;
-    }
-    std::vector<int32_t> inf(P * 8);
-    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(z, h->zgoal_ws, P * R * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < P; ++b) {
-        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
-        for (size_t k = n; k < R; ++k) z[b * R + k] = 0.0;
-    }
-    return 0;
+    return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
 }
 
 int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w) {
     if (!h || !w) return set_err(h, -1, "null argument");
-    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    if (h->last_law.robust) return last_row_output(h, n_pairs, true, h->Wws, 1, w);
     DeviceScope dev(h);
-    const size_t R = h->cfg.max_rows, P = n_pairs;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());
-    std::vector<int32_t> inf(P * 8);
-    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
-    if (h->last_robust) VITVS_HIP_CHECK(hipMemcpy(w, h->Wws, P * R * 8, hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < P; ++b) {
-        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
-        if (!h->last_robust) {
-            // the plain law: weight 1 on every live pair; fewer than 4 matches of a short selection leave none (TOO_FEW)
-            size_t live = std::min<size_t>(n, (size_t)std::max(inf[b * 8 + 3], 0));
-            if (live < n && live < 4) live = 0;
-            for (size_t k = 0; k < n; ++k) w[b * R + k] = k < live ? 1.0 : 0.0;
-        }
-        for (size_t k = n; k < R; ++k) w[b * R + k] = 0.0;
+    std::vector<int32_t> inf;
+    if (int rc = last_info(h, n_pairs, false, inf)) return rc;
+    const size_t R = h->cfg.max_rows;
+    for (size_t b = 0; b < (size_t)n_pairs; ++b) {
+        // the plain law: weight 1 on every live pair; fewer than 4 matches of a short selection leave none (TOO_FEW)
+        const size_t n = feature_rows(h, inf, b);
+        size_t live = std::min<size_t>(n, (size_t)std::max(inf[b * 8 + 3], 0));
+        if (live < n && live < 4) live = 0;
+        for (size_t k = 0; k < R; ++k) w[b * R + k] = k < live ? 1.0 : 0.0;
     }
     return 0;
 }
 
 int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets) {
     if (!h || !offsets) return set_err(h, -1, "null argument");
-    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
-    DeviceScope dev(h);
-    const size_t R = h->cfg.max_rows, P = n_pairs;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());
-    if (!h->last_refine) {
-        memset(offsets, 0, P * R * 2 * sizeof(float));
-        return 0;
-    }
-    std::vector<int32_t> inf(P * 8);
-    VITVS_HIP_CHECK(hipMemcpy(inf.data(), h->info, P * 8 * 4, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(offsets, h->off_ws, P * R * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < P; ++b) {
-        const size_t n = std::min<size_t>(R, (size_t)std::max(inf[b * 8 + 1], 0));
-        for (size_t k = n; k < R; ++k) offsets[(b * R + k) * 2] = offsets[(b * R + k) * 2 + 1] = 0.f;
-    }
-    return 0;
+    return last_row_output(h, n_pairs, h->last_law.refine, h->off_ws, 2, offsets);
 }
 
 int vitvs_timing_enable(vitvs_handle* h, int32_t on) {
@@ -1737,6 +1700,14 @@ int vitvs_op_gram_plan(int32_t precision, int32_t binned, int32_t T, int32_t D, 
     out[0] = pl.form; out[1] = pl.rows; out[2] = pl.cols; out[3] = pl.kgroups; out[4] = pl.hb; out[5] = pl.per_xcd;
     out[6] = pl.split;
     return pl.rows ? 0 : -2;
+}
+int vitvs_op_servo_plan(int32_t T, int32_t max_rows, int32_t robust_iters, int32_t refine_source, int32_t interaction, int32_t* out) {
+    if (!out) return -1;
+    ServoPlan pl;
+    const int rc = plan_servo(T, max_rows, robust_iters, refine_source, interaction, &pl);
+    out[0] = pl.robust; out[1] = pl.refine; out[2] = pl.goalz; out[3] = (int32_t)pl.lds; out[4] = pl.source;
+    out[5] = pl.reads_depth; out[6] = pl.depth_anywhere;
+    return rc;
 }
 // the arg-max keys of n_pairs pairs -> nn_1 / nn_2 / sim_1 [n_pairs][T], as the law's kernel decodes them
 static int decode_pairs(const unsigned long long* row_best, const unsigned long long* col_best, int T, int n_pairs, int32_t* nn_1,

@@ -332,7 +332,25 @@ struct ServoArgs {
     const uint16_t* zgoal;    // [n_goal][T + 1] mm: goal depth at every token's patch centre, entry T at pixel (0, 0)
     double* zgoal_out;        // [n_pairs][max_rows] Z* of every feature row in metres (output)
 };
-int launch_servo(const ServoArgs& a, hipStream_t stream);
+// One law launch, decided by plan_servo and carried out by launch_servo.  RefineSource: where servo_kernel<., REFINE, .> takes its
+// sub-patch offsets from (the codes are ABI: vitvs_op_servo_plan): a given table (off_in), the raw Gram with the squared norms
+// (G, sq: GRAM_STENCIL), or the normalised descriptors (dn: every other form)
+enum RefineSource : int { RS_OFF = 0, RS_TABLE, RS_GRAM, RS_DESC };
+struct ServoPlan {
+    int T = 0, max_rows = 0, robust_iters = 0;   // what the plan was made for: launch_servo refuses other arguments
+    Interaction interaction = IL_CURRENT;
+    RefineSource source = RS_OFF;
+    bool robust = false, refine = false, goalz = false;   // servo_kernel<robust, refine, goalz>; writes W_ws, off_out, zgoal_out
+    size_t lds = 0;                // dynamic LDS bytes
+    bool lds_opt_in = false;       // ... beyond 64 KiB: the instantiation opts in (per device) before its launch
+    bool reads_depth = true;       // the current depth image takes part (not IL_DESIRED): a host-pointer call stages it,
+    bool depth_anywhere = false;   // whole (a refined match can lie on any pixel) or at the T patch centres only
+};
+// -2: an argument out of range (T, max_rows < 1; robust_iters outside 0 .. 16; source; interaction), -3: more than 160 KiB of LDS
+int plan_servo(int T, int max_rows, int robust_iters, int source, int interaction, ServoPlan* plan);
+// -2 also for arguments that are not the plan's, a source whose pointers are missing or not the first the kernel finds (off_in,
+// then G, then dn), an output of the plan without a place
+int launch_servo(const ServoPlan& plan, const ServoArgs& a, hipStream_t stream);
 // table [n_goal][T + 1] <- goal depth images Z [n_goal][depth_h][depth_w] (mm) at the sites the law reads; `geom` carries
 // the geometry fields of a law call (T, grid, scale_*, half_f, depth_h, depth_w)
 int launch_goal_depth(const ServoArgs& geom, const uint16_t* Z, int n_goal, uint16_t* table, hipStream_t stream);

@@ -801,42 +801,56 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     }
 }
 
-static size_t servo_lds_bytes(const ServoArgs& a, bool robust, bool refine) {
-    size_t lds = servo_f64_offset(a.T, a.max_rows) + (size_t)7 * kLdsRows * 8 + (40 + 8 * 27) * 8;
-    if (robust) lds += ((size_t)7 * kLdsRows + kLdsRows / 2 + a.max_rows) * 8;
-    if (refine) lds += (size_t)a.max_rows * 2 * 4;
-    return lds;
+int plan_servo(int T, int max_rows, int robust_iters, int source, int interaction, ServoPlan* plan) {
+    if (!plan || T <= 0 || max_rows <= 0 || robust_iters < 0 || robust_iters > 16 || source < RS_OFF || source > RS_DESC ||
+        interaction < IL_CURRENT || interaction > IL_MEAN)
+        return -2;
+    ServoPlan& p = *plan;
+    p.T = T; p.max_rows = max_rows; p.robust_iters = robust_iters;
+    p.interaction = (Interaction)interaction; p.source = (RefineSource)source;
+    p.robust = robust_iters > 0; p.refine = source != RS_OFF; p.goalz = interaction != IL_CURRENT;
+    p.lds = servo_f64_offset(T, max_rows) + (size_t)7 * kLdsRows * 8 + (40 + 8 * 27) * 8;
+    if (p.robust) p.lds += ((size_t)7 * kLdsRows + kLdsRows / 2 + max_rows) * 8;
+    if (p.refine) p.lds += (size_t)max_rows * 2 * 4;
+    p.lds_opt_in = p.lds > 64 * 1024;   // (dense selection over thousands of tokens)
+    p.reads_depth = interaction != IL_DESIRED;
+    p.depth_anywhere = p.refine;
+    return p.lds > 160 * 1024 ? -3 : 0;
 }
 
-template <bool ROBUST, bool REFINE, bool GOALZ>
-static int launch_servo_as(const ServoArgs& a, size_t lds, hipStream_t stream) {
-    // > 64 KiB of dynamic LDS (dense selection over thousands of tokens): per-device opt-in, per instantiation
-    static std::atomic<unsigned long long> raised{0};
-    if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(&servo_kernel<ROBUST, REFINE, GOALZ>), 160 * 1024, raised)) return -3;
-    launch(servo_kernel<ROBUST, REFINE, GOALZ>, dim3(a.n_pairs), dim3(256), lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth,
-           a.T, a.mode, a.sel_stride, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_servo(const ServoArgs& a, hipStream_t stream) {
-    if (a.n_pairs <= 0 || a.T <= 0 || a.grid * a.grid != a.T || a.max_rows < a.num_pairs || a.num_pairs <= 0) return -2;
-    if (a.mode == SEL_DENSE && a.max_rows < a.T) return -2;
-    if (a.robust_iters < 0 || a.robust_iters > 16 || (a.robust_iters > 0 && !a.W_ws)) return -2;
-    // the refinement needs a place for its offsets and one source of them: a table, the raw Gram with the squared norms, or
-    // the normalised descriptors (16-byte rows)
-    if (a.refine && (!a.off_out || !(a.off_in || (a.G && a.sq) || (a.dn && a.Dp > 0 && a.Dp % 4 == 0)))) return -2;
-    // the goal-side interaction matrices need the goal-depth table (T + 1 entries per goal image) and a place for Z*
-    if (a.interaction < IL_CURRENT || a.interaction > IL_MEAN) return -2;
-    if (a.interaction != IL_CURRENT && (!a.zgoal || !a.zgoal_out || (a.zgoal_stride != 0 && a.zgoal_stride != a.T + 1))) return -2;
-    const bool robust = a.robust_iters > 0, refine = a.refine != 0;
-    const size_t lds = servo_lds_bytes(a, robust, refine);
-    if (lds > 160 * 1024) return -3;
-    if (a.interaction != IL_CURRENT) {
-        if (robust) return refine ? launch_servo_as<true, true, true>(a, lds, stream) : launch_servo_as<true, false, true>(a, lds, stream);
-        return refine ? launch_servo_as<false, true, true>(a, lds, stream) : launch_servo_as<false, false, true>(a, lds, stream);
+// The plan's instantiation: each level turns one of its booleans into a template argument (goalz first: the order in which the
+// eight kernels are instantiated, and so laid out in the code object, stays what it was)
+template <bool... B>
+static int launch_servo_as(const ServoPlan& p, const ServoArgs& a, hipStream_t stream) {
+    if constexpr (sizeof...(B) < 3) {
+        const bool next[3] = {p.goalz, p.robust, p.refine};
+        return next[sizeof...(B)] ? launch_servo_as<B..., true>(p, a, stream) : launch_servo_as<B..., false>(p, a, stream);
+    } else {
+        constexpr bool b[3] = {B...};
+        const auto kernel = servo_kernel<b[1], b[2], b[0]>;
+        // > 64 KiB of dynamic LDS: per-device opt-in, per instantiation
+        static std::atomic<unsigned long long> raised{0};
+        if (p.lds_opt_in && (p.lds > 160 * 1024 || raise_lds_limit(reinterpret_cast<const void*>(kernel), 160 * 1024, raised))) return -3;
+        launch(kernel, dim3(a.n_pairs), dim3(256), p.lds, stream, a.row_best, a.col_best, a.K, a.selection, a.depth, a.T, a.mode,
+               a.sel_stride, a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    if (robust) return refine ? launch_servo_as<true, true, false>(a, lds, stream) : launch_servo_as<true, false, false>(a, lds, stream);
-    return refine ? launch_servo_as<false, true, false>(a, lds, stream) : launch_servo_as<false, false, false>(a, lds, stream);
+}
+
+int launch_servo(const ServoPlan& p, const ServoArgs& a, hipStream_t stream) {
+    if (!p.lds || a.T != p.T || a.max_rows != p.max_rows || a.robust_iters != p.robust_iters ||
+        a.interaction != p.interaction || (a.refine != 0) != p.refine)
+        return -2;
+    if (a.n_pairs <= 0 || a.grid * a.grid != a.T || a.max_rows < a.num_pairs || a.num_pairs <= 0) return -2;
+    if (a.mode == SEL_DENSE && a.max_rows < a.T) return -2;
+    if (p.robust && !a.W_ws) return -2;
+    // the refinement needs a place for its offsets and its source: a table, the raw Gram with the squared norms, or the
+    // normalised descriptors (16-byte rows)
+    const bool table = a.off_in != nullptr, gram = !table && a.G && a.sq, desc = !table && !a.G && a.dn && a.Dp > 0 && a.Dp % 4 == 0;
+    if (p.refine && (!a.off_out || !(p.source == RS_TABLE ? table : p.source == RS_GRAM ? gram : desc))) return -2;
+    // the goal-side interaction matrices need the goal-depth table (T + 1 entries per goal image) and a place for Z*
+    if (p.goalz && (!a.zgoal || !a.zgoal_out || (a.zgoal_stride != 0 && a.zgoal_stride != a.T + 1))) return -2;
+    return launch_servo_as<>(p, a, stream);
 }
 
 // Goal depth of every token (vitvs_set_goal_depth_dev): table[g][t] = Z[g] at token t's patch centre (token_pixel; 0 outside the

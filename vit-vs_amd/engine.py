@@ -38,7 +38,8 @@ class Engine:
             raise VitvsError("no HIP device: the ViT-VS hot path has no CPU fallback")
         self.lib = _lib.load()
         self.cfg = cfg
-        self.params = params or ServoParams(dino_input_size=cfg.img_size)
+        given = params or ServoParams(dino_input_size=cfg.img_size)
+        self.params = given.replace(robust_iterations=0, subpatch=False, interaction="current")   # a fresh handle's law: apply_law_params
         # "f16x2": split-f16 (include/vitvs.h VITVS_F16X2) — fp32-class results on the f16 matrix cores, the parity mode at servo rate
         self.precision = {"fp32": _lib.F32, "f32": _lib.F32, "bf16": _lib.BF16, "fp16": _lib.F16, "f16": _lib.F16,
                           "f16x2": _lib.F16X2, "split-f16": _lib.F16X2}[precision]
@@ -77,12 +78,7 @@ class Engine:
         self.tokens = self.lib.vitvs_tokens(self.handle)
         self.desc_dim = self.lib.vitvs_desc_dim(self.handle)
         assert self.tokens == cfg.tokens and self.lib.vitvs_register_tokens(self.handle) == cfg.registers
-        if self.params.robust_iterations:
-            self.set_option("robust_law", self.params.robust_iterations)
-        if self.params.subpatch:
-            self.set_option("subpatch", 1)
-        if self.params.interaction != "current":
-            self.set_option("interaction", INTERACTIONS.index(self.params.interaction))
+        self.apply_law_params(given)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -383,6 +379,24 @@ class Engine:
         sel, cnt = self._selection_args(mode, selection, n, self.tokens, k)
         return self.compute_velocity_dev(cur, des, z, kk, mode, sel, cnt, des_shared, num_pairs=k)
 
+    def _selection_arrays_host(self, mode, selection, n, k):
+        """The selection of a host-pointer call as the int32 numpy arrays the C ABI takes: (ids [n, k], counts [n]) for
+        EXPLICIT, (visiting order [n, T], None) for ORDER, (None, None) for DENSE."""
+        if mode == _lib.SELECT_EXPLICIT:
+            rows = selection if isinstance(selection, (list, tuple)) else [selection]
+            if len(rows) != n:
+                raise VitvsError("one id list per pair expected")
+            sel = np.zeros((n, k), np.int32)
+            cnt = np.zeros(n, np.int32)
+            for b, ids in enumerate(rows):
+                ids = np.asarray(ids, np.int32).reshape(-1)[:k]
+                sel[b, :ids.size] = ids
+                cnt[b] = ids.size
+            return sel, cnt
+        if mode == _lib.SELECT_ORDER:
+            return np.ascontiguousarray(np.asarray(selection, np.int32).reshape(n, self.tokens)), None
+        return None, None
+
     def compute_velocity_host(self, I_cur, I_des, Z, K, mode: int = _lib.SELECT_DENSE, selection=None, n_selected=None,
                               des_shared: bool = False, num_pairs: Optional[int] = None):
         """The host-pointer entry point (``vitvs_compute_velocity``): numpy arrays in — uint8 frames [n, H, W, 3] in the
@@ -410,19 +424,7 @@ class Engine:
                 raise VitvsError("Z must be the sensor's uint16 millimetre image(s) [v_max, u_max]")
         kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
         k = self._num_pairs(num_pairs)
-        sel = cnt = None
-        if mode == _lib.SELECT_EXPLICIT:
-            rows = selection if isinstance(selection, (list, tuple)) else [selection]
-            if len(rows) != n:
-                raise VitvsError("one id list per pair expected")
-            sel = np.zeros((n, k), np.int32)
-            cnt = np.zeros(n, np.int32)
-            for b, ids in enumerate(rows):
-                ids = np.asarray(ids, np.int32).reshape(-1)[:k]
-                sel[b, :ids.size] = ids
-                cnt[b] = ids.size
-        elif mode == _lib.SELECT_ORDER:
-            sel = np.ascontiguousarray(np.asarray(selection, np.int32).reshape(n, self.tokens))
+        sel, cnt = self._selection_arrays_host(mode, selection, n, k)
         v = np.zeros((n, 6), np.float64)
         st = np.zeros(n, np.int32)
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
@@ -439,19 +441,7 @@ class Engine:
         the host between the correspondence and the law (vitvs_v2.py:127-141).  numpy ``(v_c [n, 6], status [n])``."""
         n = self._last_host_pairs
         k = self._num_pairs(num_pairs)
-        sel = cnt = None
-        if mode == _lib.SELECT_EXPLICIT:
-            rows = selection if isinstance(selection, (list, tuple)) else [selection]
-            if len(rows) != n:
-                raise VitvsError("one id list per pair expected")
-            sel = np.zeros((n, k), np.int32)
-            cnt = np.zeros(n, np.int32)
-            for b, ids in enumerate(rows):
-                ids = np.asarray(ids, np.int32).reshape(-1)[:k]
-                sel[b, :ids.size] = ids
-                cnt[b] = ids.size
-        elif mode == _lib.SELECT_ORDER:
-            sel = np.ascontiguousarray(np.asarray(selection, np.int32).reshape(n, self.tokens))
+        sel, cnt = self._selection_arrays_host(mode, selection, n, k)
         v = np.zeros((n, 6), np.float64)
         st = np.zeros(n, np.int32)
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
@@ -489,6 +479,17 @@ class Engine:
         ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings), ``subpatch`` (0: patch centres; 1: matches
         refined by their sub-patch offsets), ``interaction`` (0: L(s, Z); 1: L(s*, Z*); 2: their mean)."""
         self._check(self.lib.vitvs_set_option(self.handle, name.encode(), int(value)), f"vitvs_set_option({name})")
+        return self
+
+    def apply_law_params(self, params: ServoParams) -> "Engine":
+        """The control law of ``params`` (``robust_iterations``, ``subpatch``, ``interaction``): sets the options that differ from
+        this engine's and keeps ``self.params`` in step."""
+        for field, option, value in (("robust_iterations", "robust_law", params.robust_iterations),
+                                     ("subpatch", "subpatch", int(params.subpatch)),
+                                     ("interaction", "interaction", INTERACTIONS.index(params.interaction))):
+            if getattr(params, field) != getattr(self.params, field):
+                self.set_option(option, value)
+                self.params = self.params.replace(**{field: getattr(params, field)})
         return self
 
     # ------------------------------------------------------------------ measurement hooks

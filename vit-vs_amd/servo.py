@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import INTERACTIONS, ServoParams
+from .config import ServoParams
 from .engine import Engine, VitvsError
 
 STATUS_NAMES = {0: "ok", 1: "no_correspondence", 2: "too_few_features", 3: "no_depth"}
@@ -220,18 +220,11 @@ class Controller:
                  selection: str = "reference", goal_depth=None):
         self.engine = engine
         self.params = params or engine.params
-        if params is not None and params.interaction != engine.params.interaction:
-            engine.set_option("interaction", INTERACTIONS.index(params.interaction))
-            engine.params = engine.params.replace(interaction=params.interaction)
+        if params is not None:
+            engine.apply_law_params(params)               # the law of the params this controller was given
         self.goal_depth = None                            # uint16 millimetres at the goal pose (interaction "desired" / "mean")
         if goal_depth is not None:
             self.set_goal_depth(goal_depth)
-        if params is not None and params.robust_iterations != engine.params.robust_iterations:
-            engine.set_option("robust_law", params.robust_iterations)      # the law of the params this controller was given
-            engine.params = engine.params.replace(robust_iterations=params.robust_iterations)
-        if params is not None and params.subpatch != engine.params.subpatch:
-            engine.set_option("subpatch", int(params.subpatch))
-            engine.params = engine.params.replace(subpatch=params.subpatch)
         self.num_pairs = self.params.num_pairs
         self.dino_input_size = engine.cfg.img_size
         self.goal_image = goal_image                      # PIL image or uint8 array, any size
@@ -458,15 +451,7 @@ class MultiController:
             raise ValueError(f"engine.max_pairs ({self.engine.max_pairs}) is smaller than the number of cameras ({n})")
         if params is not None:
             for e in self.engines:                        # every pipeline slot evaluates the law of the params given
-                if e.params.robust_iterations != params.robust_iterations:
-                    e.set_option("robust_law", params.robust_iterations)
-                    e.params = e.params.replace(robust_iterations=params.robust_iterations)
-                if e.params.subpatch != params.subpatch:
-                    e.set_option("subpatch", int(params.subpatch))
-                    e.params = e.params.replace(subpatch=params.subpatch)
-                if e.params.interaction != params.interaction:
-                    e.set_option("interaction", INTERACTIONS.index(params.interaction))
-                    e.params = e.params.replace(interaction=params.interaction)
+                e.apply_law_params(params)
         self.cameras = [Controller(self.engine, g, params, selection="order") for g in goal_images]
         self.params = self.cameras[0].params
         # the goal depth of interaction "desired" / "mean": one image (uint16 [v_max, u_max]) that serves every camera, in every
