@@ -6,7 +6,12 @@
  *   layernorm                  nn.LayerNorm(eps=1e-6)                              dino_patch/block.py:57,75
  *   attention                  scaled_dot_product_attention over [B,H,N,64]        dino_patch/attention.py:73-78
  *   linear_partial+residual_ln the same nn.Linear + residual (+ next LayerNorm), as K slices  dino_patch/block.py:90-115
- * All pointers are device pointers; `precision` is enum vitvs_precision; `stream` a hipStream_t.
+ *   patchify / embed_ln        ToTensor + Normalize + patch extraction, cls / register / pos_embed rows, norm1 of block 0
+ *                                                                                  dinov2_extractor.py:141,177-191,259
+ *   residual_desc / descriptors / normalize_rows   last residual add, 3x3 log-bin, cosine normalisation
+ *                                                                                  dinov2_extractor.py:289-308; vitvs_v2.py:55
+ *   facet / saliency           the q / k / v facets and the class token's attention maps  dinov2_extractor.py:193-217,339-353
+ * All pointers are device pointers unless a comment says host; `precision` is enum vitvs_precision; `stream` a hipStream_t.
  */
 #ifndef VITVS_OPS_H
 #define VITVS_OPS_H
@@ -110,6 +115,53 @@ VITVS_API int vitvs_op_linear_partial(int32_t precision, const void* A, const vo
 VITVS_API int vitvs_op_residual_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias,
                          const float* ls, const float* gamma, const float* beta, void* out, int32_t M, int32_t D,
                          float eps, void* stream);
+
+/* The two ends of the forward (csrc/elementwise.hip; tests/test_gpu_ends_cover.py).  No handle, no planning: the arguments go
+ * straight to the launch.  T = grid * grid patch tokens per image, P = prefix rows per image (cls + register tokens), x the fp32
+ * residual stream [n_img][P + T][D], D in {128,256,384,768,1024} where a LayerNorm or a K-slice sum takes part.
+ *
+ * Patch rows: Ape[(img * T + t)][k] = ((u8 / 255) - mean[c]) / std[c] in `precision`, k = c p^2 + py p + px, every step rounded
+ * to nearest in fp32; +0 for 3 p^2 <= k < Kp.  Images are the n_des frames of `des` then the n_cur of `cur` (either may be NULL
+ * with a count of 0), RGB u8 [S][S][3]; grid = 1 + (S - patch) / stride.  Of x only the class rows x[img * (T + prefix)][:] =
+ * cls + pos[0] are written.  mean / std are HOST arrays of 3.  in_h = in_w = 0: frames arrive at S x S.  Otherwise they are camera
+ * frames [in_h][in_w][3] and u8 is the pixel of Pillow's bicubic resize to S x S, computed while the row is built: the hook builds
+ * the tables, uploads them, launches, synchronises the stream and frees them.  -3 when the camera rows of one patch pass the
+ * 64 KiB of LDS (as vitvs_set_frame_size). */
+VITVS_API int vitvs_op_patchify(int32_t precision, const uint8_t* des, int32_t n_des, const uint8_t* cur, int32_t n_cur, int32_t S,
+                      int32_t patch, int32_t stride, int32_t Kp, int32_t D, int32_t prefix, const float* mean, const float* std,
+                      const float* cls, const float* pos, int32_t in_h, int32_t in_w, void* Ape, float* x, void* stream);
+/* Finishes a split-K patch embedding, part [slices][n_img * T][D] fp32 (1 .. 8 slices, summed in index order):
+ *   x[img][0] = cls + pos[0];  x[img][r] = reg[r - 1] for 1 <= r < P (no position, no bias; reg may be NULL when P = 1);
+ *   x[img][P + t] = pos[1 + t] + sum_z part[z][img * T + t] + bias;  out = LayerNorm(x) * gamma + beta in `precision`.
+ * x is written only (its previous contents are not read). */
+VITVS_API int vitvs_op_embed_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias, const float* pos,
+                      const float* cls, const float* reg, const float* gamma, const float* beta, void* out, int32_t n_img, int32_t T,
+                      int32_t P, int32_t D, float eps, void* stream);
+/* The forward's last launch: vitvs_op_residual_ln without a LayerNorm on M = n_img * (T + P) rows, which also writes, for the
+ * patch rows only, dn[img][t][:] = x_row / max(|x_row|, 1e-8) and / or sq[img * T + t] = |x_row|^2 of the updated row (either
+ * may be NULL, not both) and clears zero_count <= M * 64 64-bit words of zero_a and zero_b.  `precision` selects the
+ * instantiation only (nothing is written in it).  -2 for arguments out of range. */
+VITVS_API int vitvs_op_residual_desc(int32_t precision, float* x, const float* part, int32_t slices, const float* bias, const float* ls,
+                           float* dn, float* sq, uint64_t* zero_a, uint64_t* zero_b, int32_t zero_count, int32_t T, int32_t P,
+                           int32_t M, int32_t D, void* stream);
+/* Descriptors from x: plain (binned = 0) dn[img][t][D] = x[img][P + t] / max(norm, 1e-8) (D <= 1024, dn required); binned
+ * dn[img][t][9 D] = the 3 x 3 replicate-clamped neighbourhood in row-major (dy, dx) order, normalised as a whole, through the
+ * squared-norm workspace sq_ws [n_img * T] (dn may be NULL when raw is given).  raw (may be NULL): the same rows un-normalised.
+ * zero_count <= n_img * T * 64 words of zero_a / zero_b are cleared.  -2 when grid * grid != T or an argument is out of range. */
+VITVS_API int vitvs_op_descriptors(const float* x, float* dn, float* raw, float* sq_ws, int32_t n_img, int32_t T, int32_t P, int32_t grid,
+                         int32_t D, int32_t binned, uint64_t* zero_a, uint64_t* zero_b, int32_t zero_count, void* stream);
+/* out[img][t][d * H + h] (fp32) = float(qkv[img * (P + T) + P + t][which][h][d]) * unscale, which = 0 q, 1 k, 2 v; keep_cls = 0:
+ * out [n_img][T][64 H]; 1: out [n_img][1 + T][64 H] with the class row first.  Register rows are dropped. */
+VITVS_API int vitvs_op_facet(int32_t precision, const void* qkv, float* out, int32_t n_img, int32_t T, int32_t P, int32_t H, int32_t which,
+                   float unscale, int32_t keep_cls, void* stream);
+/* out[img][t] (fp32): softmax over all P + T keys of q_cls . k / 8 per chosen head (q_prescaled != 0: 2^(q_cls . k), the q third
+ * carrying 0.125 * log2(e)), patch columns kept, mean over the n_heads heads of head_idx (a HOST array, 1 .. 16 entries in
+ * 0 .. H - 1), min-max normalised per image.  fp32, bf16 and fp16 only; -2 for VITVS_F16X2 and for a head out of range, -3 when
+ * 2 T + P floats pass 64 KiB of LDS. */
+VITVS_API int vitvs_op_saliency(int32_t precision, const void* qkv, float* out, int32_t n_img, int32_t T, int32_t P, int32_t H,
+                      const int32_t* head_idx, int32_t n_heads, int32_t q_prescaled, void* stream);
+/* dst[r][:] = src[r][:] / max(|src[r]|, 1e-8), fp32 rows of any width Dp >= 1 */
+VITVS_API int vitvs_op_normalize_rows(const float* src, float* dst, int32_t rows, int32_t Dp, void* stream);
 
 #ifdef __cplusplus
 }

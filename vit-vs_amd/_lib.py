@@ -96,6 +96,13 @@ PROTOTYPES = {
     "vitvs_op_gram_stencil": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_linear_partial": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "vitvs_op_residual_ln": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, C.c_float, _P]),
+    "vitvs_op_patchify": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "vitvs_op_embed_ln": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, _P]),
+    "vitvs_op_residual_desc": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vitvs_op_descriptors": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "vitvs_op_facet": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P]),
+    "vitvs_op_saliency": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "vitvs_op_normalize_rows": (_I, [_P, _P, _I, _I, _P]),
 }
 
 

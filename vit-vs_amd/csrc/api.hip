@@ -988,6 +988,17 @@ static int upload_table(vitvs_handle* h, const std::vector<int>& v, int** dev) {
     return 0;
 }
 
+// ResizeArgs::rows from Pillow's bounds `yb` of the height: the most camera rows the pixels of one patch draw on.
+// The patch-row build (patchify_resize_kernel) takes the camera rows of a patch from its first and last pixel row: both
+// bounds of Pillow's windows grow with the output row (they do: the centre does), checked here rather than assumed (-1).
+static int resize_patch_rows(const std::vector<int>& yb, int S, int patch) {
+    int rows = 0;
+    for (int y = 0; y + 1 < S; ++y)
+        if (yb[2 * y] > yb[2 * y + 2] || yb[2 * y] + yb[2 * y + 1] > yb[2 * y + 2] + yb[2 * y + 3]) return -1;
+    for (int y = 0; y + patch <= S; ++y) rows = std::max(rows, yb[2 * (y + patch - 1)] + yb[2 * (y + patch - 1) + 1] - yb[2 * y]);
+    return rows;
+}
+
 // Pillow's tables for (in_h, in_w) -> img_size in `t` (a new resolution replaces the previous tables; synchronises once).
 static int resize_tables(vitvs_handle* h, ResizeArgs& t, int in_h, int in_w) {
     if (in_h == t.in_h && in_w == t.in_w) return 0;
@@ -1004,12 +1015,8 @@ static int resize_tables(vitvs_handle* h, ResizeArgs& t, int in_h, int in_w) {
     std::vector<int> xb, xk, yb, yk;
     const int ksx = resize_coefficients(in_w, S, xb, xk);
     const int ksy = resize_coefficients(in_h, S, yb, yk);
-    // the patch-row build (patchify_resize_kernel) takes the camera rows of a patch from its first and last pixel row: both
-    // bounds of Pillow's windows grow with the output row (they do: the centre does), checked here rather than assumed
-    int rows = 0;
-    for (int y = 0; y + 1 < S; ++y)
-        if (yb[2 * y] > yb[2 * y + 2] || yb[2 * y] + yb[2 * y + 1] > yb[2 * y + 2] + yb[2 * y + 3]) return set_err(h, -5, "resize windows are not monotone");
-    for (int y = 0; y + patch <= S; ++y) rows = std::max(rows, yb[2 * (y + patch - 1)] + yb[2 * (y + patch - 1) + 1] - yb[2 * y]);
+    const int rows = resize_patch_rows(yb, S, patch);
+    if (rows < 0) return set_err(h, -5, "resize windows are not monotone");
     int *dxb = nullptr, *dxk = nullptr, *dyb = nullptr, *dyk = nullptr;
     if (upload_table(h, xb, &dxb) || upload_table(h, xk, &dxk) || upload_table(h, yb, &dyb) || upload_table(h, yk, &dyk))
         return set_err(h, -6, "resize table upload failed");
@@ -1777,6 +1784,89 @@ int vitvs_op_residual_ln(int32_t precision, float* x, const float* part, int32_t
     DeviceScope dev(nullptr);
     return launch_residual_ln(to_prec(precision), x, part, slices, bias, ls, gamma, beta, out, M, D,
                               eps, as_stream(stream));
+}
+
+// ---- the two ends of the forward (elementwise.hip), pointer-only: arguments go straight to the launch_* function ----
+int vitvs_op_patchify(int32_t precision, const uint8_t* des, int32_t n_des, const uint8_t* cur, int32_t n_cur, int32_t S,
+                      int32_t patch, int32_t stride, int32_t Kp, int32_t D, int32_t prefix, const float* mean, const float* std,
+                      const float* cls, const float* pos, int32_t in_h, int32_t in_w, void* Ape, float* x, void* stream) {
+    if (!mean || !std || !cls || !pos || !Ape || !x || (n_des > 0 && !des) || (n_cur > 0 && !cur)) return -1;
+    if (n_des < 0 || n_cur < 0 || S <= 0 || patch <= 0 || patch > S || stride <= 0 || D <= 0 || prefix < 1 || in_h < 0 || in_w < 0 ||
+        (in_h == 0) != (in_w == 0))
+        return -2;
+    DeviceScope dev(nullptr);
+    hipStream_t st = as_stream(stream);
+    PatchifyArgs pa{};
+    pa.des = des; pa.cur = cur; pa.n_des = n_des; pa.n_cur = n_cur;
+    pa.S = S; pa.patch = patch; pa.stride = stride; pa.grid = 1 + (S - patch) / stride; pa.Kp = Kp; pa.D = D;
+    for (int i = 0; i < 3; ++i) { pa.mean[i] = mean[i]; pa.std[i] = std[i]; }
+    pa.cls = cls; pa.pos = pos; pa.prefix = prefix;
+    if (in_h == 0) return launch_patchify(to_prec(precision), pa, nullptr, Ape, x, st);
+    // the fused resize: Pillow's tables for (in_h, in_w) -> S, as vitvs_set_frame_size builds them, for this launch only
+    std::vector<int> tab[4];   // xb, xk, yb, yk
+    ResizeArgs rs{};
+    rs.ksx = resize_coefficients(in_w, S, tab[0], tab[1]);
+    rs.ksy = resize_coefficients(in_h, S, tab[2], tab[3]);
+    rs.in_h = in_h; rs.in_w = in_w;
+    rs.rows = resize_patch_rows(tab[2], S, patch);
+    if (rs.rows < 0) return -5;
+    if ((size_t)rs.rows * patch * 3 > 64 * 1024) return -3;
+    int* d[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    for (int i = 0; i < 4 && !rc; ++i) {
+        if (hipMalloc((void**)&d[i], tab[i].size() * sizeof(int)) != hipSuccess ||
+            hipMemcpyAsync(d[i], tab[i].data(), tab[i].size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)
+            rc = -6;
+    }
+    rs.xb = d[0]; rs.xk = d[1]; rs.yb = d[2]; rs.yk = d[3];
+    if (!rc) rc = launch_patchify(to_prec(precision), pa, &rs, Ape, x, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -1;   // the launch is done with the tables before they go
+    for (int i = 0; i < 4; ++i)
+        if (d[i]) (void)hipFree(d[i]);
+    return rc;
+}
+int vitvs_op_embed_ln(int32_t precision, float* x, const float* part, int32_t slices, const float* bias, const float* pos,
+                      const float* cls, const float* reg, const float* gamma, const float* beta, void* out, int32_t n_img, int32_t T,
+                      int32_t P, int32_t D, float eps, void* stream) {
+    DeviceScope dev(nullptr);
+    return launch_embed_ln(to_prec(precision), x, part, slices, bias, pos, cls, reg, gamma, beta, out, n_img, T, P, D, eps,
+                           as_stream(stream));
+}
+int vitvs_op_residual_desc(int32_t precision, float* x, const float* part, int32_t slices, const float* bias, const float* ls,
+                           float* dn, float* sq, uint64_t* zero_a, uint64_t* zero_b, int32_t zero_count, int32_t T, int32_t P,
+                           int32_t M, int32_t D, void* stream) {
+    if (zero_count < 0 || (zero_count > 0 && (!zero_a || !zero_b))) return -2;
+    DeviceScope dev(nullptr);
+    DescOut d;
+    d.dn = dn; d.sq = sq; d.T = T; d.P = P; d.zero_count = zero_count;
+    d.zero_a = reinterpret_cast<unsigned long long*>(zero_a);
+    d.zero_b = reinterpret_cast<unsigned long long*>(zero_b);
+    return launch_residual_ln(to_prec(precision), x, part, slices, bias, ls, nullptr, nullptr, nullptr, M, D, 0.f, as_stream(stream),
+                              &d);
+}
+int vitvs_op_descriptors(const float* x, float* dn, float* raw, float* sq_ws, int32_t n_img, int32_t T, int32_t P, int32_t grid,
+                         int32_t D, int32_t binned, uint64_t* zero_a, uint64_t* zero_b, int32_t zero_count, void* stream) {
+    // the plain kernel always writes dn and keeps a row in 4 float4 per lane; the binned one reads the squared-norm workspace
+    if (!x || D <= 0 || D % 4 != 0 || zero_count < 0 || (zero_count > 0 && (!zero_a || !zero_b))) return -2;
+    if (binned ? (!sq_ws || (!dn && !raw)) : (!dn || D > 1024)) return -2;
+    DeviceScope dev(nullptr);
+    return launch_descriptors(x, dn, raw, sq_ws, n_img, T, P, grid, D, binned, reinterpret_cast<unsigned long long*>(zero_a),
+                              reinterpret_cast<unsigned long long*>(zero_b), zero_count, as_stream(stream));
+}
+int vitvs_op_facet(int32_t precision, const void* qkv, float* out, int32_t n_img, int32_t T, int32_t P, int32_t H, int32_t which,
+                   float unscale, int32_t keep_cls, void* stream) {
+    DeviceScope dev(nullptr);
+    return launch_facet(to_prec(precision), qkv, out, n_img, T, P, H, which, unscale, keep_cls, as_stream(stream));
+}
+int vitvs_op_saliency(int32_t precision, const void* qkv, float* out, int32_t n_img, int32_t T, int32_t P, int32_t H,
+                      const int32_t* head_idx, int32_t n_heads, int32_t q_prescaled, void* stream) {
+    if (!head_idx) return -1;
+    DeviceScope dev(nullptr);
+    return launch_saliency(to_prec(precision), qkv, out, n_img, T, P, H, head_idx, n_heads, q_prescaled != 0, as_stream(stream));
+}
+int vitvs_op_normalize_rows(const float* src, float* dst, int32_t rows, int32_t Dp, void* stream) {
+    DeviceScope dev(nullptr);
+    return launch_normalize_rows(src, dst, rows, Dp, as_stream(stream));
 }
 
 }  // extern "C"

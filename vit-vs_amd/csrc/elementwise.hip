@@ -343,7 +343,9 @@ __global__ __launch_bounds__(64) void residual_ln_kernel(float* __restrict__ x, 
     }
     if constexpr (DESC) {
         // last block: the row is final; emit its L2-normalised descriptor (patch tokens only) and clear the
-        // correspondence keys (same arithmetic and summation order as desc_plain_kernel)
+        // correspondence keys.  Same arithmetic as desc_plain_kernel; the same summation order, hence the same bits, where a
+        // lane owns the same float4s as there (LANES = 64: D = 256, 768, 1024).  At D = 128 and 384 (LANES = 32) the 32 lanes
+        // sum other partial sums: equal to fp32 rounding only (tests/test_gpu_ends_cover.py checks both)
         const DescOut& desc = ex.desc;
         const int gid = blockIdx.x * 64 + lane;
         if (gid < desc.zero_count) { desc.zero_a[gid] = 0ull; desc.zero_b[gid] = 0ull; }
