@@ -289,6 +289,42 @@ VITVS_API int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16
  * everywhere with option "interaction" at 0.  Synchronising, always read from the device. */
 VITVS_API int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z);
 
+/* --- the rig law: one twist for a rigid multi-camera rig ------------------------------------------
+ * A velocity call of N pairs whose current frames are the N cameras of one rigid rig leaves N camera twists; this evaluates the
+ * ONE twist the rig should execute, the least-squares solution of the stacked problem (ViSP's cVe per feature set).  Camera i
+ * has pose (R_i, t_i) in the rig frame, X_rig = R_i X_cam + t_i; a rig twist v_r = (v, w), expressed in the rig frame, moves
+ * camera i with the twist, in its own optical frame,
+ *     v_ci = W_i v_r,   W_i = [[R_i^T, -R_i^T [t_i]x], [0, R_i^T]]      (6 x 6)
+ * and with L_i (rows x 6), e_i what camera i's law built — under whichever of "subpatch" / "interaction" is on, zero-padded
+ * rows included, exactly as the camera's own law used them (L and e of vitvs_last_details) —
+ *     M = stack_i(L_i W_i),  e = stack_i(e_i),  v_r = -lambda pinv(M) e
+ * over the cameras whose status is VITVS_OK, in fp64: the 6 x 6 normal equations G = M^T M, g = M^T e by the LDL^T
+ * factorisation of the camera law with its pivot test d > 1e-8 G_jj, and behind a failed pivot the one-sided Jacobi SVD of the
+ * stacked M with numpy.linalg.pinv's rcond = 1e-15.  The average of the cameras' twists mapped back to the rig frame is NOT this
+ * solution, and is wrong whenever one camera alone cannot observe all six degrees of freedom.
+ *   cVr      double [n_cams][36], row-major W_i
+ *   status   int32 [n_cams], the array the velocity call wrote: a camera whose status is not VITVS_OK contributes no rows
+ *   v_rig    double [6]; 0 when no camera contributes
+ *   rig_status  int32: VITVS_OK when a camera contributed, else the largest camera status
+ *   rig_info int32 [8] or NULL: cameras used, total rows of M, Jacobi sweeps (-1: the LDL^T path), n_cams, the largest camera
+ *            status, 0, 0, 0
+ *   normal   double [28] or NULL: G's upper triangle row-major (21), g (6), the total rows as a double — what a rig spread over
+ *            several GPUs sums across them (vit-vs_amd/dist.py rig_velocity)
+ * All pointers are device memory (_dev; one launch on `stream`, asynchronous) or host memory (the other form: copy in, run,
+ * wait, copy out).  Evaluated on what the handle's last law evaluation left on the device, with the handle's lambda: valid after
+ * vitvs_compute_velocity[_dev] / vitvs_reselect with n_pairs == n_cams, in stream order behind it; it changes nothing that call
+ * left (v_c, status, vitvs_last_*).  The result is bit-reproducible: the cameras' sums are added in camera order.
+ * The stacked workspace lives in the handle, sized for max_pairs cameras and allocated by the first rig call, which therefore
+ * synchronises and must not be made inside a stream capture; later calls may be captured and replayed.
+ * With option "robust_law" on the call is error -5: a robust rig law needs ONE median over all cameras' residuals, which the
+ * cameras' own re-weighted laws do not give, and is not built.
+ * Returns 0, -1 (a null required pointer), -5 (no law evaluation yet, n_cams is not its pair count, more than 256 cameras,
+ * robust_law on).  Replaces nothing: the reference runs one controller per camera (vitvs_v2.py:702-819). */
+VITVS_API int vitvs_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
+                                     int32_t* rig_status, int32_t* rig_info, double* normal, void* stream);
+VITVS_API int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
+                                 int32_t* rig_status, int32_t* rig_info, double* normal);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several

@@ -97,6 +97,23 @@ VITVS_API int vitvs_op_gram_plan(int32_t precision, int32_t binned, int32_t T, i
  * 160 KiB of LDS (out filled). */
 VITVS_API int vitvs_op_servo_plan(int32_t T, int32_t max_rows, int32_t robust_iters, int32_t refine_source, int32_t interaction,
                         int32_t* out);
+/* The rig law's kernel (vitvs_rig_velocity_dev, include/vitvs.h) on caller systems, no handle and no forward:
+ *   rows    int32 [n_cams], the rows of camera i's system (0 .. ld); 0: the camera does not contribute
+ *   L       double [n_cams][7][ld], column-major as vitvs_last_details returns it: L_i's six columns, then e_i
+ *   W       double [n_cams][36], row-major W_i;  v_rig = -lambda pinv(stack_i(L_i W_i)) stack_i(e_i)
+ *   scratch vitvs_op_rig_scratch_bytes(n_cams, ld) = 256 + 8 (32 n_cams + 14 n_cams ld) bytes of device memory (hipMalloc),
+ *           zeroed by the caller before the FIRST call only (its first word is the hand-off's ticket, which every launch
+ *           leaves zero; a block may serve calls of other n_cams and ld that fit it)
+ *   v_rig [6], rig_status, rig_info [8] or NULL, normal [28] or NULL as vitvs_rig_velocity_dev's; a camera without rows counts
+ *   as VITVS_TOO_FEW.  Everything is device memory; one launch on `stream`.
+ * Returns 0, -1 (a null required pointer), -2 (n_cams outside 1 .. 256, ld < 1). */
+VITVS_API int vitvs_op_rig_law(int32_t n_cams, const int32_t* rows, const double* L, int32_t ld, const double* W, double lambda,
+                     void* scratch, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal, void* stream);
+VITVS_API int vitvs_op_rig_scratch_bytes(int32_t n_cams, int32_t ld);   /* -2 as above, -3 past 2 GiB */
+/* Measurement hook (tools/rig_times.py): on != 0 makes the calling thread's vitvs_op_rig_law run as two plain launches (the
+ * cameras' sums, then the solve) instead of the one launch with its in-launch fan-in.  Same results bit for bit.  Returns the
+ * previous setting. */
+VITVS_API int vitvs_op_rig_two_launches(int32_t on);
 /* The fused Gram arg-max of the velocity path on caller-normalised descriptors dn [n_des + n_pairs][T][Dp] fp32 (desired frames
  * first; n_des = 1 with des_shared): the plan of vitvs_op_gram_plan(precision, 0, T, Dp, n_pairs, n_pairs), the split into dh
  * (3 (n_des + n_pairs) T Dp fp16, only when the plan splits) and the keys row_best / col_best [n_pairs][T] (cleared here), decoded

@@ -22,6 +22,7 @@ static thread_local std::string g_last_error;
 thread_local LaunchTiming g_launch_timing;
 thread_local int g_current_device = -1;
 thread_local int g_updates_in_flight = 1;
+static thread_local bool g_op_rig_two_launches = false;   // vitvs_op_rig_two_launches: vitvs_op_rig_law as two plain launches (the measured alternative)
 static thread_local int g_op_wexp = 0;   // vitvs_op_weight_exponent: the 2^e the f16x2 weights of the operator hooks carry
 
 int fail_hip(hipError_t e, const char* what, const char* file, int line) {
@@ -125,6 +126,10 @@ struct vitvs_handle {
     uint16_t* zgoal = nullptr;  // [max_pairs][T + 1] mm, goal depth at every token's patch centre and at pixel (0, 0) (vitvs_set_goal_depth_dev)
     int n_goal_depth = 0;     // goal depth images held in zgoal, 0: none
     double* zgoal_ws = nullptr; // [max_pairs][max_rows] Z* of the last law evaluation's feature rows (vitvs_last_goal_depth)
+    // the rig law (vitvs_rig_velocity_dev): its scratch block (ticket, the cameras' sums, the stacked rows and their working copy)
+    // at max_pairs cameras, and the device side of the host-pointer form, allocated by the first rig call
+    unsigned char* rig_ws = nullptr;
+    unsigned char* rig_io = nullptr;   // cVr [max_pairs][36] f64 | v_rig [6] | normal [28] | status [max_pairs] i32 | rig_status | rig_info [8]
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -1585,6 +1590,65 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
     return rc;
 }
 
+// --- the rig law ---------------------------------------------------------------------------------
+static int rig_prepare(vitvs_handle* h, int n_cams) {
+    if (!h->last_pairs) return set_err(h, -5, "vitvs_rig_velocity follows a velocity call on the same handle");
+    if (n_cams != h->last_pairs)
+        return set_err(h, -5, "n_cams (" + std::to_string(n_cams) + ") is not the pair count of the last law evaluation (" +
+                                  std::to_string(h->last_pairs) + ")");
+    if (h->last_law.robust || h->robust_iters)
+        return set_err(h, -5, "the rig law does not combine with option robust_law (one median over all cameras' residuals: not built)");
+    if (n_cams > kRigMaxCams) return set_err(h, -5, "the rig law takes at most " + std::to_string(kRigMaxCams) + " cameras");
+    if (!h->rig_ws) {                           // set-up, not the call path (and never inside a capture): as vitvs_set_goal_depth_dev
+        const size_t P = h->cfg.max_pairs;
+        int rc = dev_alloc(h, &h->rig_ws, rig_scratch_bytes((int)P, 2 * h->cfg.max_rows));
+        if (!rc) rc = dev_alloc(h, &h->rig_io, P * 36 * 8 + 34 * 8 + (P + 9) * 4 + 64);
+        if (rc) return set_err(h, rc, "rig workspace allocation failed");
+        VITVS_HIP_CHECK(hipDeviceSynchronize());   // the blocks (the ticket above all) are zero before any stream uses them
+    }
+    return 0;
+}
+
+int vitvs_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
+                           int32_t* rig_status, int32_t* rig_info, double* normal, void* stream) {
+    if (!h || !cVr || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = rig_prepare(h, n_cams)) return rc;
+    RigArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_cams = n_cams; a.status = status; a.rows = h->info + 5; a.rows_stride = 8;
+    a.L = h->Lws; a.ld = 2 * h->cfg.max_rows; a.W = cVr; a.lambda = h->cfg.lambda;
+    rig_carve(h->rig_ws, h->cfg.max_pairs, a.ld, a);
+    a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
+    const int rc = launch_rig(a, as_stream(stream));
+    return rc ? set_err(h, rc, "rig law launch failed") : 0;
+}
+
+int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
+                       int32_t* rig_status, int32_t* rig_info, double* normal) {
+    if (!h || !cVr || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = rig_prepare(h, n_cams)) return rc;
+    const size_t P = h->cfg.max_pairs;
+    double* d_W = reinterpret_cast<double*>(h->rig_io);
+    double* d_v = d_W + P * 36;
+    double* d_normal = d_v + 6;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_normal + 28);
+    int32_t* d_rig_status = d_status + P;
+    int32_t* d_info = d_rig_status + 1;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    VITVS_HIP_CHECK(hipMemcpy(d_W, cVr, (size_t)n_cams * 36 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_status, status, (size_t)n_cams * 4, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = vitvs_rig_velocity_dev(h, n_cams, d_W, d_status, d_v, d_rig_status, d_info, d_normal, st)) return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
+    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
+    if (normal) VITVS_HIP_CHECK(hipMemcpy(normal, d_normal, 28 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -1717,6 +1781,30 @@ int vitvs_op_servo_plan(int32_t T, int32_t max_rows, int32_t robust_iters, int32
     return rc;
 }
 // the arg-max keys of n_pairs pairs -> nn_1 / nn_2 / sim_1 [n_pairs][T], as the law's kernel decodes them
+int vitvs_op_rig_law(int32_t n_cams, const int32_t* rows, const double* L, int32_t ld, const double* W, double lambda,
+                     void* scratch, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal, void* stream) {
+    if (!rows || !L || !W || !scratch || !v_rig || !rig_status) return -1;
+    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
+    RigArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_cams = n_cams; a.rows = rows; a.rows_stride = 1; a.L = L; a.ld = ld; a.W = W; a.lambda = lambda;
+    rig_carve(scratch, n_cams, ld, a);
+    a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
+    return launch_rig(a, as_stream(stream), g_op_rig_two_launches);
+}
+
+int vitvs_op_rig_scratch_bytes(int32_t n_cams, int32_t ld) {
+    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
+    const size_t b = rig_scratch_bytes(n_cams, ld);
+    return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_rig_two_launches(int32_t on) {
+    const int prev = g_op_rig_two_launches ? 1 : 0;
+    g_op_rig_two_launches = on != 0;
+    return prev;
+}
+
 static int decode_pairs(const unsigned long long* row_best, const unsigned long long* col_best, int T, int n_pairs, int32_t* nn_1,
                         int32_t* nn_2, float* sim_1, hipStream_t st) {
     int rc = 0;

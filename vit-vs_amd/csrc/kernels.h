@@ -355,6 +355,41 @@ int launch_servo(const ServoPlan& plan, const ServoArgs& a, hipStream_t stream);
 // the geometry fields of a law call (T, grid, scale_*, half_f, depth_h, depth_w)
 int launch_goal_depth(const ServoArgs& geom, const uint16_t* Z, int n_goal, uint16_t* table, hipStream_t stream);
 
+// ---- rig.hip -------------------------------------------------------------------------------
+// The rig law: ONE twist for a rigid rig of cameras.  Camera i's law left L_i (rows x 6) and e_i; with W_i the
+// 6 x 6 twist transform from the rig frame to camera i's optical frame, v_rig = -lambda * pinv(stack_i(L_i W_i)) stack_i(e_i)
+// over the cameras whose status is ST_OK.  One launch, one workgroup per camera; the workgroup that finishes last adds the
+// cameras' normal equations in camera order and solves (LDL^T, then the Jacobi SVD over the stacked rows: solve.h).
+constexpr int kRigMaxCams = 256;      // one workgroup per camera, at most one per CU (the hand-off's measured form)
+constexpr int kRigPartDoubles = 32;   // per camera: G (21) + g (6) + its rows, padded to 256 bytes
+struct RigArgs {
+    int n_cams;
+    const int32_t* status;    // [n_cams] the cameras' statuses; null: a camera with rows is ST_OK, one without ST_TOO_FEW
+    const int32_t* rows;      // rows of camera i (both rows of every feature pair, zero-padded ones included) at rows[i * rows_stride]
+    int rows_stride;
+    const double* L;          // [n_cams][7][ld] column-major: L_i's 6 columns, then e_i (ServoArgs::L_ws)
+    int ld;
+    const double* W;          // [n_cams][36] row-major W_i
+    double lambda;
+    // workspaces: cap >= n_cams * ld rows; `ticket` zero before the first launch (every launch leaves it zero)
+    double* stack;            // [7][cap] the stacked M = L_i W_i and e, contributing cameras in camera order
+    double* work;             // [7][cap] the Jacobi SVD's working copy
+    int cap;
+    double* part;             // [n_cams][kRigPartDoubles] every camera's normal equations
+    int* ticket;
+    // outputs
+    double* v_rig;            // [6]
+    int32_t* rig_status;      // ST_OK when a camera contributed, else the largest camera status (v_rig = 0)
+    int32_t* rig_info;        // [8] or null: cameras used, total rows, sweeps (-1: LDL^T), n_cams, largest camera status, 0, 0, 0
+    double* normal;           // [28] or null: G upper triangle row-major (21), g (6), total rows
+};
+// Bytes of one scratch block for n_cams cameras of ld rows each, and its parts (ticket first, on a line of its own)
+size_t rig_scratch_bytes(int n_cams, int ld);
+void rig_carve(void* scratch, int n_cams, int ld, RigArgs& a);
+// two_launches: the partial sums and the solve as two plain launches instead of the in-launch fan-in (the alternative
+// tools/rig_times.py times it against).  -2: n_cams outside 1 .. kRigMaxCams, ld < 1, cap < n_cams * ld, a null pointer
+int launch_rig(const RigArgs& a, hipStream_t stream, bool two_launches = false);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

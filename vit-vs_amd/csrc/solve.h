@@ -1,0 +1,143 @@
+// The fp64 solvers of the control laws: the 6x6 normal equations by LDL^T, and the one-sided Jacobi SVD behind a failed pivot.
+// Shared by servo.hip (one camera's law) and rig.hip (the rig law over the cameras' stacked rows).
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace vitvs {
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains every outstanding
+// global load AND store (vmcnt(0)); this kernel is one serial chain of short phases, and its detail
+// stores and prefetched loads must stay in flight across the phase boundaries.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// One wavefront: 27 lanes add the 8 slices, every lane then factors the same 6x6 system in registers (fully unrolled: no
+// private-memory arrays, no cross-lane traffic).  True, and xsol = G^-1 g, when every pivot passes the 1e-8 test.
+__device__ __forceinline__ bool solve_ldlt(double* Gs, int lane, double xsol[6]) {
+    if (lane < 27) {
+        double acc = 0.0;
+#pragma unroll
+        for (int sl = 0; sl < 8; ++sl) acc += Gs[40 + sl * 27 + lane];
+        Gs[lane] = acc;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same wave: LDS writes above are visible below
+    double Gm[6][6], rhs[6];
+    {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) { Gm[j][i] = Gs[q]; ++q; }   // lower triangle
+#pragma unroll
+        for (int i = 0; i < 6; ++i) rhs[i] = Gs[21 + i];
+    }
+    // G = L D L^T (unit lower-triangular L, no square roots, one reciprocal per pivot)
+    bool good = true;
+    double Lf[6][6], dinv[6], dpiv[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = Gm[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= Lf[j][k] * Lf[j][k] * dpiv[k];
+        good = good && (d > 1e-8 * Gm[j][j]) && (Gm[j][j] > 0.0);
+        dpiv[j] = d;
+        dinv[j] = 1.0 / d;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double t = Gm[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t -= Lf[i][k] * Lf[j][k] * dpiv[k];
+            Lf[i][j] = t * dinv[j];
+        }
+    }
+    if (good) {
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {          // L y = rhs
+            double t = rhs[i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) t -= Lf[i][k] * y[k];
+            y[i] = t;
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {         // L^T x = D^-1 y
+            double t = y[i] * dinv[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) t -= Lf[k][i] * xsol[k];
+            xsol[i] = t;
+        }
+    }
+    return good;
+}
+
+// One wavefront: xsol = pinv(A) rhs by one-sided Jacobi SVD with numpy.linalg.pinv's rcond = 1e-15 cut-off; A = the 6 columns
+// of Lc, rhs its 7th.  The rotations overwrite Lc.  Returns the sweeps that ran (<= 40).
+__device__ __forceinline__ int solve_jacobi(double* Lc, int rcap, int R, int lane, double xsol[6]) {
+    double V[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+    const double tol = 4e-15;
+    int sweeps;
+    for (sweeps = 0; sweeps < 40; ++sweeps) {
+        int rotated = 0;
+#pragma unroll
+        for (int p = 0; p < 5; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 6; ++q) {
+                double al = 0.0, be = 0.0, ga = 0.0;
+                for (int r = lane; r < R; r += 64) {
+                    const double ap = Lc[p * rcap + r], aq = Lc[q * rcap + r];
+                    al += ap * ap; be += aq * aq; ga += ap * aq;
+                }
+                al = wave_sum(al); be = wave_sum(be); ga = wave_sum(ga);
+                if (fabs(ga) > tol * sqrt(al * be) && al > 0.0 && be > 0.0) {
+                    ++rotated;
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+                    for (int r = lane; r < R; r += 64) {
+                        const double ap = Lc[p * rcap + r], aq = Lc[q * rcap + r];
+                        Lc[p * rcap + r] = c * ap - s * aq;
+                        Lc[q * rcap + r] = s * ap + c * aq;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) {
+                        const double vp = V[i][p], vq = V[i][q];
+                        V[i][p] = c * vp - s * vq;
+                        V[i][q] = s * vp + c * vq;
+                    }
+                }
+            }
+        if (rotated == 0) break;
+    }
+    double sig2[6], w[6], smax2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double s2 = 0.0, dot = 0.0;
+        for (int r = lane; r < R; r += 64) {
+            const double aj = Lc[j * rcap + r];
+            s2 += aj * aj;
+            dot += aj * Lc[6 * rcap + r];
+        }
+        sig2[j] = wave_sum(s2);
+        w[j] = wave_sum(dot);
+        smax2 = fmax(smax2, sig2[j]);
+    }
+    const double cutoff = 1e-15 * sqrt(smax2);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) xsol[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        if (sqrt(sig2[j]) > cutoff) {
+            const double coef = w[j] / sig2[j];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xsol[i] += V[i][j] * coef;
+        }
+    }
+    return sweeps;
+}
+
+}  // namespace vitvs

@@ -1,6 +1,7 @@
 """Multi-GPU layout of the hot path: independent frame pairs sharded contiguously over ranks, one
 process per GPU, weights replicated, and a single collective per update — the all-gather of the
 6-double twists (48 bytes per pair; latency-bound, so a flat gather, never a ring of buckets).
+A rigid rig that wants ONE twist instead sums its cameras' normal equations (``rig_velocity``: one all-reduce of 28 doubles).
 
 The reference has no distributed code; this is the 8-camera-rig layout of
 BASELINE.json configs[3].  ``torch.distributed`` backend "nccl" is RCCL on ROCm; the same code runs
@@ -54,6 +55,43 @@ def gather_velocities(v_local: torch.Tensor, n_pairs: int, group=None, out: torc
     for r, (b2, e2) in enumerate(sizes):
         full[b2:e2] = buf[r * n_max: r * n_max + (e2 - b2)]
     return full
+
+
+def unpack_normal(normal: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(G [6, 6] symmetric, g [6]) of the 28 doubles ``vitvs_rig_velocity_dev`` writes: G's upper triangle row-major, g, rows."""
+    iu = torch.triu_indices(6, 6, device=normal.device)
+    G = torch.zeros((6, 6), dtype=normal.dtype, device=normal.device)
+    G[iu[0], iu[1]] = normal[:21]
+    G = G + torch.triu(G, 1).T
+    return G, normal[21:27]
+
+
+def rig_velocity(normal_local: torch.Tensor, lam: float, group=None) -> torch.Tensor:
+    """The rig law (include/vitvs.h, vitvs_rig_velocity_dev) for a rig spread over ranks: one camera, or one shard of cameras,
+    per GPU.  ``normal_local`` is the 28 doubles this rank's rig call left (``Engine.rig_velocity(...)[2]["normal"]``: the normal
+    equations G = M^T M, g = M^T e of ITS cameras' stacked rows, and their row count; all zeros when none of its cameras
+    contributed).  The project's second collective beside the ``v_c`` gather: ONE ``all_reduce(SUM)`` of the 28 doubles (G and g
+    of a stack are the sums of its parts'), then ``v_rig = -lam * pinv(G) g`` in fp64 torch on every rank — the same [6] tensor
+    everywhere, all zeros when no rank contributed a row.
+
+    ``torch.linalg.pinv(G, hermitian=True)`` applies its cut-off (eigenvalues below ~6 eps |lambda|_max) to G, whose condition is
+    that of M squared — not numpy's rcond = 1e-15 on M as the single-GPU kernel's Jacobi path does: the two agree for the
+    well-conditioned stacks a rig produces (tests/test_rig_gloo.py, <= 1e-9) and differ for a stack whose smallest singular value
+    is below ~1e-8 of its largest, which the sum of normal equations cannot resolve."""
+    import torch.distributed as dist
+    if normal_local.shape != (28,) or normal_local.dtype != torch.float64:
+        raise ValueError("normal_local is the float64 [28] a rig call writes")
+    total = normal_local.clone()
+    if total.is_cuda and dist.get_backend(group) == "gloo":   # rehearsal path, as gather_velocities
+        host = total.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        total = host.to(normal_local.device)
+    else:
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+    G, g = unpack_normal(total)
+    if float(total[27]) == 0.0:
+        return torch.zeros(6, dtype=torch.float64, device=normal_local.device)
+    return -float(lam) * (torch.linalg.pinv(G, hermitian=True) @ g)
 
 
 class VelocityGather:

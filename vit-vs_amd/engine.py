@@ -473,6 +473,36 @@ class Engine:
         self._check(rc, "vitvs_last_details")
         return dict(info=info, s_uv=suv, feat=feat)
 
+    def rig_velocity(self, cVr, status):
+        """``vitvs_rig_velocity_dev``: the ONE twist of a rigid rig whose cameras were the pairs of the last velocity call, from
+        what that call left in the handle.  ``cVr``: float64 [n, 6, 6], camera i's twist transform from the rig frame
+        (``servo.twist_matrix``); ``status``: the int32 [n] the velocity call returned (a device tensor stays on the device).
+        Returns ``(v_rig float64 tensor [6] on the device, rig_status int, info)`` with ``info`` = dict(cameras, rows, sweeps
+        (-1: LDL^T), worst_status, normal float64 [28] device tensor: G upper triangle, g, rows).  Reading the status synchronises."""
+        w = torch.as_tensor(cVr, dtype=torch.float64).reshape(-1, 36).to(self.device).contiguous()
+        n = int(w.shape[0])
+        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+        if st.numel() != n:
+            raise VitvsError("one status per camera expected")
+        v = torch.empty(6, dtype=torch.float64, device=self.device)
+        out = torch.empty(9, dtype=torch.int32, device=self.device)      # rig_status | rig_info [8]
+        normal = torch.empty(28, dtype=torch.float64, device=self.device)
+        rc = self.lib.vitvs_rig_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(v), _ptr(out), _ptr(out[1:]), _ptr(normal),
+                                             _stream_ptr(self.device))
+        self._check(rc, "vitvs_rig_velocity_dev")
+        o = out.cpu().numpy()
+        return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal)
+
+    def rig_velocity_host(self, cVr, status):
+        """``vitvs_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info [8] int32, normal [28])`` out."""
+        w = np.ascontiguousarray(np.asarray(cVr, np.float64).reshape(-1, 36))
+        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        v, rs, info, normal = np.zeros(6), np.zeros(1, np.int32), np.zeros(8, np.int32), np.zeros(28)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_rig_velocity(self.handle, int(w.shape[0]), p(w), p(st), p(v), p(rs), p(info), p(normal))
+        self._check(rc, "vitvs_rig_velocity")
+        return v, int(rs[0]), info, normal
+
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),

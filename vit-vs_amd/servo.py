@@ -211,6 +211,20 @@ def twist_from_velocity(v_c, max_velocity: float):
     return (c(v_c[2]), c(-v_c[0]), c(-v_c[1])), (c(v_c[5]), c(-v_c[3]), c(-v_c[4]))
 
 
+def twist_matrix(R, t) -> np.ndarray:
+    """The 6 x 6 twist transform W from a rig frame to a camera's optical frame (ViSP's ``cVe``), fp64.  The camera has pose
+    (R, t) in the rig frame, X_rig = R X_cam + t; a rig twist v_r = (v, w) expressed in the rig frame moves the camera with
+    v_c = W v_r in its own frame:  W = [[R^T, -R^T [t]x], [0, R^T]]."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = np.asarray(t, np.float64).reshape(3)
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    W = np.zeros((6, 6))
+    W[:3, :3] = R.T
+    W[:3, 3:] = -R.T @ tx
+    W[3:, 3:] = R.T
+    return W
+
+
 # ------------------------------------------------------------------------------------------ Controller adapter
 class Controller:
     """ROS-free stand-in for the reference ``Controller``'s hot-path half: feed it frames, call ``ibvs()``
@@ -438,9 +452,21 @@ class MultiController:
     """
 
     def __init__(self, backend, goal_images: Sequence, params: Optional[ServoParams] = None, selection: str = "order",
-                 generator: Optional[torch.Generator] = None, goal_depth=None):
+                 generator: Optional[torch.Generator] = None, goal_depth=None, rig: Optional[Sequence] = None):
         from .pipeline import UpdatePipeline
         self.pipe = backend if isinstance(backend, UpdatePipeline) else None
+        # rig = [(R_i, t_i), ...]: the cameras are one rigid body, camera i at pose (R_i, t_i) in the rig frame.  After each
+        # round's batched call the rig law (Engine.rig_velocity) gives the ONE twist of the rig over that round's live cameras:
+        # ``rig_velocity_raw``, and ``v_rig`` smoothed by the cameras' EMA; the cameras' own state is exactly as without it.
+        self.rig_W = None
+        self.rig_velocity_raw, self.v_rig, self.rig_status, self.rig_info = None, None, None, None
+        self._rig_ema = [None] * 6
+        if rig is not None:
+            if self.pipe is not None:
+                raise ValueError("rig= needs the Engine backend: a pipeline slot sees one camera, the rig law all of them in one handle")
+            if len(rig) != len(goal_images):
+                raise ValueError("rig= takes one (R, t) per camera")
+            self.rig_W = np.stack([twist_matrix(R, t) for R, t in rig])
         self.engines = list(backend.engines) if self.pipe is not None else [backend]
         self.engine = self.engines[0]
         if selection not in ("order", "dense"):
@@ -530,6 +556,11 @@ class MultiController:
             stack = lambda xs: torch.stack([torch.as_tensor(x).to(eng.device) for x in xs])   # noqa: E731
             v, st = eng.compute_velocity(stack(cur), stack(des), np.stack(depth), p.intrinsics(), mode=mode,
                                          selection=(torch.stack(sel) if mode == _lib.SELECT_ORDER else sel), num_pairs=k)
+            if self.rig_W is not None:                    # (before the host reads: the law is one more launch behind the call)
+                v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st)
+                if self.rig_status == _lib.STATUS_OK:
+                    self.rig_velocity_raw = v_r.cpu().numpy()
+                    self.v_rig = ema_update(self._rig_ema, self.rig_velocity_raw, p.ema_alpha)
             v, st = v.cpu().numpy(), st.cpu().numpy()
             det = eng.last_features(len(live)) if want_features else None
             failure = None
