@@ -317,13 +317,48 @@ VITVS_API int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z)
  * The stacked workspace lives in the handle, sized for max_pairs cameras and allocated by the first rig call, which therefore
  * synchronises and must not be made inside a stream capture; later calls may be captured and replayed.
  * With option "robust_law" on the call is error -5: a robust rig law needs ONE median over all cameras' residuals, which the
- * cameras' own re-weighted laws do not give, and is not built.
+ * cameras' own re-weighted laws do not give; that law is vitvs_rig_robust_velocity[_dev] below.
  * Returns 0, -1 (a null required pointer), -5 (no law evaluation yet, n_cams is not its pair count, more than 256 cameras,
  * robust_law on).  Replaces nothing: the reference runs one controller per camera (vitvs_v2.py:702-819). */
 VITVS_API int vitvs_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
                                      int32_t* rig_status, int32_t* rig_info, double* normal, void* stream);
 VITVS_API int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
                                  int32_t* rig_status, int32_t* rig_info, double* normal);
+
+/* --- the robust rig law: Tukey IRLS over the stacked rig system --------------------------------
+ * The rig law above with the re-weighting of option "robust_law" applied to the STACK: one scale, from one median over the live
+ * feature pairs of all contributing cameras.  (Re-weighting every camera by itself and stacking is not this law: a camera whose
+ * own matches are mostly wrong has a median that sits among its outliers; the rig's median does not.)  In fp64, on the same
+ * L_i, e_i, rows and statuses as vitvs_rig_velocity_dev (L_i and e_i are never scaled, also when "robust_law" ran), with
+ * live_i = the camera's matched pairs (vitvs_last_details info[3]; its zero-padded pairs have weight 0 throughout).  A camera
+ * contributes when its status is VITVS_OK and it has rows and a live pair.  M = stack_i(L_i W_i), e = stack_i(e_i); pair k of the
+ * stack is its rows 2k, 2k + 1:
+ *     w_k = 1 on live pairs;   n_iter times:  x = pinv(sqrt(W) M) sqrt(W) e,  rho_k = |e_k - M_k x|_2,
+ *         sigma = max(1.4826 median(rho over ALL live pairs), sigma_min),  t = rho_k / (4.6851 sigma),  w_k = (1 - t^2)^2 or 0 (t >= 1);
+ *     x once more;  v_rig = -lambda x
+ * sigma_min = the largest, over the contributing cameras, of 0.5 max(pitch_u / fx_i, pitch_v / fy_i) ("robust_law"'s floor;
+ * residuals are in normalised image coordinates and compare across cameras).  The median of an even count is the mean of the
+ * two middle values.  Solves as the rig law's: LDL^T of the weighted normal equations (the weight as a factor, pivot test
+ * d > 1e-8 G_jj), behind a failed pivot the Jacobi SVD (rcond 1e-15) of a copy of the rows scaled by sqrt(w).
+ *   cVr, status, v_rig, rig_status   as vitvs_rig_velocity_dev's
+ *   K        double [n_cams][4]: fx, fy, cx, cy of camera i
+ *   n_iter   re-weightings, 1 .. 16
+ *   rig_info int32 [8] or NULL: [0..4] as vitvs_rig_velocity_dev's (cameras used and total rows count contributing cameras),
+ *            [5] the re-weightings done, [6] the pairs of contributing cameras whose final weight is 0, padded ones included, [7] 0
+ *   normal   double [28] or NULL: the weighted G = M^T W M (21), g = M^T W e (6) of the last solve, the total rows
+ *   weights  double [n_cams][max_rows] or NULL: the final weights; 0 on padded pairs, unused pairs and non-contributing cameras
+ *   sigma    double [1] or NULL: the last scale; 0 when no re-weighting ran (no camera contributed)
+ * One launch on `stream`; valid behind the same calls as vitvs_rig_velocity_dev, whether the last law was robust or not, and it
+ * changes nothing that call left.  Bit-reproducible.  Workspace and capture rules as vitvs_rig_velocity_dev's (the two share
+ * the handle's block).  The residuals and weights of the whole rig sit in LDS: n_cams * max_rows pairs beyond ~10,000 are -3.
+ * Returns 0, -1 (a null required pointer), -2 (n_iter outside 1 .. 16), -3, -5 (no law evaluation yet, n_cams is not its pair
+ * count, more than 256 cameras).  No counterpart in the reference. */
+VITVS_API int vitvs_rig_robust_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status,
+                                            const double* K, int32_t n_iter, double* v_rig, int32_t* rig_status, int32_t* rig_info,
+                                            double* normal, double* weights, double* sigma, void* stream);
+VITVS_API int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, const double* K,
+                                        int32_t n_iter, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal,
+                                        double* weights, double* sigma);
 
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own

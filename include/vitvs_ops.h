@@ -114,6 +114,25 @@ VITVS_API int vitvs_op_rig_scratch_bytes(int32_t n_cams, int32_t ld);   /* -2 as
  * cameras' sums, then the solve) instead of the one launch with its in-launch fan-in.  Same results bit for bit.  Returns the
  * previous setting. */
 VITVS_API int vitvs_op_rig_two_launches(int32_t on);
+/* The robust rig law's kernel (vitvs_rig_robust_velocity_dev, include/vitvs.h) on caller systems:
+ *   rows, L, ld, W, lambda, v_rig, rig_status   as vitvs_op_rig_law's; a camera's rows count in pairs (an odd last row is dropped)
+ *   live    int32 [n_cams] or NULL: the live pairs of camera i, the first of its rows (clamped to rows / 2); NULL: every pair.
+ *           A camera without rows or without a live pair does not contribute.
+ *   n_iter  1 .. 16;  sigma_min  the floor of the scale, given directly
+ *   scratch vitvs_op_rig_robust_scratch_bytes(n_cams, ld) = vitvs_op_rig_scratch_bytes + 8 * 7 n_cams ld bytes, zeroed before the
+ *           FIRST call only; the plain op may use the same block
+ *   rig_info [8], normal [28], sigma [1] or NULL as vitvs_rig_robust_velocity_dev's; weights double [n_cams][ld / 2] or NULL
+ * Returns 0, -1 (a null required pointer), -2 (n_cams outside 1 .. 256, ld < 1, n_iter outside 1 .. 16), -3 (the plan's). */
+VITVS_API int vitvs_op_rig_robust_law(int32_t n_cams, const int32_t* rows, const int32_t* live, const double* L, int32_t ld,
+                            const double* W, double lambda, int32_t n_iter, double sigma_min, void* scratch, double* v_rig,
+                            int32_t* rig_status, int32_t* rig_info, double* normal, double* weights, double* sigma, void* stream);
+VITVS_API int vitvs_op_rig_robust_scratch_bytes(int32_t n_cams, int32_t ld);   /* -2 as above, -3 past 2 GiB */
+/* The launch plan of the robust rig law for n_cams cameras of ld rows (host arithmetic, no device): out[0] the dynamic LDS bytes
+ * = 8 (260 + (resident ? 7 * 384 : 0) + 2 pairs), out[1] 1 when the last arriver's copy of the stack is LDS-resident
+ * (n_cams ld <= 384 rows: 8 cameras x 48), out[2] pairs = n_cams (ld / 2), the residuals and weights held in LDS, out[3] 1 when
+ * the launch opts in to more than 64 KiB.  Returns 0, -1 (out NULL), -2 (n_cams outside 1 .. 256, ld < 1; out untouched but
+ * zeroed), -3 (out filled): more than 160 KiB of LDS. */
+VITVS_API int vitvs_op_rig_robust_plan(int32_t n_cams, int32_t ld, int32_t* out);
 /* The fused Gram arg-max of the velocity path on caller-normalised descriptors dn [n_des + n_pairs][T][Dp] fp32 (desired frames
  * first; n_des = 1 with des_shared): the plan of vitvs_op_gram_plan(precision, 0, T, Dp, n_pairs, n_pairs), the split into dh
  * (3 (n_des + n_pairs) T Dp fp16, only when the plan splits) and the keys row_best / col_best [n_pairs][T] (cleared here), decoded

@@ -178,9 +178,14 @@ class ServoParams:
     interaction: str = "current"   # the interaction matrix the law inverts (option "interaction"): "current" L(s, Z), the reference's;
                                    # "desired" L(s*, Z*); "mean" of the two.  The last two need a goal depth (Engine.set_goal_depth)
 
+    rig_robust_iterations: int = 0  # Tukey re-weightings of the RIG law (MultiController(rig=...): one median over all cameras'
+                                    # residuals, vitvs_rig_robust_velocity_dev; 1 .. 16); 0 = the plain rig law
+
     def __post_init__(self):
         if self.interaction not in INTERACTIONS:
             raise ValueError(f"interaction is one of {INTERACTIONS}, got {self.interaction!r}")
+        if not 0 <= int(self.rig_robust_iterations) <= 16:
+            raise ValueError(f"rig_robust_iterations is 0 .. 16, got {self.rig_robust_iterations!r}")
 
     @property
     def c_x(self) -> float:
@@ -256,10 +261,11 @@ def load_reference_config(source) -> ReferenceConfig:
                         dino_input_size=int(cfg["dino_input_size"]), use_feature_binning=bool(cfg["use_feature_binning"]),
                         ema_alpha=float(cfg.get("ema_alpha", 0.1)), max_velocity=float(cfg.get("max_velocity", 1.0)),
                         robust_iterations=int(cfg.get("robust_iterations", 0)), subpatch=bool(cfg.get("subpatch", False)),
-                        interaction=str(cfg.get("interaction", "current")))
+                        interaction=str(cfg.get("interaction", "current")),
+                        rig_robust_iterations=int(cfg.get("rig_robust_iterations", 0)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
-            "subpatch", "interaction"}
+            "subpatch", "interaction", "rig_robust_iterations"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -130,6 +130,7 @@ struct vitvs_handle {
     // at max_pairs cameras, and the device side of the host-pointer form, allocated by the first rig call
     unsigned char* rig_ws = nullptr;
     unsigned char* rig_io = nullptr;   // cVr [max_pairs][36] f64 | v_rig [6] | normal [28] | status [max_pairs] i32 | rig_status | rig_info [8]
+                                       // | (rig_io_head) K [max_pairs][4] f64 | sigma | weights [max_pairs][max_rows]
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -1591,18 +1592,23 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
 }
 
 // --- the rig law ---------------------------------------------------------------------------------
-static int rig_prepare(vitvs_handle* h, int n_cams) {
+// bytes of rig_io's first part (see vitvs_handle::rig_io); the robust form's K, sigma and weights follow it
+static size_t rig_io_head(size_t P) { return (P * 36 * 8 + 34 * 8 + (P + 9) * 4 + 63) & ~(size_t)63; }
+
+static int rig_prepare(vitvs_handle* h, int n_cams, bool robust_form = false) {
     if (!h->last_pairs) return set_err(h, -5, "vitvs_rig_velocity follows a velocity call on the same handle");
     if (n_cams != h->last_pairs)
         return set_err(h, -5, "n_cams (" + std::to_string(n_cams) + ") is not the pair count of the last law evaluation (" +
                                   std::to_string(h->last_pairs) + ")");
-    if (h->last_law.robust || h->robust_iters)
-        return set_err(h, -5, "the rig law does not combine with option robust_law (one median over all cameras' residuals: not built)");
+    if (!robust_form && (h->last_law.robust || h->robust_iters))
+        return set_err(h, -5, "the rig law does not combine with option robust_law (one median over all cameras' residuals: "
+                              "vitvs_rig_robust_velocity)");
     if (n_cams > kRigMaxCams) return set_err(h, -5, "the rig law takes at most " + std::to_string(kRigMaxCams) + " cameras");
     if (!h->rig_ws) {                           // set-up, not the call path (and never inside a capture): as vitvs_set_goal_depth_dev
         const size_t P = h->cfg.max_pairs;
-        int rc = dev_alloc(h, &h->rig_ws, rig_scratch_bytes((int)P, 2 * h->cfg.max_rows));
-        if (!rc) rc = dev_alloc(h, &h->rig_io, P * 36 * 8 + 34 * 8 + (P + 9) * 4 + 64);
+        // (sized for the robust form, a third block of stacked rows, whichever form comes first: allocated once)
+        int rc = dev_alloc(h, &h->rig_ws, rig_robust_scratch_bytes((int)P, 2 * h->cfg.max_rows));
+        if (!rc) rc = dev_alloc(h, &h->rig_io, rig_io_head(P) + (P * 4 + 1 + P * (size_t)h->cfg.max_rows) * 8);
         if (rc) return set_err(h, rc, "rig workspace allocation failed");
         VITVS_HIP_CHECK(hipDeviceSynchronize());   // the blocks (the ticket above all) are zero before any stream uses them
     }
@@ -1646,6 +1652,66 @@ int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const
     VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
     if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
     if (normal) VITVS_HIP_CHECK(hipMemcpy(normal, d_normal, 28 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// --- the robust rig law ----------------------------------------------------------------------------
+int vitvs_rig_robust_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, const double* K,
+                                  int32_t n_iter, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal,
+                                  double* weights, double* sigma, void* stream) {
+    if (!h || !cVr || !status || !K || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    if (n_iter < 1 || n_iter > 16) return set_err(h, -2, "n_iter is 1 .. 16");
+    DeviceScope dev(h);
+    if (int rc = rig_prepare(h, n_cams, true)) return rc;
+    const vitvs_config& c = h->cfg;
+    RigRobustArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    RigArgs& a = ra.r;
+    a.n_cams = n_cams; a.status = status; a.rows = h->info + 5; a.rows_stride = 8;
+    a.L = h->Lws; a.ld = 2 * c.max_rows; a.W = cVr; a.lambda = c.lambda;
+    rig_robust_carve(h->rig_ws, c.max_pairs, a.ld, ra);
+    a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
+    ra.live = h->info + 3; ra.live_stride = 8; ra.K = K; ra.n_iter = n_iter;
+    ra.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
+    ra.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    ra.weights = weights; ra.weights_stride = c.max_rows; ra.sigma = sigma;
+    const int rc = launch_rig_robust(ra, as_stream(stream));
+    if (rc == -3) return set_err(h, rc, "the robust rig law keeps two doubles per feature pair of the rig in LDS: n_cams * max_rows is too large");
+    return rc ? set_err(h, rc, "robust rig law launch failed") : 0;
+}
+
+int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, const double* K,
+                              int32_t n_iter, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal,
+                              double* weights, double* sigma) {
+    if (!h || !cVr || !status || !K || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    if (n_iter < 1 || n_iter > 16) return set_err(h, -2, "n_iter is 1 .. 16");
+    DeviceScope dev(h);
+    if (int rc = rig_prepare(h, n_cams, true)) return rc;
+    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
+    double* d_W = reinterpret_cast<double*>(h->rig_io);
+    double* d_v = d_W + P * 36;
+    double* d_normal = d_v + 6;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_normal + 28);
+    int32_t* d_rig_status = d_status + P;
+    int32_t* d_info = d_rig_status + 1;
+    double* d_K = reinterpret_cast<double*>(h->rig_io + rig_io_head(P));
+    double* d_sigma = d_K + P * 4;
+    double* d_weights = d_sigma + 1;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    VITVS_HIP_CHECK(hipMemcpy(d_W, cVr, (size_t)n_cams * 36 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_status, status, (size_t)n_cams * 4, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_K, K, (size_t)n_cams * 4 * 8, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = vitvs_rig_robust_velocity_dev(h, n_cams, d_W, d_status, d_K, n_iter, d_v, d_rig_status, d_info, d_normal, d_weights,
+                                               d_sigma, st))
+        return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
+    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
+    if (normal) VITVS_HIP_CHECK(hipMemcpy(normal, d_normal, 28 * 8, hipMemcpyDeviceToHost));
+    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, (size_t)n_cams * R * 8, hipMemcpyDeviceToHost));
+    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1797,6 +1863,37 @@ int vitvs_op_rig_scratch_bytes(int32_t n_cams, int32_t ld) {
     if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
     const size_t b = rig_scratch_bytes(n_cams, ld);
     return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_rig_robust_law(int32_t n_cams, const int32_t* rows, const int32_t* live, const double* L, int32_t ld, const double* W,
+                            double lambda, int32_t n_iter, double sigma_min, void* scratch, double* v_rig, int32_t* rig_status,
+                            int32_t* rig_info, double* normal, double* weights, double* sigma, void* stream) {
+    if (!rows || !L || !W || !scratch || !v_rig || !rig_status) return -1;
+    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1 || n_iter < 1 || n_iter > 16) return -2;
+    RigRobustArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    RigArgs& a = ra.r;
+    a.n_cams = n_cams; a.rows = rows; a.rows_stride = 1; a.L = L; a.ld = ld; a.W = W; a.lambda = lambda;
+    rig_robust_carve(scratch, n_cams, ld, ra);
+    a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
+    ra.live = live; ra.live_stride = 1; ra.n_iter = n_iter; ra.sigma_min = sigma_min;
+    ra.weights = weights; ra.weights_stride = ld / 2; ra.sigma = sigma;
+    return launch_rig_robust(ra, as_stream(stream));
+}
+
+int vitvs_op_rig_robust_scratch_bytes(int32_t n_cams, int32_t ld) {
+    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
+    const size_t b = rig_robust_scratch_bytes(n_cams, ld);
+    return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_rig_robust_plan(int32_t n_cams, int32_t ld, int32_t* out) {
+    if (!out) return -1;
+    RigRobustPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_rig_robust(n_cams, ld, &pl);
+    out[0] = (int32_t)pl.lds; out[1] = pl.lds_resident; out[2] = pl.pairs; out[3] = pl.lds_opt_in;
+    return rc;
 }
 
 int vitvs_op_rig_two_launches(int32_t on) {

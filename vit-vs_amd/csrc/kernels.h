@@ -390,6 +390,38 @@ void rig_carve(void* scratch, int n_cams, int ld, RigArgs& a);
 // tools/rig_times.py times it against).  -2: n_cams outside 1 .. kRigMaxCams, ld < 1, cap < n_cams * ld, a null pointer
 int launch_rig(const RigArgs& a, hipStream_t stream, bool two_launches = false);
 
+// The robust rig law: Tukey IRLS over the stacked system, ONE median over the live pairs of all contributing
+// cameras.  Same launch shape and fan-in as the rig law; the workgroup that arrives last copies the stack once (into LDS while
+// n_cams * ld <= kRigRobustTile rows, else into `work`) and runs the n_iter re-weightings and n_iter + 1 weighted solves with all
+// four waves, as servo_kernel<true, .> does for one camera.  A camera contributes when its status is ST_OK, it has rows and a
+// live pair; its rows count in pairs (an odd last row is dropped).
+constexpr int kRigRobustTile = 384;   // stacked rows kept in LDS: 8 cameras x 48 rows
+struct RigRobustArgs {
+    RigArgs r;                // as the rig law's; r.part is not used, r.normal takes the weighted G, g of the last solve
+    const int32_t* live;      // live pairs of camera i at live[i * live_stride] (the first pairs of its rows); null: every pair
+    int live_stride;
+    const double* K;          // [n_cams][4] fx, fy, cx, cy: sigma_min = max_i 0.5 max(pitch_u / fx_i, pitch_v / fy_i); null: sigma_min
+    double pitch_u, pitch_v;
+    double sigma_min;
+    int n_iter;               // 1 .. 16
+    double* work2;            // [7][cap] the Jacobi SVD's copy when `work` holds the stack
+    double* weights;          // [n_cams][weights_stride] or null: the final weights, 0 where no live pair of a contributing camera is
+    int weights_stride;
+    double* sigma;            // [1] or null: the last scale
+};
+struct RigRobustPlan {
+    size_t lds;               // dynamic LDS of the launch
+    bool lds_resident;        // the stack's copy sits in LDS
+    bool lds_opt_in;          // > 64 KiB
+    int pairs;                // n_cams * (ld / 2): the residuals and weights the LDS holds
+};
+// -2: n_cams outside 1 .. kRigMaxCams, ld < 1; -3 (plan filled): more than 160 KiB of LDS
+int plan_rig_robust(int n_cams, int ld, RigRobustPlan* plan);
+// the rig law's block and a third [7][cap] block (work2)
+size_t rig_robust_scratch_bytes(int n_cams, int ld);
+void rig_robust_carve(void* scratch, int n_cams, int ld, RigRobustArgs& a);
+int launch_rig_robust(const RigRobustArgs& a, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

@@ -193,4 +193,270 @@ int launch_rig(const RigArgs& a, hipStream_t stream, bool two_launches) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---- the robust rig law --------------------------------------------------------------------------------------
+// Tukey IRLS over the stacked system with ONE median over the live pairs of all contributing cameras: the rig law's launch shape
+// and its fan-in, word for word (the four conditions of the header, with "all 256 threads of the last arriver, behind the
+// workgroup barrier its wave 0 joins after the add has returned" in place of "wave 0 alone" in (1): the same row of the table
+// allows both).  The cameras store their rows and e and nothing else: the first solve is weighted already (a zero-padded pair
+// has weight 0), so no camera's own 27 sums are of use.  The last arriver copies the stack ONCE with sc1 loads, into LDS when
+// n_cams * ld <= kRigRobustTile, else into `work` (which it alone writes and reads, plain accesses from there on), and runs
+// servo_kernel<true, .>'s loop on it: the 27 x 8-slice weighted sums (solve.h), wave 0's solve, the residuals, the median by
+// rank counting, the weights.  A pair that is not live carries rho = +inf from the start to the end: it ranks behind every live
+// pair, takes weight 0 from the weight formula itself and is skipped by the residual pass.
+// dynamic LDS, in doubles: Gs [256] (solve.h's layout; [28 .. 34) x, [34] [35] the two middle residuals) | 4: the ticket drawn
+// and four counts as ints | tile [7][kRigRobustTile] when resident | rho [pairs] | w [pairs]
+constexpr int kRigRobustHead = 256 + 4;
+constexpr unsigned long long kInfBits = 0x7ff0000000000000ull;
+
+// rows (even) camera i contributes, its live pairs and its status
+__device__ __forceinline__ int rig_robust_camera(const RigRobustArgs& ra, int i, int& lv, int& st) {
+    const RigArgs& a = ra.r;
+    const int ri = min(max(a.rows[(size_t)i * a.rows_stride], 0), a.ld) & ~1;
+    st = a.status ? a.status[i] : (ri > 0 ? ST_OK : ST_TOO_FEW);
+    lv = ra.live ? min(max(ra.live[(size_t)i * ra.live_stride], 0), ri >> 1) : (ri >> 1);
+    const int eff = (st == ST_OK && lv > 0) ? ri : 0;
+    if (eff == 0) lv = 0;
+    return eff;
+}
+
+// The two middle values of rho[0 .. n) among its n_live smallest into Gs[34], Gs[35]: rank counting as in servo.hip (integer
+// compares on the bit patterns of values >= +0, ties by index: every value has a rank of its own and each cell one writer).
+__device__ __forceinline__ void rig_robust_middles(const double* rho, int n, int n_live, double* Gs, int tid) {
+    const int m_lo = (n_live - 1) >> 1, m_hi = n_live >> 1;
+    if (n <= 256) {
+        if (tid < n) {
+            const long long ki = __double_as_longlong(rho[tid]);
+            int rank = 0;
+#pragma unroll 4
+            for (int j = 0; j < n; ++j) {
+                const long long kj = __double_as_longlong(rho[j]);
+                rank += (int)(kj < ki) | ((int)(kj == ki) & (int)(j < tid));
+            }
+            if (rank == m_lo) Gs[34] = __longlong_as_double(ki);
+            if (rank == m_hi) Gs[35] = __longlong_as_double(ki);
+        }
+    } else {
+        for (int i0 = tid; i0 < n; i0 += 4 * 256) {
+            long long ki[4];
+            int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
+#pragma unroll 4
+            for (int j = 0; j < n; ++j) {
+                const long long kj = __double_as_longlong(rho[j]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + 256 * u < n && rank[u] == m_lo) Gs[34] = __longlong_as_double(ki[u]);
+                if (i0 + 256 * u < n && rank[u] == m_hi) Gs[35] = __longlong_as_double(ki[u]);
+            }
+        }
+    }
+}
+
+// RESIDENT: the stack's copy sits in LDS (the plan's lds_resident)
+template <bool RESIDENT>
+__global__ __launch_bounds__(256) void rig_robust_kernel(RigRobustArgs ra) {
+    extern __shared__ __attribute__((aligned(16))) double smr[];
+    const RigArgs& a = ra.r;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.n_cams;
+    constexpr bool resident = RESIDENT;
+    double* Gs = smr;
+    int* iscr = reinterpret_cast<int*>(smr + 256);              // [0] the ticket drawn, [1 .. 4] the waves' zero weights
+    double* tile = smr + kRigRobustHead;
+    double* rho = tile + (resident ? 7 * kRigRobustTile : 0);
+    double* wk = rho + n * (a.ld >> 1);
+
+    int off = 0, total = 0, used = 0, worst = 0, R = 0, n_live = 0;
+    for (int i = 0; i < n; ++i) {
+        int lv, st;
+        const int eff = rig_robust_camera(ra, i, lv, st);
+        if (i < b) off += eff;
+        if (i == b) R = eff;
+        total += eff;
+        n_live += lv;
+        used += eff > 0 ? 1 : 0;
+        worst = max(worst, st);
+    }
+
+    // Phase A: this camera's rows of M = L W (the rig law's order of sums) and e, behind the contributing cameras before it
+    if (R > 0) {
+        double W[36];
+#pragma unroll
+        for (int i = 0; i < 36; ++i) W[i] = a.W[(size_t)b * 36 + i];
+        const double* Lb = a.L + (size_t)b * 7 * a.ld;
+        for (int r = tid; r < R; r += 256) {
+            double l[7];
+#pragma unroll
+            for (int c = 0; c < 7; ++c) l[c] = Lb[(size_t)c * a.ld + r];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                double m = 0.0;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) m += l[c] * W[c * 6 + j];
+                store_wt(a.stack + (size_t)j * a.cap + off + r, m);
+            }
+            store_wt(a.stack + (size_t)6 * a.cap + off + r, l[6]);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its stores ...
+    __syncthreads();                                       // ... before the workgroup's one ticket
+    if (tid == 0) {
+        const int drawn = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (drawn == n - 1) __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+        iscr[0] = drawn;
+    }
+    __syncthreads();
+    if (iscr[0] != n - 1) return;                          // another workgroup finishes the rig
+
+    // The last arriver, all four waves from here.  The one copy of the stack: every byte by an sc1 load to a register.
+    const int rcap = resident ? kRigRobustTile : a.cap;
+    double* Lc = resident ? tile : a.work;
+    for (int c = 0; c < 7; ++c)
+        for (int r = tid; r < total; r += 256) Lc[(size_t)c * rcap + r] = load_wt(a.stack + (size_t)c * a.cap + r);
+    const int P = total >> 1;
+    double sigma_min = ra.sigma_min;
+    {
+        int o = 0;
+        double smin = 0.0;
+        for (int i = 0; i < n; ++i) {
+            int lv, st;
+            const int eff = rig_robust_camera(ra, i, lv, st);
+            for (int p = tid; p < (eff >> 1); p += 256) {
+                wk[o + p] = p < lv ? 1.0 : 0.0;
+                rho[o + p] = p < lv ? 0.0 : __longlong_as_double((long long)kInfBits);
+            }
+            if (eff > 0 && ra.K) smin = fmax(smin, 0.5 * fmax(ra.pitch_u / ra.K[i * 4 + 0], ra.pitch_v / ra.K[i * 4 + 1]));
+            o += eff >> 1;
+        }
+        if (ra.K) sigma_min = smin;
+    }
+    __syncthreads();                                       // (the stack's copy may be global memory: full fence)
+
+    double vout[6] = {0, 0, 0, 0, 0, 0};
+    double sigma = 0.0;
+    int sweeps = 0, reweighted = 0, n_zero = 0;
+    if (total > 0) {
+        const int N = ra.n_iter;
+        for (int it = 0;; ++it) {
+            normal_equation_slices(Lc, rcap, total, wk, Gs, tid);
+            lds_barrier();
+            if (wave == 0) {
+                double xsol[6];
+                const bool solved = solve_ldlt(Gs, lane, xsol);
+                sweeps = -1;
+                if (!solved) {
+                    // each lane scales and copies the rows it alone rotates (r = lane mod 64)
+                    double* Lw = resident ? a.work : ra.work2;
+                    for (int r = lane; r < total; r += 64) {
+                        const double sw = sqrt(wk[r >> 1]);
+                        for (int c = 0; c < 7; ++c) Lw[(size_t)c * a.cap + r] = sw * Lc[(size_t)c * rcap + r];
+                    }
+                    sweeps = solve_jacobi(Lw, a.cap, total, lane, xsol);
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    vout[i] = -a.lambda * xsol[i];
+                    if (lane == 0) Gs[28 + i] = xsol[i];
+                }
+                if (lane == 0) { Gs[34] = 0.0; Gs[35] = 0.0; }
+            }
+            if (it == N) break;
+            lds_barrier();
+            double x[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) x[i] = Gs[28 + i];
+            for (int k = tid; k < P; k += 256) {
+                if ((unsigned long long)__double_as_longlong(rho[k]) == kInfBits) continue;    // not a live pair
+                double r0 = Lc[(size_t)6 * rcap + 2 * k], r1 = Lc[(size_t)6 * rcap + 2 * k + 1];
+                double p0 = 0.0, p1 = 0.0;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    p0 += Lc[(size_t)c * rcap + 2 * k] * x[c];
+                    p1 += Lc[(size_t)c * rcap + 2 * k + 1] * x[c];
+                }
+                r0 -= p0; r1 -= p1;
+                rho[k] = sqrt(r0 * r0 + r1 * r1);
+            }
+            lds_barrier();
+            rig_robust_middles(rho, P, n_live, Gs, tid);
+            lds_barrier();
+            sigma = fmax(1.4826 * ((Gs[34] + Gs[35]) * 0.5), sigma_min);
+            const double cs = 4.6851 * sigma;
+            int zeros = 0;
+            for (int k = tid; k < P; k += 256) {
+                const double t = rho[k] / cs;
+                const double u = 1.0 - t * t;
+                const double w1 = t < 1.0 ? u * u : 0.0;
+                wk[k] = w1;
+                zeros += w1 == 0.0 ? 1 : 0;
+            }
+            zeros = wave_sum(zeros);
+            if (lane == 0) iscr[1 + wave] = zeros;
+            lds_barrier();
+            n_zero = iscr[1] + iscr[2] + iscr[3] + iscr[4];
+            reweighted = it + 1;
+        }
+    }
+    if (ra.weights) {
+        int o = 0;
+        for (int i = 0; i < n; ++i) {
+            int lv, st;
+            const int eff = rig_robust_camera(ra, i, lv, st);
+            for (int p = tid; p < ra.weights_stride; p += 256)
+                ra.weights[(size_t)i * ra.weights_stride + p] = p < (eff >> 1) ? wk[o + p] : 0.0;
+            o += eff >> 1;
+        }
+    }
+    if (wave != 0) return;
+    if (a.normal && lane < 28) a.normal[lane] = total > 0 ? (lane < 27 ? Gs[lane] : (double)total) : 0.0;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.v_rig[i] = vout[i];
+        *a.rig_status = total > 0 ? (int)ST_OK : max(worst, (int)ST_NO_CORRESPONDENCE);
+        if (ra.sigma) *ra.sigma = sigma;
+        if (a.rig_info) {
+            a.rig_info[0] = used; a.rig_info[1] = total; a.rig_info[2] = sweeps; a.rig_info[3] = n;
+            a.rig_info[4] = worst; a.rig_info[5] = reweighted; a.rig_info[6] = n_zero; a.rig_info[7] = 0;
+        }
+    }
+}
+
+int plan_rig_robust(int n_cams, int ld, RigRobustPlan* plan) {
+    if (!plan || n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
+    RigRobustPlan& p = *plan;
+    p.lds_resident = (long)n_cams * ld <= kRigRobustTile;
+    p.pairs = (int)std::min<long>((long)n_cams * (ld / 2), 1 << 28);
+    p.lds = ((size_t)kRigRobustHead + (p.lds_resident ? 7 * kRigRobustTile : 0) + (size_t)2 * p.pairs) * sizeof(double);
+    p.lds_opt_in = p.lds > 64 * 1024;
+    return p.lds > 160 * 1024 ? -3 : 0;
+}
+
+size_t rig_robust_scratch_bytes(int n_cams, int ld) { return rig_scratch_bytes(n_cams, ld) + (size_t)7 * n_cams * ld * sizeof(double); }
+
+void rig_robust_carve(void* scratch, int n_cams, int ld, RigRobustArgs& a) {
+    rig_carve(scratch, n_cams, ld, a.r);
+    a.work2 = a.r.work + (size_t)7 * a.r.cap;
+}
+
+int launch_rig_robust(const RigRobustArgs& ra, hipStream_t stream) {
+    const RigArgs& a = ra.r;
+    if (a.n_cams < 1 || a.n_cams > kRigMaxCams || a.ld < 1 || a.rows_stride < 1 || (long)a.cap < (long)a.n_cams * a.ld) return -2;
+    if (ra.n_iter < 1 || ra.n_iter > 16 || (ra.live && ra.live_stride < 1) || (ra.weights && ra.weights_stride < 0)) return -2;
+    if (!a.rows || !a.L || !a.W || !a.stack || !a.work || !ra.work2 || !a.ticket || !a.v_rig || !a.rig_status) return -2;
+    RigRobustPlan p;
+    if (int rc = plan_rig_robust(a.n_cams, a.ld, &p)) return rc;
+    static std::atomic<unsigned long long> raised{0};
+    if (p.lds_resident) {                                  // (at most 8 (260 + 7 * 384 + 384) bytes: no opt-in)
+        launch(rig_robust_kernel<true>, dim3(a.n_cams), dim3(256), p.lds, stream, ra);
+    } else {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(rig_robust_kernel<false>), 160 * 1024, raised)) return -3;
+        launch(rig_robust_kernel<false>, dim3(a.n_cams), dim3(256), p.lds, stream, ra);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace vitvs

@@ -62,38 +62,6 @@ __device__ __forceinline__ void refined_pixel(const ServoArgs& a, int tok, float
     v = (long)rint(((double)r + (double)dr * a.pitch_in) * a.scale_y);
 }
 
-// G = L^T W L (21, upper triangle) and g = L^T W e (6): 27 quantities x 8 row slices on 216 threads into Gs[40 ..) (fixed
-// slice order -> deterministic), W = wk[pair] on both rows of a pair.
-__device__ __forceinline__ void normal_equation_slices(const double* Lc, int rcap, int R, const double* wk, double* Gs, int tid) {
-    const int qid = tid & 31, slice = tid >> 5;
-    if (qid < 27) {
-        int ca, cb;
-        if (qid < 21) {
-            int q = qid;
-            ca = 0;
-            while (q >= 6 - ca) { q -= 6 - ca; ++ca; }
-            cb = ca + q;
-        } else {
-            ca = qid - 21;
-            cb = 6;
-        }
-        // 4 independent chains keep 8 loads in flight (dense selections read L from the global workspace);
-        // fixed combination order -> still deterministic
-        double acc4[4] = {0.0, 0.0, 0.0, 0.0};
-        int r = slice;
-        for (; r + 24 < R; r += 32) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc4[u] += wk[(r + 8 * u) >> 1] * (Lc[ca * rcap + r + 8 * u] * Lc[cb * rcap + r + 8 * u]);
-            }
-        }
-        for (; r < R; r += 8) {
-            acc4[0] += wk[r >> 1] * (Lc[ca * rcap + r] * Lc[cb * rcap + r]);
-        }
-        Gs[40 + slice * 27 + qid] = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
-    }
-}
-
 // The leading flat arguments repeat the fields of `a` the first memory requests depend on: they are
 // preloaded into SGPRs by the command processor (kernarg preload), the struct is fetched by the wave.
 template <bool ROBUST, bool REFINE, bool GOALZ>

@@ -12,6 +12,38 @@ namespace vitvs {
 // stores and prefetched loads must stay in flight across the phase boundaries.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// G = L^T W L (21, upper triangle) and g = L^T W e (6): 27 quantities x 8 row slices on 216 threads into Gs[40 ..) (fixed
+// slice order -> deterministic), W = wk[pair] on both rows of a pair.
+__device__ __forceinline__ void normal_equation_slices(const double* Lc, int rcap, int R, const double* wk, double* Gs, int tid) {
+    const int qid = tid & 31, slice = tid >> 5;
+    if (qid < 27) {
+        int ca, cb;
+        if (qid < 21) {
+            int q = qid;
+            ca = 0;
+            while (q >= 6 - ca) { q -= 6 - ca; ++ca; }
+            cb = ca + q;
+        } else {
+            ca = qid - 21;
+            cb = 6;
+        }
+        // 4 independent chains keep 8 loads in flight (dense selections read L from the global workspace);
+        // fixed combination order -> still deterministic
+        double acc4[4] = {0.0, 0.0, 0.0, 0.0};
+        int r = slice;
+        for (; r + 24 < R; r += 32) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                acc4[u] += wk[(r + 8 * u) >> 1] * (Lc[ca * rcap + r + 8 * u] * Lc[cb * rcap + r + 8 * u]);
+            }
+        }
+        for (; r < R; r += 8) {
+            acc4[0] += wk[r >> 1] * (Lc[ca * rcap + r] * Lc[cb * rcap + r]);
+        }
+        Gs[40 + slice * 27 + qid] = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
+    }
+}
+
 // One wavefront: 27 lanes add the 8 slices, every lane then factors the same 6x6 system in registers (fully unrolled: no
 // private-memory arrays, no cross-lane traffic).  True, and xsol = G^-1 g, when every pivot passes the 1e-8 test.
 __device__ __forceinline__ bool solve_ldlt(double* Gs, int lane, double xsol[6]) {

@@ -66,7 +66,7 @@ def unpack_normal(normal: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return G, normal[21:27]
 
 
-def rig_velocity(normal_local: torch.Tensor, lam: float, group=None) -> torch.Tensor:
+def rig_velocity(normal_local: torch.Tensor, lam: float, group=None, robust_iterations: int = 0) -> torch.Tensor:
     """The rig law (include/vitvs.h, vitvs_rig_velocity_dev) for a rig spread over ranks: one camera, or one shard of cameras,
     per GPU.  ``normal_local`` is the 28 doubles this rank's rig call left (``Engine.rig_velocity(...)[2]["normal"]``: the normal
     equations G = M^T M, g = M^T e of ITS cameras' stacked rows, and their row count; all zeros when none of its cameras
@@ -77,7 +77,14 @@ def rig_velocity(normal_local: torch.Tensor, lam: float, group=None) -> torch.Te
     ``torch.linalg.pinv(G, hermitian=True)`` applies its cut-off (eigenvalues below ~6 eps |lambda|_max) to G, whose condition is
     that of M squared — not numpy's rcond = 1e-15 on M as the single-GPU kernel's Jacobi path does: the two agree for the
     well-conditioned stacks a rig produces (tests/test_rig_gloo.py, <= 1e-9) and differ for a stack whose smallest singular value
-    is below ~1e-8 of its largest, which the sum of normal equations cannot resolve."""
+    is below ~1e-8 of its largest, which the sum of normal equations cannot resolve.
+
+    ``robust_iterations`` > 0 raises ``ValueError``: the robust rig law (``Engine.rig_velocity(..., robust_iterations=N)``) takes
+    one median over ALL cameras' residuals per re-weighting, which across ranks is another collective per iteration and is not
+    built; it runs on one GPU."""
+    if int(robust_iterations) != 0:
+        raise ValueError("the robust rig law is not built across ranks (a median over all ranks' residuals per re-weighting); "
+                         "run the rig's cameras on one handle: Engine.rig_velocity(..., robust_iterations=N)")
     import torch.distributed as dist
     if normal_local.shape != (28,) or normal_local.dtype != torch.float64:
         raise ValueError("normal_local is the float64 [28] a rig call writes")

@@ -473,35 +473,78 @@ class Engine:
         self._check(rc, "vitvs_last_details")
         return dict(info=info, s_uv=suv, feat=feat)
 
-    def rig_velocity(self, cVr, status):
+    @staticmethod
+    def _rig_robust_arguments(n, robust_iterations, K):
+        """The checks of the robust rig law's extra arguments (no handle needed): float64 [n, 4] intrinsics, or None for N = 0."""
+        N = int(robust_iterations)
+        if not 0 <= N <= 16:
+            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        if N == 0:
+            return None
+        if K is None:
+            raise ValueError("robust_iterations > 0 needs K: the cameras' intrinsics (fx, fy, cx, cy), one row per camera or one for all")
+        k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
+        k = np.broadcast_to(k.reshape(-1, 4), (n, 4)) if k.size == 4 else k.reshape(-1, 4)
+        if k.shape[0] != n:
+            raise ValueError("one (fx, fy, cx, cy) per camera expected")
+        return np.ascontiguousarray(k)
+
+    def rig_velocity(self, cVr, status, robust_iterations: int = 0, K=None):
         """``vitvs_rig_velocity_dev``: the ONE twist of a rigid rig whose cameras were the pairs of the last velocity call, from
         what that call left in the handle.  ``cVr``: float64 [n, 6, 6], camera i's twist transform from the rig frame
         (``servo.twist_matrix``); ``status``: the int32 [n] the velocity call returned (a device tensor stays on the device).
         Returns ``(v_rig float64 tensor [6] on the device, rig_status int, info)`` with ``info`` = dict(cameras, rows, sweeps
-        (-1: LDL^T), worst_status, normal float64 [28] device tensor: G upper triangle, g, rows).  Reading the status synchronises."""
-        w = torch.as_tensor(cVr, dtype=torch.float64).reshape(-1, 36).to(self.device).contiguous()
+        (-1: LDL^T), worst_status, normal float64 [28] device tensor: G upper triangle, g, rows).  Reading the status synchronises.
+
+        ``robust_iterations`` = N > 0: ``vitvs_rig_robust_velocity_dev``, Tukey IRLS over the stacked system with one median over
+        all cameras' residuals (valid with option ``robust_law`` on or off); ``K`` (required then) the cameras' intrinsics, [n, 4]
+        or one (fx, fy, cx, cy) for all.  ``info`` gains ``reweighted``, ``zero_weights``, ``sigma`` (float) and ``weights``
+        (float64 [n, max_rows] device tensor, 0 on padded and unused pairs and on cameras that did not contribute)."""
+        w = torch.as_tensor(cVr, dtype=torch.float64).reshape(-1, 36)
         n = int(w.shape[0])
+        k = self._rig_robust_arguments(n, robust_iterations, K)      # (before anything touches the device)
+        w = w.to(self.device).contiguous()
         st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
         if st.numel() != n:
             raise VitvsError("one status per camera expected")
         v = torch.empty(6, dtype=torch.float64, device=self.device)
         out = torch.empty(9, dtype=torch.int32, device=self.device)      # rig_status | rig_info [8]
         normal = torch.empty(28, dtype=torch.float64, device=self.device)
-        rc = self.lib.vitvs_rig_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(v), _ptr(out), _ptr(out[1:]), _ptr(normal),
-                                             _stream_ptr(self.device))
-        self._check(rc, "vitvs_rig_velocity_dev")
+        if k is None:
+            rc = self.lib.vitvs_rig_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(v), _ptr(out), _ptr(out[1:]), _ptr(normal),
+                                                 _stream_ptr(self.device))
+            self._check(rc, "vitvs_rig_velocity_dev")
+            o = out.cpu().numpy()
+            return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal)
+        kd = torch.from_numpy(k).to(self.device)
+        weights = torch.empty((n, self.max_rows), dtype=torch.float64, device=self.device)
+        sigma = torch.empty(1, dtype=torch.float64, device=self.device)
+        rc = self.lib.vitvs_rig_robust_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(kd), int(robust_iterations), _ptr(v),
+                                                    _ptr(out), _ptr(out[1:]), _ptr(normal), _ptr(weights), _ptr(sigma),
+                                                    _stream_ptr(self.device))
+        self._check(rc, "vitvs_rig_robust_velocity_dev")
         o = out.cpu().numpy()
-        return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal)
+        return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal,
+                                  reweighted=int(o[6]), zero_weights=int(o[7]), sigma=float(sigma.cpu()[0]), weights=weights)
 
-    def rig_velocity_host(self, cVr, status):
-        """``vitvs_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info [8] int32, normal [28])`` out."""
+    def rig_velocity_host(self, cVr, status, robust_iterations: int = 0, K=None):
+        """``vitvs_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info [8] int32, normal [28])``
+        out; with ``robust_iterations`` > 0 (``vitvs_rig_robust_velocity``, ``K`` as ``rig_velocity`` takes it) two more:
+        ``weights`` float64 [n, max_rows] and ``sigma``."""
         w = np.ascontiguousarray(np.asarray(cVr, np.float64).reshape(-1, 36))
+        k = self._rig_robust_arguments(int(w.shape[0]), robust_iterations, K)
         st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
         v, rs, info, normal = np.zeros(6), np.zeros(1, np.int32), np.zeros(8, np.int32), np.zeros(28)
         p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.vitvs_rig_velocity(self.handle, int(w.shape[0]), p(w), p(st), p(v), p(rs), p(info), p(normal))
-        self._check(rc, "vitvs_rig_velocity")
-        return v, int(rs[0]), info, normal
+        if k is None:
+            rc = self.lib.vitvs_rig_velocity(self.handle, int(w.shape[0]), p(w), p(st), p(v), p(rs), p(info), p(normal))
+            self._check(rc, "vitvs_rig_velocity")
+            return v, int(rs[0]), info, normal
+        weights, sigma = np.zeros((w.shape[0], self.max_rows)), np.zeros(1)
+        rc = self.lib.vitvs_rig_robust_velocity(self.handle, int(w.shape[0]), p(w), p(st), p(k), int(robust_iterations), p(v), p(rs),
+                                                p(info), p(normal), p(weights), p(sigma))
+        self._check(rc, "vitvs_rig_robust_velocity")
+        return v, int(rs[0]), info, normal, weights, float(sigma[0])
 
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":

@@ -458,7 +458,10 @@ class MultiController:
         # rig = [(R_i, t_i), ...]: the cameras are one rigid body, camera i at pose (R_i, t_i) in the rig frame.  After each
         # round's batched call the rig law (Engine.rig_velocity) gives the ONE twist of the rig over that round's live cameras:
         # ``rig_velocity_raw``, and ``v_rig`` smoothed by the cameras' EMA; the cameras' own state is exactly as without it.
+        # With ``params.rig_robust_iterations`` = N > 0 that law is the robust rig law (N Tukey re-weightings of the stack) and
+        # ``rig_weights`` [cameras, max_rows] holds the round's final weights (0 for a camera without an image, None before).
         self.rig_W = None
+        self.rig_weights = None
         self.rig_velocity_raw, self.v_rig, self.rig_status, self.rig_info = None, None, None, None
         self._rig_ema = [None] * 6
         if rig is not None:
@@ -557,7 +560,13 @@ class MultiController:
             v, st = eng.compute_velocity(stack(cur), stack(des), np.stack(depth), p.intrinsics(), mode=mode,
                                          selection=(torch.stack(sel) if mode == _lib.SELECT_ORDER else sel), num_pairs=k)
             if self.rig_W is not None:                    # (before the host reads: the law is one more launch behind the call)
-                v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st)
+                if p.rig_robust_iterations:               # Tukey IRLS over the stack, one median over all live cameras' residuals
+                    v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st, p.rig_robust_iterations,
+                                                                           K=p.intrinsics())
+                    self.rig_weights = np.zeros((len(self.cameras), eng.max_rows))
+                    self.rig_weights[live] = self.rig_info["weights"].cpu().numpy()
+                else:
+                    v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st)
                 if self.rig_status == _lib.STATUS_OK:
                     self.rig_velocity_raw = v_r.cpu().numpy()
                     self.v_rig = ema_update(self._rig_ema, self.rig_velocity_raw, p.ema_alpha)
