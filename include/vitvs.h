@@ -360,6 +360,42 @@ VITVS_API int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const d
                                         int32_t n_iter, double* v_rig, int32_t* rig_status, int32_t* rig_info, double* normal,
                                         double* weights, double* sigma);
 
+/* --- the pose law --------------------------------------------------------------------------------
+ * A position-based law from what the camera's law left in the handle.  Every usable feature row k of pair b gives a
+ * current 3-D point P_k = Z (x, y, 1) (feat) in the current camera's frame and a goal point Q_k = Z* (xs, ys, 1) in the goal
+ * camera's (xs = (u* - cx) / fx, ys = (v* - cy) / fy from s_uv; Z* = the goal-depth table's entry of the row's goal token / 1000).
+ * A row is usable when its token is selected (>= 0), its current depth is not a hole (Z < 100) and its table entry is not 0.
+ * (R, t) minimises sum w |Q - (R P + t)|^2 — the pose of the current camera in the goal camera's frame, X_goal = R X_cam + t —
+ * by Horn's closed form (weighted centroids, S = sum w (P - pc)(Q - qc)^T, the eigenvector of the largest eigenvalue of the
+ * symmetric 4 x 4 N(S) as the unit quaternion with q_w >= 0), and
+ *   v_pose = -lambda (R^T t, theta u)      theta u = 2 atan2(|q_v|, q_w) q_v / |q_v|
+ * is ViSP's PBVS twist in the current camera's own optical frame, the convention of v_c.  n_iter > 0: Tukey IRLS as the robust
+ * control law's (c = 4.6851), rho = |Q - (R P + t)|, sigma = max(1.4826 median(rho over usable rows), sigma_min), sigma_min =
+ * 0.5 max(pitch_u / fx, pitch_v / fy) median(Z* over usable rows); one more solve after the last re-weighting.
+ *   K, status    device double [n_pairs][4] and int32 [n_pairs]: the K and the status of the velocity call
+ *   n_iter       re-weightings, 0 .. 16
+ *   v_pose       double [n_pairs][6];  pose_status int32 [n_pairs]: the camera's status when that is not VITVS_OK (v_pose = 0);
+ *                VITVS_OK with v_pose = 0, R = I under the same-image shortcut; VITVS_TOO_FEW (v_pose = 0, R = I) when fewer
+ *                than 3 rows are usable or keep a weight > 0, or the clouds are degenerate: ev_1 - ev_2 <= 1e-8 (sum w |P - pc|^2
+ *                + sum w |Q - qc|^2) (collinear points leave a rotation free); VITVS_OK otherwise
+ *   pose         double [n_pairs][12] or NULL: R row-major, then t
+ *   pose_info    int32 [n_pairs][8] or NULL: usable rows, Jacobi sweeps of the last solve, re-weightings done, usable rows with
+ *                final weight 0, degenerate flag, rows dropped for a hole, 0, 0
+ *   weights      double [n_pairs][max_rows] or NULL;  sigma double [n_pairs] or NULL: the last scale
+ * One launch on `stream`; valid in stream order behind any law evaluation of the handle with n_pairs pairs, replayed graphs
+ * included, and it changes nothing that call left.  Bit-reproducible.  Needs a goal depth that pairs with the call (n_goal ==
+ * n_pairs or 1).  The first call allocates the workspace and synchronises the device: make it outside any stream capture.
+ * Returns 0, -1 (a null required pointer), -2 (n_iter outside 0 .. 16), -3 (max_rows too large for the robust form's LDS),
+ * -5 (no law evaluation yet, n_pairs is not its pair count, no goal depth or one that does not pair, a law evaluation with option
+ * interaction at 1: its feature rows hold Z*, not Z).  No counterpart in the reference. */
+VITVS_API int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter,
+                                      double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info, double* weights,
+                                      double* sigma, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous. */
+VITVS_API int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter,
+                                  double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info, double* weights,
+                                  double* sigma);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several

@@ -132,6 +132,11 @@ struct vitvs_handle {
     unsigned char* rig_io = nullptr;   // cVr [max_pairs][36] f64 | v_rig [6] | normal [28] | status [max_pairs] i32 | rig_status | rig_info [8]
                                        // | (rig_io_head) K [max_pairs][4] f64 | sigma | weights [max_pairs][max_rows]
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
+    // the pose law (vitvs_pose_velocity_dev): its points [max_pairs][7][max_rows] f64, and the device side of the host-pointer
+    // form, allocated by the first pose call
+    double* pose_ws = nullptr;
+    unsigned char* pose_io = nullptr;  // K [P][4] | v_pose [P][6] | pose [P][12] | sigma [P] | weights [P][max_rows] f64 | status [P] |
+                                       // pose_status [P] | pose_info [P][8] i32
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
@@ -1715,6 +1720,82 @@ int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr
     return 0;
 }
 
+// --- the pose law --------------------------------------------------------------------------------
+static int pose_prepare(vitvs_handle* h, int n_pairs, int n_iter) {
+    if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
+    if (!h->last_pairs) return set_err(h, -5, "vitvs_pose_velocity follows a velocity call on the same handle");
+    if (n_pairs != h->last_pairs)
+        return set_err(h, -5, "n_pairs (" + std::to_string(n_pairs) + ") is not the pair count of the last law evaluation (" +
+                                  std::to_string(h->last_pairs) + ")");
+    if (!h->n_goal_depth) return set_err(h, -5, "the pose law needs a goal depth (vitvs_set_goal_depth_dev)");
+    if (h->last_T != h->T) return set_err(h, -5, "the goal depth table is laid out for the handle's own token grid");
+    if (h->n_goal_depth != n_pairs && h->n_goal_depth != 1)
+        return set_err(h, -5, "the goal depth holds " + std::to_string(h->n_goal_depth) + " images: one per pair, or one for all");
+    if (h->last_law.interaction == IL_DESIRED)
+        return set_err(h, -5, "the pose law needs the current depth: with option interaction at 1 the feature rows hold Z*, not Z");
+    PosePlan pl;
+    if (plan_pose(h->cfg.max_rows, n_iter, &pl))
+        return set_err(h, -3, "the robust pose law keeps two doubles per feature row in LDS: max_rows is too large");
+    if (!h->pose_ws) {                          // set-up, not the call path (and never inside a capture): as the rig law's
+        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
+        int rc = dev_alloc(h, &h->pose_ws, P * 7 * R);
+        if (!rc) rc = dev_alloc(h, &h->pose_io, (P * (4 + 6 + 12 + 1 + R)) * 8 + P * 10 * 4);
+        if (rc) return set_err(h, rc, "pose workspace allocation failed");
+        VITVS_HIP_CHECK(hipDeviceSynchronize());
+    }
+    return 0;
+}
+
+int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
+                            int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma, void* stream) {
+    if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
+    const vitvs_config& c = h->cfg;
+    PoseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_pairs = n_pairs; a.ld = c.max_rows; a.status = status;
+    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
+    a.zgoal = h->zgoal; a.zgoal_stride = h->n_goal_depth == 1 ? 0 : h->T + 1; a.T = h->T;
+    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
+    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    a.lambda = c.lambda; a.n_iter = n_iter; a.ws = h->pose_ws;
+    a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info;
+    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    const int rc = launch_pose(a, as_stream(stream));
+    return rc ? set_err(h, rc, "pose law launch failed") : 0;
+}
+
+int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
+                        int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma) {
+    if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
+    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_pairs;
+    double* d_K = reinterpret_cast<double*>(h->pose_io);
+    double* d_v = d_K + P * 4;
+    double* d_pose = d_v + P * 6;
+    double* d_sigma = d_pose + P * 12;
+    double* d_weights = d_sigma + P;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
+    int32_t* d_pose_status = d_status + P;
+    int32_t* d_info = d_pose_status + P;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = vitvs_pose_velocity_dev(h, n_pairs, d_K, d_status, n_iter, d_v, d_pose_status, d_pose, d_info, d_weights, d_sigma, st))
+        return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    VITVS_HIP_CHECK(hipMemcpy(v_pose, d_v, n * 6 * 8, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(pose_status, d_pose_status, n * 4, hipMemcpyDeviceToHost));
+    if (pose) VITVS_HIP_CHECK(hipMemcpy(pose, d_pose, n * 12 * 8, hipMemcpyDeviceToHost));
+    if (pose_info) VITVS_HIP_CHECK(hipMemcpy(pose_info, d_info, n * 8 * 4, hipMemcpyDeviceToHost));
+    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
+    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -1893,6 +1974,35 @@ int vitvs_op_rig_robust_plan(int32_t n_cams, int32_t ld, int32_t* out) {
     memset(&pl, 0, sizeof(pl));
     const int rc = plan_rig_robust(n_cams, ld, &pl);
     out[0] = (int32_t)pl.lds; out[1] = pl.lds_resident; out[2] = pl.pairs; out[3] = pl.lds_opt_in;
+    return rc;
+}
+
+int vitvs_op_pose_law(int32_t n_pairs, int32_t ld, const double* P, const double* Q, const int32_t* usable, double lambda,
+                      int32_t n_iter, double sigma_min, void* scratch, double* v_pose, int32_t* pose_status, double* pose,
+                      int32_t* pose_info, double* weights, double* sigma, void* stream) {
+    if (!P || !Q || !usable || !scratch || !v_pose || !pose_status) return -1;
+    if (n_pairs < 1 || ld < 1 || n_iter < 0 || n_iter > 16) return -2;
+    PoseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_pairs = n_pairs; a.ld = ld; a.P = P; a.Q = Q; a.usable = usable; a.lambda = lambda; a.n_iter = n_iter;
+    a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch);
+    a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info;
+    a.weights = weights; a.weights_stride = ld; a.sigma = sigma;
+    return launch_pose(a, as_stream(stream));
+}
+
+int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld) {
+    if (n_pairs < 1 || ld < 1) return -2;
+    const size_t b = pose_scratch_bytes(n_pairs, ld);
+    return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
+    if (!out) return -1;
+    PosePlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_pose(max_rows, n_iter, &pl);
+    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
     return rc;
 }
 

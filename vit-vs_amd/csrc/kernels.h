@@ -422,6 +422,51 @@ size_t rig_robust_scratch_bytes(int n_cams, int ld);
 void rig_robust_carve(void* scratch, int n_cams, int ld, RigRobustArgs& a);
 int launch_rig_robust(const RigRobustArgs& a, hipStream_t stream);
 
+// ---- pose.hip ------------------------------------------------------------------------------
+// The pose law: per pair ONE rigid displacement (R, t), X_goal = R X_cam + t, aligning the current 3-D points of
+// the feature rows with their goal points (Horn's quaternion form), and v_pose = -lambda (R^T t, theta u).  One launch, one
+// workgroup per pair.  The points come from what the camera's law left (selected, s_uv, feat, info, the goal-depth table) or,
+// for the seam tests, from the caller (P, Q, usable).
+struct PoseArgs {
+    int n_pairs;
+    int ld;                   // rows per pair of every per-row array (max_rows)
+    const int32_t* status;    // [n_pairs] the cameras' statuses, or null (all ST_OK): a pair that is not ST_OK keeps its status, v = 0
+    // the handle's form (P == null): rows k < info[b][1] of pair b
+    const int32_t* selected;  // [n_pairs][ld] goal token of every row, -1 padded
+    const int32_t* s_uv;      // [n_pairs][ld][4]
+    const double* feat;       // [n_pairs][ld][4]: Z (100 = a hole), x, y, sim
+    const int32_t* info;      // [n_pairs][8] of the camera's law: [1] rows written, [2] the same-image shortcut
+    const double* K;          // [n_pairs][4] fx, fy, cx, cy; also sigma_min = 0.5 max(pitch_u / fx, pitch_v / fy) median(Z*)
+    const uint16_t* zgoal;    // [n_goal][T + 1] mm (ServoArgs::zgoal), 0 = a hole
+    int zgoal_stride, T;
+    double pitch_u, pitch_v;
+    // given points (P != null): all ld rows
+    const double* P;          // [n_pairs][ld][3]
+    const double* Q;          // [n_pairs][ld][3]
+    const int32_t* usable;    // [n_pairs][ld]: > 0 usable, 0 padded, < 0 a hole
+    double sigma_min;         // read when K is null
+    double lambda;
+    int n_iter;               // Tukey re-weightings, 0 .. 16
+    double* ws;               // [n_pairs][7][ld] the points and their flags (pose_scratch_bytes)
+    // outputs
+    double* v_pose;           // [n_pairs][6]
+    int32_t* pose_status;     // [n_pairs] the camera's status when that is not ST_OK; ST_TOO_FEW: < 3 rows with a weight, or degenerate
+    double* pose;             // [n_pairs][12] or null: R row-major, t (identity when the status is not ST_OK)
+    int32_t* pose_info;       // [n_pairs][8] or null: usable rows, sweeps, re-weightings, usable rows at weight 0, degenerate, holes, 0, 0
+    double* weights;          // [n_pairs][weights_stride] or null
+    int weights_stride;
+    double* sigma;            // [n_pairs] or null: the last scale
+};
+struct PosePlan {
+    size_t lds;               // dynamic LDS of the launch
+    bool robust;              // pose_kernel<robust>
+    bool lds_opt_in;          // > 64 KiB
+};
+// -2: max_rows < 1, n_iter outside 0 .. 16; -3 (plan filled): more than 160 KiB of LDS
+int plan_pose(int max_rows, int n_iter, PosePlan* plan);
+size_t pose_scratch_bytes(int n_pairs, int ld);
+int launch_pose(const PoseArgs& a, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

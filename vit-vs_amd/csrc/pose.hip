@@ -1,0 +1,409 @@
+// The pose law: one rigid 3-D alignment of the matched points.
+//   P_k = Z (x, y, 1)       the current point of feature row k in the current camera's frame (feat of the camera's law)
+//   Q_k = Z* (xs, ys, 1)    its goal point in the goal camera's frame (s_uv and the handle's goal-depth table)
+//   (R, t) = argmin sum_k w_k |Q_k - (R P_k + t)|^2      Horn's closed form: the unit quaternion of R is the eigenvector of the
+//                                                        largest eigenvalue of the symmetric 4 x 4 matrix N(S),
+//                                                        S = sum w (P - pc)(Q - qc)^T, t = qc - R pc
+//   v_pose = -lambda (R^T t, theta u)                    ViSP's PBVS law, a twist in the current camera's own optical frame
+// One launch, one 256-thread workgroup per pair; nothing passes between workgroups.  Phase A writes P, Q and the usable flag of
+// every row into the pair's block of a global workspace that this workgroup alone writes and reads, behind __syncthreads() (as
+// servo_kernel treats a global L): any max_rows works.  Every solve takes the weighted centroids first and the centred sums
+// second, each as quantities x 8 row slices (row r belongs to slice r mod 8, ascending rows, the slices added in ascending order):
+// bit-reproducible.  Wave 0 then solves, every lane the same arithmetic: a cyclic Jacobi eigen-decomposition of the 4 x 4 matrix
+// in fp64, all indices compile-time (no scratch).  ROBUST: n_iter Tukey re-weightings with rho and w in dynamic LDS, the median by
+// the rank counting of servo.hip (integer compares on the bit patterns, ties by index), one more solve behind the last.
+#include "common.h"
+#include "kernels.h"
+#include "solve.h"
+
+#pragma clang fp contract(off)
+
+namespace vitvs {
+
+constexpr unsigned long long kPoseInfBits = 0x7ff0000000000000ull;
+// dynamic LDS in doubles: slices [8][32] | 64 results (see the kPose* offsets) | ROBUST: rho [ld] | w [ld]
+constexpr int kPoseHead = 8 * 32 + 64;
+constexpr int kPoseSum = 256;        // [0 .. 11): the centred sums
+constexpr int kPoseCen = 256 + 12;   // sw, pc [3], qc [3]
+constexpr int kPoseRt = 256 + 20;    // R [9] row-major, t [3], q [4]
+constexpr int kPoseMid = 256 + 36;   // the two middle values of the median
+constexpr int kPoseInt = 256 + 40;   // ints: [0] solve outcome (0 ok, 1 degenerate), [1] sweeps, [2 .. 6) the waves' zero weights,
+                                     //       [6 .. 10) their usable rows, [10 .. 14) their holes
+
+// The two middle values of rho[0 .. n) among its n_live smallest into mid[0], mid[1] (rig.hip's form of servo.hip's rank
+// counting: every value has a rank of its own and each cell one writer).
+__device__ __forceinline__ void pose_middles(const double* rho, int n, int n_live, double* mid, int tid) {
+    const int m_lo = (n_live - 1) >> 1, m_hi = n_live >> 1;
+    for (int i0 = tid; i0 < n; i0 += 4 * 256) {
+        long long ki[4];
+        int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const long long kj = __double_as_longlong(rho[j]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i0 + 256 * u < n && rank[u] == m_lo) mid[0] = __longlong_as_double(ki[u]);
+            if (i0 + 256 * u < n && rank[u] == m_hi) mid[1] = __longlong_as_double(ki[u]);
+        }
+    }
+}
+
+// One Jacobi rotation of the symmetric A in the (P, Q) plane, accumulated into V (eigenvectors in columns)
+template <int P, int Q>
+__device__ __forceinline__ void pose_rotate(double (&A)[4][4], double (&V)[4][4]) {
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    A[P][P] = A[P][P] - t * apq;
+    A[Q][Q] = A[Q][Q] + t * apq;
+    A[P][Q] = A[Q][P] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r != P && r != Q) {
+            const double arp = A[r][P], arq = A[r][Q];
+            A[r][P] = A[P][r] = c * arp - s * arq;
+            A[r][Q] = A[Q][r] = s * arp + c * arq;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double vrp = V[r][P], vrq = V[r][Q];
+        V[r][P] = c * vrp - s * vrq;
+        V[r][Q] = s * vrp + c * vrq;
+    }
+}
+
+// Horn's solve from the sums in sm (every lane of the calling wave computes the same): R, t, the quaternion; returns false when
+// the clouds are degenerate (ev_1 - ev_2 <= 1e-8 of the two scatters: collinear points leave a rotation free)
+__device__ __forceinline__ bool pose_solve(const double* sm, double (&R)[9], double (&t)[3], double (&q)[4], int& sweeps) {
+    const double* S = sm + kPoseSum;
+    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+    const double scatter = S[9] + S[10];
+    double A[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                      {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                      {Szx - Sxz, Sxy + Syx, Syy - Sxx - Szz, Syz + Szy},
+                      {Sxy - Syx, Szx + Sxz, Syz + Szy, Szz - Sxx - Syy}};
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    double normsq = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) normsq += A[i][j] * A[i][j];
+    sweeps = 0;
+    for (int sw = 0; sw < 32; ++sw) {
+        double off = 0.0;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int r = p + 1; r < 4; ++r) off += A[p][r] * A[p][r];
+        if (off <= 1e-40 * normsq) break;
+        ++sweeps;
+        pose_rotate<0, 1>(A, V); pose_rotate<0, 2>(A, V); pose_rotate<0, 3>(A, V);
+        pose_rotate<1, 2>(A, V); pose_rotate<1, 3>(A, V); pose_rotate<2, 3>(A, V);
+    }
+    int i1 = 0;
+    double ev1 = A[0][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (A[i][i] > ev1) { ev1 = A[i][i]; i1 = i; }
+    double ev2 = -__builtin_huge_val();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i != i1) ev2 = fmax(ev2, A[i][i]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        q[r] = V[r][0];
+#pragma unroll
+        for (int i = 1; i < 4; ++i)
+            if (i == i1) q[r] = V[r][i];
+    }
+    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double sg = q[0] / qn < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) q[r] = sg * (q[r] / qn);
+    const double a = q[0], b = q[1], c = q[2], d = q[3];
+    R[0] = a * a + b * b - c * c - d * d; R[1] = 2.0 * (b * c - a * d);         R[2] = 2.0 * (b * d + a * c);
+    R[3] = 2.0 * (b * c + a * d);         R[4] = a * a - b * b + c * c - d * d; R[5] = 2.0 * (c * d - a * b);
+    R[6] = 2.0 * (b * d - a * c);         R[7] = 2.0 * (c * d + a * b);         R[8] = a * a - b * b - c * c + d * d;
+    const double* cen = sm + kPoseCen;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = cen[4 + i] - ((R[3 * i] * cen[1] + R[3 * i + 1] * cen[2]) + R[3 * i + 2] * cen[3]);
+    return !(ev1 - ev2 <= 1e-8 * scatter);
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double smp[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ld = a.ld;
+    double* ws = a.ws + (size_t)b * 7 * ld;                 // P [3][ld] | Q [3][ld] | flag [ld]: 1 usable, 0 padded, -1 a hole
+    int* iscr = reinterpret_cast<int*>(smp + kPoseInt);
+    double* rho = smp + kPoseHead;
+    double* wk = rho + ld;
+    double* vout = a.v_pose + (size_t)b * 6;
+
+    // the early outs: the camera's own failure, the same-image shortcut (the camera is at the goal: v = 0, R = I exactly)
+    const int cam = a.status ? a.status[b] : (int)ST_OK;
+    const bool same = a.info && a.info[(size_t)b * 8 + 2] != 0;
+    if (cam != ST_OK || same) {
+        if (a.weights)
+            for (int k = tid; k < a.weights_stride; k += 256) a.weights[(size_t)b * a.weights_stride + k] = 0.0;
+        if (tid < 6) vout[tid] = 0.0;
+        if (tid < 12 && a.pose) a.pose[(size_t)b * 12 + tid] = (tid == 0 || tid == 4 || tid == 8) ? 1.0 : 0.0;
+        if (tid < 8 && a.pose_info) a.pose_info[(size_t)b * 8 + tid] = 0;
+        if (tid == 0) {
+            a.pose_status[b] = cam;
+            if (a.sigma) a.sigma[b] = 0.0;
+        }
+        return;
+    }
+
+    // Phase A: the points.  n rows take part: the rows the camera's law wrote (info[1]), or every row of given points
+    int n = ld, n_us = 0, holes = 0;
+    if (a.P) {
+        const double* Pb = a.P + (size_t)b * ld * 3;
+        const double* Qb = a.Q + (size_t)b * ld * 3;
+        const int32_t* ub = a.usable + (size_t)b * ld;
+        for (int k = tid; k < n; k += 256) {
+            const int f = ub[k] > 0 ? 1 : (ub[k] < 0 ? -1 : 0);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                ws[(size_t)c * ld + k] = f > 0 ? Pb[k * 3 + c] : 0.0;
+                ws[(size_t)(3 + c) * ld + k] = f > 0 ? Qb[k * 3 + c] : 0.0;
+            }
+            ws[(size_t)6 * ld + k] = (double)f;
+            n_us += f > 0;
+            holes += f < 0;
+        }
+    } else {
+        n = min(max(a.info[(size_t)b * 8 + 1], 0), ld);
+        const double fx = a.K[b * 4 + 0], fy = a.K[b * 4 + 1], cx = a.K[b * 4 + 2], cy = a.K[b * 4 + 3];
+        const int32_t* sel = a.selected + (size_t)b * ld;
+        const int32_t* uv = a.s_uv + (size_t)b * ld * 4;
+        const double* ft = a.feat + (size_t)b * ld * 4;
+        const uint16_t* tab = a.zgoal + (size_t)b * a.zgoal_stride;
+        for (int k = tid; k < n; k += 256) {
+            const int tok = sel[k];
+            int f = 0;
+            double p[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
+            if (tok >= 0 && tok < a.T) {
+                const double Z = ft[k * 4 + 0], x = ft[k * 4 + 1], y = ft[k * 4 + 2];
+                const unsigned ds = tab[tok];
+                f = (Z < 100.0 && ds != 0) ? 1 : -1;         // a hole in either depth drops the row
+                if (f > 0) {
+                    const double Zs = (double)ds / 1000.0;
+                    const double xs = ((double)uv[k * 4 + 0] - cx) / fx, ys = ((double)uv[k * 4 + 1] - cy) / fy;
+                    p[0] = Z * x; p[1] = Z * y; p[2] = Z;
+                    g[0] = Zs * xs; g[1] = Zs * ys; g[2] = Zs;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                ws[(size_t)c * ld + k] = p[c];
+                ws[(size_t)(3 + c) * ld + k] = g[c];
+            }
+            ws[(size_t)6 * ld + k] = (double)f;
+            n_us += f > 0;
+            holes += f < 0;
+        }
+    }
+    n_us = wave_sum(n_us);
+    holes = wave_sum(holes);
+    if (lane == 0) { iscr[6 + wave] = n_us; iscr[10 + wave] = holes; }
+    __syncthreads();                                        // (the points are global memory: full fence)
+    n_us = iscr[6] + iscr[7] + iscr[8] + iscr[9];
+    holes = iscr[10] + iscr[11] + iscr[12] + iscr[13];
+    const double* flag = ws + (size_t)6 * ld;
+
+    double sigma_min = a.sigma_min;
+    if constexpr (ROBUST) {
+        for (int k = tid; k < n; k += 256) {
+            const bool us = flag[k] > 0.0;
+            wk[k] = us ? 1.0 : 0.0;
+            rho[k] = us ? ws[(size_t)5 * ld + k] : __longlong_as_double((long long)kPoseInfBits);   // Z* for sigma_min's median
+        }
+        if (a.K && n_us > 0) {
+            lds_barrier();
+            pose_middles(rho, n, n_us, smp + kPoseMid, tid);
+            lds_barrier();
+            sigma_min = 0.5 * fmax(a.pitch_u / a.K[b * 4 + 0], a.pitch_v / a.K[b * 4 + 1]) * ((smp[kPoseMid] + smp[kPoseMid + 1]) * 0.5);
+        }
+        lds_barrier();
+    }
+
+    const int qid = tid & 31, slice = tid >> 5;
+    int status = ST_OK, sweeps = 0, reweighted = 0, n_zero = 0, degenerate = 0;
+    double sigma = 0.0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0};
+    const int N = ROBUST ? a.n_iter : 0;
+    for (int it = 0;; ++it) {
+        if (n_us - n_zero < 3) { status = ST_TOO_FEW; break; }
+        // the weighted centroids: sw, sum w P, sum w Q
+        if (qid < 7) {
+            double acc = 0.0;
+            for (int r = slice; r < n; r += 8) {
+                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
+                acc += qid == 0 ? w : w * ws[(size_t)(qid - 1) * ld + r];
+            }
+            smp[slice * 32 + qid] = acc;
+        }
+        lds_barrier();
+        if (tid < 7) {
+            double s = 0.0, s0 = 0.0;
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) { s += smp[sl * 32 + tid]; s0 += smp[sl * 32]; }
+            smp[kPoseCen + tid] = tid == 0 ? s : s / s0;
+        }
+        lds_barrier();
+        // the centred sums: S [9] = sum w (P - pc)(Q - qc)^T, sum w |P - pc|^2, sum w |Q - qc|^2
+        if (qid < 11) {
+            const double* cen = smp + kPoseCen;
+            const int ca = qid < 9 ? qid / 3 : 0, cb = qid < 9 ? qid % 3 : 0;
+            double acc = 0.0;
+            for (int r = slice; r < n; r += 8) {
+                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
+                double term;
+                if (qid < 9) {
+                    term = w * (ws[(size_t)ca * ld + r] - cen[1 + ca]) * (ws[(size_t)(3 + cb) * ld + r] - cen[4 + cb]);
+                } else {
+                    const int o = qid == 9 ? 0 : 3;
+                    const double d0 = ws[(size_t)o * ld + r] - cen[1 + o], d1 = ws[(size_t)(o + 1) * ld + r] - cen[2 + o],
+                                 d2 = ws[(size_t)(o + 2) * ld + r] - cen[3 + o];
+                    term = w * ((d0 * d0 + d1 * d1) + d2 * d2);
+                }
+                acc += term;
+            }
+            smp[slice * 32 + qid] = acc;
+        }
+        lds_barrier();
+        if (tid < 11) {
+            double s = 0.0;
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) s += smp[sl * 32 + tid];
+            smp[kPoseSum + tid] = s;
+        }
+        lds_barrier();
+        if (wave == 0) {
+            double Rn[9], tn[3], qn[4];
+            int sw;
+            const bool ok = pose_solve(smp, Rn, tn, qn, sw);
+            if (lane == 0) {
+                iscr[0] = ok ? 0 : 1;
+                iscr[1] = sw;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) smp[kPoseRt + i] = Rn[i];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) smp[kPoseRt + 9 + i] = tn[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) smp[kPoseRt + 12 + i] = qn[i];
+            }
+        }
+        lds_barrier();
+        sweeps = iscr[1];
+        if (iscr[0]) { degenerate = 1; status = ST_TOO_FEW; break; }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = smp[kPoseRt + i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = smp[kPoseRt + 9 + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = smp[kPoseRt + 12 + i];
+        if (it == N) break;
+        if constexpr (ROBUST) {
+            for (int k = tid; k < n; k += 256) {
+                if (!(flag[k] > 0.0)) continue;             // not a usable row: rho stays +inf
+                const double p0 = ws[k], p1 = ws[(size_t)ld + k], p2 = ws[(size_t)2 * ld + k];
+                const double d0 = ws[(size_t)3 * ld + k] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
+                const double d1 = ws[(size_t)4 * ld + k] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
+                const double d2 = ws[(size_t)5 * ld + k] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
+                rho[k] = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            }
+            lds_barrier();
+            pose_middles(rho, n, n_us, smp + kPoseMid, tid);
+            lds_barrier();
+            sigma = fmax(1.4826 * ((smp[kPoseMid] + smp[kPoseMid + 1]) * 0.5), sigma_min);
+            const double cs = 4.6851 * sigma;
+            int zeros = 0;
+            for (int k = tid; k < n; k += 256) {
+                const bool us = flag[k] > 0.0;
+                const double tt = rho[k] / cs;
+                const double u = 1.0 - tt * tt;
+                const double w1 = (us && tt < 1.0) ? u * u : 0.0;
+                wk[k] = w1;
+                zeros += (us && w1 == 0.0) ? 1 : 0;
+            }
+            zeros = wave_sum(zeros);
+            if (lane == 0) iscr[2 + wave] = zeros;
+            lds_barrier();
+            n_zero = iscr[2] + iscr[3] + iscr[4] + iscr[5];
+            reweighted = it + 1;
+        }
+    }
+
+    if (a.weights) {
+        for (int k = tid; k < a.weights_stride; k += 256) {
+            double w = 0.0;
+            if (k < n) w = ROBUST ? wk[k] : (flag[k] > 0.0 ? 1.0 : 0.0);
+            a.weights[(size_t)b * a.weights_stride + k] = w;
+        }
+    }
+    if (tid != 0) return;
+    const bool ok = status == ST_OK;
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    if (ok) {
+        const double nv = sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
+        const double f = nv == 0.0 ? 0.0 : 2.0 * atan2(nv, q[0]) / nv;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            v[i] = -a.lambda * ((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
+            v[3 + i] = -a.lambda * (f * q[1 + i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) vout[i] = v[i];
+    a.pose_status[b] = status;
+    if (a.pose) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a.pose[(size_t)b * 12 + i] = ok ? R[i] : ((i & 3) == 0 ? 1.0 : 0.0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) a.pose[(size_t)b * 12 + 9 + i] = ok ? t[i] : 0.0;
+    }
+    if (a.sigma) a.sigma[b] = sigma;
+    if (a.pose_info) {
+        int32_t* pi = a.pose_info + (size_t)b * 8;
+        pi[0] = n_us; pi[1] = sweeps; pi[2] = reweighted; pi[3] = n_zero; pi[4] = degenerate; pi[5] = holes; pi[6] = 0; pi[7] = 0;
+    }
+}
+
+int plan_pose(int max_rows, int n_iter, PosePlan* plan) {
+    if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16) return -2;
+    plan->robust = n_iter > 0;
+    plan->lds = ((size_t)kPoseHead + (plan->robust ? (size_t)2 * max_rows : 0)) * sizeof(double);
+    plan->lds_opt_in = plan->lds > 64 * 1024;
+    return plan->lds > 160 * 1024 ? -3 : 0;
+}
+
+size_t pose_scratch_bytes(int n_pairs, int ld) { return (size_t)n_pairs * 7 * ld * sizeof(double); }
+
+int launch_pose(const PoseArgs& a, hipStream_t stream) {
+    if (a.n_pairs < 1 || a.ld < 1 || !a.ws || !a.v_pose || !a.pose_status || (a.weights && a.weights_stride < 0)) return -2;
+    if (a.P ? (!a.Q || !a.usable) : (!a.selected || !a.s_uv || !a.feat || !a.info || !a.K || !a.zgoal || a.T < 1)) return -2;
+    PosePlan p;
+    if (int rc = plan_pose(a.ld, a.n_iter, &p)) return rc;
+    static std::atomic<unsigned long long> raised{0};
+    if (p.robust) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true>), 160 * 1024, raised)) return -3;
+        launch(pose_kernel<true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    } else {
+        launch(pose_kernel<false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace vitvs

@@ -546,6 +546,56 @@ class Engine:
         self._check(rc, "vitvs_rig_robust_velocity")
         return v, int(rs[0]), info, normal, weights, float(sigma[0])
 
+    POSE_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes")
+
+    def pose_velocity(self, K, status, robust_iterations: int = 0):
+        """``vitvs_pose_velocity_dev``: the pose law of every pair of the last velocity call, from what that call left
+        in the handle and the goal depth (``set_goal_depth``): one rigid alignment (R, t) of the matched 3-D points per pair,
+        X_goal = R X_cam + t, and ``v_pose = -lambda (R^T t, theta u)``.  ``K``: the intrinsics of that call, [n, 4] or one (fx, fy, cx,
+        cy) for all; ``status``: the int32 [n] it returned (a device tensor stays on the device); ``robust_iterations``: Tukey
+        re-weightings, 0 .. 16.  Returns ``(v_pose float64 [n, 6] device tensor, info)``, ``info`` = dict of device tensors: ``status``
+        int32 [n], ``R`` [n, 3, 3], ``t`` [n, 3], ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` /
+        ``holes`` int32 [n], ``weights`` float64 [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing
+        synchronises after the first call (which allocates: make it outside a stream capture)."""
+        N = int(robust_iterations)
+        if not 0 <= N <= 16:
+            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+        n = int(st.numel())
+        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
+        if kk.shape[0] == 1 and n > 1:
+            kk = kk.expand(n, 4)
+        if kk.shape[0] != n:
+            raise VitvsError("one (fx, fy, cx, cy) per pair expected")
+        kk = kk.contiguous().to(self.device)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
+        v, pose, weights, sigma = f64(n, 6), f64(n, 12), f64(n, self.max_rows), f64(n)
+        pst, pinfo = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty((n, 8), dtype=torch.int32, device=self.device)
+        rc = self.lib.vitvs_pose_velocity_dev(self.handle, n, _ptr(kk), _ptr(st), N, _ptr(v), _ptr(pst), _ptr(pose), _ptr(pinfo),
+                                              _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
+        self._check(rc, "vitvs_pose_velocity_dev")
+        info = dict(status=pst, R=pose[:, :9].reshape(n, 3, 3), t=pose[:, 9:], weights=weights, sigma=sigma)
+        info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
+        return v, info
+
+    def pose_velocity_host(self, K, status, robust_iterations: int = 0):
+        """``vitvs_pose_velocity``, the host-pointer form: numpy in, ``(v_pose float64 [n, 6], info)`` out, ``info`` as
+        ``pose_velocity``'s with numpy arrays.  Synchronous."""
+        N = int(robust_iterations)
+        if not 0 <= N <= 16:
+            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        n = int(st.size)
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
+        v, pose, weights, sigma = np.zeros((n, 6)), np.zeros((n, 12)), np.zeros((n, self.max_rows)), np.zeros(n)
+        pst, pinfo = np.zeros(n, np.int32), np.zeros((n, 8), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_pose_velocity(self.handle, n, p(kk), p(st), N, p(v), p(pst), p(pose), p(pinfo), p(weights), p(sigma))
+        self._check(rc, "vitvs_pose_velocity")
+        info = dict(status=pst, R=pose[:, :9].reshape(n, 3, 3), t=pose[:, 9:], weights=weights, sigma=sigma)
+        info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
+        return v, info
+
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),

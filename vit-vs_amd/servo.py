@@ -236,9 +236,18 @@ class Controller:
         self.params = params or engine.params
         if params is not None:
             engine.apply_law_params(params)               # the law of the params this controller was given
-        self.goal_depth = None                            # uint16 millimetres at the goal pose (interaction "desired" / "mean")
+        self.goal_depth = None                            # uint16 millimetres at the goal pose (interaction "desired" / "mean", law "pose")
+        if self.params.law == "pose":
+            # the pose law aligns the current 3-D points with the goal's: it needs Z* from a goal depth image and Z in
+            # the feature rows, which interaction "desired" replaces by Z*
+            if goal_depth is None:
+                raise ValueError('law="pose" needs goal_depth: the depth image taken at the goal pose')
+            if self.params.interaction == "desired":
+                raise ValueError('law="pose" does not combine with interaction="desired" (its feature rows hold Z*, not Z)')
         if goal_depth is not None:
             self.set_goal_depth(goal_depth)
+        self.last_pose_status = None                      # law "pose": the pose law's status of the last update, and its
+        self.last_pose = None                             # (R [3, 3], t [3]): the current camera in the goal camera's frame
         self.num_pairs = self.params.num_pairs
         self.dino_input_size = engine.cfg.img_size
         self.goal_image = goal_image                      # PIL image or uint8 array, any size
@@ -351,6 +360,8 @@ class Controller:
         """Bookkeeping of one finished update (whoever computed it: this controller's engine, or a ``MultiController``'s batched
         call / pipeline slot): raw twist, status, the consecutive-failure counter of vitvs_v2.py:500-505."""
         self._raw_v, self.last_status = v, st
+        if self.params.law == "pose":
+            self._pose_step(st)
         if st == _lib.STATUS_NO_CORRESPONDENCE:
             self.feature_failure_count += 1
             if self.feature_failure_count >= 10:
@@ -358,6 +369,20 @@ class Controller:
             return False
         self.feature_failure_count = 0
         return True
+
+    def _pose_step(self, st):
+        """law "pose": the pose law behind this update's law evaluation (one more launch on what it left in the handle).  When its
+        status is OK its twist replaces the raw ``v_c`` that the EMA, the remap and the history see; otherwise the update stays the
+        image-based law's."""
+        p = self.params
+        if st == _lib.STATUS_NO_CORRESPONDENCE:           # (the reference draw may have ended before any law evaluation)
+            self.last_pose_status, self.last_pose = int(st), None
+            return
+        v, info = self.engine.pose_velocity_host(p.intrinsics(), [st], p.pose_robust_iterations)
+        self.last_pose_status = int(info["status"][0])
+        self.last_pose = (info["R"][0].copy(), info["t"][0].copy())
+        if self.last_pose_status == _lib.STATUS_OK:
+            self._raw_v = v[0]
 
     def _features(self, det, b: int = 0):
         """``detect_features``' return value from pair ``b`` of an engine's ``last_details``."""
@@ -472,6 +497,9 @@ class MultiController:
             self.rig_W = np.stack([twist_matrix(R, t) for R, t in rig])
         self.engines = list(backend.engines) if self.pipe is not None else [backend]
         self.engine = self.engines[0]
+        if (params or self.engine.params).law != "ibvs":
+            raise ValueError('MultiController runs the image-based law per camera: law="pose" is servo.Controller\'s (a pose rig law is '
+                             'not part of the library)')
         if selection not in ("order", "dense"):
             raise ValueError('MultiController draws on the device: selection is "order" or "dense" (explicit ids per round: ibvs(selection=...))')
         self.selection, self.generator = selection, generator
