@@ -396,6 +396,42 @@ VITVS_API int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double
                                   double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info, double* weights,
                                   double* sigma);
 
+/* --- the pose rig law ----------------------------------------------------------------------------
+ * ONE rigid 3-D alignment over the matched points of ALL cameras of a rigid rig, for a rig whose cameras were the
+ * pairs of the last law evaluation.  Camera i has pose (R_i, t_i) in the rig frame, X_rig = R_i X_cam + t_i (the (R, t) of
+ * vitvs_rig_velocity_dev's cVr).  A camera contributes when its status is VITVS_OK and it is not under the same-image shortcut;
+ * its usable rows (the pose law's rule) give P_k, Q_k as the pose law's, and the stack holds P'_k = R_i P_k + t_i and Q'_k =
+ * R_i Q_k + t_i at stack row i * max_rows + k.  (R, t) minimises sum w |Q' - (R P' + t)|^2 over the whole stack by the pose law's
+ * solve (same sums, Jacobi, degeneracy rule): the current rig in the goal rig's frame, and
+ *   v_rig = -lambda (R^T t, theta u)
+ * is a twist in the rig's own frame, the convention of vitvs_rig_velocity_dev's v_rig.  n_iter > 0: Tukey IRLS with ONE median
+ * over the usable rows of all contributing cameras, sigma = max(1.4826 median(rho), sigma_min), sigma_min = 0.5 max_i max(pitch_u
+ * / fx_i, pitch_v / fy_i) median(Z* over all usable rows), Z* in the camera's frame, i over the contributing cameras.
+ *   rTc          device double [n_cams][12]: R_i row-major, then t_i
+ *   K, status    device double [n_cams][4] and int32 [n_cams]: the K and the status of the velocity call
+ *   n_iter       re-weightings, 0 .. 16
+ *   v_rig        double [6];  rig_status int32 [1]: VITVS_OK; VITVS_TOO_FEW (v_rig = 0, R = I) when fewer than 3 rows of the stack
+ *                are usable or keep a weight > 0, or the stack is degenerate; when no camera contributes v_rig = 0, R = I and
+ *                the status is the largest camera status (VITVS_OK when every camera is at its goal by the shortcut)
+ *   pose         double [12] or NULL: R row-major, then t
+ *   rig_info     int32 [8] or NULL: contributing cameras, usable rows, Jacobi sweeps of the last solve, re-weightings done,
+ *                usable rows with final weight 0, degenerate flag, rows dropped for a hole, the largest camera status
+ *   moments      double [18] or NULL, for a rig spread over ranks: the raw sums of the final weights over the stack: sum w,
+ *                sum w P' [3], sum w Q' [3], sum w P' Q'^T [9] row-major, sum w |P'|^2, sum w |Q'|^2 (zeros when nobody contributes)
+ *   weights      double [n_cams][max_rows] or NULL;  sigma double [1] or NULL: the last scale
+ * One launch of one workgroup on `stream`; valid exactly where vitvs_pose_velocity_dev is, with n_cams the pair count of the law
+ * evaluation, and it changes nothing that call left.  Bit-reproducible.  The first call allocates the workspace and synchronises
+ * the device: make it outside any stream capture.  Returns 0, -1 (a null required pointer), -2 (n_iter outside 0 .. 16, n_cams
+ * < 1), -3 (n_cams * max_rows too large for the robust form's LDS), -5 (vitvs_pose_velocity_dev's cases).  No counterpart in the
+ * reference. */
+VITVS_API int vitvs_pose_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* rTc, const double* K, const int32_t* status,
+                                          int32_t n_iter, double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info,
+                                          double* moments, double* weights, double* sigma, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous. */
+VITVS_API int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* rTc, const double* K, const int32_t* status,
+                                      int32_t n_iter, double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info,
+                                      double* moments, double* weights, double* sigma);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several

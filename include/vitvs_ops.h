@@ -147,6 +147,23 @@ VITVS_API int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld);   /* -2 
  * 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out NULL),
  * -2 (max_rows < 1, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
 VITVS_API int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out);
+/* The pose rig law's kernel (vitvs_pose_rig_velocity_dev, include/vitvs.h) on caller-given camera-frame points:
+ *   P, Q        device double [n_cams][ld][3];  usable int32 [n_cams][ld]: > 0 usable, 0 padded, < 0 a hole
+ *   rTc         device double [n_cams][12]: R_i row-major, then t_i;  cam_status int32 [n_cams] or NULL (all VITVS_OK)
+ *   n_iter      0 .. 16;  sigma_min  the floor of the scale, given directly
+ *   scratch     vitvs_op_pose_rig_scratch_bytes(n_cams, ld) = 8 * 7 n_cams ld bytes
+ *   v_rig [6], rig_status [1]; pose [12], rig_info [8], moments [18], weights [n_cams][ld], sigma [1] or NULL
+ * Returns 0, -1 (a null required pointer), -2 (n_cams or ld < 1, n_iter outside 0 .. 16), -3 (the plan's). */
+VITVS_API int vitvs_op_pose_rig_law(int32_t n_cams, int32_t ld, const double* P, const double* Q, const int32_t* usable,
+                                    const double* rTc, const int32_t* cam_status, double lambda, int32_t n_iter, double sigma_min,
+                                    void* scratch, double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info,
+                                    double* moments, double* weights, double* sigma, void* stream);
+VITVS_API int vitvs_op_pose_rig_scratch_bytes(int32_t n_cams, int32_t ld);   /* -2 as above, -3 past 2 GiB */
+/* The launch plan of the pose rig law (host arithmetic, no device): out[0] the dynamic LDS bytes = 8 (320 + (n_iter > 0 ? 2 n_cams
+ * ld : 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out
+ * NULL), -2 (n_cams or ld < 1, n_cams ld past 2^24 rows, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB
+ * of LDS. */
+VITVS_API int vitvs_op_pose_rig_plan(int32_t n_cams, int32_t ld, int32_t n_iter, int32_t* out);
 /* The fused Gram arg-max of the velocity path on caller-normalised descriptors dn [n_des + n_pairs][T][Dp] fp32 (desired frames
  * first; n_des = 1 with des_shared): the plan of vitvs_op_gram_plan(precision, 0, T, Dp, n_pairs, n_pairs), the split into dh
  * (3 (n_des + n_pairs) T Dp fp16, only when the plan splits) and the keys row_best / col_best [n_pairs][T] (cleared here), decoded

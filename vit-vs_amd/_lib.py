@@ -68,6 +68,8 @@ PROTOTYPES = {
     "vitvs_rig_robust_velocity": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_velocity_dev": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_velocity": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vitvs_pose_rig_velocity_dev": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_pose_rig_velocity": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_details": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_weights": (_I, [_P, _I, _P]),
     "vitvs_set_option": (_I, [_P, C.c_char_p, C.c_int64]),
@@ -107,6 +109,9 @@ PROTOTYPES = {
     "vitvs_op_pose_law": (_I, [_I, _I, _P, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_pose_scratch_bytes": (_I, [_I, _I]),
     "vitvs_op_pose_plan": (_I, [_I, _I, _P]),
+    "vitvs_op_pose_rig_law": (_I, [_I, _I, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_op_pose_rig_scratch_bytes": (_I, [_I, _I]),
+    "vitvs_op_pose_rig_plan": (_I, [_I, _I, _I, _P]),
     "vitvs_op_gram_argmax": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_gram_stencil": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_linear_partial": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),

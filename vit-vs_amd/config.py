@@ -185,6 +185,8 @@ class ServoParams:
     law: str = "ibvs"              # the twist a servo.Controller executes: "ibvs", the image-based law above (the reference's), or
                                    # "pose": the pose law on the matched 3-D points (Engine.pose_velocity), which needs a goal depth
     pose_robust_iterations: int = 0  # Tukey re-weightings of the pose law (0 .. 16); 0 = the plain alignment
+    rig_pose_robust_iterations: int = 0  # Tukey re-weightings of the pose RIG law (MultiController(rig=..., law "pose"): one median
+                                         # over all cameras' 3-D residuals, vitvs_pose_rig_velocity_dev; 0 .. 16); 0 = the plain one
 
     def __post_init__(self):
         if self.interaction not in INTERACTIONS:
@@ -195,6 +197,8 @@ class ServoParams:
             raise ValueError(f"pose_robust_iterations is 0 .. 16, got {self.pose_robust_iterations!r}")
         if not 0 <= int(self.rig_robust_iterations) <= 16:
             raise ValueError(f"rig_robust_iterations is 0 .. 16, got {self.rig_robust_iterations!r}")
+        if not 0 <= int(self.rig_pose_robust_iterations) <= 16:
+            raise ValueError(f"rig_pose_robust_iterations is 0 .. 16, got {self.rig_pose_robust_iterations!r}")
 
     @property
     def c_x(self) -> float:
@@ -253,7 +257,8 @@ def load_reference_config(source) -> ReferenceConfig:
     ``max_velocity_vector_history`` 200, ``background_thresh`` 0.5 (vitvs_v2.py:287, 296, 316, 319).  ``robust_iterations`` (this
     project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
-    else "current"; ``law`` ("ibvs" / "pose") and ``pose_robust_iterations`` likewise, else "ibvs" and 0."""
+    else "current"; ``law`` ("ibvs" / "pose"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise, else "ibvs",
+    0 and 0."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -272,10 +277,12 @@ def load_reference_config(source) -> ReferenceConfig:
                         robust_iterations=int(cfg.get("robust_iterations", 0)), subpatch=bool(cfg.get("subpatch", False)),
                         interaction=str(cfg.get("interaction", "current")),
                         rig_robust_iterations=int(cfg.get("rig_robust_iterations", 0)), law=str(cfg.get("law", "ibvs")),
-                        pose_robust_iterations=int(cfg.get("pose_robust_iterations", 0)))
+                        pose_robust_iterations=int(cfg.get("pose_robust_iterations", 0)),
+                        rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
-            "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations"}
+            "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
+            "rig_pose_robust_iterations"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

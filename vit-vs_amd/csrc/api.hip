@@ -137,6 +137,11 @@ struct vitvs_handle {
     double* pose_ws = nullptr;
     unsigned char* pose_io = nullptr;  // K [P][4] | v_pose [P][6] | pose [P][12] | sigma [P] | weights [P][max_rows] f64 | status [P] |
                                        // pose_status [P] | pose_info [P][8] i32
+    // the pose rig law (vitvs_pose_rig_velocity_dev): its stack [7][max_pairs * max_rows] f64, and the device side of the
+    // host-pointer form, allocated by the first pose rig call
+    double* pose_rig_ws = nullptr;
+    unsigned char* pose_rig_io = nullptr;  // rTc [P][12] | K [P][4] | v_rig [6] | pose [12] | moments [18] | sigma [1] |
+                                           // weights [P][max_rows] f64 | status [P] | rig_status [1] | rig_info [8] i32
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
@@ -1796,6 +1801,80 @@ int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const
     return 0;
 }
 
+// --- the pose rig law ----------------------------------------------------------------------------
+static int pose_rig_prepare(vitvs_handle* h, int n_cams, int n_iter) {
+    if (n_cams < 1) return set_err(h, -2, "n_cams is at least 1");
+    if (int rc = pose_prepare(h, n_cams, n_iter)) return rc;     // valid exactly where the pose law is, n_cams == last_pairs
+    PoseRigPlan pl;
+    if (plan_pose_rig(n_cams, h->cfg.max_rows, n_iter, &pl))
+        return set_err(h, -3, "the robust pose rig law keeps two doubles per feature row of the rig in LDS: n_cams * max_rows is too large");
+    if (!h->pose_rig_ws) {                      // set-up, not the call path (and never inside a capture): as the pose law's
+        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
+        int rc = dev_alloc(h, &h->pose_rig_ws, P * 7 * R);
+        if (!rc) rc = dev_alloc(h, &h->pose_rig_io, (P * (12 + 4 + R) + 6 + 12 + 18 + 1) * 8 + (P + 9) * 4);
+        if (rc) return set_err(h, rc, "pose rig workspace allocation failed");
+        VITVS_HIP_CHECK(hipDeviceSynchronize());
+    }
+    return 0;
+}
+
+int vitvs_pose_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* rTc, const double* K, const int32_t* status,
+                                int32_t n_iter, double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info, double* moments,
+                                double* weights, double* sigma, void* stream) {
+    if (!h || !rTc || !K || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = pose_rig_prepare(h, n_cams, n_iter)) return rc;
+    const vitvs_config& c = h->cfg;
+    PoseRigArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_cams = n_cams; a.ld = c.max_rows; a.status = status; a.rTc = rTc;
+    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
+    a.zgoal = h->zgoal; a.zgoal_stride = h->n_goal_depth == 1 ? 0 : h->T + 1; a.T = h->T;
+    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
+    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    a.lambda = c.lambda; a.n_iter = n_iter; a.ws = h->pose_rig_ws;
+    a.v_rig = v_rig; a.rig_status = rig_status; a.pose = pose; a.rig_info = rig_info; a.moments = moments;
+    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    const int rc = launch_pose_rig(a, as_stream(stream));
+    return rc ? set_err(h, rc, "pose rig law launch failed") : 0;
+}
+
+int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* rTc, const double* K, const int32_t* status, int32_t n_iter,
+                            double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info, double* moments, double* weights,
+                            double* sigma) {
+    if (!h || !rTc || !K || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = pose_rig_prepare(h, n_cams, n_iter)) return rc;
+    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_cams;
+    double* d_rTc = reinterpret_cast<double*>(h->pose_rig_io);
+    double* d_K = d_rTc + P * 12;
+    double* d_v = d_K + P * 4;
+    double* d_pose = d_v + 6;
+    double* d_moments = d_pose + 12;
+    double* d_sigma = d_moments + 18;
+    double* d_weights = d_sigma + 1;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
+    int32_t* d_rig_status = d_status + P;
+    int32_t* d_info = d_rig_status + 1;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    VITVS_HIP_CHECK(hipMemcpy(d_rTc, rTc, n * 12 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = vitvs_pose_rig_velocity_dev(h, n_cams, d_rTc, d_K, d_status, n_iter, d_v, d_rig_status, d_pose, d_info, d_moments,
+                                             d_weights, d_sigma, st))
+        return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
+    if (pose) VITVS_HIP_CHECK(hipMemcpy(pose, d_pose, 12 * 8, hipMemcpyDeviceToHost));
+    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
+    if (moments) VITVS_HIP_CHECK(hipMemcpy(moments, d_moments, 18 * 8, hipMemcpyDeviceToHost));
+    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
+    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -2002,6 +2081,36 @@ int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
     PosePlan pl;
     memset(&pl, 0, sizeof(pl));
     const int rc = plan_pose(max_rows, n_iter, &pl);
+    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
+    return rc;
+}
+
+int vitvs_op_pose_rig_law(int32_t n_cams, int32_t ld, const double* P, const double* Q, const int32_t* usable, const double* rTc,
+                          const int32_t* cam_status, double lambda, int32_t n_iter, double sigma_min, void* scratch, double* v_rig,
+                          int32_t* rig_status, double* pose, int32_t* rig_info, double* moments, double* weights, double* sigma,
+                          void* stream) {
+    if (!P || !Q || !usable || !rTc || !scratch || !v_rig || !rig_status) return -1;
+    if (n_cams < 1 || ld < 1 || n_iter < 0 || n_iter > 16) return -2;
+    PoseRigArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_cams = n_cams; a.ld = ld; a.status = cam_status; a.rTc = rTc; a.P = P; a.Q = Q; a.usable = usable; a.lambda = lambda;
+    a.n_iter = n_iter; a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch);
+    a.v_rig = v_rig; a.rig_status = rig_status; a.pose = pose; a.rig_info = rig_info; a.moments = moments;
+    a.weights = weights; a.weights_stride = ld; a.sigma = sigma;
+    return launch_pose_rig(a, as_stream(stream));
+}
+
+int vitvs_op_pose_rig_scratch_bytes(int32_t n_cams, int32_t ld) {
+    if (n_cams < 1 || ld < 1) return -2;
+    const size_t b = pose_rig_scratch_bytes(n_cams, ld);
+    return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_pose_rig_plan(int32_t n_cams, int32_t ld, int32_t n_iter, int32_t* out) {
+    if (!out) return -1;
+    PoseRigPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_pose_rig(n_cams, ld, n_iter, &pl);
     out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
     return rc;
 }

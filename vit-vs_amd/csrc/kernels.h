@@ -467,6 +467,56 @@ int plan_pose(int max_rows, int n_iter, PosePlan* plan);
 size_t pose_scratch_bytes(int n_pairs, int ld);
 int launch_pose(const PoseArgs& a, hipStream_t stream);
 
+// ---- pose_rig.hip --------------------------------------------------------------------------
+// The pose rig law: ONE rigid displacement (R, t) of a rigid rig, aligning the matched 3-D points of ALL its
+// cameras in the rig frame.  Camera i has pose (R_i, t_i) in the rig frame; its points P, Q (PoseArgs' rule) enter the stack as
+// P' = R_i P + t_i, Q' = R_i Q + t_i at stack row i * ld + k, and v_rig = -lambda (R^T t, theta u) is a twist in the rig's own
+// frame.  One launch of ONE workgroup: pose_kernel's loop over n_cams * ld rows.  A camera contributes when its status is ST_OK
+// and it is not under the same-image shortcut.
+struct PoseRigArgs {
+    int n_cams;
+    int ld;                   // rows per camera of every per-row array (max_rows)
+    const int32_t* status;    // [n_cams] the cameras' statuses, or null (all ST_OK)
+    const double* rTc;        // [n_cams][12] R_i row-major, then t_i
+    // the handle's form (P == null): as PoseArgs'
+    const int32_t* selected;
+    const int32_t* s_uv;
+    const double* feat;
+    const int32_t* info;
+    const double* K;          // [n_cams][4]; sigma_min = 0.5 max_i max(pitch_u / fx_i, pitch_v / fy_i) median(Z*), i contributing
+    const uint16_t* zgoal;
+    int zgoal_stride, T;
+    double pitch_u, pitch_v;
+    // given camera-frame points (P != null): all ld rows of every camera
+    const double* P;          // [n_cams][ld][3]
+    const double* Q;          // [n_cams][ld][3]
+    const int32_t* usable;    // [n_cams][ld]: > 0 usable, 0 padded, < 0 a hole
+    double sigma_min;         // read when K is null
+    double lambda;
+    int n_iter;               // Tukey re-weightings, 0 .. 16
+    double* ws;               // [7][n_cams * ld] the stack: P' [3], Q' [3], the flag (pose_rig_scratch_bytes)
+    // outputs
+    double* v_rig;            // [6]
+    int32_t* rig_status;      // ST_OK; ST_TOO_FEW: < 3 rows with a weight, or degenerate; nobody contributes: the largest camera status
+    double* pose;             // [12] or null: R row-major, t (identity when the twist is zero)
+    int32_t* rig_info;        // [8] or null: contributing cameras, usable rows, sweeps, re-weightings, usable rows at weight 0,
+                              //              degenerate, holes, the largest camera status
+    double* moments;          // [18] or null: sum w, sum w P' [3], sum w Q' [3], sum w P' Q'^T [9], sum w |P'|^2, sum w |Q'|^2 over
+                              //               the stack with the final weights (zeros when nobody contributes)
+    double* weights;          // [n_cams][weights_stride] or null
+    int weights_stride;
+    double* sigma;            // [1] or null: the last scale
+};
+struct PoseRigPlan {
+    size_t lds;               // dynamic LDS of the launch
+    bool robust;              // pose_rig_kernel<robust>
+    bool lds_opt_in;          // > 64 KiB
+};
+// -2: n_cams, ld < 1, n_iter outside 0 .. 16; -3 (plan filled): more than 160 KiB of LDS
+int plan_pose_rig(int n_cams, int ld, int n_iter, PoseRigPlan* plan);
+size_t pose_rig_scratch_bytes(int n_cams, int ld);
+int launch_pose_rig(const PoseRigArgs& a, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

@@ -11,6 +11,8 @@ from __future__ import annotations
 
 from typing import Tuple
 
+import math
+
 import torch
 
 
@@ -99,6 +101,65 @@ def rig_velocity(normal_local: torch.Tensor, lam: float, group=None, robust_iter
     if float(total[27]) == 0.0:
         return torch.zeros(6, dtype=torch.float64, device=normal_local.device)
     return -float(lam) * (torch.linalg.pinv(G, hermitian=True) @ g)
+
+
+def pose_rig_velocity(moments_local: torch.Tensor, lam: float, group=None, robust_iterations: int = 0) -> torch.Tensor:
+    """The pose rig law (include/vitvs.h, vitvs_pose_rig_velocity_dev) for a rig spread over ranks: one camera, or
+    one shard of cameras, per GPU, every rank calling the law on ITS cameras with their poses in the common rig frame.
+    ``moments_local`` is the 18 doubles that call left (``Engine.pose_rig_velocity(...)[2]["moments"]``: sum w, sum w P', sum w Q',
+    sum w P' Q'^T, sum w |P'|^2, sum w |Q'|^2 over its stack; zeros when none of its cameras contributed).  ONE ``all_reduce(SUM)``
+    of the 18 doubles (the sums of a stack are the sums of its parts'), then on every rank in fp64 torch: the centroids pc, qc,
+    S = sum w P' Q'^T - sw pc qc^T and the two scatters likewise, Horn's 4 x 4 matrix, ``torch.linalg.eigh``, the quaternion of the
+    largest eigenvalue with q_w >= 0, t = qc - R pc and ``v_rig = -lam (R^T t, theta u)`` - the same [6] tensor everywhere.  All
+    zeros when no rank contributed a row or the stack is degenerate by the kernel's rule (ev_1 - ev_2 <= 1e-8 of the two scatters).
+
+    Raw moments lose the digits the centroid costs: centring AFTER the sum subtracts sw pc qc^T from a sum of the same size, so
+    about log10(|pc|^2 / scatter per point) digits of S go, where the single-GPU kernel centres every point first.  For a rig
+    whose points lie within a few metres and spread over decimetres that is two or three of sixteen digits
+    (tests/test_pose_rig_gloo.py: <= 1e-9 against the single-process law).
+
+    ``robust_iterations`` > 0 raises ``ValueError``: the robust form takes one median over ALL cameras' residuals per
+    re-weighting, which across ranks is another collective per iteration and is not built; it runs on one GPU."""
+    if int(robust_iterations) != 0:
+        raise ValueError("the robust pose rig law is not built across ranks (a median over all ranks' residuals per re-weighting); "
+                         "run the rig's cameras on one handle: Engine.pose_rig_velocity(..., robust_iterations=N)")
+    import torch.distributed as dist
+    if moments_local.shape != (18,) or moments_local.dtype != torch.float64:
+        raise ValueError("moments_local is the float64 [18] a pose rig call writes")
+    total = moments_local.clone()
+    if total.is_cuda and dist.get_backend(group) == "gloo":   # rehearsal path, as gather_velocities
+        host = total.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        total = host.to(moments_local.device)
+    else:
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+    zero = torch.zeros(6, dtype=torch.float64, device=moments_local.device)
+    m = total.cpu()
+    sw = float(m[0])
+    if sw <= 0.0:
+        return zero
+    pc, qc = m[1:4] / sw, m[4:7] / sw
+    S = m[7:16].reshape(3, 3) - sw * torch.outer(pc, qc)
+    scatter = float((m[16] - sw * (pc @ pc)) + (m[17] - sw * (qc @ qc)))
+    (Sxx, Sxy, Sxz), (Syx, Syy, Syz), (Szx, Szy, Szz) = S.tolist()
+    N = torch.tensor([[Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx],
+                      [Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz],
+                      [Szx - Sxz, Sxy + Syx, Syy - Sxx - Szz, Syz + Szy],
+                      [Sxy - Syx, Szx + Sxz, Syz + Szy, Szz - Sxx - Syy]], dtype=torch.float64)
+    ev, V = torch.linalg.eigh(N)                              # ascending
+    if float(ev[3] - ev[2]) <= 1e-8 * scatter:
+        return zero
+    q = V[:, 3] / torch.linalg.norm(V[:, 3])
+    if float(q[0]) < 0.0:
+        q = -q
+    a, b, c, d = q.tolist()
+    R = torch.tensor([[a * a + b * b - c * c - d * d, 2.0 * (b * c - a * d), 2.0 * (b * d + a * c)],
+                      [2.0 * (b * c + a * d), a * a - b * b + c * c - d * d, 2.0 * (c * d - a * b)],
+                      [2.0 * (b * d - a * c), 2.0 * (c * d + a * b), a * a - b * b - c * c + d * d]], dtype=torch.float64)
+    t = qc - R @ pc
+    nv = float(torch.linalg.norm(q[1:]))
+    theta_u = torch.zeros(3, dtype=torch.float64) if nv == 0.0 else (2.0 * math.atan2(nv, a) / nv) * q[1:]
+    return (-float(lam) * torch.cat([R.T @ t, theta_u])).to(moments_local.device)
 
 
 class VelocityGather:

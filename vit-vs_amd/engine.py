@@ -596,6 +596,72 @@ class Engine:
         info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
         return v, info
 
+    POSE_RIG_INFO_FIELDS = ("cameras", "usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes", "worst_status")
+
+    @staticmethod
+    def _pose_rig_arguments(rig, K, status, robust_iterations):
+        """The checks of the pose rig law's arguments (no handle needed): float64 rTc [n, 12], K [n, 4] and N."""
+        N = int(robust_iterations)
+        if not 0 <= N <= 16:
+            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        n = len(rig)
+        if n < 1:
+            raise ValueError("rig is a sequence of (R_i, t_i), one per camera of the last velocity call")
+        rtc = np.zeros((n, 12))
+        for i, (R, t) in enumerate(rig):
+            R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
+            if R.size != 9 or t.size != 3:
+                raise ValueError("rig is a sequence of (R_i [3, 3], t_i [3])")
+            rtc[i, :9], rtc[i, 9:] = R.reshape(9), t.reshape(3)
+        if int(status.numel() if torch.is_tensor(status) else np.asarray(status).size) != n:
+            raise ValueError("one status per camera of the rig expected")
+        k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
+        k = np.broadcast_to(k.reshape(-1, 4), (n, 4)) if k.size == 4 else k.reshape(-1, 4)
+        if k.shape[0] != n:
+            raise ValueError("one (fx, fy, cx, cy) per camera expected")
+        return rtc, np.ascontiguousarray(k), N
+
+    def pose_rig_velocity(self, rig, K, status, robust_iterations: int = 0):
+        """``vitvs_pose_rig_velocity_dev``: the pose rig law of a rigid rig whose cameras were the pairs of the last
+        velocity call: ONE rigid alignment (R, t) of the matched 3-D points of all cameras in the rig frame, and ``v_rig = -lambda
+        (R^T t, theta u)`` in the rig's own frame.  ``rig``: a sequence of (R_i, t_i), camera i's pose in the rig frame (what
+        ``MultiController(rig=...)`` takes); ``K``: the intrinsics of that call, [n, 4] or one (fx, fy, cx, cy) for all; ``status``:
+        the int32 [n] it returned (a device tensor stays on the device); ``robust_iterations``: Tukey re-weightings with one median
+        over all cameras' residuals, 0 .. 16.  Returns ``(v_rig float64 [6] device tensor, rig_status int, info)``, ``info`` = dict
+        (cameras, usable, sweeps, reweighted, zero_weights, degenerate, holes, worst_status as ints; R [3, 3], t [3], moments [18],
+        weights [n, max_rows], sigma [1] as device tensors).  One launch on the current stream; reading the status synchronises.
+        The first call allocates: make it outside a stream capture."""
+        rtc, k, N = self._pose_rig_arguments(rig, K, status, robust_iterations)      # (before anything touches the device)
+        n = int(rtc.shape[0])
+        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+        rd, kd = torch.from_numpy(rtc).to(self.device), torch.from_numpy(k).to(self.device)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
+        v, pose, moments, weights, sigma = f64(6), f64(12), f64(18), f64(n, self.max_rows), f64(1)
+        out = torch.empty(9, dtype=torch.int32, device=self.device)      # rig_status | rig_info [8]
+        rc = self.lib.vitvs_pose_rig_velocity_dev(self.handle, n, _ptr(rd), _ptr(kd), _ptr(st), N, _ptr(v), _ptr(out), _ptr(pose),
+                                                  _ptr(out[1:]), _ptr(moments), _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
+        self._check(rc, "vitvs_pose_rig_velocity_dev")
+        o = out.cpu().numpy()
+        info = dict(R=pose[:9].reshape(3, 3), t=pose[9:], moments=moments, weights=weights, sigma=sigma)
+        info.update({name: int(o[1 + i]) for i, name in enumerate(self.POSE_RIG_INFO_FIELDS)})
+        return v, int(o[0]), info
+
+    def pose_rig_velocity_host(self, rig, K, status, robust_iterations: int = 0):
+        """``vitvs_pose_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info)`` out, ``info`` as
+        ``pose_rig_velocity``'s with numpy arrays (``sigma`` a float).  Synchronous."""
+        rtc, k, N = self._pose_rig_arguments(rig, K, status, robust_iterations)
+        n = int(rtc.shape[0])
+        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        v, pose, moments, weights, sigma = np.zeros(6), np.zeros(12), np.zeros(18), np.zeros((n, self.max_rows)), np.zeros(1)
+        rs, rinfo = np.zeros(1, np.int32), np.zeros(8, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_pose_rig_velocity(self.handle, n, p(rtc), p(k), p(st), N, p(v), p(rs), p(pose), p(rinfo), p(moments),
+                                              p(weights), p(sigma))
+        self._check(rc, "vitvs_pose_rig_velocity")
+        info = dict(R=pose[:9].reshape(3, 3), t=pose[9:], moments=moments, weights=weights, sigma=float(sigma[0]))
+        info.update({name: int(rinfo[i]) for i, name in enumerate(self.POSE_RIG_INFO_FIELDS)})
+        return v, int(rs[0]), info
+
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),

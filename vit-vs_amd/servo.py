@@ -485,8 +485,13 @@ class MultiController:
         # ``rig_velocity_raw``, and ``v_rig`` smoothed by the cameras' EMA; the cameras' own state is exactly as without it.
         # With ``params.rig_robust_iterations`` = N > 0 that law is the robust rig law (N Tukey re-weightings of the stack) and
         # ``rig_weights`` [cameras, max_rows] holds the round's final weights (0 for a camera without an image, None before).
+        # With ``params.law`` = "pose" (Engine backend, ``rig=`` and ``goal_depth=`` required) that law is the pose rig law
+        # (Engine.pose_rig_velocity) with ``params.rig_pose_robust_iterations`` re-weightings, and ``rig_pose`` = (R, t)
+        # is the current rig in the goal rig's frame; ``goal_depth`` is then one image for all cameras or [N, v, u], one per camera.
         self.rig_W = None
+        self.rig = None
         self.rig_weights = None
+        self.rig_pose = None
         self.rig_velocity_raw, self.v_rig, self.rig_status, self.rig_info = None, None, None, None
         self._rig_ema = [None] * 6
         if rig is not None:
@@ -495,11 +500,27 @@ class MultiController:
             if len(rig) != len(goal_images):
                 raise ValueError("rig= takes one (R, t) per camera")
             self.rig_W = np.stack([twist_matrix(R, t) for R, t in rig])
+            self.rig = [(np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)) for R, t in rig]
         self.engines = list(backend.engines) if self.pipe is not None else [backend]
         self.engine = self.engines[0]
-        if (params or self.engine.params).law != "ibvs":
-            raise ValueError('MultiController runs the image-based law per camera: law="pose" is servo.Controller\'s (a pose rig law is '
-                             'not part of the library)')
+        self.law = (params or self.engine.params).law
+        self._goal_depths, self._goal_depth_live = None, None
+        if self.law == "pose":
+            # the cameras run the image-based law exactly as with law "ibvs"; the pose law of a MultiController is the RIG's
+            if self.pipe is not None:
+                raise ValueError('law="pose" needs the Engine backend: the pose rig law reads all cameras in one handle')
+            if rig is None:
+                raise ValueError('MultiController runs the image-based law per camera: law="pose" here is the pose rig law and needs '
+                                 'rig=[(R_i, t_i), ...] (one camera: servo.Controller)')
+            if goal_depth is None:
+                raise ValueError('law="pose" needs goal_depth: the depth image(s) taken at the goal pose')
+            if (params or self.engine.params).interaction == "desired":
+                raise ValueError('law="pose" does not combine with interaction="desired" (its feature rows hold Z*, not Z)')
+            gd = np.asarray(goal_depth)
+            if gd.ndim == 3 and gd.shape[0] != len(goal_images):
+                raise ValueError("goal_depth is one image for all cameras, or one per camera")
+            self._goal_depths = gd if gd.ndim == 3 else None
+            params = (params or self.engine.params).replace(law="ibvs")
         if selection not in ("order", "dense"):
             raise ValueError('MultiController draws on the device: selection is "order" or "dense" (explicit ids per round: ibvs(selection=...))')
         self.selection, self.generator = selection, generator
@@ -511,6 +532,8 @@ class MultiController:
                 e.apply_law_params(params)
         self.cameras = [Controller(self.engine, g, params, selection="order") for g in goal_images]
         self.params = self.cameras[0].params
+        if self.law == "pose":
+            self.params = self.params.replace(law="pose")
         # the goal depth of interaction "desired" / "mean": one image (uint16 [v_max, u_max]) that serves every camera, in every
         # engine or slot (one image pairs with a call of any number of pairs)
         if goal_depth is not None:
@@ -584,10 +607,24 @@ class MultiController:
             mode = _lib.SELECT_ORDER
             sel = [torch.randperm(eng.tokens, generator=self.generator).to(torch.int32) for _ in live]
         if self.pipe is None:
+            if self._goal_depths is not None and self._goal_depth_live != live:
+                # one goal depth per camera: the engine pairs image j with pair j of the call, so a round of other live
+                # cameras needs theirs (set-up, only when the live set changed)
+                eng.set_goal_depth(np.ascontiguousarray(self._goal_depths[live]))
+                self._goal_depth_live = list(live)
             stack = lambda xs: torch.stack([torch.as_tensor(x).to(eng.device) for x in xs])   # noqa: E731
             v, st = eng.compute_velocity(stack(cur), stack(des), np.stack(depth), p.intrinsics(), mode=mode,
                                          selection=(torch.stack(sel) if mode == _lib.SELECT_ORDER else sel), num_pairs=k)
-            if self.rig_W is not None:                    # (before the host reads: the law is one more launch behind the call)
+            if self.law == "pose":                        # the pose rig law in place of the image-based rig law
+                v_r, self.rig_status, self.rig_info = eng.pose_rig_velocity([self.rig[i] for i in live], p.intrinsics(), st,
+                                                                            p.rig_pose_robust_iterations)
+                if self.rig_status == _lib.STATUS_OK:
+                    self.rig_velocity_raw = v_r.cpu().numpy()
+                    self.v_rig = ema_update(self._rig_ema, self.rig_velocity_raw, p.ema_alpha)
+                    self.rig_pose = (self.rig_info["R"].cpu().numpy(), self.rig_info["t"].cpu().numpy())
+                    self.rig_weights = np.zeros((len(self.cameras), eng.max_rows))
+                    self.rig_weights[live] = self.rig_info["weights"].cpu().numpy()
+            elif self.rig_W is not None:                  # (before the host reads: the law is one more launch behind the call)
                 if p.rig_robust_iterations:               # Tukey IRLS over the stack, one median over all live cameras' residuals
                     v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st, p.rig_robust_iterations,
                                                                            K=p.intrinsics())
