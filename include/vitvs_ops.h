@@ -77,6 +77,14 @@ VITVS_API int vitvs_op_linear_tile(int32_t precision, int32_t M, int32_t N, int3
  * out[0..6] = big family (gemm_big.hip), rows, columns, k-groups, ring stages, K slices, XCD map.  0, or -2 when unlaunchable.
  * (k-groups 0: the kernels of gemm_big.hip; ring stages 0: the tile's default ring.) */
 VITVS_API int vitvs_op_linear_plan(int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t slices, int32_t* out);
+/* the grid of a launch on a tile of gemm_big.hip (rows x cols = 256 x 256 / 192 / 128, 192 x 128 / 256), decided on the launch
+ * side from the shape alone; slices as vitvs_op_linear_variant's (0: the store form, one slice).  out[0..3] = tiles (slices x row
+ * tiles x column tiles), persistent workgroups (a multiple of 8, at most 256), XCD map (0: every XCD walks an eighth of the tile
+ * list; XR in {1, 2, 4, 8}: the XCDs form an XR x 8 / XR grid over (slice and row tile, column tile) and each walks its block),
+ * k-tiles per slice.  Returns 0, or -2 (out zeroed) wherever vitvs_op_linear_variant refuses that tile at that shape: fp32, N not
+ * a multiple of cols, a slice that is not 2 .. 255 k-tiles, more than 255 column tiles or slices.  No device work. */
+VITVS_API int vitvs_op_linear_big_grid(int32_t precision, int32_t rows, int32_t cols, int32_t M, int32_t N, int32_t K,
+                             int32_t slices, int32_t* out);
 /* the attention launch the library makes for vitvs_op_attention / _q (and the handle's forward) at this shape, under the
  * calling thread's plan hint: out[0..5] = kernel, workgroups, threads per workgroup, dynamic LDS bytes, key tiles per
  * workgroup (long kernel; 0 otherwise), divided (1: the 16-bit long kernel cuts the keys of a query block into ranges merged

@@ -144,6 +144,25 @@ def test_linear_tile_plan_of_the_library():
         lib.vitvs_op_plan_in_flight(prev)
 
 
+def test_linear_big_grid_of_the_library():
+    """The grid of a launch on the 256- / 192-row tiles is host arithmetic on the launch side (vitvs_op_linear_big_grid, no device
+    call): tiles, persistent workgroups, the XCD map of the tile walk, k-tiles per slice.  Pins the map rule at the shapes its
+    comments name; tests/test_gemm_exact_host.py walks the product domain and checks the refusals."""
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 4)()
+
+    def grid(prec, rows, cols, m, n, k, slices=0):
+        assert lib.vitvs_op_linear_big_grid(prec, rows, cols, m, n, k, slices, out) == 0
+        return list(out)
+    b = _lib.BF16
+    assert grid(b, 256, 256, 6274, 2304, 768) == [225, 232, 0, 12]       # under one tile per CU: the balanced list
+    assert grid(b, 256, 128, 6274, 3072, 768) == [600, 256, 4, 12]       # several tiles per CU: a 4 x 2 XCD grid
+    assert grid(b, 256, 192, 6274, 3072, 768) == [400, 256, 4, 12]
+    assert grid(b, 192, 128, 6274, 768, 3072, 3) == [594, 256, 8, 16]    # K slices count as rows of the grid
+    assert grid(_lib.F16X2, 256, 256, 1542, 1024, 1024, 2) == [56, 56, 0, 16]   # f16x2: 32 logical k per k-tile
+    assert grid(b, 256, 192, 5245, 4224, 128) == [462, 256, 1, 2]        # one row of eight column blocks
+
+
 def test_attention_plan_of_the_library():
     """The attention launch per shape is host arithmetic too (vitvs_op_attention_plan, no device call): kernel, workgroups,
     threads, dynamic LDS bytes, key tiles per workgroup, divided.  Every attention kernel is exact for every shape it accepts,

@@ -98,6 +98,7 @@ PROTOTYPES = {
     "vitvs_op_linear_tile": (_I, [_I, _I, _I, _I, _I, _P]),
     "vitvs_op_attention_plan": (_I, [_I, _I, _I, _I, _P]),
     "vitvs_op_linear_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "vitvs_op_linear_big_grid": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "vitvs_op_gram_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "vitvs_op_servo_plan": (_I, [_I, _I, _I, _I, _I, _P]),
     "vitvs_op_rig_law": (_I, [_I, _P, _P, _I, _P, C.c_double, _P, _P, _P, _P, _P, _P]),

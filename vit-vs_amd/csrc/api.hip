@@ -1984,6 +1984,14 @@ int vitvs_op_linear_plan(int32_t precision, int32_t epilogue, int32_t M, int32_t
     out[5] = pl.splits; out[6] = pl.xcd_map;
     return pl.rows ? 0 : -2;
 }
+int vitvs_op_linear_big_grid(int32_t precision, int32_t rows, int32_t cols, int32_t M, int32_t N, int32_t K, int32_t slices,
+                             int32_t* out) {
+    if (!out || slices < 0) return -1;
+    BigGrid g;
+    const int rc = linear_big_grid(to_prec(precision), rows, cols, M, N, K, slices > 0 ? slices : 1, &g);
+    out[0] = (int32_t)std::min<long>(g.tiles, INT32_MAX); out[1] = g.slots; out[2] = g.xmap; out[3] = g.nk;
+    return rc;
+}
 int vitvs_op_attention_plan(int32_t precision, int32_t n_img, int32_t N, int32_t H, int32_t* out) {
     if (!out) return -1;
     const AttnPlan pl = plan_attention(to_prec(precision), n_img, N, H);

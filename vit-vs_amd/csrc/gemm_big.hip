@@ -477,15 +477,12 @@ typedef BigTile<4, 2, 4, 6> Tile256x192;
 typedef BigTile<2, 4, 6, 2> Tile192x128;
 typedef BigTile<2, 4, 6, 4> Tile192x256;
 
-template <typename T, class Tile, class Epi>
-static int launch_big_one(const T* A, const T* W, typename Epi::Out* out, const float* bias, int M, int N, int K, int splits,
-                          int gelu, hipStream_t stream, int wexp = 0) {
-    // (f16x2: K counts fp16 per row, two per logical k; a k-tile is 32 logical k)
-    static std::atomic<unsigned long long> raised{0};
-    constexpr int LDS_BYTES = Tile::lds_bytes(Epi::HAS_BIAS);
-    if (raise_lds_limit(reinterpret_cast<const void*>(&linear_big_kernel<T, Tile, Epi>), LDS_BYTES, raised)) return -1;
-    const int nx = N / Tile::BN, ny = (M + Tile::BM - 1) / Tile::BM, nk = K / splits / 64;
-    if (N % Tile::BN || K % (splits * 64) || nk < 2 || nk > 255 || nx > 255 || splits > 255 || wexp < 0 || wexp > 31) return -2;
+// The grid of one launch on BM x BN tiles; K counts 16-bit elements per row (f16x2: two per logical k).  -2: not launchable.
+static int big_grid(int BM, int BN, int M, int N, int K, int splits, int wexp, BigGrid* g) {
+    *g = BigGrid{};
+    if (M < 1 || N < 1 || K < 1 || splits < 1) return -2;
+    const int nx = N / BN, ny = (M + BM - 1) / BM, nk = K / splits / 64;
+    if (N % BN || K % (splits * 64) || nk < 2 || nk > 255 || nx > 255 || splits > 255 || wexp < 0 || wexp > 31) return -2;
     const long tiles = (long)nx * ny * splits;
     const int slots = (int)std::min<long>(8 * ((tiles + 7) / 8), 256);       // one workgroup per CU at most
     // XCD map (see the kernel): blocks of an XR x (8 / XR) XCD grid when CUs walk several tiles; among the grids whose
@@ -498,10 +495,32 @@ static int launch_big_one(const T* A, const T* W, typename Epi::Out* out, const 
         for (int xr : {1, 2, 4, 8}) {
             const long xc = 8 / xr, rows = (R + xr - 1) / xr, cols = (nx + xc - 1) / xc;
             if ((rows * cols + wgs - 1) / wgs > passes_1d) continue;
-            const double bytes = (double)rows * Tile::BM + (double)cols * Tile::BN * std::max<long>(1, (rows + ny - 1) / ny);
+            const double bytes = (double)rows * BM + (double)cols * BN * std::max<long>(1, (rows + ny - 1) / ny);
             if (bytes < best) { best = bytes; xmap = xr; }
         }
     }
+    g->tiles = tiles; g->slots = slots; g->xmap = xmap; g->nk = nk; g->nx = nx;
+    return 0;
+}
+
+int linear_big_grid(Precision p, int rows, int cols, int M, int N, int K, int splits, BigGrid* g) {
+    *g = BigGrid{};
+    // what launch_linear is given for a forced tile: plan_linear knows the tiles, the shapes and the precisions that have them
+    const LinearPlan pl = rows > 0 && splits > 0 ? plan_linear(p, M, N, K, EPI_PARTIAL, splits, true, rows, cols) : LinearPlan{};
+    if (!pl.rows || !pl.big) return -2;
+    return big_grid(rows, cols, M, N, p == PREC_X2 ? 2 * K : K, splits, 0, g);
+}
+
+template <typename T, class Tile, class Epi>
+static int launch_big_one(const T* A, const T* W, typename Epi::Out* out, const float* bias, int M, int N, int K, int splits,
+                          int gelu, hipStream_t stream, int wexp = 0) {
+    // (f16x2: K counts fp16 per row, two per logical k; a k-tile is 32 logical k)
+    static std::atomic<unsigned long long> raised{0};
+    constexpr int LDS_BYTES = Tile::lds_bytes(Epi::HAS_BIAS);
+    if (raise_lds_limit(reinterpret_cast<const void*>(&linear_big_kernel<T, Tile, Epi>), LDS_BYTES, raised)) return -1;
+    BigGrid g;
+    if (int rc = big_grid(Tile::BM, Tile::BN, M, N, K, splits, wexp, &g)) return rc;
+    const int nx = g.nx, nk = g.nk, slots = g.slots, xmap = g.xmap;
     launch(linear_big_kernel<T, Tile, Epi>, dim3((unsigned)slots), dim3(512), LDS_BYTES, stream, A, W, out, bias, M, N, K,
            (int)(((unsigned)nk << 24) | ((unsigned)nx << 16) | ((unsigned)splits << 8) | ((unsigned)wexp << 1) | (unsigned)(gelu & 1)),
            (int)((unsigned)slots | ((unsigned)xmap << 16)));

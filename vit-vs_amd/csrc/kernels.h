@@ -97,6 +97,15 @@ int launch_linear(const LinearPlan& plan, const void* A, const void* W, const fl
 template <typename T>
 int launch_linear_big(const LinearPlan& plan, const T* A, const T* W, const float* bias, void* out, int K, int gelu,
                       hipStream_t stream, int wexp);
+// The grid launch_linear_big makes for one launch, host arithmetic (gemm_big.hip; vitvs_op_linear_big_grid): the (slice, row tile,
+// column tile) list, the persistent workgroups that walk it (a multiple of 8, at most 256), the XCD map (0: eighths of the list;
+// XR in {1, 2, 4, 8}: an XR x 8 / XR XCD grid over (row-slices, column tiles)) and the k-tiles of a slice.
+struct BigGrid {
+    long tiles = 0;
+    int slots = 0, xmap = 0, nk = 0, nx = 0;
+};
+// rows x cols: a tile of gemm_big.hip; K logical.  0, or -2 wherever launch_linear refuses the launch on that tile.
+int linear_big_grid(Precision p, int rows, int cols, int M, int N, int K, int splits, BigGrid* g);
 
 // ---- elementwise.hip -----------------------------------------------------------------------
 struct PatchifyArgs {
