@@ -396,6 +396,41 @@ VITVS_API int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double
                                   double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info, double* weights,
                                   double* sigma);
 
+/* --- the homography law --------------------------------------------------------------------------
+ * A law for a planar target that needs no depth at all (Benhimane and Malis, "Homography-based 2D visual servoing",
+ * IJRR 2007).  Every feature row k < info[1] of pair b whose token is selected (>= 0) gives a current normalised image point
+ * m_k = (x, y) (feat; the moved match under option subpatch) and a goal point m*_k = ((u* - cx) / fx, (v* - cy) / fy) (s_uv).  H, the
+ * 3 x 3 homography with m* ~ H m, is the eigenvector of the smallest eigenvalue of the 9 x 9 DLT normal matrix of the Hartley-
+ * normalised points (cyclic Jacobi in fp64), denormalised and scaled to det H = 1, and
+ *   v_h = -lambda (depth_scale (H - I) m_c, (H21 - H12, H02 - H20, H10 - H01))      m_c = (sum w x / sum w, sum w y / sum w, 1)
+ * is a twist in the current camera's own optical frame, the convention of v_c.  depth_scale (metres) is a rough guess of the
+ * distance to the target: it scales the translational gain, not the fixed point.  n_iter > 0: Tukey IRLS (c = 4.6851) on the
+ * transfer error rho = |pi(H m) - m*| (+inf when the third component of H m is <= 0), sigma = max(1.4826 median(rho over usable
+ * rows), sigma_min), sigma_min = 0.5 max(pitch_u / fx, pitch_v / fy); one more solve after the last re-weighting.
+ *   K, status    device double [n_pairs][4] and int32 [n_pairs]: the K and the status of the velocity call
+ *   depth_scale  > 0 and finite;  n_iter  re-weightings, 0 .. 16
+ *   v_h          double [n_pairs][6];  h_status int32 [n_pairs]: the camera's status with v_h = 0 when that is
+ *                VITVS_NO_CORRESPONDENCE or VITVS_TOO_FEW (VITVS_NO_DEPTH does NOT stop this law: the camera's law writes its rows
+ *                before it looks for a depth); VITVS_OK with v_h = 0, H = I under the same-image shortcut; VITVS_TOO_FEW (v_h = 0,
+ *                H = I) when fewer than 4 rows are usable or keep a weight > 0, or the set is degenerate: a mean distance of 0, the
+ *                second-smallest eigenvalue <= 1e-8 trace(M) (collinear points), or |det H| <= 1e-8 |H|_F^3; VITVS_OK otherwise
+ *   H            double [n_pairs][9] or NULL: row-major
+ *   h_info       int32 [n_pairs][8] or NULL: usable rows, Jacobi sweeps of the last solve, re-weightings done, usable rows with
+ *                final weight 0, degenerate flag, rows with rho = +inf at the last re-weighting, 0, 0
+ *   weights      double [n_pairs][max_rows] or NULL;  sigma double [n_pairs] or NULL: the last scale
+ * One launch on `stream`; valid in stream order behind any law evaluation of the handle with n_pairs pairs under every value of
+ * option interaction, replayed graphs included, and it changes nothing that call left.  Bit-reproducible.  The first call
+ * allocates the workspace and synchronises the device: make it outside any stream capture.
+ * Returns 0, -1 (a null required pointer), -2 (n_iter outside 0 .. 16, depth_scale <= 0 or not finite), -3 (max_rows too large
+ * for the robust form's LDS), -5 (no law evaluation yet, or n_pairs is not its pair count).  No counterpart in the reference. */
+VITVS_API int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status,
+                                            double depth_scale, int32_t n_iter, double* v_h, int32_t* h_status, double* H,
+                                            int32_t* h_info, double* weights, double* sigma, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous. */
+VITVS_API int vitvs_homography_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
+                                        int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
+                                        double* sigma);
+
 /* --- the pose rig law ----------------------------------------------------------------------------
  * ONE rigid 3-D alignment over the matched points of ALL cameras of a rigid rig, for a rig whose cameras were the
  * pairs of the last law evaluation.  Camera i has pose (R_i, t_i) in the rig frame, X_rig = R_i X_cam + t_i (the (R, t) of

@@ -155,6 +155,21 @@ VITVS_API int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld);   /* -2 
  * 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out NULL),
  * -2 (max_rows < 1, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
 VITVS_API int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out);
+/* The homography law's kernel (vitvs_homography_velocity_dev, include/vitvs.h) on caller-given points:
+ *   m, ms    device double [n_pairs][ld][2]: current and goal normalised image points;  usable int32 [n_pairs][ld]: > 0 usable
+ *   depth_scale > 0 and finite;  n_iter 0 .. 16;  sigma_min  the floor of the scale, given directly
+ *   scratch  vitvs_op_homography_scratch_bytes(n_pairs, ld) = 8 * 5 n_pairs ld bytes
+ *   v_h [n_pairs][6], h_status [n_pairs]; H [n_pairs][9], h_info [n_pairs][8], weights [n_pairs][ld], sigma [n_pairs] or NULL
+ * Returns 0, -1 (a null required pointer), -2 (n_pairs or ld < 1, n_iter outside 0 .. 16, depth_scale <= 0 or not finite), -3 (the
+ * plan's). */
+VITVS_API int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable,
+                                      double lambda, double depth_scale, int32_t n_iter, double sigma_min, void* scratch, double* v_h,
+                                      int32_t* h_status, double* H, int32_t* h_info, double* weights, double* sigma, void* stream);
+VITVS_API int vitvs_op_homography_scratch_bytes(int32_t n_pairs, int32_t ld);   /* -2 as above, -3 past 2 GiB */
+/* The launch plan of the homography law (host arithmetic, no device): out[0] the dynamic LDS bytes = 8 (752 + (n_iter > 0 ? 2
+ * max_rows : 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out
+ * NULL), -2 (max_rows < 1, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
+VITVS_API int vitvs_op_homography_plan(int32_t max_rows, int32_t n_iter, int32_t* out);
 /* The pose rig law's kernel (vitvs_pose_rig_velocity_dev, include/vitvs.h) on caller-given camera-frame points:
  *   P, Q        device double [n_cams][ld][3];  usable int32 [n_cams][ld]: > 0 usable, 0 padded, < 0 a hole
  *   rTc         device double [n_cams][12]: R_i row-major, then t_i;  cam_status int32 [n_cams] or NULL (all VITVS_OK)

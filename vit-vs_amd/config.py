@@ -155,7 +155,8 @@ def baseline_config(key: str) -> ViTConfig:
     return vit_config(name, size)
 
 
-LAWS = ("ibvs", "pose")                          # ServoParams.law: the image-based law of the reference, or the pose law
+LAWS = ("ibvs", "pose", "homography")            # ServoParams.law: the image-based law of the reference, the pose law,
+                                                 # or the homography law of a planar target, which needs no depth
 INTERACTIONS = ("current", "desired", "mean")    # values 0 / 1 / 2 of option "interaction" (include/vitvs.h)
 
 
@@ -182,11 +183,16 @@ class ServoParams:
     rig_robust_iterations: int = 0  # Tukey re-weightings of the RIG law (MultiController(rig=...): one median over all cameras'
                                     # residuals, vitvs_rig_robust_velocity_dev; 1 .. 16); 0 = the plain rig law
 
-    law: str = "ibvs"              # the twist a servo.Controller executes: "ibvs", the image-based law above (the reference's), or
-                                   # "pose": the pose law on the matched 3-D points (Engine.pose_velocity), which needs a goal depth
+    law: str = "ibvs"              # the twist a servo.Controller executes: "ibvs", the image-based law above (the reference's),
+                                   # "pose": the pose law on the matched 3-D points (Engine.pose_velocity), which needs a goal depth, or
+                                   # "homography": the homography law of a planar target (Engine.homography_velocity): RGB only
     pose_robust_iterations: int = 0  # Tukey re-weightings of the pose law (0 .. 16); 0 = the plain alignment
     rig_pose_robust_iterations: int = 0  # Tukey re-weightings of the pose RIG law (MultiController(rig=..., law "pose"): one median
                                          # over all cameras' 3-D residuals, vitvs_pose_rig_velocity_dev; 0 .. 16); 0 = the plain one
+
+    homography_robust_iterations: int = 0  # Tukey re-weightings of the homography law (0 .. 16); 0 = the plain DLT
+    homography_depth: float = 1.0  # the homography law's depth scale in metres (> 0): a rough guess of the distance to the target,
+                                   # which scales its translational gain and nothing else
 
     def __post_init__(self):
         if self.interaction not in INTERACTIONS:
@@ -195,6 +201,10 @@ class ServoParams:
             raise ValueError(f"law is one of {LAWS}, got {self.law!r}")
         if not 0 <= int(self.pose_robust_iterations) <= 16:
             raise ValueError(f"pose_robust_iterations is 0 .. 16, got {self.pose_robust_iterations!r}")
+        if not 0 <= int(self.homography_robust_iterations) <= 16:
+            raise ValueError(f"homography_robust_iterations is 0 .. 16, got {self.homography_robust_iterations!r}")
+        if not (float(self.homography_depth) > 0.0 and math.isfinite(float(self.homography_depth))):
+            raise ValueError(f"homography_depth is a positive, finite length in metres, got {self.homography_depth!r}")
         if not 0 <= int(self.rig_robust_iterations) <= 16:
             raise ValueError(f"rig_robust_iterations is 0 .. 16, got {self.rig_robust_iterations!r}")
         if not 0 <= int(self.rig_pose_robust_iterations) <= 16:
@@ -257,8 +267,8 @@ def load_reference_config(source) -> ReferenceConfig:
     ``max_velocity_vector_history`` 200, ``background_thresh`` 0.5 (vitvs_v2.py:287, 296, 316, 319).  ``robust_iterations`` (this
     project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
-    else "current"; ``law`` ("ibvs" / "pose"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise, else "ibvs",
-    0 and 0."""
+    else "current"; ``law`` ("ibvs" / "pose" / "homography"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise,
+    else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -278,11 +288,13 @@ def load_reference_config(source) -> ReferenceConfig:
                         interaction=str(cfg.get("interaction", "current")),
                         rig_robust_iterations=int(cfg.get("rig_robust_iterations", 0)), law=str(cfg.get("law", "ibvs")),
                         pose_robust_iterations=int(cfg.get("pose_robust_iterations", 0)),
-                        rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)))
+                        rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)),
+                        homography_robust_iterations=int(cfg.get("homography_robust_iterations", 0)),
+                        homography_depth=float(cfg.get("homography_depth", 1.0)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
-            "rig_pose_robust_iterations"}
+            "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

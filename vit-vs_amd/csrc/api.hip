@@ -137,6 +137,11 @@ struct vitvs_handle {
     double* pose_ws = nullptr;
     unsigned char* pose_io = nullptr;  // K [P][4] | v_pose [P][6] | pose [P][12] | sigma [P] | weights [P][max_rows] f64 | status [P] |
                                        // pose_status [P] | pose_info [P][8] i32
+    // the homography law (vitvs_homography_velocity_dev): its points [max_pairs][5][max_rows] f64, and the device side of the
+    // host-pointer form, allocated by the first homography call
+    double* hom_ws = nullptr;
+    unsigned char* hom_io = nullptr;   // K [P][4] | v_h [P][6] | H [P][9] | sigma [P] | weights [P][max_rows] f64 | status [P] |
+                                       // h_status [P] | h_info [P][8] i32
     // the pose rig law (vitvs_pose_rig_velocity_dev): its stack [7][max_pairs * max_rows] f64, and the device side of the
     // host-pointer form, allocated by the first pose rig call
     double* pose_rig_ws = nullptr;
@@ -1801,6 +1806,79 @@ int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const
     return 0;
 }
 
+// --- the homography law --------------------------------------------------------------------------
+static int homography_prepare(vitvs_handle* h, int n_pairs, double depth_scale, int n_iter) {
+    if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
+    if (!(depth_scale > 0.0) || !std::isfinite(depth_scale)) return set_err(h, -2, "depth_scale is a positive, finite length in metres");
+    if (!h->last_pairs) return set_err(h, -5, "vitvs_homography_velocity follows a velocity call on the same handle");
+    if (n_pairs != h->last_pairs)
+        return set_err(h, -5, "n_pairs (" + std::to_string(n_pairs) + ") is not the pair count of the last law evaluation (" +
+                                  std::to_string(h->last_pairs) + ")");
+    HomographyPlan pl;
+    if (plan_homography(h->cfg.max_rows, n_iter, &pl))
+        return set_err(h, -3, "the robust homography law keeps two doubles per feature row in LDS: max_rows is too large");
+    if (!h->hom_ws) {                           // set-up, not the call path (and never inside a capture): as the pose law's
+        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
+        int rc = dev_alloc(h, &h->hom_ws, P * 5 * R);
+        if (!rc) rc = dev_alloc(h, &h->hom_io, (P * (4 + 6 + 9 + 1 + R)) * 8 + P * 10 * 4);
+        if (rc) return set_err(h, rc, "homography workspace allocation failed");
+        VITVS_HIP_CHECK(hipDeviceSynchronize());
+    }
+    return 0;
+}
+
+int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
+                                  int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
+                                  double* sigma, void* stream) {
+    if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
+    const vitvs_config& c = h->cfg;
+    HomographyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_pairs = n_pairs; a.ld = c.max_rows; a.status = status;
+    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
+    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
+    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    a.lambda = c.lambda; a.depth_scale = depth_scale; a.n_iter = n_iter; a.ws = h->hom_ws;
+    a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info;
+    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    const int rc = launch_homography(a, as_stream(stream));
+    return rc ? set_err(h, rc, "homography law launch failed") : 0;
+}
+
+int vitvs_homography_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
+                              int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
+                              double* sigma) {
+    if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
+    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_pairs;
+    double* d_K = reinterpret_cast<double*>(h->hom_io);
+    double* d_v = d_K + P * 4;
+    double* d_H = d_v + P * 6;
+    double* d_sigma = d_H + P * 9;
+    double* d_weights = d_sigma + P;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
+    int32_t* d_h_status = d_status + P;
+    int32_t* d_info = d_h_status + P;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
+    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = vitvs_homography_velocity_dev(h, n_pairs, d_K, d_status, depth_scale, n_iter, d_v, d_h_status, d_H, d_info, d_weights,
+                                               d_sigma, st))
+        return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    VITVS_HIP_CHECK(hipMemcpy(v_h, d_v, n * 6 * 8, hipMemcpyDeviceToHost));
+    VITVS_HIP_CHECK(hipMemcpy(h_status, d_h_status, n * 4, hipMemcpyDeviceToHost));
+    if (H) VITVS_HIP_CHECK(hipMemcpy(H, d_H, n * 9 * 8, hipMemcpyDeviceToHost));
+    if (h_info) VITVS_HIP_CHECK(hipMemcpy(h_info, d_info, n * 8 * 4, hipMemcpyDeviceToHost));
+    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
+    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // --- the pose rig law ----------------------------------------------------------------------------
 static int pose_rig_prepare(vitvs_handle* h, int n_cams, int n_iter) {
     if (n_cams < 1) return set_err(h, -2, "n_cams is at least 1");
@@ -2119,6 +2197,35 @@ int vitvs_op_pose_rig_plan(int32_t n_cams, int32_t ld, int32_t n_iter, int32_t* 
     PoseRigPlan pl;
     memset(&pl, 0, sizeof(pl));
     const int rc = plan_pose_rig(n_cams, ld, n_iter, &pl);
+    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
+    return rc;
+}
+
+int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable, double lambda,
+                            double depth_scale, int32_t n_iter, double sigma_min, void* scratch, double* v_h, int32_t* h_status,
+                            double* H, int32_t* h_info, double* weights, double* sigma, void* stream) {
+    if (!m || !ms || !usable || !scratch || !v_h || !h_status) return -1;
+    if (n_pairs < 1 || ld < 1 || n_iter < 0 || n_iter > 16 || !(depth_scale > 0.0) || !std::isfinite(depth_scale)) return -2;
+    HomographyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_pairs = n_pairs; a.ld = ld; a.m = m; a.ms = ms; a.usable = usable; a.lambda = lambda; a.depth_scale = depth_scale;
+    a.n_iter = n_iter; a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch);
+    a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info;
+    a.weights = weights; a.weights_stride = ld; a.sigma = sigma;
+    return launch_homography(a, as_stream(stream));
+}
+
+int vitvs_op_homography_scratch_bytes(int32_t n_pairs, int32_t ld) {
+    if (n_pairs < 1 || ld < 1) return -2;
+    const size_t b = homography_scratch_bytes(n_pairs, ld);
+    return b > 0x7fffffffu ? -3 : (int)b;
+}
+
+int vitvs_op_homography_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
+    if (!out) return -1;
+    HomographyPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_homography(max_rows, n_iter, &pl);
     out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
     return rc;
 }

@@ -526,6 +526,54 @@ int plan_pose_rig(int n_cams, int ld, int n_iter, PoseRigPlan* plan);
 size_t pose_rig_scratch_bytes(int n_cams, int ld);
 int launch_pose_rig(const PoseRigArgs& a, hipStream_t stream);
 
+// ---- homography.hip ------------------------------------------------------------------------
+// The homography law: per pair the 3 x 3 homography H of the matched normalised image points, m* ~ H m (Hartley
+// normalisation, the 9 x 9 DLT normal matrix, its smallest eigenvector by a cyclic Jacobi, det H = 1), and Benhimane and Malis'
+// twist v_h = -lambda (depth_scale (H - I) m_c, (H21 - H12, H02 - H20, H10 - H01)).  No depth takes part.  One launch, one
+// workgroup per pair.  The points come from what the camera's law left (selected, s_uv, feat, info) or, for the seam tests, from
+// the caller (m, ms, usable).
+struct HomographyArgs {
+    int n_pairs;
+    int ld;                   // rows per pair of every per-row array (max_rows)
+    const int32_t* status;    // [n_pairs] the cameras' statuses, or null: ST_NO_CORRESPONDENCE and ST_TOO_FEW are kept with v = 0,
+                              // ST_NO_DEPTH does not stop this law
+    // the handle's form (m == null): rows k < info[b][1] of pair b, usable when selected[k] >= 0
+    const int32_t* selected;  // [n_pairs][ld] goal token of every row, -1 padded
+    const int32_t* s_uv;      // [n_pairs][ld][4]
+    const double* feat;       // [n_pairs][ld][4]: Z (not read), x, y, sim
+    const int32_t* info;      // [n_pairs][8] of the camera's law: [1] rows written, [2] the same-image shortcut
+    const double* K;          // [n_pairs][4] fx, fy, cx, cy; also sigma_min = 0.5 max(pitch_u / fx, pitch_v / fy)
+    double pitch_u, pitch_v;
+    // given points (m != null): all ld rows
+    const double* m;          // [n_pairs][ld][2] current normalised points
+    const double* ms;         // [n_pairs][ld][2] goal normalised points
+    const int32_t* usable;    // [n_pairs][ld]: > 0 usable
+    double sigma_min;         // read when K is null
+    double lambda;
+    double depth_scale;       // metres, > 0: scales the translational half only
+    int n_iter;               // Tukey re-weightings, 0 .. 16
+    double* ws;               // [n_pairs][5][ld] the points and their flags (homography_scratch_bytes)
+    // outputs
+    double* v_h;              // [n_pairs][6]
+    int32_t* h_status;        // [n_pairs] ST_OK; the camera's ST_NO_CORRESPONDENCE / ST_TOO_FEW; ST_TOO_FEW: < 4 rows with a weight,
+                              // or degenerate
+    double* H;                // [n_pairs][9] or null: row-major, det 1 (identity when the twist is zero)
+    int32_t* h_info;          // [n_pairs][8] or null: usable rows, sweeps of the last solve, re-weightings, usable rows at weight 0,
+                              // degenerate, rows with rho = inf at the last re-weighting, 0, 0
+    double* weights;          // [n_pairs][weights_stride] or null
+    int weights_stride;
+    double* sigma;            // [n_pairs] or null: the last scale
+};
+struct HomographyPlan {
+    size_t lds;               // dynamic LDS of the launch: (752 + (robust ? 2 max_rows : 0)) doubles
+    bool robust;              // homography_kernel<robust>
+    bool lds_opt_in;          // > 64 KiB
+};
+// -2: max_rows < 1, n_iter outside 0 .. 16; -3 (plan filled): more than 160 KiB of LDS
+int plan_homography(int max_rows, int n_iter, HomographyPlan* plan);
+size_t homography_scratch_bytes(int n_pairs, int ld);
+int launch_homography(const HomographyArgs& a, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

@@ -7,6 +7,7 @@ behind the C ABI (include/vitvs.h); nothing here falls back to torch ops or to t
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -594,6 +595,65 @@ class Engine:
         self._check(rc, "vitvs_pose_velocity")
         info = dict(status=pst, R=pose[:, :9].reshape(n, 3, 3), t=pose[:, 9:], weights=weights, sigma=sigma)
         info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
+        return v, info
+
+    HOMOGRAPHY_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "behind")
+
+    @staticmethod
+    def _homography_arguments(depth_scale, robust_iterations):
+        """The checks of the homography law's arguments (no handle needed)."""
+        N = int(robust_iterations)
+        if not 0 <= N <= 16:
+            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        z = float(depth_scale)
+        if not (z > 0.0 and math.isfinite(z)):
+            raise ValueError(f"depth_scale is a positive, finite length in metres, got {depth_scale!r}")
+        return z, N
+
+    def homography_velocity(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
+        """``vitvs_homography_velocity_dev``: the homography law of every pair of the last velocity call, from the
+        matched image points that call left in the handle and nothing else: no depth image, no goal depth.  Per pair the 3 x 3
+        homography ``H`` of a planar target, m* ~ H m, and ``v_h = -lambda (depth_scale (H - I) m_c, (H21 - H12, H02 - H20, H10 -
+        H01))``.  ``K``: the intrinsics of that call, [n, 4] or one (fx, fy, cx, cy) for all; ``status``: the int32 [n] it returned
+        (a device tensor stays on the device; NO_DEPTH does not stop this law); ``depth_scale``: a rough guess of the distance to the
+        target in metres, which scales the translational gain only; ``robust_iterations``: Tukey re-weightings, 0 .. 16.  Returns
+        ``(v_h float64 [n, 6] device tensor, info)``, ``info`` = dict of device tensors: ``status`` int32 [n], ``H`` [n, 3, 3],
+        ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` / ``behind`` int32 [n], ``weights`` float64
+        [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing synchronises after the first call (which
+        allocates: make it outside a stream capture)."""
+        z, N = self._homography_arguments(depth_scale, robust_iterations)
+        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+        n = int(st.numel())
+        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
+        if kk.shape[0] == 1 and n > 1:
+            kk = kk.expand(n, 4)
+        if kk.shape[0] != n:
+            raise VitvsError("one (fx, fy, cx, cy) per pair expected")
+        kk = kk.contiguous().to(self.device)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
+        v, H, weights, sigma = f64(n, 6), f64(n, 9), f64(n, self.max_rows), f64(n)
+        hst, hinfo = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty((n, 8), dtype=torch.int32, device=self.device)
+        rc = self.lib.vitvs_homography_velocity_dev(self.handle, n, _ptr(kk), _ptr(st), z, N, _ptr(v), _ptr(hst), _ptr(H), _ptr(hinfo),
+                                                    _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
+        self._check(rc, "vitvs_homography_velocity_dev")
+        info = dict(status=hst, H=H.reshape(n, 3, 3), weights=weights, sigma=sigma)
+        info.update({name: hinfo[:, i] for i, name in enumerate(self.HOMOGRAPHY_INFO_FIELDS)})
+        return v, info
+
+    def homography_velocity_host(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
+        """``vitvs_homography_velocity``, the host-pointer form: numpy in, ``(v_h float64 [n, 6], info)`` out, ``info`` as
+        ``homography_velocity``'s with numpy arrays.  Synchronous."""
+        z, N = self._homography_arguments(depth_scale, robust_iterations)
+        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        n = int(st.size)
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
+        v, H, weights, sigma = np.zeros((n, 6)), np.zeros((n, 9)), np.zeros((n, self.max_rows)), np.zeros(n)
+        hst, hinfo = np.zeros(n, np.int32), np.zeros((n, 8), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_homography_velocity(self.handle, n, p(kk), p(st), z, N, p(v), p(hst), p(H), p(hinfo), p(weights), p(sigma))
+        self._check(rc, "vitvs_homography_velocity")
+        info = dict(status=hst, H=H.reshape(n, 3, 3), weights=weights, sigma=sigma)
+        info.update({name: hinfo[:, i] for i, name in enumerate(self.HOMOGRAPHY_INFO_FIELDS)})
         return v, info
 
     POSE_RIG_INFO_FIELDS = ("cameras", "usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes", "worst_status")

@@ -46,6 +46,8 @@ class UpdatePipeline:
                  stage_inputs: bool = False, streams: Optional[List[torch.cuda.Stream]] = None):
         if depth < 1:
             raise VitvsError("depth must be >= 1")
+        if getattr(params, "law", "ibvs") == "homography":
+            raise ValueError('UpdatePipeline slots run the image-based law: law="homography" is servo.Controller\'s (one handle, one camera)')
         if getattr(params, "law", "ibvs") != "ibvs":
             raise ValueError('UpdatePipeline slots run the image-based law: law="pose" is servo.Controller\'s (one handle, one camera)')
         self.depth = int(depth)

@@ -248,6 +248,8 @@ class Controller:
             self.set_goal_depth(goal_depth)
         self.last_pose_status = None                      # law "pose": the pose law's status of the last update, and its
         self.last_pose = None                             # (R [3, 3], t [3]): the current camera in the goal camera's frame
+        self.last_homography_status = None                # law "homography": the homography law's status of the last update, and
+        self.last_homography = None                       # its H [3, 3] (m* ~ H m, det 1); needs no goal_depth and no depth callback
         self.num_pairs = self.params.num_pairs
         self.dino_input_size = engine.cfg.img_size
         self.goal_image = goal_image                      # PIL image or uint8 array, any size
@@ -362,6 +364,8 @@ class Controller:
         self._raw_v, self.last_status = v, st
         if self.params.law == "pose":
             self._pose_step(st)
+        elif self.params.law == "homography":
+            self._homography_step(st)
         if st == _lib.STATUS_NO_CORRESPONDENCE:
             self.feature_failure_count += 1
             if self.feature_failure_count >= 10:
@@ -384,6 +388,21 @@ class Controller:
         if self.last_pose_status == _lib.STATUS_OK:
             self._raw_v = v[0]
 
+    def _homography_step(self, st):
+        """law "homography": the homography law behind this update's law evaluation (one more launch on the matched image points it
+        left in the handle; a camera status of NO_DEPTH does not stop it).  When its status is OK its twist replaces the raw ``v_c``
+        that the EMA, the remap and the history see; otherwise the update stays the image-based law's where that had a depth image
+        to read, and is the homography law's zero twist where it had none."""
+        p = self.params
+        if st == _lib.STATUS_NO_CORRESPONDENCE:           # (the reference draw may have ended before any law evaluation)
+            self.last_homography_status, self.last_homography = int(st), None
+            return
+        v, info = self.engine.homography_velocity_host(p.intrinsics(), [st], p.homography_depth, p.homography_robust_iterations)
+        self.last_homography_status = int(info["status"][0])
+        self.last_homography = info["H"][0].copy()
+        if self.last_homography_status == _lib.STATUS_OK or (self.latest_image_depth is None and p.interaction != "desired"):
+            self._raw_v = v[0]                            # (not OK and no depth image for the image-based law either: its zero twist)
+
     def _features(self, det, b: int = 0):
         """``detect_features``' return value from pair ``b`` of an engine's ``last_details``."""
         k = self.num_pairs
@@ -403,8 +422,9 @@ class Controller:
     def _law_step(self, have_features: bool):
         if not have_features:
             return
-        if self.latest_image_depth is None and self.params.interaction != "desired":
-            return                                        # reference: "Failed to get depth - skipping"; L(s*, Z*) reads none
+        if self.latest_image_depth is None and self.params.interaction != "desired" and self.params.law != "homography":
+            return                                        # reference: "Failed to get depth - skipping"; L(s*, Z*) reads none, and
+                                                          # neither does the homography law
         # fewer than 4 matches: the reference's calculate_uv hands back all-zero feature arrays of num_pairs rows
         # (vitvs_v2.py:539-541), len() >= 4 passes the check at :604, e = 0 and the raw twist is exactly 0 — which is
         # what the kernel reports with status TOO_FEW; the EMA is updated with it, as in the reference
@@ -505,6 +525,8 @@ class MultiController:
         self.engine = self.engines[0]
         self.law = (params or self.engine.params).law
         self._goal_depths, self._goal_depth_live = None, None
+        if self.law == "homography":
+            raise ValueError('law="homography" is servo.Controller\'s: the homography law has no rig form (one camera, one plane)')
         if self.law == "pose":
             # the cameras run the image-based law exactly as with law "ibvs"; the pose law of a MultiController is the RIG's
             if self.pipe is not None:
