@@ -167,8 +167,11 @@ VITVS_API int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t
  * points forward n_goal goal frames ONCE (uint8 [n_goal][S][S][3]; n_goal = the later calls' n_pairs, or 1 for des_shared
  * calls) and keep their descriptors in the handle; a later vitvs_compute_velocity[_dev] with I_des == NULL then forwards
  * only the current frames.  The cache is dropped by any call that forwards frames of its own choice through the handle
- * (a velocity call WITH I_des, vitvs_forward_tokens_dev, vitvs_extract_*): a NULL I_des without a matching cached goal is
- * error -5.  Results equal the recomputing call's up to the summation order of the GEMMs (the row count differs). */
+ * (a velocity call WITH I_des, vitvs_forward_tokens_dev, vitvs_extract_*) and by vitvs_correspond_dev / vitvs_refine_dev, whose
+ * descriptors overwrite the cached ones: a NULL I_des without a matching cached goal is error -5.  vitvs_reselect,
+ * vitvs_servo_from_nn[_ex]_dev, the follow-on laws and vitvs_set_option keep it (a goal forwarded under another "in_flight" hint
+ * keeps that plan's summation order).  Results equal the recomputing call's up to the summation order of the GEMMs (the row
+ * count differs). */
 VITVS_API int vitvs_set_goal_dev(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des, void* stream);
 VITVS_API int vitvs_set_goal(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des);
 
