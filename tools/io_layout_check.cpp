@@ -1,0 +1,86 @@
+// Checks csrc/io_layout.h's lists on the CPU (no GPU, no HIP): for every follow-on law at a few (max_pairs, max_rows, n), placed
+// in a host buffer of exactly the computed size, the fields do not overlap, each is aligned to its element size, the last one
+// ends at the computed total, no call copies more than a field reserves, and writing every field end to end stays inside the
+// buffer (which is what the sanitizers watch).
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o io_layout_check io_layout_check.cpp && ./io_layout_check
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../vit-vs_amd/csrc/io_layout.h"
+
+using namespace vitvs;
+
+static int failures = 0;
+#define EXPECT(cond, ...)                          \
+    do {                                           \
+        if (!(cond)) {                             \
+            ++failures;                            \
+            printf("FAILED %s: ", #cond);          \
+            printf(__VA_ARGS__);                   \
+            printf("\n");                          \
+        }                                          \
+    } while (0)
+
+static void check(const char* law, IoList l, size_t P, size_t R, size_t n) {
+    const size_t total = io_place(l, nullptr);
+    for (size_t i = 0; i < l.n; ++i) EXPECT(l.f[i].dev == nullptr, "%s field %zu: a pointer without a block", law, i);
+    std::vector<unsigned char> block(total);      // exactly the allocation: a byte past it is the sanitizer's
+    EXPECT(io_place(l, block.data()) == total, "%s: the size depends on the base", law);
+    size_t end = 0, seen8 = 0, seen4 = 0;
+    for (size_t i = 0; i < l.n; ++i) {
+        const IoField& f = l.f[i];
+        const size_t off = (size_t)(f.dev - block.data());
+        EXPECT(f.elem == 8 || f.elem == 4, "%s field %zu: element size %zu", law, i, f.elem);
+        EXPECT(f.elem == 8 ? seen4 == 0 : true, "%s field %zu: an 8-byte field behind a 4-byte one", law, i);
+        (f.elem == 8 ? seen8 : seen4) += 1;
+        EXPECT(off == end, "%s field %zu begins at %zu, the one before it ends at %zu (P %zu R %zu)", law, i, off, end, P, R);
+        EXPECT(off % f.elem == 0, "%s field %zu at offset %zu is not aligned to %zu (P %zu R %zu)", law, i, off, f.elem, P, R);
+        EXPECT(f.cap > 0 && f.count <= f.cap, "%s field %zu: count %zu, capacity %zu (P %zu R %zu n %zu)", law, i, f.count, f.cap, P, R, n);
+        memset(f.dev, (int)(i + 1), f.cap * f.elem);
+        end = off + f.cap * f.elem;
+    }
+    EXPECT(end == total, "%s: the last field ends at %zu, the block at %zu (P %zu R %zu)", law, end, total, P, R);
+    for (size_t i = 0; i < l.n; ++i)              // nobody wrote over a neighbour
+        for (size_t b = 0; b < l.f[i].cap * l.f[i].elem; ++b)
+            if (l.f[i].dev[b] != (unsigned char)(i + 1)) { EXPECT(false, "%s field %zu byte %zu was overwritten", law, i, b); break; }
+    EXPECT(seen8 > 0 && seen4 > 0, "%s: %zu 8-byte and %zu 4-byte fields", law, seen8, seen4);
+}
+
+int main() {
+    const size_t shapes[][3] = {{1, 1, 1}, {3, 8, 2}, {3, 8, 3}, {8, 24, 5}, {256, 48, 3}, {256, 3136, 256}};
+    double d = 0;                                  // any non-null caller pointer: the layout does not read it
+    int32_t i = 0;
+    for (const auto& s : shapes) {
+        const size_t P = s[0], R = s[1], n = s[2];
+        RigIo rig = rig_io(P, R, n, &d, &i, nullptr, &d, &i, &i, &d);
+        check("rig", io_list(rig), P, R, n);
+        RigIo robust = rig_io(P, R, n, &d, &i, &d, &d, &i, &i, &d, &d, &d);
+        check("rig robust", io_list(robust), P, R, n);
+        EXPECT(io_place(io_list(rig), nullptr) == io_place(io_list(robust), nullptr), "the rig law's two forms share one block");
+        PoseIo pose = pose_io(P, R, n, &d, &i, &d, &i, &d, &i, &d, &d);
+        check("pose", io_list(pose), P, R, n);
+        HomographyIo hom = homography_io(P, R, n, &d, &i, &d, &i, &d, &i, &d, &d);
+        check("homography", io_list(hom), P, R, n);
+        PoseRigIo pose_rig = pose_rig_io(P, R, n, &d, &d, &i, &d, &i, &d, &i, &d, &d, &d);
+        check("pose rig", io_list(pose_rig), P, R, n);
+        // the sizes *_prepare allocates (the lists of P and R alone) are the sizes the calls place their fields in
+        RigIo rig0 = rig_io(P, R);
+        PoseIo pose0 = pose_io(P, R);
+        HomographyIo hom0 = homography_io(P, R);
+        PoseRigIo pose_rig0 = pose_rig_io(P, R);
+        EXPECT(io_place(io_list(rig0), nullptr) == io_place(io_list(rig), nullptr), "rig: allocation and call disagree");
+        EXPECT(io_place(io_list(pose0), nullptr) == io_place(io_list(pose), nullptr), "pose: allocation and call disagree");
+        EXPECT(io_place(io_list(hom0), nullptr) == io_place(io_list(hom), nullptr), "homography: allocation and call disagree");
+        EXPECT(io_place(io_list(pose_rig0), nullptr) == io_place(io_list(pose_rig), nullptr), "pose rig: allocation and call disagree");
+        // and the sizes in closed form, from the fields' shapes in include/vitvs.h
+        EXPECT(io_place(io_list(pose0), nullptr) == (P * (4 + 6 + 12 + 1 + R)) * 8 + P * 10 * 4, "pose: %zu %zu", P, R);
+        EXPECT(io_place(io_list(hom0), nullptr) == (P * (4 + 6 + 9 + 1 + R)) * 8 + P * 10 * 4, "homography: %zu %zu", P, R);
+        EXPECT(io_place(io_list(pose_rig0), nullptr) == (P * (12 + 4 + R) + 6 + 12 + 18 + 1) * 8 + (P + 9) * 4, "pose rig: %zu %zu", P, R);
+        EXPECT(io_place(io_list(rig0), nullptr) == (P * 36 + 34 + P * 4 + 1 + P * R) * 8 + (P + 9) * 4, "rig: %zu %zu", P, R);
+    }
+    if (failures) printf("io_layout_check: %d FAILED\n", failures);
+    else printf("io_layout_check: ok\n");
+    return failures ? 1 : 0;
+}

@@ -14,6 +14,7 @@
 
 #include "../../include/vitvs.h"
 #include "../../include/vitvs_ops.h"
+#include "io_layout.h"
 #include "kernels.h"
 
 namespace vitvs {
@@ -126,27 +127,15 @@ struct vitvs_handle {
     uint16_t* zgoal = nullptr;  // [max_pairs][T + 1] mm, goal depth at every token's patch centre and at pixel (0, 0) (vitvs_set_goal_depth_dev)
     int n_goal_depth = 0;     // goal depth images held in zgoal, 0: none
     double* zgoal_ws = nullptr; // [max_pairs][max_rows] Z* of the last law evaluation's feature rows (vitvs_last_goal_depth)
-    // the rig law (vitvs_rig_velocity_dev): its scratch block (ticket, the cameras' sums, the stacked rows and their working copy)
-    // at max_pairs cameras, and the device side of the host-pointer form, allocated by the first rig call
-    unsigned char* rig_ws = nullptr;
-    unsigned char* rig_io = nullptr;   // cVr [max_pairs][36] f64 | v_rig [6] | normal [28] | status [max_pairs] i32 | rig_status | rig_info [8]
-                                       // | (rig_io_head) K [max_pairs][4] f64 | sigma | weights [max_pairs][max_rows]
+    // The follow-on laws (vitvs_{rig,rig_robust,pose,homography,pose_rig}_velocity[_dev]), each with two blocks that its first
+    // call allocates (law_blocks): *_ws, the kernels' own scratch at max_pairs x max_rows (rig.hip's begins with a ticket that
+    // every launch must find zero: the laws share nothing), and *_io, the device side of the host-pointer form, laid out by
+    // io_layout.h's list of that law.
+    unsigned char *rig_ws = nullptr, *rig_io = nullptr;             // RigIo: both forms of the rig law
+    unsigned char *pose_ws = nullptr, *pose_io = nullptr;           // PoseIo
+    unsigned char *hom_ws = nullptr, *hom_io = nullptr;             // HomographyIo
+    unsigned char *pose_rig_ws = nullptr, *pose_rig_io = nullptr;   // PoseRigIo
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
-    // the pose law (vitvs_pose_velocity_dev): its points [max_pairs][7][max_rows] f64, and the device side of the host-pointer
-    // form, allocated by the first pose call
-    double* pose_ws = nullptr;
-    unsigned char* pose_io = nullptr;  // K [P][4] | v_pose [P][6] | pose [P][12] | sigma [P] | weights [P][max_rows] f64 | status [P] |
-                                       // pose_status [P] | pose_info [P][8] i32
-    // the homography law (vitvs_homography_velocity_dev): its points [max_pairs][5][max_rows] f64, and the device side of the
-    // host-pointer form, allocated by the first homography call
-    double* hom_ws = nullptr;
-    unsigned char* hom_io = nullptr;   // K [P][4] | v_h [P][6] | H [P][9] | sigma [P] | weights [P][max_rows] f64 | status [P] |
-                                       // h_status [P] | h_info [P][8] i32
-    // the pose rig law (vitvs_pose_rig_velocity_dev): its stack [7][max_pairs * max_rows] f64, and the device side of the
-    // host-pointer form, allocated by the first pose rig call
-    double* pose_rig_ws = nullptr;
-    unsigned char* pose_rig_io = nullptr;  // rTc [P][12] | K [P][4] | v_rig [6] | pose [12] | moments [18] | sigma [1] |
-                                           // weights [P][max_rows] f64 | status [P] | rig_status [1] | rig_info [8] i32
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
@@ -258,6 +247,69 @@ void dev_free(vitvs_handle* h, void* p) {
     if (!p) return;
     h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), p), h->allocs.end());
     (void)hipFree(p);
+}
+
+// ---- what the follow-on laws' entry points share (the rig law .. the pose rig law below) ----
+// A law's two blocks, allocated by its first call: set-up, not the call path (and never inside a capture), as
+// vitvs_set_goal_depth_dev's.
+int law_blocks(vitvs_handle* h, const char* law, unsigned char** ws, size_t ws_bytes, unsigned char** io, size_t io_bytes) {
+    if (*ws) return 0;
+    int rc = dev_alloc(h, ws, ws_bytes);
+    if (!rc) rc = dev_alloc(h, io, io_bytes);
+    if (rc) return set_err(h, rc, std::string(law) + " workspace allocation failed");
+    VITVS_HIP_CHECK(hipDeviceSynchronize());   // the blocks (the rig law's ticket above all) are zero before any stream uses them
+    return 0;
+}
+
+// A law evaluates what the last velocity call left: there was one, and `n` (the entry point's `count`) is its pair count.
+int follows_velocity_call(vitvs_handle* h, const char* entry, const char* count, int n) {
+    if (!h->last_pairs) return set_err(h, -5, std::string(entry) + " follows a velocity call on the same handle");
+    if (n != h->last_pairs)
+        return set_err(h, -5, std::string(count) + " (" + std::to_string(n) + ") is not the pair count of the last law evaluation (" +
+                                  std::to_string(h->last_pairs) + ")");
+    return 0;
+}
+
+// the token grid's pitch along an image side of `extent` sensor pixels, in those pixels
+double token_pitch(const vitvs_config& c, int extent) { return (double)(c.stride * extent) / (double)c.img_size; }
+
+// What the camera's law left in the handle, as PoseArgs, PoseRigArgs and HomographyArgs read it ...
+template <typename Args>
+void camera_law_state(const vitvs_handle* h, const double* K, int n_iter, Args& a) {
+    const vitvs_config& c = h->cfg;
+    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
+    a.pitch_u = token_pitch(c, c.u_max); a.pitch_v = token_pitch(c, c.v_max);
+    a.lambda = c.lambda; a.n_iter = n_iter; a.weights_stride = c.max_rows;
+}
+// ... and the goal depth, for the two laws that read it
+template <typename Args>
+void goal_depth_state(const vitvs_handle* h, Args& a) {
+    a.zgoal = h->zgoal; a.zgoal_stride = h->n_goal_depth == 1 ? 0 : h->T + 1; a.T = h->T;
+}
+
+// The host-pointer form of a follow-on law over its list `io`, placed in the handle's `block` of that law: the inputs up at the
+// call's counts, the law's _dev form on the handle's host stream, the outputs the caller asked for down.  A failing _dev form
+// returns before anything is copied back.
+template <typename DevForm>
+int host_call(vitvs_handle* h, IoList io, unsigned char* block, DevForm dev_form) {
+    io_place(io, block);
+    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
+    for (const IoField* f = io.f; f != io.f + io.n; ++f)
+        if (f->input && f->host) VITVS_HIP_CHECK(hipMemcpy(f->dev, f->host, f->count * f->elem, hipMemcpyHostToDevice));
+    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
+    if (int rc = dev_form(st)) return rc;
+    VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    for (const IoField* f = io.f; f != io.f + io.n; ++f)
+        if (!f->input && f->host) VITVS_HIP_CHECK(hipMemcpy(f->host, f->dev, f->count * f->elem, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the laws' operator hooks: a scratch size as the int32 they return, and the pose, pose rig and homography plans' common output
+int bytes_i32(size_t b) { return b > 0x7fffffffu ? -3 : (int)b; }
+template <typename Plan>
+int plan_out(int rc, const Plan& pl, int32_t* out) {
+    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
+    return rc;
 }
 
 int upload_f32(vitvs_handle* h, float** dst, const float* src, size_t n) {
@@ -1607,27 +1659,17 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
 }
 
 // --- the rig law ---------------------------------------------------------------------------------
-// bytes of rig_io's first part (see vitvs_handle::rig_io); the robust form's K, sigma and weights follow it
-static size_t rig_io_head(size_t P) { return (P * 36 * 8 + 34 * 8 + (P + 9) * 4 + 63) & ~(size_t)63; }
-
 static int rig_prepare(vitvs_handle* h, int n_cams, bool robust_form = false) {
-    if (!h->last_pairs) return set_err(h, -5, "vitvs_rig_velocity follows a velocity call on the same handle");
-    if (n_cams != h->last_pairs)
-        return set_err(h, -5, "n_cams (" + std::to_string(n_cams) + ") is not the pair count of the last law evaluation (" +
-                                  std::to_string(h->last_pairs) + ")");
+    if (int rc = follows_velocity_call(h, "vitvs_rig_velocity", "n_cams", n_cams)) return rc;
     if (!robust_form && (h->last_law.robust || h->robust_iters))
         return set_err(h, -5, "the rig law does not combine with option robust_law (one median over all cameras' residuals: "
                               "vitvs_rig_robust_velocity)");
     if (n_cams > kRigMaxCams) return set_err(h, -5, "the rig law takes at most " + std::to_string(kRigMaxCams) + " cameras");
-    if (!h->rig_ws) {                           // set-up, not the call path (and never inside a capture): as vitvs_set_goal_depth_dev
-        const size_t P = h->cfg.max_pairs;
-        // (sized for the robust form, a third block of stacked rows, whichever form comes first: allocated once)
-        int rc = dev_alloc(h, &h->rig_ws, rig_robust_scratch_bytes((int)P, 2 * h->cfg.max_rows));
-        if (!rc) rc = dev_alloc(h, &h->rig_io, rig_io_head(P) + (P * 4 + 1 + P * (size_t)h->cfg.max_rows) * 8);
-        if (rc) return set_err(h, rc, "rig workspace allocation failed");
-        VITVS_HIP_CHECK(hipDeviceSynchronize());   // the blocks (the ticket above all) are zero before any stream uses them
-    }
-    return 0;
+    const vitvs_config& c = h->cfg;
+    RigIo io = rig_io(c.max_pairs, c.max_rows);
+    // (sized for the robust form, a third block of stacked rows, whichever form comes first: allocated once)
+    return law_blocks(h, "rig", &h->rig_ws, rig_robust_scratch_bytes(c.max_pairs, 2 * c.max_rows), &h->rig_io,
+                      io_place(io_list(io), nullptr));
 }
 
 int vitvs_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, const int32_t* status, double* v_rig,
@@ -1650,24 +1692,11 @@ int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr, const
     if (!h || !cVr || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = rig_prepare(h, n_cams)) return rc;
-    const size_t P = h->cfg.max_pairs;
-    double* d_W = reinterpret_cast<double*>(h->rig_io);
-    double* d_v = d_W + P * 36;
-    double* d_normal = d_v + 6;
-    int32_t* d_status = reinterpret_cast<int32_t*>(d_normal + 28);
-    int32_t* d_rig_status = d_status + P;
-    int32_t* d_info = d_rig_status + 1;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
-    VITVS_HIP_CHECK(hipMemcpy(d_W, cVr, (size_t)n_cams * 36 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_status, status, (size_t)n_cams * 4, hipMemcpyHostToDevice));
-    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
-    if (int rc = vitvs_rig_velocity_dev(h, n_cams, d_W, d_status, d_v, d_rig_status, d_info, d_normal, st)) return rc;
-    VITVS_HIP_CHECK(hipStreamSynchronize(st));
-    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
-    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
-    if (normal) VITVS_HIP_CHECK(hipMemcpy(normal, d_normal, 28 * 8, hipMemcpyDeviceToHost));
-    return 0;
+    RigIo io = rig_io(h->cfg.max_pairs, h->cfg.max_rows, n_cams, cVr, status, nullptr, v_rig, rig_status, rig_info, normal);
+    return host_call(h, io_list(io), h->rig_io, [&](hipStream_t st) {
+        return vitvs_rig_velocity_dev(h, n_cams, io.cVr.f64(), io.status.i32(), io.v_rig.f64(), io.rig_status.i32(),
+                                      io.rig_info.i32(), io.normal.f64(), st);
+    });
 }
 
 // --- the robust rig law ----------------------------------------------------------------------------
@@ -1687,8 +1716,7 @@ int vitvs_rig_robust_velocity_dev(vitvs_handle* h, int32_t n_cams, const double*
     rig_robust_carve(h->rig_ws, c.max_pairs, a.ld, ra);
     a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
     ra.live = h->info + 3; ra.live_stride = 8; ra.K = K; ra.n_iter = n_iter;
-    ra.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
-    ra.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
+    ra.pitch_u = token_pitch(c, c.u_max); ra.pitch_v = token_pitch(c, c.v_max);
     ra.weights = weights; ra.weights_stride = c.max_rows; ra.sigma = sigma;
     const int rc = launch_rig_robust(ra, as_stream(stream));
     if (rc == -3) return set_err(h, rc, "the robust rig law keeps two doubles per feature pair of the rig in LDS: n_cams * max_rows is too large");
@@ -1702,58 +1730,30 @@ int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr
     if (n_iter < 1 || n_iter > 16) return set_err(h, -2, "n_iter is 1 .. 16");
     DeviceScope dev(h);
     if (int rc = rig_prepare(h, n_cams, true)) return rc;
-    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
-    double* d_W = reinterpret_cast<double*>(h->rig_io);
-    double* d_v = d_W + P * 36;
-    double* d_normal = d_v + 6;
-    int32_t* d_status = reinterpret_cast<int32_t*>(d_normal + 28);
-    int32_t* d_rig_status = d_status + P;
-    int32_t* d_info = d_rig_status + 1;
-    double* d_K = reinterpret_cast<double*>(h->rig_io + rig_io_head(P));
-    double* d_sigma = d_K + P * 4;
-    double* d_weights = d_sigma + 1;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
-    VITVS_HIP_CHECK(hipMemcpy(d_W, cVr, (size_t)n_cams * 36 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_status, status, (size_t)n_cams * 4, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_K, K, (size_t)n_cams * 4 * 8, hipMemcpyHostToDevice));
-    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
-    if (int rc = vitvs_rig_robust_velocity_dev(h, n_cams, d_W, d_status, d_K, n_iter, d_v, d_rig_status, d_info, d_normal, d_weights,
-                                               d_sigma, st))
-        return rc;
-    VITVS_HIP_CHECK(hipStreamSynchronize(st));
-    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
-    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
-    if (normal) VITVS_HIP_CHECK(hipMemcpy(normal, d_normal, 28 * 8, hipMemcpyDeviceToHost));
-    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, (size_t)n_cams * R * 8, hipMemcpyDeviceToHost));
-    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, 8, hipMemcpyDeviceToHost));
-    return 0;
+    RigIo io = rig_io(h->cfg.max_pairs, h->cfg.max_rows, n_cams, cVr, status, K, v_rig, rig_status, rig_info, normal, weights, sigma);
+    return host_call(h, io_list(io), h->rig_io, [&](hipStream_t st) {
+        return vitvs_rig_robust_velocity_dev(h, n_cams, io.cVr.f64(), io.status.i32(), io.K.f64(), n_iter, io.v_rig.f64(),
+                                             io.rig_status.i32(), io.rig_info.i32(), io.normal.f64(), io.weights.f64(),
+                                             io.sigma.f64(), st);
+    });
 }
 
 // --- the pose law --------------------------------------------------------------------------------
 static int pose_prepare(vitvs_handle* h, int n_pairs, int n_iter) {
     if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
-    if (!h->last_pairs) return set_err(h, -5, "vitvs_pose_velocity follows a velocity call on the same handle");
-    if (n_pairs != h->last_pairs)
-        return set_err(h, -5, "n_pairs (" + std::to_string(n_pairs) + ") is not the pair count of the last law evaluation (" +
-                                  std::to_string(h->last_pairs) + ")");
+    if (int rc = follows_velocity_call(h, "vitvs_pose_velocity", "n_pairs", n_pairs)) return rc;
     if (!h->n_goal_depth) return set_err(h, -5, "the pose law needs a goal depth (vitvs_set_goal_depth_dev)");
     if (h->last_T != h->T) return set_err(h, -5, "the goal depth table is laid out for the handle's own token grid");
     if (h->n_goal_depth != n_pairs && h->n_goal_depth != 1)
         return set_err(h, -5, "the goal depth holds " + std::to_string(h->n_goal_depth) + " images: one per pair, or one for all");
     if (h->last_law.interaction == IL_DESIRED)
         return set_err(h, -5, "the pose law needs the current depth: with option interaction at 1 the feature rows hold Z*, not Z");
+    const vitvs_config& c = h->cfg;
     PosePlan pl;
-    if (plan_pose(h->cfg.max_rows, n_iter, &pl))
+    if (plan_pose(c.max_rows, n_iter, &pl))
         return set_err(h, -3, "the robust pose law keeps two doubles per feature row in LDS: max_rows is too large");
-    if (!h->pose_ws) {                          // set-up, not the call path (and never inside a capture): as the rig law's
-        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
-        int rc = dev_alloc(h, &h->pose_ws, P * 7 * R);
-        if (!rc) rc = dev_alloc(h, &h->pose_io, (P * (4 + 6 + 12 + 1 + R)) * 8 + P * 10 * 4);
-        if (rc) return set_err(h, rc, "pose workspace allocation failed");
-        VITVS_HIP_CHECK(hipDeviceSynchronize());
-    }
-    return 0;
+    PoseIo io = pose_io(c.max_pairs, c.max_rows);
+    return law_blocks(h, "pose", &h->pose_ws, pose_scratch_bytes(c.max_pairs, c.max_rows), &h->pose_io, io_place(io_list(io), nullptr));
 }
 
 int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
@@ -1761,17 +1761,12 @@ int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, c
     if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
-    const vitvs_config& c = h->cfg;
     PoseArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_pairs = n_pairs; a.ld = c.max_rows; a.status = status;
-    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
-    a.zgoal = h->zgoal; a.zgoal_stride = h->n_goal_depth == 1 ? 0 : h->T + 1; a.T = h->T;
-    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
-    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
-    a.lambda = c.lambda; a.n_iter = n_iter; a.ws = h->pose_ws;
-    a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info;
-    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    a.n_pairs = n_pairs; a.ld = h->cfg.max_rows; a.status = status; a.ws = reinterpret_cast<double*>(h->pose_ws);
+    camera_law_state(h, K, n_iter, a);
+    goal_depth_state(h, a);
+    a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info; a.weights = weights; a.sigma = sigma;
     const int rc = launch_pose(a, as_stream(stream));
     return rc ? set_err(h, rc, "pose law launch failed") : 0;
 }
@@ -1781,50 +1776,25 @@ int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const
     if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
-    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_pairs;
-    double* d_K = reinterpret_cast<double*>(h->pose_io);
-    double* d_v = d_K + P * 4;
-    double* d_pose = d_v + P * 6;
-    double* d_sigma = d_pose + P * 12;
-    double* d_weights = d_sigma + P;
-    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
-    int32_t* d_pose_status = d_status + P;
-    int32_t* d_info = d_pose_status + P;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
-    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
-    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
-    if (int rc = vitvs_pose_velocity_dev(h, n_pairs, d_K, d_status, n_iter, d_v, d_pose_status, d_pose, d_info, d_weights, d_sigma, st))
-        return rc;
-    VITVS_HIP_CHECK(hipStreamSynchronize(st));
-    VITVS_HIP_CHECK(hipMemcpy(v_pose, d_v, n * 6 * 8, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(pose_status, d_pose_status, n * 4, hipMemcpyDeviceToHost));
-    if (pose) VITVS_HIP_CHECK(hipMemcpy(pose, d_pose, n * 12 * 8, hipMemcpyDeviceToHost));
-    if (pose_info) VITVS_HIP_CHECK(hipMemcpy(pose_info, d_info, n * 8 * 4, hipMemcpyDeviceToHost));
-    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
-    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, n * 8, hipMemcpyDeviceToHost));
-    return 0;
+    PoseIo io = pose_io(h->cfg.max_pairs, h->cfg.max_rows, n_pairs, K, status, v_pose, pose_status, pose, pose_info, weights, sigma);
+    return host_call(h, io_list(io), h->pose_io, [&](hipStream_t st) {
+        return vitvs_pose_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), n_iter, io.v_pose.f64(), io.pose_status.i32(),
+                                       io.pose.f64(), io.pose_info.i32(), io.weights.f64(), io.sigma.f64(), st);
+    });
 }
 
 // --- the homography law --------------------------------------------------------------------------
 static int homography_prepare(vitvs_handle* h, int n_pairs, double depth_scale, int n_iter) {
     if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
     if (!(depth_scale > 0.0) || !std::isfinite(depth_scale)) return set_err(h, -2, "depth_scale is a positive, finite length in metres");
-    if (!h->last_pairs) return set_err(h, -5, "vitvs_homography_velocity follows a velocity call on the same handle");
-    if (n_pairs != h->last_pairs)
-        return set_err(h, -5, "n_pairs (" + std::to_string(n_pairs) + ") is not the pair count of the last law evaluation (" +
-                                  std::to_string(h->last_pairs) + ")");
+    if (int rc = follows_velocity_call(h, "vitvs_homography_velocity", "n_pairs", n_pairs)) return rc;
+    const vitvs_config& c = h->cfg;
     HomographyPlan pl;
-    if (plan_homography(h->cfg.max_rows, n_iter, &pl))
+    if (plan_homography(c.max_rows, n_iter, &pl))
         return set_err(h, -3, "the robust homography law keeps two doubles per feature row in LDS: max_rows is too large");
-    if (!h->hom_ws) {                           // set-up, not the call path (and never inside a capture): as the pose law's
-        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
-        int rc = dev_alloc(h, &h->hom_ws, P * 5 * R);
-        if (!rc) rc = dev_alloc(h, &h->hom_io, (P * (4 + 6 + 9 + 1 + R)) * 8 + P * 10 * 4);
-        if (rc) return set_err(h, rc, "homography workspace allocation failed");
-        VITVS_HIP_CHECK(hipDeviceSynchronize());
-    }
-    return 0;
+    HomographyIo io = homography_io(c.max_pairs, c.max_rows);
+    return law_blocks(h, "homography", &h->hom_ws, homography_scratch_bytes(c.max_pairs, c.max_rows), &h->hom_io,
+                      io_place(io_list(io), nullptr));
 }
 
 int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
@@ -1833,16 +1803,12 @@ int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double
     if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
-    const vitvs_config& c = h->cfg;
     HomographyArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_pairs = n_pairs; a.ld = c.max_rows; a.status = status;
-    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
-    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
-    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
-    a.lambda = c.lambda; a.depth_scale = depth_scale; a.n_iter = n_iter; a.ws = h->hom_ws;
-    a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info;
-    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    a.n_pairs = n_pairs; a.ld = h->cfg.max_rows; a.status = status; a.ws = reinterpret_cast<double*>(h->hom_ws);
+    camera_law_state(h, K, n_iter, a);
+    a.depth_scale = depth_scale;
+    a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info; a.weights = weights; a.sigma = sigma;
     const int rc = launch_homography(a, as_stream(stream));
     return rc ? set_err(h, rc, "homography law launch failed") : 0;
 }
@@ -1853,47 +1819,24 @@ int vitvs_homography_velocity(vitvs_handle* h, int32_t n_pairs, const double* K,
     if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
-    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_pairs;
-    double* d_K = reinterpret_cast<double*>(h->hom_io);
-    double* d_v = d_K + P * 4;
-    double* d_H = d_v + P * 6;
-    double* d_sigma = d_H + P * 9;
-    double* d_weights = d_sigma + P;
-    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
-    int32_t* d_h_status = d_status + P;
-    int32_t* d_info = d_h_status + P;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
-    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
-    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
-    if (int rc = vitvs_homography_velocity_dev(h, n_pairs, d_K, d_status, depth_scale, n_iter, d_v, d_h_status, d_H, d_info, d_weights,
-                                               d_sigma, st))
-        return rc;
-    VITVS_HIP_CHECK(hipStreamSynchronize(st));
-    VITVS_HIP_CHECK(hipMemcpy(v_h, d_v, n * 6 * 8, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(h_status, d_h_status, n * 4, hipMemcpyDeviceToHost));
-    if (H) VITVS_HIP_CHECK(hipMemcpy(H, d_H, n * 9 * 8, hipMemcpyDeviceToHost));
-    if (h_info) VITVS_HIP_CHECK(hipMemcpy(h_info, d_info, n * 8 * 4, hipMemcpyDeviceToHost));
-    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
-    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, n * 8, hipMemcpyDeviceToHost));
-    return 0;
+    HomographyIo io = homography_io(h->cfg.max_pairs, h->cfg.max_rows, n_pairs, K, status, v_h, h_status, H, h_info, weights, sigma);
+    return host_call(h, io_list(io), h->hom_io, [&](hipStream_t st) {
+        return vitvs_homography_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), depth_scale, n_iter, io.v_h.f64(),
+                                             io.h_status.i32(), io.H.f64(), io.h_info.i32(), io.weights.f64(), io.sigma.f64(), st);
+    });
 }
 
 // --- the pose rig law ----------------------------------------------------------------------------
 static int pose_rig_prepare(vitvs_handle* h, int n_cams, int n_iter) {
     if (n_cams < 1) return set_err(h, -2, "n_cams is at least 1");
     if (int rc = pose_prepare(h, n_cams, n_iter)) return rc;     // valid exactly where the pose law is, n_cams == last_pairs
+    const vitvs_config& c = h->cfg;
     PoseRigPlan pl;
-    if (plan_pose_rig(n_cams, h->cfg.max_rows, n_iter, &pl))
+    if (plan_pose_rig(n_cams, c.max_rows, n_iter, &pl))
         return set_err(h, -3, "the robust pose rig law keeps two doubles per feature row of the rig in LDS: n_cams * max_rows is too large");
-    if (!h->pose_rig_ws) {                      // set-up, not the call path (and never inside a capture): as the pose law's
-        const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows;
-        int rc = dev_alloc(h, &h->pose_rig_ws, P * 7 * R);
-        if (!rc) rc = dev_alloc(h, &h->pose_rig_io, (P * (12 + 4 + R) + 6 + 12 + 18 + 1) * 8 + (P + 9) * 4);
-        if (rc) return set_err(h, rc, "pose rig workspace allocation failed");
-        VITVS_HIP_CHECK(hipDeviceSynchronize());
-    }
-    return 0;
+    PoseRigIo io = pose_rig_io(c.max_pairs, c.max_rows);
+    return law_blocks(h, "pose rig", &h->pose_rig_ws, pose_rig_scratch_bytes(c.max_pairs, c.max_rows), &h->pose_rig_io,
+                      io_place(io_list(io), nullptr));
 }
 
 int vitvs_pose_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* rTc, const double* K, const int32_t* status,
@@ -1902,17 +1845,13 @@ int vitvs_pose_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* r
     if (!h || !rTc || !K || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = pose_rig_prepare(h, n_cams, n_iter)) return rc;
-    const vitvs_config& c = h->cfg;
     PoseRigArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_cams = n_cams; a.ld = c.max_rows; a.status = status; a.rTc = rTc;
-    a.selected = h->sel_out; a.s_uv = h->s_uv; a.feat = h->feat; a.info = h->info; a.K = K;
-    a.zgoal = h->zgoal; a.zgoal_stride = h->n_goal_depth == 1 ? 0 : h->T + 1; a.T = h->T;
-    a.pitch_u = (double)(c.stride * c.u_max) / (double)c.img_size;
-    a.pitch_v = (double)(c.stride * c.v_max) / (double)c.img_size;
-    a.lambda = c.lambda; a.n_iter = n_iter; a.ws = h->pose_rig_ws;
+    a.n_cams = n_cams; a.ld = h->cfg.max_rows; a.status = status; a.rTc = rTc; a.ws = reinterpret_cast<double*>(h->pose_rig_ws);
+    camera_law_state(h, K, n_iter, a);
+    goal_depth_state(h, a);
     a.v_rig = v_rig; a.rig_status = rig_status; a.pose = pose; a.rig_info = rig_info; a.moments = moments;
-    a.weights = weights; a.weights_stride = c.max_rows; a.sigma = sigma;
+    a.weights = weights; a.sigma = sigma;
     const int rc = launch_pose_rig(a, as_stream(stream));
     return rc ? set_err(h, rc, "pose rig law launch failed") : 0;
 }
@@ -1923,34 +1862,13 @@ int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* rTc, 
     if (!h || !rTc || !K || !status || !v_rig || !rig_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     if (int rc = pose_rig_prepare(h, n_cams, n_iter)) return rc;
-    const size_t P = h->cfg.max_pairs, R = h->cfg.max_rows, n = n_cams;
-    double* d_rTc = reinterpret_cast<double*>(h->pose_rig_io);
-    double* d_K = d_rTc + P * 12;
-    double* d_v = d_K + P * 4;
-    double* d_pose = d_v + 6;
-    double* d_moments = d_pose + 12;
-    double* d_sigma = d_moments + 18;
-    double* d_weights = d_sigma + 1;
-    int32_t* d_status = reinterpret_cast<int32_t*>(d_weights + P * R);
-    int32_t* d_rig_status = d_status + P;
-    int32_t* d_info = d_rig_status + 1;
-    VITVS_HIP_CHECK(hipDeviceSynchronize());    // the law evaluation this builds on may still run on a stream of the caller's
-    VITVS_HIP_CHECK(hipMemcpy(d_rTc, rTc, n * 12 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_K, K, n * 4 * 8, hipMemcpyHostToDevice));
-    VITVS_HIP_CHECK(hipMemcpy(d_status, status, n * 4, hipMemcpyHostToDevice));
-    hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
-    if (int rc = vitvs_pose_rig_velocity_dev(h, n_cams, d_rTc, d_K, d_status, n_iter, d_v, d_rig_status, d_pose, d_info, d_moments,
-                                             d_weights, d_sigma, st))
-        return rc;
-    VITVS_HIP_CHECK(hipStreamSynchronize(st));
-    VITVS_HIP_CHECK(hipMemcpy(v_rig, d_v, 6 * 8, hipMemcpyDeviceToHost));
-    VITVS_HIP_CHECK(hipMemcpy(rig_status, d_rig_status, 4, hipMemcpyDeviceToHost));
-    if (pose) VITVS_HIP_CHECK(hipMemcpy(pose, d_pose, 12 * 8, hipMemcpyDeviceToHost));
-    if (rig_info) VITVS_HIP_CHECK(hipMemcpy(rig_info, d_info, 8 * 4, hipMemcpyDeviceToHost));
-    if (moments) VITVS_HIP_CHECK(hipMemcpy(moments, d_moments, 18 * 8, hipMemcpyDeviceToHost));
-    if (weights) VITVS_HIP_CHECK(hipMemcpy(weights, d_weights, n * R * 8, hipMemcpyDeviceToHost));
-    if (sigma) VITVS_HIP_CHECK(hipMemcpy(sigma, d_sigma, 8, hipMemcpyDeviceToHost));
-    return 0;
+    PoseRigIo io = pose_rig_io(h->cfg.max_pairs, h->cfg.max_rows, n_cams, rTc, K, status, v_rig, rig_status, pose, rig_info, moments,
+                               weights, sigma);
+    return host_call(h, io_list(io), h->pose_rig_io, [&](hipStream_t st) {
+        return vitvs_pose_rig_velocity_dev(h, n_cams, io.rTc.f64(), io.K.f64(), io.status.i32(), n_iter, io.v_rig.f64(),
+                                           io.rig_status.i32(), io.pose.f64(), io.rig_info.i32(), io.moments.f64(), io.weights.f64(),
+                                           io.sigma.f64(), st);
+    });
 }
 
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
@@ -2106,9 +2024,7 @@ int vitvs_op_rig_law(int32_t n_cams, const int32_t* rows, const double* L, int32
 }
 
 int vitvs_op_rig_scratch_bytes(int32_t n_cams, int32_t ld) {
-    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
-    const size_t b = rig_scratch_bytes(n_cams, ld);
-    return b > 0x7fffffffu ? -3 : (int)b;
+    return (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) ? -2 : bytes_i32(rig_scratch_bytes(n_cams, ld));
 }
 
 int vitvs_op_rig_robust_law(int32_t n_cams, const int32_t* rows, const int32_t* live, const double* L, int32_t ld, const double* W,
@@ -2128,9 +2044,7 @@ int vitvs_op_rig_robust_law(int32_t n_cams, const int32_t* rows, const int32_t* 
 }
 
 int vitvs_op_rig_robust_scratch_bytes(int32_t n_cams, int32_t ld) {
-    if (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) return -2;
-    const size_t b = rig_robust_scratch_bytes(n_cams, ld);
-    return b > 0x7fffffffu ? -3 : (int)b;
+    return (n_cams < 1 || n_cams > kRigMaxCams || ld < 1) ? -2 : bytes_i32(rig_robust_scratch_bytes(n_cams, ld));
 }
 
 int vitvs_op_rig_robust_plan(int32_t n_cams, int32_t ld, int32_t* out) {
@@ -2157,18 +2071,14 @@ int vitvs_op_pose_law(int32_t n_pairs, int32_t ld, const double* P, const double
 }
 
 int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld) {
-    if (n_pairs < 1 || ld < 1) return -2;
-    const size_t b = pose_scratch_bytes(n_pairs, ld);
-    return b > 0x7fffffffu ? -3 : (int)b;
+    return (n_pairs < 1 || ld < 1) ? -2 : bytes_i32(pose_scratch_bytes(n_pairs, ld));
 }
 
 int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
     if (!out) return -1;
     PosePlan pl;
     memset(&pl, 0, sizeof(pl));
-    const int rc = plan_pose(max_rows, n_iter, &pl);
-    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
-    return rc;
+    return plan_out(plan_pose(max_rows, n_iter, &pl), pl, out);
 }
 
 int vitvs_op_pose_rig_law(int32_t n_cams, int32_t ld, const double* P, const double* Q, const int32_t* usable, const double* rTc,
@@ -2187,18 +2097,14 @@ int vitvs_op_pose_rig_law(int32_t n_cams, int32_t ld, const double* P, const dou
 }
 
 int vitvs_op_pose_rig_scratch_bytes(int32_t n_cams, int32_t ld) {
-    if (n_cams < 1 || ld < 1) return -2;
-    const size_t b = pose_rig_scratch_bytes(n_cams, ld);
-    return b > 0x7fffffffu ? -3 : (int)b;
+    return (n_cams < 1 || ld < 1) ? -2 : bytes_i32(pose_rig_scratch_bytes(n_cams, ld));
 }
 
 int vitvs_op_pose_rig_plan(int32_t n_cams, int32_t ld, int32_t n_iter, int32_t* out) {
     if (!out) return -1;
     PoseRigPlan pl;
     memset(&pl, 0, sizeof(pl));
-    const int rc = plan_pose_rig(n_cams, ld, n_iter, &pl);
-    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
-    return rc;
+    return plan_out(plan_pose_rig(n_cams, ld, n_iter, &pl), pl, out);
 }
 
 int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable, double lambda,
@@ -2216,18 +2122,14 @@ int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const 
 }
 
 int vitvs_op_homography_scratch_bytes(int32_t n_pairs, int32_t ld) {
-    if (n_pairs < 1 || ld < 1) return -2;
-    const size_t b = homography_scratch_bytes(n_pairs, ld);
-    return b > 0x7fffffffu ? -3 : (int)b;
+    return (n_pairs < 1 || ld < 1) ? -2 : bytes_i32(homography_scratch_bytes(n_pairs, ld));
 }
 
 int vitvs_op_homography_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
     if (!out) return -1;
     HomographyPlan pl;
     memset(&pl, 0, sizeof(pl));
-    const int rc = plan_homography(max_rows, n_iter, &pl);
-    out[0] = (int32_t)pl.lds; out[1] = pl.robust; out[2] = pl.lds_opt_in;
-    return rc;
+    return plan_out(plan_homography(max_rows, n_iter, &pl), pl, out);
 }
 
 int vitvs_op_rig_two_launches(int32_t on) {

@@ -1,0 +1,100 @@
+// The device side of the follow-on laws' host-pointer entry points (api.hip): per law ONE list of the fields its block holds,
+// in the block's order.  io_place turns a list into the block's size and every field's device pointer, so the allocation and the
+// pointers cannot disagree; host_call (api.hip) copies along the same list.  No HIP here: tools/io_layout_check.cpp checks the
+// lists on the CPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace vitvs {
+
+struct IoField {
+    size_t elem;                  // bytes per element: 8 (f64) or 4 (i32); a list holds its 8-byte fields first, so nothing is padded
+    size_t cap;                   // elements the block reserves: the field at max_pairs / max_rows
+    size_t count;                 // elements of the call at hand: what is copied
+    bool input;                   // copied to the device before the launch; an output is copied back after it
+    void* host;                   // the caller's array; null: an optional output nobody asked for
+    unsigned char* dev = nullptr; // io_place
+    double* f64() const { return reinterpret_cast<double*>(dev); }
+    int32_t* i32() const { return reinterpret_cast<int32_t*>(dev); }
+};
+
+inline IoField io_in(size_t elem, size_t cap, size_t count, const void* host) {
+    return IoField{elem, cap, count, true, const_cast<void*>(host)};
+}
+inline IoField io_out(size_t elem, size_t cap, size_t count, void* host) { return IoField{elem, cap, count, false, host}; }
+
+// A law's list is a struct of IoFields and nothing else: its members, in declaration order, are the block.
+struct IoList {
+    IoField* f;
+    size_t n;
+};
+template <typename Io>
+IoList io_list(Io& io) {
+    static_assert(sizeof(Io) % sizeof(IoField) == 0 && alignof(Io) == alignof(IoField), "a struct of IoFields only");
+    return IoList{reinterpret_cast<IoField*>(&io), sizeof(Io) / sizeof(IoField)};
+}
+
+// The fields one after the other from `base` (null: sizes only); returns the block's bytes.
+inline size_t io_place(IoList l, unsigned char* base) {
+    size_t off = 0;
+    for (size_t i = 0; i < l.n; ++i) {
+        l.f[i].dev = base ? base + off : nullptr;
+        off += l.f[i].cap * l.f[i].elem;
+    }
+    return off;
+}
+
+// P = max_pairs, R = max_rows, n = the call's pairs / cameras.  A list of P and R alone still sizes the block (*_prepare).
+
+// the rig law and its robust form (K, sigma and weights are the robust form's: null, nothing copied, in the plain one)
+struct RigIo {
+    IoField cVr, v_rig, normal, K, sigma, weights, status, rig_status, rig_info;
+};
+inline RigIo rig_io(size_t P, size_t R, size_t n = 0, const double* cVr = nullptr, const int32_t* status = nullptr,
+                    const double* K = nullptr, double* v_rig = nullptr, int32_t* rig_status = nullptr, int32_t* rig_info = nullptr,
+                    double* normal = nullptr, double* weights = nullptr, double* sigma = nullptr) {
+    return RigIo{io_in(8, P * 36, n * 36, cVr), io_out(8, 6, 6, v_rig),        io_out(8, 28, 28, normal),
+                 io_in(8, P * 4, n * 4, K),     io_out(8, 1, 1, sigma),        io_out(8, P * R, n * R, weights),
+                 io_in(4, P, n, status),        io_out(4, 1, 1, rig_status),   io_out(4, 8, 8, rig_info)};
+}
+
+// the pose law
+struct PoseIo {
+    IoField K, v_pose, pose, sigma, weights, status, pose_status, pose_info;
+};
+inline PoseIo pose_io(size_t P, size_t R, size_t n = 0, const double* K = nullptr, const int32_t* status = nullptr,
+                      double* v_pose = nullptr, int32_t* pose_status = nullptr, double* pose = nullptr, int32_t* pose_info = nullptr,
+                      double* weights = nullptr, double* sigma = nullptr) {
+    return PoseIo{io_in(8, P * 4, n * 4, K),        io_out(8, P * 6, n * 6, v_pose), io_out(8, P * 12, n * 12, pose),
+                  io_out(8, P, n, sigma),           io_out(8, P * R, n * R, weights), io_in(4, P, n, status),
+                  io_out(4, P, n, pose_status),     io_out(4, P * 8, n * 8, pose_info)};
+}
+
+// the homography law
+struct HomographyIo {
+    IoField K, v_h, H, sigma, weights, status, h_status, h_info;
+};
+inline HomographyIo homography_io(size_t P, size_t R, size_t n = 0, const double* K = nullptr, const int32_t* status = nullptr,
+                                  double* v_h = nullptr, int32_t* h_status = nullptr, double* H = nullptr, int32_t* h_info = nullptr,
+                                  double* weights = nullptr, double* sigma = nullptr) {
+    return HomographyIo{io_in(8, P * 4, n * 4, K),    io_out(8, P * 6, n * 6, v_h),     io_out(8, P * 9, n * 9, H),
+                        io_out(8, P, n, sigma),       io_out(8, P * R, n * R, weights), io_in(4, P, n, status),
+                        io_out(4, P, n, h_status),    io_out(4, P * 8, n * 8, h_info)};
+}
+
+// the pose rig law
+struct PoseRigIo {
+    IoField rTc, K, v_rig, pose, moments, sigma, weights, status, rig_status, rig_info;
+};
+inline PoseRigIo pose_rig_io(size_t P, size_t R, size_t n = 0, const double* rTc = nullptr, const double* K = nullptr,
+                             const int32_t* status = nullptr, double* v_rig = nullptr, int32_t* rig_status = nullptr,
+                             double* pose = nullptr, int32_t* rig_info = nullptr, double* moments = nullptr, double* weights = nullptr,
+                             double* sigma = nullptr) {
+    return PoseRigIo{io_in(8, P * 12, n * 12, rTc), io_in(8, P * 4, n * 4, K),        io_out(8, 6, 6, v_rig),
+                     io_out(8, 12, 12, pose),       io_out(8, 18, 18, moments),       io_out(8, 1, 1, sigma),
+                     io_out(8, P * R, n * R, weights), io_in(4, P, n, status),        io_out(4, 1, 1, rig_status),
+                     io_out(4, 8, 8, rig_info)};
+}
+
+}  // namespace vitvs

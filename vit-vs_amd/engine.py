@@ -474,21 +474,63 @@ class Engine:
         self._check(rc, "vitvs_last_details")
         return dict(info=info, s_uv=suv, feat=feat)
 
+    # ------------------------------------------------------------------ the follow-on laws
     @staticmethod
-    def _rig_robust_arguments(n, robust_iterations, K):
-        """The checks of the robust rig law's extra arguments (no handle needed): float64 [n, 4] intrinsics, or None for N = 0."""
+    def _robust_iterations(robust_iterations) -> int:
         N = int(robust_iterations)
         if not 0 <= N <= 16:
             raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
-        if N == 0:
+        return N
+
+    @staticmethod
+    def _intrinsics_rows(K, n, who="camera"):
+        """``K`` (numpy, a sequence or a tensor) as contiguous float64 numpy [n, 4]: one (fx, fy, cx, cy) per ``who``, or one for all."""
+        k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64).reshape(-1, 4)
+        if k.shape[0] == 1:
+            k = np.broadcast_to(k, (n, 4))
+        if k.shape[0] != n:
+            raise ValueError(f"one (fx, fy, cx, cy) per {who} expected")
+        return np.ascontiguousarray(k)
+
+    def _intrinsics_rows_dev(self, K, n):
+        """``_intrinsics_rows`` for a device call: a contiguous float64 tensor [n, 4] on the device (a device tensor stays there)."""
+        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
+        if kk.shape[0] == 1:
+            kk = kk.expand(n, 4)
+        if kk.shape[0] != n:
+            raise VitvsError("one (fx, fy, cx, cy) per pair expected")
+        return kk.contiguous().to(self.device)
+
+    def _status(self, status, host):
+        """The velocity call's statuses as a law's call reads them: contiguous int32 [n], numpy or on the device."""
+        if host:
+            return np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        return torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+
+    def _outputs(self, host):
+        """What a law's host-pointer form (numpy) and device form (tensors, the current stream) make their calls of: ``(a float64
+        output of a shape, an int32 one, an array's pointer, the trailing stream argument)``."""
+        if host:
+            return (lambda *s: np.zeros(s)), (lambda *s: np.zeros(s, np.int32)), (lambda a: a.ctypes.data_as(C.c_void_p)), ()
+        return ((lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)),
+                (lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)), _ptr, (_stream_ptr(self.device),))
+
+    @staticmethod
+    def _law_info(fields, counters, per_pair, **arrays):
+        """A law's ``info``: ``arrays`` as given, then the counters ``fields`` names: column i of ``counters`` [n, 8] for a law per
+        pair, the int ``counters[i]`` for a rig's."""
+        info = dict(arrays)
+        info.update({name: counters[:, i] if per_pair else int(counters[i]) for i, name in enumerate(fields)})
+        return info
+
+    @staticmethod
+    def _rig_robust_arguments(n, robust_iterations, K):
+        """The checks of the robust rig law's extra arguments (no handle needed): float64 [n, 4] intrinsics, or None for N = 0."""
+        if Engine._robust_iterations(robust_iterations) == 0:
             return None
         if K is None:
             raise ValueError("robust_iterations > 0 needs K: the cameras' intrinsics (fx, fy, cx, cy), one row per camera or one for all")
-        k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
-        k = np.broadcast_to(k.reshape(-1, 4), (n, 4)) if k.size == 4 else k.reshape(-1, 4)
-        if k.shape[0] != n:
-            raise ValueError("one (fx, fy, cx, cy) per camera expected")
-        return np.ascontiguousarray(k)
+        return Engine._intrinsics_rows(K, n)
 
     def rig_velocity(self, cVr, status, robust_iterations: int = 0, K=None):
         """``vitvs_rig_velocity_dev``: the ONE twist of a rigid rig whose cameras were the pairs of the last velocity call, from
@@ -505,28 +547,28 @@ class Engine:
         n = int(w.shape[0])
         k = self._rig_robust_arguments(n, robust_iterations, K)      # (before anything touches the device)
         w = w.to(self.device).contiguous()
-        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
+        st = self._status(status, False)
         if st.numel() != n:
             raise VitvsError("one status per camera expected")
-        v = torch.empty(6, dtype=torch.float64, device=self.device)
-        out = torch.empty(9, dtype=torch.int32, device=self.device)      # rig_status | rig_info [8]
-        normal = torch.empty(28, dtype=torch.float64, device=self.device)
+        f64, i32, _, _ = self._outputs(False)
+        v, normal = f64(6), f64(28)
+        out = i32(9)                                                     # rig_status | rig_info [8]
         if k is None:
             rc = self.lib.vitvs_rig_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(v), _ptr(out), _ptr(out[1:]), _ptr(normal),
                                                  _stream_ptr(self.device))
             self._check(rc, "vitvs_rig_velocity_dev")
-            o = out.cpu().numpy()
-            return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal)
-        kd = torch.from_numpy(k).to(self.device)
-        weights = torch.empty((n, self.max_rows), dtype=torch.float64, device=self.device)
-        sigma = torch.empty(1, dtype=torch.float64, device=self.device)
-        rc = self.lib.vitvs_rig_robust_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(kd), int(robust_iterations), _ptr(v),
-                                                    _ptr(out), _ptr(out[1:]), _ptr(normal), _ptr(weights), _ptr(sigma),
-                                                    _stream_ptr(self.device))
-        self._check(rc, "vitvs_rig_robust_velocity_dev")
+        else:
+            kd = torch.from_numpy(k).to(self.device)
+            weights, sigma = f64(n, self.max_rows), f64(1)
+            rc = self.lib.vitvs_rig_robust_velocity_dev(self.handle, n, _ptr(w), _ptr(st), _ptr(kd), int(robust_iterations), _ptr(v),
+                                                        _ptr(out), _ptr(out[1:]), _ptr(normal), _ptr(weights), _ptr(sigma),
+                                                        _stream_ptr(self.device))
+            self._check(rc, "vitvs_rig_robust_velocity_dev")
         o = out.cpu().numpy()
-        return v, int(o[0]), dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal,
-                                  reweighted=int(o[6]), zero_weights=int(o[7]), sigma=float(sigma.cpu()[0]), weights=weights)
+        info = dict(cameras=int(o[1]), rows=int(o[2]), sweeps=int(o[3]), worst_status=int(o[5]), normal=normal)
+        if k is not None:
+            info.update(reweighted=int(o[6]), zero_weights=int(o[7]), sigma=float(sigma.cpu()[0]), weights=weights)
+        return v, int(o[0]), info
 
     def rig_velocity_host(self, cVr, status, robust_iterations: int = 0, K=None):
         """``vitvs_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info [8] int32, normal [28])``
@@ -534,7 +576,7 @@ class Engine:
         ``weights`` float64 [n, max_rows] and ``sigma``."""
         w = np.ascontiguousarray(np.asarray(cVr, np.float64).reshape(-1, 36))
         k = self._rig_robust_arguments(int(w.shape[0]), robust_iterations, K)
-        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
+        st = self._status(status, True)
         v, rs, info, normal = np.zeros(6), np.zeros(1, np.int32), np.zeros(8, np.int32), np.zeros(28)
         p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         if k is None:
@@ -547,7 +589,27 @@ class Engine:
         self._check(rc, "vitvs_rig_robust_velocity")
         return v, int(rs[0]), info, normal, weights, float(sigma[0])
 
+    def _pair_law(self, entry, host, K, status, scalars, cols):
+        """A law per pair of the last velocity call through ``entry`` (host-pointer form) or ``entry + "_dev"``: numpy or device
+        tensors ``(v [n, 6], law status [n], the law's own output [n, cols], counters [n, 8], weights [n, max_rows], sigma [n])``."""
+        f64, i32, p, stream = self._outputs(host)
+        st = self._status(status, host)
+        kk = self._intrinsics_rows(K, st.size, "pair") if host else self._intrinsics_rows_dev(K, st.numel())
+        entry += "" if host else "_dev"
+        n = int(kk.shape[0])
+        v, own, weights, sigma, lst, counters = f64(n, 6), f64(n, cols), f64(n, self.max_rows), f64(n), i32(n), i32(n, 8)
+        rc = getattr(self.lib, entry)(self.handle, n, p(kk), p(st), *scalars, p(v), p(lst), p(own), p(counters), p(weights), p(sigma),
+                                      *stream)
+        self._check(rc, entry)
+        return v, lst, own, counters, weights, sigma
+
     POSE_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes")
+
+    def _pose_law(self, host, K, status, robust_iterations):
+        N = self._robust_iterations(robust_iterations)
+        v, pst, pose, pinfo, weights, sigma = self._pair_law("vitvs_pose_velocity", host, K, status, (N,), 12)
+        return v, self._law_info(self.POSE_INFO_FIELDS, pinfo, True, status=pst, R=pose[:, :9].reshape(len(pst), 3, 3), t=pose[:, 9:],
+                                 weights=weights, sigma=sigma)
 
     def pose_velocity(self, K, status, robust_iterations: int = 0):
         """``vitvs_pose_velocity_dev``: the pose law of every pair of the last velocity call, from what that call left
@@ -558,57 +620,29 @@ class Engine:
         int32 [n], ``R`` [n, 3, 3], ``t`` [n, 3], ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` /
         ``holes`` int32 [n], ``weights`` float64 [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing
         synchronises after the first call (which allocates: make it outside a stream capture)."""
-        N = int(robust_iterations)
-        if not 0 <= N <= 16:
-            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
-        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        n = int(st.numel())
-        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
-        if kk.shape[0] == 1 and n > 1:
-            kk = kk.expand(n, 4)
-        if kk.shape[0] != n:
-            raise VitvsError("one (fx, fy, cx, cy) per pair expected")
-        kk = kk.contiguous().to(self.device)
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
-        v, pose, weights, sigma = f64(n, 6), f64(n, 12), f64(n, self.max_rows), f64(n)
-        pst, pinfo = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty((n, 8), dtype=torch.int32, device=self.device)
-        rc = self.lib.vitvs_pose_velocity_dev(self.handle, n, _ptr(kk), _ptr(st), N, _ptr(v), _ptr(pst), _ptr(pose), _ptr(pinfo),
-                                              _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
-        self._check(rc, "vitvs_pose_velocity_dev")
-        info = dict(status=pst, R=pose[:, :9].reshape(n, 3, 3), t=pose[:, 9:], weights=weights, sigma=sigma)
-        info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
-        return v, info
+        return self._pose_law(False, K, status, robust_iterations)
 
     def pose_velocity_host(self, K, status, robust_iterations: int = 0):
         """``vitvs_pose_velocity``, the host-pointer form: numpy in, ``(v_pose float64 [n, 6], info)`` out, ``info`` as
         ``pose_velocity``'s with numpy arrays.  Synchronous."""
-        N = int(robust_iterations)
-        if not 0 <= N <= 16:
-            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
-        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
-        n = int(st.size)
-        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
-        v, pose, weights, sigma = np.zeros((n, 6)), np.zeros((n, 12)), np.zeros((n, self.max_rows)), np.zeros(n)
-        pst, pinfo = np.zeros(n, np.int32), np.zeros((n, 8), np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.vitvs_pose_velocity(self.handle, n, p(kk), p(st), N, p(v), p(pst), p(pose), p(pinfo), p(weights), p(sigma))
-        self._check(rc, "vitvs_pose_velocity")
-        info = dict(status=pst, R=pose[:, :9].reshape(n, 3, 3), t=pose[:, 9:], weights=weights, sigma=sigma)
-        info.update({name: pinfo[:, i] for i, name in enumerate(self.POSE_INFO_FIELDS)})
-        return v, info
+        return self._pose_law(True, K, status, robust_iterations)
 
     HOMOGRAPHY_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "behind")
 
     @staticmethod
     def _homography_arguments(depth_scale, robust_iterations):
         """The checks of the homography law's arguments (no handle needed)."""
-        N = int(robust_iterations)
-        if not 0 <= N <= 16:
-            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        N = Engine._robust_iterations(robust_iterations)
         z = float(depth_scale)
         if not (z > 0.0 and math.isfinite(z)):
             raise ValueError(f"depth_scale is a positive, finite length in metres, got {depth_scale!r}")
         return z, N
+
+    def _homography_law(self, host, K, status, depth_scale, robust_iterations):
+        z, N = self._homography_arguments(depth_scale, robust_iterations)
+        v, hst, H, hinfo, weights, sigma = self._pair_law("vitvs_homography_velocity", host, K, status, (z, N), 9)
+        return v, self._law_info(self.HOMOGRAPHY_INFO_FIELDS, hinfo, True, status=hst, H=H.reshape(len(hst), 3, 3), weights=weights,
+                                 sigma=sigma)
 
     def homography_velocity(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
         """``vitvs_homography_velocity_dev``: the homography law of every pair of the last velocity call, from the
@@ -621,49 +655,19 @@ class Engine:
         ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` / ``behind`` int32 [n], ``weights`` float64
         [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing synchronises after the first call (which
         allocates: make it outside a stream capture)."""
-        z, N = self._homography_arguments(depth_scale, robust_iterations)
-        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        n = int(st.numel())
-        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
-        if kk.shape[0] == 1 and n > 1:
-            kk = kk.expand(n, 4)
-        if kk.shape[0] != n:
-            raise VitvsError("one (fx, fy, cx, cy) per pair expected")
-        kk = kk.contiguous().to(self.device)
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
-        v, H, weights, sigma = f64(n, 6), f64(n, 9), f64(n, self.max_rows), f64(n)
-        hst, hinfo = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty((n, 8), dtype=torch.int32, device=self.device)
-        rc = self.lib.vitvs_homography_velocity_dev(self.handle, n, _ptr(kk), _ptr(st), z, N, _ptr(v), _ptr(hst), _ptr(H), _ptr(hinfo),
-                                                    _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
-        self._check(rc, "vitvs_homography_velocity_dev")
-        info = dict(status=hst, H=H.reshape(n, 3, 3), weights=weights, sigma=sigma)
-        info.update({name: hinfo[:, i] for i, name in enumerate(self.HOMOGRAPHY_INFO_FIELDS)})
-        return v, info
+        return self._homography_law(False, K, status, depth_scale, robust_iterations)
 
     def homography_velocity_host(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
         """``vitvs_homography_velocity``, the host-pointer form: numpy in, ``(v_h float64 [n, 6], info)`` out, ``info`` as
         ``homography_velocity``'s with numpy arrays.  Synchronous."""
-        z, N = self._homography_arguments(depth_scale, robust_iterations)
-        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
-        n = int(st.size)
-        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
-        v, H, weights, sigma = np.zeros((n, 6)), np.zeros((n, 9)), np.zeros((n, self.max_rows)), np.zeros(n)
-        hst, hinfo = np.zeros(n, np.int32), np.zeros((n, 8), np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.vitvs_homography_velocity(self.handle, n, p(kk), p(st), z, N, p(v), p(hst), p(H), p(hinfo), p(weights), p(sigma))
-        self._check(rc, "vitvs_homography_velocity")
-        info = dict(status=hst, H=H.reshape(n, 3, 3), weights=weights, sigma=sigma)
-        info.update({name: hinfo[:, i] for i, name in enumerate(self.HOMOGRAPHY_INFO_FIELDS)})
-        return v, info
+        return self._homography_law(True, K, status, depth_scale, robust_iterations)
 
     POSE_RIG_INFO_FIELDS = ("cameras", "usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes", "worst_status")
 
     @staticmethod
     def _pose_rig_arguments(rig, K, status, robust_iterations):
         """The checks of the pose rig law's arguments (no handle needed): float64 rTc [n, 12], K [n, 4] and N."""
-        N = int(robust_iterations)
-        if not 0 <= N <= 16:
-            raise ValueError(f"robust_iterations is 0 .. 16, got {robust_iterations!r}")
+        N = Engine._robust_iterations(robust_iterations)
         n = len(rig)
         if n < 1:
             raise ValueError("rig is a sequence of (R_i, t_i), one per camera of the last velocity call")
@@ -675,11 +679,23 @@ class Engine:
             rtc[i, :9], rtc[i, 9:] = R.reshape(9), t.reshape(3)
         if int(status.numel() if torch.is_tensor(status) else np.asarray(status).size) != n:
             raise ValueError("one status per camera of the rig expected")
-        k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
-        k = np.broadcast_to(k.reshape(-1, 4), (n, 4)) if k.size == 4 else k.reshape(-1, 4)
-        if k.shape[0] != n:
-            raise ValueError("one (fx, fy, cx, cy) per camera expected")
-        return rtc, np.ascontiguousarray(k), N
+        return rtc, Engine._intrinsics_rows(K, n), N
+
+    def _pose_rig_law(self, host, rig, K, status, robust_iterations):
+        rtc, k, N = self._pose_rig_arguments(rig, K, status, robust_iterations)      # (before anything touches the device)
+        n, entry = int(rtc.shape[0]), "vitvs_pose_rig_velocity" + ("" if host else "_dev")
+        f64, i32, p, stream = self._outputs(host)
+        st = self._status(status, host)
+        if not host:
+            rtc, k = torch.from_numpy(rtc).to(self.device), torch.from_numpy(k).to(self.device)
+        v, pose, moments, weights, sigma = f64(6), f64(12), f64(18), f64(n, self.max_rows), f64(1)
+        out = i32(9)                                                     # rig_status | rig_info [8]
+        rc = getattr(self.lib, entry)(self.handle, n, p(rtc), p(k), p(st), N, p(v), p(out), p(pose), p(out[1:]), p(moments),
+                                      p(weights), p(sigma), *stream)
+        self._check(rc, entry)
+        o = out if host else out.cpu().numpy()
+        return v, int(o[0]), self._law_info(self.POSE_RIG_INFO_FIELDS, o[1:], False, R=pose[:9].reshape(3, 3), t=pose[9:],
+                                            moments=moments, weights=weights, sigma=float(sigma[0]) if host else sigma)
 
     def pose_rig_velocity(self, rig, K, status, robust_iterations: int = 0):
         """``vitvs_pose_rig_velocity_dev``: the pose rig law of a rigid rig whose cameras were the pairs of the last
@@ -691,36 +707,12 @@ class Engine:
         (cameras, usable, sweeps, reweighted, zero_weights, degenerate, holes, worst_status as ints; R [3, 3], t [3], moments [18],
         weights [n, max_rows], sigma [1] as device tensors).  One launch on the current stream; reading the status synchronises.
         The first call allocates: make it outside a stream capture."""
-        rtc, k, N = self._pose_rig_arguments(rig, K, status, robust_iterations)      # (before anything touches the device)
-        n = int(rtc.shape[0])
-        st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        rd, kd = torch.from_numpy(rtc).to(self.device), torch.from_numpy(k).to(self.device)
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)   # noqa: E731
-        v, pose, moments, weights, sigma = f64(6), f64(12), f64(18), f64(n, self.max_rows), f64(1)
-        out = torch.empty(9, dtype=torch.int32, device=self.device)      # rig_status | rig_info [8]
-        rc = self.lib.vitvs_pose_rig_velocity_dev(self.handle, n, _ptr(rd), _ptr(kd), _ptr(st), N, _ptr(v), _ptr(out), _ptr(pose),
-                                                  _ptr(out[1:]), _ptr(moments), _ptr(weights), _ptr(sigma), _stream_ptr(self.device))
-        self._check(rc, "vitvs_pose_rig_velocity_dev")
-        o = out.cpu().numpy()
-        info = dict(R=pose[:9].reshape(3, 3), t=pose[9:], moments=moments, weights=weights, sigma=sigma)
-        info.update({name: int(o[1 + i]) for i, name in enumerate(self.POSE_RIG_INFO_FIELDS)})
-        return v, int(o[0]), info
+        return self._pose_rig_law(False, rig, K, status, robust_iterations)
 
     def pose_rig_velocity_host(self, rig, K, status, robust_iterations: int = 0):
         """``vitvs_pose_rig_velocity``, the host-pointer form: numpy in, ``(v_rig float64 [6], rig_status, info)`` out, ``info`` as
         ``pose_rig_velocity``'s with numpy arrays (``sigma`` a float).  Synchronous."""
-        rtc, k, N = self._pose_rig_arguments(rig, K, status, robust_iterations)
-        n = int(rtc.shape[0])
-        st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(-1))
-        v, pose, moments, weights, sigma = np.zeros(6), np.zeros(12), np.zeros(18), np.zeros((n, self.max_rows)), np.zeros(1)
-        rs, rinfo = np.zeros(1, np.int32), np.zeros(8, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.vitvs_pose_rig_velocity(self.handle, n, p(rtc), p(k), p(st), N, p(v), p(rs), p(pose), p(rinfo), p(moments),
-                                              p(weights), p(sigma))
-        self._check(rc, "vitvs_pose_rig_velocity")
-        info = dict(R=pose[:9].reshape(3, 3), t=pose[9:], moments=moments, weights=weights, sigma=float(sigma[0]))
-        info.update({name: int(rinfo[i]) for i, name in enumerate(self.POSE_RIG_INFO_FIELDS)})
-        return v, int(rs[0]), info
+        return self._pose_rig_law(True, rig, K, status, robust_iterations)
 
     # ------------------------------------------------------------------ options
     def set_option(self, name: str, value: int) -> "Engine":
