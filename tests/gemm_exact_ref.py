@@ -12,8 +12,9 @@ outputs <= 256, fp16 and f16x2 outputs <= 2048, where the f16x2 low halves are z
   W     in {-2, -1, 1, 2}, hashed by (column, k)
   bias  integer in [-8, 8];  ls in {-1, 1, 2};  x0 integer in [-4, 4]
 
-The reference is the fp64 product A @ W.T (per K slice for the partial sums).  GELU and LayerNorm are not exact and stay with
-the randn tests; so do the hi / lo cross terms of f16x2 (integer operands have no low halves).
+The reference is the fp64 product A @ W.T (per K slice for the partial sums).  GELU is not exact, and integer operands have no
+f16x2 low halves: tests/epilogue_exact_ref.py makes the pre-activation and the hi / lo cross terms exact instead and
+tests/test_gpu_epilogue_exact.py compares per element; LayerNorm is held per row by test_layernorm_stress_rows.
 
 CASES is literal: every case declares the plan it must get, `key` = [big family, rows, columns, k-groups, ring stages, K slices >
 1, XCD map] as tools/plan_cover.py keys a linear launch, and for the tiles of gemm_big.hip `grid` = [tiles, workgroups, XCD map

@@ -24,8 +24,9 @@ __device__ __forceinline__ void store4(T* dst, f32x4 v) {
 }
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-// erf to ~1.5e-7 absolute (Abramowitz & Stegun 7.1.26): two orders below bf16 output rounding, a
-// fraction of libm erff's instruction count.  Used only when the layer's output is bf16.
+// erf to ~1.5e-7 absolute (Abramowitz & Stegun 7.1.26; with fp32 rounding ~5e-7): four orders below bf16 output
+// rounding and three below fp16's, a fraction of libm erff's instruction count.  Used when the layer's output is
+// one of the plain 16-bit types, bf16 or fp16 (FAST_GELU below; BigStore::apply of gemm_big.hip holds a copy).
 __device__ __forceinline__ float gelu_erf_fast(float v) {
     const float x = fabsf(v) * 0.70710678118654752440f;
     const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * x);
@@ -51,7 +52,8 @@ struct EpiStore {
     // staged epilogue (linear_kernel): the tile leaves through an LDS image as whole rows
     using Out = T;
     static constexpr bool STAGED = true;
-    // the fast erf is two orders below the output rounding of the plain 16-bit types only; f16x2 keeps fp32-class outputs
+    // bf16 and fp16 outputs take the fast erf (its error is orders below their output rounding; tests/test_gpu_epilogue_exact.py
+    // holds both forms per element); fp32 and f16x2 keep fp32-class outputs: libm erff
     static constexpr bool FAST_GELU = sizeof(T) == 2 && !kSplit<T>;
     static constexpr int OUT_BYTES = kSplit<T> ? 4 : (int)sizeof(T);     // bytes per logical output column
     __device__ __forceinline__ f32x4 value(f32x4 v, float4 b) const {
