@@ -61,7 +61,11 @@ enum vitvs_select {
     VITVS_SELECT_EXPLICIT = 0, /* caller passes the chosen token ids of the desired frame            */
     VITVS_SELECT_ORDER = 1,    /* caller passes a visiting order (permutation of 0..T-1); the first  */
                                /* num_pairs candidates met in that order are used                    */
-    VITVS_SELECT_DENSE = 2     /* every candidate, ascending token id (no zero padding)              */
+    VITVS_SELECT_DENSE = 2,    /* every candidate, ascending token id (no zero padding)              */
+    VITVS_SELECT_BEST = 3      /* an extension beyond the reference: ORDER on a visiting order made  */
+                               /* on the device, deterministic: candidates ranked by similarity and  */
+                               /* taken round-robin over a grid of image cells (option               */
+                               /* "select_cells"); nothing comes from the caller                     */
 };
 
 typedef struct vitvs_config {
@@ -127,7 +131,7 @@ VITVS_API int vitvs_weights_ready(const vitvs_handle* h);
  *   Z_mm             uint16 [n_pairs][v_max][u_max], or NULL -> status NO_DEPTH
  *   K                double [n_pairs][4] = fx, fy, cx, cy
  *   select_mode      vitvs_select; `selection` int32: EXPLICIT [n_pairs][num_pairs] token ids with
- *                    n_selected[n_pairs] counts; ORDER [n_pairs][T]; DENSE ignored (NULL)
+ *                    n_selected[n_pairs] counts; ORDER [n_pairs][T]; DENSE and BEST ignored (NULL)
  *   num_pairs        feature pairs of the control law for THIS call (the reference's Controller.num_pairs, which its
  *                    callers change between calls: 24 in the servo loop, 48 in find_and_set_best_pose,
  *                    vitvs_v2.py:1151-1189); 1 .. cfg.max_rows, or <= 0 for cfg.num_pairs
@@ -274,6 +278,14 @@ VITVS_API int vitvs_last_weights(vitvs_handle* h, int32_t n_pairs, double* w);
  * and with the option off.  With the option on, s_uv[..][2:4], feat (Z, x, y) and L of vitvs_last_details are those of the
  * moved matches.  Synchronising, always read from the device.  Replaces nothing (vitvs_v2.py:511-513: patch centres). */
 VITVS_API int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets);
+/* The visiting order the last law evaluation ran on when its select_mode was VITVS_SELECT_BEST: order int32 [n_pairs][T], a
+ * permutation of 0 .. T-1 per pair (T of that call), the tokens of the desired frame sorted ascending by (class, rho, -sim_1, id):
+ * class 0 for a mutual nearest neighbour (0 <= nn_1[i] < T and nn_2[nn_1[i]] == i) and 1 otherwise; rho the number of tokens of
+ * the same class in the same image cell with a larger sim_1, or the same sim_1 and a smaller id; cell of token i on the g x g
+ * grid = ((i / g) * c / g) * c + (i % g) * c / g in integer arithmetic, c = min(option "select_cells", g).  The law takes the
+ * first num_pairs candidates met in it, exactly as for VITVS_SELECT_ORDER.  Synchronising, always read from the device.  Error -5
+ * when the last law evaluation ran in another mode. */
+VITVS_API int vitvs_last_order(vitvs_handle* h, int32_t n_pairs, int32_t* order);
 
 /* --- the goal depth (option "interaction", below) ------------------------------------------------
  * Z_des_mm uint16 [n_goal][v_max][u_max], the depth image(s) taken at the goal pose, in the sensor's millimetres (device memory
@@ -521,6 +533,13 @@ VITVS_API int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const dou
  *                          vitvs_reselect), composes with "robust_law" and "subpatch" (the goal side of a refined match stays
  *                          the patch centre), and drops the handle's captured graphs when changed.  vitvs_last_goal_depth
  *                          returns Z*; L of vitvs_last_details is the matrix the mode built.
+ *   "select_cells" 1 .. 16  image cells per side of selection mode VITVS_SELECT_BEST (default 4; a token grid with fewer rows
+ *                          than that has one cell per row).  1: the num_pairs most similar mutual matches.  n: the best match
+ *                          of every non-empty cell first, then every cell's second best, and so on (vitvs_last_order states the
+ *                          order exactly).  Read by every entry point that takes a select_mode; changing it drops the handle's
+ *                          captured graphs.  The mode is one more launch in front of the law's (87 per update instead of 86),
+ *                          measured on an MI355X at 7.4 us for 196 tokens, 18.0 us for 484 and 69.5 us for 3136
+ *                          (profiles/best_selection.txt): more than the law it feeds at every size.
  * Returns 0, or -5 for an unknown name / a value out of range. */
 VITVS_API int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value);
 /* The handles of such an arrangement run ONE network: `h` (created with the same network, input geometry and precision, no

@@ -252,6 +252,13 @@ VITVS_API int vitvs_op_saliency(int32_t precision, const void* qkv, float* out, 
                       const int32_t* head_idx, int32_t n_heads, int32_t q_prescaled, void* stream);
 /* dst[r][:] = src[r][:] / max(|src[r]|, 1e-8), fp32 rows of any width Dp >= 1 */
 VITVS_API int vitvs_op_normalize_rows(const float* src, float* dst, int32_t rows, int32_t Dp, void* stream);
+/* The kernel of selection mode VITVS_SELECT_BEST alone on given tables (device pointers nn_1, nn_2 int32 and sim_1 fp32
+ * [n_pairs][T]): order int32 [n_pairs][T] as vitvs_last_order states it, for `cells` in 1 .. 16 image cells per side.  The tables
+ * are packed into the keys the law reads, as vitvs_servo_from_nn_dev packs them, in scratch memory of the call's own; the call
+ * returns after the launches have finished.  -2 when T is not a square grid or an argument is out of range, -3, without a launch,
+ * when T keys do not fit in 160 KiB of LDS. */
+VITVS_API int vitvs_op_best_order_dev(int32_t T, int32_t cells, int32_t n_pairs, const int32_t* nn_1, const int32_t* nn_2,
+                            const float* sim_1, int32_t* order, void* stream);
 
 #ifdef __cplusplus
 }

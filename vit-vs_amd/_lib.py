@@ -18,7 +18,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 ABI_VERSION = 2
 F32, BF16, F16, F16X2 = 0, 1, 2, 3
 STATUS_OK, STATUS_NO_CORRESPONDENCE, STATUS_TOO_FEW, STATUS_NO_DEPTH = 0, 1, 2, 3
-SELECT_EXPLICIT, SELECT_ORDER, SELECT_DENSE = 0, 1, 2
+SELECT_EXPLICIT, SELECT_ORDER, SELECT_DENSE, SELECT_BEST = 0, 1, 2, 3
 
 
 class VitvsConfig(C.Structure):
@@ -59,6 +59,7 @@ PROTOTYPES = {
     "vitvs_servo_from_nn_ex_dev": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "vitvs_refine_dev": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "vitvs_last_offsets": (_I, [_P, _I, _P]),
+    "vitvs_last_order": (_I, [_P, _I, _P]),
     "vitvs_set_goal_depth_dev": (_I, [_P, _I, _P, _P]),
     "vitvs_set_goal_depth": (_I, [_P, _I, _P]),
     "vitvs_last_goal_depth": (_I, [_P, _I, _P]),
@@ -129,6 +130,7 @@ PROTOTYPES = {
     "vitvs_op_facet": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P]),
     "vitvs_op_saliency": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vitvs_op_normalize_rows": (_I, [_P, _P, _I, _I, _P]),
+    "vitvs_op_best_order_dev": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 

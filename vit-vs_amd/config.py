@@ -180,6 +180,10 @@ class ServoParams:
     interaction: str = "current"   # the interaction matrix the law inverts (option "interaction"): "current" L(s, Z), the reference's;
                                    # "desired" L(s*, Z*); "mean" of the two.  The last two need a goal depth (Engine.set_goal_depth)
 
+    select_cells: int = 4          # image cells per side of selection "best" (option "select_cells", 1 .. 16): the best matches are
+                                   # taken round-robin over a select_cells x select_cells grid; 1 = the most similar ones wherever
+                                   # they lie.  Not in the reference's config.yaml: it belongs to an extension
+
     rig_robust_iterations: int = 0  # Tukey re-weightings of the RIG law (MultiController(rig=...): one median over all cameras'
                                     # residuals, vitvs_rig_robust_velocity_dev; 1 .. 16); 0 = the plain rig law
 
@@ -197,6 +201,8 @@ class ServoParams:
     def __post_init__(self):
         if self.interaction not in INTERACTIONS:
             raise ValueError(f"interaction is one of {INTERACTIONS}, got {self.interaction!r}")
+        if not 1 <= int(self.select_cells) <= 16:
+            raise ValueError(f"select_cells is 1 .. 16, got {self.select_cells!r}")
         if self.law not in LAWS:
             raise ValueError(f"law is one of {LAWS}, got {self.law!r}")
         if not 0 <= int(self.pose_robust_iterations) <= 16:
@@ -268,7 +274,8 @@ def load_reference_config(source) -> ReferenceConfig:
     project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
     else "current"; ``law`` ("ibvs" / "pose" / "homography"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise,
-    else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0."""
+    else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``select_cells`` (the
+    cell grid of selection "best") likewise, else 4."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -290,11 +297,13 @@ def load_reference_config(source) -> ReferenceConfig:
                         pose_robust_iterations=int(cfg.get("pose_robust_iterations", 0)),
                         rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)),
                         homography_robust_iterations=int(cfg.get("homography_robust_iterations", 0)),
-                        homography_depth=float(cfg.get("homography_depth", 1.0)))
+                        homography_depth=float(cfg.get("homography_depth", 1.0)),
+                        select_cells=int(cfg.get("select_cells", 4)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
-            "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth"}
+            "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
+            "select_cells"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -138,6 +138,11 @@ struct vitvs_handle {
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
+    // Selection mode BEST (select.hip): the visiting order its kernel leaves for the law, laid out as nn1 is ([pairs][T] of the call,
+    // best_elems entries), the option "select_cells", and whether the last law evaluation ran on it (vitvs_last_order)
+    int32_t* order_ws = nullptr;
+    int select_cells = 4;
+    bool last_best = false;
     // device copies of the frames a host-pointer call hands over (filled from the pinned block, HostStage below), and the
     // graph replays' own copy of the selection
     uint8_t *st_cur = nullptr, *st_des = nullptr;
@@ -584,8 +589,9 @@ int plan_law(vitvs_handle* h, int T, const RefineSpec& rf, ServoPlan& plan) {
 }
 
 // The one place that records which law the handle's per-row workspaces and detail block are about to hold
-void note_law(vitvs_handle* h, int n_pairs, int T, const ServoPlan& plan) {
+void note_law(vitvs_handle* h, int n_pairs, int T, const ServoPlan& plan, int select_mode) {
     h->last_pairs = n_pairs; h->last_T = T; h->last_law = plan;
+    h->last_best = select_mode == VITVS_SELECT_BEST;
 }
 
 // The geometry of a law call over T = g * g tokens: what token_pixel (servo.hip) reads
@@ -613,7 +619,12 @@ int check_interaction(vitvs_handle* h, int n_pairs, int T) {
 // What every entry point asks of a call's selection over T tokens, before it stages or enqueues anything
 int check_selection(vitvs_handle* h, int T, int mode, const int32_t* selection, const int32_t* n_selected, int num_pairs) {
     if (num_pairs <= 0 || num_pairs > h->cfg.max_rows) return set_err(h, -5, "num_pairs must be in 1 .. max_rows");
-    if (mode < 0 || mode > 2) return set_err(h, -5, "unknown selection mode");
+    if (mode < 0 || mode > VITVS_SELECT_BEST) return set_err(h, -5, "unknown selection mode");
+    if (mode == VITVS_SELECT_BEST) {            // the order is made on the device: selection and n_selected are not read
+        BestOrderPlan bp;
+        const int rc = plan_best_order(T, h->select_cells, &bp);
+        return rc ? set_err(h, rc == -3 ? -3 : -5, "BEST selection needs a square token grid whose keys fit in LDS") : 0;
+    }
     if (mode != VITVS_SELECT_DENSE && !selection) return set_err(h, -5, "selection array required for this mode");
     if (mode == VITVS_SELECT_EXPLICIT && !n_selected) return set_err(h, -5, "n_selected required for EXPLICIT");
     if (mode == VITVS_SELECT_DENSE && h->cfg.max_rows < T) return set_err(h, -5, "DENSE selection needs max_rows >= T");
@@ -629,9 +640,20 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
     if (g * g != T) return set_err(h, -5, "token count is not a square grid");
     ServoPlan plan;
     if (int rc = plan_law(h, T, rf, plan)) return rc;
+    const bool best = mode == VITVS_SELECT_BEST;
+    if (best) {
+        // the visiting order from the keys themselves (select.hip), then the law exactly as on a caller's order
+        BestOrderPlan bp;
+        if (int rc = plan_best_order(T, h->select_cells, &bp)) return set_err(h, rc, "BEST selection: the token count does not fit in LDS");
+        if ((size_t)n_pairs * T > h->best_elems) return set_err(h, -3, "T exceeds the handle's workspace");
+        int rc = 0;
+        { Span sp(h, KC_SERVO, st); rc = launch_best_order(bp, n_pairs, h->row_best, h->col_best, h->order_ws, st); }
+        if (rc) return set_err(h, rc, "best-order launch failed");
+        selection = h->order_ws; n_selected = nullptr;
+    }
     ServoArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_pairs = n_pairs; a.num_pairs = num_pairs; a.mode = mode;
+    a.n_pairs = n_pairs; a.num_pairs = num_pairs; a.mode = best ? (int)VITVS_SELECT_ORDER : mode;
     servo_geometry(h, T, g, a);
     a.K = K; a.lambda = c.lambda;
     a.row_best = h->row_best; a.col_best = h->col_best; a.depth = Z;
@@ -654,7 +676,7 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
         a.interaction = plan.interaction; a.zgoal = h->zgoal; a.zgoal_out = h->zgoal_ws;
         a.zgoal_stride = h->n_goal_depth == 1 ? 0 : T + 1;
     }
-    note_law(h, n_pairs, T, plan);
+    note_law(h, n_pairs, T, plan, mode);
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(plan, a, st); }
     if (rc) return set_err(h, rc, "servo launch failed (LDS budget or bad arguments)");
@@ -891,6 +913,7 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     const size_t sel_cap = P * (size_t)(h->T > cfg->max_rows ? h->T : cfg->max_rows);
     if (!rc) rc = dev_alloc(h, &h->st_sel, sel_cap);
     if (!rc) rc = dev_alloc(h, &h->st_nsel, P);
+    if (!rc) rc = dev_alloc(h, &h->order_ws, h->best_elems);
     if (rc) {
         std::string msg = g_last_error;
         vitvs_destroy(h);
@@ -1399,7 +1422,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
         ge = &h->graphs.back();
     }
     ge->last_use = ++h->graph_clock;
-    note_law(h, u.n_pairs, h->T, u.law);        // (a replay runs none of run_servo's host code)
+    note_law(h, u.n_pairs, h->T, u.law, u.select_mode);   // (a replay runs none of run_servo's host code)
     VITVS_HIP_CHECK(hipGraphLaunch(ge->exec, st));
     return 0;
 }
@@ -1604,7 +1627,8 @@ int vitvs_set_option(vitvs_handle* h, const char* name, int64_t value) {
     const struct { const char* name; int* option; int lo, hi; bool staged_depth; const char* takes; } law[] = {
         {"robust_law", &h->robust_iters, 0, 16, false, "robust_law takes 0 (the plain law) or 1 .. 16 re-weightings"},
         {"subpatch", &h->subpatch, 0, 1, true, "subpatch takes 0 (patch centres) or 1 (refined matches)"},
-        {"interaction", &h->interaction, IL_CURRENT, IL_MEAN, true, "interaction takes 0 (current, L(s, Z)), 1 (desired, L(s*, Z*)) or 2 (their mean)"}};
+        {"interaction", &h->interaction, IL_CURRENT, IL_MEAN, true, "interaction takes 0 (current, L(s, Z)), 1 (desired, L(s*, Z*)) or 2 (their mean)"},
+        {"select_cells", &h->select_cells, 1, 16, false, "select_cells takes 1 .. 16 image cells per side (selection mode BEST)"}};
     for (const auto& o : law) {
         if (nm != o.name) continue;
         if (value < o.lo || value > o.hi) return set_err(h, -5, o.takes);
@@ -1898,6 +1922,16 @@ int vitvs_last_offsets(vitvs_handle* h, int32_t n_pairs, float* offsets) {
     return last_row_output(h, n_pairs, h->last_law.refine, h->off_ws, 2, offsets);
 }
 
+int vitvs_last_order(vitvs_handle* h, int32_t n_pairs, int32_t* order) {
+    if (!h || !order) return set_err(h, -1, "null argument");
+    if (!h->last_best) return set_err(h, -5, "the last law evaluation did not run in selection mode BEST");
+    if (n_pairs <= 0 || n_pairs > h->last_pairs) return set_err(h, -3, "no such pairs in the last call");
+    DeviceScope dev(h);
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    VITVS_HIP_CHECK(hipMemcpy(order, h->order_ws, (size_t)n_pairs * h->last_T * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int vitvs_timing_enable(vitvs_handle* h, int32_t on) {
     if (!h) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
@@ -2179,6 +2213,28 @@ int vitvs_op_gram_stencil(const float* x, int32_t T, int32_t P, int32_t D, int32
     go.x = x; go.P = P; go.G = G; go.sq = sq; go.grid = grid; go.des_shared = des_shared; go.row_best = rb; go.col_best = cb;
     if (!rc) rc = launch_gram(pl, go, st);
     return rc ? rc : decode_pairs(rb, cb, T, n_pairs, nn_1, nn_2, sim_1, st);
+}
+int vitvs_op_best_order_dev(int32_t T, int32_t cells, int32_t n_pairs, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1,
+                            int32_t* order, void* stream) {
+    if (!nn_1 || !nn_2 || !sim_1 || !order) return -1;
+    if (n_pairs < 1) return -2;
+    BestOrderPlan bp;
+    if (int rc = plan_best_order(T, cells, &bp)) return rc;    // (before anything is allocated or launched)
+    DeviceScope dev(nullptr);
+    hipStream_t st = as_stream(stream);
+    // the packed keys the law reads, made from the tables as vitvs_servo_from_nn_dev makes them; freed behind the launches
+    unsigned long long* keys = nullptr;
+    if (hipMalloc((void**)&keys, (size_t)2 * n_pairs * T * 8) != hipSuccess) return -6;
+    unsigned long long *rb = keys, *cb = keys + (size_t)n_pairs * T;
+    int rc = 0;
+    for (int b = 0; !rc && b < n_pairs; ++b) {
+        const size_t o = (size_t)b * T;
+        rc = launch_encode_best(nn_1 + o, nn_2 + o, sim_1 + o, T, rb + o, cb + o, st);
+    }
+    if (!rc) rc = launch_best_order(bp, n_pairs, rb, cb, order, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -1;
+    (void)hipFree(keys);
+    return rc;
 }
 int vitvs_op_touch(const void* p, int64_t bytes, int32_t share_xcds, void* stream) {
     DeviceScope dev(nullptr);

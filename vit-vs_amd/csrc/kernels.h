@@ -285,6 +285,23 @@ int launch_decode_best(const unsigned long long* row_best, const unsigned long l
 int launch_encode_best(const int32_t* nn1, const int32_t* nn2, const float* sim1, int T, unsigned long long* row_best,
                        unsigned long long* col_best, hipStream_t stream);
 
+// ---- select.hip ----------------------------------------------------------------------------
+// Selection mode BEST: the visiting order the law then runs on as on a caller's (SEL_PRIORITY).  order [n_pairs][T] <- the tokens
+// of every pair sorted by (class, rank within the token's image cell, -similarity, id), decoded from the packed keys the law
+// reads; one workgroup per pair, everything in LDS.
+struct BestOrderPlan {
+    int T = 0, grid = 0, cells = 0;   // cells: min(option "select_cells", grid)
+    int n = 0;                        // sorted keys: the next power of two of T
+    bool small = false;               // T <= 256: rank counting, one token per thread; else the bitonic network
+    int threads = 0;
+    size_t lds = 0;                   // dynamic LDS bytes
+    bool lds_opt_in = false;          // ... beyond 64 KiB
+};
+// -2: T not a square grid or cells outside 1 .. 16, -3: more than 160 KiB of LDS
+int plan_best_order(int T, int cells, BestOrderPlan* plan);
+int launch_best_order(const BestOrderPlan& plan, int n_pairs, const unsigned long long* row_best,
+                      const unsigned long long* col_best, int32_t* order, hipStream_t stream);
+
 // ---- servo.hip -----------------------------------------------------------------------------
 enum SelectMode : int { SEL_EXPLICIT = 0, SEL_PRIORITY = 1, SEL_DENSE = 2 };
 enum Status : int { ST_OK = 0, ST_NO_CORRESPONDENCE = 1, ST_TOO_FEW = 2, ST_NO_DEPTH = 3 };

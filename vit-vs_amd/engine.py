@@ -40,7 +40,7 @@ class Engine:
         self.lib = _lib.load()
         self.cfg = cfg
         given = params or ServoParams(dino_input_size=cfg.img_size)
-        self.params = given.replace(robust_iterations=0, subpatch=False, interaction="current")   # a fresh handle's law: apply_law_params
+        self.params = given.replace(robust_iterations=0, subpatch=False, interaction="current", select_cells=4)   # a fresh handle's law: apply_law_params
         # "f16x2": split-f16 (include/vitvs.h VITVS_F16X2) — fp32-class results on the f16 matrix cores, the parity mode at servo rate
         self.precision = {"fp32": _lib.F32, "f32": _lib.F32, "bf16": _lib.BF16, "fp16": _lib.F16, "f16": _lib.F16,
                           "f16x2": _lib.F16X2, "split-f16": _lib.F16X2}[precision]
@@ -258,7 +258,7 @@ class Engine:
         return k
 
     def _selection_args(self, mode, selection, n_pairs, tokens, num_pairs=None):
-        if mode == _lib.SELECT_DENSE:
+        if mode in (_lib.SELECT_DENSE, _lib.SELECT_BEST):   # nothing comes from the caller
             return None, None
         if selection is None:
             raise VitvsError("this selection mode needs a selection array")
@@ -382,7 +382,7 @@ class Engine:
 
     def _selection_arrays_host(self, mode, selection, n, k):
         """The selection of a host-pointer call as the int32 numpy arrays the C ABI takes: (ids [n, k], counts [n]) for
-        EXPLICIT, (visiting order [n, T], None) for ORDER, (None, None) for DENSE."""
+        EXPLICIT, (visiting order [n, T], None) for ORDER, (None, None) for DENSE and BEST."""
         if mode == _lib.SELECT_EXPLICIT:
             rows = selection if isinstance(selection, (list, tuple)) else [selection]
             if len(rows) != n:
@@ -718,16 +718,18 @@ class Engine:
     def set_option(self, name: str, value: int) -> "Engine":
         """Per-handle options of include/vitvs.h: ``graph_replay`` (0 / 1), ``in_flight`` (updates run beside this handle's),
         ``robust_law`` (0: the plain control law; 1 .. 16: Tukey re-weightings), ``subpatch`` (0: patch centres; 1: matches
-        refined by their sub-patch offsets), ``interaction`` (0: L(s, Z); 1: L(s*, Z*); 2: their mean)."""
+        refined by their sub-patch offsets), ``interaction`` (0: L(s, Z); 1: L(s*, Z*); 2: their mean), ``select_cells`` (1 .. 16:
+        image cells per side of ``SELECT_BEST``)."""
         self._check(self.lib.vitvs_set_option(self.handle, name.encode(), int(value)), f"vitvs_set_option({name})")
         return self
 
     def apply_law_params(self, params: ServoParams) -> "Engine":
-        """The control law of ``params`` (``robust_iterations``, ``subpatch``, ``interaction``): sets the options that differ from
-        this engine's and keeps ``self.params`` in step."""
+        """The control law of ``params`` (``robust_iterations``, ``subpatch``, ``interaction``, and ``select_cells`` of the selection
+        in front of it): sets the options that differ from this engine's and keeps ``self.params`` in step."""
         for field, option, value in (("robust_iterations", "robust_law", params.robust_iterations),
                                      ("subpatch", "subpatch", int(params.subpatch)),
-                                     ("interaction", "interaction", INTERACTIONS.index(params.interaction))):
+                                     ("interaction", "interaction", INTERACTIONS.index(params.interaction)),
+                                     ("select_cells", "select_cells", int(params.select_cells))):
             if getattr(params, field) != getattr(self.params, field):
                 self.set_option(option, value)
                 self.params = self.params.replace(**{field: getattr(params, field)})
@@ -769,6 +771,13 @@ class Engine:
         z = np.empty((n_pairs, self.max_rows), np.float64)
         self._check(self.lib.vitvs_last_goal_depth(self.handle, n_pairs, z.ctypes.data_as(C.c_void_p)), "vitvs_last_goal_depth")
         return z
+
+    def last_order(self, n_pairs: int = 1) -> np.ndarray:
+        """``vitvs_last_order``: int32 [n, T], the visiting order the last law evaluation ran on when its mode was ``SELECT_BEST``
+        (an error after any other mode).  Synchronises."""
+        order = np.empty((n_pairs, getattr(self, "_last_tokens", self.tokens)), np.int32)
+        self._check(self.lib.vitvs_last_order(self.handle, n_pairs, order.ctypes.data_as(C.c_void_p)), "vitvs_last_order")
+        return order
 
     def last_offsets(self, n_pairs: int = 1) -> np.ndarray:
         """``vitvs_last_offsets``: float32 [n, max_rows, 2], the sub-patch offsets (dr, dc) of every feature row's match in the

@@ -111,7 +111,8 @@ class UpdatePipeline:
                mode: int = _lib.SELECT_DENSE, selection: Optional[torch.Tensor] = None,
                n_selected: Optional[torch.Tensor] = None, des_shared: bool = False, num_pairs: int = 0,
                inputs_ready: bool = False) -> int:
-        """Arguments as ``Engine.compute_velocity_dev`` (device tensors).  The slot's stream first waits for the caller's
+        """Arguments as ``Engine.compute_velocity_dev`` (device tensors; ``mode=SELECT_BEST`` takes no selection tensor: the slot's
+        handle makes the visiting order itself).  The slot's stream first waits for the caller's
         current stream, so inputs produced there are complete; nothing synchronises the host.  ``inputs_ready``: the caller
         vouches that the inputs are complete already (e.g. device-resident buffers written before a synchronisation) — no event is
         recorded on the caller's stream, which otherwise is one more hardware queue with traffic on every update (module docstring).

@@ -40,6 +40,8 @@ def compute_velocity(engine: Engine, I_cur, I_des, Z, K=None, *, selection="orde
       "reference"  the reference's exact procedure and RNG stream (torch sort + randperm on the host between the
                    correspondence and the control law; two device round trips, as in the reference)
       "dense"      every mutual-NN token
+      "best"       the device's own deterministic choice (``SELECT_BEST``): the mutual-NN tokens ranked by similarity and taken
+                   round-robin over ``params.select_cells`` x ``select_cells`` image cells; no draw, nothing from the host
       array-like   explicit token ids of the desired frame
     ``num_pairs``: feature pairs of the law for this call (the reference's ``Controller.num_pairs``; default: the
     engine's parameters).
@@ -67,6 +69,8 @@ def compute_velocity_batch(engine: Engine, I_cur, I_des, Z, K=None, *, selection
                                         des_shared=des_shared, num_pairs=num_pairs)
     elif isinstance(selection, str) and selection == "dense":
         v, st = engine.compute_velocity(I_cur, I_des, Z, K, mode=_lib.SELECT_DENSE, des_shared=des_shared)
+    elif isinstance(selection, str) and selection == "best":
+        v, st = engine.compute_velocity(I_cur, I_des, Z, K, mode=_lib.SELECT_BEST, des_shared=des_shared, num_pairs=num_pairs)
     else:
         ids = selection if isinstance(selection, (list, tuple)) and n > 1 else [selection]
         v, st = engine.compute_velocity(I_cur, I_des, Z, K, mode=_lib.SELECT_EXPLICIT, selection=list(ids),
@@ -339,7 +343,7 @@ class Controller:
         # the law needs a depth image; detect_features itself does not, so feed a dummy one if it is missing
         z = depth if depth is not None else np.zeros((self.params.v_max, self.params.u_max), np.uint16)
         eng = self.engine
-        if isinstance(self.selection, str) and self.selection in ("order", "dense") and not torch.is_tensor(cur) \
+        if isinstance(self.selection, str) and self.selection in ("order", "dense", "best") and not torch.is_tensor(cur) \
                 and not torch.is_tensor(des) and tuple(cur.shape[:2]) == tuple(eng.frame_size) and np.asarray(z).dtype == np.uint16:
             # the callbacks' own arrays straight into the host-pointer entry point: one C call, no torch tensor, the feature
             # rows come back with it (Engine.last_features reads them from the handle's pinned block)
@@ -347,8 +351,9 @@ class Controller:
                 order = torch.randperm(eng.tokens, generator=self.generator).to(torch.int32).numpy()
                 v, st = eng.compute_velocity_host(cur, des, z, self.params.intrinsics(), _lib.SELECT_ORDER, order,
                                                   num_pairs=self.num_pairs)
-            else:
-                v, st = eng.compute_velocity_host(cur, des, z, self.params.intrinsics(), _lib.SELECT_DENSE, num_pairs=self.num_pairs)
+            else:                                         # "dense", "best": nothing to draw
+                mode = _lib.SELECT_DENSE if self.selection == "dense" else _lib.SELECT_BEST
+                v, st = eng.compute_velocity_host(cur, des, z, self.params.intrinsics(), mode, num_pairs=self.num_pairs)
             if not self._absorb(v[0], int(st[0])):
                 return None, None
             return self._features(eng.last_features(1), 0)
@@ -492,7 +497,8 @@ class MultiController:
     Each camera's raw and smoothed ``v_c`` equal those of an independent ``Controller(Engine)`` fed the same frames and the same
     draw (tests/test_gpu_multi.py: bit for bit).  ``selection``: "order" (a fresh random visiting order per camera and round, drawn
     in camera order from ``generator`` / torch's global RNG, exactly the draws N ``Controller(selection="order")`` make when their
-    ``ibvs()`` are called in camera order), "dense", or — per round, through ``ibvs(selection=[ids_0, ...])`` — explicit token ids.
+    ``ibvs()`` are called in camera order), "dense", "best" (the device's own deterministic choice per camera, ``SELECT_BEST``: no
+    draw at all), or — per round, through ``ibvs(selection=[ids_0, ...])`` — explicit token ids.
     The reference's host-side sort + randperm draw ("reference") needs a host round trip per camera and stays with ``Controller``.
     """
 
@@ -543,8 +549,8 @@ class MultiController:
                 raise ValueError("goal_depth is one image for all cameras, or one per camera")
             self._goal_depths = gd if gd.ndim == 3 else None
             params = (params or self.engine.params).replace(law="ibvs")
-        if selection not in ("order", "dense"):
-            raise ValueError('MultiController draws on the device: selection is "order" or "dense" (explicit ids per round: ibvs(selection=...))')
+        if selection not in ("order", "dense", "best"):
+            raise ValueError('MultiController draws on the device: selection is "order", "dense" or "best" (explicit ids per round: ibvs(selection=...))')
         self.selection, self.generator = selection, generator
         n = len(goal_images)
         if self.pipe is None and self.engine.max_pairs < n:
@@ -623,8 +629,8 @@ class MultiController:
         k = self.cameras[0].num_pairs
         if selection is not None:
             mode, sel = _lib.SELECT_EXPLICIT, [np.asarray(selection[i]) for i in live]
-        elif self.selection == "dense":
-            mode, sel = _lib.SELECT_DENSE, None
+        elif self.selection in ("dense", "best"):
+            mode, sel = (_lib.SELECT_DENSE if self.selection == "dense" else _lib.SELECT_BEST), None
         else:                                             # one fresh order per camera, drawn in camera order
             mode = _lib.SELECT_ORDER
             sel = [torch.randperm(eng.tokens, generator=self.generator).to(torch.int32) for _ in live]
