@@ -307,7 +307,8 @@ def test_null_outputs_and_error_returns():
 
 @gpu
 def test_the_pose_law_keeps_its_bits():
-    """vitvs_op_pose_law (pose.hip, whose shared functions moved into pose_core.h) before and after the rig law's launches."""
+    """vitvs_op_pose_law (pose.hip, which runs pose_core.h's pose_align as the rig law does) before and after the rig law's
+    launches."""
     import test_gpu_pose_op as single
     case = single.CASES["3x24"]
     one = single._Op(3, 24).load(case)
@@ -320,3 +321,49 @@ def test_the_pose_law_keeps_its_bits():
     for key in before:
         assert np.array_equal(before[key], after[key], equal_nan=True), key
     single._compare(after, single._reference("3x24", 4), "the pose law beside the rig law")
+
+
+# (case of tests/test_gpu_pose_op.py, its pair): 3 rows, <= 256 rows with unusable rows and outliers, > 256 rows with ties
+_ONE_CAMERA = (("1x3", 0), ("3x24", 0), ("1x130_coplanar", 0), ("1x258_ties", 0))
+
+
+def _one_camera_case(name, pair):
+    import test_gpu_pose_op as single
+    c = single.CASES[name]
+    return dict(P=c["P"][pair:pair + 1], Q=c["Q"][pair:pair + 1], usable=c["usable"][pair:pair + 1],
+                rig=[(np.eye(3), np.zeros(3))], status=np.zeros(1, np.int32), degenerate=c["degenerate"])
+
+
+@pytest.mark.parametrize("name,pair", _ONE_CAMERA)
+def test_one_camera_cases_make_the_identity_exact(name, pair):
+    """No GPU: ((1 p0 + 0 p1) + 0 p2) + 0 is p0 bit for bit only for a finite p0 that is not +-0 (and finite p1, p2)."""
+    c = _one_camera_case(name, pair)
+    live = c["usable"][0] > 0
+    assert live.sum() >= 3
+    for X in (c["P"][0][live], c["Q"][0][live]):
+        assert np.isfinite(X).all() and (X != 0.0).all(), name
+
+
+@gpu
+@pytest.mark.parametrize("name,pair", _ONE_CAMERA)
+def test_a_one_camera_rig_at_the_identity_has_the_pose_laws_bits(name, pair):
+    """One camera with rTc = (I, 0): the rig frame is the camera's frame and the stack is the pose law's point block, bit for bit,
+    so pose_rig_kernel and pose_kernel run pose_align on the same numbers.  v, R, t, the weights, sigma and the shared info fields
+    (usable rows, sweeps, re-weightings, zero weights, degenerate, holes) must be EQUAL for N = 0, 4 and 16."""
+    import test_gpu_pose_op as single
+    c = _one_camera_case(name, pair)
+    live = c["usable"][0] > 0
+    for X in (c["P"][0][live], c["Q"][0][live]):                # (before the GPU is touched)
+        assert np.isfinite(X).all() and (X != 0.0).all(), name
+    ld = c["usable"].shape[1]
+    one = single._Op(1, ld).load(c)
+    rig = _Op(1, ld).load(c)
+    for n_iter in (0, 4, 16):
+        assert one.call(n_iter) == 0 and rig.call(n_iter) == 0
+        a, b = one.results(), rig.results()
+        tag = f"{name} N={n_iter}"
+        assert a["status"][0] == b["status"], tag
+        for key in ("v", "R", "t", "weights", "sigma"):
+            assert np.array_equal(np.asarray(a[key][0]), np.asarray(b[key]).reshape(np.shape(a[key][0]))), (tag, key, a[key][0], b[key])
+        assert np.array_equal(a["info"][0][:6], b["info"][1:7]), (tag, a["info"][0], b["info"])
+        assert b["info"][0] == 1 and b["info"][7] == 0, (tag, b["info"])

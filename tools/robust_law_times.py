@@ -3,12 +3,14 @@
 Tiny handles (the law alone, through vitvs_servo_from_nn_dev): 24 pairs in ORDER mode at T = 196 (L and the weights in LDS) and a
 DENSE selection at T = 3136 (about a thousand pairs: L, the weights and the Jacobi copy in the global workspace, the residuals
 in LDS).  Times are the library's own event pairs around the launch (vitvs_timing_*), mean over --reps launches after a
-warm-up; one line per configuration.
+warm-up; one line per configuration and round.  --rounds repeats everything on the same handle, so the run-to-run spread of a line
+shows in one output.
 
-    python tools/robust_law_times.py [--reps 200]
+    python tools/robust_law_times.py [--reps 200] [--rounds 1]
 """
 import argparse
 import dataclasses
+import itertools
 import os
 import sys
 
@@ -33,6 +35,7 @@ def tables(rng, t, n_boost):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=1)
     args = ap.parse_args()
     for g, mode, name in ((14, _lib.SELECT_ORDER, "24 pairs, T = 196"), (56, _lib.SELECT_DENSE, "DENSE, T = 3136")):
         t, img = g * g, 16 * g
@@ -44,7 +47,7 @@ def main():
         nn1, nn2, sim1 = tables(rng, t, t // 3)
         order = rng.permutation(t).astype(np.int32) if mode == _lib.SELECT_ORDER else None
         depth, K = synth.depth_pattern(), params.intrinsics()
-        for n in (0, 1, 4, 16):
+        for rnd, n in itertools.product(range(args.rounds), (0, 1, 4, 16)):
             eng.set_option("robust_law", n)
             call = lambda: eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=mode, selection=order, num_pairs=24)  # noqa: E731
             for _ in range(10):
@@ -56,8 +59,8 @@ def main():
             ms, launches = eng.timing_collect()["servo"]
             eng.timing_enable(False)
             info = eng.last_details(1)["info"][0]
-            print(f"{name}: robust_law = {n:2d}: servo_kernel {1000 * ms / launches:8.2f} us (mean of {launches} launches), "
-                  f"{int(info[1])} feature pairs, {int(info[7])} with weight 0, final solve {'LDL^T' if info[4] < 0 else 'Jacobi'}")
+            print(f"round {rnd} {name}: robust_law = {n:2d}: servo_kernel {1000 * ms / launches:8.2f} us (mean of {launches} "
+                  f"launches), {int(info[1])} feature pairs, {int(info[7])} with weight 0, final solve {'LDL^T' if info[4] < 0 else 'Jacobi'}")
         eng.close()
 
 

@@ -11,11 +11,11 @@
 // M), each as quantities x 8 row slices (row r belongs to slice r mod 8, ascending rows, the slices added in ascending order):
 // bit-reproducible.  Wave 0 then runs the cyclic Jacobi eigen-decomposition of M with M and V (162 doubles) in LDS: every lane
 // computes the same rotation, lanes 0 .. 8 turn the rows of M and lanes 16 .. 24 the rows of V, in the reference's order of
-// arithmetic.  ROBUST: n_iter Tukey re-weightings on the transfer error with rho and w in dynamic LDS, the median by the rank
-// counting of servo.hip (pose_core.h's form), one more solve behind the last.
+// arithmetic.  ROBUST: n_iter Tukey re-weightings on the transfer error with rho and w in dynamic LDS (median_middles and
+// tukey_reweight of robust_core.h), one more solve behind the last.
 #include "common.h"
 #include "kernels.h"
-#include "pose_core.h"
+#include "robust_core.h"
 #include "solve.h"
 
 #pragma clang fp contract(off)
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
     if constexpr (ROBUST) {
         for (int k = tid; k < n; k += 256) {
             wk[k] = flag[k];
-            rho[k] = __longlong_as_double((long long)kPoseInfBits);
+            rho[k] = __longlong_as_double((long long)kInfBits);
         }
         lds_barrier();
     }
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
                 if (!(flag[k] > 0.0)) continue;             // not a usable row: rho stays +inf
                 const double x = ws[k], y = ws[(size_t)ld + k];
                 const double X = (H[0] * x + H[1] * y) + H[2], Y = (H[3] * x + H[4] * y) + H[5], Z = (H[6] * x + H[7] * y) + H[8];
-                double r = __longlong_as_double((long long)kPoseInfBits);
+                double r = __longlong_as_double((long long)kInfBits);
                 if (Z > 0.0) {
                     const double d0 = X / Z - ws[(size_t)2 * ld + k], d1 = Y / Z - ws[(size_t)3 * ld + k];
                     r = sqrt(d0 * d0 + d1 * d1);
@@ -340,21 +340,9 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
             infs = wave_sum(infs);
             if (lane == 0) iscr[10 + wave] = infs;
             lds_barrier();
-            pose_middles(rho, n, n_us, smh + kHomMid, tid);
+            median_middles(rho, n, n_us, smh + kHomMid, tid);
             lds_barrier();
-            sigma = fmax(1.4826 * ((smh[kHomMid] + smh[kHomMid + 1]) * 0.5), sigma_min);
-            const double cs = 4.6851 * sigma;
-            int zeros = 0;
-            for (int k = tid; k < n; k += 256) {
-                const bool us = flag[k] > 0.0;
-                const double tt = rho[k] / cs;
-                const double u = 1.0 - tt * tt;
-                const double w1 = (us && tt < 1.0) ? u * u : 0.0;
-                wk[k] = w1;
-                zeros += (us && w1 == 0.0) ? 1 : 0;
-            }
-            zeros = wave_sum(zeros);
-            if (lane == 0) iscr[2 + wave] = zeros;
+            sigma = tukey_reweight<true>(rho, flag, n, smh + kHomMid, sigma_min, wk, nullptr, iscr + 2, tid);
             lds_barrier();
             n_zero = iscr[2] + iscr[3] + iscr[4] + iscr[5];
             n_inf = iscr[10] + iscr[11] + iscr[12] + iscr[13];

@@ -1,14 +1,17 @@
-// What the pose law (pose.hip) and the pose rig law (pose_rig.hip) share: the layout of the head of
-// their dynamic LDS, the rank-counting median and Horn's solve (a cyclic Jacobi eigen-decomposition of the 4 x 4 matrix in fp64,
-// all indices compile-time: no scratch).
+// What the pose law (pose.hip) and the pose rig law (pose_rig.hip) share: the handle's form of a point
+// row, the layout of the head of their dynamic LDS, Horn's solve (a cyclic Jacobi eigen-decomposition of the 4 x 4 matrix in fp64,
+// all indices compile-time: no scratch), the alignment loop around it (pose_align) and the twist.  The median and the Tukey step
+// of the loop are robust_core.h's.
 #pragma once
 #include "common.h"
+#include "kernels.h"
+#include "robust_core.h"
+#include "solve.h"
 
 #pragma clang fp contract(off)
 
 namespace vitvs {
 
-constexpr unsigned long long kPoseInfBits = 0x7ff0000000000000ull;
 // dynamic LDS in doubles: slices [8][32] | 64 results (see the kPose* offsets) | ROBUST: rho [ld] | w [ld]
 constexpr int kPoseHead = 8 * 32 + 64;
 constexpr int kPoseSum = 256;        // [0 .. 11): the centred sums
@@ -18,27 +21,21 @@ constexpr int kPoseMid = 256 + 36;   // the two middle values of the median
 constexpr int kPoseInt = 256 + 40;   // ints: [0] solve outcome (0 ok, 1 degenerate), [1] sweeps, [2 .. 6) the waves' zero weights,
                                      //       [6 .. 10) their usable rows, [10 .. 14) their holes
 
-// The two middle values of rho[0 .. n) among its n_live smallest into mid[0], mid[1] (rig.hip's form of servo.hip's rank
-// counting: every value has a rank of its own and each cell one writer).
-__device__ __forceinline__ void pose_middles(const double* rho, int n, int n_live, double* mid, int tid) {
-    const int m_lo = (n_live - 1) >> 1, m_hi = n_live >> 1;
-    for (int i0 = tid; i0 < n; i0 += 4 * 256) {
-        long long ki[4];
-        int rank[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
-#pragma unroll 4
-        for (int j = 0; j < n; ++j) {
-            const long long kj = __double_as_longlong(rho[j]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (i0 + 256 * u < n && rank[u] == m_lo) mid[0] = __longlong_as_double(ki[u]);
-            if (i0 + 256 * u < n && rank[u] == m_hi) mid[1] = __longlong_as_double(ki[u]);
-        }
-    }
+// The handle's form of a point row (PoseArgs and PoseRigArgs name its arrays alike): row `row` = cam * ld + k of what camera `cam`'s
+// law left -> the current point p and the goal point g in that camera's frames.  Returns the flag: 1 usable, 0 padded, -1 a hole.
+template <class Args>
+__device__ __forceinline__ int pose_handle_row(const Args& a, int cam, size_t row, double (&p)[3], double (&g)[3]) {
+    const int tok = a.selected[row];
+    if (!(tok >= 0 && tok < a.T)) return 0;
+    const double Z = a.feat[row * 4 + 0], x = a.feat[row * 4 + 1], y = a.feat[row * 4 + 2];
+    const unsigned ds = a.zgoal[(size_t)cam * a.zgoal_stride + tok];
+    if (!(Z < 100.0 && ds != 0)) return -1;                 // a hole in either depth drops the row
+    const double fx = a.K[cam * 4 + 0], fy = a.K[cam * 4 + 1], cx = a.K[cam * 4 + 2], cy = a.K[cam * 4 + 3];
+    const double Zs = (double)ds / 1000.0;
+    const double xs = ((double)a.s_uv[row * 4 + 0] - cx) / fx, ys = ((double)a.s_uv[row * 4 + 1] - cy) / fy;
+    p[0] = Z * x; p[1] = Z * y; p[2] = Z;
+    g[0] = Zs * xs; g[1] = Zs * ys; g[2] = Zs;
+    return 1;
 }
 
 // One Jacobi rotation of the symmetric A in the (P, Q) plane, accumulated into V (eigenvectors in columns)
@@ -124,6 +121,137 @@ __device__ __forceinline__ bool pose_solve(const double* sm, double (&R)[9], dou
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[i] = cen[4 + i] - ((R[3 * i] * cen[1] + R[3 * i + 1] * cen[2]) + R[3 * i + 2] * cen[3]);
     return !(ev1 - ev2 <= 1e-8 * scatter);
+}
+
+// What pose_align leaves in every thread's registers
+struct PoseFit {
+    double R[9], t[3], q[4];
+    int status, sweeps, reweighted, n_zero, degenerate;
+    double sigma;
+};
+
+// The alignment loop, 256 threads: n_iter Tukey re-weightings (ROBUST; else none) and one more solve behind the last.  ws holds
+// P [3][stride] | Q [3][stride] | flag [stride]; rows [0, n) take part, n_us of them usable.  Every solve takes the weighted
+// centroids first and the centred sums second, each as quantities x 8 row slices (row r belongs to slice r mod 8, ascending rows,
+// the slices added in ascending order): bit-reproducible.  Wave 0 then solves and publishes R, t, q through LDS.  ROBUST: wk
+// (LDS) holds the caller's first weights on entry and the last ones on return; rho (LDS) holds +inf in every row that is not usable.
+// Every barrier here orders LDS only (lds_barrier): the loop writes nothing but LDS (smp, rho, wk).  The point block is global
+// memory, but the caller wrote it before the __syncthreads() that follows its Phase A, and the loop only reads it.
+template <bool ROBUST>
+__device__ __forceinline__ void pose_align(const double* ws, int stride, int n, int n_us, double sigma_min, int n_iter, double* smp,
+                                           double* rho, double* wk, PoseFit& fit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int qid = tid & 31, slice = tid >> 5;
+    const double* flag = ws + (size_t)6 * stride;
+    int* iscr = reinterpret_cast<int*>(smp + kPoseInt);
+    fit = PoseFit{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}, {1, 0, 0, 0}, ST_OK, 0, 0, 0, 0, 0.0};
+    const int N = ROBUST ? n_iter : 0;
+    for (int it = 0;; ++it) {
+        if (n_us - fit.n_zero < 3) { fit.status = ST_TOO_FEW; break; }
+        // the weighted centroids: sw, sum w P, sum w Q
+        if (qid < 7) {
+            double acc = 0.0;
+            for (int r = slice; r < n; r += 8) {
+                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
+                acc += qid == 0 ? w : w * ws[(size_t)(qid - 1) * stride + r];
+            }
+            smp[slice * 32 + qid] = acc;
+        }
+        lds_barrier();
+        if (tid < 7) {
+            double s = 0.0, s0 = 0.0;
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) { s += smp[sl * 32 + tid]; s0 += smp[sl * 32]; }
+            smp[kPoseCen + tid] = tid == 0 ? s : s / s0;
+        }
+        lds_barrier();
+        // the centred sums: S [9] = sum w (P - pc)(Q - qc)^T, sum w |P - pc|^2, sum w |Q - qc|^2
+        if (qid < 11) {
+            const double* cen = smp + kPoseCen;
+            const int ca = qid < 9 ? qid / 3 : 0, cb = qid < 9 ? qid % 3 : 0;
+            double acc = 0.0;
+            for (int r = slice; r < n; r += 8) {
+                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
+                double term;
+                if (qid < 9) {
+                    term = w * (ws[(size_t)ca * stride + r] - cen[1 + ca]) * (ws[(size_t)(3 + cb) * stride + r] - cen[4 + cb]);
+                } else {
+                    const int o = qid == 9 ? 0 : 3;
+                    const double d0 = ws[(size_t)o * stride + r] - cen[1 + o], d1 = ws[(size_t)(o + 1) * stride + r] - cen[2 + o],
+                                 d2 = ws[(size_t)(o + 2) * stride + r] - cen[3 + o];
+                    term = w * ((d0 * d0 + d1 * d1) + d2 * d2);
+                }
+                acc += term;
+            }
+            smp[slice * 32 + qid] = acc;
+        }
+        lds_barrier();
+        if (tid < 11) {
+            double s = 0.0;
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) s += smp[sl * 32 + tid];
+            smp[kPoseSum + tid] = s;
+        }
+        lds_barrier();
+        if (wave == 0) {
+            double Rn[9], tn[3], qn[4];
+            int sw;
+            const bool ok = pose_solve(smp, Rn, tn, qn, sw);
+            if (lane == 0) {
+                iscr[0] = ok ? 0 : 1;
+                iscr[1] = sw;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) smp[kPoseRt + i] = Rn[i];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) smp[kPoseRt + 9 + i] = tn[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) smp[kPoseRt + 12 + i] = qn[i];
+            }
+        }
+        lds_barrier();
+        fit.sweeps = iscr[1];
+        if (iscr[0]) { fit.degenerate = 1; fit.status = ST_TOO_FEW; break; }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) fit.R[i] = smp[kPoseRt + i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) fit.t[i] = smp[kPoseRt + 9 + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fit.q[i] = smp[kPoseRt + 12 + i];
+        if (it == N) break;
+        if constexpr (ROBUST) {
+            const double* R = fit.R;
+            const double* t = fit.t;
+            for (int k = tid; k < n; k += 256) {
+                if (!(flag[k] > 0.0)) continue;             // not a usable row: rho stays +inf
+                const double p0 = ws[k], p1 = ws[(size_t)stride + k], p2 = ws[(size_t)2 * stride + k];
+                const double d0 = ws[(size_t)3 * stride + k] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
+                const double d1 = ws[(size_t)4 * stride + k] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
+                const double d2 = ws[(size_t)5 * stride + k] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
+                rho[k] = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            }
+            lds_barrier();
+            median_middles(rho, n, n_us, smp + kPoseMid, tid);
+            lds_barrier();
+            fit.sigma = tukey_reweight<true>(rho, flag, n, smp + kPoseMid, sigma_min, wk, nullptr, iscr + 2, tid);
+            lds_barrier();
+            fit.n_zero = iscr[2] + iscr[3] + iscr[4] + iscr[5];
+            fit.reweighted = it + 1;
+        }
+    }
+}
+
+// v = -lambda (R^T t, theta u): ViSP's PBVS law on a fit whose status is ST_OK
+__device__ __forceinline__ void pose_twist(double lambda, const PoseFit& fit, double (&v)[6]) {
+    const double* R = fit.R;
+    const double* t = fit.t;
+    const double* q = fit.q;
+    const double nv = sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
+    const double f = nv == 0.0 ? 0.0 : 2.0 * atan2(nv, q[0]) / nv;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        v[i] = -lambda * ((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
+        v[3 + i] = -lambda * (f * q[1 + i]);
+    }
 }
 
 }  // namespace vitvs

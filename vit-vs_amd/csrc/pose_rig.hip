@@ -9,8 +9,8 @@
 // workgroup anyway, so nothing passes between workgroups.  Phase A strides the n_cams * ld stack rows (row i * ld + k: a fixed
 // layout) over the threads and writes P', Q' and the flag into a [7][n_cams * ld] block of global memory that this workgroup alone
 // writes and reads, behind __syncthreads(); rows a camera did not write and rows of cameras that do not contribute have flag 0.
-// The loop is then pose_kernel's with n = n_cams * ld: centroids and centred sums as quantities x 8 row slices, wave 0 solves,
-// ROBUST re-weights with ONE median over the usable rows of all contributing cameras.
+// The loop is then pose_core.h's pose_align over the n = n_cams * ld rows, as in the pose law: centroids and centred sums as
+// quantities x 8 row slices, wave 0 solves, ROBUST re-weights with ONE median over the usable rows of all contributing cameras.
 #include "common.h"
 #include "kernels.h"
 #include "pose_core.h"
@@ -72,19 +72,7 @@ __global__ __launch_bounds__(256) void pose_rig_kernel(PoseRigArgs a) {
                     for (int c = 0; c < 3; ++c) { p[c] = a.P[(size_t)r * 3 + c]; g[c] = a.Q[(size_t)r * 3 + c]; }
                 }
             } else if (k < min(max(a.info[(size_t)i * 8 + 1], 0), ld)) {
-                const int tok = a.selected[r];
-                if (tok >= 0 && tok < a.T) {
-                    const double Z = a.feat[(size_t)r * 4 + 0], x = a.feat[(size_t)r * 4 + 1], y = a.feat[(size_t)r * 4 + 2];
-                    const unsigned ds = a.zgoal[(size_t)i * a.zgoal_stride + tok];
-                    f = (Z < 100.0 && ds != 0) ? 1 : -1;    // a hole in either depth drops the row
-                    if (f > 0) {
-                        const double fx = a.K[i * 4 + 0], fy = a.K[i * 4 + 1], cx = a.K[i * 4 + 2], cy = a.K[i * 4 + 3];
-                        const double Zs = (double)ds / 1000.0;
-                        const double xs = ((double)a.s_uv[(size_t)r * 4 + 0] - cx) / fx, ys = ((double)a.s_uv[(size_t)r * 4 + 1] - cy) / fy;
-                        p[0] = Z * x; p[1] = Z * y; p[2] = Z;
-                        g[0] = Zs * xs; g[1] = Zs * ys; g[2] = Zs;
-                    }
-                }
+                f = pose_handle_row(a, i, (size_t)r, p, g);
             }
         }
         const double zs = g[2];                             // Z* in the camera's frame, for sigma_min's median
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(256) void pose_rig_kernel(PoseRigArgs a) {
         ws[(size_t)6 * n + r] = (double)f;
         if constexpr (ROBUST) {
             wk[r] = f > 0 ? 1.0 : 0.0;
-            rho[r] = f > 0 ? zs : __longlong_as_double((long long)kPoseInfBits);
+            rho[r] = f > 0 ? zs : __longlong_as_double((long long)kInfBits);
         }
         n_us += f > 0;
         holes += f < 0;
@@ -123,120 +111,15 @@ __global__ __launch_bounds__(256) void pose_rig_kernel(PoseRigArgs a) {
     double sigma_min = a.sigma_min;
     if constexpr (ROBUST) {
         if (a.K && n_us > 0) {
-            pose_middles(rho, n, n_us, smp + kPoseMid, tid);
+            median_middles(rho, n, n_us, smp + kPoseMid, tid);
             __syncthreads();
             sigma_min = 0.5 * pix * ((smp[kPoseMid] + smp[kPoseMid + 1]) * 0.5);
         }
         __syncthreads();
     }
 
-    const int qid = tid & 31, slice = tid >> 5;
-    int status = ST_OK, sweeps = 0, reweighted = 0, n_zero = 0, degenerate = 0;
-    double sigma = 0.0;
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0};
-    const int N = ROBUST ? a.n_iter : 0;
-    for (int it = 0;; ++it) {
-        if (n_us - n_zero < 3) { status = ST_TOO_FEW; break; }
-        // the weighted centroids: sw, sum w P', sum w Q'
-        if (qid < 7) {
-            double acc = 0.0;
-            for (int r = slice; r < n; r += 8) {
-                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
-                acc += qid == 0 ? w : w * ws[(size_t)(qid - 1) * n + r];
-            }
-            smp[slice * 32 + qid] = acc;
-        }
-        __syncthreads();
-        if (tid < 7) {
-            double s = 0.0, s0 = 0.0;
-#pragma unroll
-            for (int sl = 0; sl < 8; ++sl) { s += smp[sl * 32 + tid]; s0 += smp[sl * 32]; }
-            smp[kPoseCen + tid] = tid == 0 ? s : s / s0;
-        }
-        __syncthreads();
-        // the centred sums: S [9] = sum w (P' - pc)(Q' - qc)^T, sum w |P' - pc|^2, sum w |Q' - qc|^2
-        if (qid < 11) {
-            const double* cen = smp + kPoseCen;
-            const int ca = qid < 9 ? qid / 3 : 0, cb = qid < 9 ? qid % 3 : 0;
-            double acc = 0.0;
-            for (int r = slice; r < n; r += 8) {
-                const double w = ROBUST ? wk[r] : (flag[r] > 0.0 ? 1.0 : 0.0);
-                double term;
-                if (qid < 9) {
-                    term = w * (ws[(size_t)ca * n + r] - cen[1 + ca]) * (ws[(size_t)(3 + cb) * n + r] - cen[4 + cb]);
-                } else {
-                    const int o = qid == 9 ? 0 : 3;
-                    const double d0 = ws[(size_t)o * n + r] - cen[1 + o], d1 = ws[(size_t)(o + 1) * n + r] - cen[2 + o],
-                                 d2 = ws[(size_t)(o + 2) * n + r] - cen[3 + o];
-                    term = w * ((d0 * d0 + d1 * d1) + d2 * d2);
-                }
-                acc += term;
-            }
-            smp[slice * 32 + qid] = acc;
-        }
-        __syncthreads();
-        if (tid < 11) {
-            double s = 0.0;
-#pragma unroll
-            for (int sl = 0; sl < 8; ++sl) s += smp[sl * 32 + tid];
-            smp[kPoseSum + tid] = s;
-        }
-        __syncthreads();
-        if (wave == 0) {
-            double Rn[9], tn[3], qn[4];
-            int sw;
-            const bool ok = pose_solve(smp, Rn, tn, qn, sw);
-            if (lane == 0) {
-                iscr[0] = ok ? 0 : 1;
-                iscr[1] = sw;
-#pragma unroll
-                for (int i = 0; i < 9; ++i) smp[kPoseRt + i] = Rn[i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) smp[kPoseRt + 9 + i] = tn[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) smp[kPoseRt + 12 + i] = qn[i];
-            }
-        }
-        __syncthreads();
-        sweeps = iscr[1];
-        if (iscr[0]) { degenerate = 1; status = ST_TOO_FEW; break; }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = smp[kPoseRt + i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) t[i] = smp[kPoseRt + 9 + i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = smp[kPoseRt + 12 + i];
-        if (it == N) break;
-        if constexpr (ROBUST) {
-            for (int k = tid; k < n; k += 256) {
-                if (!(flag[k] > 0.0)) continue;             // not a usable row: rho stays +inf
-                const double p0 = ws[k], p1 = ws[(size_t)n + k], p2 = ws[(size_t)2 * n + k];
-                const double d0 = ws[(size_t)3 * n + k] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
-                const double d1 = ws[(size_t)4 * n + k] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
-                const double d2 = ws[(size_t)5 * n + k] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
-                rho[k] = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
-            }
-            __syncthreads();
-            pose_middles(rho, n, n_us, smp + kPoseMid, tid);
-            __syncthreads();
-            sigma = fmax(1.4826 * ((smp[kPoseMid] + smp[kPoseMid + 1]) * 0.5), sigma_min);
-            const double cs = 4.6851 * sigma;
-            int zeros = 0;
-            for (int k = tid; k < n; k += 256) {
-                const bool us = flag[k] > 0.0;
-                const double tt = rho[k] / cs;
-                const double u = 1.0 - tt * tt;
-                const double w1 = (us && tt < 1.0) ? u * u : 0.0;
-                wk[k] = w1;
-                zeros += (us && w1 == 0.0) ? 1 : 0;
-            }
-            zeros = wave_sum(zeros);
-            if (lane == 0) iscr[2 + wave] = zeros;
-            __syncthreads();
-            n_zero = iscr[2] + iscr[3] + iscr[4] + iscr[5];
-            reweighted = it + 1;
-        }
-    }
+    PoseFit fit;
+    pose_align<ROBUST>(ws, n, n, n_us, sigma_min, a.n_iter, smp, rho, wk, fit);
 
     if (a.weights) {
         for (int idx = tid; idx < a.n_cams * a.weights_stride; idx += 256) {
@@ -249,6 +132,7 @@ __global__ __launch_bounds__(256) void pose_rig_kernel(PoseRigArgs a) {
     // the raw sums of the final weights, for a rig spread over ranks (every exit of the loop left a barrier behind its last reads
     // of the slices)
     if (a.moments) {
+        const int qid = tid & 31, slice = tid >> 5;
         if (qid < 18) {
             double acc = 0.0;
             for (int r = slice; r < n; r += 8) {
@@ -279,31 +163,23 @@ __global__ __launch_bounds__(256) void pose_rig_kernel(PoseRigArgs a) {
         }
     }
     if (tid != 0) return;
-    const bool ok = status == ST_OK;
+    const bool ok = fit.status == ST_OK;
     double v[6] = {0, 0, 0, 0, 0, 0};
-    if (ok) {
-        const double nv = sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
-        const double f = nv == 0.0 ? 0.0 : 2.0 * atan2(nv, q[0]) / nv;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            v[i] = -a.lambda * ((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
-            v[3 + i] = -a.lambda * (f * q[1 + i]);
-        }
-    }
+    if (ok) pose_twist(a.lambda, fit, v);
 #pragma unroll
     for (int i = 0; i < 6; ++i) a.v_rig[i] = v[i];
-    *a.rig_status = status;
+    *a.rig_status = fit.status;
     if (a.pose) {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) a.pose[i] = ok ? R[i] : ((i & 3) == 0 ? 1.0 : 0.0);
+        for (int i = 0; i < 9; ++i) a.pose[i] = ok ? fit.R[i] : ((i & 3) == 0 ? 1.0 : 0.0);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) a.pose[9 + i] = ok ? t[i] : 0.0;
+        for (int i = 0; i < 3; ++i) a.pose[9 + i] = ok ? fit.t[i] : 0.0;
     }
-    if (a.sigma) *a.sigma = sigma;
+    if (a.sigma) *a.sigma = fit.sigma;
     if (a.rig_info) {
         int32_t* ri = a.rig_info;
-        ri[0] = n_contrib; ri[1] = n_us; ri[2] = sweeps; ri[3] = reweighted; ri[4] = n_zero; ri[5] = degenerate; ri[6] = holes;
-        ri[7] = worst;
+        ri[0] = n_contrib; ri[1] = n_us; ri[2] = fit.sweeps; ri[3] = fit.reweighted; ri[4] = fit.n_zero; ri[5] = fit.degenerate;
+        ri[6] = holes; ri[7] = worst;
     }
 }
 

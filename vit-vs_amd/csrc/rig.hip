@@ -200,13 +200,12 @@ int launch_rig(const RigArgs& a, hipStream_t stream, bool two_launches) {
 // allows both).  The cameras store their rows and e and nothing else: the first solve is weighted already (a zero-padded pair
 // has weight 0), so no camera's own 27 sums are of use.  The last arriver copies the stack ONCE with sc1 loads, into LDS when
 // n_cams * ld <= kRigRobustTile, else into `work` (which it alone writes and reads, plain accesses from there on), and runs
-// servo_kernel<true, .>'s loop on it: the 27 x 8-slice weighted sums (solve.h), wave 0's solve, the residuals, the median by
-// rank counting, the weights.  A pair that is not live carries rho = +inf from the start to the end: it ranks behind every live
+// the camera's robust loop on it, from the same functions: weighted_solve and pair_residuals (solve.h), median_middles and
+// tukey_reweight (robust_core.h).  A pair that is not live carries rho = +inf from the start to the end: it ranks behind every live
 // pair, takes weight 0 from the weight formula itself and is skipped by the residual pass.
 // dynamic LDS, in doubles: Gs [256] (solve.h's layout; [28 .. 34) x, [34] [35] the two middle residuals) | 4: the ticket drawn
 // and four counts as ints | tile [7][kRigRobustTile] when resident | rho [pairs] | w [pairs]
 constexpr int kRigRobustHead = 256 + 4;
-constexpr unsigned long long kInfBits = 0x7ff0000000000000ull;
 
 // rows (even) camera i contributes, its live pairs and its status
 __device__ __forceinline__ int rig_robust_camera(const RigRobustArgs& ra, int i, int& lv, int& st) {
@@ -217,43 +216,6 @@ __device__ __forceinline__ int rig_robust_camera(const RigRobustArgs& ra, int i,
     const int eff = (st == ST_OK && lv > 0) ? ri : 0;
     if (eff == 0) lv = 0;
     return eff;
-}
-
-// The two middle values of rho[0 .. n) among its n_live smallest into Gs[34], Gs[35]: rank counting as in servo.hip (integer
-// compares on the bit patterns of values >= +0, ties by index: every value has a rank of its own and each cell one writer).
-__device__ __forceinline__ void rig_robust_middles(const double* rho, int n, int n_live, double* Gs, int tid) {
-    const int m_lo = (n_live - 1) >> 1, m_hi = n_live >> 1;
-    if (n <= 256) {
-        if (tid < n) {
-            const long long ki = __double_as_longlong(rho[tid]);
-            int rank = 0;
-#pragma unroll 4
-            for (int j = 0; j < n; ++j) {
-                const long long kj = __double_as_longlong(rho[j]);
-                rank += (int)(kj < ki) | ((int)(kj == ki) & (int)(j < tid));
-            }
-            if (rank == m_lo) Gs[34] = __longlong_as_double(ki);
-            if (rank == m_hi) Gs[35] = __longlong_as_double(ki);
-        }
-    } else {
-        for (int i0 = tid; i0 < n; i0 += 4 * 256) {
-            long long ki[4];
-            int rank[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
-#pragma unroll 4
-            for (int j = 0; j < n; ++j) {
-                const long long kj = __double_as_longlong(rho[j]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (i0 + 256 * u < n && rank[u] == m_lo) Gs[34] = __longlong_as_double(ki[u]);
-                if (i0 + 256 * u < n && rank[u] == m_hi) Gs[35] = __longlong_as_double(ki[u]);
-            }
-        }
-    }
 }
 
 // RESIDENT: the stack's copy sits in LDS (the plan's lds_resident)
@@ -345,57 +307,16 @@ __global__ __launch_bounds__(256) void rig_robust_kernel(RigRobustArgs ra) {
             normal_equation_slices(Lc, rcap, total, wk, Gs, tid);
             lds_barrier();
             if (wave == 0) {
-                double xsol[6];
-                const bool solved = solve_ldlt(Gs, lane, xsol);
-                sweeps = -1;
-                if (!solved) {
-                    // each lane scales and copies the rows it alone rotates (r = lane mod 64)
-                    double* Lw = resident ? a.work : ra.work2;
-                    for (int r = lane; r < total; r += 64) {
-                        const double sw = sqrt(wk[r >> 1]);
-                        for (int c = 0; c < 7; ++c) Lw[(size_t)c * a.cap + r] = sw * Lc[(size_t)c * rcap + r];
-                    }
-                    sweeps = solve_jacobi(Lw, a.cap, total, lane, xsol);
-                }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    vout[i] = -a.lambda * xsol[i];
-                    if (lane == 0) Gs[28 + i] = xsol[i];
-                }
-                if (lane == 0) { Gs[34] = 0.0; Gs[35] = 0.0; }
+                double* Lw = resident ? a.work : ra.work2;
+                sweeps = weighted_solve(Lc, rcap, total, wk, Gs, Lw, a.cap, lane, a.lambda, vout);
             }
             if (it == N) break;
             lds_barrier();
-            double x[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) x[i] = Gs[28 + i];
-            for (int k = tid; k < P; k += 256) {
-                if ((unsigned long long)__double_as_longlong(rho[k]) == kInfBits) continue;    // not a live pair
-                double r0 = Lc[(size_t)6 * rcap + 2 * k], r1 = Lc[(size_t)6 * rcap + 2 * k + 1];
-                double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    p0 += Lc[(size_t)c * rcap + 2 * k] * x[c];
-                    p1 += Lc[(size_t)c * rcap + 2 * k + 1] * x[c];
-                }
-                r0 -= p0; r1 -= p1;
-                rho[k] = sqrt(r0 * r0 + r1 * r1);
-            }
+            pair_residuals<true>(Lc, rcap, P, Gs, rho, tid);
             lds_barrier();
-            rig_robust_middles(rho, P, n_live, Gs, tid);
+            median_middles(rho, P, n_live, Gs + 34, tid);
             lds_barrier();
-            sigma = fmax(1.4826 * ((Gs[34] + Gs[35]) * 0.5), sigma_min);
-            const double cs = 4.6851 * sigma;
-            int zeros = 0;
-            for (int k = tid; k < P; k += 256) {
-                const double t = rho[k] / cs;
-                const double u = 1.0 - t * t;
-                const double w1 = t < 1.0 ? u * u : 0.0;
-                wk[k] = w1;
-                zeros += w1 == 0.0 ? 1 : 0;
-            }
-            zeros = wave_sum(zeros);
-            if (lane == 0) iscr[1 + wave] = zeros;
+            sigma = tukey_reweight<false>(rho, nullptr, P, Gs + 34, sigma_min, wk, nullptr, iscr + 1, tid);
             lds_barrier();
             n_zero = iscr[1] + iscr[2] + iscr[3] + iscr[4];
             reweighted = it + 1;

@@ -353,94 +353,16 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
                 normal_equation_slices(Lc, rcap, R, wk, Gs, tid);
                 lds_barrier();
                 if (wave == 0) {
-                    double xsol[6];
-                    const bool solved = solve_ldlt(Gs, lane, xsol);
-                    sweeps = -1;
-                    if (!solved) {
-                        // each lane scales and copies the rows it alone rotates (r = lane mod 64)
-                        double* Lw = use_lds ? Lwk : a.L_work + (size_t)b * 7 * gcap;
-                        for (int r = lane; r < R; r += 64) {
-                            const double sw = sqrt(wk[r >> 1]);
-                            for (int c = 0; c < 7; ++c) Lw[(size_t)c * rcap + r] = sw * Lc[(size_t)c * rcap + r];
-                        }
-                        sweeps = solve_jacobi(Lw, rcap, R, lane, xsol);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        vout[i] = -a.lambda * xsol[i];
-                        if (lane == 0) Gs[28 + i] = xsol[i];
-                    }
-                    if (lane == 0) { Gs[34] = 0.0; Gs[35] = 0.0; }
+                    double* Lw = use_lds ? Lwk : a.L_work + (size_t)b * 7 * gcap;
+                    sweeps = weighted_solve(Lc, rcap, R, wk, Gs, Lw, rcap, lane, a.lambda, vout);
                 }
                 if (it == N) break;
                 lds_barrier();
-                // residual of every live pair
-                double x[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) x[i] = Gs[28 + i];
-                for (int k = tid; k < n; k += 256) {
-                    double r0 = Lc[6 * rcap + 2 * k], r1 = Lc[6 * rcap + 2 * k + 1];
-                    double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        p0 += Lc[c * rcap + 2 * k] * x[c];
-                        p1 += Lc[c * rcap + 2 * k + 1] * x[c];
-                    }
-                    r0 -= p0; r1 -= p1;
-                    rho[k] = sqrt(r0 * r0 + r1 * r1);
-                }
+                pair_residuals<false>(Lc, rcap, n, Gs, rho, tid);       // every pair below n is live
                 lds_barrier();
-                // median by rank counting: ties are ordered by index, so every value has its own rank; the two middle ranks
-                // (the same one for an odd count) each have exactly one writer
-                const int m_lo = (n - 1) >> 1, m_hi = n >> 1;
-                // (the residuals are >= +0, so their bit patterns order like their values: integer compares, no branches)
-                if (n <= 256) {
-                    if (tid < n) {
-                        const long long ki = __double_as_longlong(rho[tid]);
-                        int rank = 0;
-#pragma unroll 4
-                        for (int j = 0; j < n; ++j) {
-                            const long long kj = __double_as_longlong(rho[j]);
-                            rank += (int)(kj < ki) | ((int)(kj == ki) & (int)(j < tid));
-                        }
-                        if (rank == m_lo) Gs[34] = __longlong_as_double(ki);
-                        if (rank == m_hi) Gs[35] = __longlong_as_double(ki);
-                    }
-                } else {
-                    // dense selections rank thousands of values: 4 per thread and pass over the others
-                    for (int i0 = tid; i0 < n; i0 += 4 * 256) {
-                        long long ki[4];
-                        int rank[4] = {0, 0, 0, 0};
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) ki[u] = __double_as_longlong(rho[min(i0 + 256 * u, n - 1)]);
-#pragma unroll 4
-                        for (int j = 0; j < n; ++j) {
-                            const long long kj = __double_as_longlong(rho[j]);
-#pragma unroll
-                            for (int u = 0; u < 4; ++u)
-                                rank[u] += (int)(kj < ki[u]) | ((int)(kj == ki[u]) & (int)(j < i0 + 256 * u));
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if (i0 + 256 * u < n && rank[u] == m_lo) Gs[34] = __longlong_as_double(ki[u]);
-                            if (i0 + 256 * u < n && rank[u] == m_hi) Gs[35] = __longlong_as_double(ki[u]);
-                        }
-                    }
-                }
+                median_middles(rho, n, n, Gs + 34, tid);
                 lds_barrier();
-                const double sigma = fmax(1.4826 * ((Gs[34] + Gs[35]) * 0.5), sigma_min);
-                const double cs = 4.6851 * sigma;
-                int zeros = 0;
-                for (int k = tid; k < n; k += 256) {
-                    const double t = rho[k] / cs;
-                    const double u = 1.0 - t * t;
-                    const double w1 = t < 1.0 ? u * u : 0.0;
-                    wk[k] = w1;
-                    if (use_lds) Wg[k] = w1;
-                    zeros += w1 == 0.0 ? 1 : 0;
-                }
-                zeros = wave_sum(zeros);
-                if (lane == 0) iscr[8 + wave] = zeros;
+                tukey_reweight<false>(rho, nullptr, n, Gs + 34, sigma_min, wk, use_lds ? Wg : nullptr, iscr + 8, tid);
                 if (use_lds) lds_barrier();
                 else __syncthreads();
                 n_zero = iscr[8] + iscr[9] + iscr[10] + iscr[11] + (n_rows - n);

@@ -1,7 +1,9 @@
 // The fp64 solvers of the control laws: the 6x6 normal equations by LDL^T, and the one-sided Jacobi SVD behind a failed pivot.
-// Shared by servo.hip (one camera's law) and rig.hip (the rig law over the cameras' stacked rows).
+// Shared by servo.hip (one camera's law) and rig.hip (the rig law over the cameras' stacked rows); their robust laws also share
+// the weighted solve step and the pair-residual pass at the end of this file.
 #pragma once
 #include "common.h"
+#include "robust_core.h"
 
 #pragma clang fp contract(off)
 
@@ -170,6 +172,57 @@ __device__ __forceinline__ int solve_jacobi(double* Lc, int rcap, int R, int lan
         }
     }
     return sweeps;
+}
+
+// The weighted solve step of a robust law (servo_kernel<true, .>, rig_robust_kernel), wave 0 behind normal_equation_slices and a
+// barrier: LDL^T of the 6 x 6 system under the pair weights wk; behind a failed pivot the Jacobi SVD of a copy of the R rows of Lc
+// (capacity rcap) scaled by sqrt(w), in Lw (capacity wcap).  L and e themselves are never scaled.  Lane 0 publishes x in
+// Gs[28 .. 34) and clears the two median cells Gs[34], Gs[35]; vout = -lambda x in every lane.  Returns -1 when LDL^T solved, else
+// the Jacobi sweeps.  (x stays a local here: handed back through the caller's array it cost servo_kernel<true, true, .> eight
+// VGPRs and an occupancy step.)
+__device__ __forceinline__ int weighted_solve(const double* Lc, int rcap, int R, const double* wk, double* Gs, double* Lw, int wcap,
+                                              int lane, double lambda, double (&vout)[6]) {
+    double xsol[6];
+    const bool solved = solve_ldlt(Gs, lane, xsol);
+    int sweeps = -1;
+    if (!solved) {
+        // each lane scales and copies the rows it alone rotates (r = lane mod 64)
+        for (int r = lane; r < R; r += 64) {
+            const double sw = sqrt(wk[r >> 1]);
+            for (int c = 0; c < 7; ++c) Lw[(size_t)c * wcap + r] = sw * Lc[(size_t)c * rcap + r];
+        }
+        sweeps = solve_jacobi(Lw, wcap, R, lane, xsol);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        vout[i] = -lambda * xsol[i];
+        if (lane == 0) Gs[28 + i] = xsol[i];
+    }
+    if (lane == 0) { Gs[34] = 0.0; Gs[35] = 0.0; }
+    return sweeps;
+}
+
+// rho[k] = |e - L x| of pairs k < n (rows 2k, 2k + 1 of Lc), x = Gs[28 .. 34).  SKIP_INF: a pair whose rho is +inf is not live and
+// keeps it.
+template <bool SKIP_INF>
+__device__ __forceinline__ void pair_residuals(const double* Lc, int rcap, int n, const double* Gs, double* rho, int tid) {
+    double x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = Gs[28 + i];
+    for (int k = tid; k < n; k += 256) {
+        if constexpr (SKIP_INF) {
+            if ((unsigned long long)__double_as_longlong(rho[k]) == kInfBits) continue;
+        }
+        double r0 = Lc[6 * rcap + 2 * k], r1 = Lc[6 * rcap + 2 * k + 1];
+        double p0 = 0.0, p1 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            p0 += Lc[c * rcap + 2 * k] * x[c];
+            p1 += Lc[c * rcap + 2 * k + 1] * x[c];
+        }
+        r0 -= p0; r1 -= p1;
+        rho[k] = sqrt(r0 * r0 + r1 * r1);
+    }
 }
 
 }  // namespace vitvs
