@@ -446,6 +446,23 @@ VITVS_API int vitvs_homography_velocity(vitvs_handle* h, int32_t n_pairs, const 
                                         int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
                                         double* sigma);
 
+/* The homography law with a consensus start ("The consensus start"): n_hyp four-point hypotheses, each a closed-form
+ * homography of 4 usable rows drawn from `seed` (an integer hash of (seed, j, usable rows): the same frames give the same twist),
+ * are scored in parallel with the truncated cost sum min(rho^2, T^2), T = 4.6851 sigma_min; the rows within T of the winner start
+ * at weight 1 and the others at 0, and the law goes on from there as above (n_iter = 0: the DLT over the consensus set).  When
+ * every hypothesis is degenerate the start is the one without consensus.  h_info[6] = the winner's j + 1 (0: no consensus start),
+ * h_info[7] = the start weights at 1; h_info[3] counts the rows the consensus start left out as weights of 0.  n_hyp is 0 .. 4096;
+ * 0 is vitvs_homography_velocity_dev bit for bit.  Still one launch.  Returns as vitvs_homography_velocity_dev, and -2 also for
+ * n_hyp outside its range; -3 counts half a double per feature row more of LDS. */
+VITVS_API int vitvs_homography_consensus_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status,
+                                                      double depth_scale, int32_t n_iter, int32_t n_hyp, uint32_t seed, double* v_h,
+                                                      int32_t* h_status, double* H, int32_t* h_info, double* weights, double* sigma,
+                                                      void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous. */
+VITVS_API int vitvs_homography_consensus_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status,
+                                                  double depth_scale, int32_t n_iter, int32_t n_hyp, uint32_t seed, double* v_h,
+                                                  int32_t* h_status, double* H, int32_t* h_info, double* weights, double* sigma);
+
 /* --- the pose rig law ----------------------------------------------------------------------------
  * ONE rigid 3-D alignment over the matched points of ALL cameras of a rigid rig, for a rig whose cameras were the
  * pairs of the last law evaluation.  Camera i has pose (R_i, t_i) in the rig frame, X_rig = R_i X_cam + t_i (the (R, t) of

@@ -170,6 +170,20 @@ VITVS_API int vitvs_op_homography_scratch_bytes(int32_t n_pairs, int32_t ld);   
  * max_rows : 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out
  * NULL), -2 (max_rows < 1, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
 VITVS_API int vitvs_op_homography_plan(int32_t max_rows, int32_t n_iter, int32_t* out);
+/* vitvs_op_homography_law with the consensus start in front of its solve loop (vitvs_homography_consensus_velocity_dev,
+ * include/vitvs.h): n_hyp 0 .. 4096 four-point hypotheses drawn from `seed`; n_hyp = 0 is vitvs_op_homography_law bit for bit.
+ * The cut-off is T = 4.6851 sigma_min.  h_info[6] = the winner's j + 1 (0: n_hyp = 0, fewer than 4 usable rows, or every hypothesis
+ * skipped), h_info[7] = the start weights at 1.  Returns as vitvs_op_homography_law, and -2 also for n_hyp outside 0 .. 4096 and
+ * for n_hyp > 0 with sigma_min <= 0. */
+VITVS_API int vitvs_op_homography_consensus_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable,
+                                                double lambda, double depth_scale, int32_t n_iter, double sigma_min, void* scratch,
+                                                double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
+                                                double* sigma, void* stream, int32_t n_hyp, uint32_t seed);
+/* The launch plan with the consensus start: out[0] the dynamic LDS bytes = 8 (752 + (n_iter > 0 ? 2 max_rows : 0) + (n_hyp > 0 ?
+ * 8 + (max_rows + 1) / 2 : 0)): the reduction cells (4 costs, 4 + 4 ints) and the usable rows as ints, out[1] and out[2] as
+ * vitvs_op_homography_plan's, out[3] 1 for the consensus instantiation.  Returns 0, -1 (out NULL), -2 (as vitvs_op_homography_plan,
+ * or n_hyp outside 0 .. 4096; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
+VITVS_API int vitvs_op_homography_consensus_plan(int32_t max_rows, int32_t n_iter, int32_t n_hyp, int32_t* out);
 /* The pose rig law's kernel (vitvs_pose_rig_velocity_dev, include/vitvs.h) on caller-given camera-frame points:
  *   P, Q        device double [n_cams][ld][3];  usable int32 [n_cams][ld]: > 0 usable, 0 padded, < 0 a hole
  *   rTc         device double [n_cams][12]: R_i row-major, then t_i;  cam_status int32 [n_cams] or NULL (all VITVS_OK)

@@ -6,7 +6,11 @@ Times are HIP event pairs on the stream around ONE call (what a control loop wai
 p10 / p90 over --reps calls after a warm-up, and around --burst calls back to back divided by their number (the event pair's own
 cost amortised).  --rounds repeats everything, so the run-to-run spread of a line shows in one output.
 
-    python tools/homography_times.py [--reps 200] [--rounds 3] [--burst 50] [--out profiles/homography_law.txt]
+--consensus M adds a second leg behind every line: the same call with the consensus start of M four-point hypotheses in front of its
+solve loop (vitvs_op_homography_consensus_law), in the same run, so the legs without it are the yardstick; its output goes to
+profiles/homography_consensus.txt.
+
+    python tools/homography_times.py [--reps 200] [--rounds 3] [--burst 50] [--consensus M] [--out profiles/homography_law.txt]
 """
 import argparse
 import ctypes as C
@@ -48,12 +52,17 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--burst", type=int, default=50)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "homography_law.txt"))
+    ap.add_argument("--consensus", type=int, default=0, help="hypotheses of the consensus leg (0: no such leg)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "homography_consensus.txt" if args.consensus else "homography_law.txt")
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
     lines = [f"homography law (vitvs_op_homography_law), {torch.cuda.get_device_name(dev)}; HIP event pairs, microseconds"]
+    if args.consensus:
+        lines[0] += f"; 'consensus {args.consensus}' lines: vitvs_op_homography_consensus_law with that many hypotheses, seed 0"
     print(lines[0])
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     for rnd in range(args.rounds):
@@ -66,10 +75,15 @@ def main():
             H = torch.zeros((n, 9), dtype=torch.float64, device=dev)
             w = torch.zeros((n, rows), dtype=torch.float64, device=dev)
             sigma = torch.zeros(n, dtype=torch.float64, device=dev)
-            for n_iter in (0, 4):
-                call = lambda: lib.vitvs_op_homography_law(n, rows, p(m), p(ms), p(usable), 0.03, 0.61, n_iter, 0.004,  # noqa: E731
-                                                           p(scratch), p(v), p(st), p(H), p(info), p(w), p(sigma),
-                                                           C.c_void_p(stream.cuda_stream))
+            for n_iter, n_hyp in [(N, M) for N in (0, 4) for M in ((0, args.consensus) if args.consensus else (0,))]:
+                if n_hyp:
+                    call = lambda: lib.vitvs_op_homography_consensus_law(n, rows, p(m), p(ms), p(usable), 0.03, 0.61, n_iter, 0.004,  # noqa: E731
+                                                                         p(scratch), p(v), p(st), p(H), p(info), p(w), p(sigma),
+                                                                         C.c_void_p(stream.cuda_stream), n_hyp, 0)
+                else:
+                    call = lambda: lib.vitvs_op_homography_law(n, rows, p(m), p(ms), p(usable), 0.03, 0.61, n_iter, 0.004,  # noqa: E731
+                                                               p(scratch), p(v), p(st), p(H), p(info), p(w), p(sigma),
+                                                               C.c_void_p(stream.cuda_stream))
                 with torch.cuda.stream(stream):
                     for _ in range(20):
                         assert call() == 0
@@ -91,9 +105,12 @@ def main():
                     burst = 1000 * a.elapsed_time(b) / args.burst
                 i0 = info.cpu().numpy()[0]
                 assert not st.cpu().numpy().any()
-                line = (f"round {rnd} {n} x {rows:4d} rows, N = {n_iter}: median {np.median(us):7.2f} us, mean {np.mean(us):7.2f}, p10 "
+                leg = f", consensus {n_hyp}" if n_hyp else ""
+                line = (f"round {rnd} {n} x {rows:4d} rows, N = {n_iter}{leg}: median {np.median(us):7.2f} us, mean {np.mean(us):7.2f}, p10 "
                         f"{np.percentile(us, 10):7.2f}, p90 {np.percentile(us, 90):7.2f} over {len(us)} calls; {burst:7.2f} us per call in a "
                         f"burst of {args.burst}; pair 0: sweeps {int(i0[1])}, re-weightings {int(i0[2])}, zero weights {int(i0[3])}")
+                if n_hyp:
+                    line += f", winner {int(i0[6])}, start weights at 1: {int(i0[7])} of {int(i0[0])}"
                 print(line, flush=True)
                 lines.append(line)
     if args.out:

@@ -71,6 +71,8 @@ PROTOTYPES = {
     "vitvs_pose_velocity": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vitvs_homography_velocity_dev": (_I, [_P, _I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_homography_velocity": (_I, [_P, _I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
+    "vitvs_homography_consensus_velocity_dev": (_I, [_P, _I, _P, _P, C.c_double, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_homography_consensus_velocity": (_I, [_P, _I, _P, _P, C.c_double, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_rig_velocity_dev": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_rig_velocity": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_details": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -116,6 +118,9 @@ PROTOTYPES = {
     "vitvs_op_homography_law": (_I, [_I, _I, _P, _P, _P, C.c_double, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_homography_scratch_bytes": (_I, [_I, _I]),
     "vitvs_op_homography_plan": (_I, [_I, _I, _P]),
+    "vitvs_op_homography_consensus_law": (_I, [_I, _I, _P, _P, _P, C.c_double, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _I, C.c_uint32]),
+    "vitvs_op_homography_consensus_plan": (_I, [_I, _I, _I, _P]),
     "vitvs_op_pose_rig_law": (_I, [_I, _I, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_pose_rig_scratch_bytes": (_I, [_I, _I]),
     "vitvs_op_pose_rig_plan": (_I, [_I, _I, _I, _P]),

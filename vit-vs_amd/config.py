@@ -197,6 +197,10 @@ class ServoParams:
     homography_robust_iterations: int = 0  # Tukey re-weightings of the homography law (0 .. 16); 0 = the plain DLT
     homography_depth: float = 1.0  # the homography law's depth scale in metres (> 0): a rough guess of the distance to the target,
                                    # which scales its translational gain and nothing else
+    homography_consensus: int = 0  # four-point hypotheses of the homography law's consensus start (0 .. 4096): the law
+                                   # starts from the rows that agree with the best of them instead of from all rows; 0 = no such
+                                   # start.  256 fills one round of the kernel's workgroup
+    homography_consensus_seed: int = 0  # of the hypotheses' draw (0 .. 2^32 - 1); fixed across updates: same frames, same twist
 
     def __post_init__(self):
         if self.interaction not in INTERACTIONS:
@@ -211,6 +215,10 @@ class ServoParams:
             raise ValueError(f"homography_robust_iterations is 0 .. 16, got {self.homography_robust_iterations!r}")
         if not (float(self.homography_depth) > 0.0 and math.isfinite(float(self.homography_depth))):
             raise ValueError(f"homography_depth is a positive, finite length in metres, got {self.homography_depth!r}")
+        if not 0 <= int(self.homography_consensus) <= 4096:
+            raise ValueError(f"homography_consensus is 0 .. 4096, got {self.homography_consensus!r}")
+        if not 0 <= int(self.homography_consensus_seed) <= 0xFFFFFFFF:
+            raise ValueError(f"homography_consensus_seed is 0 .. 2^32 - 1, got {self.homography_consensus_seed!r}")
         if not 0 <= int(self.rig_robust_iterations) <= 16:
             raise ValueError(f"rig_robust_iterations is 0 .. 16, got {self.rig_robust_iterations!r}")
         if not 0 <= int(self.rig_pose_robust_iterations) <= 16:
@@ -274,8 +282,8 @@ def load_reference_config(source) -> ReferenceConfig:
     project's robust control law, no key of the reference's file) is taken when the mapping carries it, else 0; ``subpatch`` (the
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
     else "current"; ``law`` ("ibvs" / "pose" / "homography"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise,
-    else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``select_cells`` (the
-    cell grid of selection "best") likewise, else 4."""
+    else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``homography_consensus`` and
+    ``homography_consensus_seed`` likewise, else 0 and 0; ``select_cells`` (the cell grid of selection "best") likewise, else 4."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -298,12 +306,14 @@ def load_reference_config(source) -> ReferenceConfig:
                         rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)),
                         homography_robust_iterations=int(cfg.get("homography_robust_iterations", 0)),
                         homography_depth=float(cfg.get("homography_depth", 1.0)),
+                        homography_consensus=int(cfg.get("homography_consensus", 0)),
+                        homography_consensus_seed=int(cfg.get("homography_consensus_seed", 0)),
                         select_cells=int(cfg.get("select_cells", 4)))
     used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
-            "select_cells"}
+            "homography_consensus", "homography_consensus_seed", "select_cells"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -1808,46 +1808,64 @@ int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const
 }
 
 // --- the homography law --------------------------------------------------------------------------
-static int homography_prepare(vitvs_handle* h, int n_pairs, double depth_scale, int n_iter) {
+static int homography_prepare(vitvs_handle* h, int n_pairs, double depth_scale, int n_iter, int n_hyp = 0) {
     if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
+    if (n_hyp < 0 || n_hyp > 4096) return set_err(h, -2, "n_hyp is 0 .. 4096");
     if (!(depth_scale > 0.0) || !std::isfinite(depth_scale)) return set_err(h, -2, "depth_scale is a positive, finite length in metres");
     if (int rc = follows_velocity_call(h, "vitvs_homography_velocity", "n_pairs", n_pairs)) return rc;
     const vitvs_config& c = h->cfg;
     HomographyPlan pl;
-    if (plan_homography(c.max_rows, n_iter, &pl))
-        return set_err(h, -3, "the robust homography law keeps two doubles per feature row in LDS: max_rows is too large");
+    if (plan_homography(c.max_rows, n_iter, n_hyp, &pl))
+        return set_err(h, -3, "the robust homography law keeps two doubles per feature row in LDS, its consensus start half a double "
+                              "more: max_rows is too large");
     HomographyIo io = homography_io(c.max_pairs, c.max_rows);
     return law_blocks(h, "homography", &h->hom_ws, homography_scratch_bytes(c.max_pairs, c.max_rows), &h->hom_io,
                       io_place(io_list(io), nullptr));
 }
 
-int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
-                                  int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
-                                  double* sigma, void* stream) {
+int vitvs_homography_consensus_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status,
+                                            double depth_scale, int32_t n_iter, int32_t n_hyp, uint32_t seed, double* v_h,
+                                            int32_t* h_status, double* H, int32_t* h_info, double* weights, double* sigma,
+                                            void* stream) {
     if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
-    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
+    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter, n_hyp)) return rc;
     HomographyArgs a;
     memset(&a, 0, sizeof(a));
     a.n_pairs = n_pairs; a.ld = h->cfg.max_rows; a.status = status; a.ws = reinterpret_cast<double*>(h->hom_ws);
     camera_law_state(h, K, n_iter, a);
-    a.depth_scale = depth_scale;
+    a.depth_scale = depth_scale; a.n_hyp = n_hyp; a.seed = seed;
     a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info; a.weights = weights; a.sigma = sigma;
     const int rc = launch_homography(a, as_stream(stream));
     return rc ? set_err(h, rc, "homography law launch failed") : 0;
 }
 
+int vitvs_homography_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
+                                  int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
+                                  double* sigma, void* stream) {
+    return vitvs_homography_consensus_velocity_dev(h, n_pairs, K, status, depth_scale, n_iter, 0, 0, v_h, h_status, H, h_info, weights,
+                                                   sigma, stream);
+}
+
+int vitvs_homography_consensus_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
+                                        int32_t n_iter, int32_t n_hyp, uint32_t seed, double* v_h, int32_t* h_status, double* H,
+                                        int32_t* h_info, double* weights, double* sigma) {
+    if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter, n_hyp)) return rc;
+    HomographyIo io = homography_io(h->cfg.max_pairs, h->cfg.max_rows, n_pairs, K, status, v_h, h_status, H, h_info, weights, sigma);
+    return host_call(h, io_list(io), h->hom_io, [&](hipStream_t st) {
+        return vitvs_homography_consensus_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), depth_scale, n_iter, n_hyp, seed,
+                                                       io.v_h.f64(), io.h_status.i32(), io.H.f64(), io.h_info.i32(),
+                                                       io.weights.f64(), io.sigma.f64(), st);
+    });
+}
+
 int vitvs_homography_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, double depth_scale,
                               int32_t n_iter, double* v_h, int32_t* h_status, double* H, int32_t* h_info, double* weights,
                               double* sigma) {
-    if (!h || !K || !status || !v_h || !h_status) return set_err(h, -1, "null argument");
-    DeviceScope dev(h);
-    if (int rc = homography_prepare(h, n_pairs, depth_scale, n_iter)) return rc;
-    HomographyIo io = homography_io(h->cfg.max_pairs, h->cfg.max_rows, n_pairs, K, status, v_h, h_status, H, h_info, weights, sigma);
-    return host_call(h, io_list(io), h->hom_io, [&](hipStream_t st) {
-        return vitvs_homography_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), depth_scale, n_iter, io.v_h.f64(),
-                                             io.h_status.i32(), io.H.f64(), io.h_info.i32(), io.weights.f64(), io.sigma.f64(), st);
-    });
+    return vitvs_homography_consensus_velocity(h, n_pairs, K, status, depth_scale, n_iter, 0, 0, v_h, h_status, H, h_info, weights,
+                                               sigma);
 }
 
 // --- the pose rig law ----------------------------------------------------------------------------
@@ -2141,18 +2159,27 @@ int vitvs_op_pose_rig_plan(int32_t n_cams, int32_t ld, int32_t n_iter, int32_t* 
     return plan_out(plan_pose_rig(n_cams, ld, n_iter, &pl), pl, out);
 }
 
-int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable, double lambda,
-                            double depth_scale, int32_t n_iter, double sigma_min, void* scratch, double* v_h, int32_t* h_status,
-                            double* H, int32_t* h_info, double* weights, double* sigma, void* stream) {
+int vitvs_op_homography_consensus_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable,
+                                      double lambda, double depth_scale, int32_t n_iter, double sigma_min, void* scratch, double* v_h,
+                                      int32_t* h_status, double* H, int32_t* h_info, double* weights, double* sigma, void* stream,
+                                      int32_t n_hyp, uint32_t seed) {
     if (!m || !ms || !usable || !scratch || !v_h || !h_status) return -1;
     if (n_pairs < 1 || ld < 1 || n_iter < 0 || n_iter > 16 || !(depth_scale > 0.0) || !std::isfinite(depth_scale)) return -2;
+    if (n_hyp < 0 || n_hyp > 4096 || (n_hyp > 0 && !(sigma_min > 0.0))) return -2;
     HomographyArgs a;
     memset(&a, 0, sizeof(a));
     a.n_pairs = n_pairs; a.ld = ld; a.m = m; a.ms = ms; a.usable = usable; a.lambda = lambda; a.depth_scale = depth_scale;
-    a.n_iter = n_iter; a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch);
+    a.n_iter = n_iter; a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch); a.n_hyp = n_hyp; a.seed = seed;
     a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info;
     a.weights = weights; a.weights_stride = ld; a.sigma = sigma;
     return launch_homography(a, as_stream(stream));
+}
+
+int vitvs_op_homography_law(int32_t n_pairs, int32_t ld, const double* m, const double* ms, const int32_t* usable, double lambda,
+                            double depth_scale, int32_t n_iter, double sigma_min, void* scratch, double* v_h, int32_t* h_status,
+                            double* H, int32_t* h_info, double* weights, double* sigma, void* stream) {
+    return vitvs_op_homography_consensus_law(n_pairs, ld, m, ms, usable, lambda, depth_scale, n_iter, sigma_min, scratch, v_h,
+                                             h_status, H, h_info, weights, sigma, stream, 0, 0);
 }
 
 int vitvs_op_homography_scratch_bytes(int32_t n_pairs, int32_t ld) {
@@ -2163,7 +2190,16 @@ int vitvs_op_homography_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
     if (!out) return -1;
     HomographyPlan pl;
     memset(&pl, 0, sizeof(pl));
-    return plan_out(plan_homography(max_rows, n_iter, &pl), pl, out);
+    return plan_out(plan_homography(max_rows, n_iter, 0, &pl), pl, out);
+}
+
+int vitvs_op_homography_consensus_plan(int32_t max_rows, int32_t n_iter, int32_t n_hyp, int32_t* out) {
+    if (!out) return -1;
+    HomographyPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_out(plan_homography(max_rows, n_iter, n_hyp, &pl), pl, out);
+    out[3] = pl.consensus;
+    return rc;
 }
 
 int vitvs_op_rig_two_launches(int32_t on) {

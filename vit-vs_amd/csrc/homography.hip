@@ -12,7 +12,8 @@
 // bit-reproducible.  Wave 0 then runs the cyclic Jacobi eigen-decomposition of M with M and V (162 doubles) in LDS: every lane
 // computes the same rotation, lanes 0 .. 8 turn the rows of M and lanes 16 .. 24 the rows of V, in the reference's order of
 // arithmetic.  ROBUST: n_iter Tukey re-weightings on the transfer error with rho and w in dynamic LDS (median_middles and
-// tukey_reweight of robust_core.h), one more solve behind the last.
+// tukey_reweight of robust_core.h), one more solve behind the last.  CONSENSUS: a phase between Phase A and the solve loop scores
+// n_hyp four-point hypotheses, one per thread and round, and starts the loop from the winner's consensus set (below, at hom_draw).
 #include "common.h"
 #include "kernels.h"
 #include "robust_core.h"
@@ -22,7 +23,8 @@
 
 namespace vitvs {
 
-// dynamic LDS in doubles: slices [8][64] | the results below | ROBUST: rho [ld] | w [ld]
+// dynamic LDS in doubles: slices [8][64] | the results below | ROBUST: rho [ld] | w [ld] | CONSENSUS: the waves' best costs [4],
+// as ints their best j [4] and their start weights at 1 [4] | as ints the usable rows in ascending order [ld, rounded up to even]
 constexpr int kHomSum = 8 * 64;          // [0 .. 45): the upper triangle of M, row-major
 constexpr int kHomCen = kHomSum + 48;    // sw, c [2], c* [2], dbar, dbar*, trace(M)
 constexpr int kHomA = kHomCen + 8;       // M [9][9], turned in place
@@ -32,6 +34,7 @@ constexpr int kHomMid = kHomH + 12;      // the two middle values of the median
 constexpr int kHomInt = kHomMid + 2;     // ints: [0] solve outcome (0 ok, 1 degenerate), [1] sweeps, [2 .. 6) the waves' zero weights,
                                          //       [6 .. 10) their usable rows, [10 .. 14) their rows with rho = inf
 constexpr int kHomHead = kHomInt + 8;
+constexpr int kHomCons = 8;              // doubles of the consensus cells in front of the usable-row list
 
 // Orders the LDS traffic of ONE wave: its lanes run in lock step and the LDS serves a wave's accesses in issue order, so this
 // only has to keep the compiler from moving them.
@@ -155,7 +158,178 @@ __device__ __forceinline__ bool hom_solve(double* sm, int lane, int& sweeps) {
     return ok;
 }
 
+// ---- the consensus start ("The consensus start"); tests/homography_consensus_ref.py restates every line below in
+// the same order of arithmetic
+__device__ __forceinline__ unsigned hom_mix(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The 4 distinct positions of hypothesis j in a list of n_us usable rows, ascending (a row set gives one H whatever the order it was
+// drawn in): r_c = mix(mix(seed 0x9e3779b9 + j) + c) mod n_us for c = 0 .. 63, repeats rejected; false when 64 draws do not give 4.
+__device__ __forceinline__ bool hom_draw(unsigned seed, int j, int n_us, int* pos) {
+    const unsigned base = hom_mix(seed * 0x9e3779b9u + (unsigned)j);
+    int p0 = -1, p1 = -1, p2 = -1, p3 = -1, cnt = 0;
+    for (unsigned c = 0; c < 64u && cnt < 4; ++c) {
+        const int r = (int)(hom_mix(base + c) % (unsigned)n_us);
+        if (r == p0 || r == p1 || r == p2 || r == p3) continue;
+        if (cnt == 0) p0 = r; else if (cnt == 1) p1 = r; else if (cnt == 2) p2 = r; else p3 = r;
+        ++cnt;
+    }
+    if (cnt < 4) return false;
+    int t;
+#define HOM_CSWAP(a, b) if (b < a) { t = a; a = b; b = t; }
+    HOM_CSWAP(p0, p1) HOM_CSWAP(p2, p3) HOM_CSWAP(p0, p2) HOM_CSWAP(p1, p3) HOM_CSWAP(p1, p2)
+#undef HOM_CSWAP
+    pos[0] = p0; pos[1] = p1; pos[2] = p2; pos[3] = p3;
+    return true;
+}
+
+// B = A diag(adj(A) (x3, y3, 1)), A with the columns (x_i, y_i, 1), i = 0 .. 2: the map of the projective basis onto four points.
+// The l_i and their sum (det A) are twice the signed areas of the four triangles of the points: false when one of them is <= 1e-8
+// of the squared extent, i.e. three points are collinear (of four collinear points every l_i is rounding noise, and so would be H
+// and its determinant: the rule on det H cannot see that case).
+__device__ __forceinline__ bool hom_basis(const double* x, const double* y, double* B) {
+    const double l0 = ((y[1] - y[2]) * x[3] + (x[2] - x[1]) * y[3]) + (x[1] * y[2] - x[2] * y[1]);
+    const double l1 = ((y[2] - y[0]) * x[3] + (x[0] - x[2]) * y[3]) + (x[2] * y[0] - x[0] * y[2]);
+    const double l2 = ((y[0] - y[1]) * x[3] + (x[1] - x[0]) * y[3]) + (x[0] * y[1] - x[1] * y[0]);
+    B[0] = x[0] * l0; B[1] = x[1] * l1; B[2] = x[2] * l2;
+    B[3] = y[0] * l0; B[4] = y[1] * l1; B[5] = y[2] * l2;
+    B[6] = l0; B[7] = l1; B[8] = l2;
+    const double ex = fmax(fmax(x[0], x[1]), fmax(x[2], x[3])) - fmin(fmin(x[0], x[1]), fmin(x[2], x[3]));
+    const double ey = fmax(fmax(y[0], y[1]), fmax(y[2], y[3])) - fmin(fmin(y[0], y[1]), fmin(y[2], y[3]));
+    const double ext = ex + ey;
+    const double area = fmin(fmin(fabs(l0), fabs(l1)), fmin(fabs(l2), fabs((l0 + l1) + l2)));
+    return area > 1e-8 * (ext * ext);
+}
+
+// The homography of the four usable rows `rows` in closed form, H = B(m*) adj(B(m)) on the raw normalised points, with the sign
+// that makes det H > 0 (what the law's det-1 scaling does); false when three of the points are collinear in either image, an entry
+// is not finite or |det H| <= 1e-8 |H|_F^3
+__device__ __forceinline__ bool hom_four_point(const double* ws, int ld, const int* rows, double* H) {
+    double x[4], y[4], xs[4], ys[4], B[9], S[9], J[9];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[i] = ws[rows[i]]; y[i] = ws[(size_t)ld + rows[i]];
+        xs[i] = ws[(size_t)2 * ld + rows[i]]; ys[i] = ws[(size_t)3 * ld + rows[i]];
+    }
+    const bool spread = hom_basis(x, y, B), spread_s = hom_basis(xs, ys, S);
+    J[0] = B[4] * B[8] - B[5] * B[7]; J[1] = B[2] * B[7] - B[1] * B[8]; J[2] = B[1] * B[5] - B[2] * B[4];
+    J[3] = B[5] * B[6] - B[3] * B[8]; J[4] = B[0] * B[8] - B[2] * B[6]; J[5] = B[2] * B[3] - B[0] * B[5];
+    J[6] = B[3] * B[7] - B[4] * B[6]; J[7] = B[1] * B[6] - B[0] * B[7]; J[8] = B[0] * B[4] - B[1] * B[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) H[3 * i + k] = (S[3 * i] * J[k] + S[3 * i + 1] * J[3 + k]) + S[3 * i + 2] * J[6 + k];
+    const double det = (H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6])) + H[2] * (H[3] * H[7] - H[4] * H[6]);
+    double fro2 = 0.0;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        fro2 += H[k] * H[k];
+        finite = finite && fabs(H[k]) < __builtin_huge_val();
+    }
+    const double fro = sqrt(fro2);
+    if (!spread || !spread_s || !finite || !(fabs(det) > 1e-8 * (fro * fro * fro))) return false;
+    if (det < 0.0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) H[k] = -H[k];
+    }
+    return true;
+}
+
+// The squared transfer error of row r under H: |pi(H m) - m*|^2, or +inf where the third component of H m is <= 0
+__device__ __forceinline__ double hom_transfer_sq(const double* H, const double* ws, int ld, int r) {
+    const double x = ws[r], y = ws[(size_t)ld + r];
+    const double X = (H[0] * x + H[1] * y) + H[2], Y = (H[3] * x + H[4] * y) + H[5], Z = (H[6] * x + H[7] * y) + H[8];
+    if (!(Z > 0.0)) return __longlong_as_double((long long)kInfBits);
+    const double d0 = X / Z - ws[(size_t)2 * ld + r], d1 = Y / Z - ws[(size_t)3 * ld + r];
+    return d0 * d0 + d1 * d1;
+}
+
+// The consensus phase, all 256 threads, behind Phase A's barrier and with n_us >= 4.  Thread t scores the hypotheses t, t + 256, ..
+// with the truncated cost C_j = sum over the usable rows, ascending, of min(rho^2, T^2) (T = 4.6851 sigma_min; a skipped
+// hypothesis costs +inf) and keeps its best (cost, j) in registers; costs are >= +0, so (cost bits, j) orders by integer compares
+// and ties go to the smallest j.  One reduction: a butterfly within each wave, then 4 cells in LDS.  Every thread then solves
+// the winner again and the start weights are 1 where rho <= T and 0 elsewhere, into `start` (LDS for the robust form, the flags'
+// row of the workspace for the plain one).  Returns the winner's j + 1 and the number of start weights at 1, or 0 and n_us when
+// every hypothesis was skipped (the weights stay at 1: the start without consensus).  The caller's barrier follows.
 template <bool ROBUST>
+__device__ __forceinline__ int hom_consensus(const HomographyArgs& a, double* ws, double* cons, double* start, int n, int n_us,
+                                             double sigma_min, int tid, int& n_start) {
+    const int lane = tid & 63, wave = tid >> 6, ld = a.ld;
+    unsigned long long* cell_cost = reinterpret_cast<unsigned long long*>(cons);
+    int* cell_j = reinterpret_cast<int*>(cons + 4);
+    int* cell_ones = cell_j + 4;
+    int* list = reinterpret_cast<int*>(cons + kHomCons);
+    const double* flag = ws + (size_t)4 * ld;
+    if (wave == 0) {                                        // the usable rows in ascending order: wave 0, 64 rows a step
+        int base = 0;
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int k = k0 + lane;
+            const bool f = k < n && flag[k] > 0.0;
+            const unsigned long long bal = __ballot(f);
+            if (f) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = k;
+            base += __popcll(bal);
+        }
+    }
+    lds_barrier();
+    const double T = 4.6851 * sigma_min, T2 = T * T;
+    unsigned long long best = kInfBits;
+    int best_j = 0x7fffffff;
+    for (int j = tid; j < a.n_hyp; j += 256) {
+        int pos[4], rows[4];
+        double H[9];
+        if (!hom_draw(a.seed, j, n_us, pos)) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rows[i] = list[pos[i]];
+        if (!hom_four_point(ws, ld, rows, H)) continue;
+        double cost = 0.0;
+        for (int p = 0; p < n_us; ++p) {                    // (every lane reads the same row: one broadcast load each)
+            const double q = hom_transfer_sq(H, ws, ld, list[p]);
+            cost += q < T2 ? q : T2;
+        }
+        const unsigned long long key = (unsigned long long)__double_as_longlong(cost);
+        if (key < best) { best = key; best_j = j; }         // (j ascends: a tie keeps the smaller one)
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long oc = shfl_xor_u64(best, o);
+        const int oj = __shfl_xor(best_j, o, WAVE);
+        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
+    }
+    if (lane == 0) { cell_cost[wave] = best; cell_j[wave] = best_j; }
+    lds_barrier();
+    best = cell_cost[0]; best_j = cell_j[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const unsigned long long oc = cell_cost[w];
+        const int oj = cell_j[w];
+        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
+    }
+    if (best >= kInfBits) { n_start = n_us; return 0; }     // every hypothesis skipped: the same for every thread
+    int pos[4], rows[4], ones = 0;
+    double H[9];
+    hom_draw(a.seed, best_j, n_us, pos);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rows[i] = list[pos[i]];
+    hom_four_point(ws, ld, rows, H);
+    for (int k = tid; k < n; k += 256) {
+        if (!(flag[k] > 0.0)) continue;
+        const double w1 = sqrt(hom_transfer_sq(H, ws, ld, k)) <= T ? 1.0 : 0.0;
+        start[k] = w1;
+        ones += w1 > 0.0 ? 1 : 0;
+    }
+    ones = wave_sum(ones);
+    if (lane == 0) cell_ones[wave] = ones;
+    if constexpr (ROBUST) lds_barrier(); else __syncthreads();    // (the plain form's start weights are global memory: full fence)
+    n_start = cell_ones[0] + cell_ones[1] + cell_ones[2] + cell_ones[3];
+    return best_j + 1;
+}
+
+template <bool ROBUST, bool CONSENSUS>
 __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smh[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -234,6 +408,14 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
     const int qid = tid & 31, slice = tid >> 5;
     int status = ST_OK, sweeps = 0, reweighted = 0, n_zero = 0, degenerate = 0, n_inf = 0;
     double sigma = 0.0;
+    int winner = 0, n_start = 0;
+    if constexpr (CONSENSUS) {
+        if (n_us >= 4) {
+            winner = hom_consensus<ROBUST>(a, ws, rho + (ROBUST ? 2 * ld : 0), ROBUST ? wk : ws + (size_t)4 * ld, n, n_us, sigma_min,
+                                           tid, n_start);
+            if (winner) n_zero = n_us - n_start;            // the rows outside the consensus set start at weight 0
+        }
+    }
     const int N = ROBUST ? a.n_iter : 0;
     for (int it = 0;; ++it) {
         if (n_us - n_zero < 4) { status = ST_TOO_FEW; break; }
@@ -383,14 +565,17 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
     if (a.sigma) a.sigma[b] = sigma;
     if (a.h_info) {
         int32_t* hi = a.h_info + (size_t)b * 8;
-        hi[0] = n_us; hi[1] = sweeps; hi[2] = reweighted; hi[3] = n_zero; hi[4] = degenerate; hi[5] = n_inf; hi[6] = 0; hi[7] = 0;
+        hi[0] = n_us; hi[1] = sweeps; hi[2] = reweighted; hi[3] = n_zero; hi[4] = degenerate; hi[5] = n_inf;
+        hi[6] = CONSENSUS ? winner : 0; hi[7] = CONSENSUS ? n_start : 0;
     }
 }
 
-int plan_homography(int max_rows, int n_iter, HomographyPlan* plan) {
-    if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16) return -2;
+int plan_homography(int max_rows, int n_iter, int n_hyp, HomographyPlan* plan) {
+    if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16 || n_hyp < 0 || n_hyp > 4096) return -2;
     plan->robust = n_iter > 0;
-    plan->lds = ((size_t)kHomHead + (plan->robust ? (size_t)2 * max_rows : 0)) * sizeof(double);
+    plan->consensus = n_hyp > 0;
+    plan->lds = ((size_t)kHomHead + (plan->robust ? (size_t)2 * max_rows : 0) +
+                 (plan->consensus ? (size_t)kHomCons + ((size_t)max_rows + 1) / 2 : 0)) * sizeof(double);
     plan->lds_opt_in = plan->lds > 64 * 1024;
     return plan->lds > 160 * 1024 ? -3 : 0;
 }
@@ -402,13 +587,20 @@ int launch_homography(const HomographyArgs& a, hipStream_t stream) {
     if (a.m ? (!a.ms || !a.usable) : (!a.selected || !a.s_uv || !a.feat || !a.info || !a.K)) return -2;
     if (!(a.depth_scale > 0.0) || !(a.depth_scale < __builtin_huge_val())) return -2;
     HomographyPlan p;
-    if (int rc = plan_homography(a.ld, a.n_iter, &p)) return rc;
-    static std::atomic<unsigned long long> raised{0};
-    if (p.robust) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<true>), 160 * 1024, raised)) return -3;
-        launch(homography_kernel<true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    if (int rc = plan_homography(a.ld, a.n_iter, a.n_hyp, &p)) return rc;
+    if (p.consensus && !a.K && !(a.sigma_min > 0.0)) return -2;      // the cut-off T = 4.6851 sigma_min has to be positive
+    static std::atomic<unsigned long long> raised{0}, raised_rc{0}, raised_c{0};
+    if (p.robust && p.consensus) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<true, true>), 160 * 1024, raised_rc)) return -3;
+        launch(homography_kernel<true, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    } else if (p.consensus) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<false, true>), 160 * 1024, raised_c)) return -3;
+        launch(homography_kernel<false, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    } else if (p.robust) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<true, false>), 160 * 1024, raised)) return -3;
+        launch(homography_kernel<true, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
     } else {
-        launch(homography_kernel<false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+        launch(homography_kernel<false, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

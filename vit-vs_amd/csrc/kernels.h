@@ -548,7 +548,8 @@ int launch_pose_rig(const PoseRigArgs& a, hipStream_t stream);
 // normalisation, the 9 x 9 DLT normal matrix, its smallest eigenvector by a cyclic Jacobi, det H = 1), and Benhimane and Malis'
 // twist v_h = -lambda (depth_scale (H - I) m_c, (H21 - H12, H02 - H20, H10 - H01)).  No depth takes part.  One launch, one
 // workgroup per pair.  The points come from what the camera's law left (selected, s_uv, feat, info) or, for the seam tests, from
-// the caller (m, ms, usable).
+// the caller (m, ms, usable).  n_hyp > 0: the consensus start, n_hyp four-point hypotheses scored in parallel in front of the solve
+// loop, which then starts from the winner's consensus set instead of every usable row.
 struct HomographyArgs {
     int n_pairs;
     int ld;                   // rows per pair of every per-row array (max_rows)
@@ -576,18 +577,24 @@ struct HomographyArgs {
                               // or degenerate
     double* H;                // [n_pairs][9] or null: row-major, det 1 (identity when the twist is zero)
     int32_t* h_info;          // [n_pairs][8] or null: usable rows, sweeps of the last solve, re-weightings, usable rows at weight 0,
-                              // degenerate, rows with rho = inf at the last re-weighting, 0, 0
+                              // degenerate, rows with rho = inf at the last re-weighting, the consensus winner's j + 1 (0: consensus
+                              // off, not run for fewer than 4 usable rows, or every hypothesis skipped), the start weights at 1
     double* weights;          // [n_pairs][weights_stride] or null
     int weights_stride;
     double* sigma;            // [n_pairs] or null: the last scale
+    // the consensus start (behind everything the kernel read before it had one)
+    int n_hyp;                // hypotheses, 0 .. 4096; 0: no consensus phase, the kernel is the one without it
+    unsigned seed;            // of the draw; the positions depend on (seed, j, usable rows) only
 };
 struct HomographyPlan {
-    size_t lds;               // dynamic LDS of the launch: (752 + (robust ? 2 max_rows : 0)) doubles
-    bool robust;              // homography_kernel<robust>
+    size_t lds;               // dynamic LDS of the launch: (752 + (robust ? 2 max_rows : 0) + (consensus ? 8 + (max_rows + 1) / 2 : 0))
+                              // doubles
+    bool robust;              // homography_kernel<robust, consensus>
     bool lds_opt_in;          // > 64 KiB
+    bool consensus;
 };
-// -2: max_rows < 1, n_iter outside 0 .. 16; -3 (plan filled): more than 160 KiB of LDS
-int plan_homography(int max_rows, int n_iter, HomographyPlan* plan);
+// -2: max_rows < 1, n_iter outside 0 .. 16, n_hyp outside 0 .. 4096; -3 (plan filled): more than 160 KiB of LDS
+int plan_homography(int max_rows, int n_iter, int n_hyp, HomographyPlan* plan);
 size_t homography_scratch_bytes(int n_pairs, int ld);
 int launch_homography(const HomographyArgs& a, hipStream_t stream);
 

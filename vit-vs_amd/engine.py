@@ -630,21 +630,29 @@ class Engine:
     HOMOGRAPHY_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "behind")
 
     @staticmethod
-    def _homography_arguments(depth_scale, robust_iterations):
+    def _homography_arguments(depth_scale, robust_iterations, consensus=0, seed=0):
         """The checks of the homography law's arguments (no handle needed)."""
         N = Engine._robust_iterations(robust_iterations)
         z = float(depth_scale)
         if not (z > 0.0 and math.isfinite(z)):
             raise ValueError(f"depth_scale is a positive, finite length in metres, got {depth_scale!r}")
-        return z, N
+        M, s = int(consensus), int(seed)
+        if not 0 <= M <= 4096:
+            raise ValueError(f"consensus is 0 .. 4096 hypotheses, got {consensus!r}")
+        if not 0 <= s <= 0xFFFFFFFF:
+            raise ValueError(f"seed is 0 .. 2^32 - 1, got {seed!r}")
+        return z, N, M, s
 
-    def _homography_law(self, host, K, status, depth_scale, robust_iterations):
-        z, N = self._homography_arguments(depth_scale, robust_iterations)
-        v, hst, H, hinfo, weights, sigma = self._pair_law("vitvs_homography_velocity", host, K, status, (z, N), 9)
+    def _homography_law(self, host, K, status, depth_scale, robust_iterations, consensus=0, seed=0):
+        z, N, M, s = self._homography_arguments(depth_scale, robust_iterations, consensus, seed)
+        if M:
+            v, hst, H, hinfo, weights, sigma = self._pair_law("vitvs_homography_consensus_velocity", host, K, status, (z, N, M, s), 9)
+        else:
+            v, hst, H, hinfo, weights, sigma = self._pair_law("vitvs_homography_velocity", host, K, status, (z, N), 9)
         return v, self._law_info(self.HOMOGRAPHY_INFO_FIELDS, hinfo, True, status=hst, H=H.reshape(len(hst), 3, 3), weights=weights,
-                                 sigma=sigma)
+                                 sigma=sigma, winner=hinfo[:, 6], start_weights=hinfo[:, 7])
 
-    def homography_velocity(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
+    def homography_velocity(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0, consensus: int = 0, seed: int = 0):
         """``vitvs_homography_velocity_dev``: the homography law of every pair of the last velocity call, from the
         matched image points that call left in the handle and nothing else: no depth image, no goal depth.  Per pair the 3 x 3
         homography ``H`` of a planar target, m* ~ H m, and ``v_h = -lambda (depth_scale (H - I) m_c, (H21 - H12, H02 - H20, H10 -
@@ -653,14 +661,18 @@ class Engine:
         target in metres, which scales the translational gain only; ``robust_iterations``: Tukey re-weightings, 0 .. 16.  Returns
         ``(v_h float64 [n, 6] device tensor, info)``, ``info`` = dict of device tensors: ``status`` int32 [n], ``H`` [n, 3, 3],
         ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` / ``behind`` int32 [n], ``weights`` float64
-        [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing synchronises after the first call (which
-        allocates: make it outside a stream capture)."""
-        return self._homography_law(False, K, status, depth_scale, robust_iterations)
+        [n, max_rows], ``sigma`` float64 [n].  ``consensus`` > 0 (``vitvs_homography_consensus_velocity_dev``): that many four-point
+        hypotheses (0 .. 4096) drawn from ``seed`` are scored in front of the solve and the law starts from the rows that agree with
+        the best one; ``info`` then also says which won (``winner`` int32 [n], j + 1, 0 without a consensus start) and how many rows
+        started at weight 1 (``start_weights`` int32 [n]), and ``zero_weights`` counts the rows it left out.  One launch on the
+        current stream either way; nothing synchronises after the first call (which allocates: make it outside a stream capture)."""
+        return self._homography_law(False, K, status, depth_scale, robust_iterations, consensus, seed)
 
-    def homography_velocity_host(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0):
-        """``vitvs_homography_velocity``, the host-pointer form: numpy in, ``(v_h float64 [n, 6], info)`` out, ``info`` as
-        ``homography_velocity``'s with numpy arrays.  Synchronous."""
-        return self._homography_law(True, K, status, depth_scale, robust_iterations)
+    def homography_velocity_host(self, K, status, depth_scale: float = 1.0, robust_iterations: int = 0, consensus: int = 0,
+                                 seed: int = 0):
+        """``vitvs_homography_velocity`` (``vitvs_homography_consensus_velocity`` with ``consensus`` > 0), the host-pointer form:
+        numpy in, ``(v_h float64 [n, 6], info)`` out, ``info`` as ``homography_velocity``'s with numpy arrays.  Synchronous."""
+        return self._homography_law(True, K, status, depth_scale, robust_iterations, consensus, seed)
 
     POSE_RIG_INFO_FIELDS = ("cameras", "usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes", "worst_status")
 

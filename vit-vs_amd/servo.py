@@ -402,7 +402,8 @@ class Controller:
         if st == _lib.STATUS_NO_CORRESPONDENCE:           # (the reference draw may have ended before any law evaluation)
             self.last_homography_status, self.last_homography = int(st), None
             return
-        v, info = self.engine.homography_velocity_host(p.intrinsics(), [st], p.homography_depth, p.homography_robust_iterations)
+        v, info = self.engine.homography_velocity_host(p.intrinsics(), [st], p.homography_depth, p.homography_robust_iterations,
+                                                        p.homography_consensus, p.homography_consensus_seed)
         self.last_homography_status = int(info["status"][0])
         self.last_homography = info["H"][0].copy()
         if self.last_homography_status == _lib.STATUS_OK or (self.latest_image_depth is None and p.interaction != "desired"):
