@@ -14,10 +14,18 @@
  *     NULL = the null stream) without synchronising; outputs are valid once the stream has reached
  *     the end of the call's work.  The un-suffixed forms take HOST pointers, copy, run and wait.
  *   - inputs are borrowed for the duration of the call; outputs go to caller-allocated buffers;
- *     the handle owns the device weights and workspaces.  One in-flight call per handle; a handle
- *     is bound to the HIP device that was current when it was created: every entry point that takes
- *     a handle runs on that device (and restores the caller's current device before returning), so
- *     handles of several GPUs may be driven from one thread.
+ *     the handle owns the device weights and workspaces.  A handle is bound to the HIP device that
+ *     was current when it was created: every entry point that takes a handle runs on that device
+ *     (and restores the caller's current device before returning), so handles of several GPUs may be
+ *     driven from one thread.
+ *   - ordering of the calls on ONE handle (they share its workspaces; a handle is not thread-safe):
+ *     a host-pointer form orders itself behind the _dev work the handle still has pending on a
+ *     caller's stream — if a _dev call was made since the last host-pointer call it synchronises the
+ *     device before its first launch, else it makes no extra HIP call — and has finished when it
+ *     returns, so a _dev call made after it needs nothing either.  _dev calls on one stream run in
+ *     stream order.  Two _dev calls on DIFFERENT streams remain the caller's to order (an event, a
+ *     synchronisation), and so does a replay of a graph the CALLER captured around a _dev call: the
+ *     library sees the capture, not the replays.
  *   - images are RGB uint8, HWC, already resized to img_size x img_size (reference:
  *     vitvs_v2.py:474-475 PIL resize happens before the path; dinov2_extractor.py:177-191);
  *     vitvs_resize_frames_dev does that resize on the device, bit-identically to PIL, and after

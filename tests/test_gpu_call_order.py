@@ -1,0 +1,497 @@
+"""A handle's answers do not depend on where the caller synchronises (GPU).
+
+A sequence of calls on one handle, made with NO synchronisation between them, must give what the same sequence gives on a fresh
+handle with torch.cuda.synchronize() after every call (the side the other suites hold to the fp64 oracle) - BIT FOR BIT: v_c,
+status and every array of last_details / last_features (tests/test_gpu_history.py's snapshot).  The `_dev` forms enqueue on the
+caller's stream and return; the host-pointer forms run on the handle's own non-blocking stream (vitvs_set_goal_depth: the null
+stream), which no stream orders.  include/vitvs.h: a host-pointer form orders itself behind the handle's pending `_dev` work.
+
+The race is made deterministic, never provoked: the caller's stream is HELD by a filler (plain torch.mm calls, >= 20 ms and >= 50
+tiny-model updates long) enqueued before the `_dev` call, so that call has certainly not started when the next one is made; an
+event behind the filler must still be pending immediately before the call under test (a validity condition: asserted, not
+skipped).  A library that does not order the two then answers from a KNOWN stale state - a different, well-defined answer, which
+every sequence asserts differs from the expected one - and nothing overlaps on the workspace.  Sequences A - G, each with the
+caller's stream torch's default stream and a side stream, with graph_replay 0 and (side stream) 1:
+
+  A  set_goal(G0), sync; hold; set_goal(G1); compute_velocity_host(cur, None)          = the host call on the goal G1
+  B  hold; dev velocity call (drops the goal cache); vitvs_set_goal(G1) (host form)    = that goal survives the dev call
+  C  interaction "desired", goal depth Z0; hold; dev velocity call; set_goal_depth(Z1) = the dev call reads Z0, the next one Z1
+  D  hold; extract_descriptors / forward_tokens; compute_velocity_host                 = both their synchronised values
+  E  hold; dev velocity call; compute_velocity_host; last_details                      = both, and the details are the host call's
+  F  compute_velocity_host; hold; dev velocity call; reselect_host                     = error -5 (nothing to reselect on)
+  G  a dev velocity call captured by the CALLER; hold; replay; compute_velocity_host   = capture and replay work, the host call too
+
+and three tests of state that outlives a call: a refused saliency call keeps the cached goal, and a Controller whose goal image
+is rewritten in place servoes towards the goal it holds now."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import vitvs_amd  # noqa: F401
+from vitvs_amd import _lib, servo
+from vitvs_amd.engine import VitvsError
+
+import history_cases as hc
+import test_gpu_history as th
+
+pytestmark = pytest.mark.gpu
+
+KIND, NUM_PAIRS, ORDER_SEED = "tiny", 24, 11
+# (the caller's stream, option graph_replay): on the null stream the library never replays
+CALLERS = [pytest.param("default", 0, id="default_stream"), pytest.param("side", 0, id="side_stream"),
+           pytest.param("side", 1, id="side_stream_graph_replay")]
+STALE = "the stale state gives the expected answer: the sequence would pass without any ordering"
+
+
+# ----------------------------------------------------------------------------------------------------- holding a stream
+class _Filler:
+    """A chain of torch.mm calls on a 4096 x 4096 fp32 pair, measured once on an idle device with events and lengthened until it
+    lasts >= 20 ms and >= 50 x one tiny-model update (at most 1 s)."""
+
+    def __init__(self):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        g = torch.Generator(device="cpu").manual_seed(1)
+        self.a = torch.randn(4096, 4096, generator=g).to(dev)
+        self.b = torch.randn(4096, 4096, generator=g).to(dev)
+        self.out = torch.empty_like(self.a)
+        self.side = torch.cuda.Stream(dev)
+        self.fill(2)                                                           # the BLAS library's own set-up
+        self.mm_ms = self._timed(lambda: self.fill(8)) / 8
+        with th.Ctx(KIND) as ctx:
+            inp = _Inputs(ctx)
+            inp.dev_call(ctx, 1)
+            self.update_ms = self._timed(lambda: inp.dev_call(ctx, 1))
+        want_ms = max(20.0, 50.0 * self.update_ms)
+        self.count = max(1, min(math.ceil(want_ms / self.mm_ms), int(1000.0 / self.mm_ms)))
+        self.ms = self.count * self.mm_ms
+        print(f"\ncall order: one tiny-model update {self.update_ms:.3f} ms, one filler product {self.mm_ms:.3f} ms, "
+              f"the filler is {self.count} products = {self.ms:.1f} ms")
+        assert self.ms >= min(want_ms, 1000.0 - self.mm_ms), "the filler cannot be made long enough"
+
+    @staticmethod
+    def _timed(work):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        work()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def fill(self, n):
+        for _ in range(n):
+            torch.mm(self.a, self.b, out=self.out)
+
+    def stream(self, which):
+        return self.side if which == "side" else torch.cuda.default_stream()
+
+
+@pytest.fixture(scope="module")
+def filler():
+    f = _Filler()
+    yield f
+    torch.cuda.synchronize()
+    _EXPECTED.clear()
+
+
+class _Held:
+    """The unsynchronised side: hold() enqueues the filler on the current stream with an event behind it, pending() asserts -
+    immediately before the call under test - that the stream is still held, so the `_dev` work behind the filler has not begun."""
+    synchronised = False
+
+    def __init__(self, filler):
+        self.filler, self.event = filler, None
+
+    def hold(self):
+        self.filler.fill(self.filler.count)
+        self.event = torch.cuda.Event()
+        self.event.record()
+
+    def pending(self):
+        assert self.event is not None and not self.event.query(), \
+            "NOT VALID: the filler had ended before the call under test was made, so this run shows nothing about ordering"
+
+
+class _Synced:
+    """The reference side: nothing held, torch.cuda.synchronize() after every call."""
+    synchronised = True
+
+    def hold(self):
+        torch.cuda.synchronize()
+
+    def pending(self):
+        torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------------------------------- inputs
+class _Inputs:
+    """Two frame pairs (0, 1), depth, intrinsics and a visiting order, on the host and - staged before anything is held, so that no
+    call under test copies from pageable memory - on the device."""
+
+    def __init__(self, ctx):
+        eng, size = ctx.eng, ctx.cfg.img_size
+        pairs = [th._pair(s, "synth", None, size) for s in hc.PROBE_SEEDS[:2]]
+        self.des = [np.ascontiguousarray(p[0][None]) for p in pairs]
+        self.cur = [np.ascontiguousarray(p[1][None]) for p in pairs]
+        self.z, self.K = th._depths(1), ctx.params.intrinsics()
+        self.order = th._orders(ORDER_SEED, 1, ctx.cfg.tokens)
+        self.des_d, self.cur_d = [eng._frames(a) for a in self.des], [eng._frames(a) for a in self.cur]
+        self.both_d = eng._frames(np.concatenate([self.des[1], self.cur[1]]))
+        self.z_d = torch.as_tensor(self.z).to(eng.device).contiguous()
+        self.K_d = torch.as_tensor(self.K, dtype=torch.float64).reshape(1, 4).contiguous().to(eng.device)
+        self.order_d = torch.as_tensor(self.order).to(eng.device)
+        self.out = [(torch.zeros((1, 6), dtype=torch.float64, device=eng.device), torch.zeros(1, dtype=torch.int32, device=eng.device))
+                    for _ in range(2)]
+        torch.cuda.synchronize()
+
+    def dev_call(self, ctx, pair, goal=True, slot=0):
+        """vitvs_compute_velocity_dev of frame pair `pair` on the current stream (goal False: I_des NULL, the cached goal)."""
+        v, st = self.out[slot]
+        return ctx.eng.compute_velocity_dev(self.cur_d[pair], self.des_d[pair] if goal else None, self.z_d, self.K_d, _lib.SELECT_ORDER,
+                                            self.order_d, None, out_v=v, out_status=st, num_pairs=NUM_PAIRS)
+
+    def host_call(self, ctx, pair, goal=True):
+        """vitvs_compute_velocity of frame pair `pair` and its snapshot (v_c, status, last_details, last_features)."""
+        v, st = ctx.eng.compute_velocity_host(self.cur[pair], self.des[pair] if goal else None, self.z, self.K, _lib.SELECT_ORDER,
+                                              self.order, num_pairs=NUM_PAIRS)
+        return th._law_snapshot(ctx.eng, v, st, 1)
+
+
+def _warm(ctx, inp, mode, pair, slot=0):
+    """Option graph_replay: the call under test is a REPLAY - its capture and instantiation (host work of some milliseconds) are
+    spent before the stream is held.  The handle's past does not change its answers (tests/test_gpu_history.py)."""
+    if ctx.graph_replay and not mode.synchronised:
+        inp.dev_call(ctx, pair, slot=slot)
+        torch.cuda.synchronize()
+
+
+def _dev_result(out):
+    torch.cuda.synchronize()
+    return dict(v_c=th._np(out[0]), status=th._np(out[1]))
+
+
+def _handle(precision, in_flight, graph_replay=0, options=hc.OFF):
+    ctx = th.Ctx(KIND, precision, in_flight)
+    th._set_options(ctx, options)
+    ctx.eng.set_option("graph_replay", graph_replay)
+    ctx.graph_replay = graph_replay
+    return ctx, _Inputs(ctx)
+
+
+_EXPECTED = {}
+
+
+def _expected(key, make):
+    """What a sequence must give, from fresh handles with a synchronisation after every call: once per module."""
+    if key not in _EXPECTED:
+        _EXPECTED[key] = make()
+        torch.cuda.synchronize()
+    return _EXPECTED[key]
+
+
+def _differ(a, b):
+    return th._first_difference(a, b) is not None
+
+
+def _run(filler, caller, graph_replay, precision, in_flight, body, options=hc.OFF):
+    """`body(ctx, inp, mode)` on a fresh handle with the caller's stream current and held (mode.hold / mode.pending)."""
+    ctx, inp = _handle(precision, in_flight, graph_replay, options)
+    with ctx:
+        with torch.cuda.stream(filler.stream(caller)):
+            got = body(ctx, inp, _Held(filler))
+        torch.cuda.synchronize()
+    return got
+
+
+def _synced(precision, in_flight, body, options=hc.OFF):
+    ctx, inp = _handle(precision, in_flight, 0, options)
+    with ctx:
+        return body(ctx, inp, _Synced())
+
+
+# ----------------------------------------------------------------------------------------------------- A
+def _cached_goal_then_host_call(goal_pair):
+    def body(ctx, inp, mode):
+        ctx.eng.set_goal(inp.des_d[goal_pair])
+        torch.cuda.synchronize()
+        return inp.host_call(ctx, 0, goal=False)
+    return body
+
+
+def _sequence_a(ctx, inp, mode):
+    ctx.eng.set_goal(inp.des_d[1])                                              # G0
+    torch.cuda.synchronize()
+    mode.hold()
+    ctx.eng.set_goal(inp.des_d[0])                                              # G1, behind the filler
+    mode.pending()
+    return inp.host_call(ctx, 0, goal=False)
+
+
+# (ordering does not depend on the precision: one bf16 run, under the in-flight plan, on the side stream)
+@pytest.mark.parametrize("caller,graph_replay,precision,in_flight",
+                         [pytest.param(*c.values, "fp32", 1, id=c.id) for c in CALLERS] + [pytest.param("side", 0, "bf16", 3, id="side_stream_bf16_in_flight_3")])
+def test_a_host_call_on_a_goal_set_just_before(filler, caller, graph_replay, precision, in_flight):
+    """Engine.set_goal returns with the goal's forward merely enqueued; compute_velocity_host(cur, None) right behind it passes the
+    goal-cache check (host state) and must servo towards THAT goal, not towards the rows the workspace holds at that moment."""
+    want = _expected(("A", precision, in_flight), lambda: _synced(precision, in_flight, _cached_goal_then_host_call(0)))
+    stale = _expected(("A-stale", precision, in_flight), lambda: _synced(precision, in_flight, _cached_goal_then_host_call(1)))
+    assert _differ(stale, want), STALE
+    assert int(want["status"][0]) == _lib.STATUS_OK
+    got = _run(filler, caller, graph_replay, precision, in_flight, _sequence_a)
+    if not _differ(got, stale):
+        pytest.fail(f"the host call answered from the PREVIOUS goal's rows: v_c {got['v_c'][0]} where the goal set last gives {want['v_c'][0]}")
+    th._same(got, want, "set_goal, compute_velocity_host(cur, None)")
+
+
+# ----------------------------------------------------------------------------------------------------- B
+def _host_set_goal(ctx, frames):
+    rc = ctx.eng.lib.vitvs_set_goal(ctx.eng.handle, int(frames.shape[0]), frames.ctypes.data_as(C.c_void_p))
+    ctx.eng._check(rc, "vitvs_set_goal")
+
+
+def _sequence_b(ctx, inp, mode):
+    _warm(ctx, inp, mode, 1)
+    mode.hold()
+    out = inp.dev_call(ctx, 1)                                                  # forwards goal frames of its own: drops the cache
+    mode.pending()
+    _host_set_goal(ctx, inp.des[0])                                             # G1, the host form
+    torch.cuda.synchronize()
+    return _dev_result(out), inp.host_call(ctx, 0, goal=False)
+
+
+def _expected_b():
+    def host_goal(pair):
+        def body(ctx, inp, mode):
+            _host_set_goal(ctx, inp.des[pair])
+            return inp.host_call(ctx, 0, goal=False)
+        return body
+    return (_synced("fp32", 1, lambda ctx, inp, mode: _dev_result(inp.dev_call(ctx, 1))), _synced("fp32", 1, host_goal(0)),
+            _synced("fp32", 1, host_goal(1)))
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_b_host_set_goal_behind_a_pending_velocity_call(filler, caller, graph_replay):
+    """A dev velocity call with goal frames of its own overwrites the goal rows WHEN IT RUNS; vitvs_set_goal (host form) made after
+    it in program order must find it done, or the rows it caches are overwritten behind its back while goal_frames says they hold."""
+    want_dev, want, stale = _expected("B", _expected_b)
+    assert _differ(stale, want), STALE
+    got_dev, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_b)
+    th._same(got_dev, want_dev, "the dev velocity call")
+    th._same(got, want, "dev velocity call, vitvs_set_goal, compute_velocity_host(cur, None)")
+
+
+# ----------------------------------------------------------------------------------------------------- C
+DESIRED = (0, 0, 1)                                                             # interaction "desired": L(s*, Z*), Z* from the goal depth
+
+
+def _other_goal_depth():
+    return (th._goal_depth().astype(np.int64) + 900).clip(1, 65535).astype(np.uint16)
+
+
+def _sequence_c(ctx, inp, mode):
+    _warm(ctx, inp, mode, 0)
+    mode.hold()
+    first = inp.dev_call(ctx, 0, slot=0)
+    mode.pending()
+    ctx.eng.set_goal_depth(_other_goal_depth())                                 # numpy: vitvs_set_goal_depth, same count
+    first = th._law_snapshot(ctx.eng, *first, 1)                                # (the host form has drained the device)
+    second = inp.dev_call(ctx, 0, slot=1)
+    torch.cuda.synchronize()
+    return first, th._law_snapshot(ctx.eng, *second, 1)
+
+
+def _expected_c():
+    def with_depth(other):
+        def body(ctx, inp, mode):
+            if other:
+                ctx.eng.set_goal_depth(_other_goal_depth())
+            out = inp.dev_call(ctx, 0)
+            torch.cuda.synchronize()
+            return th._law_snapshot(ctx.eng, *out, 1)
+        return body
+    return _synced("fp32", 1, with_depth(False), DESIRED), _synced("fp32", 1, with_depth(True), DESIRED)
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_c_goal_depth_rewritten_behind_a_pending_velocity_call(filler, caller, graph_replay):
+    """vitvs_set_goal_depth (host form) rewrites the goal-depth table on the null stream.  A dev velocity call made EARLIER reads
+    the table as it was when it was made, also when it still waits on a side stream the null stream does not order; the call after
+    reads the new table.  (On the null stream the two were always in order: asserted as well.)"""
+    with_z0, with_z1 = _expected("C", _expected_c)
+    assert _differ(with_z0, with_z1), STALE
+    assert int(with_z0["status"][0]) == _lib.STATUS_OK and with_z0["Z_goal"].any()
+    first, second = _run(filler, caller, graph_replay, "fp32", 1, _sequence_c, DESIRED)
+    if not _differ(first, with_z1):
+        pytest.fail(f"the earlier dev call read the goal depth set AFTER it: v_c {first['v_c'][0]}, with its own table {with_z0['v_c'][0]}")
+    th._same(first, with_z0, "the dev velocity call made before set_goal_depth")
+    th._same(second, with_z1, "the dev velocity call made after set_goal_depth")
+
+
+# ----------------------------------------------------------------------------------------------------- D
+FORWARD_OPS = {"extract_descriptors": lambda eng, frames: eng.extract_descriptors(frames),
+               "forward_tokens": lambda eng, frames: eng.forward_tokens(frames)}
+
+
+def _sequence_d(op):
+    def body(ctx, inp, mode):
+        mode.hold()
+        out = FORWARD_OPS[op](ctx.eng, inp.both_d)                              # frames of pair 1
+        mode.pending()
+        snap = inp.host_call(ctx, 0)
+        torch.cuda.synchronize()
+        return dict(out=th._np(out)), snap
+    return body
+
+
+def _expected_d(op):
+    def other(ctx, inp, mode):                                                  # the op on the HOST call's frames, the host call on the op's
+        frames = ctx.eng._frames(np.concatenate([inp.des[0], inp.cur[0]]))
+        out = dict(out=th._np(FORWARD_OPS[op](ctx.eng, frames)))
+        return out, inp.host_call(ctx, 1)
+    return _synced("fp32", 1, _sequence_d(op)), _synced("fp32", 1, other)
+
+
+@pytest.mark.parametrize("op", list(FORWARD_OPS))
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_d_host_call_behind_a_pending_forward(filler, caller, graph_replay, op):
+    """A forward-only dev call and a host-pointer velocity call share x / xn / qkv / part: each gives its synchronised value."""
+    (want_out, want), (other_out, other) = _expected(("D", op), lambda: _expected_d(op))
+    assert _differ(other_out, want_out) and _differ(other, want), STALE
+    got_out, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_d(op))
+    th._same(got_out, want_out, op)
+    th._same(got, want, f"{op}, compute_velocity_host")
+
+
+# ----------------------------------------------------------------------------------------------------- E
+def _sequence_e(ctx, inp, mode):
+    _warm(ctx, inp, mode, 1)
+    mode.hold()
+    out = inp.dev_call(ctx, 1)
+    mode.pending()
+    snap = inp.host_call(ctx, 0)                                                # last_details: the host call's
+    return _dev_result(out), snap
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_e_host_call_behind_a_pending_velocity_call(filler, caller, graph_replay):
+    """Two velocity calls, dev then host: the dev outputs, the host outputs and the detail arrays read after the host call (served
+    partly from the pinned block, `selected` and L from the device) are those of the synchronised sequence."""
+    want_dev, want = _expected("E", lambda: _synced("fp32", 1, _sequence_e))
+    assert _differ(dict(v_c=want["v_c"], status=want["status"]), want_dev), STALE
+    got_dev, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_e)
+    th._same(got_dev, want_dev, "the dev velocity call")
+    th._same(got, want, "dev velocity call, compute_velocity_host, last_details")
+
+
+# ----------------------------------------------------------------------------------------------------- F
+def _reselect(ctx):
+    return ctx.eng.reselect_host(_lib.SELECT_ORDER, th._orders(ORDER_SEED + 500, 1, ctx.cfg.tokens), num_pairs=NUM_PAIRS)
+
+
+def _sequence_f(ctx, inp, mode):
+    _warm(ctx, inp, mode, 1)
+    inp.host_call(ctx, 0)
+    mode.hold()
+    out = inp.dev_call(ctx, 1)
+    mode.pending()
+    with pytest.raises(VitvsError, match=r"\(-5\)"):
+        _reselect(ctx)
+    return _dev_result(out)
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_f_reselect_behind_a_dev_velocity_call_is_refused(filler, caller, graph_replay):
+    """vitvs_reselect builds on what the last HOST-pointer velocity call left; a dev velocity call in between ends that, whether it
+    has run yet or not: error -5 (and the dev call is unharmed).  Without the dev call the same reselect is served."""
+    def served(ctx, inp, mode):
+        inp.host_call(ctx, 0)
+        v, st = _reselect(ctx)
+        return dict(v_c=v, status=st)
+    assert int(_expected("F-served", lambda: _synced("fp32", 1, served))["status"][0]) == _lib.STATUS_OK, STALE
+    want_dev = _expected("F", lambda: _synced("fp32", 1, _sequence_f))
+    th._same(_run(filler, caller, graph_replay, "fp32", 1, _sequence_f), want_dev, "the dev velocity call")
+
+
+# ----------------------------------------------------------------------------------------------------- G
+def test_g_host_call_behind_the_replay_of_a_callers_capture(filler):
+    """The caller captures a dev velocity call into a graph of its own (torch.cuda.graph on a side stream, after a warm-up call) and
+    replays it: the library records and waits on nothing inside the capture, so capture and replay succeed, the replayed call
+    gives its eager value, and a host-pointer call made behind the (held) replay gives its synchronised value."""
+    want_dev, want = _expected("E", lambda: _synced("fp32", 1, _sequence_e))
+    ctx, inp = _handle("fp32", 1)
+    with ctx:
+        side = filler.side
+        with torch.cuda.stream(side):
+            inp.dev_call(ctx, 1)                                                # warm-up
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            out = inp.dev_call(ctx, 1)
+        torch.cuda.synchronize()
+        out[0].fill_(-1.0)
+        out[1].fill_(-1)
+        torch.cuda.synchronize()
+        mode = _Held(filler)
+        with torch.cuda.stream(side):
+            mode.hold()
+            graph.replay()
+            mode.pending()
+            got = inp.host_call(ctx, 0)
+        th._same(_dev_result(out), want_dev, "the replayed dev velocity call")
+        th._same(got, want, "replay, compute_velocity_host")
+        del graph
+
+
+# ----------------------------------------------------------------------------------------------------- state that outlives a call
+@pytest.mark.parametrize("in_flight", [1, 3])
+def test_a_refused_saliency_call_keeps_the_cached_goal(in_flight):
+    """f16x2 has no saliency kernel: vitvs_extract_saliency_dev is error -5 there, and a refused call leaves the handle as it found
+    it - it used to run its forward first, which drops the goal cache.  set_goal(G), the refused call, compute_velocity(cur, None)
+    equals the same without the refused call."""
+    def body(refused):
+        def run(ctx, inp, mode):
+            ctx.eng.set_goal(inp.des_d[0])
+            if refused:
+                rc, _ = th._saliency(ctx.eng, np.concatenate([inp.des[1], inp.cur[1]]))
+                assert rc == -5 and "f16x2" in ctx.eng.lib.vitvs_last_error(ctx.eng.handle).decode()
+            out = inp.dev_call(ctx, 0, goal=False)
+            torch.cuda.synchronize()
+            return th._law_snapshot(ctx.eng, *out, 1)
+        return run
+    want = _synced("f16x2", in_flight, body(False))
+    assert int(want["status"][0]) == _lib.STATUS_OK
+    th._same(_synced("f16x2", in_flight, body(True)), want, "set_goal, refused saliency call, compute_velocity(cur, None)")
+
+
+def _controller(ctx, goal, cur):
+    ctl = servo.Controller(ctx.eng, goal, selection="order")
+    ctl.image_callback_rgb(cur)
+    ctl.image_callback_depth(th._depths(1)[0])
+    return ctl
+
+
+def _update(ctl):
+    ctl.generator = torch.Generator().manual_seed(77)                           # the same visiting order on both sides
+    ctl.ibvs()
+    return dict(v_c=np.asarray(ctl._raw_v, np.float64).copy(), status=np.asarray(ctl.last_status).copy(),
+                **{k: np.asarray(a).copy() for k, a in ctl.engine.last_features(1).items()})
+
+
+def test_controller_servoes_towards_a_goal_rewritten_in_place():
+    """The reference reads self.goal_image on every update.  A real Controller on the tiny model, two updates, the goal array
+    rewritten in place between them (same object, same shape): the second update's raw twist, status and feature rows are a fresh
+    controller's with that goal - and differ from the first goal's."""
+    with th.Ctx(KIND) as ctx:
+        inp = _Inputs(ctx)
+        want = _update(_controller(ctx, inp.des[0][0].copy(), inp.cur[0][0]))
+    with th.Ctx(KIND) as ctx:
+        goal = inp.des[1][0].copy()
+        ctl = _controller(ctx, goal, inp.cur[0][0])
+        first = _update(ctl)
+        assert _differ(first, want), STALE
+        goal[...] = inp.des[0][0]
+        th._same(_update(ctl), want, "the update after goal[...] = other")
+        th._same(_update(ctl), want, "the update after that (the private copy is reused)")

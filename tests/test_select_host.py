@@ -156,11 +156,14 @@ class _HostEngine:
     def __init__(self, params):
         self.params = params
         self.calls = []
+        self.goals = []
+        self.options = []
 
     def set_frame_size(self, *a):
         return self
 
     def set_option(self, *a):
+        self.options.append(a)
         return self
 
     def apply_law_params(self, params):
@@ -169,6 +172,7 @@ class _HostEngine:
 
     def compute_velocity_host(self, cur, des, z, K, mode=None, selection=None, n_selected=None, des_shared=False, num_pairs=None):
         self.calls.append(dict(mode=mode, selection=selection, num_pairs=num_pairs))
+        self.goals.append((des.ctypes.data, np.array(des, copy=True)))        # the address handed over, and what it held then
         return np.full((1, 6), 0.5), np.zeros(1, np.int32)
 
     def compute_velocity(self, cur, des, z, K, mode=None, selection=None, des_shared=False, num_pairs=None):
@@ -192,6 +196,49 @@ def test_controller_best_is_one_host_call_with_no_selection():
     assert torch.equal(torch.random.get_rng_state(), state)      # nothing was drawn
     assert eng.calls == [dict(mode=_lib.SELECT_BEST, selection=None, num_pairs=5)]
     assert np.array_equal(ctl.v_c, np.full(6, 0.5))
+
+
+def test_controller_stages_the_goal_it_holds_now():
+    """The reference reads ``self.goal_image`` on every update (vitvs_v2.py:482-487).  The controller hands the engine a private copy
+    whose ADDRESS tells the library that the goal frame staged before is still the goal (option "reuse_goal_frames"): the copy
+    follows the goal's content, not the goal object's id.  An unchanged goal: the same address on every update.  A goal rewritten
+    in place, a replacement of equal shape, a goal that returns to an earlier content: an array equal to the goal as it is now,
+    with the option set again (which makes the library forget the address staged before, recycled or not)."""
+    params = config.ServoParams(dino_input_size=8, use_feature_binning=False, num_pairs=5)
+    eng = _HostEngine(params)
+    rng = np.random.default_rng(4)
+    first, other, third = (rng.integers(0, 256, size=(8, 8, 3), dtype=np.uint8) for _ in range(3))
+    goal = first.copy()
+    ctl = servo.Controller(eng, goal, selection="best")
+    ctl.image_callback_rgb(np.zeros((8, 8, 3), np.uint8) + 3)
+    ctl.image_callback_depth(np.ones((params.v_max, params.u_max), np.uint16))
+
+    def update():
+        ctl.ibvs()
+        return eng.goals[-1]
+
+    addr, held = update()
+    assert np.array_equal(held, first) and addr != goal.ctypes.data          # a private copy, not the caller's buffer
+    assert eng.options.count(("reuse_goal_frames", 1)) == 1
+    for _ in range(3):                                                       # unchanged goal: the same buffer, nothing staged again
+        assert update()[0] == addr
+    assert eng.options.count(("reuse_goal_frames", 1)) == 1
+    goal[...] = other                                                        # rewritten in place: same object, same id, same shape
+    addr2, held = update()
+    assert np.array_equal(held, other)
+    assert eng.options.count(("reuse_goal_frames", 1)) == 2                  # the library forgets the staged address
+    assert update()[0] == addr2 and eng.options.count(("reuse_goal_frames", 1)) == 2
+    goal[3, 4, 1] ^= 1                                                       # one byte
+    assert np.array_equal(update()[1], goal) and eng.options.count(("reuse_goal_frames", 1)) == 3
+    ctl.goal_image = third.copy()                                            # a replacement goal of equal shape
+    addr3, held = update()
+    assert np.array_equal(held, third) and eng.options.count(("reuse_goal_frames", 1)) == 4
+    assert update()[0] == addr3
+    replacement = third.copy()                                               # another object, equal content: nothing to stage
+    ctl.goal_image = replacement
+    assert update()[0] == addr3 and eng.options.count(("reuse_goal_frames", 1)) == 4
+    ctl.goal_image = first.copy()                                            # back to an earlier content
+    assert np.array_equal(update()[1], first) and eng.options.count(("reuse_goal_frames", 1)) == 5
 
 
 def test_multi_controller_best_calls_once_with_no_selection():

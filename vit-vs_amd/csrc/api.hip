@@ -189,6 +189,12 @@ struct vitvs_handle {
     bool reuse_goal = false;            // option "reuse_goal_frames": I_des of a host-pointer call is not staged again while its address repeats
     const void* staged_des = nullptr;   // host address, frame count and geometry of the goal frames in st_des
     size_t staged_des_bytes = 0;
+    // A _dev call returns once its work is enqueued on the CALLER's stream, and nothing orders that stream against host_stream (non-
+    // blocking) or the null stream.  Every _dev entry point that touches the workspace, the arg-max keys, the goal rows, the detail
+    // block or the goal-depth table sets this; a host-pointer form that finds it set drains the device before its first launch
+    // (order_behind_dev) and clears it.  A flag, not an event or the stream: nothing may be recorded inside a caller's capture, and
+    // the caller may destroy the stream when the call has returned.
+    bool dev_pending = false;
 };
 
 namespace {
@@ -304,6 +310,7 @@ int host_call(vitvs_handle* h, IoList io, unsigned char* block, DevForm dev_form
     hipStream_t st = h->host_stream;            // (null before the first host-pointer velocity call: the default stream)
     if (int rc = dev_form(st)) return rc;
     VITVS_HIP_CHECK(hipStreamSynchronize(st));
+    h->dev_pending = false;                     // (the device was drained above, and this call's own work just now)
     for (const IoField* f = io.f; f != io.f + io.n; ++f)
         if (!f->input && f->host) VITVS_HIP_CHECK(hipMemcpy(f->host, f->dev, f->count * f->elem, hipMemcpyDeviceToHost));
     return 0;
@@ -396,6 +403,23 @@ int check_cfg(const vitvs_config* c, std::string& why) {
 }
 
 hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The stream of a _dev entry point: work on any stream but the handle's own host stream is the caller's to wait for, so it counts as
+// pending until a host-pointer form has drained the device (vitvs_handle::dev_pending).  The host-pointer forms that pass the null
+// stream through a _dev form (host_call before the first host-pointer velocity call, vitvs_set_goal_depth) drain it themselves.
+hipStream_t dev_stream(vitvs_handle* h, void* s) {
+    hipStream_t st = as_stream(s);
+    if (!st || st != h->host_stream) h->dev_pending = true;
+    return st;
+}
+// What a host-pointer form does before its first launch: wait for the _dev work this handle may still have on a caller's stream.
+// A loop of host-pointer calls alone finds the flag clear and makes no HIP call here.
+int order_behind_dev(vitvs_handle* h) {
+    if (!h->dev_pending) return 0;
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    h->dev_pending = false;
+    return 0;
+}
 
 // Captured updates hold addresses (weights, resize tables) and a tile plan: whoever changes one of those drops them, after
 // the device has drained (a replay may still be running).
@@ -1067,7 +1091,7 @@ int vitvs_weights_ready(const vitvs_handle* hc) {
 int vitvs_forward_tokens_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, float* tokens, void* stream) {
     if (!h || !frames || !tokens) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     int rc = forward(h, n_frames, frames, 0, nullptr, st);
     if (rc) return rc;
     VITVS_HIP_CHECK(hipMemcpyAsync(tokens, h->x, (size_t)n_frames * h->N * h->cfg.dim * sizeof(float),
@@ -1177,7 +1201,7 @@ int vitvs_set_frame_size(vitvs_handle* h, int32_t in_h, int32_t in_w) {
 int vitvs_extract_descriptors_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, float* desc, void* stream) {
     if (!h || !frames || !desc) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     int rc = forward(h, n_frames, frames, 0, nullptr, st);
     if (rc) return rc;
     rc = launch_descriptors(h->x, h->dn, desc, h->sq, n_frames, h->T, 1 + h->R, h->grid, h->cfg.dim, h->cfg.binned, nullptr, nullptr,
@@ -1199,7 +1223,7 @@ int vitvs_extract_descriptors_ex_dev(vitvs_handle* h, int32_t n_frames, const ui
     if (bin && include_cls)   // the reference's assertion (dinov2_extractor.py:330-331)
         return set_err(h, -5, "bin = True and include_cls = True are not supported together, set one of them False.");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     int rc = forward(h, n_frames, frames, 0, nullptr, st);   // the last block's qkv launch leaves its output in h->qkv
     if (rc) return rc;
     const int T = h->T, D = h->cfg.dim;
@@ -1237,11 +1261,12 @@ int vitvs_extract_saliency_dev(vitvs_handle* h, int32_t n_frames, const uint8_t*
     if (n_heads <= 0 || n_heads > 16) return set_err(h, -5, "1 .. 16 heads");
     for (int i = 0; i < n_heads; ++i)
         if (head_idxs[i] < 0 || head_idxs[i] >= h->cfg.heads) return set_err(h, -5, "head index outside the model's heads");
+    // (refused before the forward: a call that fails leaves the handle as it found it, a cached goal included)
+    if (h->prec == PREC_X2) return set_err(h, -5, "saliency maps are not available in the f16x2 precision (use fp32)");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     int rc = forward(h, n_frames, frames, 0, nullptr, st);   // the last block's qkv launch leaves its output in h->qkv
     if (rc) return rc;
-    if (h->prec == PREC_X2) return set_err(h, -5, "saliency maps are not available in the f16x2 precision (use fp32)");
     rc = launch_saliency(h->prec, h->qkv, saliency, n_frames, h->T, 1 + h->R, h->cfg.heads, head_idxs, n_heads, plain16(h->prec),
                          st);
     if (rc) return set_err(h, rc, rc == -3 ? "too many tokens for the saliency kernel's LDS rows" : "saliency launch failed");
@@ -1255,7 +1280,7 @@ int vitvs_correspond_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* de
     if ((size_t)2 * T * Dp > h->dn_elems || (size_t)T > h->best_elems)
         return set_err(h, -3, "descriptors exceed the handle's workspace");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     h->goal_frames = 0;                         // the descriptor workspace is overwritten
     h->details_pinned = false;                  // and the arg-max keys: nothing left for vitvs_reselect
     h->host_tables = vitvs_handle::HostTables{};
@@ -1282,7 +1307,7 @@ int vitvs_refine_dev(vitvs_handle* h, int32_t T, int32_t Dp, const float* desc1,
     if (g * g != T) return set_err(h, -5, "token count is not a square grid");
     if ((size_t)2 * T * Dp > h->dn_elems) return set_err(h, -3, "descriptors exceed the handle's workspace");
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     h->goal_frames = 0;                         // the descriptor workspace is overwritten
     h->host_tables = vitvs_handle::HostTables{};   // and with it what vitvs_reselect would refine from
     int rc = launch_normalize_rows(desc1, h->dn, T, Dp, st);
@@ -1310,7 +1335,7 @@ int vitvs_servo_from_nn_ex_dev(vitvs_handle* h, int32_t T, const int32_t* nn_1, 
     if (int rc = check_selection(h, T, select_mode, selection, h->st_nsel, np)) return rc;
     if (int rc = check_interaction(h, 1, T)) return rc;
     DeviceScope dev(h);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     h->details_pinned = false;
     int rc = launch_encode_best(nn_1, nn_2, sim_1, T, h->row_best, h->col_best, st);
     if (rc) return set_err(h, rc, "encode launch failed");
@@ -1432,7 +1457,7 @@ int vitvs_set_goal_dev(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des, vo
     if (n_goal <= 0 || n_goal > h->cfg.max_pairs) return set_err(h, -3, "n_goal exceeds max_pairs");
     DeviceScope dev(h);
     if (vitvs_weights_ready(h) != 0) return set_err(h, -4, "weights not fully loaded: " + h->err);
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = dev_stream(h, stream);
     h->desc_keys = 0;                           // plain descriptors come out of the forward's last launch; no keys to clear
     int rc = forward_chain(h, 0, n_goal, n_goal, I_des, nullptr, h->part, st);
     h->desc_keys = -1;
@@ -1446,6 +1471,7 @@ int vitvs_set_goal(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des) {
     if (n_goal <= 0 || n_goal > h->cfg.max_pairs) return set_err(h, -3, "n_goal exceeds max_pairs");
     DeviceScope dev(h);
     if (int rc = ensure_host_stage(h)) return rc;
+    if (int rc = order_behind_dev(h)) return rc;
     const size_t img = frame_bytes(h);
     memcpy(h->hs.des, I_des, n_goal * img);
     h->staged_des = nullptr;
@@ -1483,7 +1509,7 @@ int vitvs_compute_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* 
     if (!h) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
     UpdateArgs u{n_pairs, des_shared, select_mode, num_pairs, I_cur, I_des, Z_mm, K, selection, n_selected, v_c, status};
-    return velocity_update(h, u, as_stream(stream));
+    return velocity_update(h, u, dev_stream(h, stream));
 }
 
 // The reference's seam as it is called (vitvs_v2.py:464-523, 588-632: numpy arrays in, a numpy twist out).  Per call: the
@@ -1502,6 +1528,7 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     if (int rc = check_interaction(h, n_pairs, h->T)) return rc;
     DeviceScope dev(h);
     if (int rc = ensure_host_stage(h)) return rc;
+    if (int rc = order_behind_dev(h)) return rc;
     vitvs_handle::HostStage& hs = h->hs;
     hipStream_t st = h->host_stream;
     const size_t img = frame_bytes(h), n_des = des_shared ? 1 : n_pairs;
@@ -1512,18 +1539,27 @@ int vitvs_compute_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cu
     const bool goal_staged = h->reuse_goal && I_des && I_des == h->staged_des && n_des * img == h->staged_des_bytes;
     if (!rc && I_des && !goal_staged) {
         memcpy(hs.des, I_des, n_des * img);
+        h->staged_des = nullptr;                // st_des changes hands; the address counts as staged once the copy is enqueued
         rc = launch_copy16(hs.des, h->st_des, n_des * img, st);
-        h->staged_des = I_des;
-        h->staged_des_bytes = n_des * img;
+        if (!rc) {
+            h->staged_des = I_des;
+            h->staged_des_bytes = n_des * img;
+        }
     }
-    if (rc) return set_err(h, rc, "frame staging launch failed");
+    if (rc) {
+        h->staged_des = nullptr;
+        return set_err(h, rc, "frame staging launch failed");
+    }
     memcpy(hs.K, K, (size_t)n_pairs * 4 * sizeof(double));
     stage_selection(h, n_pairs, h->T, select_mode, selection, n_selected, np);
     UpdateArgs u{n_pairs, des_shared, select_mode, np, h->st_cur, I_des ? h->st_des : nullptr, Z_mm ? hs.depth : nullptr, hs.K,
                  hs.sel, hs.nsel, hs.vc, hs.status, Z_mm};
     rc = velocity_update(h, u, st);
     if (!rc) rc = finish_host_call(h, n_pairs, v_c, status);
-    if (rc) return rc;
+    if (rc) {
+        h->staged_des = nullptr;                // a call that failed vouches for nothing in st_des
+        return rc;
+    }
     h->details_pinned = true;
     h->host_tables = vitvs_handle::HostTables{n_pairs, h->T, Z_mm != nullptr, des_shared ? 1 : 0};
     return 0;
@@ -1544,6 +1580,7 @@ int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t* selectio
     if (int rc = check_selection(h, T, select_mode, selection, n_selected, np)) return rc;
     if (int rc = check_interaction(h, n_pairs, T)) return rc;
     DeviceScope dev(h);
+    if (int rc = order_behind_dev(h)) return rc;
     vitvs_handle::HostStage& hs = h->hs;
     stage_selection(h, n_pairs, T, select_mode, selection, n_selected, np);
     const int rc = run_servo(h, n_pairs, T, h->host_tables.have_depth ? hs.depth : nullptr, hs.K, select_mode, np, hs.sel, hs.nsel,
@@ -1657,7 +1694,7 @@ int vitvs_set_goal_depth_dev(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_
     memset(&geom, 0, sizeof(geom));
     servo_geometry(h, h->T, h->grid, geom);
     // same count as before: the table is rewritten in place, in stream order — captured updates read the new goal
-    const int rc = launch_goal_depth(geom, Z_des_mm, n_goal, h->zgoal, as_stream(stream));
+    const int rc = launch_goal_depth(geom, Z_des_mm, n_goal, h->zgoal, dev_stream(h, stream));
     if (rc) return set_err(h, rc, "goal depth launch failed");
     return 0;
 }
@@ -1667,6 +1704,9 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
     if (n_goal < 0 || n_goal > h->cfg.max_pairs) return set_err(h, -3, "n_goal exceeds max_pairs");
     if (n_goal == 0) return vitvs_set_goal_depth_dev(h, 0, nullptr, nullptr);
     DeviceScope dev(h);
+    // a _dev velocity call made earlier may still be waiting on a stream the null stream does not order (a non-blocking one):
+    // it reads the table as it was when it was made
+    if (int rc = order_behind_dev(h)) return rc;
     // set-up: a device copy of the images for the one launch that reads them, released again behind it
     const size_t bytes = (size_t)n_goal * h->cfg.u_max * h->cfg.v_max * sizeof(uint16_t);
     void* tmp = nullptr;
@@ -1677,6 +1717,7 @@ int vitvs_set_goal_depth(vitvs_handle* h, int32_t n_goal, const uint16_t* Z_des_
     if (!rc) {
         e = hipDeviceSynchronize();
         if (e != hipSuccess) rc = fail_hip(e, "hipDeviceSynchronize", __FILE__, __LINE__);
+        else h->dev_pending = false;            // (the _dev form above ran on the null stream: drained with everything else)
     }
     (void)hipFree(tmp);
     return rc;
@@ -1707,7 +1748,7 @@ int vitvs_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* cVr, c
     a.L = h->Lws; a.ld = 2 * h->cfg.max_rows; a.W = cVr; a.lambda = h->cfg.lambda;
     rig_carve(h->rig_ws, h->cfg.max_pairs, a.ld, a);
     a.v_rig = v_rig; a.rig_status = rig_status; a.rig_info = rig_info; a.normal = normal;
-    const int rc = launch_rig(a, as_stream(stream));
+    const int rc = launch_rig(a, dev_stream(h, stream));
     return rc ? set_err(h, rc, "rig law launch failed") : 0;
 }
 
@@ -1742,7 +1783,7 @@ int vitvs_rig_robust_velocity_dev(vitvs_handle* h, int32_t n_cams, const double*
     ra.live = h->info + 3; ra.live_stride = 8; ra.K = K; ra.n_iter = n_iter;
     ra.pitch_u = token_pitch(c, c.u_max); ra.pitch_v = token_pitch(c, c.v_max);
     ra.weights = weights; ra.weights_stride = c.max_rows; ra.sigma = sigma;
-    const int rc = launch_rig_robust(ra, as_stream(stream));
+    const int rc = launch_rig_robust(ra, dev_stream(h, stream));
     if (rc == -3) return set_err(h, rc, "the robust rig law keeps two doubles per feature pair of the rig in LDS: n_cams * max_rows is too large");
     return rc ? set_err(h, rc, "robust rig law launch failed") : 0;
 }
@@ -1791,7 +1832,7 @@ int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, c
     camera_law_state(h, K, n_iter, a);
     goal_depth_state(h, a);
     a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info; a.weights = weights; a.sigma = sigma;
-    const int rc = launch_pose(a, as_stream(stream));
+    const int rc = launch_pose(a, dev_stream(h, stream));
     return rc ? set_err(h, rc, "pose law launch failed") : 0;
 }
 
@@ -1836,7 +1877,7 @@ int vitvs_homography_consensus_velocity_dev(vitvs_handle* h, int32_t n_pairs, co
     camera_law_state(h, K, n_iter, a);
     a.depth_scale = depth_scale; a.n_hyp = n_hyp; a.seed = seed;
     a.v_h = v_h; a.h_status = h_status; a.H = H; a.h_info = h_info; a.weights = weights; a.sigma = sigma;
-    const int rc = launch_homography(a, as_stream(stream));
+    const int rc = launch_homography(a, dev_stream(h, stream));
     return rc ? set_err(h, rc, "homography law launch failed") : 0;
 }
 
@@ -1894,7 +1935,7 @@ int vitvs_pose_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const double* r
     goal_depth_state(h, a);
     a.v_rig = v_rig; a.rig_status = rig_status; a.pose = pose; a.rig_info = rig_info; a.moments = moments;
     a.weights = weights; a.sigma = sigma;
-    const int rc = launch_pose_rig(a, as_stream(stream));
+    const int rc = launch_pose_rig(a, dev_stream(h, stream));
     return rc ? set_err(h, rc, "pose rig law launch failed") : 0;
 }
 

@@ -312,7 +312,9 @@ class Engine:
         ``compute_velocity(..., I_des=None, ...)`` calls forward only the current frames.  One frame per pair of the later
         calls, or one frame for ``des_shared`` calls.  The reference recomputes the goal every update
         (vitvs_v2.py:482-487); the cache is for servo loops whose goal image does not change, and any call that forwards
-        other frames through the engine drops it."""
+        other frames through the engine drops it.  Enqueued on torch's current stream, no synchronisation: a later call on
+        that stream runs behind it, a host-pointer call (``compute_velocity_host``, ``reselect_host``) orders itself behind it
+        whatever the stream; only a ``_dev`` call on ANOTHER stream is the caller's to order (include/vitvs.h)."""
         des = self._frames(I_des)
         self._check(self.lib.vitvs_set_goal_dev(self.handle, int(des.shape[0]), _ptr(des), _stream_ptr(self.device)), "vitvs_set_goal_dev")
         return self

@@ -268,7 +268,7 @@ class Controller:
         self.max_velocity_vector_history = 200            # config.yaml:37
         self.last_status = None
         self.generator = None                             # torch.Generator of the "order" / "reference" draws (None: torch's global RNG)
-        self._goal_key, self._goal_np = None, None        # a private, never-written copy of the goal frame: its address tells the
+        self._goal_np = None                              # a private, never-written copy of the goal frame: its address tells the
                                                           # library that the staged goal is still the goal (option "reuse_goal_frames")
         self._rejected_geometries = set()                 # camera geometries the fused resize refused (set_frame_size), per engine
 
@@ -333,10 +333,11 @@ class Controller:
         if not torch.is_tensor(des):
             # the goal image does not change from update to update (vitvs_v2.py:264): hand the library the SAME private buffer every
             # time, so that it forwards the goal frame already in device memory instead of staging it again (its tokens are still
-            # recomputed on every update, like the reference does)
-            key = (id(self.goal_image), des.shape)
-            if self._goal_key != key:
-                self._goal_key, self._goal_np = key, np.array(des, dtype=np.uint8, copy=True, order="C")
+            # recomputed on every update, like the reference does).  The copy is keyed on the goal's CONTENT (one comparison of S x S x 3
+            # bytes: microseconds), as the reference reads self.goal_image on every update: a goal rewritten in place or replaced,
+            # at whatever address, is copied and staged again (setting the option forgets the address staged before)
+            if self._goal_np is None or self._goal_np.shape != des.shape or not np.array_equal(self._goal_np, des):
+                self._goal_np = np.array(des, dtype=np.uint8, copy=True, order="C")
                 self.engine.set_option("reuse_goal_frames", 1)
             des = self._goal_np
         depth = self.latest_image_depth
