@@ -33,6 +33,8 @@ import collections
 
 import torch
 
+from op_support import from_x2, to_x2, values  # noqa: F401
+
 F32, BF16, F16, F16X2 = 0, 1, 2, 3               # vitvs_amd._lib's precision codes
 K_F32, K_SHORT, K_Q64, K_Q64KS2, K_LONG = 1, 2, 3, 4, 5   # vitvs_op_attention_plan's kernel codes
 PREC_NAMES = {F32: "fp32", BF16: "bf16", F16: "fp16", F16X2: "f16x2"}
@@ -140,20 +142,6 @@ def fixture(n_img, N, H, family, launch, q_factor=Q_FACTOR) -> Fixture:
 
 
 # the f16x2 layout (csrc/common.h; the same helpers as tests/test_gpu_ops_x2.py and tests/test_gpu_plan_cover.py)
-def to_x2(t, exp=0):
-    """fp32 [R, C] -> fp16 [R, 2C]: per 32 columns [hi | lo] of t * 2^exp."""
-    r, c = t.shape
-    ts = t.float() * (2.0 ** exp)
-    hi = ts.clamp(-65504, 65504).half()
-    lo = (ts - hi.float()).half()
-    return torch.stack([hi.view(r, c // 32, 32), lo.view(r, c // 32, 32)], dim=2).reshape(r, 2 * c).contiguous()
-
-
-def from_x2(t):
-    """fp16 [R, 2C] -> the fp64 values hi + lo [R, C]."""
-    r, c2 = t.shape
-    v = t.reshape(r, c2 // 64, 2, 32).double()
-    return (v[:, :, 0] + v[:, :, 1]).reshape(r, c2 // 2)
 
 
 def operand(prec, qkv32, prescaled=False):
@@ -173,10 +161,6 @@ def operand(prec, qkv32, prescaled=False):
     if prescaled:
         t[:, :D] /= 0.125 * LOG2E
     return x, t
-
-
-def values(prec, out):
-    return from_x2(out) if prec == F16X2 else out.double()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference

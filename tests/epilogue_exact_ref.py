@@ -35,7 +35,7 @@ import torch
 
 import gemm_exact_ref as ge
 from gemm_exact_ref import BF16, F16, F16X2, F32, STORE
-from test_gpu_plan_cover import weight_exp  # noqa: F401  (the rule a handle applies to its f16x2 weights)
+from op_support import weight_exp  # noqa: F401  (the rule a handle applies to its f16x2 weights)
 
 GUARD = 3                         # rows in front of and behind every output that no launch may write
 X2_MAX_K, X2_MAX_OUT = 1024, 1 << 21

@@ -16,32 +16,14 @@ from __future__ import annotations
 
 import numpy as np
 
+from homography_ref import median_middle, rodrigues, sliced_sum, step  # noqa: F401  (re-exported)
+
 OK, TOO_FEW = 0, 2
 TUKEY_C = 4.6851
 HOLE_Z = 100.0          # the camera law's depth of a pixel without a reading
 GAP_TOL = 1e-8          # degenerate: ev_1 - ev_2 <= GAP_TOL (sum w |P - pc|^2 + sum w |Q - qc|^2)
 JACOBI_TOL = 1e-40      # sweeps end when the off-diagonal squares are <= JACOBI_TOL of all squares
 JACOBI_MAX = 32
-
-
-def rodrigues(w):
-    w = np.asarray(w, np.float64)
-    th = float(np.linalg.norm(w))
-    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
-    if th < 1e-12:
-        return np.eye(3) + K
-    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
-
-
-def sliced_sum(x: np.ndarray) -> np.ndarray:
-    """Column sums of x [n, c] in the kernel's order: eight row slices r mod 8, each added in ascending rows (cumsum is
-    sequential), then the slices in ascending order."""
-    x = np.asarray(x, np.float64).reshape(len(x), -1)
-    tot = np.zeros(x.shape[1])
-    for s in range(8):
-        part = x[s::8]
-        tot = tot + (np.cumsum(part, axis=0)[-1] if len(part) else np.zeros(x.shape[1]))
-    return tot
 
 
 def jacobi4(N: np.ndarray):
@@ -132,13 +114,6 @@ def theta_u(q):
 
 def twist(R, t, q, lam):
     return np.concatenate([-lam * (R.T @ t), -lam * theta_u(q)])
-
-
-def median_middle(x):
-    """The median as the mean of the two middle values (the same one for an odd count)."""
-    s = np.sort(np.asarray(x, np.float64))
-    n = len(s)
-    return (s[(n - 1) >> 1] + s[n >> 1]) * 0.5
 
 
 def pose_law(P, Q, usable, lam, n_iter=0, sigma_min=0.0):
@@ -243,11 +218,19 @@ def ibvs_velocity(P, Q, lam):
     return -lam * (np.linalg.pinv(interaction_rows(x, y, Z)) @ e)
 
 
-def step(R, t, v, dt):
-    """tests/planar_sim.py's integration of a body twist."""
-    return R @ rodrigues(v[3:] * dt), t + R @ v[:3] * dt
-
-
 def points_in_camera(X_goal, R, t):
     """Points given in the goal frame as the camera at pose (R, t) sees them: X_cam = R^T (X_goal - t)."""
     return (np.asarray(X_goal) - t) @ R
+
+
+def unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v)
+
+
+def unusable_flags(rows, where, n_off):
+    """`n_off` unusable rows first / in the middle / last, alternating padded rows (0) and holes (-1)."""
+    u = np.ones(rows, np.int32)
+    start = {"first": 0, "middle": (rows - n_off) // 2, "last": rows - n_off}[where]
+    u[start:start + n_off] = np.where(np.arange(n_off) % 2 == 0, 0, -1)
+    return u

@@ -19,6 +19,8 @@ from __future__ import annotations
 import numpy as np
 
 import pose_ref as pr
+from pose_ref import unit  # noqa: F401
+from rig_robust_ref import rel_miss  # noqa: F401
 
 OK, TOO_FEW = pr.OK, pr.TOO_FEW
 
@@ -131,9 +133,6 @@ def per_camera_average(P, Q, usable, rig, lam=1.0, n_iter=0, sigma_min=0.0):
 
 
 # ---------------------------------------------------------------------------------------------- seeded rigs
-def unit(v):
-    v = np.asarray(v, np.float64)
-    return v / np.linalg.norm(v)
 
 
 def toe_in_rig(n_cams=3, spacing=0.15, toe_deg=10.0):
@@ -173,10 +172,6 @@ def true_twist(R, t, lam):
     X = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]])
     q = pr.horn(pr.points_in_camera(X, R, t), X, np.ones(4))["q"]
     return pr.twist(np.asarray(R, np.float64), np.asarray(t, np.float64), q, lam)
-
-
-def rel_miss(v, v_true):
-    return float(np.linalg.norm(np.asarray(v) - v_true) / np.linalg.norm(v_true))
 
 
 def outlier_case(seed, n_cams=3, rows=16, noise=0.002, n_out=6):

@@ -10,6 +10,8 @@ over the cameras whose status is 0.  ``averaged_law`` is the obvious alternative
 pseudo-inverse twist mapped back to the rig frame, then the mean — which is not the least-squares solution of the stack."""
 import numpy as np
 
+from homography_ref import rodrigues  # noqa: F401
+
 STATUS_OK, STATUS_NO_CORRESPONDENCE, STATUS_TOO_FEW, STATUS_NO_DEPTH = 0, 1, 2, 3
 
 
@@ -93,15 +95,6 @@ def point_rows(x, y, Z):
                      [0.0, -1.0 / Z, y / Z, 1.0 + y * y, -(x * y), -x]])
 
 
-def rodrigues(w):
-    w = np.asarray(w, np.float64)
-    th = float(np.linalg.norm(w))
-    K = skew(w)
-    if th < 1e-12:
-        return np.eye(3) + K
-    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
-
-
 def random_extrinsic(rng, angle=0.6, baseline=0.3):
     return rodrigues(rng.uniform(-angle, angle, 3)), rng.uniform(-baseline, baseline, 3)
 
@@ -120,3 +113,8 @@ def scenario(seed, n_cams=3, pairs=2):
     v_star = rng.standard_normal(6)
     es = [L @ W @ v_star for L, W in zip(Ls, Ws)]
     return Ls, es, Ws, v_star
+
+
+def statuses(case):
+    """What the rig kernels report per camera of a case: 0 with rows, 2 (too few) without."""
+    return [0 if L.shape[0] > 0 else 2 for L in case["Ls"]]

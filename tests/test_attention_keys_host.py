@@ -22,18 +22,12 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import host_lib as lib  # noqa: F401
 
 import attention_keys_ref as ak
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = sorted({(c.n_img, c.N, c.H) for c in ak.CASES if c.N > 1})
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
 
 
 def _plan(lib, c):

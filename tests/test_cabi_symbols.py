@@ -8,15 +8,9 @@ import pytest
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import host_lib as lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
 
 
 def _declared(header):

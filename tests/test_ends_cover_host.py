@@ -8,6 +8,7 @@ statement from a one-pass variance.  No kernel runs here."""
 import torch
 
 import test_gpu_ends_cover as ec
+from op_support import rel_max
 from vitvs_amd import _lib
 
 
@@ -19,8 +20,8 @@ def _worst():
                 t = ec.epilogue_inputs(D, n_img, T, P, slices)
                 for use_ls in (False, True):
                     rows = ec.patch_rows_of(ec.epilogue_x(t, use_ls)[1].float(), n_img, T, P)
-                    w["epilogue_dn"] = max(w["epilogue_dn"], ec._rel(ec.dn_f32(rows), ec.dn_ref(rows)))
-                    w["epilogue_sq"] = max(w["epilogue_sq"], ec._rel(ec.sq_f32(rows), ec.sq_ref(rows)))
+                    w["epilogue_dn"] = max(w["epilogue_dn"], rel_max(ec.dn_f32(rows), ec.dn_ref(rows)))
+                    w["epilogue_sq"] = max(w["epilogue_sq"], rel_max(ec.sq_f32(rows), ec.sq_ref(rows)))
     for grid in (1, 2, 3, 5):
         for D in (128, 384, 1024):
             for P in (1, 5):
@@ -30,14 +31,14 @@ def _worst():
                         rows = ec.patch_rows_of(x.view(-1, D), n_img, grid * grid, P)
                         wide = ec.binned_gather(rows, n_img, grid)
                         if rows.any():
-                            w["plain_dn"] = max(w["plain_dn"], ec._rel(ec.dn_f32(rows), ec.dn_ref(rows)))
-                            w["binned_dn"] = max(w["binned_dn"], ec._rel(ec.dn_f32(wide), ec.dn_ref(wide)))
+                            w["plain_dn"] = max(w["plain_dn"], rel_max(ec.dn_f32(rows), ec.dn_ref(rows)))
+                            w["binned_dn"] = max(w["binned_dn"], rel_max(ec.dn_f32(wide), ec.dn_ref(wide)))
     for Dp in (1, 63, 64, 65, 1152):
         for rows in (1, 5):
             for zero_row in (True, False):
                 src = ec.normalize_inputs(rows, Dp, zero_row)
                 if src.any():
-                    w["normalize"] = max(w["normalize"], ec._rel(ec.dn_f32(src), ec.dn_ref(src)))
+                    w["normalize"] = max(w["normalize"], rel_max(ec.dn_f32(src), ec.dn_ref(src)))
     return w
 
 
@@ -75,11 +76,11 @@ def test_offset_row_bar_separates_two_pass_from_one_pass():
         ref = ec.layer_norm64(x, gamma, beta)
         y2, y1 = ec.ln_f32(x, gamma, beta), ec.ln_f32(x, gamma, beta, one_pass=True)
         for r in ec.OFFSET:
-            two = max(two, ec._rel(y2[r], ref[r]))
-            e1 = ec._rel(y1[r], ref[r])
+            two = max(two, rel_max(y2[r], ref[r]))
+            e1 = rel_max(y1[r], ref[r])
             one = min(one, e1 if e1 == e1 else float("inf"))             # a negative one-pass variance gives NaN: no better
         for r in ec.ORDINARY + ec.SPIKE:
-            assert ec._rel(y2[r], ref[r]) <= ec.BAR_LN[_lib.F32] / 8
+            assert rel_max(y2[r], ref[r]) <= ec.BAR_LN[_lib.F32] / 8
         assert torch.equal(y2[ec.CONSTANT], beta.view(1, -1))           # exact in the statement too
         # the 16-bit check of the value before the cast: the two-pass statement passes it, the one-pass variance does not
         for prec in (_lib.BF16, _lib.F16):

@@ -11,20 +11,13 @@ import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import _lib
+from op_support import host_lib as lib  # noqa: F401
 
 import epilogue_exact_ref as er
 import gemm_exact_ref as ge
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRECS = (ge.F32, ge.BF16, ge.F16, ge.F16X2)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
 
 
 def _shape(c):

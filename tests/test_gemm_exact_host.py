@@ -3,7 +3,6 @@ declares, and every fault model changes the reference in every tile it touches. 
 import collections
 import ctypes
 import functools
-import importlib.util
 import json
 import os
 
@@ -11,26 +10,12 @@ import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import _lib
+from op_support import host_lib as lib  # noqa: F401
+from op_support import plan_cover as cover  # noqa: F401
 
 import gemm_exact_ref as ge
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def cover():
-    spec = importlib.util.spec_from_file_location("plan_cover", os.path.join(ROOT, "tools", "plan_cover.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @functools.lru_cache(maxsize=2)

@@ -42,6 +42,8 @@ if ROOT not in sys.path:                     # the child process of the ONES tes
 
 import vitvs_amd  # noqa: E402,F401
 from vitvs_amd import _lib  # noqa: E402
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import ptr, stream
 
 import attention_keys_ref as ak  # noqa: E402
 
@@ -55,20 +57,6 @@ def run_id(c, form):
     return f"{ak.case_id(c)}-{form}"
 
 
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def bar(c, form):
     return ak.BAR_F16_RAW_LONG if (c.prec == ak.F16 and form == "raw" and c.N >= 512) else ak.BARS[c.prec]
 
@@ -78,9 +66,9 @@ def _launch(lib, c, form, x):
     rows, D = c.n_img * c.N, c.H * 64
     out = torch.full((rows + GUARD, 2 * D if c.prec == ak.F16X2 else D), float("nan"), dtype=ak.DTYPES[c.prec], device="cuda")
     if form == "forward":
-        rc = lib.vitvs_op_attention_q(c.prec, _p(x), _p(out), c.n_img, c.N, c.H, 1, _stream())
+        rc = lib.vitvs_op_attention_q(c.prec, ptr(x), ptr(out), c.n_img, c.N, c.H, 1, stream())
     else:
-        rc = lib.vitvs_op_attention(c.prec, _p(x), _p(out), c.n_img, c.N, c.H, _stream())
+        rc = lib.vitvs_op_attention(c.prec, ptr(x), ptr(out), c.n_img, c.N, c.H, stream())
     assert rc == 0, f"{run_id(c, form)}: launch returned {rc}"
     return out
 

@@ -22,6 +22,8 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import ptr, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -116,20 +118,6 @@ def key_id(key):
     return f"{FORM_NAMES.get(form, form)}-{rows}x{cols}-kg{kg}-{goal}"
 
 
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _unit(x):
     return x / x.norm(dim=-1, keepdim=True)
 
@@ -220,8 +208,8 @@ def test_gram_form_matches_fp64(lib, case):
         dn = _descriptors(case, gen)
         dh = torch.empty(3 * frames * T * case.D, dtype=torch.float16, device=dev) if plan[6] else None
         dn_dev = dn.to(dev)
-        rc = lib.vitvs_op_gram_argmax(case.prec, _p(dn_dev), T, case.D, n, int(case.shared), _p(dh), _p(keys_r), _p(keys_c),
-                                      _p(nn1), _p(nn2), _p(sim1), _stream())
+        rc = lib.vitvs_op_gram_argmax(case.prec, ptr(dn_dev), T, case.D, n, int(case.shared), ptr(dh), ptr(keys_r), ptr(keys_c),
+                                      ptr(nn1), ptr(nn2), ptr(sim1), stream())
         ref = dn.double()
     else:
         grid = int(round(T ** 0.5))
@@ -230,8 +218,8 @@ def test_gram_form_matches_fp64(lib, case):
         G = torch.full(((n + 1) * T * T,), float("nan"), dtype=torch.float32, device=dev)
         sq = torch.full(((frames + 1) * T,), float("nan"), dtype=torch.float32, device=dev)
         x_dev = x.to(dev)
-        rc = lib.vitvs_op_gram_stencil(_p(x_dev), T, case.P, case.D, grid, n, int(case.shared), _p(G), _p(sq), _p(keys_r),
-                                       _p(keys_c), _p(nn1), _p(nn2), _p(sim1), _stream())
+        rc = lib.vitvs_op_gram_stencil(ptr(x_dev), T, case.P, case.D, grid, n, int(case.shared), ptr(G), ptr(sq), ptr(keys_r),
+                                       ptr(keys_c), ptr(nn1), ptr(nn2), ptr(sim1), stream())
         ref = _binned_fp64(x, T, case.P, grid)
     assert rc == 0, (case.id, rc, _lib.last_error(None))
     torch.cuda.synchronize()

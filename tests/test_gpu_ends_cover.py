@@ -26,6 +26,8 @@ import torch
 import vitvs_amd  # noqa: F401
 from oracle import resize_ref
 from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import DTYPES, mk, nan_like, ptr, rel_max, stream, to_x2, values
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +37,6 @@ Q_SCALE = float(np.float32(0.125) * np.float32(1.44269504088896340736))   # kAtt
 Q_UNSCALE = float(np.float32(1.0) / np.float32(Q_SCALE))
 WIDTHS = (128, 256, 384, 768, 1024)
 PRECS = [("fp32", _lib.F32), ("bf16", _lib.BF16), ("fp16", _lib.F16), ("f16x2", _lib.F16X2)]
-DTYPES = {_lib.F32: torch.float32, _lib.BF16: torch.bfloat16, _lib.F16: torch.float16, _lib.F16X2: torch.float16}
 # tests/test_gpu_plan_cover.py
 BAR_X = {_lib.F32: 2e-5, _lib.BF16: 2e-6 + 1e-3, _lib.F16: 2e-6 + 1e-3, _lib.F16X2: 2e-5}
 BAR_LN = {_lib.F32: 2e-5, _lib.BF16: 1e-2, _lib.F16: 2e-3, _lib.F16X2: 2e-5}
@@ -65,33 +66,11 @@ LN_TWO_PASS_WORST = 2.1e-5
 LN_ONE_PASS_BEST = 7.7e-3
 
 
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
-
-
 def _gen(*key):
     seed = 0
     for k in key:
         seed = (seed * 1000003 + int(k) + 17) % (2 ** 31)
     return torch.Generator().manual_seed(seed)
-
-
-def _mk(shape, gen, scale=1.0):
-    return (torch.randn(shape, generator=gen) * scale).float()
 
 
 def _dyadic(t, denom):
@@ -100,34 +79,11 @@ def _dyadic(t, denom):
 
 
 # the f16x2 layout (csrc/common.h; the same helpers as tests/test_gpu_plan_cover.py)
-def to_x2(t, exp=0):
-    """fp32 [R, C] -> fp16 [R, 2C]: per 32 columns [hi | lo] of t * 2^exp."""
-    r, c = t.shape
-    ts = t.float() * (2.0 ** exp)
-    hi = ts.clamp(-65504, 65504).half()
-    lo = (ts - hi.float()).half()
-    return torch.stack([hi.view(r, c // 32, 32), lo.view(r, c // 32, 32)], dim=2).reshape(r, 2 * c).contiguous()
-
-
-def from_x2(t):
-    """fp16 [R, 2C] -> the fp64 values hi + lo [R, C]."""
-    r, c2 = t.shape
-    v = t.reshape(r, c2 // 64, 2, 32).double()
-    return (v[:, :, 0] + v[:, :, 1]).reshape(r, c2 // 2)
 
 
 def _operand(prec, t):
     """fp32 [R, C] -> what the kernel is given in the precision (CPU)"""
     return to_x2(t) if prec == _lib.F16X2 else t.to(DTYPES[prec]).contiguous()
-
-
-def _values(prec, out):
-    return from_x2(out) if prec == _lib.F16X2 else out.double()
-
-
-def _nan(prec, rows, cols):
-    """NaN rows of `cols` logical columns in the precision's output layout"""
-    return torch.full((rows, 2 * cols if prec == _lib.F16X2 else cols), float("nan"), dtype=DTYPES[prec], device="cuda")
 
 
 def _nan32(rows, cols):
@@ -197,7 +153,7 @@ def _run_patchify(lib, prec, frames, small, n_des, n_cur, geom, prefix, D, in_hw
     want, grid = patch_rows_ref(small[:n], patch, stride, Kp)
     T = grid * grid
     g = _gen(S, patch, stride, prefix, D)
-    cls, pos = _mk((D,), g), _mk((1 + T, D), g, 0.5)
+    cls, pos = mk((D,), g), mk((1 + T, D), g, 0.5)
 
     def upload(part):
         if part.shape[0] == 0:
@@ -206,12 +162,12 @@ def _run_patchify(lib, prec, frames, small, n_des, n_cur, geom, prefix, D, in_hw
         flat[:part.size] = torch.from_numpy(np.ascontiguousarray(part)).reshape(-1)
         return flat.cuda()
     des, cur = upload(frames[:n_des]), upload(frames[n_des:n])
-    ape = _nan(prec, n * T + GUARD, Kp)
+    ape = nan_like(prec, n * T + GUARD, Kp)
     x = _nan32(n * (T + prefix) + GUARD, D)
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
     clsd, posd = cls.cuda(), pos.cuda()
-    rc = lib.vitvs_op_patchify(prec, _p(des), n_des, _p(cur), n_cur, S, patch, stride, Kp, D, prefix, mean, std, _p(clsd), _p(posd),
-                               in_hw[0], in_hw[1], _p(ape), _p(x), _stream())
+    rc = lib.vitvs_op_patchify(prec, ptr(des), n_des, ptr(cur), n_cur, S, patch, stride, Kp, D, prefix, mean, std, ptr(clsd), ptr(posd),
+                               in_hw[0], in_hw[1], ptr(ape), ptr(x), stream())
     assert rc == 0
     torch.cuda.synchronize()
     what = f"frames {n_des}+{n_cur} prefix {prefix} D {D}"
@@ -253,12 +209,12 @@ def test_patchify_refuses_what_it_cannot_launch(lib):
     S, patch = 64, 16
     frames = torch.zeros(6000 * 64 * 3 + FRAME_SLACK, dtype=torch.uint8, device="cuda")
     cls, pos = torch.zeros(128, device="cuda"), torch.zeros((17, 128), device="cuda")
-    ape, x = _nan(_lib.F32, 16 + GUARD, 768), _nan32(17 + GUARD, 128)
+    ape, x = nan_like(_lib.F32, 16 + GUARD, 768), _nan32(17 + GUARD, 128)
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
 
     def call(Kp=768, in_h=0, in_w=0):
-        return lib.vitvs_op_patchify(_lib.F32, None, 0, _p(frames), 1, S, patch, patch, Kp, 128, 1, mean, std, _p(cls), _p(pos),
-                                     in_h, in_w, _p(ape), _p(x), _stream())
+        return lib.vitvs_op_patchify(_lib.F32, None, 0, ptr(frames), 1, S, patch, patch, Kp, 128, 1, mean, std, ptr(cls), ptr(pos),
+                                     in_h, in_w, ptr(ape), ptr(x), stream())
     assert call(Kp=704) == -2                     # Kp below 3 p^2
     assert call(in_h=0, in_w=5) == -2             # half a geometry
     assert call(in_h=6000, in_w=64) == -3         # one patch draws on ~1900 camera rows: 1900 * 16 * 3 bytes pass 64 KiB of LDS
@@ -273,10 +229,10 @@ EMBED_SHAPES = [(1, 1, 1, 4), (5, 3, 3, 7), (2, 8, 2, 1)]         # P, slices, n
 def embed_inputs(D, P, slices, n_img, T):
     g = _gen(D, P, slices, n_img, T)
     # the buffer is as large as slices of n_img * (T + P) rows would be; the slices are its first slices * n_img * T rows
-    buf = _mk((slices * n_img * (T + P) * D,), g, 0.5)
+    buf = mk((slices * n_img * (T + P) * D,), g, 0.5)
     part = buf[:slices * n_img * T * D].view(slices, n_img * T, D)
-    t = dict(buf=buf, part=part, reg=_mk((max(P - 1, 1), D), g, 2.0), cls=_mk((D,), g), pos=_mk((1 + T, D), g, 0.7),
-             bias=_mk((D,), g, 0.3), gamma=1.0 + 0.1 * _mk((D,), g), beta=0.1 * _mk((D,), g))
+    t = dict(buf=buf, part=part, reg=mk((max(P - 1, 1), D), g, 2.0), cls=mk((D,), g), pos=mk((1 + T, D), g, 0.7),
+             bias=mk((D,), g, 0.3), gamma=1.0 + 0.1 * mk((D,), g), beta=0.1 * mk((D,), g))
     x = torch.empty((n_img, T + P, D), dtype=torch.float64)
     x[:, 0] = t["cls"].double() + t["pos"][0].double()                   # class row
     x[:, 1:P] = t["reg"][:P - 1].double()                                # register rows as given: no position, no bias
@@ -292,26 +248,26 @@ def test_embedding_epilogue(lib, record_property, name, prec, D, P, slices, n_im
     t = embed_inputs(D, P, slices, n_img, T)
     M = n_img * (T + P)
     d = {k: v.cuda() for k, v in t.items() if k not in ("part", "x_ref")}
-    x, out = _nan32(M + GUARD, D), _nan(prec, M + GUARD, D)              # x is write-only: a read of it would spread the NaN
-    rc = lib.vitvs_op_embed_ln(prec, _p(x), _p(d["buf"]), slices, _p(d["bias"]), _p(d["pos"]), _p(d["cls"]),
-                               _p(d["reg"]) if P > 1 else None, _p(d["gamma"]), _p(d["beta"]), _p(out), n_img, T, P, D, 1e-6,
-                               _stream())
+    x, out = _nan32(M + GUARD, D), nan_like(prec, M + GUARD, D)              # x is write-only: a read of it would spread the NaN
+    rc = lib.vitvs_op_embed_ln(prec, ptr(x), ptr(d["buf"]), slices, ptr(d["bias"]), ptr(d["pos"]), ptr(d["cls"]),
+                               ptr(d["reg"]) if P > 1 else None, ptr(d["gamma"]), ptr(d["beta"]), ptr(out), n_img, T, P, D, 1e-6,
+                               stream())
     assert rc == 0
     torch.cuda.synchronize()
     x, out = x.cpu(), out.cpu()
     assert _all_nan(x[M:]) and _all_nan(out[M:]), "rows beyond M were written"
-    got = _values(prec, out[:M])
+    got = values(prec, out[:M])
     assert torch.isfinite(x[:M]).all() and torch.isfinite(got).all()
-    _check(record_property, "x", _rel(x[:M], t["x_ref"]), BAR_X[prec])
-    _check(record_property, "layernorm", _rel(got, layer_norm64(t["x_ref"], t["gamma"], t["beta"])), BAR_LN[prec])
+    _check(record_property, "x", rel_max(x[:M], t["x_ref"]), BAR_X[prec])
+    _check(record_property, "layernorm", rel_max(got, layer_norm64(t["x_ref"], t["gamma"], t["beta"])), BAR_LN[prec])
 
 
 def test_embedding_epilogue_refusals(lib):
     z = torch.zeros((64, 128), device="cuda")
 
     def call(slices=1, P=1, reg=None, D=128):
-        return lib.vitvs_op_embed_ln(_lib.F32, _p(z), _p(z), slices, _p(z), _p(z), _p(z), reg, _p(z), _p(z), _p(z), 1, 4, P, D, 1e-6,
-                                     _stream())
+        return lib.vitvs_op_embed_ln(_lib.F32, ptr(z), ptr(z), slices, ptr(z), ptr(z), ptr(z), reg, ptr(z), ptr(z), ptr(z), 1, 4, P, D, 1e-6,
+                                     stream())
     assert call(slices=0) == -2 and call(slices=9) == -2 and call(P=0) == -2 and call(P=2, reg=None) == -2 and call(D=192) == -2
 
 
@@ -326,10 +282,10 @@ def epilogue_inputs(D, n_img, T, P, slices):
     x0 = -(ls * (sum part + bias)) is an fp32 number and every sum on the way is exact in any order."""
     g = _gen(D, n_img, T, P, slices, 5)
     M = n_img * (T + P)
-    part = _mk((slices, M, D), g, 0.5)
-    bias = _dyadic(_mk((D,), g, 0.3), 256)
+    part = mk((slices, M, D), g, 0.5)
+    bias = _dyadic(mk((D,), g, 0.3), 256)
     ls = torch.randint(2, 7, (D,), generator=g).float() / 4            # 0.5 .. 1.5
-    x0 = _mk((M, D), g)
+    x0 = mk((M, D), g)
     zero_row = (n_img - 1) * (T + P) + P + 1
     part[:, zero_row] = _dyadic(part[:, zero_row], 256)
     return dict(part=part, bias=bias, ls=ls, x0=x0, zero_row=zero_row)
@@ -400,16 +356,16 @@ def test_descriptor_epilogue(lib, record_property, name, prec, D, n_img, T, P, s
                 dn = _nan32(GUARD + toks + GUARD, D) if emit != "sq" else None
                 sq = _nan32(1, GUARD + toks + GUARD)[0] if emit != "dn" else None
                 za, zb = _keys(M * 64), _keys(M * 64)
-                rc = lib.vitvs_op_residual_desc(prec, _p(x), _p(part), slices, _p(bias), _p(ls) if use_ls else None,
-                                                _p(dn[GUARD:]) if dn is not None else None, _p(sq[GUARD:]) if sq is not None else None,
-                                                _p(za), _p(zb), zero_count, T, P, M, D, _stream())
+                rc = lib.vitvs_op_residual_desc(prec, ptr(x), ptr(part), slices, ptr(bias), ptr(ls) if use_ls else None,
+                                                ptr(dn[GUARD:]) if dn is not None else None, ptr(sq[GUARD:]) if sq is not None else None,
+                                                ptr(za), ptr(zb), zero_count, T, P, M, D, stream())
                 assert rc == 0, what
                 torch.cuda.synchronize()
                 _check_keys(za, zb, zero_count, what)
                 xc = x.cpu()
                 assert _all_nan(xc[M:]), f"{what}: rows of x beyond M were written"
                 assert torch.isfinite(xc[:M]).all(), what
-                worst["x"] = max(worst["x"], _rel(xc[:M], x_ref))
+                worst["x"] = max(worst["x"], rel_max(xc[:M], x_ref))
                 assert not xc[t["zero_row"]].any(), f"{what}: the cancelling row did not come out zero"
                 rows = patch_rows_of(xc[:M], n_img, T, P)                        # the x the launch left, patch rows only
                 zr = t["zero_row"] - (n_img - 1) * P - P                         # the zero row among the patch rows
@@ -419,11 +375,11 @@ def test_descriptor_epilogue(lib, record_property, name, prec, D, n_img, T, P, s
                         f"{what}: dn was written outside its {toks} patch rows (class / register rows write nothing)"
                     got = dc[GUARD:GUARD + toks]
                     assert torch.isfinite(got).all() and not got[zr].any(), f"{what}: dn of the zero row is not finite zeros"
-                    worst["dn"] = max(worst["dn"], _rel(got, dn_ref(rows)))
+                    worst["dn"] = max(worst["dn"], rel_max(got, dn_ref(rows)))
                     if D in SAME_LANES:   # "the same arithmetic and summation order as desc_plain_kernel" where the lanes agree
                         plain = _nan32(toks + GUARD, D)
-                        assert lib.vitvs_op_descriptors(_p(x), _p(plain), None, None, n_img, T, P, grid, D, 0, None, None, 0,
-                                                        _stream()) == 0
+                        assert lib.vitvs_op_descriptors(ptr(x), ptr(plain), None, None, n_img, T, P, grid, D, 0, None, None, 0,
+                                                        stream()) == 0
                         torch.cuda.synchronize()
                         assert torch.equal(_bits(plain.cpu()[:toks]), _bits(got)), f"{what}: dn differs from desc_plain_kernel's"
                 if sq is not None:
@@ -431,7 +387,7 @@ def test_descriptor_epilogue(lib, record_property, name, prec, D, n_img, T, P, s
                     assert _all_nan(sc[:GUARD]) and _all_nan(sc[GUARD + toks:]), f"{what}: sq was written outside its {toks} words"
                     got = sc[GUARD:GUARD + toks]
                     assert torch.isfinite(got).all() and float(got[zr]) == 0.0, what
-                    worst["sq"] = max(worst["sq"], _rel(got, sq_ref(rows)))
+                    worst["sq"] = max(worst["sq"], rel_max(got, sq_ref(rows)))
     _check(record_property, "x", worst["x"], BAR_X[prec])
     _check(record_property, "dn", worst["dn"], BAR["epilogue_dn"])
     _check(record_property, "sq", worst["sq"], BAR["epilogue_sq"])
@@ -445,8 +401,8 @@ def test_descriptor_epilogue_refusals(lib):
     za, zb = _keys(M * 64 + 1), _keys(M * 64 + 1)
 
     def call(zero_count=0, dn=dn, T=T, M=M, slices=1):
-        return lib.vitvs_op_residual_desc(_lib.F32, _p(x), _p(part), slices, _p(bias), None, _p(dn), None, _p(za), _p(zb), zero_count,
-                                          T, P, M, D, _stream())
+        return lib.vitvs_op_residual_desc(_lib.F32, ptr(x), ptr(part), slices, ptr(bias), None, ptr(dn), None, ptr(za), ptr(zb), zero_count,
+                                          T, P, M, D, stream())
     assert call(zero_count=M * 64 + 1) == -2
     assert call(dn=None) == -2 and call(T=7) == -2 and call(slices=9) == -2 and call(zero_count=-1) == -2
     torch.cuda.synchronize()
@@ -470,7 +426,7 @@ def binned_gather(rows, n_img, grid):
 
 def descriptor_inputs(grid, P, n_img, D, zero_image):
     """x [n_img, P + T, D]; zero_image: the patch rows of image 0 are zero (every neighbourhood there is), its prefix rows not"""
-    x = _mk((n_img, P + grid * grid, D), _gen(grid, P, n_img, D))
+    x = mk((n_img, P + grid * grid, D), _gen(grid, P, n_img, D))
     if zero_image:
         x[0, P:] = 0.0
     return x
@@ -499,8 +455,8 @@ def test_descriptors(lib, record_property, binned, grid, D):
                 for zero_count in counts[2 * i:2 * i + 2]:
                     dn.fill_(float("nan"))
                     za, zb = _keys(toks * 64), _keys(toks * 64)
-                    assert lib.vitvs_op_descriptors(_p(x), _p(dn), _p(raw), _p(ws), n_img, T, P, grid, D, binned, _p(za), _p(zb),
-                                                    zero_count, _stream()) == 0, what
+                    assert lib.vitvs_op_descriptors(ptr(x), ptr(dn), ptr(raw), ptr(ws), n_img, T, P, grid, D, binned, ptr(za), ptr(zb),
+                                                    zero_count, stream()) == 0, what
                     torch.cuda.synchronize()
                     _check_keys(za, zb, zero_count, what)
                 dc, rc_ = dn.cpu(), raw.cpu()
@@ -510,11 +466,11 @@ def test_descriptors(lib, record_property, binned, grid, D):
                 assert torch.isfinite(dc[:toks]).all()
                 if zero_image:
                     assert not dc[:T].any(), f"{what}: all-zero neighbourhoods do not give zeros"
-                worst = max(worst, _rel(dc[:toks], dn_ref(want_raw)))
+                worst = max(worst, rel_max(dc[:toks], dn_ref(want_raw)))
                 if binned:                       # the form of vitvs_extract_descriptors_ex_dev: raw only
                     raw.fill_(float("nan"))
-                    assert lib.vitvs_op_descriptors(_p(x), None, _p(raw), _p(ws), n_img, T, P, grid, D, 1, None, None, 0,
-                                                    _stream()) == 0, what
+                    assert lib.vitvs_op_descriptors(ptr(x), None, ptr(raw), ptr(ws), n_img, T, P, grid, D, 1, None, None, 0,
+                                                    stream()) == 0, what
                     torch.cuda.synchronize()
                     rc_ = raw.cpu()
                     assert _all_nan(rc_[toks:]) and torch.equal(_bits(rc_[:toks]), _bits(want_raw)), f"{what}: raw-only form"
@@ -526,7 +482,7 @@ def test_descriptors_refusals(lib):
     za, zb = _keys(18 * 64 + 1), _keys(18 * 64 + 1)
 
     def call(binned, grid=3, zero_count=0, dn=dn):
-        return lib.vitvs_op_descriptors(_p(x), _p(dn), None, _p(ws), 2, 9, 1, grid, 128, binned, _p(za), _p(zb), zero_count, _stream())
+        return lib.vitvs_op_descriptors(ptr(x), ptr(dn), None, ptr(ws), 2, 9, 1, grid, 128, binned, ptr(za), ptr(zb), zero_count, stream())
     for binned in (0, 1):
         assert call(binned, grid=2) == -2 and call(binned, grid=4) == -2          # grid * grid != T
         assert call(binned, zero_count=18 * 64 + 1) == -2
@@ -537,7 +493,7 @@ def test_descriptors_refusals(lib):
 
 
 def normalize_inputs(rows, Dp, zero_row):
-    src = _mk((rows, Dp), _gen(rows, Dp, zero_row), 3.0)
+    src = mk((rows, Dp), _gen(rows, Dp, zero_row), 3.0)
     if zero_row:
         src[rows // 2] = 0.0           # a zero row gives zeros
     return src
@@ -551,7 +507,7 @@ def test_normalize_rows(lib, record_property, Dp, rows):
         src = normalize_inputs(rows, Dp, keep_zero_row)
         dst = _nan32(rows + GUARD, Dp)
         srcd = src.cuda()
-        assert lib.vitvs_op_normalize_rows(_p(srcd), _p(dst), rows, Dp, _stream()) == 0
+        assert lib.vitvs_op_normalize_rows(ptr(srcd), ptr(dst), rows, Dp, stream()) == 0
         torch.cuda.synchronize()
         got = dst.cpu()
         assert _all_nan(got[rows:]), "rows beyond the last were written"
@@ -559,9 +515,9 @@ def test_normalize_rows(lib, record_property, Dp, rows):
         if keep_zero_row:
             assert not got[rows // 2].any(), "a zero row does not give zeros"
         if src.any():
-            worst = max(worst, _rel(got[:rows], dn_ref(src)))
+            worst = max(worst, rel_max(got[:rows], dn_ref(src)))
     _check(record_property, "normalize", worst, BAR["normalize"])
-    assert lib.vitvs_op_normalize_rows(_p(srcd), _p(dst), 0, Dp, _stream()) == -2
+    assert lib.vitvs_op_normalize_rows(ptr(srcd), ptr(dst), 0, Dp, stream()) == -2
 
 
 # ================================================================================================================== facet
@@ -582,7 +538,7 @@ def test_facet_is_the_fp32_statement(lib, record_property, name, prec, which, ke
             for T in (1, 9):
                 for n_img in (1, 2):
                     D = 64 * H
-                    qkv = _operand(prec, _mk((n_img * (P + T), 3 * D), _gen(P, H, T, n_img)))
+                    qkv = _operand(prec, mk((n_img * (P + T), 3 * D), _gen(P, H, T, n_img)))
                     if prec == _lib.F16X2:       # load_x2: hi + lo, one fp32 addition
                         v = qkv.view(-1, 3 * D // 32, 2, 32)
                         vals = (v[:, :, 0].float() + v[:, :, 1].float()).reshape(-1, 3 * D)
@@ -592,14 +548,14 @@ def test_facet_is_the_fp32_statement(lib, record_property, name, prec, which, ke
                     for unscale in (1.0, Q_UNSCALE):
                         rows = n_img * (T + keep_cls)
                         out = _nan32(rows + GUARD, D)
-                        assert lib.vitvs_op_facet(prec, _p(qd), _p(out), n_img, T, P, H, which, unscale, keep_cls, _stream()) == 0
+                        assert lib.vitvs_op_facet(prec, ptr(qd), ptr(out), n_img, T, P, H, which, unscale, keep_cls, stream()) == 0
                         torch.cuda.synchronize()
                         got = out.cpu()
                         what = f"P {P} H {H} T {T} n_img {n_img} unscale {unscale}"
                         assert _all_nan(got[rows:]), f"{what}: rows beyond the last were written"
                         assert torch.equal(_bits(got[:rows]), _bits(facet_ref(vals, n_img, T, P, H, which, unscale, keep_cls))), what
     record_property("facet", "0.000e+00")            # equality held in every launch
-    assert lib.vitvs_op_facet(prec, _p(qd), _p(out), 1, 9, 1, 2, 3, 1.0, 0, _stream()) == -2
+    assert lib.vitvs_op_facet(prec, ptr(qd), ptr(out), 1, 9, 1, 2, 3, 1.0, 0, stream()) == -2
 
 
 # =============================================================================================================== saliency
@@ -612,7 +568,7 @@ SCORE_SCALES = (4.0, 2.0)        # per image: the rows are peaked, and different
 def saliency_inputs(prec, T, P, prescaled):
     """qkv [2 * (P + T), 3 * 64 H] in the precision: what the kernel reads and what the reference sees"""
     H, N = SALIENCY_H, P + T
-    q = _mk((2, N, 3 * 64 * H), _gen(T, P))
+    q = mk((2, N, 3 * 64 * H), _gen(T, P))
     for img, s in enumerate(SCORE_SCALES):
         q[img, :, :64 * H] *= s * (0.125 * LOG2E if prescaled else 1.0)
     return q.view(2 * N, -1).to(DTYPES[prec]).contiguous()
@@ -653,7 +609,7 @@ def test_saliency(lib, record_property, name, prec, T, P):
             what = f"heads {heads} prescaled {prescaled}"
             out = _nan32(2 + GUARD, T)
             idx = (C.c_int32 * len(heads))(*heads)
-            assert lib.vitvs_op_saliency(prec, _p(qd), _p(out), 2, T, P, SALIENCY_H, idx, len(heads), prescaled, _stream()) == 0, what
+            assert lib.vitvs_op_saliency(prec, ptr(qd), ptr(out), 2, T, P, SALIENCY_H, idx, len(heads), prescaled, stream()) == 0, what
             torch.cuda.synchronize()
             got = out.cpu()
             assert _all_nan(got[2:]), f"{what}: rows beyond the last image were written"
@@ -672,7 +628,7 @@ def test_saliency_refusals(lib):
 
     def call(prec, heads, n=None):
         idx = (C.c_int32 * len(heads))(*heads)
-        return lib.vitvs_op_saliency(prec, _p(qkv), _p(out), 2, T, P, H, idx, len(heads) if n is None else n, 0, _stream())
+        return lib.vitvs_op_saliency(prec, ptr(qkv), ptr(out), 2, T, P, H, idx, len(heads) if n is None else n, 0, stream())
     assert call(_lib.F16X2, [1]) == -2
     assert call(_lib.F32, [H]) == -2 and call(_lib.F32, [0, -1]) == -2          # a head outside 0 .. H - 1
     assert call(_lib.F32, [0] * 17) == -2 and call(_lib.F32, [0], n=0) == -2    # 1 .. 16 heads
@@ -688,13 +644,13 @@ ORDINARY, OFFSET, SPIKE, CONSTANT = [0, 1], [2, 3], [4], [5]
 def ln_stress_rows(D):
     """two ordinary rows, `+-1000 + randn`, one 300.0 spike among randn, one constant row of 2.0"""
     g = _gen(D, 77)
-    x = _mk((LN_ROWS, D), g)
+    x = mk((LN_ROWS, D), g)
     x[0:2] = x[0:2] * 3.0 + 0.7
     x[2] += 1000.0
     x[3] -= 1000.0
     x[4, D // 3] = 300.0
     x[5] = 2.0
-    gamma, beta = 1.0 + 0.1 * _mk((D,), g), 0.1 * _mk((D,), g)
+    gamma, beta = 1.0 + 0.1 * mk((D,), g), 0.1 * mk((D,), g)
     return x, gamma, beta
 
 
@@ -703,8 +659,8 @@ def ln_stress_parts(D, slices):
     exactly 2.0 whatever the order (dyadic terms)"""
     target, _, _ = ln_stress_rows(D)
     g = _gen(D, slices, 78)
-    part = _mk((slices, LN_ROWS, D), g, 0.3)
-    bias = _dyadic(_mk((D,), g, 0.3), 1024)
+    part = mk((slices, LN_ROWS, D), g, 0.3)
+    bias = _dyadic(mk((D,), g, 0.3), 1024)
     part[:, 5] = _dyadic(part[:, 5], 1024)
     acc = part.double().sum(0) + bias.double()
     x0 = (target.double() - acc).float()
@@ -751,10 +707,10 @@ def cast_excess(got, ref, prec):
 def _check_ln_rows(record, prec, tag, out, x_left, gamma, beta):
     """out: the launch's LayerNorm output rows in the precision; x_left: the fp32 rows it normalised"""
     ref = layer_norm64(x_left, gamma, beta)
-    got = _values(prec, out)
+    got = values(prec, out)
     assert torch.isfinite(got).all(), f"{tag}: non-finite outputs"
     if prec in BAR_LN16:
-        _check(record, f"{tag}_all", max(_rel(got[r], ref[r]) for r in range(LN_ROWS)), BAR_LN16[prec])
+        _check(record, f"{tag}_all", max(rel_max(got[r], ref[r]) for r in range(LN_ROWS)), BAR_LN16[prec])
         # The value before the final cast: against the reference cast to the type.  Where the type resolves the fp32 bar of these
         # rows (ulp >= e = BAR_LN_OFFSET * max |ref|) an fp32 value within e of the reference rounds to the reference's 16-bit
         # number or a neighbour: one ulp.  On smaller elements both are rounded from within e of each other: e plus one ulp.
@@ -763,7 +719,7 @@ def _check_ln_rows(record, prec, tag, out, x_left, gamma, beta):
         assert excess <= 1.0, f"{tag}: {excess:.2f} x the allowed distance from the reference cast to the type"
     else:
         for rows, bar, what in ((ORDINARY + SPIKE, BAR_LN[prec], "ordinary"), (OFFSET, BAR_LN_OFFSET, "offset")):
-            _check(record, f"{tag}_{what}", max(_rel(got[r], ref[r]) for r in rows), bar)
+            _check(record, f"{tag}_{what}", max(rel_max(got[r], ref[r]) for r in rows), bar)
     # the constant row: sum, mean and deviations are exact, so out = beta rounded once
     want = _operand(prec, beta.view(1, -1))
     assert torch.equal(_bits(out[CONSTANT]), _bits(want)), f"{tag}: the constant row is not beta rounded once"
@@ -777,8 +733,8 @@ def test_layernorm_stress_rows(lib, record_property, name, prec, D, slices):
     rows, gamma, beta = ln_stress_rows(D)
     gd, bd = gamma.cuda(), beta.cuda()
     # vitvs_op_layernorm on the rows themselves
-    xd, out = rows.cuda(), _nan(prec, M + GUARD, D)
-    assert lib.vitvs_op_layernorm(prec, _p(xd), _p(gd), _p(bd), _p(out), M, D, 1e-6, _stream()) == 0
+    xd, out = rows.cuda(), nan_like(prec, M + GUARD, D)
+    assert lib.vitvs_op_layernorm(prec, ptr(xd), ptr(gd), ptr(bd), ptr(out), M, D, 1e-6, stream()) == 0
     torch.cuda.synchronize()
     out = out.cpu()
     assert _all_nan(out[M:]), "layernorm: rows beyond M were written"
@@ -786,11 +742,11 @@ def test_layernorm_stress_rows(lib, record_property, name, prec, D, slices):
     # vitvs_op_residual_ln: the rows arrive as x0 + sum of `slices` hand-made partial sums + bias
     x0, part, bias, x_ref = ln_stress_parts(D, slices)
     x = torch.cat([x0, torch.full((GUARD, D), float("nan"))]).cuda()
-    pd, biasd, out = part.cuda(), bias.cuda(), _nan(prec, M + GUARD, D)
-    assert lib.vitvs_op_residual_ln(prec, _p(x), _p(pd), slices, _p(biasd), None, _p(gd), _p(bd), _p(out), M, D, 1e-6, _stream()) == 0
+    pd, biasd, out = part.cuda(), bias.cuda(), nan_like(prec, M + GUARD, D)
+    assert lib.vitvs_op_residual_ln(prec, ptr(x), ptr(pd), slices, ptr(biasd), None, ptr(gd), ptr(bd), ptr(out), M, D, 1e-6, stream()) == 0
     torch.cuda.synchronize()
     x, out = x.cpu(), out.cpu()
     assert _all_nan(x[M:]) and _all_nan(out[M:]), "residual_ln: rows beyond M were written"
-    _check(record_property, "residual_ln_x", max(_rel(x[r], x_ref[r]) for r in range(M)), BAR_X[prec])
+    _check(record_property, "residual_ln_x", max(rel_max(x[r], x_ref[r]) for r in range(M)), BAR_X[prec])
     assert torch.equal(x[CONSTANT], torch.full((1, D), 2.0)), "residual_ln: the constant row's sum is not exact"
     _check_ln_rows(record_property, prec, "residual_ln", out[:M], x[:M], gamma, beta)

@@ -19,13 +19,12 @@ than the launch owns - which must stay NaN while every owned element is finite. 
 the exponent a handle would give these weights.  The last test puts vitvs_op_residual_ln on both sides of its store-policy
 switch (M <= 2048) on the stress rows of tests/test_gpu_ends_cover.py.
 """
-import ctypes as C
-
 import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import nan_like, ptr, stream
 
 import epilogue_exact_ref as er
 import gemm_exact_ref as ge
@@ -34,20 +33,6 @@ import test_gpu_ends_cover as ec
 pytestmark = pytest.mark.gpu
 
 GUARD = er.GUARD
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t, offset=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + offset)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _launch(lib, c, A, W, bias, gelu, e):
@@ -61,16 +46,16 @@ def _launch(lib, c, A, W, bias, gelu, e):
     else:
         buf = torch.full((GUARD + (s + 1) * c.M + GUARD, c.N), float("nan"), dtype=torch.float32, device="cuda")
         own = buf[GUARD:GUARD + s * c.M].view(s, c.M, c.N)
-    dst = _p(buf, GUARD * buf.shape[1] * buf.element_size())
+    dst = ptr(buf, GUARD * buf.shape[1] * buf.element_size())
     prev_hint, prev_exp = lib.vitvs_op_plan_in_flight(c.hint), lib.vitvs_op_weight_exponent(e)
     try:
         if c.variant:
-            rc = lib.vitvs_op_linear_variant(c.prec, c.variant, _p(A), _p(W), _p(bias), dst, c.M, c.N, c.K, gelu,
-                                             c.slices if c.epi == ge.PARTIAL else 0, _stream())
+            rc = lib.vitvs_op_linear_variant(c.prec, c.variant, ptr(A), ptr(W), ptr(bias), dst, c.M, c.N, c.K, gelu,
+                                             c.slices if c.epi == ge.PARTIAL else 0, stream())
         elif c.epi == ge.STORE:
-            rc = lib.vitvs_op_linear(c.prec, _p(A), _p(W), _p(bias), dst, c.M, c.N, c.K, gelu, _stream())
+            rc = lib.vitvs_op_linear(c.prec, ptr(A), ptr(W), ptr(bias), dst, c.M, c.N, c.K, gelu, stream())
         else:
-            rc = lib.vitvs_op_linear_partial(c.prec, _p(A), _p(W), dst, c.M, c.N, c.K, c.slices, _stream())
+            rc = lib.vitvs_op_linear_partial(c.prec, ptr(A), ptr(W), dst, c.M, c.N, c.K, c.slices, stream())
     finally:
         lib.vitvs_op_plan_in_flight(prev_hint)
         lib.vitvs_op_weight_exponent(prev_exp)
@@ -114,8 +99,8 @@ def _residual(lib, c, who, own, part_ref, bias, ls):
     x = torch.full((GUARD + M + GUARD, c.N), float("nan"), dtype=torch.float32, device="cuda")
     x[GUARD:GUARD + M] = x0.cuda()
     bd, lsd = bias.cuda(), ls.cuda()
-    rc = lib.vitvs_op_residual_ln(c.prec, _p(x, GUARD * c.N * 4), _p(own), s, _p(bd), _p(lsd), None, None, None, M, c.N, 1e-6,
-                                  _stream())
+    rc = lib.vitvs_op_residual_ln(c.prec, ptr(x, GUARD * c.N * 4), ptr(own), s, ptr(bd), ptr(lsd), None, None, None, M, c.N, 1e-6,
+                                  stream())
     assert rc == 0, f"{who}: vitvs_op_residual_ln returned {rc}"
     torch.cuda.synchronize()
     x = x.cpu()
@@ -159,10 +144,10 @@ def test_residual_ln_on_both_sides_of_its_store_policy_switch(lib, record_proper
     idx = torch.arange(M) % ec.LN_ROWS
     nan = torch.full((GUARD, D), float("nan"))
     x = torch.cat([nan, x0[idx], nan]).cuda()
-    out = ec._nan(prec, GUARD + M + GUARD, D)
+    out = nan_like(prec, GUARD + M + GUARD, D)
     pd, biasd, gd, bd = part[:, idx].contiguous().cuda(), bias.cuda(), gamma.cuda(), beta.cuda()
-    rc = lib.vitvs_op_residual_ln(prec, _p(x, GUARD * D * 4), _p(pd), slices, _p(biasd), None, _p(gd), _p(bd),
-                                  _p(out, GUARD * out.shape[1] * out.element_size()), M, D, 1e-6, _stream())
+    rc = lib.vitvs_op_residual_ln(prec, ptr(x, GUARD * D * 4), ptr(pd), slices, ptr(biasd), None, ptr(gd), ptr(bd),
+                                  ptr(out, GUARD * out.shape[1] * out.element_size()), M, D, 1e-6, stream())
     assert rc == 0
     torch.cuda.synchronize()
     x, out = x.cpu(), out.cpu()

@@ -11,13 +11,12 @@ owns - and, where vitvs_op_residual_ln has the width, sums the slices into x.  T
 output is finite, got == ref everywhere (f16x2: hi + lo == ref).  A miss reports the count and the first few elements with their
 tile, wave and 16-row block.  The row sweeps run every M of a (tile, precision, epilogue) inside one test.
 """
-import ctypes as C
-
 import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import ptr, stream
 
 import gemm_exact_ref as ge
 
@@ -25,20 +24,6 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 3                      # rows in front of and behind every output that no launch may write
 ON_DEVICE = 1 << 28            # M N K from which operands and the fp64 reference are made on the device
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t, offset=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + offset)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class Operands:
@@ -73,16 +58,16 @@ def _launch(lib, c, ops, M):
     else:
         buf = torch.full((GUARD + (s + 1) * M + GUARD, c.N), float("nan"), dtype=torch.float32, device="cuda")
         own = buf[GUARD:GUARD + s * M].view(s, M, c.N)
-    dst = _p(buf, GUARD * buf.shape[1] * buf.element_size())
+    dst = ptr(buf, GUARD * buf.shape[1] * buf.element_size())
     prev_hint, prev_exp = lib.vitvs_op_plan_in_flight(c.hint), lib.vitvs_op_weight_exponent(0)
     try:
         if c.variant:
-            rc = lib.vitvs_op_linear_variant(c.prec, c.variant, _p(ops.A), _p(ops.W), _p(ops.bias), dst, M, c.N, c.K, 0,
-                                             c.slices if c.epi == ge.PARTIAL else 0, _stream())
+            rc = lib.vitvs_op_linear_variant(c.prec, c.variant, ptr(ops.A), ptr(ops.W), ptr(ops.bias), dst, M, c.N, c.K, 0,
+                                             c.slices if c.epi == ge.PARTIAL else 0, stream())
         elif c.epi == ge.STORE:
-            rc = lib.vitvs_op_linear(c.prec, _p(ops.A), _p(ops.W), _p(ops.bias), dst, M, c.N, c.K, 0, _stream())
+            rc = lib.vitvs_op_linear(c.prec, ptr(ops.A), ptr(ops.W), ptr(ops.bias), dst, M, c.N, c.K, 0, stream())
         else:
-            rc = lib.vitvs_op_linear_partial(c.prec, _p(ops.A), _p(ops.W), dst, M, c.N, c.K, c.slices, _stream())
+            rc = lib.vitvs_op_linear_partial(c.prec, ptr(ops.A), ptr(ops.W), dst, M, c.N, c.K, c.slices, stream())
     finally:
         lib.vitvs_op_plan_in_flight(prev_hint)
         lib.vitvs_op_weight_exponent(prev_exp)
@@ -111,8 +96,8 @@ def _residual(lib, c, ops, own):
     x0 = ge.make_x0(M, c.N, "cuda")
     x = torch.full((GUARD + M + GUARD, c.N), float("nan"), dtype=torch.float32, device="cuda")
     x[GUARD:GUARD + M] = x0
-    rc = lib.vitvs_op_residual_ln(c.prec, _p(x, GUARD * c.N * 4), _p(own), s, _p(ops.bias), _p(ops.ls), None, None, None, M, c.N,
-                                  1e-6, _stream())
+    rc = lib.vitvs_op_residual_ln(c.prec, ptr(x, GUARD * c.N * 4), ptr(own), s, ptr(ops.bias), ptr(ops.ls), None, None, None, M, c.N,
+                                  1e-6, stream())
     assert rc == 0, f"{ge.case_id(c)}: vitvs_op_residual_ln returned {rc}"
     torch.cuda.synchronize()
     assert bool(torch.isnan(x[:GUARD]).all()) and bool(torch.isnan(x[GUARD + M:]).all()), f"{ge.case_id(c)}: x guard rows were written"

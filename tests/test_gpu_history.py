@@ -25,7 +25,7 @@ from vitvs_amd.engine import Engine, VitvsError
 
 import history_cases as hc
 import rig_ref as rg
-import test_gpu_servo_cover as cover
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
 
@@ -41,12 +41,12 @@ def _model(kind):
         cfg = config.baseline_config("vits16_224")
         return cfg, weights.synthetic_state_dict(cfg, 0)
     if kind == "law17":
-        return cover._tiny_cfg(16 * 17), None
+        return ls.tiny_cfg(16 * 17), None
     if kind == "tiny_long":
         base = config.vit_config("dino_vits8", 8 * 23)
         cfg = dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
         return cfg, weights.synthetic_state_dict(cfg, 3)
-    cfg = cover._tiny_cfg(224)
+    cfg = ls.tiny_cfg(224)
     return cfg, weights.synthetic_state_dict(cfg, 3)
 
 
@@ -249,8 +249,8 @@ def _run_law(ctx, c):
     t = g * g
     _set_options(ctx, hc.OFF)
     rng = np.random.default_rng(c["table_seed"])
-    nn1, nn2, sim1, mutual = cover._tables(rng, t, (2 * t) // 3)
-    depth, K, pick = cover._depth(rng), cover._intrinsics(rng, ctx.params), c["pick"]
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, (2 * t) // 3)
+    depth, K, pick = ls.depth(rng), ls.intrinsics(rng, ctx.params), c["pick"]
     ident = np.arange(t)
     moved = np.nonzero(nn1 != ident)[0]
     ids, want = None, _lib.STATUS_OK

@@ -7,7 +7,7 @@ second-smallest eigenvalue >= 1e-4 of trace(M) and an eigen-gap >= 1e-6, and eve
 (asserted here, on the CPU side of each comparison).  The law reads no depth: a velocity call without a depth image (camera status
 NO_DEPTH) is followed by the same twist, bit for bit, as one with it."""
 import ctypes as C
-import dataclasses
+import functools
 
 import numpy as np
 import pytest
@@ -19,21 +19,17 @@ from vitvs_amd.engine import Engine, VitvsError
 
 import homography_ref as hr
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
+
 G = 14
 IMG = 16 * G
+_scenario = functools.partial(ls.planted_case, ENGINES, G)
 ZHAT = 0.61
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _pitches(params, stride, img):
-    return stride * params.u_max / img, stride * params.v_max / img
 
 
 def _reference(det, b, cam_status, K, lam, n_iter, pitches, margins=True):
@@ -44,12 +40,8 @@ def _reference(det, b, cam_status, K, lam, n_iter, pitches, margins=True):
     return ref
 
 
-def _host(info):
-    return {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in info.items()}
-
-
 def _compare(v, info, b, ref, what):
-    info = _host(info)
+    info = ls.host(info)
     v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
     assert int(info["status"][b]) == ref["status"], (what, info["status"][b], ref["status"])
     got_info = [int(info[name][b]) for name in Engine.HOMOGRAPHY_INFO_FIELDS]
@@ -61,61 +53,15 @@ def _compare(v, info, b, ref, what):
     assert float(info["sigma"][b]) == ref["sigma"] or abs(float(info["sigma"][b]) - ref["sigma"]) <= 1e-12, what
 
 
-_ENGINES = {}
-
-
-def _engine(max_rows=130):
-    if max_rows not in _ENGINES:
-        params = config.ServoParams(dino_input_size=IMG)
-        _ENGINES[max_rows] = (Engine(_tiny_cfg(IMG), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    eng, params = _ENGINES[max_rows]
-    for option in ("robust_law", "subpatch", "interaction"):
-        eng.set_option(option, 0)
-    return eng, params
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
-
-
-def _law(eng, sc, num_pairs=None, ids=None, select=_lib.SELECT_EXPLICIT, offsets=None, depth=True):
-    ids = sc["ids"] if ids is None else ids
-    k = len(sc["ids"]) if num_pairs is None else num_pairs
-    v, st = eng.servo_from_nn(sc["nn_1"], sc["nn_2"], sc["sim_1"], sc["depth"] if depth else None, sc["K"], mode=select,
-                              selection=[ids] if select == _lib.SELECT_EXPLICIT else ids, num_pairs=k, offsets=offsets)
-    return v.cpu().numpy(), int(st)
-
-
-def _snapshot(eng, v):
-    det = eng.last_details(1)
-    return dict(det, v_c=np.array(v, copy=True))
-
-
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
-
-
-def _scenario(seed, num_pairs, share=0.125):
-    eng, params = _engine()
-    rng = np.random.default_rng(seed)
-    K = (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-         params.v_max / 2 + float(rng.uniform(-20, 20)))
-    return eng, params, rr.planted_scenario(rng, num_pairs, share, params, K=K, g=G, holes=True)
-
-
 @pytest.mark.parametrize("num_pairs", [8, 24, 130])
 def test_device_equals_the_reference_with_and_without_a_depth_image(num_pairs):
     """Random intrinsics, 12 % wrong matches; N = 0 and 4; 130 pairs: L of the camera's law is global.  The call changes nothing
     the velocity call left, and a velocity call with Z = None (NO_DEPTH) is followed by the same twist bit for bit."""
     eng, params, sc = _scenario(71000 + num_pairs, num_pairs)
-    pitches = _pitches(params, 16, IMG)
-    v_c, st = _law(eng, sc)
+    pitches = ls.pitches(params, 16, IMG)
+    v_c, st = ls.servo_law(eng, sc)
     assert st == _lib.STATUS_OK
-    before = _snapshot(eng, v_c)
+    before = ls.snapshot(eng, v_c)
     with_depth = {}
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter)
@@ -123,21 +69,21 @@ def test_device_equals_the_reference_with_and_without_a_depth_image(num_pairs):
         assert ref["status"] == hr.OK or (num_pairs == 8 and n_iter == 4)      # (8 pairs with one wrong match: the first fit maps 6
         _compare(v, info, 0, ref, f"{num_pairs} pairs, N = {n_iter}")          # behind the camera, and 2 rows are too few)
         v_h, info_h = eng.homography_velocity_host(sc["K"], [st], ZHAT, n_iter)          # the host-pointer form: the same launch
-        assert np.array_equal(v_h, v.cpu().numpy()) and _same(_host(info), info_h)
-        with_depth[n_iter] = (v.cpu().numpy(), _host(info))
-    assert _same(_snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
-    v_c, st = _law(eng, sc, depth=False)
+        assert np.array_equal(v_h, v.cpu().numpy()) and ls.same_values(ls.host(info), info_h)
+        with_depth[n_iter] = (v.cpu().numpy(), ls.host(info))
+    assert ls.same_values(ls.snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
+    v_c, st = ls.servo_law(eng, sc, depth=False)
     assert st == _lib.STATUS_NO_DEPTH and not v_c.any()
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter)
-        assert np.array_equal(v.cpu().numpy(), with_depth[n_iter][0]) and _same(_host(info), with_depth[n_iter][1])
+        assert np.array_equal(v.cpu().numpy(), with_depth[n_iter][0]) and ls.same_values(ls.host(info), with_depth[n_iter][1])
         if n_iter == 0:
             assert int(info["status"][0]) == _lib.STATUS_OK and v.cpu().numpy().any()
 
 
 def test_the_depth_scale_scales_the_translation_alone():
     eng, params, sc = _scenario(71500, 24)
-    v_c, st = _law(eng, sc)
+    v_c, st = ls.servo_law(eng, sc)
     v1, i1 = eng.homography_velocity(sc["K"], [st], 1.0)
     v2, i2 = eng.homography_velocity(sc["K"], [st], 0.25)
     v1, v2 = v1.cpu().numpy()[0], v2.cpu().numpy()[0]
@@ -157,16 +103,16 @@ def test_with_the_other_law_options(option):
     else:
         eng.set_goal_depth(np.full((params.v_max, params.u_max), 610, np.uint16))
         eng.set_option("interaction", int(option[-1]))
-    v_c, st = _law(eng, sc, offsets=offsets)
+    v_c, st = ls.servo_law(eng, sc, offsets=offsets)
     assert st == _lib.STATUS_OK
-    before = _snapshot(eng, v_c)
+    before = ls.snapshot(eng, v_c)
     if option == "subpatch":
         assert before["offsets"][0, :24].any()
-    pitches = _pitches(params, 16, IMG)
+    pitches = ls.pitches(params, 16, IMG)
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter)
         _compare(v, info, 0, _reference(before, 0, st, sc["K"], params.lambda_, n_iter, pitches), f"{option}, N = {n_iter}")
-    assert _same(_snapshot(eng, v_c), before)
+    assert ls.same_values(ls.snapshot(eng, v_c), before)
     eng.set_option("interaction", 0)
     eng.set_option("robust_law", 0)
     eng.set_goal_depth(None)
@@ -179,41 +125,41 @@ def test_camera_statuses_and_the_same_image():
     mutual = np.nonzero(sc["nn_2"][sc["nn_1"]] == np.arange(t))[0]
     few = np.intersect1d(mutual, sc["ids"])[:3].astype(np.int32)
     assert len(few) == 3
-    v_c, st = _law(eng, sc, num_pairs=24, ids=few)
+    v_c, st = ls.servo_law(eng, sc, num_pairs=24, ids=few)
     assert st == _lib.STATUS_TOO_FEW
     v, info = eng.homography_velocity(sc["K"], [st], ZHAT, 4)
-    info = _host(info)
+    info = ls.host(info)
     assert int(info["status"][0]) == _lib.STATUS_TOO_FEW and not v.cpu().numpy().any() and np.array_equal(info["H"][0], np.eye(3))
     assert not info["weights"].any() and float(info["sigma"][0]) == 0.0
     # the same camera without a depth image reports NO_DEPTH and has written no usable row: the law counts them itself
-    v_c, st = _law(eng, sc, num_pairs=24, ids=few, depth=False)
+    v_c, st = ls.servo_law(eng, sc, num_pairs=24, ids=few, depth=False)
     assert st == _lib.STATUS_NO_DEPTH
     v, info = eng.homography_velocity(sc["K"], [st], ZHAT, 4)
-    info = _host(info)
+    info = ls.host(info)
     assert int(info["status"][0]) == _lib.STATUS_TOO_FEW and not v.cpu().numpy().any() and int(info["usable"][0]) == 0
     # no correspondence
     ident = dict(sc, nn_1=np.arange(t), nn_2=np.arange(t), sim_1=np.full(t, 0.5, np.float32))
     order = np.random.default_rng(1).permutation(t).astype(np.int32)
-    v_c, st = _law(eng, ident, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
+    v_c, st = ls.servo_law(eng, ident, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
     assert st == _lib.STATUS_NO_CORRESPONDENCE
     v, info = eng.homography_velocity(sc["K"], [st], ZHAT)
     assert int(info["status"][0]) == _lib.STATUS_NO_CORRESPONDENCE and not v.cpu().numpy().any()
     # the same image: OK, v = 0 and H = I exactly, with and without a depth image
     same = dict(sc, sim_1=np.ones(t, np.float32))
     for depth in (True, False):
-        v_c, st = _law(eng, same, num_pairs=24, ids=order, select=_lib.SELECT_ORDER, depth=depth)
+        v_c, st = ls.servo_law(eng, same, num_pairs=24, ids=order, select=_lib.SELECT_ORDER, depth=depth)
         det = eng.last_details(1)
         assert st == (_lib.STATUS_OK if depth else _lib.STATUS_NO_DEPTH) and int(det["info"][0, 2]) == 1
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, 4)
-        info = _host(info)
+        info = ls.host(info)
         assert int(info["status"][0]) == _lib.STATUS_OK and not v.cpu().numpy().any() and np.array_equal(info["H"][0], np.eye(3))
     # a law of four rows: the fewest the homography takes (spread over the grid: OK), and four of one grid row (collinear)
     cand = np.intersect1d(mutual, sc["ids"])
     for what, four in (("four rows", cand[[0, len(cand) // 3, 2 * len(cand) // 3, -1]]), ("four rows of one line", cand[:4])):
-        v_c, st = _law(eng, sc, num_pairs=4, ids=four.astype(np.int32))
+        v_c, st = ls.servo_law(eng, sc, num_pairs=4, ids=four.astype(np.int32))
         assert st == _lib.STATUS_OK
         det = eng.last_details(1)
-        ref = _reference(det, 0, st, sc["K"], params.lambda_, 0, _pitches(params, 16, IMG), margins=False)
+        ref = _reference(det, 0, st, sc["K"], params.lambda_, 0, ls.pitches(params, 16, IMG), margins=False)
         assert ref["info"][0] == 4
         if what == "four rows":
             assert ref["status"] == hr.OK and ref["ratios"][0] >= 1e-4 and ref["gaps"][0] >= 1e-6
@@ -225,7 +171,7 @@ def test_camera_statuses_and_the_same_image():
 
 def test_error_returns():
     params = config.ServoParams(dino_input_size=IMG)
-    eng = Engine(_tiny_cfg(IMG), params, precision="fp32", max_pairs=2, max_rows=48)
+    eng = Engine(ls.tiny_cfg(IMG), params, precision="fp32", max_pairs=2, max_rows=48)
     rng = np.random.default_rng(64)
     sc = rr.planted_scenario(rng, 24, 0.0, params, g=G, holes=True)
     K, st = params.intrinsics(), [0]
@@ -233,7 +179,7 @@ def test_error_returns():
         eng.homography_velocity(K, st)
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         eng.homography_velocity_host(K, st)
-    _law(eng, sc)
+    ls.servo_law(eng, sc)
     v, info = eng.homography_velocity(K, st)
     assert int(info["status"][0]) == _lib.STATUS_OK
     with pytest.raises(VitvsError, match=r"\(-5\)"):           # not the pair count of the last law evaluation
@@ -269,7 +215,7 @@ def test_through_a_vits16_handle():
     k, n = params.num_pairs, 3
     three = lambda a: np.stack([a] * n)   # noqa: E731
     orders = np.stack([np.random.default_rng(70 + b).permutation(cfg.tokens) for b in range(n)]).astype(np.int32)
-    pitches = _pitches(params, cfg.stride, cfg.img_size)
+    pitches = ls.pitches(params, cfg.stride, cfg.img_size)
 
     def check(v_c, st, what):
         st_h = st.cpu().numpy()
@@ -280,8 +226,8 @@ def test_through_a_vits16_handle():
             for b in range(n):
                 ref = _reference(before, b, st_h[b], K, params.lambda_, n_iter, pitches)
                 _compare(v, info, b, ref, f"{what}, pair {b}, N = {n_iter}")
-            out[n_iter] = (v.cpu().numpy(), _host(info))
-        assert _same(dict(eng.last_details(n), v_c=v_c.cpu().numpy()), before)
+            out[n_iter] = (v.cpu().numpy(), ls.host(info))
+        assert ls.same_values(dict(eng.last_details(n), v_c=v_c.cpu().numpy()), before)
         return out
 
     v_c, st = eng.compute_velocity(three(cur), three(des), three(depth), K, mode=_lib.SELECT_ORDER, selection=orders)
@@ -294,7 +240,7 @@ def test_through_a_vits16_handle():
     assert list(st.cpu().numpy()) == [_lib.STATUS_NO_DEPTH] * n
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(K, st, ZHAT, n_iter)
-        assert np.array_equal(v.cpu().numpy(), first[n_iter][0]) and _same(_host(info), first[n_iter][1])
+        assert np.array_equal(v.cpu().numpy(), first[n_iter][0]) and ls.same_values(ls.host(info), first[n_iter][1])
     # a captured update, replayed: the homography law is valid behind it
     eng.set_option("graph_replay", 1)
     cur_d, des_d = eng._frames(three(cur)), eng._frames(three(des))

@@ -8,37 +8,32 @@ law's counters, the winner's id and the start weights at 1, and with N = 0 the w
 row set's, no residual within 1e-6 of the cut-off or of a rejection edge, second-smallest eigenvalues >= 1e-4 of the trace,
 eigen-gaps >= 1e-6), so that no winner, start weight or status can flip."""
 import ctypes as C
-import dataclasses
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import _lib, config
+from vitvs_amd import _lib
 from vitvs_amd.engine import Engine
 
 import homography_consensus_ref as cr
 import homography_ref as hr
-import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
+
 G = 14
 IMG = 16 * G
+_scenario = functools.partial(ls.planted_case, ENGINES, G)
 ZHAT = 0.61
 M = 256
 SEED = 5
 FIELDS = Engine.HOMOGRAPHY_INFO_FIELDS + ("winner", "start_weights")
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _pitches(params, stride, img):
-    return stride * params.u_max / img, stride * params.v_max / img
 
 
 def _reference(det, cam_status, K, lam, n_iter, pitches, n_hyp=M, seed=SEED):
@@ -48,12 +43,8 @@ def _reference(det, cam_status, K, lam, n_iter, pitches, n_hyp=M, seed=SEED):
     return ref
 
 
-def _host(info):
-    return {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in info.items()}
-
-
 def _compare(v, info, ref, what, n_iter):
-    info = _host(info)
+    info = ls.host(info)
     v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
     assert int(info["status"][0]) == ref["status"], (what, info["status"][0], ref["status"])
     got_info = [int(info[name][0]) for name in FIELDS]
@@ -68,47 +59,8 @@ def _compare(v, info, ref, what, n_iter):
     assert float(info["sigma"][0]) == ref["sigma"] or abs(float(info["sigma"][0]) - ref["sigma"]) <= 1e-12, what
 
 
-_ENGINES = {}
-
-
-def _engine(max_rows=130):
-    if max_rows not in _ENGINES:
-        params = config.ServoParams(dino_input_size=IMG)
-        _ENGINES[max_rows] = (Engine(_tiny_cfg(IMG), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    eng, params = _ENGINES[max_rows]
-    for option in ("robust_law", "subpatch", "interaction"):
-        eng.set_option(option, 0)
-    return eng, params
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
-
-
-def _law(eng, sc, offsets=None, depth=True):
-    v, st = eng.servo_from_nn(sc["nn_1"], sc["nn_2"], sc["sim_1"], sc["depth"] if depth else None, sc["K"], mode=_lib.SELECT_EXPLICIT,
-                              selection=[sc["ids"]], num_pairs=len(sc["ids"]), offsets=offsets)
-    return v.cpu().numpy(), int(st)
-
-
 def _snapshot(eng, v):
     return dict(eng.last_details(1), v_c=np.array(v, copy=True))
-
-
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
-
-
-def _scenario(seed, num_pairs, share=0.125):
-    eng, params = _engine()
-    rng = np.random.default_rng(seed)
-    K = (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-         params.v_max / 2 + float(rng.uniform(-20, 20)))
-    return eng, params, rr.planted_scenario(rng, num_pairs, share, params, K=K, g=G, holes=True)
 
 
 def _c_entry(eng, K, st, n_iter, n_hyp, seed):
@@ -133,8 +85,8 @@ def test_device_equals_the_reference_with_and_without_a_depth_image(num_pairs):
     host-pointer form is the same launch; no hypotheses through the new entry point is homography_velocity bit for bit; and a
     velocity call without a depth image (NO_DEPTH) is followed by the same twist bit for bit."""
     eng, params, sc = _scenario(81000 + num_pairs, num_pairs)
-    pitches = _pitches(params, 16, IMG)
-    v_c, st = _law(eng, sc)
+    pitches = ls.pitches(params, 16, IMG)
+    v_c, st = ls.servo_law(eng, sc)
     assert st == _lib.STATUS_OK
     before = _snapshot(eng, v_c)
     with_depth = {}
@@ -144,22 +96,22 @@ def test_device_equals_the_reference_with_and_without_a_depth_image(num_pairs):
         assert ref["status"] == hr.OK and ref["info"][6] >= 1 and 4 <= ref["info"][7] < ref["info"][0]
         _compare(v, info, ref, f"{num_pairs} pairs, N = {n_iter}", n_iter)
         v_h, info_h = eng.homography_velocity_host(sc["K"], [st], ZHAT, n_iter, M, SEED)
-        assert np.array_equal(v_h, v.cpu().numpy()) and _same(_host(info), info_h)
-        with_depth[n_iter] = (v.cpu().numpy(), _host(info))
+        assert np.array_equal(v_h, v.cpu().numpy()) and ls.same_values(ls.host(info), info_h)
+        with_depth[n_iter] = (v.cpu().numpy(), ls.host(info))
         # no hypotheses: the law as it was, through the old and the new entry point
         v0, info0 = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter)
         rc, got = _c_entry(eng, sc["K"], st, n_iter, 0, SEED)
-        info0 = _host(info0)
+        info0 = ls.host(info0)
         assert rc == 0 and np.array_equal(got["v"], v0.cpu().numpy()) and np.array_equal(got["H"], info0["H"].reshape(1, 9))
         assert np.array_equal(got["weights"], info0["weights"]) and np.array_equal(got["sigma"], info0["sigma"])
         assert list(got["info"][0]) == [int(info0[name][0]) for name in Engine.HOMOGRAPHY_INFO_FIELDS] + [0, 0]
         assert not info0["winner"].any() and not info0["start_weights"].any()
-    assert _same(_snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
-    v_c, st = _law(eng, sc, depth=False)
+    assert ls.same_values(_snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
+    v_c, st = ls.servo_law(eng, sc, depth=False)
     assert st == _lib.STATUS_NO_DEPTH and not v_c.any()
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter, M, SEED)
-        assert np.array_equal(v.cpu().numpy(), with_depth[n_iter][0]) and _same(_host(info), with_depth[n_iter][1])
+        assert np.array_equal(v.cpu().numpy(), with_depth[n_iter][0]) and ls.same_values(ls.host(info), with_depth[n_iter][1])
 
 
 @pytest.mark.parametrize("option", ["subpatch", "robust_law"])
@@ -172,16 +124,16 @@ def test_with_the_other_law_options(option):
         offsets = np.random.default_rng(7).uniform(-0.5, 0.5, size=(G * G, 2)).astype(np.float32)
     else:
         eng.set_option("robust_law", 4)
-    v_c, st = _law(eng, sc, offsets=offsets)
+    v_c, st = ls.servo_law(eng, sc, offsets=offsets)
     assert st == _lib.STATUS_OK
     before = _snapshot(eng, v_c)
     if option == "subpatch":
         assert before["offsets"][0, :24].any()
-    pitches = _pitches(params, 16, IMG)
+    pitches = ls.pitches(params, 16, IMG)
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter, M, SEED)
         _compare(v, info, _reference(before, st, sc["K"], params.lambda_, n_iter, pitches), f"{option}, N = {n_iter}", n_iter)
-    assert _same(_snapshot(eng, v_c), before)
+    assert ls.same_values(_snapshot(eng, v_c), before)
     eng.set_option("robust_law", 0)
 
 
@@ -197,16 +149,16 @@ def test_a_third_of_the_matches_permuted_to_wrong_tokens(num_pairs):
     nn2 = np.zeros_like(sc["nn_2"])
     nn2[nn1] = np.arange(len(nn1))
     sc = dict(sc, nn_1=nn1, nn_2=nn2)
-    v_c, st = _law(eng, sc)
+    v_c, st = ls.servo_law(eng, sc)
     assert st == _lib.STATUS_OK
     before = _snapshot(eng, v_c)
-    pitches = _pitches(params, 16, IMG)
+    pitches = ls.pitches(params, 16, IMG)
     for n_iter in (0, 4):
         v, info = eng.homography_velocity(sc["K"], [st], ZHAT, n_iter, M, SEED)
         ref = _reference(before, st, sc["K"], params.lambda_, n_iter, pitches)
         _compare(v, info, ref, f"{num_pairs} pairs, a third permuted, N = {n_iter}", n_iter)
         if n_iter == 0:
-            got = _host(info)["weights"][0]
+            got = ls.host(info)["weights"][0]
             usable = np.asarray(before["selected"][0]) >= 0
             assert np.array_equal(got == 0.0, ref["start"] == 0.0)
             dropped = usable & (ref["start"] == 0.0)
@@ -217,7 +169,7 @@ def test_a_third_of_the_matches_permuted_to_wrong_tokens(num_pairs):
 
 def test_error_returns():
     eng, params, sc = _scenario(84000, 24)
-    v_c, st = _law(eng, sc)
+    v_c, st = ls.servo_law(eng, sc)
     for bad in (-1, 4097):
         assert _c_entry(eng, sc["K"], st, 4, bad, 0)[0] == -2
     assert _c_entry(eng, sc["K"], st, 17, 256, 0)[0] == -2

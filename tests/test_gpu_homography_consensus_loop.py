@@ -12,51 +12,20 @@ nobody had measured these loops before this test was written.  The three end err
 and the mean number of start weights at 1 are printed (DESIGN.md §5h quotes them)."""
 import numpy as np
 import pytest
-import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, quat_xyzw, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
 UPDATES = 120
 RUNS = {"N = 4 alone": (4, 0), "consensus 256, N = 0": (0, 256), "consensus 256, N = 4": (4, 256)}
 
 
-class RgbOnlyCameraSim(CameraSim):
-    """A plain RGB camera: the rendered depth image is thrown away."""
-
-    def sense(self):
-        self.last_rgb, _ = self.scene.render(self.R, self.t)
-        self.last_depth = None
-        self.ctl.image_callback_rgb(self.last_rgb)
-        self.frames += 1
-
-
-def _pose_error(sim):
-    """(position error in cm, orientation error in degrees) against the goal pose (the world frame's origin)."""
-    q = quat_xyzw(sim.R)
-    return float(np.linalg.norm(sim.t) * 100), float(np.rad2deg(2 * np.arccos(min(1.0, abs(q[3])))))
-
-
 def _run_loop(n_iter, consensus):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, law="homography", homography_depth=0.61,
-                                homography_robust_iterations=n_iter, homography_consensus=consensus)
-    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(512, 11), 1.6 / 512, params, plane_z=0.61, device="cuda")
-    goal_rgb, _ = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, params=params, selection="order")
-    ctl.generator = torch.Generator().manual_seed(121)
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = RgbOnlyCameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
+    eng, params, ctl, sim = cl.set_up(dict(law="homography", homography_depth=0.61, homography_robust_iterations=n_iter,
+                                           homography_consensus=consensus), tex_px=512, sim_class=cl.RgbOnlyCameraSim,
+                                      give_params=True, generator_seed=121)
     start_weights, usable = [], []
     law = eng.homography_velocity_host
 
@@ -66,7 +35,7 @@ def _run_loop(n_iter, consensus):
         usable.append(int(info["usable"][0]))
         return v, info
     eng.homography_velocity_host = recording_law
-    track, status, law_status, aborted = [_pose_error(sim)], [], [], None
+    track, status, law_status, aborted = [cl.sim_pose_error(sim)], [], [], None
     for _ in range(UPDATES):
         sim.sense()
         try:
@@ -78,7 +47,7 @@ def _run_loop(n_iter, consensus):
         law_status.append(ctl.last_homography_status)
         lin, ang = ctl.publish_twist()
         sim.apply_twist(lin, ang)
-        track.append(_pose_error(sim))
+        track.append(cl.sim_pose_error(sim))
     depth_seen = ctl.latest_image_depth is not None or ctl.goal_depth is not None
     eng.close()
     return np.array(track), status, law_status, np.array(start_weights), np.array(usable), aborted, depth_seen

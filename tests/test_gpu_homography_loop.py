@@ -8,58 +8,21 @@ depth image and no goal depth ever reach the controller.  Each run must end thro
 a skipped update, every update's camera status must be in {0, 2, 3}, the law must be OK in at least one update, and with N = 4 the
 final position and orientation errors must be below their 5 cm / 5 degree start.  No ratio against the image-based run is asserted:
 none was measured before this test was written; the final pose errors of all three are printed (DESIGN.md §5h quotes them)."""
-import numpy as np
 import pytest
-import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, loop, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, rodrigues
+from planar_sim import CameraSim
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
-
-
-class RgbOnlyCameraSim(CameraSim):
-    """A plain RGB camera: the rendered depth image is thrown away."""
-
-    def sense(self):
-        self.last_rgb, _ = self.scene.render(self.R, self.t)
-        self.last_depth = None
-        self.ctl.image_callback_rgb(self.last_rgb)
-        self.frames += 1
-
 
 def _run_loop(law, n_iter):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, law=law, homography_robust_iterations=n_iter,
-                                homography_depth=0.61)
-    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(128, 11), 1.6 / 128, params, plane_z=0.61, device="cuda")
-    goal_rgb, _ = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, params=params, selection="order")
-    ctl.generator = torch.Generator().manual_seed(121)
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim_class = RgbOnlyCameraSim if law == "homography" else CameraSim
-    sim = sim_class(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
-    status, law_status = [], []
-    real_ibvs = ctl.ibvs
-
-    def recording_ibvs():
-        real_ibvs()
-        status.append(ctl.last_status)
-        law_status.append(ctl.last_homography_status)
-    ctl.ibvs = recording_ibvs
-    logs = []
-    sl = loop.ServoLoop(ctl, np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0]), get_pose=sim.get_pose, apply_twist=sim.apply_twist,
-                        sense=sim.sense, max_iterations=360, log=logs.append)
-    res = sl.run()
+    eng, _, ctl, sim = cl.set_up(dict(law=law, homography_robust_iterations=n_iter, homography_depth=0.61),
+                                 sim_class=cl.RgbOnlyCameraSim if law == "homography" else CameraSim, give_params=True,
+                                 generator_seed=121)
+    status, law_status = cl.record_ibvs(ctl, ["last_status", "last_homography_status"])
+    res, sl, logs = cl.run_servo_loop(ctl, sim)
     depth_seen = ctl.latest_image_depth is not None or ctl.goal_depth is not None
     eng.close()
     return res, sl, logs, status, law_status, len(ctl.velocity_vector_history), depth_seen

@@ -2,13 +2,11 @@
 against their fp64 numpy statement (tests/interaction_ref.py).
 
 Tiny weight-less handles through ``vitvs_servo_from_nn[_ex]_dev`` in EXPLICIT mode, in the style of tests/test_gpu_robust_law.py
-(whose helpers are copied here): both modes on both sides of the LDS / global-workspace edge (R = 2 * pairs <= 128 keeps L in LDS),
-both solvers, zero padding, the same-image shortcut, the statuses that skip the law, a DENSE selection at T = 1024, the quarter
-turn about the optical axis, the depth requirements and error returns of each mode, composition with ``robust_law`` and with a
+(shared helpers: tests/law_support.py): both modes on both sides of the LDS / global-workspace edge (R = 2 * pairs <= 128
+keeps L in LDS), both solvers, zero padding, the same-image shortcut, the statuses that skip the law, a DENSE selection at
+T = 1024, the quarter turn about the optical axis, the depth requirements and error returns of each mode, composition with ``robust_law`` and with a
 given offset table, "off means off", and every entry point of a ViT-S/16 handle.  The bars are the plain law's: s_uv, Z and Z*
 exact, L / e within 1e-13, v_c within 1e-9 (relative L2)."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
@@ -20,8 +18,12 @@ from oracle import servo_ref as sr
 import interaction_ref as ir
 import refine_ref as rf
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
 
 LDLT = -1
 MAX_SWEEPS = 40
@@ -31,66 +33,12 @@ OPTION = {"current": 0, "desired": 1, "mean": 2}
 GOAL_MODES = ("desired", "mean")
 
 
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _tables(rng, t, n_boost):
-    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
-    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
-    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
-    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
-    nn1, nn2 = nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64)
-    mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
-    assert 0 < len(mutual) < t
-    return nn1, nn2, sim1.numpy(), mutual
-
-
-def _depth(rng):
-    depth = synth.depth_pattern().copy()
-    depth.reshape(-1)[rng.integers(0, depth.size, size=depth.size // 7)] = 0     # holes: the 100 m sentinel
-    return depth
-
-
-def _goal_depth(rng):
-    """Another depth image with holes: the goal pose's (a transposed-and-flipped pattern, so Z* differs from Z nearly everywhere)."""
-    d = np.ascontiguousarray(synth.depth_pattern()[::-1, ::-1]).copy()
-    d = (d.astype(np.int64) + 137).clip(1, 65535).astype(np.uint16)
-    d.reshape(-1)[rng.integers(0, d.size, size=d.size // 7)] = 0
-    return d
-
-
-def _intrinsics(rng, params):
-    return (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-            params.v_max / 2 + float(rng.uniform(-20, 20)))
-
-
 def _features(g, img, params, nn1, ids, rows):
     ids = np.asarray(ids, np.int64)
     p1 = torch.from_numpy(np.stack([ids // g, ids % g], 1))
     p2 = torch.from_numpy(np.stack([nn1[ids] // g, nn1[ids] % g], 1))
     s_star, s_ = sr.calculate_uv(sr.patch_centres(p1, img, g), sr.patch_centres(p2, img, g), rows, params.u_max, params.v_max, img)
     return np.asarray(s_star), np.asarray(s_)
-
-
-def _ldlt_passes(L):
-    """servo.hip's pivot test on the normal equations of L (rows x 6), restated in fp64."""
-    G = L.T @ L
-    Lf, dpiv = np.zeros((6, 6)), np.zeros(6)
-    good = True
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for j in range(6):
-            d = G[j, j] - sum(Lf[j, k] ** 2 * dpiv[k] for k in range(j))
-            good = good and d > 1e-8 * G[j, j] and G[j, j] > 0
-            dpiv[j] = d
-            for i in range(j + 1, 6):
-                Lf[i, j] = (G[i, j] - sum(Lf[i, k] * Lf[j, k] * dpiv[k] for k in range(j))) / d
-    return bool(good)
-
-
-def _s_min(params, img, K):
-    return rr.sigma_min(16, params.u_max, params.v_max, img, K[0], K[1])
 
 
 def _check_law(det, b, v, st, ref, s_star, s_, rows, mode, what, solver=None):
@@ -113,34 +61,11 @@ def _check_law(det, b, v, st, ref, s_star, s_, rows, mode, what, solver=None):
     assert err <= VC_BAR, (what, err)
     if solver is not None:
         Lw = ref["L"] if "rob" not in ref else np.sqrt(np.repeat(ref["rob"]["w"], 2))[:, None] * ref["L"]
-        assert (_ldlt_passes(Lw) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
+        assert (ls.ldlt_passes(Lw) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
         if solver == "ldlt":
             assert int(info[4]) == LDLT, (what, "expected LDL^T", info)
         else:
             assert 0 <= int(info[4]) <= MAX_SWEEPS, (what, "expected Jacobi", info)
-
-
-_ENGINES = {}
-
-
-def _servo_engine(g, max_rows, lam=None):
-    """A tiny handle (no weights: the law alone) for a g x g grid."""
-    key = (g, max_rows, lam)
-    if key not in _ENGINES:
-        img = 16 * g
-        params = config.ServoParams(dino_input_size=img) if lam is None else config.ServoParams(dino_input_size=img, lambda_=lam)
-        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    eng, params = _ENGINES[key]
-    eng.set_option("robust_law", 0)
-    return eng, params
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
 
 
 def _run(eng, mode, sc, goal_depth, num_pairs=None, ids=None, depth="scenario", offsets=None, select=_lib.SELECT_EXPLICIT):
@@ -156,10 +81,10 @@ def _run(eng, mode, sc, goal_depth, num_pairs=None, ids=None, depth="scenario", 
 
 
 def _scenario(seed, num_pairs, g=14, max_rows=130, share=0.125):
-    eng, params = _servo_engine(g, max(max_rows, 130))
+    eng, params = ENGINES.fetch(g, max(max_rows, 130), reset=("robust_law",))
     rng = np.random.default_rng(seed)
-    sc = rr.planted_scenario(rng, num_pairs, share, params, K=_intrinsics(rng, params), g=g, holes=True)
-    return eng, params, sc, _goal_depth(rng)
+    sc = rr.planted_scenario(rng, num_pairs, share, params, K=ls.intrinsics(rng, params), g=g, holes=True)
+    return eng, params, sc, ls.goal_depth(rng)
 
 
 # ----------------------------------------------------------------------------- equality with the reference
@@ -187,9 +112,9 @@ def test_both_solvers(num_pairs, solver, mode):
     g, max_rows = 17, 80
     t = g * g
     rng = np.random.default_rng(300 * num_pairs + 7 * OPTION[mode] + (solver == "jacobi"))
-    eng, params = _servo_engine(g, max_rows)
-    nn1, nn2, sim1, mutual = _tables(rng, t, 200)
-    depth, zg, K = _depth(rng), _goal_depth(rng), _intrinsics(rng, params)
+    eng, params = ENGINES.fetch(g, max_rows, reset=("robust_law",))
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, 200)
+    depth, zg, K = ls.depth(rng), ls.goal_depth(rng), ls.intrinsics(rng, params)
     if solver == "ldlt":
         ids = rng.choice(mutual, size=num_pairs, replace=False)
     else:
@@ -226,10 +151,10 @@ def test_zero_padded_rows(mode):
 def test_same_image_and_skipped_laws(mode):
     g, k = 14, 24
     t = g * g
-    eng, params = _servo_engine(g, 130)
+    eng, params = ENGINES.fetch(g, 130, reset=("robust_law",))
     rng = np.random.default_rng(53 + OPTION[mode])
-    nn1, nn2, sim1, mutual = _tables(rng, t, t // 3)
-    depth, zg, K = _depth(rng), _goal_depth(rng), params.intrinsics()
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, t // 3)
+    depth, zg, K = ls.depth(rng), ls.goal_depth(rng), params.intrinsics()
     order = rng.permutation(t).astype(np.int32)
     sc = dict(nn_1=nn1, nn_2=nn2, sim_1=np.ones(t, np.float32), depth=depth, K=K, ids=order)
     v, st, det = _run(eng, mode, sc, zg, num_pairs=k, select=_lib.SELECT_ORDER)
@@ -270,10 +195,10 @@ def test_depth_requirements_of_each_mode():
 def test_error_returns():
     img = 224
     params = config.ServoParams(dino_input_size=img)
-    eng = Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=2, max_rows=48)
+    eng = Engine(ls.tiny_cfg(img), params, precision="fp32", max_pairs=2, max_rows=48)
     rng = np.random.default_rng(55)
     sc = rr.planted_scenario(rng, 24, 0.0, params, holes=True)
-    zg = _goal_depth(rng)
+    zg = ls.goal_depth(rng)
     for mode in GOAL_MODES:                                  # no goal depth in the handle
         with pytest.raises(VitvsError, match=r"\(-5\)"):
             _run(eng, mode, sc, None)
@@ -304,10 +229,10 @@ def test_dense_selection_at_1024_tokens(mode):
     """Every mutual token (a few hundred) enters the law: L in the global workspace, Z* from a table of 1025 entries."""
     g = 32
     t = g * g
-    eng, params = _servo_engine(g, t)
+    eng, params = ENGINES.fetch(g, t, reset=("robust_law",))
     rng = np.random.default_rng(4300 + OPTION[mode])
-    nn1, nn2, sim1, mutual = _tables(rng, t, 300)
-    depth, zg, K = _depth(rng), _goal_depth(rng), _intrinsics(rng, params)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, 300)
+    depth, zg, K = ls.depth(rng), ls.goal_depth(rng), ls.intrinsics(rng, params)
     sc = dict(nn_1=nn1, nn_2=nn2, sim_1=sim1, depth=depth, K=K, ids=None)
     v, st, det = _run(eng, mode, sc, zg, num_pairs=24, select=_lib.SELECT_DENSE)
     rows = int(det["info"][0, 3])
@@ -323,7 +248,7 @@ def test_quarter_turn_about_the_optical_axis():
     """tests/test_interaction_host.py's case on the device: nn_1 is the rotation permutation of the 14 x 14 grid, nn_2 its inverse
     except at three unselected tokens; the device equals the reference and the properties hold on the device's own values."""
     case = ir.quarter_turn_case()
-    eng, params = _servo_engine(case["g"], 130, lam=case["lam"])
+    eng, params = ENGINES.fetch(case["g"], 130, lam=case["lam"], reset=("robust_law",))
     laws = ir.quarter_turn_laws(case)
     vz = {}
     for mode in ir.MODES:
@@ -347,7 +272,7 @@ def test_with_the_robust_law(num_pairs, mode):
     """robust_law = 4 on the mode's L: the residuals e_k - L_k x use the matrix the mode built."""
     eng, params, sc, zg = _scenario(56000 + 10 * num_pairs + OPTION[mode], num_pairs, share=0.25 if num_pairs >= 48 else 0.125)
     s_star, s_, _ = rr.oracle_law(sc, params)
-    ref = ir.law(s_star, s_, sc["depth"], zg, sc["K"], params.lambda_, mode, robust=4, s_min=_s_min(params, sc["img"], sc["K"]))
+    ref = ir.law(s_star, s_, sc["depth"], zg, sc["K"], params.lambda_, mode, robust=4, s_min=ls.s_min(params, sc["img"], sc["K"]))
     rob = ref["rob"]
     assert rob["margin"] >= MARGIN, ("the case sits on the rejection point: choose other inputs", rob["margin"])
     eng.set_option("interaction", OPTION[mode])                                   # (_servo_engine reset robust_law to 0)
@@ -389,16 +314,16 @@ def test_off_means_off():
     params = config.ServoParams(dino_input_size=img)
     rng = np.random.default_rng(58)
     sc = rr.planted_scenario(rng, 24, 0.125, params, holes=True)
-    zg = _goal_depth(rng)
+    zg = ls.goal_depth(rng)
 
     def run(eng):
         v, st = eng.servo_from_nn(sc["nn_1"], sc["nn_2"], sc["sim_1"], sc["depth"], sc["K"], mode=_lib.SELECT_EXPLICIT,
                                   selection=[sc["ids"]], num_pairs=24)
         return v.cpu().numpy(), int(st), eng.last_details(1)
-    fresh = Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)      # never saw the feature
+    fresh = Engine(ls.tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)      # never saw the feature
     v0, st0, d0 = run(fresh)
     fresh.close()
-    eng = Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)
+    eng = Engine(ls.tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)
     eng.set_goal_depth(zg)
     v1, st1, d1 = run(eng)                                                                  # a goal depth, option never set
     eng.set_option("interaction", 2)
@@ -432,7 +357,7 @@ def test_every_entry_point_evaluates_the_mode(mode):
     des, cur = synth.frame_pair(cfg.img_size, 20250705)
     rng = np.random.default_rng(59)
     depth, K = synth.depth_pattern(), params.intrinsics()
-    zg, zg2 = _goal_depth(rng), _goal_depth(rng)
+    zg, zg2 = ls.goal_depth(rng), ls.goal_depth(rng)
     k, g = params.num_pairs, cfg.grid
     identity = np.arange(cfg.tokens, dtype=np.int32)
     with pytest.raises(VitvsError, match=r"\(-5\)"):                                       # no goal depth yet: every entry point refuses
@@ -534,7 +459,7 @@ def test_through_a_pipeline_slot_and_the_controllers(mode):
     cfg, params, sd = _vits16(mode)
     des, cur = synth.frame_pair(cfg.img_size, 20250705)
     rng = np.random.default_rng(60)
-    depth, K, zg = synth.depth_pattern(), params.intrinsics(), _goal_depth(rng)
+    depth, K, zg = synth.depth_pattern(), params.intrinsics(), ls.goal_depth(rng)
     order = rng.permutation(cfg.tokens).astype(np.int32)
     eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(sd)
     eng.set_goal_depth(zg)

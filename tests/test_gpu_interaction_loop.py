@@ -9,50 +9,24 @@ pose-error ratio between the laws is asserted: none was measured before this tes
 (DESIGN.md §5c and profiles/interaction.txt quote them)."""
 import numpy as np
 import pytest
-import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, loop, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
-
 
 def _run_loop(interaction, withhold_depth):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, interaction=interaction)
-    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(128, 11), 1.6 / 128, params, plane_z=0.61, device="cuda")
-    goal_rgb, goal_depth = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, selection="order",
-                           goal_depth=None if interaction == "current" else goal_depth)
-    ctl.generator = torch.Generator().manual_seed(121)
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = CameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
+    eng, params, ctl, sim = cl.set_up(dict(interaction=interaction), give_goal_depth=interaction != "current", generator_seed=121)
 
     def sense():
         sim.sense()
         if withhold_depth:
             ctl.latest_image_depth = None                 # no depth camera at run time
-    status, feat_err = [], []
-    real_ibvs = ctl.ibvs
-
-    def recording_ibvs():
-        real_ibvs()
-        status.append(ctl.last_status)
-        feat_err.append(float(np.linalg.norm(eng.last_details(1)["L"][0, 6, :2 * params.num_pairs])))
-    ctl.ibvs = recording_ibvs
-    logs = []
-    sl = loop.ServoLoop(ctl, np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0]), get_pose=sim.get_pose, apply_twist=sim.apply_twist,
-                        sense=sense, max_iterations=360, log=logs.append)
-    res = sl.run()
+    feat_err = []
+    status, = cl.record_ibvs(ctl, ["last_status"], also=lambda: feat_err.append(
+        float(np.linalg.norm(eng.last_details(1)["L"][0, 6, :2 * params.num_pairs]))))
+    res, sl, logs = cl.run_servo_loop(ctl, sim, sense)
     eng.close()
     return res, sl, logs, status, feat_err, len(ctl.velocity_vector_history)
 

@@ -16,6 +16,7 @@ from vitvs_amd.engine import Engine
 
 import pose_rig_ref as rr
 import rig_ref as rg
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
 
@@ -44,14 +45,6 @@ LAWS = {
 }
 
 
-def _goal_depth(seed):
-    rng = np.random.default_rng(seed)
-    d = np.ascontiguousarray(synth.depth_pattern()[::-1, ::-1]).copy()
-    d = (d.astype(np.int64) + 137 + 11 * seed).clip(1, 65535).astype(np.uint16)
-    d.reshape(-1)[rng.integers(0, d.size, size=d.size // 7)] = 0
-    return d
-
-
 @pytest.fixture(scope="module")
 def call():
     """One velocity call of N pairs on a handle for P, and the laws' inputs in caller arrays of P rows (rows N .. P - 1 are the
@@ -62,7 +55,7 @@ def call():
     curs = np.stack([np.roll(cur, shift=2 * c - 2, axis=1).copy() for c in range(N)])
     depth = np.stack([np.roll(synth.depth_pattern(), 7 * c, axis=1) for c in range(N)])
     eng = Engine(cfg, params, precision="fp32", max_pairs=P, max_rows=R).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    eng.set_goal_depth(np.stack([_goal_depth(s) for s in range(N)]))
+    eng.set_goal_depth(np.stack([ls.goal_depth_of(s) for s in range(N)]))
     g = torch.Generator().manual_seed(11)
     order = torch.stack([torch.randperm(cfg.tokens, generator=g) for _ in range(N)]).to(torch.int32)
     _, st = eng.compute_velocity(curs, np.stack([des] * N), depth, params.intrinsics(), mode=_lib.SELECT_ORDER, selection=order)

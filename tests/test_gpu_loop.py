@@ -26,16 +26,12 @@ from vitvs_amd import _lib, config, loop, servo, synth, weights
 from oracle import servo_ref as sr
 from oracle import vit_ref
 from planar_sim import CameraSim, PlanarScene, rodrigues
+from robust_ref import rel_l2
 
 pytestmark = pytest.mark.gpu
 
 KEY = "vits16_224"
 DT = 0.5            # seconds of simulated motion per update (lambda * dt = 0.015: e-folding in 67 updates)
-
-
-def _rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def _setup(precision, selection):
@@ -85,8 +81,8 @@ def test_closed_loop_raw_twist_equals_the_oracle_update_by_update():
             identical += 1
             assert np.array_equal(det["selected"][0, :params.num_pairs], out["corr"]["selected"].numpy())   # the same draw
             assert np.array_equal(det["s_uv"][0, :params.num_pairs, 2:], out["s_uv"])
-            assert _rel_l2(ctl._raw_v, out["v_c"]) <= 1e-9
-            assert _rel_l2(ctl.v_c, ema.update(out["v_c"])) <= 1e-9
+            assert rel_l2(ctl._raw_v, out["v_c"]) <= 1e-9
+            assert rel_l2(ctl.v_c, ema.update(out["v_c"])) <= 1e-9
         else:       # an arg-max on the other side of a numerical tie changes the candidate list and hence the draw:
             S = sr.cosine_matrix(goal_tokens, _oracle_tokens(cfg, sd, sim.last_rgb), exact_order=False).numpy()
             for got, ref, M in ((det["nn_1"][0], n1, S), (det["nn_2"][0], n2, S.T)):

@@ -11,33 +11,13 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import attention_ref, mk, ptr, rel_max, stream
 
 pytestmark = pytest.mark.gpu
 
 F32_TOL = 2e-5
 BF16_TOL = 1.5e-2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
-
-
-def _mk(shape, gen, scale=1.0):
-    return (torch.randn(shape, generator=gen) * scale).float()
 
 
 F16_TOL = 2e-3   # fp16 operands: 11-bit significand, output rounding 2^-11
@@ -51,19 +31,19 @@ PRECS = [("fp32", _lib.F32, torch.float32, F32_TOL), ("bf16", _lib.BF16, torch.b
                                         (985, 2304, 768, 0), (2364, 3072, 768, 1), (788, 3072, 768, 1)])
 def test_linear(lib, name, prec, dtype, tol, M, N, K, gelu):
     g = torch.Generator().manual_seed(M * 7 + N)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((N, K), g, K ** -0.5).to(dtype)
-    bias = _mk((N,), g, 0.1)
+    A = mk((M, K), g).to(dtype)
+    W = mk((N, K), g, K ** -0.5).to(dtype)
+    bias = mk((N,), g, 0.1)
     ref = A.double() @ W.double().t() + bias.double()
     if gelu:
         ref = torch.nn.functional.gelu(ref)
     Ad, Wd, bd = A.cuda(), W.cuda(), bias.cuda()
     out = torch.full((M, N), float("nan"), dtype=dtype, device="cuda")
-    rc = lib.vitvs_op_linear(prec, _p(Ad), _p(Wd), _p(bd), _p(out), M, N, K, gelu, _stream())
+    rc = lib.vitvs_op_linear(prec, ptr(Ad), ptr(Wd), ptr(bd), ptr(out), M, N, K, gelu, stream())
     assert rc == 0
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
-    assert _rel(out.cpu(), ref) <= tol
+    assert rel_max(out.cpu(), ref) <= tol
 
 
 @pytest.fixture
@@ -83,18 +63,18 @@ def test_linear_under_the_in_flight_plan(lib, in_flight_plan, name, prec, dtype,
     t = (C.c_int32 * 3)()
     assert lib.vitvs_op_linear_tile(prec, M, N, K, 0, t) == 0 and t[0] == 64 and t[2] == 1
     g = torch.Generator().manual_seed(M * 7 + N)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((N, K), g, K ** -0.5).to(dtype)
-    bias = _mk((N,), g, 0.1)
+    A = mk((M, K), g).to(dtype)
+    W = mk((N, K), g, K ** -0.5).to(dtype)
+    bias = mk((N,), g, 0.1)
     ref = A.double() @ W.double().t() + bias.double()
     if gelu:
         ref = torch.nn.functional.gelu(ref)
     guard = 3                                            # rows behind the matrix must stay untouched by the row stores
     out = torch.full((M + guard, N), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_linear(prec, _p(A.cuda()), _p(W.cuda()), _p(bias.cuda()), _p(out), M, N, K, gelu, _stream()) == 0
+    assert lib.vitvs_op_linear(prec, ptr(A.cuda()), ptr(W.cuda()), ptr(bias.cuda()), ptr(out), M, N, K, gelu, stream()) == 0
     torch.cuda.synchronize()
     assert torch.isnan(out[M:].float()).all()
-    assert _rel(out[:M].cpu(), ref) <= tol
+    assert rel_max(out[:M].cpu(), ref) <= tol
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", PRECS)
@@ -106,29 +86,29 @@ def test_split_k_pair_under_the_in_flight_plan(lib, in_flight_plan, name, prec, 
     slices = lib.vitvs_op_splitk_slices(prec, M, D, K)
     assert slices == 2
     g = torch.Generator().manual_seed(M + D + K)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((D, K), g, K ** -0.5).to(dtype)
-    bias = _mk((D,), g, 0.1)
-    x0 = _mk((M, D), g)
+    A = mk((M, K), g).to(dtype)
+    W = mk((D, K), g, K ** -0.5).to(dtype)
+    bias = mk((D,), g, 0.1)
+    x0 = mk((M, D), g)
     x_ref = x0.double() + A.double() @ W.double().t() + bias.double()
     Ad, Wd, bd = A.cuda(), W.cuda(), bias.cuda()
     x = x0.clone().cuda()
     part = torch.full((slices, M, D), float("nan"), dtype=torch.float32, device="cuda")
-    assert lib.vitvs_op_linear_partial(prec, _p(Ad), _p(Wd), _p(part), M, D, K, slices, _stream()) == 0
-    assert lib.vitvs_op_residual_ln(prec, _p(x), _p(part), slices, _p(bd), None, None, None, None, M, D, 1e-6, _stream()) == 0
+    assert lib.vitvs_op_linear_partial(prec, ptr(Ad), ptr(Wd), ptr(part), M, D, K, slices, stream()) == 0
+    assert lib.vitvs_op_residual_ln(prec, ptr(x), ptr(part), slices, ptr(bd), None, None, None, None, M, D, 1e-6, stream()) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(part).all()
-    assert _rel(x.cpu(), x_ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)
+    assert rel_max(x.cpu(), x_ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)
     # the same two slices without the hint (plain 3-D grid, the 8-wave plan where it applies)
     lib.vitvs_op_plan_in_flight(1)
     part1 = torch.full((slices, M, D), float("nan"), dtype=torch.float32, device="cuda")
-    assert lib.vitvs_op_linear_partial(prec, _p(Ad), _p(Wd), _p(part1), M, D, K, slices, _stream()) == 0
+    assert lib.vitvs_op_linear_partial(prec, ptr(Ad), ptr(Wd), ptr(part1), M, D, K, slices, stream()) == 0
     torch.cuda.synchronize()
     lib.vitvs_op_plan_in_flight(3)
     ref_slices = torch.stack([A[:, z * (K // 2):(z + 1) * (K // 2)].double() @ W[:, z * (K // 2):(z + 1) * (K // 2)].double().t()
                               for z in range(2)])
     for got in (part, part1):                            # each slice holds ITS half of K, whichever workgroup computed it
-        assert _rel(got.cpu(), ref_slices) <= (tol if prec == _lib.F32 else 1e-3)
+        assert rel_max(got.cpu(), ref_slices) <= (tol if prec == _lib.F32 else 1e-3)
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", PRECS)
@@ -139,11 +119,11 @@ def test_split_k_pair_under_the_in_flight_plan(lib, in_flight_plan, name, prec, 
                                           (3100, 768, 64, True)])
 def test_linear_residual(lib, name, prec, dtype, tol, M, N, K, use_ls):
     g = torch.Generator().manual_seed(M + N + K)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((N, K), g, K ** -0.5).to(dtype)
-    bias = _mk((N,), g, 0.1)
-    ls = (1.0 + 0.3 * _mk((N,), g)) if use_ls else None
-    x0 = _mk((M, N), g)
+    A = mk((M, K), g).to(dtype)
+    W = mk((N, K), g, K ** -0.5).to(dtype)
+    bias = mk((N,), g, 0.1)
+    ls = (1.0 + 0.3 * mk((N,), g)) if use_ls else None
+    x0 = mk((M, N), g)
     upd = A.double() @ W.double().t() + bias.double()
     if use_ls:
         upd = upd * ls.double()
@@ -151,34 +131,26 @@ def test_linear_residual(lib, name, prec, dtype, tol, M, N, K, use_ls):
     x = x0.clone().cuda()
     Ad, Wd, bd = A.cuda(), W.cuda(), bias.cuda()
     lsd = ls.cuda() if use_ls else None
-    rc = lib.vitvs_op_linear_residual(prec, _p(Ad), _p(Wd), _p(bd), _p(lsd), _p(x), M, N, K, _stream())
+    rc = lib.vitvs_op_linear_residual(prec, ptr(Ad), ptr(Wd), ptr(bd), ptr(lsd), ptr(x), M, N, K, stream())
     assert rc == 0
     torch.cuda.synchronize()
-    assert _rel(x.cpu(), ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)  # 16-bit operands: fp32 accumulate, fp32 output
+    assert rel_max(x.cpu(), ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)  # 16-bit operands: fp32 accumulate, fp32 output
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", PRECS)
 @pytest.mark.parametrize("M,D", [(394, 768), (394, 384), (7, 1024), (1, 128), (2740, 1024)])
 def test_layernorm(lib, name, prec, dtype, tol, M, D):
     g = torch.Generator().manual_seed(D + M)
-    x = _mk((M, D), g, 3.0) + 0.7
-    gamma = 1.0 + 0.1 * _mk((D,), g)
-    beta = 0.1 * _mk((D,), g)
+    x = mk((M, D), g, 3.0) + 0.7
+    gamma = 1.0 + 0.1 * mk((D,), g)
+    beta = 0.1 * mk((D,), g)
     ref = torch.nn.functional.layer_norm(x.double(), (D,), gamma.double(), beta.double(), 1e-6)
     out = torch.empty((M, D), dtype=dtype, device="cuda")
     xd, gd, bd = x.cuda(), gamma.cuda(), beta.cuda()
-    rc = lib.vitvs_op_layernorm(prec, _p(xd), _p(gd), _p(bd), _p(out), M, D, 1e-6, _stream())
+    rc = lib.vitvs_op_layernorm(prec, ptr(xd), ptr(gd), ptr(bd), ptr(out), M, D, 1e-6, stream())
     assert rc == 0
     torch.cuda.synchronize()
-    assert _rel(out.cpu(), ref) <= {_lib.F32: 5e-6, _lib.BF16: 8e-3, _lib.F16: 1e-3}[prec]
-
-
-def _attention_ref(qkv, n_img, N, H):
-    D = H * 64
-    q, k, v = qkv.double().reshape(n_img, N, 3, H, 64).unbind(2)
-    q, k, v = (t.transpose(1, 2) for t in (q, k, v))
-    att = ((q @ k.transpose(-2, -1)) * 0.125).softmax(-1)
-    return (att @ v).transpose(1, 2).reshape(n_img * N, D)
+    assert rel_max(out.cpu(), ref) <= {_lib.F32: 5e-6, _lib.BF16: 8e-3, _lib.F16: 1e-3}[prec]
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", PRECS)
@@ -189,16 +161,16 @@ def _attention_ref(qkv, n_img, N, H):
 def test_attention(lib, name, prec, dtype, tol, n_img, N, H, scale):
     g = torch.Generator().manual_seed(N * 3 + H)
     D = H * 64
-    qkv = _mk((n_img * N, 3 * D), g, scale).to(dtype)
-    ref = _attention_ref(qkv, n_img, N, H)
+    qkv = mk((n_img * N, 3 * D), g, scale).to(dtype)
+    ref = attention_ref(qkv, n_img, N, H)
     out = torch.full((n_img * N, D), float("nan"), dtype=dtype, device="cuda")
     qd = qkv.cuda()
-    rc = lib.vitvs_op_attention(prec, _p(qd), _p(out), n_img, N, H, _stream())
+    rc = lib.vitvs_op_attention(prec, ptr(qd), ptr(out), n_img, N, H, stream())
     assert rc == 0
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
     # raw q: from 512 tokens on the 16-bit kernel scales q itself, one more 16-bit rounding of q than the forward's form below
-    assert _rel(out.cpu(), ref) <= {_lib.F32: 1e-5, _lib.BF16: 2e-2, _lib.F16: 4e-3 if N >= 512 else 3e-3}[prec]
+    assert rel_max(out.cpu(), ref) <= {_lib.F32: 1e-5, _lib.BF16: 2e-2, _lib.F16: 4e-3 if N >= 512 else 3e-3}[prec]
     if prec != _lib.F32:
         # the forward's form: q carries 0.125 * log2(e), applied in fp32 BEFORE the one rounding to 16 bits (the handle folds
         # it into the q rows of the qkv weights); reference = softmax of the values the kernel is given, 2^(q' . k)
@@ -207,12 +179,12 @@ def test_attention(lib, name, prec, dtype, tol, n_img, N, H, scale):
         qs = qs.to(dtype)
         t = qs.double().clone()
         t[:, :D] /= 0.125 * 1.4426950408889634
-        ref_q = _attention_ref(t, n_img, N, H)
+        ref_q = attention_ref(t, n_img, N, H)
         out2 = torch.full((n_img * N, D), float("nan"), dtype=dtype, device="cuda")
         qsd = qs.cuda()
-        assert lib.vitvs_op_attention_q(prec, _p(qsd), _p(out2), n_img, N, H, 1, _stream()) == 0
+        assert lib.vitvs_op_attention_q(prec, ptr(qsd), ptr(out2), n_img, N, H, 1, stream()) == 0
         torch.cuda.synchronize()
-        assert _rel(out2.cpu(), ref_q) <= {_lib.BF16: 2e-2, _lib.F16: 3e-3}[prec]
+        assert rel_max(out2.cpu(), ref_q) <= {_lib.BF16: 2e-2, _lib.F16: 3e-3}[prec]
 
 
 def test_attention_asymmetric_values_catch_transposed_operands(lib):
@@ -224,14 +196,14 @@ def test_attention_asymmetric_values_catch_transposed_operands(lib):
     qkv[:, 0] = 40.0  # q . k = 40 * k[0]
     qkv[:, 64] = torch.where(keys == 77, 40.0, -40.0)  # softmax collapses onto key 77
     qkv[:, 128:192] = keys[:, None] * 0.5 + torch.arange(64, dtype=torch.float32)[None, :] * 0.01
-    ref = _attention_ref(qkv, 1, N, H)
+    ref = attention_ref(qkv, 1, N, H)
     for prec, dtype, tol in ((_lib.F32, torch.float32, 1e-5), (_lib.BF16, torch.bfloat16, 1e-2), (_lib.F16, torch.float16, 2e-3)):
         q = qkv.to(dtype)
         out = torch.empty((N, 64), dtype=dtype, device="cuda")
         qd = q.cuda()
-        assert lib.vitvs_op_attention(prec, _p(qd), _p(out), 1, N, H, _stream()) == 0
+        assert lib.vitvs_op_attention(prec, ptr(qd), ptr(out), 1, N, H, stream()) == 0
         torch.cuda.synchronize()
-        assert _rel(out.cpu(), _attention_ref(q, 1, N, H)) <= tol
+        assert rel_max(out.cpu(), attention_ref(q, 1, N, H)) <= tol
     assert float(ref[0, 0]) == pytest.approx(38.5, abs=1e-6)
 
 
@@ -243,12 +215,12 @@ def test_attention_asymmetric_values_catch_transposed_operands(lib):
 def test_split_k_pair(lib, name, prec, dtype, tol, M, D, K, use_ls, use_ln):
     """linear_partial + residual_ln == x + ls * (A W^T + bias), then LayerNorm (the proj / fc2 path of the forward)."""
     g = torch.Generator().manual_seed(M + D + K)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((D, K), g, K ** -0.5).to(dtype)
-    bias = _mk((D,), g, 0.1)
-    ls = (1.0 + 0.3 * _mk((D,), g)) if use_ls else None
-    gamma, beta = 1.0 + 0.1 * _mk((D,), g), 0.1 * _mk((D,), g)
-    x0 = _mk((M, D), g)
+    A = mk((M, K), g).to(dtype)
+    W = mk((D, K), g, K ** -0.5).to(dtype)
+    bias = mk((D,), g, 0.1)
+    ls = (1.0 + 0.3 * mk((D,), g)) if use_ls else None
+    gamma, beta = 1.0 + 0.1 * mk((D,), g), 0.1 * mk((D,), g)
+    x0 = mk((M, D), g)
     upd = A.double() @ W.double().t() + bias.double()
     if use_ls:
         upd = upd * ls.double()
@@ -262,13 +234,13 @@ def test_split_k_pair(lib, name, prec, dtype, tol, M, D, K, use_ls, use_ln):
     x = x0.clone().cuda()
     part = torch.full((slices, M, D), float("nan"), dtype=torch.float32, device="cuda")
     out = torch.full((M, D), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_linear_partial(prec, _p(Ad), _p(Wd), _p(part), M, D, K, slices, _stream()) == 0
-    assert lib.vitvs_op_residual_ln(prec, _p(x), _p(part), slices, _p(bd), _p(lsd), _p(gd) if use_ln else None,
-                                    _p(bed) if use_ln else None, _p(out) if use_ln else None, M, D, 1e-6, _stream()) == 0
+    assert lib.vitvs_op_linear_partial(prec, ptr(Ad), ptr(Wd), ptr(part), M, D, K, slices, stream()) == 0
+    assert lib.vitvs_op_residual_ln(prec, ptr(x), ptr(part), slices, ptr(bd), ptr(lsd), ptr(gd) if use_ln else None,
+                                    ptr(bed) if use_ln else None, ptr(out) if use_ln else None, M, D, 1e-6, stream()) == 0
     torch.cuda.synchronize()
-    assert _rel(x.cpu(), x_ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)      # fp32 accumulate, fp32 residual stream
+    assert rel_max(x.cpu(), x_ref) <= (tol if prec == _lib.F32 else 2e-6 + 1e-3)      # fp32 accumulate, fp32 residual stream
     if use_ln:
-        assert _rel(out.cpu(), y_ref) <= {_lib.F32: 2e-5, _lib.BF16: 1e-2, _lib.F16: 2e-3}[prec]
+        assert rel_max(out.cpu(), y_ref) <= {_lib.F32: 2e-5, _lib.BF16: 1e-2, _lib.F16: 2e-3}[prec]
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])
@@ -282,20 +254,20 @@ def test_linear_tile_families_agree_with_the_reference(lib, name, prec, dtype, t
     if variant >= 128 and N % {1192: 128, 1256: 256}.get(variant, variant) != 0:
         pytest.skip("this tile width does not divide N")
     g = torch.Generator().manual_seed(M * 3 + N + K)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((N, K), g, K ** -0.5).to(dtype)
-    bias = _mk((N,), g, 0.1)
+    A = mk((M, K), g).to(dtype)
+    W = mk((N, K), g, K ** -0.5).to(dtype)
+    bias = mk((N,), g, 0.1)
     ref = A.double() @ W.double().t() + bias.double()
     if gelu:
         ref = torch.nn.functional.gelu(ref)
     Ad, Wd, bd = A.cuda(), W.cuda(), bias.cuda()
     out = torch.full((M + 3, N), float("nan"), dtype=dtype, device="cuda")      # 3 guard rows behind the matrix
-    rc = lib.vitvs_op_linear_variant(prec, variant, _p(Ad), _p(Wd), _p(bd), _p(out), M, N, K, gelu, 0, _stream())
+    rc = lib.vitvs_op_linear_variant(prec, variant, ptr(Ad), ptr(Wd), ptr(bd), ptr(out), M, N, K, gelu, 0, stream())
     assert rc == 0
     torch.cuda.synchronize()
     assert torch.isnan(out[M:].float()).all(), "rows beyond M were written"
     assert torch.isfinite(out[:M].float()).all()
-    assert _rel(out[:M].cpu(), ref) <= tol
+    assert rel_max(out[:M].cpu(), ref) <= tol
 
 
 @pytest.mark.parametrize("variant", [256, 192, 128, 1192, 1256, 1, 2])
@@ -305,17 +277,17 @@ def test_linear_partial_tile_families(lib, variant, M, N, K, slices):
     if variant >= 128 and N % {1192: 128, 1256: 256}.get(variant, variant) != 0:
         pytest.skip("this tile width does not divide N")
     g = torch.Generator().manual_seed(M + N + K + slices)
-    A = _mk((M, K), g).to(torch.bfloat16)
-    W = _mk((N, K), g, K ** -0.5).to(torch.bfloat16)
+    A = mk((M, K), g).to(torch.bfloat16)
+    W = mk((N, K), g, K ** -0.5).to(torch.bfloat16)
     Ad, Wd = A.cuda(), W.cuda()
     part = torch.full((slices, M, N), float("nan"), dtype=torch.float32, device="cuda")
-    rc = lib.vitvs_op_linear_variant(_lib.BF16, variant, _p(Ad), _p(Wd), None, _p(part), M, N, K, 0, slices, _stream())
+    rc = lib.vitvs_op_linear_variant(_lib.BF16, variant, ptr(Ad), ptr(Wd), None, ptr(part), M, N, K, 0, slices, stream())
     assert rc == 0
     torch.cuda.synchronize()
     ks = K // slices
     for z in range(slices):
         ref = A[:, z * ks:(z + 1) * ks].double() @ W[:, z * ks:(z + 1) * ks].double().t()
-        assert _rel(part[z].cpu(), ref) <= 2e-6 + 1e-3
+        assert rel_max(part[z].cpu(), ref) <= 2e-6 + 1e-3
 
 
 def test_long_attention_rescale_branch_is_forced(lib):
@@ -324,16 +296,16 @@ def test_long_attention_rescale_branch_is_forced(lib):
     loop, with and without a ragged last tile; full-tensor fp64 reference."""
     for N in (640, 777):
         g = torch.Generator().manual_seed(N)
-        qkv = _mk((N, 192), g, 0.5)
+        qkv = mk((N, 192), g, 0.5)
         for qrow, krow in ((3, 70), (130, 400), (131, 639), (600, N - 1), (17, 5)):
             qkv[krow, 64:128] = qkv[qrow, 0:64] * 6.0          # key `krow` aligned with query `qrow`: a late, large maximum
         for prec, dtype, tol in ((_lib.BF16, torch.bfloat16, 2e-2), (_lib.F16, torch.float16, 3e-3)):
             q = qkv.to(dtype)
             out = torch.full((N, 64), float("nan"), dtype=dtype, device="cuda")
             qd = q.cuda()
-            assert lib.vitvs_op_attention(prec, _p(qd), _p(out), 1, N, 1, _stream()) == 0
+            assert lib.vitvs_op_attention(prec, ptr(qd), ptr(out), 1, N, 1, stream()) == 0
             torch.cuda.synchronize()
-            assert _rel(out.cpu(), _attention_ref(q, 1, N, 1)) <= tol
+            assert rel_max(out.cpu(), attention_ref(q, 1, N, 1)) <= tol
 
 
 def test_split_attention_on_two_streams_at_once(lib):
@@ -343,22 +315,22 @@ def test_split_attention_on_two_streams_at_once(lib):
     n_img, N, H = 1, 1370, 16                                   # 352 query blocks -> keys split in two ranges
     D = H * 64
     g = torch.Generator().manual_seed(99)
-    qa = _mk((n_img * N, 3 * D), g).to(torch.bfloat16).cuda()
-    qb = _mk((n_img * N, 3 * D), g, 2.0).to(torch.bfloat16).cuda()
+    qa = mk((n_img * N, 3 * D), g).to(torch.bfloat16).cuda()
+    qb = mk((n_img * N, 3 * D), g, 2.0).to(torch.bfloat16).cuda()
     alone = []
     for q in (qa, qb):
         out = torch.empty((n_img * N, D), dtype=torch.bfloat16, device="cuda")
-        assert lib.vitvs_op_attention(_lib.BF16, _p(q), _p(out), n_img, N, H, _stream()) == 0
+        assert lib.vitvs_op_attention(_lib.BF16, ptr(q), ptr(out), n_img, N, H, stream()) == 0
         torch.cuda.synchronize()
         alone.append(out.clone())
-    assert _rel(alone[0].cpu(), _attention_ref(qa.cpu(), n_img, N, H)) <= 2e-2
+    assert rel_max(alone[0].cpu(), attention_ref(qa.cpu(), n_img, N, H)) <= 2e-2
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
     outs_a = [torch.empty_like(alone[0]) for _ in range(6)]
     outs_b = [torch.empty_like(alone[1]) for _ in range(6)]
     torch.cuda.synchronize()
     for i in range(6):                                          # interleaved enqueue: the launches of the two streams overlap
-        assert lib.vitvs_op_attention(_lib.BF16, _p(qa), _p(outs_a[i]), n_img, N, H, C.c_void_p(sa.cuda_stream)) == 0
-        assert lib.vitvs_op_attention(_lib.BF16, _p(qb), _p(outs_b[i]), n_img, N, H, C.c_void_p(sb.cuda_stream)) == 0
+        assert lib.vitvs_op_attention(_lib.BF16, ptr(qa), ptr(outs_a[i]), n_img, N, H, C.c_void_p(sa.cuda_stream)) == 0
+        assert lib.vitvs_op_attention(_lib.BF16, ptr(qb), ptr(outs_b[i]), n_img, N, H, C.c_void_p(sb.cuda_stream)) == 0
     torch.cuda.synchronize()
     for i in range(6):
         assert torch.equal(outs_a[i], alone[0]) and torch.equal(outs_b[i], alone[1])
@@ -367,7 +339,7 @@ def test_split_attention_on_two_streams_at_once(lib):
     seq = [qa, qb, qb, qa, qb, qa, qa, qb]
     outs = [torch.empty_like(alone[0]) for _ in seq]
     for q, o in zip(seq, outs):
-        assert lib.vitvs_op_attention(_lib.BF16, _p(q), _p(o), n_img, N, H, _stream()) == 0
+        assert lib.vitvs_op_attention(_lib.BF16, ptr(q), ptr(o), n_img, N, H, stream()) == 0
     torch.cuda.synchronize()
     for q, o in zip(seq, outs):
         assert torch.equal(o, alone[0] if q is qa else alone[1])
@@ -382,7 +354,7 @@ def test_long_attention_deferred_rescale_with_slowly_growing_scores(lib, slope):
     result must still be the softmax, against a full-tensor fp64 reference (CDNA4 guide T13: test the deferral itself)."""
     N, H = 1100, 2
     g = torch.Generator().manual_seed(int(slope * 1000))
-    qkv = _mk((N, 3 * 64 * H), g, 0.3)
+    qkv = mk((N, 3 * 64 * H), g, 0.3)
     keys = torch.arange(N, dtype=torch.float32)
     for h in range(H):
         qkv[:, h * 64] = 8.0                                            # q . k / 8 = k[0] + noise
@@ -391,10 +363,10 @@ def test_long_attention_deferred_rescale_with_slowly_growing_scores(lib, slope):
         q = qkv.to(dtype)
         out = torch.full((N, 64 * H), float("nan"), dtype=dtype, device="cuda")
         qd = q.cuda()
-        assert lib.vitvs_op_attention(prec, _p(qd), _p(out), 1, N, H, _stream()) == 0
+        assert lib.vitvs_op_attention(prec, ptr(qd), ptr(out), 1, N, H, stream()) == 0
         torch.cuda.synchronize()
         assert torch.isfinite(out.float()).all()
-        assert _rel(out.cpu(), _attention_ref(q, 1, N, H)) <= tol
+        assert rel_max(out.cpu(), attention_ref(q, 1, N, H)) <= tol
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -414,17 +386,17 @@ def test_linear_many_rows_under_the_in_flight_plan(lib, in_flight_plan, name, pr
     alone = tuple(t)
     lib.vitvs_op_plan_in_flight(3)
     g = torch.Generator().manual_seed(M * 7 + N)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((N, K), g, K ** -0.5).to(dtype)
-    bias = _mk((N,), g, 0.1)
+    A = mk((M, K), g).to(dtype)
+    W = mk((N, K), g, K ** -0.5).to(dtype)
+    bias = mk((N,), g, 0.1)
     ref = A.double() @ W.double().t() + bias.double()
     if gelu:
         ref = torch.nn.functional.gelu(ref)
     out = torch.full((M + 3, N), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_linear(prec, _p(A.cuda()), _p(W.cuda()), _p(bias.cuda()), _p(out), M, N, K, gelu, _stream()) == 0
+    assert lib.vitvs_op_linear(prec, ptr(A.cuda()), ptr(W.cuda()), ptr(bias.cuda()), ptr(out), M, N, K, gelu, stream()) == 0
     torch.cuda.synchronize()
     assert torch.isnan(out[M:].float()).all(), "rows beyond M were written"
-    assert _rel(out[:M].cpu(), ref) <= tol, f"(the alone plan's tile here: {alone})"
+    assert rel_max(out[:M].cpu(), ref) <= tol, f"(the alone plan's tile here: {alone})"
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])
@@ -440,12 +412,12 @@ def test_split_k_pair_many_rows_under_the_in_flight_plan(lib, in_flight_plan, na
     lib.vitvs_op_plan_in_flight(3)
     assert 1 <= slices <= (2 if M >= 2048 else 4) and slices <= slices_alone
     g = torch.Generator().manual_seed(M + D + K)
-    A = _mk((M, K), g).to(dtype)
-    W = _mk((D, K), g, K ** -0.5).to(dtype)
-    bias = _mk((D,), g, 0.1)
-    ls = (1.0 + 0.3 * _mk((D,), g)) if use_ls else None
-    gamma, beta = 1.0 + 0.1 * _mk((D,), g), 0.1 * _mk((D,), g)
-    x0 = _mk((M, D), g)
+    A = mk((M, K), g).to(dtype)
+    W = mk((D, K), g, K ** -0.5).to(dtype)
+    bias = mk((D,), g, 0.1)
+    ls = (1.0 + 0.3 * mk((D,), g)) if use_ls else None
+    gamma, beta = 1.0 + 0.1 * mk((D,), g), 0.1 * mk((D,), g)
+    x0 = mk((M, D), g)
     upd = A.double() @ W.double().t() + bias.double()
     if use_ls:
         upd = upd * ls.double()
@@ -456,16 +428,16 @@ def test_split_k_pair_many_rows_under_the_in_flight_plan(lib, in_flight_plan, na
     x = x0.clone().cuda()
     part = torch.full((slices, M, D), float("nan"), dtype=torch.float32, device="cuda")
     out = torch.full((M, D), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_linear_partial(prec, _p(Ad), _p(Wd), _p(part), M, D, K, slices, _stream()) == 0
-    assert lib.vitvs_op_residual_ln(prec, _p(x), _p(part), slices, _p(bd), _p(lsd), _p(gamma.cuda()), _p(beta.cuda()), _p(out),
-                                    M, D, 1e-6, _stream()) == 0
+    assert lib.vitvs_op_linear_partial(prec, ptr(Ad), ptr(Wd), ptr(part), M, D, K, slices, stream()) == 0
+    assert lib.vitvs_op_residual_ln(prec, ptr(x), ptr(part), slices, ptr(bd), ptr(lsd), ptr(gamma.cuda()), ptr(beta.cuda()), ptr(out),
+                                    M, D, 1e-6, stream()) == 0
     torch.cuda.synchronize()
     ks = K // slices
     for z in range(slices):
         ref_z = A[:, z * ks:(z + 1) * ks].double() @ W[:, z * ks:(z + 1) * ks].double().t()
-        assert _rel(part[z].cpu(), ref_z) <= 1e-3
-    assert _rel(x.cpu(), x_ref) <= 2e-6 + 1e-3
-    assert _rel(out.cpu(), y_ref) <= {_lib.BF16: 1e-2, _lib.F16: 2e-3}[prec]
+        assert rel_max(part[z].cpu(), ref_z) <= 1e-3
+    assert rel_max(x.cpu(), x_ref) <= 2e-6 + 1e-3
+    assert rel_max(out.cpu(), y_ref) <= {_lib.BF16: 1e-2, _lib.F16: 2e-3}[prec]
 
 
 @pytest.mark.parametrize("name,prec,dtype,tol", [p for p in PRECS if p[0] != "fp32"])
@@ -479,26 +451,26 @@ def test_attention_under_the_in_flight_plan(lib, in_flight_plan, name, prec, dty
     assert plan[0] == 5 and plan[5] == 0, f"the hint should select the long kernel with whole query blocks, got {list(plan)}"
     g = torch.Generator().manual_seed(N * 3 + H)
     D = H * 64
-    qkv = _mk((n_img * N, 3 * D), g).to(dtype)
+    qkv = mk((n_img * N, 3 * D), g).to(dtype)
     qs = qkv.clone().float()
     qs[:, :D] *= 0.125 * 1.4426950408889634
     qs = qs.to(dtype)
     t = qs.double().clone()
     t[:, :D] /= 0.125 * 1.4426950408889634
-    ref = _attention_ref(t, n_img, N, H)
+    ref = attention_ref(t, n_img, N, H)
     qd = qs.cuda()
     out = torch.full((n_img * N, D), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_attention_q(prec, _p(qd), _p(out), n_img, N, H, 1, _stream()) == 0
+    assert lib.vitvs_op_attention_q(prec, ptr(qd), ptr(out), n_img, N, H, 1, stream()) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
     bar = {_lib.BF16: 2e-2, _lib.F16: 3e-3}[prec]
-    assert _rel(out.cpu(), ref) <= bar
+    assert rel_max(out.cpu(), ref) <= bar
     lib.vitvs_op_plan_in_flight(1)
     out1 = torch.full((n_img * N, D), float("nan"), dtype=dtype, device="cuda")
-    assert lib.vitvs_op_attention_q(prec, _p(qd), _p(out1), n_img, N, H, 1, _stream()) == 0
+    assert lib.vitvs_op_attention_q(prec, ptr(qd), ptr(out1), n_img, N, H, 1, stream()) == 0
     torch.cuda.synchronize()
     lib.vitvs_op_plan_in_flight(3)
-    assert _rel(out1.cpu(), ref) <= bar and _rel(out.cpu(), out1.cpu()) <= bar
+    assert rel_max(out1.cpu(), ref) <= bar and rel_max(out.cpu(), out1.cpu()) <= bar
 
 
 def test_a_16bit_many_token_handle_created_under_a_thread_hint_still_runs_alone(lib):

@@ -13,9 +13,11 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
+from vitvs_amd.engine import Engine
 from oracle import servo_ref as sr
 from oracle import vit_ref
 from conftest import golden_case, load_golden
+from robust_ref import rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +27,9 @@ VC_TOL = 1e-4  # north_star: relative L2 on v_c
 EXACT = ["fp32", "f16x2"]
 
 
-def _engine(cfg, params=None, **kw):
-    from vitvs_amd.engine import Engine
-    return Engine(cfg, params, **kw)
-
-
 def _tiny_cfg(layerscale=False, img=64):
     base = config.vit_config("dinov2_vits14" if layerscale else "dino_vits16", 56 if layerscale else img)
     return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def _oracle_tokens(cfg, sd, frames):
@@ -79,7 +71,7 @@ class _PlanRunner:
             self.pipe = UpdatePipeline(cfg, params, sd, precision=precision, depth=3, max_pairs=max_pairs, max_rows=max_rows)
             self.eng = self.pipe.engines[2]
         else:
-            self.eng = _engine(cfg, params, precision=precision, max_pairs=max_pairs, max_rows=max_rows, binned=binned).load_state_dict(sd)
+            self.eng = Engine(cfg, params, precision=precision, max_pairs=max_pairs, max_rows=max_rows, binned=binned).load_state_dict(sd)
             if plan == "in_flight3":
                 self.eng.set_option("in_flight", 3)
 
@@ -126,7 +118,7 @@ def test_forward_tokens_tiny_fp32(layerscale, exact):
     cfg = _tiny_cfg(layerscale)
     sd = weights.synthetic_state_dict(cfg, 11)
     frames = np.random.default_rng(0).integers(0, 256, size=(3, cfg.img_size, cfg.img_size, 3), dtype=np.uint8)
-    eng = _engine(cfg, precision=exact, max_pairs=2).load_state_dict(sd)
+    eng = Engine(cfg, precision=exact, max_pairs=2).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     ref = _oracle_tokens(cfg, sd, frames)
     assert float((got - ref).abs().max()) <= 2e-5 * float(ref.abs().max())
@@ -139,7 +131,7 @@ def test_forward_tokens_resampled_pos_embed_and_stride(exact):
     cfg = dataclasses.replace(base, dim=128, depth=1, heads=2, layer=0, native_grid=4)
     sd = weights.synthetic_state_dict(cfg, 5)
     frames = np.random.default_rng(1).integers(0, 256, size=(2, 64, 64, 3), dtype=np.uint8)
-    eng = _engine(cfg, precision=exact, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, precision=exact, max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     ref = _oracle_tokens(cfg, sd, frames)
     assert got.shape == (2, 1 + 49, 128)
@@ -153,7 +145,7 @@ def test_forward_tokens_fp32_full_size(key, exact):
     cfg = config.baseline_config(key)
     sd = weights.synthetic_state_dict(cfg, int(blob["weight_seed"]))
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
-    eng = _engine(cfg, precision=exact, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, precision=exact, max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(np.stack([des, cur])).cpu()
     np.testing.assert_allclose(got[:, ::37, ::97].numpy(), blob["token_probe"], rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(got.norm(dim=-1).numpy(), blob["token_norms"], rtol=1e-5)
@@ -166,7 +158,7 @@ def test_descriptors_plain_and_binned(exact):
     frames = np.random.default_rng(2).integers(0, 256, size=(2, 96, 96, 3), dtype=np.uint8)
     ref = _oracle_tokens(cfg, sd, frames)[:, 1:]
     for binned in (False, True):
-        eng = _engine(cfg, precision=exact, max_pairs=1, binned=binned).load_state_dict(sd)
+        eng = Engine(cfg, precision=exact, max_pairs=1, binned=binned).load_state_dict(sd)
         d = eng.extract_descriptors(frames).cpu()
         want = vit_ref.log_bin(ref, cfg.grid) if binned else ref
         assert d.shape == (2, 1, cfg.tokens, cfg.dim * (9 if binned else 1))
@@ -188,7 +180,7 @@ def test_binned_correspondence_as_a_stencil_over_the_raw_gram(img, pairs, shared
     cfg = _tiny_cfg(False, img=img)
     sd = weights.synthetic_state_dict(cfg, 5)
     params = config.ServoParams(dino_input_size=img, use_feature_binning=True)
-    eng = _engine(cfg, params, precision=precision, max_pairs=pairs, max_rows=cfg.tokens, binned=True).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=precision, max_pairs=pairs, max_rows=cfg.tokens, binned=True).load_state_dict(sd)
     frames = [synth.frame_pair(img, 20250801 + k) for k in range(pairs)]
     des = np.stack([f[0] for f in frames])[:1 if shared else pairs]
     cur = np.stack([f[1] for f in frames])
@@ -216,7 +208,7 @@ CORR_CASES = ["partial", "short", "tiny", "all_mutual", "grid14", "same_image"]
 @pytest.fixture(scope="module")
 def small_engine():
     cfg = _tiny_cfg(False, img=224)  # T = 196 capacity, img_size 224 as in the fixtures
-    return _engine(cfg, precision="fp32", max_pairs=1, max_rows=196)
+    return Engine(cfg, precision="fp32", max_pairs=1, max_rows=196)
 
 
 @pytest.mark.parametrize("name", CORR_CASES)
@@ -240,7 +232,7 @@ def test_correspond_band_ordered_tiles_cover_every_token(g, d):
     maximum (a tile left out shows as a zero key, i.e. index 2^32 - 1), against an fp64 Gram of the normalised rows."""
     t = g * g
     cfg = _tiny_cfg(False, img=16 * g)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=16 * g), precision="fp32", max_pairs=1, max_rows=max(t, 48))
+    eng = Engine(cfg, config.ServoParams(dino_input_size=16 * g), precision="fp32", max_pairs=1, max_rows=max(t, 48))
     gen = torch.Generator().manual_seed(100 * g + d)
     d1, d2 = torch.randn(t, d, generator=gen), torch.randn(t, d, generator=gen)
     nn1, nn2, sim1, smat = eng.correspond(d1, d2, want_matrix=True)
@@ -283,7 +275,7 @@ def test_servo_law_matches_reference_given_selection(name):
     k = int(case["num_pairs"])
     cfg = _tiny_cfg(False, img=224)
     params = config.ServoParams(num_pairs=k, dino_input_size=224)
-    eng = _engine(cfg, params, precision="fp32", max_pairs=1, max_rows=max(k, 196))
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1, max_rows=max(k, 196))
     status_ref = int(case["status"])
     sel = _ids(case["points1"], grid) if status_ref != 1 else np.zeros(0, np.int32)
     v, st = eng.servo_from_nn(case["nn_1"], case["nn_2"], case["sim_1"], synth.depth_pattern(),
@@ -301,7 +293,7 @@ def test_servo_law_matches_reference_given_selection(name):
     np.testing.assert_allclose(L, case["L"], rtol=0, atol=1e-14)
     np.testing.assert_allclose(det["L"][0, 6, :2 * k], case["e"][:, 0], rtol=0, atol=1e-15)
     if status_ref == 0:
-        assert _rel_l2(v.cpu().numpy(), case["v_c"]) <= 1e-9 <= VC_TOL
+        assert rel_l2(v.cpu().numpy(), case["v_c"]) <= 1e-9 <= VC_TOL
     else:
         assert np.all(v.cpu().numpy() == 0.0)
 
@@ -310,7 +302,7 @@ def test_servo_order_and_dense_selection_match_oracle():
     case = golden_case(load_golden("corr_cases.npz"), "grid14")
     t, grid, k = 196, 14, 24
     params = config.ServoParams(num_pairs=k, dino_input_size=224)
-    eng = _engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
+    eng = Engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
     depth = synth.depth_pattern()
     nn1, nn2 = case["nn_1"].astype(np.int64), case["nn_2"].astype(np.int64)
     mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
@@ -328,12 +320,12 @@ def test_servo_order_and_dense_selection_match_oracle():
                               selection=order)
     det = eng.last_details(1)
     assert int(st) == 0 and det["selected"][0, :k].tolist() == [int(x) for x in want]
-    assert _rel_l2(v.cpu().numpy(), oracle(np.array(want), k)["v_c"]) <= 1e-9
+    assert rel_l2(v.cpu().numpy(), oracle(np.array(want), k)["v_c"]) <= 1e-9
     v, st = eng.servo_from_nn(nn1, nn2, case["sim_1"], depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
     det = eng.last_details(1)
     assert int(st) == 0 and det["selected"][0, :len(mutual)].tolist() == mutual.tolist()
     assert int(det["info"][0, 1]) == len(mutual)
-    assert _rel_l2(v.cpu().numpy(), oracle(mutual, len(mutual))["v_c"]) <= 1e-9
+    assert rel_l2(v.cpu().numpy(), oracle(mutual, len(mutual))["v_c"]) <= 1e-9
 
 
 def _random_similarity(rng, t, n_boost):
@@ -359,7 +351,7 @@ def test_servo_law_on_random_tables_matches_the_oracle(seed):
     k = int(rng.integers(4, min(t, 48) + 1))
     cfg = _tiny_cfg(False, img=16 * g)
     params = config.ServoParams(num_pairs=k, dino_input_size=16 * g)
-    eng = _engine(cfg, params, precision="fp32", max_pairs=1, max_rows=max(k, t))
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1, max_rows=max(k, t))
     all_mutual = seed % 8 == 7
     S = _random_similarity(rng, t, t if all_mutual else int(rng.integers(4, t)))
     sim1_t, nn1_t, _, nn2_t = sr.nearest_neighbours(torch.from_numpy(S))
@@ -409,7 +401,7 @@ def test_servo_law_on_random_tables_matches_the_oracle(seed):
         if want_status == _lib.STATUS_OK:
             assert np.array_equal(det["feat"][0, :rows, 0:1], ref["Z"]), (name, seed)
             np.testing.assert_allclose(det["L"][0, :6, :2 * rows].T, ref["L"], rtol=0, atol=1e-13)
-            assert _rel_l2(v, ref["v_c"]) <= 1e-9 <= VC_TOL, (name, seed, _rel_l2(v, ref["v_c"]))
+            assert rel_l2(v, ref["v_c"]) <= 1e-9 <= VC_TOL, (name, seed, rel_l2(v, ref["v_c"]))
         else:
             assert np.all(v == 0.0) and not s_star.any() and not s_.any()               # calculate_uv's all-zero arrays, e = 0
     eng.close()
@@ -418,7 +410,7 @@ def test_servo_law_on_random_tables_matches_the_oracle(seed):
 def test_servo_no_depth_status():
     case = golden_case(load_golden("corr_cases.npz"), "partial")
     params = config.ServoParams(num_pairs=24, dino_input_size=224)
-    eng = _engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
+    eng = Engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
     v, st = eng.servo_from_nn(case["nn_1"], case["nn_2"], case["sim_1"], None, params.intrinsics(),
                               mode=_lib.SELECT_DENSE)
     assert int(st) == _lib.STATUS_NO_DEPTH and np.all(v.cpu().numpy() == 0)
@@ -431,7 +423,7 @@ def test_pinv_rank_deficient_matches_numpy():
     nn2 = np.arange(t, dtype=np.int32)
     nn1[5], nn1[6] = 6, 5   # two non-mutual tokens so that the filter does not return None
     params = config.ServoParams(num_pairs=k, dino_input_size=224)
-    eng = _engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
+    eng = Engine(_tiny_cfg(False, img=224), params, precision="fp32", max_pairs=1, max_rows=196)
     sel = np.full(k, 9, np.int32)
     nn1[9] = 27             # a displaced match so that e != 0
     nn2[27] = 9
@@ -445,7 +437,7 @@ def test_pinv_rank_deficient_matches_numpy():
                                 params.v_max, 224)
     ref = sr.velocity(s_star, s, depth, params.f_x, params.f_y, params.c_x, params.c_y, params.lambda_)
     assert np.linalg.matrix_rank(ref["L"]) == 2
-    assert _rel_l2(v.cpu().numpy(), ref["v_c"]) <= 1e-9
+    assert rel_l2(v.cpu().numpy(), ref["v_c"]) <= 1e-9
 
 
 # ----------------------------------------------------------------------------- end to end
@@ -478,7 +470,7 @@ def test_compute_velocity_fp32_matches_reference(key, tag, plan, exact):
     np.testing.assert_allclose(det["sim_1"][0], case["sim_1"], rtol=0, atol=2e-5)
     k = case["s_uv"].shape[0]
     assert np.array_equal(det["s_uv"][0, :k, 2:4], case["s_uv"]) and np.array_equal(det["s_uv"][0, :k, 0:2], case["s_uv_star"])
-    assert _rel_l2(v, case["v_c"]) <= 1e-9 <= VC_TOL
+    assert rel_l2(v, case["v_c"]) <= 1e-9 <= VC_TOL
 
 
 @pytest.mark.parametrize("exact", EXACT)
@@ -494,7 +486,7 @@ def test_cached_goal_gives_the_reference_update(key, tag, exact):
     sd = weights.synthetic_state_dict(cfg, int(blob["weight_seed"]))
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=(tag == "binned"))
-    eng = _engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(sd)
     sel = _ids(case["points1"], cfg.grid)
     depth = synth.depth_pattern()
     with pytest.raises(VitvsError):                       # nothing cached yet
@@ -506,7 +498,7 @@ def test_cached_goal_gives_the_reference_update(key, tag, exact):
         assert int(st[0]) == 0
         assert np.array_equal(det["nn_1"][0], case["nn_1"]) and np.array_equal(det["nn_2"][0], case["nn_2"])
         np.testing.assert_allclose(det["sim_1"][0], case["sim_1"], rtol=0, atol=2e-5)
-        assert _rel_l2(v.cpu().numpy()[0], case["v_c"]) <= 1e-9 <= VC_TOL
+        assert rel_l2(v.cpu().numpy()[0], case["v_c"]) <= 1e-9 <= VC_TOL
     eng.forward_tokens(np.stack([cur]))                    # forwards a frame of its own: the goal rows are gone
     with pytest.raises(VitvsError):
         eng.compute_velocity(cur, None, depth, params.intrinsics(), mode=_lib.SELECT_EXPLICIT, selection=[sel])
@@ -523,7 +515,7 @@ def test_cached_shared_goal_batch_matches_the_recomputing_call(precision):
     des = pairs[0][0]
     cur = np.stack([p[1] for p in pairs])
     depth = np.stack([synth.depth_pattern()] * 3)
-    eng = _engine(cfg, params, precision=precision, max_pairs=3, max_rows=196).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=precision, max_pairs=3, max_rows=196).load_state_dict(sd)
     v_ref, s_ref = eng.compute_velocity(cur, des[None], depth, params.intrinsics(), mode=_lib.SELECT_DENSE, des_shared=True)
     det_ref = eng.last_details(3)
     eng.set_goal(des[None])
@@ -542,7 +534,7 @@ def test_cached_shared_goal_batch_matches_the_recomputing_call(precision):
             mutual = np.nonzero(n2[n1] == np.arange(cfg.tokens))[0]
             assert 4 <= len(mutual) < cfg.tokens
             want = _law_on(cfg, params, mutual, n1[mutual], depth[b], len(mutual))["v_c"]
-            assert _rel_l2(vv[b].cpu().numpy(), want) <= 1e-9
+            assert rel_l2(vv[b].cpu().numpy(), want) <= 1e-9
 
 
 def _tie_tolerant_agreement(got, ref_idx, sim_ref_rows, tol):
@@ -593,7 +585,7 @@ def test_compute_velocity_fp32_many_tokens(key, exact):
                            params.lambda_)["v_c"]
     print(f"{key}: selected tokens' nn_1 {'identical to' if same else 'tie-different from'} the fixture's; "
           f"agreement nn_1 {a1:.4f} nn_2 {a2:.4f}")
-    assert _rel_l2(v, want) <= 1e-9 <= VC_TOL
+    assert rel_l2(v, want) <= 1e-9 <= VC_TOL
 
 
 # 16-bit operand modes (the headline dtype): over the 8 accepted ViT-B/16 pairs of the rig fixture.
@@ -663,7 +655,7 @@ def test_16bit_modes_over_8_accepted_pairs(precision, plan):
             want = case["v_c"]
         else:
             want = _law_on(cfg, params, sel, dev_matches, depth, k)["v_c"]
-        assert _rel_l2(v.cpu().numpy()[0], want) <= 1e-9 <= VC_TOL, (i, "explicit")
+        assert rel_l2(v.cpu().numpy()[0], want) <= 1e-9 <= VC_TOL, (i, "explicit")
         # (2) a visiting order: the draw is exact given the device's own tables; v_c is the oracle's law on that draw
         order = np.random.default_rng(1000 + i).permutation(t).astype(np.int32)
         v2, st2 = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_ORDER, selection=order[None])
@@ -673,7 +665,7 @@ def test_16bit_modes_over_8_accepted_pairs(precision, plan):
         want_sel = _first_mutual_in_order(order, d1, d2, k)
         got_sel = det2["selected"][0, :k].astype(np.int64)
         assert int(st2[0]) == 0 and len(want_sel) == k and np.array_equal(got_sel, want_sel), (i, "order draw")
-        assert _rel_l2(v2.cpu().numpy()[0], _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
+        assert rel_l2(v2.cpu().numpy()[0], _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
         ref_sel = _first_mutual_in_order(order, n1r, n2r, k)
         same_draw += int(np.array_equal(ref_sel, want_sel) and np.array_equal(d1[want_sel], n1r[ref_sel]))
     eng.close()
@@ -710,7 +702,7 @@ def test_16bit_binned_reference_default_config(precision, plan):
     dev_matches = det["nn_1"][0].astype(np.int64)[sel]
     want = case["v_c"] if np.array_equal(dev_matches, case["nn_1"].astype(np.int64)[sel]) else \
         _law_on(cfg, params, sel, dev_matches, synth.depth_pattern(), params.num_pairs)["v_c"]
-    assert _rel_l2(v, want) <= 1e-9 <= VC_TOL
+    assert rel_l2(v, want) <= 1e-9 <= VC_TOL
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
@@ -722,7 +714,7 @@ def test_many_token_gram_of_the_16bit_modes_equals_an_exact_gram_of_the_same_des
     cfg = _tiny_cfg(False, img=512)  # 32 x 32 = 1024 tokens
     sd = weights.synthetic_state_dict(cfg, 5)
     params = config.ServoParams(dino_input_size=512, use_feature_binning=binned)
-    eng = _engine(cfg, params, precision=precision, max_pairs=2, binned=binned).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=precision, max_pairs=2, binned=binned).load_state_dict(sd)
     des, cur0 = synth.frame_pair(512, 20250801)
     _, cur1 = synth.frame_pair(512, 20250802)
     cur = np.stack([cur0, cur1])
@@ -750,7 +742,7 @@ def test_forward_tokens_fp16_large_config(key):
     """DINOv2 ViT-L/14 518² in fp16 (configs[4]): tokens against the fp32 oracle, LayerScale model, resampled grid."""
     cfg = config.baseline_config(key)
     sd = weights.synthetic_state_dict(cfg, 0)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision="fp16",
+    eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision="fp16",
                   max_pairs=1).load_state_dict(sd)
     frame = synth.frame_pair(cfg.img_size, 5)[0][None]
     got = eng.forward_tokens(frame).cpu()
@@ -769,7 +761,7 @@ def test_forward_tokens_strided_full_size(exact):
     assert cfg.grid == 55 and cfg.tokens == 3025
     sd = weights.synthetic_state_dict(cfg, 2)
     frames = np.stack(synth.frame_pair(224, 20250901))
-    eng = _engine(cfg, config.ServoParams(dino_input_size=224, use_feature_binning=False), precision=exact,
+    eng = Engine(cfg, config.ServoParams(dino_input_size=224, use_feature_binning=False), precision=exact,
                   max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     ref = _oracle_tokens(cfg, sd, frames)
@@ -809,7 +801,7 @@ def test_forward_tokens_with_trained_like_statistics(precision):
     chan = ref.abs().amax(dim=(0, 1))
     assert all(0.5 <= e <= 3.0 for e in ents), ents
     assert float(chan.topk(4).values.min() / chan.median()) >= 30.0
-    eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
+    eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
                   max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     per_chan = (got - ref).abs().amax(dim=(0, 1)) / chan
@@ -902,7 +894,7 @@ def test_trained_like_statistics_end_to_end(key, precision, plan):
     # the draw: exact given the device's tables; the law on it
     want_sel = _first_mutual_in_order(order, d1, d2, k)
     assert len(want_sel) == k and np.array_equal(det["selected"][0, :k].astype(np.int64), want_sel)
-    assert _rel_l2(v, _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
+    assert rel_l2(v, _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
     ref_sel = _first_mutual_in_order(order, n1r, n2r, k)
     v_ref = _law_on(cfg, params, ref_sel, n1r[ref_sel], depth, k)["v_c"]
     drawn_same = float(np.mean([(x in set(ref_sel.tolist())) and d1[x] == n1r[x] for x in want_sel]))
@@ -910,12 +902,12 @@ def test_trained_like_statistics_end_to_end(key, precision, plan):
     print(f"trained-like {key} {precision} [{plan}]: oracle margins median {np.median(margins):.2e} min {margins.min():.2e}, "
           f"{mutual_ref} mutual NNs (device {mutual_dev}); max |S_device - S_oracle| {sim_err:.2e}; arg-max agreement nn_1 {a1:.4f} "
           f"nn_2 {a2:.4f}, largest oracle gap of a differing choice {max(g1, g2):.2e}; {drawn_same:.2f} of the {k} drawn features are "
-          f"the oracle's (token and match); v_c vs the oracle's v_c under the same visiting order: rel-L2 {_rel_l2(v, v_ref):.2e}")
+          f"the oracle's (token and match); v_c vs the oracle's v_c under the same visiting order: rel-L2 {rel_l2(v, v_ref):.2e}")
     eng.close()
     assert sim_err <= bars["sim_err"] and max(g1, g2) <= min(bars["gap"], 2 * sim_err + 1e-6)
     assert min(a1, a2) >= bars["agree"] and drawn_same >= bars["drawn_same"]
     if np.array_equal(d1, n1r) and np.array_equal(d2, n2r):
-        assert _rel_l2(v, v_ref) <= 1e-9
+        assert rel_l2(v, v_ref) <= 1e-9
 
 
 # BASELINE.json configs[4] (fp16 DINOv2 ViT-L/14 518², 1369 tokens) and configs[2] in the throughput dtype (bf16 DINO ViT-B/8
@@ -971,7 +963,7 @@ def test_compute_velocity_16bit_many_tokens_full_size(key, precision, plan):
     # (c) the draw and the law
     want_sel = _first_mutual_in_order(order, d1, d2, k)
     assert len(want_sel) == k and np.array_equal(det["selected"][0, :k].astype(np.int64), want_sel)
-    assert _rel_l2(v, _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
+    assert rel_l2(v, _law_on(cfg, params, want_sel, d1[want_sel], depth, k)["v_c"]) <= 1e-9 <= VC_TOL
 
 
 @pytest.mark.parametrize("exact", EXACT)
@@ -984,7 +976,7 @@ def test_batched_pairs_and_shared_goal(exact):
     des = np.stack([p[0] for p in pairs])
     cur = np.stack([p[1] for p in pairs])
     depth = np.stack([synth.depth_pattern()] * 3)
-    eng = _engine(cfg, params, precision=exact, max_pairs=3, max_rows=196).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=3, max_rows=196).load_state_dict(sd)
     vb, sb = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
     detb = eng.last_details(3)
     for i in range(3):
@@ -1020,13 +1012,13 @@ def test_rig_of_8_vitb16_pairs_in_one_call(plan, exact):
     detb = eng.last_details(8)
     vb = vb.cpu().numpy()
     head = golden_case(load_golden("e2e_vitb16_224.npz"), "plain")
-    assert _rel_l2(vb[0], head["v_c"]) <= 1e-9 and np.array_equal(detb["nn_1"][0], head["nn_1"])
+    assert rel_l2(vb[0], head["v_c"]) <= 1e-9 and np.array_equal(detb["nn_1"][0], head["nn_1"])
     for i in range(8):
         case = golden_case(blob, f"pair{i}")
         assert int(sb[i]) == 0
         assert np.array_equal(detb["nn_1"][i], case["nn_1"]) and np.array_equal(detb["nn_2"][i], case["nn_2"])
         assert np.array_equal(detb["s_uv"][i, :params.num_pairs, 2:4], case["s_uv"])
-        assert _rel_l2(vb[i], case["v_c"]) <= 1e-9 <= VC_TOL
+        assert rel_l2(vb[i], case["v_c"]) <= 1e-9 <= VC_TOL
         v1, s1 = eng.compute_velocity(cur[i], des[i], depth[i], params.intrinsics(), mode=_lib.SELECT_EXPLICIT,
                                       selection=[sels[i]])
         det1 = eng.last_details(1)
@@ -1044,14 +1036,14 @@ def test_num_pairs_is_a_per_call_argument():
     depth = synth.depth_pattern()
     order = torch.randperm(cfg.tokens, generator=torch.Generator().manual_seed(8)).to(torch.int32)[None]
     p24 = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, p24, precision="fp32", max_pairs=1).load_state_dict(sd)          # max_rows defaults to 48
+    eng = Engine(cfg, p24, precision="fp32", max_pairs=1).load_state_dict(sd)          # max_rows defaults to 48
     v24, _ = eng.compute_velocity(cur, des, depth, p24.intrinsics(), mode=_lib.SELECT_ORDER, selection=order)
     d24 = eng.last_details(1)
     v48, _ = eng.compute_velocity(cur, des, depth, p24.intrinsics(), mode=_lib.SELECT_ORDER, selection=order, num_pairs=48)
     d48 = eng.last_details(1)
     assert int(d24["info"][0, 1]) == 24 and int(d48["info"][0, 1]) == 48
     assert d48["selected"][0, :24].tolist() == d24["selected"][0, :24].tolist()
-    eng48 = _engine(cfg, p24.replace(num_pairs=48), precision="fp32", max_pairs=1).load_state_dict(sd)
+    eng48 = Engine(cfg, p24.replace(num_pairs=48), precision="fp32", max_pairs=1).load_state_dict(sd)
     w48, _ = eng48.compute_velocity(cur, des, depth, p24.intrinsics(), mode=_lib.SELECT_ORDER, selection=order)
     assert torch.equal(v48, w48) and not torch.equal(v24, v48)
     from vitvs_amd.engine import VitvsError
@@ -1072,7 +1064,7 @@ def test_rotation_compensation_scores_match_the_reference(exact):
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
     views = np.stack([np.rot90(cur, int(k)).copy() for k in blob["rot90_k"]])
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=4).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=4).load_state_dict(sd)
     k = int(blob["num_pairs"])
     sels = [_ids(blob[f"view{i}/points1"], cfg.grid) for i in range(4)]
     depth = np.zeros((4, params.v_max, params.u_max), np.uint16)
@@ -1121,7 +1113,7 @@ def test_graph_replay_matches_eager(monkeypatch, many_tokens):
     results = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("VITVS_GRAPH", mode)
-        eng = _engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
+        eng = Engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
         out = []
         with torch.cuda.stream(torch.cuda.Stream()):              # graphs need a non-null stream
             for o in orders + orders[:2]:
@@ -1152,11 +1144,11 @@ def test_graph_mode_keeps_the_goal_cache_contract(monkeypatch):
     K = torch.tensor([params.intrinsics()], dtype=torch.float64, device=dev)
     order = torch.randperm(cfg.tokens, generator=torch.Generator().manual_seed(2)).to(torch.int32)[None].to(dev)
     monkeypatch.setenv("VITVS_GRAPH", "0")
-    eager = _engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
+    eager = Engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
     eager.set_goal(I_des)
     want = eager.compute_velocity_dev(I_cur, None, Z, K, _lib.SELECT_ORDER, order)[0].cpu().numpy().copy()
     monkeypatch.setenv("VITVS_GRAPH", "1")
-    eng = _engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, params, precision="bf16", max_pairs=1).load_state_dict(sd)
     with torch.cuda.stream(torch.cuda.Stream()):
         def call(goal):
             v, _ = eng.compute_velocity_dev(I_cur, goal, Z, K, _lib.SELECT_ORDER, order)
@@ -1188,8 +1180,8 @@ def test_two_handles_interleaved():
     ca, cb = config.baseline_config("vits16_224"), _tiny_cfg(True)
     pa = config.ServoParams(dino_input_size=ca.img_size, use_feature_binning=False)
     pb = config.ServoParams(dino_input_size=cb.img_size, use_feature_binning=False)
-    ea = _engine(ca, pa, precision="bf16", max_pairs=2).load_state_dict(weights.synthetic_state_dict(ca, 0))
-    eb = _engine(cb, pb, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cb, 4))
+    ea = Engine(ca, pa, precision="bf16", max_pairs=2).load_state_dict(weights.synthetic_state_dict(ca, 0))
+    eb = Engine(cb, pb, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cb, 4))
     fa = np.stack(synth.frame_pair(ca.img_size, 31))
     fb = np.stack(synth.frame_pair(cb.img_size, 32))
     ta0, tb0 = ea.forward_tokens(fa).cpu(), eb.forward_tokens(fb).cpu()
@@ -1212,7 +1204,7 @@ def test_host_pointer_entry_point_matches_device_entry_point(key):
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
     des, cur = synth.frame_pair(cfg.img_size, 20250705)
     depth = synth.depth_pattern()
-    eng = _engine(cfg, params, precision="fp32", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
     vd, sd_ = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
     det_d = eng.last_details(1)
     K = np.array(params.intrinsics(), np.float64)
@@ -1266,7 +1258,7 @@ def test_reuse_goal_frames_option_of_the_host_pointer_call():
     des, cur = synth.frame_pair(224, 20250705)
     des2, _ = synth.frame_pair(224, 20250706)
     depth = synth.depth_pattern()
-    eng = _engine(cfg, params, precision="fp32", max_pairs=1, max_rows=196).load_state_dict(sd)
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1, max_rows=196).load_state_dict(sd)
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     K = np.array(params.intrinsics(), np.float64)
 
@@ -1302,7 +1294,7 @@ def test_controller_adapter_reproduces_reference_update(exact):
     sd = weights.synthetic_state_dict(cfg, int(blob["weight_seed"]))
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=4).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=4).load_state_dict(sd)
     ctl = servo.Controller(eng, goal_image=des, selection="reference")
     assert ctl.detect_features() == (None, None)          # no image yet
     ctl.image_callback_rgb(cur)
@@ -1313,7 +1305,7 @@ def test_controller_adapter_reproduces_reference_update(exact):
     np.testing.assert_allclose(sim.numpy().reshape(-1), case["sim_selected"], atol=2e-5)
     torch.manual_seed(121)
     ctl.ibvs()
-    assert _rel_l2(ctl.v_c, case["ema_first"]) <= 1e-9     # first EMA sample == raw v_c
+    assert rel_l2(ctl.v_c, case["ema_first"]) <= 1e-9     # first EMA sample == raw v_c
     lin, ang = ctl.publish_twist()
     assert lin == pytest.approx((ctl.v_c[2], -ctl.v_c[0], -ctl.v_c[1]))
     # order selection: every chosen token is a mutual NN and v_c stays a sane twist
@@ -1337,7 +1329,7 @@ def test_controller_with_camera_resolution_frames_and_reference_selection(exact)
     cfg = config.baseline_config("vits16_224")
     sd = weights.synthetic_state_dict(cfg, 0)
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(sd)
     rng = np.random.default_rng(77)
     goal = synth.texture(640, 5)[:480]                                  # 480 x 640 x 3
     cam = synth.warp_similarity(goal, shift=(14.0, -8.0), rot_deg=3.0, scale=1.02, seed=6)
@@ -1363,7 +1355,7 @@ def test_controller_failure_counter_raises_like_the_reference():
     cfg = config.baseline_config("vits16_224")
     sd = weights.synthetic_state_dict(cfg, 0)
     params = config.ServoParams(dino_input_size=224, use_feature_binning=False)
-    eng = _engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(sd)
     des, _ = synth.frame_pair(224, 1)
     # distinct flat frames: every token of a frame is identical up to position, all arg-maxes collapse ...
     ctl = servo.Controller(eng, goal_image=des, selection="reference")
@@ -1394,7 +1386,7 @@ def test_extract_descriptors_facets(precision, tol, layerscale):
     refused like the reference's assertion, an unknown facet like its message."""
     cfg = _tiny_cfg(layerscale)
     sd = weights.synthetic_state_dict(cfg, 11, affine_jitter=True)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
+    eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
                   max_pairs=1).load_state_dict(sd)
     frames = np.stack(synth.frame_pair(cfg.img_size, 4242))
     kw = dict(patch=cfg.patch, stride=cfg.stride, heads=cfg.heads, layer=cfg.layer, mean=cfg.mean, std=cfg.std)
@@ -1432,7 +1424,7 @@ def test_extract_saliency_maps(precision, stride):
     from vitvs_amd.engine import VitvsError
     cfg = config.vit_config("dino_vits8", 224, stride=stride)
     sd = weights.trained_like_state_dict(cfg, 5)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
+    eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision=precision,
                   max_pairs=1).load_state_dict(sd)
     frames = np.stack(synth.frame_pair(cfg.img_size, 99))
     kw = dict(patch=cfg.patch, stride=cfg.stride, heads=cfg.heads, layer=cfg.layer, mean=cfg.mean, std=cfg.std)
@@ -1454,7 +1446,7 @@ def test_extract_saliency_maps(precision, stride):
     with pytest.raises(VitvsError):
         eng.extract_saliency_maps(frames, head_idxs=(0, 6))              # dino_vits8 has 6 heads
     wrong = config.baseline_config("vits16_224")
-    eng2 = _engine(wrong, config.ServoParams(dino_input_size=224, use_feature_binning=False), precision="bf16", max_pairs=1)
+    eng2 = Engine(wrong, config.ServoParams(dino_input_size=224, use_feature_binning=False), precision="bf16", max_pairs=1)
     with pytest.raises(AssertionError, match="supported only for dino_vits"):
         eng2.extract_saliency_maps(frames)
 
@@ -1466,7 +1458,7 @@ def test_update_is_bit_reproducible_run_to_run(precision):
     update on the headline configuration must agree bit for bit (indices, similarities, v_c)."""
     cfg = config.baseline_config("vitb16_224")
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
+    eng = Engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     des, cur = synth.frame_pair(cfg.img_size, synth.ACCEPTED_FRAME_SEEDS["vitb16_224"])
     order = torch.randperm(cfg.tokens, generator=torch.Generator().manual_seed(3)).to(torch.int32)[None]
     runs = []
@@ -1485,7 +1477,7 @@ def test_many_token_updates_alternating_inputs_are_bit_reproducible():
     on one handle give, each time, exactly what they give first — indices, similarities and v_c bit for bit."""
     cfg = config.baseline_config("vitl14_518")
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision="fp16", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
+    eng = Engine(cfg, params, precision="fp16", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     pairs = [synth.frame_pair(cfg.img_size, 20250705), synth.frame_pair(cfg.img_size, 20250911)]
     order = torch.randperm(cfg.tokens, generator=torch.Generator().manual_seed(3)).to(torch.int32)[None]
     first = {}
@@ -1508,7 +1500,7 @@ def test_swapping_the_frames_swaps_the_nearest_neighbour_tables(exact):
     fp32; the fixture's margins rule out ties)."""
     cfg = config.baseline_config("vitb16_224")
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
+    eng = Engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     des, cur = synth.frame_pair(cfg.img_size, synth.ACCEPTED_FRAME_SEEDS["vitb16_224"])
     d = eng.extract_descriptors(np.stack([des, cur]))[:, 0]
     nn1_a, nn2_a, sim_a = (t.cpu() for t in eng.correspond(d[0], d[1]))
@@ -1526,7 +1518,7 @@ def test_identical_frames_take_the_same_image_shortcut_and_give_zero_velocity(ex
     """mean(sim_1) > 0.99 (vitvs_v2.py:84-101): identical points on both sides, e = 0, so v_c = 0 exactly."""
     cfg = config.baseline_config("vits16_224")
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
+    eng = Engine(cfg, params, precision=exact, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     des, _ = synth.frame_pair(cfg.img_size, 99)
     v, st = eng.compute_velocity(des, des, synth.depth_pattern(), params.intrinsics(), mode=_lib.SELECT_ORDER,
                                  selection=torch.randperm(cfg.tokens).to(torch.int32)[None])
@@ -1560,7 +1552,7 @@ def test_dense_correspondence_and_interaction_matrix_at_3136_tokens(exact):
     sd = weights.synthetic_state_dict(cfg, int(blob["weight_seed"]))
     des, cur = synth.frame_pair(cfg.img_size, int(blob["frame_seed"]))
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
     depth = synth.depth_pattern()
     v, st = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
     det = eng.last_details(1)
@@ -1576,7 +1568,7 @@ def test_dense_correspondence_and_interaction_matrix_at_3136_tokens(exact):
                                 params.u_max, params.v_max, cfg.img_size)
     ref = sr.velocity(s_star, s, depth, params.f_x, params.f_y, params.c_x, params.c_y, params.lambda_)
     assert np.array_equal(det["s_uv"][0, :len(mutual), :2], np.asarray(s_star)) and np.array_equal(det["s_uv"][0, :len(mutual), 2:], np.asarray(s))
-    assert _rel_l2(v.cpu().numpy()[0], ref["v_c"]) <= 1e-9
+    assert rel_l2(v.cpu().numpy()[0], ref["v_c"]) <= 1e-9
 
 
 @pytest.mark.parametrize("exact", EXACT)
@@ -1587,7 +1579,7 @@ def test_argmax_parity_over_a_sweep_of_frame_pairs(exact):
     cfg = config.baseline_config("vits16_224")
     sd = weights.synthetic_state_dict(cfg, 0)
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision=exact, max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=exact, max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
     depth = synth.depth_pattern()
     g = cfg.grid
     exact = 0
@@ -1611,7 +1603,7 @@ def test_argmax_parity_over_a_sweep_of_frame_pairs(exact):
         s_star, s = sr.calculate_uv(sr.patch_centres(p1, cfg.img_size, g), sr.patch_centres(p2, cfg.img_size, g), len(mutual),
                                     params.u_max, params.v_max, cfg.img_size)
         ref = sr.velocity(s_star, s, depth, params.f_x, params.f_y, params.c_x, params.c_y, params.lambda_)
-        assert _rel_l2(v.cpu().numpy()[0], ref["v_c"]) <= 1e-9
+        assert rel_l2(v.cpu().numpy()[0], ref["v_c"]) <= 1e-9
     print(f"sweep: {exact} of 8 pairs with every arg-max identical to the oracle's")
 
 
@@ -1621,7 +1613,7 @@ def test_error_convention_of_the_c_abi():
     lib = _lib.load()
     cfg = config.baseline_config("vits16_224")
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
-    eng = _engine(cfg, params, precision="bf16", max_pairs=1)             # weights NOT loaded
+    eng = Engine(cfg, params, precision="bf16", max_pairs=1)             # weights NOT loaded
     frames = torch.zeros((1, cfg.img_size, cfg.img_size, 3), dtype=torch.uint8, device="cuda")
     out = torch.empty((1, cfg.seq, cfg.dim), dtype=torch.float32, device="cuda")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -12,7 +12,6 @@ records its worst relative error (max |got - ref| / max |ref|) as a junit proper
 (`--junitxml=FILE -o junit_family=legacy`)."""
 import ctypes as C
 import json
-import math
 import os
 
 import pytest
@@ -20,6 +19,8 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import gpu_lib as lib  # noqa: F401
+from op_support import DTYPES, attention_ref, from_x2, nan_like, ptr, rel_max, stream, to_x2, values, weight_exp
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +31,6 @@ with open(os.path.join(ROOT, "tests", "golden", "plan_cover.json")) as _fh:
 STORE, PARTIAL = 0, 1
 GUARD = 3                 # rows behind every output that no launch may write
 LOG2E = 1.4426950408889634
-DTYPES = {_lib.F32: torch.float32, _lib.BF16: torch.bfloat16, _lib.F16: torch.float16, _lib.F16X2: torch.float16}
 # (the op tests' bars)  store: test_linear; slice / x / LayerNorm: test_split_k_pair; attention: test_attention (forward form)
 BAR_STORE = {_lib.F32: 2e-5, _lib.BF16: 1.5e-2, _lib.F16: 2e-3, _lib.F16X2: 2e-5}
 BAR_SLICE = {_lib.F32: 2e-5, _lib.BF16: 1e-3, _lib.F16: 1e-3, _lib.F16X2: 2e-5}
@@ -39,48 +39,11 @@ BAR_LN = {_lib.F32: 2e-5, _lib.BF16: 1e-2, _lib.F16: 2e-3, _lib.F16X2: 2e-5}
 BAR_ATTN = {_lib.F32: 1e-5, _lib.BF16: 2e-2, _lib.F16: 3e-3, _lib.F16X2: 1e-5}
 
 
-@pytest.fixture(scope="module")
-def lib():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return _lib.load()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
-
-
 def _mk(shape, gen, scale=1.0):
     return (torch.randn(shape, generator=gen) * scale).float().cuda()
 
 
 # the f16x2 layout (csrc/common.h; the same helpers as tests/test_gpu_ops_x2.py)
-def to_x2(t, exp=0):
-    """fp32 [R, C] -> fp16 [R, 2C]: per 32 columns [hi | lo] of t * 2^exp."""
-    r, c = t.shape
-    ts = t.float() * (2.0 ** exp)
-    hi = ts.clamp(-65504, 65504).half()
-    lo = (ts - hi.float()).half()
-    return torch.stack([hi.view(r, c // 32, 32), lo.view(r, c // 32, 32)], dim=2).reshape(r, 2 * c).contiguous()
-
-
-def from_x2(t):
-    """fp16 [R, 2C] -> the fp64 values hi + lo [R, C]."""
-    r, c2 = t.shape
-    v = t.reshape(r, c2 // 64, 2, 32).double()
-    return (v[:, :, 0] + v[:, :, 1]).reshape(r, c2 // 2)
-
-
-def weight_exp(w):
-    m = float(w.abs().max())
-    return max(0, min(31, 13 - math.frexp(m)[1])) if m > 0 else 0
 
 
 def _operand(prec, t, exp=0):
@@ -90,15 +53,6 @@ def _operand(prec, t, exp=0):
         return x, from_x2(x) / (2.0 ** exp)
     x = t.to(DTYPES[prec]).contiguous()
     return x, x.double()
-
-
-def _values(prec, out):
-    return from_x2(out) if prec == _lib.F16X2 else out.double()
-
-
-def _nan(prec, rows, cols):
-    """NaN rows of `cols` logical columns in the precision's output layout"""
-    return torch.full((rows, 2 * cols if prec == _lib.F16X2 else cols), float("nan"), dtype=DTYPES[prec], device="cuda")
 
 
 @pytest.fixture
@@ -134,14 +88,6 @@ def _attention_plan(lib, row):
     return rc, [prec, out[0], out[5], ranges, int(ranges > 1 and nt % per != 0)]
 
 
-def _attention_ref(qkv, n_img, N, H):
-    D = H * 64
-    q, k, v = qkv.double().reshape(n_img, N, 3, H, 64).unbind(2)
-    q, k, v = (t.transpose(1, 2) for t in (q, k, v))
-    att = ((q @ k.transpose(-2, -1)) * 0.125).softmax(-1)
-    return (att @ v).transpose(1, 2).reshape(n_img * N, D)
-
-
 def _run_store(lib, row, record):
     prec, M, N, K = row["key"][0], row["M"], row["N"], row["K"]
     g = torch.Generator().manual_seed(M * 7 + N + K)
@@ -152,16 +98,16 @@ def _run_store(lib, row, record):
     lin = Ar @ Wr.t() + bias.double()
     for gelu in row["gelu"]:
         ref = torch.nn.functional.gelu(lin) if gelu else lin
-        out = _nan(prec, M + GUARD, N)
+        out = nan_like(prec, M + GUARD, N)
         lib.vitvs_op_weight_exponent(e)
-        rc = lib.vitvs_op_linear(prec, _p(A), _p(W), _p(bias), _p(out), M, N, K, gelu, _stream())
+        rc = lib.vitvs_op_linear(prec, ptr(A), ptr(W), ptr(bias), ptr(out), M, N, K, gelu, stream())
         lib.vitvs_op_weight_exponent(0)
         assert rc == 0
         torch.cuda.synchronize()
         assert torch.isnan(out[M:].float()).all(), f"{row['id']}: rows beyond M were written"
-        got = _values(prec, out[:M])
+        got = values(prec, out[:M])
         assert torch.isfinite(got).all(), f"{row['id']}: non-finite outputs"
-        _check(record, f"store_gelu{gelu}", _rel(got, ref), BAR_STORE[prec], row)
+        _check(record, f"store_gelu{gelu}", rel_max(got, ref), BAR_STORE[prec], row)
 
 
 def _run_partial(lib, row, record):
@@ -177,27 +123,27 @@ def _run_partial(lib, row, record):
     # one slice more than the launch owns: it must stay NaN, as must every row past M of the last one
     part = torch.full((slices + 1, M, D), float("nan"), dtype=torch.float32, device="cuda")
     lib.vitvs_op_weight_exponent(e)
-    rc = lib.vitvs_op_linear_partial(prec, _p(A), _p(W), _p(part), M, D, K, slices, _stream())
+    rc = lib.vitvs_op_linear_partial(prec, ptr(A), ptr(W), ptr(part), M, D, K, slices, stream())
     lib.vitvs_op_weight_exponent(0)
     assert rc == 0
     x = torch.cat([x0, torch.full((GUARD, D), float("nan"), device="cuda")]).contiguous()
-    out = _nan(prec, M + GUARD, D)
-    assert lib.vitvs_op_residual_ln(prec, _p(x), _p(part), slices, _p(bias), _p(ls), _p(gamma), _p(beta), _p(out), M, D, 1e-6,
-                                    _stream()) == 0
+    out = nan_like(prec, M + GUARD, D)
+    assert lib.vitvs_op_residual_ln(prec, ptr(x), ptr(part), slices, ptr(bias), ptr(ls), ptr(gamma), ptr(beta), ptr(out), M, D, 1e-6,
+                                    stream()) == 0
     torch.cuda.synchronize()
     assert torch.isnan(part[slices]).all(), f"{row['id']}: the slice past the launch's {slices} was written"
     assert torch.isfinite(part[:slices]).all(), f"{row['id']}: non-finite partial sums"
     ks = K // slices
     for z in range(slices):            # each slice holds the products of ITS K range, whichever workgroup computed it
         ref_z = Ar[:, z * ks:(z + 1) * ks] @ Wr[:, z * ks:(z + 1) * ks].t()
-        _check(record, f"slice{z}", _rel(part[z], ref_z), BAR_SLICE[prec], row)
+        _check(record, f"slice{z}", rel_max(part[z], ref_z), BAR_SLICE[prec], row)
     x_ref = x0.double() + ls.double() * (Ar @ Wr.t() + bias.double())
     y_ref = torch.nn.functional.layer_norm(x_ref, (D,), gamma.double(), beta.double(), 1e-6)
     assert torch.isnan(x[M:]).all() and torch.isnan(out[M:].float()).all(), f"{row['id']}: rows beyond M were written"
-    got_y = _values(prec, out[:M])
+    got_y = values(prec, out[:M])
     assert torch.isfinite(x[:M]).all() and torch.isfinite(got_y).all(), f"{row['id']}: non-finite outputs"
-    _check(record, "x", _rel(x[:M], x_ref), BAR_X[prec], row)
-    _check(record, "layernorm", _rel(got_y, y_ref), BAR_LN[prec], row)
+    _check(record, "x", rel_max(x[:M], x_ref), BAR_X[prec], row)
+    _check(record, "layernorm", rel_max(got_y, y_ref), BAR_LN[prec], row)
 
 
 def _run_attention(lib, row, record):
@@ -205,24 +151,24 @@ def _run_attention(lib, row, record):
     D = H * 64
     g = torch.Generator().manual_seed(N * 3 + H + n_img)
     qkv32 = _mk((n_img * N, 3 * D), g)
-    out = _nan(prec, n_img * N + GUARD, D)
+    out = nan_like(prec, n_img * N + GUARD, D)
     if prec in (_lib.BF16, _lib.F16):
         # the forward's form: q carries 0.125 * log2(e), applied in fp32 before the one rounding to 16 bits
         qkv32[:, :D] *= 0.125 * LOG2E
         qkv, t = _operand(prec, qkv32)
         t = t.clone()
         t[:, :D] /= 0.125 * LOG2E
-        rc = lib.vitvs_op_attention_q(prec, _p(qkv), _p(out), n_img, N, H, 1, _stream())
+        rc = lib.vitvs_op_attention_q(prec, ptr(qkv), ptr(out), n_img, N, H, 1, stream())
     else:
         qkv, t = _operand(prec, qkv32)
-        rc = lib.vitvs_op_attention(prec, _p(qkv), _p(out), n_img, N, H, _stream())
+        rc = lib.vitvs_op_attention(prec, ptr(qkv), ptr(out), n_img, N, H, stream())
     assert rc == 0
-    ref = _attention_ref(t, n_img, N, H)
+    ref = attention_ref(t, n_img, N, H)
     torch.cuda.synchronize()
     assert torch.isnan(out[n_img * N:].float()).all(), f"{row['id']}: rows beyond the last token were written"
-    got = _values(prec, out[:n_img * N])
+    got = values(prec, out[:n_img * N])
     assert torch.isfinite(got).all(), f"{row['id']}: non-finite outputs"
-    _check(record, "attention", _rel(got, ref), BAR_ATTN[prec], row)
+    _check(record, "attention", rel_max(got, ref), BAR_ATTN[prec], row)
 
 
 @pytest.mark.parametrize("row", [pytest.param(r, id=r["id"]) for r in ROWS])

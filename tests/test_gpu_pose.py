@@ -6,7 +6,6 @@ the goal-depth table restated on the host (the goal depth at every goal token's 
 v_pose, R, t, weights <= 1e-9, sigma <= 1e-12, status and pose_info exact; every reference solve keeps a relative eigen-gap >= 1e-6
 and every residual stays >= 1e-6 off the rejection edge (asserted here, on the CPU side of each comparison)."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -19,34 +18,15 @@ from vitvs_amd.engine import Engine, VitvsError
 import interaction_ref as ir
 import pose_ref as pr
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
+
 G = 14
 IMG = 16 * G
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _goal_depth(rng, holes=True):
-    d = np.ascontiguousarray(synth.depth_pattern()[::-1, ::-1]).copy()
-    d = (d.astype(np.int64) + 137).clip(1, 65535).astype(np.uint16)
-    if holes:
-        d.reshape(-1)[rng.integers(0, d.size, size=d.size // 7)] = 0
-    return d
-
-
-def _table(zg, g, img, params):
-    """The handle's goal-depth table restated: zg at every token's patch centre, entry T at pixel (0, 0)."""
-    uv = rr.token_pixels(np.arange(g * g), g, img, params.u_max, params.v_max)
-    return np.concatenate([zg[uv[:, 1], uv[:, 0]], zg[0:1, 0]]).astype(np.uint16)
-
-
-def _pitches(params, stride, img):
-    return stride * params.u_max / img, stride * params.v_max / img
 
 
 def _reference(det, b, cam_status, K, table, lam, n_iter, pitches, degenerate=False):
@@ -57,12 +37,8 @@ def _reference(det, b, cam_status, K, table, lam, n_iter, pitches, degenerate=Fa
     return ref
 
 
-def _host(info):
-    return {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in info.items()}
-
-
 def _compare(v, info, b, ref, what, up_to_sign=False):
-    info = _host(info)
+    info = ls.host(info)
     v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
     assert int(info["status"][b]) == ref["status"], (what, info["status"][b], ref["status"])
     got_info = [int(info[name][b]) for name in Engine.POSE_INFO_FIELDS]
@@ -75,52 +51,13 @@ def _compare(v, info, b, ref, what, up_to_sign=False):
     assert abs(float(info["sigma"][b]) - ref["sigma"]) <= 1e-12, what
 
 
-_ENGINES = {}
-
-
-def _engine(lam=None, max_rows=130):
-    key = (lam, max_rows)
-    if key not in _ENGINES:
-        params = config.ServoParams(dino_input_size=IMG) if lam is None else config.ServoParams(dino_input_size=IMG, lambda_=lam)
-        _ENGINES[key] = (Engine(_tiny_cfg(IMG), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    eng, params = _ENGINES[key]
-    for option in ("robust_law", "subpatch", "interaction"):
-        eng.set_option(option, 0)
-    return eng, params
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
-
-
-def _law(eng, sc, num_pairs=None, ids=None, select=_lib.SELECT_EXPLICIT, offsets=None):
-    ids = sc["ids"] if ids is None else ids
-    k = len(sc["ids"]) if num_pairs is None else num_pairs
-    v, st = eng.servo_from_nn(sc["nn_1"], sc["nn_2"], sc["sim_1"], sc["depth"], sc["K"], mode=select,
-                              selection=[ids] if select == _lib.SELECT_EXPLICIT else ids, num_pairs=k, offsets=offsets)
-    return v.cpu().numpy(), int(st)
-
-
-def _snapshot(eng, v):
-    det = eng.last_details(1)
-    return dict(det, v_c=np.array(v, copy=True))
-
-
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
-
-
 def _scenario(seed, num_pairs, share=0.125):
-    eng, params = _engine()
+    eng, params = ENGINES.fetch(G, 130, reset=ls.LAW_OPTIONS)
     rng = np.random.default_rng(seed)
     K = (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
          params.v_max / 2 + float(rng.uniform(-20, 20)))
     sc = rr.planted_scenario(rng, num_pairs, share, params, K=K, g=G, holes=True)
-    return eng, params, sc, _goal_depth(rng)
+    return eng, params, sc, ls.goal_depth(rng)
 
 
 @pytest.mark.parametrize("num_pairs", [8, 24, 130])
@@ -128,10 +65,10 @@ def test_device_equals_the_reference_and_leaves_the_call_untouched(num_pairs):
     """Holes in both depth images, random intrinsics, 12 % wrong matches; N = 0 and 4; 130 pairs: L of the camera's law is global."""
     eng, params, sc, zg = _scenario(61000 + num_pairs, num_pairs)
     eng.set_goal_depth(zg)
-    v_c, st = _law(eng, sc)
+    v_c, st = ls.servo_law(eng, sc)
     assert st == _lib.STATUS_OK
-    before = _snapshot(eng, v_c)
-    table, pitches = _table(zg, G, IMG, params), _pitches(params, 16, IMG)
+    before = ls.snapshot(eng, v_c)
+    table, pitches = ls.goal_table(zg, G, IMG, params), ls.pitches(params, 16, IMG)
     holes = 0
     for n_iter in (0, 4):
         v, info = eng.pose_velocity(sc["K"], [st], n_iter)
@@ -140,21 +77,21 @@ def test_device_equals_the_reference_and_leaves_the_call_untouched(num_pairs):
         holes = int(ref["info"][5])
         # the host-pointer form: the same launch
         v_h, info_h = eng.pose_velocity_host(sc["K"], [st], n_iter)
-        assert np.array_equal(v_h, v.cpu().numpy()) and _same(_host(info), info_h)
+        assert np.array_equal(v_h, v.cpu().numpy()) and ls.same_values(ls.host(info), info_h)
     assert holes > 0 or num_pairs == 8                          # the depth images have holes: some rows are dropped
-    assert _same(_snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
+    assert ls.same_values(ls.snapshot(eng, v_c), before)                   # v_c and every vitvs_last_* output as the velocity call left them
 
 
 def test_quarter_turn_has_no_retreat():
     """§5c's case: the image-based law backs away at 0.61 m/s for lambda = 1; the pose law turns on the spot."""
     case = ir.quarter_turn_case()
-    eng, params = _engine(lam=case["lam"])
+    eng, params = ENGINES.fetch(G, 130, lam=case["lam"], reset=ls.LAW_OPTIONS)
     eng.set_goal_depth(case["goal_depth"])
-    v_c, st = _law(eng, case)
+    v_c, st = ls.servo_law(eng, case)
     assert st == _lib.STATUS_OK and abs(v_c[2] + 0.61) < 0.01
     det = eng.last_details(1)
     v, info = eng.pose_velocity(case["K"], [st])
-    ref = _reference(det, 0, st, case["K"], _table(case["goal_depth"], G, IMG, params), case["lam"], 0, _pitches(params, 16, IMG))
+    ref = _reference(det, 0, st, case["K"], ls.goal_table(case["goal_depth"], G, IMG, params), case["lam"], 0, ls.pitches(params, 16, IMG))
     _compare(v, info, 0, ref, "quarter turn")
     v = v.cpu().numpy()[0]
     print(f"quarter turn: image-based v_z = {v_c[2]:+.4f}, pose law v_z = {v[2]:+.2e}, w_z = {v[5]:+.4f}")
@@ -170,13 +107,13 @@ def test_half_turn():
     nn2 = nn1.copy()
     nn2[[nn1[0], nn1[1], nn1[2]]] = (np.array([0, 1, 2]) + 50) % t          # tokens 0, 1, 2 are not mutual (no goal token of `ids`)
     case = dict(case, nn_1=nn1, nn_2=nn2)
-    eng, params = _engine(lam=case["lam"])
+    eng, params = ENGINES.fetch(G, 130, lam=case["lam"], reset=ls.LAW_OPTIONS)
     eng.set_goal_depth(case["goal_depth"])
-    v_c, st = _law(eng, case)
+    v_c, st = ls.servo_law(eng, case)
     assert st == _lib.STATUS_OK
     det = eng.last_details(1)
     v, info = eng.pose_velocity(case["K"], [st])
-    ref = _reference(det, 0, st, case["K"], _table(case["goal_depth"], G, IMG, params), case["lam"], 0, _pitches(params, 16, IMG))
+    ref = _reference(det, 0, st, case["K"], ls.goal_table(case["goal_depth"], G, IMG, params), case["lam"], 0, ls.pitches(params, 16, IMG))
     _compare(v, info, 0, ref, "half turn", up_to_sign=True)
     v = v.cpu().numpy()[0]
     print(f"half turn: image-based w_z = {v_c[5]:+.4f}, pose law |w_z| = {abs(v[5]):.6f}, v_z = {v[2]:+.2e}")
@@ -194,12 +131,12 @@ def test_with_the_other_law_options(option):
         offsets = np.random.default_rng(7).uniform(-0.5, 0.5, size=(G * G, 2)).astype(np.float32)
     else:
         eng.set_option(option, 2 if option == "interaction" else 4)
-    v_c, st = _law(eng, sc, offsets=offsets)
+    v_c, st = ls.servo_law(eng, sc, offsets=offsets)
     assert st == _lib.STATUS_OK
     det = eng.last_details(1)
     if option == "subpatch":
         assert det["offsets"][0, :24].any()
-    table, pitches = _table(zg, G, IMG, params), _pitches(params, 16, IMG)
+    table, pitches = ls.goal_table(zg, G, IMG, params), ls.pitches(params, 16, IMG)
     for n_iter in (0, 4):
         v, info = eng.pose_velocity(sc["K"], [st], n_iter)
         _compare(v, info, 0, _reference(det, 0, st, sc["K"], table, params.lambda_, n_iter, pitches), f"{option}, N = {n_iter}")
@@ -214,34 +151,34 @@ def test_camera_statuses_and_the_same_image():
     mutual = np.nonzero(sc["nn_2"][sc["nn_1"]] == np.arange(t))[0]
     few = np.intersect1d(mutual, sc["ids"])[:3].astype(np.int32)
     assert len(few) == 3
-    v_c, st = _law(eng, sc, num_pairs=24, ids=few)
+    v_c, st = ls.servo_law(eng, sc, num_pairs=24, ids=few)
     assert st == _lib.STATUS_TOO_FEW
     v, info = eng.pose_velocity(sc["K"], [st], 4)
-    info = _host(info)
+    info = ls.host(info)
     assert int(info["status"][0]) == _lib.STATUS_TOO_FEW and not v.cpu().numpy().any() and np.array_equal(info["R"][0], np.eye(3))
     assert not info["weights"].any() and float(info["sigma"][0]) == 0.0
     # no correspondence
     ident = dict(sc, nn_1=np.arange(t), nn_2=np.arange(t), sim_1=np.full(t, 0.5, np.float32))
     order = np.random.default_rng(1).permutation(t).astype(np.int32)
-    v_c, st = _law(eng, ident, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
+    v_c, st = ls.servo_law(eng, ident, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
     assert st == _lib.STATUS_NO_CORRESPONDENCE
     v, info = eng.pose_velocity(sc["K"], [st])
     assert int(info["status"][0]) == _lib.STATUS_NO_CORRESPONDENCE and not v.cpu().numpy().any()
     # the same image: OK, v = 0 and R = I exactly
     same = dict(sc, sim_1=np.ones(t, np.float32))
-    v_c, st = _law(eng, same, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
+    v_c, st = ls.servo_law(eng, same, num_pairs=24, ids=order, select=_lib.SELECT_ORDER)
     det = eng.last_details(1)
     assert st == _lib.STATUS_OK and int(det["info"][0, 2]) == 1
     v, info = eng.pose_velocity(sc["K"], [st], 4)
-    info = _host(info)
+    info = ls.host(info)
     assert int(info["status"][0]) == _lib.STATUS_OK and not v.cpu().numpy().any()
     assert np.array_equal(info["R"][0], np.eye(3)) and not info["t"].any()
     # a law of four rows: the pose law counts its own usable rows (a hole in either depth leaves fewer than the camera's four)
     four = np.intersect1d(mutual, sc["ids"])[:4].astype(np.int32)
-    v_c, st = _law(eng, sc, num_pairs=4, ids=four)
+    v_c, st = ls.servo_law(eng, sc, num_pairs=4, ids=four)
     assert st == _lib.STATUS_OK
     det = eng.last_details(1)
-    table, pitches = _table(zg, G, IMG, params), _pitches(params, 16, IMG)
+    table, pitches = ls.goal_table(zg, G, IMG, params), ls.pitches(params, 16, IMG)
     ref = _reference(det, 0, st, sc["K"], table, params.lambda_, 0, pitches, degenerate=True)
     v, info = eng.pose_velocity(sc["K"], [st])
     _compare(v, info, 0, ref, "four rows")
@@ -249,15 +186,15 @@ def test_camera_statuses_and_the_same_image():
 
 def test_error_returns():
     params = config.ServoParams(dino_input_size=IMG)
-    eng = Engine(_tiny_cfg(IMG), params, precision="fp32", max_pairs=2, max_rows=48)
+    eng = Engine(ls.tiny_cfg(IMG), params, precision="fp32", max_pairs=2, max_rows=48)
     rng = np.random.default_rng(64)
     sc = rr.planted_scenario(rng, 24, 0.0, params, g=G, holes=True)
-    zg = _goal_depth(rng)
+    zg = ls.goal_depth(rng)
     K, st = params.intrinsics(), [0]
     eng.set_goal_depth(zg)
     with pytest.raises(VitvsError, match=r"\(-5\)"):           # no law evaluation yet
         eng.pose_velocity(K, st)
-    _law(eng, sc)
+    ls.servo_law(eng, sc)
     eng.pose_velocity(K, st)
     with pytest.raises(VitvsError, match=r"\(-5\)"):           # not the pair count of the last law evaluation
         eng.pose_velocity(K, [0, 0])
@@ -271,11 +208,11 @@ def test_error_returns():
         eng.pose_velocity(K, st)
     eng.set_goal_depth(zg)
     eng.set_option("interaction", 1)
-    _law(eng, sc)
+    ls.servo_law(eng, sc)
     with pytest.raises(VitvsError, match=r"\(-5\)"):           # feat holds Z*, not Z
         eng.pose_velocity(K, st)
     eng.set_option("interaction", 0)
-    _law(eng, sc)
+    ls.servo_law(eng, sc)
     v, info = eng.pose_velocity(K, st)
     assert int(info["status"][0]) == _lib.STATUS_OK
     # the C entry points' own checks
@@ -306,23 +243,23 @@ def test_through_a_vits16_handle():
     des, cur = synth.frame_pair(cfg.img_size, 20250705)
     rng = np.random.default_rng(65)
     depth, K = synth.depth_pattern(), params.intrinsics()
-    zg, zg2 = _goal_depth(rng), _goal_depth(rng)
+    zg, zg2 = ls.goal_depth(rng), ls.goal_depth(rng)
     k, g, n = params.num_pairs, cfg.grid, 3
     three = lambda a: np.stack([a] * n)   # noqa: E731
     orders = np.stack([np.random.default_rng(70 + b).permutation(cfg.tokens) for b in range(n)]).astype(np.int32)
     eng.set_goal_depth(zg)                                      # n_goal = 1 serves the three pairs
-    pitches = _pitches(params, cfg.stride, cfg.img_size)
+    pitches = ls.pitches(params, cfg.stride, cfg.img_size)
 
     def check(v_c, st, goal, what):
         st_h = st.cpu().numpy()
         before = dict(eng.last_details(n), v_c=v_c.cpu().numpy().copy())
-        table = _table(goal, g, cfg.img_size, params)
+        table = ls.goal_table(goal, g, cfg.img_size, params)
         for n_iter in (0, 4):
             v, info = eng.pose_velocity(K, st, n_iter)
             for b in range(n):
                 ref = _reference(before, b, st_h[b], K, table, params.lambda_, n_iter, pitches)
                 _compare(v, info, b, ref, f"{what}, pair {b}, N = {n_iter}")
-        assert _same(dict(eng.last_details(n), v_c=v_c.cpu().numpy()), before)
+        assert ls.same_values(dict(eng.last_details(n), v_c=v_c.cpu().numpy()), before)
         return v.cpu().numpy()
 
     v_c, st = eng.compute_velocity(three(cur), three(des), three(depth), K, mode=_lib.SELECT_ORDER, selection=orders)

@@ -7,46 +7,19 @@ image rendered at the goal pose is the goal depth.  Each pose run must end throu
 skipped update; with N = 4 the final position and orientation errors must be below their 5 cm / 5 degree start.  No ratio against
 the image-based run is asserted: none was measured before this test was written; the final pose errors of all three are printed
 (DESIGN.md §5f quotes them)."""
-import numpy as np
 import pytest
-import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, loop, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
-
 
 def _run_loop(law, n_iter):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, law=law, pose_robust_iterations=n_iter)
-    eng = Engine(cfg, params, precision="fp32", max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(128, 11), 1.6 / 128, params, plane_z=0.61, device="cuda")
-    goal_rgb, goal_depth = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, params=params, selection="order", goal_depth=goal_depth)
-    ctl.generator = torch.Generator().manual_seed(121)
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = CameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
-    status, pose_status = [], []
-    real_ibvs = ctl.ibvs
-
-    def recording_ibvs():
-        real_ibvs()
-        status.append(ctl.last_status)
-        pose_status.append(ctl.last_pose_status)
-    ctl.ibvs = recording_ibvs
-    logs = []
-    sl = loop.ServoLoop(ctl, np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0]), get_pose=sim.get_pose, apply_twist=sim.apply_twist,
-                        sense=sim.sense, max_iterations=360, log=logs.append)
-    res = sl.run()
+    eng, _, ctl, sim = cl.set_up(dict(law=law, pose_robust_iterations=n_iter), give_params=True, give_goal_depth=True,
+                                 generator_seed=121)
+    status, pose_status = cl.record_ibvs(ctl, ["last_status", "last_pose_status"])
+    res, sl, logs = cl.run_servo_loop(ctl, sim)
     eng.close()
     return res, sl, logs, status, pose_status, len(ctl.velocity_vector_history)
 

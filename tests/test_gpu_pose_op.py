@@ -27,17 +27,12 @@ N_ITERS = (0, 1, 4, 16)
 SMIN = 0.004
 
 
-def _unit(v):
-    v = np.asarray(v, np.float64)
-    return v / np.linalg.norm(v)
-
-
 def _pair(seed, rows, angle, usable=None, coplanar=False, outliers=0, noise=0.002, ties=0):
     """One pair's (P, Q, usable): a seeded pose at the given rotation angle, Q at 0.5 - 0.8 m (or on the plane z = 0.61),
     P = the same points in the camera + noise, `outliers` usable rows moved by 0.1 - 0.4 m, the first `ties` usable rows repeated in
     the following `ties` usable rows (equal residuals, bit for bit)."""
     rng = np.random.default_rng(seed)
-    R, t = pr.rodrigues(_unit(rng.standard_normal(3)) * angle), rng.uniform(-0.08, 0.08, 3)
+    R, t = pr.rodrigues(pr.unit(rng.standard_normal(3)) * angle), rng.uniform(-0.08, 0.08, 3)
     Z = np.full(rows, 0.61) if coplanar else rng.uniform(0.5, 0.8, rows)
     Q = np.stack([rng.uniform(-0.4, 0.4, rows) * Z, rng.uniform(-0.3, 0.3, rows) * Z, Z], 1)
     P = pr.points_in_camera(Q, R, t) + rng.standard_normal((rows, 3)) * noise
@@ -45,19 +40,11 @@ def _pair(seed, rows, angle, usable=None, coplanar=False, outliers=0, noise=0.00
     live = np.nonzero(usable > 0)[0]
     if outliers:
         bad = rng.choice(live[2 * ties:], outliers, replace=False)
-        P[bad] += np.stack([_unit(d) for d in rng.standard_normal((outliers, 3))]) * rng.uniform(0.1, 0.4, (outliers, 1))
+        P[bad] += np.stack([pr.unit(d) for d in rng.standard_normal((outliers, 3))]) * rng.uniform(0.1, 0.4, (outliers, 1))
     if ties:
         P[live[ties:2 * ties]], Q[live[ties:2 * ties]] = P[live[:ties]], Q[live[:ties]]
     P[usable <= 0], Q[usable <= 0] = 0.0, 0.0
     return P, Q, usable
-
-
-def _flags(rows, where, n_off):
-    """`n_off` unusable rows first / in the middle / last, alternating padded rows (0) and holes (-1)."""
-    u = np.ones(rows, np.int32)
-    start = {"first": 0, "middle": (rows - n_off) // 2, "last": rows - n_off}[where]
-    u[start:start + n_off] = np.where(np.arange(n_off) % 2 == 0, 0, -1)
-    return u
 
 
 def _case(*pairs, degenerate=False):
@@ -66,8 +53,8 @@ def _case(*pairs, degenerate=False):
 
 
 def _collinear(rows):
-    line = np.outer(np.linspace(-0.3, 0.3, rows), _unit([1.0, -1.0, 0.2])) + np.array([0.0, 0.0, 0.6])
-    R, t = pr.rodrigues(_unit([0.2, 0.5, -0.3]) * 0.5), np.array([0.03, -0.02, 0.04])
+    line = np.outer(np.linspace(-0.3, 0.3, rows), pr.unit([1.0, -1.0, 0.2])) + np.array([0.0, 0.0, 0.6])
+    R, t = pr.rodrigues(pr.unit([0.2, 0.5, -0.3]) * 0.5), np.array([0.03, -0.02, 0.04])
     return pr.points_in_camera(line, R, t), line
 
 
@@ -75,13 +62,13 @@ def _cases():
     out = {}
     out["1x3"] = _case(_pair(1, 3, 1.0))
     out["1x4_coplanar_near_pi"] = _case(_pair(2, 4, np.pi - 1e-3, coplanar=True, noise=0.0))
-    out["3x24"] = _case(_pair(3, 24, 0.4, _flags(24, "first", 5), outliers=4),               # 19 usable
-                        _pair(4, 24, 2.0, _flags(24, "middle", 4), outliers=3),              # 20 usable
-                        _pair(5, 24, np.pi - 1e-3, _flags(24, "last", 3), coplanar=True))    # 21 usable
-    out["1x130_coplanar"] = _case(_pair(6, 130, 2.5, _flags(130, "middle", 7), coplanar=True, outliers=20))
-    out["1x258_ties"] = _case(_pair(7, 258, 0.7, _flags(258, "first", 2), outliers=30, ties=40))
-    out["1x1100"] = _case(_pair(8, 1100, 1.3, _flags(1100, "last", 37), outliers=150, ties=3))
-    out["1x24_two_usable"] = _case(_pair(9, 24, 0.5, _flags(24, "first", 22)), degenerate=True)
+    out["3x24"] = _case(_pair(3, 24, 0.4, pr.unusable_flags(24, "first", 5), outliers=4),               # 19 usable
+                        _pair(4, 24, 2.0, pr.unusable_flags(24, "middle", 4), outliers=3),              # 20 usable
+                        _pair(5, 24, np.pi - 1e-3, pr.unusable_flags(24, "last", 3), coplanar=True))    # 21 usable
+    out["1x130_coplanar"] = _case(_pair(6, 130, 2.5, pr.unusable_flags(130, "middle", 7), coplanar=True, outliers=20))
+    out["1x258_ties"] = _case(_pair(7, 258, 0.7, pr.unusable_flags(258, "first", 2), outliers=30, ties=40))
+    out["1x1100"] = _case(_pair(8, 1100, 1.3, pr.unusable_flags(1100, "last", 37), outliers=150, ties=3))
+    out["1x24_two_usable"] = _case(_pair(9, 24, 0.5, pr.unusable_flags(24, "first", 22)), degenerate=True)
     P, Q = _collinear(24)
     out["1x24_collinear"] = _case((P, Q, np.ones(24, np.int32)), degenerate=True)
     # 9 collinear inliers and 3 rows far off the line: a full-rank cloud until the re-weighting has thrown the three out

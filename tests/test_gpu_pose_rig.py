@@ -15,26 +15,12 @@ from vitvs_amd import _lib, config, servo, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
 
 import pose_rig_ref as rr
-import robust_ref as rb
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
 
 KEY = "vits16_224"
-N = 3
-
-
-def _goal_depth(seed):
-    rng = np.random.default_rng(seed)
-    d = np.ascontiguousarray(synth.depth_pattern()[::-1, ::-1]).copy()
-    d = (d.astype(np.int64) + 137 + 11 * seed).clip(1, 65535).astype(np.uint16)
-    d.reshape(-1)[rng.integers(0, d.size, size=d.size // 7)] = 0
-    return d
-
-
-def _table(zg, g, img, params):
-    """The handle's goal-depth table restated: zg at every token's patch centre, entry T at pixel (0, 0)."""
-    uv = rb.token_pixels(np.arange(g * g), g, img, params.u_max, params.v_max)
-    return np.concatenate([zg[uv[:, 1], uv[:, 0]], zg[0:1, 0]]).astype(np.uint16)
+N = ls.N_CAMERAS
 
 
 @pytest.fixture(scope="module")
@@ -48,23 +34,12 @@ def setup():
     eng = Engine(cfg, params, precision="fp32", max_pairs=N).load_state_dict(sd)
     rng = np.random.default_rng(3)
     rig = rr.seeded_rig(rng, N)
-    goals = np.stack([_goal_depth(s) for s in range(N)])
+    goals = np.stack([ls.goal_depth_of(s) for s in range(N)])
     yield dict(cfg=cfg, params=params, sd=sd, des=np.stack([des] * N), curs=[np.stack(c) for c in curs], depth=depth, eng=eng,
-               rig=rig, goals=goals, tables=np.stack([_table(z, cfg.grid, cfg.img_size, params) for z in goals]),
+               rig=rig, goals=goals, tables=np.stack([ls.goal_table(z, cfg.grid, cfg.img_size, params) for z in goals]),
                pitches=(cfg.stride * params.u_max / cfg.img_size, cfg.stride * params.v_max / cfg.img_size),
                K=np.array([params.intrinsics()] * N))
     eng.close()
-
-
-def _order(cfg, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.stack([torch.randperm(cfg.tokens, generator=g) for _ in range(n)]).to(torch.int32)
-
-
-def _velocity(s, eng=None, r=0, n=N, seed=11):
-    eng = eng or s["eng"]
-    return eng.compute_velocity(s["curs"][r][:n], s["des"][:n], s["depth"][:n], s["params"].intrinsics(), mode=_lib.SELECT_ORDER,
-                                selection=_order(s["cfg"], n, seed))
 
 
 def _reference(s, det, status, n_iter, tables, rig=None, K=None, degenerate=False):
@@ -110,7 +85,7 @@ def test_device_equals_the_reference_and_leaves_the_call_untouched(setup, per_ca
     eng.set_goal_depth(s["goals"] if per_camera else s["goals"][0])
     tables = s["tables"] if per_camera else s["tables"][:1]
     try:
-        v_c, st = _velocity(s)
+        v_c, st = ls.rig_velocity(s)
         assert not st.cpu().numpy().any()
         before = _snapshot(eng, v_c, st)
         pose_before = eng.pose_velocity_host(s["params"].intrinsics(), before["status"], 4)
@@ -137,7 +112,7 @@ def test_a_camera_with_too_few_features_and_nobody(setup):
     s, eng = setup, setup["eng"]
     eng.set_goal_depth(s["goals"])
     try:
-        _velocity(s)
+        ls.rig_velocity(s)
         tab = eng.last_tables(N)
         ids = []
         for b in range(N):
@@ -171,7 +146,7 @@ def test_with_the_other_law_options(setup, option):
     eng.set_goal_depth(s["goals"])
     try:
         eng.set_option(option, {"subpatch": 1, "interaction": 2, "robust_law": 4}[option])
-        v_c, st = _velocity(s)
+        v_c, st = ls.rig_velocity(s)
         sth = st.cpu().numpy()
         assert not sth.any()
         det = eng.last_details(N)
@@ -194,7 +169,7 @@ def test_error_returns(setup):
     fresh.close()
     try:
         eng.set_goal_depth(None)
-        _, st = _velocity(s)
+        _, st = ls.rig_velocity(s)
         with pytest.raises(VitvsError, match=r"\(-5\)"):           # no goal depth
             eng.pose_rig_velocity(s["rig"], K, st)
         with pytest.raises(VitvsError, match=r"\(-5\)"):
@@ -206,11 +181,11 @@ def test_error_returns(setup):
         with pytest.raises(VitvsError, match=r"\(-5\)"):           # not the call's pair count
             eng.pose_rig_velocity(s["rig"][:2], K, st[:2])
         eng.set_option("interaction", 1)
-        _, st = _velocity(s)
+        _, st = ls.rig_velocity(s)
         with pytest.raises(VitvsError, match=r"\(-5\)"):           # feat holds Z*, not Z
             eng.pose_rig_velocity(s["rig"], K, st)
         eng.set_option("interaction", 0)
-        _, st = _velocity(s)
+        _, st = ls.rig_velocity(s)
         v, rs, info = eng.pose_rig_velocity(s["rig"], K, st)
         assert rs == 0
         # the C entry points' own checks
@@ -245,7 +220,7 @@ def test_under_graph_replay_with_new_frames(setup):
     des = torch.as_tensor(s["des"]).to(dev)
     z = torch.as_tensor(s["depth"]).to(dev)
     K = torch.tensor([s["params"].intrinsics()] * N, dtype=torch.float64, device=dev)
-    order = _order(s["cfg"], N, 12).to(dev)
+    order = ls.order(s["cfg"], N, 12).to(dev)
     v = torch.zeros((N, 6), dtype=torch.float64, device=dev)
     st = torch.zeros(N, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)

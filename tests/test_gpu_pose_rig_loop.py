@@ -13,6 +13,7 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import config, servo, synth, weights
 from planar_sim import PlanarScene, rodrigues
+import closed_loop as cl
 
 import test_gpu_rig_loop as base
 
@@ -25,18 +26,18 @@ def _run_pose(seed=SEED):
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, law="pose")
     eng = Engine(cfg, params.replace(law="ibvs"), precision="fp32", max_pairs=2).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     scene = PlanarScene(synth.texture(base.TEX_PX, 11), base.MPP, params, plane_z=base.PLANE_Z, device="cuda")
-    ext = base._extrinsics()
-    at_goal = [scene.render(*base._camera_pose(np.eye(3), np.zeros(3), e)) for e in ext]
+    ext = cl.toed_in_pair()
+    at_goal = [scene.render(*cl.camera_pose(np.eye(3), np.zeros(3), e)) for e in ext]
     goals = [g[0] for g in at_goal]
     goal_depth = np.stack([np.asarray(g[1].cpu() if torch.is_tensor(g[1]) else g[1]).astype(np.uint16) for g in at_goal])
     mc = servo.MultiController(eng, goals, params=params, selection="order", rig=ext, goal_depth=goal_depth,
                                generator=torch.Generator().manual_seed(seed))
-    Rr, tr = base._start_pose()
-    start_pose = base._pose_error(Rr, tr)
+    Rr, tr = cl.start_pose()
+    start_pose = cl.rig_pose_error(Rr, tr)
     statuses = []
     for _ in range(base.UPDATES):
         for i, e in enumerate(ext):
-            rgb, depth = scene.render(*base._camera_pose(Rr, tr, e))
+            rgb, depth = scene.render(*cl.camera_pose(Rr, tr, e))
             mc.image_callback_rgb(i, rgb)
             mc.image_callback_depth(i, depth)
         mc.ibvs()
@@ -46,7 +47,7 @@ def _run_pose(seed=SEED):
             tr = tr + Rr @ v[:3] * base.DT
             Rr = Rr @ rodrigues(v[3:] * base.DT)
     eng.close()
-    return statuses, start_pose, base._pose_error(Rr, tr)
+    return statuses, start_pose, cl.rig_pose_error(Rr, tr)
 
 
 @pytest.mark.gpu

@@ -29,14 +29,6 @@ N_ITERS = (0, 1, 4, 16)
 SMIN = 0.004
 
 
-def _flags(rows, where, n_off):
-    """`n_off` unusable rows first / in the middle / last, alternating padded rows (0) and holes (-1)."""
-    u = np.ones(rows, np.int32)
-    start = {"first": 0, "middle": (rows - n_off) // 2, "last": rows - n_off}[where]
-    u[start:start + n_off] = np.where(np.arange(n_off) % 2 == 0, 0, -1)
-    return u
-
-
 def _from_rig(X, rig):
     """Rig-frame points [n_cams, rows, 3] in their cameras' frames."""
     return np.stack([(X[i] - ti) @ Ri for i, (Ri, ti) in enumerate(rig)])
@@ -88,9 +80,9 @@ def _cases():
     out["1x3"] = _case(1, 1, 3, 1.0)
     out["1x4_coplanar_near_pi"] = _case(2, 1, 4, np.pi - 1e-3, coplanar=True, noise=0.0)
     out["2x2"] = _case(3, 2, 2, 0.6)
-    f24 = np.stack([_flags(24, "first", 5), _flags(24, "middle", 4), _flags(24, "last", 3)])      # 19 + 20 + 21 usable
+    f24 = np.stack([pr.unusable_flags(24, "first", 5), pr.unusable_flags(24, "middle", 4), pr.unusable_flags(24, "last", 3)])      # 19 + 20 + 21 usable
     out["3x24"] = _case(4, 3, 24, 0.4, f24, outliers=5)
-    out["3x24_odd_near_pi"] = _case(5, 3, 24, np.pi - 1e-3, np.stack([_flags(24, "last", 4)] + [np.ones(24, np.int32)] * 2),
+    out["3x24_odd_near_pi"] = _case(5, 3, 24, np.pi - 1e-3, np.stack([pr.unusable_flags(24, "last", 4)] + [np.ones(24, np.int32)] * 2),
                                     coplanar=True)
     out["3x24_odd_near_pi"]["usable"][1, 7] = 0                                                   # 20 + 23 + 24 usable: an odd count
     out["3x24_odd_near_pi"]["P"][1, 7] = out["3x24_odd_near_pi"]["Q"][1, 7] = 0.0
@@ -98,10 +90,10 @@ def _cases():
         out[f"3x24_out_{where}"] = _case(6, 3, 24, 2.0, f24, status=st, outliers=0 if where == "first" else 4)
     out["3x24_nobody"] = _case(7, 3, 24, 0.5, status=[2, 1, 3])
     out["8x24"] = _case(8, 8, 24, 1.2, status=[0, 0, 0, 2, 0, 0, 0, 0], outliers=8)
-    out["2x130_coplanar"] = _case(9, 2, 130, 2.5, np.stack([_flags(130, "middle", 7), _flags(130, "first", 2)]), coplanar=True,
+    out["2x130_coplanar"] = _case(9, 2, 130, 2.5, np.stack([pr.unusable_flags(130, "middle", 7), pr.unusable_flags(130, "first", 2)]), coplanar=True,
                                   outliers=20)
-    out["3x258_ties"] = _case(10, 3, 258, 0.7, np.stack([_flags(258, "first", 2)] * 3), outliers=60, ties=40)
-    out["5x260"] = _case(11, 5, 260, 1.3, np.stack([_flags(260, "last", 37)] * 5), outliers=100, ties=3)
+    out["3x258_ties"] = _case(10, 3, 258, 0.7, np.stack([pr.unusable_flags(258, "first", 2)] * 3), outliers=60, ties=40)
+    out["5x260"] = _case(11, 5, 260, 1.3, np.stack([pr.unusable_flags(260, "last", 37)] * 5), outliers=100, ties=3)
     two = np.zeros((3, 24), np.int32)
     two[0, 3], two[2, 20] = 1, 1
     out["3x24_two_usable"] = _case(12, 3, 24, 0.5, two, degenerate=True)

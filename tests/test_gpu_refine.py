@@ -12,8 +12,6 @@
     bar of the first item; s_uv, Z and v_c against the oracle's law on the pixels those offsets give.
   * off means off, identical frames, graph replay.
 Helpers follow tests/test_gpu_robust_law.py."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
@@ -21,46 +19,18 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
-from oracle import servo_ref as sr
 import refine_ref as rf
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
 
 LDLT = -1
 VC_BAR, L_BAR, W_BAR = 1e-9, 1e-13, 1e-9
 BAR_FACTOR = 4.0
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-_ENGINES = {}
-
-
-def _servo_engine(g, max_rows, max_pairs=1):
-    """A tiny handle (no weights: the law and the seam alone) for a g x g grid."""
-    key = (g, max_rows, max_pairs)
-    if key not in _ENGINES:
-        img = 16 * g
-        params = config.ServoParams(dino_input_size=img)
-        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=max_pairs, max_rows=max_rows), params)
-    return _ENGINES[key]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
-
-
-def _intrinsics(rng, params):
-    return (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-            params.v_max / 2 + float(rng.uniform(-20, 20)))
 
 
 # ----------------------------------------------------------------------------- the seam: vitvs_refine_dev
@@ -69,7 +39,7 @@ def _intrinsics(rng, params):
 @pytest.mark.parametrize("T", rf.SEAM_TOKENS)
 def test_refine_dev_equals_the_reference(T, Dp, kind):
     # the handle's descriptor workspace holds 2 * max_pairs * T_handle * 128 floats: 28 pairs of 1369 tokens take 2 x 1369 x 3456
-    eng, _ = _servo_engine(37, 48, max_pairs=28)
+    eng, _ = ENGINES.fetch(37, 48, max_pairs=28)
     g = int(round(np.sqrt(T)))
     d1, d2 = rf.descriptor_case(T, Dp, kind)
     S = rf.cosine_similarity(d1, d2)
@@ -91,7 +61,7 @@ def test_refine_dev_equals_the_reference(T, Dp, kind):
 
 
 def test_refine_dev_matches_outside_the_grid_and_bad_arguments():
-    eng, _ = _servo_engine(37, 48, max_pairs=28)
+    eng, _ = ENGINES.fetch(37, 48, max_pairs=28)
     d1, d2 = rf.descriptor_case(196, 384, "smooth")
     nn1 = rf.cosine_similarity(d1, d2).argmax(1)
     nn1[:3] = (-1, 196, 10 ** 6)
@@ -116,9 +86,9 @@ def _check_law(det, v, st, ref, s_star, s_, rows, what, off_rows=None):
 
 
 def _scenario(seed, num_pairs, g=14, share=0.0):
-    eng, params = _servo_engine(g, max(130, g * g))
+    eng, params = ENGINES.fetch(g, max(130, g * g))
     rng = np.random.default_rng(seed)
-    sc = rr.planted_scenario(rng, num_pairs, share, params, K=_intrinsics(rng, params), g=g, holes=True)
+    sc = rr.planted_scenario(rng, num_pairs, share, params, K=ls.intrinsics(rng, params), g=g, holes=True)
     table = rng.uniform(-0.5, 0.5, size=(g * g, 2)).astype(np.float32)
     table[rng.integers(0, g * g, size=g * g // 8)] = 0.0
     return eng, params, sc, table

@@ -1,6 +1,6 @@
 """Closed loop on the GPU with the sub-patch refinement of matches (option ``subpatch``).
 
-The set-up of tests/test_gpu_loop.py (copied, not imported): ``servo.Controller(Engine)`` on ViT-S/16 224² with synthetic weights
+The set-up of tests/test_gpu_loop.py (tests/closed_loop.py): ``servo.Controller(Engine)`` on ViT-S/16 224² with synthetic weights
 driving a simulated camera (tests/planar_sim.py) over the smooth texture (synth.texture at 128 px over 1.6 m, 0.61 m away) from a
 5 cm / 5 degree offset, ``selection="order"``, dt = 0.5 s, torch seed 121.  That loop ends in the patch-quantisation dead zone: the
 features are patch centres, so once every match is the identity the error is 0 wherever within a patch pitch the camera stands.
@@ -18,39 +18,19 @@ import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, quat_xyzw, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
 UPDATES = 360
 # (position, orientation): refined final error <= ratio x unrefined final error
 RATIO = {"fp32": (0.72, 0.90), "bf16": (0.72, 0.90)}
 
 
-def _pose_error(sim):
-    """(position error in cm, orientation error in degrees) against the goal pose (the world frame's origin)."""
-    q = quat_xyzw(sim.R)
-    return float(np.linalg.norm(sim.t) * 100), float(np.rad2deg(2 * np.arccos(min(1.0, abs(q[3])))))
-
-
 def _run_loop(precision, subpatch):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, subpatch=subpatch)
-    eng = Engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(128, 11), 1.6 / 128, params, plane_z=0.61, device="cuda")
-    goal_rgb, _ = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, selection="order")
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = CameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
+    eng, _, ctl, sim = cl.set_up(dict(subpatch=subpatch), precision)
     torch.manual_seed(121)          # the visiting orders come from torch's global RNG: both runs see the same draws (vitvs_v2.py:1397)
-    track, statuses, moved, same = [_pose_error(sim)], [], 0, []
+    track, statuses, moved, same = [cl.sim_pose_error(sim)], [], 0, []
     for it in range(UPDATES):
         sim.sense()
         ctl.ibvs()
@@ -60,7 +40,7 @@ def _run_loop(precision, subpatch):
             moved += int(np.any(eng.last_offsets(1)))
         lin, ang = ctl.publish_twist()
         sim.apply_twist(lin, ang)
-        track.append(_pose_error(sim))
+        track.append(cl.sim_pose_error(sim))
     eng.close()
     return np.array(track), statuses, moved, np.array(same)
 

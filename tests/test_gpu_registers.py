@@ -12,9 +12,11 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
+from vitvs_amd.engine import Engine
 from oracle import servo_ref as sr
 
 import registers_ref as rr
+from robust_ref import rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -22,16 +24,6 @@ EXACT = ["fp32", "f16x2"]
 TOKEN_BARS = {"fp32": 2e-5, "f16x2": 2e-5, "bf16": 2e-2}
 FRAME_SEED = 20250738        # synth.ACCEPTED_FRAME_SEEDS["vits14_308"]: meets the acceptance rule with the registers too (asserted)
 REG = "dinov2_vits14_reg"
-
-
-def _engine(cfg, params=None, **kw):
-    from vitvs_amd.engine import Engine
-    return Engine(cfg, params, **kw)
-
-
-def _rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def _rel_max(got, ref):
@@ -56,7 +48,7 @@ def _default_case():
 @pytest.mark.parametrize("precision", ["fp32", "f16x2", "bf16"])
 def test_forward_tokens_of_the_register_model(precision):
     cfg, sd, des, cur, ref = _default_case()
-    eng = _engine(cfg, precision=precision, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, precision=precision, max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(np.stack([des, cur])).cpu()
     assert got.shape == ref.shape == (2, 489, 384)
     err = _rel_max(got, ref)
@@ -81,7 +73,7 @@ def test_forward_tokens_long_sequence(precision):
     if "l14" not in _MEMO:
         _MEMO["l14"] = rr.tokens(cfg, sd, frames)
     ref = _MEMO["l14"]
-    eng = _engine(cfg, config.ServoParams(dino_input_size=518, use_feature_binning=False), precision=precision,
+    eng = Engine(cfg, config.ServoParams(dino_input_size=518, use_feature_binning=False), precision=precision,
                   max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     assert got.shape == ref.shape == (2, 1374, 1024)
@@ -103,7 +95,7 @@ def test_zero_registers_through_create_ex_is_bit_identical(monkeypatch):
         lib = _lib.load()
         if via_ex:
             monkeypatch.setattr(lib, "vitvs_create", lambda c, out: lib.vitvs_create_ex(c, 0, out))
-        eng = _engine(cfg, params, precision="fp32", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
+        eng = Engine(cfg, params, precision="fp32", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
         assert lib.vitvs_register_tokens(eng.handle) == 0
         toks = eng.forward_tokens(np.stack([des, cur])).cpu()
         v, st = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_DENSE)
@@ -126,7 +118,7 @@ def test_descriptors_and_facets_skip_the_registers(precision):
     toks = rr.tokens(cfg, sd, frames)
     engines = {}
     for binned in (False, True):
-        eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=binned), precision=precision,
+        eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=binned), precision=precision,
                       max_pairs=1).load_state_dict(sd)
         engines[binned] = eng
         got = eng.extract_descriptors(frames).cpu()[:, 0]
@@ -171,7 +163,7 @@ def test_reference_default_with_registers_end_to_end(precision):
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=True)
     depth = synth.depth_pattern()
     ref, order = _accepted_reference(cfg, sd, des, cur, toks, params, depth, seed=7)
-    eng = _engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(sd)
+    eng = Engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(sd)
     v, st = eng.compute_velocity(cur, des, depth, params.intrinsics(), mode=_lib.SELECT_ORDER, selection=order[None])
     det = eng.last_details(1)
     assert int(st[0]) == 0
@@ -180,7 +172,7 @@ def test_reference_default_with_registers_end_to_end(precision):
     k = params.num_pairs
     assert np.array_equal(det["selected"][0, :k], ref["corr"]["selected"].numpy())
     v = v.cpu().numpy()[0].copy()
-    assert _rel_l2(v, ref["v_c"]) <= 1e-9
+    assert rel_l2(v, ref["v_c"]) <= 1e-9
     # the host-pointer entry point: the same bits
     v_h, st_h = eng.compute_velocity_host(cur, des, depth, np.array(params.intrinsics()), mode=_lib.SELECT_ORDER,
                                           selection=order[None])
@@ -191,7 +183,7 @@ def test_reference_default_with_registers_end_to_end(precision):
     det_g = eng.last_details(1)
     assert int(st_g[0]) == 0
     assert np.array_equal(det_g["nn_1"], det["nn_1"]) and np.array_equal(det_g["nn_2"], det["nn_2"])
-    assert _rel_l2(v_g.cpu().numpy()[0], v) <= 1e-9
+    assert rel_l2(v_g.cpu().numpy()[0], v) <= 1e-9
     eng.close()
 
 
@@ -201,7 +193,7 @@ def test_saliency_attends_over_the_registers():
     sd = weights.trained_like_state_dict(cfg, 5)
     frames = np.stack(synth.frame_pair(cfg.img_size, 99))
     want = rr.saliency_maps(cfg, sd, frames)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision="fp32",
+    eng = Engine(cfg, config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False), precision="fp32",
                   max_pairs=1).load_state_dict(sd)
     fr = torch.from_numpy(frames).to(eng.device)
     heads = (C.c_int32 * 4)(0, 2, 4, 5)
@@ -224,7 +216,7 @@ def test_pipeline_with_borrowed_weights_equals_a_lone_engine():
     Ic, Id = torch.from_numpy(cur[None]).to(dev), torch.from_numpy(des[None]).to(dev)
     Z = torch.from_numpy(synth.depth_pattern()[None]).to(dev)
     K = torch.tensor([params.intrinsics()], dtype=torch.float64, device=dev)
-    lone = _engine(cfg, params, precision="f16x2", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
+    lone = Engine(cfg, params, precision="f16x2", max_pairs=1, max_rows=cfg.tokens).load_state_dict(sd)
     lone.set_option("in_flight", 4)                                          # the tile plan the pipeline's slots run
     v_ref, st_ref = lone.compute_velocity(cur, des, synth.depth_pattern(), params.intrinsics(), mode=_lib.SELECT_DENSE)
     pipe = UpdatePipeline(cfg, params, sd, precision="f16x2", depth=4, max_rows=cfg.tokens, device=dev)
@@ -236,19 +228,19 @@ def test_pipeline_with_borrowed_weights_equals_a_lone_engine():
     pipe.close()
     # borrowing across different register counts is refused: the same geometry, another network
     plain = config.vit_config("dinov2_vits14", 308)
-    other = _engine(plain, params, precision="f16x2", max_pairs=1).load_state_dict(weights.synthetic_state_dict(plain, 0))
-    borrower = _engine(cfg, params, precision="f16x2", max_pairs=1)
+    other = Engine(plain, params, precision="f16x2", max_pairs=1).load_state_dict(weights.synthetic_state_dict(plain, 0))
+    borrower = Engine(cfg, params, precision="f16x2", max_pairs=1)
     with pytest.raises(VitvsError, match="register"):
         borrower.share_weights(other)
     with pytest.raises(VitvsError):
-        _engine(plain, params, precision="f16x2", max_pairs=1).share_weights(lone)
+        Engine(plain, params, precision="f16x2", max_pairs=1).share_weights(lone)
     for e in (lone, other, borrower):
         e.close()
 
 
 def test_register_tokens_upload_is_checked():
     cfg, sd, _, _, _ = _default_case()
-    eng = _engine(cfg, precision="fp32", max_pairs=1)
+    eng = Engine(cfg, precision="fp32", max_pairs=1)
     lib, h = eng.lib, eng.handle
     for name, t in sd.items():
         if name == "register_tokens":
@@ -267,19 +259,19 @@ def test_register_tokens_upload_is_checked():
     assert lib.vitvs_weights_ready(h) == 0
     eng.close()
     plain = config.vit_config("dinov2_vits14", 308)
-    eng0 = _engine(plain, precision="fp32", max_pairs=1)
+    eng0 = Engine(plain, precision="fp32", max_pairs=1)
     assert eng0.lib.vitvs_set_tensor(eng0.handle, b"register_tokens", reg.ctypes.data_as(C.c_void_p), reg.size) == -5
     eng0.close()
     # the engine refuses a register checkpoint under the plain name before anything reaches the device
     with pytest.raises(ValueError, match="_reg"):
-        _engine(plain, precision="fp32", max_pairs=1).load_state_dict(sd)
+        Engine(plain, precision="fp32", max_pairs=1).load_state_dict(sd)
 
 
 def test_register_counts_through_the_engine():
     cfg = dataclasses.replace(config.vit_config(REG, 56), dim=128, heads=2, depth=1, layer=0, native_grid=4, registers=16)
     sd = weights.synthetic_state_dict(cfg, 3)
     frames = np.random.default_rng(0).integers(0, 256, size=(2, 56, 56, 3), dtype=np.uint8)
-    eng = _engine(cfg, config.ServoParams(dino_input_size=56, use_feature_binning=False), precision="fp32",
+    eng = Engine(cfg, config.ServoParams(dino_input_size=56, use_feature_binning=False), precision="fp32",
                   max_pairs=1).load_state_dict(sd)
     got = eng.forward_tokens(frames).cpu()
     ref = rr.tokens(cfg, sd, frames)

@@ -12,16 +12,13 @@ from vitvs_amd import _lib, config, servo, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
 
 import rig_ref as rg
+import robust_ref as rr
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
 
 KEY = "vits16_224"
-N = 3
-
-
-def _extrinsics(seed=3, n=N):
-    rng = np.random.default_rng(seed)
-    return [rg.random_extrinsic(rng, 0.3, 0.2) for _ in range(n)]
+N = ls.N_CAMERAS
 
 
 @pytest.fixture(scope="module")
@@ -35,19 +32,8 @@ def setup():
     depth = np.stack([np.roll(synth.depth_pattern(), 7 * c, axis=1) for c in range(N)])
     eng = Engine(cfg, params, precision="fp32", max_pairs=N).load_state_dict(sd)
     yield dict(cfg=cfg, params=params, sd=sd, des=np.stack([des] * N), curs=[np.stack(c) for c in curs], depth=depth, eng=eng,
-               Ws=np.stack([servo.twist_matrix(R, t) for R, t in _extrinsics()]))
+               Ws=np.stack([servo.twist_matrix(R, t) for R, t in ls.extrinsics()]))
     eng.close()
-
-
-def _order(cfg, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.stack([torch.randperm(cfg.tokens, generator=g) for _ in range(n)]).to(torch.int32)
-
-
-def _velocity(s, eng=None, r=0, n=N, seed=11):
-    eng = eng or s["eng"]
-    return eng.compute_velocity(s["curs"][r][:n], s["des"][:n], s["depth"][:n], s["params"].intrinsics(), mode=_lib.SELECT_ORDER,
-                                selection=_order(s["cfg"], n, seed))
 
 
 def _reference(eng, n, Ws, status, lam):
@@ -58,40 +44,36 @@ def _reference(eng, n, Ws, status, lam):
     return rg.rig_law(Ls, es, Ws[:n], status, lam), det
 
 
-def _rel(a, b):
-    return float(np.linalg.norm(np.asarray(a) - b) / np.linalg.norm(b))
-
-
 def test_order_selection_equals_the_reference(setup):
     s, eng = setup, setup["eng"]
-    v, st = _velocity(s)
+    v, st = ls.rig_velocity(s)
     v_rig, rs, info = eng.rig_velocity(s["Ws"], st)
     st = st.cpu().numpy()
     assert (st == 0).all(), st                                     # (the set-up: three live cameras)
     ref, det = _reference(eng, N, s["Ws"], st, s["params"].lambda_)
     assert rs == 0 and info["cameras"] == 3 and info["rows"] == ref["rows"] == 3 * 2 * s["params"].num_pairs and info["sweeps"] == -1
     assert rg.ldlt_margin(ref["M"]) >= 100
-    err = _rel(v_rig.cpu().numpy(), ref["v_rig"])
+    err = rr.rel_l2(v_rig.cpu().numpy(), ref["v_rig"])
     print(f"3 cameras, ORDER: v_rig rel err {err:.2e}")
     assert err <= 1e-9
     normal = info["normal"].cpu().numpy()
     assert np.allclose(normal, rg.normal_packed(ref["M"], ref["e"]), rtol=1e-11, atol=1e-12 * np.abs(normal).max()) and normal[27] == ref["rows"]
     # ... which is not what averaging the cameras' own twists gives
     avg = np.mean([np.linalg.solve(W, vc) for W, vc in zip(s["Ws"], v.cpu().numpy())], axis=0)
-    print(f"  averaged camera twists differ from it by {_rel(avg, ref['v_rig']):.3f} (relative)")
+    print(f"  averaged camera twists differ from it by {rr.rel_l2(avg, ref['v_rig']):.3f} (relative)")
 
 
 def test_one_camera_at_the_rig_origin_is_its_own_twist(setup):
     s, eng = setup, setup["eng"]
-    v, st = _velocity(s, n=1)
+    v, st = ls.rig_velocity(s, n=1)
     v_rig, rs, info = eng.rig_velocity(np.eye(6)[None], st)
     assert rs == 0 and int(st[0]) == 0 and info["cameras"] == 1 and info["sweeps"] == -1
-    assert _rel(v_rig.cpu().numpy(), v.cpu().numpy()[0]) <= 1e-12
+    assert rr.rel_l2(v_rig.cpu().numpy(), v.cpu().numpy()[0]) <= 1e-12
 
 
 def test_explicit_selection_and_a_camera_with_too_few_features_is_excluded(setup):
     s, eng = setup, setup["eng"]
-    _velocity(s)
+    ls.rig_velocity(s)
     tab = eng.last_tables(N)
     ids = []
     for b in range(N):
@@ -107,7 +89,7 @@ def test_explicit_selection_and_a_camera_with_too_few_features_is_excluded(setup
         ref, _ = _reference(eng, N, s["Ws"], st, s["params"].lambda_)
         live = N - (dead is not None)
         assert rs == 0 and info["cameras"] == live and info["rows"] == ref["rows"] == live * 24 and info["worst_status"] == int(st.max())
-        assert _rel(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9
+        assert rr.rel_l2(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9
     # nobody contributes: zero twist, the largest camera status
     v, st = eng.compute_velocity(s["curs"][0], s["des"], s["depth"], s["params"].intrinsics(), mode=_lib.SELECT_EXPLICIT,
                                  selection=[np.zeros(0, np.int32)] * N, num_pairs=12)
@@ -124,13 +106,13 @@ def test_the_law_reads_whatever_matrix_the_camera_law_built(setup, option):
             eng.set_option("interaction", 2)
         else:
             eng.set_option("subpatch", 1)
-        _, st = _velocity(s)
+        _, st = ls.rig_velocity(s)
         v_rig, rs, info = eng.rig_velocity(s["Ws"], st)
         st = st.cpu().numpy()
         ref, det = _reference(eng, N, s["Ws"], st, s["params"].lambda_)
         assert (st == 0).all() and rs == 0 and info["rows"] == ref["rows"] > 0
         assert (det["Z_goal"].any() if option == "interaction" else det["offsets"].any())     # the option really was on
-        assert _rel(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9
+        assert rr.rel_l2(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9
     finally:
         eng.set_option(option, 0)
         eng.set_goal_depth(None)
@@ -143,7 +125,7 @@ def test_error_returns(setup):
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         fresh.rig_velocity(s["Ws"], np.zeros(N, np.int32))
     fresh.close()
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         eng.rig_velocity(s["Ws"][:2], st[:2])                                     # not the call's pair count
     w = torch.as_tensor(s["Ws"]).reshape(N, 36).to(eng.device)
@@ -157,14 +139,14 @@ def test_error_returns(setup):
         eng.set_option("robust_law", 2)
         with pytest.raises(VitvsError, match=r"\(-5\)"):
             eng.rig_velocity(s["Ws"], st)                                         # on, before any robust evaluation
-        _, st2 = _velocity(s)
+        _, st2 = ls.rig_velocity(s)
         with pytest.raises(VitvsError, match=r"\(-5\)"):
             eng.rig_velocity(s["Ws"], st2)
     finally:
         eng.set_option("robust_law", 0)
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         eng.rig_velocity(s["Ws"], st)                                             # the last evaluation was still a robust one
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     assert eng.rig_velocity(s["Ws"], st)[1] == 0
 
 
@@ -175,7 +157,7 @@ def test_under_graph_replay_with_new_frames(setup):
     des = torch.as_tensor(s["des"]).to(dev)
     z = torch.as_tensor(s["depth"]).to(dev)
     K = torch.tensor([s["params"].intrinsics()] * N, dtype=torch.float64, device=dev)
-    order = _order(s["cfg"], N, 12).to(dev)
+    order = ls.order(s["cfg"], N, 12).to(dev)
     v = torch.zeros((N, 6), dtype=torch.float64, device=dev)
     st = torch.zeros(N, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)
@@ -189,7 +171,7 @@ def test_under_graph_replay_with_new_frames(setup):
                 v_rig, rs, info = eng.rig_velocity(s["Ws"], st)
                 ref, _ = _reference(eng, N, s["Ws"], st.cpu().numpy(), s["params"].lambda_)
                 assert rs == 0 and info["rows"] == ref["rows"]
-                assert _rel(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9, r
+                assert rr.rel_l2(v_rig.cpu().numpy(), ref["v_rig"]) <= 1e-9, r
                 twists.append(v_rig.cpu().numpy())
         assert not np.array_equal(twists[0], twists[1]) and not np.array_equal(twists[1], twists[2])   # new frames, new twists
     finally:
@@ -199,17 +181,17 @@ def test_under_graph_replay_with_new_frames(setup):
 
 def test_host_pointer_form_equals_the_device_form(setup):
     s, eng = setup, setup["eng"]
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     v_rig, rs, info = eng.rig_velocity(s["Ws"], st)
     hv, hrs, hinfo, hnormal = eng.rig_velocity_host(s["Ws"], st.cpu().numpy())
     assert hrs == rs and list(hinfo[:3]) == [info["cameras"], info["rows"], info["sweeps"]]
     assert np.array_equal(hv, v_rig.cpu().numpy()) and np.array_equal(hnormal, info["normal"].cpu().numpy())
     # ... and behind a host-pointer velocity call
-    order = _order(s["cfg"], N, 11).numpy()
+    order = ls.order(s["cfg"], N, 11).numpy()
     v2, st2 = eng.compute_velocity_host(s["curs"][0], s["des"], s["depth"], s["params"].intrinsics(), _lib.SELECT_ORDER, order)
     hv2, hrs2, _, _ = eng.rig_velocity_host(s["Ws"], st2)
     ref, _ = _reference(eng, N, s["Ws"], st2, s["params"].lambda_)
-    assert hrs2 == 0 and _rel(hv2, ref["v_rig"]) <= 1e-9
+    assert hrs2 == 0 and rr.rel_l2(hv2, ref["v_rig"]) <= 1e-9
 
 
 def _snapshot(eng, v, st):
@@ -221,15 +203,15 @@ def test_nothing_else_moves(setup):
     """v_c, status and every last_details array of a velocity call are bit-identical with and without a rig call after it, and to
     those of a fresh handle that never saw the feature."""
     s, eng = setup, setup["eng"]
-    v, st = _velocity(s)
+    v, st = ls.rig_velocity(s)
     before = _snapshot(eng, v, st)
     eng.rig_velocity(s["Ws"], st)
     eng.rig_velocity_host(s["Ws"], st.cpu().numpy())
     after = _snapshot(eng, v, st)
-    v2, st2 = _velocity(s)                                                        # and the next velocity call after it
+    v2, st2 = ls.rig_velocity(s)                                                        # and the next velocity call after it
     again = _snapshot(eng, v2, st2)
     fresh = Engine(s["cfg"], s["params"], precision="fp32", max_pairs=N).load_state_dict(s["sd"])
-    v3, st3 = _velocity(s, eng=fresh)
+    v3, st3 = ls.rig_velocity(s, eng=fresh)
     never = _snapshot(fresh, v3, st3)
     fresh.close()
     for key in before:
@@ -241,7 +223,7 @@ def test_nothing_else_moves(setup):
 def test_multi_controller_with_a_rig(setup):
     s, eng = setup, setup["eng"]
     goals = [s["des"][i] for i in range(N)]
-    ext = _extrinsics()
+    ext = ls.extrinsics()
 
     def run(rig):
         mc = servo.MultiController(eng, goals, selection="order", rig=rig, generator=torch.Generator().manual_seed(4))
@@ -255,7 +237,7 @@ def test_multi_controller_with_a_rig(setup):
             smooth.append([np.array(c.v_c) for c in mc.cameras])
             if rig is not None:
                 ref, _ = _reference(eng, N, s["Ws"], [c.last_status for c in mc.cameras], s["params"].lambda_)
-                assert mc.rig_status == 0 and _rel(mc.rig_velocity_raw, ref["v_rig"]) <= 1e-9
+                assert mc.rig_status == 0 and rr.rel_l2(mc.rig_velocity_raw, ref["v_rig"]) <= 1e-9
                 rigs.append(mc.rig_velocity_raw.copy())
                 state = [None] * 6
                 for x in rigs:
@@ -278,6 +260,6 @@ def test_multi_controller_rig_needs_the_engine_backend(setup):
     pipe = UpdatePipeline(s["cfg"], s["params"], s["sd"], precision="fp32", depth=2)
     try:
         with pytest.raises(ValueError, match="Engine backend"):
-            servo.MultiController(pipe, [s["des"][i] for i in range(N)], rig=_extrinsics())
+            servo.MultiController(pipe, [s["des"][i] for i in range(N)], rig=ls.extrinsics())
     finally:
         pipe.close()

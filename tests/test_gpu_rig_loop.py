@@ -14,31 +14,12 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import config, servo, synth, weights
 from planar_sim import PlanarScene, rodrigues
+import closed_loop as cl
 
 KEY = "vits16_224"
 DT = 1.0
 UPDATES = 200
 PLANE_Z, TEX_PX, MPP = 0.61, 128, 1.6 / 128
-
-
-def _extrinsics():
-    """Two cameras 16 cm apart on the rig's x axis, each toed in by 3 degrees about y (towards the other's side)."""
-    toe = np.deg2rad(3.0)
-    return [(rodrigues(np.array([0.0, toe, 0.0])), np.array([-0.08, 0.0, 0.0])),
-            (rodrigues(np.array([0.0, -toe, 0.0])), np.array([0.08, 0.0, 0.0]))]
-
-
-def _start_pose():
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    return rodrigues(axis * np.deg2rad(5.0)), direction * 0.05
-
-
-def _camera_pose(Rr, tr, ext):
-    Re, te = ext
-    return Rr @ Re, Rr @ te + tr
 
 
 def _footprint(params, R, t):
@@ -54,14 +35,10 @@ def _footprint(params, R, t):
 
 def test_both_views_stay_on_the_texture_at_the_start_and_goal_poses():
     params = config.ServoParams(dino_input_size=224, use_feature_binning=False)
-    for Rr, tr in ((np.eye(3), np.zeros(3)), _start_pose()):
-        for ext in _extrinsics():
-            fp = _footprint(params, *_camera_pose(Rr, tr, ext))
+    for Rr, tr in ((np.eye(3), np.zeros(3)), cl.start_pose()):
+        for ext in cl.toed_in_pair():
+            fp = _footprint(params, *cl.camera_pose(Rr, tr, ext))
             assert (fp >= 0).all() and (fp <= TEX_PX - 1).all(), fp
-
-
-def _pose_error(Rr, tr):
-    return 100.0 * float(np.linalg.norm(tr)), float(np.rad2deg(np.arccos(np.clip((np.trace(Rr) - 1.0) / 2.0, -1.0, 1.0))))
 
 
 def _run(mode="rig", seed=121):
@@ -71,16 +48,16 @@ def _run(mode="rig", seed=121):
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False)
     eng = Engine(cfg, params, precision="fp32", max_pairs=2).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     scene = PlanarScene(synth.texture(TEX_PX, 11), MPP, params, plane_z=PLANE_Z, device="cuda")
-    ext = _extrinsics()
-    goals = [scene.render(*_camera_pose(np.eye(3), np.zeros(3), e))[0] for e in ext]
+    ext = cl.toed_in_pair()
+    goals = [scene.render(*cl.camera_pose(np.eye(3), np.zeros(3), e))[0] for e in ext]
     mc = servo.MultiController(eng, goals, selection="order", rig=ext, generator=torch.Generator().manual_seed(seed))
     W0 = servo.twist_matrix(*ext[0])
-    Rr, tr = _start_pose()
-    start_pose = _pose_error(Rr, tr)
+    Rr, tr = cl.start_pose()
+    start_pose = cl.rig_pose_error(Rr, tr)
     feat_err, statuses = [], []
     for _ in range(UPDATES):
         for i, e in enumerate(ext):
-            rgb, depth = scene.render(*_camera_pose(Rr, tr, e))
+            rgb, depth = scene.render(*cl.camera_pose(Rr, tr, e))
             mc.image_callback_rgb(i, rgb)
             mc.image_callback_depth(i, depth)
         mc.ibvs()
@@ -92,7 +69,7 @@ def _run(mode="rig", seed=121):
             tr = tr + Rr @ v[:3] * DT
             Rr = Rr @ rodrigues(v[3:] * DT)
     eng.close()
-    return np.array(feat_err), statuses, start_pose, _pose_error(Rr, tr)
+    return np.array(feat_err), statuses, start_pose, cl.rig_pose_error(Rr, tr)
 
 
 @pytest.mark.gpu

@@ -84,12 +84,8 @@ def _cases():
 CASES = _cases()
 
 
-def _statuses(case):
-    return [0 if L.shape[0] > 0 else 2 for L in case["Ls"]]
-
-
 def _reference(case):
-    return rg.rig_law(case["Ls"], case["es"], case["Ws"], _statuses(case), LAM)
+    return rg.rig_law(case["Ls"], case["es"], case["Ws"], rg.statuses(case), LAM)
 
 
 def _pack(case):

@@ -1,7 +1,8 @@
 """The robust rig law through a handle (vitvs_rig_robust_velocity[_dev], Engine.rig_velocity(robust_iterations=N),
 MultiController(rig=..., rig_robust_iterations)) against the fp64 numpy statement of tests/rig_robust_ref.py evaluated on the
 handle's OWN last_details L, e, rows and matched pairs: this tests the rig stage, not the forward.  The set-up of
-tests/test_gpu_rig.py (copied, not imported): ViT-S/16 224², synthetic weights, max_pairs = 3, fp32.  Bar: v_rig <= 1e-9."""
+tests/test_gpu_rig.py (its shared helpers are in tests/law_support.py): ViT-S/16 224², synthetic weights, max_pairs = 3, fp32.
+Bar: v_rig <= 1e-9."""
 import ctypes as C
 import dataclasses
 
@@ -13,20 +14,15 @@ import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, servo, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
 
-import rig_ref as rg
 import rig_robust_ref as rr
 import robust_ref
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
 
 KEY = "vits16_224"
-N = 3
+N = ls.N_CAMERAS
 ITER = 4
-
-
-def _extrinsics(seed=3, n=N):
-    rng = np.random.default_rng(seed)
-    return [rg.random_extrinsic(rng, 0.3, 0.2) for _ in range(n)]
 
 
 @pytest.fixture(scope="module")
@@ -40,19 +36,8 @@ def setup():
     eng = Engine(cfg, params, precision="fp32", max_pairs=N).load_state_dict(sd)
     K = np.array([params.intrinsics()] * N)
     yield dict(cfg=cfg, params=params, sd=sd, des=np.stack([des] * N), curs=[np.stack(c) for c in curs], depth=depth, eng=eng, K=K,
-               Ws=np.stack([servo.twist_matrix(R, t) for R, t in _extrinsics()]))
+               Ws=np.stack([servo.twist_matrix(R, t) for R, t in ls.extrinsics()]))
     eng.close()
-
-
-def _order(cfg, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.stack([torch.randperm(cfg.tokens, generator=g) for _ in range(n)]).to(torch.int32)
-
-
-def _velocity(s, eng=None, r=0, n=N, seed=11):
-    eng = eng or s["eng"]
-    return eng.compute_velocity(s["curs"][r][:n], s["des"][:n], s["depth"][:n], s["params"].intrinsics(), mode=_lib.SELECT_ORDER,
-                                selection=_order(s["cfg"], n, seed))
 
 
 def _smin(s, K, contributing):
@@ -72,16 +57,12 @@ def _reference(s, eng, n, status, K, n_iter=ITER):
                 cameras=sum(1 for r, _ in con if r), smin=smin)
 
 
-def _rel(a, b):
-    return float(np.linalg.norm(np.asarray(a) - b) / np.linalg.norm(b))
-
-
 def _check(got, ref, n_iter=ITER):
     v_rig, rs, info = got
     assert ref["margin"] >= 1e-6                                                   # (no weight on the rejection edge)
     assert rs == 0 and (info["cameras"], info["rows"], info["reweighted"], info["zero_weights"]) == \
         (ref["cameras"], ref["rows"], n_iter, ref["n_zero"]), (info, ref)
-    assert _rel(v_rig.cpu().numpy(), ref["v"]) <= 1e-9
+    assert robust_ref.rel_l2(v_rig.cpu().numpy(), ref["v"]) <= 1e-9
     assert np.abs(info["weights"].cpu().numpy() - ref["w"]).max() <= 1e-9
     assert abs(info["sigma"] - ref["sigma"]) <= 1e-12 * ref["sigma"]
 
@@ -101,7 +82,7 @@ def test_order_selection_equals_the_reference_and_nothing_else_moves(setup, robu
     s, eng = setup, setup["eng"]
     try:
         eng.set_option("robust_law", robust_law)
-        v, st = _velocity(s)
+        v, st = ls.rig_velocity(s)
         before = _snapshot(eng, v, st)
         got = eng.rig_velocity(s["Ws"], st, robust_iterations=ITER, K=s["K"])
         stn = st.cpu().numpy()
@@ -110,7 +91,7 @@ def test_order_selection_equals_the_reference_and_nothing_else_moves(setup, robu
         _check(got, ref)
         assert got[2]["cameras"] == 3 and got[2]["rows"] == 3 * 2 * s["params"].num_pairs
         print(f"3 cameras, ORDER, robust_law {robust_law}: sigma {got[2]['sigma']:.4g} (floor {ref['smin']:.4g}), "
-              f"{got[2]['zero_weights']} zero weights, v_rig rel err {_rel(got[0].cpu().numpy(), ref['v']):.2e}")
+              f"{got[2]['zero_weights']} zero weights, v_rig rel err {robust_ref.rel_l2(got[0].cpu().numpy(), ref['v']):.2e}")
         _same(before, _snapshot(eng, v, st))                                      # v_c, statuses, details and the cameras' own weights
         if robust_law:
             with pytest.raises(VitvsError, match=r"\(-5\)"):
@@ -118,12 +99,12 @@ def test_order_selection_equals_the_reference_and_nothing_else_moves(setup, robu
             assert int(eng.last_features(N)["info"][0, 6]) == robust_law          # (the cameras' laws really were robust)
     finally:
         eng.set_option("robust_law", 0)
-        _velocity(s)
+        ls.rig_velocity(s)
 
 
 def test_one_iteration_and_sixteen_and_cameras_with_their_own_intrinsics(setup):
     s, eng = setup, setup["eng"]
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     stn = st.cpu().numpy()
     for n_iter in (1, 16):
         _check(eng.rig_velocity(s["Ws"], st, robust_iterations=n_iter, K=s["K"]), _reference(s, eng, N, stn, s["K"], n_iter), n_iter)
@@ -138,7 +119,7 @@ def test_one_iteration_and_sixteen_and_cameras_with_their_own_intrinsics(setup):
 
 def test_explicit_selection_and_a_camera_with_too_few_features_is_excluded(setup):
     s, eng = setup, setup["eng"]
-    _velocity(s)
+    ls.rig_velocity(s)
     tab = eng.last_tables(N)
     ids = []
     for b in range(N):
@@ -173,7 +154,7 @@ def test_the_law_reads_whatever_matrix_the_camera_law_built(setup, option):
             eng.set_option("interaction", 2)
         else:
             eng.set_option("subpatch", 1)
-        _, st = _velocity(s)
+        _, st = ls.rig_velocity(s)
         got = eng.rig_velocity(s["Ws"], st, robust_iterations=ITER, K=s["K"])
         st = st.cpu().numpy()
         det = eng.last_details(N)
@@ -186,18 +167,18 @@ def test_the_law_reads_whatever_matrix_the_camera_law_built(setup, option):
 
 def test_host_pointer_form_equals_the_device_form(setup):
     s, eng = setup, setup["eng"]
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     v_rig, rs, info = eng.rig_velocity(s["Ws"], st, robust_iterations=ITER, K=s["K"])
     hv, hrs, hinfo, hnormal, hw, hsigma = eng.rig_velocity_host(s["Ws"], st.cpu().numpy(), robust_iterations=ITER, K=s["K"])
     assert hrs == rs and list(hinfo[:3]) == [info["cameras"], info["rows"], info["sweeps"]]
     assert list(hinfo[5:7]) == [info["reweighted"], info["zero_weights"]] and hsigma == info["sigma"]
     assert np.array_equal(hv, v_rig.cpu().numpy()) and np.array_equal(hnormal, info["normal"].cpu().numpy())
     assert np.array_equal(hw, info["weights"].cpu().numpy())
-    order = _order(s["cfg"], N, 11).numpy()
+    order = ls.order(s["cfg"], N, 11).numpy()
     v2, st2 = eng.compute_velocity_host(s["curs"][0], s["des"], s["depth"], s["params"].intrinsics(), _lib.SELECT_ORDER, order)
     hv2, hrs2, _, _, hw2, _ = eng.rig_velocity_host(s["Ws"], st2, robust_iterations=ITER, K=s["K"])
     ref = _reference(s, eng, N, st2, s["K"])
-    assert hrs2 == 0 and _rel(hv2, ref["v"]) <= 1e-9 and np.abs(hw2 - ref["w"]).max() <= 1e-9
+    assert hrs2 == 0 and robust_ref.rel_l2(hv2, ref["v"]) <= 1e-9 and np.abs(hw2 - ref["w"]).max() <= 1e-9
 
 
 def test_under_graph_replay_with_new_frames(setup):
@@ -207,7 +188,7 @@ def test_under_graph_replay_with_new_frames(setup):
     des = torch.as_tensor(s["des"]).to(dev)
     z = torch.as_tensor(s["depth"]).to(dev)
     K = torch.tensor(s["K"], dtype=torch.float64, device=dev)
-    order = _order(s["cfg"], N, 12).to(dev)
+    order = ls.order(s["cfg"], N, 12).to(dev)
     v = torch.zeros((N, 6), dtype=torch.float64, device=dev)
     st = torch.zeros(N, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)
@@ -234,7 +215,7 @@ def test_error_returns(setup):
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         fresh.rig_velocity(s["Ws"], np.zeros(N, np.int32), robust_iterations=ITER, K=s["K"])
     fresh.close()
-    _, st = _velocity(s)
+    _, st = ls.rig_velocity(s)
     with pytest.raises(VitvsError, match=r"\(-5\)"):
         eng.rig_velocity(s["Ws"][:2], st[:2], robust_iterations=ITER, K=s["K"][:2])   # not the call's pair count
     w = torch.as_tensor(s["Ws"]).reshape(N, 36).to(eng.device)
@@ -249,13 +230,13 @@ def test_error_returns(setup):
     assert f() == 0                                                               # every optional output may be NULL
     torch.cuda.synchronize()
     ref = _reference(s, eng, N, st.cpu().numpy(), s["K"])
-    assert int(rs[0]) == 0 and _rel(out.cpu().numpy(), ref["v"]) <= 1e-9
+    assert int(rs[0]) == 0 and robust_ref.rel_l2(out.cpu().numpy(), ref["v"]) <= 1e-9
 
 
 def test_multi_controller_with_a_robust_rig(setup):
     s, eng = setup, setup["eng"]
     goals = [s["des"][i] for i in range(N)]
-    ext = _extrinsics()
+    ext = ls.extrinsics()
 
     def run(n_iter):
         params = dataclasses.replace(s["params"], rig_robust_iterations=n_iter) if n_iter is not None else None
@@ -271,7 +252,7 @@ def test_multi_controller_with_a_robust_rig(setup):
             rigs.append((mc.rig_velocity_raw.copy(), mc.v_rig.copy()))
             if n_iter:
                 ref = _reference(s, eng, N, [c.last_status for c in mc.cameras], s["K"], n_iter)
-                assert mc.rig_status == 0 and _rel(mc.rig_velocity_raw, ref["v"]) <= 1e-9
+                assert mc.rig_status == 0 and robust_ref.rel_l2(mc.rig_velocity_raw, ref["v"]) <= 1e-9
                 assert mc.rig_weights.shape == (N, eng.max_rows) and np.abs(mc.rig_weights - ref["w"]).max() <= 1e-9
                 assert mc.rig_info["reweighted"] == n_iter
         return raws, smooth, rigs, mc

@@ -1,6 +1,6 @@
-"""Closed loop on the GPU with the robust rig law: the two-camera rig of tests/test_gpu_rig_loop.py (set-up
-copied, not imported) over the FINE texture of tests/test_gpu_robust_loop.py (synth.texture at 512 px over 1.6 m), whose
-nearest-neighbour matches under untrained weights contain gross outliers.  ViT-S/16 224², synthetic weights, fp32,
+"""Closed loop on the GPU with the robust rig law: the two-camera rig of tests/test_gpu_rig_loop.py (poses
+and extrinsics: tests/closed_loop.py) over the FINE texture of tests/test_gpu_robust_loop.py (synth.texture at 512 px over 1.6 m),
+whose nearest-neighbour matches under untrained weights contain gross outliers.  ViT-S/16 224², synthetic weights, fp32,
 ``selection="order"`` with a seeded generator (both laws see the same draws), the 5 cm / 5 degree start, 120 updates.
 ``MultiController(rig=...)`` drives the rig once with the plain rig law and once with ``rig_robust_iterations=4``.
 
@@ -15,35 +15,12 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import config, servo, synth, weights
 from planar_sim import PlanarScene, rodrigues
+import closed_loop as cl
 
 KEY = "vits16_224"
 DT = 1.0
 UPDATES = 120
 PLANE_Z, TEX_PX, MPP = 0.61, 512, 1.6 / 512
-
-
-def _extrinsics():
-    """Two cameras 16 cm apart on the rig's x axis, each toed in by 3 degrees about y (towards the other's side)."""
-    toe = np.deg2rad(3.0)
-    return [(rodrigues(np.array([0.0, toe, 0.0])), np.array([-0.08, 0.0, 0.0])),
-            (rodrigues(np.array([0.0, -toe, 0.0])), np.array([0.08, 0.0, 0.0]))]
-
-
-def _start_pose():
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    return rodrigues(axis * np.deg2rad(5.0)), direction * 0.05
-
-
-def _camera_pose(Rr, tr, ext):
-    Re, te = ext
-    return Rr @ Re, Rr @ te + tr
-
-
-def _pose_error(Rr, tr):
-    return 100.0 * float(np.linalg.norm(tr)), float(np.rad2deg(np.arccos(np.clip((np.trace(Rr) - 1.0) / 2.0, -1.0, 1.0))))
 
 
 def _run(robust_iterations, seed=121):
@@ -52,14 +29,14 @@ def _run(robust_iterations, seed=121):
     params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, rig_robust_iterations=robust_iterations)
     eng = Engine(cfg, params, precision="fp32", max_pairs=2).load_state_dict(weights.synthetic_state_dict(cfg, 0))
     scene = PlanarScene(synth.texture(TEX_PX, 11), MPP, params, plane_z=PLANE_Z, device="cuda")
-    ext = _extrinsics()
-    goals = [scene.render(*_camera_pose(np.eye(3), np.zeros(3), e))[0] for e in ext]
+    ext = cl.toed_in_pair()
+    goals = [scene.render(*cl.camera_pose(np.eye(3), np.zeros(3), e))[0] for e in ext]
     mc = servo.MultiController(eng, goals, params=params, selection="order", rig=ext, generator=torch.Generator().manual_seed(seed))
-    Rr, tr = _start_pose()
-    track, zero_weights, reweighted = [_pose_error(Rr, tr)], [], []
+    Rr, tr = cl.start_pose()
+    track, zero_weights, reweighted = [cl.rig_pose_error(Rr, tr)], [], []
     for _ in range(UPDATES):
         for i, e in enumerate(ext):
-            rgb, depth = scene.render(*_camera_pose(Rr, tr, e))
+            rgb, depth = scene.render(*cl.camera_pose(Rr, tr, e))
             mc.image_callback_rgb(i, rgb)
             mc.image_callback_depth(i, depth)
         mc.ibvs()
@@ -69,7 +46,7 @@ def _run(robust_iterations, seed=121):
         if mc.v_rig is not None:
             tr = tr + Rr @ mc.v_rig[:3] * DT
             Rr = Rr @ rodrigues(mc.v_rig[3:] * DT)
-        track.append(_pose_error(Rr, tr))
+        track.append(cl.rig_pose_error(Rr, tr))
     eng.close()
     return np.array(track), np.array(reweighted), np.array(zero_weights)
 

@@ -118,15 +118,11 @@ SOLVER.update({"1x4": "jacobi", "rank_deficient": "jacobi", "nobody": "none", "n
                "rank_lost_after_rejection": "ldlt_then_jacobi"})
 
 
-def _statuses(case):
-    return [0 if L.shape[0] > 0 else 2 for L in case["Ls"]]
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name, n_iter):
     """Computed once per (case, N) and shared; never modified."""
     case = CASES[name]
-    st = _statuses(case)
+    st = rg.statuses(case)
     trace = []
     v, w, rho, sigma, n_zero, margin, M, e = rr.robust_rig_law(case["Ls"], case["es"], case["Ws"], st, case["lives"], LAM, n_iter,
                                                                case["smin"], trace=trace)
@@ -153,7 +149,7 @@ def _back_to_back_cases(n=9, ld=60):
 
 
 def _ref_of(case, n_iter):
-    st = _statuses(case)
+    st = rg.statuses(case)
     trace = []
     v, w, _, sigma, n_zero, margin, M, e = rr.robust_rig_law(case["Ls"], case["es"], case["Ws"], st, case["lives"], LAM, n_iter,
                                                              case["smin"], trace=trace)
@@ -428,5 +424,5 @@ def test_the_plain_op_is_untouched_by_a_robust_call_on_the_same_block():
     torch.cuda.synchronize()
     for x, y in zip(before, after):
         assert torch.equal(x.view(torch.int32), y.view(torch.int32))
-    ref = rg.rig_law(case["Ls"], case["es"], case["Ws"], _statuses(case), LAM)
+    ref = rg.rig_law(case["Ls"], case["es"], case["Ws"], rg.statuses(case), LAM)
     assert np.linalg.norm(after[0].cpu().numpy() - ref["v_rig"]) <= 1e-9 * np.linalg.norm(ref["v_rig"])

@@ -1,15 +1,13 @@
 """The outlier-robust control law (option ``robust_law``: Tukey IRLS inside servo_kernel) on the GPU against its fp64 numpy
 statement (tests/robust_ref.py).
 
-Tiny handles through ``vitvs_servo_from_nn_dev`` in EXPLICIT mode, in the style of tests/test_gpu_servo_cover.py (whose helpers
-are copied here): planted-outlier scenarios on both sides of the LDS / global-workspace edge (R = 2 * pairs <= 128 keeps L and the
-weights in LDS), both solvers of the weighted system, the planted-outlier property on the device, zero padding, the same-image
+Tiny handles through ``vitvs_servo_from_nn_dev`` in EXPLICIT mode, in the style of tests/test_gpu_servo_cover.py (shared
+helpers: tests/law_support.py): planted-outlier scenarios on both sides of the LDS / global-workspace edge (R = 2 * pairs <= 128
+keeps L and the weights in LDS), both solvers of the weighted system, the planted-outlier property on the device, zero padding, the same-image
 shortcut, the statuses that skip the law, a DENSE selection at T = 1024, "off means off", and every entry point of a ViT-S/16
 handle.  The bars are the plain law's: s_uv and Z exact, L / e within 1e-13, v_c within 1e-9 (relative L2); final weights
 within 1e-9 absolute.  Every equality case is checked (on the reference, before the device is asked) to keep every pair's
 t = rho / (c sigma) at least 1e-6 away from the rejection point 1, where the count of zero weights is not continuous."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
@@ -17,69 +15,18 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
-from oracle import servo_ref as sr
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
 
 LDLT = -1
 MAX_SWEEPS = 40
 VC_BAR, L_BAR, W_BAR = 1e-9, 1e-13, 1e-9
 MARGIN = 1e-6
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _tables(rng, t, n_boost):
-    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
-    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
-    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
-    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
-    nn1, nn2 = nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64)
-    mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
-    assert 0 < len(mutual) < t
-    return nn1, nn2, sim1.numpy(), mutual
-
-
-def _depth(rng):
-    depth = synth.depth_pattern().copy()
-    depth.reshape(-1)[rng.integers(0, depth.size, size=depth.size // 7)] = 0     # holes: the 100 m sentinel
-    return depth
-
-
-def _intrinsics(rng, params):
-    return (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-            params.v_max / 2 + float(rng.uniform(-20, 20)))
-
-
-def _oracle(g, img, params, nn1, ids, rows, depth, K):
-    ids = np.asarray(ids, np.int64)
-    p1 = torch.from_numpy(np.stack([ids // g, ids % g], 1))
-    p2 = torch.from_numpy(np.stack([nn1[ids] // g, nn1[ids] % g], 1))
-    s_star, s_ = sr.calculate_uv(sr.patch_centres(p1, img, g), sr.patch_centres(p2, img, g), rows, params.u_max, params.v_max, img)
-    return np.asarray(s_star), np.asarray(s_), sr.velocity(s_star, s_, depth, K[0], K[1], K[2], K[3], params.lambda_)
-
-
-def _ldlt_passes(L):
-    """servo.hip's pivot test on the normal equations of L (rows x 6), restated in fp64."""
-    G = L.T @ L
-    Lf, dpiv = np.zeros((6, 6)), np.zeros(6)
-    good = True
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for j in range(6):
-            d = G[j, j] - sum(Lf[j, k] ** 2 * dpiv[k] for k in range(j))
-            good = good and d > 1e-8 * G[j, j] and G[j, j] > 0
-            dpiv[j] = d
-            for i in range(j + 1, 6):
-                Lf[i, j] = (G[i, j] - sum(Lf[i, k] * Lf[j, k] * dpiv[k] for k in range(j))) / d
-    return bool(good)
-
-
-def _s_min(params, img, K):
-    return rr.sigma_min(16, params.u_max, params.v_max, img, K[0], K[1])
 
 
 def _check_robust(det, b, v, st, ref, rob, s_star, s_, rows, n_iter, solver, what):
@@ -102,32 +49,11 @@ def _check_robust(det, b, v, st, ref, rob, s_star, s_, rows, n_iter, solver, wha
     assert err <= VC_BAR, (what, err)
     assert int(info[6]) == n_iter and int(info[7]) == rob["n_zero"], (what, info, rob["n_zero"])
     sw = np.sqrt(np.repeat(rob["w"], 2))[:, None]
-    assert (_ldlt_passes(sw * ref["L"]) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
+    assert (ls.ldlt_passes(sw * ref["L"]) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
     if solver == "ldlt":
         assert int(info[4]) == LDLT, (what, "expected LDL^T", info)
     else:
         assert 0 <= int(info[4]) <= MAX_SWEEPS, (what, "expected Jacobi", info)
-
-
-_ENGINES = {}
-
-
-def _servo_engine(g, max_rows):
-    """A tiny handle (no weights: the law alone) for a g x g grid."""
-    key = (g, max_rows)
-    if key not in _ENGINES:
-        img = 16 * g
-        params = config.ServoParams(dino_input_size=img)
-        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    return _ENGINES[key]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
 
 
 def _run(eng, sc, n_iter, num_pairs=None, ids=None):
@@ -144,11 +70,11 @@ def _run(eng, sc, n_iter, num_pairs=None, ids=None):
 @pytest.mark.parametrize("num_pairs", [8, 24, 48, 64, 65, 130])
 def test_planted_scenarios_equal_the_reference(num_pairs, n_iter):
     """8 .. 64 pairs: L and the weights in LDS; 65 and 130: in the global workspace.  Depth holes, random intrinsics."""
-    eng, params = _servo_engine(14, 130)
+    eng, params = ENGINES.fetch(14, 130)
     rng = np.random.default_rng(9000 + 20 * num_pairs + n_iter)
-    sc = rr.planted_scenario(rng, num_pairs, 0.25 if num_pairs >= 48 else 0.125, params, K=_intrinsics(rng, params), holes=True)
+    sc = rr.planted_scenario(rng, num_pairs, 0.25 if num_pairs >= 48 else 0.125, params, K=ls.intrinsics(rng, params), holes=True)
     s_star, s_, ref = rr.oracle_law(sc, params)
-    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, n_iter, _s_min(params, sc["img"], sc["K"]))
+    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, n_iter, ls.s_min(params, sc["img"], sc["K"]))
     v, st, det = _run(eng, sc, n_iter)
     _check_robust(det, 0, v, st, ref, rob, s_star, s_, num_pairs, n_iter, "ldlt", ("planted", num_pairs, n_iter))
 
@@ -162,9 +88,9 @@ def test_both_solvers_under_weights(num_pairs, solver):
     g, max_rows = 17, 80
     t = g * g
     rng = np.random.default_rng(200 * num_pairs + (solver == "jacobi"))
-    eng, params = _servo_engine(g, max_rows)
-    nn1, nn2, sim1, mutual = _tables(rng, t, 200)
-    depth, K = _depth(rng), _intrinsics(rng, params)
+    eng, params = ENGINES.fetch(g, max_rows)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, 200)
+    depth, K = ls.depth(rng), ls.intrinsics(rng, params)
     if solver == "ldlt":
         ids = rng.choice(mutual, size=num_pairs, replace=False)
     else:
@@ -182,8 +108,8 @@ def test_both_solvers_under_weights(num_pairs, solver):
     eng.set_option("robust_law", 4)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=num_pairs)
     det = eng.last_details(1)
-    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, num_pairs, depth, K)
-    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, 4, _s_min(params, 16 * g, K))
+    s_star, s_, ref = ls.oracle(g, 16 * g, params, nn1, ids, num_pairs, depth, K)
+    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, 4, ls.s_min(params, 16 * g, K))
     assert solver == "ldlt" or np.ptp(rob["w"]) > 0.05                     # the Jacobi SVD does run on unequal weights
     _check_robust(det, 0, v.cpu().numpy(), st, ref, rob, s_star, s_, num_pairs, 4, solver, (num_pairs, solver))
 
@@ -193,7 +119,7 @@ def test_both_solvers_under_weights(num_pairs, solver):
 def test_planted_outlier_property_on_the_device(n_pairs, share, seed0):
     """The scenarios of tests/test_robust_host.py: the device's robust twist (N = 4) is closer than half the device's plain
     twist's distance to the plain law on the un-corrupted matches, in every scenario."""
-    eng, params = _servo_engine(14, 130)
+    eng, params = ENGINES.fetch(14, 130)
     errs = []
     for sc, clean in rr.property_scenarios(n_pairs, share, seed0, params):
         v_plain, st0, _ = _run(eng, sc, 0)
@@ -208,12 +134,12 @@ def test_planted_outlier_property_on_the_device(n_pairs, share, seed0):
 
 # ----------------------------------------------------------------------------- zero padding, same image, skipped laws
 def test_zero_padded_pairs_have_weight_zero():
-    eng, params = _servo_engine(14, 130)
+    eng, params = ENGINES.fetch(14, 130)
     rng = np.random.default_rng(77)
-    sc = rr.planted_scenario(rng, 24, 0.125, params, K=_intrinsics(rng, params), holes=True)
+    sc = rr.planted_scenario(rng, 24, 0.125, params, K=ls.intrinsics(rng, params), holes=True)
     n_live = 10
     s_star, s_, ref = rr.oracle_law(sc, params, n_live=n_live, rows=24)
-    s_min = _s_min(params, sc["img"], sc["K"])
+    s_min = ls.s_min(params, sc["img"], sc["K"])
     rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, 4, s_min, n_live=n_live)
     v, st, det = _run(eng, sc, 4, num_pairs=24, ids=sc["ids"][:n_live])
     assert int(det["info"][0, 3]) == n_live and int(det["info"][0, 1]) == 24
@@ -226,10 +152,10 @@ def test_zero_padded_pairs_have_weight_zero():
 def test_same_image_and_skipped_laws():
     g, k = 14, 24
     t = g * g
-    eng, params = _servo_engine(g, 130)
+    eng, params = ENGINES.fetch(g, 130)
     rng = np.random.default_rng(78)
-    nn1, nn2, sim1, mutual = _tables(rng, t, t // 3)
-    depth, K = _depth(rng), params.intrinsics()
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, t // 3)
+    depth, K = ls.depth(rng), params.intrinsics()
     eng.set_option("robust_law", 4)
     order = rng.permutation(t).astype(np.int32)
     v, st = eng.servo_from_nn(nn1, nn2, np.ones(t, np.float32), depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
@@ -260,18 +186,18 @@ def test_dense_selection_at_1024_tokens():
     residuals and the median over a few hundred values."""
     g = 32
     t = g * g
-    eng, params = _servo_engine(g, t)
+    eng, params = ENGINES.fetch(g, t)
     rng = np.random.default_rng(4242)
-    nn1, nn2, sim1, mutual = _tables(rng, t, 300)
-    depth, K = _depth(rng), _intrinsics(rng, params)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, 300)
+    depth, K = ls.depth(rng), ls.intrinsics(rng, params)
     eng.set_option("robust_law", 4)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_DENSE, num_pairs=24)
     det = eng.last_details(1)
     rows = int(det["info"][0, 3])
     ids = det["selected"][0, :rows]
     assert rows == len(mutual) > 128 and ids.tolist() == mutual.tolist()
-    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, rows, depth, K)
-    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, 4, _s_min(params, 16 * g, K))
+    s_star, s_, ref = ls.oracle(g, 16 * g, params, nn1, ids, rows, depth, K)
+    rob = rr.robust_velocity(ref["L"], ref["e"], params.lambda_, 4, ls.s_min(params, 16 * g, K))
     _check_robust(det, 0, v.cpu().numpy(), st, ref, rob, s_star, s_, rows, 4, "ldlt", ("dense", rows))
 
 
@@ -279,7 +205,7 @@ def test_dense_selection_at_1024_tokens():
 def test_off_means_off():
     img = 224
     params = config.ServoParams(dino_input_size=img)
-    eng = Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)      # the option never set
+    eng = Engine(ls.tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=48)      # the option never set
     rng = np.random.default_rng(5)
     sc = rr.planted_scenario(rng, 24, 0.125, params, holes=True)
     runs = []
@@ -319,7 +245,7 @@ def test_every_entry_point_evaluates_the_robust_law():
     det = eng.last_details(1)
     v_dev = v_dev.cpu().numpy()[0]
     assert int(st_dev[0]) == _lib.STATUS_OK and int(det["info"][0, 6]) == 4
-    rob = rr.robust_velocity(det["L"][0, :6, :2 * k].T, det["L"][0, 6, :2 * k], params.lambda_, 4, _s_min(params, cfg.img_size, K))
+    rob = rr.robust_velocity(det["L"][0, :6, :2 * k].T, det["L"][0, 6, :2 * k], params.lambda_, 4, ls.s_min(params, cfg.img_size, K))
     assert rob["margin"] >= MARGIN
     assert rr.rel_l2(v_dev, rob["v_c"]) <= VC_BAR and np.max(np.abs(det["weights"][0, :k] - rob["w"])) <= W_BAR
     v_host, st_host = eng.compute_velocity_host(cur, des, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids])

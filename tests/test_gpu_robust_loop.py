@@ -1,6 +1,6 @@
 """Closed loop on the GPU with the outlier-robust control law, on the scene the plain law cannot servo.
 
-The set-up of tests/test_gpu_loop.py (copied, not imported): ``servo.Controller(Engine)`` on ViT-S/16 224² with synthetic weights
+The set-up of tests/test_gpu_loop.py (tests/closed_loop.py): ``servo.Controller(Engine)`` on ViT-S/16 224² with synthetic weights
 driving a simulated camera (tests/planar_sim.py) from a 5 cm / 5 degree offset, ``selection="order"``, dt = 0.5 s — but over the FINE
 texture (synth.texture at 512 px over 1.6 m) that test avoids: with untrained weights the nearest-neighbour matches of fine
 texture contain gross outliers, and the least-squares law has no defence against them (the CPU oracle's plain law diverges to
@@ -19,37 +19,17 @@ import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, quat_xyzw, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
 UPDATES = 120
 
 
-def _pose_error(sim):
-    """(position error in cm, orientation error in degrees) against the goal pose (the world frame's origin)."""
-    q = quat_xyzw(sim.R)
-    return float(np.linalg.norm(sim.t) * 100), float(np.rad2deg(2 * np.arccos(min(1.0, abs(q[3])))))
-
-
 def _run_loop(precision, robust_iterations):
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, robust_iterations=robust_iterations)
-    eng = Engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(512, 11), 1.6 / 512, params, plane_z=0.61, device="cuda")
-    goal_rgb, _ = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, selection="order")
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = CameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
+    eng, params, ctl, sim = cl.set_up(dict(robust_iterations=robust_iterations), precision, tex_px=512)
     torch.manual_seed(121)          # the visiting orders come from torch's global RNG: both laws see the same draws (vitvs_v2.py:1397)
-    track, rejected, info6 = [_pose_error(sim)], [], []
+    track, rejected, info6 = [cl.sim_pose_error(sim)], [], []
     for _ in range(UPDATES):
         sim.sense()
         ctl.ibvs()
@@ -59,7 +39,7 @@ def _run_loop(precision, robust_iterations):
             info6.append(int(eng.last_features(1)["info"][0, 6]))
         lin, ang = ctl.publish_twist()
         sim.apply_twist(lin, ang)
-        track.append(_pose_error(sim))
+        track.append(cl.sim_pose_error(sim))
     eng.close()
     return np.array(track), np.array(rejected), np.array(info6), params
 

@@ -2,8 +2,6 @@
 vitvs_last_details bit for bit equal to the same call in ORDER mode given tests/select_ref.py's order of the tables the call
 reports, and vitvs_last_order is that order.  The law behind the selection is the one ORDER runs (tests/test_gpu_servo_cover.py
 holds it to the oracle), so nothing here has a tolerance."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
@@ -12,29 +10,13 @@ import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
 from vitvs_amd.pipeline import UpdatePipeline
-from oracle import servo_ref as sr
 import select_ref as sref
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _tables(rng, t, n_boost):
-    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
-    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
-    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
-    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
-    return nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64), sim1.numpy()
-
-
-def _depth(rng):
-    depth = synth.depth_pattern().copy()
-    depth.reshape(-1)[rng.integers(0, depth.size, size=depth.size // 7)] = 0
-    return depth
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
 
 
 def _reference_orders(det, n, cells):
@@ -65,39 +47,19 @@ def _identity(eng, n, run, cells=4, what=""):
     return det_b, vb, sb
 
 
-_ENGINES = {}
-
-
-def _servo_engine(g, max_rows):
-    key = (g, max_rows)
-    if key not in _ENGINES:
-        img = 16 * g
-        params = config.ServoParams(dino_input_size=img)
-        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    return _ENGINES[key]
-
-
 @pytest.fixture(scope="module")
 def model():
     """The 2-block tiny model at 224 (T = 196), three pairs of capacity, with its frames."""
-    cfg = _tiny_cfg(224)
+    cfg = ls.tiny_cfg(224)
     params = config.ServoParams(dino_input_size=224, use_feature_binning=False)
     sd = weights.synthetic_state_dict(cfg, 3)
     eng = Engine(cfg, params, precision="fp32", max_pairs=3, max_rows=196).load_state_dict(sd)
     pairs = [synth.frame_pair(cfg.img_size, s) for s in (20250705, 20250715, 20250738)]
     rng = np.random.default_rng(5)
-    depth = np.stack([_depth(rng), np.roll(synth.depth_pattern(), 37, axis=1), (synth.depth_pattern() // 2 + 300).astype(np.uint16)])
+    depth = np.stack([ls.depth(rng), np.roll(synth.depth_pattern(), 37, axis=1), (synth.depth_pattern() // 2 + 300).astype(np.uint16)])
     yield dict(eng=eng, cfg=cfg, params=params, sd=sd, des=np.stack([p[0] for p in pairs]), cur=np.stack([p[1] for p in pairs]),
                depth=depth, K=params.intrinsics())
     eng.close()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
 
 
 def _np(v, st):
@@ -110,9 +72,9 @@ def _np(v, st):
 def test_servo_from_nn(g, rows):
     t = g * g
     rng = np.random.default_rng(100 * g + rows)
-    eng, params = _servo_engine(g, 160)
-    nn1, nn2, sim1 = _tables(rng, t, int(rng.integers(t // 4, t // 2)))
-    depth, K = _depth(rng), params.intrinsics()
+    eng, params = ENGINES.fetch(g, 160)
+    nn1, nn2, sim1, _ = ls.tables(rng, t, int(rng.integers(t // 4, t // 2)))
+    depth, K = ls.depth(rng), params.intrinsics()
 
     def run(mode, order):
         return _np(*eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=mode, selection=order, num_pairs=rows))
@@ -129,9 +91,9 @@ def test_servo_from_nn_with_other_cells_and_back():
     g, rows = 17, 24
     t = g * g
     rng = np.random.default_rng(4)
-    eng, params = _servo_engine(g, 160)
-    nn1, nn2, sim1 = _tables(rng, t, 140)
-    depth, K = _depth(rng), params.intrinsics()
+    eng, params = ENGINES.fetch(g, 160)
+    nn1, nn2, sim1, _ = ls.tables(rng, t, 140)
+    depth, K = ls.depth(rng), params.intrinsics()
 
     def run(mode, order):
         return _np(*eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=mode, selection=order, num_pairs=rows))

@@ -1,6 +1,6 @@
 """Closed loop on the GPU with selection mode BEST: ``servo.Controller(selection="best")``.
 
-The set-up of tests/test_gpu_refine_loop.py (copied, not imported): ViT-S/16 224² with synthetic weights driving a simulated camera
+The set-up of tests/test_gpu_refine_loop.py (tests/closed_loop.py): ViT-S/16 224² with synthetic weights driving a simulated camera
 (tests/planar_sim.py) over the smooth texture (synth.texture at 128 px over 1.6 m, 0.61 m away) from a 5 cm / 5 degree offset,
 dt = 0.5 s, 360 updates, fp32 and bf16.  No torch seed is set: the mode draws nothing.  Asserted, what holds by construction:
 
@@ -16,13 +16,10 @@ import pytest
 import torch
 
 import vitvs_amd  # noqa: F401
-from vitvs_amd import config, servo, synth, weights
-from planar_sim import CameraSim, PlanarScene, quat_xyzw, rodrigues
+import closed_loop as cl
 
 pytestmark = pytest.mark.gpu
 
-KEY = "vits16_224"
-DT = 0.5
 UPDATES = 360
 
 MEASURED = """final pose error, cm / degrees (profiles/best_selection.txt; "order": torch seeds 121 .. 125, or 121 .. 123)
@@ -35,37 +32,20 @@ come back update after update, so the loop stops at the first pose where their p
 the track does not move), and level with them under the robust law: the measurement supports no ratio below 1, none is asserted."""
 
 
-def _pose_error(sim):
-    """(position error in cm, orientation error in degrees) against the goal pose (the world frame's origin)."""
-    q = quat_xyzw(sim.R)
-    return float(np.linalg.norm(sim.t) * 100), float(np.rad2deg(2 * np.arccos(min(1.0, abs(q[3])))))
-
-
 def run_loop(precision, selection, seed=None, texture=128, robust_iterations=0, updates=UPDATES, select_cells=4):
     """The pose track [updates + 1, 2] (cm, degrees) and the statuses of one closed loop."""
-    from vitvs_amd.engine import Engine
-    cfg = config.baseline_config(KEY)
-    params = config.ServoParams(dino_input_size=cfg.img_size, use_feature_binning=False, robust_iterations=robust_iterations,
-                                select_cells=select_cells)
-    eng = Engine(cfg, params, precision=precision, max_pairs=1).load_state_dict(weights.synthetic_state_dict(cfg, 0))
-    scene = PlanarScene(synth.texture(texture, 11), 1.6 / texture, params, plane_z=0.61, device="cuda")
-    goal_rgb, _ = scene.render(np.eye(3), np.zeros(3))
-    ctl = servo.Controller(eng, goal_image=goal_rgb, selection=selection)
-    axis = np.array([0.3, -0.4, 0.85])
-    axis /= np.linalg.norm(axis)
-    direction = np.array([0.6, -0.5, 0.6])
-    direction /= np.linalg.norm(direction)
-    sim = CameraSim(scene, ctl, rodrigues(axis * np.deg2rad(5.0)), direction * 0.05, DT)
+    eng, _, ctl, sim = cl.set_up(dict(robust_iterations=robust_iterations, select_cells=select_cells), precision, tex_px=texture,
+                                 selection=selection)
     if seed is not None:
         torch.manual_seed(seed)     # "order": the visiting orders come from torch's global RNG
-    track, statuses = [_pose_error(sim)], []
+    track, statuses = [cl.sim_pose_error(sim)], []
     for _ in range(updates):
         sim.sense()
         ctl.ibvs()
         statuses.append(ctl.last_status)
         lin, ang = ctl.publish_twist()
         sim.apply_twist(lin, ang)
-        track.append(_pose_error(sim))
+        track.append(cl.sim_pose_error(sim))
     eng.close()
     return np.array(track), statuses
 

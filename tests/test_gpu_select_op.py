@@ -13,21 +13,10 @@ import torch
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
-from oracle import servo_ref as sr
 import select_ref as sref
+import law_support as ls
 
 pytestmark = pytest.mark.gpu
-
-
-def _tables(rng, t, n_boost):
-    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
-    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
-    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
-    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
-    nn1, nn2 = nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64)
-    mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
-    assert 0 < len(mutual) < t
-    return nn1, nn2, sim1.numpy()
 
 
 def _device_order(tables, cells):
@@ -58,12 +47,12 @@ def _check(tables, cells, what):
 @pytest.mark.parametrize("T", [16, 196, 256, 289, 484, 1024, 3136])
 def test_order_on_random_tables(T, cells):
     rng = np.random.default_rng(10 * T + cells)
-    _check([_tables(rng, T, int(rng.integers(T // 4, T // 2)))], cells, (T, cells))
+    _check([ls.tables(rng, T, int(rng.integers(T // 4, T // 2)))[:3]], cells, (T, cells))
 
 
 def test_three_pairs_in_one_launch():
     rng = np.random.default_rng(77)
-    tables = [_tables(rng, 289, n) for n in (40, 150, 250)]
+    tables = [ls.tables(rng, 289, n)[:3] for n in (40, 150, 250)]
     _check(tables, 4, "three pairs")
     got = _device_order(tables, 4)
     assert not np.array_equal(got[0], got[1]) and not np.array_equal(got[1], got[2])
@@ -74,7 +63,7 @@ def test_degenerate_tables(T):
     rng = np.random.default_rng(T)
     ident = np.arange(T)
     sim = rng.uniform(0.2, 0.9, T).astype(np.float32)
-    nn1, nn2, sim_r = _tables(rng, T, T // 3)
+    nn1, nn2, sim_r, _ = ls.tables(rng, T, T // 3)
     flat = np.full(T, 0.5, np.float32)
     ties = sim_r.copy()
     ties[rng.choice(T, size=50, replace=False)] = np.float32(0.625)      # 50 exact ties, mutual and not, across cells

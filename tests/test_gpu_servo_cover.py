@@ -9,8 +9,6 @@ law against oracle/servo_ref (numpy pinv): s_uv exact, Z exact, L within 1e-13, 
 in through vitvs_servo_from_nn_dev (tiny handles, T up to 1024) or come from velocity calls of the 2-block tiny model.
 Also here: the three law options (robust_law, subpatch, interaction) together through the forward and every entry point, and the
 reselect state of the host-pointer entry point, which ends with every call that rewrites the arg-max keys."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
@@ -18,73 +16,17 @@ import torch
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config, synth, weights
 from vitvs_amd.engine import Engine, VitvsError
-from oracle import servo_ref as sr
 import robust_ref as rr
+import law_support as ls
+from law_support import TinyEngines, close_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+ENGINES = TinyEngines()           # this module's tiny handles: close_engines closes them at its teardown
 
 LDLT = -1
 MAX_SWEEPS = 40
 VC_BAR, L_BAR = 1e-9, 1e-13
-
-
-def _tiny_cfg(img):
-    base = config.vit_config("dino_vits16", img)
-    return dataclasses.replace(base, dim=128, depth=2, heads=2, layer=1, native_grid=base.grid)
-
-
-def _rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def _tables(rng, t, n_boost):
-    """Arg-max tables of a random similarity matrix with `n_boost` planted mutual nearest neighbours."""
-    S = rng.uniform(0.2, 0.8, size=(t, t)).astype(np.float32)
-    S[rng.permutation(t)[:n_boost], rng.permutation(t)[:n_boost]] = rng.uniform(0.85, 0.95, size=n_boost).astype(np.float32)
-    sim1, nn1, _, nn2 = sr.nearest_neighbours(torch.from_numpy(S))
-    nn1, nn2 = nn1.numpy().astype(np.int64), nn2.numpy().astype(np.int64)
-    mutual = np.nonzero(nn2[nn1] == np.arange(t))[0]
-    assert 0 < len(mutual) < t
-    return nn1, nn2, sim1.numpy(), mutual
-
-
-def _depth(rng):
-    depth = synth.depth_pattern().copy()
-    depth.reshape(-1)[rng.integers(0, depth.size, size=depth.size // 7)] = 0     # holes: the 100 m sentinel
-    return depth
-
-
-def _intrinsics(rng, params):
-    return (float(rng.uniform(300, 700)), float(rng.uniform(300, 700)), params.u_max / 2 + float(rng.uniform(-20, 20)),
-            params.v_max / 2 + float(rng.uniform(-20, 20)))
-
-
-def _oracle(g, img, params, nn1, ids, rows, depth, K):
-    ids = np.asarray(ids, np.int64)
-    p1 = torch.from_numpy(np.stack([ids // g, ids % g], 1))
-    p2 = torch.from_numpy(np.stack([nn1[ids] // g, nn1[ids] % g], 1))
-    s_star, s_ = sr.calculate_uv(sr.patch_centres(p1, img, g), sr.patch_centres(p2, img, g), rows, params.u_max, params.v_max, img)
-    return np.asarray(s_star), np.asarray(s_), sr.velocity(s_star, s_, depth, K[0], K[1], K[2], K[3], params.lambda_)
-
-
-def _ldlt_passes(L):
-    """servo.hip's pivot test on the normal equations of L (rows x 6), restated in fp64."""
-    G = L.T @ L
-    Lf, dpiv = np.zeros((6, 6)), np.zeros(6)
-    good = True
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return _ldlt_pivots(G, Lf, dpiv, good)
-
-
-def _ldlt_pivots(G, Lf, dpiv, good):
-    for j in range(6):
-        d = G[j, j] - sum(Lf[j, k] ** 2 * dpiv[k] for k in range(j))
-        good = good and d > 1e-8 * G[j, j] and G[j, j] > 0
-        dpiv[j] = d
-        for i in range(j + 1, 6):
-            Lf[i, j] = (G[i, j] - sum(Lf[i, k] * Lf[j, k] * dpiv[k] for k in range(j))) / d
-    return bool(good)
 
 
 def _check_law(det, b, v, st, ref, s_star, s_, rows, solver, what):
@@ -92,7 +34,7 @@ def _check_law(det, b, v, st, ref, s_star, s_, rows, solver, what):
     assert int(st) == _lib.STATUS_OK, (what, int(st))
     info = det["info"][b]
     assert int(info[5]) == 2 * rows, (what, info)
-    assert (_ldlt_passes(ref["L"]) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
+    assert (ls.ldlt_passes(ref["L"]) == (solver == "ldlt")), (what, "the case does not reach the solver it names")
     if solver == "ldlt":
         assert int(info[4]) == LDLT, (what, "expected LDL^T", info)
     else:
@@ -102,30 +44,9 @@ def _check_law(det, b, v, st, ref, s_star, s_, rows, solver, what):
     assert np.array_equal(det["feat"][b, :rows, 0:1], ref["Z"]), what
     np.testing.assert_allclose(det["L"][b, :6, :2 * rows].T, ref["L"], rtol=0, atol=L_BAR, err_msg=what)
     np.testing.assert_allclose(det["L"][b, 6, :2 * rows], ref["e"][:, 0], rtol=0, atol=L_BAR, err_msg=what)
-    err = _rel_l2(v, ref["v_c"])
+    err = rr.rel_l2(v, ref["v_c"])
     assert err <= VC_BAR, (what, err)
     return int(info[4])
-
-
-_ENGINES = {}
-
-
-def _servo_engine(g, max_rows):
-    """A tiny handle (no weights: the law alone) for a g x g grid."""
-    key = (g, max_rows)
-    if key not in _ENGINES:
-        img = 16 * g
-        params = config.ServoParams(dino_input_size=img)
-        _ENGINES[key] = (Engine(_tiny_cfg(img), params, precision="fp32", max_pairs=1, max_rows=max_rows), params)
-    return _ENGINES[key]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_engines():
-    yield
-    for eng, _ in _ENGINES.values():
-        eng.close()
-    _ENGINES.clear()
 
 
 # ----------------------------------------------------------------------------- random tables, every selection mode
@@ -136,10 +57,10 @@ def test_law_on_random_tables(g, mode):
     484 and 1024 (4 positions per thread).  ORDER and EXPLICIT keep 24 pairs (L in LDS), DENSE all mutual tokens (L global)."""
     t, k = g * g, 24
     rng = np.random.default_rng(7000 + 10 * g + ["order", "explicit", "dense"].index(mode))
-    eng, params = _servo_engine(g, t)
+    eng, params = ENGINES.fetch(g, t)
     img = 16 * g
-    nn1, nn2, sim1, mutual = _tables(rng, t, int(rng.integers(t // 4, t // 2)))
-    depth, K = _depth(rng), _intrinsics(rng, params)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, int(rng.integers(t // 4, t // 2)))
+    depth, K = ls.depth(rng), ls.intrinsics(rng, params)
     if mode == "order":
         order = rng.permutation(t).astype(np.int32)
         mset = set(mutual.tolist())
@@ -154,7 +75,7 @@ def test_law_on_random_tables(g, mode):
     det = eng.last_details(1)
     assert int(det["info"][0, 0]) == len(mutual) and int(det["info"][0, 3]) == rows
     assert det["selected"][0, :rows].tolist() == [int(x) for x in ids]
-    s_star, s_, ref = _oracle(g, img, params, nn1, ids, rows, depth, K)
+    s_star, s_, ref = ls.oracle(g, img, params, nn1, ids, rows, depth, K)
     _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, rows, "ldlt", (g, mode))
     if mode == "dense":
         assert 2 * rows > 128                                 # L in the global workspace
@@ -171,9 +92,9 @@ def test_both_solvers_across_the_lds_edge(num_pairs, solver):
     g, max_rows = 17, 80
     t = g * g
     rng = np.random.default_rng(100 * num_pairs + (solver == "jacobi"))
-    eng, params = _servo_engine(g, max_rows)
-    nn1, nn2, sim1, mutual = _tables(rng, t, 200)
-    depth, K = _depth(rng), _intrinsics(rng, params)
+    eng, params = ENGINES.fetch(g, max_rows)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, 200)
+    depth, K = ls.depth(rng), ls.intrinsics(rng, params)
     if solver == "ldlt":
         ids = rng.choice(mutual, size=num_pairs, replace=False)
     else:
@@ -186,7 +107,7 @@ def test_both_solvers_across_the_lds_edge(num_pairs, solver):
     ids = ids.astype(np.int32)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=num_pairs)
     det = eng.last_details(1)
-    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, num_pairs, depth, K)
+    s_star, s_, ref = ls.oracle(g, 16 * g, params, nn1, ids, num_pairs, depth, K)
     _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, num_pairs, solver, (num_pairs, solver))
 
 
@@ -196,14 +117,14 @@ def test_rank_four_selections_within_the_sweep_cap(seed):
     g, k = 14, 24
     t = g * g
     rng = np.random.default_rng(500 + seed)
-    eng, params = _servo_engine(g, 48)
-    nn1, nn2, sim1, _ = _tables(rng, t, 80)
-    depth, K = _depth(rng), _intrinsics(rng, params)
+    eng, params = ENGINES.fetch(g, 48)
+    nn1, nn2, sim1, _ = ls.tables(rng, t, 80)
+    depth, K = ls.depth(rng), ls.intrinsics(rng, params)
     moved = np.nonzero(nn1 != np.arange(t))[0]
     ids = np.resize(rng.choice(moved, size=2, replace=False), k).astype(np.int32)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[ids], num_pairs=k)
     det = eng.last_details(1)
-    s_star, s_, ref = _oracle(g, 16 * g, params, nn1, ids, k, depth, K)
+    s_star, s_, ref = ls.oracle(g, 16 * g, params, nn1, ids, k, depth, K)
     assert np.linalg.matrix_rank(ref["L"]) == 4
     sweeps = _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, k, "jacobi", seed)
     print(f"rank-4 selection {seed}: {sweeps} sweeps")
@@ -214,9 +135,9 @@ def test_rank_four_selections_within_the_sweep_cap(seed):
 def test_statuses_at_many_tokens(g):
     t, k = g * g, 24
     rng = np.random.default_rng(300 + g)
-    eng, params = _servo_engine(g, t)
-    nn1, nn2, sim1, mutual = _tables(rng, t, t // 3)
-    depth, K = _depth(rng), params.intrinsics()
+    eng, params = ENGINES.fetch(g, t)
+    nn1, nn2, sim1, mutual = ls.tables(rng, t, t // 3)
+    depth, K = ls.depth(rng), params.intrinsics()
     few = rng.choice(mutual, size=3, replace=False).astype(np.int32)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=_lib.SELECT_EXPLICIT, selection=[few], num_pairs=k)
     det = eng.last_details(1)
@@ -235,14 +156,14 @@ def test_statuses_at_many_tokens(g):
     v, st = eng.servo_from_nn(nn1, nn2, np.ones(t, np.float32), depth, K, mode=_lib.SELECT_ORDER, selection=order, num_pairs=k)
     det = eng.last_details(1)
     assert int(det["info"][0, 2]) == 1 and det["selected"][0, :k].tolist() == order[:k].tolist()
-    s_star, s_, ref = _oracle(g, 16 * g, params, ident, order[:k], k, depth, K)
+    s_star, s_, ref = ls.oracle(g, 16 * g, params, ident, order[:k], k, depth, K)
     assert np.all(v.cpu().numpy() == 0) and np.array_equal(s_star, s_)
-    _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, k, "ldlt" if _ldlt_passes(ref["L"]) else "jacobi", ("same", g))
+    _check_law(det, 0, v.cpu().numpy(), st, ref, s_star, s_, k, "ldlt" if ls.ldlt_passes(ref["L"]) else "jacobi", ("same", g))
 
 
 # ----------------------------------------------------------------------------- several pairs in one velocity call
 def _tiny_model(max_pairs, max_rows):
-    cfg = _tiny_cfg(224)
+    cfg = ls.tiny_cfg(224)
     params = config.ServoParams(dino_input_size=224, use_feature_binning=False)
     eng = Engine(cfg, params, precision="fp32", max_pairs=max_pairs, max_rows=max_rows)
     return eng.load_state_dict(weights.synthetic_state_dict(cfg, 3)), cfg, params
@@ -257,8 +178,8 @@ def test_three_pairs_each_with_its_own_intrinsics_depth_and_selection():
     pairs = [synth.frame_pair(cfg.img_size, s) for s in (20250705, 20250715, 20250738)]
     des = np.stack([p[0] for p in pairs])
     cur = np.stack([p[1] for p in pairs])
-    depth = np.stack([_depth(rng), np.roll(synth.depth_pattern(), 37, axis=1), (synth.depth_pattern() // 2 + 300).astype(np.uint16)])
-    K = np.array([_intrinsics(rng, params) for _ in range(3)])
+    depth = np.stack([ls.depth(rng), np.roll(synth.depth_pattern(), 37, axis=1), (synth.depth_pattern() // 2 + 300).astype(np.uint16)])
+    K = np.array([ls.intrinsics(rng, params) for _ in range(3)])
     eng.compute_velocity(cur, des, depth, K, mode=_lib.SELECT_DENSE, num_pairs=k)    # the tables, to draw from
     tabs = eng.last_details(3)
     ids = []
@@ -273,7 +194,7 @@ def test_three_pairs_each_with_its_own_intrinsics_depth_and_selection():
     v, st = v.cpu().numpy(), st.cpu().numpy()
     for b in range(3):
         assert np.array_equal(det["nn_1"][b], tabs["nn_1"][b]) and int(det["info"][b, 2]) == 0
-        s_star, s_, ref = _oracle(g, cfg.img_size, params, det["nn_1"][b].astype(np.int64), ids[b], k, depth[b], K[b])
+        s_star, s_, ref = ls.oracle(g, cfg.img_size, params, det["nn_1"][b].astype(np.int64), ids[b], k, depth[b], K[b])
         _check_law(det, b, v[b], st[b], ref, s_star, s_, k, "jacobi" if b == 1 else "ldlt", ("pair", b))
     eng.close()
 

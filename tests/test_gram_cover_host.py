@@ -12,6 +12,7 @@ import pytest
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib
+from op_support import host_lib as lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,13 +22,6 @@ def _module(name, path):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")

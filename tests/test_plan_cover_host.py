@@ -2,31 +2,17 @@
 (tools/plan_cover.py; tests/test_gpu_plan_cover.py runs every row against fp64).  The plans are host arithmetic in the library
 (vitvs_op_linear_plan, vitvs_op_attention_plan): no device calls here."""
 import ctypes
-import importlib.util
 import os
 
 import pytest
 
 import vitvs_amd  # noqa: F401
 from vitvs_amd import _lib, config
+from op_support import host_lib as lib  # noqa: F401
+from op_support import plan_cover as cover  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REGEN = "run `python tools/plan_cover.py --write`"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.isfile(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def cover():
-    spec = importlib.util.spec_from_file_location("plan_cover", os.path.join(ROOT, "tools", "plan_cover.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.fixture(scope="module")

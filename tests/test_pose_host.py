@@ -17,13 +17,8 @@ LDS_CAP = 160 * 1024
 ANGLES = (0.1, 1.0, 3.0, 3.1415)
 
 
-def _unit(v):
-    v = np.asarray(v, np.float64)
-    return v / np.linalg.norm(v)
-
-
 def _seeded_pose(rng, angle):
-    return pr.rodrigues(_unit(rng.standard_normal(3)) * angle), rng.uniform(-0.1, 0.1, 3)
+    return pr.rodrigues(pr.unit(rng.standard_normal(3)) * angle), rng.uniform(-0.1, 0.1, 3)
 
 
 def test_exact_recovery_on_coplanar_points():
@@ -41,14 +36,14 @@ def test_exact_recovery_on_coplanar_points():
             assert not h["degenerate"] and abs(np.linalg.det(h["R"]) - 1.0) < 1e-12
             out = pr.pose_law(P, Q, np.ones(8), 0.7, 0)
             assert out["status"] == pr.OK and out["info"][0] == 8
-            th = angle * _unit(pr.theta_u(h["q"]))
+            th = angle * pr.unit(pr.theta_u(h["q"]))
             assert np.allclose(out["v"], -0.7 * np.concatenate([R.T @ t, th]), atol=1e-12)
     print(f"exact recovery: worst |R|, |t| miss {worst:.2e}; smallest relative eigen-gap {gap:.3f}")
     assert worst <= 1e-12 and gap > 1e-6
 
 
 def test_collinear_points_have_no_gap():
-    line = np.outer(np.linspace(-0.3, 0.3, 8), _unit([1.0, 2.0, 0.5])) + np.array([0.0, 0.0, 0.61])
+    line = np.outer(np.linspace(-0.3, 0.3, 8), pr.unit([1.0, 2.0, 0.5])) + np.array([0.0, 0.0, 0.61])
     R, t = _seeded_pose(np.random.default_rng(5), 1.0)
     h = pr.horn(pr.points_in_camera(line, R, t), line, np.ones(8))
     assert h["gap"] / h["scatter"] < 1e-12 and h["degenerate"]
@@ -60,7 +55,7 @@ T0 = np.array([0.04, -0.03, 0.03])                         # 5.8 cm from the goa
 
 def _start(turn_deg):
     Rz = pr.rodrigues(np.array([0.0, 0.0, np.deg2rad(turn_deg)]))
-    return Rz @ pr.rodrigues(_unit([1.0, 0.5, 0.0]) * np.deg2rad(3.0)), T0.copy()
+    return Rz @ pr.rodrigues(pr.unit([1.0, 0.5, 0.0]) * np.deg2rad(3.0)), T0.copy()
 
 
 def _closed_loop(law, turn_deg, steps=400, lam=1.0, dt=0.05):
@@ -123,12 +118,12 @@ PITCH_U, PITCH_V = 14 * _PARAMS.u_max / 308, 14 * _PARAMS.v_max / 308
 
 def _outlier_case(seed):
     rng = np.random.default_rng(7000 + seed)
-    R, t = pr.rodrigues(_unit(rng.standard_normal(3)) * rng.uniform(0.05, 0.6)), rng.uniform(-0.08, 0.08, 3)
+    R, t = pr.rodrigues(pr.unit(rng.standard_normal(3)) * rng.uniform(0.05, 0.6)), rng.uniform(-0.08, 0.08, 3)
     Z = rng.uniform(0.5, 0.8, 24)
     Q = np.stack([rng.uniform(-0.4, 0.4, 24) * Z, rng.uniform(-0.3, 0.3, 24) * Z, Z], 1)
     P = pr.points_in_camera(Q, R, t) + rng.standard_normal((24, 3)) * 0.002
     bad = rng.choice(24, 6, replace=False)
-    P[bad] += np.stack([_unit(d) for d in rng.standard_normal((6, 3))]) * rng.uniform(0.1, 0.4, (6, 1))
+    P[bad] += np.stack([pr.unit(d) for d in rng.standard_normal((6, 3))]) * rng.uniform(0.1, 0.4, (6, 1))
     smin = 0.5 * max(PITCH_U / _PARAMS.f_x, PITCH_V / _PARAMS.f_y) * pr.median_middle(Q[:, 2])
     return P, Q, bad, R, t, smin
 
@@ -193,7 +188,7 @@ def test_status_too_few_rows():
 
 
 def test_status_collinear_clouds_are_degenerate():
-    line = np.outer(np.linspace(-0.3, 0.3, 9), _unit([1.0, -1.0, 0.2])) + np.array([0.0, 0.0, 0.6])
+    line = np.outer(np.linspace(-0.3, 0.3, 9), pr.unit([1.0, -1.0, 0.2])) + np.array([0.0, 0.0, 0.6])
     R, t = _seeded_pose(np.random.default_rng(3), 0.5)
     out = pr.pose_law(pr.points_in_camera(line, R, t), line, np.ones(9), 1.0, 0)
     assert out["status"] == pr.TOO_FEW and out["info"][4] == 1 and np.array_equal(out["v"], np.zeros(6))
