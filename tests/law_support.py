@@ -149,9 +149,12 @@ def same_values(a, b):
 
 
 def goal_table(zg, g, img, params):
-    """The handle's goal-depth table restated: zg at every token's patch centre, entry T at pixel (0, 0)."""
+    """The handle's goal-depth table restated: zg at every token's patch centre (0 where that lies outside the image: the law
+    reads it as 100 m, like a hole), entry T at pixel (0, 0)."""
     uv = rr.token_pixels(np.arange(g * g), g, img, params.u_max, params.v_max)
-    return np.concatenate([zg[uv[:, 1], uv[:, 0]], zg[0:1, 0]]).astype(np.uint16)
+    inside = (uv[:, 0] < params.u_max) & (uv[:, 1] < params.v_max)
+    at = np.where(inside[:, None], uv, 0)
+    return np.concatenate([np.where(inside, zg[at[:, 1], at[:, 0]], 0), zg[0:1, 0]]).astype(np.uint16)
 
 
 def servo_law(eng, sc, num_pairs=None, ids=None, select=_lib.SELECT_EXPLICIT, offsets=None, depth=True):

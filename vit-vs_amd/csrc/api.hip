@@ -184,8 +184,9 @@ struct vitvs_handle {
     struct HostTables { int n_pairs = 0, T = 0; bool have_depth = false; int des_shared = 0; } host_tables;   // what vitvs_reselect may build on
     unsigned char* det_block = nullptr; // device copy of the detail block (detail_pointers), one allocation
     size_t det_bytes = 0;
-    std::vector<int32_t> depth_sites;   // linear pixel index of every token's patch centre that lies inside the depth image (the only
-                                        // pixels the law reads: servo.hip token_pixel, restated on the host at creation)
+    std::vector<int32_t> depth_sites;   // linear pixel index of every token's patch centre that lies inside the depth image, and of pixel
+                                        // (0, 0), which a zero-padded row reads (the only pixels the law reads: servo.hip token_pixel,
+                                        // restated on the host at creation)
     bool reuse_goal = false;            // option "reuse_goal_frames": I_des of a host-pointer call is not staged again while its address repeats
     const void* staged_des = nullptr;   // host address, frame count and geometry of the goal frames in st_des
     size_t staged_des_bytes = 0;
@@ -865,7 +866,9 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
     h->blk.resize(cfg->blocks);
     {   // The depth pixels the law can read: the patch centre of each token in camera resolution — servo.hip token_pixel, the
         // same operations in the same precisions (fp32 centre, fp64 scale, round half to even; vitvs_v2.py:511-513, 544-549).
-        // tests/test_gpu_path.py::test_host_pointer_entry_point_matches_device_entry_point holds the two restatements together.
+        // tests/test_gpu_path.py::test_host_pointer_entry_point_matches_device_entry_point holds the two restatements together at
+        // 640 x 480, tests/test_gpu_geometry.py where every product is a rounding tie, where the order of the fp64 operations
+        // shows, and where patch centres fall on the image's edge.
         const int g = (int)floor(sqrt((double)h->T));
         if (g * g == h->T) {
             const double scale = (double)cfg->img_size / (double)g;
@@ -877,6 +880,10 @@ int vitvs_create_ex(const vitvs_config* cfg, int32_t register_tokens, vitvs_hand
                 const long u = (long)rint((double)cc * sx), v = (long)rint((double)r * sy);
                 if (u >= 0 && u < cfg->u_max && v >= 0 && v < cfg->v_max) h->depth_sites.push_back((int32_t)(v * cfg->u_max + u));
             }
+            // and pixel (0, 0): a zero-padded row (4 <= matches < num_pairs) has the pixel (0, 0) and reads the depth there, as
+            // get_depth does in the reference (vitvs_v2.py:525-553, 566-586).  It is a patch centre in no ordinary geometry; where
+            // it is one, the site is listed twice, which costs one more 2-byte copy.
+            if (cfg->u_max > 0 && cfg->v_max > 0) h->depth_sites.push_back(0);
         }
     }
     // hipGraph replay of the update is opt-in (VITVS_GRAPH=1, read once per handle): with kernel arguments in device
@@ -1357,7 +1364,8 @@ struct UpdateArgs {
     // forward's launches have been enqueued and before the law's launch (the only kernel that reads it): off the critical path
     // Only the pixels the law can ask for are copied: it looks the depth up at the patch CENTRE of a current-frame token
     // (vitvs_v2.py:511-553, 566-586), i.e. at one of T fixed sites of the image (linear pixel indices, the handle's depth_sites),
-    // so T 2-byte gathers stand for the 614 KB image.  A law whose plan reads the depth anywhere (a refined match can lie on any
+    // or, for a zero-padded row (4 <= matches < num_pairs), at pixel (0, 0), which is one of the sites for that reason: T + 1
+    // 2-byte gathers stand for the 614 KB image.  A law whose plan reads the depth anywhere (a refined match can lie on any
     // pixel) has the whole image copied; one that does not read it (L(s*, Z*)) none of it.
     const uint16_t* late_src = nullptr;
     ServoPlan law;                              // the law of this update (velocity_update)

@@ -373,6 +373,8 @@ class Engine:
             z = torch.as_tensor(Z)
             if z.dtype != torch.uint16:
                 raise VitvsError("Z must be the sensor's uint16 millimetre image")
+            if z.dim() >= 2 and tuple(z.shape[-2:]) != (self.params.v_max, self.params.u_max):
+                raise VitvsError("Z must be the sensor's uint16 millimetre image(s) [v_max, u_max]")
             z = z.reshape(n, self.params.v_max, self.params.u_max).to(self.device).contiguous()
         kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
         if kk.shape[0] == 1 and n > 1:
@@ -423,7 +425,8 @@ class Engine:
         z = None
         if Z is not None:
             z = np.ascontiguousarray(Z)
-            if z.dtype != np.uint16 or z.size != n * self.params.v_max * self.params.u_max:
+            if z.dtype != np.uint16 or z.size != n * self.params.v_max * self.params.u_max \
+                    or (z.ndim >= 2 and tuple(z.shape[-2:]) != (self.params.v_max, self.params.u_max)):
                 raise VitvsError("Z must be the sensor's uint16 millimetre image(s) [v_max, u_max]")
         kk = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (n, 4)))
         k = self._num_pairs(num_pairs)
