@@ -507,6 +507,43 @@ VITVS_API int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const dou
                                       int32_t n_iter, double* v_rig, int32_t* rig_status, double* pose, int32_t* rig_info,
                                       double* moments, double* weights, double* sigma);
 
+/* --- the roll search -----------------------------------------------------------------------------
+ * ViT tokens are not rotation invariant: past ~45 degrees of in-plane rotation between the current frame and the goal the matches
+ * degrade.  The reference turns the robot to four poses and scores the views (find_and_set_best_pose, vitvs_v2.py:1151-1189).
+ * The search needs no motion: a quarter turn of a square frame is lossless and a quarter turn of its token grid is a permutation
+ * of token ids.
+ *
+ * vitvs_quarter_turns_dev: out [n_frames][4][S][S][3] <- frames [n_frames][S][S][3] uint8, S = img_size, copy k =
+ * numpy.rot90(frame, k) (k = 1: out[r][c] = in[c][S-1-r]).  One launch on `stream`; independent of vitvs_set_frame_size.
+ * Returns 0, -1 (null), -5 (n_frames < 1). */
+VITVS_API int vitvs_quarter_turns_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, uint8_t* out, void* stream);
+/* vitvs_roll_velocity_dev: ONE frame pair, from any in-plane rotation.  The current frame's four quarter-turned copies are matched
+ * against the goal exactly as a des_shared call of four pairs matches them (I_des NULL: a cached goal of ONE image); candidate k's
+ * score is the fp64 mean of sim_1 over its mutual nearest neighbours, a candidate is valid when 0 < n_mutual < T or under the
+ * same-image shortcut, the winner k* is the largest score (the smallest k on an exact tie; -1 without a valid candidate).  With P =
+ * numpy.rot90(arange(T).reshape(g, g), k*).reshape(-1) the winner's tables are carried back into the unturned frame, nn_1'[i] =
+ * P[nn_1[i]], nn_2'[P[j]] = nn_2[j], sim_1' = sim_1, and the law runs on them for one pair with the caller's depth image, K and
+ * selection (arguments as vitvs_compute_velocity_dev's for n_pairs = 1).  When the winner is a turned copy under the same-image
+ * shortcut (the camera sits a quarter turn from the goal), a feature row's current-side token is nn_1'[i] instead of i and info[2]
+ * is 0: the twist turns the camera, and the follow-on laws do not take their at-goal early out.
+ *   roll_info    device int32 [8]: k*, the four n_mutual, the same-image flag of k*, 0, 0
+ *   scores       device double [4]: NaN for a candidate that is not valid
+ * Afterwards the handle's last law evaluation is a one-pair one: vitvs_last_details(1) returns the carried-back tables, and the
+ * pose and homography laws with n_pairs = 1 are valid behind it; "robust_law", "interaction" and every select_mode compose.
+ * With k* = -1 pair 0 keeps candidate 0's keys and the law reports VITVS_NO_CORRESPONDENCE by itself.  Option "graph_replay"
+ * does not replay this call.  The first call allocates the turned copies' buffer and synchronises the device: make it outside
+ * any stream capture.  Returns 0, -1 (null), -3 (max_pairs < 4), -4, -5 (option "subpatch" on; a frame size other than S x S set
+ * with vitvs_set_frame_size; a token grid that is not symmetric under the turn, (S - patch) % stride != 0; I_des NULL without a
+ * cached goal of one image; a bad selection).  No counterpart in the reference. */
+VITVS_API int vitvs_roll_velocity_dev(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_des, const uint16_t* Z_mm,
+                                      const double* K, int32_t select_mode, const int32_t* selection, const int32_t* n_selected,
+                                      int32_t num_pairs, double* v_c, int32_t* status, int32_t* roll_info, double* scores,
+                                      void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_roll_velocity(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_des, const uint16_t* Z_mm, const double* K,
+                                  int32_t select_mode, const int32_t* selection, const int32_t* n_selected, int32_t num_pairs,
+                                  double* v_c, int32_t* status, int32_t* roll_info, double* scores);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several

@@ -273,6 +273,15 @@ VITVS_API int vitvs_op_normalize_rows(const float* src, float* dst, int32_t rows
  * when T keys do not fit in 160 KiB of LDS. */
 VITVS_API int vitvs_op_best_order_dev(int32_t T, int32_t cells, int32_t n_pairs, const int32_t* nn_1, const int32_t* nn_2,
                             const float* sim_1, int32_t* order, void* stream);
+/* The two kernels of the roll search (vitvs_roll_velocity_dev) alone.  vitvs_op_quarter_turns: out [n][4][S][S][3] <- frames
+ * [n][S][S][3] uint8 (device pointers), copy k = numpy.rot90(frame, k), for any S >= 1; -2 for an argument out of range. */
+VITVS_API int vitvs_op_quarter_turns(const uint8_t* frames, int32_t n, int32_t S, uint8_t* out, void* stream);
+/* vitvs_op_roll_pick: the four candidates' tables (device pointers nn_1, nn_2 int32 and sim_1 fp32 [4][T]) -> the winner's tables
+ * in the unturned frame (nn_1_out, nn_2_out, sim_1_out [T]; candidate 0's when nobody is valid), roll_info int32 [8] and scores
+ * double [4] as vitvs_roll_velocity_dev states them.  The tables are packed into the keys the law reads in scratch memory of the
+ * call's own; the call returns after the launches have finished.  -2 when T is not a square grid. */
+VITVS_API int vitvs_op_roll_pick(int32_t T, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1, int32_t* nn_1_out,
+                                 int32_t* nn_2_out, float* sim_1_out, int32_t* roll_info, double* scores, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,13 +28,17 @@ static void check(const char* law, IoList l, size_t P, size_t R, size_t n) {
     for (size_t i = 0; i < l.n; ++i) EXPECT(l.f[i].dev == nullptr, "%s field %zu: a pointer without a block", law, i);
     std::vector<unsigned char> block(total);      // exactly the allocation: a byte past it is the sanitizer's
     EXPECT(io_place(l, block.data()) == total, "%s: the size depends on the base", law);
-    size_t end = 0, seen8 = 0, seen4 = 0;
+    size_t end = 0, seen8 = 0, seen4 = 0, widest = 8;
     for (size_t i = 0; i < l.n; ++i) {
         const IoField& f = l.f[i];
         const size_t off = (size_t)(f.dev - block.data());
-        EXPECT(f.elem == 8 || f.elem == 4, "%s field %zu: element size %zu", law, i, f.elem);
-        EXPECT(f.elem == 8 ? seen4 == 0 : true, "%s field %zu: an 8-byte field behind a 4-byte one", law, i);
-        (f.elem == 8 ? seen8 : seen4) += 1;
+        // 8- and 4-byte fields; the roll search's list ends with its depth image (2-byte elements) and its frames (bytes)
+        EXPECT(f.elem == 8 || f.elem == 4 || f.elem == 2 || f.elem == 1, "%s field %zu: element size %zu", law, i, f.elem);
+        EXPECT(f.elem <= widest, "%s field %zu: a %zu-byte field behind a %zu-byte one", law, i, f.elem, widest);
+        widest = f.elem;
+        if (f.elem == 8) seen8 += 1;
+        if (f.elem == 4) seen4 += 1;
+        if (f.elem < 4) EXPECT(off % 16 == 0, "%s field %zu (an image) at offset %zu is not on a 16-byte boundary", law, i, off);
         EXPECT(off == end, "%s field %zu begins at %zu, the one before it ends at %zu (P %zu R %zu)", law, i, off, end, P, R);
         EXPECT(off % f.elem == 0, "%s field %zu at offset %zu is not aligned to %zu (P %zu R %zu)", law, i, off, f.elem, P, R);
         EXPECT(f.cap > 0 && f.count <= f.cap, "%s field %zu: count %zu, capacity %zu (P %zu R %zu n %zu)", law, i, f.count, f.cap, P, R, n);
@@ -79,6 +83,21 @@ int main() {
         EXPECT(io_place(io_list(hom0), nullptr) == (P * (4 + 6 + 9 + 1 + R)) * 8 + P * 10 * 4, "homography: %zu %zu", P, R);
         EXPECT(io_place(io_list(pose_rig0), nullptr) == (P * (12 + 4 + R) + 6 + 12 + 18 + 1) * 8 + (P + 9) * 4, "pose rig: %zu %zu", P, R);
         EXPECT(io_place(io_list(rig0), nullptr) == (P * 36 + 34 + P * 4 + 1 + P * R) * 8 + (P + 9) * 4, "rig: %zu %zu", P, R);
+    }
+    // the roll search: one pair; T tokens, R rows, S x S x 3 frame bytes, u_max x v_max depth pixels
+    const size_t rolls[][5] = {{16, 48, 64, 640, 480}, {196, 48, 224, 640, 480}, {196, 196, 224, 480, 480}, {484, 24, 308, 641, 479},
+                               {3136, 3136, 448, 1280, 720}, {1, 1, 16, 1, 1}};
+    uint8_t b8 = 0;
+    uint16_t b16 = 0;
+    for (const auto& r : rolls) {
+        const size_t T = r[0], R = r[1], frame = r[2] * r[2] * 3, depth = r[3] * r[4];
+        for (size_t n_sel : {(size_t)0, R < T ? R : T, T}) {
+            RollIo roll = roll_io(T, R, frame, depth, n_sel, &d, &i, &i, &b16, &b8, &b8, &d, &i, &i, &d);
+            check("roll", io_list(roll), T, R, n_sel);
+            RollIo roll0 = roll_io(T, R, frame, depth);
+            EXPECT(io_place(io_list(roll0), nullptr) == io_place(io_list(roll), nullptr), "roll: allocation and call disagree");
+            EXPECT(roll.Z.count == depth && roll.I_cur.count == frame && roll.selection.count == n_sel, "roll: counts");
+        }
     }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");

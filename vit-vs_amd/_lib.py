@@ -75,6 +75,9 @@ PROTOTYPES = {
     "vitvs_homography_consensus_velocity": (_I, [_P, _I, _P, _P, C.c_double, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_rig_velocity_dev": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_rig_velocity": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_quarter_turns_dev": (_I, [_P, _I, _P, _P, _P]),
+    "vitvs_roll_velocity_dev": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "vitvs_roll_velocity": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "vitvs_last_details": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_weights": (_I, [_P, _I, _P]),
     "vitvs_set_option": (_I, [_P, C.c_char_p, C.c_int64]),
@@ -136,6 +139,8 @@ PROTOTYPES = {
     "vitvs_op_saliency": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vitvs_op_normalize_rows": (_I, [_P, _P, _I, _I, _P]),
     "vitvs_op_best_order_dev": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "vitvs_op_quarter_turns": (_I, [_P, _I, _I, _P, _P]),
+    "vitvs_op_roll_pick": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

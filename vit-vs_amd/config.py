@@ -202,7 +202,15 @@ class ServoParams:
                                    # start.  256 fills one round of the kernel's workgroup
     homography_consensus_seed: int = 0  # of the hypotheses' draw (0 .. 2^32 - 1); fixed across updates: same frames, same twist
 
+    roll_search: bool = False      # a servo.Controller runs every update through the roll search (Engine.roll_velocity): the
+                                   # current frame is matched as its four quarter-turned copies and the law runs on the best one's
+                                   # matches, so the servo starts from any in-plane rotation.  Four or five forwards per update
+                                   # instead of two; needs an engine with max_pairs >= 4; not with subpatch or selection "reference"
+
     def __post_init__(self):
+        if self.roll_search and self.subpatch:
+            raise ValueError("roll_search does not combine with subpatch: the sub-patch offsets of a turned copy would have to be "
+                             "turned too")
         if self.interaction not in INTERACTIONS:
             raise ValueError(f"interaction is one of {INTERACTIONS}, got {self.interaction!r}")
         if not 1 <= int(self.select_cells) <= 16:
@@ -283,7 +291,8 @@ def load_reference_config(source) -> ReferenceConfig:
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
     else "current"; ``law`` ("ibvs" / "pose" / "homography"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise,
     else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``homography_consensus`` and
-    ``homography_consensus_seed`` likewise, else 0 and 0; ``select_cells`` (the cell grid of selection "best") likewise, else 4."""
+    ``homography_consensus_seed`` likewise, else 0 and 0; ``select_cells`` (the cell grid of selection "best") likewise, else 4;
+    ``roll_search`` (the roll search in front of every update) likewise, else False."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -308,8 +317,8 @@ def load_reference_config(source) -> ReferenceConfig:
                         homography_depth=float(cfg.get("homography_depth", 1.0)),
                         homography_consensus=int(cfg.get("homography_consensus", 0)),
                         homography_consensus_seed=int(cfg.get("homography_consensus_seed", 0)),
-                        select_cells=int(cfg.get("select_cells", 4)))
-    used = {"u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
+                        select_cells=int(cfg.get("select_cells", 4)), roll_search=bool(cfg.get("roll_search", False)))
+    used = {"roll_search","u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",

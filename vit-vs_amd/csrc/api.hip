@@ -135,6 +135,9 @@ struct vitvs_handle {
     unsigned char *pose_ws = nullptr, *pose_io = nullptr;           // PoseIo
     unsigned char *hom_ws = nullptr, *hom_io = nullptr;             // HomographyIo
     unsigned char *pose_rig_ws = nullptr, *pose_rig_io = nullptr;   // PoseRigIo
+    // The roll search (vitvs_roll_velocity[_dev], roll.hip), the same arrangement: roll_ws = the flag `rolled` the pick leaves for
+    // the law (one int32 on a 256-byte line of its own), then the current frame's four quarter-turned copies [4][S][S][3]
+    unsigned char *roll_ws = nullptr, *roll_io = nullptr;           // RollIo
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -659,7 +662,7 @@ int check_selection(vitvs_handle* h, int T, int mode, const int32_t* selection, 
 // The law on the arg-max keys in the handle, for a selection the entry point has checked (check_selection)
 int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const double* K, int mode, int num_pairs,
               const int32_t* selection, const int32_t* n_selected, double* v_c, int32_t* status, hipStream_t st,
-              const RefineSpec& rf = RefineSpec{}) {
+              const RefineSpec& rf = RefineSpec{}, const int32_t* rolled = nullptr) {
     const vitvs_config& c = h->cfg;
     const int g = (int)floor(sqrt((double)T));  // reference: int(np.sqrt(T)), vitvs_v2.py:75
     if (g * g != T) return set_err(h, -5, "token count is not a square grid");
@@ -701,6 +704,7 @@ int run_servo(vitvs_handle* h, int n_pairs, int T, const uint16_t* Z, const doub
         a.interaction = plan.interaction; a.zgoal = h->zgoal; a.zgoal_out = h->zgoal_ws;
         a.zgoal_stride = h->n_goal_depth == 1 ? 0 : T + 1;
     }
+    a.rolled = rolled;                          // (the roll search only; null: the law as it always was)
     note_law(h, n_pairs, T, plan, mode);
     int rc = 0;
     { Span sp(h, KC_SERVO, st); rc = launch_servo(plan, a, st); }
@@ -1381,9 +1385,10 @@ static inline void late_inputs(vitvs_handle* h, const UpdateArgs& u) {
     }
 }
 
-static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) {
+// The first half of an update: the forward of the call's frames and the correspondence stage, up to the packed arg-max keys of
+// its n_pairs pairs in h->row_best / col_best (of `u` it reads the frames, n_pairs and des_shared)
+static int enqueue_forward_gram(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) {
     const int n_des = u.des_shared ? 1 : u.n_pairs, n_img = n_des + u.n_pairs;
-    const RefineSpec rf{nullptr, h->subpatch != 0, u.des_shared ? 1 : 0};
     h->desc_keys = u.n_pairs * h->T;
     // cached goal: only the current frames (images n_des .. n_img - 1 of the call's list) go through the network
     int rc = u.I_des ? forward_chain(h, 0, n_img, n_des, u.I_des, u.I_cur, h->part, st)
@@ -1394,12 +1399,18 @@ static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) 
     const GramPlan gp = plan_gram(h->prec, h->cfg.binned != 0, h->T, h->cfg.dim, u.n_pairs, h->cfg.max_pairs);
     GramOperands go;
     go.x = h->x; go.P = 1 + h->R; go.dn = h->dn; go.dh = h->dh; go.G = h->gram_ws; go.sq = h->sq; go.grid = h->grid;
-    go.des_shared = rf.des_shared; go.row_best = h->row_best; go.col_best = h->col_best;
+    go.des_shared = u.des_shared ? 1 : 0; go.row_best = h->row_best; go.col_best = h->col_best;
     for (int i = 0; i < gp.n_steps && !rc; ++i) {
         Span sp(h, kGramStepClass[gp.steps[i]], st);
         rc = launch_gram_step(gp, i, go, st);
     }
     if (rc) return set_err(h, rc, "correspondence launch failed");
+    return 0;
+}
+
+static int enqueue_update(vitvs_handle* h, const UpdateArgs& u, hipStream_t st) {
+    const RefineSpec rf{nullptr, h->subpatch != 0, u.des_shared ? 1 : 0};
+    if (int rc = enqueue_forward_gram(h, u, st)) return rc;
     late_inputs(h, u);
     return run_servo(h, u.n_pairs, h->T, u.Z_mm, u.K, u.select_mode, u.num_pairs, u.selection, u.n_selected, u.v_c, u.status, st, rf);
 }
@@ -1962,6 +1973,80 @@ int vitvs_pose_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* rTc, 
     });
 }
 
+// --- the roll search -----------------------------------------------------------------------------
+int vitvs_quarter_turns_dev(vitvs_handle* h, int32_t n_frames, const uint8_t* frames, uint8_t* out, void* stream) {
+    if (!h || !frames || !out) return set_err(h, -1, "null argument");
+    if (n_frames <= 0) return set_err(h, -5, "n_frames is at least 1");
+    DeviceScope dev(h);
+    int rc = 0;
+    { Span sp(h, KC_PATCHIFY, as_stream(stream)); rc = launch_quarter_turns(frames, out, n_frames, h->cfg.img_size, as_stream(stream)); }
+    return rc ? set_err(h, rc, "quarter-turn launch failed") : 0;
+}
+
+// What a roll call asks of the handle and of the call's selection, before anything is staged or enqueued; the first call allocates
+static int roll_prepare(vitvs_handle* h, int select_mode, const int32_t* selection, const int32_t* n_selected, int np) {
+    const vitvs_config& c = h->cfg;
+    if (c.max_pairs < 4) return set_err(h, -3, "the roll search matches four turned copies at once: max_pairs must be at least 4");
+    if (h->subpatch) return set_err(h, -5, "the roll search does not combine with option subpatch (the offsets would have to be turned too)");
+    if (h->fr.in_h) return set_err(h, -5, "the roll search takes frames at img_size x img_size: clear vitvs_set_frame_size first");
+    if ((c.img_size - c.patch) % c.stride != 0 || h->grid * h->grid != h->T)
+        return set_err(h, -5, "the token grid is not symmetric under a quarter turn ((img_size - patch) % stride != 0)");
+    if (int rc = check_selection(h, h->T, select_mode, selection, n_selected, np)) return rc;
+    if (vitvs_weights_ready(h) != 0) return set_err(h, -4, "weights not fully loaded: " + h->err);
+    if (int rc = check_interaction(h, 1, h->T)) return rc;
+    const size_t frame = (size_t)c.img_size * c.img_size * 3;
+    RollIo io = roll_io(h->T, c.max_rows, frame, (size_t)c.u_max * c.v_max);
+    return law_blocks(h, "roll search", &h->roll_ws, 256 + 4 * frame, &h->roll_io, io_place(io_list(io), nullptr));
+}
+
+int vitvs_roll_velocity_dev(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_des, const uint16_t* Z_mm, const double* K,
+                            int32_t select_mode, const int32_t* selection, const int32_t* n_selected, int32_t num_pairs, double* v_c,
+                            int32_t* status, int32_t* roll_info, double* scores, void* stream) {
+    if (!h || !I_cur || !K || !v_c || !status || !roll_info || !scores) return set_err(h, -1, "null argument");   // I_des NULL: the cached goal
+    const int np = call_num_pairs(h, num_pairs);
+    DeviceScope dev(h);
+    if (int rc = roll_prepare(h, select_mode, selection, n_selected, np)) return rc;
+    ServoPlan law;
+    if (int rc = plan_law(h, h->T, RefineSpec{}, law)) return rc;
+    if (!I_des && h->goal_frames != 1) return set_err(h, -5, "I_des is NULL and no goal of one image is cached (vitvs_set_goal_dev)");
+    if (I_des) h->goal_frames = 0;              // the call forwards a goal frame of its own over the cached rows
+    h->details_pinned = false;
+    h->host_tables = vitvs_handle::HostTables{};
+    hipStream_t st = dev_stream(h, stream);
+    int32_t* rolled = reinterpret_cast<int32_t*>(h->roll_ws);
+    uint8_t* turned = h->roll_ws + 256;
+    int rc = 0;
+    { Span sp(h, KC_PATCHIFY, st); rc = launch_quarter_turns(I_cur, turned, 1, h->cfg.img_size, st); }
+    if (rc) return set_err(h, rc, "quarter-turn launch failed");
+    // the four copies against the one goal: the forward and the correspondence stage of a des_shared call of four pairs
+    UpdateArgs u{4, 1, select_mode, np, turned, I_des, Z_mm, K, selection, n_selected, v_c, status};
+    if ((rc = enqueue_forward_gram(h, u, st))) return rc;
+    { Span sp(h, KC_SERVO, st); rc = launch_roll_pick(h->row_best, h->col_best, h->T, h->grid, scores, roll_info, rolled, st); }
+    if (rc) return set_err(h, rc, "roll pick launch failed");
+    // the law for ONE pair on pair 0's keys: the winner's tables in the unturned frame
+    return run_servo(h, 1, h->T, Z_mm, K, select_mode, np, selection, n_selected, v_c, status, st, RefineSpec{}, rolled);
+}
+
+int vitvs_roll_velocity(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_des, const uint16_t* Z_mm, const double* K,
+                        int32_t select_mode, const int32_t* selection, const int32_t* n_selected, int32_t num_pairs, double* v_c,
+                        int32_t* status, int32_t* roll_info, double* scores) {
+    if (!h || !I_cur || !K || !v_c || !status || !roll_info || !scores) return set_err(h, -1, "null argument");
+    const int np = call_num_pairs(h, num_pairs);
+    DeviceScope dev(h);
+    if (int rc = roll_prepare(h, select_mode, selection, n_selected, np)) return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t n_sel = select_mode == VITVS_SELECT_EXPLICIT ? (size_t)np : select_mode == VITVS_SELECT_ORDER ? (size_t)h->T : 0;
+    RollIo io = roll_io(h->T, c.max_rows, (size_t)c.img_size * c.img_size * 3, (size_t)c.u_max * c.v_max, n_sel, K,
+                        n_sel ? selection : nullptr, select_mode == VITVS_SELECT_EXPLICIT ? n_selected : nullptr, Z_mm, I_cur, I_des,
+                        v_c, status, roll_info, scores);
+    return host_call(h, io_list(io), h->roll_io, [&](hipStream_t st) {
+        return vitvs_roll_velocity_dev(h, io.I_cur.dev, I_des ? io.I_des.dev : nullptr,
+                                       Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, io.K.f64(), select_mode,
+                                       io.selection.i32(), io.n_selected.i32(), np, io.v_c.f64(), io.status.i32(), io.roll_info.i32(),
+                                       io.scores.f64(), st);
+    });
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -2317,6 +2402,34 @@ int vitvs_op_best_order_dev(int32_t T, int32_t cells, int32_t n_pairs, const int
         rc = launch_encode_best(nn_1 + o, nn_2 + o, sim_1 + o, T, rb + o, cb + o, st);
     }
     if (!rc) rc = launch_best_order(bp, n_pairs, rb, cb, order, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -1;
+    (void)hipFree(keys);
+    return rc;
+}
+int vitvs_op_quarter_turns(const uint8_t* frames, int32_t n, int32_t S, uint8_t* out, void* stream) {
+    DeviceScope dev(nullptr);
+    return launch_quarter_turns(frames, out, n, S, as_stream(stream));
+}
+int vitvs_op_roll_pick(int32_t T, const int32_t* nn_1, const int32_t* nn_2, const float* sim_1, int32_t* nn_1_out, int32_t* nn_2_out,
+                       float* sim_1_out, int32_t* roll_info, double* scores, void* stream) {
+    if (!nn_1 || !nn_2 || !sim_1 || !nn_1_out || !nn_2_out || !sim_1_out || !roll_info || !scores) return -1;
+    const int g = T > 0 ? (int)floor(sqrt((double)T)) : 0;
+    if (T <= 0 || g * g != T) return -2;
+    DeviceScope dev(nullptr);
+    hipStream_t st = as_stream(stream);
+    // the packed keys of the four candidates, made from the tables as vitvs_servo_from_nn_dev makes them, and the flag the pick
+    // leaves for the law; freed behind the launches
+    unsigned long long* keys = nullptr;
+    if (hipMalloc((void**)&keys, (size_t)2 * 4 * T * 8 + 256) != hipSuccess) return -6;
+    unsigned long long *rb = keys, *cb = keys + (size_t)4 * T;
+    int32_t* rolled = reinterpret_cast<int32_t*>(keys + (size_t)8 * T);
+    int rc = 0;
+    for (int k = 0; !rc && k < 4; ++k) {
+        const size_t o = (size_t)k * T;
+        rc = launch_encode_best(nn_1 + o, nn_2 + o, sim_1 + o, T, rb + o, cb + o, st);
+    }
+    if (!rc) rc = launch_roll_pick(rb, cb, T, g, scores, roll_info, rolled, st);
+    if (!rc) rc = launch_decode_best(rb, cb, T, nn_1_out, nn_2_out, sim_1_out, st);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -1;
     (void)hipFree(keys);
     return rc;

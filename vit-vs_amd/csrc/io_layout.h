@@ -9,7 +9,8 @@
 namespace vitvs {
 
 struct IoField {
-    size_t elem;                  // bytes per element: 8 (f64) or 4 (i32); a list holds its 8-byte fields first, so nothing is padded
+    size_t elem;                  // bytes per element: 8 (f64) or 4 (i32) (the roll search's list: also 2 (u16) and 1 (u8)); a list
+                                  // holds its widest fields first, so nothing is padded
     size_t cap;                   // elements the block reserves: the field at max_pairs / max_rows
     size_t count;                 // elements of the call at hand: what is copied
     bool input;                   // copied to the device before the launch; an output is copied back after it
@@ -95,6 +96,24 @@ inline PoseRigIo pose_rig_io(size_t P, size_t R, size_t n = 0, const double* rTc
                      io_out(8, 12, 12, pose),       io_out(8, 18, 18, moments),       io_out(8, 1, 1, sigma),
                      io_out(8, P * R, n * R, weights), io_in(4, P, n, status),        io_out(4, 1, 1, rig_status),
                      io_out(4, 8, 8, rig_info)};
+}
+
+// the roll search (vitvs_roll_velocity): ONE pair.  T tokens, R = max_rows, `frame` = S * S * 3 bytes, `depth` = u_max * v_max
+// pixels.  Behind the 8- and 4-byte fields come the depth image (2-byte elements) and the two frames (bytes); the capacities are
+// rounded so that each of the three begins on a 16-byte boundary of the block.  n_sel = the ids / order entries the call's
+// selection mode hands over (0: none).  Z and I_des are optional INPUTS: null, nothing is copied and the _dev form gets null.
+struct RollIo {
+    IoField K, v_c, scores, status, roll_info, n_selected, selection, Z, I_cur, I_des;
+};
+inline RollIo roll_io(size_t T, size_t R, size_t frame, size_t depth, size_t n_sel = 0, const double* K = nullptr,
+                      const int32_t* selection = nullptr, const int32_t* n_selected = nullptr, const uint16_t* Z = nullptr,
+                      const uint8_t* I_cur = nullptr, const uint8_t* I_des = nullptr, double* v_c = nullptr, int32_t* status = nullptr,
+                      int32_t* roll_info = nullptr, double* scores = nullptr) {
+    const size_t sel_cap = ((T > R ? T : R) + 3) & ~(size_t)3, z_cap = (depth + 7) & ~(size_t)7, f_cap = (frame + 15) & ~(size_t)15;
+    return RollIo{io_in(8, 4, 4, K),               io_out(8, 6, 6, v_c),              io_out(8, 4, 4, scores),
+                  io_out(4, 4, 1, status),         io_out(4, 8, 8, roll_info),        io_in(4, 4, 1, n_selected),
+                  io_in(4, sel_cap, n_sel, selection), io_in(2, z_cap, depth, Z),     io_in(1, f_cap, frame, I_cur),
+                  io_in(1, f_cap, frame, I_des)};
 }
 
 }  // namespace vitvs

@@ -302,6 +302,16 @@ int plan_best_order(int T, int cells, BestOrderPlan* plan);
 int launch_best_order(const BestOrderPlan& plan, int n_pairs, const unsigned long long* row_best,
                       const unsigned long long* col_best, int32_t* order, hipStream_t stream);
 
+// ---- roll.hip ------------------------------------------------------------------------------
+// The roll search.  out [n][4][S][S][3] <- frames [n][S][S][3] uint8: copy k is numpy.rot90(frame, k); one launch,
+// a pixel tile per workgroup through LDS.  -2: a null pointer, n outside 1 .. 65535, S < 1
+int launch_quarter_turns(const uint8_t* frames, uint8_t* out, int n, int S, hipStream_t stream);
+// The four candidates' keys (pairs 0 .. 3 of row_best / col_best, [4][T]) -> scores [4] (fp64 mean of sim_1 over the mutual
+// nearest neighbours; NaN: not a valid candidate), roll_info [8] (k*, the four n_mutual, same-image of k*, 0, 0), *rolled = k* > 0,
+// and pair 0's keys = the winner's tables in the unturned frame.  One workgroup.  -2: a null pointer, grid * grid != T
+int launch_roll_pick(unsigned long long* row_best, unsigned long long* col_best, int T, int grid, double* scores,
+                     int32_t* roll_info, int32_t* rolled, hipStream_t stream);
+
 // ---- servo.hip -----------------------------------------------------------------------------
 enum SelectMode : int { SEL_EXPLICIT = 0, SEL_PRIORITY = 1, SEL_DENSE = 2 };
 enum Status : int { ST_OK = 0, ST_NO_CORRESPONDENCE = 1, ST_TOO_FEW = 2, ST_NO_DEPTH = 3 };
@@ -357,6 +367,9 @@ struct ServoArgs {
     int zgoal_stride;         // entries between the goal images of consecutive pairs: T + 1, or 0 when one image serves all
     const uint16_t* zgoal;    // [n_goal][T + 1] mm: goal depth at every token's patch centre, entry T at pixel (0, 0)
     double* zgoal_out;        // [n_pairs][max_rows] Z* of every feature row in metres (output)
+    // The roll search (roll.hip); null on every other path, and then nothing below is read
+    const int32_t* rolled;    // [1] != 0: the keys are a quarter-turned winner's, carried back into the unturned frame.  Under the
+                              // same-image shortcut a feature row's current-side token is then nn_1[tok], not tok, and info[2] is 0
 };
 // One law launch, decided by plan_servo and carried out by launch_servo.  RefineSource: where servo_kernel<., REFINE, .> takes its
 // sub-patch offsets from (the codes are ABI: vitvs_op_servo_plan): a given table (off_in), the raw Gram with the squared norms

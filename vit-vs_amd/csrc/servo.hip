@@ -7,6 +7,8 @@
 // centre by the sub-patch offsets of refine.h before the pixel features are formed.
 // servo_kernel<., ., true> (option "interaction", ViSP's DESIRED / MEAN choices of the interaction matrix) builds L at the goal
 // features with the goal depth, L(s*, Z*), or the mean of that and the reference's L(s, Z).
+// ServoArgs::rolled (the roll search, roll.hip; null everywhere else) changes the same-image shortcut behind a turned winner
+// (DESIGN.md 5j).
 //
 // Reference arithmetic being replaced (vitvs_v2.py):
 //   same-image shortcut  mean(sim_1) > 0.99                   :84-101
@@ -131,9 +133,17 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     }
     ssum = wave_sum(ssum);
     if (lane == 0) fscr[wave] = ssum;
+    // (the roll search only: the keys are a quarter-turned winner's, carried back into the unturned frame; null everywhere else.
+    // Read here, behind the decode loop: nothing on the other paths waits for it)
+    int turned = 0;
+    if (a.rolled) turned = *a.rolled;
     lds_barrier();
     const float mean_sim = (fscr[0] + fscr[1] + fscr[2] + fscr[3]) / (float)T;
     const bool same_image = mean_sim > 0.99f;
+    // the shortcut pairs every token with itself: the goal seen from the goal pose.  A quarter-turned copy of the goal is not the
+    // goal pose: behind a turned winner the shortcut keeps its candidates (every token) and its similarity (1), but a row's
+    // current-side token is the match nn_1[tok], and the follow-on laws are not told "at the goal" (info[2])
+    const bool self_match = same_image && turned == 0;
 
     // 2. mutual nearest neighbours
     int cnt = 0;
@@ -270,14 +280,14 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         if (live) {
             tok = sel[k];
             token_pixel(a, tok, us, vs);
-            if constexpr (REFINE) refined_pixel(a, same_image ? tok : nn1[tok], offL[2 * k], offL[2 * k + 1], u, v);
-            else token_pixel(a, same_image ? tok : nn1[tok], u, v);
+            if constexpr (REFINE) refined_pixel(a, self_match ? tok : nn1[tok], offL[2 * k], offL[2 * k + 1], u, v);
+            else token_pixel(a, self_match ? tok : nn1[tok], u, v);
             simk = same_image ? 1.0 : (double)simL[tok];
         }
         const double x = ((double)u - cx) / fx, y = ((double)v - cy) / fy;
         const double xs = ((double)us - cx) / fx, ys = ((double)vs - cy) / fy;
         unsigned d = 0;
-        if (live && prefetch_depth && !same_image) d = (unsigned)zraw[tok];
+        if (live && prefetch_depth && !self_match) d = (unsigned)zraw[tok];
         else if (depth && u >= 0 && u < a.depth_w && v >= 0 && v < a.depth_h) d = depth[(size_t)v * a.depth_w + u];
         double z = d != 0 ? (double)d / 1000.0 : 100.0;
         const int r0 = 2 * k, r1i = 2 * k + 1;
@@ -377,7 +387,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
             for (int i = 0; i < 6; ++i) a.v_c[(size_t)b * 6 + i] = vout[i];
             a.status[b] = status;
             int32_t* info = a.info + (size_t)b * 8;
-            info[0] = n_mutual; info[1] = n_rows; info[2] = same_image ? 1 : 0; info[3] = n_matched;
+            info[0] = n_mutual; info[1] = n_rows; info[2] = self_match ? 1 : 0; info[3] = n_matched;
             info[4] = sweeps; info[5] = R; info[6] = reweighted; info[7] = n_zero;
         }
         return;
@@ -554,7 +564,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
         for (int i = 0; i < 6; ++i) a.v_c[(size_t)b * 6 + i] = vout[i];
         a.status[b] = status;
         int32_t* info = a.info + (size_t)b * 8;
-        info[0] = n_mutual; info[1] = n_rows; info[2] = same_image ? 1 : 0; info[3] = n_matched;
+        info[0] = n_mutual; info[1] = n_rows; info[2] = self_match ? 1 : 0; info[3] = n_matched;
         info[4] = sweeps; info[5] = R; info[6] = 0; info[7] = 0;
     }
 }

@@ -454,6 +454,94 @@ class Engine:
         self._check(self.lib.vitvs_reselect(self.handle, mode, p(sel), p(cnt), k, p(v), p(st)), "vitvs_reselect")
         return v, st
 
+    # ------------------------------------------------------------------ the roll search
+    def _square_frames(self, frames, n=None) -> torch.Tensor:
+        """uint8 frames [n, S, S, 3] (or one [S, S, 3]) at the extractor's input size, whatever ``set_frame_size`` says, on the device."""
+        t = torch.as_tensor(frames)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        s = self.cfg.img_size
+        if t.dtype != torch.uint8 or t.dim() != 4 or tuple(t.shape[1:]) != (s, s, 3) or (n is not None and t.shape[0] != n):
+            raise VitvsError(f"frames must be uint8 [{'n' if n is None else n},{s},{s},3], got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device).contiguous()
+
+    def quarter_turns(self, frames) -> torch.Tensor:
+        """``vitvs_quarter_turns_dev``: uint8 frames [n, S, S, 3] (or [S, S, 3]) -> uint8 [n, 4, S, S, 3] on the device, copy k =
+        ``numpy.rot90(frame, k)``.  One launch on the current stream."""
+        f = self._square_frames(frames)
+        out = torch.empty((f.shape[0], 4) + tuple(f.shape[1:]), dtype=torch.uint8, device=self.device)
+        rc = self.lib.vitvs_quarter_turns_dev(self.handle, int(f.shape[0]), _ptr(f), _ptr(out), _stream_ptr(self.device))
+        self._check(rc, "vitvs_quarter_turns_dev")
+        return out
+
+    @staticmethod
+    def _roll_info(roll_info, scores) -> dict:
+        return dict(roll=int(roll_info[0]), scores=np.array(scores, np.float64), n_mutual=np.array(roll_info[1:5], np.int32),
+                    same_image=bool(roll_info[5]))
+
+    def roll_velocity(self, I_cur, I_des, Z, K, mode: int = _lib.SELECT_DENSE, selection=None, num_pairs: Optional[int] = None):
+        """``vitvs_roll_velocity_dev``: one servo update of ONE frame pair from any in-plane rotation.  The current
+        frame [S, S, 3] is matched against the goal (``I_des`` [S, S, 3], or None: the one goal image cached by ``set_goal``) as its
+        four quarter-turned copies in one batch, the best copy wins, its matches are carried back into the unturned frame and the
+        law runs on them with ``Z``, ``K`` and the selection as ``compute_velocity`` takes them for one pair.  Needs ``max_pairs >= 4``,
+        frames at S x S and ``subpatch`` off.  Returns ``(v_c float64 [6] device tensor, status int32 device scalar, info)``, ``info``
+        = dict(``roll``: the winner k (the current frame turned by k quarter turns matched best; -1: no valid candidate),
+        ``scores`` float64 [4] (NaN: not valid), ``n_mutual`` int32 [4], ``same_image``: the winner fell under the same-image
+        shortcut).  Afterwards ``last_details(1)``, ``pose_velocity`` and ``homography_velocity`` see a one-pair call.  Reading
+        ``info`` synchronises; the first call allocates: make it outside a stream capture."""
+        cur = self._square_frames(I_cur, 1)
+        des = None if I_des is None else self._square_frames(I_des, 1)
+        z = None
+        if Z is not None:
+            z = torch.as_tensor(Z)
+            if z.dtype != torch.uint16 or tuple(z.shape[-2:]) != (self.params.v_max, self.params.u_max) or z.numel() != self.params.v_max * self.params.u_max:
+                raise VitvsError("Z must be the sensor's uint16 millimetre image [v_max, u_max]")
+            z = z.to(self.device).contiguous()
+        kk = torch.as_tensor(K, dtype=torch.float64).reshape(1, 4).contiguous().to(self.device)
+        k = self._num_pairs(num_pairs)
+        sel, cnt = self._selection_args(mode, [selection] if mode == _lib.SELECT_EXPLICIT and not isinstance(selection, (list, tuple))
+                                        else selection, 1, self.tokens, k)
+        v = torch.empty((1, 6), dtype=torch.float64, device=self.device)
+        st = torch.empty(1, dtype=torch.int32, device=self.device)
+        rinfo = torch.empty(8, dtype=torch.int32, device=self.device)
+        scores = torch.empty(4, dtype=torch.float64, device=self.device)
+        rc = self.lib.vitvs_roll_velocity_dev(self.handle, _ptr(cur), _ptr(des), _ptr(z), _ptr(kk), mode, _ptr(sel), _ptr(cnt), k,
+                                              _ptr(v), _ptr(st), _ptr(rinfo), _ptr(scores), _stream_ptr(self.device))
+        self._check(rc, "vitvs_roll_velocity_dev")
+        self._last_tokens = self.tokens
+        return v[0], st[0], self._roll_info(rinfo.cpu().numpy(), scores.cpu().numpy())
+
+    def roll_velocity_host(self, I_cur, I_des, Z, K, mode: int = _lib.SELECT_DENSE, selection=None, num_pairs: Optional[int] = None):
+        """``vitvs_roll_velocity``, the host-pointer form of ``roll_velocity``: numpy arrays in, ``(v_c float64 [6], status int,
+        info)`` out, one synchronous C call, ordered behind whatever ``_dev`` work the engine still has pending."""
+        s = self.cfg.img_size
+
+        def frame(a):
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            a = a[0] if a.ndim == 4 and a.shape[0] == 1 else a
+            if tuple(a.shape) != (s, s, 3):
+                raise VitvsError(f"frames must be uint8 [{s},{s},3], got {tuple(a.shape)}")
+            return a
+        cur = frame(I_cur)
+        des = None if I_des is None else frame(I_des)
+        z = None
+        if Z is not None:
+            z = np.ascontiguousarray(Z)
+            if z.dtype != np.uint16 or z.size != self.params.v_max * self.params.u_max or tuple(z.shape[-2:]) != (self.params.v_max, self.params.u_max):
+                raise VitvsError("Z must be the sensor's uint16 millimetre image [v_max, u_max]")
+        kk = np.ascontiguousarray(np.asarray(K, np.float64).reshape(1, 4))
+        k = self._num_pairs(num_pairs)
+        if mode == _lib.SELECT_EXPLICIT and not isinstance(selection, (list, tuple)):
+            selection = [selection]
+        sel, cnt = self._selection_arrays_host(mode, selection, 1, k)
+        v, st, rinfo, scores = np.zeros(6), np.zeros(1, np.int32), np.zeros(8, np.int32), np.zeros(4)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_roll_velocity(self.handle, p(cur), p(des), p(z), p(kk), mode, p(sel), p(cnt), k, p(v), p(st), p(rinfo),
+                                          p(scores))
+        self._check(rc, "vitvs_roll_velocity")
+        self._last_tokens = self.tokens
+        return v, int(st[0]), self._roll_info(rinfo, scores)
+
     def last_tables(self, n_pairs: int = 1) -> dict:
         """``nn_1``, ``nn_2`` (int32) and ``sim_1`` (float32) [n, T] of the last servo call; after ``compute_velocity_host`` they
         come from host memory (the handle's pinned block), no device call."""

@@ -48,6 +48,9 @@ class UpdatePipeline:
             raise VitvsError("depth must be >= 1")
         if getattr(params, "law", "ibvs") == "homography":
             raise ValueError('UpdatePipeline slots run the image-based law: law="homography" is servo.Controller\'s (one handle, one camera)')
+        if getattr(params, "roll_search", False):
+            raise ValueError("UpdatePipeline slots run plain one-pair updates: roll_search is servo.Controller's (one handle with "
+                             "max_pairs >= 4 matches the four turned copies in one batch)")
         if getattr(params, "law", "ibvs") != "ibvs":
             raise ValueError('UpdatePipeline slots run the image-based law: law="pose" is servo.Controller\'s (one handle, one camera)')
         self.depth = int(depth)

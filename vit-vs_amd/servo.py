@@ -8,6 +8,7 @@ Same names, argument meaning and error behaviour as the reference's callables, w
   Controller.detect_features() / .ibvs()      reference: vitvs_v2.py:464-523, 588-632 (EMA :325-343, failure
                                               counter :500-505, twist remap :661-676)
   Controller.best_rotation(frames)            reference: find_and_set_best_pose, vitvs_v2.py:1151-1189
+  Controller.best_roll()                      the same question answered from ONE frame (the roll search)
   ServoLoop (vit-vs_amd/loop.py)              reference: Controller.run / is_visual_servoing_done, :702-819, :345-421
 
 All arithmetic of the path runs on the GPU through ``Engine`` (C ABI); what stays on the host is what the
@@ -248,6 +249,18 @@ class Controller:
                 raise ValueError('law="pose" needs goal_depth: the depth image taken at the goal pose')
             if self.params.interaction == "desired":
                 raise ValueError('law="pose" does not combine with interaction="desired" (its feature rows hold Z*, not Z)')
+        if self.params.roll_search:
+            # every update goes through the roll search (Engine.roll_velocity): the four quarter-turned copies of the
+            # current frame in one batch, so the handle needs room for four pairs; the draw must be the device's or an order / ids
+            if self.params.subpatch:
+                raise ValueError("roll_search does not combine with subpatch: the sub-patch offsets of a turned copy would have to be turned too")
+            if isinstance(selection, str) and selection == "reference":
+                raise ValueError('roll_search does not combine with selection="reference": the reference draws on the host between the '
+                                 'correspondence and the law, the roll search picks and carries back on the device in between')
+            if engine.max_pairs < 4:
+                raise ValueError(f"roll_search matches four turned copies in one batch: engine.max_pairs is {engine.max_pairs}, needs >= 4")
+        self.last_roll = None                             # roll_search: the winner k of the last update (-1: no valid candidate), and
+        self.last_roll_info = None                        # Engine.roll_velocity's info dict of it
         if goal_depth is not None:
             self.set_goal_depth(goal_depth)
         self.last_pose_status = None                      # law "pose": the pose law's status of the last update, and its
@@ -329,6 +342,8 @@ class Controller:
         The 10th consecutive failure raises RuntimeError("Persistent feature detection failure")."""
         if self.latest_image is None:
             return None, None
+        if self.params.roll_search:
+            return self._detect_features_rolled()
         cur, des = self._path_frames(self.latest_pil_image, self.goal_image)
         if not torch.is_tensor(des):
             # the goal image does not change from update to update (vitvs_v2.py:264): hand the library the SAME private buffer every
@@ -363,6 +378,48 @@ class Controller:
         if not self._absorb(v, st):
             return None, None
         return self._features(eng.last_features(1), 0)
+
+    def _square_frames(self, *imgs):
+        """The frames at S x S for the roll search: the engine's frame size is reset and every frame of another geometry goes
+        through the stand-alone resize launch on its own (``_resized``; a quarter turn needs the square frame in memory)."""
+        self.engine.set_frame_size()
+        return [self._resized(img) for img in imgs]
+
+    def _roll_call(self, num_pairs, depth):
+        """One ``Engine.roll_velocity`` on the latest frame with this controller's selection."""
+        eng = self.engine
+        cur, des = self._square_frames(self.latest_pil_image, self.goal_image)
+        z = depth if depth is not None else np.zeros((self.params.v_max, self.params.u_max), np.uint16)
+        if isinstance(self.selection, str) and self.selection == "order":
+            mode, sel = _lib.SELECT_ORDER, torch.randperm(eng.tokens, generator=self.generator).to(torch.int32)
+        elif isinstance(self.selection, str) and self.selection in ("dense", "best"):
+            mode, sel = (_lib.SELECT_DENSE if self.selection == "dense" else _lib.SELECT_BEST), None
+        else:
+            mode, sel = _lib.SELECT_EXPLICIT, [self.selection]
+        return eng.roll_velocity(cur, des, z, self.params.intrinsics(), mode, sel, num_pairs=num_pairs)
+
+    def _detect_features_rolled(self):
+        """``detect_features`` with ``params.roll_search``: the update through the roll search, then the configured law as ever."""
+        v, st, info = self._roll_call(self.num_pairs, self.latest_image_depth)
+        self.last_roll, self.last_roll_info = info["roll"], info
+        if not self._absorb(v.cpu().numpy(), int(st)):
+            return None, None
+        return self._features(self.engine.last_features(1), 0)
+
+    def best_roll(self):
+        """``(k, scores)`` for the latest frame: the quarter turn k (``numpy.rot90(frame, k)``) under which it matches the goal best,
+        and the four candidates' scores (None where a candidate is not valid); ``(None, scores)`` when none is.  It answers
+        ``best_rotation``'s question from ONE frame, without the robot moving (``Engine.roll_velocity``; needs ``max_pairs >= 4``).
+        The controller's own state (EMA, counters, ``last_roll``) is not touched."""
+        if self.latest_image is None:
+            raise ValueError("best_roll needs a frame: image_callback_rgb first")
+        if self.engine.max_pairs < 4:
+            raise ValueError(f"the roll search matches four turned copies in one batch: engine.max_pairs is {self.engine.max_pairs}, needs >= 4")
+        if isinstance(self.selection, str) and self.selection == "reference":
+            raise ValueError('best_roll draws on the device: selection "order", "dense", "best" or explicit ids')
+        _, _, info = self._roll_call(self.num_pairs, None)
+        scores = [None if np.isnan(s) else float(s) for s in info["scores"]]
+        return (info["roll"] if info["roll"] >= 0 else None), scores
 
     def _absorb(self, v, st) -> bool:
         """Bookkeeping of one finished update (whoever computed it: this controller's engine, or a ``MultiController``'s batched
@@ -533,6 +590,9 @@ class MultiController:
         self.engine = self.engines[0]
         self.law = (params or self.engine.params).law
         self._goal_depths, self._goal_depth_live = None, None
+        if (params or self.engine.params).roll_search:
+            raise ValueError("roll_search is servo.Controller's: a MultiController round is one batched call over the cameras, the roll "
+                             "search one call of four turned copies per camera")
         if self.law == "homography":
             raise ValueError('law="homography" is servo.Controller\'s: the homography law has no rig form (one camera, one plane)')
         if self.law == "pose":
