@@ -419,6 +419,23 @@ VITVS_API int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double
                                   double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info, double* weights,
                                   double* sigma);
 
+/* The pose law with a consensus start ("The consensus start"): n_hyp three-point hypotheses, each the closed-form
+ * rigid displacement of 3 usable rows drawn from `seed` (an integer hash of (seed, j, usable rows): the same frames give the same
+ * twist), are scored in parallel with the truncated cost sum min(rho^2, T^2), T = 4.6851 sigma_min; the rows within T of the winner
+ * start at weight 1 and the others at 0, and the law goes on from there as above (n_iter = 0: the alignment of the consensus set
+ * alone, the setting for more than half of wrong matches).  When every hypothesis is degenerate the start is the one without
+ * consensus.  pose_info[6] = the winner's j + 1 (0: no consensus start), pose_info[7] = the start weights at 1; pose_info[3]
+ * counts the rows the consensus start left out as weights of 0.  n_hyp is 0 .. 4096; 0 is vitvs_pose_velocity_dev bit for bit.
+ * Still one launch.  Returns as vitvs_pose_velocity_dev, and -2 also for n_hyp outside its range; -3 counts half a double per
+ * feature row more of LDS (one and a half with n_iter = 0). */
+VITVS_API int vitvs_pose_consensus_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status,
+                                                int32_t n_iter, int32_t n_hyp, uint32_t seed, double* v_pose, int32_t* pose_status,
+                                                double* pose, int32_t* pose_info, double* weights, double* sigma, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous. */
+VITVS_API int vitvs_pose_consensus_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter,
+                                            int32_t n_hyp, uint32_t seed, double* v_pose, int32_t* pose_status, double* pose,
+                                            int32_t* pose_info, double* weights, double* sigma);
+
 /* --- the homography law --------------------------------------------------------------------------
  * A law for a planar target that needs no depth at all (Benhimane and Malis, "Homography-based 2D visual servoing",
  * IJRR 2007).  Every feature row k < info[1] of pair b whose token is selected (>= 0) gives a current normalised image point

@@ -155,6 +155,21 @@ VITVS_API int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld);   /* -2 
  * 0)), out[1] 1 for the robust instantiation, out[2] 1 when the launch opts in to more than 64 KiB.  Returns 0, -1 (out NULL),
  * -2 (max_rows < 1, n_iter outside 0 .. 16; out zeroed), -3 (out filled): more than 160 KiB of LDS. */
 VITVS_API int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out);
+/* vitvs_op_pose_law with the consensus start in front of its alignment loop (vitvs_pose_consensus_velocity_dev, include/vitvs.h):
+ * n_hyp 0 .. 4096 three-point hypotheses drawn from `seed`; n_hyp = 0 is vitvs_op_pose_law bit for bit.  The cut-off is T = 4.6851
+ * sigma_min.  pose_info[6] = the winner's j + 1 (0: n_hyp = 0, fewer than 3 usable rows, or every hypothesis skipped), pose_info[7]
+ * = the start weights at 1.  Returns as vitvs_op_pose_law, and -2 also for n_hyp outside 0 .. 4096 and for n_hyp > 0 with
+ * sigma_min <= 0. */
+VITVS_API int vitvs_op_pose_consensus_law(int32_t n_pairs, int32_t ld, const double* P, const double* Q, const int32_t* usable,
+                                          double lambda, int32_t n_iter, double sigma_min, void* scratch, double* v_pose,
+                                          int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma,
+                                          void* stream, int32_t n_hyp, uint32_t seed);
+/* The launch plan with the consensus start: out[0] the dynamic LDS bytes = 8 (320 + (n_iter > 0 ? 2 max_rows : n_hyp > 0 ? max_rows
+ * : 0) + (n_hyp > 0 ? 8 + (max_rows + 1) / 2 : 0)): the reduction cells (4 costs, 4 + 4 ints) and the usable rows as ints; without
+ * re-weightings the consensus form keeps the rows' Z* for the median behind its cut-off.  out[1] and out[2] as vitvs_op_pose_plan's,
+ * out[3] 1 for the consensus instantiation.  Returns 0, -1 (out NULL), -2 (as vitvs_op_pose_plan, or n_hyp outside 0 .. 4096; out
+ * zeroed), -3 (out filled): more than 160 KiB of LDS. */
+VITVS_API int vitvs_op_pose_consensus_plan(int32_t max_rows, int32_t n_iter, int32_t n_hyp, int32_t* out);
 /* The homography law's kernel (vitvs_homography_velocity_dev, include/vitvs.h) on caller-given points:
  *   m, ms    device double [n_pairs][ld][2]: current and goal normalised image points;  usable int32 [n_pairs][ld]: > 0 usable
  *   depth_scale > 0 and finite;  n_iter 0 .. 16;  sigma_min  the floor of the scale, given directly

@@ -6,7 +6,10 @@ Times are HIP event pairs on the stream around ONE call (what a control loop wai
 p10 / p90 over --reps calls after a warm-up, and around --burst calls back to back divided by their number (the event pair's own
 cost amortised).  --rounds repeats everything, so the run-to-run spread of a line shows in one output.
 
-    python tools/pose_times.py [--reps 200] [--rounds 3] [--burst 50] [--out profiles/pose_law.txt]
+--consensus M adds, behind every leg, the same leg with the consensus start of M three-point hypotheses
+(vitvs_op_pose_consensus_law, seed 0): the legs without it are the yardstick of the same run.
+
+    python tools/pose_times.py [--reps 200] [--rounds 3] [--burst 50] [--consensus 0] [--out profiles/pose_law.txt]
 """
 import argparse
 import ctypes as C
@@ -46,12 +49,13 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--burst", type=int, default=50)
+    ap.add_argument("--consensus", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_law.txt"))
     args = ap.parse_args()
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
-    lines = [f"pose law (vitvs_op_pose_law), {torch.cuda.get_device_name(dev)}; HIP event pairs, microseconds"]
+    lines = [f"pose law (vitvs_op_pose_consensus_law; consensus 0 is vitvs_op_pose_law), {torch.cuda.get_device_name(dev)}; HIP event pairs, microseconds"]
     print(lines[0])
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     for rnd in range(args.rounds):
@@ -64,9 +68,10 @@ def main():
             pose = torch.zeros((n, 12), dtype=torch.float64, device=dev)
             w = torch.zeros((n, rows), dtype=torch.float64, device=dev)
             sigma = torch.zeros(n, dtype=torch.float64, device=dev)
-            for n_iter in (0, 4):
-                call = lambda: lib.vitvs_op_pose_law(n, rows, p(P), p(Q), p(usable), 0.03, n_iter, 0.004, p(scratch), p(v), p(st),  # noqa: E731
-                                                     p(pose), p(info), p(w), p(sigma), C.c_void_p(stream.cuda_stream))
+            for n_iter, n_hyp in [(N, M) for N in (0, 4) for M in sorted({0, args.consensus})]:
+                call = lambda: lib.vitvs_op_pose_consensus_law(n, rows, p(P), p(Q), p(usable), 0.03, n_iter, 0.004, p(scratch), p(v),  # noqa: E731
+                                                               p(st), p(pose), p(info), p(w), p(sigma), C.c_void_p(stream.cuda_stream),
+                                                               n_hyp, 0)
                 with torch.cuda.stream(stream):
                     for _ in range(20):
                         assert call() == 0
@@ -88,9 +93,10 @@ def main():
                     burst = 1000 * a.elapsed_time(b) / args.burst
                 i0 = info.cpu().numpy()[0]
                 assert not st.cpu().numpy().any()
-                line = (f"round {rnd} {n} x {rows:4d} rows, N = {n_iter}: median {np.median(us):7.2f} us, mean {np.mean(us):7.2f}, p10 "
+                line = (f"round {rnd} {n} x {rows:4d} rows, N = {n_iter}, consensus {n_hyp:3d}: median {np.median(us):7.2f} us, mean {np.mean(us):7.2f}, p10 "
                         f"{np.percentile(us, 10):7.2f}, p90 {np.percentile(us, 90):7.2f} over {len(us)} calls; {burst:7.2f} us per call in a "
-                        f"burst of {args.burst}; pair 0: sweeps {int(i0[1])}, re-weightings {int(i0[2])}, zero weights {int(i0[3])}")
+                        f"burst of {args.burst}; pair 0: sweeps {int(i0[1])}, re-weightings {int(i0[2])}, zero weights {int(i0[3])}, winner {int(i0[6])}, "
+                        f"start weights {int(i0[7])}")
                 print(line, flush=True)
                 lines.append(line)
     if args.out:

@@ -69,6 +69,8 @@ PROTOTYPES = {
     "vitvs_rig_robust_velocity": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_velocity_dev": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_pose_velocity": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vitvs_pose_consensus_velocity_dev": (_I, [_P, _I, _P, _P, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_pose_consensus_velocity": (_I, [_P, _I, _P, _P, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "vitvs_homography_velocity_dev": (_I, [_P, _I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_homography_velocity": (_I, [_P, _I, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
     "vitvs_homography_consensus_velocity_dev": (_I, [_P, _I, _P, _P, C.c_double, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
@@ -118,6 +120,8 @@ PROTOTYPES = {
     "vitvs_op_pose_law": (_I, [_I, _I, _P, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_pose_scratch_bytes": (_I, [_I, _I]),
     "vitvs_op_pose_plan": (_I, [_I, _I, _P]),
+    "vitvs_op_pose_consensus_law": (_I, [_I, _I, _P, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_uint32]),
+    "vitvs_op_pose_consensus_plan": (_I, [_I, _I, _I, _P]),
     "vitvs_op_homography_law": (_I, [_I, _I, _P, _P, _P, C.c_double, C.c_double, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_homography_scratch_bytes": (_I, [_I, _I]),
     "vitvs_op_homography_plan": (_I, [_I, _I, _P]),

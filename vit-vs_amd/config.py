@@ -191,6 +191,11 @@ class ServoParams:
                                    # "pose": the pose law on the matched 3-D points (Engine.pose_velocity), which needs a goal depth, or
                                    # "homography": the homography law of a planar target (Engine.homography_velocity): RGB only
     pose_robust_iterations: int = 0  # Tukey re-weightings of the pose law (0 .. 16); 0 = the plain alignment
+    pose_consensus: int = 0        # three-point hypotheses of the pose law's consensus start (0 .. 4096): the law starts
+                                   # from the rows that agree with the best of them instead of from all rows; 0 = no such start.
+                                   # 256 fills one round of the kernel's workgroup.  Past one half of wrong matches run it with
+                                   # pose_robust_iterations = 0: the re-weightings' scale is a median over all rows
+    pose_consensus_seed: int = 0   # of the hypotheses' draw (0 .. 2^32 - 1); fixed across updates: same frames, same twist
     rig_pose_robust_iterations: int = 0  # Tukey re-weightings of the pose RIG law (MultiController(rig=..., law "pose"): one median
                                          # over all cameras' 3-D residuals, vitvs_pose_rig_velocity_dev; 0 .. 16); 0 = the plain one
 
@@ -219,6 +224,10 @@ class ServoParams:
             raise ValueError(f"law is one of {LAWS}, got {self.law!r}")
         if not 0 <= int(self.pose_robust_iterations) <= 16:
             raise ValueError(f"pose_robust_iterations is 0 .. 16, got {self.pose_robust_iterations!r}")
+        if not 0 <= int(self.pose_consensus) <= 4096:
+            raise ValueError(f"pose_consensus is 0 .. 4096, got {self.pose_consensus!r}")
+        if not 0 <= int(self.pose_consensus_seed) <= 0xFFFFFFFF:
+            raise ValueError(f"pose_consensus_seed is 0 .. 2^32 - 1, got {self.pose_consensus_seed!r}")
         if not 0 <= int(self.homography_robust_iterations) <= 16:
             raise ValueError(f"homography_robust_iterations is 0 .. 16, got {self.homography_robust_iterations!r}")
         if not (float(self.homography_depth) > 0.0 and math.isfinite(float(self.homography_depth))):
@@ -291,7 +300,8 @@ def load_reference_config(source) -> ReferenceConfig:
     sub-patch refinement of the matches) likewise, else False; ``interaction`` (which interaction matrix the law inverts) likewise,
     else "current"; ``law`` ("ibvs" / "pose" / "homography"), ``pose_robust_iterations`` and ``rig_pose_robust_iterations`` likewise,
     else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``homography_consensus`` and
-    ``homography_consensus_seed`` likewise, else 0 and 0; ``select_cells`` (the cell grid of selection "best") likewise, else 4;
+    ``homography_consensus_seed`` likewise, else 0 and 0; ``pose_consensus`` and ``pose_consensus_seed`` likewise, else 0 and 0;
+    ``select_cells`` (the cell grid of selection "best") likewise, else 4;
     ``roll_search`` (the roll search in front of every update) likewise, else False."""
     if isinstance(source, dict):
         cfg = dict(source)
@@ -312,6 +322,8 @@ def load_reference_config(source) -> ReferenceConfig:
                         interaction=str(cfg.get("interaction", "current")),
                         rig_robust_iterations=int(cfg.get("rig_robust_iterations", 0)), law=str(cfg.get("law", "ibvs")),
                         pose_robust_iterations=int(cfg.get("pose_robust_iterations", 0)),
+                        pose_consensus=int(cfg.get("pose_consensus", 0)),
+                        pose_consensus_seed=int(cfg.get("pose_consensus_seed", 0)),
                         rig_pose_robust_iterations=int(cfg.get("rig_pose_robust_iterations", 0)),
                         homography_robust_iterations=int(cfg.get("homography_robust_iterations", 0)),
                         homography_depth=float(cfg.get("homography_depth", 1.0)),
@@ -322,7 +334,7 @@ def load_reference_config(source) -> ReferenceConfig:
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
-            "homography_consensus", "homography_consensus_seed", "select_cells"}
+            "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -1823,8 +1823,9 @@ int vitvs_rig_robust_velocity(vitvs_handle* h, int32_t n_cams, const double* cVr
 }
 
 // --- the pose law --------------------------------------------------------------------------------
-static int pose_prepare(vitvs_handle* h, int n_pairs, int n_iter) {
+static int pose_prepare(vitvs_handle* h, int n_pairs, int n_iter, int n_hyp = 0) {
     if (n_iter < 0 || n_iter > 16) return set_err(h, -2, "n_iter is 0 .. 16");
+    if (n_hyp < 0 || n_hyp > 4096) return set_err(h, -2, "n_hyp is 0 .. 4096");
     if (int rc = follows_velocity_call(h, "vitvs_pose_velocity", "n_pairs", n_pairs)) return rc;
     if (!h->n_goal_depth) return set_err(h, -5, "the pose law needs a goal depth (vitvs_set_goal_depth_dev)");
     if (h->last_T != h->T) return set_err(h, -5, "the goal depth table is laid out for the handle's own token grid");
@@ -1834,37 +1835,53 @@ static int pose_prepare(vitvs_handle* h, int n_pairs, int n_iter) {
         return set_err(h, -5, "the pose law needs the current depth: with option interaction at 1 the feature rows hold Z*, not Z");
     const vitvs_config& c = h->cfg;
     PosePlan pl;
-    if (plan_pose(c.max_rows, n_iter, &pl))
-        return set_err(h, -3, "the robust pose law keeps two doubles per feature row in LDS: max_rows is too large");
+    if (plan_pose(c.max_rows, n_iter, n_hyp, &pl))
+        return set_err(h, -3, "the robust pose law keeps two doubles per feature row in LDS, its consensus start half a double more (one "
+                              "and a half without re-weightings): max_rows is too large");
     PoseIo io = pose_io(c.max_pairs, c.max_rows);
     return law_blocks(h, "pose", &h->pose_ws, pose_scratch_bytes(c.max_pairs, c.max_rows), &h->pose_io, io_place(io_list(io), nullptr));
 }
 
-int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
-                            int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma, void* stream) {
+int vitvs_pose_consensus_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter,
+                                      int32_t n_hyp, uint32_t seed, double* v_pose, int32_t* pose_status, double* pose,
+                                      int32_t* pose_info, double* weights, double* sigma, void* stream) {
     if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
-    if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
+    if (int rc = pose_prepare(h, n_pairs, n_iter, n_hyp)) return rc;
     PoseArgs a;
     memset(&a, 0, sizeof(a));
     a.n_pairs = n_pairs; a.ld = h->cfg.max_rows; a.status = status; a.ws = reinterpret_cast<double*>(h->pose_ws);
     camera_law_state(h, K, n_iter, a);
     goal_depth_state(h, a);
+    a.n_hyp = n_hyp; a.seed = seed;
     a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info; a.weights = weights; a.sigma = sigma;
     const int rc = launch_pose(a, dev_stream(h, stream));
     return rc ? set_err(h, rc, "pose law launch failed") : 0;
 }
 
-int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
-                        int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma) {
+int vitvs_pose_velocity_dev(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
+                            int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma, void* stream) {
+    return vitvs_pose_consensus_velocity_dev(h, n_pairs, K, status, n_iter, 0, 0, v_pose, pose_status, pose, pose_info, weights, sigma,
+                                             stream);
+}
+
+int vitvs_pose_consensus_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter,
+                                  int32_t n_hyp, uint32_t seed, double* v_pose, int32_t* pose_status, double* pose, int32_t* pose_info,
+                                  double* weights, double* sigma) {
     if (!h || !K || !status || !v_pose || !pose_status) return set_err(h, -1, "null argument");
     DeviceScope dev(h);
-    if (int rc = pose_prepare(h, n_pairs, n_iter)) return rc;
+    if (int rc = pose_prepare(h, n_pairs, n_iter, n_hyp)) return rc;
     PoseIo io = pose_io(h->cfg.max_pairs, h->cfg.max_rows, n_pairs, K, status, v_pose, pose_status, pose, pose_info, weights, sigma);
     return host_call(h, io_list(io), h->pose_io, [&](hipStream_t st) {
-        return vitvs_pose_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), n_iter, io.v_pose.f64(), io.pose_status.i32(),
-                                       io.pose.f64(), io.pose_info.i32(), io.weights.f64(), io.sigma.f64(), st);
+        return vitvs_pose_consensus_velocity_dev(h, n_pairs, io.K.f64(), io.status.i32(), n_iter, n_hyp, seed, io.v_pose.f64(),
+                                                 io.pose_status.i32(), io.pose.f64(), io.pose_info.i32(), io.weights.f64(),
+                                                 io.sigma.f64(), st);
     });
+}
+
+int vitvs_pose_velocity(vitvs_handle* h, int32_t n_pairs, const double* K, const int32_t* status, int32_t n_iter, double* v_pose,
+                        int32_t* pose_status, double* pose, int32_t* pose_info, double* weights, double* sigma) {
+    return vitvs_pose_consensus_velocity(h, n_pairs, K, status, n_iter, 0, 0, v_pose, pose_status, pose, pose_info, weights, sigma);
 }
 
 // --- the homography law --------------------------------------------------------------------------
@@ -2242,18 +2259,26 @@ int vitvs_op_rig_robust_plan(int32_t n_cams, int32_t ld, int32_t* out) {
     return rc;
 }
 
-int vitvs_op_pose_law(int32_t n_pairs, int32_t ld, const double* P, const double* Q, const int32_t* usable, double lambda,
-                      int32_t n_iter, double sigma_min, void* scratch, double* v_pose, int32_t* pose_status, double* pose,
-                      int32_t* pose_info, double* weights, double* sigma, void* stream) {
+int vitvs_op_pose_consensus_law(int32_t n_pairs, int32_t ld, const double* P, const double* Q, const int32_t* usable, double lambda,
+                                int32_t n_iter, double sigma_min, void* scratch, double* v_pose, int32_t* pose_status, double* pose,
+                                int32_t* pose_info, double* weights, double* sigma, void* stream, int32_t n_hyp, uint32_t seed) {
     if (!P || !Q || !usable || !scratch || !v_pose || !pose_status) return -1;
     if (n_pairs < 1 || ld < 1 || n_iter < 0 || n_iter > 16) return -2;
+    if (n_hyp < 0 || n_hyp > 4096 || (n_hyp > 0 && !(sigma_min > 0.0))) return -2;
     PoseArgs a;
     memset(&a, 0, sizeof(a));
     a.n_pairs = n_pairs; a.ld = ld; a.P = P; a.Q = Q; a.usable = usable; a.lambda = lambda; a.n_iter = n_iter;
-    a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch);
+    a.sigma_min = sigma_min; a.ws = static_cast<double*>(scratch); a.n_hyp = n_hyp; a.seed = seed;
     a.v_pose = v_pose; a.pose_status = pose_status; a.pose = pose; a.pose_info = pose_info;
     a.weights = weights; a.weights_stride = ld; a.sigma = sigma;
     return launch_pose(a, as_stream(stream));
+}
+
+int vitvs_op_pose_law(int32_t n_pairs, int32_t ld, const double* P, const double* Q, const int32_t* usable, double lambda,
+                      int32_t n_iter, double sigma_min, void* scratch, double* v_pose, int32_t* pose_status, double* pose,
+                      int32_t* pose_info, double* weights, double* sigma, void* stream) {
+    return vitvs_op_pose_consensus_law(n_pairs, ld, P, Q, usable, lambda, n_iter, sigma_min, scratch, v_pose, pose_status, pose,
+                                       pose_info, weights, sigma, stream, 0, 0);
 }
 
 int vitvs_op_pose_scratch_bytes(int32_t n_pairs, int32_t ld) {
@@ -2264,7 +2289,16 @@ int vitvs_op_pose_plan(int32_t max_rows, int32_t n_iter, int32_t* out) {
     if (!out) return -1;
     PosePlan pl;
     memset(&pl, 0, sizeof(pl));
-    return plan_out(plan_pose(max_rows, n_iter, &pl), pl, out);
+    return plan_out(plan_pose(max_rows, n_iter, 0, &pl), pl, out);
+}
+
+int vitvs_op_pose_consensus_plan(int32_t max_rows, int32_t n_iter, int32_t n_hyp, int32_t* out) {
+    if (!out) return -1;
+    PosePlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_out(plan_pose(max_rows, n_iter, n_hyp, &pl), pl, out);
+    out[3] = pl.consensus;
+    return rc;
 }
 
 int vitvs_op_pose_rig_law(int32_t n_cams, int32_t ld, const double* P, const double* Q, const int32_t* usable, const double* rTc,

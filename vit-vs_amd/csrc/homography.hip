@@ -160,32 +160,9 @@ __device__ __forceinline__ bool hom_solve(double* sm, int lane, int& sweeps) {
 
 // ---- the consensus start ("The consensus start"); tests/homography_consensus_ref.py restates every line below in
 // the same order of arithmetic
-__device__ __forceinline__ unsigned hom_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// The 4 distinct positions of hypothesis j in a list of n_us usable rows, ascending (a row set gives one H whatever the order it was
-// drawn in): r_c = mix(mix(seed 0x9e3779b9 + j) + c) mod n_us for c = 0 .. 63, repeats rejected; false when 64 draws do not give 4.
-__device__ __forceinline__ bool hom_draw(unsigned seed, int j, int n_us, int* pos) {
-    const unsigned base = hom_mix(seed * 0x9e3779b9u + (unsigned)j);
-    int p0 = -1, p1 = -1, p2 = -1, p3 = -1, cnt = 0;
-    for (unsigned c = 0; c < 64u && cnt < 4; ++c) {
-        const int r = (int)(hom_mix(base + c) % (unsigned)n_us);
-        if (r == p0 || r == p1 || r == p2 || r == p3) continue;
-        if (cnt == 0) p0 = r; else if (cnt == 1) p1 = r; else if (cnt == 2) p2 = r; else p3 = r;
-        ++cnt;
-    }
-    if (cnt < 4) return false;
-    int t;
-#define HOM_CSWAP(a, b) if (b < a) { t = a; a = b; b = t; }
-    HOM_CSWAP(p0, p1) HOM_CSWAP(p2, p3) HOM_CSWAP(p0, p2) HOM_CSWAP(p1, p3) HOM_CSWAP(p1, p2)
-#undef HOM_CSWAP
-    pos[0] = p0; pos[1] = p1; pos[2] = p2; pos[3] = p3;
-    return true;
-}
+// The 4 distinct positions of hypothesis j in a list of n_us usable rows, ascending: robust_core.h's draw, which the pose law's
+// three-point hypotheses share
+__device__ __forceinline__ bool hom_draw(unsigned seed, int j, int n_us, int* pos) { return consensus_draw<4>(seed, j, n_us, pos); }
 
 // B = A diag(adj(A) (x3, y3, 1)), A with the columns (x_i, y_i, 1), i = 0 .. 2: the map of the projective basis onto four points.
 // The l_i and their sum (det A) are twice the signed areas of the four triangles of the points: false when one of them is <= 1e-8

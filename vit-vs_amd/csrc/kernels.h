@@ -465,7 +465,8 @@ int launch_rig_robust(const RigRobustArgs& a, hipStream_t stream);
 // The pose law: per pair ONE rigid displacement (R, t), X_goal = R X_cam + t, aligning the current 3-D points of
 // the feature rows with their goal points (Horn's quaternion form), and v_pose = -lambda (R^T t, theta u).  One launch, one
 // workgroup per pair.  The points come from what the camera's law left (selected, s_uv, feat, info, the goal-depth table) or,
-// for the seam tests, from the caller (P, Q, usable).
+// for the seam tests, from the caller (P, Q, usable).  n_hyp > 0: the consensus start, n_hyp three-point hypotheses scored in parallel
+// in front of the alignment loop, which then starts from the winner's consensus set instead of every usable row.
 struct PoseArgs {
     int n_pairs;
     int ld;                   // rows per pair of every per-row array (max_rows)
@@ -491,18 +492,25 @@ struct PoseArgs {
     double* v_pose;           // [n_pairs][6]
     int32_t* pose_status;     // [n_pairs] the camera's status when that is not ST_OK; ST_TOO_FEW: < 3 rows with a weight, or degenerate
     double* pose;             // [n_pairs][12] or null: R row-major, t (identity when the status is not ST_OK)
-    int32_t* pose_info;       // [n_pairs][8] or null: usable rows, sweeps, re-weightings, usable rows at weight 0, degenerate, holes, 0, 0
+    int32_t* pose_info;       // [n_pairs][8] or null: usable rows, sweeps, re-weightings, usable rows at weight 0, degenerate, holes,
+                              // the consensus winner's j + 1 (0: consensus off, not run for fewer than 3 usable rows, or every
+                              // hypothesis skipped), the start weights at 1 (0 where the phase did not run)
     double* weights;          // [n_pairs][weights_stride] or null
     int weights_stride;
     double* sigma;            // [n_pairs] or null: the last scale
+    // the consensus start (behind everything the kernel read before it had one)
+    int n_hyp;                // hypotheses, 0 .. 4096; 0: no consensus phase, the kernel is the one without it
+    unsigned seed;            // of the draw; the positions depend on (seed, j, usable rows) only
 };
 struct PosePlan {
-    size_t lds;               // dynamic LDS of the launch
-    bool robust;              // pose_kernel<robust>
+    size_t lds;               // dynamic LDS of the launch: (320 + (robust ? 2 max_rows : consensus ? max_rows : 0) +
+                              // (consensus ? 8 + (max_rows + 1) / 2 : 0)) doubles
+    bool robust;              // pose_kernel<robust, consensus>
     bool lds_opt_in;          // > 64 KiB
+    bool consensus;
 };
-// -2: max_rows < 1, n_iter outside 0 .. 16; -3 (plan filled): more than 160 KiB of LDS
-int plan_pose(int max_rows, int n_iter, PosePlan* plan);
+// -2: max_rows < 1, n_iter outside 0 .. 16, n_hyp outside 0 .. 4096; -3 (plan filled): more than 160 KiB of LDS
+int plan_pose(int max_rows, int n_iter, int n_hyp, PosePlan* plan);
 size_t pose_scratch_bytes(int n_pairs, int ld);
 int launch_pose(const PoseArgs& a, hipStream_t stream);
 

@@ -12,7 +12,9 @@
 // bit-reproducible.  Wave 0 then solves, every lane the same arithmetic: a cyclic Jacobi eigen-decomposition of the 4 x 4 matrix
 // in fp64, all indices compile-time (no scratch).  ROBUST: n_iter Tukey re-weightings with rho and w in dynamic LDS (median_middles
 // and tukey_reweight of robust_core.h), one more solve behind the last.  The loop is pose_core.h's pose_align, which the pose rig
-// law runs too; this file keeps the early outs, Phase A, sigma_min and the outputs.
+// law runs too; this file keeps the early outs, Phase A, sigma_min and the outputs.  CONSENSUS: a phase between Phase A and the
+// loop scores n_hyp three-point hypotheses, one per thread and round, and starts the loop from the winner's consensus set
+// (pose_core.h's pose_consensus); the plain form then takes the median of Z* too, for the cut-off T = 4.6851 sigma_min.
 #include "common.h"
 #include "kernels.h"
 #include "pose_core.h"
@@ -21,7 +23,7 @@
 
 namespace vitvs {
 
-template <bool ROBUST>
+template <bool ROBUST, bool CONSENSUS>
 __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smp[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -89,10 +91,10 @@ __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
     const double* flag = ws + (size_t)6 * ld;
 
     double sigma_min = a.sigma_min;
-    if constexpr (ROBUST) {
+    if constexpr (ROBUST || CONSENSUS) {                    // (the plain form with a consensus start: rho alone, for the cut-off T)
         for (int k = tid; k < n; k += 256) {
             const bool us = flag[k] > 0.0;
-            wk[k] = us ? 1.0 : 0.0;
+            if constexpr (ROBUST) wk[k] = us ? 1.0 : 0.0;
             rho[k] = us ? ws[(size_t)5 * ld + k] : __longlong_as_double((long long)kInfBits);   // Z* for sigma_min's median
         }
         if (a.K && n_us > 0) {
@@ -104,8 +106,18 @@ __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
         lds_barrier();
     }
 
+    // the consensus start: the winner's j + 1, the rows that start at weight 1, the usable rows that start at 0
+    int winner = 0, n_start = 0, n_zero0 = 0;
+    if constexpr (CONSENSUS) {
+        if (n_us >= 3) {
+            winner = pose_consensus<ROBUST>(ws, ld, n, n_us, a.n_hyp, a.seed, 4.6851 * sigma_min, rho + (ROBUST ? 2 : 1) * (size_t)ld,
+                                            ROBUST ? wk : ws + (size_t)6 * ld, n_start);
+            if (winner) n_zero0 = n_us - n_start;
+        }
+    }
+
     PoseFit fit;
-    pose_align<ROBUST>(ws, ld, n, n_us, sigma_min, a.n_iter, smp, rho, wk, fit);
+    pose_align<ROBUST>(ws, ld, n, n_us, sigma_min, a.n_iter, smp, rho, wk, fit, n_zero0);
 
     if (a.weights) {
         for (int k = tid; k < a.weights_stride; k += 256) {
@@ -131,14 +143,18 @@ __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
     if (a.pose_info) {
         int32_t* pi = a.pose_info + (size_t)b * 8;
         pi[0] = n_us; pi[1] = fit.sweeps; pi[2] = fit.reweighted; pi[3] = fit.n_zero; pi[4] = fit.degenerate; pi[5] = holes;
-        pi[6] = 0; pi[7] = 0;
+        pi[6] = winner; pi[7] = n_start;
     }
 }
 
-int plan_pose(int max_rows, int n_iter, PosePlan* plan) {
-    if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16) return -2;
+int plan_pose(int max_rows, int n_iter, int n_hyp, PosePlan* plan) {
+    if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16 || n_hyp < 0 || n_hyp > 4096) return -2;
     plan->robust = n_iter > 0;
-    plan->lds = ((size_t)kPoseHead + (plan->robust ? (size_t)2 * max_rows : 0)) * sizeof(double);
+    plan->consensus = n_hyp > 0;
+    // rho and w of the robust form; the plain form with a consensus start keeps rho alone, for the median of Z* behind its cut-off
+    const size_t per_row = plan->robust ? 2 : (plan->consensus ? 1 : 0);
+    plan->lds = ((size_t)kPoseHead + per_row * max_rows + (plan->consensus ? (size_t)kPoseCons + ((size_t)max_rows + 1) / 2 : 0)) *
+                sizeof(double);
     plan->lds_opt_in = plan->lds > 64 * 1024;
     return plan->lds > 160 * 1024 ? -3 : 0;
 }
@@ -149,13 +165,20 @@ int launch_pose(const PoseArgs& a, hipStream_t stream) {
     if (a.n_pairs < 1 || a.ld < 1 || !a.ws || !a.v_pose || !a.pose_status || (a.weights && a.weights_stride < 0)) return -2;
     if (a.P ? (!a.Q || !a.usable) : (!a.selected || !a.s_uv || !a.feat || !a.info || !a.K || !a.zgoal || a.T < 1)) return -2;
     PosePlan p;
-    if (int rc = plan_pose(a.ld, a.n_iter, &p)) return rc;
-    static std::atomic<unsigned long long> raised{0};
-    if (p.robust) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true>), 160 * 1024, raised)) return -3;
-        launch(pose_kernel<true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    if (int rc = plan_pose(a.ld, a.n_iter, a.n_hyp, &p)) return rc;
+    if (p.consensus && !a.K && !(a.sigma_min > 0.0)) return -2;      // the cut-off T = 4.6851 sigma_min has to be positive
+    static std::atomic<unsigned long long> raised{0}, raised_rc{0}, raised_c{0};
+    if (p.robust && p.consensus) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true, true>), 160 * 1024, raised_rc)) return -3;
+        launch(pose_kernel<true, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    } else if (p.consensus) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<false, true>), 160 * 1024, raised_c)) return -3;
+        launch(pose_kernel<false, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    } else if (p.robust) {
+        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true, false>), 160 * 1024, raised)) return -3;
+        launch(pose_kernel<true, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
     } else {
-        launch(pose_kernel<false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+        launch(pose_kernel<false, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

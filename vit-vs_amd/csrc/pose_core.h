@@ -137,14 +137,17 @@ struct PoseFit {
 // (LDS) holds the caller's first weights on entry and the last ones on return; rho (LDS) holds +inf in every row that is not usable.
 // Every barrier here orders LDS only (lds_barrier): the loop writes nothing but LDS (smp, rho, wk).  The point block is global
 // memory, but the caller wrote it before the __syncthreads() that follows its Phase A, and the loop only reads it.
+// A consensus start (pose_consensus below) hands over its weights where the loop reads them (wk, or the flag row in the plain form)
+// and n_zero0, the usable rows it left at weight 0.
 template <bool ROBUST>
 __device__ __forceinline__ void pose_align(const double* ws, int stride, int n, int n_us, double sigma_min, int n_iter, double* smp,
-                                           double* rho, double* wk, PoseFit& fit) {
+                                           double* rho, double* wk, PoseFit& fit, int n_zero0 = 0) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qid = tid & 31, slice = tid >> 5;
     const double* flag = ws + (size_t)6 * stride;
     int* iscr = reinterpret_cast<int*>(smp + kPoseInt);
     fit = PoseFit{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}, {1, 0, 0, 0}, ST_OK, 0, 0, 0, 0, 0.0};
+    fit.n_zero = n_zero0;
     const int N = ROBUST ? n_iter : 0;
     for (int it = 0;; ++it) {
         if (n_us - fit.n_zero < 3) { fit.status = ST_TOO_FEW; break; }
@@ -252,6 +255,156 @@ __device__ __forceinline__ void pose_twist(double lambda, const PoseFit& fit, do
         v[i] = -lambda * ((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
         v[3 + i] = -lambda * (f * q[1 + i]);
     }
+}
+
+// ---- the consensus start ("The consensus start"); tests/pose_consensus_ref.py restates every line below in the same
+// order of arithmetic.  Behind the law's dynamic LDS: the waves' best costs [4], as ints their best j [4] and their start weights
+// at 1 [4] | as ints the usable rows in ascending order [rows, rounded up to even]
+constexpr int kPoseCons = 8;             // doubles of the consensus cells in front of the usable-row list
+
+// The orthonormal triad of three points: e1 along x1 - x0, e3 along the normal of their plane, e2 = e3 x e1 (rows of e).  False when
+// the points are collinear or coincide: |a x b|^2 <= 1e-8 |a|^2 |b|^2.
+__device__ __forceinline__ bool pose_triad(const double (&x)[3][3], double (&e)[3][3]) {
+    double a[3], b[3], n[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a[c] = x[1][c] - x[0][c]; b[c] = x[2][c] - x[0][c]; }
+    n[0] = a[1] * b[2] - a[2] * b[1];
+    n[1] = a[2] * b[0] - a[0] * b[2];
+    n[2] = a[0] * b[1] - a[1] * b[0];
+    const double aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    const double bb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    const double sa = sqrt(aa), sn = sqrt(nn);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { e[0][c] = a[c] / sa; e[2][c] = n[c] / sn; }
+    e[1][0] = e[2][1] * e[0][2] - e[2][2] * e[0][1];
+    e[1][1] = e[2][2] * e[0][0] - e[2][0] * e[0][2];
+    e[1][2] = e[2][0] * e[0][1] - e[2][1] * e[0][0];
+    return nn > (1e-8 * aa) * bb;
+}
+
+// The rigid displacement of the three rows `rows` in closed form: R carries the triad of the current points onto that of the goal
+// points, t = qm - R pm with the means of the three.  False when either triple is collinear or an entry is not finite.
+__device__ __forceinline__ bool pose_three_point(const double* ws, int stride, const int* rows, double (&R)[9], double (&t)[3]) {
+    double p[3][3], g[3][3], ep[3][3], eg[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            p[i][c] = ws[(size_t)c * stride + rows[i]];
+            g[i][c] = ws[(size_t)(3 + c) * stride + rows[i]];
+        }
+    const bool spread = pose_triad(p, ep), spread_g = pose_triad(g, eg);
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            R[3 * i + j] = (eg[0][i] * ep[0][j] + eg[1][i] * ep[1][j]) + eg[2][i] * ep[2][j];
+            finite = finite && fabs(R[3 * i + j]) < __builtin_huge_val();
+        }
+    double pm[3], gm[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        pm[c] = ((p[0][c] + p[1][c]) + p[2][c]) / 3.0;
+        gm[c] = ((g[0][c] + g[1][c]) + g[2][c]) / 3.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        t[i] = gm[i] - ((R[3 * i] * pm[0] + R[3 * i + 1] * pm[1]) + R[3 * i + 2] * pm[2]);
+        finite = finite && fabs(t[i]) < __builtin_huge_val();
+    }
+    return spread && spread_g && finite;
+}
+
+// |Q_r - (R P_r + t)|^2 in pose_align's own residual arithmetic, before its square root
+__device__ __forceinline__ double pose_residual_sq(const double (&R)[9], const double (&t)[3], const double* ws, int stride, int r) {
+    const double p0 = ws[r], p1 = ws[(size_t)stride + r], p2 = ws[(size_t)2 * stride + r];
+    const double d0 = ws[(size_t)3 * stride + r] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
+    const double d1 = ws[(size_t)4 * stride + r] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
+    const double d2 = ws[(size_t)5 * stride + r] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
+    return (d0 * d0 + d1 * d1) + d2 * d2;
+}
+
+// The consensus phase, all 256 threads, behind Phase A's barrier and with n_us >= 3.  Wave 0 compacts the usable rows of [0, n) into
+// an ascending list.  Thread t scores the hypotheses t, t + 256, .. with the truncated cost C_j = sum over the usable rows, ascending,
+// of min(q, T^2) (a skipped hypothesis costs +inf) and keeps its best (cost, j) in registers; costs are >= +0, so (cost bits, j)
+// orders by integer compares and ties go to the smallest j.  One reduction: a butterfly within each wave, then 4 cells in LDS.
+// Every thread then solves the winner again and the start weights are 1 where sqrt(q) <= T and 0 elsewhere, into `start` (LDS for
+// the robust form, the flags' row of the workspace for the plain one: there a usable row at weight 0 reads as an unusable one).
+// Returns the winner's j + 1 and the number of start weights at 1, or 0 and n_us when every hypothesis was skipped (nothing is
+// written: the start without consensus).  The last barrier is the phase's own.
+template <bool ROBUST>
+__device__ __forceinline__ int pose_consensus(const double* ws, int stride, int n, int n_us, int n_hyp, unsigned seed, double T,
+                                              double* cons, double* start, int& n_start) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long* cell_cost = reinterpret_cast<unsigned long long*>(cons);
+    int* cell_j = reinterpret_cast<int*>(cons + 4);
+    int* cell_ones = cell_j + 4;
+    int* list = reinterpret_cast<int*>(cons + kPoseCons);
+    const double* flag = ws + (size_t)6 * stride;
+    if (wave == 0) {                                        // the usable rows in ascending order: wave 0, 64 rows a step
+        int base = 0;
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int k = k0 + lane;
+            const bool f = k < n && flag[k] > 0.0;
+            const unsigned long long bal = __ballot(f);
+            if (f) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = k;
+            base += __popcll(bal);
+        }
+    }
+    lds_barrier();
+    const double T2 = T * T;
+    unsigned long long best = kInfBits;
+    int best_j = 0x7fffffff;
+    for (int j = tid; j < n_hyp; j += 256) {
+        int pos[3], rows[3];
+        double R[9], t[3];
+        if (!consensus_draw<3>(seed, j, n_us, pos)) continue;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rows[i] = list[pos[i]];
+        if (!pose_three_point(ws, stride, rows, R, t)) continue;
+        double cost = 0.0;
+        for (int p = 0; p < n_us; ++p) {                    // (every lane reads the same row: one broadcast load per point)
+            const double q = pose_residual_sq(R, t, ws, stride, list[p]);
+            cost += q < T2 ? q : T2;
+        }
+        const unsigned long long key = (unsigned long long)__double_as_longlong(cost);
+        if (key < best) { best = key; best_j = j; }         // (j ascends: a tie keeps the smaller one)
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long oc = shfl_xor_u64(best, o);
+        const int oj = __shfl_xor(best_j, o, WAVE);
+        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
+    }
+    if (lane == 0) { cell_cost[wave] = best; cell_j[wave] = best_j; }
+    lds_barrier();
+    best = cell_cost[0]; best_j = cell_j[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const unsigned long long oc = cell_cost[w];
+        const int oj = cell_j[w];
+        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
+    }
+    if (best >= kInfBits) { n_start = n_us; return 0; }     // every hypothesis skipped: the same for every thread
+    int pos[3], rows[3], ones = 0;
+    double R[9], t[3];
+    consensus_draw<3>(seed, best_j, n_us, pos);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) rows[i] = list[pos[i]];
+    pose_three_point(ws, stride, rows, R, t);
+    for (int k = tid; k < n; k += 256) {
+        if (!(flag[k] > 0.0)) continue;
+        const double w1 = sqrt(pose_residual_sq(R, t, ws, stride, k)) <= T ? 1.0 : 0.0;
+        start[k] = w1;
+        ones += w1 > 0.0 ? 1 : 0;
+    }
+    ones = wave_sum(ones);
+    if (lane == 0) cell_ones[wave] = ones;
+    if constexpr (ROBUST) lds_barrier(); else __syncthreads();    // (the plain form's start weights are global memory: full fence)
+    n_start = cell_ones[0] + cell_ones[1] + cell_ones[2] + cell_ones[3];
+    return best_j + 1;
 }
 
 }  // namespace vitvs

@@ -698,27 +698,46 @@ class Engine:
 
     POSE_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "holes")
 
-    def _pose_law(self, host, K, status, robust_iterations):
-        N = self._robust_iterations(robust_iterations)
-        v, pst, pose, pinfo, weights, sigma = self._pair_law("vitvs_pose_velocity", host, K, status, (N,), 12)
-        return v, self._law_info(self.POSE_INFO_FIELDS, pinfo, True, status=pst, R=pose[:, :9].reshape(len(pst), 3, 3), t=pose[:, 9:],
-                                 weights=weights, sigma=sigma)
+    @staticmethod
+    def _consensus_arguments(consensus, seed):
+        """The checks of a consensus start's arguments (no handle needed)."""
+        M, s = int(consensus), int(seed)
+        if not 0 <= M <= 4096:
+            raise ValueError(f"consensus is 0 .. 4096 hypotheses, got {consensus!r}")
+        if not 0 <= s <= 0xFFFFFFFF:
+            raise ValueError(f"seed is 0 .. 2^32 - 1, got {seed!r}")
+        return M, s
 
-    def pose_velocity(self, K, status, robust_iterations: int = 0):
+    def _pose_law(self, host, K, status, robust_iterations, consensus=0, seed=0):
+        N = self._robust_iterations(robust_iterations)
+        M, s = self._consensus_arguments(consensus, seed)
+        if M:
+            v, pst, pose, pinfo, weights, sigma = self._pair_law("vitvs_pose_consensus_velocity", host, K, status, (N, M, s), 12)
+        else:
+            v, pst, pose, pinfo, weights, sigma = self._pair_law("vitvs_pose_velocity", host, K, status, (N,), 12)
+        return v, self._law_info(self.POSE_INFO_FIELDS, pinfo, True, status=pst, R=pose[:, :9].reshape(len(pst), 3, 3), t=pose[:, 9:],
+                                 weights=weights, sigma=sigma, winner=pinfo[:, 6], start_weights=pinfo[:, 7])
+
+    def pose_velocity(self, K, status, robust_iterations: int = 0, consensus: int = 0, seed: int = 0):
         """``vitvs_pose_velocity_dev``: the pose law of every pair of the last velocity call, from what that call left
         in the handle and the goal depth (``set_goal_depth``): one rigid alignment (R, t) of the matched 3-D points per pair,
         X_goal = R X_cam + t, and ``v_pose = -lambda (R^T t, theta u)``.  ``K``: the intrinsics of that call, [n, 4] or one (fx, fy, cx,
         cy) for all; ``status``: the int32 [n] it returned (a device tensor stays on the device); ``robust_iterations``: Tukey
         re-weightings, 0 .. 16.  Returns ``(v_pose float64 [n, 6] device tensor, info)``, ``info`` = dict of device tensors: ``status``
         int32 [n], ``R`` [n, 3, 3], ``t`` [n, 3], ``usable`` / ``sweeps`` / ``reweighted`` / ``zero_weights`` / ``degenerate`` /
-        ``holes`` int32 [n], ``weights`` float64 [n, max_rows], ``sigma`` float64 [n].  One launch on the current stream; nothing
-        synchronises after the first call (which allocates: make it outside a stream capture)."""
-        return self._pose_law(False, K, status, robust_iterations)
+        ``holes`` int32 [n], ``weights`` float64 [n, max_rows], ``sigma`` float64 [n].  ``consensus`` > 0
+        (``vitvs_pose_consensus_velocity_dev``): that many three-point hypotheses (0 .. 4096) drawn from ``seed`` are scored in front
+        of the alignment and the law starts from the rows that agree with the best one; ``info`` then also says which won (``winner``
+        int32 [n], j + 1, 0 without a consensus start) and how many rows started at weight 1 (``start_weights`` int32 [n]), and
+        ``zero_weights`` counts the rows it left out.  With more than half of the matches wrong use ``robust_iterations`` = 0 behind
+        it: the re-weightings' scale is a median over all rows.  One launch on the current stream either way; nothing synchronises
+        after the first call (which allocates: make it outside a stream capture)."""
+        return self._pose_law(False, K, status, robust_iterations, consensus, seed)
 
-    def pose_velocity_host(self, K, status, robust_iterations: int = 0):
-        """``vitvs_pose_velocity``, the host-pointer form: numpy in, ``(v_pose float64 [n, 6], info)`` out, ``info`` as
-        ``pose_velocity``'s with numpy arrays.  Synchronous."""
-        return self._pose_law(True, K, status, robust_iterations)
+    def pose_velocity_host(self, K, status, robust_iterations: int = 0, consensus: int = 0, seed: int = 0):
+        """``vitvs_pose_velocity`` (``vitvs_pose_consensus_velocity`` with ``consensus`` > 0), the host-pointer form: numpy in,
+        ``(v_pose float64 [n, 6], info)`` out, ``info`` as ``pose_velocity``'s with numpy arrays.  Synchronous."""
+        return self._pose_law(True, K, status, robust_iterations, consensus, seed)
 
     HOMOGRAPHY_INFO_FIELDS = ("usable", "sweeps", "reweighted", "zero_weights", "degenerate", "behind")
 
@@ -729,11 +748,7 @@ class Engine:
         z = float(depth_scale)
         if not (z > 0.0 and math.isfinite(z)):
             raise ValueError(f"depth_scale is a positive, finite length in metres, got {depth_scale!r}")
-        M, s = int(consensus), int(seed)
-        if not 0 <= M <= 4096:
-            raise ValueError(f"consensus is 0 .. 4096 hypotheses, got {consensus!r}")
-        if not 0 <= s <= 0xFFFFFFFF:
-            raise ValueError(f"seed is 0 .. 2^32 - 1, got {seed!r}")
+        M, s = Engine._consensus_arguments(consensus, seed)
         return z, N, M, s
 
     def _homography_law(self, host, K, status, depth_scale, robust_iterations, consensus=0, seed=0):

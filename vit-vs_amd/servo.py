@@ -445,7 +445,8 @@ class Controller:
         if st == _lib.STATUS_NO_CORRESPONDENCE:           # (the reference draw may have ended before any law evaluation)
             self.last_pose_status, self.last_pose = int(st), None
             return
-        v, info = self.engine.pose_velocity_host(p.intrinsics(), [st], p.pose_robust_iterations)
+        v, info = self.engine.pose_velocity_host(p.intrinsics(), [st], p.pose_robust_iterations, p.pose_consensus,
+                                                 p.pose_consensus_seed)
         self.last_pose_status = int(info["status"][0])
         self.last_pose = (info["R"][0].copy(), info["t"][0].copy())
         if self.last_pose_status == _lib.STATUS_OK:
