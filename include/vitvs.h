@@ -182,7 +182,9 @@ VITVS_API int vitvs_reselect(vitvs_handle* h, int32_t select_mode, const int32_t
  * (a velocity call WITH I_des, vitvs_forward_tokens_dev, vitvs_extract_*) and by vitvs_correspond_dev / vitvs_refine_dev, whose
  * descriptors overwrite the cached ones: a NULL I_des without a matching cached goal is error -5.  vitvs_reselect,
  * vitvs_servo_from_nn[_ex]_dev, the follow-on laws and vitvs_set_option keep it (a goal forwarded under another "in_flight" hint
- * keeps that plan's summation order).  Results equal the recomputing call's up to the summation order of the GEMMs (the row
+ * keeps that plan's summation order).  vitvs_roll_velocity[_dev] follows the velocity call: WITH I_des it drops the cache; with
+ * I_des == NULL it matches its four turned copies against the cached goal of one image and keeps it, so a later call with a NULL
+ * I_des servoes towards the same goal.  Results equal the recomputing call's up to the summation order of the GEMMs (the row
  * count differs). */
 VITVS_API int vitvs_set_goal_dev(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des, void* stream);
 VITVS_API int vitvs_set_goal(vitvs_handle* h, int32_t n_goal, const uint8_t* I_des);

@@ -20,6 +20,13 @@ caller's stream torch's default stream and a side stream, with graph_replay 0 an
   E  hold; dev velocity call; compute_velocity_host; last_details                      = both, and the details are the host call's
   F  compute_velocity_host; hold; dev velocity call; reselect_host                     = error -5 (nothing to reselect on)
   G  a dev velocity call captured by the CALLER; hold; replay; compute_velocity_host   = capture and replay work, the host call too
+  H  hold; dev roll call; compute_velocity_host                                        = both, and the details are the host call's
+  I  hold; dev velocity call of four pairs; roll_velocity_host                         = both; last_details(1): the carried-back tables
+  J  a BEST call; hold; dev velocity call in BEST on other frames; last_order          = the order of the call made last
+  K  hold; dev velocity call; dev pose_velocity(consensus=256); compute_velocity_host  = all three (the host call rewrites the rows
+                                                                                         the pose law reads)
+  L  as K with homography_velocity(consensus=256)
+  M  a dev velocity call; hold; another; pose_velocity_host(consensus=256)             = the law builds on the call made last
 
 and three tests of state that outlives a call: a refused saliency call keeps the cached goal, and a Controller whose goal image
 is rewritten in place servoes towards the goal it holds now."""
@@ -145,13 +152,50 @@ class _Inputs:
         self.order_d = torch.as_tensor(self.order).to(eng.device)
         self.out = [(torch.zeros((1, 6), dtype=torch.float64, device=eng.device), torch.zeros(1, dtype=torch.int32, device=eng.device))
                     for _ in range(2)]
+        # four pairs for one call, and the current frame of pair 0 and of pair 1 a quarter turn on for the roll search
+        four = [th._pair(s, "synth", None, size) for s in hc.PROBE_SEEDS]
+        self.des4_d, self.cur4_d = eng._frames(np.stack([p[0] for p in four])), eng._frames(np.stack([p[1] for p in four]))
+        self.z4_d = torch.as_tensor(th._depths(4)).to(eng.device).contiguous()
+        self.K4_d = self.K_d.expand(4, 4).contiguous()
+        self.order4_d = torch.as_tensor(th._orders(ORDER_SEED, 4, ctx.cfg.tokens)).to(eng.device)
+        self.out4 = (torch.zeros((4, 6), dtype=torch.float64, device=eng.device), torch.zeros(4, dtype=torch.int32, device=eng.device))
+        self.turned = [np.ascontiguousarray(np.rot90(a[0], 1)) for a in self.cur]
+        self.turned_d = [eng._frames(a) for a in self.turned]
+        self.roll_out = (torch.zeros((1, 6), dtype=torch.float64, device=eng.device), torch.zeros(1, dtype=torch.int32, device=eng.device),
+                         torch.zeros(8, dtype=torch.int32, device=eng.device), torch.zeros(4, dtype=torch.float64, device=eng.device))
         torch.cuda.synchronize()
 
-    def dev_call(self, ctx, pair, goal=True, slot=0):
+    def dev_call(self, ctx, pair, goal=True, slot=0, select=_lib.SELECT_ORDER):
         """vitvs_compute_velocity_dev of frame pair `pair` on the current stream (goal False: I_des NULL, the cached goal)."""
         v, st = self.out[slot]
-        return ctx.eng.compute_velocity_dev(self.cur_d[pair], self.des_d[pair] if goal else None, self.z_d, self.K_d, _lib.SELECT_ORDER,
-                                            self.order_d, None, out_v=v, out_status=st, num_pairs=NUM_PAIRS)
+        return ctx.eng.compute_velocity_dev(self.cur_d[pair], self.des_d[pair] if goal else None, self.z_d, self.K_d, select,
+                                            self.order_d if select == _lib.SELECT_ORDER else None, None, out_v=v, out_status=st,
+                                            num_pairs=NUM_PAIRS)
+
+    def dev_call_of_four(self, ctx):
+        """vitvs_compute_velocity_dev of four pairs with four goals on the current stream."""
+        v, st = self.out4
+        return ctx.eng.compute_velocity_dev(self.cur4_d, self.des4_d, self.z4_d, self.K4_d, _lib.SELECT_ORDER, self.order4_d, None, out_v=v,
+                                            out_status=st, num_pairs=NUM_PAIRS)
+
+    def roll_dev_call(self, ctx, pair):
+        """vitvs_roll_velocity_dev itself on the current stream (Engine.roll_velocity reads the winner back, which synchronises)."""
+        eng = ctx.eng
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        rc = eng.lib.vitvs_roll_velocity_dev(eng.handle, p(self.turned_d[pair]), p(self.des_d[pair]), p(self.z_d), p(self.K_d), _lib.SELECT_ORDER,
+                                             p(self.order_d), None, NUM_PAIRS, *map(p, self.roll_out),
+                                             C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
+        eng._check(rc, "vitvs_roll_velocity_dev")
+        eng._last_tokens = eng.tokens
+        return self.roll_out
+
+    def roll_host_call(self, ctx, pair):
+        """vitvs_roll_velocity of frame pair `pair`, its current frame a quarter turn on, and its snapshot."""
+        v, st, info = ctx.eng.roll_velocity_host(self.turned[pair], self.des[pair], self.z[0], self.K, _lib.SELECT_ORDER, self.order,
+                                                 num_pairs=NUM_PAIRS)
+        snap = th._law_snapshot(ctx.eng, v, np.array([st], np.int32), 1)
+        snap.update({"roll." + k: np.asarray(a).copy() for k, a in info.items()})
+        return snap
 
     def host_call(self, ctx, pair, goal=True):
         """vitvs_compute_velocity of frame pair `pair` and its snapshot (v_c, status, last_details, last_features)."""
@@ -160,11 +204,11 @@ class _Inputs:
         return th._law_snapshot(ctx.eng, v, st, 1)
 
 
-def _warm(ctx, inp, mode, pair, slot=0):
+def _warm(ctx, inp, mode, pair, slot=0, **how):
     """Option graph_replay: the call under test is a REPLAY - its capture and instantiation (host work of some milliseconds) are
     spent before the stream is held.  The handle's past does not change its answers (tests/test_gpu_history.py)."""
     if ctx.graph_replay and not mode.synchronised:
-        inp.dev_call(ctx, pair, slot=slot)
+        inp.dev_call(ctx, pair, slot=slot, **how)
         torch.cuda.synchronize()
 
 
@@ -443,6 +487,192 @@ def test_g_host_call_behind_the_replay_of_a_callers_capture(filler):
         th._same(_dev_result(out), want_dev, "the replayed dev velocity call")
         th._same(got, want, "replay, compute_velocity_host")
         del graph
+
+
+# ----------------------------------------------------------------------------------------------------- H
+def _roll_result(out):
+    torch.cuda.synchronize()
+    return dict(v_c=th._np(out[0]), status=th._np(out[1]), roll_info=th._np(out[2]), scores=th._np(out[3]))
+
+
+def _warm_roll(ctx, inp):
+    """include/vitvs.h: a handle's first roll call allocates the turned copies' buffer and synchronises the device - spent, on both
+    sides, before anything is held.  The handle's past does not change its answers (tests/test_gpu_history.py)."""
+    inp.roll_dev_call(ctx, 0)
+    torch.cuda.synchronize()
+
+
+def _sequence_h(ctx, inp, mode):
+    _warm_roll(ctx, inp)
+    mode.hold()
+    out = inp.roll_dev_call(ctx, 1)                                             # five images, the keys of four pairs, pair 0's rewritten
+    mode.pending()
+    snap = inp.host_call(ctx, 0)                                                # last_details: the host call's
+    return _roll_result(out), snap
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_h_host_call_behind_a_pending_roll_call(filler, caller, graph_replay):
+    """The roll search enqueues a quarter-turn launch, a forward of five images, the pick and a one-pair law, and returns; a
+    host-pointer velocity call made behind it finds it done: the roll outputs (a winner that is not 0), the host outputs and the
+    details read after the host call are those of the synchronised sequence."""
+    want_roll, want = _expected("H", lambda: _synced("fp32", 1, _sequence_h))
+    assert int(want_roll["roll_info"][0]) > 0 and int(want_roll["status"][0]) == _lib.STATUS_OK, want_roll
+    assert _differ(dict(v_c=want["v_c"], status=want["status"]), dict(v_c=want_roll["v_c"], status=want_roll["status"])), STALE
+    got_roll, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_h)
+    th._same(got_roll, want_roll, "the dev roll call")
+    th._same(got, want, "dev roll call, compute_velocity_host, last_details")
+
+
+# ----------------------------------------------------------------------------------------------------- I
+def _sequence_i(ctx, inp, mode):
+    _warm_roll(ctx, inp)
+    if ctx.graph_replay and not mode.synchronised:
+        inp.dev_call_of_four(ctx)
+        torch.cuda.synchronize()
+    mode.hold()
+    out = inp.dev_call_of_four(ctx)                                             # the keys of four pairs, four goals
+    mode.pending()
+    snap = inp.roll_host_call(ctx, 0)                                           # last_details(1): the winner's tables, carried back
+    return _dev_result(out), snap
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_i_host_roll_call_behind_a_pending_call_of_four_pairs(filler, caller, graph_replay):
+    """vitvs_roll_velocity (host form) behind a pending dev call of four pairs, whose keys lie where the four turned copies' go: the
+    dev outputs, the roll outputs and last_details(1) - the carried-back tables of a winner that is not 0, not pair 0 of the dev
+    call - are those of the synchronised sequence."""
+    want_dev, want = _expected("I", lambda: _synced("fp32", 1, _sequence_i))
+
+    def four_alone(ctx, inp, mode):
+        out = inp.dev_call_of_four(ctx)
+        torch.cuda.synchronize()
+        return th._law_snapshot(ctx.eng, out[0][:1], out[1][:1], 1)
+    stale = _expected("I-stale", lambda: _synced("fp32", 1, four_alone))
+    assert int(want["roll.roll"]) > 0 and int(want["status"][0]) == _lib.STATUS_OK and not want["roll.same_image"], want["roll.roll"]
+    assert not np.array_equal(stale["nn_1"], want["nn_1"]) and not np.array_equal(stale["v_c"], want["v_c"]), STALE
+    got_dev, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_i)
+    th._same(got_dev, want_dev, "the dev velocity call of four pairs")
+    th._same(got, want, "dev velocity call of four pairs, roll_velocity_host, last_details(1)")
+
+
+# ----------------------------------------------------------------------------------------------------- J
+def _sequence_j(ctx, inp, mode):
+    _warm(ctx, inp, mode, 0, select=_lib.SELECT_BEST)
+    inp.dev_call(ctx, 1, slot=1, select=_lib.SELECT_BEST)                       # the workspace holds pair 1's order, last_best is set
+    torch.cuda.synchronize()
+    mode.hold()
+    out = inp.dev_call(ctx, 0, select=_lib.SELECT_BEST)
+    mode.pending()
+    order = ctx.eng.last_order(1)
+    return _dev_result(out), dict(order=order)
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_j_last_order_behind_a_pending_best_call(filler, caller, graph_replay):
+    """vitvs_last_order is served from the device: behind a pending dev call in BEST it returns THAT call's visiting order, not the
+    one an earlier BEST call left in the workspace."""
+    def earlier(ctx, inp, mode):
+        inp.dev_call(ctx, 1, slot=1, select=_lib.SELECT_BEST)
+        torch.cuda.synchronize()
+        return dict(order=ctx.eng.last_order(1))
+    want_dev, want = _expected("J", lambda: _synced("fp32", 1, _sequence_j))
+    stale = _expected("J-stale", lambda: _synced("fp32", 1, earlier))
+    assert _differ(stale, want), STALE
+    assert int(want_dev["status"][0]) == _lib.STATUS_OK and sorted(want["order"][0].tolist()) == list(range(want["order"].shape[1]))
+    got_dev, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_j)
+    th._same(got_dev, want_dev, "the dev velocity call in BEST")
+    th._same(got, want, "dev velocity call in BEST, last_order")
+
+
+# ----------------------------------------------------------------------------------------------------- K, L, M
+CONSENSUS, SEED = 256, 7
+DEV_LAWS = {"pose": lambda eng, K, st: eng.pose_velocity(K, st, 4, CONSENSUS, SEED),
+            "homography": lambda eng, K, st: eng.homography_velocity(K, st, 0.6, 4, CONSENSUS, SEED)}
+
+
+def _law_result(v, info):
+    torch.cuda.synchronize()
+    return {k: th._np(a) for k, a in dict(v=v, **info).items()}
+
+
+def _live(law_out):
+    return not law_out["status"].any() and bool(np.all(law_out["winner"] > 0))
+
+
+def _sequence_kl(law):
+    def body(ctx, inp, mode):
+        ctx.eng.set_goal_depth(th._goal_depth())
+        out = inp.dev_call(ctx, 1)                                              # the law's first call allocates: spent before the hold
+        DEV_LAWS[law](ctx.eng, inp.K_d, out[1])
+        torch.cuda.synchronize()
+        mode.hold()
+        out = inp.dev_call(ctx, 1)
+        v_law, info = DEV_LAWS[law](ctx.eng, inp.K_d, out[1])                   # on the caller's stream, behind the velocity call
+        mode.pending()
+        snap = inp.host_call(ctx, 0)                                            # rewrites feat, s_uv and selected
+        return _dev_result(out), _law_result(v_law, info), snap
+    return body
+
+
+def _law_behind_the_host_call(law):
+    def body(ctx, inp, mode):
+        ctx.eng.set_goal_depth(th._goal_depth())
+        snap = inp.host_call(ctx, 0)
+        return _law_result(*DEV_LAWS[law](ctx.eng, inp.K_d, snap["status"]))
+    return body
+
+
+@pytest.mark.parametrize("law", list(DEV_LAWS))
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_kl_host_call_behind_a_pending_consensus_law(filler, caller, graph_replay, law):
+    """A dev velocity call and the pose (K) or homography (L) law with a consensus start behind it on the caller's stream, then a
+    host-pointer velocity call, which rewrites the feature rows the law reads: the law ran on the dev call's rows (a live consensus
+    start), and all three give their synchronised values."""
+    want_dev, want_law, want = _expected(("KL", law), lambda: _synced("fp32", 1, _sequence_kl(law)))
+    stale = _expected(("KL-stale", law), lambda: _synced("fp32", 1, _law_behind_the_host_call(law)))
+    assert _live(want_law), (want_law["status"], want_law["winner"])
+    assert _differ(stale, want_law) and _differ(dict(v_c=want["v_c"], status=want["status"]), want_dev), STALE
+    got_dev, got_law, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_kl(law))
+    th._same(got_dev, want_dev, "the dev velocity call")
+    th._same(got_law, want_law, f"the dev {law} law with a consensus start")
+    th._same(got, want, f"dev velocity call, {law} law, compute_velocity_host")
+
+
+def _host_pose(ctx, inp):
+    v, info = ctx.eng.pose_velocity_host(inp.K, np.zeros(1, np.int32), 4, CONSENSUS, SEED)     # (the status the dev call will give)
+    return {k: np.asarray(a).copy() for k, a in dict(v=v, **info).items()}
+
+
+def _sequence_m(ctx, inp, mode):
+    ctx.eng.set_goal_depth(th._goal_depth())
+    _warm(ctx, inp, mode, 1)
+    inp.dev_call(ctx, 0, slot=1)                                                # the rows an unordered law would build on
+    _host_pose(ctx, inp)                                                        # (the law's first call allocates)
+    torch.cuda.synchronize()
+    mode.hold()
+    out = inp.dev_call(ctx, 1)
+    mode.pending()
+    law = _host_pose(ctx, inp)
+    return _dev_result(out), law
+
+
+@pytest.mark.parametrize("caller,graph_replay", CALLERS)
+def test_m_host_pose_law_behind_a_pending_velocity_call(filler, caller, graph_replay):
+    """vitvs_pose_consensus_velocity (host form) builds on the handle's last velocity call, also when that call still waits on the
+    caller's stream: the law's outputs are those behind the call made last, not behind the one before it."""
+    def earlier(ctx, inp, mode):
+        ctx.eng.set_goal_depth(th._goal_depth())
+        inp.dev_call(ctx, 0, slot=1)
+        torch.cuda.synchronize()
+        return _host_pose(ctx, inp)
+    want_dev, want = _expected("M", lambda: _synced("fp32", 1, _sequence_m))
+    stale = _expected("M-stale", lambda: _synced("fp32", 1, earlier))
+    assert int(want_dev["status"][0]) == _lib.STATUS_OK and _live(want)
+    assert _differ(stale, want), STALE
+    got_dev, got = _run(filler, caller, graph_replay, "fp32", 1, _sequence_m)
+    th._same(got_dev, want_dev, "the dev velocity call")
+    th._same(got, want, "dev velocity call, pose_velocity_host with a consensus start")
 
 
 # ----------------------------------------------------------------------------------------------------- state that outlives a call

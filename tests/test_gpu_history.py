@@ -9,7 +9,9 @@ tests/history_cases.py's; every axis test also asserts that D's outputs differ f
 A snapshot of a velocity / law call: v_c, status, every array of last_details (with last_weights, last_offsets, last_goal_depth)
 and of last_features; the header's promises past the rows a call defines (selected -1, everything else 0, the options' "off"
 values) are asserted on both sides.  A follow-on law's snapshot: its own outputs and the camera's snapshot read after it.  A
-forward-only call's: the tensors it returns."""
+forward-only call's: the tensors it returns.  A call in selection mode BEST adds its visiting order (last_order); after any other
+mode last_order must be refused with -5.  A roll call's: v_c, status, the winner, the scores, the four n_mutual, the same-image flag
+and the one-pair law's snapshot behind it."""
 import ctypes as C
 import dataclasses
 import functools
@@ -129,10 +131,23 @@ def _law_snapshot(eng, v, st, n):
     return snap
 
 
+def _with_order(eng, snap, n, best):
+    """BEST: the visiting order the law ran on joins the snapshot.  Any other mode: vitvs_last_order is refused, whatever ran before."""
+    if best:
+        snap["order"] = eng.last_order(n)
+    else:
+        with pytest.raises(VitvsError, match=r"\(-5\)"):
+            eng.last_order(n)
+    return snap
+
+
 def _check_promises(snap, options=hc.OFF):
     """include/vitvs.h: past a call's feature rows the getters return -1 / 0 whatever an earlier call left; the options' "off"
     values; a status that skips the law leaves v_c = 0."""
     n = snap["status"].shape[0]
+    if "order" in snap:                                                 # a permutation of 0 .. T - 1 per pair
+        tokens = snap["order"].shape[1]
+        assert snap["order"].shape[0] == n and np.array_equal(np.sort(snap["order"], axis=1), np.tile(np.arange(tokens, dtype=np.int32), (n, 1)))
     for b in range(n):
         rows = int(snap["info"][b, 1])
         assert np.all(snap["selected"][b, rows:] == -1) and not snap["s_uv"][b, rows:].any() and not snap["feat"][b, rows:].any()
@@ -180,6 +195,7 @@ def _run_velocity(ctx, c):
     eng, n, size = ctx.eng, len(c["seeds"]), ctx.cfg.img_size
     eng.set_option("in_flight", c["in_flight"] or ctx.in_flight)
     _set_options(ctx, c["options"])
+    eng.set_option("select_cells", c["select_cells"])
     eng.set_frame_size(*(c["geometry"] or (None, None)))
     K, mode = ctx.params.intrinsics(), hc.SELECT[c["mode"]]
     for u in range(c["updates"]):
@@ -199,7 +215,7 @@ def _run_velocity(ctx, c):
             v, st = eng.compute_velocity_host(cur, des, z, K, mode=mode, selection=sel, des_shared=shared, num_pairs=c["num_pairs"])
             if c["entry"] == "reselect":
                 v, st = eng.reselect_host(_lib.SELECT_ORDER, _orders(c["order_seed"] + 500, n, ctx.cfg.tokens), num_pairs=c["num_pairs"])
-    snap = _law_snapshot(eng, v, st, n)
+    snap = _with_order(eng, _law_snapshot(eng, v, st, n), n, c["mode"] == "best")
     _check_promises(snap, c["options"])
     if c["frames"] == "synth" and c["depth"]:
         assert not snap["status"].any() and not snap["info"][:, 2].any(), (c, snap["status"], snap["info"])   # a live law, not a shortcut
@@ -248,14 +264,23 @@ def _run_law(ctx, c):
     eng, g, k = ctx.eng, c["grid"], c["num_pairs"]
     t = g * g
     _set_options(ctx, hc.OFF)
+    eng.set_option("select_cells", c["select_cells"])
     rng = np.random.default_rng(c["table_seed"])
     nn1, nn2, sim1, mutual = ls.tables(rng, t, (2 * t) // 3)
     depth, K, pick = ls.depth(rng), ls.intrinsics(rng, ctx.params), c["pick"]
     ident = np.arange(t)
+    if c["mutual"] is not None:                                  # exactly that many mutual tokens: the others' partners point elsewhere
+        keep = np.sort(rng.choice(mutual, size=c["mutual"], replace=False))
+        for i in np.setdiff1d(mutual, keep):
+            nn2[nn1[i]] = next(x for x in range(t) if nn1[x] != nn1[i])
+        mutual = keep
+        assert np.array_equal(np.nonzero(nn2[nn1] == ident)[0], mutual)
     moved = np.nonzero(nn1 != ident)[0]
     ids, want = None, _lib.STATUS_OK
-    if pick == "mutual":
+    if pick == "mutual" and c["mode"] != "best":
         ids = rng.choice(mutual, size=k, replace=False)
+    elif pick == "mutual":
+        pass                                                           # BEST draws for itself: the k best mutual tokens, spread
     elif pick == "repeat1":
         ids = np.full(k, rng.choice(moved))
     elif pick == "repeat2":
@@ -279,7 +304,7 @@ def _run_law(ctx, c):
     elif c["mode"] == "order":
         sel = rng.permutation(t).astype(np.int32)
     v, st = eng.servo_from_nn(nn1, nn2, sim1, depth, K, mode=mode, selection=sel, num_pairs=k)
-    snap = _law_snapshot(eng, v, st, 1)
+    snap = _with_order(eng, _law_snapshot(eng, v, st, 1), 1, c["mode"] == "best")
     _check_promises(snap)
     info = snap["info"][0]
     assert int(snap["status"][0]) == want, (c, snap["status"])
@@ -287,6 +312,10 @@ def _run_law(ctx, c):
         assert (int(info[5]) > hc.LDS_ROWS) == (hc.extent(c, "rows")[0]), (c, info)
         if pick == "same_image":
             assert int(info[2]) == 1 and not snap["v_c"].any()
+        elif pick == "mutual" and c["mode"] == "best":
+            # the order's mutual class is the planted tokens; a short one fills fewer rows than the call asks for
+            assert int(info[0]) == len(mutual) >= (c["mutual"] or 0) and int(info[3]) == min(len(mutual), k), (c, info, len(mutual))
+            assert np.array_equal(np.sort(snap["order"][0, :len(mutual)]), mutual) and (c["mutual"] is None or len(mutual) < k)
         elif pick == "mutual":
             assert int(info[4]) == -1, (c, "expected LDL^T", info)
         elif pick in ("repeat1", "repeat2"):
@@ -306,23 +335,62 @@ def _run_follow(ctx, c):
         v_law, status, info = eng.rig_velocity(Ws, st, robust_iterations=N, K=K if N else None)
         out = dict(v=v_law, status=status, **info)
     elif c["law"] == "pose":
-        v_law, info = eng.pose_velocity(K, st, robust_iterations=N)
+        v_law, info = eng.pose_velocity(K, st, robust_iterations=N, consensus=c["consensus"], seed=c["seed"])
         out = dict(v=v_law, **info)
     elif c["law"] == "pose_rig":
         v_law, status, info = eng.pose_rig_velocity(ext, K, st, robust_iterations=N)
         out = dict(v=v_law, status=status, **info)
     else:
         assert c["law"] == "homography"
-        v_law, info = eng.homography_velocity(K, st, depth_scale=0.6, robust_iterations=N)
+        v_law, info = eng.homography_velocity(K, st, depth_scale=0.6, robust_iterations=N, consensus=c["consensus"], seed=c["seed"])
         out = dict(v=v_law, **info)
     snap = {"law." + k: _np(a) for k, a in out.items()}
+    if c["consensus"]:                                           # a live consensus start on every pair, not the fallback without one
+        assert c["law"] in hc.CONSENSUS_LAWS
+        assert not snap["law.status"].any() and np.all(snap["law.winner"] > 0) and np.all(snap["law.start_weights"] >= 3), \
+            (c, snap["law.status"], snap["law.winner"], snap["law.start_weights"])
+    else:
+        assert not snap.get("law.winner", np.zeros(1)).any()
     camera = _law_snapshot(eng, v, st, n)                    # the camera's law, read AFTER the follow-on law
     _check_promises(camera, cam["options"])
     snap.update({"camera." + k: a for k, a in camera.items()})
     return snap
 
 
+ROLL_WINNERS = {}                                                # (precision, in_flight, seed, turn, goal, mode) -> k*, as observed
+
+
+def _run_roll(ctx, c):
+    """vitvs_roll_velocity[_dev]; asserts that the search picked what the row says (c["winner"]) with a live law behind it."""
+    eng, size = ctx.eng, ctx.cfg.img_size
+    eng.set_option("in_flight", ctx.in_flight)
+    _set_options(ctx, hc.OFF)
+    eng.set_option("select_cells", c["select_cells"])
+    eng.set_frame_size()
+    des, cur = _pair(c["seed"], "synth", None, size)
+    cur = np.ascontiguousarray(np.rot90(des if c["at_goal"] else cur, c["turn"]))
+    if c["goal"] == "cached":
+        eng.set_goal(des[None])
+    if c["goal"] != "own":
+        des = None
+    sel = _orders(c["order_seed"], 1, ctx.cfg.tokens) if c["mode"] == "order" else None
+    call = eng.roll_velocity if c["entry"] == "dev" else eng.roll_velocity_host
+    v, st, info = call(cur, des, _depths(1)[0], ctx.params.intrinsics(), mode=hc.SELECT[c["mode"]], selection=sel, num_pairs=c["num_pairs"])
+    snap = _with_order(eng, _law_snapshot(eng, v, st, 1), 1, c["mode"] == "best")
+    snap["status"] = snap["status"].astype(np.int32)
+    snap.update({"roll." + k: np.asarray(a).copy() for k, a in info.items()})
+    _check_promises(snap)
+    ROLL_WINNERS[(ctx.precision, ctx.in_flight, c["seed"], c["turn"], c["goal"], c["mode"])] = info["roll"]
+    if c["winner"] != "any":
+        assert (info["roll"] > 0) if c["winner"] == "nonzero" else (info["roll"] == 0), (c, info)
+        assert int(snap["status"][0]) == _lib.STATUS_OK, (c, snap["status"])
+        assert info["same_image"] == c["at_goal"] and int(snap["info"][0, 2]) == int(c["at_goal"]), (c, info, snap["info"])
+    return snap
+
+
 def _run(ctx, c):
+    if c["kind"] == "roll":
+        return _run_roll(ctx, c)
     if c["kind"] == "seq":
         for part in c["calls"]:
             snap = _run(ctx, part)
@@ -352,6 +420,13 @@ def _fresh(kind, precision, in_flight, c):
 def _forget():
     yield
     _FRESH.clear()
+    # which candidate won the roll calls of this run (the rows assert the class of each; shown with -s)
+    print("\nroll winners (seed, turn, goal, mode, k*):", sorted({(*key[2:], k) for key, k in ROLL_WINNERS.items()}))
+    by_call = {}
+    for key, k in ROLL_WINNERS.items():
+        by_call.setdefault(key[2:], set()).add(k)
+    print("roll calls whose winner depends on the precision or the plan:", {c: ks for c, ks in by_call.items() if len(ks) > 1})
+    ROLL_WINNERS.clear()
 
 
 def _same(got, want, what):
@@ -425,13 +500,14 @@ def test_entry_points_and_the_goal_cache(name, d, survives, when, precision, in_
     call that forwards frames of its own choice or rewrites the descriptors (a velocity call WITH I_des, vitvs_extract_*,
     vitvs_correspond_dev) - then P is error -5, never a twist from a stale goal - and survives the calls that do neither
     (vitvs_reselect behind a call on the cached goal, vitvs_servo_from_nn_dev) - and a call the library REFUSES: f16x2 has no
-    saliency kernel, and vitvs_extract_saliency_dev says so before it forwards anything."""
+    saliency kernel, and vitvs_extract_saliency_dev says so before it forwards anything.  The roll search follows the velocity
+    call: with an I_des of its own it drops the cache, with I_des = NULL it matches the cached goal and keeps it."""
     survives = survives or (name == "extract_saliency_maps" and precision == "f16x2")
     p = hc.P1_CACHED
     want = _fresh("tiny", precision, in_flight, p)
     with Ctx("tiny", precision, in_flight) as ctx:
         if when == "goal_after":
-            dirt = _run(ctx, dict(d, goal="own") if d["kind"] == "velocity" else d)
+            dirt = _run(ctx, dict(d, goal="own") if d["kind"] in ("velocity", "roll") else d)
             assert _first_difference(dirt, want) is not None
             _same(_run(ctx, p), want, name)
             return
@@ -452,7 +528,8 @@ def test_entry_points_and_the_goal_cache(name, d, survives, when, precision, in_
 @pytest.mark.parametrize("d,p", _rows("graph"))
 def test_graph_replay_around_eager_calls(d, p, precision, in_flight, request):
     """Axis 5.  P captured on a side stream, D eagerly (the default stream is never captured) with other arguments and sizes,
-    P replayed, then P eagerly with replay off: all three equal the fresh handle's eager P."""
+    P replayed, then P eagerly with replay off: all three equal the fresh handle's eager P.  A BEST probe's capture holds the
+    launch that makes its visiting order; a roll call is never replayed and runs eagerly between the replays of a handle that is."""
     name = request.node.callspec.id
     want = _fresh("tiny", precision, in_flight, p)
     with Ctx("tiny", precision, in_flight) as ctx:
@@ -461,7 +538,8 @@ def test_graph_replay_around_eager_calls(d, p, precision, in_flight, request):
         cur_d, des_d = eng._frames(cur), eng._frames(des)
         z_d = torch.as_tensor(_depths(n)).to(eng.device).contiguous()
         k_d = torch.as_tensor(ctx.params.intrinsics(), dtype=torch.float64).reshape(1, 4).expand(n, 4).contiguous().to(eng.device)
-        sel_d = torch.as_tensor(_orders(p["order_seed"], n, ctx.cfg.tokens)).to(eng.device)
+        best = p["mode"] == "best"                               # (the order is made on the device: nothing comes from the caller)
+        sel_d = None if best else torch.as_tensor(_orders(p["order_seed"], n, ctx.cfg.tokens)).to(eng.device)
         out_v = torch.zeros((n, 6), dtype=torch.float64, device=eng.device)
         out_s = torch.zeros(n, dtype=torch.int32, device=eng.device)
         side = torch.cuda.Stream(eng.device)
@@ -474,9 +552,9 @@ def test_graph_replay_around_eager_calls(d, p, precision, in_flight, request):
             out_s.fill_(-1)
             torch.cuda.synchronize()
             with torch.cuda.stream(side):
-                eng.compute_velocity_dev(cur_d, des_d, z_d, k_d, _lib.SELECT_ORDER, sel_d, None, out_v=out_v, out_status=out_s, num_pairs=k)
+                eng.compute_velocity_dev(cur_d, des_d, z_d, k_d, hc.SELECT[p["mode"]], sel_d, None, out_v=out_v, out_status=out_s, num_pairs=k)
             torch.cuda.synchronize()
-            return _law_snapshot(eng, out_v, out_s, n)
+            return _with_order(eng, _law_snapshot(eng, out_v, out_s, n), n, best)
         _same(replayed(), want, name + ": captured")
         dirt = _run(ctx, d)
         assert _first_difference(dirt, want) is not None
@@ -508,6 +586,39 @@ def test_follow_on_laws(d, p, request):
     the first time (its block is allocated then) on a handle that has run 20 updates.  The camera's own v_c and detail block,
     read after the follow-on law, equal the fresh handle's as well."""
     _dirty_then_probe("tiny", "fp32", 1, request.node.callspec.id, d, p)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("d,p", [r for r in _rows("select") if r.values[0]["kind"] != "law"])
+def test_best_selection_through_the_forward(d, p, precision, request):
+    """Axis 12 through the forward: BEST's visiting order of n_pairs * T tokens in the handle's workspace behind a larger one, an
+    ORDER call behind a BEST call (vitvs_last_order is refused again) and the reverse, select_cells 4 and 1 in both orders."""
+    _dirty_then_probe("tiny", precision, 1, request.node.callspec.id, d, p)
+
+
+@pytest.mark.parametrize("d,p", [r for r in _rows("select") if r.values[0]["kind"] == "law"])
+def test_best_selection_on_planted_tables(d, p, request):
+    """Axis 12 on planted tables (17 x 17 tokens): an order with 12 mutual tokens for 24 feature pairs behind one with 192, and the
+    reverse - the short one's zero-padded rows borrow nothing from the long one's tail - and an order without any mutual token."""
+    _dirty_then_probe("law17", "fp32", 1, request.node.callspec.id, d, p)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("d,p", _rows("consensus"))
+def test_consensus_starts(d, p, precision, request):
+    """Axis 14: the pose and the homography law with 4096, 256 and no hypotheses, with another seed, behind three cameras and
+    two, in the law's one scratch block; _run_follow asserts that every consensus start is a live one."""
+    _dirty_then_probe("tiny", precision, 1, request.node.callspec.id, d, p)
+
+
+@pytest.mark.parametrize("in_flight", IN_FLIGHT)
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("d,p", _rows("roll"))
+def test_roll_search(d, p, precision, in_flight, request):
+    """Axis 13: a roll call forwards five images, fills the keys of four pairs, rewrites pair 0's in place from the winner's and
+    leaves the flag `rolled` and a one-pair law behind; plain calls of one pair and of four pairs with four goals behind it, a
+    roll call behind those, winner 0 (the pick's early return) behind winner 3, the pose law's consensus start on either side."""
+    _dirty_then_probe("tiny", precision, in_flight, request.node.callspec.id, d, p)
 
 
 def _refuse(ctx, kind):
