@@ -324,7 +324,7 @@ VITVS_API int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z)
  * rows included, exactly as the camera's own law used them (L and e of vitvs_last_details) —
  *     M = stack_i(L_i W_i),  e = stack_i(e_i),  v_r = -lambda pinv(M) e
  * over the cameras whose status is VITVS_OK, in fp64: the 6 x 6 normal equations G = M^T M, g = M^T e by the LDL^T
- * factorisation of the camera law with its pivot test d > 1e-8 G_jj, and behind a failed pivot the one-sided Jacobi SVD of the
+ * factorisation of the camera law with its pivot test d > 1e-4 G_jj, and behind a failed pivot the one-sided Jacobi SVD of the
  * stacked M with numpy.linalg.pinv's rcond = 1e-15.  The average of the cameras' twists mapped back to the rig frame is NOT this
  * solution, and is wrong whenever one camera alone cannot observe all six degrees of freedom.
  *   cVr      double [n_cams][36], row-major W_i
@@ -364,7 +364,7 @@ VITVS_API int vitvs_rig_velocity(vitvs_handle* h, int32_t n_cams, const double* 
  * sigma_min = the largest, over the contributing cameras, of 0.5 max(pitch_u / fx_i, pitch_v / fy_i) ("robust_law"'s floor;
  * residuals are in normalised image coordinates and compare across cameras).  The median of an even count is the mean of the
  * two middle values.  Solves as the rig law's: LDL^T of the weighted normal equations (the weight as a factor, pivot test
- * d > 1e-8 G_jj), behind a failed pivot the Jacobi SVD (rcond 1e-15) of a copy of the rows scaled by sqrt(w).
+ * d > 1e-4 G_jj), behind a failed pivot the Jacobi SVD (rcond 1e-15) of a copy of the rows scaled by sqrt(w).
  *   cVr, status, v_rig, rig_status   as vitvs_rig_velocity_dev's
  *   K        double [n_cams][4]: fx, fy, cx, cy of camera i
  *   n_iter   re-weightings, 1 .. 16

@@ -11,6 +11,7 @@ pseudo-inverse twist mapped back to the rig frame, then the mean — which is no
 import numpy as np
 
 from homography_ref import rodrigues  # noqa: F401
+from solve_ref import THRESHOLD
 
 STATUS_OK, STATUS_NO_CORRESPONDENCE, STATUS_TOO_FEW, STATUS_NO_DEPTH = 0, 1, 2, 3
 
@@ -70,7 +71,7 @@ def normal_packed(M, e):
 
 
 def ldlt_margin(M):
-    """The LDL^T pivots of G = M^T M relative to the kernel's test d > 1e-8 G_jj: min_j d_j / (1e-8 G_jj) in fp64 (solve.h
+    """The LDL^T pivots of G = M^T M relative to the kernel's test d > THRESHOLD G_jj: min_j d_j / (THRESHOLD G_jj) in fp64 (solve.h
     restated).  > 1: every pivot passes (the LDL^T path); a failing factorisation returns the ratio of its first failing pivot
     (<= 1; 0 for a zero or negative one).  A case is only a fair test of a path when this is >= 100 or <= 0.01."""
     G = M.T @ M
@@ -79,7 +80,7 @@ def ldlt_margin(M):
         d = G[j, j] - sum(Lf[j, k] ** 2 * dpiv[k] for k in range(j))
         if not G[j, j] > 0:
             return 0.0
-        ratio = d / (1e-8 * G[j, j])
+        ratio = d / (THRESHOLD * G[j, j])
         if ratio <= 1.0:
             return max(float(ratio), 0.0)
         worst = min(worst, ratio)

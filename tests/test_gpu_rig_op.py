@@ -6,7 +6,7 @@ XCD: the fan-in meets both placements), 2 / 4 / 48 / 130 / 258 rows per camera (
 past 128 rows; past one row per thread), one 2 x 2048-row case, mixed counts with an empty camera first, in the middle and last
 (the prefix offsets, the camera-order sum), both solvers, nobody contributing, the same buffers reused back to back (the
 hand-off's stale-line case) and determinism.  Every case names the solver its fp64 reference takes and keeps the reference's own
-LDL^T pivots >= 100 x away from the 1e-8 test on either side (checked on the CPU by the first test)."""
+LDL^T pivots >= 100 x away from the pivot test (solve_ref.THRESHOLD) on either side (checked on the CPU by the first test)."""
 import ctypes as C
 
 import numpy as np

@@ -3,7 +3,7 @@
 servo_kernel picks among several paths: the depth prefetch (T <= 256) or direct depth reads; the one-position ballot scan
 (T <= 256) or the shuffle scan over ceil(T / 256) positions per thread, with tail threads holding none (T = 289: threads from
 145 on); L in LDS (R = 2 * rows <= 128) or in the global workspace with column stride 2 * max_rows; the LDL^T normal equations or,
-when a pivot falls below 1e-8 of its diagonal, one-sided Jacobi SVD, whose lanes loop over several rows once R > 64.  Every case
+when a pivot falls below 1e-4 of its diagonal, one-sided Jacobi SVD, whose lanes loop over several rows once R > 64.  Every case
 asserts which solver ran through info[4] (-1: LDL^T, otherwise the Jacobi sweeps, <= 40) and R through info[5], and checks the
 law against oracle/servo_ref (numpy pinv): s_uv exact, Z exact, L within 1e-13, v_c within 1e-9 (relative L2).  The tables go
 in through vitvs_servo_from_nn_dev (tiny handles, T up to 1024) or come from velocity calls of the 2-block tiny model.

@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
     // 5. v_c = -lambda * pinv(L) e, fp64.
     // Fast path (L_e of full column rank and well conditioned, the normal servo case): pinv(L) e is the
     // least-squares solution, obtained from the 6x6 normal equations G = L^T L, g = L^T e by an LDL^T
-    // factorisation.  If a pivot falls below 1e-8 of its diagonal (cond(L) > ~1e4, or rank deficiency,
+    // factorisation.  If a pivot falls below kPivotThreshold (solve.h: 1e-4) of its diagonal (cond(L) > ~2e2, or rank deficiency,
     // e.g. all-identical zero-padded rows) the general path below runs instead: one-sided Jacobi SVD
     // with numpy.linalg.pinv's rcond = 1e-15 cut-off.
     int status = ST_OK;
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void servo_kernel(const unsigned long long* __
             double d = Gm[j][j];
 #pragma unroll
             for (int k = 0; k < j; ++k) d -= Lf[j][k] * Lf[j][k] * dpiv[k];
-            good = good && (d > 1e-8 * Gm[j][j]) && (Gm[j][j] > 0.0);
+            good = good && (d > kPivotThreshold * Gm[j][j]) && (Gm[j][j] > 0.0);
             dpiv[j] = d;
             dinv[j] = 1.0 / d;
 #pragma unroll
