@@ -1,5 +1,6 @@
 """The consensus start of the homography law in fp64 numpy ("The consensus start"): the statement the consensus phase of
-csrc/homography.hip is tested against, in the kernel's order of arithmetic.
+csrc/consensus_core.h is tested against on csrc/homography.hip's four-point model, in the kernel's order of arithmetic.  The draw,
+the score, the winner and the start are consensus_ref's, shared with pose_consensus_ref.
 
 Per pair, with the usable rows in ascending order, n_us of them, and the cut-off T = 4.6851 sigma_min:
 
@@ -24,38 +25,16 @@ from __future__ import annotations
 
 import numpy as np
 
+import consensus_ref as cs
 import homography_ref as hr
+from consensus_ref import DRAWS, MAX_HYP, mix  # noqa: F401
 
-MAX_HYP = 4096
-DRAWS = 64
 COLLINEAR_TOL = 1e-8   # a hypothesis with a triangle of its four points, in either image, of <= COLLINEAR_TOL extent^2 is skipped
-_M32 = np.uint64(0xFFFFFFFF)
-
-
-def mix(x):
-    """lowbias32 on an array of 32-bit values held in uint64."""
-    x = np.asarray(x, np.uint64) & _M32
-    x = x ^ (x >> np.uint64(16))
-    x = (x * np.uint64(0x7FEB352D)) & _M32
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(0x846CA68B)) & _M32
-    return x ^ (x >> np.uint64(16))
 
 
 def draw(seed, n_hyp, n_us):
-    """-> (pos int64 [n_hyp, 4] ascending, ok bool [n_hyp]) for the hypotheses j = 0 .. n_hyp - 1; a function of (seed, j, n_us)."""
-    j = np.arange(n_hyp, dtype=np.uint64)
-    base = mix(((np.uint64(int(seed) & 0xFFFFFFFF) * np.uint64(0x9E3779B9)) & _M32) + j)
-    pos = np.full((n_hyp, 4), -1, np.int64)
-    cnt = np.zeros(n_hyp, np.int64)
-    for c in range(DRAWS):
-        r = (mix(base + np.uint64(c)) % np.uint64(n_us)).astype(np.int64)
-        new = (cnt < 4) & ~(pos == r[:, None]).any(1)
-        rows = np.nonzero(new)[0]
-        pos[rows, cnt[rows]] = r[rows]
-        cnt[rows] += 1
-    ok = cnt == 4
-    return np.where(ok[:, None], np.sort(pos, 1), -1), ok
+    """consensus_ref.draw with 4 positions."""
+    return cs.draw(seed, n_hyp, n_us, 4)
 
 
 def _basis(x, y):
@@ -110,43 +89,11 @@ def transfer_sq(H, m, ms):
 
 
 def consensus(m, ms, usable, sigma_min, n_hyp, seed):
-    """The consensus phase on one pair's points -> dict(winner (j + 1, or 0), start [n] weights, n_start, costs [n_hyp], gap, edge_T,
-    H (the winner's, or None)): ``gap`` = (C' - C) / C' with C the winner's cost and C' the best cost of a hypothesis with another
-    row set (inf when there is none), ``edge_T`` = the closest |rho_k / T - 1| of a usable row under the winner."""
+    """consensus_ref.consensus on one pair's points with four_point and transfer_sq -> its dict with the winner's ``H`` (or None)
+    for ``model``."""
     m, ms = np.asarray(m, np.float64).reshape(-1, 2), np.asarray(ms, np.float64).reshape(-1, 2)
-    us = np.asarray(usable).reshape(-1) > 0
-    rows = np.nonzero(us)[0]
-    n_us = len(rows)
-    out = dict(winner=0, start=np.where(us, 1.0, 0.0), n_start=0, costs=np.full(n_hyp, np.inf), gap=np.inf, edge_T=np.inf, H=None)
-    if n_hyp < 1 or n_us < 4:
-        return out
-    out["n_start"] = n_us
-    T = hr.TUKEY_C * sigma_min
-    T2 = T * T
-    pos, ok = draw(seed, n_hyp, n_us)
-    sets = rows[np.where(ok[:, None], pos, 0)]
-    H, solved = four_point(m[sets], ms[sets])
-    ok &= solved
-    q = transfer_sq(H, m[rows], ms[rows])
-    with np.errstate(all="ignore"):
-        terms = np.where(q < T2, q, T2)
-        costs = np.cumsum(terms, 1)[:, -1]                   # (cumsum adds in ascending rows, one after the other)
-    costs = np.where(ok, costs, np.inf)
-    costs = np.where(costs >= 0.0, costs, np.inf)            # (a NaN cost ranks with the skipped ones)
-    out["costs"] = costs
-    j = int(np.argmin(costs))                                # the first of equal minima: ties go to the smallest j
-    if not costs[j] < np.inf:
-        return out
-    other = ok & (pos != pos[j]).any(1)
-    if other.any():
-        c2 = float(costs[other].min())
-        out["gap"] = (c2 - float(costs[j])) / c2 if c2 < np.inf and c2 > 0.0 else (np.inf if c2 == np.inf else 0.0)
-    rho = np.full(len(m), np.inf)
-    rho[rows] = np.sqrt(q[j])
-    start = np.where(us & (rho <= T), 1.0, 0.0)
-    finite = us & np.isfinite(rho)
-    out.update(winner=j + 1, start=start, n_start=int(start.sum()), H=H[j],
-               edge_T=float(np.abs(rho[finite] / T - 1.0).min()) if finite.any() else np.inf)
+    out = cs.consensus((m, ms), usable, hr.TUKEY_C * sigma_min, n_hyp, seed, 4, four_point, transfer_sq)
+    (out["H"],) = out.pop("model") or (None,)
     return out
 
 
@@ -156,52 +103,16 @@ def homography_consensus_law(m, ms, usable, lam, depth_scale=1.0, n_iter=0, sigm
     m, ms = np.asarray(m, np.float64).reshape(-1, 2), np.asarray(ms, np.float64).reshape(-1, 2)
     us = np.asarray(usable).reshape(-1) > 0
     m, ms = np.where(us[:, None], m, 0.0), np.where(us[:, None], ms, 0.0)
-    n_us = int(us.sum())
     if n_hyp < 1:
         out = hr.homography_law(m, ms, usable, lam, depth_scale, n_iter, sigma_min)
         out.update(start=np.where(us, 1.0, 0.0), gap=np.inf, edge_T=np.inf)
         return out
     con = consensus(m, ms, us, sigma_min, n_hyp, seed)
-    w = con["start"].copy()
-    n_zero = n_us - con["n_start"] if con["winner"] else 0
-    status, sweeps, reweighted, degenerate, n_inf, sigma = hr.OK, 0, 0, 0, 0, 0.0
-    H, mc = np.eye(3), np.zeros(2)
-    ratios, gaps, edge = [], [], np.inf
-    it = 0
-    with np.errstate(all="ignore"):
-        while True:                                          # homography_ref.homography_law's loop from other start weights
-            if n_us - n_zero < 4:
-                status = hr.TOO_FEW
-                break
-            h = hr.dlt(m, ms, w)
-            sweeps = h["sweeps"]
-            ratios.append(h["ratio"])
-            gaps.append(h["gap"])
-            if h["degenerate"]:
-                degenerate, status = 1, hr.TOO_FEW
-                break
-            H, mc = h["H"], h["mc"]
-            if it == n_iter:
-                break
-            rho = np.where(us, hr.transfer_error(H, m, ms), np.inf)
-            n_inf = int((us & np.isinf(rho)).sum())
-            sigma = max(1.4826 * hr.median_middle(rho[us]), sigma_min)
-            tt = rho / (hr.TUKEY_C * sigma)
-            u = 1.0 - tt * tt
-            finite = us & np.isfinite(tt)
-            if finite.any():
-                edge = min(edge, float(np.abs(tt[finite] - 1.0).min()))
-            w = np.where(us & (tt < 1.0), u * u, 0.0)
-            n_zero = int((us & (w == 0.0)).sum())
-            it += 1
-            reweighted = it
-    if status != hr.OK:
-        H, v = np.eye(3), np.zeros(6)
-    else:
-        v = hr.twist(H, mc, lam, depth_scale)
-    info = np.array([n_us, sweeps, reweighted, n_zero, degenerate, n_inf, con["winner"], con["n_start"]], np.int32)
-    return dict(v=v, status=status, H=H, info=info, weights=w, sigma=sigma, ratios=ratios, gaps=gaps, edge=edge,
-                start=con["start"], gap=con["gap"], edge_T=con["edge_T"])
+    n_zero = int(us.sum()) - con["n_start"] if con["winner"] else 0
+    out = hr.homography_law(m, ms, usable, lam, depth_scale, n_iter, sigma_min, start=con["start"], n_zero=n_zero)
+    out["info"][6:8] = con["winner"], con["n_start"]
+    out.update(start=con["start"], gap=con["gap"], edge_T=con["edge_T"])
+    return out
 
 
 def homography_consensus_from_details(det, b, cam_status, K, lam, depth_scale, n_iter, pitch_u, pitch_v, n_hyp, seed):

@@ -179,17 +179,19 @@ def median_middle(x):
     return (s[(n - 1) >> 1] + s[n >> 1]) * 0.5
 
 
-def homography_law(m, ms, usable, lam, depth_scale=1.0, n_iter=0, sigma_min=0.0):
+def homography_law(m, ms, usable, lam, depth_scale=1.0, n_iter=0, sigma_min=0.0, start=None, n_zero=0):
     """The law on given points (the seam vitvs_op_homography_law).  ``usable`` [n]: > 0 a usable row.  -> dict(v [6], status, H,
     info [8], weights [n], sigma, ratios, edge): info = usable rows, Jacobi sweeps of the last solve, re-weightings done, usable
     rows with final weight 0, degenerate flag, rows with rho = inf at the last re-weighting, 0, 0; ``ratios`` = every solve's
-    ev_2 / trace(M), ``gaps`` = every solve's (ev_2 - ev_1) / trace(M), ``edge`` = the closest |rho / (c sigma) - 1| of a usable row."""
+    ev_2 / trace(M), ``gaps`` = every solve's (ev_2 - ev_1) / trace(M), ``edge`` = the closest |rho / (c sigma) - 1| of a usable row.
+    ``start`` [n]: the weights of the first solve instead of 1 on every usable row, ``n_zero`` the usable rows it leaves at weight 0
+    (a consensus start: homography_consensus_ref)."""
     m, ms = np.asarray(m, np.float64).reshape(-1, 2), np.asarray(ms, np.float64).reshape(-1, 2)
     us = np.asarray(usable).reshape(-1) > 0
     m, ms = np.where(us[:, None], m, 0.0), np.where(us[:, None], ms, 0.0)
     n_us = int(us.sum())
-    w = np.where(us, 1.0, 0.0)
-    status, sweeps, reweighted, n_zero, degenerate, n_inf, sigma = OK, 0, 0, 0, 0, 0, 0.0
+    w = np.where(us, 1.0, 0.0) if start is None else np.array(start, np.float64).reshape(-1)
+    status, sweeps, reweighted, degenerate, n_inf, sigma = OK, 0, 0, 0, 0, 0.0
     H, mc = np.eye(3), np.zeros(2)
     ratios, gaps, edge = [], [], np.inf
     it = 0

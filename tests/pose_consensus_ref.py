@@ -1,12 +1,13 @@
 """The consensus start of the pose law in fp64 numpy ("The consensus start"): the statement the consensus phase of
-csrc/pose_core.h is tested against, in the kernel's order of arithmetic.
+csrc/consensus_core.h is tested against on csrc/pose_core.h's three-point model, in the kernel's order of arithmetic.  The draw, the
+score, the winner and the start are consensus_ref's, shared with homography_consensus_ref.
 
 Per pair, with the usable rows in ascending order, n_us of them (at least 3, else nothing is drawn), and the cut-off T = 4.6851
 sigma_min:
 
   draw      hypothesis j draws positions r_c = mix(mix(seed 0x9e3779b9 + j) + c) mod n_us for c = 0 .. 63 (32-bit integers), rejects
             repeats and stops at 3 distinct ones; without 3 it is skipped.  The 3 positions are then taken in ascending order, so a
-            row set gives one fit whatever the order it was drawn in.  (The draw of homography_consensus_ref with 3 positions.)
+            row set gives one fit whatever the order it was drawn in.
   solve     a triad per cloud x0, x1, x2: a = x1 - x0, b = x2 - x0, n = a x b, e1 = a / |a|, e3 = n / |n|, e2 = e3 x e1;
             R = sum_m e_m(Q) e_m(P)^T, t = qm - R pm with the means of the three points.  Skipped when either cloud has
             |n|^2 <= 1e-8 |a|^2 |b|^2 (collinear or coincident points) or an entry of R or t is not finite.
@@ -24,28 +25,16 @@ from __future__ import annotations
 
 import numpy as np
 
+import consensus_ref as cs
 import pose_ref as pr
-from homography_consensus_ref import mix
+from consensus_ref import DRAWS, MAX_HYP, mix  # noqa: F401
 
-MAX_HYP = 4096
-DRAWS = 64
 COLLINEAR_TOL = 1e-8   # a hypothesis with |a x b|^2 <= COLLINEAR_TOL |a|^2 |b|^2 in either cloud is skipped
 
 
 def draw(seed, n_hyp, n_us):
-    """-> (pos int64 [n_hyp, 3] ascending, ok bool [n_hyp]) for the hypotheses j = 0 .. n_hyp - 1; a function of (seed, j, n_us)."""
-    j = np.arange(n_hyp, dtype=np.uint64)
-    base = mix(((np.uint64(int(seed) & 0xFFFFFFFF) * np.uint64(0x9E3779B9)) & np.uint64(0xFFFFFFFF)) + j)
-    pos = np.full((n_hyp, 3), -1, np.int64)
-    cnt = np.zeros(n_hyp, np.int64)
-    for c in range(DRAWS):
-        r = (mix(base + np.uint64(c)) % np.uint64(n_us)).astype(np.int64)
-        new = (cnt < 3) & ~(pos == r[:, None]).any(1)
-        rows = np.nonzero(new)[0]
-        pos[rows, cnt[rows]] = r[rows]
-        cnt[rows] += 1
-    ok = cnt == 3
-    return np.where(ok[:, None], np.sort(pos, 1), -1), ok
+    """consensus_ref.draw with 3 positions."""
+    return cs.draw(seed, n_hyp, n_us, 3)
 
 
 def _triad(x):
@@ -91,43 +80,11 @@ def residual_sq(R, t, P, Q):
 
 
 def consensus(P, Q, usable, sigma_min, n_hyp, seed):
-    """The consensus phase on one pair's points -> dict(winner (j + 1, or 0), start [n] weights, n_start, costs [n_hyp], gap, edge_T,
-    R, t (the winner's, or None)): ``gap`` = (C' - C) / C' with C the winner's cost and C' the best cost of a hypothesis with another
-    row set (inf when there is none), ``edge_T`` = the closest |rho_k / T - 1| of a usable row under the winner."""
+    """consensus_ref.consensus on one pair's points with three_point and residual_sq -> its dict with the winner's ``R``, ``t`` (or
+    None) for ``model``."""
     P, Q = np.asarray(P, np.float64).reshape(-1, 3), np.asarray(Q, np.float64).reshape(-1, 3)
-    us = np.asarray(usable).reshape(-1) > 0
-    rows = np.nonzero(us)[0]
-    n_us = len(rows)
-    out = dict(winner=0, start=np.where(us, 1.0, 0.0), n_start=0, costs=np.full(n_hyp, np.inf), gap=np.inf, edge_T=np.inf, R=None, t=None)
-    if n_hyp < 1 or n_us < 3:
-        return out
-    out["n_start"] = n_us
-    T = pr.TUKEY_C * sigma_min
-    T2 = T * T
-    pos, ok = draw(seed, n_hyp, n_us)
-    sets = rows[np.where(ok[:, None], pos, 0)]
-    R, t, solved = three_point(P[sets], Q[sets])
-    ok &= solved
-    q = residual_sq(R, t, P[rows], Q[rows])
-    with np.errstate(all="ignore"):
-        terms = np.where(q < T2, q, T2)
-        costs = np.zeros(n_hyp)
-        for k in range(n_us):                                # ascending rows, one after the other
-            costs = costs + terms[:, k]
-    costs = np.where(ok, costs, np.inf)
-    costs = np.where(costs >= 0.0, costs, np.inf)            # (a NaN cost ranks with the skipped ones)
-    out["costs"] = costs
-    j = int(np.argmin(costs))                                # the first of equal minima: ties go to the smallest j
-    if not costs[j] < np.inf:
-        return out
-    other = ok & (pos != pos[j]).any(1)
-    if other.any():
-        c2 = float(costs[other].min())
-        out["gap"] = (c2 - float(costs[j])) / c2 if c2 < np.inf and c2 > 0.0 else (np.inf if c2 == np.inf else 0.0)
-    rho = np.full(len(P), np.inf)
-    rho[rows] = np.sqrt(q[j])
-    start = np.where(us & (rho <= T), 1.0, 0.0)
-    out.update(winner=j + 1, start=start, n_start=int(start.sum()), R=R[j], t=t[j], edge_T=float(np.abs(rho[us] / T - 1.0).min()))
+    out = cs.consensus((P, Q), usable, pr.TUKEY_C * sigma_min, n_hyp, seed, 3, three_point, residual_sq)
+    out["R"], out["t"] = out.pop("model") or (None, None)
     return out
 
 
@@ -138,48 +95,16 @@ def pose_consensus_law(P, Q, usable, lam, n_iter=0, sigma_min=0.0, n_hyp=0, seed
     usable = np.asarray(usable).reshape(-1)
     us = usable > 0
     P, Q = np.where(us[:, None], P, 0.0), np.where(us[:, None], Q, 0.0)
-    n_us, holes = int(us.sum()), int((usable < 0).sum())
     if n_hyp < 1:
         out = pr.pose_law(P, Q, usable, lam, n_iter, sigma_min)
         out.update(start=np.where(us, 1.0, 0.0), cgap=np.inf, edge_T=np.inf)
         return out
     con = consensus(P, Q, us, sigma_min, n_hyp, seed)
-    w = con["start"].copy()
-    n_zero = n_us - con["n_start"] if con["winner"] else 0
-    status, sweeps, reweighted, degenerate, sigma = pr.OK, 0, 0, 0, 0.0
-    R, t, q, gap, scatter = np.eye(3), np.zeros(3), np.array([1.0, 0, 0, 0]), 0.0, 0.0
-    gaps, edge = [], np.inf
-    it = 0
-    while True:                                              # pose_ref.pose_law's loop from other start weights
-        if n_us - n_zero < 3:
-            status = pr.TOO_FEW
-            break
-        h = pr.horn(P, Q, w)
-        sweeps, gap, scatter = h["sweeps"], h["gap"], h["scatter"]
-        gaps.append(gap / scatter if scatter > 0.0 else 0.0)
-        if h["degenerate"]:
-            degenerate, status = 1, pr.TOO_FEW
-            break
-        R, t, q = h["R"], h["t"], h["q"]
-        if it == n_iter:
-            break
-        d = Q - (P @ R.T + t)
-        rho = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
-        sigma = max(1.4826 * pr.median_middle(rho[us]), sigma_min)
-        tt = rho / (pr.TUKEY_C * sigma)
-        u = 1.0 - tt * tt
-        edge = min(edge, float(np.abs(tt[us] - 1.0).min()))
-        w = np.where(us & (tt < 1.0), u * u, 0.0)
-        n_zero = int((us & (w == 0.0)).sum())
-        it += 1
-        reweighted = it
-    if status != pr.OK:
-        R, t, v = np.eye(3), np.zeros(3), np.zeros(6)
-    else:
-        v = pr.twist(R, t, q, lam)
-    info = np.array([n_us, sweeps, reweighted, n_zero, degenerate, holes, con["winner"], con["n_start"]], np.int32)
-    return dict(v=v, status=status, R=R, t=t, info=info, weights=w, sigma=sigma, gap=gap, scatter=scatter, gaps=gaps, edge=edge,
-                start=con["start"], cgap=con["gap"], edge_T=con["edge_T"])
+    n_zero = int(us.sum()) - con["n_start"] if con["winner"] else 0
+    out = pr.pose_law(P, Q, usable, lam, n_iter, sigma_min, start=con["start"], n_zero=n_zero)
+    out["info"][6:8] = con["winner"], con["n_start"]
+    out.update(start=con["start"], cgap=con["gap"], edge_T=con["edge_T"])
+    return out
 
 
 def pose_consensus_from_details(det, b, cam_status, K, table, lam, n_iter, pitch_u, pitch_v, n_hyp, seed):

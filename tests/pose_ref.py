@@ -116,16 +116,18 @@ def twist(R, t, q, lam):
     return np.concatenate([-lam * (R.T @ t), -lam * theta_u(q)])
 
 
-def pose_law(P, Q, usable, lam, n_iter=0, sigma_min=0.0):
+def pose_law(P, Q, usable, lam, n_iter=0, sigma_min=0.0, start=None, n_zero=0):
     """The law on given points (the seam vitvs_op_pose_law).  ``usable`` [n]: > 0 a usable row, 0 a padded one, < 0 a hole (a row
     dropped for want of a depth).  -> dict(v [6], status, R, t, info [8], weights [n], sigma, gap, scatter): info = usable rows,
-    Jacobi sweeps of the last solve, re-weightings done, usable rows with final weight 0, degenerate flag, holes dropped, 0, 0."""
+    Jacobi sweeps of the last solve, re-weightings done, usable rows with final weight 0, degenerate flag, holes dropped, 0, 0.
+    ``start`` [n]: the weights of the first solve instead of 1 on every usable row, ``n_zero`` the usable rows it leaves at weight 0
+    (a consensus start: pose_consensus_ref)."""
     P, Q = np.asarray(P, np.float64).reshape(-1, 3), np.asarray(Q, np.float64).reshape(-1, 3)
     usable = np.asarray(usable).reshape(-1)
     us = usable > 0
     n_us, holes = int(us.sum()), int((usable < 0).sum())
-    w = np.where(us, 1.0, 0.0)
-    status, sweeps, reweighted, n_zero, degenerate, sigma = OK, 0, 0, 0, 0, 0.0
+    w = np.where(us, 1.0, 0.0) if start is None else np.array(start, np.float64).reshape(-1)
+    status, sweeps, reweighted, degenerate, sigma = OK, 0, 0, 0, 0.0
     R, t, q, gap, scatter = np.eye(3), np.zeros(3), np.array([1.0, 0, 0, 0]), 0.0, 0.0
     gaps, edge = [], np.inf                               # every solve's relative gap; the closest |rho / (c sigma) - 1| of a usable row
     it = 0

@@ -1,5 +1,5 @@
 """The consensus start of the homography law on the CPU: what tests/homography_consensus_ref.py buys with wrong
-matches, its draw, its four-point solve and its fallback, the Python arguments refused before any device call, the new symbols, the
+matches, its four-point solve and its fallback, the Python arguments refused before any device call, the new symbols, the
 launch plan, and the margins of every case tests/test_gpu_homography_consensus_op.py runs.  No GPU call.
 
 The bars of the wrong-match table are the issue's; the figures measured with the reference as committed are printed by the test and
@@ -79,38 +79,6 @@ def test_no_hypotheses_is_the_law_itself():
         a = hr.homography_law(m, ms, np.ones(24), 1.0, 0.61, n_iter, SIGMA_MIN)
         b = cr.homography_consensus_law(m, ms, np.ones(24), 1.0, 0.61, n_iter, SIGMA_MIN, 0, 5)
         assert all(np.array_equal(a[k], b[k]) for k in ("v", "H", "weights", "sigma", "status", "info"))
-
-
-# ---------------------------------------------------------------------------------------------- the draw
-def _mix(x):
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & 0xFFFFFFFF
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & 0xFFFFFFFF
-    return x ^ (x >> 16)
-
-
-def test_the_draw():
-    """4 distinct positions below n_us for n_us in 4 .. 300 and j < 4096 (none skipped there), a function of (seed, j, n_us) alone,
-    and the rule as stated, in plain integers."""
-    for n_us in range(4, 301):
-        pos, ok = cr.draw(0, 4096, n_us)
-        assert ok.all(), n_us
-        assert (pos >= 0).all() and (pos < n_us).all() and (np.diff(pos, axis=1) > 0).all(), n_us
-    for seed, n_us in ((0, 4), (1, 5), (0xFFFFFFFF, 24), (123456789, 297)):
-        pos, ok = cr.draw(seed, 300, n_us)
-        again, _ = cr.draw(seed, 100, n_us)                      # (not of the number of hypotheses)
-        assert np.array_equal(pos[:100], again)
-        for j in (0, 1, 99, 299):
-            base, got, c = _mix((seed * 0x9E3779B9 + j) & 0xFFFFFFFF), [], 0
-            while len(got) < 4:
-                r = _mix((base + c) & 0xFFFFFFFF) % n_us
-                c += 1
-                if r not in got:
-                    got.append(r)
-            assert c <= 64 and sorted(got) == list(pos[j]), (seed, n_us, j)
-    assert not np.array_equal(cr.draw(0, 64, 24)[0], cr.draw(1, 64, 24)[0])
-    assert not np.array_equal(cr.draw(0, 64, 24)[0], cr.draw(0, 64, 25)[0])
 
 
 # ---------------------------------------------------------------------------------------------- the four-point solve

@@ -13,8 +13,10 @@
 // computes the same rotation, lanes 0 .. 8 turn the rows of M and lanes 16 .. 24 the rows of V, in the reference's order of
 // arithmetic.  ROBUST: n_iter Tukey re-weightings on the transfer error with rho and w in dynamic LDS (median_middles and
 // tukey_reweight of robust_core.h), one more solve behind the last.  CONSENSUS: a phase between Phase A and the solve loop scores
-// n_hyp four-point hypotheses, one per thread and round, and starts the loop from the winner's consensus set (below, at hom_draw).
+// n_hyp four-point hypotheses, one per thread and round, and starts the loop from the winner's consensus set (consensus_core.h's
+// consensus_start on the model HomFourPoint below).
 #include "common.h"
+#include "consensus_core.h"
 #include "kernels.h"
 #include "robust_core.h"
 #include "solve.h"
@@ -23,8 +25,8 @@
 
 namespace vitvs {
 
-// dynamic LDS in doubles: slices [8][64] | the results below | ROBUST: rho [ld] | w [ld] | CONSENSUS: the waves' best costs [4],
-// as ints their best j [4] and their start weights at 1 [4] | as ints the usable rows in ascending order [ld, rounded up to even]
+// dynamic LDS in doubles: slices [8][64] | the results below | ROBUST: rho [ld] | w [ld] | CONSENSUS: consensus_core.h's cells and
+// row list
 constexpr int kHomSum = 8 * 64;          // [0 .. 45): the upper triangle of M, row-major
 constexpr int kHomCen = kHomSum + 48;    // sw, c [2], c* [2], dbar, dbar*, trace(M)
 constexpr int kHomA = kHomCen + 8;       // M [9][9], turned in place
@@ -34,7 +36,6 @@ constexpr int kHomMid = kHomH + 12;      // the two middle values of the median
 constexpr int kHomInt = kHomMid + 2;     // ints: [0] solve outcome (0 ok, 1 degenerate), [1] sweeps, [2 .. 6) the waves' zero weights,
                                          //       [6 .. 10) their usable rows, [10 .. 14) their rows with rho = inf
 constexpr int kHomHead = kHomInt + 8;
-constexpr int kHomCons = 8;              // doubles of the consensus cells in front of the usable-row list
 
 // Orders the LDS traffic of ONE wave: its lanes run in lock step and the LDS serves a wave's accesses in issue order, so this
 // only has to keep the compiler from moving them.
@@ -158,11 +159,8 @@ __device__ __forceinline__ bool hom_solve(double* sm, int lane, int& sweeps) {
     return ok;
 }
 
-// ---- the consensus start ("The consensus start"); tests/homography_consensus_ref.py restates every line below in
-// the same order of arithmetic
-// The 4 distinct positions of hypothesis j in a list of n_us usable rows, ascending: robust_core.h's draw, which the pose law's
-// three-point hypotheses share
-__device__ __forceinline__ bool hom_draw(unsigned seed, int j, int n_us, int* pos) { return consensus_draw<4>(seed, j, n_us, pos); }
+// ---- the model of the consensus start ("The consensus start"; the phase itself is consensus_core.h's);
+// tests/homography_consensus_ref.py restates every line below in the same order of arithmetic
 
 // B = A diag(adj(A) (x3, y3, 1)), A with the columns (x_i, y_i, 1), i = 0 .. 2: the map of the projective basis onto four points.
 // The l_i and their sum (det A) are twice the signed areas of the four triangles of the points: false when one of them is <= 1e-8
@@ -226,85 +224,16 @@ __device__ __forceinline__ double hom_transfer_sq(const double* H, const double*
     return d0 * d0 + d1 * d1;
 }
 
-// The consensus phase, all 256 threads, behind Phase A's barrier and with n_us >= 4.  Thread t scores the hypotheses t, t + 256, ..
-// with the truncated cost C_j = sum over the usable rows, ascending, of min(rho^2, T^2) (T = 4.6851 sigma_min; a skipped
-// hypothesis costs +inf) and keeps its best (cost, j) in registers; costs are >= +0, so (cost bits, j) orders by integer compares
-// and ties go to the smallest j.  One reduction: a butterfly within each wave, then 4 cells in LDS.  Every thread then solves
-// the winner again and the start weights are 1 where rho <= T and 0 elsewhere, into `start` (LDS for the robust form, the flags'
-// row of the workspace for the plain one).  Returns the winner's j + 1 and the number of start weights at 1, or 0 and n_us when
-// every hypothesis was skipped (the weights stay at 1: the start without consensus).  The caller's barrier follows.
-template <bool ROBUST>
-__device__ __forceinline__ int hom_consensus(const HomographyArgs& a, double* ws, double* cons, double* start, int n, int n_us,
-                                             double sigma_min, int tid, int& n_start) {
-    const int lane = tid & 63, wave = tid >> 6, ld = a.ld;
-    unsigned long long* cell_cost = reinterpret_cast<unsigned long long*>(cons);
-    int* cell_j = reinterpret_cast<int*>(cons + 4);
-    int* cell_ones = cell_j + 4;
-    int* list = reinterpret_cast<int*>(cons + kHomCons);
-    const double* flag = ws + (size_t)4 * ld;
-    if (wave == 0) {                                        // the usable rows in ascending order: wave 0, 64 rows a step
-        int base = 0;
-        for (int k0 = 0; k0 < n; k0 += 64) {
-            const int k = k0 + lane;
-            const bool f = k < n && flag[k] > 0.0;
-            const unsigned long long bal = __ballot(f);
-            if (f) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = k;
-            base += __popcll(bal);
-        }
+// One hypothesis of the law's consensus start (consensus_core.h's consensus_start): four rows, the homography in closed form
+struct HomFourPoint {
+    static constexpr int kRows = 4, kFlagRow = 4, kFit = 9;                    // H, row-major
+    static __device__ __forceinline__ bool fit(const double* ws, int ld, const int* rows, double* H) {
+        return hom_four_point(ws, ld, rows, H);
     }
-    lds_barrier();
-    const double T = 4.6851 * sigma_min, T2 = T * T;
-    unsigned long long best = kInfBits;
-    int best_j = 0x7fffffff;
-    for (int j = tid; j < a.n_hyp; j += 256) {
-        int pos[4], rows[4];
-        double H[9];
-        if (!hom_draw(a.seed, j, n_us, pos)) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rows[i] = list[pos[i]];
-        if (!hom_four_point(ws, ld, rows, H)) continue;
-        double cost = 0.0;
-        for (int p = 0; p < n_us; ++p) {                    // (every lane reads the same row: one broadcast load each)
-            const double q = hom_transfer_sq(H, ws, ld, list[p]);
-            cost += q < T2 ? q : T2;
-        }
-        const unsigned long long key = (unsigned long long)__double_as_longlong(cost);
-        if (key < best) { best = key; best_j = j; }         // (j ascends: a tie keeps the smaller one)
+    static __device__ __forceinline__ double residual_sq(const double* H, const double* ws, int ld, int r) {
+        return hom_transfer_sq(H, ws, ld, r);
     }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long oc = shfl_xor_u64(best, o);
-        const int oj = __shfl_xor(best_j, o, WAVE);
-        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
-    }
-    if (lane == 0) { cell_cost[wave] = best; cell_j[wave] = best_j; }
-    lds_barrier();
-    best = cell_cost[0]; best_j = cell_j[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const unsigned long long oc = cell_cost[w];
-        const int oj = cell_j[w];
-        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
-    }
-    if (best >= kInfBits) { n_start = n_us; return 0; }     // every hypothesis skipped: the same for every thread
-    int pos[4], rows[4], ones = 0;
-    double H[9];
-    hom_draw(a.seed, best_j, n_us, pos);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rows[i] = list[pos[i]];
-    hom_four_point(ws, ld, rows, H);
-    for (int k = tid; k < n; k += 256) {
-        if (!(flag[k] > 0.0)) continue;
-        const double w1 = sqrt(hom_transfer_sq(H, ws, ld, k)) <= T ? 1.0 : 0.0;
-        start[k] = w1;
-        ones += w1 > 0.0 ? 1 : 0;
-    }
-    ones = wave_sum(ones);
-    if (lane == 0) cell_ones[wave] = ones;
-    if constexpr (ROBUST) lds_barrier(); else __syncthreads();    // (the plain form's start weights are global memory: full fence)
-    n_start = cell_ones[0] + cell_ones[1] + cell_ones[2] + cell_ones[3];
-    return best_j + 1;
-}
+};
 
 template <bool ROBUST, bool CONSENSUS>
 __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
@@ -388,8 +317,8 @@ __global__ __launch_bounds__(256) void homography_kernel(HomographyArgs a) {
     int winner = 0, n_start = 0;
     if constexpr (CONSENSUS) {
         if (n_us >= 4) {
-            winner = hom_consensus<ROBUST>(a, ws, rho + (ROBUST ? 2 * ld : 0), ROBUST ? wk : ws + (size_t)4 * ld, n, n_us, sigma_min,
-                                           tid, n_start);
+            winner = consensus_start<ROBUST, HomFourPoint>(ws, ld, n, n_us, a.n_hyp, a.seed, 4.6851 * sigma_min,
+                                                           rho + (ROBUST ? 2 * ld : 0), ROBUST ? wk : ws + (size_t)4 * ld, n_start);
             if (winner) n_zero = n_us - n_start;            // the rows outside the consensus set start at weight 0
         }
     }
@@ -551,8 +480,8 @@ int plan_homography(int max_rows, int n_iter, int n_hyp, HomographyPlan* plan) {
     if (!plan || max_rows < 1 || n_iter < 0 || n_iter > 16 || n_hyp < 0 || n_hyp > 4096) return -2;
     plan->robust = n_iter > 0;
     plan->consensus = n_hyp > 0;
-    plan->lds = ((size_t)kHomHead + (plan->robust ? (size_t)2 * max_rows : 0) +
-                 (plan->consensus ? (size_t)kHomCons + ((size_t)max_rows + 1) / 2 : 0)) * sizeof(double);
+    plan->lds = ((size_t)kHomHead + (plan->robust ? (size_t)2 * max_rows : 0) + (plan->consensus ? consensus_lds_doubles(max_rows) : 0)) *
+                sizeof(double);
     plan->lds_opt_in = plan->lds > 64 * 1024;
     return plan->lds > 160 * 1024 ? -3 : 0;
 }
@@ -566,20 +495,12 @@ int launch_homography(const HomographyArgs& a, hipStream_t stream) {
     HomographyPlan p;
     if (int rc = plan_homography(a.ld, a.n_iter, a.n_hyp, &p)) return rc;
     if (p.consensus && !a.K && !(a.sigma_min > 0.0)) return -2;      // the cut-off T = 4.6851 sigma_min has to be positive
-    static std::atomic<unsigned long long> raised{0}, raised_rc{0}, raised_c{0};
-    if (p.robust && p.consensus) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<true, true>), 160 * 1024, raised_rc)) return -3;
-        launch(homography_kernel<true, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else if (p.consensus) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<false, true>), 160 * 1024, raised_c)) return -3;
-        launch(homography_kernel<false, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else if (p.robust) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(homography_kernel<true, false>), 160 * 1024, raised)) return -3;
-        launch(homography_kernel<true, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else {
-        launch(homography_kernel<false, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    if (p.robust) {
+        return p.consensus ? launch_planned<homography_kernel<true, true>>(p, a, stream)
+                           : launch_planned<homography_kernel<true, false>>(p, a, stream);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return p.consensus ? launch_planned<homography_kernel<false, true>>(p, a, stream)
+                       : launch_planned<homography_kernel<false, false>>(p, a, stream);
 }
 
 }  // namespace vitvs

@@ -57,6 +57,15 @@ inline int raise_lds_limit(const void* fn, int bytes, std::atomic<unsigned long 
     done.fetch_or(1ull << dev, std::memory_order_relaxed);
     return 0;
 }
+// The launch of a follow-on law from its plan, one 256-thread workgroup per pair: `kernel` is the instantiation the plan's booleans
+// name, and the opt-in flag is that instantiation's own.  -3: the opt-in failed; -1: the launch did.
+template <auto kernel, class Plan, class Args>
+inline int launch_planned(const Plan& p, const Args& a, hipStream_t stream) {
+    static std::atomic<unsigned long long> raised{0};
+    if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(kernel), 160 * 1024, raised)) return -3;
+    launch(kernel, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 // operand type of the GEMMs / attention; fp32 accumulate.  PREC_X2 = split-f16 (common.h hx2): every operand is an fp16
 // hi / lo pair, rows are [hi of 32 columns | lo of the same 32] per 64 fp16, three f16 MFMAs per k-step: fp32-class results
@@ -504,7 +513,8 @@ struct PoseArgs {
 };
 struct PosePlan {
     size_t lds;               // dynamic LDS of the launch: (320 + (robust ? 2 max_rows : consensus ? max_rows : 0) +
-                              // (consensus ? 8 + (max_rows + 1) / 2 : 0)) doubles
+                              // (consensus ? 8 + (max_rows + 1) / 2 : 0)) doubles, the last term consensus_core.h's
+                              // consensus_lds_doubles
     bool robust;              // pose_kernel<robust, consensus>
     bool lds_opt_in;          // > 64 KiB
     bool consensus;
@@ -609,7 +619,7 @@ struct HomographyArgs {
 };
 struct HomographyPlan {
     size_t lds;               // dynamic LDS of the launch: (752 + (robust ? 2 max_rows : 0) + (consensus ? 8 + (max_rows + 1) / 2 : 0))
-                              // doubles
+                              // doubles, the last term consensus_core.h's consensus_lds_doubles
     bool robust;              // homography_kernel<robust, consensus>
     bool lds_opt_in;          // > 64 KiB
     bool consensus;

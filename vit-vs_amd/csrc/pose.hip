@@ -14,7 +14,8 @@
 // and tukey_reweight of robust_core.h), one more solve behind the last.  The loop is pose_core.h's pose_align, which the pose rig
 // law runs too; this file keeps the early outs, Phase A, sigma_min and the outputs.  CONSENSUS: a phase between Phase A and the
 // loop scores n_hyp three-point hypotheses, one per thread and round, and starts the loop from the winner's consensus set
-// (pose_core.h's pose_consensus); the plain form then takes the median of Z* too, for the cut-off T = 4.6851 sigma_min.
+// (consensus_core.h's consensus_start on pose_core.h's PoseThreePoint); the plain form then takes the median of Z* too, for the
+// cut-off T = 4.6851 sigma_min.
 #include "common.h"
 #include "kernels.h"
 #include "pose_core.h"
@@ -110,8 +111,9 @@ __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a) {
     int winner = 0, n_start = 0, n_zero0 = 0;
     if constexpr (CONSENSUS) {
         if (n_us >= 3) {
-            winner = pose_consensus<ROBUST>(ws, ld, n, n_us, a.n_hyp, a.seed, 4.6851 * sigma_min, rho + (ROBUST ? 2 : 1) * (size_t)ld,
-                                            ROBUST ? wk : ws + (size_t)6 * ld, n_start);
+            winner = consensus_start<ROBUST, PoseThreePoint>(ws, ld, n, n_us, a.n_hyp, a.seed, 4.6851 * sigma_min,
+                                                             rho + (ROBUST ? 2 : 1) * (size_t)ld, ROBUST ? wk : ws + (size_t)6 * ld,
+                                                             n_start);
             if (winner) n_zero0 = n_us - n_start;
         }
     }
@@ -153,8 +155,7 @@ int plan_pose(int max_rows, int n_iter, int n_hyp, PosePlan* plan) {
     plan->consensus = n_hyp > 0;
     // rho and w of the robust form; the plain form with a consensus start keeps rho alone, for the median of Z* behind its cut-off
     const size_t per_row = plan->robust ? 2 : (plan->consensus ? 1 : 0);
-    plan->lds = ((size_t)kPoseHead + per_row * max_rows + (plan->consensus ? (size_t)kPoseCons + ((size_t)max_rows + 1) / 2 : 0)) *
-                sizeof(double);
+    plan->lds = ((size_t)kPoseHead + per_row * max_rows + (plan->consensus ? consensus_lds_doubles(max_rows) : 0)) * sizeof(double);
     plan->lds_opt_in = plan->lds > 64 * 1024;
     return plan->lds > 160 * 1024 ? -3 : 0;
 }
@@ -167,20 +168,10 @@ int launch_pose(const PoseArgs& a, hipStream_t stream) {
     PosePlan p;
     if (int rc = plan_pose(a.ld, a.n_iter, a.n_hyp, &p)) return rc;
     if (p.consensus && !a.K && !(a.sigma_min > 0.0)) return -2;      // the cut-off T = 4.6851 sigma_min has to be positive
-    static std::atomic<unsigned long long> raised{0}, raised_rc{0}, raised_c{0};
-    if (p.robust && p.consensus) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true, true>), 160 * 1024, raised_rc)) return -3;
-        launch(pose_kernel<true, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else if (p.consensus) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<false, true>), 160 * 1024, raised_c)) return -3;
-        launch(pose_kernel<false, true>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else if (p.robust) {
-        if (p.lds_opt_in && raise_lds_limit(reinterpret_cast<const void*>(pose_kernel<true, false>), 160 * 1024, raised)) return -3;
-        launch(pose_kernel<true, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
-    } else {
-        launch(pose_kernel<false, false>, dim3(a.n_pairs), dim3(256), p.lds, stream, a);
+    if (p.robust) {
+        return p.consensus ? launch_planned<pose_kernel<true, true>>(p, a, stream) : launch_planned<pose_kernel<true, false>>(p, a, stream);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return p.consensus ? launch_planned<pose_kernel<false, true>>(p, a, stream) : launch_planned<pose_kernel<false, false>>(p, a, stream);
 }
 
 }  // namespace vitvs

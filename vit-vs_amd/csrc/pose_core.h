@@ -1,9 +1,10 @@
 // What the pose law (pose.hip) and the pose rig law (pose_rig.hip) share: the handle's form of a point
 // row, the layout of the head of their dynamic LDS, Horn's solve (a cyclic Jacobi eigen-decomposition of the 4 x 4 matrix in fp64,
 // all indices compile-time: no scratch), the alignment loop around it (pose_align) and the twist.  The median and the Tukey step
-// of the loop are robust_core.h's.
+// of the loop are robust_core.h's.  At the end: the three-point model of the pose law's consensus start (consensus_core.h).
 #pragma once
 #include "common.h"
+#include "consensus_core.h"
 #include "kernels.h"
 #include "robust_core.h"
 #include "solve.h"
@@ -123,6 +124,16 @@ __device__ __forceinline__ bool pose_solve(const double* sm, double (&R)[9], dou
     return !(ev1 - ev2 <= 1e-8 * scatter);
 }
 
+// |Q_r - (R P_r + t)|^2: the squared residual of row r of a point block (pose_align's rho before the square root, and what the
+// consensus start scores)
+__device__ __forceinline__ double pose_residual_sq(const double* R, const double* t, const double* ws, int stride, int r) {
+    const double p0 = ws[r], p1 = ws[(size_t)stride + r], p2 = ws[(size_t)2 * stride + r];
+    const double d0 = ws[(size_t)3 * stride + r] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
+    const double d1 = ws[(size_t)4 * stride + r] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
+    const double d2 = ws[(size_t)5 * stride + r] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
+    return (d0 * d0 + d1 * d1) + d2 * d2;
+}
+
 // What pose_align leaves in every thread's registers
 struct PoseFit {
     double R[9], t[3], q[4];
@@ -137,7 +148,7 @@ struct PoseFit {
 // (LDS) holds the caller's first weights on entry and the last ones on return; rho (LDS) holds +inf in every row that is not usable.
 // Every barrier here orders LDS only (lds_barrier): the loop writes nothing but LDS (smp, rho, wk).  The point block is global
 // memory, but the caller wrote it before the __syncthreads() that follows its Phase A, and the loop only reads it.
-// A consensus start (pose_consensus below) hands over its weights where the loop reads them (wk, or the flag row in the plain form)
+// A consensus start (consensus_core.h) hands over its weights where the loop reads them (wk, or the flag row in the plain form)
 // and n_zero0, the usable rows it left at weight 0.
 template <bool ROBUST>
 __device__ __forceinline__ void pose_align(const double* ws, int stride, int n, int n_us, double sigma_min, int n_iter, double* smp,
@@ -222,15 +233,9 @@ __device__ __forceinline__ void pose_align(const double* ws, int stride, int n, 
         for (int i = 0; i < 4; ++i) fit.q[i] = smp[kPoseRt + 12 + i];
         if (it == N) break;
         if constexpr (ROBUST) {
-            const double* R = fit.R;
-            const double* t = fit.t;
             for (int k = tid; k < n; k += 256) {
                 if (!(flag[k] > 0.0)) continue;             // not a usable row: rho stays +inf
-                const double p0 = ws[k], p1 = ws[(size_t)stride + k], p2 = ws[(size_t)2 * stride + k];
-                const double d0 = ws[(size_t)3 * stride + k] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
-                const double d1 = ws[(size_t)4 * stride + k] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
-                const double d2 = ws[(size_t)5 * stride + k] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
-                rho[k] = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+                rho[k] = sqrt(pose_residual_sq(fit.R, fit.t, ws, stride, k));
             }
             lds_barrier();
             median_middles(rho, n, n_us, smp + kPoseMid, tid);
@@ -257,10 +262,8 @@ __device__ __forceinline__ void pose_twist(double lambda, const PoseFit& fit, do
     }
 }
 
-// ---- the consensus start ("The consensus start"); tests/pose_consensus_ref.py restates every line below in the same
-// order of arithmetic.  Behind the law's dynamic LDS: the waves' best costs [4], as ints their best j [4] and their start weights
-// at 1 [4] | as ints the usable rows in ascending order [rows, rounded up to even]
-constexpr int kPoseCons = 8;             // doubles of the consensus cells in front of the usable-row list
+// ---- the model of the consensus start ("The consensus start"; the phase itself is consensus_core.h's);
+// tests/pose_consensus_ref.py restates every line below in the same order of arithmetic
 
 // The orthonormal triad of three points: e1 along x1 - x0, e3 along the normal of their plane, e2 = e3 x e1 (rows of e).  False when
 // the points are collinear or coincide: |a x b|^2 <= 1e-8 |a|^2 |b|^2.
@@ -285,7 +288,7 @@ __device__ __forceinline__ bool pose_triad(const double (&x)[3][3], double (&e)[
 
 // The rigid displacement of the three rows `rows` in closed form: R carries the triad of the current points onto that of the goal
 // points, t = qm - R pm with the means of the three.  False when either triple is collinear or an entry is not finite.
-__device__ __forceinline__ bool pose_three_point(const double* ws, int stride, const int* rows, double (&R)[9], double (&t)[3]) {
+__device__ __forceinline__ bool pose_three_point(const double* ws, int stride, const int* rows, double* R, double* t) {
     double p[3][3], g[3][3], ep[3][3], eg[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -317,94 +320,15 @@ __device__ __forceinline__ bool pose_three_point(const double* ws, int stride, c
     return spread && spread_g && finite;
 }
 
-// |Q_r - (R P_r + t)|^2 in pose_align's own residual arithmetic, before its square root
-__device__ __forceinline__ double pose_residual_sq(const double (&R)[9], const double (&t)[3], const double* ws, int stride, int r) {
-    const double p0 = ws[r], p1 = ws[(size_t)stride + r], p2 = ws[(size_t)2 * stride + r];
-    const double d0 = ws[(size_t)3 * stride + r] - (((R[0] * p0 + R[1] * p1) + R[2] * p2) + t[0]);
-    const double d1 = ws[(size_t)4 * stride + r] - (((R[3] * p0 + R[4] * p1) + R[5] * p2) + t[1]);
-    const double d2 = ws[(size_t)5 * stride + r] - (((R[6] * p0 + R[7] * p1) + R[8] * p2) + t[2]);
-    return (d0 * d0 + d1 * d1) + d2 * d2;
-}
-
-// The consensus phase, all 256 threads, behind Phase A's barrier and with n_us >= 3.  Wave 0 compacts the usable rows of [0, n) into
-// an ascending list.  Thread t scores the hypotheses t, t + 256, .. with the truncated cost C_j = sum over the usable rows, ascending,
-// of min(q, T^2) (a skipped hypothesis costs +inf) and keeps its best (cost, j) in registers; costs are >= +0, so (cost bits, j)
-// orders by integer compares and ties go to the smallest j.  One reduction: a butterfly within each wave, then 4 cells in LDS.
-// Every thread then solves the winner again and the start weights are 1 where sqrt(q) <= T and 0 elsewhere, into `start` (LDS for
-// the robust form, the flags' row of the workspace for the plain one: there a usable row at weight 0 reads as an unusable one).
-// Returns the winner's j + 1 and the number of start weights at 1, or 0 and n_us when every hypothesis was skipped (nothing is
-// written: the start without consensus).  The last barrier is the phase's own.
-template <bool ROBUST>
-__device__ __forceinline__ int pose_consensus(const double* ws, int stride, int n, int n_us, int n_hyp, unsigned seed, double T,
-                                              double* cons, double* start, int& n_start) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long* cell_cost = reinterpret_cast<unsigned long long*>(cons);
-    int* cell_j = reinterpret_cast<int*>(cons + 4);
-    int* cell_ones = cell_j + 4;
-    int* list = reinterpret_cast<int*>(cons + kPoseCons);
-    const double* flag = ws + (size_t)6 * stride;
-    if (wave == 0) {                                        // the usable rows in ascending order: wave 0, 64 rows a step
-        int base = 0;
-        for (int k0 = 0; k0 < n; k0 += 64) {
-            const int k = k0 + lane;
-            const bool f = k < n && flag[k] > 0.0;
-            const unsigned long long bal = __ballot(f);
-            if (f) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = k;
-            base += __popcll(bal);
-        }
+// One hypothesis of the pose law's consensus start (consensus_core.h's consensus_start): three rows, the displacement in closed form
+struct PoseThreePoint {
+    static constexpr int kRows = 3, kFlagRow = 6, kFit = 12;                   // R row-major, t
+    static __device__ __forceinline__ bool fit(const double* ws, int stride, const int* rows, double* Rt) {
+        return pose_three_point(ws, stride, rows, Rt, Rt + 9);
     }
-    lds_barrier();
-    const double T2 = T * T;
-    unsigned long long best = kInfBits;
-    int best_j = 0x7fffffff;
-    for (int j = tid; j < n_hyp; j += 256) {
-        int pos[3], rows[3];
-        double R[9], t[3];
-        if (!consensus_draw<3>(seed, j, n_us, pos)) continue;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) rows[i] = list[pos[i]];
-        if (!pose_three_point(ws, stride, rows, R, t)) continue;
-        double cost = 0.0;
-        for (int p = 0; p < n_us; ++p) {                    // (every lane reads the same row: one broadcast load per point)
-            const double q = pose_residual_sq(R, t, ws, stride, list[p]);
-            cost += q < T2 ? q : T2;
-        }
-        const unsigned long long key = (unsigned long long)__double_as_longlong(cost);
-        if (key < best) { best = key; best_j = j; }         // (j ascends: a tie keeps the smaller one)
+    static __device__ __forceinline__ double residual_sq(const double* Rt, const double* ws, int stride, int r) {
+        return pose_residual_sq(Rt, Rt + 9, ws, stride, r);
     }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long oc = shfl_xor_u64(best, o);
-        const int oj = __shfl_xor(best_j, o, WAVE);
-        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
-    }
-    if (lane == 0) { cell_cost[wave] = best; cell_j[wave] = best_j; }
-    lds_barrier();
-    best = cell_cost[0]; best_j = cell_j[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const unsigned long long oc = cell_cost[w];
-        const int oj = cell_j[w];
-        if (oc < best || (oc == best && oj < best_j)) { best = oc; best_j = oj; }
-    }
-    if (best >= kInfBits) { n_start = n_us; return 0; }     // every hypothesis skipped: the same for every thread
-    int pos[3], rows[3], ones = 0;
-    double R[9], t[3];
-    consensus_draw<3>(seed, best_j, n_us, pos);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) rows[i] = list[pos[i]];
-    pose_three_point(ws, stride, rows, R, t);
-    for (int k = tid; k < n; k += 256) {
-        if (!(flag[k] > 0.0)) continue;
-        const double w1 = sqrt(pose_residual_sq(R, t, ws, stride, k)) <= T ? 1.0 : 0.0;
-        start[k] = w1;
-        ones += w1 > 0.0 ? 1 : 0;
-    }
-    ones = wave_sum(ones);
-    if (lane == 0) cell_ones[wave] = ones;
-    if constexpr (ROBUST) lds_barrier(); else __syncthreads();    // (the plain form's start weights are global memory: full fence)
-    n_start = cell_ones[0] + cell_ones[1] + cell_ones[2] + cell_ones[3];
-    return best_j + 1;
-}
+};
 
 }  // namespace vitvs

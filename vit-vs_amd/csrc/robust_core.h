@@ -1,7 +1,7 @@
 // The robust core of the five Tukey IRLS laws (servo.hip, rig.hip, pose.hip, pose_rig.hip, homography.hip): the
 // median of the residuals by rank counting and the re-weighting step.  The laws keep what differs between them: their residuals,
-// their solves, the barriers around these two steps and where in LDS the cells sit.  At the end: the seeded draw of the two
-// consensus starts (homography.hip, pose_core.h).
+// their solves, the barriers around these two steps and where in LDS the cells sit.  (The consensus start of the pose and the
+// homography law is consensus_core.h's.)
 #pragma once
 #include "common.h"
 
@@ -78,42 +78,6 @@ __device__ __forceinline__ double tukey_reweight(const double* rho, const double
     z = wave_sum(z);
     if ((tid & 63) == 0) zeros[tid >> 6] = z;
     return sigma;
-}
-
-// ---- the draw of the consensus starts (homography.hip: 4 rows; pose_core.h: 3 rows)
-__device__ __forceinline__ unsigned consensus_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// The K (3 or 4) distinct positions of hypothesis j in a list of n_us usable rows, ascending (a row set gives one fit whatever the
-// order it was drawn in): r_c = mix(mix(seed 0x9e3779b9 + j) + c) mod n_us for c = 0 .. 63, repeats rejected; false when 64 draws do
-// not give K.
-template <int K>
-__device__ __forceinline__ bool consensus_draw(unsigned seed, int j, int n_us, int* pos) {
-    static_assert(K == 3 || K == 4, "three- and four-row hypotheses");
-    const unsigned base = consensus_mix(seed * 0x9e3779b9u + (unsigned)j);
-    int p0 = -1, p1 = -1, p2 = -1, p3 = -1, cnt = 0;
-    for (unsigned c = 0; c < 64u && cnt < K; ++c) {
-        const int r = (int)(consensus_mix(base + c) % (unsigned)n_us);
-        if (r == p0 || r == p1 || r == p2 || (K == 4 && r == p3)) continue;
-        if (cnt == 0) p0 = r; else if (cnt == 1) p1 = r; else if (cnt == 2) p2 = r; else p3 = r;
-        ++cnt;
-    }
-    if (cnt < K) return false;
-    int t;
-#define VITVS_CSWAP(a, b) if (b < a) { t = a; a = b; b = t; }
-    if constexpr (K == 4) {
-        VITVS_CSWAP(p0, p1) VITVS_CSWAP(p2, p3) VITVS_CSWAP(p0, p2) VITVS_CSWAP(p1, p3) VITVS_CSWAP(p1, p2)
-        pos[0] = p0; pos[1] = p1; pos[2] = p2; pos[3] = p3;
-    } else {
-        VITVS_CSWAP(p0, p1) VITVS_CSWAP(p1, p2) VITVS_CSWAP(p0, p1)
-        pos[0] = p0; pos[1] = p1; pos[2] = p2;
-    }
-#undef VITVS_CSWAP
-    return true;
 }
 
 }  // namespace vitvs
