@@ -574,11 +574,11 @@ def saliency_inputs(prec, T, P, prescaled):
     return q.view(2 * N, -1).to(DTYPES[prec]).contiguous()
 
 
-def _saliency(qkv, T, P, heads, prescaled, dt):
-    H, N = SALIENCY_H, P + T
-    v = qkv.to(dt).view(2, N, 3, H, 64)
+def _saliency(qkv, T, P, heads, prescaled, dt, H=SALIENCY_H, n_img=2):
+    N = P + T
+    v = qkv.to(dt).view(n_img, N, 3, H, 64)
     maps = []
-    for img in range(2):
+    for img in range(n_img):
         acc = torch.zeros(T, dtype=dt)
         for h in heads:
             s = (v[img, :, 1, h] * v[img, 0, 0, h]).sum(-1)             # q_cls . k over all P + T keys
@@ -589,12 +589,12 @@ def _saliency(qkv, T, P, heads, prescaled, dt):
     return torch.stack(maps)
 
 
-def saliency_ref(qkv, T, P, heads, prescaled):
-    return _saliency(qkv, T, P, heads, prescaled, torch.float64)
+def saliency_ref(qkv, T, P, heads, prescaled, **shape):
+    return _saliency(qkv, T, P, heads, prescaled, torch.float64, **shape)
 
 
-def saliency_f32(qkv, T, P, heads, prescaled):
-    return _saliency(qkv, T, P, heads, prescaled, torch.float32)
+def saliency_f32(qkv, T, P, heads, prescaled, **shape):
+    return _saliency(qkv, T, P, heads, prescaled, torch.float32, **shape)
 
 
 @pytest.mark.parametrize("name,prec", SALIENCY_PRECS)
