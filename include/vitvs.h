@@ -563,6 +563,51 @@ VITVS_API int vitvs_roll_velocity(vitvs_handle* h, const uint8_t* I_cur, const u
                                   int32_t select_mode, const int32_t* selection, const int32_t* n_selected, int32_t num_pairs,
                                   double* v_c, int32_t* status, int32_t* roll_info, double* scores);
 
+/* --- the photometric law: a dense final approach (photometric.hip) -----------------------------
+ * Direct visual servoing on the luminance of every pixel (Collewet & Marchand; ViSP's vpFeatureLuminance), DESIGN.md 5k: the
+ * law to hand over to once a ViT law stands in its dead zone of one patch pitch.  It reads frames, never tokens: no forward, no
+ * weights, no preceding velocity call; it uses workspaces of its own and leaves everything the velocity path, vitvs_last_details,
+ * vitvs_reselect and the other follow-on laws read and write alone.  Its convergence domain is small: outside it the twist is wrong,
+ * not zero.
+ *   I_cur, I_des  uint8 [n_pairs][height][width][3] interleaved RGB, height and width 1 .. 4096
+ *   Z_mm          uint16 [n_pairs][height][width] millimetres, 0 = hole, or NULL.  It is the depth of the image the gradients are
+ *                 taken of: the current depth for interaction 0, the goal depth for 1
+ *   depth_scale   metres: the depth of every pixel when Z_mm is NULL (RGB only); then <= 0 gives VITVS_NO_DEPTH
+ *   K             double [n_pairs][4] fx, fy, cx, cy at height x width
+ *   level         0 .. 3, s = 2^level: Y = 77 R + 150 G + 29 B is summed over s x s blocks (h = height / s, w = width / s rounded
+ *                 down, the tail ignored), I = Ysum / (256 s^2); the pooled image is at least 3 x 3
+ *   interaction   0: gradients of I_cur; 1: of I_des
+ * Per pooled pixel (r, c) inside the one-pixel border whose depth block holds a non-zero sample (Z = their mean / 1000), with
+ * gx = (G(r, c+1) - G(r, c-1)) / 2, gy likewise, fx' = fx / s, cx' = (cx + 0.5) / s - 0.5, x = (c - cx') / fx', a = gx fx' (y, b
+ * likewise): L = [a/Z, b/Z, -(x a + y b)/Z, -(x y a + (1 + y^2) b), (1 + x^2) a + x y b, x b - y a], e = I_cur - I_des, and
+ * v_p = -lambda (H + mu diag(H))^-1 g of H = sum L^T L, g = sum L^T e (mu = 0: Gauss-Newton), by LDL^T.
+ *   v_p        double [n_pairs][6];  p_status int32 [n_pairs]: VITVS_OK; VITVS_TOO_FEW (v_p = 0) with fewer than 6 rows or a failed
+ *              pivot (a textureless frame, every depth a hole); VITVS_NO_DEPTH (v_p = 0).  Identical frames: VITVS_OK, v_p = 0
+ *   normal     double [n_pairs][28] or NULL: H (upper triangle, row-major, 21), g (6), sum e^2
+ *   p_info     int32 [n_pairs][8] or NULL: rows, pooled h, pooled w, bands of the launch, holes left out, a pivot failed, 0, 0
+ * The sums are the same bits from call to call, and for a pair alone or at any place of a batch.  Two launches on `stream`; the
+ * handle's first call allocates the law's blocks (1 MiB of band partials per pair of max_pairs, and the host form's staging) and
+ * synchronises the device: make it outside any stream capture.  Calls on different streams of one handle share the partials: one
+ * call in flight per handle, as for the other laws.  Returns 0, -1 (null), -2 (n_pairs outside 1 .. max_pairs, level, interaction, mu < 0, a scalar that
+ * is not finite, height or width outside 1 .. 4096, a pooled side < 3; the host-pointer form: height x width > v_max x u_max).  No
+ * counterpart in the reference. */
+VITVS_API int vitvs_photometric_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                             int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K,
+                                             int32_t level, int32_t interaction, double mu, double lambda, double* v_p,
+                                             int32_t* p_status, double* normal, int32_t* p_info, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_photometric_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                         int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                         int32_t interaction, double mu, double lambda, double* v_p, int32_t* p_status,
+                                         double* normal, int32_t* p_info);
+/* The launch plan of the photometric law as host arithmetic, for one pair (no handle, no device).  It is declared here, beside the
+ * calls it plans, and not among the operator hooks of include/vitvs_ops.h: out int32 [8] = the
+ * pooled h = height >> level and w = width >> level, the pooled rows per band max(1, min((2048 >> level) / w, h / 256)), the bands
+ * ceil(h / rows) (the grid is bands x n_pairs workgroups of 256 threads), the dynamic LDS bytes 1024 + 4 ((rows + 2) 2 w + rows w),
+ * the workspace bytes per pair 256 bands, 1 when the LDS needs the opt-in past 64 KiB, 0.  Returns 0, -1 (out NULL), -2 (height
+ * or width outside 1 .. 4096, level outside 0 .. 3, a pooled side < 3; out is zeros). */
+VITVS_API int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t level, int32_t* out);
+
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own
  * ramp, so the chain leaves most of the chip idle most of the time.  Updates that do not depend on each other (several

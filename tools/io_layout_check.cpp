@@ -99,6 +99,21 @@ int main() {
             EXPECT(roll.Z.count == depth && roll.I_cur.count == frame && roll.selection.count == n_sel, "roll: counts");
         }
     }
+    // the photometric law: P pairs at v_max x u_max, a call of n pairs at height x width
+    const size_t photos[][6] = {{1, 640, 480, 1, 640, 480}, {1, 640, 480, 1, 37, 29}, {3, 641, 479, 2, 96, 88}, {8, 640, 480, 8, 224, 224},
+                                {8, 1280, 720, 5, 1, 1}, {2, 3, 3, 2, 3, 3}};
+    for (const auto& q : photos) {
+        const size_t P = q[0], px_max = q[1] * q[2], n = q[3], px = q[4] * q[5];
+        PhotometricIo ph = photometric_io(P, px_max * 3, px_max, n, px * 3, px, &d, &b16, &b8, &b8, &d, &i, &d, &i);
+        check("photometric", io_list(ph), P, px_max, n);
+        PhotometricIo ph0 = photometric_io(P, px_max * 3, px_max);
+        EXPECT(io_place(io_list(ph0), nullptr) == io_place(io_list(ph), nullptr), "photometric: allocation and call disagree");
+        EXPECT(ph.Z.count == n * px && ph.I_cur.count == n * px * 3 && ph.I_des.count == n * px * 3 && ph.normal.count == n * 28,
+               "photometric: counts");
+        EXPECT(io_place(io_list(ph0), nullptr) == P * (4 + 6 + 28) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
+                                                      ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
+               "photometric: %zu %zu", P, px_max);
+    }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");
     return failures ? 1 : 0;

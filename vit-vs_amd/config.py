@@ -10,6 +10,7 @@ from __future__ import annotations
 import dataclasses
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -157,6 +158,7 @@ def baseline_config(key: str) -> ViTConfig:
 
 LAWS = ("ibvs", "pose", "homography")            # ServoParams.law: the image-based law of the reference, the pose law,
                                                  # or the homography law of a planar target, which needs no depth
+PHOTOMETRIC_INTERACTIONS = ("current", "desired")  # ServoParams.photometric_interaction: the photometric law has no mean form
 INTERACTIONS = ("current", "desired", "mean")    # values 0 / 1 / 2 of option "interaction" (include/vitvs.h)
 
 
@@ -212,7 +214,30 @@ class ServoParams:
                                    # matches, so the servo starts from any in-plane rotation.  Four or five forwards per update
                                    # instead of two; needs an engine with max_pairs >= 4; not with subpatch or selection "reference"
 
+    photometric_handover: float = 0.0  # > 0: a servo.Controller hands the robot to the photometric law (Engine.photometric_velocity,
+                                       # DESIGN.md 5k) once an update's raw twist says less than this is left, max |v_c| / lambda_ in
+                                       # metres / radians; from then on no forward runs.  0 = off, nothing changes.  The photometric
+                                       # law's domain is small: hand over inside the ViT law's dead zone, not before
+    photometric_level: int = 2         # its pyramid level, 0 .. 3: luminance pooled over 2^level x 2^level pixels
+    photometric_mu: float = 0.01       # its Levenberg-Marquardt damping (>= 0; 0 = Gauss-Newton)
+    photometric_lambda: Optional[float] = None  # its gain; None: lambda_
+    photometric_interaction: str = "desired"    # "desired": gradients of the goal image, depth = the goal depth; "current": of the
+                                                # current frame, depth = the latest depth image
+
     def __post_init__(self):
+        if not (math.isfinite(float(self.photometric_handover)) and float(self.photometric_handover) >= 0.0):
+            raise ValueError(f"photometric_handover is a finite threshold >= 0 (0 = off), got {self.photometric_handover!r}")
+        if isinstance(self.photometric_level, bool) or int(self.photometric_level) != self.photometric_level \
+                or not 0 <= int(self.photometric_level) <= 3:
+            raise ValueError(f"photometric_level is 0 .. 3, got {self.photometric_level!r}")
+        if not (math.isfinite(float(self.photometric_mu)) and float(self.photometric_mu) >= 0.0):
+            raise ValueError(f"photometric_mu is finite and >= 0, got {self.photometric_mu!r}")
+        if self.photometric_lambda is not None and not math.isfinite(float(self.photometric_lambda)):
+            raise ValueError(f"photometric_lambda is a finite gain or None, got {self.photometric_lambda!r}")
+        if self.photometric_interaction not in PHOTOMETRIC_INTERACTIONS:
+            raise ValueError(f"photometric_interaction is one of {PHOTOMETRIC_INTERACTIONS}, got {self.photometric_interaction!r}")
+        if self.photometric_handover > 0 and self.roll_search:
+            raise ValueError("photometric_handover does not combine with roll_search: the hand-over watches the plain update's twist")
         if self.roll_search and self.subpatch:
             raise ValueError("roll_search does not combine with subpatch: the sub-patch offsets of a turned copy would have to be "
                              "turned too")
@@ -302,7 +327,9 @@ def load_reference_config(source) -> ReferenceConfig:
     else "ibvs", 0 and 0; ``homography_robust_iterations`` and ``homography_depth`` likewise, else 0 and 1.0; ``homography_consensus`` and
     ``homography_consensus_seed`` likewise, else 0 and 0; ``pose_consensus`` and ``pose_consensus_seed`` likewise, else 0 and 0;
     ``select_cells`` (the cell grid of selection "best") likewise, else 4;
-    ``roll_search`` (the roll search in front of every update) likewise, else False."""
+    ``roll_search`` (the roll search in front of every update) likewise, else False; ``photometric_handover``, ``photometric_level``,
+    ``photometric_mu``, ``photometric_lambda`` and ``photometric_interaction`` (the hand-over to the photometric law) likewise, else
+    0.0 (off), 2, 0.01, None and "desired"."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -329,12 +356,18 @@ def load_reference_config(source) -> ReferenceConfig:
                         homography_depth=float(cfg.get("homography_depth", 1.0)),
                         homography_consensus=int(cfg.get("homography_consensus", 0)),
                         homography_consensus_seed=int(cfg.get("homography_consensus_seed", 0)),
-                        select_cells=int(cfg.get("select_cells", 4)), roll_search=bool(cfg.get("roll_search", False)))
+                        select_cells=int(cfg.get("select_cells", 4)), roll_search=bool(cfg.get("roll_search", False)),
+                        photometric_handover=float(cfg.get("photometric_handover", 0.0)),
+                        photometric_level=cfg.get("photometric_level", 2),
+                        photometric_mu=float(cfg.get("photometric_mu", 0.01)),
+                        photometric_lambda=(None if cfg.get("photometric_lambda") is None else float(cfg["photometric_lambda"])),
+                        photometric_interaction=str(cfg.get("photometric_interaction", "desired")))
     used = {"roll_search","u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
-            "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed"}
+            "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed",
+            "photometric_handover", "photometric_level", "photometric_mu", "photometric_lambda", "photometric_interaction"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -138,6 +138,10 @@ struct vitvs_handle {
     // The roll search (vitvs_roll_velocity[_dev], roll.hip), the same arrangement: roll_ws = the flag `rolled` the pick leaves for
     // the law (one int32 on a 256-byte line of its own), then the current frame's four quarter-turned copies [4][S][S][3]
     unsigned char *roll_ws = nullptr, *roll_io = nullptr;           // RollIo
+    // The photometric law (vitvs_photometric_velocity[_dev], photometric.hip) reads frames, not what a velocity call left: photo_ws =
+    // its band partials at max_pairs pairs of the most bands a frame can have, photo_io = PhotometricIo at max_pairs frames of
+    // v_max x u_max
+    unsigned char *photo_ws = nullptr, *photo_io = nullptr;
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -2064,6 +2068,69 @@ int vitvs_roll_velocity(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_
     });
 }
 
+// --- the photometric law -------------------------------------------------------------------------
+// What a photometric call asks of its arguments, before anything is staged or enqueued; the first call allocates the law's two
+// blocks: the band partials at max_pairs pairs of the most bands a frame can have (4096 rows in bands of one: 1 MiB per pair), so
+// no later call allocates, and PhotometricIo at max_pairs frames of v_max x u_max.  As with the other laws, calls on different
+// streams of one handle share the partials: one call in flight per handle.
+constexpr size_t kPhotoWsPerPair = (size_t)4096 * 32 * sizeof(double);
+static int photometric_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction, double depth_scale,
+                               double mu, double lambda, bool host_form) {
+    const vitvs_config& c = h->cfg;
+    if (n_pairs < 1 || n_pairs > c.max_pairs) return set_err(h, -2, "n_pairs is 1 .. max_pairs");
+    if (level < 0 || level > 3) return set_err(h, -2, "level is 0 .. 3");
+    if (interaction != IL_CURRENT && interaction != IL_DESIRED) return set_err(h, -2, "interaction is 0 (current) or 1 (desired)");
+    if (!std::isfinite(mu) || !std::isfinite(lambda) || !std::isfinite(depth_scale))
+        return set_err(h, -2, "mu, lambda and depth_scale are finite");
+    if (mu < 0.0) return set_err(h, -2, "mu is not negative");
+    if (height < 1 || width < 1 || height > 4096 || width > 4096) return set_err(h, -2, "height and width are 1 .. 4096");
+    if ((height >> level) < 3 || (width >> level) < 3) return set_err(h, -2, "the pooled image is at least 3 x 3 pixels");
+    const size_t px_max = (size_t)c.u_max * c.v_max;
+    if (host_form && (size_t)height * width > px_max)
+        return set_err(h, -2, "the host-pointer form stages frames of at most v_max x u_max pixels");
+    PhotometricPlan pl;
+    if (int rc = plan_photometric(height, width, level, c.max_pairs, &pl)) return set_err(h, rc, "no photometric plan");
+    if (pl.ws_bytes > (size_t)c.max_pairs * kPhotoWsPerPair) return set_err(h, -3, "the photometric plan has more bands than the workspace");
+    PhotometricIo io = photometric_io(c.max_pairs, px_max * 3, px_max);
+    return law_blocks(h, "photometric", &h->photo_ws, (size_t)c.max_pairs * kPhotoWsPerPair, &h->photo_io, io_place(io_list(io), nullptr));
+}
+
+int vitvs_photometric_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                   int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                   int32_t interaction, double mu, double lambda, double* v_p, int32_t* p_status, double* normal,
+                                   int32_t* p_info, void* stream) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, false)) return rc;
+    PhotometricArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_pairs = n_pairs; a.height = height; a.width = width; a.level = level; a.interaction = interaction;
+    a.I_cur = I_cur; a.I_des = I_des; a.Z_mm = Z_mm; a.depth_scale = depth_scale; a.K = K; a.mu = mu; a.lambda = lambda;
+    a.ws = reinterpret_cast<double*>(h->photo_ws);
+    a.v_p = v_p; a.p_status = p_status; a.normal = normal; a.p_info = p_info;
+    const int rc = launch_photometric(a, dev_stream(h, stream));
+    return rc ? set_err(h, rc, "photometric law launch failed") : 0;
+}
+
+int vitvs_photometric_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                               int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                               int32_t interaction, double mu, double lambda, double* v_p, int32_t* p_status, double* normal,
+                               int32_t* p_info) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, true)) return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max, px = (size_t)height * width;
+    PhotometricIo io = photometric_io(c.max_pairs, px_max * 3, px_max, n_pairs, px * 3, px, K, Z_mm, I_cur, I_des, v_p, p_status, normal,
+                                      p_info);
+    return host_call(h, io_list(io), h->photo_io, [&](hipStream_t st) {
+        return vitvs_photometric_velocity_dev(h, n_pairs, io.I_cur.dev, io.I_des.dev, height, width,
+                                              Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale, io.K.f64(), level,
+                                              interaction, mu, lambda, io.v_p.f64(), io.p_status.i32(), normal ? io.normal.f64() : nullptr,
+                                              p_info ? io.p_info.i32() : nullptr, st);
+    });
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -2367,6 +2434,16 @@ int vitvs_op_homography_consensus_plan(int32_t max_rows, int32_t n_iter, int32_t
     memset(&pl, 0, sizeof(pl));
     const int rc = plan_out(plan_homography(max_rows, n_iter, n_hyp, &pl), pl, out);
     out[3] = pl.consensus;
+    return rc;
+}
+
+int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t level, int32_t* out) {
+    if (!out) return -1;
+    PhotometricPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_photometric(height, width, level, 1, &pl);
+    out[0] = pl.h; out[1] = pl.w; out[2] = pl.rows; out[3] = pl.bands; out[4] = (int32_t)pl.lds; out[5] = (int32_t)pl.ws_bytes;
+    out[6] = pl.lds_opt_in; out[7] = 0;
     return rc;
 }
 

@@ -9,7 +9,7 @@
 namespace vitvs {
 
 struct IoField {
-    size_t elem;                  // bytes per element: 8 (f64) or 4 (i32) (the roll search's list: also 2 (u16) and 1 (u8)); a list
+    size_t elem;                  // bytes per element: 8 (f64) or 4 (i32) (the roll search's and the photometric law's lists: also 2 (u16) and 1 (u8)); a list
                                   // holds its widest fields first, so nothing is padded
     size_t cap;                   // elements the block reserves: the field at max_pairs / max_rows
     size_t count;                 // elements of the call at hand: what is copied
@@ -114,6 +114,23 @@ inline RollIo roll_io(size_t T, size_t R, size_t frame, size_t depth, size_t n_s
                   io_out(4, 4, 1, status),         io_out(4, 8, 8, roll_info),        io_in(4, 4, 1, n_selected),
                   io_in(4, sel_cap, n_sel, selection), io_in(2, z_cap, depth, Z),     io_in(1, f_cap, frame, I_cur),
                   io_in(1, f_cap, frame, I_des)};
+}
+
+// the photometric law (vitvs_photometric_velocity): n pairs of frames of `frame` = height * width * 3 bytes and depth images of
+// `depth` = height * width pixels each, one pair behind the other; the block holds P pairs at the handle's v_max x u_max (`frame_max`,
+// `depth_max`).  Behind the 8- and 4-byte fields (the statuses' capacity rounded to four entries) come the depth images and the
+// frames, each on a 16-byte boundary of the block as in RollIo.  Z is an optional INPUT.
+struct PhotometricIo {
+    IoField K, v_p, normal, p_status, p_info, Z, I_cur, I_des;
+};
+inline PhotometricIo photometric_io(size_t P, size_t frame_max, size_t depth_max, size_t n = 0, size_t frame = 0, size_t depth = 0,
+                                    const double* K = nullptr, const uint16_t* Z = nullptr, const uint8_t* I_cur = nullptr,
+                                    const uint8_t* I_des = nullptr, double* v_p = nullptr, int32_t* p_status = nullptr,
+                                    double* normal = nullptr, int32_t* p_info = nullptr) {
+    const size_t st_cap = (P + 3) & ~(size_t)3, z_cap = (P * depth_max + 7) & ~(size_t)7, f_cap = (P * frame_max + 15) & ~(size_t)15;
+    return PhotometricIo{io_in(8, P * 4, n * 4, K),          io_out(8, P * 6, n * 6, v_p),       io_out(8, P * 28, n * 28, normal),
+                         io_out(4, st_cap, n, p_status),     io_out(4, P * 8, n * 8, p_info),    io_in(2, z_cap, n * depth, Z),
+                         io_in(1, f_cap, n * frame, I_cur),  io_in(1, f_cap, n * frame, I_des)};
 }
 
 }  // namespace vitvs

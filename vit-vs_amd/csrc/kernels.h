@@ -629,6 +629,40 @@ int plan_homography(int max_rows, int n_iter, int n_hyp, HomographyPlan* plan);
 size_t homography_scratch_bytes(int n_pairs, int ld);
 int launch_homography(const HomographyArgs& a, hipStream_t stream);
 
+// ---- photometric.hip -----------------------------------------------------------------------
+// The photometric law: per pair one interaction row per pixel of the pooled luminance image (2^level x 2^level
+// blocks), v_p = -lambda (H + mu diag(H))^-1 g of H = sum L^T L, g = sum L^T (I_cur - I_des).  Reads frames, never tokens.  Two
+// launches: the 28 sums per (pair, band of pooled rows), then one workgroup per pair, one wave of which adds the bands in order and solves.
+struct PhotometricArgs {
+    int n_pairs;
+    int height, width;        // of every frame and depth image
+    int level;                // 0 .. 3
+    int interaction;          // IL_CURRENT or IL_DESIRED: the image the gradients are taken of, and whose depth Z_mm is
+    const uint8_t* I_cur;     // [n_pairs][height][width][3]
+    const uint8_t* I_des;     // [n_pairs][height][width][3]
+    const uint16_t* Z_mm;     // [n_pairs][height][width] mm, 0 = hole; null: depth_scale everywhere
+    double depth_scale;       // metres; Z_mm null and depth_scale <= 0: ST_NO_DEPTH
+    const double* K;          // [n_pairs][4] fx, fy, cx, cy at height x width
+    double mu, lambda;
+    double* ws;               // [n_pairs][bands][32] the band partials (PhotometricPlan::ws_bytes)
+    // outputs
+    double* v_p;              // [n_pairs][6]
+    int32_t* p_status;        // [n_pairs] ST_OK; ST_TOO_FEW (v = 0): fewer than 6 rows or a failed pivot; ST_NO_DEPTH (v = 0)
+    double* normal;           // [n_pairs][28] or null: H upper triangle row-major (21), g (6), sum e^2
+    int32_t* p_info;          // [n_pairs][8] or null: rows, pooled h, pooled w, bands, holes left out, a pivot failed, 0, 0
+};
+struct PhotometricPlan {
+    int h, w;                 // the pooled image: height >> level, width >> level
+    int rows;                 // pooled rows per band: max(1, min((2048 >> level) / w, h / 256))
+    int bands;                // ceil(h / rows): the grid is bands x n_pairs
+    size_t lds;               // dynamic LDS of the rows launch: 4 x 32 doubles, then ((rows + 2) 2 w + rows w) int32
+    bool lds_opt_in;          // > 64 KiB (rows wider than 2048 pooled pixels)
+    size_t ws_bytes;          // max_pairs x bands x 256
+};
+// -2: height or width outside 1 .. 4096, level outside 0 .. 3, a pooled side < 3, max_pairs < 1
+int plan_photometric(int height, int width, int level, int max_pairs, PhotometricPlan* plan);
+int launch_photometric(const PhotometricArgs& a, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

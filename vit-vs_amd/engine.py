@@ -542,6 +542,96 @@ class Engine:
         self._last_tokens = self.tokens
         return v, int(st[0]), self._roll_info(rinfo, scores)
 
+    # ------------------------------------------------------------------ the photometric law
+    _PHOTOMETRIC_INTERACTIONS = {"current": 0, "desired": 1, 0: 0, 1: 1}
+
+    def _photometric_scalars(self, level, interaction, mu, lambda_, depth_scale):
+        if interaction not in self._PHOTOMETRIC_INTERACTIONS:
+            raise VitvsError(f'the photometric law inverts the "current" or the "desired" interaction matrix, got {interaction!r}')
+        lam = self.params.lambda_ if lambda_ is None else float(lambda_)
+        return int(level), self._PHOTOMETRIC_INTERACTIONS[interaction], float(mu), lam, float(depth_scale)
+
+    @staticmethod
+    def _photometric_info(status, normal, pinfo) -> dict:
+        n = pinfo[:, 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cost = np.where(n > 0, normal[:, 27] / np.maximum(n, 1), 0.0)
+        return dict(status=status, normal=normal, n=n.copy(), cost=cost, pooled=pinfo[:, 1:3].copy(), bands=pinfo[:, 3].copy(),
+                    holes=pinfo[:, 4].copy(), pivot_failed=pinfo[:, 5].astype(bool))
+
+    def photometric_velocity(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                             lambda_: Optional[float] = None, depth_scale: float = 0.0):
+        """``vitvs_photometric_velocity_dev``: the photometric law of ``n`` frame pairs, uint8 ``[n, H, W, 3]`` (or
+        ``[H, W, 3]``) at any one geometry up to 4096 x 4096 — camera resolution, not the extractor's input.  ``Z``: uint16
+        millimetres ``[n, H, W]`` — the depth of the image the gradients are taken of, the goal's for ``interaction`` "desired", the
+        current one for "current" — or None: ``depth_scale`` metres everywhere (RGB only).  ``K``: (fx, fy, cx, cy) at that geometry,
+        one for all or ``[n, 4]``.  ``lambda_`` None: the engine's ``params.lambda_``.  No forward runs and no velocity call is needed
+        or disturbed.  Two launches on the current stream.  Returns ``(v float64 [n, 6] device tensor, info)``, ``info`` =
+        dict(``status`` int32 [n], ``normal`` float64 [n, 28], ``n`` rows, ``cost`` = sum e^2 / n, ``pooled`` [n, 2], ``bands``,
+        ``holes``, ``pivot_failed``) as numpy arrays.  Reading ``info`` synchronises; the engine's first call allocates: make it
+        outside a stream capture."""
+        cur = torch.as_tensor(I_cur)
+        des = torch.as_tensor(I_des)
+        if cur.dim() == 3:
+            cur, des = cur[None], des[None]
+        if cur.dtype != torch.uint8 or des.dtype != torch.uint8 or cur.dim() != 4 or cur.shape[-1] != 3 or cur.shape != des.shape:
+            raise VitvsError("frames must be uint8 [n, H, W, 3], both of one shape")
+        n, hh, ww = int(cur.shape[0]), int(cur.shape[1]), int(cur.shape[2])
+        cur, des = cur.to(self.device).contiguous(), des.to(self.device).contiguous()
+        z = None
+        if Z is not None:
+            z = torch.as_tensor(Z)
+            if z.dtype != torch.uint16 or z.numel() != n * hh * ww or tuple(z.shape[-2:]) != (hh, ww):
+                raise VitvsError("Z must be uint16 millimetres [n, H, W] at the frames' geometry")
+            z = z.to(self.device).contiguous()
+        kk = torch.as_tensor(K, dtype=torch.float64).reshape(-1, 4)
+        if kk.shape[0] == 1 and n > 1:
+            kk = kk.repeat(n, 1)
+        if kk.shape[0] != n:
+            raise VitvsError("K is one (fx, fy, cx, cy) for all pairs or one per pair")
+        kk = kk.contiguous().to(self.device)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        v = torch.empty((n, 6), dtype=torch.float64, device=self.device)
+        st = torch.empty(n, dtype=torch.int32, device=self.device)
+        normal = torch.empty((n, 28), dtype=torch.float64, device=self.device)
+        pinfo = torch.empty((n, 8), dtype=torch.int32, device=self.device)
+        rc = self.lib.vitvs_photometric_velocity_dev(self.handle, n, _ptr(cur), _ptr(des), hh, ww, _ptr(z), ds, _ptr(kk), level, inter,
+                                                     mu, lam, _ptr(v), _ptr(st), _ptr(normal), _ptr(pinfo), _stream_ptr(self.device))
+        self._check(rc, "vitvs_photometric_velocity_dev")
+        return v, self._photometric_info(st.cpu().numpy(), normal.cpu().numpy(), pinfo.cpu().numpy())
+
+    def photometric_velocity_host(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                  lambda_: Optional[float] = None, depth_scale: float = 0.0):
+        """``vitvs_photometric_velocity``, the host-pointer form of ``photometric_velocity``: numpy arrays in, ``(v float64 [n, 6],
+        info)`` out, one synchronous C call, ordered behind whatever ``_dev`` work the engine still has pending.  Frames of at most
+        ``params.v_max`` x ``params.u_max`` pixels."""
+        cur = np.ascontiguousarray(I_cur)
+        des = np.ascontiguousarray(I_des)
+        if cur.ndim == 3:
+            cur, des = cur[None], des[None]
+        if cur.dtype != np.uint8 or des.dtype != np.uint8 or cur.ndim != 4 or cur.shape[-1] != 3 or cur.shape != des.shape:
+            raise VitvsError("frames must be uint8 [n, H, W, 3], both of one shape")
+        n, hh, ww = (int(x) for x in cur.shape[:3])
+        z = None
+        if Z is not None:
+            z = np.ascontiguousarray(Z)
+            if z.dtype != np.uint16 or z.size != n * hh * ww or tuple(z.shape[-2:]) != (hh, ww):
+                raise VitvsError("Z must be uint16 millimetres [n, H, W] at the frames' geometry")
+        kk = np.asarray(K, np.float64).reshape(-1, 4)
+        if kk.shape[0] == 1 and n > 1:
+            kk = np.repeat(kk, n, axis=0)
+        if kk.shape[0] != n:
+            raise VitvsError("K is one (fx, fy, cx, cy) for all pairs or one per pair")
+        kk = np.ascontiguousarray(kk)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        v, st = np.zeros((n, 6)), np.zeros(n, np.int32)
+        normal, pinfo = np.zeros((n, 28)), np.zeros((n, 8), np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.vitvs_photometric_velocity(self.handle, n, p(cur), p(des), hh, ww, p(z), ds, p(kk), level, inter, mu, lam, p(v),
+                                                 p(st), p(normal), p(pinfo))
+        self._check(rc, "vitvs_photometric_velocity")
+        return v, self._photometric_info(st, normal, pinfo)
+
     def last_tables(self, n_pairs: int = 1) -> dict:
         """``nn_1``, ``nn_2`` (int32) and ``sim_1`` (float32) [n, T] of the last servo call; after ``compute_velocity_host`` they
         come from host memory (the handle's pinned block), no device call."""

@@ -51,6 +51,9 @@ class UpdatePipeline:
         if getattr(params, "roll_search", False):
             raise ValueError("UpdatePipeline slots run plain one-pair updates: roll_search is servo.Controller's (one handle with "
                              "max_pairs >= 4 matches the four turned copies in one batch)")
+        if getattr(params, "photometric_handover", 0.0) > 0:
+            raise ValueError("UpdatePipeline slots run ViT updates: photometric_handover is servo.Controller's (the hand-over is one "
+                             "camera's state, and the photometric law runs no forward to pipeline)")
         if getattr(params, "law", "ibvs") != "ibvs":
             raise ValueError('UpdatePipeline slots run the image-based law: law="pose" is servo.Controller\'s (one handle, one camera)')
         self.depth = int(depth)

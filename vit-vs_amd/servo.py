@@ -259,6 +259,21 @@ class Controller:
                                  'correspondence and the law, the roll search picks and carries back on the device in between')
             if engine.max_pairs < 4:
                 raise ValueError(f"roll_search matches four turned copies in one batch: engine.max_pairs is {engine.max_pairs}, needs >= 4")
+        if self.params.photometric_handover > 0 and self.params.roll_search:
+            raise ValueError("photometric_handover does not combine with roll_search: the hand-over watches the plain update's twist")
+        if self.params.photometric_handover > 0 and goal_image is not None:
+            # the photometric law runs on the camera-resolution frames with the camera's intrinsics: a goal of another size could
+            # never be handed over to
+            size = (goal_image.size[1], goal_image.size[0]) if hasattr(goal_image, "convert") and not isinstance(goal_image, np.ndarray) \
+                else tuple(np.asarray(goal_image).shape[:2])
+            if size != (self.params.v_max, self.params.u_max):
+                raise ValueError(f"photometric_handover needs the goal image at the camera's v_max x u_max "
+                                 f"({self.params.v_max} x {self.params.u_max}), got {size[0]} x {size[1]}")
+        self.photometric_active = False                   # photometric_handover: the photometric law has the robot
+        self.last_photometric = None                      # dict(status, cost = sum e^2 / n, n) of its last call
+        self._photo_goal_src = None                       # the PIL goal image _photo_goal was converted from
+        self._photo_goal = None                           # (host copy, device tensor) of the goal frame at camera resolution, and
+        self._photo_goal_depth = None                     # of the goal depth: uploaded once, compared by content like _goal_np
         self.last_roll = None                             # roll_search: the winner k of the last update (-1: no valid candidate), and
         self.last_roll_info = None                        # Engine.roll_velocity's info dict of it
         if goal_depth is not None:
@@ -478,25 +493,101 @@ class Controller:
         return (s_uv_star, s_uv), sim
 
     def ibvs(self):
-        """One control-law step: updates ``self.v_c`` (EMA-smoothed) or leaves it untouched on failure."""
+        """One control-law step: updates ``self.v_c`` (EMA-smoothed) or leaves it untouched on failure.  With
+        ``params.photometric_handover`` > 0 and the hand-over made (``photometric_active``), the step is the photometric law's alone:
+        no forward runs."""
         if self.latest_image is None:
             return
-        result = self.detect_features()
-        self._law_step(result is not None and result[0] is not None)
-
-    def _law_step(self, have_features: bool):
-        if not have_features:
+        if self.photometric_active and self._photometric_step():
             return
+        result = self.detect_features()
+        if self._law_step(result is not None and result[0] is not None):
+            self._watch_handover()
+
+    def _law_step(self, have_features: bool) -> bool:
+        if not have_features:
+            return False
         if self.latest_image_depth is None and self.params.interaction != "desired" and self.params.law != "homography":
-            return                                        # reference: "Failed to get depth - skipping"; L(s*, Z*) reads none, and
+            return False                                  # reference: "Failed to get depth - skipping"; L(s*, Z*) reads none, and
                                                           # neither does the homography law
         # fewer than 4 matches: the reference's calculate_uv hands back all-zero feature arrays of num_pairs rows
         # (vitvs_v2.py:539-541), len() >= 4 passes the check at :604, e = 0 and the raw twist is exactly 0 — which is
         # what the kernel reports with status TOO_FEW; the EMA is updated with it, as in the reference
+        self._smooth()
+        return True
+
+    def _smooth(self):
+        """The raw twist through the EMA into ``v_c`` and the history."""
         self.v_c = ema_update(self.ema_velocities, self._raw_v, self.params.ema_alpha)
         self.velocity_vector_history.append(self.v_c)
         if len(self.velocity_vector_history) > self.max_velocity_vector_history:
             self.velocity_vector_history.pop(0)
+
+    # -- the hand-over to the photometric law (params.photometric_handover > 0, DESIGN.md 5k)
+    def _watch_handover(self):
+        """Behind a ViT update that reached the EMA: with status OK and max |raw v_c| / lambda_ — the law's own estimate of what is
+        left, in metres / radians; exactly 0 under the same-image shortcut — below the threshold, the next ``ibvs()`` is the
+        photometric law's."""
+        p = self.params
+        if not p.photometric_handover > 0 or self.last_status != _lib.STATUS_OK or p.lambda_ == 0:
+            return
+        left = float(np.max(np.abs(np.asarray(self._raw_v, np.float64)))) / abs(p.lambda_)
+        if left < p.photometric_handover and self._photometric_inputs() is not None:
+            self.photometric_active = True
+
+    def _device_copy(self, cached, arr):
+        """(host copy, device tensor) of ``arr``, uploaded again only when its content changed."""
+        if cached is None or cached[0].shape != arr.shape or not np.array_equal(cached[0], arr):
+            host = np.array(arr, copy=True, order="C")
+            cached = (host, torch.from_numpy(host).to(self.engine.device))
+        return cached
+
+    def _photometric_inputs(self):
+        """(current frame, goal frame on the device, depth image or None, scalar depth) at camera resolution, or None when the goal
+        image is not at the camera's v_max x u_max (the intrinsics are that geometry's)."""
+        p = self.params
+        goal = self.goal_image
+        cur = np.asarray(self.latest_image, dtype=np.uint8)
+        if hasattr(goal, "convert") and not isinstance(goal, np.ndarray):     # a PIL image: converted and uploaded once per object
+            if self._photo_goal is None or self._photo_goal_src is not goal:
+                self._photo_goal = self._device_copy(None, np.asarray(goal.convert("RGB"), dtype=np.uint8))
+                self._photo_goal_src = goal
+        else:                                                                 # an array may be rewritten in place: compared by content
+            self._photo_goal = self._device_copy(self._photo_goal, np.asarray(goal, dtype=np.uint8))
+        if cur.shape != (p.v_max, p.u_max, 3) or self._photo_goal[0].shape != cur.shape:
+            return None
+        depth = self.goal_depth if p.photometric_interaction == "desired" else self.latest_image_depth
+        z = None
+        if depth is not None and np.asarray(depth).dtype == np.uint16 and np.asarray(depth).shape[-2:] == (p.v_max, p.u_max) \
+                and np.asarray(depth).size == p.v_max * p.u_max:
+            if p.photometric_interaction == "desired":
+                self._photo_goal_depth = self._device_copy(self._photo_goal_depth, np.asarray(depth).reshape(p.v_max, p.u_max))
+                z = self._photo_goal_depth[1]
+            else:
+                z = np.asarray(depth).reshape(p.v_max, p.u_max)
+        return cur, self._photo_goal[1], z, (0.0 if z is not None else p.homography_depth)
+
+    def _photometric_step(self) -> bool:
+        """One update by the photometric law alone.  False, with the hand-over cleared, when its status is not OK: the caller runs
+        the ViT update for this call."""
+        p = self.params
+        inputs = self._photometric_inputs()
+        if inputs is None:
+            self.photometric_active = False
+            return False
+        cur, goal, z, scalar = inputs
+        lam = p.lambda_ if p.photometric_lambda is None else p.photometric_lambda
+        v, info = self.engine.photometric_velocity(cur, goal, None if z is None else z[None], p.intrinsics(), p.photometric_level,
+                                                   p.photometric_interaction, p.photometric_mu, lam, scalar)
+        st = int(info["status"][0])
+        self.last_photometric = dict(status=st, cost=float(info["cost"][0]), n=int(info["n"][0]))
+        if st != _lib.STATUS_OK:
+            self.photometric_active = False
+            return False
+        self._raw_v, self.last_status = v[0].cpu().numpy(), st
+        self.feature_failure_count = 0
+        self._smooth()
+        return True
 
     def publish_twist(self, v_c=None):
         return twist_from_velocity(self.v_c if v_c is None else v_c, self.params.max_velocity)
@@ -594,6 +685,9 @@ class MultiController:
         if (params or self.engine.params).roll_search:
             raise ValueError("roll_search is servo.Controller's: a MultiController round is one batched call over the cameras, the roll "
                              "search one call of four turned copies per camera")
+        if (params or self.engine.params).photometric_handover > 0:
+            raise ValueError("photometric_handover is servo.Controller's: a MultiController round is one batched ViT call over the "
+                             "cameras, the hand-over one camera's own state")
         if self.law == "homography":
             raise ValueError('law="homography" is servo.Controller\'s: the homography law has no rig form (one camera, one plane)')
         if self.law == "pose":
