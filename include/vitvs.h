@@ -615,7 +615,8 @@ VITVS_API int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t l
  * DIFFERENT handles on DIFFERENT streams: one call in flight per handle, any number of handles (vit-vs_amd/pipeline.py is
  * that arrangement; measured: profiles/r03_notes.md section 5).  Per-handle options for it:
  *   "graph_replay" 0 / 1   velocity calls replay a hipGraph captured per argument tuple — up to 32 tuples per handle, least
- *                          recently used evicted — (host cost ~50 us per update
+ *                          recently used evicted; evicting a tuple drains the device, like every other event that drops a
+ *                          capture — (host cost ~50 us per update
  *                          instead of ~370 us of launch calls, so ONE host thread keeps several streams busy; on a single
  *                          stream plain launches are ~2 % faster, hence the default 0, or the VITVS_GRAPH environment variable
  *                          at creation).  The reference has no counterpart (one torch call chain per update, vitvs_v2.py:464-523).

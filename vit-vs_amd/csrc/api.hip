@@ -1445,6 +1445,7 @@ static int replay_update(vitvs_handle* h, UpdateArgs u, hipStream_t st) {
             size_t victim = 0;
             for (size_t i = 1; i < h->graphs.size(); ++i)
                 if (h->graphs[i].last_use < h->graphs[victim].last_use) victim = i;
+            VITVS_HIP_CHECK(hipDeviceSynchronize());   // the victim's last replay may still be queued on a stream of the caller's
             if (h->graphs[victim].exec) (void)hipGraphExecDestroy(h->graphs[victim].exec);
             if (h->graphs[victim].graph) (void)hipGraphDestroy(h->graphs[victim].graph);
             h->graphs.erase(h->graphs.begin() + victim);
