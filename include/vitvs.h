@@ -600,6 +600,42 @@ VITVS_API int vitvs_photometric_velocity(vitvs_handle* h, int32_t n_pairs, const
                                          int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
                                          int32_t interaction, double mu, double lambda, double* v_p, int32_t* p_status,
                                          double* normal, int32_t* p_info);
+/* --- the robust photometric law: lighting gain / bias and Tukey weights (photometric.hip) ------
+ * The photometric law above under a change of exposure and with objects entering the view, DESIGN.md 5l.  Every argument of
+ * vitvs_photometric_velocity_dev means what it means there; D is the pooled goal luminance I_des at a row's pixel.
+ *   illumination       0 / 1: the model I_cur ~ (1 + gamma) I_des + beta along the motion; (gamma, beta) are eliminated from the
+ *                      normal equations by a 2 x 2 LDL^T under the 6 x 6 one's pivot rule (a failed pivot: VITVS_TOO_FEW)
+ *   robust_iterations  N = 0 .. 4 re-weightings: N + 1 weighted solves x = -(H' + mu diag H')^-1 g', between two of them
+ *                      rho = |e + L x - gamma D - beta| per row, its median from a histogram of 4096 bins of 1/16 grey level
+ *                      (the first bin whose cumulative count reaches ceil(n / 2), its centre), sigma = max(1.4826 median,
+ *                      sigma_min), t = rho / (4.6851 sigma), w = (1 - t^2)^2 below t = 1, else 0
+ *   sigma_min          > 0, grey levels
+ *   v_p        lambda x of the last solve; p_status as the plain law's, VITVS_TOO_FEW (v_p = 0, p_robust = 0) also when fewer than
+ *              6 rows keep a weight or any pivot of any pass fails
+ *   p_robust   double [n_pairs][4]: gamma, beta, the last sigma (0 with N = 0), the final sum of the weights
+ *   normal45   double [n_pairs][45] or NULL, the last pass's weighted sums: A = sum w L^T L (21, upper triangle, row-major),
+ *              b = sum w L^T e (6), c = sum w e^2, B = sum w L^T [D, 1] (12, row-major), C = sum w [D,1]^T [D,1] (DD, D, sum w),
+ *              d = sum w [D,1]^T e (2)
+ *   p_info     int32 [n_pairs][8] or NULL: the plain law's six, then the rows of final weight 0 and the re-weightings run
+ * With illumination 0 and N = 0, v_p, p_status, p_info[0 .. 6) and normal45[0 .. 28) are the plain law's bit for bit.  The same
+ * bits from call to call and for a pair alone or at any place of a batch (integer atomics only).  3 N + 2 launches on `stream`,
+ * no host round trip, capturable; the handle's first call allocates the law's own blocks (1.5 MiB of band partials, a 16 KiB
+ * histogram and a state per pair of max_pairs, and the host form's staging) and synchronises the device: make it outside any
+ * stream capture.  It shares nothing with the plain law, the velocity path or the other follow-on laws; one call in flight per
+ * handle.  Returns 0, -1 (null), -2 (what the plain law refuses; illumination outside 0 / 1; robust_iterations outside 0 .. 4;
+ * sigma_min not finite or <= 0).  No counterpart in the reference. */
+VITVS_API int vitvs_photometric_robust_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                                    int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                    const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                                    int32_t illumination, int32_t robust_iterations, double sigma_min, double* v_p,
+                                                    int32_t* p_status, double* p_robust, double* normal45, int32_t* p_info,
+                                                    void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_photometric_robust_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                                int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                                int32_t illumination, int32_t robust_iterations, double sigma_min, double* v_p,
+                                                int32_t* p_status, double* p_robust, double* normal45, int32_t* p_info);
 /* The launch plan of the photometric law as host arithmetic, for one pair (no handle, no device).  It is declared here, beside the
  * calls it plans, and not among the operator hooks of include/vitvs_ops.h: out int32 [8] = the
  * pooled h = height >> level and w = width >> level, the pooled rows per band max(1, min((2048 >> level) / w, h / 256)), the bands

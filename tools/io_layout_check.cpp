@@ -113,6 +113,17 @@ int main() {
         EXPECT(io_place(io_list(ph0), nullptr) == P * (4 + 6 + 28) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
                                                       ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
                "photometric: %zu %zu", P, px_max);
+        // its robust form: the 45 sums (an even capacity) and p_robust
+        PhotometricRobustIo pr = photometric_robust_io(P, px_max * 3, px_max, n, px * 3, px, &d, &b16, &b8, &b8, &d, &i, &d, &d, &i);
+        check("photometric robust", io_list(pr), P, px_max, n);
+        PhotometricRobustIo pr0 = photometric_robust_io(P, px_max * 3, px_max);
+        EXPECT(io_place(io_list(pr0), nullptr) == io_place(io_list(pr), nullptr), "photometric robust: allocation and call disagree");
+        EXPECT(pr.Z.count == n * px && pr.I_cur.count == n * px * 3 && pr.I_des.count == n * px * 3 && pr.normal45.count == n * 45 &&
+                   pr.p_robust.count == n * 4,
+               "photometric robust: counts");
+        EXPECT(io_place(io_list(pr0), nullptr) == (P * (4 + 6 + 4) + ((P * 45 + 1) & ~(size_t)1)) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
+                                                      ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
+               "photometric robust: %zu %zu", P, px_max);
     }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");

@@ -223,8 +223,20 @@ class ServoParams:
     photometric_lambda: Optional[float] = None  # its gain; None: lambda_
     photometric_interaction: str = "desired"    # "desired": gradients of the goal image, depth = the goal depth; "current": of the
                                                 # current frame, depth = the latest depth image
+    photometric_illumination: bool = False      # the hand-over runs the robust photometric law (Engine.photometric_robust_velocity,
+                                                # DESIGN.md 5l) and estimates a lighting gain and bias with the twist
+    photometric_robust_iterations: int = 0      # 0 .. 4 Tukey re-weightings of its rows (> 0: the robust law); both off: the plain law
+    photometric_sigma_min: float = 1.0          # > 0, grey levels: the floor of the robust law's residual scale
 
     def __post_init__(self):
+        if not isinstance(self.photometric_illumination, bool):
+            raise ValueError(f"photometric_illumination is a flag, got {self.photometric_illumination!r}")
+        if isinstance(self.photometric_robust_iterations, bool) or not isinstance(self.photometric_robust_iterations, int) \
+                or not 0 <= int(self.photometric_robust_iterations) <= 4:
+            raise ValueError(f"photometric_robust_iterations is 0 .. 4, got {self.photometric_robust_iterations!r}")
+        if isinstance(self.photometric_sigma_min, bool) or not isinstance(self.photometric_sigma_min, (int, float)) \
+                or not (math.isfinite(float(self.photometric_sigma_min)) and float(self.photometric_sigma_min) > 0.0):
+            raise ValueError(f"photometric_sigma_min is finite and > 0 grey levels, got {self.photometric_sigma_min!r}")
         if not (math.isfinite(float(self.photometric_handover)) and float(self.photometric_handover) >= 0.0):
             raise ValueError(f"photometric_handover is a finite threshold >= 0 (0 = off), got {self.photometric_handover!r}")
         if isinstance(self.photometric_level, bool) or int(self.photometric_level) != self.photometric_level \
@@ -329,7 +341,8 @@ def load_reference_config(source) -> ReferenceConfig:
     ``select_cells`` (the cell grid of selection "best") likewise, else 4;
     ``roll_search`` (the roll search in front of every update) likewise, else False; ``photometric_handover``, ``photometric_level``,
     ``photometric_mu``, ``photometric_lambda`` and ``photometric_interaction`` (the hand-over to the photometric law) likewise, else
-    0.0 (off), 2, 0.01, None and "desired"."""
+    0.0 (off), 2, 0.01, None and "desired"; ``photometric_illumination``, ``photometric_robust_iterations`` and
+    ``photometric_sigma_min`` (its robust form) likewise, else False, 0 and 1.0."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -361,13 +374,17 @@ def load_reference_config(source) -> ReferenceConfig:
                         photometric_level=cfg.get("photometric_level", 2),
                         photometric_mu=float(cfg.get("photometric_mu", 0.01)),
                         photometric_lambda=(None if cfg.get("photometric_lambda") is None else float(cfg["photometric_lambda"])),
-                        photometric_interaction=str(cfg.get("photometric_interaction", "desired")))
+                        photometric_interaction=str(cfg.get("photometric_interaction", "desired")),
+                        photometric_illumination=cfg.get("photometric_illumination", False),
+                        photometric_robust_iterations=cfg.get("photometric_robust_iterations", 0),
+                        photometric_sigma_min=cfg.get("photometric_sigma_min", 1.0))
     used = {"roll_search","u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
             "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed",
-            "photometric_handover", "photometric_level", "photometric_mu", "photometric_lambda", "photometric_interaction"}
+            "photometric_handover", "photometric_level", "photometric_mu", "photometric_lambda", "photometric_interaction",
+            "photometric_illumination", "photometric_robust_iterations", "photometric_sigma_min"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -142,6 +142,9 @@ struct vitvs_handle {
     // its band partials at max_pairs pairs of the most bands a frame can have, photo_io = PhotometricIo at max_pairs frames of
     // v_max x u_max
     unsigned char *photo_ws = nullptr, *photo_io = nullptr;
+    // its robust form (vitvs_photometric_robust_velocity[_dev]) shares nothing with it: photo_robust_ws = the 48-double band partials,
+    // one histogram and one state per pair (photometric_robust_ws_bytes), photo_robust_io = PhotometricRobustIo
+    unsigned char *photo_robust_ws = nullptr, *photo_robust_io = nullptr;
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -2075,8 +2078,8 @@ int vitvs_roll_velocity(vitvs_handle* h, const uint8_t* I_cur, const uint8_t* I_
 // no later call allocates, and PhotometricIo at max_pairs frames of v_max x u_max.  As with the other laws, calls on different
 // streams of one handle share the partials: one call in flight per handle.
 constexpr size_t kPhotoWsPerPair = (size_t)4096 * 32 * sizeof(double);
-static int photometric_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction, double depth_scale,
-                               double mu, double lambda, bool host_form) {
+static int photometric_check(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction, double depth_scale,
+                             double mu, double lambda, bool host_form) {
     const vitvs_config& c = h->cfg;
     if (n_pairs < 1 || n_pairs > c.max_pairs) return set_err(h, -2, "n_pairs is 1 .. max_pairs");
     if (level < 0 || level > 3) return set_err(h, -2, "level is 0 .. 3");
@@ -2092,6 +2095,13 @@ static int photometric_prepare(vitvs_handle* h, int n_pairs, int height, int wid
     PhotometricPlan pl;
     if (int rc = plan_photometric(height, width, level, c.max_pairs, &pl)) return set_err(h, rc, "no photometric plan");
     if (pl.ws_bytes > (size_t)c.max_pairs * kPhotoWsPerPair) return set_err(h, -3, "the photometric plan has more bands than the workspace");
+    return 0;
+}
+static int photometric_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction, double depth_scale,
+                               double mu, double lambda, bool host_form) {
+    if (int rc = photometric_check(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, host_form)) return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max;
     PhotometricIo io = photometric_io(c.max_pairs, px_max * 3, px_max);
     return law_blocks(h, "photometric", &h->photo_ws, (size_t)c.max_pairs * kPhotoWsPerPair, &h->photo_io, io_place(io_list(io), nullptr));
 }
@@ -2129,6 +2139,69 @@ int vitvs_photometric_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* 
                                               Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale, io.K.f64(), level,
                                               interaction, mu, lambda, io.v_p.f64(), io.p_status.i32(), normal ? io.normal.f64() : nullptr,
                                               p_info ? io.p_info.i32() : nullptr, st);
+    });
+}
+
+// --- the robust photometric law ------------------------------------------------------------------
+// Everything the plain law refuses, and the three parameters of its own; the first call allocates the law's own two blocks (the
+// 48-double band partials at 4096 bands, a histogram and a state per pair of max_pairs; PhotometricRobustIo), zeroed, so no later
+// call allocates.
+static int photometric_robust_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction,
+                                      double depth_scale, double mu, double lambda, int illumination, int robust_iterations,
+                                      double sigma_min, bool host_form) {
+    if (int rc = photometric_check(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, host_form)) return rc;
+    if (illumination != 0 && illumination != 1) return set_err(h, -2, "illumination is 0 or 1");
+    if (robust_iterations < 0 || robust_iterations > 4) return set_err(h, -2, "robust_iterations is 0 .. 4");
+    if (!std::isfinite(sigma_min) || !(sigma_min > 0.0)) return set_err(h, -2, "sigma_min is finite and > 0");
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max;
+    PhotometricRobustIo io = photometric_robust_io(c.max_pairs, px_max * 3, px_max);
+    return law_blocks(h, "robust photometric", &h->photo_robust_ws, photometric_robust_ws_bytes(c.max_pairs), &h->photo_robust_io,
+                      io_place(io_list(io), nullptr));
+}
+
+int vitvs_photometric_robust_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                          int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                          int32_t interaction, double mu, double lambda, int32_t illumination,
+                                          int32_t robust_iterations, double sigma_min, double* v_p, int32_t* p_status, double* p_robust,
+                                          double* normal45, int32_t* p_info, void* stream) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_robust_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, illumination,
+                                            robust_iterations, sigma_min, false))
+        return rc;
+    PhotometricRobustArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    PhotometricArgs& a = ra.p;
+    a.n_pairs = n_pairs; a.height = height; a.width = width; a.level = level; a.interaction = interaction;
+    a.I_cur = I_cur; a.I_des = I_des; a.Z_mm = Z_mm; a.depth_scale = depth_scale; a.K = K; a.mu = mu; a.lambda = lambda;
+    a.v_p = v_p; a.p_status = p_status; a.p_info = p_info;
+    ra.illumination = illumination; ra.iterations = robust_iterations; ra.sigma_min = sigma_min;
+    ra.p_robust = p_robust; ra.normal45 = normal45;
+    const int rc = launch_photometric_robust(ra, h->photo_robust_ws, h->cfg.max_pairs, dev_stream(h, stream));
+    return rc ? set_err(h, rc, "robust photometric law launch failed") : 0;
+}
+
+int vitvs_photometric_robust_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                      int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                      int32_t interaction, double mu, double lambda, int32_t illumination, int32_t robust_iterations,
+                                      double sigma_min, double* v_p, int32_t* p_status, double* p_robust, double* normal45,
+                                      int32_t* p_info) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_robust_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, illumination,
+                                            robust_iterations, sigma_min, true))
+        return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max, px = (size_t)height * width;
+    PhotometricRobustIo io = photometric_robust_io(c.max_pairs, px_max * 3, px_max, n_pairs, px * 3, px, K, Z_mm, I_cur, I_des, v_p,
+                                                   p_status, p_robust, normal45, p_info);
+    return host_call(h, io_list(io), h->photo_robust_io, [&](hipStream_t st) {
+        return vitvs_photometric_robust_velocity_dev(h, n_pairs, io.I_cur.dev, io.I_des.dev, height, width,
+                                                     Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale,
+                                                     io.K.f64(), level, interaction, mu, lambda, illumination, robust_iterations,
+                                                     sigma_min, io.v_p.f64(), io.p_status.i32(), io.p_robust.f64(),
+                                                     normal45 ? io.normal45.f64() : nullptr, p_info ? io.p_info.i32() : nullptr, st);
     });
 }
 

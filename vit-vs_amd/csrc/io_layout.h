@@ -133,4 +133,22 @@ inline PhotometricIo photometric_io(size_t P, size_t frame_max, size_t depth_max
                          io_in(1, f_cap, n * frame, I_cur),  io_in(1, f_cap, n * frame, I_des)};
 }
 
+// the robust photometric law (vitvs_photometric_robust_velocity): PhotometricIo with the 45 sums in place of the 28 and p_robust
+// (gamma, beta, sigma, sum w per pair).  The 45 sums' capacity is rounded to an even count, so that the images still begin on
+// 16-byte boundaries.
+struct PhotometricRobustIo {
+    IoField K, v_p, normal45, p_robust, p_status, p_info, Z, I_cur, I_des;
+};
+inline PhotometricRobustIo photometric_robust_io(size_t P, size_t frame_max, size_t depth_max, size_t n = 0, size_t frame = 0,
+                                                 size_t depth = 0, const double* K = nullptr, const uint16_t* Z = nullptr,
+                                                 const uint8_t* I_cur = nullptr, const uint8_t* I_des = nullptr, double* v_p = nullptr,
+                                                 int32_t* p_status = nullptr, double* p_robust = nullptr, double* normal45 = nullptr,
+                                                 int32_t* p_info = nullptr) {
+    const size_t st_cap = (P + 3) & ~(size_t)3, z_cap = (P * depth_max + 7) & ~(size_t)7, f_cap = (P * frame_max + 15) & ~(size_t)15;
+    const size_t n45_cap = (P * 45 + 1) & ~(size_t)1;
+    return PhotometricRobustIo{io_in(8, P * 4, n * 4, K),          io_out(8, P * 6, n * 6, v_p),      io_out(8, n45_cap, n * 45, normal45),
+                               io_out(8, P * 4, n * 4, p_robust),  io_out(4, st_cap, n, p_status),    io_out(4, P * 8, n * 8, p_info),
+                               io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur), io_in(1, f_cap, n * frame, I_des)};
+}
+
 }  // namespace vitvs

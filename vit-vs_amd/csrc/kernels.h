@@ -663,6 +663,25 @@ struct PhotometricPlan {
 int plan_photometric(int height, int width, int level, int max_pairs, PhotometricPlan* plan);
 int launch_photometric(const PhotometricArgs& a, hipStream_t stream);
 
+// The robust photometric law: the plain law's rows under the lighting model I_cur ~ (1 + gamma) I_des + beta
+// (`illumination`) and Tukey weights (`iterations` re-weightings, the scale from a histogram median of the residuals, at least
+// sigma_min grey levels).  3 iterations + 2 launches, no host round trip.  p.ws, hist and state are set by launch_photometric_robust
+// from its block of photometric_robust_ws_bytes(max_pairs) bytes, which every call must find with its histograms zero (as the
+// allocation and every call leave them); p.normal is not read.
+struct PhotometricRobustArgs {
+    PhotometricArgs p;        // p.ws: [n_pairs][bands][48] the band partials
+    int illumination;         // 0 / 1
+    int iterations;           // 0 .. 4
+    double sigma_min;         // > 0
+    uint32_t* hist;           // [n_pairs][4096] bins of 1 / 16 grey level
+    double* state;            // [n_pairs][16] x (6), gamma, beta, sigma, (rows, failed), (median bin)
+    // outputs (p.p_info slot 6: rows of final weight 0; slot 7: re-weightings run)
+    double* p_robust;         // [n_pairs][4] gamma, beta, the last sigma (0: no re-weighting), the final sum of the weights
+    double* normal45;         // [n_pairs][45] or null: the last pass's sums A (21), b (6), c, B (12), C (3), d (2)
+};
+size_t photometric_robust_ws_bytes(int max_pairs);
+int launch_photometric_robust(const PhotometricRobustArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

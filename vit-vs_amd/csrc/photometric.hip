@@ -9,7 +9,7 @@
 //                              ascending band order, damps and runs LDL^T (solve.h)
 // No float atomics: pixel -> thread -> wave -> band is a function of (H, W, level) alone (plan_photometric), so the sums are the
 // same bits from call to call and for a pair alone or anywhere in a batch.  (One launch with a last-arriver ticket in place of the
-// second: priced and not built)
+// second: priced and not built)  The law's robust form has kernels of its own at the end of the file.
 #include <algorithm>
 
 #include "common.h"
@@ -318,6 +318,425 @@ int launch_photometric(const PhotometricArgs& a, hipStream_t stream) {
     }
     launch(photometric_solve_kernel, dim3(a.n_pairs), dim3(256), 0, stream, a, p.h, p.w, p.bands, no_depth);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- the robust photometric law ---------------------------------------------------------------------------------
+// The plain law's rows under a lighting model I_cur ~ (1 + gamma) I_des + beta and Tukey weights: N + 1 weighted solves with a
+// re-weighting between two of them, 3 N + 2 launches and no host round trip (kernels.h PhotometricRobustArgs).  The same band plan
+// and the same pixel -> thread -> wave -> band order as above; the median of the residuals comes from a histogram of integer
+// counts (integer atomics only: order-free), so every pass is the same bits from call to call.
+//   photometric_robust_rows_kernel<WEIGHTED>   the 45 weighted sums of a band; WEIGHTED (passes >= 1): sigma from the pair's
+//                                              histogram (every workgroup for itself), w from the state of the solve before
+//   photometric_residual_kernel                rho of the band's rows into an LDS histogram, its non-empty bins into the pair's
+//   photometric_robust_solve_kernel            the bands in ascending order, the 2 x 2 elimination of (gamma, beta), LDL^T; writes
+//                                              the state and clears the histogram
+constexpr int kPhotoRPart = 48;      // doubles per (pair, band) partial: the 45 sums, rows and holes as two int32, the zero weights
+constexpr int kPhotoBins = 4096;     // histogram bins of 1 / 16 grey level; the last one takes everything from 256 grey levels on
+constexpr int kPhotoState = 16;      // doubles per pair: x (6), gamma, beta, sigma, (int32 rows, int32 failed), (int32 median bin)
+constexpr double kTukeyC = 4.6851, kMadScale = 1.4826;
+
+// the pooled luminances (and depth) of the band [r0, r1) into LDS, as photometric_rows_kernel's first half; ends on a barrier
+__device__ __forceinline__ void pool_band(const PhotometricArgs& a, int pair, int h, int w, int rows, int r0, int r1, int* lum_cur,
+                                          int* lum_des, int* zs, int tid) {
+    const int H = a.height, W = a.width, level = a.level, s = 1 << level;
+    for (int i = tid; i < ((rows + 2) * 2 + rows) * w; i += 256) lum_cur[i] = 0;
+    __syncthreads();
+    const int p0 = max(r0 - 1, 0), p1 = min(r1 + 1, h), cols = w * s;
+    const uint8_t* cur = a.I_cur + (size_t)pair * H * W * 3;
+    const uint8_t* des = a.I_des + (size_t)pair * H * W * 3;
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+        const uint8_t* img = which ? des : cur;
+        int* lum = which ? lum_des : lum_cur;
+        const unsigned long long addr = (unsigned long long)(uintptr_t)img;
+        const bool halo = which == (a.interaction ? 1 : 0);
+        const int f0 = (halo ? p0 : r0) * s, f1 = (halo ? p1 : r1) * s;
+        if (W % 16 == 0 && addr % 16 == 0) pool_frame<16>(img, W, f0, f1, cols, level, r0 - 1, w, lum, tid);
+        else if (W % 4 == 0 && addr % 4 == 0) pool_frame<4>(img, W, f0, f1, cols, level, r0 - 1, w, lum, tid);
+        else pool_frame<1>(img, W, f0, f1, cols, level, r0 - 1, w, lum, tid);
+    }
+    if (a.Z_mm) {
+        const uint16_t* z = a.Z_mm + (size_t)pair * H * W;
+        const unsigned long long addr = (unsigned long long)(uintptr_t)z;
+        if (W % 8 == 0 && addr % 16 == 0) pool_depth<8>(z, W, r0 * s, r1 * s, cols, level, r0, w, zs, tid);
+        else if (W % 2 == 0 && addr % 4 == 0) pool_depth<2>(z, W, r0 * s, r1 * s, cols, level, r0, w, zs, tid);
+        else pool_depth<1>(z, W, r0 * s, r1 * s, cols, level, r0, w, zs, tid);
+    }
+    __syncthreads();
+}
+
+// what a row needs of the intrinsics at the pooled scale
+struct PhotoCamera {
+    double fxp, fyp, cxp, cyp, inv;
+};
+__device__ __forceinline__ PhotoCamera photo_camera(const double* K, int level) {
+    const double sd = (double)(1 << level);
+    return PhotoCamera{K[0] / sd, K[1] / sd, (K[2] + 0.5) / sd - 0.5, (K[3] + 0.5) / sd - 0.5, 1.0 / (256.0 * sd * sd)};
+}
+
+// The row of pooled pixel (r, c), LDS row lr of the band: L, e and D in photometric_rows_kernel's operations.  0: a row; 1: the
+// border, no row; 2: a hole, no row.
+__device__ __forceinline__ int photo_row(const PhotoCamera& k, const int* grad, const int* lum_cur, const int* lum_des, const int* zs,
+                                         bool have_z, double depth_scale, int h, int w, int lr, int c, int r, double (&L)[6], double& e,
+                                         double& D) {
+    if (r < 1 || r > h - 2 || c < 1 || c > w - 2) return 1;
+    const int at = (lr + 1) * w + c;
+    double Z = depth_scale;
+    if (have_z) {
+        const int zp = zs[lr * w + c], count = zp & 127;
+        if (count == 0) return 2;
+        Z = (double)(zp >> 7) / ((double)count * 1000.0);
+    }
+    const double gx = (double)(grad[at + 1] - grad[at - 1]) * k.inv * 0.5;
+    const double gy = (double)(grad[at + w] - grad[at - w]) * k.inv * 0.5;
+    e = (double)(lum_cur[at] - lum_des[at]) * k.inv;
+    D = (double)lum_des[at] * k.inv;
+    const double x = ((double)c - k.cxp) / k.fxp, y = ((double)r - k.cyp) / k.fyp;
+    const double ga = gx * k.fxp, gb = gy * k.fyp;
+    L[0] = ga / Z;
+    L[1] = gb / Z;
+    L[2] = -(x * ga + y * gb) / Z;
+    L[3] = -(x * y * ga + (1.0 + y * y) * gb);
+    L[4] = (1.0 + x * x) * ga + x * y * gb;
+    L[5] = x * gb - y * ga;
+    return 0;
+}
+
+// rho = |((e + L.x) - gamma D) - beta|, st = the pair's state
+__device__ __forceinline__ double photo_rho(const double (&L)[6], double e, double D, const double (&st)[8]) {
+    double p = L[0] * st[0];
+#pragma unroll
+    for (int i = 1; i < 6; ++i) p += L[i] * st[i];
+    return fabs(((e + p) - st[6] * D) - st[7]);
+}
+
+// The first bin at which the cumulative count of the pair's histogram reaches `need`, by all 256 threads (16 bins each); scan[257]
+// is LDS.  Ends on a barrier.  (need < 1 or past the total: 0)
+__device__ __forceinline__ int photo_median_bin(const uint32_t* __restrict__ hist, int need, int* scan, int tid) {
+    unsigned c[16];
+    const u32x4* q = reinterpret_cast<const u32x4*>(hist + tid * 16);
+    int mine = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const u32x4 d = q[i];
+        c[4 * i] = d[0]; c[4 * i + 1] = d[1]; c[4 * i + 2] = d[2]; c[4 * i + 3] = d[3];
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mine += (int)c[i];
+    scan[tid] = mine;
+    if (tid == 0) scan[256] = 0;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int below = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += below;
+        __syncthreads();
+    }
+    const int upto = scan[tid], before = upto - mine;
+    if (before < need && upto >= need) {                // one thread: the counts are integers
+        int cum = before, bin = 15;
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            cum += (int)c[i];
+            if (!found && cum >= need) { bin = i; found = true; }
+        }
+        scan[256] = tid * 16 + bin;
+    }
+    __syncthreads();
+    return scan[256];
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void photometric_robust_rows_kernel(PhotometricRobustArgs ra, int h, int w, int rows, int bands) {
+    extern __shared__ double photo_lds[];
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int band = blockIdx.x, pair = blockIdx.y;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    double* red = photo_lds;                            // [4][48]; before the sums, the scan of the histogram (257 int32)
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    double st[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double scale = 1.0;                                 // kTukeyC * sigma
+    if constexpr (WEIGHTED) {
+        double* state = ra.state + (size_t)pair * kPhotoState;
+        const int32_t* si = reinterpret_cast<const int32_t*>(state + 9);
+        if (si[1]) return;                              // a solve before this one failed: the call's answer is written
+#pragma unroll
+        for (int i = 0; i < 8; ++i) st[i] = state[i];
+        const int bin = photo_median_bin(ra.hist + (size_t)pair * kPhotoBins, (si[0] + 1) / 2, reinterpret_cast<int*>(red), tid);
+        const double median = ((double)bin + 0.5) / 16.0;
+        const double sigma = fmax(kMadScale * median, ra.sigma_min);
+        scale = kTukeyC * sigma;
+        if (band == 0 && tid == 0) { state[8] = sigma; reinterpret_cast<int32_t*>(state + 10)[0] = bin; }
+    }
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    double acc[45];
+#pragma unroll
+    for (int q = 0; q < 45; ++q) acc[q] = 0.0;
+    int n = 0, holes = 0, zeros = 0;
+    for (int idx = tid; idx < (r1 - r0) * w; idx += 256) {
+        const int lr = idx / w, c = idx - lr * w, r = r0 + lr;
+        double L[6], e, D;
+        const int kind = photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D);
+        if (kind == 2) ++holes;
+        if (kind != 0) continue;
+        double wt = 1.0;
+        if constexpr (WEIGHTED) {
+            const double t = photo_rho(L, e, D, st) / scale;
+            const double u = 1.0 - t * t;
+            wt = t < 1.0 ? u * u : 0.0;
+            if (wt == 0.0) ++zeros;
+        }
+        double wv[8];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wv[i] = wt * L[i];
+        wv[6] = wt * e;
+        wv[7] = wt * D;
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) { acc[q] += wv[i] * L[j]; ++q; }
+#pragma unroll
+        for (int i = 0; i < 7; ++i) acc[21 + i] += wv[i] * e;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { acc[28 + 2 * i] += wv[i] * D; acc[29 + 2 * i] += wv[i]; }
+        acc[40] += wv[7] * D;
+        acc[41] += wv[7];
+        acc[42] += wt;
+        acc[43] += wv[7] * e;
+        acc[44] += wv[6];
+        ++n;
+    }
+    __syncthreads();                                    // (WEIGHTED: the scan is read; `red` is the sums' from here)
+#pragma unroll
+    for (int q = 0; q < 45; ++q) {
+        const double t = wave_sum(acc[q]);
+        if (lane == 0) red[wave * kPhotoRPart + q] = t;
+    }
+    n = wave_sum(n);
+    holes = wave_sum(holes);
+    zeros = wave_sum(zeros);
+    if (lane == 0) { int* c = reinterpret_cast<int*>(red + wave * kPhotoRPart + 45); c[0] = n; c[1] = holes; c[2] = zeros; c[3] = 0; }
+    __syncthreads();
+    double* part = a.ws + ((size_t)pair * bands + band) * kPhotoRPart;
+    if (tid < 45) {                                     // the four waves in wave order
+        double t = red[tid];
+        t += red[kPhotoRPart + tid];
+        t += red[2 * kPhotoRPart + tid];
+        t += red[3 * kPhotoRPart + tid];
+        part[tid] = t;
+    } else if (tid < 49) {
+        const int k = tid - 45;
+        const int* c = reinterpret_cast<const int*>(red + 45) + k;
+        reinterpret_cast<int32_t*>(part + 45)[k] = c[0] + c[2 * kPhotoRPart] + c[4 * kPhotoRPart] + c[6 * kPhotoRPart];
+    }
+}
+
+__global__ __launch_bounds__(256) void photometric_residual_kernel(PhotometricRobustArgs ra, int h, int w, int rows, int bands) {
+    extern __shared__ double photo_lds[];
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, band = blockIdx.x, pair = blockIdx.y;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);          // the rows launch's layout, the histogram behind it
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    unsigned* bins = reinterpret_cast<unsigned*>(zs + rows * w);
+    const double* state = ra.state + (size_t)pair * kPhotoState;
+    if (reinterpret_cast<const int32_t*>(state + 9)[1]) return;
+    double st[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = state[i];
+    for (int i = tid; i < kPhotoBins; i += 256) bins[i] = 0u;
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);          // (its barriers order the zeros above too)
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    for (int idx = tid; idx < (r1 - r0) * w; idx += 256) {
+        const int lr = idx / w, c = idx - lr * w, r = r0 + lr;
+        double L[6], e, D;
+        if (photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D) != 0) continue;
+        const double rho = photo_rho(L, e, D, st);
+        const int q = rho < (double)(kPhotoBins / 16) ? (int)(16.0 * rho) : kPhotoBins - 1;      // (a NaN: the last bin)
+        atomicAdd(&bins[q], 1u);
+    }
+    __syncthreads();
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;
+    for (int i = tid; i < kPhotoBins; i += 256) {
+        const unsigned cnt = bins[i];
+        if (cnt) atomicAdd(&hist[i], cnt);
+    }
+}
+
+constexpr int kPhotoRChunk = 64;     // bands per chunk: 64 x 48 doubles = 12 per thread
+
+__global__ __launch_bounds__(256) void photometric_robust_solve_kernel(PhotometricRobustArgs ra, int h, int w, int bands, int no_depth,
+                                                                       int pass) {
+    __shared__ double Gs[40 + 8 * 27];
+    __shared__ double S[kPhotoRPart];
+    __shared__ double chunk[kPhotoRChunk * kPhotoRPart];
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.x;
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;                         // read by this pass's rows launch; the next
+    for (int i = tid; i < kPhotoBins; i += 256) hist[i] = 0u;                    // re-weighting (this call's or the next's) fills it
+    double* state = ra.state + (size_t)pair * kPhotoState;
+    int32_t* si = reinterpret_cast<int32_t*>(state + 9);
+    if (pass > 0 && si[1]) return;
+    for (int i = tid; i < 40 + 8 * 27; i += 256) Gs[i] = 0.0;
+    const double* part = a.ws + (size_t)pair * bands * kPhotoRPart;
+    double sum = 0.0;                                   // lanes 0 .. 44 of wave 0: one of the 45 sums each
+    int count = 0;                                      // lane 45: the rows; 46: the holes; 47: the rows of weight 0
+    const int total = no_depth ? 0 : bands * kPhotoRPart;
+    double held[12];
+#pragma unroll
+    for (int u = 0; u < 12; ++u) { const int i = tid + 256 * u; held[u] = i < total ? part[i] : 0.0; }
+    for (int c0 = 0; c0 < total; c0 += kPhotoRChunk * kPhotoRPart) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 12; ++u) chunk[tid + 256 * u] = held[u];
+        __syncthreads();
+        const int next = c0 + kPhotoRChunk * kPhotoRPart;
+#pragma unroll
+        for (int u = 0; u < 12; ++u) { const int i = next + tid + 256 * u; held[u] = i < total ? part[i] : 0.0; }
+        if (wave == 0) {
+            const int nb = min(kPhotoRChunk, bands - c0 / kPhotoRPart);
+            if (lane < 45) {
+                for (int b = 0; b < nb; ++b) sum += chunk[b * kPhotoRPart + lane];         // ascending band order
+            } else if (lane < 48) {
+                const int32_t* c = reinterpret_cast<const int32_t*>(chunk + 45) + (lane - 45);
+                for (int b = 0; b < nb; ++b) count += c[b * kPhotoRPart * 2];
+            }
+        }
+    }
+    if (wave != 0) return;
+    const int n = __builtin_amdgcn_readlane(count, 45), holes = __builtin_amdgcn_readlane(count, 46);
+    const int zeros = __builtin_amdgcn_readlane(count, 47);
+    if (ra.normal45 && lane < 45) ra.normal45[(size_t)pair * 45 + lane] = sum;
+    if (lane < 45) S[lane] = sum;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same wave: the LDS writes above are visible below
+    // C = [[S40, S41], [S41, S42]] = l d l^T under solve_ldlt's pivot rule; z = C^-1 (p, q): z1 = (q - l p) / d1, z0 = p / d0 - l z1
+    bool cgood = true;
+    double l = 0.0, i0 = 0.0, i1 = 0.0;
+    if (ra.illumination) {
+        const double DD = S[40], Dm = S[41], Sw = S[42];
+        const double d0 = DD;
+        cgood = (d0 > kPivotThreshold * DD) && (DD > 0.0);
+        i0 = 1.0 / d0;
+        l = Dm * i0;
+        const double d1 = Sw - l * l * d0;
+        cgood = cgood && (d1 > kPivotThreshold * Sw) && (Sw > 0.0);
+        i1 = 1.0 / d1;
+    }
+    if (lane < 27) {
+        double val = sum;
+        if (ra.illumination) {
+            int i, j = 0;
+            if (lane < 21) {
+                int q = lane;
+                i = 0;
+                while (q >= 6 - i) { q -= 6 - i; ++i; }
+                j = i + q;
+            } else {
+                i = lane - 21;
+            }
+            const double p = S[28 + 2 * i], q1 = S[29 + 2 * i];
+            const double u1 = (q1 - l * p) * i1, u0 = p * i0 - l * u1;
+            const double o0 = lane < 21 ? S[28 + 2 * j] : S[43], o1 = lane < 21 ? S[29 + 2 * j] : S[44];
+            val = sum - (u0 * o0 + u1 * o1);
+        }
+        const bool diag = lane == 0 || lane == 6 || lane == 11 || lane == 15 || lane == 18 || lane == 20;
+        Gs[40 + lane] = diag ? val + a.mu * val : val;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool solved = false;
+    const bool tried = !no_depth && n >= 6 && n - zeros >= 6;
+    if (tried && cgood) solved = solve_ldlt(Gs, lane, x);
+    double gamma = 0.0, beta = 0.0;
+    if (solved && ra.illumination) {
+        double t0 = S[43], t1 = S[44];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { t0 = t0 + S[28 + 2 * i] * -x[i]; t1 = t1 + S[29 + 2 * i] * -x[i]; }
+        beta = (t1 - l * t0) * i1;
+        gamma = t0 * i0 - l * beta;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            state[i] = -x[i];
+            a.v_p[(size_t)pair * 6 + i] = solved ? -a.lambda * x[i] : 0.0;
+        }
+        state[6] = gamma;
+        state[7] = beta;
+        si[0] = n;
+        si[1] = solved ? 0 : 1;
+        a.p_status[pair] = no_depth ? ST_NO_DEPTH : solved ? ST_OK : ST_TOO_FEW;
+        if (a.p_info) {
+            int32_t* pi = a.p_info + (size_t)pair * 8;
+            pi[0] = n; pi[1] = h; pi[2] = w; pi[3] = bands; pi[4] = holes; pi[5] = (tried && !solved) ? 1 : 0; pi[6] = zeros; pi[7] = pass;
+        }
+        double* pr = ra.p_robust + (size_t)pair * 4;
+        pr[0] = gamma;
+        pr[1] = beta;
+        pr[2] = (solved && pass > 0) ? state[8] : 0.0;
+        pr[3] = solved ? S[42] : 0.0;
+    }
+}
+
+size_t photometric_robust_ws_bytes(int max_pairs) {
+    return (size_t)max_pairs * ((size_t)4096 * kPhotoRPart * sizeof(double) + kPhotoBins * sizeof(uint32_t) + kPhotoState * sizeof(double));
+}
+
+int launch_photometric_robust(const PhotometricRobustArgs& ra_in, unsigned char* ws, int max_pairs, hipStream_t stream) {
+    PhotometricRobustArgs ra = ra_in;
+    PhotometricArgs& a = ra.p;
+    if (a.n_pairs < 1 || a.n_pairs > 65535 || a.n_pairs > max_pairs || !a.I_cur || !a.I_des || !a.K || !ws || !a.v_p || !a.p_status ||
+        !ra.p_robust)
+        return -2;
+    if (a.interaction < 0 || a.interaction > 1 || !(a.mu >= 0.0) || !(a.mu < __builtin_huge_val())) return -2;
+    if (!(a.lambda == a.lambda) || !(a.depth_scale == a.depth_scale)) return -2;
+    if (ra.illumination < 0 || ra.illumination > 1 || ra.iterations < 0 || ra.iterations > 4) return -2;
+    if (!(ra.sigma_min > 0.0) || !(ra.sigma_min < __builtin_huge_val())) return -2;
+    PhotometricPlan p;
+    if (int rc = plan_photometric(a.height, a.width, a.level, a.n_pairs, &p)) return rc;
+    // the block: the partials of max_pairs pairs at 4096 bands, then the histograms, then the states
+    a.ws = reinterpret_cast<double*>(ws);
+    ra.hist = reinterpret_cast<uint32_t*>(ws + (size_t)max_pairs * 4096 * kPhotoRPart * sizeof(double));
+    ra.state = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(ra.hist) + (size_t)max_pairs * kPhotoBins * sizeof(uint32_t));
+    const size_t lds = p.lds - 4 * kPhotoPart * sizeof(double) + 4 * kPhotoRPart * sizeof(double);
+    const size_t lds_res = lds + kPhotoBins * sizeof(uint32_t);
+    const int no_depth = (!a.Z_mm && !(a.depth_scale > 0.0)) ? 1 : 0;
+    if (no_depth) {
+        launch(photometric_robust_solve_kernel, dim3(a.n_pairs), dim3(256), 0, stream, ra, p.h, p.w, p.bands, 1, 0);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    static std::atomic<unsigned long long> raised0{0}, raised1{0}, raised2{0};
+    if (lds > 64 * 1024 &&
+        (raise_lds_limit(reinterpret_cast<const void*>(photometric_robust_rows_kernel<false>), 160 * 1024, raised0) ||
+         raise_lds_limit(reinterpret_cast<const void*>(photometric_robust_rows_kernel<true>), 160 * 1024, raised1)))
+        return -3;
+    if (ra.iterations > 0 && lds_res > 64 * 1024 &&
+        raise_lds_limit(reinterpret_cast<const void*>(photometric_residual_kernel), 160 * 1024, raised2))
+        return -3;
+    const dim3 grid(p.bands, a.n_pairs);
+    for (int pass = 0; pass <= ra.iterations; ++pass) {
+        if (pass > 0) {
+            launch(photometric_residual_kernel, grid, dim3(256), lds_res, stream, ra, p.h, p.w, p.rows, p.bands);
+            launch(photometric_robust_rows_kernel<true>, grid, dim3(256), lds, stream, ra, p.h, p.w, p.rows, p.bands);
+        } else {
+            launch(photometric_robust_rows_kernel<false>, grid, dim3(256), lds, stream, ra, p.h, p.w, p.rows, p.bands);
+        }
+        if (hipGetLastError() != hipSuccess) return -1;
+        launch(photometric_robust_solve_kernel, dim3(a.n_pairs), dim3(256), 0, stream, ra, p.h, p.w, p.bands, 0, pass);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
 }
 
 }  // namespace vitvs

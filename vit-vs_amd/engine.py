@@ -606,6 +606,70 @@ class Engine:
         ``params.v_max`` x ``params.u_max`` pixels."""
         return self._photometric(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale)
 
+    # ------------------------------------------------------------------ the robust photometric law
+    @staticmethod
+    def _photometric_robust_scalars(illumination, robust_iterations, sigma_min):
+        if illumination not in (False, True, 0, 1):
+            raise VitvsError(f"illumination is a flag, got {illumination!r}")
+        if isinstance(robust_iterations, bool) or int(robust_iterations) != robust_iterations or not 0 <= int(robust_iterations) <= 4:
+            raise VitvsError(f"robust_iterations is 0 .. 4, got {robust_iterations!r}")
+        if not (math.isfinite(float(sigma_min)) and float(sigma_min) > 0.0):
+            raise VitvsError(f"sigma_min is finite and > 0 grey levels, got {sigma_min!r}")
+        return int(bool(illumination)), int(robust_iterations), float(sigma_min)
+
+    def photometric_robust_velocity(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                    lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,
+                                    robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_robust_velocity_dev``: the photometric law under a lighting model and Tukey weights.
+        The arguments of ``photometric_velocity``, and ``illumination`` (estimate the gain and bias ``I_cur ~ (1 + gamma) I_des +
+        beta`` with the twist), ``robust_iterations`` 0 .. 4 re-weightings and ``sigma_min`` > 0, the floor of the residual scale in
+        grey levels.  3 ``robust_iterations`` + 2 launches on the current stream.  Returns ``(v float64 [n, 6] device tensor,
+        info)``: ``photometric_velocity``'s ``info`` with ``normal`` float64 [n, 45] (``cost`` = sum w e^2 / sum w), and ``gamma``, ``gain``
+        (1 + gamma), ``bias``, ``sigma`` (the last scale; 0 without a re-weighting), ``weight`` (the final sum of the weights),
+        ``rejected`` (the share of rows at weight 0) and ``reweightings``.  With ``illumination`` off and ``robust_iterations`` 0
+        the twist is ``photometric_velocity``'s bit for bit.  Reading ``info`` synchronises; the engine's first call allocates:
+        make it outside a stream capture."""
+        return self._photometric_robust(False, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, illumination,
+                                        robust_iterations, sigma_min)
+
+    def _photometric_robust(self, host, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, illumination,
+                            robust_iterations, sigma_min):
+        """``photometric_robust_velocity`` (``vitvs_photometric_robust_velocity_dev``) and ``photometric_robust_velocity_host``
+        (``vitvs_photometric_robust_velocity``)."""
+        stage = self._stage(host)
+        cur = stage.frames(I_cur, None, None)
+        n, hh, ww = (int(x) for x in cur.shape[:3])
+        des = stage.frames(I_des, n, (hh, ww))
+        z = stage.depth(Z, n, (hh, ww))
+        kk = stage.intrinsics(K, n)
+        illum, iters, smin = self._photometric_robust_scalars(illumination, robust_iterations, sigma_min)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        v, st, robust, normal, pinfo, p = stage.f64(n, 6), stage.i32(n), stage.f64(n, 4), stage.f64(n, 45), stage.i32(n, 8), stage.ptr
+        entry = "vitvs_photometric_robust_velocity" + ("" if host else "_dev")
+        rc = getattr(self.lib, entry)(self.handle, n, p(cur), p(des), hh, ww, p(z), ds, p(kk), level, inter, mu, lam, illum, iters, smin,
+                                      p(v), p(st), p(robust), p(normal), p(pinfo), *stage.stream)
+        self._check(rc, entry)
+        return v, self._photometric_robust_info(stage.read(st), stage.read(normal), stage.read(pinfo), stage.read(robust))
+
+    @staticmethod
+    def _photometric_robust_info(status, normal, pinfo, robust) -> dict:
+        n, weight = pinfo[:, 0], robust[:, 3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cost = np.where(weight > 0, normal[:, 27] / np.where(weight > 0, weight, 1.0), 0.0)
+            rejected = np.where(n > 0, pinfo[:, 6] / np.maximum(n, 1), 0.0)
+        return dict(status=status, normal=normal, n=n.copy(), cost=cost, pooled=pinfo[:, 1:3].copy(), bands=pinfo[:, 3].copy(),
+                    holes=pinfo[:, 4].copy(), pivot_failed=pinfo[:, 5].astype(bool), zero_weight=pinfo[:, 6].copy(),
+                    reweightings=pinfo[:, 7].copy(), gamma=robust[:, 0].copy(), gain=1.0 + robust[:, 0], bias=robust[:, 1].copy(), sigma=robust[:, 2].copy(),
+                    weight=weight.copy(), rejected=rejected)
+
+    def photometric_robust_velocity_host(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                         lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,
+                                         robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_robust_velocity``, the host-pointer form of ``photometric_robust_velocity``: numpy arrays in, ``(v
+        float64 [n, 6], info)`` out, one synchronous C call.  Frames of at most ``params.v_max`` x ``params.u_max`` pixels."""
+        return self._photometric_robust(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, illumination,
+                                        robust_iterations, sigma_min)
+
     def last_tables(self, n_pairs: int = 1) -> dict:
         """``nn_1``, ``nn_2`` (int32) and ``sim_1`` (float32) [n, T] of the last servo call; after ``compute_velocity_host`` they
         come from host memory (the handle's pinned block), no device call."""

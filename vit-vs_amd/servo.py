@@ -318,7 +318,8 @@ class Controller:
                 raise ValueError(f"photometric_handover needs the goal image at the camera's v_max x u_max "
                                  f"({self.params.v_max} x {self.params.u_max}), got {size[0]} x {size[1]}")
         self.photometric_active = False                   # photometric_handover: the photometric law has the robot
-        self.last_photometric = None                      # dict(status, cost = sum e^2 / n, n) of its last call
+        self.last_photometric = None                      # dict(status, cost = sum e^2 / n, n) of its last call; its robust form
+                                                          # (photometric_illumination / _robust_iterations): and gain, bias, sigma, rejected
         self._photo_goal_src = None                       # the PIL goal image _photo_goal was converted from
         self._photo_goal = None                           # (host copy, device tensor) of the goal frame at camera resolution, and
         self._photo_goal_depth = None                     # of the goal depth: uploaded once, compared by content like _goal_np
@@ -583,10 +584,19 @@ class Controller:
             return False
         cur, goal, z, scalar = inputs
         lam = p.lambda_ if p.photometric_lambda is None else p.photometric_lambda
-        v, info = self.engine.photometric_velocity(cur, goal, None if z is None else z[None], p.intrinsics(), p.photometric_level,
-                                                   p.photometric_interaction, p.photometric_mu, lam, scalar)
+        robust = p.photometric_illumination or p.photometric_robust_iterations > 0
+        if robust:
+            v, info = self.engine.photometric_robust_velocity(cur, goal, None if z is None else z[None], p.intrinsics(),
+                                                              p.photometric_level, p.photometric_interaction, p.photometric_mu, lam, scalar,
+                                                              p.photometric_illumination, p.photometric_robust_iterations,
+                                                              p.photometric_sigma_min)
+        else:
+            v, info = self.engine.photometric_velocity(cur, goal, None if z is None else z[None], p.intrinsics(), p.photometric_level,
+                                                       p.photometric_interaction, p.photometric_mu, lam, scalar)
         st = int(info["status"][0])
         self.last_photometric = dict(status=st, cost=float(info["cost"][0]), n=int(info["n"][0]))
+        if robust:
+            self.last_photometric.update({k: float(info[k][0]) for k in ("gain", "bias", "sigma", "rejected")})
         if st != _lib.STATUS_OK:
             self.photometric_active = False
             return False
