@@ -636,6 +636,50 @@ VITVS_API int vitvs_photometric_robust_velocity(vitvs_handle* h, int32_t n_pairs
                                                 const double* K, int32_t level, int32_t interaction, double mu, double lambda,
                                                 int32_t illumination, int32_t robust_iterations, double sigma_min, double* v_p,
                                                 int32_t* p_status, double* p_robust, double* normal45, int32_t* p_info);
+/* --- the photometric rig law: one dense final approach for a rigid multi-camera rig (photometric.hip) ------
+ * The robust photometric law above for n_cams cameras of one rigid rig, DESIGN.md 5m: ONE twist of the rig from every camera's
+ * rows, every camera with a lighting model of its own, and ONE median over all cameras' residuals.  Per camera the arguments of
+ * vitvs_photometric_robust_velocity_dev, a camera in the place of a pair: I_cur, I_des uint8 [n_cams][height][width][3], Z_mm uint16
+ * [n_cams][height][width] or NULL with depth_scale, K double [n_cams][4].
+ *   cVr        double [n_cams][6][6]: W_i, the twist transform from the rig frame to camera i (v_cam_i = W_i v_rig)
+ *   live       int32 [n_cams] or NULL (all live): a camera at 0 leaves no trace in any sum, count or median
+ * One solve: per live camera the 45 weighted sums over its own rows; with illumination its own (gamma_i, beta_i) eliminated by the
+ * 2 x 2 LDL^T (H'_i, g'_i; without: A_i, b_i); T_i = W_i^T (H'_i W_i) and W_i^T g'_i, every inner sum in ascending index;
+ * H_r = sum T_i, g_r = sum W_i^T g'_i, c_r = sum c_i over the cameras in ascending order; x = -(H_r + mu diag H_r)^-1 g_r by LDL^T;
+ * x_i = W_i x, (gamma_i, beta_i) = C_i^-1 (d_i + B_i^T x_i).  One re-weighting: rho = |e + L_i x_i - gamma_i D - beta_i| of every row
+ * of every live camera into one histogram (the robust law's bins), the median at ceil(n_total / 2), one sigma, Tukey weights.
+ *   v_rig      double [6]: lambda x of the last solve, in the rig frame
+ *   rig_status int32 [1]: VITVS_OK; VITVS_TOO_FEW (v_rig = 0, p_robust = 0) when the live cameras have fewer than 6 rows between
+ *              them, fewer than 6 rows keep a weight, a live camera's 2 x 2 pivot fails or the 6 x 6 factorisation fails;
+ *              VITVS_NO_DEPTH as the plain law.  A live camera without a row (all holes) adds nothing and fails nothing.
+ *   p_robust   double [n_cams][4]: gamma_i, beta_i, the last sigma (the stack's; 0 with N = 0), the camera's final sum of weights;
+ *              0 for a camera that is not live or has no row
+ *   normal45   double [n_cams][45] or NULL: each camera's own sums of the last pass, as the robust law's (0 for a dead camera)
+ *   rig_normal double [28] or NULL: H_r (21, upper triangle, row-major), g_r (6), c_r of the last pass: what a form across ranks
+ *              would add up
+ *   rig_info   int32 [8] or NULL: live cameras, n_total, rows of final weight 0, re-weightings run, holes, a pivot failed, the
+ *              pooled h and w
+ * With n_cams = 1 and cVr = I, v_rig, p_robust, rig_status and normal45 are vitvs_photometric_robust_velocity_dev's bit for bit.
+ * Each camera's 45 sums do not depend on its place among the cameras; v_rig depends on the cameras' order only through the order
+ * of the sum over them.  The same bits from call to call (integer atomics only).  4 N + 2 launches on `stream`, no host round
+ * trip, capturable.  The call runs in the robust photometric law's blocks (allocated by the handle's first call of either, which
+ * synchronises the device: make it outside any stream capture), so one photometric call of either kind is in flight per handle;
+ * the host form's staging is its own.  Returns 0, -1 (null, cVr too), -2 (what the robust law refuses, n_cams in the place of
+ * n_pairs; n_cams above 16).  No counterpart in the reference. */
+VITVS_API int vitvs_photometric_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const uint8_t* I_cur, const uint8_t* I_des,
+                                                 int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                 const double* K, const double* cVr, const int32_t* live, int32_t level,
+                                                 int32_t interaction, double mu, double lambda, int32_t illumination,
+                                                 int32_t robust_iterations, double sigma_min, double* v_rig, int32_t* rig_status,
+                                                 double* p_robust, double* normal45, double* rig_normal, int32_t* rig_info,
+                                                 void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_photometric_rig_velocity(vitvs_handle* h, int32_t n_cams, const uint8_t* I_cur, const uint8_t* I_des,
+                                             int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                             const double* K, const double* cVr, const int32_t* live, int32_t level,
+                                             int32_t interaction, double mu, double lambda, int32_t illumination,
+                                             int32_t robust_iterations, double sigma_min, double* v_rig, int32_t* rig_status,
+                                             double* p_robust, double* normal45, double* rig_normal, int32_t* rig_info);
 /* The launch plan of the photometric law as host arithmetic, for one pair (no handle, no device).  It is declared here, beside the
  * calls it plans, and not among the operator hooks of include/vitvs_ops.h: out int32 [8] = the
  * pooled h = height >> level and w = width >> level, the pooled rows per band max(1, min((2048 >> level) / w, h / 256)), the bands

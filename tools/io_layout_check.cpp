@@ -124,6 +124,19 @@ int main() {
         EXPECT(io_place(io_list(pr0), nullptr) == (P * (4 + 6 + 4) + ((P * 45 + 1) & ~(size_t)1)) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
                                                       ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
                "photometric robust: %zu %zu", P, px_max);
+        // the rig form: the cameras' twist transforms and live flags, and the rig's twist, 28 sums, status (four reserved) and info
+        PhotometricRigIo pg = photometric_rig_io(P, px_max * 3, px_max, n, px * 3, px, &d, &d, &i, &b16, &b8, &b8, &d, &i, &d, &d, &d, &i);
+        check("photometric rig", io_list(pg), P, px_max, n);
+        PhotometricRigIo pg0 = photometric_rig_io(P, px_max * 3, px_max);
+        EXPECT(io_place(io_list(pg0), nullptr) == io_place(io_list(pg), nullptr), "photometric rig: allocation and call disagree");
+        EXPECT(pg.Z.count == n * px && pg.I_cur.count == n * px * 3 && pg.I_des.count == n * px * 3 && pg.normal45.count == n * 45 &&
+                   pg.p_robust.count == n * 4 && pg.cVr.count == n * 36 && pg.live.count == n && pg.v_rig.count == 6 &&
+                   pg.rig_normal.count == 28 && pg.rig_status.count == 1 && pg.rig_info.count == 8,
+               "photometric rig: counts");
+        EXPECT(io_place(io_list(pg0), nullptr) ==
+                   (P * (4 + 36 + 4) + 6 + 28 + ((P * 45 + 1) & ~(size_t)1)) * 8 + (((P + 3) & ~(size_t)3) + 4 + 8) * 4 +
+                       ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
+               "photometric rig: %zu %zu", P, px_max);
     }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");

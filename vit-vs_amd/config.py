@@ -217,7 +217,9 @@ class ServoParams:
     photometric_handover: float = 0.0  # > 0: a servo.Controller hands the robot to the photometric law (Engine.photometric_velocity,
                                        # DESIGN.md 5k) once an update's raw twist says less than this is left, max |v_c| / lambda_ in
                                        # metres / radians; from then on no forward runs.  0 = off, nothing changes.  The photometric
-                                       # law's domain is small: hand over inside the ViT law's dead zone, not before
+                                       # law's domain is small: hand over inside the ViT law's dead zone, not before.  A
+                                       # servo.MultiController(rig=...) hands over to the photometric RIG law on
+                                       # max |rig twist| / lambda_
     photometric_level: int = 2         # its pyramid level, 0 .. 3: luminance pooled over 2^level x 2^level pixels
     photometric_mu: float = 0.01       # its Levenberg-Marquardt damping (>= 0; 0 = Gauss-Newton)
     photometric_lambda: Optional[float] = None  # its gain; None: lambda_

@@ -145,6 +145,8 @@ struct vitvs_handle {
     // its robust form (vitvs_photometric_robust_velocity[_dev]) shares nothing with it: photo_robust_ws = the 48-double band partials,
     // one histogram and one state per pair (photometric_robust_ws_bytes), photo_robust_io = PhotometricRobustIo
     unsigned char *photo_robust_ws = nullptr, *photo_robust_io = nullptr;
+    // the rig form (vitvs_photometric_rig_velocity[_dev]) runs in photo_robust_ws; photo_rig_io = PhotometricRigIo
+    unsigned char* photo_rig_io = nullptr;
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -2202,6 +2204,75 @@ int vitvs_photometric_robust_velocity(vitvs_handle* h, int32_t n_pairs, const ui
                                                      io.K.f64(), level, interaction, mu, lambda, illumination, robust_iterations,
                                                      sigma_min, io.v_p.f64(), io.p_status.i32(), io.p_robust.f64(),
                                                      normal45 ? io.normal45.f64() : nullptr, p_info ? io.p_info.i32() : nullptr, st);
+    });
+}
+
+// --- the photometric rig law ----------------------------------------------------------------------
+// The robust photometric law's refusals with the cameras in the place of the pairs, and at most kPhotoRigMaxCams of them.  It
+// runs in the robust law's workspace block (allocated here if no robust call came first); only PhotometricRigIo is its own.
+static int photometric_rig_prepare(vitvs_handle* h, int n_cams, int height, int width, int level, int interaction, double depth_scale,
+                                   double mu, double lambda, int illumination, int robust_iterations, double sigma_min, bool host_form) {
+    const vitvs_config& c = h->cfg;
+    if (n_cams < 1 || n_cams > c.max_pairs || n_cams > kPhotoRigMaxCams)
+        return set_err(h, -2, "n_cams is 1 .. min(max_pairs, " + std::to_string(kPhotoRigMaxCams) + ")");
+    if (int rc = photometric_robust_prepare(h, n_cams, height, width, level, interaction, depth_scale, mu, lambda, illumination,
+                                            robust_iterations, sigma_min, host_form))
+        return rc;
+    if (h->photo_rig_io) return 0;
+    const size_t px_max = (size_t)c.u_max * c.v_max;
+    PhotometricRigIo io = photometric_rig_io(c.max_pairs, px_max * 3, px_max);
+    if (int rc = dev_alloc(h, &h->photo_rig_io, io_place(io_list(io), nullptr)))
+        return set_err(h, rc, "photometric rig workspace allocation failed");
+    VITVS_HIP_CHECK(hipDeviceSynchronize());
+    return 0;
+}
+
+int vitvs_photometric_rig_velocity_dev(vitvs_handle* h, int32_t n_cams, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                       int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, const double* cVr,
+                                       const int32_t* live, int32_t level, int32_t interaction, double mu, double lambda,
+                                       int32_t illumination, int32_t robust_iterations, double sigma_min, double* v_rig,
+                                       int32_t* rig_status, double* p_robust, double* normal45, double* rig_normal, int32_t* rig_info,
+                                       void* stream) {
+    if (!h || !I_cur || !I_des || !K || !cVr || !v_rig || !rig_status || !p_robust) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_rig_prepare(h, n_cams, height, width, level, interaction, depth_scale, mu, lambda, illumination,
+                                         robust_iterations, sigma_min, false))
+        return rc;
+    PhotometricRigArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    PhotometricRobustArgs& ra = ga.r;
+    PhotometricArgs& a = ra.p;
+    a.n_pairs = n_cams; a.height = height; a.width = width; a.level = level; a.interaction = interaction;
+    a.I_cur = I_cur; a.I_des = I_des; a.Z_mm = Z_mm; a.depth_scale = depth_scale; a.K = K; a.mu = mu; a.lambda = lambda;
+    a.v_p = v_rig; a.p_status = rig_status; a.p_info = rig_info;
+    ra.illumination = illumination; ra.iterations = robust_iterations; ra.sigma_min = sigma_min;
+    ra.p_robust = p_robust; ra.normal45 = normal45;
+    ga.cVr = cVr; ga.live = live; ga.rig_normal = rig_normal;
+    const int rc = launch_photometric_rig(ga, h->photo_robust_ws, h->cfg.max_pairs, dev_stream(h, stream));
+    return rc ? set_err(h, rc, "photometric rig law launch failed") : 0;
+}
+
+int vitvs_photometric_rig_velocity(vitvs_handle* h, int32_t n_cams, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                   int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, const double* cVr,
+                                   const int32_t* live, int32_t level, int32_t interaction, double mu, double lambda,
+                                   int32_t illumination, int32_t robust_iterations, double sigma_min, double* v_rig, int32_t* rig_status,
+                                   double* p_robust, double* normal45, double* rig_normal, int32_t* rig_info) {
+    if (!h || !I_cur || !I_des || !K || !cVr || !v_rig || !rig_status || !p_robust) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_rig_prepare(h, n_cams, height, width, level, interaction, depth_scale, mu, lambda, illumination,
+                                         robust_iterations, sigma_min, true))
+        return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max, px = (size_t)height * width;
+    PhotometricRigIo io = photometric_rig_io(c.max_pairs, px_max * 3, px_max, n_cams, px * 3, px, K, cVr, live, Z_mm, I_cur, I_des, v_rig,
+                                             rig_status, p_robust, normal45, rig_normal, rig_info);
+    return host_call(h, io_list(io), h->photo_rig_io, [&](hipStream_t st) {
+        return vitvs_photometric_rig_velocity_dev(h, n_cams, io.I_cur.dev, io.I_des.dev, height, width,
+                                                  Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale, io.K.f64(),
+                                                  io.cVr.f64(), live ? io.live.i32() : nullptr, level, interaction, mu, lambda,
+                                                  illumination, robust_iterations, sigma_min, io.v_rig.f64(), io.rig_status.i32(),
+                                                  io.p_robust.f64(), normal45 ? io.normal45.f64() : nullptr,
+                                                  rig_normal ? io.rig_normal.f64() : nullptr, rig_info ? io.rig_info.i32() : nullptr, st);
     });
 }
 

@@ -151,4 +151,23 @@ inline PhotometricRobustIo photometric_robust_io(size_t P, size_t frame_max, siz
                                io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur), io_in(1, f_cap, n * frame, I_des)};
 }
 
+// the photometric rig law (vitvs_photometric_rig_velocity): PhotometricRobustIo's per-camera fields, the cameras' twist transforms
+// and live flags (null: nothing copied, all live), and the rig's one twist, status, 28 sums and info.  rig_status reserves four
+// int32 so that the fields behind it keep their 16-byte boundaries.
+struct PhotometricRigIo {
+    IoField K, cVr, v_rig, rig_normal, normal45, p_robust, live, rig_status, rig_info, Z, I_cur, I_des;
+};
+inline PhotometricRigIo photometric_rig_io(size_t P, size_t frame_max, size_t depth_max, size_t n = 0, size_t frame = 0, size_t depth = 0,
+                                           const double* K = nullptr, const double* cVr = nullptr, const int32_t* live = nullptr,
+                                           const uint16_t* Z = nullptr, const uint8_t* I_cur = nullptr, const uint8_t* I_des = nullptr,
+                                           double* v_rig = nullptr, int32_t* rig_status = nullptr, double* p_robust = nullptr,
+                                           double* normal45 = nullptr, double* rig_normal = nullptr, int32_t* rig_info = nullptr) {
+    const size_t st_cap = (P + 3) & ~(size_t)3, z_cap = (P * depth_max + 7) & ~(size_t)7, f_cap = (P * frame_max + 15) & ~(size_t)15;
+    const size_t n45_cap = (P * 45 + 1) & ~(size_t)1;
+    return PhotometricRigIo{io_in(8, P * 4, n * 4, K),          io_in(8, P * 36, n * 36, cVr),       io_out(8, 6, 6, v_rig),
+                            io_out(8, 28, 28, rig_normal),      io_out(8, n45_cap, n * 45, normal45), io_out(8, P * 4, n * 4, p_robust),
+                            io_in(4, st_cap, n, live),          io_out(4, 4, 1, rig_status),         io_out(4, 8, 8, rig_info),
+                            io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur),   io_in(1, f_cap, n * frame, I_des)};
+}
+
 }  // namespace vitvs

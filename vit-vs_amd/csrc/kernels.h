@@ -682,6 +682,21 @@ struct PhotometricRobustArgs {
 size_t photometric_robust_ws_bytes(int max_pairs);
 int launch_photometric_robust(const PhotometricRobustArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
 
+// The photometric rig law: the robust photometric law's rows of r.p.n_pairs = n_cams cameras of one rigid rig
+// stacked into one 6 x 6 system in the rig frame, every camera with a lighting model of its own, and one median over all
+// cameras' residuals.  4 iterations + 2 launches, no host round trip; the block is launch_photometric_robust's (one photometric
+// call of either kind in flight per block).  The per-pair fields of r.p are per camera, except the outputs of the rig:
+// r.p.v_p [6] the rig twist, r.p.p_status [1], r.p.p_info [8] = live cameras, n_total, rows of final weight 0, re-weightings run,
+// holes, a pivot failed, pooled h, pooled w.  r.p_robust [n_cams][4] and r.normal45 [n_cams][45] stay per camera.
+constexpr int kPhotoRigMaxCams = 16;
+struct PhotometricRigArgs {
+    PhotometricRobustArgs r;
+    const double* cVr;        // [n_cams][6][6] rig twist -> camera twist
+    const int32_t* live;      // [n_cams] or null (all live): a camera at 0 leaves no trace in any sum
+    double* rig_normal;       // [28] or null: H_r (21, upper triangle, row-major), g_r (6), c_r of the last pass
+};
+int launch_photometric_rig(const PhotometricRigArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

@@ -9,7 +9,8 @@
 //                              ascending band order, damps and runs LDL^T (solve.h)
 // No float atomics: pixel -> thread -> wave -> band is a function of (H, W, level) alone (plan_photometric), so the sums are the
 // same bits from call to call and for a pair alone or anywhere in a batch.  (One launch with a last-arriver ticket in place of the
-// second: priced and not built)  The law's robust form has kernels of its own at the end of the file.
+// second: priced and not built)  The law's robust form has kernels of its own further down, and its
+// rig form two more at the end of the file.
 #include <algorithm>
 
 #include "common.h"
@@ -734,6 +735,295 @@ int launch_photometric_robust(const PhotometricRobustArgs& ra_in, unsigned char*
         }
         if (hipGetLastError() != hipSuccess) return -1;
         launch(photometric_robust_solve_kernel, dim3(a.n_pairs), dim3(256), 0, stream, ra, p.h, p.w, p.bands, 0, pass);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
+}
+
+// ---- the photometric rig law --------------------------------------------------------------------------------------
+// The robust law's rows of n_cams cameras of one rigid rig in ONE system: camera i's 45 sums, its own (gamma_i, beta_i) eliminated,
+// carried into the rig frame by its twist transform W_i = cVr[i] (T_i = W_i^T H'_i W_i, W_i^T g'_i) and added in camera order; one
+// 6 x 6 solve, and one median over all cameras' residuals.  The rows and residual launches are the robust law's own, a camera being
+// a pair: they read (x_i, gamma_i, beta_i, rows, failed) from the camera's state block and the median at (rows + 1) / 2 of the
+// camera's histogram, so the rig solve writes n_total into every camera's rows field and the merge launch makes every live
+// camera's histogram the stack's.  4 N + 2 launches (kernels.h PhotometricRigArgs).
+//   photometric_rig_solve_kernel   one workgroup per call: wave v takes cameras v, v + 4, ..: the bands in ascending order, the
+//                                  2 x 2 elimination, T_i and W_i^T g'_i into LDS; wave 0 adds the cameras in ascending order,
+//                                  LDL^T, every camera's x_i, gamma_i, beta_i; writes the states and clears the histograms
+//   photometric_rig_merge_kernel   every live camera's histogram <- the integer sum over the live cameras
+constexpr int kPhotoRigChunk = 16;   // bands per chunk and wave: 16 x 48 doubles = 12 per lane
+constexpr int kPhotoRigDepth = 2;    // chunks a wave holds in flight
+constexpr int kPhotoRigCam = 120;    // LDS doubles per camera: S (48), T / W^T g' / c (28), W (36), l, 1 / d0, 1 / d1, (int32 adds, good)
+
+// same wave: the LDS writes above are visible below, and the reads above are done before the writes below
+__device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// lane q < 21 of the upper triangle, row-major -> (i, j)
+__device__ __forceinline__ void triu_index(int q, int& i, int& j) {
+    i = 0;
+    while (q >= 6 - i) { q -= 6 - i; ++i; }
+    j = i + q;
+}
+
+__global__ __launch_bounds__(256) void photometric_rig_solve_kernel(PhotometricRigArgs ga, int h, int w, int bands, int no_depth,
+                                                                    int pass) {
+    __shared__ double Gs[40 + 8 * 27];
+    __shared__ double chunks[4][kPhotoRigChunk * kPhotoRPart];
+    __shared__ double cams[kPhotoRigMaxCams * kPhotoRigCam];
+    __shared__ double scratch[4][80];                   // per wave: H' (36, full), g' (6), M = H' W (36)
+    const PhotometricRobustArgs& ra = ga.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63, n_cams = a.n_pairs;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                   // uniform: the loops over a wave's cameras and bands branch as one
+    {
+        u32x4* hz = reinterpret_cast<u32x4*>(ra.hist);  // the cameras' histograms are one block
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        for (int i = tid; i < n_cams * (kPhotoBins / 4); i += 256) hz[i] = zero;
+    }
+    int32_t* rig_failed = reinterpret_cast<int32_t*>(ra.state + 11);             // camera 0's block: the call's failed flag
+    if (pass > 0 && rig_failed[0]) return;
+    for (int i = tid; i < 40 + 8 * 27; i += 256) Gs[i] = 0.0;
+    double* chunk = chunks[wave];
+    double* Hs = scratch[wave];
+    double* gs = Hs + 36;
+    double* Ms = Hs + 42;
+    for (int cam = wave; cam < n_cams; cam += 4) {
+        double* Sc = cams + cam * kPhotoRigCam;
+        double* TW = Sc + 48;
+        double* Wc = Sc + 76;
+        const bool alive = !ga.live || ga.live[cam] != 0;
+        if (lane < 36) Wc[lane] = ga.cVr[(size_t)cam * 36 + lane];
+        const double* part = a.ws + (size_t)cam * bands * kPhotoRPart;
+        double sum = 0.0;                               // lanes 0 .. 44: one of the camera's 45 sums each
+        int count = 0;                                  // lane 45: the rows; 46: the holes; 47: the rows of weight 0
+        const int total = (no_depth || !alive) ? 0 : bands * kPhotoRPart;
+        // kPhotoRigDepth chunks in flight in registers: one wave fetches for itself, and a chunk's round trip is longer than its adds
+        constexpr int kStep = kPhotoRigChunk * kPhotoRPart;
+        double held[kPhotoRigDepth][12];
+#pragma unroll
+        for (int d = 0; d < kPhotoRigDepth; ++d)
+#pragma unroll
+            for (int u = 0; u < 12; ++u) { const int i = d * kStep + lane + 64 * u; held[d][u] = i < total ? part[i] : 0.0; }
+        for (int c0 = 0; c0 < total; c0 += kPhotoRigDepth * kStep) {
+#pragma unroll
+            for (int d = 0; d < kPhotoRigDepth; ++d) {
+                const int at = c0 + d * kStep;
+                if (at >= total) break;
+                wave_lds_fence();
+#pragma unroll
+                for (int u = 0; u < 12; ++u) chunk[lane + 64 * u] = held[d][u];
+                wave_lds_fence();
+                const int next = at + kPhotoRigDepth * kStep;
+#pragma unroll
+                for (int u = 0; u < 12; ++u) { const int i = next + lane + 64 * u; held[d][u] = i < total ? part[i] : 0.0; }
+                const int nb = min(kPhotoRigChunk, bands - at / kPhotoRPart);
+                if (lane < 45) {
+#pragma unroll 8
+                    for (int b = 0; b < nb; ++b) sum += chunk[b * kPhotoRPart + lane];     // ascending band order
+                } else if (lane < 48) {
+                    const int32_t* c = reinterpret_cast<const int32_t*>(chunk + 45) + (lane - 45);
+#pragma unroll 8
+                    for (int b = 0; b < nb; ++b) count += c[b * kPhotoRPart * 2];
+                }
+            }
+        }
+        if (ra.normal45 && lane < 45) ra.normal45[(size_t)cam * 45 + lane] = sum;
+        if (lane < 45) Sc[lane] = sum;
+        else if (lane < 48) reinterpret_cast<int32_t*>(Sc + 45)[lane - 45] = count;
+        wave_lds_fence();
+        const int n = reinterpret_cast<const int32_t*>(Sc + 45)[0];
+        const bool adds = alive && n > 0;               // a live camera without a row adds nothing and fails nothing
+        // C_i = l d l^T as photometric_robust_solve_kernel's
+        bool cgood = true;
+        double l = 0.0, i0 = 0.0, i1 = 0.0;
+        if (ra.illumination) {
+            const double DD = Sc[40], Dm = Sc[41], Sw = Sc[42];
+            const double d0 = DD;
+            cgood = (d0 > kPivotThreshold * DD) && (DD > 0.0);
+            i0 = 1.0 / d0;
+            l = Dm * i0;
+            const double d1 = Sw - l * l * d0;
+            cgood = cgood && (d1 > kPivotThreshold * Sw) && (Sw > 0.0);
+            i1 = 1.0 / d1;
+        }
+        if (lane < 27) {
+            double val = sum;
+            int i, j = 0;
+            if (lane < 21) triu_index(lane, i, j);
+            else i = lane - 21;
+            if (ra.illumination) {
+                const double p = Sc[28 + 2 * i], q1 = Sc[29 + 2 * i];
+                const double u1 = (q1 - l * p) * i1, u0 = p * i0 - l * u1;
+                const double o0 = lane < 21 ? Sc[28 + 2 * j] : Sc[43], o1 = lane < 21 ? Sc[29 + 2 * j] : Sc[44];
+                val = sum - (u0 * o0 + u1 * o1);
+            }
+            if (lane < 21) { Hs[i * 6 + j] = val; Hs[j * 6 + i] = val; }
+            else gs[i] = val;
+        }
+        wave_lds_fence();
+        if (lane < 36) {                                // M = H' W
+            const int r = lane / 6, k = lane - r * 6;
+            double t = Hs[r * 6] * Wc[k];
+#pragma unroll
+            for (int b = 1; b < 6; ++b) t += Hs[r * 6 + b] * Wc[b * 6 + k];
+            Ms[lane] = t;
+        }
+        wave_lds_fence();
+        if (lane < 28) {                                // T_i = W^T M (upper triangle), W^T g', c
+            double t;
+            if (lane < 21) {
+                int j, k;
+                triu_index(lane, j, k);
+                t = Wc[j] * Ms[k];
+#pragma unroll
+                for (int r = 1; r < 6; ++r) t += Wc[r * 6 + j] * Ms[r * 6 + k];
+            } else if (lane < 27) {
+                const int k = lane - 21;
+                t = Wc[k] * gs[0];
+#pragma unroll
+                for (int r = 1; r < 6; ++r) t += Wc[r * 6 + k] * gs[r];
+            } else {
+                t = Sc[27];
+            }
+            TW[lane] = t;
+        }
+        if (lane == 0) {
+            Sc[112] = l; Sc[113] = i0; Sc[114] = i1;
+            int32_t* f = reinterpret_cast<int32_t*>(Sc + 115);
+            f[0] = adds ? 1 : 0; f[1] = cgood ? 1 : 0;
+        }
+        wave_lds_fence();
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // the cameras in ascending order: which wave held which does not show
+    double sum = 0.0;
+    int n = 0, holes = 0, zeros = 0, n_live = 0;
+    bool cgood = true;
+    for (int cam = 0; cam < n_cams; ++cam) {
+        const double* Sc = cams + cam * kPhotoRigCam;
+        const int32_t* f = reinterpret_cast<const int32_t*>(Sc + 115);
+        const int32_t* c = reinterpret_cast<const int32_t*>(Sc + 45);
+        if (!ga.live || ga.live[cam] != 0) { ++n_live; holes += c[1]; }
+        if (!f[0]) continue;
+        if (lane < 28) sum += Sc[48 + lane];
+        n += c[0];
+        zeros += c[2];
+        cgood = cgood && f[1] != 0;
+    }
+    if (ga.rig_normal && lane < 28) ga.rig_normal[lane] = sum;
+    if (lane < 27) {
+        const bool diag = lane == 0 || lane == 6 || lane == 11 || lane == 15 || lane == 18 || lane == 20;
+        Gs[40 + lane] = diag ? sum + a.mu * sum : sum;
+    }
+    wave_lds_fence();
+    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool solved = false;
+    const bool tried = !no_depth && n >= 6 && n - zeros >= 6;
+    if (tried && cgood) solved = solve_ldlt(Gs, lane, x);
+    if (lane < n_cams) {                                // lane = camera: its step, lighting and state
+        const int cam = lane;
+        const double* Sc = cams + cam * kPhotoRigCam;
+        const double* Wc = Sc + 76;
+        const bool alive = !ga.live || ga.live[cam] != 0;
+        const bool adds = reinterpret_cast<const int32_t*>(Sc + 115)[0] != 0;
+        double xi[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            double t = Wc[r * 6] * -x[0];
+#pragma unroll
+            for (int k = 1; k < 6; ++k) t += Wc[r * 6 + k] * -x[k];
+            xi[r] = solved ? t : 0.0;
+        }
+        double gamma = 0.0, beta = 0.0;
+        if (solved && adds && ra.illumination) {
+            const double l = Sc[112], i0 = Sc[113], i1 = Sc[114];
+            double t0 = Sc[43], t1 = Sc[44];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { t0 = t0 + Sc[28 + 2 * i] * xi[i]; t1 = t1 + Sc[29 + 2 * i] * xi[i]; }
+            beta = (t1 - l * t0) * i1;
+            gamma = t0 * i0 - l * beta;
+        }
+        double* state = ra.state + (size_t)cam * kPhotoState;
+        int32_t* si = reinterpret_cast<int32_t*>(state + 9);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) state[i] = xi[i];
+        state[6] = gamma;
+        state[7] = beta;
+        si[0] = n;                                      // the stack's rows: the rows launch takes the median at (n + 1) / 2
+        si[1] = (solved && alive) ? 0 : 1;              // a dead camera: the residual and weighted rows launches pass it by
+        double* pr = ra.p_robust + (size_t)cam * 4;
+        pr[0] = gamma;
+        pr[1] = beta;
+        pr[2] = (solved && adds && pass > 0) ? state[8] : 0.0;
+        pr[3] = (solved && adds) ? Sc[42] : 0.0;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.v_p[i] = solved ? -a.lambda * x[i] : 0.0;
+        rig_failed[0] = solved ? 0 : 1;
+        a.p_status[0] = no_depth ? ST_NO_DEPTH : solved ? ST_OK : ST_TOO_FEW;
+        if (a.p_info) {
+            int32_t* pi = a.p_info;
+            pi[0] = n_live; pi[1] = n; pi[2] = zeros; pi[3] = pass; pi[4] = holes; pi[5] = (tried && !solved) ? 1 : 0; pi[6] = h; pi[7] = w;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void photometric_rig_merge_kernel(PhotometricRigArgs ga) {
+    const PhotometricRobustArgs& ra = ga.r;
+    if (reinterpret_cast<const int32_t*>(ra.state + 11)[0]) return;
+    const int bin = blockIdx.x * 256 + threadIdx.x, n_cams = ra.p.n_pairs;
+    unsigned total = 0u;
+    for (int cam = 0; cam < n_cams; ++cam)
+        if (!ga.live || ga.live[cam] != 0) total += ra.hist[(size_t)cam * kPhotoBins + bin];
+    for (int cam = 0; cam < n_cams; ++cam)
+        if (!ga.live || ga.live[cam] != 0) ra.hist[(size_t)cam * kPhotoBins + bin] = total;
+}
+
+int launch_photometric_rig(const PhotometricRigArgs& ga_in, unsigned char* ws, int max_pairs, hipStream_t stream) {
+    PhotometricRigArgs ga = ga_in;
+    PhotometricRobustArgs& ra = ga.r;
+    PhotometricArgs& a = ra.p;
+    if (a.n_pairs < 1 || a.n_pairs > kPhotoRigMaxCams || a.n_pairs > max_pairs || !a.I_cur || !a.I_des || !a.K || !ws || !a.v_p ||
+        !a.p_status || !ra.p_robust || !ga.cVr)
+        return -2;
+    if (a.interaction < 0 || a.interaction > 1 || !(a.mu >= 0.0) || !(a.mu < __builtin_huge_val())) return -2;
+    if (!(a.lambda == a.lambda) || !(a.depth_scale == a.depth_scale)) return -2;
+    if (ra.illumination < 0 || ra.illumination > 1 || ra.iterations < 0 || ra.iterations > 4) return -2;
+    if (!(ra.sigma_min > 0.0) || !(ra.sigma_min < __builtin_huge_val())) return -2;
+    PhotometricPlan p;
+    if (int rc = plan_photometric(a.height, a.width, a.level, a.n_pairs, &p)) return rc;
+    // the robust law's block, laid out as launch_photometric_robust lays it out
+    a.ws = reinterpret_cast<double*>(ws);
+    ra.hist = reinterpret_cast<uint32_t*>(ws + (size_t)max_pairs * 4096 * kPhotoRPart * sizeof(double));
+    ra.state = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(ra.hist) + (size_t)max_pairs * kPhotoBins * sizeof(uint32_t));
+    const size_t lds = p.lds - 4 * kPhotoPart * sizeof(double) + 4 * kPhotoRPart * sizeof(double);
+    const size_t lds_res = lds + kPhotoBins * sizeof(uint32_t);
+    const int no_depth = (!a.Z_mm && !(a.depth_scale > 0.0)) ? 1 : 0;
+    if (no_depth) {
+        launch(photometric_rig_solve_kernel, dim3(1), dim3(256), 0, stream, ga, p.h, p.w, p.bands, 1, 0);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    static std::atomic<unsigned long long> raised0{0}, raised1{0}, raised2{0};
+    if (lds > 64 * 1024 &&
+        (raise_lds_limit(reinterpret_cast<const void*>(photometric_robust_rows_kernel<false>), 160 * 1024, raised0) ||
+         raise_lds_limit(reinterpret_cast<const void*>(photometric_robust_rows_kernel<true>), 160 * 1024, raised1)))
+        return -3;
+    if (ra.iterations > 0 && lds_res > 64 * 1024 &&
+        raise_lds_limit(reinterpret_cast<const void*>(photometric_residual_kernel), 160 * 1024, raised2))
+        return -3;
+    const dim3 grid(p.bands, a.n_pairs);
+    for (int pass = 0; pass <= ra.iterations; ++pass) {
+        if (pass > 0) {
+            launch(photometric_residual_kernel, grid, dim3(256), lds_res, stream, ra, p.h, p.w, p.rows, p.bands);
+            launch(photometric_rig_merge_kernel, dim3(kPhotoBins / 256), dim3(256), 0, stream, ga);
+            launch(photometric_robust_rows_kernel<true>, grid, dim3(256), lds, stream, ra, p.h, p.w, p.rows, p.bands);
+        } else {
+            launch(photometric_robust_rows_kernel<false>, grid, dim3(256), lds, stream, ra, p.h, p.w, p.rows, p.bands);
+        }
+        if (hipGetLastError() != hipSuccess) return -1;
+        launch(photometric_rig_solve_kernel, dim3(1), dim3(256), 0, stream, ga, p.h, p.w, p.bands, 0, pass);
         if (hipGetLastError() != hipSuccess) return -1;
     }
     return 0;

@@ -670,6 +670,69 @@ class Engine:
         return self._photometric_robust(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, illumination,
                                         robust_iterations, sigma_min)
 
+    # ------------------------------------------------------------------ the photometric rig law
+    def photometric_rig_velocity(self, I_cur, I_des, Z, K, cVr, live=None, level: int = 2, interaction="desired", mu: float = 0.01,
+                                 lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,
+                                 robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_rig_velocity_dev``: the robust photometric law of the ``n`` cameras of one rigid rig as ONE system
+        (DESIGN.md 5m).  The arguments of ``photometric_robust_velocity`` with a camera in the place of a pair, ``cVr`` float64
+        ``[n, 6, 6]`` (``servo.twist_matrix`` per camera) and ``live`` (one flag per camera, None: all; a camera at 0 leaves no
+        trace).  Every camera has its own gain and bias; the re-weighting takes one median over all cameras' residuals.  4
+        ``robust_iterations`` + 2 launches on the current stream.  Returns ``(v_rig float64 [6] device tensor, info)``: ``status``
+        (int), ``n`` (rows of the stack), ``cost`` (sum w e^2 / sum w of the stack), ``live``, ``zero_weight``, ``reweightings``,
+        ``holes``, ``pivot_failed``, ``pooled``, ``rig_normal`` float64 [28], and per camera ``normal`` float64 [n, 45], ``gamma``,
+        ``gain``, ``bias``, ``sigma`` and ``weight`` (the camera's final sum of weights; against its rows it tells the share set
+        aside).  Reading ``info`` synchronises; the engine's first call allocates: make it outside a stream capture."""
+        return self._photometric_rig(False, I_cur, I_des, Z, K, cVr, live, level, interaction, mu, lambda_, depth_scale, illumination,
+                                     robust_iterations, sigma_min)
+
+    def photometric_rig_velocity_host(self, I_cur, I_des, Z, K, cVr, live=None, level: int = 2, interaction="desired",
+                                      mu: float = 0.01, lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,
+                                      robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_rig_velocity``, the host-pointer form of ``photometric_rig_velocity``: numpy arrays in, ``(v_rig
+        float64 [6], info)`` out, one synchronous C call.  Frames of at most ``params.v_max`` x ``params.u_max`` pixels."""
+        return self._photometric_rig(True, I_cur, I_des, Z, K, cVr, live, level, interaction, mu, lambda_, depth_scale, illumination,
+                                     robust_iterations, sigma_min)
+
+    def _photometric_rig(self, host, I_cur, I_des, Z, K, cVr, live, level, interaction, mu, lambda_, depth_scale, illumination,
+                         robust_iterations, sigma_min):
+        stage = self._stage(host)
+        cur = stage.frames(I_cur, None, None)
+        n, hh, ww = (int(x) for x in cur.shape[:3])
+        des = stage.frames(I_des, n, (hh, ww))
+        z = stage.depth(Z, n, (hh, ww))
+        kk = stage.intrinsics(K, n, "camera")
+        W = stage.array(cVr, "float64")
+        if tuple(W.shape) != (n, 6, 6):
+            raise VitvsError(f"cVr is one 6 x 6 twist transform per camera, [{n},6,6], got {tuple(W.shape)}")
+        W = stage.put(W)
+        alive = None
+        if live is not None:
+            alive = stage.array(np.asarray(live.cpu() if torch.is_tensor(live) else live).astype(bool).astype(np.int32), "int32")
+            if tuple(alive.shape) != (n,):
+                raise VitvsError(f"live is one flag per camera, [{n}], got {tuple(alive.shape)}")
+            alive = stage.put(alive)
+        illum, iters, smin = self._photometric_robust_scalars(illumination, robust_iterations, sigma_min)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        v, st, robust, normal, rig_normal, rinfo, p = (stage.f64(6), stage.i32(1), stage.f64(n, 4), stage.f64(n, 45), stage.f64(28),
+                                                       stage.i32(8), stage.ptr)
+        entry = "vitvs_photometric_rig_velocity" + ("" if host else "_dev")
+        rc = getattr(self.lib, entry)(self.handle, n, p(cur), p(des), hh, ww, p(z), ds, p(kk), p(W), p(alive), level, inter, mu, lam, illum,
+                                      iters, smin, p(v), p(st), p(robust), p(normal), p(rig_normal), p(rinfo), *stage.stream)
+        self._check(rc, entry)
+        return v, self._photometric_rig_info(stage.read(st), stage.read(normal), stage.read(rig_normal), stage.read(rinfo),
+                                             stage.read(robust))
+
+    @staticmethod
+    def _photometric_rig_info(status, normal, rig_normal, rinfo, robust) -> dict:
+        weight = robust[:, 3]
+        total = float(weight.sum())
+        # (a camera's own rows are not an output: the caller that knows its depth images counts them, servo.MultiController does)
+        return dict(status=int(status[0]), n=int(rinfo[1]), cost=float(rig_normal[27] / total) if total > 0 else 0.0, live=int(rinfo[0]),
+                    zero_weight=int(rinfo[2]), reweightings=int(rinfo[3]), holes=int(rinfo[4]), pivot_failed=bool(rinfo[5]),
+                    pooled=(int(rinfo[6]), int(rinfo[7])), rig_normal=rig_normal, normal=normal, gamma=robust[:, 0].copy(),
+                    gain=1.0 + robust[:, 0], bias=robust[:, 1].copy(), sigma=robust[:, 2].copy(), weight=weight.copy())
+
     def last_tables(self, n_pairs: int = 1) -> dict:
         """``nn_1``, ``nn_2`` (int32) and ``sim_1`` (float32) [n, T] of the last servo call; after ``compute_velocity_host`` they
         come from host memory (the handle's pinned block), no device call."""

@@ -700,9 +700,20 @@ class MultiController:
         if (params or self.engine.params).roll_search:
             raise ValueError("roll_search is servo.Controller's: a MultiController round is one batched call over the cameras, the roll "
                              "search one call of four turned copies per camera")
+        # photometric_handover > 0: once a round's rig twist says less than that is left, the rounds are the photometric rig law's
+        # alone (Engine.photometric_rig_velocity) on the live cameras' camera-resolution frames, until its status is
+        # not OK.  ``goal_depth`` (one image, or one per camera) is then also the depth of interaction "desired".
+        self.photometric_active = False
+        self.last_photometric = None                      # dict(status, cost, n, cameras, gain, bias, sigma, rejected) of its last call
+        self._photo_goal, self._photo_depth, self._photo_rows = None, None, None
+        self._photo_goal_depth = None if goal_depth is None else np.asarray(goal_depth)
         if (params or self.engine.params).photometric_handover > 0:
-            raise ValueError("photometric_handover is servo.Controller's: a MultiController round is one batched ViT call over the "
-                             "cameras, the hand-over one camera's own state")
+            if self.pipe is not None:
+                raise ValueError("photometric_handover needs the Engine backend: the photometric rig law reads all cameras in one handle, "
+                                 "a pipeline slot sees one camera")
+            if rig is None:
+                raise ValueError("photometric_handover in a MultiController hands over to the photometric RIG law and needs "
+                                 "rig=[(R_i, t_i), ...]: the hand-over watches the rig's one twist (one camera: servo.Controller)")
         if self.law == "homography":
             raise ValueError('law="homography" is servo.Controller\'s: the homography law has no rig form (one camera, one plane)')
         if self.law == "pose":
@@ -779,13 +790,97 @@ class MultiController:
         self.v_rig = ema_update(self._rig_ema, self.rig_velocity_raw, self.params.ema_alpha)
         return True
 
+    # -- the hand-over to the photometric rig law (params.photometric_handover > 0)
+    def _watch_handover(self, live):
+        """Behind a round whose rig law ran: with rig status OK and max |raw rig twist| / lambda_ below the threshold, the next
+        rounds are the photometric rig law's."""
+        p = self.params
+        if not p.photometric_handover > 0 or self.rig_status != _lib.STATUS_OK or p.lambda_ == 0 or self.rig_velocity_raw is None:
+            return
+        left = float(np.max(np.abs(np.asarray(self.rig_velocity_raw, np.float64)))) / abs(p.lambda_)
+        if left < p.photometric_handover and self._photometric_inputs(live) is not None:
+            self.photometric_active = True
+
+    @staticmethod
+    def _photometric_rows(z, n, shape, level):
+        """The rows of each of ``n`` cameras at pooled ``level``: the pooled pixels inside the one-pixel border whose block holds a
+        depth sample (``z`` uint16 [n, v, u]; None: every one)."""
+        h, w = shape[0] >> level, shape[1] >> level
+        if z is None:
+            return np.full(n, (h - 2) * (w - 2), np.int64)
+        s = 1 << level
+        filled = (np.asarray(z)[:, :h * s, :w * s].reshape(n, h, s, w, s) != 0).any(axis=(2, 4))
+        return filled[:, 1:-1, 1:-1].sum(axis=(1, 2)).astype(np.int64)
+
+    def _photometric_inputs(self, live):
+        """(current frames, goal frames on the device, depth images or None, scalar depth, rows per camera) of the live cameras at
+        camera resolution, or None when a frame or a goal image is not at the cameras' v_max x u_max."""
+        p, cam0 = self.params, self.cameras[0]
+        shape = (p.v_max, p.u_max)
+        cur = [np.asarray(self.cameras[i].latest_image, dtype=np.uint8) for i in live]
+        goals = [_as_array(self.cameras[i].goal_image) for i in live]
+        if any(a.shape != shape + (3,) for a in cur + goals):
+            return None
+        self._photo_goal = cam0._device_copy(self._photo_goal, np.stack(goals).astype(np.uint8, copy=False))
+        z, rows = None, None
+        if p.photometric_interaction == "desired":
+            gd = self._photo_goal_depth
+            if gd is not None and gd.dtype == np.uint16 and gd.shape[-2:] == shape and gd.ndim in (2, 3) \
+                    and (gd.ndim == 2 or gd.shape[0] == len(self.cameras)):
+                stack = np.broadcast_to(gd, (len(live),) + shape) if gd.ndim == 2 else gd[live]
+                before = self._photo_depth
+                self._photo_depth = cam0._device_copy(before, stack)
+                if self._photo_depth is not before or self._photo_rows is None:
+                    self._photo_rows = self._photometric_rows(self._photo_depth[0], len(live), shape, p.photometric_level)
+                z, rows = self._photo_depth[1], self._photo_rows
+        else:
+            depths = [self.cameras[i].latest_image_depth for i in live]
+            if all(d is not None and np.asarray(d).dtype == np.uint16 and np.asarray(d).size == shape[0] * shape[1] for d in depths):
+                z = np.stack([np.asarray(d).reshape(shape) for d in depths])
+                rows = self._photometric_rows(z, len(live), shape, p.photometric_level)
+        if z is None:
+            rows = self._photometric_rows(None, len(live), shape, p.photometric_level)
+        return np.stack(cur), self._photo_goal[1], z, (0.0 if z is not None else p.homography_depth), rows
+
+    def _photometric_round(self, live) -> bool:
+        """One round by the photometric rig law alone.  False, with the hand-over cleared, when its status is not OK: the caller
+        runs the batched ViT round for this call."""
+        p = self.params
+        inputs = self._photometric_inputs(live)
+        if inputs is None:
+            self.photometric_active = False
+            return False
+        cur, goal, z, scalar, rows = inputs
+        lam = p.lambda_ if p.photometric_lambda is None else p.photometric_lambda
+        v, info = self.engine.photometric_rig_velocity(cur, goal, z, p.intrinsics(), self.rig_W[live], None, p.photometric_level,
+                                                       p.photometric_interaction, p.photometric_mu, lam, scalar,
+                                                       p.photometric_illumination, p.photometric_robust_iterations,
+                                                       p.photometric_sigma_min)
+        st = int(info["status"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rejected = np.where(rows > 0, 1.0 - info["weight"] / np.maximum(rows, 1), 0.0)
+        self.last_photometric = dict(status=st, cost=float(info["cost"]), n=int(info["n"]), cameras=list(live),
+                                     gain=info["gain"].tolist(), bias=info["bias"].tolist(), sigma=float(info["sigma"].max()),
+                                     rejected=rejected.tolist())
+        if st != _lib.STATUS_OK:
+            self.photometric_active = False
+            return False
+        self.rig_status, self.rig_info = st, info
+        self.rig_velocity_raw = v.cpu().numpy()
+        self.v_rig = ema_update(self._rig_ema, self.rig_velocity_raw, p.ema_alpha)
+        return True
+
     def ibvs(self, selection=None, want_features: bool = False):
         """One control-law step for every camera that has an image: each camera's ``v_c`` is updated (EMA) or left untouched on
         failure, exactly as its own ``Controller.ibvs()`` would.  Returns the per-camera ``detect_features`` results
-        (``((s_uv_star, s_uv), sim)`` or ``(None, None)``; ``None`` for cameras without an image) when ``want_features``."""
+        (``((s_uv_star, s_uv), sim)`` or ``(None, None)``; ``None`` for cameras without an image) when ``want_features``.
+        With ``params.photometric_handover`` > 0 and the hand-over made (``photometric_active``), the round is the photometric rig
+        law's alone: no forward runs, the cameras' own state stays, and only ``v_rig`` moves."""
         live = [i for i, c in enumerate(self.cameras) if c.latest_image is not None]
         results = [None] * len(self.cameras)
         if not live:
+            return results if want_features else None
+        if self.photometric_active and self._photometric_round(live):
             return results if want_features else None
         p, eng = self.params, self.engine
         cur, des = self._frames_for(live)
@@ -813,6 +908,8 @@ class MultiController:
                 N = p.rig_robust_iterations               # > 0: Tukey IRLS over the stack, one median over all live cameras' residuals
                 v_r, self.rig_status, self.rig_info = eng.rig_velocity(self.rig_W[live], st, N, K=p.intrinsics() if N else None)
                 self._absorb_rig(v_r, live, weights=N > 0)
+            if self.rig_W is not None:
+                self._watch_handover(live)
             v, st = v.cpu().numpy(), st.cpu().numpy()
             det = eng.last_features(len(live)) if want_features else None
             failure = None
