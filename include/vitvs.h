@@ -680,6 +680,43 @@ VITVS_API int vitvs_photometric_rig_velocity(vitvs_handle* h, int32_t n_cams, co
                                              int32_t interaction, double mu, double lambda, int32_t illumination,
                                              int32_t robust_iterations, double sigma_min, double* v_rig, int32_t* rig_status,
                                              double* p_robust, double* normal45, double* rig_normal, int32_t* rig_info);
+/* --- the tile photometric law: a local lighting model, one gain / bias per tile (photometric.hip) ------
+ * The robust photometric law above with the lighting model LOCAL, DESIGN.md 5n: a cast shadow, a lamp on half the target or a
+ * regional exposure change breaks the one-gain model and is read as motion.  Every argument of vitvs_photometric_robust_velocity_dev
+ * means what it means there; the lighting model is always on, so there is no `illumination`.
+ *   tiles_y, tiles_x   gy, gx = 1 .. 8 each, at most the pooled image's sides; T = gy gx.  The row at pooled pixel (r, c) belongs to
+ *                      tile k = floor(r gy / h) gx + floor(c gx / w) (the one-pixel border counts in the indexing, it has no row)
+ * One solve: per tile the 45 weighted sums over its rows, C_k = l d l^T under the pivot rule.  A tile whose factor fails (flat,
+ * empty, every weight 0) is DEAD in this pass: it adds nothing, gamma_k = beta_k = 0, and its rows stay in the next re-weighting with
+ * those zeros.  The live tiles add, from zero and in ascending k, H' += A_k - B_k C_k^-1 B_k^T and g' += b_k - B_k C_k^-1 d_k;
+ * x = -(H' + mu diag H')^-1 g' by LDL^T; (gamma_k, beta_k) = C_k^-1 (d_k + B_k^T x).  One re-weighting: rho = |e + L x - gamma_k D -
+ * beta_k| with the row's own tile's pair, ONE histogram, median and sigma over all rows of the pair, Tukey's weights.
+ *   v_p        lambda x of the last solve; VITVS_TOO_FEW (every output 0) with fewer than 6 rows, fewer than 6 rows that keep a
+ *              weight, no live tile, or a failed 6 x 6 pivot in any pass; VITVS_NO_DEPTH as the plain law
+ *   p_robust   double [n_pairs][4]: live tiles, dead tiles, the last sigma (0 with N = 0), the live tiles' final sum of weights
+ *   p_tiles    double [n_pairs][T][4]: gamma_k, beta_k, the tile's final sum of weights, live (1.0 / 0.0)
+ *   normal45   double [n_pairs][T][45] or NULL: every tile's sums of the last pass, laid out as the robust law's
+ *   p_info     int32 [n_pairs][8] or NULL: the robust law's
+ * A smooth lighting field (a ramp, a spot) is NOT what a piecewise-constant model fits: the tiles only slow that failure
+ * (DESIGN.md 5n has the numbers).  The same bits from call to call and for a pair alone or at any place of a batch (integer
+ * atomics only).  3 N + 2 launches on `stream`, no host round trip, capturable; the handle's first call allocates the law's own
+ * blocks (12 MiB of segment partials, a 16 KiB histogram and a state per pair of max_pairs, and the host form's staging) and
+ * synchronises the device: make it outside any stream capture.  It shares nothing with the other laws or the velocity path; one
+ * call in flight per handle.  Returns 0, -1 (null), -2 (what the robust law refuses; tiles_y or tiles_x outside 1 .. 8 or above
+ * the pooled side).  No counterpart in the reference. */
+VITVS_API int vitvs_photometric_tile_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                                  int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                  const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                                  int32_t tiles_y, int32_t tiles_x, int32_t robust_iterations, double sigma_min,
+                                                  double* v_p, int32_t* p_status, double* p_robust, double* p_tiles, double* normal45,
+                                                  int32_t* p_info, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_photometric_tile_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                              int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                              const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                              int32_t tiles_y, int32_t tiles_x, int32_t robust_iterations, double sigma_min,
+                                              double* v_p, int32_t* p_status, double* p_robust, double* p_tiles, double* normal45,
+                                              int32_t* p_info);
 /* The launch plan of the photometric law as host arithmetic, for one pair (no handle, no device).  It is declared here, beside the
  * calls it plans, and not among the operator hooks of include/vitvs_ops.h: out int32 [8] = the
  * pooled h = height >> level and w = width >> level, the pooled rows per band max(1, min((2048 >> level) / w, h / 256)), the bands
@@ -687,6 +724,16 @@ VITVS_API int vitvs_photometric_rig_velocity(vitvs_handle* h, int32_t n_cams, co
  * the workspace bytes per pair 256 bands, 1 when the LDS needs the opt-in past 64 KiB, 0.  Returns 0, -1 (out NULL), -2 (height
  * or width outside 1 .. 4096, level outside 0 .. 3, a pooled side < 3; out is zeros). */
 VITVS_API int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t level, int32_t* out);
+/* The tile law's plan, likewise: out int32 [8] = the pooled h and w, the rows per band and the bands (the plain law's), the slots
+ * per band, the dynamic LDS bytes of the rows launch 1536 + 4 ((rows + 2) 2 w + rows w) and of the residual launch (16384 more),
+ * the workspace doubles per pair bands x slots x tiles_x x 48.  A band of more than one row (pooled h >= 512) may lie across ONE
+ * tile-row boundary, since rows <= h / 256 and a tile row has at least floor(h / 8) rows: such a plan has 2 slots, slot s of a band
+ * for tile row floor(band rows tiles_y / h) + s; a plan of one-row bands has 1.  The partial of (band, slot, tile column) is 48
+ * doubles at ((band slots + slot) tiles_x + tile column) 48; wave v of a band's workgroup takes the (slot, tile column) segments
+ * v, v + 4, .. in slot-major order and its lanes stride over the segment's pixels row-major.  Returns 0, -1 (out NULL), -2 (what
+ * vitvs_op_photometric_plan refuses; tiles_y or tiles_x outside 1 .. 8 or above the pooled side; out is zeros). */
+VITVS_API int vitvs_op_photometric_tile_plan(int32_t height, int32_t width, int32_t level, int32_t tiles_y, int32_t tiles_x,
+                                             int32_t* out);
 
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own

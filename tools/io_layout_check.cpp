@@ -137,6 +137,19 @@ int main() {
                    (P * (4 + 36 + 4) + 6 + 28 + ((P * 45 + 1) & ~(size_t)1)) * 8 + (((P + 3) & ~(size_t)3) + 4 + 8) * 4 +
                        ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
                "photometric rig: %zu %zu", P, px_max);
+        // the tile form: the sums and the lighting per tile, 64 tiles reserved per pair, T of them in a call
+        for (size_t T : {(size_t)1, (size_t)15, (size_t)64}) {
+            PhotometricTileIo pt = photometric_tile_io(P, px_max * 3, px_max, n, T, px * 3, px, &d, &b16, &b8, &b8, &d, &i, &d, &d, &d, &i);
+            check("photometric tile", io_list(pt), P, px_max, n);
+            PhotometricTileIo pt0 = photometric_tile_io(P, px_max * 3, px_max);
+            EXPECT(io_place(io_list(pt0), nullptr) == io_place(io_list(pt), nullptr), "photometric tile: allocation and call disagree");
+            EXPECT(pt.Z.count == n * px && pt.I_cur.count == n * px * 3 && pt.I_des.count == n * px * 3 &&
+                       pt.normal45.count == n * T * 45 && pt.p_tiles.count == n * T * 4 && pt.p_robust.count == n * 4,
+                   "photometric tile: counts");
+            EXPECT(io_place(io_list(pt0), nullptr) == P * (4 + 6 + 64 * 45 + 64 * 4 + 4) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
+                                                          ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
+                   "photometric tile: %zu %zu", P, px_max);
+        }
     }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");

@@ -229,6 +229,12 @@ class ServoParams:
                                                 # DESIGN.md 5l) and estimates a lighting gain and bias with the twist
     photometric_robust_iterations: int = 0      # 0 .. 4 Tukey re-weightings of its rows (> 0: the robust law); both off: the plain law
     photometric_sigma_min: float = 1.0          # > 0, grey levels: the floor of the robust law's residual scale
+    photometric_tiles: tuple = (1, 1)           # (tiles_y, tiles_x), each 1 .. 8: a lighting gain / bias per tile of that grid
+                                                # (Engine.photometric_tile_velocity); needs photometric_illumination.
+                                                # (1, 1) = off: the hand-over calls exactly what it calls without this field
+    photometric_handback_rejected: float = 0.0  # a share in (0, 1]: a robust, tile or rig photometric call that leaves more than
+                                                # this share of its rows at weight 0 hands back to the ViT update, as a status
+                                                # that is not OK does; needs photometric_robust_iterations > 0.  0 = off
 
     def __post_init__(self):
         if not isinstance(self.photometric_illumination, bool):
@@ -239,6 +245,21 @@ class ServoParams:
         if isinstance(self.photometric_sigma_min, bool) or not isinstance(self.photometric_sigma_min, (int, float)) \
                 or not (math.isfinite(float(self.photometric_sigma_min)) and float(self.photometric_sigma_min) > 0.0):
             raise ValueError(f"photometric_sigma_min is finite and > 0 grey levels, got {self.photometric_sigma_min!r}")
+        t = self.photometric_tiles
+        if isinstance(t, list):
+            t = tuple(t)                                                          # a YAML sequence
+            object.__setattr__(self, "photometric_tiles", t)
+        if not (isinstance(t, tuple) and len(t) == 2 and all(isinstance(g, int) and not isinstance(g, bool) and 1 <= g <= 8 for g in t)):
+            raise ValueError(f"photometric_tiles is (tiles_y, tiles_x), each 1 .. 8, got {self.photometric_tiles!r}")
+        if t != (1, 1) and not self.photometric_illumination:
+            raise ValueError("photometric_tiles other than (1, 1) needs photometric_illumination=True: the tiles are the grid of the "
+                             "lighting model, and a grid without a lighting model means nothing")
+        hb = self.photometric_handback_rejected
+        if isinstance(hb, bool) or not isinstance(hb, (int, float)) or not (math.isfinite(float(hb)) and 0.0 <= float(hb) <= 1.0):
+            raise ValueError(f"photometric_handback_rejected is 0 (off) or a share in (0, 1], got {hb!r}")
+        if hb > 0 and self.photometric_robust_iterations == 0:
+            raise ValueError("photometric_handback_rejected needs photometric_robust_iterations > 0: without a re-weighting no row "
+                             "is ever rejected")
         if not (math.isfinite(float(self.photometric_handover)) and float(self.photometric_handover) >= 0.0):
             raise ValueError(f"photometric_handover is a finite threshold >= 0 (0 = off), got {self.photometric_handover!r}")
         if isinstance(self.photometric_level, bool) or int(self.photometric_level) != self.photometric_level \
@@ -344,7 +365,8 @@ def load_reference_config(source) -> ReferenceConfig:
     ``roll_search`` (the roll search in front of every update) likewise, else False; ``photometric_handover``, ``photometric_level``,
     ``photometric_mu``, ``photometric_lambda`` and ``photometric_interaction`` (the hand-over to the photometric law) likewise, else
     0.0 (off), 2, 0.01, None and "desired"; ``photometric_illumination``, ``photometric_robust_iterations`` and
-    ``photometric_sigma_min`` (its robust form) likewise, else False, 0 and 1.0."""
+    ``photometric_sigma_min`` (its robust form) likewise, else False, 0 and 1.0; ``photometric_tiles`` (its tile form, a sequence of
+    two) and ``photometric_handback_rejected`` likewise, else (1, 1) and 0.0."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -379,14 +401,17 @@ def load_reference_config(source) -> ReferenceConfig:
                         photometric_interaction=str(cfg.get("photometric_interaction", "desired")),
                         photometric_illumination=cfg.get("photometric_illumination", False),
                         photometric_robust_iterations=cfg.get("photometric_robust_iterations", 0),
-                        photometric_sigma_min=cfg.get("photometric_sigma_min", 1.0))
+                        photometric_sigma_min=cfg.get("photometric_sigma_min", 1.0),
+                        photometric_tiles=cfg.get("photometric_tiles", (1, 1)),
+                        photometric_handback_rejected=cfg.get("photometric_handback_rejected", 0.0))
     used = {"roll_search","u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
             "rig_pose_robust_iterations", "homography_robust_iterations", "homography_depth",
             "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed",
             "photometric_handover", "photometric_level", "photometric_mu", "photometric_lambda", "photometric_interaction",
-            "photometric_illumination", "photometric_robust_iterations", "photometric_sigma_min"}
+            "photometric_illumination", "photometric_robust_iterations", "photometric_sigma_min", "photometric_tiles",
+            "photometric_handback_rejected"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

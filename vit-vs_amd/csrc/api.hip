@@ -147,6 +147,9 @@ struct vitvs_handle {
     unsigned char *photo_robust_ws = nullptr, *photo_robust_io = nullptr;
     // the rig form (vitvs_photometric_rig_velocity[_dev]) runs in photo_robust_ws; photo_rig_io = PhotometricRigIo
     unsigned char* photo_rig_io = nullptr;
+    // the tile form (vitvs_photometric_tile_velocity[_dev]) shares nothing with them: photo_tile_ws = the 48-double segment partials,
+    // one histogram and one state per pair (photometric_tile_ws_bytes), photo_tile_io = PhotometricTileIo
+    unsigned char *photo_tile_ws = nullptr, *photo_tile_io = nullptr;
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -2276,6 +2279,75 @@ int vitvs_photometric_rig_velocity(vitvs_handle* h, int32_t n_cams, const uint8_
     });
 }
 
+// --- the tile photometric law ---------------------------------------------------------------------
+// Everything the robust law refuses (the lighting model is always on), and the tile grid; the first call allocates the law's own
+// two blocks (the 48-double segment partials at 4096 segment rows of 8 tile columns, a histogram and a state per pair of max_pairs;
+// PhotometricTileIo at 64 tiles per pair), zeroed, so no later call allocates.
+static int photometric_tile_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction, double depth_scale,
+                                    double mu, double lambda, int tiles_y, int tiles_x, int robust_iterations, double sigma_min,
+                                    bool host_form) {
+    if (int rc = photometric_check(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, host_form)) return rc;
+    if (tiles_y < 1 || tiles_y > 8 || tiles_x < 1 || tiles_x > 8) return set_err(h, -2, "tiles_y and tiles_x are 1 .. 8");
+    if (tiles_y > (height >> level) || tiles_x > (width >> level))
+        return set_err(h, -2, "tiles_y and tiles_x are at most the pooled image's sides");
+    if (robust_iterations < 0 || robust_iterations > 4) return set_err(h, -2, "robust_iterations is 0 .. 4");
+    if (!std::isfinite(sigma_min) || !(sigma_min > 0.0)) return set_err(h, -2, "sigma_min is finite and > 0");
+    const vitvs_config& c = h->cfg;
+    PhotometricTilePlan pl;
+    if (int rc = plan_photometric_tiles(height, width, level, tiles_y, tiles_x, c.max_pairs, &pl)) return set_err(h, rc, "no tile photometric plan");
+    const size_t px_max = (size_t)c.u_max * c.v_max;
+    PhotometricTileIo io = photometric_tile_io(c.max_pairs, px_max * 3, px_max);
+    return law_blocks(h, "tile photometric", &h->photo_tile_ws, photometric_tile_ws_bytes(c.max_pairs), &h->photo_tile_io,
+                      io_place(io_list(io), nullptr));
+}
+
+int vitvs_photometric_tile_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                        int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                        int32_t interaction, double mu, double lambda, int32_t tiles_y, int32_t tiles_x,
+                                        int32_t robust_iterations, double sigma_min, double* v_p, int32_t* p_status, double* p_robust,
+                                        double* p_tiles, double* normal45, int32_t* p_info, void* stream) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust || !p_tiles) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_tile_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, tiles_y, tiles_x,
+                                          robust_iterations, sigma_min, false))
+        return rc;
+    PhotometricTileArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    PhotometricRobustArgs& ra = ta.r;
+    PhotometricArgs& a = ra.p;
+    a.n_pairs = n_pairs; a.height = height; a.width = width; a.level = level; a.interaction = interaction;
+    a.I_cur = I_cur; a.I_des = I_des; a.Z_mm = Z_mm; a.depth_scale = depth_scale; a.K = K; a.mu = mu; a.lambda = lambda;
+    a.v_p = v_p; a.p_status = p_status; a.p_info = p_info;
+    ra.illumination = 1; ra.iterations = robust_iterations; ra.sigma_min = sigma_min;
+    ra.p_robust = p_robust; ra.normal45 = normal45;
+    ta.tiles_y = tiles_y; ta.tiles_x = tiles_x; ta.p_tiles = p_tiles;
+    const int rc = launch_photometric_tiles(ta, h->photo_tile_ws, h->cfg.max_pairs, dev_stream(h, stream));
+    return rc ? set_err(h, rc, "tile photometric law launch failed") : 0;
+}
+
+int vitvs_photometric_tile_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                    int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                    int32_t interaction, double mu, double lambda, int32_t tiles_y, int32_t tiles_x,
+                                    int32_t robust_iterations, double sigma_min, double* v_p, int32_t* p_status, double* p_robust,
+                                    double* p_tiles, double* normal45, int32_t* p_info) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust || !p_tiles) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_tile_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, tiles_y, tiles_x,
+                                          robust_iterations, sigma_min, true))
+        return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max, px = (size_t)height * width, T = (size_t)tiles_y * tiles_x;
+    PhotometricTileIo io = photometric_tile_io(c.max_pairs, px_max * 3, px_max, n_pairs, T, px * 3, px, K, Z_mm, I_cur, I_des, v_p,
+                                               p_status, p_robust, p_tiles, normal45, p_info);
+    return host_call(h, io_list(io), h->photo_tile_io, [&](hipStream_t st) {
+        return vitvs_photometric_tile_velocity_dev(h, n_pairs, io.I_cur.dev, io.I_des.dev, height, width,
+                                                   Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale, io.K.f64(),
+                                                   level, interaction, mu, lambda, tiles_y, tiles_x, robust_iterations, sigma_min,
+                                                   io.v_p.f64(), io.p_status.i32(), io.p_robust.f64(), io.p_tiles.f64(),
+                                                   normal45 ? io.normal45.f64() : nullptr, p_info ? io.p_info.i32() : nullptr, st);
+    });
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -2589,6 +2661,17 @@ int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t level, int3
     const int rc = plan_photometric(height, width, level, 1, &pl);
     out[0] = pl.h; out[1] = pl.w; out[2] = pl.rows; out[3] = pl.bands; out[4] = (int32_t)pl.lds; out[5] = (int32_t)pl.ws_bytes;
     out[6] = pl.lds_opt_in; out[7] = 0;
+    return rc;
+}
+
+int vitvs_op_photometric_tile_plan(int32_t height, int32_t width, int32_t level, int32_t tiles_y, int32_t tiles_x, int32_t* out) {
+    if (!out) return -1;
+    PhotometricTilePlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_photometric_tiles(height, width, level, tiles_y, tiles_x, 1, &pl);
+    if (rc) memset(&pl, 0, sizeof(pl));
+    out[0] = pl.h; out[1] = pl.w; out[2] = pl.rows; out[3] = pl.bands; out[4] = pl.slots; out[5] = (int32_t)pl.lds;
+    out[6] = (int32_t)pl.lds_res; out[7] = (int32_t)pl.ws_doubles;
     return rc;
 }
 

@@ -170,4 +170,21 @@ inline PhotometricRigIo photometric_rig_io(size_t P, size_t frame_max, size_t de
                             io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur),   io_in(1, f_cap, n * frame, I_des)};
 }
 
+// the tile photometric law (vitvs_photometric_tile_velocity): PhotometricRobustIo with the sums and the lighting per tile.  T =
+// tiles_y * tiles_x of the call; the block reserves 64 tiles per pair (even capacities: the images keep their 16-byte boundaries).
+struct PhotometricTileIo {
+    IoField K, v_p, normal45, p_tiles, p_robust, p_status, p_info, Z, I_cur, I_des;
+};
+inline PhotometricTileIo photometric_tile_io(size_t P, size_t frame_max, size_t depth_max, size_t n = 0, size_t T = 0, size_t frame = 0,
+                                             size_t depth = 0, const double* K = nullptr, const uint16_t* Z = nullptr,
+                                             const uint8_t* I_cur = nullptr, const uint8_t* I_des = nullptr, double* v_p = nullptr,
+                                             int32_t* p_status = nullptr, double* p_robust = nullptr, double* p_tiles = nullptr,
+                                             double* normal45 = nullptr, int32_t* p_info = nullptr) {
+    const size_t st_cap = (P + 3) & ~(size_t)3, z_cap = (P * depth_max + 7) & ~(size_t)7, f_cap = (P * frame_max + 15) & ~(size_t)15;
+    return PhotometricTileIo{io_in(8, P * 4, n * 4, K),          io_out(8, P * 6, n * 6, v_p),
+                             io_out(8, P * 64 * 45, n * T * 45, normal45), io_out(8, P * 64 * 4, n * T * 4, p_tiles),
+                             io_out(8, P * 4, n * 4, p_robust),  io_out(4, st_cap, n, p_status),    io_out(4, P * 8, n * 8, p_info),
+                             io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur), io_in(1, f_cap, n * frame, I_des)};
+}
+
 }  // namespace vitvs

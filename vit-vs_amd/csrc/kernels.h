@@ -697,6 +697,32 @@ struct PhotometricRigArgs {
 };
 int launch_photometric_rig(const PhotometricRigArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
 
+// The tile photometric law: the robust photometric law with a LOCAL lighting model, one (gamma_k, beta_k) per tile
+// of a tiles_y x tiles_x grid over the pooled image (tile of pooled pixel (r, c): floor(r tiles_y / h) tiles_x + floor(c tiles_x /
+// w)), always on (r.illumination is not read).  Per tile the 45 sums and the 2 x 2 elimination; the live tiles add into one 6 x 6
+// system in ascending order; a tile whose 2 x 2 factor fails is dead in that pass (adds nothing, gamma = beta = 0).  One median over
+// all rows.  3 iterations + 2 launches, no host round trip, in a block of its own of photometric_tile_ws_bytes(max_pairs) bytes
+// that every call must find with its histograms zero.
+constexpr int kPhotoTileMax = 64;
+struct PhotometricTileArgs {
+    PhotometricRobustArgs r;  // r.p.ws: [n_pairs][bands][slots][tiles_x][48] the segment partials; r.state: [n_pairs][16 + 128]
+                              // r.p_robust [n_pairs][4]: live tiles, dead tiles, the last sigma, the live tiles' final sum of weights
+                              // r.normal45 [n_pairs][T][45] or null: every tile's sums of the last pass
+    int tiles_y, tiles_x;     // 1 .. 8 each, at most the pooled side
+    double* p_tiles;          // [n_pairs][T][4] gamma_k, beta_k, the tile's final sum of weights, live (1.0 / 0.0)
+};
+struct PhotometricTilePlan {
+    int h, w, rows, bands;    // plan_photometric's
+    int slots;                // partials a band keeps per tile column: 2 when rows > 1 (a band may lie across one tile-row boundary;
+                              // slot s is tile row floor(band rows tiles_y / h) + s), else 1
+    size_t lds, lds_res;      // dynamic LDS of the rows and the residual launch: the robust law's
+    size_t ws_doubles;        // per pair: bands x slots x tiles_x x 48
+};
+// -2: what plan_photometric refuses, tiles_y or tiles_x outside 1 .. 8 or above the pooled side
+int plan_photometric_tiles(int height, int width, int level, int tiles_y, int tiles_x, int max_pairs, PhotometricTilePlan* plan);
+size_t photometric_tile_ws_bytes(int max_pairs);
+int launch_photometric_tiles(const PhotometricTileArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

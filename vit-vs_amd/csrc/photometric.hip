@@ -10,7 +10,7 @@
 // No float atomics: pixel -> thread -> wave -> band is a function of (H, W, level) alone (plan_photometric), so the sums are the
 // same bits from call to call and for a pair alone or anywhere in a batch.  (One launch with a last-arriver ticket in place of the
 // second: priced and not built)  The law's robust form has kernels of its own further down, and its
-// rig form two more at the end of the file.
+// rig form two more behind them, and its tile form three at the end of the file.
 #include <algorithm>
 
 #include "common.h"
@@ -1024,6 +1024,397 @@ int launch_photometric_rig(const PhotometricRigArgs& ga_in, unsigned char* ws, i
         }
         if (hipGetLastError() != hipSuccess) return -1;
         launch(photometric_rig_solve_kernel, dim3(1), dim3(256), 0, stream, ga, p.h, p.w, p.bands, 0, pass);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
+}
+
+// ---- the tile photometric law -------------------------------------------------------------------------------------
+// The robust law with a LOCAL lighting model: one (gamma_k, beta_k) per tile of a gy x gx grid over the pooled image, the tile of
+// pooled pixel (r, c) being floor(r gy / h) gx + floor(c gx / w).  Per tile the 45 sums and the 2 x 2 elimination; the live tiles'
+// Schur terms add into ONE 6 x 6 system in ascending tile order; one median over all rows.  A tile whose 2 x 2 factor fails is dead
+// in that pass.  3 N + 2 launches as the robust law's, in a block of its own (kernels.h PhotometricTileArgs).  pool_band,
+// photo_row, photo_camera and photo_median_bin are the robust law's; the band plan is the plain law's (plan_photometric_tiles).
+//   photometric_tile_rows_kernel<WEIGHTED>   per (band, pair): the band's (slot, tile column) segments, wave v taking segments
+//                                            v, v + 4, ..; the lanes stride over a segment's pixels row-major, one wave_sum per
+//                                            sum, one 48-double partial per segment and no step across waves
+//   photometric_tile_residual_kernel         the robust law's, (gamma, beta) looked up by the pixel's tile
+//   photometric_tile_solve_kernel            one workgroup of 16 waves per pair: wave v takes tiles v, v + 16, .. (the bands of the tile's rows
+//                                            in ascending order, the 2 x 2 factor, the Schur terms into LDS); wave 0 adds the
+//                                            live tiles in ascending order, LDL^T, every tile's (gamma_k, beta_k)
+constexpr int kPhotoTileState = 16 + 2 * kPhotoTileMax;     // doubles per pair: the robust law's 16 (its gamma, beta slots unused), T x (gamma, beta)
+constexpr int kPhotoTileSegs = 4096;                        // the most bands x slots a plan has
+constexpr int kPhotoTileTerm = 32;                          // LDS doubles per tile: H'_k (21), g'_k (6), -, l, 1 / d0, 1 / d1, (int32 live)
+
+// the first index of tile t of g over n indices: ceil(t n / g); tile t is [tile_begin(t), tile_begin(t + 1))
+__host__ __device__ inline int tile_begin(int t, int n, int g) { return (t * n + g - 1) / g; }
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void photometric_tile_rows_kernel(PhotometricTileArgs ta, int h, int w, int rows, int bands,
+                                                                    int slots) {
+    extern __shared__ double photo_lds[];
+    const PhotometricRobustArgs& ra = ta.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                   // uniform: a wave's segments branch as one
+    const int band = blockIdx.x, pair = blockIdx.y;
+    const int gy = ta.tiles_y, gx = ta.tiles_x;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    double* red = photo_lds;                            // [4][48]: before the sums, the scan of the histogram (257 int32); then each wave's own 48
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    double* state = ra.state + (size_t)pair * kPhotoTileState;
+    double st[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double scale = 1.0;                                 // kTukeyC * sigma
+    if constexpr (WEIGHTED) {
+        const int32_t* si = reinterpret_cast<const int32_t*>(state + 9);
+        if (si[1]) return;                              // a solve before this one failed: the call's answer is written
+#pragma unroll
+        for (int i = 0; i < 6; ++i) st[i] = state[i];
+        const int bin = photo_median_bin(ra.hist + (size_t)pair * kPhotoBins, (si[0] + 1) / 2, reinterpret_cast<int*>(red), tid);
+        const double median = ((double)bin + 0.5) / 16.0;
+        const double sigma = fmax(kMadScale * median, ra.sigma_min);
+        scale = kTukeyC * sigma;
+        if (band == 0 && tid == 0) { state[8] = sigma; reinterpret_cast<int32_t*>(state + 10)[0] = bin; }
+    }
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    const int ty0 = r0 * gy / h;                        // slot s of the band is tile row ty0 + s
+    for (int seg = wave; seg < slots * gx; seg += 4) {
+        const int slot = seg / gx, tx = seg - slot * gx, ty = ty0 + slot;
+        if (ty >= gy) continue;
+        const int ra0 = max(r0, tile_begin(ty, h, gy)), ra1 = min(r1, tile_begin(ty + 1, h, gy));
+        if (ra1 <= ra0) continue;                       // the band does not cross into that tile row: the slot is not read either
+        const int c0 = tile_begin(tx, w, gx), sw = tile_begin(tx + 1, w, gx) - c0;
+        if constexpr (WEIGHTED) {
+            const int k = ty * gx + tx;
+            st[6] = state[16 + 2 * k];
+            st[7] = state[17 + 2 * k];
+        }
+        double acc[45];
+#pragma unroll
+        for (int q = 0; q < 45; ++q) acc[q] = 0.0;
+        int n = 0, holes = 0, zeros = 0;
+        for (int idx = lane; idx < (ra1 - ra0) * sw; idx += 64) {
+            const int q0 = idx / sw, c = c0 + (idx - q0 * sw), r = ra0 + q0, lr = r - r0;
+            double L[6], e, D;
+            const int kind = photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D);
+            if (kind == 2) ++holes;
+            if (kind != 0) continue;
+            double wt = 1.0;
+            if constexpr (WEIGHTED) {
+                const double t = photo_rho(L, e, D, st) / scale;
+                const double u = 1.0 - t * t;
+                wt = t < 1.0 ? u * u : 0.0;
+                if (wt == 0.0) ++zeros;
+            }
+            double wv[8];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) wv[i] = wt * L[i];
+            wv[6] = wt * e;
+            wv[7] = wt * D;
+            int q = 0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) { acc[q] += wv[i] * L[j]; ++q; }
+#pragma unroll
+            for (int i = 0; i < 7; ++i) acc[21 + i] += wv[i] * e;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { acc[28 + 2 * i] += wv[i] * D; acc[29 + 2 * i] += wv[i]; }
+            acc[40] += wv[7] * D;
+            acc[41] += wv[7];
+            acc[42] += wt;
+            acc[43] += wv[7] * e;
+            acc[44] += wv[6];
+            ++n;
+        }
+        double* mine_red = red + wave * kPhotoRPart;    // the wave's own 48 doubles: no step across waves
+#pragma unroll
+        for (int q = 0; q < 45; ++q) {
+            const double t = wave_sum(acc[q]);
+            if (lane == 0) mine_red[q] = t;
+        }
+        wave_lds_fence();
+        double mine = lane < 45 ? mine_red[lane] : 0.0; // lane q < 45: sum q; lane 45: (rows, holes); lane 46: (zero weights, 0)
+        wave_lds_fence();
+        n = wave_sum(n);
+        holes = wave_sum(holes);
+        zeros = wave_sum(zeros);
+        if (lane == 45) mine = __builtin_bit_cast(double, ((unsigned long long)(unsigned)holes << 32) | (unsigned)n);
+        if (lane == 46) mine = __builtin_bit_cast(double, (unsigned long long)(unsigned)zeros);
+        double* part = a.ws + ((((size_t)pair * bands + band) * slots + slot) * gx + tx) * kPhotoRPart;
+        if (lane < kPhotoRPart) part[lane] = mine;
+    }
+}
+
+__global__ __launch_bounds__(256) void photometric_tile_residual_kernel(PhotometricTileArgs ta, int h, int w, int rows, int bands) {
+    extern __shared__ double photo_lds[];
+    const PhotometricRobustArgs& ra = ta.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, band = blockIdx.x, pair = blockIdx.y;
+    const int gy = ta.tiles_y, gx = ta.tiles_x;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);          // the rows launch's layout, the histogram behind it
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    unsigned* bins = reinterpret_cast<unsigned*>(zs + rows * w);
+    const double* state = ra.state + (size_t)pair * kPhotoTileState;
+    if (reinterpret_cast<const int32_t*>(state + 9)[1]) return;
+    double st[8];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) st[i] = state[i];
+    for (int i = tid; i < kPhotoBins; i += 256) bins[i] = 0u;
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);          // (its barriers order the zeros above too)
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    for (int idx = tid; idx < (r1 - r0) * w; idx += 256) {
+        const int lr = idx / w, c = idx - lr * w, r = r0 + lr;
+        double L[6], e, D;
+        if (photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D) != 0) continue;
+        const int k = (r * gy / h) * gx + c * gx / w;   // the pixel's tile: its own lighting pair
+        st[6] = state[16 + 2 * k];
+        st[7] = state[17 + 2 * k];
+        const double rho = photo_rho(L, e, D, st);
+        const int q = rho < (double)(kPhotoBins / 16) ? (int)(16.0 * rho) : kPhotoBins - 1;      // (a NaN: the last bin)
+        atomicAdd(&bins[q], 1u);
+    }
+    __syncthreads();
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;
+    for (int i = tid; i < kPhotoBins; i += 256) {
+        const unsigned cnt = bins[i];
+        if (cnt) atomicAdd(&hist[i], cnt);
+    }
+}
+
+constexpr int kPhotoTileDepth = 8;   // band partials a wave holds in flight per tile (16 measured slower)
+constexpr int kPhotoTileSolveThreads = 1024;     // 16 waves: 4 x 4 tiles are one tile per wave, 8 x 8 four
+
+__global__ __launch_bounds__(kPhotoTileSolveThreads) void photometric_tile_solve_kernel(PhotometricTileArgs ta, int h, int w, int rows, int bands,
+                                                                     int slots, int no_depth, int pass) {
+    __shared__ double Gs[40 + 8 * 27];
+    __shared__ double St[kPhotoTileMax * kPhotoRPart];  // every tile's 45 sums and counts: 24 KiB
+    __shared__ double Tm[kPhotoTileMax * kPhotoTileTerm];
+    const PhotometricRobustArgs& ra = ta.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63, pair = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int gy = ta.tiles_y, gx = ta.tiles_x, T = gy * gx;
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;                         // as photometric_robust_solve_kernel clears it
+    for (int i = tid; i < kPhotoBins; i += kPhotoTileSolveThreads) hist[i] = 0u;
+    double* state = ra.state + (size_t)pair * kPhotoTileState;
+    int32_t* si = reinterpret_cast<int32_t*>(state + 9);
+    if (pass > 0 && si[1]) return;
+    for (int i = tid; i < 40 + 8 * 27; i += kPhotoTileSolveThreads) Gs[i] = 0.0;
+    const double* pair_ws = a.ws + (size_t)pair * bands * slots * gx * kPhotoRPart;
+    for (int k = wave; k < T; k += kPhotoTileSolveThreads / 64) {
+        const int ty = k / gx, tx = k - ty * gx;
+        const int tr0 = tile_begin(ty, h, gy), tr1 = tile_begin(ty + 1, h, gy);
+        const int b0 = tr0 / rows, b1 = no_depth ? b0 : (tr1 - 1) / rows + 1;      // the bands that hold rows of the tile
+        double sum = 0.0;                               // lanes 0 .. 44: one of the tile's 45 sums each
+        int cnt0 = 0, cnt1 = 0;                         // lane 45: rows, holes; lane 46: rows of weight 0
+        for (int b = b0; b < b1; b += kPhotoTileDepth) {
+            double held[kPhotoTileDepth];
+#pragma unroll
+            for (int u = 0; u < kPhotoTileDepth; ++u) {
+                const int bb = min(b + u, b1 - 1);
+                const int slot = (slots > 1 && bb * rows < tr0) ? 1 : 0;      // the band began in the tile row before: its second slot
+                held[u] = (b + u < b1 && lane < kPhotoRPart) ? pair_ws[((size_t)(bb * slots + slot) * gx + tx) * kPhotoRPart + lane] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < kPhotoTileDepth; ++u) {
+                if (b + u >= b1) break;
+                if (lane < 45) {
+                    sum += held[u];                     // ascending band order
+                } else {
+                    const unsigned long long bits = __builtin_bit_cast(unsigned long long, held[u]);
+                    cnt0 += (int)(unsigned)bits;
+                    cnt1 += (int)(unsigned)(bits >> 32);
+                }
+            }
+        }
+        if (ra.normal45 && lane < 45) ra.normal45[((size_t)pair * T + k) * 45 + lane] = sum;
+        double* Sk = St + k * kPhotoRPart;
+        double* Tk = Tm + k * kPhotoTileTerm;
+        if (lane < 45) Sk[lane] = sum;
+        else if (lane == 45) { int32_t* c = reinterpret_cast<int32_t*>(Sk + 45); c[0] = cnt0; c[1] = cnt1; }
+        else if (lane == 46) { int32_t* c = reinterpret_cast<int32_t*>(Sk + 46); c[0] = cnt0; c[1] = 0; }
+        wave_lds_fence();
+        // C_k = l d l^T as photometric_robust_solve_kernel's
+        const double DD = Sk[40], Dm = Sk[41], Sw = Sk[42];
+        const double d0 = DD;
+        bool cgood = (d0 > kPivotThreshold * DD) && (DD > 0.0);
+        const double i0 = 1.0 / d0;
+        const double l = Dm * i0;
+        const double d1 = Sw - l * l * d0;
+        cgood = cgood && (d1 > kPivotThreshold * Sw) && (Sw > 0.0);
+        const double i1 = 1.0 / d1;
+        if (lane < 27) {
+            int i, j = 0;
+            if (lane < 21) triu_index(lane, i, j);
+            else i = lane - 21;
+            const double p = Sk[28 + 2 * i], q1 = Sk[29 + 2 * i];
+            const double u1 = (q1 - l * p) * i1, u0 = p * i0 - l * u1;
+            const double o0 = lane < 21 ? Sk[28 + 2 * j] : Sk[43], o1 = lane < 21 ? Sk[29 + 2 * j] : Sk[44];
+            Tk[lane] = sum - (u0 * o0 + u1 * o1);
+        }
+        if (lane == 0) {
+            Tk[28] = l; Tk[29] = i0; Tk[30] = i1;
+            reinterpret_cast<int32_t*>(Tk + 31)[0] = cgood ? 1 : 0;
+        }
+        wave_lds_fence();
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // the live tiles in ascending order: which wave held which does not show.  Lane k holds tile k's counts and flag; the sums
+    // run over all T tiles with the reads in flight together, a dead tile adding +0.0 (exact: a sum that starts at +0.0 is never -0.0)
+    int n = 0, holes = 0, zeros = 0;
+    bool mine_live = false;
+    if (lane < T) {
+        const int32_t* c = reinterpret_cast<const int32_t*>(St + lane * kPhotoRPart + 45);
+        n = c[0];
+        holes = c[1];
+        zeros = c[2];
+        mine_live = reinterpret_cast<const int32_t*>(Tm + lane * kPhotoTileTerm + 31)[0] != 0;
+    }
+    n = wave_sum(n);
+    holes = wave_sum(holes);
+    zeros = wave_sum(zeros);
+    const unsigned long long live_mask = __ballot(mine_live);
+    const int n_live = __popcll(live_mask);
+    double sum = 0.0, wtotal = 0.0;
+    const int term = lane < 27 ? lane : 0;
+#pragma unroll 8
+    for (int k = 0; k < T; ++k) {
+        const double t = Tm[k * kPhotoTileTerm + term], wk = St[k * kPhotoRPart + 42];
+        const bool live = (live_mask >> k) & 1ull;
+        sum += live ? t : 0.0;
+        wtotal += live ? wk : 0.0;
+    }
+    if (lane < 27) {
+        const bool diag = lane == 0 || lane == 6 || lane == 11 || lane == 15 || lane == 18 || lane == 20;
+        Gs[40 + lane] = diag ? sum + a.mu * sum : sum;
+    }
+    wave_lds_fence();
+    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool solved = false;
+    const bool tried = !no_depth && n >= 6 && n - zeros >= 6;
+    if (tried && n_live > 0) solved = solve_ldlt(Gs, lane, x);
+    if (lane < T) {                                     // lane = tile: its lighting pair
+        const int k = lane;
+        const double* Sk = St + k * kPhotoRPart;
+        const double* Tk = Tm + k * kPhotoTileTerm;
+        const bool live = reinterpret_cast<const int32_t*>(Tk + 31)[0] != 0;
+        double gamma = 0.0, beta = 0.0;
+        if (solved && live) {
+            const double l = Tk[28], i0 = Tk[29], i1 = Tk[30];
+            double t0 = Sk[43], t1 = Sk[44];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { t0 = t0 + Sk[28 + 2 * i] * -x[i]; t1 = t1 + Sk[29 + 2 * i] * -x[i]; }
+            beta = (t1 - l * t0) * i1;
+            gamma = t0 * i0 - l * beta;
+        }
+        state[16 + 2 * k] = gamma;
+        state[17 + 2 * k] = beta;
+        double* pt = ta.p_tiles + ((size_t)pair * T + k) * 4;
+        pt[0] = gamma;
+        pt[1] = beta;
+        pt[2] = solved ? Sk[42] : 0.0;
+        pt[3] = (solved && live) ? 1.0 : 0.0;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            state[i] = -x[i];
+            a.v_p[(size_t)pair * 6 + i] = solved ? -a.lambda * x[i] : 0.0;
+        }
+        state[6] = 0.0;
+        state[7] = 0.0;
+        si[0] = n;
+        si[1] = solved ? 0 : 1;
+        a.p_status[pair] = no_depth ? ST_NO_DEPTH : solved ? ST_OK : ST_TOO_FEW;
+        if (a.p_info) {
+            int32_t* pi = a.p_info + (size_t)pair * 8;
+            pi[0] = n; pi[1] = h; pi[2] = w; pi[3] = bands; pi[4] = holes; pi[5] = (tried && !solved) ? 1 : 0; pi[6] = zeros; pi[7] = pass;
+        }
+        double* pr = ra.p_robust + (size_t)pair * 4;
+        pr[0] = solved ? (double)n_live : 0.0;
+        pr[1] = solved ? (double)(T - n_live) : 0.0;
+        pr[2] = (solved && pass > 0) ? state[8] : 0.0;
+        pr[3] = solved ? wtotal : 0.0;
+    }
+}
+
+int plan_photometric_tiles(int height, int width, int level, int tiles_y, int tiles_x, int max_pairs, PhotometricTilePlan* plan) {
+    if (!plan || tiles_y < 1 || tiles_y > 8 || tiles_x < 1 || tiles_x > 8) return -2;
+    PhotometricPlan p;
+    if (int rc = plan_photometric(height, width, level, max_pairs, &p)) return rc;
+    if (tiles_y > p.h || tiles_x > p.w) return -2;
+    plan->h = p.h;
+    plan->w = p.w;
+    plan->rows = p.rows;
+    plan->bands = p.bands;
+    // A band of more than one row (h >= 512) may lie across ONE tile-row boundary: rows <= h / 256 and a tile row has at least
+    // floor(h / 8) >= 64 rows.  Such a plan gives every band a second slot; one-row bands have one.  rows > 1 means bands <= h / 2
+    // + 1, so bands x slots stays within kPhotoTileSegs either way.
+    plan->slots = p.rows > 1 ? 2 : 1;
+    plan->lds = p.lds - 4 * kPhotoPart * sizeof(double) + 4 * kPhotoRPart * sizeof(double);
+    plan->lds_res = plan->lds + kPhotoBins * sizeof(uint32_t);
+    plan->ws_doubles = (size_t)plan->bands * plan->slots * tiles_x * kPhotoRPart;
+    return plan->bands * plan->slots <= kPhotoTileSegs ? 0 : -3;
+}
+
+size_t photometric_tile_ws_bytes(int max_pairs) {
+    return (size_t)max_pairs * ((size_t)kPhotoTileSegs * 8 * kPhotoRPart * sizeof(double) + kPhotoBins * sizeof(uint32_t) +
+                                kPhotoTileState * sizeof(double));
+}
+
+int launch_photometric_tiles(const PhotometricTileArgs& ta_in, unsigned char* ws, int max_pairs, hipStream_t stream) {
+    PhotometricTileArgs ta = ta_in;
+    PhotometricRobustArgs& ra = ta.r;
+    PhotometricArgs& a = ra.p;
+    if (a.n_pairs < 1 || a.n_pairs > 65535 || a.n_pairs > max_pairs || !a.I_cur || !a.I_des || !a.K || !ws || !a.v_p || !a.p_status ||
+        !ra.p_robust || !ta.p_tiles)
+        return -2;
+    if (a.interaction < 0 || a.interaction > 1 || !(a.mu >= 0.0) || !(a.mu < __builtin_huge_val())) return -2;
+    if (!(a.lambda == a.lambda) || !(a.depth_scale == a.depth_scale)) return -2;
+    if (ra.iterations < 0 || ra.iterations > 4) return -2;
+    if (!(ra.sigma_min > 0.0) || !(ra.sigma_min < __builtin_huge_val())) return -2;
+    PhotometricTilePlan p;
+    if (int rc = plan_photometric_tiles(a.height, a.width, a.level, ta.tiles_y, ta.tiles_x, a.n_pairs, &p)) return rc;
+    ra.illumination = 1;
+    // the block: the partials of max_pairs pairs at kPhotoTileSegs segments rows of 8 tile columns, then the histograms, then the states
+    const size_t part_bytes = (size_t)max_pairs * kPhotoTileSegs * 8 * kPhotoRPart * sizeof(double);
+    a.ws = reinterpret_cast<double*>(ws);
+    ra.hist = reinterpret_cast<uint32_t*>(ws + part_bytes);
+    ra.state = reinterpret_cast<double*>(ws + part_bytes + (size_t)max_pairs * kPhotoBins * sizeof(uint32_t));
+    const int no_depth = (!a.Z_mm && !(a.depth_scale > 0.0)) ? 1 : 0;
+    if (no_depth) {
+        launch(photometric_tile_solve_kernel, dim3(a.n_pairs), dim3(kPhotoTileSolveThreads), 0, stream, ta, p.h, p.w, p.rows, p.bands, p.slots, 1, 0);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    static std::atomic<unsigned long long> raised0{0}, raised1{0}, raised2{0};
+    if (p.lds > 64 * 1024 &&
+        (raise_lds_limit(reinterpret_cast<const void*>(photometric_tile_rows_kernel<false>), 160 * 1024, raised0) ||
+         raise_lds_limit(reinterpret_cast<const void*>(photometric_tile_rows_kernel<true>), 160 * 1024, raised1)))
+        return -3;
+    if (ra.iterations > 0 && p.lds_res > 64 * 1024 &&
+        raise_lds_limit(reinterpret_cast<const void*>(photometric_tile_residual_kernel), 160 * 1024, raised2))
+        return -3;
+    const dim3 grid(p.bands, a.n_pairs);
+    for (int pass = 0; pass <= ra.iterations; ++pass) {
+        if (pass > 0) {
+            launch(photometric_tile_residual_kernel, grid, dim3(256), p.lds_res, stream, ta, p.h, p.w, p.rows, p.bands);
+            launch(photometric_tile_rows_kernel<true>, grid, dim3(256), p.lds, stream, ta, p.h, p.w, p.rows, p.bands, p.slots);
+        } else {
+            launch(photometric_tile_rows_kernel<false>, grid, dim3(256), p.lds, stream, ta, p.h, p.w, p.rows, p.bands, p.slots);
+        }
+        if (hipGetLastError() != hipSuccess) return -1;
+        launch(photometric_tile_solve_kernel, dim3(a.n_pairs), dim3(kPhotoTileSolveThreads), 0, stream, ta, p.h, p.w, p.rows, p.bands, p.slots, 0, pass);
         if (hipGetLastError() != hipSuccess) return -1;
     }
     return 0;

@@ -670,6 +670,78 @@ class Engine:
         return self._photometric_robust(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, illumination,
                                         robust_iterations, sigma_min)
 
+    # ------------------------------------------------------------------ the tile photometric law
+    @staticmethod
+    def _photometric_tile_grid(tiles):
+        try:
+            gy, gx = tiles
+        except (TypeError, ValueError):
+            raise VitvsError(f"tiles is (tiles_y, tiles_x), got {tiles!r}") from None
+        for g in (gy, gx):
+            if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 1 <= int(g) <= 8:
+                raise VitvsError(f"tiles is (tiles_y, tiles_x), each 1 .. 8, got {tiles!r}")
+        return int(gy), int(gx)
+
+    def photometric_tile_velocity(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                  lambda_: Optional[float] = None, depth_scale: float = 0.0, tiles=(4, 4), robust_iterations: int = 4,
+                                  sigma_min: float = 1.0):
+        """``vitvs_photometric_tile_velocity_dev``: the robust photometric law with a LOCAL lighting model: one gain
+        and bias per tile of a ``tiles`` = (tiles_y, tiles_x) grid (each 1 .. 8, at most the pooled side) over the pooled image, for
+        cast shadows, lighting edges and regional exposure.  The lighting model is always on; the other arguments are
+        ``photometric_robust_velocity``'s.  A tile whose rows cannot tell gain from bias (flat, empty, all rejected) is dead in that
+        pass and adds nothing.  3 ``robust_iterations`` + 2 launches on the current stream.  Returns ``(v float64 [n, 6] device
+        tensor, info)``: ``photometric_robust_velocity``'s ``info`` without ``gamma`` / ``gain`` / ``bias``, with ``normal`` float64
+        [n, T, 45] per tile, ``weight`` the live tiles' final sum of weights, and ``tile_gain`` (1 + gamma_k; 1 for a dead tile),
+        ``tile_bias``, ``tile_weight``, ``tile_live`` (bool), each [n, tiles_y, tiles_x], ``live_tiles`` and ``dead_tiles``.
+        A smooth lighting field is not what tiles fit: they only slow that failure.  Reading ``info`` synchronises; the engine's
+        first call allocates: make it outside a stream capture."""
+        return self._photometric_tile(False, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, tiles, robust_iterations,
+                                      sigma_min)
+
+    def photometric_tile_velocity_host(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                       lambda_: Optional[float] = None, depth_scale: float = 0.0, tiles=(4, 4),
+                                       robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_tile_velocity``, the host-pointer form of ``photometric_tile_velocity``: numpy arrays in, ``(v float64
+        [n, 6], info)`` out, one synchronous C call.  Frames of at most ``params.v_max`` x ``params.u_max`` pixels."""
+        return self._photometric_tile(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, tiles, robust_iterations,
+                                      sigma_min)
+
+    def _photometric_tile(self, host, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, tiles, robust_iterations,
+                          sigma_min):
+        stage = self._stage(host)
+        cur = stage.frames(I_cur, None, None)
+        n, hh, ww = (int(x) for x in cur.shape[:3])
+        des = stage.frames(I_des, n, (hh, ww))
+        z = stage.depth(Z, n, (hh, ww))
+        kk = stage.intrinsics(K, n)
+        gy, gx = self._photometric_tile_grid(tiles)
+        _, iters, smin = self._photometric_robust_scalars(True, robust_iterations, sigma_min)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        T = gy * gx
+        v, st, robust, ptiles, normal, pinfo, p = (stage.f64(n, 6), stage.i32(n), stage.f64(n, 4), stage.f64(n, T, 4),
+                                                   stage.f64(n, T, 45), stage.i32(n, 8), stage.ptr)
+        entry = "vitvs_photometric_tile_velocity" + ("" if host else "_dev")
+        rc = getattr(self.lib, entry)(self.handle, n, p(cur), p(des), hh, ww, p(z), ds, p(kk), level, inter, mu, lam, gy, gx, iters, smin,
+                                      p(v), p(st), p(robust), p(ptiles), p(normal), p(pinfo), *stage.stream)
+        self._check(rc, entry)
+        return v, self._photometric_tile_info(stage.read(st), stage.read(normal), stage.read(pinfo), stage.read(robust),
+                                              stage.read(ptiles), gy, gx)
+
+    @staticmethod
+    def _photometric_tile_info(status, normal, pinfo, robust, ptiles, gy, gx) -> dict:
+        n, weight = pinfo[:, 0], robust[:, 3]
+        t = ptiles.reshape(-1, gy, gx, 4)
+        live = t[..., 3] != 0
+        c = (normal[:, :, 27] * live.reshape(live.shape[0], -1)).sum(axis=1)      # sum w e^2 over the live tiles
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cost = np.where(weight > 0, c / np.where(weight > 0, weight, 1.0), 0.0)
+            rejected = np.where(n > 0, pinfo[:, 6] / np.maximum(n, 1), 0.0)
+        return dict(status=status, normal=normal, n=n.copy(), cost=cost, pooled=pinfo[:, 1:3].copy(), bands=pinfo[:, 3].copy(),
+                    holes=pinfo[:, 4].copy(), pivot_failed=pinfo[:, 5].astype(bool), zero_weight=pinfo[:, 6].copy(),
+                    reweightings=pinfo[:, 7].copy(), sigma=robust[:, 2].copy(), weight=weight.copy(), rejected=rejected,
+                    tile_gain=1.0 + t[..., 0], tile_bias=t[..., 1].copy(), tile_weight=t[..., 2].copy(), tile_live=live,
+                    live_tiles=robust[:, 0].astype(np.int64), dead_tiles=robust[:, 1].astype(np.int64))
+
     # ------------------------------------------------------------------ the photometric rig law
     def photometric_rig_velocity(self, I_cur, I_des, Z, K, cVr, live=None, level: int = 2, interaction="desired", mu: float = 0.01,
                                  lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,

@@ -319,7 +319,8 @@ class Controller:
                                  f"({self.params.v_max} x {self.params.u_max}), got {size[0]} x {size[1]}")
         self.photometric_active = False                   # photometric_handover: the photometric law has the robot
         self.last_photometric = None                      # dict(status, cost = sum e^2 / n, n) of its last call; its robust form
-                                                          # (photometric_illumination / _robust_iterations): and gain, bias, sigma, rejected
+                                                          # (photometric_illumination / _robust_iterations): and gain, bias, sigma, rejected;
+                                                          # its tile form (photometric_tiles): and sigma, rejected, dead_tiles, gain_min, gain_max
         self._photo_goal_src = None                       # the PIL goal image _photo_goal was converted from
         self._photo_goal = None                           # (host copy, device tensor) of the goal frame at camera resolution, and
         self._photo_goal_depth = None                     # of the goal depth: uploaded once, compared by content like _goal_np
@@ -575,8 +576,8 @@ class Controller:
         return cur, self._photo_goal[1], z, (0.0 if z is not None else p.homography_depth)
 
     def _photometric_step(self) -> bool:
-        """One update by the photometric law alone.  False, with the hand-over cleared, when its status is not OK: the caller runs
-        the ViT update for this call."""
+        """One update by the photometric law alone.  False, with the hand-over cleared, when its status is not OK or its rejected
+        share is above ``photometric_handback_rejected``: the caller runs the ViT update for this call."""
         p = self.params
         inputs = self._photometric_inputs()
         if inputs is None:
@@ -585,7 +586,13 @@ class Controller:
         cur, goal, z, scalar = inputs
         lam = p.lambda_ if p.photometric_lambda is None else p.photometric_lambda
         robust = p.photometric_illumination or p.photometric_robust_iterations > 0
-        if robust:
+        tiles = tuple(p.photometric_tiles) != (1, 1)
+        if tiles:
+            v, info = self.engine.photometric_tile_velocity(cur, goal, None if z is None else z[None], p.intrinsics(),
+                                                            p.photometric_level, p.photometric_interaction, p.photometric_mu, lam, scalar,
+                                                            tuple(p.photometric_tiles), p.photometric_robust_iterations,
+                                                            p.photometric_sigma_min)
+        elif robust:
             v, info = self.engine.photometric_robust_velocity(cur, goal, None if z is None else z[None], p.intrinsics(),
                                                               p.photometric_level, p.photometric_interaction, p.photometric_mu, lam, scalar,
                                                               p.photometric_illumination, p.photometric_robust_iterations,
@@ -595,9 +602,17 @@ class Controller:
                                                        p.photometric_interaction, p.photometric_mu, lam, scalar)
         st = int(info["status"][0])
         self.last_photometric = dict(status=st, cost=float(info["cost"][0]), n=int(info["n"][0]))
-        if robust:
+        if tiles:
+            gains = info["tile_gain"][0][info["tile_live"][0]]
+            self.last_photometric.update(sigma=float(info["sigma"][0]), rejected=float(info["rejected"][0]),
+                                         dead_tiles=int(info["dead_tiles"][0]),
+                                         gain_min=float(gains.min()) if gains.size else 0.0,
+                                         gain_max=float(gains.max()) if gains.size else 0.0)
+        elif robust:
             self.last_photometric.update({k: float(info[k][0]) for k in ("gain", "bias", "sigma", "rejected")})
-        if st != _lib.STATUS_OK:
+        # photometric_handback_rejected: a rejected share above it is a status that is not OK
+        share = p.photometric_handback_rejected
+        if st != _lib.STATUS_OK or (share > 0 and (tiles or robust) and self.last_photometric["rejected"] > share):
             self.photometric_active = False
             return False
         self._raw_v, self.last_status = v[0].cpu().numpy(), st
@@ -704,9 +719,13 @@ class MultiController:
         # alone (Engine.photometric_rig_velocity) on the live cameras' camera-resolution frames, until its status is
         # not OK.  ``goal_depth`` (one image, or one per camera) is then also the depth of interaction "desired".
         self.photometric_active = False
-        self.last_photometric = None                      # dict(status, cost, n, cameras, gain, bias, sigma, rejected) of its last call
+        self.last_photometric = None                      # dict(status, cost, n, cameras, gain, bias, sigma, rejected) of its last call;
+                                                          # with photometric_handback_rejected: and rejected_share, the stack's
         self._photo_goal, self._photo_depth, self._photo_rows = None, None, None
         self._photo_goal_depth = None if goal_depth is None else np.asarray(goal_depth)
+        if tuple((params or self.engine.params).photometric_tiles) != (1, 1):
+            raise ValueError("photometric_tiles is servo.Controller's: the photometric rig law keeps one gain per camera, and tiles "
+                             "inside a rig are not built")
         if (params or self.engine.params).photometric_handover > 0:
             if self.pipe is not None:
                 raise ValueError("photometric_handover needs the Engine backend: the photometric rig law reads all cameras in one handle, "
@@ -843,8 +862,8 @@ class MultiController:
         return np.stack(cur), self._photo_goal[1], z, (0.0 if z is not None else p.homography_depth), rows
 
     def _photometric_round(self, live) -> bool:
-        """One round by the photometric rig law alone.  False, with the hand-over cleared, when its status is not OK: the caller
-        runs the batched ViT round for this call."""
+        """One round by the photometric rig law alone.  False, with the hand-over cleared, when its status is not OK or the share
+        of rows at weight 0 is above ``photometric_handback_rejected``: the caller runs the batched ViT round for this call."""
         p = self.params
         inputs = self._photometric_inputs(live)
         if inputs is None:
@@ -862,7 +881,11 @@ class MultiController:
         self.last_photometric = dict(status=st, cost=float(info["cost"]), n=int(info["n"]), cameras=list(live),
                                      gain=info["gain"].tolist(), bias=info["bias"].tolist(), sigma=float(info["sigma"].max()),
                                      rejected=rejected.tolist())
-        if st != _lib.STATUS_OK:
+        # photometric_handback_rejected: a share of the stack's rows at weight 0 above it is a status that is not OK
+        share = p.photometric_handback_rejected
+        if share > 0:
+            self.last_photometric["rejected_share"] = float(info["zero_weight"]) / max(int(info["n"]), 1)
+        if st != _lib.STATUS_OK or (share > 0 and self.last_photometric["rejected_share"] > share):
             self.photometric_active = False
             return False
         self.rig_status, self.rig_info = st, info
