@@ -717,6 +717,50 @@ VITVS_API int vitvs_photometric_tile_velocity(vitvs_handle* h, int32_t n_pairs, 
                                               int32_t tiles_y, int32_t tiles_x, int32_t robust_iterations, double sigma_min,
                                               double* v_p, int32_t* p_status, double* p_robust, double* p_tiles, double* normal45,
                                               int32_t* p_info);
+/* --- the surface photometric law: a smooth lighting model, a bilinear spline of gains and biases (photometric.hip) ------
+ * The tile law's sibling, DESIGN.md 5o: a lamp beside the target, vignetting that changes with exposure or a window at one side of
+ * the room are SMOOTH lighting fields, which a gain and a bias per tile do not fit.  Every argument of
+ * vitvs_photometric_tile_velocity_dev means what it means there; the grid is the tile law's.
+ *   cells_y, cells_x   gy, gx = 1 .. 8 each, at most the pooled image's sides.  (gy + 1)(gx + 1) nodes, node a = i (gx + 1) + j;
+ *                      unknown 2 a is gamma_a and 2 a + 1 is beta_a, M = 2 (gy + 1)(gx + 1) <= 162.  The row at pooled pixel (r, c)
+ *                      lies in cell (i, j) = (floor(r gy / h), floor(c gx / w)), v = (r gy - i h) / h, u = (c gx - j w) / w,
+ *                      phi = [(1-v)(1-u), (1-v) u, v (1-u), v u] for the nodes (i, j), (i, j+1), (i+1, j), (i+1, j+1), and
+ *                      I_cur ~ (1 + sum phi_a gamma_a) I_des + sum phi_a beta_a
+ * One solve: per cell 120 weighted sums over its rows (below); the cells add from zero and in ascending index into the node system
+ * C_g (M x M, half-bandwidth 2 gx + 5), B_g (6 x M), d_g and A, b, c.  C_g = L D L^T in ascending index under the pivot rule:
+ * unknown j is live iff C_jj > 0 and d_j > 1e-4 C_jj, else DEAD in this pass: its row and column are left out, its value is 0, and
+ * its rows stay in every sum and in the next re-weighting with that zero.  H' = A - B_g C_g^-1 B_g^T, g' = b - B_g C_g^-1 d_g,
+ * x = -(H' + mu diag H')^-1 g' by LDL^T, the node values q = C_g^-1 (d_g + B_g^T x).  One re-weighting: rho = |e + L x -
+ * gamma(r,c) D - beta(r,c)| with the phi-sums of the pixel's four nodes, ONE histogram, median and sigma over all rows, Tukey's weights.
+ *   v_p        lambda x of the last solve; VITVS_TOO_FEW (every output 0) with fewer than 6 rows, fewer than 6 rows that keep a
+ *              weight, every unknown dead, or a failed 6 x 6 pivot in any pass; VITVS_NO_DEPTH as the plain law
+ *   p_robust   double [n_pairs][4]: live unknowns, dead unknowns, the last sigma (0 with N = 0), the final sum of weights
+ *   p_nodes    double [n_pairs][(gy + 1)(gx + 1)][4]: gamma_a, beta_a, gamma_a live (1.0 / 0.0), beta_a live
+ *   cell_sums  double [n_pairs][gy gx][120] or NULL: every cell's sums of the last pass, with wv = w [L, e] and wm = w m,
+ *              m = [D phi0, phi0, D phi1, phi1, D phi2, phi2, D phi3, phi3]: A = sum wv_i L_j (21, upper triangle, row-major),
+ *              b = sum wv_i e (6), c = sum wv_e e, B = sum wv_i m_k (6 x 8, row-major), C = sum wm_k m_l (36, upper triangle,
+ *              row-major), d = sum wm_k e (8)
+ *   p_info     int32 [n_pairs][8] or NULL: the robust law's
+ * An EDGE in the lighting (a cast shadow) is what the tile law is for and this one is not (DESIGN.md 5o has the numbers).  The same
+ * bits from call to call and for a pair alone or at any place of a batch (integer atomics only).  3 N + 2 launches on `stream`, no
+ * host round trip, capturable; the handle's first call allocates the law's own blocks (32 MiB of segment partials = 4096 segment
+ * rows x 8 cell columns x 128 doubles, a 16 KiB histogram and a state per pair of max_pairs, and the host form's staging) and
+ * synchronises the device: make it outside any stream capture.  It shares nothing with the other laws or the velocity path; one
+ * call in flight per handle.  Returns 0, -1 (null), -2 (what the robust law refuses; cells_y or cells_x outside 1 .. 8 or above
+ * the pooled side).  No counterpart in the reference. */
+VITVS_API int vitvs_photometric_surface_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                                     int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                     const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                                     int32_t cells_y, int32_t cells_x, int32_t robust_iterations, double sigma_min,
+                                                     double* v_p, int32_t* p_status, double* p_robust, double* p_nodes,
+                                                     double* cell_sums, int32_t* p_info, void* stream);
+/* The host-pointer form: every pointer is host memory; synchronous; ordered behind the handle's pending _dev work. */
+VITVS_API int vitvs_photometric_surface_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des,
+                                                 int32_t height, int32_t width, const uint16_t* Z_mm, double depth_scale,
+                                                 const double* K, int32_t level, int32_t interaction, double mu, double lambda,
+                                                 int32_t cells_y, int32_t cells_x, int32_t robust_iterations, double sigma_min,
+                                                 double* v_p, int32_t* p_status, double* p_robust, double* p_nodes, double* cell_sums,
+                                                 int32_t* p_info);
 /* The launch plan of the photometric law as host arithmetic, for one pair (no handle, no device).  It is declared here, beside the
  * calls it plans, and not among the operator hooks of include/vitvs_ops.h: out int32 [8] = the
  * pooled h = height >> level and w = width >> level, the pooled rows per band max(1, min((2048 >> level) / w, h / 256)), the bands
@@ -734,6 +778,12 @@ VITVS_API int vitvs_op_photometric_plan(int32_t height, int32_t width, int32_t l
  * vitvs_op_photometric_plan refuses; tiles_y or tiles_x outside 1 .. 8 or above the pooled side; out is zeros). */
 VITVS_API int vitvs_op_photometric_tile_plan(int32_t height, int32_t width, int32_t level, int32_t tiles_y, int32_t tiles_x,
                                              int32_t* out);
+/* The surface law's plan, likewise: the tile plan's out [0 .. 7) with cells in the place of tiles (the bands, the slots and both
+ * LDS sizes are the tile law's), and out [7] = the workspace doubles per pair bands x slots x cells_x x 128: the partial of (band,
+ * slot, cell column) is 128 doubles (the 120 sums, sum w, the counts) at ((band slots + slot) cells_x + cell column) 128.  Returns
+ * what vitvs_op_photometric_tile_plan returns. */
+VITVS_API int vitvs_op_photometric_surface_plan(int32_t height, int32_t width, int32_t level, int32_t cells_y, int32_t cells_x,
+                                                int32_t* out);
 
 /* --- several updates in flight ------------------------------------------------------------------
  * One update at one frame pair is a chain of 86 dependent launches; each pays the device's launch-to-launch floor and its own

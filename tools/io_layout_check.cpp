@@ -150,6 +150,20 @@ int main() {
                                                           ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
                    "photometric tile: %zu %zu", P, px_max);
         }
+        // the surface form: the 120 sums per cell and the lighting per node, 64 cells and 82 nodes reserved per pair
+        for (size_t g : {(size_t)1, (size_t)3, (size_t)8}) {
+            const size_t T = g * g, Q = (g + 1) * (g + 1);
+            PhotometricSurfaceIo ps = photometric_surface_io(P, px_max * 3, px_max, n, T, Q, px * 3, px, &d, &b16, &b8, &b8, &d, &i, &d, &d, &d, &i);
+            check("photometric surface", io_list(ps), P, px_max, n);
+            PhotometricSurfaceIo ps0 = photometric_surface_io(P, px_max * 3, px_max);
+            EXPECT(io_place(io_list(ps0), nullptr) == io_place(io_list(ps), nullptr), "photometric surface: allocation and call disagree");
+            EXPECT(ps.Z.count == n * px && ps.I_cur.count == n * px * 3 && ps.I_des.count == n * px * 3 &&
+                       ps.cell_sums.count == n * T * 120 && ps.p_nodes.count == n * Q * 4 && ps.p_robust.count == n * 4,
+                   "photometric surface: counts");
+            EXPECT(io_place(io_list(ps0), nullptr) == P * (4 + 6 + 64 * 120 + 82 * 4 + 4) * 8 + (((P + 3) & ~(size_t)3) + P * 8) * 4 +
+                                                          ((P * px_max + 7) & ~(size_t)7) * 2 + 2 * ((P * px_max * 3 + 15) & ~(size_t)15),
+                   "photometric surface: %zu %zu", P, px_max);
+        }
     }
     if (failures) printf("io_layout_check: %d FAILED\n", failures);
     else printf("io_layout_check: ok\n");

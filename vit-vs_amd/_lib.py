@@ -94,6 +94,10 @@ PROTOTYPES = {
                                                  C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_photometric_tile_velocity": (_I, [_P, _I, _P, _P, _I, _I, _P, C.c_double, _P, _I, _I, C.c_double, C.c_double, _I, _I, _I,
                                              C.c_double, _P, _P, _P, _P, _P, _P]),
+    "vitvs_photometric_surface_velocity_dev": (_I, [_P, _I, _P, _P, _I, _I, _P, C.c_double, _P, _I, _I, C.c_double, C.c_double, _I, _I,
+                                                    _I, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "vitvs_photometric_surface_velocity": (_I, [_P, _I, _P, _P, _I, _I, _P, C.c_double, _P, _I, _I, C.c_double, C.c_double, _I, _I, _I,
+                                                C.c_double, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_details": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_last_weights": (_I, [_P, _I, _P]),
     "vitvs_set_option": (_I, [_P, C.c_char_p, C.c_int64]),
@@ -161,6 +165,7 @@ PROTOTYPES = {
     "vitvs_op_roll_pick": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vitvs_op_photometric_plan": (_I, [_I, _I, _I, _P]),
     "vitvs_op_photometric_tile_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "vitvs_op_photometric_surface_plan": (_I, [_I, _I, _I, _I, _I, _P]),
 }
 
 

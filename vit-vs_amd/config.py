@@ -235,6 +235,10 @@ class ServoParams:
     photometric_handback_rejected: float = 0.0  # a share in (0, 1]: a robust, tile or rig photometric call that leaves more than
                                                 # this share of its rows at weight 0 hands back to the ViT update, as a status
                                                 # that is not OK does; needs photometric_robust_iterations > 0.  0 = off
+    photometric_surface: Optional[tuple] = None # (cells_y, cells_x), each 1 .. 8: a SMOOTH lighting model, a bilinear spline of gains
+                                                # and biases on the nodes of that grid (Engine.photometric_surface_velocity, DESIGN.md
+                                                # 5o); needs photometric_illumination, and excludes photometric_tiles.  None = off:
+                                                # the hand-over calls exactly what it calls without this field
 
     def __post_init__(self):
         if not isinstance(self.photometric_illumination, bool):
@@ -254,6 +258,20 @@ class ServoParams:
         if t != (1, 1) and not self.photometric_illumination:
             raise ValueError("photometric_tiles other than (1, 1) needs photometric_illumination=True: the tiles are the grid of the "
                              "lighting model, and a grid without a lighting model means nothing")
+        sf = self.photometric_surface
+        if isinstance(sf, list):
+            sf = tuple(sf)                                                        # a YAML sequence
+            object.__setattr__(self, "photometric_surface", sf)
+        if sf is not None:
+            if not (isinstance(sf, tuple) and len(sf) == 2
+                    and all(isinstance(g, int) and not isinstance(g, bool) and 1 <= g <= 8 for g in sf)):
+                raise ValueError(f"photometric_surface is None (off) or (cells_y, cells_x), each 1 .. 8, got {self.photometric_surface!r}")
+            if not self.photometric_illumination:
+                raise ValueError("photometric_surface needs photometric_illumination=True: the cells are the grid of the lighting "
+                                 "model, and a grid without a lighting model means nothing")
+            if t != (1, 1):
+                raise ValueError("photometric_surface and photometric_tiles exclude each other: the hand-over calls ONE lighting model, "
+                                 "the surface for smooth fields or the tiles for edges; both together are not built")
         hb = self.photometric_handback_rejected
         if isinstance(hb, bool) or not isinstance(hb, (int, float)) or not (math.isfinite(float(hb)) and 0.0 <= float(hb) <= 1.0):
             raise ValueError(f"photometric_handback_rejected is 0 (off) or a share in (0, 1], got {hb!r}")
@@ -366,7 +384,8 @@ def load_reference_config(source) -> ReferenceConfig:
     ``photometric_mu``, ``photometric_lambda`` and ``photometric_interaction`` (the hand-over to the photometric law) likewise, else
     0.0 (off), 2, 0.01, None and "desired"; ``photometric_illumination``, ``photometric_robust_iterations`` and
     ``photometric_sigma_min`` (its robust form) likewise, else False, 0 and 1.0; ``photometric_tiles`` (its tile form, a sequence of
-    two) and ``photometric_handback_rejected`` likewise, else (1, 1) and 0.0."""
+    two) and ``photometric_handback_rejected`` likewise, else (1, 1) and 0.0; ``photometric_surface`` (its surface form, a sequence of
+    two) likewise, else None."""
     if isinstance(source, dict):
         cfg = dict(source)
     else:
@@ -403,7 +422,8 @@ def load_reference_config(source) -> ReferenceConfig:
                         photometric_robust_iterations=cfg.get("photometric_robust_iterations", 0),
                         photometric_sigma_min=cfg.get("photometric_sigma_min", 1.0),
                         photometric_tiles=cfg.get("photometric_tiles", (1, 1)),
-                        photometric_handback_rejected=cfg.get("photometric_handback_rejected", 0.0))
+                        photometric_handback_rejected=cfg.get("photometric_handback_rejected", 0.0),
+                        photometric_surface=cfg.get("photometric_surface", None))
     used = {"roll_search","u_max", "v_max", "f_x", "f_y", "lambda_", "num_pairs", "dino_input_size", "use_feature_binning", "ema_alpha",
             "max_velocity", "max_iterations", "max_velocity_vector_history", "image_path", "robust_iterations",
             "subpatch", "interaction", "rig_robust_iterations", "law", "pose_robust_iterations",
@@ -411,7 +431,7 @@ def load_reference_config(source) -> ReferenceConfig:
             "homography_consensus", "homography_consensus_seed", "select_cells", "pose_consensus", "pose_consensus_seed",
             "photometric_handover", "photometric_level", "photometric_mu", "photometric_lambda", "photometric_interaction",
             "photometric_illumination", "photometric_robust_iterations", "photometric_sigma_min", "photometric_tiles",
-            "photometric_handback_rejected"}
+            "photometric_handback_rejected", "photometric_surface"}
     extras = {k: v for k, v in cfg.items() if k not in used}
     extras.setdefault("background_thresh", 0.5)
     return ReferenceConfig(servo=servo, max_iterations=int(cfg["max_iterations"]),

@@ -150,6 +150,9 @@ struct vitvs_handle {
     // the tile form (vitvs_photometric_tile_velocity[_dev]) shares nothing with them: photo_tile_ws = the 48-double segment partials,
     // one histogram and one state per pair (photometric_tile_ws_bytes), photo_tile_io = PhotometricTileIo
     unsigned char *photo_tile_ws = nullptr, *photo_tile_io = nullptr;
+    // the surface form (vitvs_photometric_surface_velocity[_dev]) likewise: photo_surface_ws = the 128-double segment partials, one
+    // histogram and one state per pair (photometric_surface_ws_bytes), photo_surface_io = PhotometricSurfaceIo
+    unsigned char *photo_surface_ws = nullptr, *photo_surface_io = nullptr;
     // the last law evaluation, eager or replayed (note_law); its plan says which of Wws, off_ws and zgoal_ws it wrote
     int last_pairs = 0, last_T = 0;
     ServoPlan last_law;
@@ -2348,6 +2351,77 @@ int vitvs_photometric_tile_velocity(vitvs_handle* h, int32_t n_pairs, const uint
     });
 }
 
+// --- the surface photometric law ------------------------------------------------------------------
+// Everything the robust law refuses (the lighting model is always on), and the cell grid; the first call allocates the law's own
+// two blocks (the 128-double segment partials at 4096 segment rows of 8 cell columns = 32 MiB, a histogram and a state per pair of
+// max_pairs; PhotometricSurfaceIo at 64 cells and 82 nodes per pair), zeroed, so no later call allocates.
+static int photometric_surface_prepare(vitvs_handle* h, int n_pairs, int height, int width, int level, int interaction,
+                                       double depth_scale, double mu, double lambda, int cells_y, int cells_x, int robust_iterations,
+                                       double sigma_min, bool host_form) {
+    if (int rc = photometric_check(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, host_form)) return rc;
+    if (cells_y < 1 || cells_y > 8 || cells_x < 1 || cells_x > 8) return set_err(h, -2, "cells_y and cells_x are 1 .. 8");
+    if (cells_y > (height >> level) || cells_x > (width >> level))
+        return set_err(h, -2, "cells_y and cells_x are at most the pooled image's sides");
+    if (robust_iterations < 0 || robust_iterations > 4) return set_err(h, -2, "robust_iterations is 0 .. 4");
+    if (!std::isfinite(sigma_min) || !(sigma_min > 0.0)) return set_err(h, -2, "sigma_min is finite and > 0");
+    const vitvs_config& c = h->cfg;
+    PhotometricSurfacePlan pl;
+    if (int rc = plan_photometric_surface(height, width, level, cells_y, cells_x, c.max_pairs, &pl))
+        return set_err(h, rc, "no surface photometric plan");
+    const size_t px_max = (size_t)c.u_max * c.v_max;
+    PhotometricSurfaceIo io = photometric_surface_io(c.max_pairs, px_max * 3, px_max);
+    return law_blocks(h, "surface photometric", &h->photo_surface_ws, photometric_surface_ws_bytes(c.max_pairs), &h->photo_surface_io,
+                      io_place(io_list(io), nullptr));
+}
+
+int vitvs_photometric_surface_velocity_dev(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                           int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                           int32_t interaction, double mu, double lambda, int32_t cells_y, int32_t cells_x,
+                                           int32_t robust_iterations, double sigma_min, double* v_p, int32_t* p_status, double* p_robust,
+                                           double* p_nodes, double* cell_sums, int32_t* p_info, void* stream) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust || !p_nodes) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_surface_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, cells_y, cells_x,
+                                             robust_iterations, sigma_min, false))
+        return rc;
+    PhotometricSurfaceArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    PhotometricRobustArgs& ra = sa.r;
+    PhotometricArgs& a = ra.p;
+    a.n_pairs = n_pairs; a.height = height; a.width = width; a.level = level; a.interaction = interaction;
+    a.I_cur = I_cur; a.I_des = I_des; a.Z_mm = Z_mm; a.depth_scale = depth_scale; a.K = K; a.mu = mu; a.lambda = lambda;
+    a.v_p = v_p; a.p_status = p_status; a.p_info = p_info;
+    ra.illumination = 1; ra.iterations = robust_iterations; ra.sigma_min = sigma_min;
+    ra.p_robust = p_robust;
+    sa.cells_y = cells_y; sa.cells_x = cells_x; sa.p_nodes = p_nodes; sa.cell_sums = cell_sums;
+    const int rc = launch_photometric_surface(sa, h->photo_surface_ws, h->cfg.max_pairs, dev_stream(h, stream));
+    return rc ? set_err(h, rc, "surface photometric law launch failed") : 0;
+}
+
+int vitvs_photometric_surface_velocity(vitvs_handle* h, int32_t n_pairs, const uint8_t* I_cur, const uint8_t* I_des, int32_t height,
+                                       int32_t width, const uint16_t* Z_mm, double depth_scale, const double* K, int32_t level,
+                                       int32_t interaction, double mu, double lambda, int32_t cells_y, int32_t cells_x,
+                                       int32_t robust_iterations, double sigma_min, double* v_p, int32_t* p_status, double* p_robust,
+                                       double* p_nodes, double* cell_sums, int32_t* p_info) {
+    if (!h || !I_cur || !I_des || !K || !v_p || !p_status || !p_robust || !p_nodes) return set_err(h, -1, "null argument");
+    DeviceScope dev(h);
+    if (int rc = photometric_surface_prepare(h, n_pairs, height, width, level, interaction, depth_scale, mu, lambda, cells_y, cells_x,
+                                             robust_iterations, sigma_min, true))
+        return rc;
+    const vitvs_config& c = h->cfg;
+    const size_t px_max = (size_t)c.u_max * c.v_max, px = (size_t)height * width, T = (size_t)cells_y * cells_x;
+    const size_t Q = (size_t)(cells_y + 1) * (cells_x + 1);
+    PhotometricSurfaceIo io = photometric_surface_io(c.max_pairs, px_max * 3, px_max, n_pairs, T, Q, px * 3, px, K, Z_mm, I_cur, I_des,
+                                                     v_p, p_status, p_robust, p_nodes, cell_sums, p_info);
+    return host_call(h, io_list(io), h->photo_surface_io, [&](hipStream_t st) {
+        return vitvs_photometric_surface_velocity_dev(h, n_pairs, io.I_cur.dev, io.I_des.dev, height, width,
+                                                      Z_mm ? reinterpret_cast<const uint16_t*>(io.Z.dev) : nullptr, depth_scale,
+                                                      io.K.f64(), level, interaction, mu, lambda, cells_y, cells_x, robust_iterations,
+                                                      sigma_min, io.v_p.f64(), io.p_status.i32(), io.p_robust.f64(), io.p_nodes.f64(),
+                                                      cell_sums ? io.cell_sums.f64() : nullptr, p_info ? io.p_info.i32() : nullptr, st);
+    });
+}
+
 int vitvs_last_goal_depth(vitvs_handle* h, int32_t n_pairs, double* z) {
     if (!h || !z) return set_err(h, -1, "null argument");
     return last_row_output(h, n_pairs, h->last_law.goalz, h->zgoal_ws, 1, z);
@@ -2672,6 +2746,17 @@ int vitvs_op_photometric_tile_plan(int32_t height, int32_t width, int32_t level,
     if (rc) memset(&pl, 0, sizeof(pl));
     out[0] = pl.h; out[1] = pl.w; out[2] = pl.rows; out[3] = pl.bands; out[4] = pl.slots; out[5] = (int32_t)pl.lds;
     out[6] = (int32_t)pl.lds_res; out[7] = (int32_t)pl.ws_doubles;
+    return rc;
+}
+
+int vitvs_op_photometric_surface_plan(int32_t height, int32_t width, int32_t level, int32_t cells_y, int32_t cells_x, int32_t* out) {
+    if (!out) return -1;
+    PhotometricSurfacePlan pl;
+    memset(&pl, 0, sizeof(pl));
+    const int rc = plan_photometric_surface(height, width, level, cells_y, cells_x, 1, &pl);
+    if (rc) memset(&pl, 0, sizeof(pl));
+    out[0] = pl.t.h; out[1] = pl.t.w; out[2] = pl.t.rows; out[3] = pl.t.bands; out[4] = pl.t.slots; out[5] = (int32_t)pl.t.lds;
+    out[6] = (int32_t)pl.t.lds_res; out[7] = (int32_t)pl.ws_doubles;
     return rc;
 }
 

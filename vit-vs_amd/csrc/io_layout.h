@@ -187,4 +187,23 @@ inline PhotometricTileIo photometric_tile_io(size_t P, size_t frame_max, size_t 
                              io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur), io_in(1, f_cap, n * frame, I_des)};
 }
 
+// the surface photometric law (vitvs_photometric_surface_velocity): PhotometricTileIo with the 120 sums per cell and the lighting
+// per node.  T = cells_y * cells_x and Q = (cells_y + 1)(cells_x + 1) of the call; the block reserves 64 cells and 82 nodes (81,
+// kept even) per pair.
+struct PhotometricSurfaceIo {
+    IoField K, v_p, cell_sums, p_nodes, p_robust, p_status, p_info, Z, I_cur, I_des;
+};
+inline PhotometricSurfaceIo photometric_surface_io(size_t P, size_t frame_max, size_t depth_max, size_t n = 0, size_t T = 0, size_t Q = 0,
+                                                   size_t frame = 0, size_t depth = 0, const double* K = nullptr,
+                                                   const uint16_t* Z = nullptr, const uint8_t* I_cur = nullptr,
+                                                   const uint8_t* I_des = nullptr, double* v_p = nullptr, int32_t* p_status = nullptr,
+                                                   double* p_robust = nullptr, double* p_nodes = nullptr, double* cell_sums = nullptr,
+                                                   int32_t* p_info = nullptr) {
+    const size_t st_cap = (P + 3) & ~(size_t)3, z_cap = (P * depth_max + 7) & ~(size_t)7, f_cap = (P * frame_max + 15) & ~(size_t)15;
+    return PhotometricSurfaceIo{io_in(8, P * 4, n * 4, K),          io_out(8, P * 6, n * 6, v_p),
+                                io_out(8, P * 64 * 120, n * T * 120, cell_sums), io_out(8, P * 82 * 4, n * Q * 4, p_nodes),
+                                io_out(8, P * 4, n * 4, p_robust),  io_out(4, st_cap, n, p_status),    io_out(4, P * 8, n * 8, p_info),
+                                io_in(2, z_cap, n * depth, Z),      io_in(1, f_cap, n * frame, I_cur), io_in(1, f_cap, n * frame, I_des)};
+}
+
 }  // namespace vitvs

@@ -723,6 +723,32 @@ int plan_photometric_tiles(int height, int width, int level, int tiles_y, int ti
 size_t photometric_tile_ws_bytes(int max_pairs);
 int launch_photometric_tiles(const PhotometricTileArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
 
+// The surface photometric law: the tile law's sibling for SMOOTH lighting fields, a bilinear spline of gains and
+// biases on the (cells_y + 1)(cells_x + 1) nodes of the tile law's grid (node a = i (cells_x + 1) + j; unknown 2 a = gamma_a,
+// 2 a + 1 = beta_a; M <= 162).  Per cell 120 sums; the cells add in ascending order into one banded node system, eliminated under
+// the pivot rule with the six twist columns as a border; an unknown whose pivot fails is dead in that pass (value 0).  One median
+// over all rows.  3 iterations + 2 launches, no host round trip, in a block of its own of photometric_surface_ws_bytes(max_pairs)
+// bytes (4096 segment rows x 8 cell columns x 128 doubles = 32 MiB per pair, a histogram and a state) that every call must find
+// with its histograms zero.
+constexpr int kPhotoSurfMaxNodes = 81;
+struct PhotometricSurfaceArgs {
+    PhotometricRobustArgs r;  // r.p.ws: [n_pairs][bands][slots][cells_x][128] the segment partials; r.state: [n_pairs][16 + 176]
+                              // r.p_robust [n_pairs][4]: live unknowns, dead unknowns, the last sigma, the final sum of weights
+                              // r.normal45 is not read
+    int cells_y, cells_x;     // 1 .. 8 each, at most the pooled side
+    double* p_nodes;          // [n_pairs][nodes][4] gamma_a, beta_a, gamma_a live (1.0 / 0.0), beta_a live
+    double* cell_sums;        // [n_pairs][cells][120] or null: A (21), b (6), c, B (6 x 8), C (36, upper triangle), d (8) of the last pass
+};
+struct PhotometricSurfacePlan {
+    PhotometricTilePlan t;    // the tile law's bands, slots and LDS (its ws_doubles is the tile law's)
+    size_t ws_doubles;        // per pair: bands x slots x cells_x x 128
+    size_t lds_solve;         // dynamic LDS of the solve launch: 8 (128 cells + 32 M + 296) bytes
+};
+// -2: what plan_photometric_tiles refuses
+int plan_photometric_surface(int height, int width, int level, int cells_y, int cells_x, int max_pairs, PhotometricSurfacePlan* plan);
+size_t photometric_surface_ws_bytes(int max_pairs);
+int launch_photometric_surface(const PhotometricSurfaceArgs& a, unsigned char* ws, int max_pairs, hipStream_t stream);
+
 // out[n_img][T][D] fp32, index d*H + h <- which-th (0 q, 1 k, 2 v) third of qkv[n_img*(P+T)][3][H][64], cls and registers dropped
 // q_unscale: factor that undoes a pre-scaled q third (1 / kAttnQScale for which == 0 in the 16-bit modes, else 1)
 // keep_cls: 0 -> out [n_img][T][D]; 1 -> out [n_img][1 + T][D] (the cls row first, registers dropped)

@@ -1420,4 +1420,541 @@ int launch_photometric_tiles(const PhotometricTileArgs& ta_in, unsigned char* ws
     return 0;
 }
 
+// ---- the surface photometric law ----------------------------------------------------------------------------------
+// The tile law's sibling for SMOOTH lighting fields: a bilinear spline of gains and biases on the (gy + 1)(gx + 1) nodes of the
+// same grid, I_cur ~ (1 + sum phi_a gamma_a) I_des + sum phi_a beta_a over the four nodes of the pixel's cell.  Unknown 2 a = gamma_a,
+// 2 a + 1 = beta_a, node a = i (gx + 1) + j, M = 2 (gy + 1)(gx + 1) <= 162.  Per cell 120 weighted sums (A 21, b 6, c, B 6 x 8, C 36,
+// d 8) and sum w; the cells add in ascending order into the bordered system [[C_g, R^T], [R, S]] (R = B_g and d_g, S = A, b, c),
+// which ONE right-looking banded LDL^T (half-bandwidth 2 gx + 5) eliminates under the pivot rule: what is left of S is H', g'.  An
+// unknown whose pivot fails is DEAD in that pass (column skipped, value 0).  3 N + 2 launches in a block of its own (kernels.h
+// PhotometricSurfaceArgs); the bands, slots and segments are the tile law's (plan_photometric_tiles).
+//   photometric_surface_rows_kernel<WEIGHTED>   the tile rows kernel's mapping; a wave walks its segment of the LDS-resident band
+//                                               TWICE (A, b, c, C, d, sum w: 73 accumulators; then B: 48), so that no pass holds
+//                                               all 121 in registers; one 128-double partial per segment
+//   photometric_surface_residual_kernel         the tile law's, the pixel's four node pairs interpolated
+//   photometric_surface_solve_kernel            one workgroup of 8 waves per pair: wave v adds the bands of cells v, v + 8, ..; the
+//                                               node system gathered into LDS (every entry over its <= 4 cells in ascending order);
+//                                               per column 231 + 147 + 28 independent updates behind one barrier; wave 0 solves the
+//                                               6 x 6 system and back-substitutes
+// The workspace: 4096 segment rows x 8 cell columns x 128 doubles = 32 MiB per pair of max_pairs, a histogram and a state.
+constexpr int kPhotoSurfPart = 128;       // doubles per partial: the 120 sums, sum w, (int32 rows, holes), (int32 zero weights, 0), 5 unused
+constexpr int kPhotoSurfState = 16 + 176; // doubles per pair: the robust law's 16 (gamma, beta unused), then the M unknowns
+constexpr int kPhotoSurfBand = 22;        // LDS doubles per column of C_g: the diagonal and the 21 entries below it
+constexpr int kPhotoSurfSolveThreads = 512;
+constexpr int kPhotoSurfDepth = 8;        // band partials a wave holds in flight per cell
+
+// the bilinear weights of pooled pixel (r, c) in cell (ty, tx): exact integer numerators, one division each
+__device__ __forceinline__ void surface_phi(int r, int c, int ty, int tx, int gy, int gx, int h, int w, double (&phi)[4]) {
+    const double v = (double)(r * gy - ty * h) / (double)h, u = (double)(c * gx - tx * w) / (double)w;
+    const double v1 = 1.0 - v, u1 = 1.0 - u;
+    phi[0] = v1 * u1;
+    phi[1] = v1 * u;
+    phi[2] = v * u1;
+    phi[3] = v * u;
+}
+
+// (gamma, beta) at a pixel: the phi-sums over the cell's four node pairs nd = (gamma, beta) x 4, in node order
+__device__ __forceinline__ void surface_lighting(const double (&phi)[4], const double (&nd)[8], double& gamma, double& beta) {
+    gamma = phi[0] * nd[0];
+    beta = phi[0] * nd[1];
+#pragma unroll
+    for (int s = 1; s < 4; ++s) {
+        gamma = gamma + phi[s] * nd[2 * s];
+        beta = beta + phi[s] * nd[2 * s + 1];
+    }
+}
+
+// the four node pairs of cell (ty, tx) from the pair's state block
+__device__ __forceinline__ void surface_nodes(const double* state, int ty, int tx, int gx, double (&nd)[8]) {
+    const int a0 = ty * (gx + 1) + tx;
+    const int at[4] = {a0, a0 + 1, a0 + gx + 1, a0 + gx + 2};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        nd[2 * s] = state[16 + 2 * at[s]];
+        nd[2 * s + 1] = state[17 + 2 * at[s]];
+    }
+}
+
+// lane (pos mod 64) keeps the wave-uniform t in its half pos / 64 of the partial
+__device__ __forceinline__ void surface_keep(double t, int pos, int lane, double& lo, double& hi) {
+    if (lane == (pos & 63)) {
+        if (pos < 64) lo = t;
+        else hi = t;
+    }
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void photometric_surface_rows_kernel(PhotometricSurfaceArgs sa, int h, int w, int rows, int bands,
+                                                                       int slots) {
+    extern __shared__ double photo_lds[];
+    const PhotometricRobustArgs& ra = sa.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int band = blockIdx.x, pair = blockIdx.y;
+    const int gy = sa.cells_y, gx = sa.cells_x;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    int* scan = reinterpret_cast<int*>(photo_lds);      // the tile law's layout: 4 x 48 doubles, here only the histogram's scan
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    double* state = ra.state + (size_t)pair * kPhotoSurfState;
+    double st[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double scale = 1.0;                                 // kTukeyC * sigma
+    if constexpr (WEIGHTED) {
+        const int32_t* si = reinterpret_cast<const int32_t*>(state + 9);
+        if (si[1]) return;                              // a solve before this one failed: the call's answer is written
+#pragma unroll
+        for (int i = 0; i < 6; ++i) st[i] = state[i];
+        const int bin = photo_median_bin(ra.hist + (size_t)pair * kPhotoBins, (si[0] + 1) / 2, scan, tid);
+        const double median = ((double)bin + 0.5) / 16.0;
+        const double sigma = fmax(kMadScale * median, ra.sigma_min);
+        scale = kTukeyC * sigma;
+        if (band == 0 && tid == 0) { state[8] = sigma; reinterpret_cast<int32_t*>(state + 10)[0] = bin; }
+    }
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    const int ty0 = r0 * gy / h;                        // slot s of the band is cell row ty0 + s
+    for (int seg = wave; seg < slots * gx; seg += 4) {
+        const int slot = seg / gx, tx = seg - slot * gx, ty = ty0 + slot;
+        if (ty >= gy) continue;
+        const int ra0 = max(r0, tile_begin(ty, h, gy)), ra1 = min(r1, tile_begin(ty + 1, h, gy));
+        if (ra1 <= ra0) continue;                       // the band does not cross into that cell row: the slot is not read either
+        const int c0 = tile_begin(tx, w, gx), sw = tile_begin(tx + 1, w, gx) - c0;
+        double nd[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if constexpr (WEIGHTED) surface_nodes(state, ty, tx, gx, nd);
+        double lo = 0.0, hi = 0.0;                      // lane q: sums q and 64 + q of the partial
+        // the first walk: A (21), b (6), c, then C (36), d (8), sum w
+        {
+            double acc[73];
+#pragma unroll
+            for (int q = 0; q < 73; ++q) acc[q] = 0.0;
+            int n = 0, holes = 0, zeros = 0;
+            for (int idx = lane; idx < (ra1 - ra0) * sw; idx += 64) {
+                const int q0 = idx / sw, c = c0 + (idx - q0 * sw), r = ra0 + q0, lr = r - r0;
+                double L[6], e, D;
+                const int kind = photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D);
+                if (kind == 2) ++holes;
+                if (kind != 0) continue;
+                double phi[4];
+                surface_phi(r, c, ty, tx, gy, gx, h, w, phi);
+                double wt = 1.0;
+                if constexpr (WEIGHTED) {
+                    surface_lighting(phi, nd, st[6], st[7]);
+                    const double t = photo_rho(L, e, D, st) / scale;
+                    const double u = 1.0 - t * t;
+                    wt = t < 1.0 ? u * u : 0.0;
+                    if (wt == 0.0) ++zeros;
+                }
+                double wv[7], m[8], wm[8];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) wv[i] = wt * L[i];
+                wv[6] = wt * e;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) { m[2 * s] = D * phi[s]; m[2 * s + 1] = phi[s]; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) wm[k] = wt * m[k];
+                int q = 0;
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+#pragma unroll
+                    for (int j = i; j < 6; ++j) { acc[q] += wv[i] * L[j]; ++q; }
+#pragma unroll
+                for (int i = 0; i < 7; ++i) acc[21 + i] += wv[i] * e;
+                q = 28;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+#pragma unroll
+                    for (int l = k; l < 8; ++l) { acc[q] += wm[k] * m[l]; ++q; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[64 + k] += wm[k] * e;
+                acc[72] += wt;
+                ++n;
+            }
+#pragma unroll
+            for (int q = 0; q < 28; ++q) surface_keep(wave_sum(acc[q]), q, lane, lo, hi);
+#pragma unroll
+            for (int q = 28; q < 72; ++q) surface_keep(wave_sum(acc[q]), 48 + q, lane, lo, hi);      // C at 76, d at 112
+            surface_keep(wave_sum(acc[72]), 120, lane, lo, hi);
+            n = wave_sum(n);
+            holes = wave_sum(holes);
+            zeros = wave_sum(zeros);
+            if (lane == 57) hi = __builtin_bit_cast(double, ((unsigned long long)(unsigned)holes << 32) | (unsigned)n);
+            if (lane == 58) hi = __builtin_bit_cast(double, (unsigned long long)(unsigned)zeros);
+        }
+        // the second walk: B (6 x 8), the same rows and the same weights
+        {
+            double acc[48];
+#pragma unroll
+            for (int q = 0; q < 48; ++q) acc[q] = 0.0;
+            for (int idx = lane; idx < (ra1 - ra0) * sw; idx += 64) {
+                const int q0 = idx / sw, c = c0 + (idx - q0 * sw), r = ra0 + q0, lr = r - r0;
+                double L[6], e, D;
+                if (photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D) != 0) continue;
+                double phi[4];
+                surface_phi(r, c, ty, tx, gy, gx, h, w, phi);
+                double wt = 1.0;
+                if constexpr (WEIGHTED) {
+                    surface_lighting(phi, nd, st[6], st[7]);
+                    const double t = photo_rho(L, e, D, st) / scale;
+                    const double u = 1.0 - t * t;
+                    wt = t < 1.0 ? u * u : 0.0;
+                }
+                double m[8];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) { m[2 * s] = D * phi[s]; m[2 * s + 1] = phi[s]; }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    const double wvi = wt * L[i];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc[8 * i + k] += wvi * m[k];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 48; ++q) surface_keep(wave_sum(acc[q]), 28 + q, lane, lo, hi);
+        }
+        double* part = a.ws + ((((size_t)pair * bands + band) * slots + slot) * gx + tx) * kPhotoSurfPart;
+        part[lane] = lo;
+        part[64 + lane] = hi;
+    }
+}
+
+__global__ __launch_bounds__(256) void photometric_surface_residual_kernel(PhotometricSurfaceArgs sa, int h, int w, int rows, int bands) {
+    extern __shared__ double photo_lds[];
+    const PhotometricRobustArgs& ra = sa.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, band = blockIdx.x, pair = blockIdx.y;
+    const int gy = sa.cells_y, gx = sa.cells_x;
+    const int r0 = band * rows, r1 = min(r0 + rows, h);
+    int* lum_cur = reinterpret_cast<int*>(photo_lds + 4 * kPhotoRPart);          // the rows launch's layout, the histogram behind it
+    int* lum_des = lum_cur + (rows + 2) * w;
+    int* zs = lum_des + (rows + 2) * w;
+    unsigned* bins = reinterpret_cast<unsigned*>(zs + rows * w);
+    const double* state = ra.state + (size_t)pair * kPhotoSurfState;
+    if (reinterpret_cast<const int32_t*>(state + 9)[1]) return;
+    double st[8];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) st[i] = state[i];
+    for (int i = tid; i < kPhotoBins; i += 256) bins[i] = 0u;
+    pool_band(a, pair, h, w, rows, r0, r1, lum_cur, lum_des, zs, tid);          // (its barriers order the zeros above too)
+    const PhotoCamera cam = photo_camera(a.K + (size_t)pair * 4, a.level);
+    const int* grad = a.interaction ? lum_des : lum_cur;
+    const bool have_z = a.Z_mm != nullptr;
+    for (int idx = tid; idx < (r1 - r0) * w; idx += 256) {
+        const int lr = idx / w, c = idx - lr * w, r = r0 + lr;
+        double L[6], e, D;
+        if (photo_row(cam, grad, lum_cur, lum_des, zs, have_z, a.depth_scale, h, w, lr, c, r, L, e, D) != 0) continue;
+        const int ty = r * gy / h, tx = c * gx / w;     // the pixel's cell: its four node pairs, interpolated
+        double phi[4], nd[8];
+        surface_phi(r, c, ty, tx, gy, gx, h, w, phi);
+        surface_nodes(state, ty, tx, gx, nd);
+        surface_lighting(phi, nd, st[6], st[7]);
+        const double rho = photo_rho(L, e, D, st);
+        const int q = rho < (double)(kPhotoBins / 16) ? (int)(16.0 * rho) : kPhotoBins - 1;      // (a NaN: the last bin)
+        atomicAdd(&bins[q], 1u);
+    }
+    __syncthreads();
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;
+    for (int i = tid; i < kPhotoBins; i += 256) {
+        const unsigned cnt = bins[i];
+        if (cnt) atomicAdd(&hist[i], cnt);
+    }
+}
+
+// the LDS doubles of the solve: the cells' partials, C_g's columns, R (7 rows), the original diagonal, 1 / d_j, t / q, S (32),
+// solve_ldlt's 256 and 8 of counts
+__host__ __device__ inline size_t surface_solve_lds_doubles(int gy, int gx) {
+    const size_t T = (size_t)gy * gx, M = 2 * (size_t)(gy + 1) * (gx + 1);
+    return T * kPhotoSurfPart + M * (kPhotoSurfBand + 7 + 3) + 32 + 256 + 8;
+}
+
+__global__ __launch_bounds__(kPhotoSurfSolveThreads) void photometric_surface_solve_kernel(PhotometricSurfaceArgs sa, int h, int w,
+                                                                                            int rows, int bands, int slots,
+                                                                                            int no_depth, int pass) {
+    extern __shared__ double photo_lds[];
+    const PhotometricRobustArgs& ra = sa.r;
+    const PhotometricArgs& a = ra.p;
+    const int tid = threadIdx.x, lane = tid & 63, pair = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int gy = sa.cells_y, gx = sa.cells_x, T = gy * gx, nodes = (gy + 1) * (gx + 1), M = 2 * nodes, bw = 2 * gx + 5;
+    double* cs = photo_lds;                             // [T][128]
+    double* Cc = cs + (size_t)T * kPhotoSurfPart;       // [M][22]: column j = C_jj, C_{j+1, j} .. C_{j+21, j}
+    double* R = Cc + (size_t)M * kPhotoSurfBand;        // [7][M]: B_g's six rows, d_g
+    double* diag0 = R + 7 * M;                          // [M] the assembled diagonal
+    double* dinv = diag0 + M;                           // [M] 1 / d_j, 0 for a dead unknown
+    double* tq = dinv + M;                              // [M] t, then q
+    double* S = tq + M;                                 // [32]: H' (21), g' (6), c', sum w
+    double* Gs = S + 32;                                // [256] solve_ldlt's
+    int* cnt = reinterpret_cast<int*>(Gs + 256);        // rows, holes, zero weights, live unknowns
+    unsigned* hist = ra.hist + (size_t)pair * kPhotoBins;                         // as photometric_robust_solve_kernel clears it
+    for (int i = tid; i < kPhotoBins; i += kPhotoSurfSolveThreads) hist[i] = 0u;
+    double* state = ra.state + (size_t)pair * kPhotoSurfState;
+    int32_t* si = reinterpret_cast<int32_t*>(state + 9);
+    if (pass > 0 && si[1]) return;
+    for (int i = tid; i < 256; i += kPhotoSurfSolveThreads) Gs[i] = 0.0;
+    // 1. every cell's bands in ascending order
+    const double* pair_ws = a.ws + (size_t)pair * bands * slots * gx * kPhotoSurfPart;
+    for (int k = wave; k < T; k += kPhotoSurfSolveThreads / 64) {
+        const int ty = k / gx, tx = k - ty * gx;
+        const int tr0 = tile_begin(ty, h, gy), tr1 = tile_begin(ty + 1, h, gy);
+        const int b0 = tr0 / rows, b1 = no_depth ? b0 : (tr1 - 1) / rows + 1;
+        double lo = 0.0, hi = 0.0;                      // lane q: sums q and 64 + q; lanes 57, 58 of hi: the counts
+        int cnt0 = 0, cnt1 = 0;
+        for (int b = b0; b < b1; b += kPhotoSurfDepth) {
+            double hl[kPhotoSurfDepth], hh[kPhotoSurfDepth];
+#pragma unroll
+            for (int u = 0; u < kPhotoSurfDepth; ++u) {
+                const int bb = min(b + u, b1 - 1);
+                const int slot = (slots > 1 && bb * rows < tr0) ? 1 : 0;      // the band began in the cell row before: its second slot
+                const double* p = pair_ws + ((size_t)(bb * slots + slot) * gx + tx) * kPhotoSurfPart;
+                hl[u] = b + u < b1 ? p[lane] : 0.0;
+                hh[u] = b + u < b1 ? p[64 + lane] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < kPhotoSurfDepth; ++u) {
+                if (b + u >= b1) break;
+                lo += hl[u];                            // ascending band order
+                if (lane < 57) {
+                    hi += hh[u];
+                } else {
+                    const unsigned long long bits = __builtin_bit_cast(unsigned long long, hh[u]);
+                    cnt0 += (int)(unsigned)bits;
+                    cnt1 += (int)(unsigned)(bits >> 32);
+                }
+            }
+        }
+        double* ck = cs + (size_t)k * kPhotoSurfPart;
+        ck[lane] = lo;
+        if (lane < 57) ck[64 + lane] = hi;
+        else if (lane == 57) { int32_t* c = reinterpret_cast<int32_t*>(ck + 121); c[0] = cnt0; c[1] = cnt1; }
+        else if (lane == 58) { int32_t* c = reinterpret_cast<int32_t*>(ck + 122); c[0] = cnt0; c[1] = 0; }
+        if (sa.cell_sums) {
+            double* out = sa.cell_sums + ((size_t)pair * T + k) * 120;
+            out[lane] = lo;
+            if (lane < 56) out[64 + lane] = hi;
+        }
+    }
+    __syncthreads();
+    // 2. the bordered system, every entry over its cells in ascending order from zero
+    if (tid < 29) {
+        const int q = tid < 28 ? tid : 120;
+        double t = 0.0;
+        for (int k = 0; k < T; ++k) t = t + cs[(size_t)k * kPhotoSurfPart + q];
+        S[tid] = t;
+    } else if (tid >= 32 && tid < 35) {
+        int t = 0;
+        for (int k = 0; k < T; ++k) t += reinterpret_cast<const int32_t*>(cs + (size_t)k * kPhotoSurfPart + 121)[tid - 32];
+        cnt[tid - 32] = t;
+    }
+    for (int at = tid; at < M * kPhotoSurfBand; at += kPhotoSurfSolveThreads) {
+        const int p = at / kPhotoSurfBand, o = at - p * kPhotoSurfBand, q = p + o;
+        double t = 0.0;
+        if (q < M && o <= bw) {
+            const int na = p >> 1, nb = q >> 1;
+            const int ia = na / (gx + 1), ja = na - ia * (gx + 1), ib = nb / (gx + 1), jb = nb - ib * (gx + 1);
+            for (int ci = max(ib - 1, 0); ci <= min(ia, gy - 1); ++ci)
+                for (int cj = max(max(ja, jb) - 1, 0); cj <= min(min(ja, jb), gx - 1); ++cj) {
+                    const int s = 2 * ((ia - ci) * 2 + (ja - cj)) + (p & 1), u = 2 * ((ib - ci) * 2 + (jb - cj)) + (q & 1);
+                    t = t + cs[(size_t)(ci * gx + cj) * kPhotoSurfPart + 76 + s * 8 - s * (s - 1) / 2 + (u - s)];
+                }
+        }
+        Cc[at] = t;
+        if (o == 0) { diag0[p] = t; dinv[p] = 0.0; tq[p] = 0.0; }
+    }
+    for (int at = tid; at < 7 * M; at += kPhotoSurfSolveThreads) {
+        const int r = at / M, p = at - r * M, na = p >> 1;
+        const int ia = na / (gx + 1), ja = na - ia * (gx + 1);
+        double t = 0.0;
+        for (int ci = max(ia - 1, 0); ci <= min(ia, gy - 1); ++ci)
+            for (int cj = max(ja - 1, 0); cj <= min(ja, gx - 1); ++cj) {
+                const int s = 2 * ((ia - ci) * 2 + (ja - cj)) + (p & 1);
+                t = t + cs[(size_t)(ci * gx + cj) * kPhotoSurfPart + (r < 6 ? 28 + 8 * r + s : 112 + s)];
+            }
+        R[at] = t;
+    }
+    __syncthreads();
+    const int n = cnt[0], holes = cnt[1], zeros = cnt[2];
+    const bool tried = !no_depth && n >= 6 && n - zeros >= 6;
+    // 3. the elimination, column by column: thread -> one entry behind the column
+    int kind = 3, ua = 0, ub = 0;                       // 0: C (row ua, column ub of the window); 1: R (row ua, column ub); 2: S (ua, ub)
+    {
+        const int nwin = bw * (bw + 1) / 2;
+        if (tid < nwin) {
+            kind = 0;
+            int q = tid;
+            while (q > ua) { q -= ua + 1; ++ua; }       // row ua of the lower triangle has ua + 1 entries
+            ub = q;
+        } else if (tid < nwin + 7 * bw) {
+            kind = 1;
+            ua = (tid - nwin) / bw;
+            ub = (tid - nwin) - ua * bw;
+        } else if (tid < nwin + 7 * bw + 28) {
+            kind = 2;
+            const int q = tid - nwin - 7 * bw;
+            if (q < 21) triu_index(q, ua, ub);
+            else if (q < 27) { ua = q - 21; ub = 6; }
+            else { ua = 6; ub = 6; }
+        }
+    }
+    if (tried) {
+        for (int j = 0; j < M; ++j) {
+            const double d = Cc[j * kPhotoSurfBand], c0 = diag0[j];
+            const bool live = (c0 > 0.0) && (d > kPivotThreshold * c0);
+            if (live) {
+                const double di = 1.0 / d;
+                if (tid == 0) dinv[j] = di;
+                if (kind == 0) {
+                    if (j + 1 + ua < M) {
+                        const double la = Cc[j * kPhotoSurfBand + 1 + ua] * di, lb = Cc[j * kPhotoSurfBand + 1 + ub] * di;
+                        Cc[(j + 1 + ub) * kPhotoSurfBand + (ua - ub)] -= (la * lb) * d;
+                    }
+                } else if (kind == 1) {
+                    if (j + 1 + ub < M) {
+                        const double lr = R[ua * M + j] * di, lb = Cc[j * kPhotoSurfBand + 1 + ub] * di;
+                        R[ua * M + j + 1 + ub] -= (lr * lb) * d;
+                    }
+                } else if (kind == 2) {
+                    const double lr = R[ua * M + j] * di, ls = R[ub * M + j] * di;
+                    const int q = ub < 6 ? ua * 6 - ua * (ua - 1) / 2 + (ub - ua) : (ua < 6 ? 21 + ua : 27);
+                    S[q] -= (lr * ls) * d;
+                }
+            }
+            lds_barrier();
+        }
+    }
+    if (wave != 0) return;
+    // 4. the 6 x 6 system, the unknowns
+    int n_live = 0;
+    for (int j = lane; j < M; j += 64) n_live += dinv[j] != 0.0 ? 1 : 0;
+    n_live = wave_sum(n_live);
+    if (lane < 27) {
+        const double val = S[lane];
+        const bool diag = lane == 0 || lane == 6 || lane == 11 || lane == 15 || lane == 18 || lane == 20;
+        Gs[40 + lane] = diag ? val + a.mu * val : val;
+    }
+    wave_lds_fence();
+    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool solved = false;
+    if (tried && n_live > 0) solved = solve_ldlt(Gs, lane, x);
+    for (int j = lane; j < M; j += 64) {
+        const double di = dinv[j];
+        double t = 0.0;
+        if (solved && di != 0.0) {
+            t = R[6 * M + j] * di;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) t = t + (R[i * M + j] * di) * -x[i];
+        }
+        tq[j] = t;
+    }
+    wave_lds_fence();
+    if (solved) {
+        for (int i = M - 1; i > 0; --i) {               // q_i is final; the live unknowns in front of it lose l_ij q_i
+            const double qi = tq[i];
+            const int j = i - 1 - lane;
+            if (lane < bw && j >= 0) {
+                const double di = dinv[j];
+                if (di != 0.0) tq[j] -= (Cc[j * kPhotoSurfBand + 1 + lane] * di) * qi;
+            }
+            wave_lds_fence();
+        }
+    }
+    for (int j = lane; j < M; j += 64) state[16 + j] = tq[j];
+    for (int nd = lane; nd < nodes; nd += 64) {
+        double* pn = sa.p_nodes + ((size_t)pair * nodes + nd) * 4;
+        pn[0] = tq[2 * nd];
+        pn[1] = tq[2 * nd + 1];
+        pn[2] = (solved && dinv[2 * nd] != 0.0) ? 1.0 : 0.0;
+        pn[3] = (solved && dinv[2 * nd + 1] != 0.0) ? 1.0 : 0.0;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            state[i] = -x[i];
+            a.v_p[(size_t)pair * 6 + i] = solved ? -a.lambda * x[i] : 0.0;
+        }
+        state[6] = 0.0;
+        state[7] = 0.0;
+        si[0] = n;
+        si[1] = solved ? 0 : 1;
+        a.p_status[pair] = no_depth ? ST_NO_DEPTH : solved ? ST_OK : ST_TOO_FEW;
+        if (a.p_info) {
+            int32_t* pi = a.p_info + (size_t)pair * 8;
+            pi[0] = n; pi[1] = h; pi[2] = w; pi[3] = bands; pi[4] = holes; pi[5] = (tried && !solved) ? 1 : 0; pi[6] = zeros; pi[7] = pass;
+        }
+        double* pr = ra.p_robust + (size_t)pair * 4;
+        pr[0] = solved ? (double)n_live : 0.0;
+        pr[1] = solved ? (double)(M - n_live) : 0.0;
+        pr[2] = (solved && pass > 0) ? state[8] : 0.0;
+        pr[3] = solved ? S[28] : 0.0;
+    }
+}
+
+int plan_photometric_surface(int height, int width, int level, int cells_y, int cells_x, int max_pairs, PhotometricSurfacePlan* plan) {
+    if (!plan) return -2;
+    if (int rc = plan_photometric_tiles(height, width, level, cells_y, cells_x, max_pairs, &plan->t)) return rc;
+    plan->ws_doubles = (size_t)plan->t.bands * plan->t.slots * cells_x * kPhotoSurfPart;
+    plan->lds_solve = surface_solve_lds_doubles(cells_y, cells_x) * sizeof(double);
+    return 0;
+}
+
+size_t photometric_surface_ws_bytes(int max_pairs) {
+    return (size_t)max_pairs * ((size_t)kPhotoTileSegs * 8 * kPhotoSurfPart * sizeof(double) + kPhotoBins * sizeof(uint32_t) +
+                                kPhotoSurfState * sizeof(double));
+}
+
+int launch_photometric_surface(const PhotometricSurfaceArgs& sa_in, unsigned char* ws, int max_pairs, hipStream_t stream) {
+    PhotometricSurfaceArgs sa = sa_in;
+    PhotometricRobustArgs& ra = sa.r;
+    PhotometricArgs& a = ra.p;
+    if (a.n_pairs < 1 || a.n_pairs > 65535 || a.n_pairs > max_pairs || !a.I_cur || !a.I_des || !a.K || !ws || !a.v_p || !a.p_status ||
+        !ra.p_robust || !sa.p_nodes)
+        return -2;
+    if (a.interaction < 0 || a.interaction > 1 || !(a.mu >= 0.0) || !(a.mu < __builtin_huge_val())) return -2;
+    if (!(a.lambda == a.lambda) || !(a.depth_scale == a.depth_scale)) return -2;
+    if (ra.iterations < 0 || ra.iterations > 4) return -2;
+    if (!(ra.sigma_min > 0.0) || !(ra.sigma_min < __builtin_huge_val())) return -2;
+    PhotometricSurfacePlan sp;
+    if (int rc = plan_photometric_surface(a.height, a.width, a.level, sa.cells_y, sa.cells_x, a.n_pairs, &sp)) return rc;
+    const PhotometricTilePlan& p = sp.t;
+    ra.illumination = 1;
+    // the block: the partials of max_pairs pairs at kPhotoTileSegs segment rows of 8 cell columns, then the histograms, then the states
+    const size_t part_bytes = (size_t)max_pairs * kPhotoTileSegs * 8 * kPhotoSurfPart * sizeof(double);
+    a.ws = reinterpret_cast<double*>(ws);
+    ra.hist = reinterpret_cast<uint32_t*>(ws + part_bytes);
+    ra.state = reinterpret_cast<double*>(ws + part_bytes + (size_t)max_pairs * kPhotoBins * sizeof(uint32_t));
+    const int no_depth = (!a.Z_mm && !(a.depth_scale > 0.0)) ? 1 : 0;
+    static std::atomic<unsigned long long> raised0{0}, raised1{0}, raised2{0}, raised3{0};
+    if (sp.lds_solve > 64 * 1024 &&
+        raise_lds_limit(reinterpret_cast<const void*>(photometric_surface_solve_kernel), 160 * 1024, raised3))
+        return -3;
+    if (no_depth) {
+        launch(photometric_surface_solve_kernel, dim3(a.n_pairs), dim3(kPhotoSurfSolveThreads), sp.lds_solve, stream, sa, p.h, p.w, p.rows,
+               p.bands, p.slots, 1, 0);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    if (p.lds > 64 * 1024 &&
+        (raise_lds_limit(reinterpret_cast<const void*>(photometric_surface_rows_kernel<false>), 160 * 1024, raised0) ||
+         raise_lds_limit(reinterpret_cast<const void*>(photometric_surface_rows_kernel<true>), 160 * 1024, raised1)))
+        return -3;
+    if (ra.iterations > 0 && p.lds_res > 64 * 1024 &&
+        raise_lds_limit(reinterpret_cast<const void*>(photometric_surface_residual_kernel), 160 * 1024, raised2))
+        return -3;
+    const dim3 grid(p.bands, a.n_pairs);
+    for (int pass = 0; pass <= ra.iterations; ++pass) {
+        if (pass > 0) {
+            launch(photometric_surface_residual_kernel, grid, dim3(256), p.lds_res, stream, sa, p.h, p.w, p.rows, p.bands);
+            launch(photometric_surface_rows_kernel<true>, grid, dim3(256), p.lds, stream, sa, p.h, p.w, p.rows, p.bands, p.slots);
+        } else {
+            launch(photometric_surface_rows_kernel<false>, grid, dim3(256), p.lds, stream, sa, p.h, p.w, p.rows, p.bands, p.slots);
+        }
+        if (hipGetLastError() != hipSuccess) return -1;
+        launch(photometric_surface_solve_kernel, dim3(a.n_pairs), dim3(kPhotoSurfSolveThreads), sp.lds_solve, stream, sa, p.h, p.w, p.rows,
+               p.bands, p.slots, 0, pass);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
+}
+
 }  // namespace vitvs

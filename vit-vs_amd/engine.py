@@ -742,6 +742,78 @@ class Engine:
                     tile_gain=1.0 + t[..., 0], tile_bias=t[..., 1].copy(), tile_weight=t[..., 2].copy(), tile_live=live,
                     live_tiles=robust[:, 0].astype(np.int64), dead_tiles=robust[:, 1].astype(np.int64))
 
+    # ------------------------------------------------------------------ the surface photometric law
+    @staticmethod
+    def _photometric_surface_grid(cells):
+        try:
+            gy, gx = cells
+        except (TypeError, ValueError):
+            raise VitvsError(f"cells is (cells_y, cells_x), got {cells!r}") from None
+        for g in (gy, gx):
+            if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 1 <= int(g) <= 8:
+                raise VitvsError(f"cells is (cells_y, cells_x), each 1 .. 8, got {cells!r}")
+        return int(gy), int(gx)
+
+    def photometric_surface_velocity(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                     lambda_: Optional[float] = None, depth_scale: float = 0.0, cells=(4, 4), robust_iterations: int = 4,
+                                     sigma_min: float = 1.0):
+        """``vitvs_photometric_surface_velocity_dev``: the robust photometric law with a SMOOTH lighting model: a
+        bilinear spline of gains and biases on the (cells_y + 1) x (cells_x + 1) nodes of a ``cells`` = (cells_y, cells_x) grid (each
+        1 .. 8, at most the pooled side) over the pooled image, for a lamp beside the target, vignetting or a window at one side of
+        the room.  The lighting model is always on; the other arguments are ``photometric_robust_velocity``'s.  A node unknown the
+        rows cannot tell from the ones before it (a flat or empty neighbourhood) is dead in that pass and takes the value 0.
+        3 ``robust_iterations`` + 2 launches on the current stream.  Returns ``(v float64 [n, 6] device tensor, info)``:
+        ``photometric_robust_velocity``'s ``info`` without ``gamma`` / ``gain`` / ``bias``, with ``normal`` float64 [n, cells, 120]
+        per cell, ``weight`` the final sum of weights, ``node_gain`` (1 + gamma_a; 1 for a dead unknown), ``node_bias``, each
+        [n, cells_y + 1, cells_x + 1], ``node_live`` (bool, the same shape: gamma_a is live) and ``node_bias_live`` (beta_a is),
+        ``live`` and ``dead`` (unknowns).  An edge in the lighting is the tile law's case, not this one's.  Reading ``info`` synchronises; the engine's
+        first call allocates: make it outside a stream capture."""
+        return self._photometric_surface(False, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, cells,
+                                         robust_iterations, sigma_min)
+
+    def photometric_surface_velocity_host(self, I_cur, I_des, Z, K, level: int = 2, interaction="desired", mu: float = 0.01,
+                                          lambda_: Optional[float] = None, depth_scale: float = 0.0, cells=(4, 4),
+                                          robust_iterations: int = 4, sigma_min: float = 1.0):
+        """``vitvs_photometric_surface_velocity``, the host-pointer form of ``photometric_surface_velocity``: numpy arrays in,
+        ``(v float64 [n, 6], info)`` out, one synchronous C call.  Frames of at most ``params.v_max`` x ``params.u_max`` pixels."""
+        return self._photometric_surface(True, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, cells,
+                                         robust_iterations, sigma_min)
+
+    def _photometric_surface(self, host, I_cur, I_des, Z, K, level, interaction, mu, lambda_, depth_scale, cells, robust_iterations,
+                             sigma_min):
+        stage = self._stage(host)
+        cur = stage.frames(I_cur, None, None)
+        n, hh, ww = (int(x) for x in cur.shape[:3])
+        des = stage.frames(I_des, n, (hh, ww))
+        z = stage.depth(Z, n, (hh, ww))
+        kk = stage.intrinsics(K, n)
+        gy, gx = self._photometric_surface_grid(cells)
+        _, iters, smin = self._photometric_robust_scalars(True, robust_iterations, sigma_min)
+        level, inter, mu, lam, ds = self._photometric_scalars(level, interaction, mu, lambda_, depth_scale)
+        T, Q = gy * gx, (gy + 1) * (gx + 1)
+        v, st, robust, pnodes, sums, pinfo, p = (stage.f64(n, 6), stage.i32(n), stage.f64(n, 4), stage.f64(n, Q, 4),
+                                                 stage.f64(n, T, 120), stage.i32(n, 8), stage.ptr)
+        entry = "vitvs_photometric_surface_velocity" + ("" if host else "_dev")
+        rc = getattr(self.lib, entry)(self.handle, n, p(cur), p(des), hh, ww, p(z), ds, p(kk), level, inter, mu, lam, gy, gx, iters, smin,
+                                      p(v), p(st), p(robust), p(pnodes), p(sums), p(pinfo), *stage.stream)
+        self._check(rc, entry)
+        return v, self._photometric_surface_info(stage.read(st), stage.read(sums), stage.read(pinfo), stage.read(robust),
+                                                 stage.read(pnodes), gy, gx)
+
+    @staticmethod
+    def _photometric_surface_info(status, normal, pinfo, robust, pnodes, gy, gx) -> dict:
+        n, weight = pinfo[:, 0], robust[:, 3]
+        q = pnodes.reshape(-1, gy + 1, gx + 1, 4)
+        c = normal[:, :, 27].sum(axis=1)                                            # sum w e^2 over the cells
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cost = np.where(weight > 0, c / np.where(weight > 0, weight, 1.0), 0.0)
+            rejected = np.where(n > 0, pinfo[:, 6] / np.maximum(n, 1), 0.0)
+        return dict(status=status, normal=normal, n=n.copy(), cost=cost, pooled=pinfo[:, 1:3].copy(), bands=pinfo[:, 3].copy(),
+                    holes=pinfo[:, 4].copy(), pivot_failed=pinfo[:, 5].astype(bool), zero_weight=pinfo[:, 6].copy(),
+                    reweightings=pinfo[:, 7].copy(), sigma=robust[:, 2].copy(), weight=weight.copy(), rejected=rejected,
+                    node_gain=1.0 + q[..., 0], node_bias=q[..., 1].copy(), node_live=q[..., 2] != 0, node_bias_live=q[..., 3] != 0,
+                    live=robust[:, 0].astype(np.int64), dead=robust[:, 1].astype(np.int64))
+
     # ------------------------------------------------------------------ the photometric rig law
     def photometric_rig_velocity(self, I_cur, I_des, Z, K, cVr, live=None, level: int = 2, interaction="desired", mu: float = 0.01,
                                  lambda_: Optional[float] = None, depth_scale: float = 0.0, illumination=True,

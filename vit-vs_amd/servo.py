@@ -320,7 +320,8 @@ class Controller:
         self.photometric_active = False                   # photometric_handover: the photometric law has the robot
         self.last_photometric = None                      # dict(status, cost = sum e^2 / n, n) of its last call; its robust form
                                                           # (photometric_illumination / _robust_iterations): and gain, bias, sigma, rejected;
-                                                          # its tile form (photometric_tiles): and sigma, rejected, dead_tiles, gain_min, gain_max
+                                                          # its tile form (photometric_tiles): and sigma, rejected, dead_tiles, gain_min, gain_max;
+                                                          # its surface form (photometric_surface): and sigma, rejected, dead, gain_min, gain_max
         self._photo_goal_src = None                       # the PIL goal image _photo_goal was converted from
         self._photo_goal = None                           # (host copy, device tensor) of the goal frame at camera resolution, and
         self._photo_goal_depth = None                     # of the goal depth: uploaded once, compared by content like _goal_np
@@ -587,7 +588,13 @@ class Controller:
         lam = p.lambda_ if p.photometric_lambda is None else p.photometric_lambda
         robust = p.photometric_illumination or p.photometric_robust_iterations > 0
         tiles = tuple(p.photometric_tiles) != (1, 1)
-        if tiles:
+        surface = p.photometric_surface is not None
+        if surface:
+            v, info = self.engine.photometric_surface_velocity(cur, goal, None if z is None else z[None], p.intrinsics(),
+                                                               p.photometric_level, p.photometric_interaction, p.photometric_mu, lam,
+                                                               scalar, tuple(p.photometric_surface), p.photometric_robust_iterations,
+                                                               p.photometric_sigma_min)
+        elif tiles:
             v, info = self.engine.photometric_tile_velocity(cur, goal, None if z is None else z[None], p.intrinsics(),
                                                             p.photometric_level, p.photometric_interaction, p.photometric_mu, lam, scalar,
                                                             tuple(p.photometric_tiles), p.photometric_robust_iterations,
@@ -602,7 +609,12 @@ class Controller:
                                                        p.photometric_interaction, p.photometric_mu, lam, scalar)
         st = int(info["status"][0])
         self.last_photometric = dict(status=st, cost=float(info["cost"][0]), n=int(info["n"][0]))
-        if tiles:
+        if surface:
+            gains = info["node_gain"][0][info["node_live"][0]]
+            self.last_photometric.update(sigma=float(info["sigma"][0]), rejected=float(info["rejected"][0]), dead=int(info["dead"][0]),
+                                         gain_min=float(gains.min()) if gains.size else 0.0,
+                                         gain_max=float(gains.max()) if gains.size else 0.0)
+        elif tiles:
             gains = info["tile_gain"][0][info["tile_live"][0]]
             self.last_photometric.update(sigma=float(info["sigma"][0]), rejected=float(info["rejected"][0]),
                                          dead_tiles=int(info["dead_tiles"][0]),
@@ -612,7 +624,7 @@ class Controller:
             self.last_photometric.update({k: float(info[k][0]) for k in ("gain", "bias", "sigma", "rejected")})
         # photometric_handback_rejected: a rejected share above it is a status that is not OK
         share = p.photometric_handback_rejected
-        if st != _lib.STATUS_OK or (share > 0 and (tiles or robust) and self.last_photometric["rejected"] > share):
+        if st != _lib.STATUS_OK or (share > 0 and (surface or tiles or robust) and self.last_photometric["rejected"] > share):
             self.photometric_active = False
             return False
         self._raw_v, self.last_status = v[0].cpu().numpy(), st
@@ -726,6 +738,9 @@ class MultiController:
         if tuple((params or self.engine.params).photometric_tiles) != (1, 1):
             raise ValueError("photometric_tiles is servo.Controller's: the photometric rig law keeps one gain per camera, and tiles "
                              "inside a rig are not built")
+        if (params or self.engine.params).photometric_surface is not None:
+            raise ValueError("photometric_surface is servo.Controller's: the photometric rig law keeps one gain per camera, and a "
+                             "lighting surface inside a rig is not built")
         if (params or self.engine.params).photometric_handover > 0:
             if self.pipe is not None:
                 raise ValueError("photometric_handover needs the Engine backend: the photometric rig law reads all cameras in one handle, "
